@@ -1,7 +1,12 @@
 #!/usr/bin/env python3
 """bench.py -- poses/sec of the batched clip decompressor (BASELINE.json metric), one process per GPU.
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
+
+A plain run sets up, warms up, times the K steps and prints the line; --dump-outputs DIR then also writes the poses of the last timed step
+(a fixed, seeded sample of rows, in the caller's instance order) to DIR/poses.npy. Everything else the benchmark measures or checks (the
+oracle self check, the back-to-back and store-only figures, the other workloads, layouts and footprints, the live counter passes, the CPU
+baseline, the N > 1 checks, gathers and sharded configs) runs only with --full.
 
 A "step" is one launch of aclhip_decompress_tracks_batch (seek + decompress_tracks for every instance of the
 batch). Inputs (registered clips, instance lists) and the pose buffer are resident in HBM before the timed region.
@@ -14,12 +19,12 @@ Workloads (BASELINE.json configs):
     scalar     64k instances of one 256-curve float1f track list (blend shape weights)      
     object_space / additive_object_space   the pose consumers fused into the decode         
 With N > 1 every rank decodes its own shard of instances (weak scaling, no data-path collective); rank 0 prints ONE
-JSON line (< 4 KB: compact_headline) with the whole-job poses/sec, the roofline of the decode kernel, the CPU baseline and one row per
-extra workload; the full record of the run goes to bench_details.json next to this file and to stderr. `python bench.py --gpus N`
-without WORLD_SIZE re-executes itself under torch.distributed.run with N ranks. At N = 1 the default run also measures, in the same
+JSON line (< 4 KB: compact_headline) with the whole-job poses/sec, the roofline of the decode kernel and, with --full, the CPU baseline
+and one row per extra workload; the full record of the run goes to bench_details.json next to this file and to stderr. `python bench.py --gpus N`
+without WORLD_SIZE re-executes itself under torch.distributed.run with N ranks. At N = 1 a --full run also measures, in the same
 process and OUTSIDE the timed region, the other north-star configs ("workloads"), a footprint sweep of the headline batch, the
-compact output layouts, and the CPU baseline (a pinned thread sweep of the reference's own decoder). At N > 1 the pose gather
-(RCCL all-gather, peer-to-peer writes into rank 0) is timed separately from the decode ("gather").
+compact output layouts, and the CPU baseline (a pinned thread sweep of the reference's own decoder). At N > 1 a --full run times the
+pose gather (RCCL all-gather, peer-to-peer writes into rank 0) separately from the decode ("gather").
 """
 import argparse
 import ctypes
@@ -802,6 +807,70 @@ def self_check(job, count=256):
             "against": "oracle/acl_oracle.c (held to the reference's own headers bit for bit by tests/test_oracle_vs_reference.py), rows of the last timed launch"}
 
 
+# ---- --dump-outputs ---------------------------------------------------------------------------------------------------------
+
+DUMP_BYTES = 32 << 20       # poses written per run at most: above it, a fixed seeded sample of instances
+DUMP_SEED = 20240
+
+
+def output_words(job):
+    """float32 words of an output row that the launch writes (the rest of a row is padding to the 64 byte stride)"""
+    if job.is_scalar:
+        return job.max_tracks * job.clips[0].num_components
+    if job.track_requests:
+        return 12
+    return job.max_tracks * job.runtime.LAYOUTS[job.layout][1] // 4
+
+
+def dump_rows(num_instances, row_bytes, budget_bytes=DUMP_BYTES):
+    """The instances --dump-outputs writes: all of them when they fit the budget, else a sorted sample drawn from a fixed seed"""
+    count = max(1, budget_bytes // row_bytes)
+    if num_instances <= count:
+        return np.arange(num_instances, dtype=np.int64)
+    return np.sort(np.random.default_rng(DUMP_SEED).choice(num_instances, size=count, replace=False)).astype(np.int64)
+
+
+def slot_of_instance(job):
+    """Pose row of every instance (indexed by instance) for the orders whose last step wrote poses in an order the device chose: the
+    device orderings (row k = instance out_order[k]) and instance lists (row j = instance order[j]); None where row i is instance i's
+    or the order was made on the host from fixed inputs. The device orders place the instances of one clip by atomics, so the rows
+    differ from run to run while every instance's pose does not."""
+    n = job.num_instances
+    if job.order == "device" and job.d_rows is None:
+        order = job.d_order.cpu().numpy()
+    elif job.order == "device_pipelined":
+        order = job._pipeline["sets"][(job._pipeline["step"] - 1) % 2]["order"].cpu().numpy()
+    elif job.instance_list is not None:
+        order = np.zeros(n, dtype=np.int32)
+        # hipMemcpy of the HIP runtime libaclhip.so is linked against (the one torch loaded first): the list's order lives in library memory
+        copy = job.lib.hipMemcpy
+        copy.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_int]
+        if copy(order.ctypes.data, job.context.instance_list_order(job.instance_list)[0], n * 4, 2) != 0:      # hipMemcpyDeviceToHost
+            raise SystemExit("--dump-outputs: reading the instance list's order failed")
+    else:
+        return None
+    slots = np.empty(n, dtype=np.int64)
+    slots[order.astype(np.int64)] = np.arange(n, dtype=np.int64)
+    return slots
+
+
+def dump_outputs(job, directory, rank, world_size):
+    """--dump-outputs: what a caller of the timed path holds after its last step -- the output rows of the instances of dump_rows, in
+    instance order, float32 -- as DIR/poses.npy (rank r > 0: DIR/poses_rank<r>.npy). Bones a per instance LOD does not keep are zero."""
+    torch = job.torch
+    torch.cuda.synchronize(job.device)
+    words = output_words(job)
+    instances = dump_rows(job.num_instances, words * 4, DUMP_BYTES // world_size)
+    slots = slot_of_instance(job)
+    rows = instances if slots is None else slots[instances]
+    poses = job.d_poses[torch.from_numpy(rows).to(job.device), :words].cpu().numpy()
+    if job.name == "one_clip_lods":
+        kept = np.minimum(job.track_counts[rows], job.max_tracks).astype(np.int64) * (job.runtime.LAYOUTS[job.layout][1] // 4)
+        poses[np.arange(words)[None, :] >= kept[:, None]] = 0.0
+    os.makedirs(directory, exist_ok=True)
+    np.save(os.path.join(directory, "poses.npy" if rank == 0 else f"poses_rank{rank}.npy"), np.ascontiguousarray(poses, dtype=np.float32))
+
+
 # ---- CPU baseline -----------------------------------------------------------------------------------------------------------
 
 def cgroup_cpu_max():
@@ -1122,8 +1191,9 @@ def compact_headline(result):
         line["cpu_baseline"] = _pick(cpu, ["value", "unit", "cores", "threads_at_best", "nproc", "physical_cores", "cgroup_cpu_max", "per_thread_1t", "cold_cache_1t", "kind",
                                            "gpu_over_cpu", "gpu_over_cpu_extrapolated_physical_cores"])
         line["cpu_baseline"]["sample"] = (cpu.get("sample") or "")[:200]
-    check = result.get("self_check")
-    line["self_check"] = check if check is None or "error" in check else _pick(check, ["instances", "max_abs_err", "bit_exact"])
+    if "self_check" in result:        # (--full runs)
+        check = result["self_check"]
+        line["self_check"] = check if check is None or "error" in check else _pick(check, ["instances", "max_abs_err", "bit_exact"])
     if result.get("checks") is not None:
         checks = result["checks"]
         line["checks"] = _pick(checks, ["backend", "ok", "communicator_ranks", "distinct_devices", "kernel_ms_min", "kernel_ms_max"])
@@ -1197,18 +1267,27 @@ def main():
     parser.add_argument("--order", default="random", choices=["random", "by_clip", "locality", "device", "device_pipelined", "list", "attached"],
                         help="instance order: as drawn; bucketed by clip on the host; aclhip_order_instances_for_locality (host, setup); "
                              "aclhip_order_instances_device in front of every launch (part of the step)")
-    parser.add_argument("--no-live-traffic", action="store_true", help="default run: keep roofline.traffic from profiles/traffic.json instead of measuring it with two rocprofv3 --pmc passes")
+    parser.add_argument("--full", action="store_true",
+                        help="after the timed steps also run every other measurement and check: the oracle self check, back-to-back and store-only "
+                             "figures, the other workloads, layouts and footprints, live counter passes, the CPU baseline; at N > 1 the checks, gathers and sharded configs")
+    parser.add_argument("--dump-outputs", default=None, metavar="DIR",
+                        help="after the timed steps write the poses of the last step (a fixed, seeded sample of at most 32 MiB) to DIR/poses.npy, float32")
+    parser.add_argument("--no-live-traffic", action="store_true", help="--full run: keep roofline.traffic from profiles/traffic.json instead of measuring it with two rocprofv3 --pmc passes")
     parser.add_argument("--keep-rows", action="store_true", help="with --order locality: store every pose in its instance's ORIGINAL row")
     parser.add_argument("--layout", default="qvv48", choices=["qvv48", "qvv40", "qv32"], help="output layout (aclhip_output_desc)")
     parser.add_argument("--fast", action="store_true", help="ACLHIP_DECODE_FAST: the opt in tolerance mode (rotations within 2e-6 of the bit exact kernels')")
-    parser.add_argument("--no-cpu-baseline", action="store_true", help="skip the cpu_baseline leg")
-    parser.add_argument("--no-extras", action="store_true", help="only the headline workload: no other workloads, footprint sweep, layouts")
-    parser.add_argument("--gather", default="both", choices=["none", "rccl", "p2p", "both"], help="N > 1: time the pose gather after the decode (reported separately)")
+    parser.add_argument("--no-cpu-baseline", action="store_true", help="--full run: skip the cpu_baseline leg")
+    parser.add_argument("--no-extras", action="store_true", help="--full run: only the headline workload: no other workloads, footprint sweep, layouts")
+    parser.add_argument("--gather", default="both", choices=["none", "rccl", "p2p", "both"], help="--full run, N > 1: time the pose gather after the decode (reported separately)")
     parser.add_argument("--traffic-pass", default=None, metavar="MANIFEST", help="internal (live_traffic): a few launches of every workload of the default run under rocprofv3 --pmc")
     # kept for the scripts of round 1
     parser.add_argument("--sort-by-clip", action="store_true", help="same as --order by_clip")
     parser.add_argument("--order-for-locality", action="store_true", help="same as --order locality")
     args = parser.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        parser.error("--steps must be at least 1 and --warmup at least 0")
+    if not args.full:
+        args.gather = "none"
     if args.sort_by_clip:
         args.order = "by_clip"
     if args.order_for_locality:
@@ -1287,9 +1366,13 @@ def main():
         dist.all_reduce(elapsed_tensor, op=dist.ReduceOp.MAX)
         elapsed, elapsed_behind_barrier = (float(v) for v in elapsed_tensor.tolist())
 
-    # the rows the LAST TIMED launch wrote, against the oracle -- before anything else touches the pose buffer, outside every timed region
+    # what the LAST TIMED launch wrote, as a caller would read it -- before anything else touches the pose buffer
+    if args.dump_outputs is not None:
+        dump_outputs(job, args.dump_outputs, rank, world_size)
+
+    # --full: the rows the LAST TIMED launch wrote, against the oracle -- before anything else touches the pose buffer, outside every timed region
     checked = None
-    if rank == 0 and not profiling:
+    if rank == 0 and args.full and not profiling:
         try:
             checked = self_check(job)
         except Exception as error:      # noqa: BLE001 -- reported in the line, the timing stands on its own
@@ -1297,18 +1380,21 @@ def main():
 
     # Roofline of the decode kernel: device time per launch from the HIP events of the timed region
     kernel_ms = float(start_mark.elapsed_time(stop_mark)) / args.steps
-    checks = distributed_checks(torch, dist, rank, world_size, device_index, backend, kernel_ms) if distributed else None
-    if not profiling:
-        job.prewarm(0.03)       # (the self check read poses back: the device idled for a moment)
-    kernel_ms_back_to_back = None if profiling else job.kernel_ms(max(10, min(args.steps, 100)))
+    checks = distributed_checks(torch, dist, rank, world_size, device_index, backend, kernel_ms) if distributed and args.full else None
     algorithmic_bytes = job.algorithmic_bytes()
     achieved_gbps = algorithmic_bytes / (kernel_ms * 1e-3) / 1e9
-    fill_gbps = job.context.measure_write_bandwidth(job.d_poses.data_ptr(), job.num_instances * job.pose_stride, repeats=1 if profiling else 20, stream=job.stream.cuda_stream)
+    kernel_ms_back_to_back = fill_gbps = None
     # the ceiling of THIS batch's write stream on THIS device: the pose kernels' own store pattern, nothing decoded, best occupancy
     achievable_gbps = achievable_waves = None
-    if not job.is_scalar and not job.track_requests and job.layout == "qvv48":
-        achievable_gbps, achievable_waves = job.context.measure_pose_store_bandwidth(job.d_poses.data_ptr(), job.pose_stride, job.num_instances, job.max_tracks,
-                                                                                     repeats=1 if profiling else 20, stream=job.stream.cuda_stream)
+    if args.full:
+        # (launches of their own after the timed region)
+        if not profiling:
+            job.prewarm(0.03)       # (the self check read poses back: the device idled for a moment)
+        kernel_ms_back_to_back = None if profiling else job.kernel_ms(max(10, min(args.steps, 100)))
+        fill_gbps = job.context.measure_write_bandwidth(job.d_poses.data_ptr(), job.num_instances * job.pose_stride, repeats=1 if profiling else 20, stream=job.stream.cuda_stream)
+        if not job.is_scalar and not job.track_requests and job.layout == "qvv48":
+            achievable_gbps, achievable_waves = job.context.measure_pose_store_bandwidth(job.d_poses.data_ptr(), job.pose_stride, job.num_instances, job.max_tracks,
+                                                                                         repeats=1 if profiling else 20, stream=job.stream.cuda_stream)
 
     kernel_name = job.kernel_name()
     result = None
@@ -1357,18 +1443,20 @@ def main():
                 "traffic": measured_traffic(traffic_key_of(args.workload, args.order, args.layout, args.keep_rows), kernel_name),
                 "kernel": kernel_name,
                 "kernel_ms": kernel_ms,
-                "kernel_ms_back_to_back": kernel_ms_back_to_back,
                 "algorithmic_bytes_per_launch": int(algorithmic_bytes),
-                "plain_store_stream_gbps": fill_gbps,      # a plain 16 B per lane store sweep over the same pose buffer, for scale (not a ceiling: DESIGN.md 6)
-                # the batch's own write stream alone (one wave per pose window, the kernels' 1 KiB streaming stores, nothing decoded): the best
-                # of thirteen store-only shapes (four occupancies x three pacings, the runtime's fill). A second denominator next to the
-                # specification's 8 TB/s, NOT a bound: a decode whose stores are paced by its own loads can come out above it
-                "best_store_only_gbps": achievable_gbps,
-                "best_store_only_waves_per_cu": achievable_waves,
-                "frac_of_best_store_only": None if not achievable_gbps else achieved_gbps / achievable_gbps,
             },
         }
-    if rank == 0:
+    if rank == 0 and args.full:
+        result["roofline"].update({
+            "kernel_ms_back_to_back": kernel_ms_back_to_back,
+            "plain_store_stream_gbps": fill_gbps,      # a plain 16 B per lane store sweep over the same pose buffer, for scale (not a ceiling: DESIGN.md 6)
+            # the batch's own write stream alone (one wave per pose window, the kernels' 1 KiB streaming stores, nothing decoded): the best
+            # of thirteen store-only shapes (four occupancies x three pacings, the runtime's fill). A second denominator next to the
+            # specification's 8 TB/s, NOT a bound: a decode whose stores are paced by its own loads can come out above it
+            "best_store_only_gbps": achievable_gbps,
+            "best_store_only_waves_per_cu": achievable_waves,
+            "frac_of_best_store_only": None if not achievable_gbps else achieved_gbps / achievable_gbps,
+        })
         result["self_check"] = checked
     if rank == 0 and checks is not None:
         result["checks"] = checks
@@ -1400,7 +1488,7 @@ def main():
     headline = (job.clips, job.clip_indices, job.times, job.pose_stride // 4 if job.is_scalar else job.max_tracks, job.is_scalar, job.database is not None, job.consumers is not None)
     job.close()
 
-    if distributed and not args.no_extras and not profiling and args.workload == "one_clip":
+    if distributed and args.full and not args.no_extras and not profiling and args.workload == "one_clip":
         # BASELINE.json's 8-GPU configs on this many GPUs: the 300-bone rig (65 536 instances per GPU, 944 MB shards: the gathers that
         # matter) and the database-bound clips (32 768 per GPU, tiers streamed in on all ranks together). Still under the watchdog.
         sharded = []
@@ -1416,7 +1504,7 @@ def main():
     if distributed and args.gather != "none":
         finished.set()
 
-    extras = world_size == 1 and not args.no_extras and not profiling and args.workload == "one_clip" and args.order == "random" and args.layout == "qvv48" and args.instances == INSTANCES_PER_GPU and not args.fast
+    extras = world_size == 1 and args.full and not args.no_extras and not profiling and args.workload == "one_clip" and args.order == "random" and args.layout == "qvv48" and args.instances == INSTANCES_PER_GPU and not args.fast
     if rank == 0 and extras:
         # the other north-star configs, measured in this process outside the timed region (about 0.2 s of launches each)
         specs = default_run_specs()
@@ -1445,7 +1533,7 @@ def main():
             for entry in (measure_job("one_clip", rank, device_index, num_instances=n, repeats=200) for n in (32768, 65536, 131072))]
 
     if rank == 0:
-        if world_size == 1 and not args.no_cpu_baseline:
+        if world_size == 1 and args.full and not args.no_cpu_baseline:
             clips, clip_indices, times, row_units, is_scalar, has_database, has_consumers = headline
             result["cpu_baseline"] = cpu_baseline(clips, clip_indices, times, row_units, is_scalar)
             if has_database:

@@ -120,3 +120,24 @@ def test_headline_drops_rows_rather_than_cross_the_limit():
         full["workloads"][index] = dict(entry, workload=f"{entry['workload']} #{index}")
     line = bench.compact_headline(full)
     assert len(json.dumps(line)) < 4096 and line["workloads_dropped_for_size"] > 0 and "roofline" in line and "cpu_baseline" in line
+
+
+def test_dump_rows_are_a_fixed_sample_within_the_budget():
+    # the headline batch's 314 MB of poses: the same sorted, distinct instances every time, at most DUMP_BYTES of them
+    rows = bench.dump_rows(bench.INSTANCES_PER_GPU, 100 * 48)
+    assert np.array_equal(rows, bench.dump_rows(bench.INSTANCES_PER_GPU, 100 * 48))
+    assert rows.size * 100 * 48 <= bench.DUMP_BYTES < (rows.size + 1) * 100 * 48
+    assert np.all(np.diff(rows) > 0) and rows[0] >= 0 and rows[-1] < bench.INSTANCES_PER_GPU
+    # a batch that fits is written whole; a smaller budget (ranks of an N > 1 run share one) takes fewer rows
+    assert np.array_equal(bench.dump_rows(4096, 100 * 48), np.arange(4096))
+    assert bench.dump_rows(bench.INSTANCES_PER_GPU, 100 * 48, bench.DUMP_BYTES // 8).size == rows.size // 8
+
+
+def test_command_line_has_the_plain_and_full_runs():
+    """--full and --dump-outputs exist; --steps is the number of timed steps and must be one at least (parsed before any GPU is needed)"""
+    import subprocess
+    import sys
+    usage = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--help"], stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=120)
+    assert usage.returncode == 0 and "--full" in usage.stdout and "--dump-outputs DIR" in usage.stdout
+    refused = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "0"], stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=120)
+    assert refused.returncode == 2 and "--steps" in refused.stderr

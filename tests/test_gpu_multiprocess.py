@@ -100,7 +100,7 @@ def test_bench_dry_run_of_the_multi_gpu_control_flow(world_size, workload, insta
     GPU (ACLHIP_BENCH_BACKEND=gloo): the line must carry the whole-job rate and both gathers, timed separately from the decode."""
     env = dict(os.environ, ACLHIP_BENCH_BACKEND="gloo", HSA_ENABLE_IPC_MODE_LEGACY="0", ACLHIP_BENCH_SHARDED_INSTANCES="1024")
     command = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", f"--nproc-per-node={world_size}", "--master-addr", "127.0.0.1", "--master-port", str(_free_port()),
-               os.path.join(ROOT, "bench.py"), "--gpus", str(world_size), "--steps", "20", "--warmup", "5", "--workload", workload, "--instances", str(instances), "--gather", "both"]
+               os.path.join(ROOT, "bench.py"), "--gpus", str(world_size), "--steps", "20", "--warmup", "5", "--workload", workload, "--instances", str(instances), "--gather", "both", "--full"]
     completed, headline, result = _run_bench(command, env, tmp_path, 600)
     assert completed.returncode == 0, completed.stderr[-3000:]
     assert headline["gather"]["p2p_to_rank0_ms"] > 0 and headline["checks"]["communicator_ranks"] == world_size
@@ -117,7 +117,7 @@ def test_bench_launches_itself_under_torchrun(tmp_path):
     """`python bench.py --gpus 2` without WORLD_SIZE (how the driver launches its 1-GPU run) becomes a 2-rank torch.distributed.run"""
     env = {key: value for key, value in os.environ.items() if key not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
     env.update(ACLHIP_BENCH_BACKEND="gloo", HSA_ENABLE_IPC_MODE_LEGACY="0")
-    command = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "20", "--warmup", "5", "--instances", "4096", "--no-extras", "--gather", "none"]
+    command = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "20", "--warmup", "5", "--instances", "4096", "--no-extras", "--gather", "none", "--full"]
     completed, headline, result = _run_bench(command, env, tmp_path, 600)
     assert completed.returncode == 0, completed.stderr[-3000:]
     assert headline["n_gpus"] == 2 and headline["checks"]["communicator_ranks"] == 2 and headline["self_check"]["bit_exact"] is True
@@ -130,7 +130,7 @@ def test_bench_at_8_ranks_covers_the_8_gpu_configs(tmp_path):
     world_size = 8
     env = dict(os.environ, ACLHIP_BENCH_BACKEND="gloo", HSA_ENABLE_IPC_MODE_LEGACY="0", ACLHIP_BENCH_SHARDED_INSTANCES="512")
     command = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", f"--nproc-per-node={world_size}", "--master-addr", "127.0.0.1", "--master-port", str(_free_port()),
-               os.path.join(ROOT, "bench.py"), "--gpus", str(world_size), "--steps", "20", "--warmup", "5", "--instances", "2048"]
+               os.path.join(ROOT, "bench.py"), "--gpus", str(world_size), "--steps", "20", "--warmup", "5", "--instances", "2048", "--full"]
     completed, headline, result = _run_bench(command, env, tmp_path, 900)
     assert completed.returncode == 0, completed.stderr[-3000:]
     assert set(headline["workloads"]) == {"cinematic", "database"} and all(row[0] > 0 for row in headline["workloads"].values()), headline["workloads"]
@@ -165,7 +165,7 @@ def test_a_gather_that_does_not_come_back_still_leaves_the_decode_line(tmp_path)
     world_size = 2
     env = dict(os.environ, ACLHIP_BENCH_BACKEND="gloo", HSA_ENABLE_IPC_MODE_LEGACY="0", ACLHIP_BENCH_GATHER_TIMEOUT="0.0001")
     command = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", f"--nproc-per-node={world_size}", "--master-addr", "127.0.0.1", "--master-port", str(_free_port()),
-               os.path.join(ROOT, "bench.py"), "--gpus", str(world_size), "--steps", "20", "--warmup", "5", "--instances", "8192", "--no-extras", "--gather", "both"]
+               os.path.join(ROOT, "bench.py"), "--gpus", str(world_size), "--steps", "20", "--warmup", "5", "--instances", "8192", "--no-extras", "--gather", "both", "--full"]
     completed, headline, result = _run_bench(command, env, tmp_path, 600)
     assert headline["gather"]["status"] == "timed out" and headline["value"] > 0 and headline["roofline"]["kernel_ms"] > 0
     assert result["gather"]["status"] == "timed out"

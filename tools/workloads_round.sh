@@ -6,10 +6,10 @@ cd "$GRAFT_REPO_ROOT"; mkdir -p gpurun_out
 out=gpurun_out/${tag}_workloads_bench.jsonl
 : > $out
 for w in one_clip 256_clips cinematic database scalar object_space additive_object_space; do
-  timeout 240 python bench.py --workload $w 2> /dev/null | tail -1 >> $out
+  timeout 240 python bench.py --workload $w --full 2> /dev/null | tail -1 >> $out
 done
-timeout 120 python bench.py --workload 256_clips --sort-by-clip --no-cpu-baseline 2> /dev/null | tail -1 >> $out
-ACLHIP_FORCE_GENERIC_KERNEL=1 timeout 120 python bench.py --no-cpu-baseline 2> /dev/null | tail -1 >> $out
+timeout 120 python bench.py --workload 256_clips --sort-by-clip --full --no-cpu-baseline 2> /dev/null | tail -1 >> $out
+ACLHIP_FORCE_GENERIC_KERNEL=1 timeout 120 python bench.py --full --no-cpu-baseline 2> /dev/null | tail -1 >> $out
 python -c "
 import json
 for line in open('$out'):
