@@ -39,6 +39,10 @@ CASES = {
     "medium_tier_only": (
         [(80, 22, 120), (81, 12, 33)], dict(medium_proportion=0.5, low_proportion=0.0, max_chunk_size=4096),
         [(1, 1, 1), (2, ALL, 1), (1, ALL, 1), (1, 1, 0)]),
+    # a clip of two pose windows (more than 104 bones): its keys come out of database chunks through the wide key reads
+    "two_window_clip_130_bones": (
+        [(95, 130, 40), (96, 20, 60)], dict(medium_proportion=0.3, low_proportion=0.4, max_chunk_size=4096),
+        [(2, ALL, 1), (1, ALL, 1), (2, ALL, 0)]),
 }
 POLICIES = [0, 3]     # none, nearest
 NUM_TIMES = 8

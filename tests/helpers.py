@@ -78,6 +78,28 @@ def bit_equal(a, b):
     return np.array_equal(np.ascontiguousarray(a[..., XYZ_LANES]).view(np.uint32), np.ascontiguousarray(b[..., XYZ_LANES]).view(np.uint32))
 
 
+# ACLHIP_DECODE_FAST's bound: rotation components within 2e-6 of the exact decode, translations and scales bit identical
+FAST_ROTATION_TOLERANCE = 2.0e-6
+FAST_VECTOR_LANES = [4, 5, 6, 8, 9, 10]
+
+
+def assert_within_tolerance(fast, expected, what):
+    """a fast decode against the exact one (or the oracle): returns the worst rotation difference"""
+    worst = float(np.abs(fast[..., 0:4] - expected[..., 0:4]).max()) if fast.size else 0.0
+    assert worst <= FAST_ROTATION_TOLERANCE, f"{what}: rotations differ by {worst}"
+    assert np.array_equal(np.ascontiguousarray(fast[..., FAST_VECTOR_LANES]).view(np.uint32), np.ascontiguousarray(expected[..., FAST_VECTOR_LANES]).view(np.uint32)), f"{what}: translations / scales moved"
+    return worst
+
+
+def per_instance_looping_oracle(decode, policies):
+    """decode(policy) -> values for every instance under that policy; picks every instance's own"""
+    by_policy = [decode(policy) for policy in (ob.LOOP_CLAMP, ob.LOOP_WRAP, ob.LOOP_AS_COMPRESSED)]
+    out = by_policy[0].copy()
+    for policy in (1, 2):
+        out[policies == policy] = by_policy[policy][policies == policy]
+    return out
+
+
 # ---- compressed_database fixtures (tests/golden/database/*.npz, see make_golden_database.py) ----
 DATABASE_GOLDEN_DIR = os.path.join(GOLDEN_DIR, "database")
 

@@ -14,16 +14,6 @@ import helpers
 
 pytestmark = pytest.mark.gpu
 
-ROTATION_TOLERANCE = 2.0e-6
-VECTOR_LANES = [4, 5, 6, 8, 9, 10]
-
-
-def _assert_within_tolerance(fast, expected, what):
-    worst = float(np.abs(fast[..., 0:4] - expected[..., 0:4]).max()) if fast.size else 0.0
-    assert worst <= ROTATION_TOLERANCE, f"{what}: rotations differ by {worst}"
-    assert np.array_equal(np.ascontiguousarray(fast[..., VECTOR_LANES]).view(np.uint32), np.ascontiguousarray(expected[..., VECTOR_LANES]).view(np.uint32)), f"{what}: translations / scales moved"
-    return worst
-
 
 @pytest.mark.parametrize("workload,kernel", [("one_clip", "decompress_tracks_fast_kernel"), ("cinematic", "decompress_tracks_in_turn_fast_kernel")])
 def test_every_instance_of_the_baseline_batches(workload, kernel):
@@ -49,8 +39,8 @@ def test_every_instance_of_the_baseline_batches(workload, kernel):
         expected = ob.oracle_decompress_tracks_batch([c.blob for c in clips], clip_indices[rows], times[rows], bones)
         assert helpers.bit_equal(exact[rows], expected)
         # ... and the fast ones within the tolerance of them on all 65 536 instances, and of the oracle itself on the sample
-        worst = _assert_within_tolerance(fast, exact, workload)
-        _assert_within_tolerance(fast[rows], expected, workload)
+        worst = helpers.assert_within_tolerance(fast, exact, workload)
+        helpers.assert_within_tolerance(fast[rows], expected, workload)
         assert worst > 0.0      # (the flag does select other arithmetic)
         assert context.rejected_instance_count() == 0
 
@@ -66,13 +56,13 @@ def test_corpus_and_single_track_requests():
             clips = np.full(times.size, handle, dtype=np.uint32)
             fast = context.decompress_tracks(clips, times, params=fast_params)
             exact = context.decompress_tracks(clips, times)
-            _assert_within_tolerance(fast, exact, clip["name"])
+            helpers.assert_within_tolerance(fast, exact, clip["name"])
             # single track requests: the fast track kernel against the exact whole pose
             bones = clip["spec"]["bones"]
             instance = np.repeat(np.arange(times.size), bones)
             track = np.tile(np.arange(bones, dtype=np.uint32), times.size)
             single = context.decompress_track(clips[instance], times[instance], track, params=runtime.default_params(flags=runtime.DECODE_FAST))
-            _assert_within_tolerance(single, exact[instance, track], clip["name"] + " (decompress_track)")
+            helpers.assert_within_tolerance(single, exact[instance, track], clip["name"] + " (decompress_track)")
             context.unregister_clip(handle)
 
 

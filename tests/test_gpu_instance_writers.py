@@ -168,15 +168,6 @@ def test_masks_without_a_table_are_refused(context):
     context.unregister_clip(handle)
 
 
-def _per_instance_looping_oracle(decode, policies):
-    """decode(policy) -> values for every instance under that policy; picks every instance's own"""
-    by_policy = [decode(policy) for policy in (ob.LOOP_CLAMP, ob.LOOP_WRAP, ob.LOOP_AS_COMPRESSED)]
-    out = by_policy[0].copy()
-    for policy in (1, 2):
-        out[policies == policy] = by_policy[policy][policies == policy]
-    return out
-
-
 @pytest.mark.parametrize("name", ["cmu_100", "stripped_wrap_scale", "cinematic_300"])
 def test_every_instance_has_its_own_looping_policy(context, name):
     """poses, single tracks and object space poses; sample times at and beyond the end of the clip, where the policies differ"""
@@ -191,7 +182,7 @@ def test_every_instance_has_its_own_looping_policy(context, name):
     tracks = clip.num_tracks
     zeros = np.zeros(n, dtype=np.uint32)
 
-    expected = _per_instance_looping_oracle(lambda policy: ob.oracle_decompress_tracks_batch([clip.blob], zeros, times, tracks, options=ob.default_options(looping_policy=policy)), policies)
+    expected = helpers.per_instance_looping_oracle(lambda policy: ob.oracle_decompress_tracks_batch([clip.blob], zeros, times, tracks, options=ob.default_options(looping_policy=policy)), policies)
     d_policies = torch.from_numpy(policies).cuda()
     params = runtime.default_params(looping_policy=runtime.LOOP_CLAMP)
     params.instance_looping_policies = d_policies.data_ptr()
@@ -239,7 +230,7 @@ def test_looping_policies_per_instance_in_the_pose_consumers_and_scalar_lists():
         times = rng.uniform(clip.duration * 0.7, wrap_duration * 1.05, size=n).astype(np.float32)
         policies = rng.integers(0, 3, size=n).astype(np.uint8)
         zeros = np.zeros(n, dtype=np.uint32)
-        expected = _per_instance_looping_oracle(lambda policy: ob.oracle_decompress_poses_batch([clip.blob], zeros, times, clip.num_tracks, parent_indices=parents,
+        expected = helpers.per_instance_looping_oracle(lambda policy: ob.oracle_decompress_poses_batch([clip.blob], zeros, times, clip.num_tracks, parent_indices=parents,
                                                                                                 options=ob.default_options(looping_policy=policy)), policies)
         d_policies = torch.from_numpy(policies).cuda()
         params = runtime.default_params()
@@ -260,7 +251,7 @@ def test_looping_policies_per_instance_in_the_pose_consumers_and_scalar_lists():
             curve_times = rng.uniform(curves.duration * 0.7, curves.duration * 1.2, size=count).astype(np.float32)
             curve_policies = rng.integers(0, 3, size=count).astype(np.uint8)
             zeros = np.zeros(count, dtype=np.uint32)
-            expected = _per_instance_looping_oracle(lambda policy: ob.oracle_scalar_decompress_tracks_batch([curves.blob], zeros, curve_times, curves.num_tracks,
+            expected = helpers.per_instance_looping_oracle(lambda policy: ob.oracle_scalar_decompress_tracks_batch([curves.blob], zeros, curve_times, curves.num_tracks,
                                                                                                               options=ob.default_options(looping_policy=policy)), curve_policies)
             d_curve_policies = torch.from_numpy(curve_policies).cuda()
             params = runtime.default_params()
