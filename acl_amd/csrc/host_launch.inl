@@ -352,6 +352,25 @@ extern "C" aclhip_status aclhip_order_instances_for_pose_windows(uint32_t window
 
 // Single track requests (decompress_track_kernel): workgroup b takes requests k_block_size b .. k_block_size b + k_block_size - 1 and runs on
 // XCD b % 8. The requests bucketed by clip, XCD x serving one contiguous range of that sequence through the workgroups that run on it.
+namespace
+{
+	// how many request slots of the launch run on each XCD, and where each XCD's range of the bucketed sequence starts
+	track_order_layout make_track_order_layout(uint32_t num_requests)
+	{
+		track_order_layout layout;
+		const uint32_t whole_blocks = num_requests / k_block_size, tail = num_requests % k_block_size;
+		layout.range_begin[0] = 0;
+		for (uint32_t x = 0; x < k_num_xcds; ++x)
+		{
+			uint32_t slots = (whole_blocks / k_num_xcds + (x < whole_blocks % k_num_xcds ? 1 : 0)) * k_block_size;
+			if (tail != 0 && whole_blocks % k_num_xcds == x)
+				slots += tail;
+			layout.range_begin[x + 1] = layout.range_begin[x] + slots;
+		}
+		return layout;
+	}
+}
+
 extern "C" aclhip_status aclhip_order_track_requests_for_locality(const aclhip_clip* clips, uint32_t num_requests, uint32_t* out_order)
 {
 	if ((clips == nullptr || out_order == nullptr) && num_requests != 0)
@@ -382,23 +401,10 @@ extern "C" aclhip_status aclhip_order_track_requests_for_locality(const aclhip_c
 			std::stable_sort(sorted.begin(), sorted.end(), [&](uint32_t a, uint32_t b) { return clips[a] < clips[b]; });
 		}
 
-		// how many request slots of the launch run on each XCD, and where each XCD's range of the sorted sequence starts
-		const uint64_t whole_blocks = num_requests / k_block_size, tail = num_requests % k_block_size;
-		uint64_t cursor[k_num_xcds + 1] = {};
-		for (uint32_t x = 0; x < k_num_xcds; ++x)
-		{
-			uint64_t slots = (whole_blocks / k_num_xcds + (x < whole_blocks % k_num_xcds ? 1 : 0)) * k_block_size;
-			if (tail != 0 && whole_blocks % k_num_xcds == x)
-				slots += tail;
-			cursor[x + 1] = cursor[x] + slots;
-		}
-		for (uint64_t block = 0; block * k_block_size < num_requests; ++block)
-		{
-			const uint32_t xcd = uint32_t(block % k_num_xcds);
-			const uint64_t first = block * k_block_size, count = std::min<uint64_t>(k_block_size, num_requests - first);
-			for (uint64_t k = 0; k < count; ++k)
-				out_order[first + k] = sorted[cursor[xcd]++];
-		}
+		// position p of the sorted sequence -> its slot in the launch (the device ordering maps its positions the same way)
+		const track_order_layout layout = make_track_order_layout(num_requests);
+		for (uint32_t position = 0; position < num_requests; ++position)
+			out_order[track_order_slot_of(layout, position)] = sorted[position];
 		return ACLHIP_OK;
 	});
 }
@@ -442,6 +448,88 @@ extern "C" aclhip_status aclhip_pose_windows_of_launch(aclhip_context* context, 
 
 namespace
 {
+// The ordering scratch of `stream`, shared by aclhip_order_instances_device and aclhip_order_track_requests_device (the caller holds the
+// context's lock). A kernel of the one launch form gave up at a barrier since the last call on this stream (its workgroups did not all
+// become resident within seconds: order_grid_barrier), or a three launch form's scatter found its counters written by another launch:
+// the order it was to write is not there. Said loudly, once, by whichever ordering comes next on the stream; the barrier words are reset
+// and this stream orders instances with the three launch form -- whose workgroups never wait for one another -- from now on.
+aclhip_status order_scratch_of(aclhip_context* context, hipStream_t stream, aclhip_context::order_scratch*& out_scratch)
+{
+	aclhip_context::order_scratch* scratch = nullptr;
+	for (aclhip_context::order_scratch& known : context->order_scratches)
+		if (known.stream == stream)
+			scratch = &known;
+	if (scratch == nullptr)
+	{
+		context->order_scratches.emplace_back();
+		scratch = &context->order_scratches.back();
+		scratch->stream = stream;
+	}
+	out_scratch = scratch;
+	if (scratch->host_failed != nullptr && __atomic_load_n(scratch->host_failed, __ATOMIC_RELAXED) != 0)
+	{
+		__atomic_store_n(scratch->host_failed, 0u, __ATOMIC_RELAXED);
+		scratch->one_launch_form_disabled = true;
+		if (scratch->barrier != nullptr)
+			(void)hipMemsetAsync(scratch->barrier, 0, sizeof(order_control), stream);
+		return fail(context, ACLHIP_ERROR_DEVICE, "an earlier ordering (aclhip_order_instances_device / aclhip_order_track_requests_device) on this stream did not complete "
+			"(its workgroups could not all become resident within seconds, or -- three launch form -- another ordering wrote this stream's counters at the same time: "
+			"a captured ordering replayed next to one of the stream whose scratch it holds): the order it was to write is invalid. This stream orders with three "
+			"launches from now on; order again");
+	}
+	return ACLHIP_OK;
+}
+
+// the matrix | the bins' totals of the one launch form at their LARGEST: 2^19 matrix entries + 8 192 totals, 2 MiB. A stream's scratch
+// takes this size at its first ordering of either kind, so that it does not move while the registry stays within 8 192 clips.
+constexpr size_t k_order_grid_scratch_words = size_t(k_order_grid_entries) + k_order_direct_bins;
+
+// at least `words` words of scratch; a larger allocation replaces the old one (retired: a launch in flight may still use it)
+aclhip_status reserve_order_scratch(aclhip_context* context, aclhip_context::order_scratch* scratch, size_t words)
+{
+	if (scratch->capacity >= words)
+		return ACLHIP_OK;
+	if (scratch->bins != nullptr)
+	{
+		aclhip_context::retired_item item;
+		item.device_memory = scratch->bins;
+		retire(context, std::move(item));
+		scratch->bins = nullptr;
+		scratch->capacity = 0;
+	}
+	ACLHIP_CHECK_HIP(context, hipMalloc(reinterpret_cast<void**>(&scratch->bins), words * sizeof(uint32_t)));
+	scratch->capacity = words;
+	scratch->zeroed_bins = 0;
+	return ACLHIP_OK;
+}
+
+// counters | cursors of the three launch forms (count, order_scan_kernel, scatter), zeroed on the stream once -- every scan leaves the
+// counters at zero -- and the host word through which a scatter reports a corrupted ordering
+aclhip_status three_launch_order_scratch(aclhip_context* context, aclhip_context::order_scratch* scratch, uint32_t num_bins, hipStream_t stream,
+	uint32_t*& out_counters, uint32_t*& out_cursors)
+{
+	const size_t padded_bins = (size_t(num_bins) + 4095) / 4096 * 4096;
+	{
+		const aclhip_status status = reserve_order_scratch(context, scratch, padded_bins * 2);
+		if (status != ACLHIP_OK)
+			return status;
+	}
+	if (scratch->zeroed_bins != padded_bins)
+	{
+		ACLHIP_CHECK_HIP(context, hipMemsetAsync(scratch->bins, 0, (padded_bins * 2) * sizeof(uint32_t), stream));		// once: every call leaves the counters at zero
+		scratch->zeroed_bins = padded_bins;
+	}
+	out_counters = scratch->bins;
+	out_cursors = scratch->bins + padded_bins;
+	// (the three launch form reports a corrupted ordering through the same host word as the one launch form's barrier give-up)
+	if (scratch->host_failed == nullptr)
+	{
+		ACLHIP_CHECK_HIP(context, hipHostMalloc(reinterpret_cast<void**>(&scratch->host_failed), sizeof(uint32_t), hipHostMallocMapped));
+		*scratch->host_failed = 0;
+	}
+	return ACLHIP_OK;
+}
+
 aclhip_status order_instances_on_device(aclhip_context* context, uint32_t windows_per_instance, const aclhip_clip* clips, const float* sample_times, uint32_t num_instances,
 	uint32_t* out_order, aclhip_clip* out_clips, float* out_sample_times, uint32_t* out_positions, void* stream_handle)
 {
@@ -460,49 +548,16 @@ aclhip_status order_instances_on_device(aclhip_context* context, uint32_t window
 	const uint32_t num_bins = uint32_t(context->clips.size()) + 1;		// handles are slots of the registry; the last bin takes everything else
 	note_launch_stream(context, stream);
 	aclhip_context::order_scratch* scratch = nullptr;
-	for (aclhip_context::order_scratch& known : context->order_scratches)
-		if (known.stream == stream)
-			scratch = &known;
-	if (scratch == nullptr)
 	{
-		context->order_scratches.emplace_back();
-		scratch = &context->order_scratches.back();
-		scratch->stream = stream;
+		const aclhip_status status = order_scratch_of(context, stream, scratch);
+		if (status != ACLHIP_OK)
+			return status;
 	}
-	const auto reserve = [&](size_t words) -> aclhip_status
-	{
-		if (scratch->capacity >= words)
-			return ACLHIP_OK;
-		if (scratch->bins != nullptr)
-		{
-			aclhip_context::retired_item item;
-			item.device_memory = scratch->bins;
-			retire(context, std::move(item));
-			scratch->bins = nullptr;
-			scratch->capacity = 0;
-		}
-		ACLHIP_CHECK_HIP(context, hipMalloc(reinterpret_cast<void**>(&scratch->bins), words * sizeof(uint32_t)));
-		scratch->capacity = words;
-		scratch->zeroed_bins = 0;
-		return ACLHIP_OK;
-	};
+	const auto reserve = [&](size_t words) -> aclhip_status { return reserve_order_scratch(context, scratch, words); };
 
 	// ACLHIP_ORDER_LAUNCHES=3 forces the older form (three launches: LDS hash tables + device scope atomics), what clip tables of more
 	// than k_order_direct_bins entries take anyway
 	static const int forced_form = []() { const char* value = path_knob("ACLHIP_ORDER_LAUNCHES"); return value != nullptr ? int(value[0] - '0') : 0; }();
-	// A kernel of the one launch form gave up at a barrier since the last call on this stream (its workgroups did not all become
-	// resident within seconds: order_grid_barrier): the order it was to write is not there. Said loudly, once; the barrier words are
-	// reset and this stream orders with the three launch form -- whose workgroups never wait for one another -- from now on.
-	if (scratch->host_failed != nullptr && __atomic_load_n(scratch->host_failed, __ATOMIC_RELAXED) != 0)
-	{
-		__atomic_store_n(scratch->host_failed, 0u, __ATOMIC_RELAXED);
-		scratch->one_launch_form_disabled = true;
-		if (scratch->barrier != nullptr)
-			(void)hipMemsetAsync(scratch->barrier, 0, sizeof(order_control), stream);
-		return fail(context, ACLHIP_ERROR_DEVICE, "an earlier aclhip_order_instances_device on this stream did not complete (its workgroups could not all become resident "
-			"within seconds, or -- three launch form -- another ordering wrote this stream's counters at the same time: a captured ordering replayed next to one of "
-			"the stream whose scratch it holds): the order it was to write is invalid. This stream orders with three launches from now on; order again");
-	}
 	if (num_bins <= k_order_direct_bins && forced_form != 3 && !scratch->one_launch_form_disabled)
 	{
 		// as many workgroups as keep the matrix small (every workgroup reads all of it), all of them resident at once: never more than
@@ -530,7 +585,6 @@ aclhip_status order_instances_on_device(aclhip_context* context, uint32_t window
 			// the matrix | the bins' totals, at their LARGEST once and for all: 2^19 matrix entries (the loop above) + 8 192 totals, 2 MiB.
 			// The scratch of this form then never moves -- a captured hipGraph that holds its address stays valid whatever is registered
 			// later -- and no call after the first allocates. (Only registries beyond 8 192 clips, the three launch form, can outgrow it.)
-			constexpr size_t k_order_grid_scratch_words = size_t(k_order_grid_entries) + k_order_direct_bins;
 			if ((size_t(num_bins) << log2_blocks) + num_bins > k_order_grid_scratch_words)
 				return fail(context, ACLHIP_ERROR_DEVICE, "internal: the ordering matrix outgrew its scratch (%u bins x %u workgroups)", num_bins, num_blocks);
 			const aclhip_status status = reserve(k_order_grid_scratch_words);
@@ -566,24 +620,12 @@ aclhip_status order_instances_on_device(aclhip_context* context, uint32_t window
 			return ACLHIP_OK;
 		}
 	}
-	const size_t padded_bins = (size_t(num_bins) + 4095) / 4096 * 4096;
+	uint32_t* counters = nullptr;
+	uint32_t* cursors = nullptr;
 	{
-		const aclhip_status status = reserve(padded_bins * 2);
+		const aclhip_status status = three_launch_order_scratch(context, scratch, num_bins, stream, counters, cursors);
 		if (status != ACLHIP_OK)
 			return status;
-	}
-	if (scratch->zeroed_bins != padded_bins)
-	{
-		ACLHIP_CHECK_HIP(context, hipMemsetAsync(scratch->bins, 0, (padded_bins * 2) * sizeof(uint32_t), stream));		// once: every call leaves the counters at zero
-		scratch->zeroed_bins = padded_bins;
-	}
-	uint32_t* counters = scratch->bins;
-	uint32_t* cursors = scratch->bins + padded_bins;
-	// (the three launch form reports a corrupted ordering through the same host word as the one launch form's barrier give-up)
-	if (scratch->host_failed == nullptr)
-	{
-		ACLHIP_CHECK_HIP(context, hipHostMalloc(reinterpret_cast<void**>(&scratch->host_failed), sizeof(uint32_t), hipHostMallocMapped));
-		*scratch->host_failed = 0;
 	}
 
 	const uint32_t num_blocks = (num_instances + k_order_instances_per_block - 1) / k_order_instances_per_block;
@@ -595,30 +637,102 @@ aclhip_status order_instances_on_device(aclhip_context* context, uint32_t window
 }
 }
 
+// Single track requests ordered on the device: the host order's layout (aclhip_order_track_requests_for_locality), the instance
+// ordering's scratch and failure protocol. Three launches, no host synchronization; after the first call on a stream nothing is
+// allocated unless the registry outgrows the scratch.
+extern "C" aclhip_status aclhip_order_track_requests_device(aclhip_context* context, const aclhip_clip* clips, const float* sample_times,
+	const uint32_t* track_indices, uint32_t num_requests, uint32_t* out_order, aclhip_clip* out_clips, float* out_sample_times,
+	uint32_t* out_track_indices, uint32_t* out_positions, void* stream_handle)
+{
+	if (context == nullptr)
+		return ACLHIP_ERROR_INVALID_ARGUMENT;
+	if (num_requests == 0)
+		return ACLHIP_OK;
+	if (clips == nullptr || out_order == nullptr || (out_sample_times != nullptr && sample_times == nullptr) || (out_track_indices != nullptr && track_indices == nullptr))
+		return fail(context, ACLHIP_ERROR_INVALID_ARGUMENT, "null request list or order buffer");
+
+	hipStream_t stream = static_cast<hipStream_t>(stream_handle);
+	const track_order_layout layout = make_track_order_layout(num_requests);
+
+	device_guard guard(context->device);
+	std::lock_guard<std::shared_mutex> lock(context->mutex);		// the scratch of a stream is handed to one call at a time, in stream order
+	const uint32_t num_bins = uint32_t(context->clips.size()) + 1;		// handles are slots of the registry; the last bin takes everything else
+	note_launch_stream(context, stream);
+	aclhip_context::order_scratch* scratch = nullptr;
+	uint32_t* counters = nullptr;
+	uint32_t* cursors = nullptr;
+	{
+		aclhip_status status = order_scratch_of(context, stream, scratch);
+		if (status == ACLHIP_OK)		// (the instance ordering's fixed size: neither kind of ordering moves the other's scratch)
+			status = reserve_order_scratch(context, scratch, k_order_grid_scratch_words);
+		if (status == ACLHIP_OK)
+			status = three_launch_order_scratch(context, scratch, num_bins, stream, counters, cursors);
+		if (status != ACLHIP_OK)
+			return status;
+	}
+
+	// about one workgroup per CU, each taking a share of whole k_order_instances_per_block chunks (track_order_count_kernel)
+	const uint32_t chunks = (num_requests + k_order_instances_per_block - 1) / k_order_instances_per_block;
+	const uint32_t max_blocks = std::max<uint32_t>(context->num_compute_units, 1);
+	const uint32_t share = (chunks + max_blocks - 1) / max_blocks * k_order_instances_per_block;
+	const uint32_t num_blocks = uint32_t((uint64_t(num_requests) + share - 1) / share);
+	hipLaunchKernelGGL(track_order_count_kernel, dim3(num_blocks), dim3(k_order_block_size), 0, stream, clips, num_requests, share, num_bins, counters);
+	hipLaunchKernelGGL(order_scan_kernel, dim3(1), dim3(1024), 0, stream, counters, cursors, num_bins);
+	hipLaunchKernelGGL(track_order_scatter_kernel, dim3(num_blocks), dim3(k_order_block_size), 0, stream, clips, sample_times, track_indices, num_requests, share, num_bins,
+		cursors, layout, out_order, out_clips, out_sample_times, out_track_indices, out_positions, scratch->host_failed);
+	ACLHIP_CHECK_HIP(context, hipGetLastError());
+	return ACLHIP_OK;
+}
+
+namespace
+{
+	// aclhip_decompress_track_batch[_rows]: rows == nullptr puts transform i at row i
+	aclhip_status launch_track_requests(aclhip_context* context, const aclhip_clip* clips, const float* sample_times, const uint32_t* track_indices, const uint32_t* rows,
+		uint32_t num_instances, const aclhip_decompress_params* params, void* transforms, void* stream)
+	{
+		aclhip_status status = check_batch_arguments(context, clips, sample_times, num_instances, transforms, 48);
+		if (status != ACLHIP_OK)
+			return status;
+		if (num_instances == 0)
+			return ACLHIP_OK;
+		if (track_indices == nullptr)
+			return fail(context, ACLHIP_ERROR_INVALID_ARGUMENT, "null track index list");
+
+		decode_params device_params;
+		status = resolve_params(context, params, device_params);
+		if (status != ACLHIP_OK)
+			return status;
+
+		std::shared_lock<std::shared_mutex> lock(context->mutex);		// see launch_tracks
+		device_guard guard(context->device);
+		note_launch_stream(context, static_cast<hipStream_t>(stream));
+		const uint32_t num_blocks = (num_instances + k_block_size - 1) / k_block_size;
+		// (ACLHIP_DECODE_FAST changes nothing here: the variant compiled for it never measured faster than the bit exact kernel, kernels_track.inl)
+		if (rows == nullptr)
+			hipLaunchKernelGGL(decompress_track_kernel, dim3(num_blocks), dim3(k_block_size), 0, static_cast<hipStream_t>(stream),
+				context->d_clips, context->d_clips_capacity, clips, sample_times, track_indices, num_instances, device_params,
+				static_cast<float4*>(transforms), context->d_rejected);
+		else
+			hipLaunchKernelGGL(decompress_track_rows_kernel, dim3(num_blocks), dim3(k_block_size), 0, static_cast<hipStream_t>(stream),
+				context->d_clips, context->d_clips_capacity, clips, sample_times, track_indices, rows, num_instances, device_params,
+				static_cast<float4*>(transforms), context->d_rejected);
+		ACLHIP_CHECK_HIP(context, hipGetLastError());
+		return ACLHIP_OK;
+	}
+}
+
 extern "C" aclhip_status aclhip_decompress_track_batch(aclhip_context* context, const aclhip_clip* clips, const float* sample_times, const uint32_t* track_indices,
 	uint32_t num_instances, const aclhip_decompress_params* params, void* transforms, void* stream)
 {
-	aclhip_status status = check_batch_arguments(context, clips, sample_times, num_instances, transforms, 48);
-	if (status != ACLHIP_OK)
-		return status;
-	if (num_instances == 0)
-		return ACLHIP_OK;
-	if (track_indices == nullptr)
-		return fail(context, ACLHIP_ERROR_INVALID_ARGUMENT, "null track index list");
+	return launch_track_requests(context, clips, sample_times, track_indices, nullptr, num_instances, params, transforms, stream);
+}
 
-	decode_params device_params;
-	status = resolve_params(context, params, device_params);
-	if (status != ACLHIP_OK)
-		return status;
-
-	std::shared_lock<std::shared_mutex> lock(context->mutex);		// see launch_tracks
-	device_guard guard(context->device);
-	note_launch_stream(context, static_cast<hipStream_t>(stream));
-	const uint32_t num_blocks = (num_instances + k_block_size - 1) / k_block_size;
-	// (ACLHIP_DECODE_FAST changes nothing here: the variant compiled for it never measured faster than the bit exact kernel, kernels_track.inl)
-	hipLaunchKernelGGL(decompress_track_kernel, dim3(num_blocks), dim3(k_block_size), 0, static_cast<hipStream_t>(stream),
-		context->d_clips, context->d_clips_capacity, clips, sample_times, track_indices, num_instances, device_params,
-		static_cast<float4*>(transforms), context->d_rejected);
-	ACLHIP_CHECK_HIP(context, hipGetLastError());
-	return ACLHIP_OK;
+extern "C" aclhip_status aclhip_decompress_track_batch_rows(aclhip_context* context, const aclhip_clip* clips, const float* sample_times, const uint32_t* track_indices,
+	const uint32_t* rows, uint32_t num_requests, const aclhip_decompress_params* params, void* transforms, void* stream)
+{
+	if (context == nullptr)
+		return ACLHIP_ERROR_INVALID_ARGUMENT;
+	if (rows == nullptr && num_requests != 0)
+		return fail(context, ACLHIP_ERROR_INVALID_ARGUMENT, "null row list");
+	return launch_track_requests(context, clips, sample_times, track_indices, rows, num_requests, params, transforms, stream);
 }

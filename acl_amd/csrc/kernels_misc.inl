@@ -160,10 +160,15 @@
 		__syncthreads();
 	}
 
+	__host__ __device__ inline uint32_t order_table_home(uint32_t bin)
+	{
+		return ((bin * 2654435761u) >> 16) & (k_order_table_size - 1);
+	}
+
 	// the slot of `bin` in the workgroup's table and the instance's rank among the workgroup's instances of that bin
 	__device__ inline uint32_t order_table_insert(order_table& table, uint32_t bin, uint32_t& rank)
 	{
-		uint32_t slot = ((bin * 2654435761u) >> 16) & (k_order_table_size - 1);
+		uint32_t slot = order_table_home(bin);
 		for (;;)
 		{
 			const uint32_t found = atomicCAS(&table.keys[slot], k_order_empty_key, bin);
@@ -280,6 +285,212 @@
 				out_sample_times[destination] = sample_times[instance];
 			if (out_positions != nullptr)
 				out_positions[instance] = destination;
+		}
+	}
+
+	// ---- the same for single track requests (aclhip_order_track_requests_device; host twin aclhip_order_track_requests_for_locality) ----
+	// Workgroup b of decompress_track_kernel takes requests k_block_size b .. k_block_size b + k_block_size - 1 and runs on XCD b % 8. The
+	// requests are bucketed by clip into one sequence; XCD x serves positions [range_begin[x], range_begin[x + 1]) of it through its own
+	// workgroups in ascending order (the tail workgroup is the last of its XCD). Position -> slot, for the host order and the device scatter.
+	struct track_order_layout
+	{
+		uint32_t range_begin[k_num_xcds + 1];
+	};
+
+	__host__ __device__ inline uint32_t track_order_slot_of(const track_order_layout& layout, uint32_t position)
+	{
+		// (the ranges ascend, some may be empty: the XCD is the last one whose range starts at or before the position)
+		uint32_t xcd = 0, first = 0;
+		for (uint32_t x = 1; x < k_num_xcds; ++x)
+			if (position >= layout.range_begin[x])
+			{
+				xcd = x;
+				first = layout.range_begin[x];
+			}
+		const uint32_t rank = position - first;
+		return ((rank / k_block_size) * k_num_xcds + xcd) * k_block_size + rank % k_block_size;
+	}
+
+	// Request lists run to millions (4 M per frame): at 2 048 requests per workgroup every clip's bin would take 2 048 device scope adds per
+	// pass, serialized on one word (~23 us at ~88 per us). Instead a workgroup takes a SHARE of the list -- about one workgroup per CU, the
+	// host sizes it -- counts it in LDS and flushes once: at most as many device scope adds per bin as there are workgroups.
+	// The LDS counters: registries of up to k_track_order_direct_bins bins count directly, one word per bin (the order table's memory:
+	// every bin has its slot, one LDS add per request and no probing -- the hash table's compare-and-swap + add per request measured
+	// 59 us for the count of 4 M requests over 256 clips). Larger registries use the hash table, which must never be asked to hold more
+	// distinct bins than it has slots (order_table_insert probes forever in a full table: a hang). So the table takes one flush of at
+	// most k_order_instances_per_block requests -- no more distinct bins than requests, load factor <= 0.5 -- and the share is flushed in
+	// such chunks, as the instance kernels do. The kernels decide this from num_bins themselves: no launch can ask otherwise.
+	constexpr uint32_t k_track_order_direct_bins = 2 * k_order_table_size;
+	static_assert(sizeof(order_table) == k_track_order_direct_bins * sizeof(uint32_t), "the direct counters are the table's memory");
+	static_assert(k_order_instances_per_block <= k_order_table_size / 2, "a flush of k_order_instances_per_block requests fits the table");
+	__device__ __forceinline__ uint32_t track_order_requests_per_flush(uint32_t num_bins, uint32_t share)
+	{
+		return num_bins <= k_track_order_direct_bins ? share : k_order_instances_per_block;
+	}
+	constexpr uint32_t k_track_order_loads = 4;		// requests a thread loads before it touches LDS (loads in flight)
+
+	// the slot of a bin the first pass of the flush inserted (by this very request); k_order_table_size when it is not there -- a
+	// request list the caller rewrote while it was being ordered: bounded, never a hang
+	__device__ inline uint32_t order_table_find(const order_table& table, uint32_t bin)
+	{
+		uint32_t slot = order_table_home(bin);
+		for (uint32_t probe = 0; probe < k_order_table_size; ++probe)
+		{
+			if (table.keys[slot] == bin)
+				return slot;
+			slot = (slot + 1) & (k_order_table_size - 1);
+		}
+		return k_order_table_size;
+	}
+
+	// one flush's requests [first, first + in_flush) counted into LDS: the direct counters or the hash table (cleared here first)
+	__device__ __forceinline__ void track_order_count_flush(order_table& table, bool direct, const uint32_t* __restrict__ clip_ids, uint32_t first, uint32_t in_flush, uint32_t num_bins)
+	{
+		uint32_t* direct_counts = reinterpret_cast<uint32_t*>(&table);
+		if (direct)
+		{
+			for (uint32_t bin = threadIdx.x; bin < num_bins; bin += k_order_block_size)
+				direct_counts[bin] = 0;
+			__syncthreads();
+		}
+		else
+			order_table_clear(table);
+		for (uint32_t offset = threadIdx.x; offset < in_flush; offset += k_track_order_loads * k_order_block_size)
+		{
+			uint32_t bin[k_track_order_loads];
+			#pragma unroll
+			for (uint32_t k = 0; k < k_track_order_loads; ++k)
+				if (offset + k * k_order_block_size < in_flush)
+					bin[k] = min(clip_ids[first + offset + k * k_order_block_size], num_bins - 1);
+			#pragma unroll
+			for (uint32_t k = 0; k < k_track_order_loads; ++k)
+				if (offset + k * k_order_block_size < in_flush)
+				{
+					if (direct)
+						atomicAdd(&direct_counts[bin[k]], 1u);
+					else
+					{
+						uint32_t rank;
+						order_table_insert(table, bin[k], rank);
+					}
+				}
+		}
+		__syncthreads();
+	}
+
+	// requests per clip; handles past the registry (the decode rejects them) share the last bin
+	__global__ __launch_bounds__(k_order_block_size) void track_order_count_kernel(const uint32_t* __restrict__ clip_ids, uint32_t num_requests, uint32_t share,
+		uint32_t num_bins, uint32_t* __restrict__ bins)
+	{
+		__shared__ order_table table;
+		const uint32_t* direct_counts = reinterpret_cast<const uint32_t*>(&table);
+		const bool direct = num_bins <= k_track_order_direct_bins;
+		const uint32_t begin = blockIdx.x * share;		// (the host launches ceil(num_requests / share) workgroups)
+		const uint32_t count = min(share, num_requests - begin);
+		const uint32_t per_flush = track_order_requests_per_flush(num_bins, share);
+		for (uint32_t flushed = 0; flushed < count; flushed += per_flush)
+		{
+			track_order_count_flush(table, direct, clip_ids, begin + flushed, min(per_flush, count - flushed), num_bins);
+			if (direct)
+			{
+				for (uint32_t bin = threadIdx.x; bin < num_bins; bin += k_order_block_size)
+					if (direct_counts[bin] != 0)
+						atomicAdd(&bins[bin], direct_counts[bin]);
+			}
+			else
+			{
+				for (uint32_t slot = threadIdx.x; slot < k_order_table_size; slot += k_order_block_size)
+					if (table.keys[slot] != k_order_empty_key)
+						atomicAdd(&bins[table.keys[slot]], table.counts[slot]);
+			}
+			__syncthreads();		// (the next flush clears the counters)
+		}
+	}
+
+	// every request takes the next position of its clip and lands in the slot that position maps to. Per flush: count into LDS, take
+	// the flush's positions of every clip with one device scope add, then hand them out by LDS adds in a second pass
+	__global__ __launch_bounds__(k_order_block_size) void track_order_scatter_kernel(const uint32_t* __restrict__ clip_ids, const float* __restrict__ sample_times,
+		const uint32_t* __restrict__ track_indices, uint32_t num_requests, uint32_t share, uint32_t num_bins, uint32_t* __restrict__ bins, track_order_layout layout,
+		uint32_t* __restrict__ out_order, uint32_t* __restrict__ out_clip_ids, float* __restrict__ out_sample_times, uint32_t* __restrict__ out_track_indices,
+		uint32_t* __restrict__ out_positions, uint32_t* __restrict__ host_failed)
+	{
+		__shared__ order_table table;
+		uint32_t* direct_counts = reinterpret_cast<uint32_t*>(&table);
+		const bool direct = num_bins <= k_track_order_direct_bins;
+		const uint32_t begin = blockIdx.x * share;
+		const uint32_t count = min(share, num_requests - begin);
+		const uint32_t per_flush = track_order_requests_per_flush(num_bins, share);
+		for (uint32_t flushed = 0; flushed < count; flushed += per_flush)
+		{
+			const uint32_t first = begin + flushed, in_flush = min(per_flush, count - flushed);
+			track_order_count_flush(table, direct, clip_ids, first, in_flush, num_bins);
+			// the flush's requests of a clip take consecutive positions: the counter becomes the first of them
+			if (direct)
+			{
+				for (uint32_t bin = threadIdx.x; bin < num_bins; bin += k_order_block_size)
+					if (direct_counts[bin] != 0)
+						direct_counts[bin] = atomicAdd(&bins[bin], direct_counts[bin]);
+			}
+			else
+			{
+				for (uint32_t slot = threadIdx.x; slot < k_order_table_size; slot += k_order_block_size)
+					if (table.keys[slot] != k_order_empty_key)
+						table.counts[slot] = atomicAdd(&bins[table.keys[slot]], table.counts[slot]);
+			}
+			__syncthreads();
+			for (uint32_t offset = threadIdx.x; offset < in_flush; offset += k_track_order_loads * k_order_block_size)
+			{
+				uint32_t clip_id[k_track_order_loads], track_index[k_track_order_loads];
+				float sample_time[k_track_order_loads];
+				#pragma unroll
+				for (uint32_t k = 0; k < k_track_order_loads; ++k)
+					if (offset + k * k_order_block_size < in_flush)
+					{
+						const uint32_t request = first + offset + k * k_order_block_size;
+						clip_id[k] = clip_ids[request];
+						if (out_sample_times != nullptr)
+							sample_time[k] = sample_times[request];
+						if (out_track_indices != nullptr)
+							track_index[k] = track_indices[request];
+					}
+				#pragma unroll
+				for (uint32_t k = 0; k < k_track_order_loads; ++k)
+				{
+					if (offset + k * k_order_block_size >= in_flush)
+						continue;
+					const uint32_t request = first + offset + k * k_order_block_size;
+					const uint32_t bin = min(clip_id[k], num_bins - 1);
+					uint32_t* counter = nullptr;
+					if (direct)
+						counter = &direct_counts[bin];
+					else
+					{
+						const uint32_t slot = order_table_find(table, bin);
+						counter = slot < k_order_table_size ? &table.counts[slot] : nullptr;
+					}
+					const uint32_t position = counter != nullptr ? atomicAdd(counter, 1u) : num_requests;
+					const uint32_t destination = track_order_slot_of(layout, position);
+					// (a position past the list: another launch wrote this stream's counters at the same time -- order_scatter_kernel -- or the
+					// caller rewrote the list while it was being ordered. Nothing is written out of bounds, the next ordering call on the stream
+					// reports it)
+					if (position >= num_requests || destination >= num_requests)
+					{
+						if (host_failed != nullptr)
+							__hip_atomic_store(host_failed, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+						continue;
+					}
+					out_order[destination] = request;
+					if (out_clip_ids != nullptr)
+						out_clip_ids[destination] = clip_id[k];
+					if (out_sample_times != nullptr)
+						out_sample_times[destination] = sample_time[k];
+					if (out_track_indices != nullptr)
+						out_track_indices[destination] = track_index[k];
+					if (out_positions != nullptr)
+						out_positions[request] = destination;
+				}
+			}
+			__syncthreads();		// (the next flush clears the counters)
 		}
 	}
 

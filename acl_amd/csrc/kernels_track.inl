@@ -165,10 +165,11 @@
 		return true;
 	}
 
-	template<uint32_t kFastMath>
+	// kRows: the transform of request i goes to row rows[i] of `transforms` instead of row i (aclhip_decompress_track_batch_rows)
+	template<uint32_t kFastMath, bool kRows = false>
 	__device__ __forceinline__ void decompress_track_requests(const device_clip* __restrict__ clips, uint32_t num_clips,
 		const uint32_t* __restrict__ clip_ids, const float* __restrict__ sample_times, const uint32_t* __restrict__ track_indices, uint32_t num_instances,
-		const decode_params& params, float4* __restrict__ transforms, unsigned long long* __restrict__ rejected_count)
+		const decode_params& params, float4* __restrict__ transforms, unsigned long long* __restrict__ rejected_count, const uint32_t* __restrict__ rows = nullptr)
 	{
 		__shared__ __attribute__((aligned(16))) uint8_t track_lds[k_waves_per_block * k_track_lds_bytes_per_wave];
 
@@ -328,7 +329,7 @@
 
 		// ---- 3. the wave's 64 transforms leave -----------------------------------------------------------------------------------------
 		const bool stores_all = accepted && store[0] && store[1] && store[2];
-		if (__builtin_amdgcn_ballot_w64(stores_all) == ~0ull)
+		if (!kRows && __builtin_amdgcn_ballot_w64(stores_all) == ~0ull)
 		{
 			// three 1 KiB contiguous stores
 			f32x4 staged[3];
@@ -342,13 +343,15 @@
 			return;
 		}
 
-		// a request that is refused, or whose default sub-tracks are skipped, leaves (part of) its transform as the caller had it
+		// a request that is refused, or whose default sub-tracks are skipped, leaves (part of) its transform as the caller had it.
+		// (kRows: every lane stores its own 48 bytes to its own row, a full wave as well)
 		if (accepted)
 		{
+			const size_t row = kRows ? size_t(rows[instance]) : size_t(instance);
 			#pragma unroll
 			for (uint32_t kind = 0; kind < 3; ++kind)
 				if (store[kind])
-					store_streaming(&transforms[size_t(instance) * 3u + kind], image[lane * 3u + kind]);
+					store_streaming(&transforms[row * 3u + kind], image[lane * 3u + kind]);
 		}
 	}
 
@@ -357,6 +360,14 @@
 		decode_params params, float4* __restrict__ transforms, unsigned long long* __restrict__ rejected_count)
 	{
 		decompress_track_requests<0>(clips, num_clips, clip_ids, sample_times, track_indices, num_instances, params, transforms, rejected_count);
+	}
+
+	// the same, transform of request i to row rows[i] (distinct rows, not bounds checked: aclhip_decompress_track_batch_rows)
+	__global__ __launch_bounds__(k_block_size) __attribute__((amdgpu_waves_per_eu(ACLHIP_TRACK_WAVES_PER_EU, ACLHIP_TRACK_WAVES_PER_EU))) void decompress_track_rows_kernel(const device_clip* __restrict__ clips, uint32_t num_clips,
+		const uint32_t* __restrict__ clip_ids, const float* __restrict__ sample_times, const uint32_t* __restrict__ track_indices, const uint32_t* __restrict__ rows, uint32_t num_instances,
+		decode_params params, float4* __restrict__ transforms, unsigned long long* __restrict__ rejected_count)
+	{
+		decompress_track_requests<0, true>(clips, num_clips, clip_ids, sample_times, track_indices, num_instances, params, transforms, rejected_count, rows);
 	}
 
 	// (ACLHIP_DECODE_FAST: single track requests are served by the kernel above. A variant with the hardware's 1 ulp square root and

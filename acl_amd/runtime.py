@@ -41,6 +41,7 @@ EXPORTED_SYMBOLS = [
     "aclhip_strip_database_tier", "aclhip_plan_hierarchy_walk", "aclhip_set_clip_hierarchy", "aclhip_decompress_poses_batch", "aclhip_decompress_poses_host", "aclhip_time_decompress_poses_batch",
     "aclhip_pose_windows_of_launch", "aclhip_order_instances_device_for_windows", "aclhip_describe_tracks_launch", "aclhip_analyze_clip",
     "aclhip_get_clip_metadata_info", "aclhip_get_clip_parent_indices", "aclhip_get_clip_track_descriptions", "aclhip_set_clip_hierarchy_from_metadata", "aclhip_read_clip_metadata",
+    "aclhip_order_track_requests_device", "aclhip_decompress_track_batch_rows",
 ]
 
 
@@ -207,6 +208,8 @@ def load_library():
     lib.aclhip_order_instances_for_pose_windows.argtypes = [u32, vp, u32, vp]
     lib.aclhip_order_track_requests_for_locality.argtypes = [vp, u32, vp]
     lib.aclhip_order_instances_device.argtypes = [vp, vp, vp, u32, vp, vp, vp, vp]
+    lib.aclhip_order_track_requests_device.argtypes = [vp, vp, vp, vp, u32, vp, vp, vp, vp, vp, vp]
+    lib.aclhip_decompress_track_batch_rows.argtypes = [vp, vp, vp, vp, vp, u32, pparams, vp, vp]
     pconsumers = ctypes.POINTER(PoseConsumers)
     poutput = ctypes.POINTER(OutputDesc)
     lib.aclhip_get_lifetime_stats.argtypes = [vp, ctypes.POINTER(u64)]
@@ -553,6 +556,17 @@ class Context:
     def decompress_track_batch(self, clips_ptr, times_ptr, tracks_ptr, num_instances, out_ptr, params=None, stream=None):
         params = params if params is not None else default_params()
         self._check(self._lib.aclhip_decompress_track_batch(self._handle, clips_ptr, times_ptr, tracks_ptr, num_instances, ctypes.byref(params), out_ptr, stream))
+
+    def order_track_requests_device(self, clips_ptr, times_ptr, tracks_ptr, num_requests, order_ptr, out_clips_ptr=None, out_times_ptr=None, out_tracks_ptr=None,
+                                    out_positions_ptr=None, stream=None):
+        """aclhip_order_track_requests_device: the locality order of a DEVICE single track request list, stream ordered (device pointers)."""
+        self._check(self._lib.aclhip_order_track_requests_device(self._handle, clips_ptr, times_ptr, tracks_ptr, num_requests, order_ptr, out_clips_ptr, out_times_ptr,
+                                                                 out_tracks_ptr, out_positions_ptr, stream))
+
+    def decompress_track_batch_rows(self, clips_ptr, times_ptr, tracks_ptr, rows_ptr, num_requests, out_ptr, params=None, stream=None):
+        """aclhip_decompress_track_batch with the transform of request k stored at row rows[k] (device array)."""
+        params = params if params is not None else default_params()
+        self._check(self._lib.aclhip_decompress_track_batch_rows(self._handle, clips_ptr, times_ptr, tracks_ptr, rows_ptr, num_requests, ctypes.byref(params), out_ptr, stream))
 
     def time_decompress_tracks_batch(self, clips_ptr, times_ptr, num_instances, poses_ptr, pose_stride_bytes, repeats, params=None, stream=None):
         """Average device milliseconds per launch, HIP events recorded on `stream`."""

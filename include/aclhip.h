@@ -511,6 +511,41 @@ aclhip_status aclhip_order_track_requests_for_locality(const aclhip_clip* clips,
 aclhip_status aclhip_decompress_track_batch(aclhip_context* context, const aclhip_clip* clips, const float* sample_times, const uint32_t* track_indices,
 	uint32_t num_instances, const aclhip_decompress_params* params, void* transforms, void* stream);
 
+/* The same order computed on the GPU for request lists built there every frame (IK targets, attachment bones, a crowd's root bones).
+ * All pointers are DEVICE pointers; stream ordered on `stream`: three launches (count per clip, scan, scatter), no host
+ * synchronization. Writes the permutation to out_order (required) and, when the pointers are not NULL, out_clips[k] =
+ * clips[out_order[k]], out_sample_times[k] = sample_times[out_order[k]], out_track_indices[k] = track_indices[out_order[k]] (the
+ * arguments of the aclhip_decompress_track_batch that follows on the same stream) and the inverse permutation
+ * out_positions[out_order[k]] = k (request i's transform is transform out_positions[i] of that launch). The layout is
+ * aclhip_order_track_requests_for_locality's: requests bucketed by clip in ascending handle order, every XCD one contiguous range
+ * of that sequence. Which request of a clip takes which of the clip's slots is decided by atomics: every call returns a valid order,
+ * not a stable or reproducible one -- but clips[out_order[k]] equals the host order's clips[host_order[k]] at every k whose handle
+ * is registered. Handles past the registry share the last bucket, out-of-range track indices are ordered like any other request:
+ * the decode refuses (and counts) both. Scratch and failure protocol are aclhip_order_instances_device's: the stream's ordering
+ * scratch is shared by both kinds of ordering, the first call on a stream allocates it (make it before capturing the stream into a
+ * hipGraph; no later call allocates unless the registry grows), a captured ordering holds the scratch of its stream (replay it on
+ * that stream), and an ordering that did not complete -- of either kind -- makes the next ordering call on the stream return
+ * ACLHIP_ERROR_DEVICE once. Measured for 4 M requests over 256 clips: the ordering 152 us as drawn at random (its
+ * scatter writes every request's four words to scattered positions), 50 us for character-major lists (runs of one instance's
+ * bones); ordering + decode 222 us against 176 us for the decode as drawn, 116 against 99 us character-major. So today it pays
+ * where the ordered lists are decoded more than once, not for one decode of a list drawn at random. */
+aclhip_status aclhip_order_track_requests_device(aclhip_context* context, const aclhip_clip* clips, const float* sample_times,
+	const uint32_t* track_indices, uint32_t num_requests, uint32_t* out_order, aclhip_clip* out_clips, float* out_sample_times,
+	uint32_t* out_track_indices, uint32_t* out_positions, void* stream);
+
+/* aclhip_decompress_track_batch with the transform of request k stored at (char*)transforms + rows[k] * 48 instead of k * 48
+ * (`rows`: DEVICE array of num_requests DISTINCT indices, not bounds checked, as in aclhip_decompress_tracks_batch_rows). With the
+ * lists of aclhip_order_track_requests_device and rows = out_order the transforms of a device-ordered decode land in the
+ * caller's request order. Refused requests and skipped default sub-tracks leave their row's bytes untouched, refusals are counted
+ * (aclhip_get_rejected_instance_count). Every lane stores its own 48 bytes instead of a wave's three contiguous 1 KiB, and scattered
+ * 48 byte records cost a lot of write bandwidth: 4 M requests over 256 clips take 640 us here against 76 us for the same ordered
+ * decode in decode order, and order + this decode (793 us) is SLOWER than decoding the caller's list as drawn (176 us); 336 against
+ * 68 us for character-major lists. Do not use it for throughput: decode in decode order and consume transform out_positions[i] for
+ * request i. */
+aclhip_status aclhip_decompress_track_batch_rows(aclhip_context* context, const aclhip_clip* clips, const float* sample_times,
+	const uint32_t* track_indices, const uint32_t* rows, uint32_t num_requests, const aclhip_decompress_params* params,
+	void* transforms, void* stream);
+
 /* Convenience for host callers (the C++ mirror of decompression_context uses it with a batch of one): same as the two
  * calls above but every pointer is a HOST pointer; instance lists are uploaded, poses downloaded, the call is synchronous.
  * params->default_values / track_rounding_policies / instance_rounding_policies are HOST pointers here as well;
