@@ -69,6 +69,7 @@ using namespace aclhip;
 #include "../../tools/experiments/host_experiments.inl"
 #endif
 #include "host_launch.inl"
+#include "host_track_maps.inl"
 #include "host_lists.inl"
 #include "host_consumers.inl"
 #include "host_scalar_misc.inl"

@@ -180,9 +180,33 @@ namespace aclhip
 		bool is_valid() const { return m_context != nullptr; }
 		aclhip_context* get() const { return m_context; }
 
+		// Track maps: the table an engine's track_writer uses to send track_index to the slot of its bone in the skeleton's pose
+		// (track_writer::write_rotation / write_translation / write_scale(track_index, value), core/track_writer.h), registered once.
+		// track_to_slot[t] = record of the pose row track t is written to, or ACLHIP_TRACK_DROPPED. Returns 0 when the map is refused.
+		aclhip_track_map register_track_map(const std::vector<uint32_t>& track_to_slot, uint32_t num_slots)
+		{
+			aclhip_track_map map = 0;
+			if (m_context == nullptr || aclhip_register_track_map(m_context, track_to_slot.data(), uint32_t(track_to_slot.size()), num_slots, &map) != ACLHIP_OK)
+				return 0;
+			return map;
+		}
+		bool unregister_track_map(aclhip_track_map map) { return m_context != nullptr && aclhip_unregister_track_map(m_context, map) == ACLHIP_OK; }
+
 	private:
 		aclhip_context* m_context = nullptr;
 	};
+
+	// decompress_tracks for a batch whose poses leave in SKELETON order: aclhip_decompress_tracks_batch_mapped with one map for the launch
+	// (DEVICE pointers, asynchronous on `stream`). `fill_pose` (num_slots records, or null) is written to the slots no track maps to.
+	inline bool decompress_tracks_mapped(device& gpu, const aclhip_clip* clips, const float* sample_times, uint32_t num_instances, aclhip_track_map map,
+		const void* fill_pose, void* poses, uint64_t pose_stride_bytes, void* stream = nullptr, const aclhip_decompress_params* params = nullptr, const aclhip_output_desc* output = nullptr)
+	{
+		aclhip_track_mapping mapping = {};
+		mapping.map = map;
+		mapping.fill_pose = fill_pose;
+		mapping.fill_unmapped = fill_pose != nullptr ? 1u : 0u;
+		return gpu.is_valid() && aclhip_decompress_tracks_batch_mapped(gpu.get(), clips, sample_times, num_instances, params, output, &mapping, poses, pose_stride_bytes, stream) == ACLHIP_OK;
+	}
 
 	namespace impl
 	{

@@ -71,6 +71,12 @@ struct aclhip_context
 	std::vector<host_clip> clips;
 	std::vector<uint32_t> free_slots;
 	std::vector<host_database> databases;
+	// Track maps (aclhip_register_track_map, host_track_maps.inl). The device table is ONE allocation of k_track_map_table_entries
+	// records made at the first registration: it never moves and never grows. Record 0 is never handed out (0 is the null map handle).
+	struct track_map_entry { bool in_use = false; aclhip_track_map_info info = {}; uint8_t* device_memory = nullptr; };
+	std::vector<track_map_entry> track_maps;
+	std::vector<uint32_t> free_map_slots;
+	device_track_map* d_track_maps = nullptr;
 	device_clip* d_clips = nullptr;
 	uint32_t d_clips_capacity = 0;
 	unsigned long long* d_rejected = nullptr;	// [0] instances the kernels refused, [1] transforms of the pose consumers that met a negative scale
@@ -112,6 +118,7 @@ struct aclhip_context
 		void* clip_memory = nullptr;				// a piece of a slab
 		uint32_t* hierarchy = nullptr;				// a walk schedule image (shared images are reference counted)
 		uint32_t slot = ACLHIP_INVALID_HANDLE;		// clip handle that becomes reusable
+		uint32_t map_slot = ACLHIP_INVALID_HANDLE;	// track map handle that becomes reusable
 		uint8_t* database_memory[6] = { nullptr, nullptr, nullptr, nullptr, nullptr, nullptr };		// hipMalloc'ed pieces of a database
 		uint8_t* database_pinned[4] = { nullptr, nullptr, nullptr, nullptr };		// bulk data x 2, patch mirrors x 2
 		void* device_memory = nullptr;				// any other hipMalloc'ed piece
@@ -334,7 +341,8 @@ namespace
 	// `record_to_clear` (a clip's record in the device table, or null): cleared on the context's retire stream BEHIND those same points --
 	// launches already enqueued still find the clip (kernels read the record when they execute, not when they are enqueued), launches
 	// that execute later are refused -- and the item is not recycled before the clear has happened. Nobody waits on the host.
-	void retire(aclhip_context* context, aclhip_context::retired_item&& item, device_clip* record_to_clear = nullptr)
+	// (`record_bytes`: a record of the clip table, or of the track map table)
+	void retire(aclhip_context* context, aclhip_context::retired_item&& item, void* record_to_clear = nullptr, size_t record_bytes = sizeof(device_clip))
 	{
 		for (size_t i = 0; i < context->launch_streams.size();)
 		{
@@ -358,7 +366,7 @@ namespace
 				ordered = hipStreamWaitEvent(context->retire_stream, item.events[i], 0) == hipSuccess;
 			hipEvent_t cleared = ordered ? take_event(context) : nullptr;
 			ordered = ordered && cleared != nullptr
-				&& hipMemsetAsync(record_to_clear, 0, sizeof(device_clip), context->retire_stream) == hipSuccess
+				&& hipMemsetAsync(record_to_clear, 0, record_bytes, context->retire_stream) == hipSuccess
 				&& hipEventRecord(cleared, context->retire_stream) == hipSuccess;
 			if (ordered)
 				item.events.push_back(cleared);
@@ -368,7 +376,7 @@ namespace
 				(void)hipGetLastError();
 				if (cleared != nullptr)
 					context->event_pool.push_back(cleared);
-				(void)hipMemsetAsync(record_to_clear, 0, sizeof(device_clip), context->copy_stream);
+				(void)hipMemsetAsync(record_to_clear, 0, record_bytes, context->copy_stream);
 				(void)hipStreamSynchronize(context->copy_stream);
 			}
 		}
@@ -409,6 +417,8 @@ namespace
 				release_hierarchy(context, item.hierarchy);
 			if (item.slot != ACLHIP_INVALID_HANDLE)
 				context->free_slots.push_back(item.slot);
+			if (item.map_slot != ACLHIP_INVALID_HANDLE)
+				context->free_map_slots.push_back(item.map_slot);
 			for (uint8_t* memory : item.database_memory)
 				if (memory != nullptr)
 					(void)hipFree(memory);
@@ -1002,6 +1012,8 @@ extern "C" void aclhip_destroy(aclhip_context* context)
 			(void)hipFree(context->d_clips);
 		if (context->d_rejected != nullptr)
 			(void)hipFree(context->d_rejected);
+		if (context->d_track_maps != nullptr)
+			(void)hipFree(context->d_track_maps);
 		for (const aclhip_context::order_scratch& scratch : context->order_scratches)
 		{
 			(void)hipFree(scratch.bins);

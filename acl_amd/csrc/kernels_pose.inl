@@ -344,12 +344,77 @@
 		unsigned long long* rejected_count;
 	};
 
-	template<bool kAnySettings, bool kCompactOutput, bool kWideKeyLoads = false, uint32_t kFastMath = 0>
+	// ---- track maps (aclhip_register_track_map, aclhip_decompress_tracks_batch_mapped) ------------------------------------------------
+	// track_writer::write_rotation / _translation / _scale(track_index, value) (core/track_writer.h) hand the writer an index and the
+	// writer stores where it likes: the mapped kernels store track t of a clip in record map[t] of the pose row. A map's record in the
+	// context's map table (which never moves, like the clip table) and its device image: track_to_slot[num_tracks], the sorted
+	// slots no track maps to [num_unmapped], then slot_to_track[num_slots] (ACLHIP_TRACK_DROPPED: no track maps to the slot). A cleared record (image == null) is an unknown or retired map.
+	struct device_track_map
+	{
+		const uint32_t* image;
+		uint32_t num_tracks;
+		uint32_t num_slots;
+		uint32_t num_unmapped;
+		uint32_t flags;
+		uint32_t reserved[2];
+	};
+	static_assert(sizeof(device_track_map) == 32, "load_entry: two dwordx4 loads");
+
+	// the mapped kernels' own trailing argument: decode_params and the kernarg offsets of every other pose kernel stay as they were
+	struct mapped_launch
+	{
+		const device_track_map* maps;		// the context's map table
+		uint32_t num_maps;					// its capacity
+		uint32_t map;						// the launch's map, when instance_maps is null
+		const uint32_t* instance_maps;		// [num_instances] by the caller's instance index, or null
+		const uint8_t* fill_pose;			// num_slots records in the launch's layout, or null: unmapped slots are left untouched
+	};
+
+	// Unmapped slots of an instance's map <- fill_pose, whole records in the launch's layout. The list is split evenly between the
+	// `num_shares` wavefronts of the instance (every pose window's wave takes a share, also the ones that have no window of this clip to
+	// decode); lanes <-> 16 byte pieces of consecutive entries (8 byte pieces for the 40 byte records of QVV40).
+	__device__ __forceinline__ void fill_unmapped_slots(const device_track_map& map, const uint8_t* __restrict__ fill_pose, uint8_t* __restrict__ pose_bytes,
+		uint32_t layout, uint32_t share, uint32_t num_shares, uint32_t lane)
+	{
+		if (fill_pose == nullptr || map.num_unmapped == 0)
+			return;
+		const uint32_t* unmapped = map.image + map.num_tracks;
+		const uint32_t record_bytes = layout_bytes_per_track(layout);
+		const uint32_t piece_bytes = layout == ACLHIP_LAYOUT_QVV40 ? 8u : 16u;
+		const uint32_t pieces_per_record = record_bytes / piece_bytes;		// 3, 5 or 2
+		const uint32_t entries_per_share = (map.num_unmapped + num_shares - 1) / num_shares;
+		const uint32_t first_entry = min(share * entries_per_share, map.num_unmapped);
+		const uint32_t num_pieces = (min(first_entry + entries_per_share, map.num_unmapped) - first_entry) * pieces_per_record;
+		for (uint32_t base = 0; base < num_pieces; base += k_wave_size)
+		{
+			const uint32_t index = base + lane;
+			if (index >= num_pieces)
+				continue;
+			const uint32_t entry = index / pieces_per_record;
+			const uint32_t piece = index - entry * pieces_per_record;
+			const uint32_t slot = unmapped[first_entry + entry];
+			if (slot >= map.num_slots)		// (never: registration wrote the list)
+				continue;
+			const size_t offset = size_t(slot) * record_bytes + piece * piece_bytes;
+			if (layout == ACLHIP_LAYOUT_QVV40)
+			{
+				const float* source = reinterpret_cast<const float*>(fill_pose + offset);
+				const float half[2] = { source[0], source[1] };
+				store_streaming_floats<2>(reinterpret_cast<float*>(pose_bytes + offset), half);
+			}
+			else
+				store_streaming(pose_bytes + offset, *reinterpret_cast<const f32x4*>(fill_pose + offset));
+		}
+	}
+
+	template<bool kAnySettings, bool kCompactOutput, bool kWideKeyLoads = false, uint32_t kFastMath = 0, bool kMapped = false>
 	__device__ __forceinline__ void decompress_tracks_window(const device_clip* __restrict__ clips, uint32_t num_clips,
 		const uint32_t* __restrict__ clip_ids, const float* __restrict__ sample_times, uint32_t num_instances, uint32_t windows_per_instance,
 		const decode_params& params, uint8_t* __restrict__ poses, uint64_t pose_stride_bytes, uint32_t lds_quads_per_wave,
-		unsigned long long* __restrict__ rejected_count, uint32_t work_item, uint32_t* image_clip = nullptr, const ACLHIP_CONSTANT pose_kernel_args* late_args = nullptr)
+		unsigned long long* __restrict__ rejected_count, uint32_t work_item, uint32_t* image_clip = nullptr, const ACLHIP_CONSTANT pose_kernel_args* late_args = nullptr,
+		const mapped_launch* mapping = nullptr)
 	{
+		static_assert(!kMapped || kCompactOutput, "the mapped kernels are built on the compact output store path (every layout, every skip)");
 		extern __shared__ __attribute__((aligned(16))) uint8_t dynamic_lds[];
 		ACLHIP_WAVE0_STAMP(0);
 
@@ -390,7 +455,19 @@
 #endif
 		// the tracks this instance stores: all of its clip's, or its first K (aclhip_output_desc::instance_track_counts: a per character LOD)
 		const uint32_t stored_tracks = stored_tracks_of(params, caller_instance, clip.num_tracks);
-		if (clip_id >= num_clips || !is_transform_clip(clip.flags)
+		// the instance's map (wave uniform, scalar unit): its record is requested next to the clip record. Unknown and retired handles find
+		// a cleared record; a map made for another track count, or for more slots than the row holds, is refused like a clip that does
+		// not fit the launch -- counted, the row untouched
+		device_track_map track_map = {};
+		bool map_refused = false;
+		if (kMapped)
+		{
+			const uint32_t map_id = mapping->instance_maps != nullptr ? as_constant(mapping->instance_maps)[caller_instance] : mapping->map;
+			track_map = load_entry(mapping->maps, map_id < mapping->num_maps ? map_id : 0);		// (record 0 is never handed out: always cleared)
+			map_refused = map_id >= mapping->num_maps || track_map.image == nullptr || track_map.num_tracks != clip.num_tracks
+				|| uint64_t(track_map.num_slots) * layout_bytes_per_track(params.layout) > pose_stride_bytes;
+		}
+		if (clip_id >= num_clips || !is_transform_clip(clip.flags) || (kMapped && map_refused)
 			|| launch_refuses_clip(stored_tracks, windows_per_instance, lds_quads_per_wave, kCompactOutput ? layout_bytes_per_track(params.layout) : 48u, pose_stride_bytes))
 		{
 			if (lane == 0 && window == 0)
@@ -401,8 +478,21 @@
 		// an empty track list (decompression.transform.h:1531-1533) or a pose that ends before this window
 		const uint32_t num_quads = stored_tracks * 3u;
 		const uint32_t first_quad = window * k_image_chunk_quads;
+		// mapped, QVV48, nothing skipped, defaults already resolved in the image, the whole clip in ONE window: the wave of window 0 holds
+		// every track in LDS and writes the row in SLOT order (below) -- the fill included; the instance's other waves have nothing to do
+		const bool slot_order = kMapped && !(kAnySettings && params.standard_default_modes == 0) && params.layout == ACLHIP_LAYOUT_QVV48 && params.skip_mask == 0
+			&& params.skip_tracks == nullptr && params.instance_masks == nullptr && clip.num_tracks * 3u <= k_image_chunk_quads;
 		if (first_quad >= num_quads)
+		{
+			// (a wave without a window of this clip still takes its share of the map's unmapped slots)
+			// (slot order: window 0's wave owns the whole row -- here it stores no track at all, a track count of 0, and still fills)
+			if (kMapped && (!slot_order || window == 0))
+			{
+				const uint32_t row = params.instance_rows != nullptr ? as_constant(params.instance_rows)[instance] : instance;
+				fill_unmapped_slots(track_map, mapping->fill_pose, poses + uint64_t(row) * pose_stride_bytes, params.layout, slot_order ? 0u : window, slot_order ? 1u : windows_per_instance, lane);
+			}
 			return;
+		}
 		const uint32_t window_quads = min(num_quads - first_quad, k_image_chunk_quads);
 
 		// the window's animated sub-tracks: image_chunks[window] .. image_chunks[window + 1]
@@ -490,6 +580,19 @@
 			track_rounding_policies = params.track_rounding_table + size_t(as_constant(params.instance_rounding_tables)[caller_instance]) * params.track_rounding_stride;
 		decode_window_sub_tracks<kAnySettings, kWideKeyLoads, kFastMath>(window_tables_of(clip), state, params, rounding_policy, normalization, first_ordinal, end_ordinal, first_quad, window_quads, lane, image, track_rounding_policies, one_shot);
 
+		// mapped, scattered form (poses of several windows, compact layouts, skips, unresolved defaults): the slots of the tracks this lane
+		// stores, one per row of the window (a lane's quad of row r is lane_quad + 64 r) -- five per-lane vector loads (the index differs per
+		// lane), requested behind the decode, where its registers are free again. Every instance of a clip reads the same few hundred bytes
+		// (vector cache / L2 hits), but the wait below does cover this round trip: it is in front of the stores. Not measured on its own.
+		constexpr uint32_t k_map_rows = kMapped ? (k_image_chunk_quads + k_wave_size - 1) / k_wave_size : 1;
+		uint32_t lane_slots[k_map_rows];
+		if (kMapped && !slot_order)
+		{
+			#pragma unroll
+			for (uint32_t r = 0; r < k_map_rows; ++r)
+				lane_slots[r] = as_constant(track_map.image)[min((first_quad + lane + r * k_wave_size) / 3u, track_map.num_tracks - 1)];
+		}
+
 		// DMA and the wave's own LDS writes must have landed before lanes read each other's quads
 		__builtin_amdgcn_s_waitcnt(0);
 		__builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
@@ -497,13 +600,49 @@
 		__builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
 		ACLHIP_WAVE0_STAMP(2);
 
+		if (kMapped && slot_order)
+		{
+			// The row in SLOT order: lanes <-> consecutive quads of the OUTPUT, gathered from the track ordered image in LDS through the
+			// map's inverse table (slot -> track; a gather out of LDS has no locality to lose), unmapped slots from fill_pose. With the fill
+			// every store instruction writes 1 KiB of contiguous HBM again, whatever permutation the map is; without it only the unmapped
+			// records are left out. Tracks beyond the instance's track count are mapped but not decoded: their slots are left untouched.
+			const uint32_t row = params.instance_rows != nullptr ? as_constant(params.instance_rows)[instance] : instance;
+			uint8_t* row_bytes = poses + uint64_t(row) * pose_stride_bytes;
+			const uint32_t* slot_to_track = track_map.image + track_map.num_tracks + track_map.num_unmapped;
+			const uint8_t* fill_pose = mapping->fill_pose;
+			const uint32_t row_quads = track_map.num_slots * 3u;
+			// (ONE store instruction per 64 quads, whatever mix of decoded and filled records they are: two predicated instructions would each
+			// write partial 64 byte granules -- measured: 221 us instead of 95 us for the headline batch into 128 slots with the fill; the
+			// inverse table's entry of the next pass is requested before this pass's stores)
+			uint32_t quad = lane;
+			uint32_t track = quad < row_quads ? slot_to_track[quad / 3u] : 0u;
+			for (uint32_t base = 0; base < row_quads; base += k_wave_size)
+			{
+				const uint32_t next_quad = quad + k_wave_size;
+				const uint32_t next_track = next_quad < row_quads ? slot_to_track[next_quad / 3u] : 0u;
+				const bool decoded = quad < row_quads && track < stored_tracks;
+				const bool filled = quad < row_quads && track == 0xFFFFFFFFu && fill_pose != nullptr;
+				f32x4 value = f32x4{ 0.0f, 0.0f, 0.0f, 0.0f };
+				if (decoded)
+					value = image[track * 3u + quad % 3u];
+				if (filled)
+					value = *reinterpret_cast<const f32x4*>(fill_pose + size_t(quad) * 16);
+				if (decoded || filled)
+					store_streaming(row_bytes + size_t(quad) * 16, value);
+				quad = next_quad;
+				track = next_track;
+			}
+			ACLHIP_WAVE0_STAMP(3);
+			return;
+		}
+
 		// track_writer::skip_track_rotation / _translation / _scale(track_index) (core/track_writer.h:189-191): one mask for the launch, or
 		// this instance's own out of the caller's table (aclhip_output_desc::mask_table, instance_masks)
 		const uint8_t* skip_tracks = params.skip_tracks;
 		if (kCompactOutput && params.instance_masks != nullptr)
 			skip_tracks = params.mask_table + size_t(as_constant(params.instance_masks)[caller_instance]) * params.mask_stride;
 
-		if (kCompactOutput && params.layout != ACLHIP_LAYOUT_QVV48 && (params.skip_mask & ~(params.layout == ACLHIP_LAYOUT_QV32 ? 4u : 0u)) == 0 && !resolve_defaults && skip_tracks == nullptr)
+		if (!kMapped && kCompactOutput && params.layout != ACLHIP_LAYOUT_QVV48 && (params.skip_mask & ~(params.layout == ACLHIP_LAYOUT_QV32 ? 4u : 0u)) == 0 && !resolve_defaults && skip_tracks == nullptr)
 		{
 			// Compact layouts, nothing else skipped (the common use): the window is RE-TILED on its way out -- lanes <-> consecutive 16 byte
 			// pieces of the OUTPUT, gathered from the QVV48 image in LDS -- so that every store instruction still writes 1 KiB of
@@ -641,19 +780,26 @@
 				store = store && ((params.skip_mask >> kind) & 1u) == 0;
 				if (skip_tracks != nullptr && store)
 					store = ((skip_tracks[track_index] >> kind) & 1u) == 0;
+				// mapped: everything above is indexed by TRACK, the record the quad goes to is the track's slot (ACLHIP_TRACK_DROPPED is beyond
+				// every row); the three lanes of a track still write one contiguous record
+				const uint32_t record_index = kMapped ? lane_slots[kMapped ? r : 0] : track_index;
+				if (kMapped)
+					store = store && record_index < track_map.num_slots;
 				if (params.layout == ACLHIP_LAYOUT_QVV48)
 				{
-					if (store)
+					if (store && !kMapped)
 						store_streaming(&pose[r * k_wave_size], value);
+					if (store && kMapped)
+						store_streaming(pose_bytes + (size_t(record_index) * 3u + kind) * 16, value);
 				}
 				else if (params.layout == ACLHIP_LAYOUT_QV32)
 				{
 					if (store && kind != 2)
-						store_streaming(pose_bytes + size_t(track_index * 2u + kind) * 16, value);
+						store_streaming(pose_bytes + size_t(record_index * 2u + kind) * 16, value);
 				}
 				else
 				{
-					uint8_t* address = pose_bytes + size_t(track_index) * 40 + (kind == 0 ? 0u : (kind == 1 ? 16u : 28u));
+					uint8_t* address = pose_bytes + size_t(record_index) * 40 + (kind == 0 ? 0u : (kind == 1 ? 16u : 28u));
 					if (store && kind == 0)
 						store_streaming(address, value);
 					if (store && kind != 0)
@@ -666,6 +812,9 @@
 			if (kAnySettings || kCompactOutput)
 				kind = kind == 2 ? 0u : kind + 1u;
 		}
+		// the bones this clip does not animate: behind the wave's own stores, in the same launch
+		if (kMapped)
+			fill_unmapped_slots(track_map, mapping->fill_pose, pose_bytes, params.layout, window, windows_per_instance, lane);
 		ACLHIP_WAVE0_STAMP(3);
 	}
 
@@ -968,4 +1117,17 @@
 	__global__ __launch_bounds__(k_block_size) __attribute__((amdgpu_waves_per_eu(8, 8))) void decompress_tracks_any_settings_compact_kernel(ACLHIP_POSE_KERNEL_ARGUMENTS)
 	{
 		decompress_tracks_window<true, true>(ACLHIP_POSE_KERNEL_FORWARD, one_shot_work_item());
+	}
+
+	// ---- mapped decode: track t of the clip goes to record map[t] of the row (aclhip_decompress_tracks_batch_mapped) --------------------
+	// The compact output kernels' store path with the destination record looked up per track, plus the fill of the map's unmapped slots.
+	// The mapping is a trailing argument of these entry points only.
+	__global__ __launch_bounds__(k_block_size) __attribute__((amdgpu_waves_per_eu(8, 8))) void decompress_tracks_mapped_kernel(ACLHIP_POSE_KERNEL_ARGUMENTS, mapped_launch mapping)
+	{
+		decompress_tracks_window<false, true, false, 0, true>(ACLHIP_POSE_KERNEL_FORWARD, one_shot_work_item(), nullptr, nullptr, &mapping);
+	}
+
+	__global__ __launch_bounds__(k_block_size) __attribute__((amdgpu_waves_per_eu(8, 8))) void decompress_tracks_mapped_any_settings_kernel(ACLHIP_POSE_KERNEL_ARGUMENTS, mapped_launch mapping)
+	{
+		decompress_tracks_window<true, true, false, 0, true>(ACLHIP_POSE_KERNEL_FORWARD, one_shot_work_item(), nullptr, nullptr, &mapping);
 	}

@@ -42,6 +42,7 @@ EXPORTED_SYMBOLS = [
     "aclhip_pose_windows_of_launch", "aclhip_order_instances_device_for_windows", "aclhip_describe_tracks_launch", "aclhip_analyze_clip",
     "aclhip_get_clip_metadata_info", "aclhip_get_clip_parent_indices", "aclhip_get_clip_track_descriptions", "aclhip_set_clip_hierarchy_from_metadata", "aclhip_read_clip_metadata",
     "aclhip_order_track_requests_device", "aclhip_decompress_track_batch_rows",
+    "aclhip_check_track_map", "aclhip_register_track_map", "aclhip_unregister_track_map", "aclhip_get_track_map_info", "aclhip_decompress_tracks_batch_mapped",
 ]
 
 
@@ -75,6 +76,23 @@ class OutputDesc(ctypes.Structure):
     ]
 
 
+class TrackMapInfo(ctypes.Structure):
+    """aclhip_track_map_info"""
+    _fields_ = [
+        ("num_tracks", ctypes.c_uint32), ("num_slots", ctypes.c_uint32), ("num_mapped", ctypes.c_uint32), ("num_dropped", ctypes.c_uint32),
+        ("num_unmapped_slots", ctypes.c_uint32), ("is_identity", ctypes.c_uint32), ("is_order_preserving", ctypes.c_uint32), ("reserved", ctypes.c_uint32),
+    ]
+
+
+class TrackMapping(ctypes.Structure):
+    """aclhip_track_mapping"""
+    _fields_ = [
+        ("map", ctypes.c_uint32), ("instance_maps", ctypes.c_void_p), ("fill_pose", ctypes.c_void_p), ("fill_unmapped", ctypes.c_uint32), ("reserved", ctypes.c_uint32),
+    ]
+
+
+TRACK_DROPPED = 0xFFFFFFFF  # ACLHIP_TRACK_DROPPED
+MAX_TRACK_MAPS = 16384      # ACLHIP_MAX_TRACK_MAPS
 ABI_VERSION = 6             # ACLHIP_ABI_VERSION: the struct layouts mirrored above
 PEER_HANDLE_BYTES = 72      # ACLHIP_PEER_HANDLE_BYTES
 LAYOUT_QVV48, LAYOUT_QVV40, LAYOUT_QV32 = 0, 1, 2  # aclhip_pose_layout
@@ -238,8 +256,21 @@ def load_library():
     lib.aclhip_get_clip_track_descriptions.argtypes = [vp, u32, vp, vp, vp, u32]
     lib.aclhip_set_clip_hierarchy_from_metadata.argtypes = [vp, u32]
     lib.aclhip_read_clip_metadata.argtypes = [vp, u64, ctypes.POINTER(ClipMetadataInfo), vp, vp, vp, vp, u32]
+    lib.aclhip_check_track_map.argtypes = [vp, u32, u32, ctypes.POINTER(TrackMapInfo), ctypes.c_char_p, u32]
+    lib.aclhip_register_track_map.argtypes = [vp, vp, u32, u32, ctypes.POINTER(u32)]
+    lib.aclhip_unregister_track_map.argtypes = [vp, u32]
+    lib.aclhip_get_track_map_info.argtypes = [vp, u32, ctypes.POINTER(TrackMapInfo)]
+    lib.aclhip_decompress_tracks_batch_mapped.argtypes = [vp, vp, vp, u32, pparams, poutput, ctypes.POINTER(TrackMapping), vp, u64, vp]
     _lib = lib
     return lib
+
+
+def check_track_map(track_to_slot, num_slots):
+    """Host only validation of a track map (no GPU needed): what aclhip_register_track_map checks. Returns (status, message, TrackMapInfo)."""
+    table = np.ascontiguousarray(track_to_slot, dtype=np.uint32)
+    message, info = ctypes.create_string_buffer(256), TrackMapInfo()
+    status = load_library().aclhip_check_track_map(table.ctypes.data, table.size, int(num_slots), ctypes.byref(info), message, 256)
+    return status, message.value.decode(), info
 
 
 def probe_rccl():
@@ -531,6 +562,34 @@ class Context:
         """aclhip_decompress_tracks_batch with an OutputDesc (layout, skipped sub-track kinds, rows)."""
         params = params if params is not None else default_params()
         self._check(self._lib.aclhip_decompress_tracks_batch_out(self._handle, clips_ptr, times_ptr, num_instances, ctypes.byref(params), ctypes.byref(output), poses_ptr, pose_stride_bytes, stream))
+
+    # ---- track maps (track_writer::write_*(track_index, value): the writer chooses the destination) ----
+    def register_track_map(self, track_to_slot, num_slots):
+        """track_to_slot: host array, slot of every track or TRACK_DROPPED. Returns the map handle (>= 1)."""
+        table = np.ascontiguousarray(track_to_slot, dtype=np.uint32)
+        handle = ctypes.c_uint32(0)
+        self._check(self._lib.aclhip_register_track_map(self._handle, table.ctypes.data, table.size, int(num_slots), ctypes.byref(handle)))
+        return handle.value
+
+    def unregister_track_map(self, track_map):
+        self._check(self._lib.aclhip_unregister_track_map(self._handle, track_map))
+
+    def track_map_info(self, track_map):
+        info = TrackMapInfo()
+        self._check(self._lib.aclhip_get_track_map_info(self._handle, track_map, ctypes.byref(info)))
+        return info
+
+    def decompress_tracks_batch_mapped(self, clips, sample_times, poses, pose_stride_bytes, track_map=0, instance_maps=None, fill_pose=None, output=None, params=None, stream=None):
+        """aclhip_decompress_tracks_batch_mapped on torch tensors (device): clips int32/uint32 [n], sample_times float32 [n], poses the
+        output buffer (rows pose_stride_bytes apart), instance_maps int32 [n] or None, fill_pose a tensor (unmapped slots are written from it) or None."""
+        params = params if params is not None else default_params()
+        mapping = TrackMapping()
+        mapping.map = int(track_map)
+        mapping.instance_maps = instance_maps.data_ptr() if instance_maps is not None else None
+        mapping.fill_pose = fill_pose.data_ptr() if fill_pose is not None else None
+        mapping.fill_unmapped = 1 if fill_pose is not None else 0
+        self._check(self._lib.aclhip_decompress_tracks_batch_mapped(self._handle, clips.data_ptr(), sample_times.data_ptr(), int(clips.numel()), ctypes.byref(params),
+                                                                   ctypes.byref(output) if output is not None else None, ctypes.byref(mapping), poses.data_ptr(), int(pose_stride_bytes), stream))
 
     def order_instances_for_locality(self, clips):
         """Host only: the permutation aclhip_order_instances_for_locality computes for the instance list `clips`."""

@@ -199,7 +199,9 @@ const char* aclhip_last_error_message(const aclhip_context* context);
 /* The layouts of the structs in this header as a number: bumped whenever one of them changes (3: aclhip_output_desc::skip_tracks;
  * 4: aclhip_pose_consumers::num_blend_clips, flags, blend_clips, blend_sample_times, blend_weights;
  * 5: aclhip_decompress_params::instance_looping_policies, track_rounding_table, instance_rounding_tables, track_rounding_stride, aclhip_output_desc::mask_table, instance_masks, instance_track_counts, mask_stride;
- * 6: ACLHIP_DEFAULT_BIND_POSE, aclhip_clip_metadata_info; ACLHIP_ERROR_UNSUPPORTED_FORMAT no longer covers the full-precision formats).
+ * 6: ACLHIP_DEFAULT_BIND_POSE, aclhip_clip_metadata_info; ACLHIP_ERROR_UNSUPPORTED_FORMAT no longer covers the full-precision formats;
+ * track maps -- aclhip_track_map_info, aclhip_track_mapping and their entry points -- were ADDED without a bump: no existing struct or
+ * entry point changed shape, so a caller built against the earlier header 6 hands over nothing of another shape).
  * A caller compiled against another header would hand over structs of another shape; aclhip_abi_version() says what the LIBRARY was
  * built with, and the C++ mirror (aclhip.hpp) refuses to create a context when the two differ. */
 #define ACLHIP_ABI_VERSION 6u
@@ -406,6 +408,91 @@ aclhip_status aclhip_decompress_tracks_batch_out(aclhip_context* context, const 
 /* Bytes one track takes in a pose of `layout` (48 / 40 / 32); 0 for an unknown layout. */
 uint32_t aclhip_layout_bytes_per_track(uint32_t layout);
 
+/* ---- track maps: clips whose track order is not the skeleton's -------------------------------------
+ * The run time form of the INDEX side of the track_writer protocol: track_writer::write_rotation / write_translation /
+ * write_scale(track_index, value) (core/track_writer.h) hand the writer an index and the writer stores wherever it likes. An engine's
+ * writer sends track t of a compressed clip -- which carries only the bones it animates, in its own order -- to the slot of its bone in
+ * the SKELETON's pose; the bones the clip does not carry keep the reference pose. A registered map is that table; the mapped decode
+ * below writes the pose in slot order in the ONE trip to HBM the decode makes anyway.
+ *
+ * aclhip_register_track_map: `track_to_slot` is a HOST array of `num_tracks` entries (the caller may free it when the call returns):
+ * track_to_slot[t] is the record of the pose row track t is written to, in [0, num_slots), or ACLHIP_TRACK_DROPPED: the track is not
+ * written at all. Refused with ACLHIP_ERROR_INVALID_ARGUMENT (the message names the first offending track): a slot >= num_slots, two
+ * tracks mapped to one slot, num_tracks == 0, num_slots == 0, null pointers. The table and the sorted list of UNMAPPED slots (slots of
+ * [0, num_slots) no track maps to; a dropped track maps to none) are uploaded on the context's own stream; only the calling thread
+ * waits. Handles are small numbers >= 1; 0 is the null handle. The device's map table is allocated once, at the first registration
+ * (ACLHIP_MAX_TRACK_MAPS records), and never moves: a captured hipGraph that names a map stays valid while other maps come and go.
+ * Identical maps are not shared: every registration has a device image of its own (a few hundred bytes). */
+typedef uint32_t aclhip_track_map;		/* handle returned by aclhip_register_track_map; 0 = none */
+#define ACLHIP_TRACK_DROPPED 0xFFFFFFFFu
+#define ACLHIP_MAX_TRACK_MAPS 16384u		/* live maps of one context, the null handle included */
+
+typedef struct aclhip_track_map_info
+{
+	uint32_t num_tracks;
+	uint32_t num_slots;
+	uint32_t num_mapped;					/* tracks with a slot */
+	uint32_t num_dropped;					/* tracks that are ACLHIP_TRACK_DROPPED */
+	uint32_t num_unmapped_slots;			/* num_slots - num_mapped */
+	uint32_t is_identity;					/* num_slots == num_tracks and track_to_slot[t] == t for every t */
+	uint32_t is_order_preserving;			/* the slots of the mapped tracks ascend with the track index (the common case: contiguous runs stay contiguous) */
+	uint32_t reserved;
+} aclhip_track_map_info;
+
+/* Host only (no context, no device): what registration checks and what aclhip_get_track_map_info reports. `message` (may be NULL,
+ * `message_capacity` bytes) receives the reason when the map is refused; `out_info` may be NULL. */
+aclhip_status aclhip_check_track_map(const uint32_t* track_to_slot, uint32_t num_tracks, uint32_t num_slots, aclhip_track_map_info* out_info,
+	char* message, uint32_t message_capacity);
+
+aclhip_status aclhip_register_track_map(aclhip_context* context, const uint32_t* track_to_slot, uint32_t num_tracks, uint32_t num_slots, aclhip_track_map* out_map);
+
+/* Stream ordered retirement with the guarantees of aclhip_unregister_clip: launches ALREADY ENQUEUED on the streams this context
+ * launched on still see the map (its record in the device table is cleared behind them, on a stream of the context's own); launches
+ * that execute later refuse the handle (every instance that names it is counted, its row untouched); the map's memory and its handle
+ * are recycled when both have happened. Nobody waits. */
+aclhip_status aclhip_unregister_track_map(aclhip_context* context, aclhip_track_map map);
+
+aclhip_status aclhip_get_track_map_info(const aclhip_context* context, aclhip_track_map map, aclhip_track_map_info* out_info);
+
+typedef struct aclhip_track_mapping
+{
+	aclhip_track_map map;					/* used for every instance when instance_maps is NULL */
+	const aclhip_track_map* instance_maps;	/* DEVICE [num_instances] or NULL: the map of instance i (the CALLER's instance index) */
+	const void* fill_pose;					/* DEVICE or NULL: one pose of num_slots records in the launch's layout, 16 byte aligned, shared by the launch */
+	uint32_t fill_unmapped;					/* 0: unmapped slots are left untouched; 1: written from fill_pose */
+	uint32_t reserved;
+} aclhip_track_mapping;
+
+/* aclhip_decompress_tracks_batch_out with a destination index per track (track_writer::write_*(track_index, value),
+ * core/track_writer.h). For instance i with clip c and map m: what the unmapped decode with the same `params` / `output` (may be
+ * NULL) stores in record t of the row is stored in record m[t] instead -- same bits, same layout (QVV48 / QVV40 / QV32). Everything
+ * `params` and `output` express keeps its meaning and stays indexed by TRACK: rounding and looping policies, default sub-track modes
+ * (a skipped default leaves its bytes untouched AT THE MAPPED SLOT), skip_tracks / mask_table (one byte per track),
+ * instance_track_counts (the first K tracks are decoded; their slots are their map's), rows.
+ *   The row holds num_slots records. The launch is shaped like the unmapped one (min(largest registered clip, records the stride
+ * holds) in pose windows of 104 tracks). The kernel refuses and counts (aclhip_get_rejected_instance_count; the row stays untouched)
+ * an instance whose clip the unmapped decode would refuse -- in particular a clip with more tracks than the stride holds records,
+ * whatever its map drops --, whose map handle is unknown or retired, whose map was made for another track count than its clip's, or whose
+ * num_slots records do not fit pose_stride_bytes. No instance writes outside its row, whatever handle the device array holds.
+ *   Unmapped slots (bones the clip does not animate): with fill_unmapped = 1 every slot of the instance's map that no track maps to is
+ * written from fill_pose -- whole records, whatever `output` skips -- by the same launch (the list is split between the instance's
+ * wavefronts), so the row leaves the kernel complete; tracks beyond an instance's track count are mapped, not filled. With
+ * fill_unmapped = 0 those bytes are left untouched (the caller filled the buffer once; only animated slots change per frame).
+ *   ACLHIP_ERROR_INVALID_ARGUMENT: mapping == NULL, a null map handle without instance_maps, fill_unmapped = 1 without a fill_pose,
+ * a fill_pose that is not 16 byte aligned.
+ *   What it costs (MI355X, 65 536 instances of the 100-bone clip, QVV48, tools/mapped_decode.py; DESIGN.md 4.8 has the table and the
+ * counters): the unmapped decode takes 52 us; the identity map 77 us; a map into 128 slots 141 us without the fill and 95 us WITH it -- rows
+ * written whole are cheaper than rows with holes, whose 64 byte granules are written in part. A RANDOM permutation into 128 slots costs what an
+ * order-preserving one does (142 us): for QVV48 poses of one window with nothing skipped the row is gathered out of LDS in slot order, so the
+ * permutation loses no write locality. Every other setting (poses of several windows, QVV40 / QV32, skips) stores scattered records, where a random
+ * permutation measured 297 us on the same batch. Decode + one scatter pass, what a caller did before, takes 285 / 296 / 382 / 346 us for the
+ * four cases: the mapped launch is 2.0 to 4.0 x faster than that, but it is not free.
+ *   Not mapped (out of scope here; the handle does not preclude them): instance lists (aclhip_decompress_tracks_list), the pose
+ * consumers (aclhip_decompress_poses_batch: object space needs the hierarchy in slot space), single track requests, scalar track
+ * lists, the host convenience forms. ACLHIP_DECODE_FAST is accepted and changes nothing. */
+aclhip_status aclhip_decompress_tracks_batch_mapped(aclhip_context* context, const aclhip_clip* clips, const float* sample_times, uint32_t num_instances,
+	const aclhip_decompress_params* params, const aclhip_output_desc* output, const aclhip_track_mapping* mapping, void* poses, uint64_t pose_stride_bytes, void* stream);
+
 /* Host only (no GPU work): a decode order for a batch that draws on many clips -- a permutation of [0, num_instances) for the
  * instance list `clips` (HOST array) under which every clip is decoded on ONE XCD (workgroup b of a launch runs on XCD b % 8,
  * each XCD has its own L2; a clip that straddles the boundary between two XCDs' shares is decoded on both), next to its other
@@ -494,11 +581,6 @@ aclhip_status aclhip_decompress_tracks_list(aclhip_context* context, aclhip_inst
  * ordered with the decodes) and how often the list has been (re-)ordered so far */
 aclhip_status aclhip_instance_list_get_order(aclhip_context* context, aclhip_instance_list list, const uint32_t** out_order, uint64_t* out_num_orderings);
 
-/* Replaces seek() + decompress_track(track_indices[i], writer) (decompress.h:172; decompress_track_v0 :1753-2050):
- * one 48 byte qvv per instance at (char*)transforms + i * 48. All pointers are DEVICE pointers.
- * Any order of requests is decoded; the ORDER decides what the launch fetches: 64 consecutive requests share a wavefront, and requests
- * of many clips are best bucketed by clip -- aclhip_order_track_requests_for_locality above gives the order (4 M requests over 256
- * clips: 173 us as drawn, 77 us sorted by clip = the time of one clip, 68 - 74 us in the library's order; profiles/r06_experiments.md 5b). */
 /* Host only (no GPU work): the order of a single track request list that draws on many clips -- a permutation of [0, num_requests)
  * for the request list `clips` (HOST array: the clip of every request) under which the requests are bucketed by clip (stable) and every
  * clip's requests run on ONE XCD (workgroup b of aclhip_decompress_track_batch takes requests 256 b .. 256 b + 255 and runs on XCD
@@ -508,6 +590,11 @@ aclhip_status aclhip_instance_list_get_order(aclhip_context* context, aclhip_ins
  * algorithmic bytes as drawn, 0.98 x in this order). */
 aclhip_status aclhip_order_track_requests_for_locality(const aclhip_clip* clips, uint32_t num_requests, uint32_t* out_order);
 
+/* Replaces seek() + decompress_track(track_indices[i], writer) (decompress.h:172; decompress_track_v0 :1753-2050):
+ * one 48 byte qvv per instance at (char*)transforms + i * 48. All pointers are DEVICE pointers.
+ * Any order of requests is decoded; the ORDER decides what the launch fetches: 64 consecutive requests share a wavefront, and requests
+ * of many clips are best bucketed by clip -- aclhip_order_track_requests_for_locality above gives the order (4 M requests over 256
+ * clips: 173 us as drawn, 77 us sorted by clip = the time of one clip, 68 - 74 us in the library's order; profiles/r06_experiments.md 5b). */
 aclhip_status aclhip_decompress_track_batch(aclhip_context* context, const aclhip_clip* clips, const float* sample_times, const uint32_t* track_indices,
 	uint32_t num_instances, const aclhip_decompress_params* params, void* transforms, void* stream);
 
