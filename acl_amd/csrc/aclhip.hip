@@ -52,6 +52,7 @@ namespace aclhip
 #include "../../tools/experiments/kernels_experiments.inl"		// round 3's slower variants (profiles/r03_experiments.md); not part of a default build
 #endif
 #include "kernels_consumers.inl"
+#include "kernels_skeleton.inl"
 #include "kernels_misc.inl"
 #include "kernels_scalar.inl"
 #include "kernels_track.inl"
@@ -72,4 +73,5 @@ using namespace aclhip;
 #include "host_track_maps.inl"
 #include "host_lists.inl"
 #include "host_consumers.inl"
+#include "host_skeletons.inl"
 #include "host_scalar_misc.inl"

@@ -86,6 +86,98 @@ namespace
 			out_step_end.push_back(uint32_t(out_transforms.size()));
 		}
 	}
+
+	// The device image of a hierarchy's walk schedules (clips: aclhip_set_clip_hierarchy; skeletons: aclhip_register_skeleton):
+	// [{offset of the schedule, its steps, its words, 0} for 1, 2, 4, 8 instances per workgroup: one 16 byte scalar load tells a wave
+	// all it needs to request the copy] then per schedule, 16 byte aligned and padded to whole 16 byte pieces (it travels to LDS by DMA):
+	// num_steps | words of this schedule | step_end[num_steps] | transform | parent << 16, in step order (16 bits each: the
+	// consumers' LDS images end at about 3400 transforms; every word of the copy a wave keeps in LDS costs residency)
+	// Returns the words of the longest of the four schedules.
+	uint32_t build_walk_schedule_image(const hierarchy_tree& tree, const uint32_t* parent_indices, uint32_t num_tracks, std::vector<uint32_t>& image)
+	{
+		image.assign(16, 0);
+		uint32_t max_schedule_words = 0;
+		for (uint32_t log2_instances = 0; log2_instances < 4; ++log2_instances)
+		{
+			std::vector<uint32_t> step_end, pairs;
+			schedule_hierarchy_walk(tree, num_tracks, 64u >> log2_instances, step_end, pairs);
+			for (uint32_t& pair : pairs)
+				pair |= parent_indices[pair] << 16;
+
+			const uint32_t num_steps = uint32_t(step_end.size());
+			const uint32_t header_words = 2 + num_steps;
+			const uint32_t schedule_words = align_to_u32(header_words + uint32_t(pairs.size()), 4);
+			const uint32_t offset = uint32_t(image.size());
+			image[log2_instances * 4 + 0] = offset;
+			image[log2_instances * 4 + 1] = num_steps;
+			image[log2_instances * 4 + 2] = schedule_words;
+			image.resize(size_t(offset) + schedule_words, 0);
+			image[offset + 0] = num_steps;
+			image[offset + 1] = schedule_words;
+			std::copy(step_end.begin(), step_end.end(), image.begin() + offset + 2);
+			std::copy(pairs.begin(), pairs.end(), image.begin() + offset + header_words);
+			max_schedule_words = std::max(max_schedule_words, schedule_words);
+		}
+		return max_schedule_words;
+	}
+
+	// One device image per distinct hierarchy (context->hierarchies): a clip or a skeleton whose hierarchy is already on the device shares
+	// that image. stage_hierarchy finds it or allocates and stages the upload of a new one (the caller finishes its uploads), then
+	// keep_hierarchy counts the new user -- or drop_hierarchy gives a new image back when the uploads failed. The registry lock is held.
+	struct staged_hierarchy
+	{
+		std::vector<uint32_t> canonical;		// the parent indices with every root spelled ACLHIP_NO_PARENT
+		uint32_t* d_image = nullptr;
+		bool is_shared = false;
+	};
+
+	// false: out of memory (d_image == nullptr) or the upload could not be staged
+	bool stage_hierarchy(aclhip_context* context, const uint32_t* parent_indices, uint32_t num_tracks, const std::vector<uint32_t>& image, size_t& staging_used, staged_hierarchy& out)
+	{
+		out.canonical.assign(parent_indices, parent_indices + num_tracks);
+		for (uint32_t i = 0; i < num_tracks; ++i)
+			if (i == 0 || parent_indices[i] == ACLHIP_NO_PARENT)
+				out.canonical[i] = ACLHIP_NO_PARENT;
+		// (first: what this recycles may be the very image looked for below -- its last user retired it a moment ago -- and recycling
+		// erases entries of the list the search walks. Round 3 searched first and could pick up a dangling entry: found by
+		// tests/test_gpu_lifetime.py once the timing of its launches changed)
+		collect_retired(context, false);
+
+		for (aclhip_context::hierarchy_image& candidate : context->hierarchies)
+			if (candidate.parents == out.canonical)
+			{
+				out.d_image = candidate.d_image;
+				out.is_shared = true;
+				return true;
+			}
+		// (a piece of a clip slab, uploaded on the context's copy stream: no allocation call and no copy that would stall the device)
+		out.d_image = reinterpret_cast<uint32_t*>(allocate_clip_memory(context, image.size() * sizeof(uint32_t)));
+		out.is_shared = false;
+		if (out.d_image == nullptr)
+			return false;
+		return stage_upload(context, out.d_image, image.data(), image.size() * sizeof(uint32_t), staging_used);
+	}
+
+	void keep_hierarchy(aclhip_context* context, staged_hierarchy& staged)
+	{
+		for (aclhip_context::hierarchy_image& candidate : context->hierarchies)
+			if (candidate.d_image == staged.d_image)
+			{
+				candidate.num_users++;
+				return;
+			}
+		aclhip_context::hierarchy_image created;
+		created.parents = std::move(staged.canonical);
+		created.d_image = staged.d_image;
+		created.num_users = 1;
+		context->hierarchies.push_back(std::move(created));
+	}
+
+	void drop_hierarchy(aclhip_context* context, const staged_hierarchy& staged)
+	{
+		if (!staged.is_shared && staged.d_image != nullptr)
+			free_clip_memory(context, staged.d_image);
+	}
 }
 
 extern "C" aclhip_status aclhip_plan_hierarchy_walk(const uint32_t* parent_indices, uint32_t num_tracks, uint32_t transforms_per_step, uint32_t* out_steps, uint32_t* out_num_steps)
@@ -159,86 +251,27 @@ extern "C" aclhip_status aclhip_set_clip_hierarchy(aclhip_context* context, aclh
 		uint32_t misplaced = 0;
 		if (!build_hierarchy_tree(parent_indices, num_tracks, tree, misplaced))
 			return fail(context, ACLHIP_ERROR_INVALID_ARGUMENT, "transform %u has parent %u: transforms must be sorted parent first", misplaced, parent_indices[misplaced]);
-		const auto is_root = [&](uint32_t i) { return i == 0 || parent_indices[i] == ACLHIP_NO_PARENT; };
-
-		// [{offset of the schedule, its steps, its words, 0} for 1, 2, 4, 8 instances per workgroup: one 16 byte scalar load tells a wave
-		// all it needs to request the copy] then per schedule, 16 byte aligned and padded to whole 16 byte pieces (it travels to LDS by DMA):
-		// num_steps | words of this schedule | step_end[num_steps] | transform | parent << 16, in step order (16 bits each: the
-		// consumers' LDS images end at about 3400 transforms; every word of the copy a wave keeps in LDS costs residency)
-		std::vector<uint32_t> image(16, 0);
-		uint32_t max_schedule_words = 0;
-		for (uint32_t log2_instances = 0; log2_instances < 4; ++log2_instances)
-		{
-			std::vector<uint32_t> step_end, pairs;
-			schedule_hierarchy_walk(tree, num_tracks, 64u >> log2_instances, step_end, pairs);
-			for (uint32_t& pair : pairs)
-				pair |= parent_indices[pair] << 16;
-
-			const uint32_t num_steps = uint32_t(step_end.size());
-			const uint32_t header_words = 2 + num_steps;
-			const uint32_t schedule_words = align_to_u32(header_words + uint32_t(pairs.size()), 4);
-			const uint32_t offset = uint32_t(image.size());
-			image[log2_instances * 4 + 0] = offset;
-			image[log2_instances * 4 + 1] = num_steps;
-			image[log2_instances * 4 + 2] = schedule_words;
-			image.resize(size_t(offset) + schedule_words, 0);
-			image[offset + 0] = num_steps;
-			image[offset + 1] = schedule_words;
-			std::copy(step_end.begin(), step_end.end(), image.begin() + offset + 2);
-			std::copy(pairs.begin(), pairs.end(), image.begin() + offset + header_words);
-			max_schedule_words = std::max(max_schedule_words, schedule_words);
-		}
+		std::vector<uint32_t> image;
+		const uint32_t max_schedule_words = build_walk_schedule_image(tree, parent_indices, num_tracks, image);
 
 		device_guard guard(context->device);
 
 		// an identical hierarchy (another clip of the same skeleton) is already on the device?
-		const std::vector<uint32_t> canonical = [&]()
-		{
-			std::vector<uint32_t> parents(parent_indices, parent_indices + num_tracks);
-			for (uint32_t i = 0; i < num_tracks; ++i)
-				if (is_root(i))
-					parents[i] = ACLHIP_NO_PARENT;
-			return parents;
-		}();
-		// (first: what this recycles may be the very image looked for below -- its last user retired it a moment ago -- and recycling
-		// erases entries of the list the search walks. Round 3 searched first and could pick up a dangling entry: found by
-		// tests/test_gpu_lifetime.py once the timing of its launches changed)
-		collect_retired(context, false);
-
-		aclhip_context::hierarchy_image* shared = nullptr;
-		for (aclhip_context::hierarchy_image& candidate : context->hierarchies)
-			if (candidate.parents == canonical)
-				shared = &candidate;
-		uint32_t* d_hierarchy = shared != nullptr ? shared->d_image : nullptr;
+		staged_hierarchy staged;
 		size_t staging_used = 0;
-		bool uploaded = true;
-		if (shared == nullptr)
-		{
-			// (a piece of a clip slab, uploaded on the context's copy stream: no allocation call and no copy that would stall the device)
-			d_hierarchy = reinterpret_cast<uint32_t*>(allocate_clip_memory(context, image.size() * sizeof(uint32_t)));
-			if (d_hierarchy == nullptr)
-				return fail(context, ACLHIP_ERROR_OUT_OF_MEMORY, "allocating %zu bytes for the hierarchy failed", image.size() * sizeof(uint32_t));
-			uploaded = stage_upload(context, d_hierarchy, image.data(), image.size() * sizeof(uint32_t), staging_used);
-		}
+		bool uploaded = stage_hierarchy(context, parent_indices, num_tracks, image, staging_used, staged);
+		if (staged.d_image == nullptr)
+			return fail(context, ACLHIP_ERROR_OUT_OF_MEMORY, "allocating %zu bytes for the hierarchy failed", image.size() * sizeof(uint32_t));
+		uint32_t* d_hierarchy = staged.d_image;
 		// launches in flight may still walk the hierarchy that is being replaced: it is retired, not freed (see retire())
 		uploaded = uploaded && stage_upload(context, reinterpret_cast<uint8_t*>(context->d_clips + clip) + offsetof(device_clip, hierarchy), &d_hierarchy, sizeof(d_hierarchy), staging_used)
 			&& finish_uploads(context);
 		if (!uploaded)
 		{
-			if (shared == nullptr)
-				free_clip_memory(context, d_hierarchy);
+			drop_hierarchy(context, staged);
 			return fail(context, ACLHIP_ERROR_DEVICE, "uploading the hierarchy failed");
 		}
-		if (shared != nullptr)
-			shared->num_users++;
-		else
-		{
-			aclhip_context::hierarchy_image created;
-			created.parents = canonical;
-			created.d_image = d_hierarchy;
-			created.num_users = 1;
-			context->hierarchies.push_back(std::move(created));
-		}
+		keep_hierarchy(context, staged);
 		if (entry.d_hierarchy != nullptr)
 		{
 			aclhip_context::retired_item item;
@@ -257,8 +290,47 @@ extern "C" aclhip_status aclhip_set_clip_hierarchy(aclhip_context* context, aclh
 
 namespace
 {
+	// the skeleton space kernels: a function of its own, like mapped_pose_kernel_of. The instantiations launch_consumers selects for the
+	// unmapped launch, minus the rotation | translation images and ACLHIP_CONSUMERS_FAST.
+	typedef void (*skeleton_pose_kernel)(const device_clip*, uint32_t, const uint32_t*, const float*, uint32_t, decode_params, consumer_params, uint8_t*, uint64_t, uint32_t, uint32_t, uint32_t, unsigned long long*, skeleton_launch);
+
+	template<bool kObjectSpace, bool kBlend>
+	skeleton_pose_kernel skeleton_pose_kernel_of_base(uint32_t base_kind, bool mirrored)
+	{
+		// rtm::qvv_mul's matrix route only where transforms are multiplied: object space, or the relative format (a base buffer, a second
+		// wave's image); a caller's base buffer always has it
+		switch (base_kind)
+		{
+		case k_consumer_base_none:
+			if constexpr (kObjectSpace)
+				return mirrored ? decompress_poses_skeleton_kernel<true, k_consumer_base_none, true, kBlend> : decompress_poses_skeleton_kernel<true, k_consumer_base_none, false, kBlend>;
+			return decompress_poses_skeleton_kernel<false, k_consumer_base_none, false, kBlend>;
+		case k_consumer_base_buffer:
+			return decompress_poses_skeleton_kernel<kObjectSpace, k_consumer_base_buffer, true, kBlend>;
+		case k_consumer_base_second_wave:
+			return mirrored ? decompress_poses_skeleton_kernel<kObjectSpace, k_consumer_base_second_wave, true, kBlend> : decompress_poses_skeleton_kernel<kObjectSpace, k_consumer_base_second_wave, false, kBlend>;
+		default:
+			if constexpr (!kBlend)
+			{
+				if constexpr (kObjectSpace)
+					return mirrored ? decompress_poses_skeleton_kernel<true, k_consumer_base_fused, true, false> : decompress_poses_skeleton_kernel<true, k_consumer_base_fused, false, false>;
+				return decompress_poses_skeleton_kernel<false, k_consumer_base_fused, false, false>;
+			}
+			return nullptr;		// (a blend's base clip is never fused)
+		}
+	}
+
+	skeleton_pose_kernel skeleton_pose_kernel_of(bool object_space, uint32_t base_kind, bool mirrored, bool blend)
+	{
+		if (object_space)
+			return blend ? skeleton_pose_kernel_of_base<true, true>(base_kind, mirrored) : skeleton_pose_kernel_of_base<true, false>(base_kind, mirrored);
+		return blend ? skeleton_pose_kernel_of_base<false, true>(base_kind, mirrored) : skeleton_pose_kernel_of_base<false, false>(base_kind, mirrored);
+	}
+
+	// `mapping` (aclhip_decompress_poses_batch_mapped): skeleton space -- the launch is shaped by its rows alone (pose_stride_bytes / 48
+	// slots), the skeleton kernels take the mapping as their trailing argument
 	aclhip_status launch_consumers(aclhip_context* context, const aclhip_clip* clips, const float* sample_times, uint32_t num_instances,
-		const decode_params& params, const aclhip_pose_consumers& consumers, void* poses, uint64_t pose_stride_bytes, hipStream_t stream)
+		const decode_params& params, const aclhip_pose_consumers& consumers, void* poses, uint64_t pose_stride_bytes, hipStream_t stream, const skeleton_launch* mapping = nullptr)
 	{
 		if (consumers.additive_format > ACLHIP_ADDITIVE_ADDITIVE1)
 			return fail(context, ACLHIP_ERROR_INVALID_ARGUMENT, "unknown additive format %u", consumers.additive_format);
@@ -280,6 +352,19 @@ namespace
 			return fail(context, ACLHIP_ERROR_INVALID_ARGUMENT, "pose consumers take the track_writer's default sub-track modes, no per track rounding, normalization != always");
 
 		std::shared_lock<std::shared_mutex> lock(context->mutex);		// see launch_tracks
+		skeleton_launch device_mapping = {};
+		if (mapping != nullptr)
+		{
+			if (context->d_skeletons == nullptr)
+				return fail(context, ACLHIP_ERROR_INVALID_ARGUMENT, "no skeleton was ever registered with this context");
+			if (context->d_track_maps == nullptr)
+				return fail(context, ACLHIP_ERROR_INVALID_ARGUMENT, "no track map was ever registered with this context");
+			device_mapping = *mapping;
+			device_mapping.skeletons = context->d_skeletons;
+			device_mapping.num_skeletons = ACLHIP_MAX_SKELETONS;
+			device_mapping.maps = context->d_track_maps;
+			device_mapping.num_maps = ACLHIP_MAX_TRACK_MAPS;
+		}
 		note_launch_stream(context, stream);
 
 		// one wave per instance, the whole pose (its base, its hierarchy) in LDS; as many instances per workgroup (a power of two, at
@@ -287,10 +372,11 @@ namespace
 		// No clip with a scale other than 1 registered, no base to combine with: every scale of every pose is 1, in local and in object
 		// space -- the LDS images hold rotation | translation (32 of a transform's 48 bytes: half as many poses again per CU) and the
 		// scales are written on the way out
-		const bool unit_scale = !has_base && !blend && consumers.object_space != 0 && context->num_scaled_clips == 0 && path_knob("ACLHIP_CONSUMER_KEEP_SCALE") == nullptr;
+		const bool unit_scale = mapping == nullptr && !has_base && !blend && consumers.object_space != 0 && context->num_scaled_clips == 0 && path_knob("ACLHIP_CONSUMER_KEEP_SCALE") == nullptr;
 		// (sized for the BATCH like every pose launch: no pose of it is larger than its row, pose_launch_shape_of in host_launch.inl --
 		// one 3 500-bone asset in the registry does not take object space away from the 100-bone characters)
-		const uint32_t batch_quads = batch_pose_quads(context, ACLHIP_LAYOUT_QVV48, pose_stride_bytes);
+		// (skeleton space: the slots of a row, whatever clips are registered -- a clip may have more tracks than the skeleton has bones)
+		const uint32_t batch_quads = mapping != nullptr ? uint32_t(std::min<uint64_t>(pose_stride_bytes / 48, 0xFFFFu)) * 3u : batch_pose_quads(context, ACLHIP_LAYOUT_QVV48, pose_stride_bytes);
 		const uint32_t image_quads = unit_scale ? batch_quads / 3 * 2 : batch_quads;
 		// exactly the transforms a pose row holds (or the largest registered clip has), not a quad more: the kernel's "does the pose fit
 		// its image" test is also its "does the pose fit its row" test (every quad is addressed on its own: no granularity needed)
@@ -307,7 +393,7 @@ namespace
 		static const size_t lds_pad = []() { const char* value = lab_knob("ACLHIP_CONSUMER_LDS_PAD"); return value != nullptr ? size_t(std::atol(value)) & ~size_t(15) : size_t(16); }();
 		const size_t lds_bytes_per_instance = size_t(lds_quads_per_image) * 16 * (two_waves ? 2 : 1) + lds_pad;
 		// a walk schedule of T transforms: 2 words + a step end per step + a pair per transform with a parent, at most 2 + 2 T words
-		const uint32_t lds_schedule_words = consumers.object_space != 0 ? align_to_u32(std::max<uint32_t>(std::min<uint32_t>(context->max_hierarchy_words, 2 + 2 * (batch_quads / 3) + 3), 4), 4) : 0;
+		const uint32_t lds_schedule_words = consumers.object_space != 0 ? align_to_u32(std::max<uint32_t>(std::min<uint32_t>(mapping != nullptr ? context->max_skeleton_hierarchy_words : context->max_hierarchy_words, 2 + 2 * (batch_quads / 3) + 3), 4), 4) : 0;
 		const size_t lds_schedule_bytes = size_t(lds_schedule_words) * sizeof(uint32_t);
 		// what a workgroup may ask for on top of the kernel's static words (consumer_walk_slots, kernels_consumers.inl)
 		constexpr size_t k_lds_bytes = 160 * 1024 - ((sizeof(consumer_walk_slots) + 127) / 128) * 128;
@@ -340,7 +426,8 @@ namespace
 		typedef void (*consumer_kernel)(const device_clip*, uint32_t, const uint32_t*, const float*, uint32_t, decode_params, consumer_params, uint8_t*, uint64_t, uint32_t, uint32_t, uint32_t, unsigned long long*);
 		// rtm::qvv_mul's matrix route (negative scales) is compiled into the launches that can meet one: a registered clip whose scale
 		// sub-tracks may decode below zero, or a base the library knows nothing about (a caller's pose buffer)
-		const bool mirrored = context->num_negative_scale_clips != 0 || (has_base && !base_is_clip);
+		// (skeleton space: the reference pose fills slots -- like a clip whose scales registration has looked at)
+		const bool mirrored = context->num_negative_scale_clips != 0 || (has_base && !base_is_clip) || (mapping != nullptr && context->num_negative_scale_skeletons != 0);
 		static const consumer_kernel kernels[2][2][4] =
 		{
 			{
@@ -374,7 +461,7 @@ namespace
 			},
 		};
 		// ACLHIP_CONSUMERS_FAST: object space launches without a blend, in the hardware's 1 ulp arithmetic (include/aclhip.h)
-		const bool fast = (consumers.flags & ACLHIP_CONSUMERS_FAST) != 0 && consumers.object_space != 0 && !blend;
+		const bool fast = mapping == nullptr && (consumers.flags & ACLHIP_CONSUMERS_FAST) != 0 && consumers.object_space != 0 && !blend;
 		static const consumer_kernel fast_kernels[2][4] =
 		{
 			{ decompress_poses_consumer_kernel<true, k_consumer_base_none, false, false, false, true>, decompress_poses_consumer_kernel<true, k_consumer_base_buffer, false, true, false, true>,
@@ -385,6 +472,17 @@ namespace
 		const consumer_kernel kernel = fast ? (unit_scale ? decompress_poses_consumer_kernel<true, k_consumer_base_none, true, false, false, true> : fast_kernels[mirrored ? 1 : 0][base_kind])
 			: unit_scale ? decompress_poses_consumer_kernel<true, k_consumer_base_none, true, false>
 			: (blend ? blend_kernels[mirrored ? 1 : 0][consumers.object_space != 0 ? 1 : 0][base_kind] : kernels[mirrored ? 1 : 0][consumers.object_space != 0 ? 1 : 0][base_kind]);
+		if (mapping != nullptr)
+		{
+			const skeleton_pose_kernel skeleton_kernel = skeleton_pose_kernel_of(consumers.object_space != 0, base_kind, mirrored, blend);
+			if (lds_bytes > 64 * 1024 - 128)
+				ACLHIP_CHECK_HIP(context, hipFuncSetAttribute(reinterpret_cast<const void*>(skeleton_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, int(k_lds_bytes)));
+			hipLaunchKernelGGL(skeleton_kernel, dim3(num_blocks), dim3(waves_per_block * k_wave_size), lds_bytes, stream,
+				context->d_clips, context->d_clips_capacity, clips, sample_times, num_instances, params, device_consumers,
+				static_cast<uint8_t*>(poses), pose_stride_bytes, lds_quads_per_image, uint32_t(lds_bytes_per_instance), log2_instances_per_block | (lds_schedule_words << 8), context->d_rejected, device_mapping);
+			ACLHIP_CHECK_HIP(context, hipGetLastError());
+			return ACLHIP_OK;
+		}
 		if (lds_bytes > 64 * 1024 - 128)		// above the default limit
 			ACLHIP_CHECK_HIP(context, hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, int(k_lds_bytes)));
 		hipLaunchKernelGGL(kernel, dim3(num_blocks), dim3(waves_per_block * k_wave_size), lds_bytes, stream,

@@ -77,6 +77,14 @@ struct aclhip_context
 	std::vector<track_map_entry> track_maps;
 	std::vector<uint32_t> free_map_slots;
 	device_track_map* d_track_maps = nullptr;
+	// Skeletons (aclhip_register_skeleton, host_skeletons.inl): what the slot space of a set of track maps means. The same lifetime:
+	// one table of ACLHIP_MAX_SKELETONS records made at the first registration, record 0 never handed out.
+	struct skeleton_entry { bool in_use = false; aclhip_skeleton_info info = {}; uint8_t* device_memory = nullptr; uint32_t* d_hierarchy = nullptr; bool negative_scale = false; };
+	std::vector<skeleton_entry> skeletons;
+	std::vector<uint32_t> free_skeleton_slots;
+	device_skeleton* d_skeletons = nullptr;
+	uint32_t num_negative_scale_skeletons = 0;		// live skeletons whose reference pose holds a negative scale (see num_negative_scale_clips)
+	uint32_t max_skeleton_hierarchy_words = 0;		// largest walk schedule a skeleton was ever registered with (a longer one is walked from global memory)
 	device_clip* d_clips = nullptr;
 	uint32_t d_clips_capacity = 0;
 	unsigned long long* d_rejected = nullptr;	// [0] instances the kernels refused, [1] transforms of the pose consumers that met a negative scale
@@ -119,6 +127,7 @@ struct aclhip_context
 		uint32_t* hierarchy = nullptr;				// a walk schedule image (shared images are reference counted)
 		uint32_t slot = ACLHIP_INVALID_HANDLE;		// clip handle that becomes reusable
 		uint32_t map_slot = ACLHIP_INVALID_HANDLE;	// track map handle that becomes reusable
+		uint32_t skeleton_slot = ACLHIP_INVALID_HANDLE;	// skeleton handle that becomes reusable
 		uint8_t* database_memory[6] = { nullptr, nullptr, nullptr, nullptr, nullptr, nullptr };		// hipMalloc'ed pieces of a database
 		uint8_t* database_pinned[4] = { nullptr, nullptr, nullptr, nullptr };		// bulk data x 2, patch mirrors x 2
 		void* device_memory = nullptr;				// any other hipMalloc'ed piece
@@ -419,6 +428,8 @@ namespace
 				context->free_slots.push_back(item.slot);
 			if (item.map_slot != ACLHIP_INVALID_HANDLE)
 				context->free_map_slots.push_back(item.map_slot);
+			if (item.skeleton_slot != ACLHIP_INVALID_HANDLE)
+				context->free_skeleton_slots.push_back(item.skeleton_slot);
 			for (uint8_t* memory : item.database_memory)
 				if (memory != nullptr)
 					(void)hipFree(memory);
@@ -1014,6 +1025,8 @@ extern "C" void aclhip_destroy(aclhip_context* context)
 			(void)hipFree(context->d_rejected);
 		if (context->d_track_maps != nullptr)
 			(void)hipFree(context->d_track_maps);
+		if (context->d_skeletons != nullptr)
+			(void)hipFree(context->d_skeletons);
 		for (const aclhip_context::order_scratch& scratch : context->order_scratches)
 		{
 			(void)hipFree(scratch.bins);

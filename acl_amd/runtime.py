@@ -43,6 +43,7 @@ EXPORTED_SYMBOLS = [
     "aclhip_get_clip_metadata_info", "aclhip_get_clip_parent_indices", "aclhip_get_clip_track_descriptions", "aclhip_set_clip_hierarchy_from_metadata", "aclhip_read_clip_metadata",
     "aclhip_order_track_requests_device", "aclhip_decompress_track_batch_rows",
     "aclhip_check_track_map", "aclhip_register_track_map", "aclhip_unregister_track_map", "aclhip_get_track_map_info", "aclhip_decompress_tracks_batch_mapped",
+    "aclhip_check_skeleton", "aclhip_register_skeleton", "aclhip_unregister_skeleton", "aclhip_get_skeleton_info", "aclhip_decompress_poses_batch_mapped",
 ]
 
 
@@ -91,6 +92,23 @@ class TrackMapping(ctypes.Structure):
     ]
 
 
+class SkeletonInfo(ctypes.Structure):
+    """aclhip_skeleton_info"""
+    _fields_ = [
+        ("num_bones", ctypes.c_uint32), ("has_hierarchy", ctypes.c_uint32), ("num_roots", ctypes.c_uint32), ("depth", ctypes.c_uint32),
+        ("walk_steps", ctypes.c_uint32), ("has_negative_scale", ctypes.c_uint32), ("reserved", ctypes.c_uint32 * 2),
+    ]
+
+
+class PoseMapping(ctypes.Structure):
+    """aclhip_pose_mapping"""
+    _fields_ = [
+        ("skeleton", ctypes.c_uint32), ("instance_skeletons", ctypes.c_void_p), ("map", ctypes.c_uint32), ("instance_maps", ctypes.c_void_p),
+        ("blend_maps", ctypes.c_void_p), ("base_maps", ctypes.c_void_p), ("reserved", ctypes.c_uint32 * 2),
+    ]
+
+
+MAX_SKELETONS = 1024        # ACLHIP_MAX_SKELETONS
 TRACK_DROPPED = 0xFFFFFFFF  # ACLHIP_TRACK_DROPPED
 MAX_TRACK_MAPS = 16384      # ACLHIP_MAX_TRACK_MAPS
 ABI_VERSION = 6             # ACLHIP_ABI_VERSION: the struct layouts mirrored above
@@ -261,8 +279,31 @@ def load_library():
     lib.aclhip_unregister_track_map.argtypes = [vp, u32]
     lib.aclhip_get_track_map_info.argtypes = [vp, u32, ctypes.POINTER(TrackMapInfo)]
     lib.aclhip_decompress_tracks_batch_mapped.argtypes = [vp, vp, vp, u32, pparams, poutput, ctypes.POINTER(TrackMapping), vp, u64, vp]
+    lib.aclhip_check_skeleton.argtypes = [vp, vp, u32, ctypes.POINTER(SkeletonInfo), ctypes.c_char_p, u32]
+    lib.aclhip_register_skeleton.argtypes = [vp, vp, vp, u32, ctypes.POINTER(u32)]
+    lib.aclhip_unregister_skeleton.argtypes = [vp, u32]
+    lib.aclhip_get_skeleton_info.argtypes = [vp, u32, ctypes.POINTER(SkeletonInfo)]
+    lib.aclhip_decompress_poses_batch_mapped.argtypes = [vp, vp, vp, u32, pparams, ctypes.POINTER(PoseConsumers), ctypes.POINTER(PoseMapping), vp, u64, vp]
     _lib = lib
     return lib
+
+
+def _skeleton_arrays(parent_indices, reference_pose, num_bones):
+    parents = np.ascontiguousarray(parent_indices, dtype=np.uint32) if parent_indices is not None else None
+    pose = np.ascontiguousarray(reference_pose, dtype=np.float32) if reference_pose is not None else None
+    if num_bones is None:
+        num_bones = pose.size // 12 if pose is not None else (parents.size if parents is not None else 0)
+    return parents, pose, int(num_bones)
+
+
+def check_skeleton(parent_indices, reference_pose, num_bones=None):
+    """Host only validation of a skeleton (no GPU needed): what aclhip_register_skeleton checks. parent_indices may be None (local space
+    only), reference_pose is float32 [num_bones, 12]. Returns (status, message, SkeletonInfo)."""
+    parents, pose, num_bones = _skeleton_arrays(parent_indices, reference_pose, num_bones)
+    message, info = ctypes.create_string_buffer(256), SkeletonInfo()
+    status = load_library().aclhip_check_skeleton(parents.ctypes.data if parents is not None else None, pose.ctypes.data if pose is not None else None,
+                                                  num_bones, ctypes.byref(info), message, 256)
+    return status, message.value.decode(), info
 
 
 def check_track_map(track_to_slot, num_slots):
@@ -590,6 +631,90 @@ class Context:
         mapping.fill_unmapped = 1 if fill_pose is not None else 0
         self._check(self._lib.aclhip_decompress_tracks_batch_mapped(self._handle, clips.data_ptr(), sample_times.data_ptr(), int(clips.numel()), ctypes.byref(params),
                                                                    ctypes.byref(output) if output is not None else None, ctypes.byref(mapping), poses.data_ptr(), int(pose_stride_bytes), stream))
+
+    # ---- skeletons: the pose consumers in skeleton space ----
+    def register_skeleton(self, parent_indices, reference_pose, num_bones=None):
+        """parent_indices: host array in slot order or None (local space only); reference_pose: float32 [num_bones, 12]. Returns the handle (>= 1)."""
+        parents, pose, num_bones = _skeleton_arrays(parent_indices, reference_pose, num_bones)
+        handle = ctypes.c_uint32(0)
+        self._check(self._lib.aclhip_register_skeleton(self._handle, parents.ctypes.data if parents is not None else None, pose.ctypes.data if pose is not None else None,
+                                                       num_bones, ctypes.byref(handle)))
+        return handle.value
+
+    def unregister_skeleton(self, skeleton):
+        self._check(self._lib.aclhip_unregister_skeleton(self._handle, skeleton))
+
+    def skeleton_info(self, skeleton):
+        info = SkeletonInfo()
+        self._check(self._lib.aclhip_get_skeleton_info(self._handle, skeleton, ctypes.byref(info)))
+        return info
+
+    def decompress_poses_batch_mapped(self, clips_ptr, times_ptr, num_instances, poses_ptr, pose_stride_bytes, consumers, mapping, params=None, stream=None):
+        """aclhip_decompress_poses_batch_mapped; `consumers` (PoseConsumers) and `mapping` (PoseMapping) hold device addresses."""
+        params = params if params is not None else default_params()
+        self._check(self._lib.aclhip_decompress_poses_batch_mapped(self._handle, clips_ptr, times_ptr, num_instances, ctypes.byref(params), ctypes.byref(consumers),
+                                                                  ctypes.byref(mapping) if mapping is not None else None, poses_ptr, pose_stride_bytes, stream))
+
+    def decompress_poses_mapped(self, clips, sample_times, skeletons, maps, num_bones, additive_format=ADDITIVE_NONE, object_space=False, base_clips=None,
+                                base_sample_times=None, base_maps=None, base_poses=None, params=None, out=None, instance_rounding=None, instance_looping=None,
+                                blend_clips=None, blend_sample_times=None, blend_maps=None, blend_weights=None, flags=0):
+        """Host arrays in, host poses out, like decompress_poses: float32 [n, num_bones, 12] in skeleton order. `skeletons` and `maps` are one
+        handle or an array of n; blend_maps [n, K - 1] and base_maps [n] go with blend_clips and base_clips. The library has no host form of
+        this launch: the arrays are staged through torch tensors on the context's device and the call is synchronous."""
+        import torch
+        device = torch.device("cuda", self.device_index)
+        keep = []
+
+        def upload(array, dtype):
+            tensor = torch.from_numpy(np.ascontiguousarray(array, dtype=dtype).view(np.int32 if dtype == np.uint32 else dtype)).to(device)
+            keep.append(tensor)
+            return tensor.data_ptr()
+
+        clips = np.ascontiguousarray(clips, dtype=np.uint32)
+        n = clips.size
+        if out is None:
+            out = np.zeros((n, num_bones, 12), dtype=np.float32)
+        params = params if params is not None else default_params()
+        if instance_rounding is not None:
+            params.instance_rounding_policies = upload(instance_rounding, np.uint8)
+        if instance_looping is not None:
+            params.instance_looping_policies = upload(instance_looping, np.uint8)
+        consumers, mapping = PoseConsumers(), PoseMapping()
+        consumers.additive_format = int(additive_format)
+        consumers.object_space = 1 if object_space else 0
+        consumers.flags = int(flags)
+        if np.ndim(skeletons) == 0:
+            mapping.skeleton = int(skeletons)
+        else:
+            mapping.instance_skeletons = upload(skeletons, np.uint32)
+        if np.ndim(maps) == 0:
+            mapping.map = int(maps)
+        else:
+            mapping.instance_maps = upload(maps, np.uint32)
+        if base_clips is not None:
+            consumers.base_clips = upload(base_clips, np.uint32)
+            consumers.base_sample_times = upload(base_sample_times, np.float32)
+            if base_maps is not None:
+                mapping.base_maps = upload(base_maps, np.uint32)
+        if base_poses is not None:
+            base_poses = np.ascontiguousarray(base_poses, dtype=np.float32)
+            consumers.base_poses = upload(base_poses, np.float32)
+            consumers.base_pose_stride_bytes = base_poses.strides[0] if base_poses.ndim == 3 else num_bones * 48
+        if blend_weights is not None:
+            blend_weights = np.ascontiguousarray(blend_weights, dtype=np.float32).reshape(n, -1)
+            consumers.num_blend_clips = blend_weights.shape[1]
+            consumers.blend_clips = upload(blend_clips, np.uint32)
+            consumers.blend_sample_times = upload(blend_sample_times, np.float32)
+            consumers.blend_weights = upload(blend_weights, np.float32)
+            if blend_maps is not None:
+                mapping.blend_maps = upload(blend_maps, np.uint32)
+        d_out = torch.from_numpy(out.reshape(n, -1)).to(device)
+        stream = torch.cuda.current_stream(device)
+        self.decompress_poses_batch_mapped(upload(clips, np.uint32), upload(sample_times, np.float32), n, d_out.data_ptr(), num_bones * 48, consumers, mapping,
+                                           params=params, stream=stream.cuda_stream)
+        stream.synchronize()
+        out[...] = d_out.cpu().numpy().reshape(out.shape)
+        return out
 
     def order_instances_for_locality(self, clips):
         """Host only: the permutation aclhip_order_instances_for_locality computes for the instance list `clips`."""

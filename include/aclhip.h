@@ -201,7 +201,8 @@ const char* aclhip_last_error_message(const aclhip_context* context);
  * 5: aclhip_decompress_params::instance_looping_policies, track_rounding_table, instance_rounding_tables, track_rounding_stride, aclhip_output_desc::mask_table, instance_masks, instance_track_counts, mask_stride;
  * 6: ACLHIP_DEFAULT_BIND_POSE, aclhip_clip_metadata_info; ACLHIP_ERROR_UNSUPPORTED_FORMAT no longer covers the full-precision formats;
  * track maps -- aclhip_track_map_info, aclhip_track_mapping and their entry points -- were ADDED without a bump: no existing struct or
- * entry point changed shape, so a caller built against the earlier header 6 hands over nothing of another shape).
+ * entry point changed shape, so a caller built against the earlier header 6 hands over nothing of another shape; the same goes for
+ * skeletons -- aclhip_skeleton_info, aclhip_pose_mapping and their entry points).
  * A caller compiled against another header would hand over structs of another shape; aclhip_abi_version() says what the LIBRARY was
  * built with, and the C++ mirror (aclhip.hpp) refuses to create a context when the two differ. */
 #define ACLHIP_ABI_VERSION 6u
@@ -487,9 +488,9 @@ typedef struct aclhip_track_mapping
  * permutation loses no write locality. Every other setting (poses of several windows, QVV40 / QV32, skips) stores scattered records, where a random
  * permutation measured 297 us on the same batch. Decode + one scatter pass, what a caller did before, takes 285 / 296 / 382 / 346 us for the
  * four cases: the mapped launch is 2.0 to 4.0 x faster than that, but it is not free.
- *   Not mapped (out of scope here; the handle does not preclude them): instance lists (aclhip_decompress_tracks_list), the pose
- * consumers (aclhip_decompress_poses_batch: object space needs the hierarchy in slot space), single track requests, scalar track
- * lists, the host convenience forms. ACLHIP_DECODE_FAST is accepted and changes nothing. */
+ *   The pose consumers take maps through aclhip_decompress_poses_batch_mapped (skeletons, below). Still not mapped (the handle does not
+ * preclude them): instance lists (aclhip_decompress_tracks_list), single track requests, scalar track lists, the host convenience
+ * forms. ACLHIP_DECODE_FAST is accepted and changes nothing. */
 aclhip_status aclhip_decompress_tracks_batch_mapped(aclhip_context* context, const aclhip_clip* clips, const float* sample_times, uint32_t num_instances,
 	const aclhip_decompress_params* params, const aclhip_output_desc* output, const aclhip_track_mapping* mapping, void* poses, uint64_t pose_stride_bytes, void* stream);
 
@@ -773,6 +774,93 @@ aclhip_status aclhip_decompress_poses_batch(aclhip_context* context, const aclhi
 /* Same with host arrays (clips, times, base clips / times / poses, output): staged through temporary device buffers, synchronous. */
 aclhip_status aclhip_decompress_poses_host(aclhip_context* context, const aclhip_clip* clips, const float* sample_times, uint32_t num_instances,
 	const aclhip_decompress_params* params, const aclhip_pose_consumers* consumers, void* poses, uint64_t pose_stride_bytes);
+
+/* ---- skeletons: the pose consumers in skeleton space ------------------------------------------------
+ * A registered SKELETON is what the slot space of a set of track maps means: num_bones bones, their parents in slot order and a
+ * reference (bind) pose of num_bones QVV48 records. With it the pose consumers work on clips that carry different tracks in different
+ * orders: a walk cycle, an upper-body wave and a facial clip of one character are blended, layered additively and taken to object
+ * space in ONE launch, each through its own track map, and the row leaves the kernel complete and in skeleton order.
+ *
+ * aclhip_register_skeleton: `parent_indices` (HOST, num_bones entries, or NULL) follows the rules of aclhip_set_clip_hierarchy --
+ * parents first, bone 0 is a root, ACLHIP_NO_PARENT marks further roots -- and gets the same walk schedule (skeletons and clips with
+ * identical hierarchies share one device image). A skeleton registered with NULL serves local space launches only. `reference_pose`
+ * (HOST, num_bones x 48 bytes: rotation xyzw | translation xyz, pad | scale xyz, pad; the pads are stored as 0) must be finite.
+ * Refused with ACLHIP_ERROR_INVALID_ARGUMENT before any device call (the message names the first offending bone): num_bones == 0 or
+ * > 0xFFFF, a null reference pose, a bone ahead of its parent, a value that is not finite. Lifetime is a track map's: the device table
+ * (ACLHIP_MAX_SKELETONS records) is allocated at the first registration and never moves, so a captured hipGraph that names a
+ * skeleton stays valid while others come and go; handle 0 is null; uploads go on the context's own stream; unregistration is stream
+ * ordered (launches already enqueued still see the skeleton, later ones refuse it) and nobody waits. */
+typedef uint32_t aclhip_skeleton;		/* handle returned by aclhip_register_skeleton; 0 = none */
+#define ACLHIP_MAX_SKELETONS 1024u		/* live skeletons of one context, the null handle included */
+
+typedef struct aclhip_skeleton_info
+{
+	uint32_t num_bones;
+	uint32_t has_hierarchy;				/* 0: registered without parent indices (local space only) */
+	uint32_t num_roots;					/* 0 without hierarchy */
+	uint32_t depth;						/* bones on the longest chain from a root to a leaf; 0 without hierarchy */
+	uint32_t walk_steps;				/* steps of the object space walk at 16 transforms per step (aclhip_plan_hierarchy_walk); 0 without hierarchy */
+	uint32_t has_negative_scale;		/* the reference pose holds a scale below zero (launches that multiply transforms then carry rtm::qvv_mul's matrix route) */
+	uint32_t reserved[2];
+} aclhip_skeleton_info;
+
+/* Host only (no context, no device): what registration checks and what aclhip_get_skeleton_info reports. `message` (may be NULL,
+ * `message_capacity` bytes) receives the reason when the skeleton is refused; `out_info` may be NULL. */
+aclhip_status aclhip_check_skeleton(const uint32_t* parent_indices, const void* reference_pose, uint32_t num_bones,
+	aclhip_skeleton_info* out_info, char* message, uint32_t message_capacity);
+
+aclhip_status aclhip_register_skeleton(aclhip_context* context, const uint32_t* parent_indices, const void* reference_pose,
+	uint32_t num_bones, aclhip_skeleton* out_skeleton);
+aclhip_status aclhip_unregister_skeleton(aclhip_context* context, aclhip_skeleton skeleton);
+aclhip_status aclhip_get_skeleton_info(const aclhip_context* context, aclhip_skeleton skeleton, aclhip_skeleton_info* out_info);
+
+typedef struct aclhip_pose_mapping
+{
+	aclhip_skeleton skeleton;					/* for every instance when instance_skeletons is NULL */
+	const aclhip_skeleton* instance_skeletons;	/* DEVICE [num_instances] or NULL */
+	aclhip_track_map map;						/* the map of clips[i], for every instance when instance_maps is NULL */
+	const aclhip_track_map* instance_maps;		/* DEVICE [num_instances] or NULL */
+	const aclhip_track_map* blend_maps;			/* DEVICE [num_instances * (K - 1)], laid out like blend_clips; required when K > 1 */
+	const aclhip_track_map* base_maps;			/* DEVICE [num_instances]; required when base_clips is set */
+	uint32_t reserved[2];
+} aclhip_pose_mapping;
+
+/* aclhip_decompress_poses_batch in skeleton space. `params` and `consumers` keep their meaning and their restrictions. The output is
+ * QVV48, B = num_bones records per row in skeleton order, EVERY slot written. The reference has no such function; the definition, from
+ * pieces it does have -- take instance i with skeleton S (B bones, reference pose R, parents P):
+ *   skeleton pose of a clip instance   skel(c, t, m, F)[s] = decode(c, t)[track] where m[track] == s, and F[s] for every slot no track
+ *       maps to. Dropped tracks contribute nothing. decode is the unmapped decode under `params` with the instance's rounding and
+ *       looping policies.
+ *   the fill F   additive_format == NONE: F = R for every clip of the instance. Otherwise the instance's own clip and its blend partners
+ *       are additive clips and a bone they do not animate must leave the base unchanged: their F is the ADDITIVE IDENTITY -- rotation
+ *       (0, 0, 0, 1), translation 0, scale 1 for relative and additive0, scale 0 for additive1 (the reference compressor's default for
+ *       additive clips) -- while a base clip always fills with R. A base pose BUFFER is in skeleton order already: B records,
+ *       base_pose_stride_bytes >= 48 B.
+ *   blend, additive apply, object space   today's operation orders (above; apply_additive_to_base; local_to_object_space) over the B
+ *       skeleton poses, with P as the hierarchy. A filled slot takes the same arithmetic as a decoded one.
+ * The clips of one instance may differ in track count: each only has to match its own map (map.num_tracks == clip.num_tracks), each
+ * map the skeleton (map.num_slots == B). aclhip_set_clip_hierarchy plays no part: the hierarchy is the skeleton's.
+ *   Refused and counted (aclhip_get_rejected_instance_count), the row untouched: an unknown or retired skeleton or map handle for any of
+ * the instance's clips, either size mismatch, a scalar or unknown clip, object space on a skeleton without hierarchy, 48 B >
+ * pose_stride_bytes or B beyond the launch's LDS image. No instance writes outside its row, whatever the device arrays hold.
+ *   ACLHIP_ERROR_INVALID_ARGUMENT: mapping == NULL, no skeleton (a null handle without instance_skeletons), no map, K > 1 without
+ * blend_maps, base_clips without base_maps, and everything aclhip_decompress_poses_batch refuses.
+ *   The launch is shaped by its rows alone: pose_stride_bytes / 48 slots per LDS image, whatever clips are registered (a clip may have
+ * more tracks than the skeleton has bones).
+ *   Out of scope (nothing here precludes them): ACLHIP_CONSUMERS_FAST is accepted and the default arithmetic runs; the rotation |
+ * translation images of unit-scale registries are not used; QVV40 / QV32 output; instance lists; the host convenience form; the C++
+ * mirror in aclhip.hpp.
+ *   What it costs: (MI355X, 65 536 instances of 100-bone clips, object space, tools/skeleton_poses.py; DESIGN.md 4.7 and
+ * profiles/skeleton_poses.md have the table, the kernel traces and the counters): with identity maps the launch takes 1.21 - 1.27 x the
+ * unmapped aclhip_decompress_poses_batch on the same batch (object space 106 vs 85 us, additive1 onto a base clip 181 vs 144 us, a blend of
+ * three 233 vs 192 us), into 128 slots 1.46 - 1.60 x (137 / 281 us). It does NOT beat K launches of aclhip_decompress_tracks_batch_mapped
+ * with fill -- the first step of what a caller does without it: 106 vs 77 us for K = 1 (0.73), 232 vs 232 us for K = 3 (1.00), 281 vs
+ * 286 us for K = 3 into 128 slots (1.02). That floor holds none of the caller's further passes (the blend, the additive apply and the
+ * walk each read and write the pose buffers again), which is what the launch is for. WRITE_SIZE / FETCH_SIZE equal the unmapped
+ * launch's per byte of row: the difference is in-wave (dependent map loads in front of the gather and of every LDS write). */
+aclhip_status aclhip_decompress_poses_batch_mapped(aclhip_context* context, const aclhip_clip* clips, const float* sample_times, uint32_t num_instances,
+	const aclhip_decompress_params* params, const aclhip_pose_consumers* consumers, const aclhip_pose_mapping* mapping,
+	void* poses, uint64_t pose_stride_bytes, void* stream);
 
 /* ---- multi-GPU ---------------------------------------------------------------------------------- */
 
