@@ -74,4 +74,5 @@ using namespace aclhip;
 #include "host_lists.inl"
 #include "host_consumers.inl"
 #include "host_skeletons.inl"
+#include "host_blend_masks.inl"
 #include "host_scalar_misc.inl"

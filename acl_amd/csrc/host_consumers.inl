@@ -327,10 +327,39 @@ namespace
 		return blend ? skeleton_pose_kernel_of_base<false, true>(base_kind, mirrored) : skeleton_pose_kernel_of_base<false, false>(base_kind, mirrored);
 	}
 
+	// the masked blends of skeleton space (aclhip_decompress_poses_batch_masked): kernels of their own, the masking behind the mapping
+	typedef void (*masked_pose_kernel)(const device_clip*, uint32_t, const uint32_t*, const float*, uint32_t, decode_params, consumer_params, uint8_t*, uint64_t, uint32_t, uint32_t, uint32_t, unsigned long long*, skeleton_launch, blend_mask_launch);
+
+	template<bool kObjectSpace>
+	masked_pose_kernel masked_pose_kernel_of_base(uint32_t base_kind, bool mirrored)
+	{
+		// (skeleton_pose_kernel_of_base's choices for a blend)
+		switch (base_kind)
+		{
+		case k_consumer_base_none:
+			if constexpr (kObjectSpace)
+				return mirrored ? decompress_poses_masked_kernel<true, k_consumer_base_none, true> : decompress_poses_masked_kernel<true, k_consumer_base_none, false>;
+			return decompress_poses_masked_kernel<false, k_consumer_base_none, false>;
+		case k_consumer_base_buffer:
+			return decompress_poses_masked_kernel<kObjectSpace, k_consumer_base_buffer, true>;
+		case k_consumer_base_second_wave:
+			return mirrored ? decompress_poses_masked_kernel<kObjectSpace, k_consumer_base_second_wave, true> : decompress_poses_masked_kernel<kObjectSpace, k_consumer_base_second_wave, false>;
+		default:
+			return nullptr;		// (a blend's base clip is never fused)
+		}
+	}
+
+	masked_pose_kernel masked_pose_kernel_of(bool object_space, uint32_t base_kind, bool mirrored)
+	{
+		return object_space ? masked_pose_kernel_of_base<true>(base_kind, mirrored) : masked_pose_kernel_of_base<false>(base_kind, mirrored);
+	}
+
 	// `mapping` (aclhip_decompress_poses_batch_mapped): skeleton space -- the launch is shaped by its rows alone (pose_stride_bytes / 48
-	// slots), the skeleton kernels take the mapping as their trailing argument
+	// slots), the skeleton kernels take the mapping as their trailing argument. `masking` (aclhip_decompress_poses_batch_masked, with a
+	// mapping and a blend): the same launch through the masked kernels.
 	aclhip_status launch_consumers(aclhip_context* context, const aclhip_clip* clips, const float* sample_times, uint32_t num_instances,
-		const decode_params& params, const aclhip_pose_consumers& consumers, void* poses, uint64_t pose_stride_bytes, hipStream_t stream, const skeleton_launch* mapping = nullptr)
+		const decode_params& params, const aclhip_pose_consumers& consumers, void* poses, uint64_t pose_stride_bytes, hipStream_t stream, const skeleton_launch* mapping = nullptr,
+		const blend_mask_launch* masking = nullptr)
 	{
 		if (consumers.additive_format > ACLHIP_ADDITIVE_ADDITIVE1)
 			return fail(context, ACLHIP_ERROR_INVALID_ARGUMENT, "unknown additive format %u", consumers.additive_format);
@@ -364,6 +393,16 @@ namespace
 			device_mapping.num_skeletons = ACLHIP_MAX_SKELETONS;
 			device_mapping.maps = context->d_track_maps;
 			device_mapping.num_maps = ACLHIP_MAX_TRACK_MAPS;
+		}
+		blend_mask_launch device_masking = {};
+		if (masking != nullptr)
+		{
+			if (mapping == nullptr || !blend)
+				return fail(context, ACLHIP_ERROR_INVALID_ARGUMENT, "blend masks go with a blend in skeleton space");
+			// (no mask registered yet: a table of no records -- every handle but the null handle is refused in the kernel)
+			device_masking = *masking;
+			device_masking.masks = context->d_blend_masks;
+			device_masking.num_masks = context->d_blend_masks != nullptr ? ACLHIP_MAX_BLEND_MASKS : 0u;
 		}
 		note_launch_stream(context, stream);
 
@@ -472,6 +511,19 @@ namespace
 		const consumer_kernel kernel = fast ? (unit_scale ? decompress_poses_consumer_kernel<true, k_consumer_base_none, true, false, false, true> : fast_kernels[mirrored ? 1 : 0][base_kind])
 			: unit_scale ? decompress_poses_consumer_kernel<true, k_consumer_base_none, true, false>
 			: (blend ? blend_kernels[mirrored ? 1 : 0][consumers.object_space != 0 ? 1 : 0][base_kind] : kernels[mirrored ? 1 : 0][consumers.object_space != 0 ? 1 : 0][base_kind]);
+		if (masking != nullptr)
+		{
+			const masked_pose_kernel masked_kernel = masked_pose_kernel_of(consumers.object_space != 0, base_kind, mirrored);
+			if (masked_kernel == nullptr)
+				return fail(context, ACLHIP_ERROR_INVALID_ARGUMENT, "no masked kernel for base kind %u", base_kind);
+			if (lds_bytes > 64 * 1024 - 128)
+				ACLHIP_CHECK_HIP(context, hipFuncSetAttribute(reinterpret_cast<const void*>(masked_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, int(k_lds_bytes)));
+			hipLaunchKernelGGL(masked_kernel, dim3(num_blocks), dim3(waves_per_block * k_wave_size), lds_bytes, stream,
+				context->d_clips, context->d_clips_capacity, clips, sample_times, num_instances, params, device_consumers,
+				static_cast<uint8_t*>(poses), pose_stride_bytes, lds_quads_per_image, uint32_t(lds_bytes_per_instance), log2_instances_per_block | (lds_schedule_words << 8), context->d_rejected, device_mapping, device_masking);
+			ACLHIP_CHECK_HIP(context, hipGetLastError());
+			return ACLHIP_OK;
+		}
 		if (mapping != nullptr)
 		{
 			const skeleton_pose_kernel skeleton_kernel = skeleton_pose_kernel_of(consumers.object_space != 0, base_kind, mirrored, blend);

@@ -85,6 +85,12 @@ struct aclhip_context
 	device_skeleton* d_skeletons = nullptr;
 	uint32_t num_negative_scale_skeletons = 0;		// live skeletons whose reference pose holds a negative scale (see num_negative_scale_clips)
 	uint32_t max_skeleton_hierarchy_words = 0;		// largest walk schedule a skeleton was ever registered with (a longer one is walked from global memory)
+	// Blend masks (aclhip_register_blend_mask, host_blend_masks.inl): a weight per slot for the skeleton space blends. The same lifetime:
+	// one table of ACLHIP_MAX_BLEND_MASKS records made at the first registration, record 0 never handed out.
+	struct blend_mask_entry { bool in_use = false; aclhip_blend_mask_info info = {}; uint8_t* device_memory = nullptr; };
+	std::vector<blend_mask_entry> blend_masks;
+	std::vector<uint32_t> free_blend_mask_slots;
+	device_blend_mask* d_blend_masks = nullptr;
 	device_clip* d_clips = nullptr;
 	uint32_t d_clips_capacity = 0;
 	unsigned long long* d_rejected = nullptr;	// [0] instances the kernels refused, [1] transforms of the pose consumers that met a negative scale
@@ -128,6 +134,7 @@ struct aclhip_context
 		uint32_t slot = ACLHIP_INVALID_HANDLE;		// clip handle that becomes reusable
 		uint32_t map_slot = ACLHIP_INVALID_HANDLE;	// track map handle that becomes reusable
 		uint32_t skeleton_slot = ACLHIP_INVALID_HANDLE;	// skeleton handle that becomes reusable
+		uint32_t blend_mask_slot = ACLHIP_INVALID_HANDLE;	// blend mask handle that becomes reusable
 		uint8_t* database_memory[6] = { nullptr, nullptr, nullptr, nullptr, nullptr, nullptr };		// hipMalloc'ed pieces of a database
 		uint8_t* database_pinned[4] = { nullptr, nullptr, nullptr, nullptr };		// bulk data x 2, patch mirrors x 2
 		void* device_memory = nullptr;				// any other hipMalloc'ed piece
@@ -430,6 +437,8 @@ namespace
 				context->free_map_slots.push_back(item.map_slot);
 			if (item.skeleton_slot != ACLHIP_INVALID_HANDLE)
 				context->free_skeleton_slots.push_back(item.skeleton_slot);
+			if (item.blend_mask_slot != ACLHIP_INVALID_HANDLE)
+				context->free_blend_mask_slots.push_back(item.blend_mask_slot);
 			for (uint8_t* memory : item.database_memory)
 				if (memory != nullptr)
 					(void)hipFree(memory);
@@ -1027,6 +1036,8 @@ extern "C" void aclhip_destroy(aclhip_context* context)
 			(void)hipFree(context->d_track_maps);
 		if (context->d_skeletons != nullptr)
 			(void)hipFree(context->d_skeletons);
+		if (context->d_blend_masks != nullptr)
+			(void)hipFree(context->d_blend_masks);
 		for (const aclhip_context::order_scratch& scratch : context->order_scratches)
 		{
 			(void)hipFree(scratch.bins);

@@ -498,3 +498,556 @@
 			store_streaming(&pose[quad], image[quad]);
 		ACLHIP_PHASE_STAMP(3);
 	}
+
+	// ---- blend masks (aclhip_register_blend_mask, aclhip_decompress_poses_batch_masked) ------------------------------------------------
+	// A weight per (instance, clip, SLOT) in the place of the blend's weight per (instance, clip): include/aclhip.h states the definition.
+	// A mask's record in the context's mask table (which never moves, like the map table) and its device image: num_slots floats in slot
+	// order. A cleared record (image == null) is an unknown or retired mask; record 0 is never handed out (handle 0: no mask).
+	struct device_blend_mask
+	{
+		const float* image;
+		uint32_t num_slots;
+		uint32_t reserved;
+	};
+	static_assert(sizeof(device_blend_mask) == 16, "one dwordx4 load");
+
+	// the masked kernels' own trailing argument, behind skeleton_launch
+	struct blend_mask_launch
+	{
+		const device_blend_mask* masks;			// the context's mask table
+		uint32_t num_masks;						// its capacity
+		uint32_t layered;						// ACLHIP_BLEND_LAYERED
+		const uint32_t* instance_masks;			// [num_instances * K], laid out like consumer_params::blend_weights; 0: no mask
+	};
+
+	// The weight of ONE clip of a masked blend at a slot. The pointers and the clip weights are wave uniform (read on the scalar unit next
+	// to the clip and map records); the mask values are read per lane through the vector cache, like track_to_slot: a mask is a few
+	// hundred bytes that every wave of a crowd reads. above1 .. above3: the layers over this clip in layered mode, the TOP one first -- the
+	// order the definition multiplies (1 - e_j) in. A layer that is not there (fewer than three above, or weighted mode) has no mask and
+	// weight 0: r * (1 - 0) is r, so the product is the definition's bit for bit, and e * 1 is e. (Named fields, not arrays: an array of
+	// pointers here went to scratch in the instantiations with a second wave.)
+	struct layer_weight
+	{
+		const ACLHIP_CONSTANT float* mask;		// null: no mask, every slot 1
+		float weight;
+		__device__ __forceinline__ float operator()(uint32_t slot) const { return mask != nullptr ? weight * mask[slot] : weight; }
+	};
+
+	struct slot_weight
+	{
+		layer_weight own, above1, above2, above3;
+		__device__ __forceinline__ float operator()(uint32_t slot) const
+		{
+			const float opacity = own(slot);
+			float rest = 1.0f - above1(slot);
+			rest = rest * (1.0f - above2(slot));
+			rest = rest * (1.0f - above3(slot));
+			return opacity * rest;
+		}
+	};
+	static_assert(ACLHIP_MAX_BLEND_CLIPS == 4, "slot_weight: at most three layers above a clip");
+
+	// (the mask behind a handle the kernel has checked: known, of the skeleton's slot count -- or the null handle)
+	__device__ __forceinline__ layer_weight layer_weight_of(const device_blend_mask* masks, const ACLHIP_CONSTANT uint32_t* handles, const ACLHIP_CONSTANT float* weights, uint32_t k)
+	{
+		const uint32_t handle = handles[k];
+		// (the pointer alone: two scalar registers per layer, not a record's four)
+		return layer_weight{ handle != 0 ? as_constant(as_constant(masks)[handle].image) : nullptr, weights[k] };
+	}
+
+	// clip k's weight of an instance (`handles`, `weights`: the instance's K entries): its own mask and weight and, in layered mode, those
+	// of the clips above it
+	__device__ __forceinline__ slot_weight slot_weight_of(const device_blend_mask* masks, uint32_t layered, const ACLHIP_CONSTANT uint32_t* handles, const ACLHIP_CONSTANT float* weights,
+		uint32_t num_blend_clips, uint32_t k)
+	{
+		slot_weight result;
+		result.own = layer_weight_of(masks, handles, weights, k);
+		const uint32_t num_above = layered != 0 ? num_blend_clips - 1u - k : 0u;
+		result.above1 = result.above2 = result.above3 = layer_weight{ nullptr, 0.0f };
+		if (num_above > 0)
+			result.above1 = layer_weight_of(masks, handles, weights, num_blend_clips - 1u);
+		if (num_above > 1)
+			result.above2 = layer_weight_of(masks, handles, weights, num_blend_clips - 2u);
+		if (num_above > 2)
+			result.above3 = layer_weight_of(masks, handles, weights, num_blend_clips - 3u);
+		return result;
+	}
+
+	// A map's and a skeleton's record with every field in scalar registers of its own, like load_clip_fields (kernels_pose.inl): load_entry
+	// hands back two 4 register blocks, a block lives as long as ANY of its fields and is spilled whole -- in the masked kernels with a
+	// second wave such a spill left a 16 byte stack slot behind that nothing read or wrote, and a kernel with a stack gets scratch memory
+	__device__ __forceinline__ device_track_map load_map_fields(const device_track_map* table, uint32_t index)
+	{
+		device_track_map map = load_entry(table, index);
+		asm volatile("" : "+s"(map.image), "+s"(map.num_tracks), "+s"(map.num_slots), "+s"(map.num_unmapped));
+		return map;
+	}
+
+	__device__ __forceinline__ device_skeleton load_skeleton_fields(const device_skeleton* table, uint32_t index)
+	{
+		device_skeleton skeleton = load_entry(table, index);
+		asm volatile("" : "+s"(skeleton.hierarchy), "+s"(skeleton.reference_pose), "+s"(skeleton.num_bones), "+s"(skeleton.flags));
+		return skeleton;
+	}
+
+	// The masked kernels' arguments as they lie in the kernarg segment (in order, each at its natural alignment), like pose_kernel_args
+	// (kernels_pose.inl): what the blend's passes and the tail of the kernel need -- the lists of the blend, the tables, where the pose
+	// goes -- is read THERE, where it is used, instead of being held (spilled) in scalar registers across up to four decodes.
+	struct masked_kernel_args
+	{
+		const device_clip* clips;
+		uint32_t num_clips;
+		const uint32_t* clip_ids;
+		const float* sample_times;
+		uint32_t num_instances;
+		decode_params params;
+		consumer_params consumers;
+		uint8_t* poses;
+		uint64_t pose_stride_bytes;
+		uint32_t lds_quads_per_image;
+		uint32_t lds_bytes_per_instance;
+		uint32_t packed_block_shape;
+		unsigned long long* rejected_count;
+		skeleton_launch mapping;
+		blend_mask_launch masking;
+	};
+	// (the offsets the compiler's kernel metadata lists for decompress_poses_masked_kernel: tools/kernel_resources.sh's assembly, `.offset`)
+	static_assert(offsetof(masked_kernel_args, params) == 40 && offsetof(masked_kernel_args, consumers) == 160 && offsetof(masked_kernel_args, poses) == 232
+		&& offsetof(masked_kernel_args, lds_quads_per_image) == 248 && offsetof(masked_kernel_args, rejected_count) == 264 && offsetof(masked_kernel_args, mapping) == 272
+		&& offsetof(masked_kernel_args, masking) == 336 && sizeof(masked_kernel_args) == 360, "masked_kernel_args mirrors the kernel's argument list");
+
+	__device__ __forceinline__ decode_params load_decode_params(const ACLHIP_CONSTANT decode_params* source)
+	{
+		decode_params params;
+		__builtin_memcpy(&params, (const ACLHIP_CONSTANT void*)source, sizeof(params));
+		return params;
+	}
+
+	// (opaque per use: not hoisted to the kernel's start and kept across the decodes)
+	__device__ __forceinline__ const ACLHIP_CONSTANT masked_kernel_args* late_masked_kernel_args()
+	{
+	#if defined(__HIP_DEVICE_COMPILE__)
+		const ACLHIP_CONSTANT masked_kernel_args* args = (const ACLHIP_CONSTANT masked_kernel_args*)__builtin_amdgcn_kernarg_segment_ptr();
+		asm volatile("" : "+s"(args));
+		return args;
+	#else
+		return nullptr;		// (the host pass only has to compile)
+	#endif
+	}
+
+	// blend_image_writer with the slot's weight (slot_image_writer hands over entry.track_index == slot)
+	struct masked_blend_image_writer
+	{
+		f32x4* image;
+		slot_weight weight;
+		__device__ __forceinline__ void operator()(const clip_range_entry& entry, float4 value) const
+		{
+			const uint32_t quad = entry.quad_index;
+			image[quad] = blend_accumulate(quad - entry.track_index * 3u, image[quad], value, weight(entry.track_index));
+		}
+	};
+
+	// blend_scale_image with a weight per slot: the first clip's pose, complete in `image`, times its weights
+	__device__ __forceinline__ void blend_scale_slot_image(f32x4* image, uint32_t num_quads, const slot_weight& weight, uint32_t lane)
+	{
+		for (uint32_t quad = lane; quad < num_quads; quad += k_wave_size)
+		{
+			const uint32_t slot = quad / 3u;
+			const float slot_weight_value = weight(slot);
+			const f32x4 value = image[quad];
+			const bool is_rotation = quad - slot * 3u == 0;
+			image[quad] = f32x4{ value.x * slot_weight_value, value.y * slot_weight_value, value.z * slot_weight_value, is_rotation ? value.w * slot_weight_value : 0.0f };
+		}
+	}
+
+	// blend_clip_onto_slot_image with a weight per slot
+	__device__ __forceinline__ void blend_clip_onto_masked_slot_image(const device_clip& clip, const device_track_map& map, const slot_fill& fill, float sample_time,
+		uint32_t rounding_policy, const decode_params& params, const slot_weight& weight, uint32_t lane, f32x4* image)
+	{
+		// (combine_constant_slots' text with the slot handed to the combine: its own callers keep their instructions)
+		const uint32_t num_quads = map.num_slots * 3u;
+		const ACLHIP_CONSTANT uint32_t* slot_to_track = slot_to_track_of(map);
+		for (uint32_t slot_quad = lane; slot_quad < num_quads; slot_quad += k_wave_size)
+		{
+			const uint32_t slot = slot_quad / 3u;
+			const uint32_t kind = slot_quad - slot * 3u;
+			const uint32_t track = slot_to_track[slot];
+			float4 value;
+			if (track != ACLHIP_TRACK_DROPPED)
+			{
+				value = load_quad(clip.base_pose, track * 3u + kind);
+				const uint32_t marker = __float_as_uint(value.w);
+				if (is_special_quad(marker))
+				{
+					if ((marker & k_quad_animated) != 0)
+						continue;
+					value.w = (marker & k_quad_default_w_one) != 0 ? 1.0f : 0.0f;
+				}
+			}
+			else
+			{
+				const f32x4 filled = *fill.quad(slot_quad, kind);
+				value = make_float4(filled.x, filled.y, filled.z, filled.w);
+			}
+			image[slot_quad] = blend_accumulate(kind, image[slot_quad], value, weight(slot));
+		}
+		decode_animated_into_image(clip, sample_time, rounding_policy, params, lane, into_slots(map, masked_blend_image_writer{ image, weight }));
+	}
+
+	// decompress_poses_skeleton_kernel's blend instantiations with a weight per slot (aclhip_decompress_poses_batch_masked), the masking as
+	// their own trailing argument. The text is repeated, not shared, for the reason that kernel states: its instantiations are held to
+	// identical disassembly (profiles/blend_masks.md). What differs: the K mask records are checked next to the K maps, and the three
+	// places that take a weight -- the first clip's scale, the constant / fill pass, the animated writer -- ask slot_weight for it. One quad
+	// is still touched by one lane per pass: the LDS hazards and the barriers are that kernel's.
+	template<bool kObjectSpace, uint32_t kBase, bool kMirrored>
+	__global__ __launch_bounds__(k_consumer_max_waves * k_wave_size) void decompress_poses_masked_kernel(const device_clip* __restrict__ clips, uint32_t num_clips,
+		const uint32_t* __restrict__ clip_ids, const float* __restrict__ sample_times, uint32_t num_instances, decode_params launch_params, consumer_params consumers,
+		uint8_t* __restrict__ poses, uint64_t pose_stride_bytes, uint32_t lds_quads_per_image, uint32_t lds_bytes_per_instance, uint32_t packed_block_shape,
+		unsigned long long* __restrict__ rejected_count, skeleton_launch skeleton_mapping, blend_mask_launch blend_masking)
+	{
+		const skeleton_launch* const mapping = &skeleton_mapping;
+		const blend_mask_launch* const masking = &blend_masking;
+		(void)poses;		// (read where the pose is stored: masked_kernel_args)
+		// (registers of their own, like load_map_fields: the three arrive in one dwordx4 load of the kernarg segment, and in the instantiations
+		// with a second wave the block's spill slot stayed behind as 16 bytes of stack that nothing read or wrote)
+		asm volatile("" : "+s"(lds_quads_per_image), "+s"(lds_bytes_per_instance), "+s"(packed_block_shape));
+		// packed_block_shape: log2 of the instances per workgroup (bits 0..7) | words of LDS reserved for the shared walk schedule (bits 8..31)
+		const uint32_t log2_instances_per_block = packed_block_shape & 0xFFu;
+		extern __shared__ __attribute__((aligned(16))) uint8_t dynamic_lds[];
+		__shared__ consumer_walk_slots walk;		// (what the host subtracts from the LDS it may ask for: host_consumers.inl)
+		uint32_t (&walk_levels)[k_consumer_max_instances] = walk.levels;
+		const uint32_t* (&walk_schedules)[k_consumer_max_instances] = walk.schedules;
+		uint32_t (&walk_tracks)[k_consumer_max_instances] = walk.tracks;
+		uint32_t (&walk_short_exact)[k_consumer_max_instances] = walk.short_exact;
+
+		static_assert(kBase != k_consumer_base_fused, "a blend accumulates whole qvv images; a base clip is decoded by a second wave");
+		constexpr bool has_base = kBase != k_consumer_base_none;
+		// (a blend's base clip is never fused: a second wave decodes it into its own image)
+		constexpr bool base_is_clip = kBase == k_consumer_base_second_wave;
+		constexpr bool two_waves = base_is_clip;
+		constexpr bool object_space = kObjectSpace;
+		ACLHIP_PHASE_STAMP(0);
+
+		// wave -> (instance slot of the workgroup, role): role 1 waves (base clips only) decode the slot's base
+		const uint32_t lane = threadIdx.x & (k_wave_size - 1);
+		const uint32_t wave_in_block = __builtin_amdgcn_readfirstlane(threadIdx.x / k_wave_size);
+		const uint32_t slot = wave_in_block & ((1u << log2_instances_per_block) - 1u);
+		const uint32_t role = wave_in_block >> log2_instances_per_block;
+		const uint32_t waves_per_instance = two_waves ? 2u : 1u;
+		const uint32_t instance = (blockIdx.x << log2_instances_per_block) + slot;
+
+		uint8_t* instance_lds = dynamic_lds + size_t(slot) * lds_bytes_per_instance;
+		f32x4* image = reinterpret_cast<f32x4*>(instance_lds);
+		f32x4* base_image = image + lds_quads_per_image;
+		// one LDS copy of the walk schedule per workgroup, behind the instances' images: the instances of a workgroup usually share
+		// a skeleton (identical hierarchies are one image, see aclhip_set_clip_hierarchy), and every word kept per instance costs residency
+		uint32_t* shared_schedule = reinterpret_cast<uint32_t*>(dynamic_lds + (size_t(lds_bytes_per_instance) << log2_instances_per_block));
+		const uint32_t* schedule = nullptr;
+
+		uint32_t num_tracks = 0;		// stays 0 for a wave without work: past the batch, refused instance, empty track list
+		uint32_t num_levels = 0;
+		// the walk's normalize may take the short exact forms when every rotation it meets comes out of clips that are proven safe for
+		// them (norms near 1; a caller's base pose buffer holds anything)
+		uint32_t short_exact = kBase == k_consumer_base_buffer ? 0u : 1u;
+		if (instance < num_instances)
+		{
+			const uint32_t clip_id = as_constant(clip_ids)[instance];
+			// (every field in registers of its own: load_clip_fields, kernels_pose.inl)
+			const device_clip clip = load_clip_fields(clips, clip_id < num_clips ? clip_id : 0);
+
+			// skeleton space: the instance's skeleton and its clip's map, read on the scalar unit next to the clip record. A cleared record
+			// (an unknown or retired handle) holds no image; record 0 of both tables is never handed out.
+			const uint32_t skeleton_id = mapping->instance_skeletons != nullptr ? as_constant(mapping->instance_skeletons)[instance] : mapping->skeleton;
+			const uint32_t map_id = mapping->instance_maps != nullptr ? as_constant(mapping->instance_maps)[instance] : mapping->map;
+			const device_skeleton skeleton = load_skeleton_fields(mapping->skeletons, skeleton_id < mapping->num_skeletons ? skeleton_id : 0);
+			const device_track_map clip_map = load_map_fields(mapping->maps, map_id < mapping->num_maps ? map_id : 0);
+			// the transforms of the instance's pose and the hierarchy they are walked with are the skeleton's (clip.hierarchy is not read)
+			const uint32_t pose_tracks = skeleton.num_bones;
+			const uint32_t* const hierarchy = skeleton.hierarchy;
+
+			// refused: unknown or retired masks and masks of another slot count (below, next to the blend's maps), and everything the unmasked
+			// kernel refuses: unknown / scalar clips, unknown or retired skeletons and maps, a map made for another clip or another skeleton, object
+			// space without a hierarchy, more bones than the row or the launch's LDS image holds. Both waves of an instance come to the same
+			// verdict; the first one reports it. A launch is shaped for its batch when it is enqueued (launch_consumers: LDS image sizes from
+			// the pose stride, kernel instantiation from what the registry holds) and meets its clips and skeletons when it runs: a clip or a
+			// reference pose that may hand a negative scale to a launch compiled without rtm::qvv_mul's matrix route -- registered behind a
+			// captured launch's back -- is refused here, not computed wrongly. Only launches that MULTIPLY transforms care: local space
+			// without a base, and additive0 / additive1 onto a fused base clip, combine scale with scale and serve mirrored skeletons as they are.
+			constexpr bool multiplies_transforms = object_space || kBase == k_consumer_base_buffer || kBase == k_consumer_base_second_wave;
+			bool refused = clip_id >= num_clips || !is_transform_clip(clip.flags) || (object_space && hierarchy == nullptr)
+				|| skeleton_id >= mapping->num_skeletons || skeleton.reference_pose == nullptr || !map_fits(clip_map, map_id, mapping->num_maps, clip.num_tracks, skeleton.num_bones)
+				|| uint64_t(pose_tracks) * 48u > pose_stride_bytes || pose_tracks * 3u > lds_quads_per_image
+				|| (kBase == k_consumer_base_buffer && uint64_t(pose_tracks) * 48u > consumers.base_pose_stride_bytes)
+				|| (!kMirrored && multiplies_transforms && (skeleton.flags & k_skeleton_negative_scale) != 0)
+				|| (!kMirrored && multiplies_transforms && !base_is_clip && (clip.flags & k_clip_negative_scale) != 0);
+
+			const uint32_t rounding_policy = __builtin_amdgcn_readfirstlane(instance_rounding_policy_of(launch_params, instance));
+			// the instance's own looping policy (decompress.h:149) goes for every clip decoded on its behalf -- its base, its blend partners
+			decode_params params = launch_params;
+			const uint8_t looping_policy = uint8_t(__builtin_amdgcn_readfirstlane(instance_looping_policy_of(launch_params, instance)));
+			params.looping_policy = looping_policy;
+
+			short_exact &= walk_may_use_short_exact_math(clip.flags, params.normalization);
+			short_exact &= (skeleton.flags & k_skeleton_short_exact_math) != 0 ? 1u : 0u;		// (the reference pose fills slots: its rotations are walked too)
+			// what a slot no track maps to holds: the reference pose -- or, for an additive clip and its blend partners, the additive identity
+			const slot_fill clip_fill = slot_fill_of(skeleton, consumers.additive_format);
+			if constexpr (base_is_clip)
+			{
+				const uint32_t base_clip_id = as_constant(consumers.base_clip_ids)[instance];
+				const device_clip base_clip = load_clip_fields(clips, base_clip_id < num_clips ? base_clip_id : 0);
+				// (each clip only has to match its own map, each map the skeleton)
+				const uint32_t base_map_id = as_constant(mapping->base_maps)[instance];
+				const device_track_map base_map = load_map_fields(mapping->maps, base_map_id < mapping->num_maps ? base_map_id : 0);
+				refused = refused || base_clip_id >= num_clips || !is_transform_clip(base_clip.flags) || !map_fits(base_map, base_map_id, mapping->num_maps, base_clip.num_tracks, skeleton.num_bones)
+					|| (!kMirrored && multiplies_transforms && ((clip.flags | base_clip.flags) & k_clip_negative_scale) != 0);
+				short_exact &= walk_may_use_short_exact_math(base_clip.flags, params.normalization);
+				if (!refused && two_waves && role == 1 && pose_tracks != 0)
+					decode_pose_into_slot_image(base_clip, base_map, slot_fill{ skeleton.reference_pose, 0 }, as_constant(consumers.base_sample_times)[instance], rounding_policy, params, lane, base_image);
+			}
+
+			if (!refused)
+			{
+				// every clip of the blend: known, a transform clip, with a known map of its own into this skeleton
+				for (uint32_t k = 1; k < consumers.num_blend_clips; ++k)
+				{
+					const uint32_t blend_clip_id = as_constant(consumers.blend_clip_ids)[size_t(instance) * (consumers.num_blend_clips - 1u) + (k - 1u)];
+					const ACLHIP_CONSTANT device_clip* record = as_constant(clips) + (blend_clip_id < num_clips ? blend_clip_id : 0);
+					const uint32_t blend_map_id = as_constant(mapping->blend_maps)[size_t(instance) * (consumers.num_blend_clips - 1u) + (k - 1u)];
+					const ACLHIP_CONSTANT device_track_map* map_record = as_constant(mapping->maps) + (blend_map_id < mapping->num_maps ? blend_map_id : 0);
+					refused = refused || blend_clip_id >= num_clips || !is_transform_clip(record->flags)
+						|| blend_map_id >= mapping->num_maps || map_record->image == nullptr || map_record->num_tracks != record->num_tracks || map_record->num_slots != skeleton.num_bones
+						|| (!kMirrored && multiplies_transforms && (record->flags & k_clip_negative_scale) != 0);
+					short_exact &= walk_may_use_short_exact_math(record->flags, params.normalization);
+				}
+				// every mask the instance names: the null handle, or a known mask of this skeleton's slot count
+				for (uint32_t k = 0; k < consumers.num_blend_clips; ++k)
+				{
+					const uint32_t mask_id = as_constant(masking->instance_masks)[size_t(instance) * consumers.num_blend_clips + k];
+					const ACLHIP_CONSTANT device_blend_mask* mask_record = as_constant(masking->masks) + (mask_id < masking->num_masks ? mask_id : 0);
+					refused = refused || (mask_id != 0 && (mask_id >= masking->num_masks || mask_record->image == nullptr || mask_record->num_slots != skeleton.num_bones));
+				}
+			}
+
+			if (refused)
+			{
+				if (lane == 0 && role == 0)
+					atomicAdd(rejected_count, 1ull);
+			}
+			else if (pose_tracks != 0)
+			{
+				num_tracks = pose_tracks;
+				if (role == 0)
+				{
+					if (object_space)
+					{
+						// The walk schedule for this many instances per workgroup, requested BEFORE the decode (until round 4 behind it: three
+						// more dependent round trips -- offset, header, words -- at the end of every wave's chain, 1.7 of a decode's 6.3 us).
+						// One scalar load for the schedule's header (aclhip_set_clip_hierarchy: {offset, steps, words, 0} per workgroup size,
+						// in flight next to the seek's sample records), then the words travel global -> LDS by DMA while the pose is decoded:
+						//     num_steps | words | step_end[num_steps] | transform | parent << 16 in step order, padded to whole 16 byte pieces
+						// Every wave leaves its schedule in the shared copy: the same words when they share it (the copy is only used then).
+						// A schedule longer than the launch reserved LDS for (a hierarchy set behind a captured launch's back) stays in
+						// global memory and the walk reads it there.
+						const u32x4 header = ((const ACLHIP_CONSTANT u32x4*)hierarchy)[log2_instances_per_block];
+						uint32_t schedule_offset = header.x, num_words = header.z;
+						num_levels = header.y;
+						asm volatile("" : "+s"(schedule_offset), "+s"(num_levels), "+s"(num_words));		// (registers of their own: load_map_fields)
+						schedule = hierarchy + schedule_offset;
+						if (num_words <= (packed_block_shape >> 8))
+						{
+							for (uint32_t base = 0; base < num_words; base += k_wave_size * 4u)
+								if (base + lane * 4u < num_words)
+									__builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(schedule + base + lane * 4u),
+										(__attribute__((address_space(3))) void*)(shared_schedule + base), 16, 0, 0);
+						}
+						else
+							num_levels |= 0x80000000u;
+						// (left in the walk's slots now, not held across the decodes)
+						if (lane == 0)
+						{
+							walk_levels[slot] = num_levels;
+							walk_schedules[slot] = schedule;
+						}
+					}
+					decode_pose_into_slot_image(clip, clip_map, clip_fill, as_constant(sample_times)[instance], rounding_policy, params, lane, image);
+					{
+						// (every pass reads its lists and tables from the kernarg segment: masked_kernel_args)
+						const uint32_t num_blend_clips = consumers.num_blend_clips;
+						wave_lds_barrier();		// the first pose is complete (its DMA has landed)
+						{
+							const ACLHIP_CONSTANT masked_kernel_args* args = late_masked_kernel_args();
+							blend_scale_slot_image(image, pose_tracks * 3u, slot_weight_of(args->masking.masks, args->masking.layered, as_constant(args->masking.instance_masks) + size_t(instance) * num_blend_clips,
+								as_constant(args->consumers.blend_weights) + size_t(instance) * num_blend_clips, num_blend_clips, 0), lane);
+						}
+						for (uint32_t k = 1; k < num_blend_clips; ++k)
+						{
+							const ACLHIP_CONSTANT masked_kernel_args* args = late_masked_kernel_args();
+							const size_t entry = size_t(instance) * (num_blend_clips - 1u) + (k - 1u);
+							const device_clip blend_clip = load_clip_fields(args->clips, as_constant(args->consumers.blend_clip_ids)[entry]);
+							wave_lds_barrier();		// every quad has its sum so far
+							const device_track_map blend_map = load_map_fields(args->mapping.maps, as_constant(args->mapping.blend_maps)[entry]);
+							const slot_weight weight = slot_weight_of(args->masking.masks, args->masking.layered, as_constant(args->masking.instance_masks) + size_t(instance) * num_blend_clips,
+								as_constant(args->consumers.blend_weights) + size_t(instance) * num_blend_clips, num_blend_clips, k);
+							// (the launch's decode settings too, with the instance's looping policy as above)
+							decode_params pass_params = load_decode_params(&args->params);
+							pass_params.looping_policy = looping_policy;
+							blend_clip_onto_masked_slot_image(blend_clip, blend_map, clip_fill, as_constant(args->consumers.blend_sample_times)[entry], rounding_policy, pass_params, weight, lane, image);
+						}
+						wave_lds_barrier();
+						blend_normalize_rotations(image, pose_tracks, lane);
+					}
+				}
+			}
+		}
+
+		// both images of every instance are complete
+		// (what the tail needs of the launch is read from the kernarg segment here, behind the decodes: masked_kernel_args)
+		const ACLHIP_CONSTANT masked_kernel_args* const tail_args = late_masked_kernel_args();
+		if (two_waves)
+			__syncthreads();
+		else
+			wave_lds_barrier();
+
+		if (has_base)
+		{
+			const f32x4* base_source = base_is_clip ? base_image : reinterpret_cast<const f32x4*>(tail_args->consumers.base_poses + uint64_t(instance) * tail_args->consumers.base_pose_stride_bytes);
+			const uint32_t additive_format = tail_args->consumers.additive_format;
+			for (uint32_t transform_index = role * k_wave_size + lane; transform_index < num_tracks; transform_index += waves_per_instance * k_wave_size)
+			{
+				const qvv additive = load_qvv(image, transform_index);
+				const qvv base = load_qvv(base_source, transform_index);
+				store_qvv(image, transform_index, apply_additive_to_base<kMirrored>(additive_format, base, additive));
+				// additive_clip_format8::relative is a qvv_mul (core/additive_utils.h:128-160)
+				if constexpr (kMirrored)
+				{
+					const uint64_t mirrored = __ballot(additive_format == 1 && qvv_mul_takes_matrix_path(additive, base));
+					if (mirrored != 0 && lane == uint32_t(__builtin_ctzll(mirrored)))
+						atomicAdd(tail_args->rejected_count + 1, (unsigned long long)__builtin_popcountll(mirrored));
+				}
+			}
+		}
+
+		if (object_space)
+		{
+			if (lane == 0 && role == 0)
+			{
+				if (num_tracks == 0)
+				{
+					walk_levels[slot] = 0;
+					walk_schedules[slot] = nullptr;
+				}
+				walk_tracks[slot] = num_tracks;
+				walk_short_exact[slot] = num_tracks != 0 ? short_exact : 1u;
+			}
+			__syncthreads();
+			ACLHIP_PHASE_STAMP(1);
+
+			// ONE wave walks and then stores the workgroup's poses; the others are done and give their wave slots and registers back (a
+			// pose waits in LDS for the walk about as long as its decode took: with every wave parked at a barrier the wave slots, not the
+			// LDS, decided how many poses a CU holds). The walking wave rotates with the workgroup index: waves land on SIMDs by their
+			// index inside the workgroup, and walks that all ran on a CU's first SIMD would queue there.
+			if (wave_in_block != (blockIdx.x & ((blockDim.x / k_wave_size) - 1u)))
+				return;
+			{
+				// lanes <-> (instance slot, transform of the current step): slot = lane % instances, lane / instances picks the slot's
+				// transform inside the step. A transform's parent was scheduled in an earlier step: final by the time it is read.
+				const uint32_t walk_slot = lane & ((1u << log2_instances_per_block) - 1u);
+				const uint32_t first = lane >> log2_instances_per_block;
+				f32x4* slot_image = reinterpret_cast<f32x4*>(dynamic_lds + size_t(walk_slot) * tail_args->lds_bytes_per_instance);
+				[[maybe_unused]] unsigned long long* const negative_scale_count = tail_args->rejected_count + 1;
+				const uint32_t slot_steps = walk_levels[walk_slot] & 0x7FFFFFFFu;
+				const bool slot_schedule_is_shared = (walk_levels[walk_slot] & 0x80000000u) == 0;
+				const uint32_t* slot_schedule = walk_schedules[walk_slot];
+
+				const auto walk = [&](const auto* schedule_words, auto short_exact_tag)
+				{
+					constexpr bool k_short_exact = decltype(short_exact_tag)::value;		// sqrt_rn_short / rcp_rn_short in the normalize (aclhip_device.h)
+					const auto* pairs = schedule_words + 2u + slot_steps;
+					uint32_t step_start = 0;
+					for (uint32_t step = 0; __any(int(step < slot_steps)) != 0; ++step)
+					{
+						if (step < slot_steps)
+						{
+							const uint32_t step_end = schedule_words[2 + step];
+							const uint32_t pair_index = step_start + first;
+							if (pair_index < step_end)
+							{
+								const uint32_t pair = pairs[pair_index];		// transform | parent << 16
+								const qvv child = load_qvv(slot_image, pair & 0xFFFFu), parent = load_qvv(slot_image, pair >> 16);
+								qvv object;
+								if constexpr (kMirrored)
+								{
+									const uint64_t mirrored = __ballot(qvv_mul_takes_matrix_path(child, parent));
+									if (mirrored != 0 && lane == uint32_t(__builtin_ctzll(mirrored)))
+										atomicAdd(negative_scale_count, (unsigned long long)__builtin_popcountll(mirrored));
+									object = qvv_mul(child, parent);
+									if (mirrored != 0 && qvv_mul_takes_matrix_path(child, parent))
+										object = qvv_mul_through_matrices(child, parent);
+								}
+								else
+								{
+									// neither a registered clip nor a reference pose can hand over a negative scale and the base is a clip:
+									// products and sums of non negative scales -- nothing to count, nothing to route
+									object = qvv_mul(child, parent);
+								}
+								object.rotation = quat_normalize<k_short_exact>(object.rotation);
+								store_qvv(slot_image, pair & 0xFFFFu, object);
+							}
+							step_start = step_end;
+						}
+						wave_lds_barrier();
+					}
+				};
+
+				// all instances that walk follow the same schedule? then the shared LDS copy is theirs; otherwise each reads its own
+				// from global memory (rare: mixed skeletons inside one workgroup)
+				// the rest of the workgroup waits for this wave: it goes first on its SIMD
+				__builtin_amdgcn_s_setprio(3);
+				const uint64_t walkers = __ballot(slot_steps != 0);
+				if (walkers != 0)
+				{
+					const uint32_t leader = uint32_t(__builtin_ctzll(walkers));
+					const uint64_t mine = reinterpret_cast<uint64_t>(slot_schedule);
+					const uint64_t first_schedule = (uint64_t(__shfl(uint32_t(mine >> 32), int(leader))) << 32) | __shfl(uint32_t(mine), int(leader));
+					const bool shared_copy = __all(int(slot_steps == 0 || (mine == first_schedule && slot_schedule_is_shared))) != 0;
+					const bool short_exact_walk = __all(int(walk_short_exact[walk_slot] != 0)) != 0;
+					const auto walk_with = [&](auto short_exact_tag)
+					{
+						if (shared_copy)
+							walk(static_cast<const uint32_t*>(shared_schedule), short_exact_tag);
+						else
+							walk(as_constant(slot_schedule), short_exact_tag);
+					};
+					if (short_exact_walk)
+						walk_with(std::true_type());
+					else
+						walk_with(std::false_type());
+				}
+				__builtin_amdgcn_s_setprio(0);
+			}
+			wave_lds_barrier();
+			ACLHIP_PHASE_STAMP(2);
+
+			const uint32_t instances_per_block = 1u << log2_instances_per_block;
+			for (uint32_t store_slot = 0; store_slot < instances_per_block; ++store_slot)
+			{
+				const uint32_t slot_quads = walk_tracks[store_slot] * 3u;
+				const f32x4* slot_image = reinterpret_cast<const f32x4*>(dynamic_lds + size_t(store_slot) * tail_args->lds_bytes_per_instance);
+				f32x4* slot_pose = reinterpret_cast<f32x4*>(tail_args->poses + uint64_t((blockIdx.x << log2_instances_per_block) + store_slot) * tail_args->pose_stride_bytes);
+				for (uint32_t quad = lane; quad < slot_quads; quad += k_wave_size)
+					store_streaming(&slot_pose[quad], slot_image[quad]);
+			}
+			ACLHIP_PHASE_STAMP(3);
+			return;
+		}
+		else if (two_waves)
+			__syncthreads();
+		else
+			wave_lds_barrier();
+
+		const uint32_t num_quads = num_tracks * 3u;
+		f32x4* pose = reinterpret_cast<f32x4*>(tail_args->poses + uint64_t(instance) * tail_args->pose_stride_bytes);
+		for (uint32_t quad = role * k_wave_size + lane; quad < num_quads; quad += waves_per_instance * k_wave_size)
+			store_streaming(&pose[quad], image[quad]);
+		ACLHIP_PHASE_STAMP(3);
+	}

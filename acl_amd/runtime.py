@@ -44,6 +44,7 @@ EXPORTED_SYMBOLS = [
     "aclhip_order_track_requests_device", "aclhip_decompress_track_batch_rows",
     "aclhip_check_track_map", "aclhip_register_track_map", "aclhip_unregister_track_map", "aclhip_get_track_map_info", "aclhip_decompress_tracks_batch_mapped",
     "aclhip_check_skeleton", "aclhip_register_skeleton", "aclhip_unregister_skeleton", "aclhip_get_skeleton_info", "aclhip_decompress_poses_batch_mapped",
+    "aclhip_check_blend_mask", "aclhip_register_blend_mask", "aclhip_unregister_blend_mask", "aclhip_get_blend_mask_info", "aclhip_decompress_poses_batch_masked",
 ]
 
 
@@ -108,6 +109,18 @@ class PoseMapping(ctypes.Structure):
     ]
 
 
+class BlendMaskInfo(ctypes.Structure):
+    """aclhip_blend_mask_info"""
+    _fields_ = [("num_slots", ctypes.c_uint32), ("num_zero", ctypes.c_uint32), ("num_one", ctypes.c_uint32), ("reserved", ctypes.c_uint32)]
+
+
+class BlendMasking(ctypes.Structure):
+    """aclhip_blend_masking"""
+    _fields_ = [("mode", ctypes.c_uint32), ("reserved0", ctypes.c_uint32), ("instance_masks", ctypes.c_void_p), ("reserved", ctypes.c_uint64 * 2)]
+
+
+BLEND_WEIGHTED, BLEND_LAYERED = 0, 1   # ACLHIP_BLEND_WEIGHTED / ACLHIP_BLEND_LAYERED
+MAX_BLEND_MASKS = 4096      # ACLHIP_MAX_BLEND_MASKS
 MAX_SKELETONS = 1024        # ACLHIP_MAX_SKELETONS
 TRACK_DROPPED = 0xFFFFFFFF  # ACLHIP_TRACK_DROPPED
 MAX_TRACK_MAPS = 16384      # ACLHIP_MAX_TRACK_MAPS
@@ -284,6 +297,11 @@ def load_library():
     lib.aclhip_unregister_skeleton.argtypes = [vp, u32]
     lib.aclhip_get_skeleton_info.argtypes = [vp, u32, ctypes.POINTER(SkeletonInfo)]
     lib.aclhip_decompress_poses_batch_mapped.argtypes = [vp, vp, vp, u32, pparams, ctypes.POINTER(PoseConsumers), ctypes.POINTER(PoseMapping), vp, u64, vp]
+    lib.aclhip_check_blend_mask.argtypes = [vp, u32, ctypes.POINTER(BlendMaskInfo), ctypes.c_char_p, u32]
+    lib.aclhip_register_blend_mask.argtypes = [vp, vp, u32, ctypes.POINTER(u32)]
+    lib.aclhip_unregister_blend_mask.argtypes = [vp, u32]
+    lib.aclhip_get_blend_mask_info.argtypes = [vp, u32, ctypes.POINTER(BlendMaskInfo)]
+    lib.aclhip_decompress_poses_batch_masked.argtypes = [vp, vp, vp, u32, pparams, ctypes.POINTER(PoseConsumers), ctypes.POINTER(PoseMapping), ctypes.POINTER(BlendMasking), vp, u64, vp]
     _lib = lib
     return lib
 
@@ -303,6 +321,17 @@ def check_skeleton(parent_indices, reference_pose, num_bones=None):
     message, info = ctypes.create_string_buffer(256), SkeletonInfo()
     status = load_library().aclhip_check_skeleton(parents.ctypes.data if parents is not None else None, pose.ctypes.data if pose is not None else None,
                                                   num_bones, ctypes.byref(info), message, 256)
+    return status, message.value.decode(), info
+
+
+def check_blend_mask(weights, num_slots=None):
+    """Host only validation of a blend mask (no GPU needed): what aclhip_register_blend_mask checks. weights: float32 [num_slots] in
+    skeleton slot order, or None. Returns (status, message, BlendMaskInfo)."""
+    table = np.ascontiguousarray(weights, dtype=np.float32) if weights is not None else None
+    if num_slots is None:
+        num_slots = table.size if table is not None else 0
+    message, info = ctypes.create_string_buffer(256), BlendMaskInfo()
+    status = load_library().aclhip_check_blend_mask(table.ctypes.data if table is not None else None, int(num_slots), ctypes.byref(info), message, 256)
     return status, message.value.decode(), info
 
 
@@ -654,6 +683,29 @@ class Context:
         params = params if params is not None else default_params()
         self._check(self._lib.aclhip_decompress_poses_batch_mapped(self._handle, clips_ptr, times_ptr, num_instances, ctypes.byref(params), ctypes.byref(consumers),
                                                                   ctypes.byref(mapping) if mapping is not None else None, poses_ptr, pose_stride_bytes, stream))
+
+    # ---- blend masks: a weight per bone for the blends of skeleton space ----
+    def register_blend_mask(self, weights):
+        """weights: host float32 [num_slots] in skeleton slot order, each in [0, 1]. Returns the mask handle (>= 1)."""
+        table = np.ascontiguousarray(weights, dtype=np.float32)
+        handle = ctypes.c_uint32(0)
+        self._check(self._lib.aclhip_register_blend_mask(self._handle, table.ctypes.data, table.size, ctypes.byref(handle)))
+        return handle.value
+
+    def unregister_blend_mask(self, mask):
+        self._check(self._lib.aclhip_unregister_blend_mask(self._handle, mask))
+
+    def blend_mask_info(self, mask):
+        info = BlendMaskInfo()
+        self._check(self._lib.aclhip_get_blend_mask_info(self._handle, mask, ctypes.byref(info)))
+        return info
+
+    def decompress_poses_batch_masked(self, clips_ptr, times_ptr, num_instances, poses_ptr, pose_stride_bytes, consumers, mapping, masking, params=None, stream=None):
+        """aclhip_decompress_poses_batch_masked; `consumers` (PoseConsumers), `mapping` (PoseMapping) and `masking` (BlendMasking) hold device addresses."""
+        params = params if params is not None else default_params()
+        self._check(self._lib.aclhip_decompress_poses_batch_masked(self._handle, clips_ptr, times_ptr, num_instances, ctypes.byref(params), ctypes.byref(consumers),
+                                                                  ctypes.byref(mapping) if mapping is not None else None, ctypes.byref(masking) if masking is not None else None,
+                                                                  poses_ptr, pose_stride_bytes, stream))
 
     def decompress_poses_mapped(self, clips, sample_times, skeletons, maps, num_bones, additive_format=ADDITIVE_NONE, object_space=False, base_clips=None,
                                 base_sample_times=None, base_maps=None, base_poses=None, params=None, out=None, instance_rounding=None, instance_looping=None,

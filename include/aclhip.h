@@ -862,6 +862,74 @@ aclhip_status aclhip_decompress_poses_batch_mapped(aclhip_context* context, cons
 	const aclhip_decompress_params* params, const aclhip_pose_consumers* consumers, const aclhip_pose_mapping* mapping,
 	void* poses, uint64_t pose_stride_bytes, void* stream);
 
+/* ---- blend masks: a weight per bone for the blends of the skeleton space launch ---------------------
+ * A blend of aclhip_pose_consumers has ONE weight per (instance, clip), applied to every bone: an upper-body clip layered over a walk
+ * at 0.5 pulls the legs, which it does not animate and which hold the fill, half way to the reference pose. A registered BLEND MASK is
+ * a table of B floats in skeleton slot order, each in [0, 1] ("layered blend per bone", an avatar mask), and
+ * aclhip_decompress_poses_batch_masked is aclhip_decompress_poses_batch_mapped with an effective weight per (instance, clip, slot).
+ *
+ * aclhip_register_blend_mask: `weights` (HOST, num_slots floats). Refused with ACLHIP_ERROR_INVALID_ARGUMENT before any device call (the
+ * message names the first offending slot): a null pointer, num_slots == 0 or > 0xFFFF, a value that is not finite or lies outside
+ * [0, 1] (subnormals and -0 are inside). Lifetime is a track map's: the device table (ACLHIP_MAX_BLEND_MASKS records) is allocated at
+ * the first registration and never moves, so a captured hipGraph that names a mask stays valid while others come and go; handle 0 is
+ * null ("no mask": every slot 1); uploads go on the context's own stream; unregistration is stream ordered (launches already enqueued
+ * still see the mask, later ones refuse it) and nobody waits. */
+typedef uint32_t aclhip_blend_mask;			/* handle returned by aclhip_register_blend_mask; 0 = none: every slot 1 */
+#define ACLHIP_MAX_BLEND_MASKS 4096u		/* live masks of one context, the null handle included */
+
+typedef struct aclhip_blend_mask_info
+{
+	uint32_t num_slots;
+	uint32_t num_zero;					/* slots whose weight is 0 (+0 or -0) */
+	uint32_t num_one;					/* slots whose weight is 1 */
+	uint32_t reserved;
+} aclhip_blend_mask_info;
+
+/* Host only (no context, no device): what registration checks and what aclhip_get_blend_mask_info reports. `message` (may be NULL,
+ * `message_capacity` bytes) receives the reason when the mask is refused; `out_info` may be NULL. */
+aclhip_status aclhip_check_blend_mask(const float* weights, uint32_t num_slots, aclhip_blend_mask_info* out_info, char* message, uint32_t message_capacity);
+
+aclhip_status aclhip_register_blend_mask(aclhip_context* context, const float* weights, uint32_t num_slots, aclhip_blend_mask* out_mask);
+aclhip_status aclhip_unregister_blend_mask(aclhip_context* context, aclhip_blend_mask mask);
+aclhip_status aclhip_get_blend_mask_info(const aclhip_context* context, aclhip_blend_mask mask, aclhip_blend_mask_info* out_info);
+
+#define ACLHIP_BLEND_WEIGHTED 0u		/* the masked weights are the blend's weights */
+#define ACLHIP_BLEND_LAYERED 1u			/* the clips are layers, clip 0 at the bottom; the masked weight is a layer's opacity */
+
+typedef struct aclhip_blend_masking
+{
+	uint32_t mode;								/* ACLHIP_BLEND_WEIGHTED / ACLHIP_BLEND_LAYERED */
+	uint32_t reserved0;							/* 0 */
+	const aclhip_blend_mask* instance_masks;	/* DEVICE [num_instances * K], laid out like blend_weights; entries may be 0 */
+	uint64_t reserved[2];						/* 0 */
+} aclhip_blend_masking;
+
+/* aclhip_decompress_poses_batch_mapped with a weight per bone. Everything but the weight -- decode, fill, accumulation order, the final
+ * quat_normalize, additive apply, object space walk, refusals -- is that launch's, unchanged. The definition, for instance i with
+ * K = num_blend_clips clips, weights w_k = blend_weights[i * K + k], mask handles h_k = instance_masks[i * K + k] and slot s, all in fp32,
+ * one IEEE operation at a time, never fused:
+ *   1. e_k[s] = w_k when h_k == 0 (no mask), else e_k[s] = w_k * mask(h_k)[s].
+ *   2. ACLHIP_BLEND_WEIGHTED: the weight of clip k at slot s is e_k[s].
+ *      ACLHIP_BLEND_LAYERED: the clips are layers, k = 0 at the bottom, and e is a layer's opacity:
+ *          r = 1; for j = K - 1 down to k + 1: r = r * (1 - e_j[s]);      e'_k[s] = e_k[s] * r
+ *      and the weight of clip k at slot s is e'_k[s]. With e_0 == 1 these weights sum to 1 per bone, whatever the layers above do.
+ *   3. Rotation, translation and scale of slot s follow the blend's operation order (aclhip_pose_consumers) with that weight in the
+ *      place of w_k, quat_normalize at the end included. Nothing is renormalized, and nothing is skipped when a weight is 0 (x * 0 is
+ *      added to the sum: it can turn a -0 into a +0, nothing else).
+ * A slot whose weights are ALL 0 gets what the arithmetic gives -- the normalize of a zero quaternion, 0 / 0 --: the caller must avoid
+ * it (keep clip 0's mask above 0 in weighted mode, e_0 == 1 in layered mode).
+ *   With every handle 0, or with masks that are 1 everywhere, ACLHIP_BLEND_WEIGHTED gives the bits of aclhip_decompress_poses_batch_mapped.
+ *   Refused and counted, the row untouched, on top of every refusal of the mapped launch: a mask handle that is unknown or retired, or
+ * mask.num_slots != B, on any of the K entries of the instance.
+ *   ACLHIP_ERROR_INVALID_ARGUMENT: masking == NULL, an unknown mode, reserved fields that are not 0, instance_masks == NULL,
+ * num_blend_clips < 2, and everything aclhip_decompress_poses_batch_mapped refuses.
+ *   Out of scope (nothing here precludes them): masks on the unmapped aclhip_decompress_poses_batch; masks for the additive apply (an
+ * additive layer's strength per bone); the host convenience form, the C++ mirror in aclhip.hpp and instance lists.
+ *   What it costs: DESIGN.md 4.7 ("Blend masks") and profiles/blend_masks.md (tools/blend_masks.py). */
+aclhip_status aclhip_decompress_poses_batch_masked(aclhip_context* context, const aclhip_clip* clips, const float* sample_times, uint32_t num_instances,
+	const aclhip_decompress_params* params, const aclhip_pose_consumers* consumers, const aclhip_pose_mapping* mapping, const aclhip_blend_masking* masking,
+	void* poses, uint64_t pose_stride_bytes, void* stream);
+
 /* ---- multi-GPU ---------------------------------------------------------------------------------- */
 
 /* Decoding never needs a collective: every GPU decodes its own contiguous shard of the instance list. Only a
