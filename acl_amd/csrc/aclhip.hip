@@ -56,6 +56,7 @@ namespace aclhip
 #include "kernels_misc.inl"
 #include "kernels_scalar.inl"
 #include "kernels_track.inl"
+#include "kernels_bone_object.inl"
 }
 
 // ================================================================================================
@@ -75,4 +76,5 @@ using namespace aclhip;
 #include "host_consumers.inl"
 #include "host_skeletons.inl"
 #include "host_blend_masks.inl"
+#include "host_bone_object.inl"
 #include "host_scalar_misc.inl"

@@ -88,10 +88,13 @@ namespace
 	}
 
 	// The device image of a hierarchy's walk schedules (clips: aclhip_set_clip_hierarchy; skeletons: aclhip_register_skeleton):
-	// [{offset of the schedule, its steps, its words, 0} for 1, 2, 4, 8 instances per workgroup: one 16 byte scalar load tells a wave
+	// [{offset of the schedule, its steps, its words, 0 (first header: offset of the parent table)} for 1, 2, 4, 8 instances per workgroup: one 16 byte scalar load tells a wave
 	// all it needs to request the copy] then per schedule, 16 byte aligned and padded to whole 16 byte pieces (it travels to LDS by DMA):
 	// num_steps | words of this schedule | step_end[num_steps] | transform | parent << 16, in step order (16 bits each: the
 	// consumers' LDS images end at about 3400 transforms; every word of the copy a wave keeps in LDS costs residency)
+	// Behind the four schedules, where no schedule's word count reaches: the hierarchy's PARENT TABLE, one word per transform, parent
+	// (0xFFFF: a root) | number of ancestors << 16 -- what the single bone requests in object space climb (kernels_bone_object.inl: the
+	// schedules are in step order and cannot be indexed by bone). Its offset is the fourth word of the first header.
 	// Returns the words of the longest of the four schedules.
 	uint32_t build_walk_schedule_image(const hierarchy_tree& tree, const uint32_t* parent_indices, uint32_t num_tracks, std::vector<uint32_t>& image)
 	{
@@ -117,6 +120,15 @@ namespace
 			std::copy(step_end.begin(), step_end.end(), image.begin() + offset + 2);
 			std::copy(pairs.begin(), pairs.end(), image.begin() + offset + header_words);
 			max_schedule_words = std::max(max_schedule_words, schedule_words);
+		}
+		const uint32_t parents_offset = uint32_t(image.size());
+		image[3] = parents_offset;
+		image.resize(size_t(parents_offset) + align_to_u32(num_tracks, 4), 0);
+		for (uint32_t i = 0; i < num_tracks; ++i)
+		{
+			// (parents first: the parent's word is complete)
+			const uint32_t ancestors = tree.is_root[i] ? 0u : (image[parents_offset + parent_indices[i]] >> 16) + 1u;
+			image[parents_offset + i] = (tree.is_root[i] ? 0xFFFFu : parent_indices[i]) | (ancestors << 16);
 		}
 		return max_schedule_words;
 	}

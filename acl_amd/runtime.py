@@ -45,6 +45,7 @@ EXPORTED_SYMBOLS = [
     "aclhip_check_track_map", "aclhip_register_track_map", "aclhip_unregister_track_map", "aclhip_get_track_map_info", "aclhip_decompress_tracks_batch_mapped",
     "aclhip_check_skeleton", "aclhip_register_skeleton", "aclhip_unregister_skeleton", "aclhip_get_skeleton_info", "aclhip_decompress_poses_batch_mapped",
     "aclhip_check_blend_mask", "aclhip_register_blend_mask", "aclhip_unregister_blend_mask", "aclhip_get_blend_mask_info", "aclhip_decompress_poses_batch_masked",
+    "aclhip_decompress_track_object_batch", "aclhip_decompress_bone_object_batch_mapped", "aclhip_plan_bone_chain",
 ]
 
 
@@ -302,6 +303,9 @@ def load_library():
     lib.aclhip_unregister_blend_mask.argtypes = [vp, u32]
     lib.aclhip_get_blend_mask_info.argtypes = [vp, u32, ctypes.POINTER(BlendMaskInfo)]
     lib.aclhip_decompress_poses_batch_masked.argtypes = [vp, vp, vp, u32, pparams, ctypes.POINTER(PoseConsumers), ctypes.POINTER(PoseMapping), ctypes.POINTER(BlendMasking), vp, u64, vp]
+    lib.aclhip_decompress_track_object_batch.argtypes = [vp, vp, vp, vp, u32, pparams, vp, vp]
+    lib.aclhip_decompress_bone_object_batch_mapped.argtypes = [vp, vp, vp, vp, u32, pparams, ctypes.POINTER(PoseMapping), vp, vp]
+    lib.aclhip_plan_bone_chain.argtypes = [vp, u32, u32, vp, u32, ctypes.POINTER(u32)]
     _lib = lib
     return lib
 
@@ -440,6 +444,25 @@ def plan_hierarchy_walk(parent_indices, transforms_per_step):
     if status != 0:
         raise AclHipError(status, "aclhip_plan_hierarchy_walk: transforms must be sorted parent first")
     return num_steps.value, steps
+
+
+def plan_bone_chain(parent_indices, bone, chain_capacity=None, query_length_only=False):
+    """aclhip_plan_bone_chain (host only): the chain of `bone`, root first, as the object space single bone requests walk it.
+    query_length_only: passes a NULL chain and returns the length alone."""
+    parents = np.ascontiguousarray(parent_indices, dtype=np.uint32)
+    length = ctypes.c_uint32(0)
+    lib = load_library()
+    if query_length_only:
+        status = lib.aclhip_plan_bone_chain(parents.ctypes.data, parents.size, int(bone), None, 0, ctypes.byref(length))
+        if status != 0:
+            raise AclHipError(status, "aclhip_plan_bone_chain")
+        return length.value
+    capacity = int(chain_capacity) if chain_capacity is not None else max(parents.size, 1)
+    chain = np.full(max(capacity, 1), 0xFFFFFFFF, dtype=np.uint32)
+    status = lib.aclhip_plan_bone_chain(parents.ctypes.data, parents.size, int(bone), chain.ctypes.data, capacity, ctypes.byref(length))
+    if status != 0:
+        raise AclHipError(status, "aclhip_plan_bone_chain: transforms sorted parent first, bone < num_tracks, a chain that fits")
+    return chain[:length.value].copy()
 
 
 def default_params(**overrides):
@@ -792,6 +815,17 @@ class Context:
     def decompress_track_batch(self, clips_ptr, times_ptr, tracks_ptr, num_instances, out_ptr, params=None, stream=None):
         params = params if params is not None else default_params()
         self._check(self._lib.aclhip_decompress_track_batch(self._handle, clips_ptr, times_ptr, tracks_ptr, num_instances, ctypes.byref(params), out_ptr, stream))
+
+    def decompress_track_object_batch(self, clips_ptr, times_ptr, tracks_ptr, num_requests, out_ptr, params=None, stream=None):
+        """aclhip_decompress_track_object_batch: one bone per request in OBJECT space (device pointers, 48 bytes per request)."""
+        params = params if params is not None else default_params()
+        self._check(self._lib.aclhip_decompress_track_object_batch(self._handle, clips_ptr, times_ptr, tracks_ptr, num_requests, ctypes.byref(params), out_ptr, stream))
+
+    def decompress_bone_object_batch_mapped(self, clips_ptr, times_ptr, slots_ptr, num_requests, out_ptr, mapping, params=None, stream=None):
+        """aclhip_decompress_bone_object_batch_mapped: one skeleton slot per request in object space; `mapping` (PoseMapping) holds device addresses."""
+        params = params if params is not None else default_params()
+        self._check(self._lib.aclhip_decompress_bone_object_batch_mapped(self._handle, clips_ptr, times_ptr, slots_ptr, num_requests, ctypes.byref(params),
+                                                                         ctypes.byref(mapping), out_ptr, stream))
 
     def order_track_requests_device(self, clips_ptr, times_ptr, tracks_ptr, num_requests, order_ptr, out_clips_ptr=None, out_times_ptr=None, out_tracks_ptr=None,
                                     out_positions_ptr=None, stream=None):

@@ -489,8 +489,8 @@ typedef struct aclhip_track_mapping
  * permutation measured 297 us on the same batch. Decode + one scatter pass, what a caller did before, takes 285 / 296 / 382 / 346 us for the
  * four cases: the mapped launch is 2.0 to 4.0 x faster than that, but it is not free.
  *   The pose consumers take maps through aclhip_decompress_poses_batch_mapped (skeletons, below). Still not mapped (the handle does not
- * preclude them): instance lists (aclhip_decompress_tracks_list), single track requests, scalar track lists, the host convenience
- * forms. ACLHIP_DECODE_FAST is accepted and changes nothing. */
+ * preclude them): instance lists (aclhip_decompress_tracks_list), local space single track requests (the object space ones take maps:
+ * aclhip_decompress_bone_object_batch_mapped), scalar track lists, the host convenience forms. ACLHIP_DECODE_FAST is accepted and changes nothing. */
 aclhip_status aclhip_decompress_tracks_batch_mapped(aclhip_context* context, const aclhip_clip* clips, const float* sample_times, uint32_t num_instances,
 	const aclhip_decompress_params* params, const aclhip_output_desc* output, const aclhip_track_mapping* mapping, void* poses, uint64_t pose_stride_bytes, void* stream);
 
@@ -861,6 +861,65 @@ typedef struct aclhip_pose_mapping
 aclhip_status aclhip_decompress_poses_batch_mapped(aclhip_context* context, const aclhip_clip* clips, const float* sample_times, uint32_t num_instances,
 	const aclhip_decompress_params* params, const aclhip_pose_consumers* consumers, const aclhip_pose_mapping* mapping,
 	void* poses, uint64_t pose_stride_bytes, void* stream);
+
+/* ---- single bone requests in object space ------------------------------------------------------------
+ * aclhip_decompress_track_batch returns a bone relative to its parent; a weapon socket, a camera on a head, a foot IK target or a hit
+ * volume needs it in OBJECT space. These two launches return exactly that, without decoding and writing the whole pose: request k
+ * writes one QVV48 record at (char*)transforms + k * 48. All pointers are DEVICE pointers; asynchronous on `stream`.
+ *
+ * aclhip_decompress_track_object_batch, by definition: transform k is record track_indices[k] of the row that
+ * aclhip_decompress_poses_batch writes for (clips[k], sample_times[k]) under the same `params` with additive_format = NONE,
+ * object_space = 1, no blend and default flags -- bit for bit. The operation order, with the clip's hierarchy from
+ * aclhip_set_clip_hierarchy and the chain c_0 (a root) ... c_d = the bone:
+ *     obj = local[c_0]                                   as decoded, nothing applied to it
+ *     for j = 1 .. d:  obj = qvv_mul(local[c_j], obj)    child first, then parent; through rtm::qvv_mul's matrix route exactly where a
+ *                                                        scale of either side is negative (aclhip_get_negative_scale_count's rule)
+ *                      obj.rotation = quat_normalize(obj.rotation)
+ * all in fp32, one IEEE operation at a time, never fused: what the object space walk does per (child, parent) pair. The seek runs once
+ * per request; depth(bone) + 1 transforms are decoded, 48 bytes are written.
+ *   `params` is restricted as for the pose consumers -- the track_writer's own default sub-track modes, no per track rounding,
+ * normalization != always -- else ACLHIP_ERROR_INVALID_ARGUMENT. instance_rounding_policies and instance_looping_policies are indexed
+ * by REQUEST, as in aclhip_decompress_track_batch. ACLHIP_DECODE_FAST and ACLHIP_CONSUMERS_FAST have no meaning here.
+ *
+ * aclhip_decompress_bone_object_batch_mapped, by definition: transform k is record bone_slots[k] of the row that
+ * aclhip_decompress_poses_batch_mapped writes with additive_format = NONE, object_space = 1 and no blend. mapping->skeleton /
+ * instance_skeletons and mapping->map / instance_maps are indexed by request; blend_maps and base_maps must be NULL. The chain runs
+ * over skeleton slots with the skeleton's parents; local[s] = decode(c, t)[track] where the map sends `track` to slot s, or the
+ * reference pose R[s] where no track maps to the slot. A skeleton whose R holds a negative scale takes the matrix route like a clip
+ * that can decode one.
+ *
+ *   Refused and counted (aclhip_get_rejected_instance_count), the request's 48 bytes left untouched: an unknown or scalar clip; a clip
+ * without a hierarchy (unmapped form) or a skeleton registered without one (mapped form); track_index >= num_tracks or bone_slot >=
+ * num_bones; an unknown or retired skeleton or map handle; map.num_tracks != clip.num_tracks or map.num_slots != num_bones. No request
+ * writes outside its own 48 bytes, whatever the device arrays hold. Nothing is uploaded at launch time: a captured hipGraph replays
+ * while clips come and go (a clip or skeleton that may hand out a negative scale, registered behind the back of a launch captured
+ * without the matrix route, is refused and counted, as the pose consumers do).
+ *   The launches do NOT add to aclhip_get_negative_scale_count: requests share ancestors -- four sockets of one character walk the same
+ * spine -- so a count of matrix products per launch would mean nothing.
+ *   ACLHIP_ERROR_INVALID_ARGUMENT: null lists, transforms not 16 byte aligned, the params above; mapped form: mapping == NULL, no
+ * skeleton (a null handle without instance_skeletons), no map, blend_maps or base_maps set.
+ *   Out of scope (nothing here precludes them): blends, additive bases and masks per request; a _rows form; locality ordering of these
+ * lists (aclhip_order_track_requests_for_locality / _device already order any (clip, time, index) list); the host convenience form; the
+ * C++ mirror in aclhip.hpp.
+ *   What it costs: MI355X, 65 536 characters of one 100-bone clip, character-major lists, against today's route (object space poses into
+ * full rows, then a gather of the requested records; tools/socket_requests.py, profiles/socket_requests.md): one socket
+ * per character 8.5 us shallow (depth 3) / 19.3 us deep (depth 11) against 99 us = 11.7 x / 5.1 x; four sockets 11.7 / 35.4 us against
+ * 106 - 110 us = 9.3 x / 3.0 x; sixteen 43.5 / 120.3 us against 133 - 139 us = 3.2 x / 1.1 x. Over 256 clips as drawn the launch takes
+ * about twice as long (1 socket 17.7 / 41.6 us, 4 sockets 20.9 / 59.6 us: 5.9 - 1.9 x). SIXTEEN DEEP SOCKETS PER CHARACTER DO NOT BEAT THE
+ * WHOLE-POSE ROUTE: 1.11 x on one clip (inside the spread of the measurement) and 0.78 x over 256 clips (176 against 138 us) -- past
+ * roughly a hundred chain transforms per character decode the pose and gather. Sockets that share ancestors decode them once each;
+ * the per level decode is per lane, not packed across the wave (DESIGN.md 4.3 says what that leaves on the table). */
+aclhip_status aclhip_decompress_track_object_batch(aclhip_context* context, const aclhip_clip* clips, const float* sample_times, const uint32_t* track_indices,
+	uint32_t num_requests, const aclhip_decompress_params* params, void* transforms, void* stream);
+aclhip_status aclhip_decompress_bone_object_batch_mapped(aclhip_context* context, const aclhip_clip* clips, const float* sample_times, const uint32_t* bone_slots,
+	uint32_t num_requests, const aclhip_decompress_params* params, const aclhip_pose_mapping* mapping, void* transforms, void* stream);
+
+/* Host only (no context, no device, like aclhip_plan_hierarchy_walk): the chain the launches above walk for `bone`, root first, under
+ * the rules of aclhip_set_clip_hierarchy -- transform 0 is a root whatever parent_indices[0] says, ACLHIP_NO_PARENT marks further
+ * roots. *out_length: transforms on the chain, the bone included (depth + 1). out_chain (chain_capacity entries) may be NULL to query
+ * the length only. ACLHIP_ERROR_INVALID_ARGUMENT when a transform of the hierarchy precedes its parent, bone >= num_tracks, or
+ * chain_capacity is too small. */
+aclhip_status aclhip_plan_bone_chain(const uint32_t* parent_indices, uint32_t num_tracks, uint32_t bone, uint32_t* out_chain, uint32_t chain_capacity, uint32_t* out_length);
 
 /* ---- blend masks: a weight per bone for the blends of the skeleton space launch ---------------------
  * A blend of aclhip_pose_consumers has ONE weight per (instance, clip), applied to every bone: an upper-body clip layered over a walk
