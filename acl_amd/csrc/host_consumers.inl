@@ -302,68 +302,49 @@ extern "C" aclhip_status aclhip_set_clip_hierarchy(aclhip_context* context, aclh
 
 namespace
 {
-	// the skeleton space kernels: a function of its own, like mapped_pose_kernel_of. The instantiations launch_consumers selects for the
-	// unmapped launch, minus the rotation | translation images and ACLHIP_CONSUMERS_FAST.
-	typedef void (*skeleton_pose_kernel)(const device_clip*, uint32_t, const uint32_t*, const float*, uint32_t, decode_params, consumer_params, uint8_t*, uint64_t, uint32_t, uint32_t, uint32_t, unsigned long long*, skeleton_launch);
+	// The three entry points of the pose consumers (kernels_consumers.inl, kernels_skeleton.inl) share their leading arguments; the
+	// skeleton space kernels take the mapping behind them, the masked ones the masking behind that
+	template<class... trailing_types>
+	using pose_consumer_kernel = void (*)(const device_clip*, uint32_t, const uint32_t*, const float*, uint32_t, decode_params, consumer_params, uint8_t*, uint64_t, uint32_t, uint32_t, uint32_t, unsigned long long*, trailing_types...);
 
-	template<bool kObjectSpace, bool kBlend>
-	skeleton_pose_kernel skeleton_pose_kernel_of_base(uint32_t base_kind, bool mirrored)
+	template<class function_type>
+	auto with_constant(bool value, function_type function)
 	{
-		// rtm::qvv_mul's matrix route only where transforms are multiplied: object space, or the relative format (a base buffer, a second
-		// wave's image); a caller's base buffer always has it
-		switch (base_kind)
+		return value ? function(std::true_type()) : function(std::false_type());
+	}
+
+	// rtm::qvv_mul's matrix route (kMirrored) is compiled in only where transforms are multiplied -- object space, or the relative format (a
+	// base buffer, a second wave's image) -- and a caller's base buffer, of which the library knows nothing, always has it
+	constexpr bool matrix_route_of(bool object_space, uint32_t base_kind, bool mirrored)
+	{
+		const bool multiplies_transforms = object_space || base_kind == k_consumer_base_buffer || base_kind == k_consumer_base_second_wave;
+		return base_kind == k_consumer_base_buffer || (mirrored && multiplies_transforms);
+	}
+
+	// A launch's facts -> the instantiation of one of the entry points: instantiation_of(object space, kind of base, matrix route), each
+	// an integral_constant. Only the combinations matrix_route_of can give are instantiated; a blend's base clip is never fused: no such
+	// instantiation, a null pointer.
+	template<class kernel_type, bool kBlend, class instantiation_type>
+	kernel_type pose_consumer_kernel_of(bool object_space, uint32_t base_kind, bool mirrored, instantiation_type instantiation_of)
+	{
+		const bool matrix_route = matrix_route_of(object_space, base_kind, mirrored);
+		return with_constant(object_space, [&](auto space) { return with_constant(matrix_route, [&](auto route)
 		{
-		case k_consumer_base_none:
-			if constexpr (kObjectSpace)
-				return mirrored ? decompress_poses_skeleton_kernel<true, k_consumer_base_none, true, kBlend> : decompress_poses_skeleton_kernel<true, k_consumer_base_none, false, kBlend>;
-			return decompress_poses_skeleton_kernel<false, k_consumer_base_none, false, kBlend>;
-		case k_consumer_base_buffer:
-			return decompress_poses_skeleton_kernel<kObjectSpace, k_consumer_base_buffer, true, kBlend>;
-		case k_consumer_base_second_wave:
-			return mirrored ? decompress_poses_skeleton_kernel<kObjectSpace, k_consumer_base_second_wave, true, kBlend> : decompress_poses_skeleton_kernel<kObjectSpace, k_consumer_base_second_wave, false, kBlend>;
-		default:
-			if constexpr (!kBlend)
+			const auto of_base = [&](auto base) -> kernel_type
 			{
-				if constexpr (kObjectSpace)
-					return mirrored ? decompress_poses_skeleton_kernel<true, k_consumer_base_fused, true, false> : decompress_poses_skeleton_kernel<true, k_consumer_base_fused, false, false>;
-				return decompress_poses_skeleton_kernel<false, k_consumer_base_fused, false, false>;
+				if constexpr (matrix_route_of(decltype(space)::value, decltype(base)::value, decltype(route)::value) != decltype(route)::value || (kBlend && decltype(base)::value == k_consumer_base_fused))
+					return nullptr;		// (never selected: not instantiated)
+				else
+					return instantiation_of(space, base, route);
+			};
+			switch (base_kind)
+			{
+			case k_consumer_base_none: return of_base(std::integral_constant<uint32_t, k_consumer_base_none>());
+			case k_consumer_base_buffer: return of_base(std::integral_constant<uint32_t, k_consumer_base_buffer>());
+			case k_consumer_base_second_wave: return of_base(std::integral_constant<uint32_t, k_consumer_base_second_wave>());
+			default: return of_base(std::integral_constant<uint32_t, k_consumer_base_fused>());
 			}
-			return nullptr;		// (a blend's base clip is never fused)
-		}
-	}
-
-	skeleton_pose_kernel skeleton_pose_kernel_of(bool object_space, uint32_t base_kind, bool mirrored, bool blend)
-	{
-		if (object_space)
-			return blend ? skeleton_pose_kernel_of_base<true, true>(base_kind, mirrored) : skeleton_pose_kernel_of_base<true, false>(base_kind, mirrored);
-		return blend ? skeleton_pose_kernel_of_base<false, true>(base_kind, mirrored) : skeleton_pose_kernel_of_base<false, false>(base_kind, mirrored);
-	}
-
-	// the masked blends of skeleton space (aclhip_decompress_poses_batch_masked): kernels of their own, the masking behind the mapping
-	typedef void (*masked_pose_kernel)(const device_clip*, uint32_t, const uint32_t*, const float*, uint32_t, decode_params, consumer_params, uint8_t*, uint64_t, uint32_t, uint32_t, uint32_t, unsigned long long*, skeleton_launch, blend_mask_launch);
-
-	template<bool kObjectSpace>
-	masked_pose_kernel masked_pose_kernel_of_base(uint32_t base_kind, bool mirrored)
-	{
-		// (skeleton_pose_kernel_of_base's choices for a blend)
-		switch (base_kind)
-		{
-		case k_consumer_base_none:
-			if constexpr (kObjectSpace)
-				return mirrored ? decompress_poses_masked_kernel<true, k_consumer_base_none, true> : decompress_poses_masked_kernel<true, k_consumer_base_none, false>;
-			return decompress_poses_masked_kernel<false, k_consumer_base_none, false>;
-		case k_consumer_base_buffer:
-			return decompress_poses_masked_kernel<kObjectSpace, k_consumer_base_buffer, true>;
-		case k_consumer_base_second_wave:
-			return mirrored ? decompress_poses_masked_kernel<kObjectSpace, k_consumer_base_second_wave, true> : decompress_poses_masked_kernel<kObjectSpace, k_consumer_base_second_wave, false>;
-		default:
-			return nullptr;		// (a blend's base clip is never fused)
-		}
-	}
-
-	masked_pose_kernel masked_pose_kernel_of(bool object_space, uint32_t base_kind, bool mirrored)
-	{
-		return object_space ? masked_pose_kernel_of_base<true>(base_kind, mirrored) : masked_pose_kernel_of_base<false>(base_kind, mirrored);
+		}); });
 	}
 
 	// `mapping` (aclhip_decompress_poses_batch_mapped): skeleton space -- the launch is shaped by its rows alone (pose_stride_bytes / 48
@@ -474,86 +455,46 @@ namespace
 
 		// one instantiation per (object space, kind of base, rotation | translation images)
 		const uint32_t base_kind = !has_base ? k_consumer_base_none : (!base_is_clip ? k_consumer_base_buffer : (fused_base ? k_consumer_base_fused : k_consumer_base_second_wave));
-		typedef void (*consumer_kernel)(const device_clip*, uint32_t, const uint32_t*, const float*, uint32_t, decode_params, consumer_params, uint8_t*, uint64_t, uint32_t, uint32_t, uint32_t, unsigned long long*);
 		// rtm::qvv_mul's matrix route (negative scales) is compiled into the launches that can meet one: a registered clip whose scale
 		// sub-tracks may decode below zero, or a base the library knows nothing about (a caller's pose buffer)
 		// (skeleton space: the reference pose fills slots -- like a clip whose scales registration has looked at)
 		const bool mirrored = context->num_negative_scale_clips != 0 || (has_base && !base_is_clip) || (mapping != nullptr && context->num_negative_scale_skeletons != 0);
-		static const consumer_kernel kernels[2][2][4] =
+		const bool object_space = consumers.object_space != 0;
+		// above the default limit of dynamic LDS the kernel has to be told; trailing: the mapping, the masking
+		const auto launch = [&](auto kernel, const auto&... trailing) -> aclhip_status
 		{
-			{
-				{ decompress_poses_consumer_kernel<false, k_consumer_base_none, false, false>, decompress_poses_consumer_kernel<false, k_consumer_base_buffer, false, false>,
-				  decompress_poses_consumer_kernel<false, k_consumer_base_second_wave, false, false>, decompress_poses_consumer_kernel<false, k_consumer_base_fused, false, false> },
-				{ decompress_poses_consumer_kernel<true, k_consumer_base_none, false, false>, decompress_poses_consumer_kernel<true, k_consumer_base_buffer, false, false>,
-				  decompress_poses_consumer_kernel<true, k_consumer_base_second_wave, false, false>, decompress_poses_consumer_kernel<true, k_consumer_base_fused, false, false> },
-			},
-			{
-				// (no object space: only the relative format multiplies transforms -- a base buffer or a second wave's image)
-				{ decompress_poses_consumer_kernel<false, k_consumer_base_none, false, false>, decompress_poses_consumer_kernel<false, k_consumer_base_buffer, false, true>,
-				  decompress_poses_consumer_kernel<false, k_consumer_base_second_wave, false, true>, decompress_poses_consumer_kernel<false, k_consumer_base_fused, false, false> },
-				{ decompress_poses_consumer_kernel<true, k_consumer_base_none, false, true>, decompress_poses_consumer_kernel<true, k_consumer_base_buffer, false, true>,
-				  decompress_poses_consumer_kernel<true, k_consumer_base_second_wave, false, true>, decompress_poses_consumer_kernel<true, k_consumer_base_fused, false, true> },
-			},
+			if (kernel == nullptr)
+				return fail(context, ACLHIP_ERROR_INVALID_ARGUMENT, "no pose consumer kernel for base kind %u", base_kind);
+			if (lds_bytes > 64 * 1024 - 128)
+				ACLHIP_CHECK_HIP(context, hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, int(k_lds_bytes)));
+			hipLaunchKernelGGL(kernel, dim3(num_blocks), dim3(waves_per_block * k_wave_size), lds_bytes, stream,
+				context->d_clips, context->d_clips_capacity, clips, sample_times, num_instances, params, device_consumers,
+				static_cast<uint8_t*>(poses), pose_stride_bytes, lds_quads_per_image, uint32_t(lds_bytes_per_instance), log2_instances_per_block | (lds_schedule_words << 8), context->d_rejected, trailing...);
+			ACLHIP_CHECK_HIP(context, hipGetLastError());
+			return ACLHIP_OK;
 		};
-		// the same with a blend in front (never fused, never rotation | translation images)
-		static const consumer_kernel blend_kernels[2][2][3] =
-		{
-			{
-				{ decompress_poses_consumer_kernel<false, k_consumer_base_none, false, false, true>, decompress_poses_consumer_kernel<false, k_consumer_base_buffer, false, true, true>,
-				  decompress_poses_consumer_kernel<false, k_consumer_base_second_wave, false, false, true> },
-				{ decompress_poses_consumer_kernel<true, k_consumer_base_none, false, false, true>, decompress_poses_consumer_kernel<true, k_consumer_base_buffer, false, true, true>,
-				  decompress_poses_consumer_kernel<true, k_consumer_base_second_wave, false, false, true> },
-			},
-			{
-				{ decompress_poses_consumer_kernel<false, k_consumer_base_none, false, false, true>, decompress_poses_consumer_kernel<false, k_consumer_base_buffer, false, true, true>,
-				  decompress_poses_consumer_kernel<false, k_consumer_base_second_wave, false, true, true> },
-				{ decompress_poses_consumer_kernel<true, k_consumer_base_none, false, true, true>, decompress_poses_consumer_kernel<true, k_consumer_base_buffer, false, true, true>,
-				  decompress_poses_consumer_kernel<true, k_consumer_base_second_wave, false, true, true> },
-			},
-		};
-		// ACLHIP_CONSUMERS_FAST: object space launches without a blend, in the hardware's 1 ulp arithmetic (include/aclhip.h)
-		const bool fast = mapping == nullptr && (consumers.flags & ACLHIP_CONSUMERS_FAST) != 0 && consumers.object_space != 0 && !blend;
-		static const consumer_kernel fast_kernels[2][4] =
-		{
-			{ decompress_poses_consumer_kernel<true, k_consumer_base_none, false, false, false, true>, decompress_poses_consumer_kernel<true, k_consumer_base_buffer, false, true, false, true>,
-			  decompress_poses_consumer_kernel<true, k_consumer_base_second_wave, false, false, false, true>, decompress_poses_consumer_kernel<true, k_consumer_base_fused, false, false, false, true> },
-			{ decompress_poses_consumer_kernel<true, k_consumer_base_none, false, true, false, true>, decompress_poses_consumer_kernel<true, k_consumer_base_buffer, false, true, false, true>,
-			  decompress_poses_consumer_kernel<true, k_consumer_base_second_wave, false, true, false, true>, decompress_poses_consumer_kernel<true, k_consumer_base_fused, false, true, false, true> },
-		};
-		const consumer_kernel kernel = fast ? (unit_scale ? decompress_poses_consumer_kernel<true, k_consumer_base_none, true, false, false, true> : fast_kernels[mirrored ? 1 : 0][base_kind])
-			: unit_scale ? decompress_poses_consumer_kernel<true, k_consumer_base_none, true, false>
-			: (blend ? blend_kernels[mirrored ? 1 : 0][consumers.object_space != 0 ? 1 : 0][base_kind] : kernels[mirrored ? 1 : 0][consumers.object_space != 0 ? 1 : 0][base_kind]);
 		if (masking != nullptr)
-		{
-			const masked_pose_kernel masked_kernel = masked_pose_kernel_of(consumers.object_space != 0, base_kind, mirrored);
-			if (masked_kernel == nullptr)
-				return fail(context, ACLHIP_ERROR_INVALID_ARGUMENT, "no masked kernel for base kind %u", base_kind);
-			if (lds_bytes > 64 * 1024 - 128)
-				ACLHIP_CHECK_HIP(context, hipFuncSetAttribute(reinterpret_cast<const void*>(masked_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, int(k_lds_bytes)));
-			hipLaunchKernelGGL(masked_kernel, dim3(num_blocks), dim3(waves_per_block * k_wave_size), lds_bytes, stream,
-				context->d_clips, context->d_clips_capacity, clips, sample_times, num_instances, params, device_consumers,
-				static_cast<uint8_t*>(poses), pose_stride_bytes, lds_quads_per_image, uint32_t(lds_bytes_per_instance), log2_instances_per_block | (lds_schedule_words << 8), context->d_rejected, device_mapping, device_masking);
-			ACLHIP_CHECK_HIP(context, hipGetLastError());
-			return ACLHIP_OK;
-		}
+			return launch(pose_consumer_kernel_of<pose_consumer_kernel<skeleton_launch, blend_mask_launch>, true>(object_space, base_kind, mirrored, [](auto space, auto base, auto route)
+				{ return decompress_poses_masked_kernel<space(), base(), route()>; }), device_mapping, device_masking);
 		if (mapping != nullptr)
-		{
-			const skeleton_pose_kernel skeleton_kernel = skeleton_pose_kernel_of(consumers.object_space != 0, base_kind, mirrored, blend);
-			if (lds_bytes > 64 * 1024 - 128)
-				ACLHIP_CHECK_HIP(context, hipFuncSetAttribute(reinterpret_cast<const void*>(skeleton_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, int(k_lds_bytes)));
-			hipLaunchKernelGGL(skeleton_kernel, dim3(num_blocks), dim3(waves_per_block * k_wave_size), lds_bytes, stream,
-				context->d_clips, context->d_clips_capacity, clips, sample_times, num_instances, params, device_consumers,
-				static_cast<uint8_t*>(poses), pose_stride_bytes, lds_quads_per_image, uint32_t(lds_bytes_per_instance), log2_instances_per_block | (lds_schedule_words << 8), context->d_rejected, device_mapping);
-			ACLHIP_CHECK_HIP(context, hipGetLastError());
-			return ACLHIP_OK;
-		}
-		if (lds_bytes > 64 * 1024 - 128)		// above the default limit
-			ACLHIP_CHECK_HIP(context, hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, int(k_lds_bytes)));
-		hipLaunchKernelGGL(kernel, dim3(num_blocks), dim3(waves_per_block * k_wave_size), lds_bytes, stream,
-			context->d_clips, context->d_clips_capacity, clips, sample_times, num_instances, params, device_consumers,
-			static_cast<uint8_t*>(poses), pose_stride_bytes, lds_quads_per_image, uint32_t(lds_bytes_per_instance), log2_instances_per_block | (lds_schedule_words << 8), context->d_rejected);
-		ACLHIP_CHECK_HIP(context, hipGetLastError());
-		return ACLHIP_OK;
+			return launch(blend
+				? pose_consumer_kernel_of<pose_consumer_kernel<skeleton_launch>, true>(object_space, base_kind, mirrored, [](auto space, auto base, auto route)
+					{ return decompress_poses_skeleton_kernel<space(), base(), route(), true>; })
+				: pose_consumer_kernel_of<pose_consumer_kernel<skeleton_launch>, false>(object_space, base_kind, mirrored, [](auto space, auto base, auto route)
+					{ return decompress_poses_skeleton_kernel<space(), base(), route(), false>; }), device_mapping);
+		// ACLHIP_CONSUMERS_FAST: object space launches without a blend, in the hardware's 1 ulp arithmetic (include/aclhip.h)
+		const bool fast = (consumers.flags & ACLHIP_CONSUMERS_FAST) != 0 && object_space && !blend;
+		// one instantiation per (object space, kind of base, matrix route); rotation | translation images: object space without a base only
+		if (unit_scale)
+			return launch(fast ? decompress_poses_consumer_kernel<true, k_consumer_base_none, true, false, false, true> : decompress_poses_consumer_kernel<true, k_consumer_base_none, true, false>);
+		if (blend)
+			return launch(pose_consumer_kernel_of<pose_consumer_kernel<>, true>(object_space, base_kind, mirrored, [](auto space, auto base, auto route)
+				{ return decompress_poses_consumer_kernel<space(), base(), false, route(), true>; }));
+		if (fast)		// (object space, see above)
+			return launch(pose_consumer_kernel_of<pose_consumer_kernel<>, false>(true, base_kind, mirrored, [](auto, auto base, auto route)
+				{ return decompress_poses_consumer_kernel<true, base(), false, route(), false, true>; }));
+		return launch(pose_consumer_kernel_of<pose_consumer_kernel<>, false>(object_space, base_kind, mirrored, [](auto space, auto base, auto route)
+			{ return decompress_poses_consumer_kernel<space(), base(), false, route()>; }));
 	}
 }
 

@@ -131,25 +131,38 @@
 		return f32x4{ (value.x * weight) + accumulated.x, (value.y * weight) + accumulated.y, (value.z * weight) + accumulated.z, 0.0f };
 	}
 
+	// A clip's weight in a blend, asked per transform (slot): one weight for the whole pose here, a weight per slot under blend masks
+	// (slot_weight, kernels_skeleton.inl)
+	struct uniform_weight
+	{
+		float weight;
+		__device__ __forceinline__ float operator()(uint32_t) const { return weight; }
+	};
+
+	// (entry.track_index is the transform the quad belongs to: the track, or the slot behind a slot_image_writer)
+	template<class weight_type>
 	struct blend_image_writer
 	{
 		f32x4* image;
-		float weight;
+		weight_type weight;
 		__device__ __forceinline__ void operator()(const clip_range_entry& entry, float4 value) const
 		{
 			const uint32_t quad = entry.quad_index;
-			image[quad] = blend_accumulate(quad - entry.track_index * 3u, image[quad], value, weight);
+			image[quad] = blend_accumulate(quad - entry.track_index * 3u, image[quad], value, weight(entry.track_index));
 		}
 	};
 
 	// the first clip's pose, complete in `image`, times its weight
-	__device__ __forceinline__ void blend_scale_image(f32x4* image, uint32_t num_quads, float weight, uint32_t lane)
+	template<class weight_type>
+	__device__ __forceinline__ void blend_scale_image(f32x4* image, uint32_t num_quads, const weight_type& weight, uint32_t lane)
 	{
 		for (uint32_t quad = lane; quad < num_quads; quad += k_wave_size)
 		{
+			const uint32_t transform_index = quad / 3u;
+			const float transform_weight = weight(transform_index);
 			const f32x4 value = image[quad];
-			const bool is_rotation = quad % 3u == 0;
-			image[quad] = f32x4{ value.x * weight, value.y * weight, value.z * weight, is_rotation ? value.w * weight : 0.0f };
+			const bool is_rotation = quad - transform_index * 3u == 0;
+			image[quad] = f32x4{ value.x * transform_weight, value.y * transform_weight, value.z * transform_weight, is_rotation ? value.w * transform_weight : 0.0f };
 		}
 	}
 
@@ -169,7 +182,7 @@
 			}
 			image[quad] = blend_accumulate(quad - (quad / 3u) * 3u, image[quad], value, weight);
 		}
-		decode_animated_into_image(clip, sample_time, rounding_policy, params, lane, blend_image_writer{ image, weight });
+		decode_animated_into_image(clip, sample_time, rounding_policy, params, lane, blend_image_writer<uniform_weight>{ image, uniform_weight{ weight } });
 	}
 
 	__device__ __forceinline__ void blend_normalize_rotations(f32x4* image, uint32_t num_tracks, uint32_t lane)
@@ -246,6 +259,292 @@
 	//                  none can occur (scales that are sums and products of non negative values).
 	constexpr uint32_t k_consumer_base_none = 0, k_consumer_base_buffer = 1, k_consumer_base_second_wave = 2, k_consumer_base_fused = 3;
 
+	// The walk schedule for this many instances per workgroup, requested BEFORE the decode (until round 4 behind it: three
+	// more dependent round trips -- offset, header, words -- at the end of every wave's chain, 1.7 of a decode's 6.3 us).
+	// One scalar load for the schedule's header (aclhip_set_clip_hierarchy: {offset, steps, words, 0} per workgroup size,
+	// in flight next to the seek's sample records), then the words travel global -> LDS by DMA while the pose is decoded:
+	//     num_steps | words | step_end[num_steps] | transform | parent << 16 in step order, padded to whole 16 byte pieces
+	// Every wave leaves its schedule in the shared copy: the same words when they share it (the copy is only used then).
+	// A schedule longer than the launch reserved LDS for (a hierarchy set behind a captured launch's back) stays in
+	// global memory and the walk reads it there (bit 31 of the slot's levels). Steps and schedule go into the walk's slots now,
+	// not into registers held across the decodes.
+	__device__ __forceinline__ void request_walk_schedule(const uint32_t* hierarchy, uint32_t log2_instances_per_block, uint32_t reserved_words, uint32_t* shared_schedule,
+		uint32_t slot, uint32_t lane, consumer_walk_slots& walk)
+	{
+		const u32x4 header = ((const ACLHIP_CONSTANT u32x4*)hierarchy)[log2_instances_per_block];
+		uint32_t schedule_offset = header.x, num_levels = header.y, num_words = header.z;
+		// (registers of their own: a block of four lives as long as any of its fields and is spilled whole, load_map_fields in kernels_skeleton.inl)
+		asm volatile("" : "+s"(schedule_offset), "+s"(num_levels), "+s"(num_words));
+		const uint32_t* schedule = hierarchy + schedule_offset;
+		if (num_words <= reserved_words)
+		{
+			for (uint32_t base = 0; base < num_words; base += k_wave_size * 4u)
+				if (base + lane * 4u < num_words)
+					__builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(schedule + base + lane * 4u),
+						(__attribute__((address_space(3))) void*)(shared_schedule + base), 16, 0, 0);
+		}
+		else
+			num_levels |= 0x80000000u;
+		if (lane == 0)
+		{
+			walk.levels[slot] = num_levels;
+			walk.schedules[slot] = schedule;
+		}
+	}
+
+	// The partners of a blend (consumer_params::blend_clip_ids, K - 1 per instance): is one of them unknown, not a transform clip, of
+	// tracks that do not fit -- tracks_fit(entry, record): the first clip's count, or in skeleton space a map of its own -- or, in a launch
+	// compiled without rtm::qvv_mul's matrix route that multiplies transforms, able to decode a negative scale? Every partner also has its
+	// say in the instance's short_exact.
+	template<bool kRefuseNegativeScale, class tracks_fit_type>
+	__device__ __forceinline__ bool blend_partners_refused(const device_clip* clips, uint32_t num_clips, const consumer_params& consumers, uint32_t instance,
+		uint32_t normalization, uint32_t& short_exact, tracks_fit_type tracks_fit)
+	{
+		bool refused = false;
+		for (uint32_t k = 1; k < consumers.num_blend_clips; ++k)
+		{
+			const size_t entry = size_t(instance) * (consumers.num_blend_clips - 1u) + (k - 1u);
+			const uint32_t blend_clip_id = as_constant(consumers.blend_clip_ids)[entry];
+			const ACLHIP_CONSTANT device_clip* record = as_constant(clips) + (blend_clip_id < num_clips ? blend_clip_id : 0);
+			refused = refused || blend_clip_id >= num_clips || !is_transform_clip(record->flags) || !tracks_fit(entry, record)
+				|| (kRefuseNegativeScale && (record->flags & k_clip_negative_scale) != 0);
+			short_exact &= walk_may_use_short_exact_math(record->flags, normalization);
+		}
+		return refused;
+	}
+
+	// local_to_object_space over the images of a workgroup, by ONE wave: lanes <-> (instance slot, transform of the current step); `first`
+	// picks the lane's transform inside a step of its slot's schedule (LDS copy or global memory: schedule_words). A transform's parent was
+	// scheduled in an earlier step: final by the time it is read.
+	template<bool kUnitScale, bool kMirrored, bool kFast, bool kShortExact, class schedule_word_type>
+	__device__ __forceinline__ void walk_hierarchy(const schedule_word_type* schedule_words, uint32_t slot_steps, uint32_t first, f32x4* slot_image, uint32_t lane,
+		[[maybe_unused]] unsigned long long* negative_scale_count)
+	{
+		// kShortExact: sqrt_rn_short / rcp_rn_short in the normalize (aclhip_device.h)
+		// (a copy of its own per instantiation: what the four walks of a kernel derive from it is not merged in front of them, where
+		// it would stay live through all four -- one more register than the widest of them needs: a wave per SIMD in eleven instantiations.
+		// No test guards this and the 32 bit pair index below: whoever touches this function runs tools/kernel_resources.sh decompress_poses
+		// and holds the VGPR counts against the table in profiles/consumer_kernel_sharing.md)
+		asm volatile("" : "+v"(slot_steps));
+		const uint32_t first_pair = 2u + slot_steps;		// (behind the step ends)
+		uint32_t step_start = 0;
+		for (uint32_t step = 0; __any(int(step < slot_steps)) != 0; ++step)
+		{
+			if (step < slot_steps)
+			{
+				const uint32_t step_end = schedule_words[2 + step];
+				const uint32_t pair_index = step_start + first;
+				if (pair_index < step_end)
+				{
+					const uint32_t pair = schedule_words[first_pair + pair_index];		// transform | parent << 16
+					if constexpr (kUnitScale)
+					{
+						// rotation | translation images; qvv_mul with both scales 1: translation * 1 is the translation itself
+						const uint32_t child_quad = (pair & 0xFFFFu) * 2u, parent_quad = (pair >> 16) * 2u;
+						const f32x4 child_rotation = slot_image[child_quad], child_translation = slot_image[child_quad + 1];
+						const f32x4 parent_rotation = slot_image[parent_quad], parent_translation = slot_image[parent_quad + 1];
+						const float4 parent_quat = make_float4(parent_rotation.x, parent_rotation.y, parent_rotation.z, parent_rotation.w);
+						const float4 child_quat = make_float4(child_rotation.x, child_rotation.y, child_rotation.z, child_rotation.w);
+						const float4 child_vector = make_float4(child_translation.x, child_translation.y, child_translation.z, 0.0f);
+						const float4 rotation = kFast ? quat_normalize_fast(quat_mul_fast(child_quat, parent_quat)) : quat_normalize<kShortExact>(quat_mul(child_quat, parent_quat));
+						const float4 rotated = kFast ? quat_mul_vector3_fast(child_vector, parent_quat) : quat_mul_vector3(child_vector, parent_quat);
+						slot_image[child_quad] = f32x4{ rotation.x, rotation.y, rotation.z, rotation.w };
+						slot_image[child_quad + 1] = f32x4{ rotated.x + parent_translation.x, rotated.y + parent_translation.y, rotated.z + parent_translation.z, 0.0f };
+					}
+					else
+					{
+						const qvv child = load_qvv(slot_image, pair & 0xFFFFu), parent = load_qvv(slot_image, pair >> 16);
+						qvv object;
+						if constexpr (kMirrored)
+						{
+							const uint64_t mirrored = __ballot(qvv_mul_takes_matrix_path(child, parent));
+							if (mirrored != 0 && lane == uint32_t(__builtin_ctzll(mirrored)))
+								atomicAdd(negative_scale_count, (unsigned long long)__builtin_popcountll(mirrored));
+							object = kFast ? qvv_mul_fast(child, parent) : qvv_mul(child, parent);
+							if (mirrored != 0 && qvv_mul_takes_matrix_path(child, parent))
+								object = qvv_mul_through_matrices(child, parent);
+						}
+						else
+						{
+							// neither a registered clip nor a reference pose can hand over a negative scale and the base is a clip: products
+							// and sums of non negative scales -- nothing to count, nothing to route
+							object = kFast ? qvv_mul_fast(child, parent) : qvv_mul(child, parent);
+						}
+						object.rotation = kFast ? quat_normalize_fast(object.rotation) : quat_normalize<kShortExact>(object.rotation);
+						store_qvv(slot_image, pair & 0xFFFFu, object);
+					}
+				}
+				step_start = step_end;
+			}
+			wave_lds_barrier();
+		}
+	}
+
+	// What the tail of a pose consumer kernel reads of its launch. decompress_poses_masked_kernel fills it from the kernarg segment
+	// behind its decodes (late_masked_kernel_args, kernels_skeleton.inl), the others from their arguments.
+	struct consumer_tail_args
+	{
+		uint8_t* poses;
+		uint64_t pose_stride_bytes;
+		uint32_t lds_bytes_per_instance;
+		uint32_t log2_instances_per_block;
+		unsigned long long* rejected_count;
+		const uint8_t* base_poses;				// consumer_params'
+		uint64_t base_pose_stride_bytes;
+		uint32_t additive_format;
+	};
+
+	// and what the wave brings along from its decode
+	struct consumer_wave
+	{
+		f32x4* image;
+		f32x4* base_image;
+		uint32_t* shared_schedule;
+		uint32_t slot, role, lane, wave_in_block, instance;
+		uint32_t num_tracks;		// 0 for a wave without work: past the batch, refused instance, empty track list
+		uint32_t short_exact;
+	};
+
+	// The pose consumer kernels behind their decodes, from "both images of every instance are complete" on: the combine with the base
+	// pose, the object space walk, the store. The three kernels differ in how an image is filled; this is shared. kUnitScale and kFast:
+	// decompress_poses_consumer_kernel only.
+	template<bool kObjectSpace, uint32_t kBase, bool kUnitScale, bool kMirrored, bool kFast>
+	__device__ __forceinline__ void finish_consumer_poses(const consumer_tail_args args, const consumer_wave wave, consumer_walk_slots& walk)
+	{
+		extern __shared__ __attribute__((aligned(16))) uint8_t dynamic_lds[];
+		constexpr bool has_base = kBase != k_consumer_base_none;
+		constexpr bool base_is_clip = kBase == k_consumer_base_second_wave || kBase == k_consumer_base_fused;
+		constexpr bool fused_base = kBase == k_consumer_base_fused;
+		constexpr bool two_waves = kBase == k_consumer_base_second_wave;
+		const uint32_t lane = wave.lane, role = wave.role, slot = wave.slot, num_tracks = wave.num_tracks;
+		const uint32_t log2_instances_per_block = args.log2_instances_per_block;
+		const uint32_t waves_per_instance = two_waves ? 2u : 1u;
+		f32x4* image = wave.image;
+
+		if (two_waves)
+			__syncthreads();
+		else
+			wave_lds_barrier();
+
+		if (has_base && !fused_base)
+		{
+			const f32x4* base_source = base_is_clip ? wave.base_image : reinterpret_cast<const f32x4*>(args.base_poses + uint64_t(wave.instance) * args.base_pose_stride_bytes);
+			for (uint32_t transform_index = role * k_wave_size + lane; transform_index < num_tracks; transform_index += waves_per_instance * k_wave_size)
+			{
+				const qvv additive = load_qvv(image, transform_index);
+				const qvv base = load_qvv(base_source, transform_index);
+				store_qvv(image, transform_index, apply_additive_to_base<kMirrored>(args.additive_format, base, additive));
+				// additive_clip_format8::relative is a qvv_mul (core/additive_utils.h:128-160)
+				if constexpr (kMirrored)
+				{
+					const uint64_t mirrored = __ballot(args.additive_format == 1 && qvv_mul_takes_matrix_path(additive, base));
+					if (mirrored != 0 && lane == uint32_t(__builtin_ctzll(mirrored)))
+						atomicAdd(args.rejected_count + 1, (unsigned long long)__builtin_popcountll(mirrored));
+				}
+			}
+		}
+
+		if (kObjectSpace)
+		{
+			if (lane == 0 && role == 0)
+			{
+				// (a slot with work has its steps and its schedule already: request_walk_schedule)
+				if (num_tracks == 0)
+				{
+					walk.levels[slot] = 0;
+					walk.schedules[slot] = nullptr;
+				}
+				walk.tracks[slot] = num_tracks;
+				walk.short_exact[slot] = num_tracks != 0 ? wave.short_exact : 1u;
+			}
+			__syncthreads();
+			ACLHIP_PHASE_STAMP(1);
+
+			// ONE wave walks and then stores the workgroup's poses; the others are done and give their wave slots and registers back (a
+			// pose waits in LDS for the walk about as long as its decode took: with every wave parked at a barrier the wave slots, not the
+			// LDS, decided how many poses a CU holds). The walking wave rotates with the workgroup index: waves land on SIMDs by their
+			// index inside the workgroup, and walks that all ran on a CU's first SIMD would queue there.
+			if (wave.wave_in_block != (blockIdx.x & ((blockDim.x / k_wave_size) - 1u)))
+				return;
+			{
+				// lanes <-> (instance slot, transform of the current step): slot = lane % instances, lane / instances picks the slot's
+				// transform inside the step (walk_hierarchy)
+				const uint32_t walk_slot = lane & ((1u << log2_instances_per_block) - 1u);
+				const uint32_t first = lane >> log2_instances_per_block;
+				f32x4* slot_image = reinterpret_cast<f32x4*>(dynamic_lds + size_t(walk_slot) * args.lds_bytes_per_instance);
+				unsigned long long* const negative_scale_count = args.rejected_count + 1;
+				const uint32_t slot_steps = walk.levels[walk_slot] & 0x7FFFFFFFu;
+				const bool slot_schedule_is_shared = (walk.levels[walk_slot] & 0x80000000u) == 0;
+				const uint32_t* slot_schedule = walk.schedules[walk_slot];
+
+				// all instances that walk follow the same schedule? then the shared LDS copy is theirs; otherwise each reads its own
+				// from global memory (rare: mixed skeletons inside one workgroup)
+				// the rest of the workgroup waits for this wave: it goes first on its SIMD
+				__builtin_amdgcn_s_setprio(3);
+				const uint64_t walkers = __ballot(slot_steps != 0);
+				if (walkers != 0)
+				{
+					const uint32_t leader = uint32_t(__builtin_ctzll(walkers));
+					const uint64_t mine = reinterpret_cast<uint64_t>(slot_schedule);
+					const uint64_t first_schedule = (uint64_t(__shfl(uint32_t(mine >> 32), int(leader))) << 32) | __shfl(uint32_t(mine), int(leader));
+					const bool shared_copy = __all(int(slot_steps == 0 || (mine == first_schedule && slot_schedule_is_shared))) != 0;
+					const bool short_exact_walk = !kFast && __all(int(walk.short_exact[walk_slot] != 0)) != 0;
+					const auto walk_with = [&](auto short_exact_tag)
+					{
+						constexpr bool k_short_exact = decltype(short_exact_tag)::value;
+						if (shared_copy)
+							walk_hierarchy<kUnitScale, kMirrored, kFast, k_short_exact>(static_cast<const uint32_t*>(wave.shared_schedule), slot_steps, first, slot_image, lane, negative_scale_count);
+						else
+							walk_hierarchy<kUnitScale, kMirrored, kFast, k_short_exact>(as_constant(slot_schedule), slot_steps, first, slot_image, lane, negative_scale_count);
+					};
+					if (short_exact_walk)
+						walk_with(std::true_type());
+					else
+						walk_with(std::false_type());
+				}
+				__builtin_amdgcn_s_setprio(0);
+			}
+			wave_lds_barrier();
+			ACLHIP_PHASE_STAMP(2);
+
+			const uint32_t instances_per_block = 1u << log2_instances_per_block;
+			for (uint32_t store_slot = 0; store_slot < instances_per_block; ++store_slot)
+			{
+				const uint32_t slot_quads = walk.tracks[store_slot] * 3u;
+				const f32x4* slot_image = reinterpret_cast<const f32x4*>(dynamic_lds + size_t(store_slot) * args.lds_bytes_per_instance);
+				f32x4* slot_pose = reinterpret_cast<f32x4*>(args.poses + uint64_t((blockIdx.x << log2_instances_per_block) + store_slot) * args.pose_stride_bytes);
+				if (kUnitScale)
+				{
+					// rotation | translation in LDS, rotation | translation | scale (1, 1, 1) in the pose
+					for (uint32_t quad = lane; quad < slot_quads; quad += k_wave_size)
+					{
+						const uint32_t track = quad / 3u;
+						const uint32_t kind = quad - track * 3u;
+						const f32x4 value = kind == 2 ? f32x4{ 1.0f, 1.0f, 1.0f, 0.0f } : slot_image[track * 2u + min(kind, 1u)];
+						store_streaming(&slot_pose[quad], value);
+					}
+				}
+				else
+					for (uint32_t quad = lane; quad < slot_quads; quad += k_wave_size)
+						store_streaming(&slot_pose[quad], slot_image[quad]);
+			}
+			ACLHIP_PHASE_STAMP(3);
+			return;
+		}
+		else if (two_waves)
+			__syncthreads();
+		else
+			wave_lds_barrier();
+
+		const uint32_t num_quads = num_tracks * 3u;
+		f32x4* pose = reinterpret_cast<f32x4*>(args.poses + uint64_t(wave.instance) * args.pose_stride_bytes);
+		for (uint32_t quad = role * k_wave_size + lane; quad < num_quads; quad += waves_per_instance * k_wave_size)
+			store_streaming(&pose[quad], image[quad]);
+		ACLHIP_PHASE_STAMP(3);
+	}
+
+	// The entry point of the unmapped launches (aclhip_decompress_poses_batch): the refusal test over the clips, every instance's image
+	// filled by decode_pose_into_image and its kin, then finish_consumer_poses.
 	template<bool kObjectSpace, uint32_t kBase, bool kUnitScale, bool kMirrored, bool kBlend = false, bool kFast = false>
 	__global__ __launch_bounds__(k_consumer_max_waves * k_wave_size) void decompress_poses_consumer_kernel(const device_clip* __restrict__ clips, uint32_t num_clips,
 		const uint32_t* __restrict__ clip_ids, const float* __restrict__ sample_times, uint32_t num_instances, decode_params launch_params, consumer_params consumers,
@@ -256,15 +555,10 @@
 		const uint32_t log2_instances_per_block = packed_block_shape & 0xFFu;
 		extern __shared__ __attribute__((aligned(16))) uint8_t dynamic_lds[];
 		__shared__ consumer_walk_slots walk;		// (what the host subtracts from the LDS it may ask for: host_consumers.inl)
-		uint32_t (&walk_levels)[k_consumer_max_instances] = walk.levels;
-		const uint32_t* (&walk_schedules)[k_consumer_max_instances] = walk.schedules;
-		uint32_t (&walk_tracks)[k_consumer_max_instances] = walk.tracks;
-		uint32_t (&walk_short_exact)[k_consumer_max_instances] = walk.short_exact;
 
 		static_assert(!kUnitScale || (kObjectSpace && kBase == k_consumer_base_none), "rotation | translation images: object space without a base");
 		static_assert(!kBlend || (!kUnitScale && kBase != k_consumer_base_fused), "a blend accumulates whole qvv images; a base clip is decoded by a second wave");
 		static_assert(!kFast || !kBlend, "ACLHIP_CONSUMERS_FAST: not instantiated for blends");
-		constexpr bool has_base = kBase != k_consumer_base_none;
 		constexpr bool base_is_clip = kBase == k_consumer_base_second_wave || kBase == k_consumer_base_fused;
 		// a base clip under additive0 / additive1: ONE wave decodes the base into the instance's image and the additive clip onto it
 		// (half the LDS per instance, half the waves: twice the poses a CU holds); otherwise a second wave decodes the base into its own image
@@ -279,7 +573,6 @@
 		const uint32_t wave_in_block = __builtin_amdgcn_readfirstlane(threadIdx.x / k_wave_size);
 		const uint32_t slot = wave_in_block & ((1u << log2_instances_per_block) - 1u);
 		const uint32_t role = wave_in_block >> log2_instances_per_block;
-		const uint32_t waves_per_instance = two_waves ? 2u : 1u;
 		const uint32_t instance = (blockIdx.x << log2_instances_per_block) + slot;
 
 		uint8_t* instance_lds = dynamic_lds + size_t(slot) * lds_bytes_per_instance;
@@ -288,10 +581,8 @@
 		// one LDS copy of the walk schedule per workgroup, behind the instances' images: the instances of a workgroup usually share
 		// a skeleton (identical hierarchies are one image, see aclhip_set_clip_hierarchy), and every word kept per instance costs residency
 		uint32_t* shared_schedule = reinterpret_cast<uint32_t*>(dynamic_lds + (size_t(lds_bytes_per_instance) << log2_instances_per_block));
-		const uint32_t* schedule = nullptr;
 
 		uint32_t num_tracks = 0;		// stays 0 for a wave without work: past the batch, refused instance, empty track list
-		uint32_t num_levels = 0;
 		// the walk's normalize may take the short exact forms when every rotation it meets comes out of clips that are proven safe for
 		// them (norms near 1; a caller's base pose buffer holds anything)
 		uint32_t short_exact = kBase == k_consumer_base_buffer ? 0u : 1u;
@@ -333,18 +624,10 @@
 					decode_pose_into_image<kFast>(base_clip, as_constant(consumers.base_sample_times)[instance], rounding_policy, params, lane, base_image);
 			}
 
+			// every clip of the blend: known, a transform clip, as many tracks as the first
 			if (kBlend && !refused)
-			{
-				// every clip of the blend: known, a transform clip, as many tracks as the first
-				for (uint32_t k = 1; k < consumers.num_blend_clips; ++k)
-				{
-					const uint32_t blend_clip_id = as_constant(consumers.blend_clip_ids)[size_t(instance) * (consumers.num_blend_clips - 1u) + (k - 1u)];
-					const ACLHIP_CONSTANT device_clip* record = as_constant(clips) + (blend_clip_id < num_clips ? blend_clip_id : 0);
-					refused = refused || blend_clip_id >= num_clips || !is_transform_clip(record->flags) || record->num_tracks != clip.num_tracks
-						|| (!kMirrored && multiplies_transforms && (record->flags & k_clip_negative_scale) != 0);
-					short_exact &= walk_may_use_short_exact_math(record->flags, params.normalization);
-				}
-			}
+				refused = blend_partners_refused<!kMirrored && multiplies_transforms>(clips, num_clips, consumers, instance, params.normalization, short_exact,
+					[&](size_t, const ACLHIP_CONSTANT device_clip* record) { return record->num_tracks == clip.num_tracks; });
 
 			if (refused)
 			{
@@ -357,29 +640,7 @@
 				if (role == 0)
 				{
 					if (object_space)
-					{
-						// The walk schedule for this many instances per workgroup, requested BEFORE the decode (until round 4 behind it: three
-						// more dependent round trips -- offset, header, words -- at the end of every wave's chain, 1.7 of a decode's 6.3 us).
-						// One scalar load for the schedule's header (aclhip_set_clip_hierarchy: {offset, steps, words, 0} per workgroup size,
-						// in flight next to the seek's sample records), then the words travel global -> LDS by DMA while the pose is decoded:
-						//     num_steps | words | step_end[num_steps] | transform | parent << 16 in step order, padded to whole 16 byte pieces
-						// Every wave leaves its schedule in the shared copy: the same words when they share it (the copy is only used then).
-						// A schedule longer than the launch reserved LDS for (a hierarchy set behind a captured launch's back) stays in
-						// global memory and the walk reads it there.
-						const u32x4 header = ((const ACLHIP_CONSTANT u32x4*)clip.hierarchy)[log2_instances_per_block];
-						schedule = clip.hierarchy + header.x;
-						num_levels = header.y;
-						const uint32_t num_words = header.z;
-						if (num_words <= (packed_block_shape >> 8))
-						{
-							for (uint32_t base = 0; base < num_words; base += k_wave_size * 4u)
-								if (base + lane * 4u < num_words)
-									__builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(schedule + base + lane * 4u),
-										(__attribute__((address_space(3))) void*)(shared_schedule + base), 16, 0, 0);
-						}
-						else
-							num_levels |= 0x80000000u;
-					}
+						request_walk_schedule(clip.hierarchy, log2_instances_per_block, packed_block_shape >> 8, shared_schedule, slot, lane, walk);
 					if (fused_base)
 					{
 						decode_pose_into_image<kFast>(base_clip, as_constant(consumers.base_sample_times)[instance], rounding_policy, params, lane, image);
@@ -395,7 +656,7 @@
 						const uint32_t num_blend_clips = consumers.num_blend_clips;
 						const ACLHIP_CONSTANT float* weights = as_constant(consumers.blend_weights) + size_t(instance) * num_blend_clips;
 						wave_lds_barrier();		// the first pose is complete (its DMA has landed)
-						blend_scale_image(image, clip.num_tracks * 3u, weights[0], lane);
+						blend_scale_image(image, clip.num_tracks * 3u, uniform_weight{ weights[0] }, lane);
 						for (uint32_t k = 1; k < num_blend_clips; ++k)
 						{
 							const size_t entry = size_t(instance) * (num_blend_clips - 1u) + (k - 1u);
@@ -411,176 +672,7 @@
 		}
 
 		// both images of every instance are complete
-		if (two_waves)
-			__syncthreads();
-		else
-			wave_lds_barrier();
-
-		if (has_base && !fused_base)
-		{
-			const f32x4* base_source = base_is_clip ? base_image : reinterpret_cast<const f32x4*>(consumers.base_poses + uint64_t(instance) * consumers.base_pose_stride_bytes);
-			for (uint32_t transform_index = role * k_wave_size + lane; transform_index < num_tracks; transform_index += waves_per_instance * k_wave_size)
-			{
-				const qvv additive = load_qvv(image, transform_index);
-				const qvv base = load_qvv(base_source, transform_index);
-				store_qvv(image, transform_index, apply_additive_to_base<kMirrored>(consumers.additive_format, base, additive));
-				// additive_clip_format8::relative is a qvv_mul (core/additive_utils.h:128-160)
-				if constexpr (kMirrored)
-				{
-					const uint64_t mirrored = __ballot(consumers.additive_format == 1 && qvv_mul_takes_matrix_path(additive, base));
-					if (mirrored != 0 && lane == uint32_t(__builtin_ctzll(mirrored)))
-						atomicAdd(rejected_count + 1, (unsigned long long)__builtin_popcountll(mirrored));
-				}
-			}
-		}
-
-		if (object_space)
-		{
-			if (lane == 0 && role == 0)
-			{
-				walk_levels[slot] = num_levels;
-				walk_schedules[slot] = schedule;
-				walk_tracks[slot] = num_tracks;
-				walk_short_exact[slot] = num_tracks != 0 ? short_exact : 1u;
-			}
-			__syncthreads();
-			ACLHIP_PHASE_STAMP(1);
-
-			// ONE wave walks and then stores the workgroup's poses; the others are done and give their wave slots and registers back (a
-			// pose waits in LDS for the walk about as long as its decode took: with every wave parked at a barrier the wave slots, not the
-			// LDS, decided how many poses a CU holds). The walking wave rotates with the workgroup index: waves land on SIMDs by their
-			// index inside the workgroup, and walks that all ran on a CU's first SIMD would queue there.
-			if (wave_in_block != (blockIdx.x & ((blockDim.x / k_wave_size) - 1u)))
-				return;
-			{
-				// lanes <-> (instance slot, transform of the current step): slot = lane % instances, lane / instances picks the slot's
-				// transform inside the step. A transform's parent was scheduled in an earlier step: final by the time it is read.
-				const uint32_t walk_slot = lane & ((1u << log2_instances_per_block) - 1u);
-				const uint32_t first = lane >> log2_instances_per_block;
-				f32x4* slot_image = reinterpret_cast<f32x4*>(dynamic_lds + size_t(walk_slot) * lds_bytes_per_instance);
-				const uint32_t slot_steps = walk_levels[walk_slot] & 0x7FFFFFFFu;
-				const bool slot_schedule_is_shared = (walk_levels[walk_slot] & 0x80000000u) == 0;
-				const uint32_t* slot_schedule = walk_schedules[walk_slot];
-
-				const auto walk = [&](const auto* schedule_words, auto scale_is_one, auto short_exact_tag)
-				{
-					constexpr bool k_unit_scale = decltype(scale_is_one)::value;
-					constexpr bool k_short_exact = decltype(short_exact_tag)::value;		// sqrt_rn_short / rcp_rn_short in the normalize (aclhip_device.h)
-					const auto* pairs = schedule_words + 2u + slot_steps;
-					uint32_t step_start = 0;
-					for (uint32_t step = 0; __any(int(step < slot_steps)) != 0; ++step)
-					{
-						if (step < slot_steps)
-						{
-							const uint32_t step_end = schedule_words[2 + step];
-							const uint32_t pair_index = step_start + first;
-							if (pair_index < step_end)
-							{
-								const uint32_t pair = pairs[pair_index];		// transform | parent << 16
-								if constexpr (k_unit_scale)
-								{
-									// rotation | translation images; qvv_mul with both scales 1: translation * 1 is the translation itself
-									const uint32_t child_quad = (pair & 0xFFFFu) * 2u, parent_quad = (pair >> 16) * 2u;
-									const f32x4 child_rotation = slot_image[child_quad], child_translation = slot_image[child_quad + 1];
-									const f32x4 parent_rotation = slot_image[parent_quad], parent_translation = slot_image[parent_quad + 1];
-									const float4 parent_quat = make_float4(parent_rotation.x, parent_rotation.y, parent_rotation.z, parent_rotation.w);
-									const float4 child_quat = make_float4(child_rotation.x, child_rotation.y, child_rotation.z, child_rotation.w);
-									const float4 child_vector = make_float4(child_translation.x, child_translation.y, child_translation.z, 0.0f);
-									const float4 rotation = kFast ? quat_normalize_fast(quat_mul_fast(child_quat, parent_quat)) : quat_normalize<k_short_exact>(quat_mul(child_quat, parent_quat));
-									const float4 rotated = kFast ? quat_mul_vector3_fast(child_vector, parent_quat) : quat_mul_vector3(child_vector, parent_quat);
-									slot_image[child_quad] = f32x4{ rotation.x, rotation.y, rotation.z, rotation.w };
-									slot_image[child_quad + 1] = f32x4{ rotated.x + parent_translation.x, rotated.y + parent_translation.y, rotated.z + parent_translation.z, 0.0f };
-								}
-								else
-								{
-									const qvv child = load_qvv(slot_image, pair & 0xFFFFu), parent = load_qvv(slot_image, pair >> 16);
-									qvv object;
-									if constexpr (kMirrored)
-									{
-										const uint64_t mirrored = __ballot(qvv_mul_takes_matrix_path(child, parent));
-										if (mirrored != 0 && lane == uint32_t(__builtin_ctzll(mirrored)))
-											atomicAdd(rejected_count + 1, (unsigned long long)__builtin_popcountll(mirrored));
-										object = kFast ? qvv_mul_fast(child, parent) : qvv_mul(child, parent);
-										if (mirrored != 0 && qvv_mul_takes_matrix_path(child, parent))
-											object = qvv_mul_through_matrices(child, parent);
-									}
-									else
-									{
-										// no registered clip can decode a negative scale and the base is a clip: products and sums of non
-										// negative scales -- nothing to count, nothing to route
-										object = kFast ? qvv_mul_fast(child, parent) : qvv_mul(child, parent);
-									}
-									object.rotation = kFast ? quat_normalize_fast(object.rotation) : quat_normalize<k_short_exact>(object.rotation);
-									store_qvv(slot_image, pair & 0xFFFFu, object);
-								}
-							}
-							step_start = step_end;
-						}
-						wave_lds_barrier();
-					}
-				};
-
-				// all instances that walk follow the same schedule? then the shared LDS copy is theirs; otherwise each reads its own
-				// from global memory (rare: mixed skeletons inside one workgroup)
-				// the rest of the workgroup waits for this wave: it goes first on its SIMD
-				__builtin_amdgcn_s_setprio(3);
-				const uint64_t walkers = __ballot(slot_steps != 0);
-				if (walkers != 0)
-				{
-					const uint32_t leader = uint32_t(__builtin_ctzll(walkers));
-					const uint64_t mine = reinterpret_cast<uint64_t>(slot_schedule);
-					const uint64_t first_schedule = (uint64_t(__shfl(uint32_t(mine >> 32), int(leader))) << 32) | __shfl(uint32_t(mine), int(leader));
-					const bool shared_copy = __all(int(slot_steps == 0 || (mine == first_schedule && slot_schedule_is_shared))) != 0;
-					const bool short_exact_walk = !kFast && __all(int(walk_short_exact[walk_slot] != 0)) != 0;
-					const auto walk_with = [&](auto scale_is_one, auto short_exact_tag)
-					{
-						if (shared_copy)
-							walk(static_cast<const uint32_t*>(shared_schedule), scale_is_one, short_exact_tag);
-						else
-							walk(as_constant(slot_schedule), scale_is_one, short_exact_tag);
-					};
-					if (short_exact_walk)
-						walk_with(std::integral_constant<bool, unit_scale>(), std::true_type());
-					else
-						walk_with(std::integral_constant<bool, unit_scale>(), std::false_type());
-				}
-				__builtin_amdgcn_s_setprio(0);
-			}
-			wave_lds_barrier();
-			ACLHIP_PHASE_STAMP(2);
-
-			const uint32_t instances_per_block = 1u << log2_instances_per_block;
-			for (uint32_t store_slot = 0; store_slot < instances_per_block; ++store_slot)
-			{
-				const uint32_t slot_quads = walk_tracks[store_slot] * 3u;
-				const f32x4* slot_image = reinterpret_cast<const f32x4*>(dynamic_lds + size_t(store_slot) * lds_bytes_per_instance);
-				f32x4* slot_pose = reinterpret_cast<f32x4*>(poses + uint64_t((blockIdx.x << log2_instances_per_block) + store_slot) * pose_stride_bytes);
-				if (unit_scale)
-				{
-					// rotation | translation in LDS, rotation | translation | scale (1, 1, 1) in the pose
-					for (uint32_t quad = lane; quad < slot_quads; quad += k_wave_size)
-					{
-						const uint32_t track = quad / 3u;
-						const uint32_t kind = quad - track * 3u;
-						const f32x4 value = kind == 2 ? f32x4{ 1.0f, 1.0f, 1.0f, 0.0f } : slot_image[track * 2u + min(kind, 1u)];
-						store_streaming(&slot_pose[quad], value);
-					}
-				}
-				else
-					for (uint32_t quad = lane; quad < slot_quads; quad += k_wave_size)
-						store_streaming(&slot_pose[quad], slot_image[quad]);
-			}
-			ACLHIP_PHASE_STAMP(3);
-			return;
-		}
-		else if (two_waves)
-			__syncthreads();
-		else
-			wave_lds_barrier();
-
-		const uint32_t num_quads = num_tracks * 3u;
-		f32x4* pose = reinterpret_cast<f32x4*>(poses + uint64_t(instance) * pose_stride_bytes);
-		for (uint32_t quad = role * k_wave_size + lane; quad < num_quads; quad += waves_per_instance * k_wave_size)
-			store_streaming(&pose[quad], image[quad]);
-		ACLHIP_PHASE_STAMP(3);
+		finish_consumer_poses<kObjectSpace, kBase, kUnitScale, kMirrored, kFast>(
+			consumer_tail_args{ poses, pose_stride_bytes, lds_bytes_per_instance, log2_instances_per_block, rejected_count, consumers.base_poses, consumers.base_pose_stride_bytes, consumers.additive_format },
+			consumer_wave{ image, base_image, shared_schedule, slot, role, lane, wave_in_block, instance, num_tracks, short_exact }, walk);
 	}

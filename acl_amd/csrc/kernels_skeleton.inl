@@ -120,7 +120,7 @@
 	}
 
 	// The constant / default pass of blend_clip_onto_image and apply_additive_clip_onto_image over SLOTS: the base pose table entry of
-	// the slot's track, or the fill -- a filled slot takes the same arithmetic as a decoded one
+	// the slot's track, or the fill -- a filled slot takes the same arithmetic as a decoded one. combine(slot, kind, value, what the image holds)
 	template<class combine_type>
 	__device__ __forceinline__ void combine_constant_slots(const device_clip& clip, const device_track_map& map, const slot_fill& fill, uint32_t lane, f32x4* image, combine_type combine)
 	{
@@ -148,30 +148,41 @@
 				const f32x4 filled = *fill.quad(slot_quad, kind);
 				value = make_float4(filled.x, filled.y, filled.z, filled.w);
 			}
-			image[slot_quad] = combine(kind, value, image[slot_quad]);
+			image[slot_quad] = combine(slot, kind, value, image[slot_quad]);
 		}
 	}
 
 	__device__ __forceinline__ void apply_additive_clip_onto_slot_image(const device_clip& clip, const device_track_map& map, const slot_fill& fill, float sample_time,
 		uint32_t rounding_policy, const decode_params& params, uint32_t additive_format, uint32_t lane, f32x4* image)
 	{
-		combine_constant_slots(clip, map, fill, lane, image, [&](uint32_t kind, float4 value, f32x4 base) { return apply_additive_sub_track(additive_format, kind, value, base); });
+		combine_constant_slots(clip, map, fill, lane, image, [&](uint32_t, uint32_t kind, float4 value, f32x4 base) { return apply_additive_sub_track(additive_format, kind, value, base); });
 		decode_animated_into_image(clip, sample_time, rounding_policy, params, lane, into_slots(map, additive_image_writer<>{ image, additive_format }));
 	}
 
+	// weight: uniform_weight, or under blend masks a slot_weight
+	template<class weight_type>
 	__device__ __forceinline__ void blend_clip_onto_slot_image(const device_clip& clip, const device_track_map& map, const slot_fill& fill, float sample_time,
-		uint32_t rounding_policy, const decode_params& params, float weight, uint32_t lane, f32x4* image)
+		uint32_t rounding_policy, const decode_params& params, const weight_type& weight, uint32_t lane, f32x4* image)
 	{
-		combine_constant_slots(clip, map, fill, lane, image, [&](uint32_t kind, float4 value, f32x4 accumulated) { return blend_accumulate(kind, accumulated, value, weight); });
-		decode_animated_into_image(clip, sample_time, rounding_policy, params, lane, into_slots(map, blend_image_writer{ image, weight }));
+		combine_constant_slots(clip, map, fill, lane, image, [&](uint32_t slot, uint32_t kind, float4 value, f32x4 accumulated) { return blend_accumulate(kind, accumulated, value, weight(slot)); });
+		decode_animated_into_image(clip, sample_time, rounding_policy, params, lane, into_slots(map, blend_image_writer<weight_type>{ image, weight }));
+	}
+
+	// blend_partners_refused's track test in skeleton space: the partner's own map (skeleton_launch::blend_maps), known, made for this clip and
+	// for a skeleton of this many bones
+	__device__ __forceinline__ bool blend_map_fits(const skeleton_launch* mapping, size_t entry, const ACLHIP_CONSTANT device_clip* record, uint32_t num_bones)
+	{
+		const uint32_t blend_map_id = as_constant(mapping->blend_maps)[entry];
+		const ACLHIP_CONSTANT device_track_map* map_record = as_constant(mapping->maps) + (blend_map_id < mapping->num_maps ? blend_map_id : 0);
+		return blend_map_id < mapping->num_maps && map_record->image != nullptr && map_record->num_tracks == record->num_tracks && map_record->num_slots == num_bones;
 	}
 
 	// decompress_poses_consumer_kernel (kernels_consumers.inl: the workgroup's shape, the LDS layout, the walk and the store are described
 	// there) in skeleton space, with the mapping as its own trailing argument: decode_params, consumer_params and every kernarg offset
-	// are where that kernel has them. A kernel of its own rather than a flag of that one: every way of sharing the text that was tried
-	// (a common device function, one body under two entry points) moved registers in 29 of the 32 existing instantiations, and those
-	// are held to identical disassembly (profiles/skeleton_poses.md). No rotation | translation images, no ACLHIP_CONSUMERS_FAST.
-	// What that kernel keeps for them is not repeated here.
+	// are where that kernel has them. An entry point of its own for what differs -- the refusal test takes the skeleton and the maps in, the
+	// images are filled in slot order --; behind the decodes it is that kernel's finish_consumer_poses, without rotation | translation
+	// images and without ACLHIP_CONSUMERS_FAST. (Until the three kernels were held to resources and time instead of identical disassembly
+	// the whole text was repeated here: profiles/skeleton_poses.md, profiles/consumer_kernel_sharing.md.)
 	template<bool kObjectSpace, uint32_t kBase, bool kMirrored, bool kBlend>
 	__global__ __launch_bounds__(k_consumer_max_waves * k_wave_size) void decompress_poses_skeleton_kernel(const device_clip* __restrict__ clips, uint32_t num_clips,
 		const uint32_t* __restrict__ clip_ids, const float* __restrict__ sample_times, uint32_t num_instances, decode_params launch_params, consumer_params consumers,
@@ -183,13 +194,8 @@
 		const uint32_t log2_instances_per_block = packed_block_shape & 0xFFu;
 		extern __shared__ __attribute__((aligned(16))) uint8_t dynamic_lds[];
 		__shared__ consumer_walk_slots walk;		// (what the host subtracts from the LDS it may ask for: host_consumers.inl)
-		uint32_t (&walk_levels)[k_consumer_max_instances] = walk.levels;
-		const uint32_t* (&walk_schedules)[k_consumer_max_instances] = walk.schedules;
-		uint32_t (&walk_tracks)[k_consumer_max_instances] = walk.tracks;
-		uint32_t (&walk_short_exact)[k_consumer_max_instances] = walk.short_exact;
 
 		static_assert(!kBlend || kBase != k_consumer_base_fused, "a blend accumulates whole qvv images; a base clip is decoded by a second wave");
-		constexpr bool has_base = kBase != k_consumer_base_none;
 		constexpr bool base_is_clip = kBase == k_consumer_base_second_wave || kBase == k_consumer_base_fused;
 		// a base clip under additive0 / additive1: ONE wave decodes the base into the instance's image and the additive clip onto it
 		// (half the LDS per instance, half the waves: twice the poses a CU holds); otherwise a second wave decodes the base into its own image
@@ -203,7 +209,6 @@
 		const uint32_t wave_in_block = __builtin_amdgcn_readfirstlane(threadIdx.x / k_wave_size);
 		const uint32_t slot = wave_in_block & ((1u << log2_instances_per_block) - 1u);
 		const uint32_t role = wave_in_block >> log2_instances_per_block;
-		const uint32_t waves_per_instance = two_waves ? 2u : 1u;
 		const uint32_t instance = (blockIdx.x << log2_instances_per_block) + slot;
 
 		uint8_t* instance_lds = dynamic_lds + size_t(slot) * lds_bytes_per_instance;
@@ -212,10 +217,8 @@
 		// one LDS copy of the walk schedule per workgroup, behind the instances' images: the instances of a workgroup usually share
 		// a skeleton (identical hierarchies are one image, see aclhip_set_clip_hierarchy), and every word kept per instance costs residency
 		uint32_t* shared_schedule = reinterpret_cast<uint32_t*>(dynamic_lds + (size_t(lds_bytes_per_instance) << log2_instances_per_block));
-		const uint32_t* schedule = nullptr;
 
 		uint32_t num_tracks = 0;		// stays 0 for a wave without work: past the batch, refused instance, empty track list
-		uint32_t num_levels = 0;
 		// the walk's normalize may take the short exact forms when every rotation it meets comes out of clips that are proven safe for
 		// them (norms near 1; a caller's base pose buffer holds anything)
 		uint32_t short_exact = kBase == k_consumer_base_buffer ? 0u : 1u;
@@ -275,21 +278,10 @@
 					decode_pose_into_slot_image(base_clip, base_map, slot_fill{ skeleton.reference_pose, 0 }, as_constant(consumers.base_sample_times)[instance], rounding_policy, params, lane, base_image);
 			}
 
+			// every clip of the blend: known, a transform clip, with a known map of its own into this skeleton
 			if (kBlend && !refused)
-			{
-				// every clip of the blend: known, a transform clip, with a known map of its own into this skeleton
-				for (uint32_t k = 1; k < consumers.num_blend_clips; ++k)
-				{
-					const uint32_t blend_clip_id = as_constant(consumers.blend_clip_ids)[size_t(instance) * (consumers.num_blend_clips - 1u) + (k - 1u)];
-					const ACLHIP_CONSTANT device_clip* record = as_constant(clips) + (blend_clip_id < num_clips ? blend_clip_id : 0);
-					const uint32_t blend_map_id = as_constant(mapping->blend_maps)[size_t(instance) * (consumers.num_blend_clips - 1u) + (k - 1u)];
-					const ACLHIP_CONSTANT device_track_map* map_record = as_constant(mapping->maps) + (blend_map_id < mapping->num_maps ? blend_map_id : 0);
-					refused = refused || blend_clip_id >= num_clips || !is_transform_clip(record->flags)
-						|| blend_map_id >= mapping->num_maps || map_record->image == nullptr || map_record->num_tracks != record->num_tracks || map_record->num_slots != skeleton.num_bones
-						|| (!kMirrored && multiplies_transforms && (record->flags & k_clip_negative_scale) != 0);
-					short_exact &= walk_may_use_short_exact_math(record->flags, params.normalization);
-				}
-			}
+				refused = blend_partners_refused<!kMirrored && multiplies_transforms>(clips, num_clips, consumers, instance, params.normalization, short_exact,
+					[&](size_t entry, const ACLHIP_CONSTANT device_clip* record) { return blend_map_fits(mapping, entry, record, skeleton.num_bones); });
 
 			if (refused)
 			{
@@ -302,29 +294,7 @@
 				if (role == 0)
 				{
 					if (object_space)
-					{
-						// The walk schedule for this many instances per workgroup, requested BEFORE the decode (until round 4 behind it: three
-						// more dependent round trips -- offset, header, words -- at the end of every wave's chain, 1.7 of a decode's 6.3 us).
-						// One scalar load for the schedule's header (aclhip_set_clip_hierarchy: {offset, steps, words, 0} per workgroup size,
-						// in flight next to the seek's sample records), then the words travel global -> LDS by DMA while the pose is decoded:
-						//     num_steps | words | step_end[num_steps] | transform | parent << 16 in step order, padded to whole 16 byte pieces
-						// Every wave leaves its schedule in the shared copy: the same words when they share it (the copy is only used then).
-						// A schedule longer than the launch reserved LDS for (a hierarchy set behind a captured launch's back) stays in
-						// global memory and the walk reads it there.
-						const u32x4 header = ((const ACLHIP_CONSTANT u32x4*)hierarchy)[log2_instances_per_block];
-						schedule = hierarchy + header.x;
-						num_levels = header.y;
-						const uint32_t num_words = header.z;
-						if (num_words <= (packed_block_shape >> 8))
-						{
-							for (uint32_t base = 0; base < num_words; base += k_wave_size * 4u)
-								if (base + lane * 4u < num_words)
-									__builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(schedule + base + lane * 4u),
-										(__attribute__((address_space(3))) void*)(shared_schedule + base), 16, 0, 0);
-						}
-						else
-							num_levels |= 0x80000000u;
-					}
+						request_walk_schedule(hierarchy, log2_instances_per_block, packed_block_shape >> 8, shared_schedule, slot, lane, walk);
 					if (fused_base)
 					{
 						decode_pose_into_slot_image(base_clip, base_map, slot_fill{ skeleton.reference_pose, 0 }, as_constant(consumers.base_sample_times)[instance], rounding_policy, params, lane, image);
@@ -338,14 +308,14 @@
 						const uint32_t num_blend_clips = consumers.num_blend_clips;
 						const ACLHIP_CONSTANT float* weights = as_constant(consumers.blend_weights) + size_t(instance) * num_blend_clips;
 						wave_lds_barrier();		// the first pose is complete (its DMA has landed)
-						blend_scale_image(image, pose_tracks * 3u, weights[0], lane);
+						blend_scale_image(image, pose_tracks * 3u, uniform_weight{ weights[0] }, lane);
 						for (uint32_t k = 1; k < num_blend_clips; ++k)
 						{
 							const size_t entry = size_t(instance) * (num_blend_clips - 1u) + (k - 1u);
 							const device_clip blend_clip = load_clip_fields(clips, as_constant(consumers.blend_clip_ids)[entry]);
 							wave_lds_barrier();		// every quad has its sum so far
 							const device_track_map blend_map = load_entry(mapping->maps, as_constant(mapping->blend_maps)[entry]);
-							blend_clip_onto_slot_image(blend_clip, blend_map, clip_fill, as_constant(consumers.blend_sample_times)[entry], rounding_policy, params, weights[k], lane, image);
+							blend_clip_onto_slot_image(blend_clip, blend_map, clip_fill, as_constant(consumers.blend_sample_times)[entry], rounding_policy, params, uniform_weight{ weights[k] }, lane, image);
 						}
 						wave_lds_barrier();
 						blend_normalize_rotations(image, pose_tracks, lane);
@@ -355,148 +325,9 @@
 		}
 
 		// both images of every instance are complete
-		if (two_waves)
-			__syncthreads();
-		else
-			wave_lds_barrier();
-
-		if (has_base && !fused_base)
-		{
-			const f32x4* base_source = base_is_clip ? base_image : reinterpret_cast<const f32x4*>(consumers.base_poses + uint64_t(instance) * consumers.base_pose_stride_bytes);
-			for (uint32_t transform_index = role * k_wave_size + lane; transform_index < num_tracks; transform_index += waves_per_instance * k_wave_size)
-			{
-				const qvv additive = load_qvv(image, transform_index);
-				const qvv base = load_qvv(base_source, transform_index);
-				store_qvv(image, transform_index, apply_additive_to_base<kMirrored>(consumers.additive_format, base, additive));
-				// additive_clip_format8::relative is a qvv_mul (core/additive_utils.h:128-160)
-				if constexpr (kMirrored)
-				{
-					const uint64_t mirrored = __ballot(consumers.additive_format == 1 && qvv_mul_takes_matrix_path(additive, base));
-					if (mirrored != 0 && lane == uint32_t(__builtin_ctzll(mirrored)))
-						atomicAdd(rejected_count + 1, (unsigned long long)__builtin_popcountll(mirrored));
-				}
-			}
-		}
-
-		if (object_space)
-		{
-			if (lane == 0 && role == 0)
-			{
-				walk_levels[slot] = num_levels;
-				walk_schedules[slot] = schedule;
-				walk_tracks[slot] = num_tracks;
-				walk_short_exact[slot] = num_tracks != 0 ? short_exact : 1u;
-			}
-			__syncthreads();
-			ACLHIP_PHASE_STAMP(1);
-
-			// ONE wave walks and then stores the workgroup's poses; the others are done and give their wave slots and registers back (a
-			// pose waits in LDS for the walk about as long as its decode took: with every wave parked at a barrier the wave slots, not the
-			// LDS, decided how many poses a CU holds). The walking wave rotates with the workgroup index: waves land on SIMDs by their
-			// index inside the workgroup, and walks that all ran on a CU's first SIMD would queue there.
-			if (wave_in_block != (blockIdx.x & ((blockDim.x / k_wave_size) - 1u)))
-				return;
-			{
-				// lanes <-> (instance slot, transform of the current step): slot = lane % instances, lane / instances picks the slot's
-				// transform inside the step. A transform's parent was scheduled in an earlier step: final by the time it is read.
-				const uint32_t walk_slot = lane & ((1u << log2_instances_per_block) - 1u);
-				const uint32_t first = lane >> log2_instances_per_block;
-				f32x4* slot_image = reinterpret_cast<f32x4*>(dynamic_lds + size_t(walk_slot) * lds_bytes_per_instance);
-				const uint32_t slot_steps = walk_levels[walk_slot] & 0x7FFFFFFFu;
-				const bool slot_schedule_is_shared = (walk_levels[walk_slot] & 0x80000000u) == 0;
-				const uint32_t* slot_schedule = walk_schedules[walk_slot];
-
-				const auto walk = [&](const auto* schedule_words, auto short_exact_tag)
-				{
-					constexpr bool k_short_exact = decltype(short_exact_tag)::value;		// sqrt_rn_short / rcp_rn_short in the normalize (aclhip_device.h)
-					const auto* pairs = schedule_words + 2u + slot_steps;
-					uint32_t step_start = 0;
-					for (uint32_t step = 0; __any(int(step < slot_steps)) != 0; ++step)
-					{
-						if (step < slot_steps)
-						{
-							const uint32_t step_end = schedule_words[2 + step];
-							const uint32_t pair_index = step_start + first;
-							if (pair_index < step_end)
-							{
-								const uint32_t pair = pairs[pair_index];		// transform | parent << 16
-								const qvv child = load_qvv(slot_image, pair & 0xFFFFu), parent = load_qvv(slot_image, pair >> 16);
-								qvv object;
-								if constexpr (kMirrored)
-								{
-									const uint64_t mirrored = __ballot(qvv_mul_takes_matrix_path(child, parent));
-									if (mirrored != 0 && lane == uint32_t(__builtin_ctzll(mirrored)))
-										atomicAdd(rejected_count + 1, (unsigned long long)__builtin_popcountll(mirrored));
-									object = qvv_mul(child, parent);
-									if (mirrored != 0 && qvv_mul_takes_matrix_path(child, parent))
-										object = qvv_mul_through_matrices(child, parent);
-								}
-								else
-								{
-									// neither a registered clip nor a reference pose can hand over a negative scale and the base is a clip:
-									// products and sums of non negative scales -- nothing to count, nothing to route
-									object = qvv_mul(child, parent);
-								}
-								object.rotation = quat_normalize<k_short_exact>(object.rotation);
-								store_qvv(slot_image, pair & 0xFFFFu, object);
-							}
-							step_start = step_end;
-						}
-						wave_lds_barrier();
-					}
-				};
-
-				// all instances that walk follow the same schedule? then the shared LDS copy is theirs; otherwise each reads its own
-				// from global memory (rare: mixed skeletons inside one workgroup)
-				// the rest of the workgroup waits for this wave: it goes first on its SIMD
-				__builtin_amdgcn_s_setprio(3);
-				const uint64_t walkers = __ballot(slot_steps != 0);
-				if (walkers != 0)
-				{
-					const uint32_t leader = uint32_t(__builtin_ctzll(walkers));
-					const uint64_t mine = reinterpret_cast<uint64_t>(slot_schedule);
-					const uint64_t first_schedule = (uint64_t(__shfl(uint32_t(mine >> 32), int(leader))) << 32) | __shfl(uint32_t(mine), int(leader));
-					const bool shared_copy = __all(int(slot_steps == 0 || (mine == first_schedule && slot_schedule_is_shared))) != 0;
-					const bool short_exact_walk = __all(int(walk_short_exact[walk_slot] != 0)) != 0;
-					const auto walk_with = [&](auto short_exact_tag)
-					{
-						if (shared_copy)
-							walk(static_cast<const uint32_t*>(shared_schedule), short_exact_tag);
-						else
-							walk(as_constant(slot_schedule), short_exact_tag);
-					};
-					if (short_exact_walk)
-						walk_with(std::true_type());
-					else
-						walk_with(std::false_type());
-				}
-				__builtin_amdgcn_s_setprio(0);
-			}
-			wave_lds_barrier();
-			ACLHIP_PHASE_STAMP(2);
-
-			const uint32_t instances_per_block = 1u << log2_instances_per_block;
-			for (uint32_t store_slot = 0; store_slot < instances_per_block; ++store_slot)
-			{
-				const uint32_t slot_quads = walk_tracks[store_slot] * 3u;
-				const f32x4* slot_image = reinterpret_cast<const f32x4*>(dynamic_lds + size_t(store_slot) * lds_bytes_per_instance);
-				f32x4* slot_pose = reinterpret_cast<f32x4*>(poses + uint64_t((blockIdx.x << log2_instances_per_block) + store_slot) * pose_stride_bytes);
-				for (uint32_t quad = lane; quad < slot_quads; quad += k_wave_size)
-					store_streaming(&slot_pose[quad], slot_image[quad]);
-			}
-			ACLHIP_PHASE_STAMP(3);
-			return;
-		}
-		else if (two_waves)
-			__syncthreads();
-		else
-			wave_lds_barrier();
-
-		const uint32_t num_quads = num_tracks * 3u;
-		f32x4* pose = reinterpret_cast<f32x4*>(poses + uint64_t(instance) * pose_stride_bytes);
-		for (uint32_t quad = role * k_wave_size + lane; quad < num_quads; quad += waves_per_instance * k_wave_size)
-			store_streaming(&pose[quad], image[quad]);
-		ACLHIP_PHASE_STAMP(3);
+		finish_consumer_poses<kObjectSpace, kBase, false, kMirrored, false>(
+			consumer_tail_args{ poses, pose_stride_bytes, lds_bytes_per_instance, log2_instances_per_block, rejected_count, consumers.base_poses, consumers.base_pose_stride_bytes, consumers.additive_format },
+			consumer_wave{ image, base_image, shared_schedule, slot, role, lane, wave_in_block, instance, num_tracks, short_exact }, walk);
 	}
 
 	// ---- blend masks (aclhip_register_blend_mask, aclhip_decompress_poses_batch_masked) ------------------------------------------------
@@ -635,69 +466,10 @@
 	#endif
 	}
 
-	// blend_image_writer with the slot's weight (slot_image_writer hands over entry.track_index == slot)
-	struct masked_blend_image_writer
-	{
-		f32x4* image;
-		slot_weight weight;
-		__device__ __forceinline__ void operator()(const clip_range_entry& entry, float4 value) const
-		{
-			const uint32_t quad = entry.quad_index;
-			image[quad] = blend_accumulate(quad - entry.track_index * 3u, image[quad], value, weight(entry.track_index));
-		}
-	};
-
-	// blend_scale_image with a weight per slot: the first clip's pose, complete in `image`, times its weights
-	__device__ __forceinline__ void blend_scale_slot_image(f32x4* image, uint32_t num_quads, const slot_weight& weight, uint32_t lane)
-	{
-		for (uint32_t quad = lane; quad < num_quads; quad += k_wave_size)
-		{
-			const uint32_t slot = quad / 3u;
-			const float slot_weight_value = weight(slot);
-			const f32x4 value = image[quad];
-			const bool is_rotation = quad - slot * 3u == 0;
-			image[quad] = f32x4{ value.x * slot_weight_value, value.y * slot_weight_value, value.z * slot_weight_value, is_rotation ? value.w * slot_weight_value : 0.0f };
-		}
-	}
-
-	// blend_clip_onto_slot_image with a weight per slot
-	__device__ __forceinline__ void blend_clip_onto_masked_slot_image(const device_clip& clip, const device_track_map& map, const slot_fill& fill, float sample_time,
-		uint32_t rounding_policy, const decode_params& params, const slot_weight& weight, uint32_t lane, f32x4* image)
-	{
-		// (combine_constant_slots' text with the slot handed to the combine: its own callers keep their instructions)
-		const uint32_t num_quads = map.num_slots * 3u;
-		const ACLHIP_CONSTANT uint32_t* slot_to_track = slot_to_track_of(map);
-		for (uint32_t slot_quad = lane; slot_quad < num_quads; slot_quad += k_wave_size)
-		{
-			const uint32_t slot = slot_quad / 3u;
-			const uint32_t kind = slot_quad - slot * 3u;
-			const uint32_t track = slot_to_track[slot];
-			float4 value;
-			if (track != ACLHIP_TRACK_DROPPED)
-			{
-				value = load_quad(clip.base_pose, track * 3u + kind);
-				const uint32_t marker = __float_as_uint(value.w);
-				if (is_special_quad(marker))
-				{
-					if ((marker & k_quad_animated) != 0)
-						continue;
-					value.w = (marker & k_quad_default_w_one) != 0 ? 1.0f : 0.0f;
-				}
-			}
-			else
-			{
-				const f32x4 filled = *fill.quad(slot_quad, kind);
-				value = make_float4(filled.x, filled.y, filled.z, filled.w);
-			}
-			image[slot_quad] = blend_accumulate(kind, image[slot_quad], value, weight(slot));
-		}
-		decode_animated_into_image(clip, sample_time, rounding_policy, params, lane, into_slots(map, masked_blend_image_writer{ image, weight }));
-	}
-
 	// decompress_poses_skeleton_kernel's blend instantiations with a weight per slot (aclhip_decompress_poses_batch_masked), the masking as
-	// their own trailing argument. The text is repeated, not shared, for the reason that kernel states: its instantiations are held to
-	// identical disassembly (profiles/blend_masks.md). What differs: the K mask records are checked next to the K maps, and the three
-	// places that take a weight -- the first clip's scale, the constant / fill pass, the animated writer -- ask slot_weight for it. One quad
+	// their own trailing argument. What differs from that kernel: the K mask records are checked next to the K maps; the three places
+	// that take a weight -- the first clip's scale, the constant / fill pass, the animated writer -- are handed a slot_weight; and what the
+	// blend's passes and finish_consumer_poses need of the launch is read late, from the kernarg segment (masked_kernel_args). One quad
 	// is still touched by one lane per pass: the LDS hazards and the barriers are that kernel's.
 	template<bool kObjectSpace, uint32_t kBase, bool kMirrored>
 	__global__ __launch_bounds__(k_consumer_max_waves * k_wave_size) void decompress_poses_masked_kernel(const device_clip* __restrict__ clips, uint32_t num_clips,
@@ -715,13 +487,8 @@
 		const uint32_t log2_instances_per_block = packed_block_shape & 0xFFu;
 		extern __shared__ __attribute__((aligned(16))) uint8_t dynamic_lds[];
 		__shared__ consumer_walk_slots walk;		// (what the host subtracts from the LDS it may ask for: host_consumers.inl)
-		uint32_t (&walk_levels)[k_consumer_max_instances] = walk.levels;
-		const uint32_t* (&walk_schedules)[k_consumer_max_instances] = walk.schedules;
-		uint32_t (&walk_tracks)[k_consumer_max_instances] = walk.tracks;
-		uint32_t (&walk_short_exact)[k_consumer_max_instances] = walk.short_exact;
 
 		static_assert(kBase != k_consumer_base_fused, "a blend accumulates whole qvv images; a base clip is decoded by a second wave");
-		constexpr bool has_base = kBase != k_consumer_base_none;
 		// (a blend's base clip is never fused: a second wave decodes it into its own image)
 		constexpr bool base_is_clip = kBase == k_consumer_base_second_wave;
 		constexpr bool two_waves = base_is_clip;
@@ -733,7 +500,6 @@
 		const uint32_t wave_in_block = __builtin_amdgcn_readfirstlane(threadIdx.x / k_wave_size);
 		const uint32_t slot = wave_in_block & ((1u << log2_instances_per_block) - 1u);
 		const uint32_t role = wave_in_block >> log2_instances_per_block;
-		const uint32_t waves_per_instance = two_waves ? 2u : 1u;
 		const uint32_t instance = (blockIdx.x << log2_instances_per_block) + slot;
 
 		uint8_t* instance_lds = dynamic_lds + size_t(slot) * lds_bytes_per_instance;
@@ -742,10 +508,8 @@
 		// one LDS copy of the walk schedule per workgroup, behind the instances' images: the instances of a workgroup usually share
 		// a skeleton (identical hierarchies are one image, see aclhip_set_clip_hierarchy), and every word kept per instance costs residency
 		uint32_t* shared_schedule = reinterpret_cast<uint32_t*>(dynamic_lds + (size_t(lds_bytes_per_instance) << log2_instances_per_block));
-		const uint32_t* schedule = nullptr;
 
 		uint32_t num_tracks = 0;		// stays 0 for a wave without work: past the batch, refused instance, empty track list
-		uint32_t num_levels = 0;
 		// the walk's normalize may take the short exact forms when every rotation it meets comes out of clips that are proven safe for
 		// them (norms near 1; a caller's base pose buffer holds anything)
 		uint32_t short_exact = kBase == k_consumer_base_buffer ? 0u : 1u;
@@ -808,17 +572,8 @@
 			if (!refused)
 			{
 				// every clip of the blend: known, a transform clip, with a known map of its own into this skeleton
-				for (uint32_t k = 1; k < consumers.num_blend_clips; ++k)
-				{
-					const uint32_t blend_clip_id = as_constant(consumers.blend_clip_ids)[size_t(instance) * (consumers.num_blend_clips - 1u) + (k - 1u)];
-					const ACLHIP_CONSTANT device_clip* record = as_constant(clips) + (blend_clip_id < num_clips ? blend_clip_id : 0);
-					const uint32_t blend_map_id = as_constant(mapping->blend_maps)[size_t(instance) * (consumers.num_blend_clips - 1u) + (k - 1u)];
-					const ACLHIP_CONSTANT device_track_map* map_record = as_constant(mapping->maps) + (blend_map_id < mapping->num_maps ? blend_map_id : 0);
-					refused = refused || blend_clip_id >= num_clips || !is_transform_clip(record->flags)
-						|| blend_map_id >= mapping->num_maps || map_record->image == nullptr || map_record->num_tracks != record->num_tracks || map_record->num_slots != skeleton.num_bones
-						|| (!kMirrored && multiplies_transforms && (record->flags & k_clip_negative_scale) != 0);
-					short_exact &= walk_may_use_short_exact_math(record->flags, params.normalization);
-				}
+				refused = blend_partners_refused<!kMirrored && multiplies_transforms>(clips, num_clips, consumers, instance, params.normalization, short_exact,
+					[&](size_t entry, const ACLHIP_CONSTANT device_clip* record) { return blend_map_fits(mapping, entry, record, skeleton.num_bones); });
 				// every mask the instance names: the null handle, or a known mask of this skeleton's slot count
 				for (uint32_t k = 0; k < consumers.num_blend_clips; ++k)
 				{
@@ -839,36 +594,7 @@
 				if (role == 0)
 				{
 					if (object_space)
-					{
-						// The walk schedule for this many instances per workgroup, requested BEFORE the decode (until round 4 behind it: three
-						// more dependent round trips -- offset, header, words -- at the end of every wave's chain, 1.7 of a decode's 6.3 us).
-						// One scalar load for the schedule's header (aclhip_set_clip_hierarchy: {offset, steps, words, 0} per workgroup size,
-						// in flight next to the seek's sample records), then the words travel global -> LDS by DMA while the pose is decoded:
-						//     num_steps | words | step_end[num_steps] | transform | parent << 16 in step order, padded to whole 16 byte pieces
-						// Every wave leaves its schedule in the shared copy: the same words when they share it (the copy is only used then).
-						// A schedule longer than the launch reserved LDS for (a hierarchy set behind a captured launch's back) stays in
-						// global memory and the walk reads it there.
-						const u32x4 header = ((const ACLHIP_CONSTANT u32x4*)hierarchy)[log2_instances_per_block];
-						uint32_t schedule_offset = header.x, num_words = header.z;
-						num_levels = header.y;
-						asm volatile("" : "+s"(schedule_offset), "+s"(num_levels), "+s"(num_words));		// (registers of their own: load_map_fields)
-						schedule = hierarchy + schedule_offset;
-						if (num_words <= (packed_block_shape >> 8))
-						{
-							for (uint32_t base = 0; base < num_words; base += k_wave_size * 4u)
-								if (base + lane * 4u < num_words)
-									__builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(schedule + base + lane * 4u),
-										(__attribute__((address_space(3))) void*)(shared_schedule + base), 16, 0, 0);
-						}
-						else
-							num_levels |= 0x80000000u;
-						// (left in the walk's slots now, not held across the decodes)
-						if (lane == 0)
-						{
-							walk_levels[slot] = num_levels;
-							walk_schedules[slot] = schedule;
-						}
-					}
+						request_walk_schedule(hierarchy, log2_instances_per_block, packed_block_shape >> 8, shared_schedule, slot, lane, walk);
 					decode_pose_into_slot_image(clip, clip_map, clip_fill, as_constant(sample_times)[instance], rounding_policy, params, lane, image);
 					{
 						// (every pass reads its lists and tables from the kernarg segment: masked_kernel_args)
@@ -876,7 +602,7 @@
 						wave_lds_barrier();		// the first pose is complete (its DMA has landed)
 						{
 							const ACLHIP_CONSTANT masked_kernel_args* args = late_masked_kernel_args();
-							blend_scale_slot_image(image, pose_tracks * 3u, slot_weight_of(args->masking.masks, args->masking.layered, as_constant(args->masking.instance_masks) + size_t(instance) * num_blend_clips,
+							blend_scale_image(image, pose_tracks * 3u, slot_weight_of(args->masking.masks, args->masking.layered, as_constant(args->masking.instance_masks) + size_t(instance) * num_blend_clips,
 								as_constant(args->consumers.blend_weights) + size_t(instance) * num_blend_clips, num_blend_clips, 0), lane);
 						}
 						for (uint32_t k = 1; k < num_blend_clips; ++k)
@@ -891,7 +617,7 @@
 							// (the launch's decode settings too, with the instance's looping policy as above)
 							decode_params pass_params = load_decode_params(&args->params);
 							pass_params.looping_policy = looping_policy;
-							blend_clip_onto_masked_slot_image(blend_clip, blend_map, clip_fill, as_constant(args->consumers.blend_sample_times)[entry], rounding_policy, pass_params, weight, lane, image);
+							blend_clip_onto_slot_image(blend_clip, blend_map, clip_fill, as_constant(args->consumers.blend_sample_times)[entry], rounding_policy, pass_params, weight, lane, image);
 						}
 						wave_lds_barrier();
 						blend_normalize_rotations(image, pose_tracks, lane);
@@ -903,151 +629,8 @@
 		// both images of every instance are complete
 		// (what the tail needs of the launch is read from the kernarg segment here, behind the decodes: masked_kernel_args)
 		const ACLHIP_CONSTANT masked_kernel_args* const tail_args = late_masked_kernel_args();
-		if (two_waves)
-			__syncthreads();
-		else
-			wave_lds_barrier();
-
-		if (has_base)
-		{
-			const f32x4* base_source = base_is_clip ? base_image : reinterpret_cast<const f32x4*>(tail_args->consumers.base_poses + uint64_t(instance) * tail_args->consumers.base_pose_stride_bytes);
-			const uint32_t additive_format = tail_args->consumers.additive_format;
-			for (uint32_t transform_index = role * k_wave_size + lane; transform_index < num_tracks; transform_index += waves_per_instance * k_wave_size)
-			{
-				const qvv additive = load_qvv(image, transform_index);
-				const qvv base = load_qvv(base_source, transform_index);
-				store_qvv(image, transform_index, apply_additive_to_base<kMirrored>(additive_format, base, additive));
-				// additive_clip_format8::relative is a qvv_mul (core/additive_utils.h:128-160)
-				if constexpr (kMirrored)
-				{
-					const uint64_t mirrored = __ballot(additive_format == 1 && qvv_mul_takes_matrix_path(additive, base));
-					if (mirrored != 0 && lane == uint32_t(__builtin_ctzll(mirrored)))
-						atomicAdd(tail_args->rejected_count + 1, (unsigned long long)__builtin_popcountll(mirrored));
-				}
-			}
-		}
-
-		if (object_space)
-		{
-			if (lane == 0 && role == 0)
-			{
-				if (num_tracks == 0)
-				{
-					walk_levels[slot] = 0;
-					walk_schedules[slot] = nullptr;
-				}
-				walk_tracks[slot] = num_tracks;
-				walk_short_exact[slot] = num_tracks != 0 ? short_exact : 1u;
-			}
-			__syncthreads();
-			ACLHIP_PHASE_STAMP(1);
-
-			// ONE wave walks and then stores the workgroup's poses; the others are done and give their wave slots and registers back (a
-			// pose waits in LDS for the walk about as long as its decode took: with every wave parked at a barrier the wave slots, not the
-			// LDS, decided how many poses a CU holds). The walking wave rotates with the workgroup index: waves land on SIMDs by their
-			// index inside the workgroup, and walks that all ran on a CU's first SIMD would queue there.
-			if (wave_in_block != (blockIdx.x & ((blockDim.x / k_wave_size) - 1u)))
-				return;
-			{
-				// lanes <-> (instance slot, transform of the current step): slot = lane % instances, lane / instances picks the slot's
-				// transform inside the step. A transform's parent was scheduled in an earlier step: final by the time it is read.
-				const uint32_t walk_slot = lane & ((1u << log2_instances_per_block) - 1u);
-				const uint32_t first = lane >> log2_instances_per_block;
-				f32x4* slot_image = reinterpret_cast<f32x4*>(dynamic_lds + size_t(walk_slot) * tail_args->lds_bytes_per_instance);
-				[[maybe_unused]] unsigned long long* const negative_scale_count = tail_args->rejected_count + 1;
-				const uint32_t slot_steps = walk_levels[walk_slot] & 0x7FFFFFFFu;
-				const bool slot_schedule_is_shared = (walk_levels[walk_slot] & 0x80000000u) == 0;
-				const uint32_t* slot_schedule = walk_schedules[walk_slot];
-
-				const auto walk = [&](const auto* schedule_words, auto short_exact_tag)
-				{
-					constexpr bool k_short_exact = decltype(short_exact_tag)::value;		// sqrt_rn_short / rcp_rn_short in the normalize (aclhip_device.h)
-					const auto* pairs = schedule_words + 2u + slot_steps;
-					uint32_t step_start = 0;
-					for (uint32_t step = 0; __any(int(step < slot_steps)) != 0; ++step)
-					{
-						if (step < slot_steps)
-						{
-							const uint32_t step_end = schedule_words[2 + step];
-							const uint32_t pair_index = step_start + first;
-							if (pair_index < step_end)
-							{
-								const uint32_t pair = pairs[pair_index];		// transform | parent << 16
-								const qvv child = load_qvv(slot_image, pair & 0xFFFFu), parent = load_qvv(slot_image, pair >> 16);
-								qvv object;
-								if constexpr (kMirrored)
-								{
-									const uint64_t mirrored = __ballot(qvv_mul_takes_matrix_path(child, parent));
-									if (mirrored != 0 && lane == uint32_t(__builtin_ctzll(mirrored)))
-										atomicAdd(negative_scale_count, (unsigned long long)__builtin_popcountll(mirrored));
-									object = qvv_mul(child, parent);
-									if (mirrored != 0 && qvv_mul_takes_matrix_path(child, parent))
-										object = qvv_mul_through_matrices(child, parent);
-								}
-								else
-								{
-									// neither a registered clip nor a reference pose can hand over a negative scale and the base is a clip:
-									// products and sums of non negative scales -- nothing to count, nothing to route
-									object = qvv_mul(child, parent);
-								}
-								object.rotation = quat_normalize<k_short_exact>(object.rotation);
-								store_qvv(slot_image, pair & 0xFFFFu, object);
-							}
-							step_start = step_end;
-						}
-						wave_lds_barrier();
-					}
-				};
-
-				// all instances that walk follow the same schedule? then the shared LDS copy is theirs; otherwise each reads its own
-				// from global memory (rare: mixed skeletons inside one workgroup)
-				// the rest of the workgroup waits for this wave: it goes first on its SIMD
-				__builtin_amdgcn_s_setprio(3);
-				const uint64_t walkers = __ballot(slot_steps != 0);
-				if (walkers != 0)
-				{
-					const uint32_t leader = uint32_t(__builtin_ctzll(walkers));
-					const uint64_t mine = reinterpret_cast<uint64_t>(slot_schedule);
-					const uint64_t first_schedule = (uint64_t(__shfl(uint32_t(mine >> 32), int(leader))) << 32) | __shfl(uint32_t(mine), int(leader));
-					const bool shared_copy = __all(int(slot_steps == 0 || (mine == first_schedule && slot_schedule_is_shared))) != 0;
-					const bool short_exact_walk = __all(int(walk_short_exact[walk_slot] != 0)) != 0;
-					const auto walk_with = [&](auto short_exact_tag)
-					{
-						if (shared_copy)
-							walk(static_cast<const uint32_t*>(shared_schedule), short_exact_tag);
-						else
-							walk(as_constant(slot_schedule), short_exact_tag);
-					};
-					if (short_exact_walk)
-						walk_with(std::true_type());
-					else
-						walk_with(std::false_type());
-				}
-				__builtin_amdgcn_s_setprio(0);
-			}
-			wave_lds_barrier();
-			ACLHIP_PHASE_STAMP(2);
-
-			const uint32_t instances_per_block = 1u << log2_instances_per_block;
-			for (uint32_t store_slot = 0; store_slot < instances_per_block; ++store_slot)
-			{
-				const uint32_t slot_quads = walk_tracks[store_slot] * 3u;
-				const f32x4* slot_image = reinterpret_cast<const f32x4*>(dynamic_lds + size_t(store_slot) * tail_args->lds_bytes_per_instance);
-				f32x4* slot_pose = reinterpret_cast<f32x4*>(tail_args->poses + uint64_t((blockIdx.x << log2_instances_per_block) + store_slot) * tail_args->pose_stride_bytes);
-				for (uint32_t quad = lane; quad < slot_quads; quad += k_wave_size)
-					store_streaming(&slot_pose[quad], slot_image[quad]);
-			}
-			ACLHIP_PHASE_STAMP(3);
-			return;
-		}
-		else if (two_waves)
-			__syncthreads();
-		else
-			wave_lds_barrier();
-
-		const uint32_t num_quads = num_tracks * 3u;
-		f32x4* pose = reinterpret_cast<f32x4*>(tail_args->poses + uint64_t(instance) * tail_args->pose_stride_bytes);
-		for (uint32_t quad = role * k_wave_size + lane; quad < num_quads; quad += waves_per_instance * k_wave_size)
-			store_streaming(&pose[quad], image[quad]);
-		ACLHIP_PHASE_STAMP(3);
+		finish_consumer_poses<kObjectSpace, kBase, false, kMirrored, false>(
+			consumer_tail_args{ tail_args->poses, tail_args->pose_stride_bytes, tail_args->lds_bytes_per_instance, log2_instances_per_block, tail_args->rejected_count,
+				tail_args->consumers.base_poses, tail_args->consumers.base_pose_stride_bytes, tail_args->consumers.additive_format },
+			consumer_wave{ image, base_image, shared_schedule, slot, role, lane, wave_in_block, instance, num_tracks, short_exact }, walk);
 	}
