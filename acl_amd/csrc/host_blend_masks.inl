@@ -162,6 +162,31 @@ extern "C" aclhip_status aclhip_get_blend_mask_info(const aclhip_context* contex
 	return ACLHIP_OK;
 }
 
+namespace
+{
+	// What the masked launches (_masked, _bounds with a masking) check of their masking, and the launch argument made of it
+	aclhip_status check_blend_masking(aclhip_context* context, const aclhip_pose_consumers* consumers, const aclhip_blend_masking* masking)
+	{
+		if (masking->mode > ACLHIP_BLEND_LAYERED)
+			return fail(context, ACLHIP_ERROR_INVALID_ARGUMENT, "unknown blend mode %u", masking->mode);
+		if (masking->reserved0 != 0 || masking->reserved[0] != 0 || masking->reserved[1] != 0)
+			return fail(context, ACLHIP_ERROR_INVALID_ARGUMENT, "the reserved fields of a blend masking are 0");
+		if (masking->instance_masks == nullptr)
+			return fail(context, ACLHIP_ERROR_INVALID_ARGUMENT, "a blend masking names a list of masks (entries may be 0)");
+		if (consumers->num_blend_clips < 2)
+			return fail(context, ACLHIP_ERROR_INVALID_ARGUMENT, "blend masks go with a blend: num_blend_clips is %u", consumers->num_blend_clips);
+		return ACLHIP_OK;
+	}
+
+	blend_mask_launch blend_mask_launch_of(const aclhip_blend_masking* masking)
+	{
+		blend_mask_launch launch = {};
+		launch.layered = masking->mode == ACLHIP_BLEND_LAYERED ? 1u : 0u;
+		launch.instance_masks = masking->instance_masks;
+		return launch;
+	}
+}
+
 extern "C" aclhip_status aclhip_decompress_poses_batch_masked(aclhip_context* context, const aclhip_clip* clips, const float* sample_times, uint32_t num_instances,
 	const aclhip_decompress_params* params, const aclhip_pose_consumers* consumers, const aclhip_pose_mapping* mapping, const aclhip_blend_masking* masking,
 	void* poses, uint64_t pose_stride_bytes, void* stream)
@@ -175,23 +200,11 @@ extern "C" aclhip_status aclhip_decompress_poses_batch_masked(aclhip_context* co
 		return fail(context, ACLHIP_ERROR_INVALID_ARGUMENT, "null pose mapping");
 	if (masking == nullptr)
 		return fail(context, ACLHIP_ERROR_INVALID_ARGUMENT, "null blend masking");
-	if (masking->mode > ACLHIP_BLEND_LAYERED)
-		return fail(context, ACLHIP_ERROR_INVALID_ARGUMENT, "unknown blend mode %u", masking->mode);
-	if (masking->reserved0 != 0 || masking->reserved[0] != 0 || masking->reserved[1] != 0)
-		return fail(context, ACLHIP_ERROR_INVALID_ARGUMENT, "the reserved fields of a blend masking are 0");
-	if (masking->instance_masks == nullptr)
-		return fail(context, ACLHIP_ERROR_INVALID_ARGUMENT, "a blend masking names a list of masks (entries may be 0)");
-	if (consumers->num_blend_clips < 2)
-		return fail(context, ACLHIP_ERROR_INVALID_ARGUMENT, "blend masks go with a blend: num_blend_clips is %u", consumers->num_blend_clips);
-	if (mapping->skeleton == 0 && mapping->instance_skeletons == nullptr)
-		return fail(context, ACLHIP_ERROR_INVALID_ARGUMENT, "a pose mapping names a skeleton or a list of skeletons");
-	if (mapping->map == 0 && mapping->instance_maps == nullptr)
-		return fail(context, ACLHIP_ERROR_INVALID_ARGUMENT, "a pose mapping names a map or a list of maps");
-	if (mapping->blend_maps == nullptr)
-		return fail(context, ACLHIP_ERROR_INVALID_ARGUMENT, "a blend in skeleton space needs blend_maps");
-	const bool base_is_clip = consumers->additive_format != ACLHIP_ADDITIVE_NONE && consumers->base_clips != nullptr;
-	if (base_is_clip && mapping->base_maps == nullptr)
-		return fail(context, ACLHIP_ERROR_INVALID_ARGUMENT, "base clips in skeleton space need base_maps");
+	status = check_blend_masking(context, consumers, masking);
+	if (status == ACLHIP_OK)
+		status = check_pose_mapping(context, consumers, mapping);
+	if (status != ACLHIP_OK)
+		return status;
 	if (num_instances == 0)
 		return ACLHIP_OK;
 
@@ -200,18 +213,56 @@ extern "C" aclhip_status aclhip_decompress_poses_batch_masked(aclhip_context* co
 	if (status != ACLHIP_OK)
 		return status;
 
-	// (the tables and their capacities are filled in by launch_consumers, under the registry lock)
-	skeleton_launch launch = {};
-	launch.skeleton = mapping->skeleton;
-	launch.map = mapping->map;
-	launch.instance_skeletons = mapping->instance_skeletons;
-	launch.instance_maps = mapping->instance_maps;
-	launch.blend_maps = mapping->blend_maps;
-	launch.base_maps = base_is_clip ? mapping->base_maps : nullptr;
-	blend_mask_launch mask_launch = {};
-	mask_launch.layered = masking->mode == ACLHIP_BLEND_LAYERED ? 1u : 0u;
-	mask_launch.instance_masks = masking->instance_masks;
+	const skeleton_launch launch = skeleton_launch_of(consumers, mapping);
+	const blend_mask_launch mask_launch = blend_mask_launch_of(masking);
 
 	device_guard guard(context->device);
 	return launch_consumers(context, clips, sample_times, num_instances, device_params, *consumers, poses, pose_stride_bytes, static_cast<hipStream_t>(stream), &launch, &mask_launch);
+}
+
+// The launch above, the mapped launch or the unmapped one -- by which of `mapping` and `masking` are set -- with a box per instance
+// (include/aclhip.h: aclhip_pose_bounds). The argument checks that need no device come first and leave a message, with or without a context.
+extern "C" aclhip_status aclhip_decompress_poses_batch_bounds(aclhip_context* context, const aclhip_clip* clips, const float* sample_times, uint32_t num_instances,
+	const aclhip_decompress_params* params, const aclhip_pose_consumers* consumers, const aclhip_pose_mapping* mapping, const aclhip_blend_masking* masking,
+	const aclhip_pose_bounds* bounds, void* poses, uint64_t pose_stride_bytes, void* stream)
+{
+	if (bounds == nullptr)
+		return fail(context, ACLHIP_ERROR_INVALID_ARGUMENT, "null pose bounds");
+	if (bounds->bounds == nullptr || (reinterpret_cast<uintptr_t>(bounds->bounds) & 15u) != 0)
+		return fail(context, ACLHIP_ERROR_INVALID_ARGUMENT, "the bounds buffer must be set and 16 byte aligned");
+	if (bounds->reserved[0] != 0 || bounds->reserved[1] != 0)
+		return fail(context, ACLHIP_ERROR_INVALID_ARGUMENT, "the reserved fields of pose bounds are 0");
+	if (consumers == nullptr)
+		return fail(context, ACLHIP_ERROR_INVALID_ARGUMENT, "null consumers");
+	if (consumers->object_space == 0)
+		return fail(context, ACLHIP_ERROR_INVALID_ARGUMENT, "pose bounds are taken in object space: a local space translation is not a position");
+	if (masking != nullptr && mapping == nullptr)
+		return fail(context, ACLHIP_ERROR_INVALID_ARGUMENT, "blend masks go with a pose mapping");
+	// check_batch_arguments without its pose buffer: `poses` may be null here (the bounds alone)
+	if (num_instances != 0 && (clips == nullptr || sample_times == nullptr))
+		return fail(context, ACLHIP_ERROR_INVALID_ARGUMENT, "null instance list");
+	if ((pose_stride_bytes & 15u) != 0 || (reinterpret_cast<uintptr_t>(poses) & 15u) != 0)
+		return fail(context, ACLHIP_ERROR_INVALID_ARGUMENT, "pose buffer and stride must be 16 byte aligned");
+	aclhip_status status = masking != nullptr ? check_blend_masking(context, consumers, masking) : ACLHIP_OK;
+	if (status == ACLHIP_OK && mapping != nullptr)
+		status = check_pose_mapping(context, consumers, mapping);
+	if (status != ACLHIP_OK)
+		return status;
+	if (context == nullptr)
+		return fail(context, ACLHIP_ERROR_INVALID_ARGUMENT, "null context");
+	if (num_instances == 0)
+		return ACLHIP_OK;
+
+	decode_params device_params;
+	status = resolve_params(context, params, device_params);
+	if (status != ACLHIP_OK)
+		return status;
+
+	const skeleton_launch launch = mapping != nullptr ? skeleton_launch_of(consumers, mapping) : skeleton_launch{};
+	const blend_mask_launch mask_launch = masking != nullptr ? blend_mask_launch_of(masking) : blend_mask_launch{};
+	const consumer_bounds_launch bounds_launch = { static_cast<uint8_t*>(bounds->bounds), bounds->bone_flags };
+
+	device_guard guard(context->device);
+	return launch_consumers(context, clips, sample_times, num_instances, device_params, *consumers, poses, pose_stride_bytes, static_cast<hipStream_t>(stream),
+		mapping != nullptr ? &launch : nullptr, masking != nullptr ? &mask_launch : nullptr, &bounds_launch);
 }

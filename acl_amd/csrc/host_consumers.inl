@@ -347,12 +347,49 @@ namespace
 		}); });
 	}
 
+	// The instantiations of the three entry points for a launch without (no bounds_types) or with bounds (consumer_bounds_launch, the
+	// kernels' last argument: aclhip_decompress_poses_batch_bounds). Bounds exist in object space only: no local space instantiation.
+	template<class... bounds_types>
+	struct pose_consumer_kernels
+	{
+		static constexpr bool with_bounds = sizeof...(bounds_types) != 0;
+		using unmapped_type = pose_consumer_kernel<bounds_types...>;
+		using skeleton_type = pose_consumer_kernel<skeleton_launch, bounds_types...>;
+		using masked_type = pose_consumer_kernel<skeleton_launch, blend_mask_launch, bounds_types...>;
+
+		template<bool kObjectSpace, uint32_t kBase, bool kUnitScale, bool kMirrored, bool kBlend = false, bool kFast = false>
+		static unmapped_type unmapped()
+		{
+			if constexpr (with_bounds && !kObjectSpace)
+				return nullptr;
+			else
+				return decompress_poses_consumer_kernel<kObjectSpace, kBase, kUnitScale, kMirrored, kBlend, kFast, bounds_types...>;
+		}
+		template<bool kObjectSpace, uint32_t kBase, bool kMirrored, bool kBlend>
+		static skeleton_type skeleton()
+		{
+			if constexpr (with_bounds && !kObjectSpace)
+				return nullptr;
+			else
+				return decompress_poses_skeleton_kernel<kObjectSpace, kBase, kMirrored, kBlend, bounds_types...>;
+		}
+		template<bool kObjectSpace, uint32_t kBase, bool kMirrored>
+		static masked_type masked()
+		{
+			if constexpr (with_bounds && !kObjectSpace)
+				return nullptr;
+			else
+				return decompress_poses_masked_kernel<kObjectSpace, kBase, kMirrored, bounds_types...>;
+		}
+	};
+
 	// `mapping` (aclhip_decompress_poses_batch_mapped): skeleton space -- the launch is shaped by its rows alone (pose_stride_bytes / 48
 	// slots), the skeleton kernels take the mapping as their trailing argument. `masking` (aclhip_decompress_poses_batch_masked, with a
-	// mapping and a blend): the same launch through the masked kernels.
+	// mapping and a blend): the same launch through the masked kernels. `bounds` (aclhip_decompress_poses_batch_bounds, object space): the
+	// same launch through the bounds instantiations, a box per instance on top of the rows -- or in their place, `poses` may then be null.
 	aclhip_status launch_consumers(aclhip_context* context, const aclhip_clip* clips, const float* sample_times, uint32_t num_instances,
 		const decode_params& params, const aclhip_pose_consumers& consumers, void* poses, uint64_t pose_stride_bytes, hipStream_t stream, const skeleton_launch* mapping = nullptr,
-		const blend_mask_launch* masking = nullptr)
+		const blend_mask_launch* masking = nullptr, const consumer_bounds_launch* bounds = nullptr)
 	{
 		if (consumers.additive_format > ACLHIP_ADDITIVE_ADDITIVE1)
 			return fail(context, ACLHIP_ERROR_INVALID_ARGUMENT, "unknown additive format %u", consumers.additive_format);
@@ -473,28 +510,34 @@ namespace
 			ACLHIP_CHECK_HIP(context, hipGetLastError());
 			return ACLHIP_OK;
 		};
-		if (masking != nullptr)
-			return launch(pose_consumer_kernel_of<pose_consumer_kernel<skeleton_launch, blend_mask_launch>, true>(object_space, base_kind, mirrored, [](auto space, auto base, auto route)
-				{ return decompress_poses_masked_kernel<space(), base(), route()>; }), device_mapping, device_masking);
-		if (mapping != nullptr)
-			return launch(blend
-				? pose_consumer_kernel_of<pose_consumer_kernel<skeleton_launch>, true>(object_space, base_kind, mirrored, [](auto space, auto base, auto route)
-					{ return decompress_poses_skeleton_kernel<space(), base(), route(), true>; })
-				: pose_consumer_kernel_of<pose_consumer_kernel<skeleton_launch>, false>(object_space, base_kind, mirrored, [](auto space, auto base, auto route)
-					{ return decompress_poses_skeleton_kernel<space(), base(), route(), false>; }), device_mapping);
 		// ACLHIP_CONSUMERS_FAST: object space launches without a blend, in the hardware's 1 ulp arithmetic (include/aclhip.h)
 		const bool fast = (consumers.flags & ACLHIP_CONSUMERS_FAST) != 0 && object_space && !blend;
-		// one instantiation per (object space, kind of base, matrix route); rotation | translation images: object space without a base only
-		if (unit_scale)
-			return launch(fast ? decompress_poses_consumer_kernel<true, k_consumer_base_none, true, false, false, true> : decompress_poses_consumer_kernel<true, k_consumer_base_none, true, false>);
-		if (blend)
-			return launch(pose_consumer_kernel_of<pose_consumer_kernel<>, true>(object_space, base_kind, mirrored, [](auto space, auto base, auto route)
-				{ return decompress_poses_consumer_kernel<space(), base(), false, route(), true>; }));
-		if (fast)		// (object space, see above)
-			return launch(pose_consumer_kernel_of<pose_consumer_kernel<>, false>(true, base_kind, mirrored, [](auto, auto base, auto route)
-				{ return decompress_poses_consumer_kernel<true, base(), false, route(), false, true>; }));
-		return launch(pose_consumer_kernel_of<pose_consumer_kernel<>, false>(object_space, base_kind, mirrored, [](auto space, auto base, auto route)
-			{ return decompress_poses_consumer_kernel<space(), base(), false, route()>; }));
+		// trailing: nothing, or the bounds launch
+		const auto launch_with = [&](const auto&... trailing) -> aclhip_status
+		{
+			using kernels = pose_consumer_kernels<std::decay_t<decltype(trailing)>...>;
+			if (masking != nullptr)
+				return launch(pose_consumer_kernel_of<typename kernels::masked_type, true>(object_space, base_kind, mirrored, [](auto space, auto base, auto route)
+					{ return kernels::template masked<space(), base(), route()>(); }), device_mapping, device_masking, trailing...);
+			if (mapping != nullptr)
+				return launch(blend
+					? pose_consumer_kernel_of<typename kernels::skeleton_type, true>(object_space, base_kind, mirrored, [](auto space, auto base, auto route)
+						{ return kernels::template skeleton<space(), base(), route(), true>(); })
+					: pose_consumer_kernel_of<typename kernels::skeleton_type, false>(object_space, base_kind, mirrored, [](auto space, auto base, auto route)
+						{ return kernels::template skeleton<space(), base(), route(), false>(); }), device_mapping, trailing...);
+			// one instantiation per (object space, kind of base, matrix route); rotation | translation images: object space without a base only
+			if (unit_scale)
+				return launch(fast ? kernels::template unmapped<true, k_consumer_base_none, true, false, false, true>() : kernels::template unmapped<true, k_consumer_base_none, true, false>(), trailing...);
+			if (blend)
+				return launch(pose_consumer_kernel_of<typename kernels::unmapped_type, true>(object_space, base_kind, mirrored, [](auto space, auto base, auto route)
+					{ return kernels::template unmapped<space(), base(), false, route(), true>(); }), trailing...);
+			if (fast)		// (object space, see above)
+				return launch(pose_consumer_kernel_of<typename kernels::unmapped_type, false>(true, base_kind, mirrored, [](auto, auto base, auto route)
+					{ return kernels::template unmapped<true, base(), false, route(), false, true>(); }), trailing...);
+			return launch(pose_consumer_kernel_of<typename kernels::unmapped_type, false>(object_space, base_kind, mirrored, [](auto space, auto base, auto route)
+				{ return kernels::template unmapped<space(), base(), false, route()>(); }), trailing...);
+		};
+		return bounds != nullptr ? launch_with(*bounds) : launch_with();
 	}
 }
 

@@ -227,6 +227,38 @@ extern "C" aclhip_status aclhip_get_skeleton_info(const aclhip_context* context,
 	return ACLHIP_OK;
 }
 
+namespace
+{
+	// What the skeleton space launches (_mapped, _masked, _bounds with a mapping) check of their mapping, and the launch argument made of it
+	aclhip_status check_pose_mapping(aclhip_context* context, const aclhip_pose_consumers* consumers, const aclhip_pose_mapping* mapping)
+	{
+		if (mapping->skeleton == 0 && mapping->instance_skeletons == nullptr)
+			return fail(context, ACLHIP_ERROR_INVALID_ARGUMENT, "a pose mapping names a skeleton or a list of skeletons");
+		if (mapping->map == 0 && mapping->instance_maps == nullptr)
+			return fail(context, ACLHIP_ERROR_INVALID_ARGUMENT, "a pose mapping names a map or a list of maps");
+		if (consumers->num_blend_clips > 1 && mapping->blend_maps == nullptr)
+			return fail(context, ACLHIP_ERROR_INVALID_ARGUMENT, "a blend in skeleton space needs blend_maps");
+		const bool base_is_clip = consumers->additive_format != ACLHIP_ADDITIVE_NONE && consumers->base_clips != nullptr;
+		if (base_is_clip && mapping->base_maps == nullptr)
+			return fail(context, ACLHIP_ERROR_INVALID_ARGUMENT, "base clips in skeleton space need base_maps");
+		return ACLHIP_OK;
+	}
+
+	// (the tables and their capacities are filled in by launch_consumers, under the registry lock)
+	skeleton_launch skeleton_launch_of(const aclhip_pose_consumers* consumers, const aclhip_pose_mapping* mapping)
+	{
+		const bool base_is_clip = consumers->additive_format != ACLHIP_ADDITIVE_NONE && consumers->base_clips != nullptr;
+		skeleton_launch launch = {};
+		launch.skeleton = mapping->skeleton;
+		launch.map = mapping->map;
+		launch.instance_skeletons = mapping->instance_skeletons;
+		launch.instance_maps = mapping->instance_maps;
+		launch.blend_maps = consumers->num_blend_clips > 1 ? mapping->blend_maps : nullptr;
+		launch.base_maps = base_is_clip ? mapping->base_maps : nullptr;
+		return launch;
+	}
+}
+
 extern "C" aclhip_status aclhip_decompress_poses_batch_mapped(aclhip_context* context, const aclhip_clip* clips, const float* sample_times, uint32_t num_instances,
 	const aclhip_decompress_params* params, const aclhip_pose_consumers* consumers, const aclhip_pose_mapping* mapping, void* poses, uint64_t pose_stride_bytes, void* stream)
 {
@@ -237,15 +269,9 @@ extern "C" aclhip_status aclhip_decompress_poses_batch_mapped(aclhip_context* co
 		return fail(context, ACLHIP_ERROR_INVALID_ARGUMENT, "null consumers");
 	if (mapping == nullptr)
 		return fail(context, ACLHIP_ERROR_INVALID_ARGUMENT, "null pose mapping");
-	if (mapping->skeleton == 0 && mapping->instance_skeletons == nullptr)
-		return fail(context, ACLHIP_ERROR_INVALID_ARGUMENT, "a pose mapping names a skeleton or a list of skeletons");
-	if (mapping->map == 0 && mapping->instance_maps == nullptr)
-		return fail(context, ACLHIP_ERROR_INVALID_ARGUMENT, "a pose mapping names a map or a list of maps");
-	if (consumers->num_blend_clips > 1 && mapping->blend_maps == nullptr)
-		return fail(context, ACLHIP_ERROR_INVALID_ARGUMENT, "a blend in skeleton space needs blend_maps");
-	const bool base_is_clip = consumers->additive_format != ACLHIP_ADDITIVE_NONE && consumers->base_clips != nullptr;
-	if (base_is_clip && mapping->base_maps == nullptr)
-		return fail(context, ACLHIP_ERROR_INVALID_ARGUMENT, "base clips in skeleton space need base_maps");
+	status = check_pose_mapping(context, consumers, mapping);
+	if (status != ACLHIP_OK)
+		return status;
 	if (num_instances == 0)
 		return ACLHIP_OK;
 
@@ -254,14 +280,7 @@ extern "C" aclhip_status aclhip_decompress_poses_batch_mapped(aclhip_context* co
 	if (status != ACLHIP_OK)
 		return status;
 
-	// (the tables and their capacities are filled in by launch_consumers, under the registry lock)
-	skeleton_launch launch = {};
-	launch.skeleton = mapping->skeleton;
-	launch.map = mapping->map;
-	launch.instance_skeletons = mapping->instance_skeletons;
-	launch.instance_maps = mapping->instance_maps;
-	launch.blend_maps = consumers->num_blend_clips > 1 ? mapping->blend_maps : nullptr;
-	launch.base_maps = base_is_clip ? mapping->base_maps : nullptr;
+	const skeleton_launch launch = skeleton_launch_of(consumers, mapping);
 
 	device_guard guard(context->device);
 	return launch_consumers(context, clips, sample_times, num_instances, device_params, *consumers, poses, pose_stride_bytes, static_cast<hipStream_t>(stream), &launch);

@@ -392,6 +392,76 @@
 		const uint8_t* base_poses;				// consumer_params'
 		uint64_t base_pose_stride_bytes;
 		uint32_t additive_format;
+		uint8_t* bounds = nullptr;				// kBounds: consumer_bounds_launch's
+		const uint8_t* bone_flags = nullptr;
+	};
+
+	// The bounds kernels' own trailing argument (aclhip_decompress_poses_batch_bounds): the instantiations that take it are the ones
+	// that compute bounds -- the others have no such argument and their text is what it was
+	struct consumer_bounds_launch
+	{
+		uint8_t* bounds;				// [num_instances] x 32 bytes: min.x min.y min.z 0 | max.x max.y max.z 0
+		const uint8_t* bone_flags;		// [transforms of a row] non-zero: the bone counts; null: every bone counts
+	};
+	__device__ __forceinline__ consumer_bounds_launch bounds_launch_of() { return consumer_bounds_launch{ nullptr, nullptr }; }
+	// (registers of their own for the two pointers, like load_map_fields in kernels_skeleton.inl: they arrive in one block of four, and in
+	// the instantiations with a second wave such a block's spill slot stayed behind as stack that nothing read or wrote)
+	__device__ __forceinline__ consumer_bounds_launch bounds_launch_of(const consumer_bounds_launch& launch)
+	{
+		consumer_bounds_launch own = launch;
+		asm volatile("" : "+s"(own.bounds), "+s"(own.bone_flags));
+		return own;
+	}
+	// walk.tracks of a slot in the bounds kernels: the instance is served and its pose has no transform -- the empty box is written
+	constexpr uint32_t k_consumer_empty_pose = 0x80000000u;
+
+	// A wave's minimum / maximum of a float that is no NaN in any lane, left in lane 63: four steps inside the rows of 16 lanes (quad
+	// permutes, then the mirrors: every lane of a row holds the row's result), two across them (row_bcast:15 into rows 1 and 3,
+	// row_bcast:31 into rows 2 and 3). Lanes a step does not write keep their own value: min(x, x).
+	template<bool kMaximum>
+	__device__ __forceinline__ float wave_reduce_into_last_lane(float value)
+	{
+		const auto combine = [](float a, float b) { return kMaximum ? fmaxf(a, b) : fminf(a, b); };
+		const auto moved = [](float source, auto control, auto row_mask)
+		{
+			return __int_as_float(__builtin_amdgcn_update_dpp(__float_as_int(source), __float_as_int(source), decltype(control)::value, decltype(row_mask)::value, 0xF, false));
+		};
+		using all_rows = std::integral_constant<int, 0xF>;
+		value = combine(value, moved(value, std::integral_constant<int, 0xB1>(), all_rows()));		// quad_perm:[1,0,3,2]
+		value = combine(value, moved(value, std::integral_constant<int, 0x4E>(), all_rows()));		// quad_perm:[2,3,0,1]
+		value = combine(value, moved(value, std::integral_constant<int, 0x141>(), all_rows()));	// row_half_mirror
+		value = combine(value, moved(value, std::integral_constant<int, 0x140>(), all_rows()));	// row_mirror
+		value = combine(value, moved(value, std::integral_constant<int, 0x142>(), std::integral_constant<int, 0xA>()));		// row_bcast:15
+		value = combine(value, moved(value, std::integral_constant<int, 0x143>(), std::integral_constant<int, 0xC>()));		// row_bcast:31
+		return value;
+	}
+
+	// The box of one pose (aclhip_pose_bounds): a lane's running minimum and maximum over the translations it meets. Compared as floats
+	// with < and >: a NaN coordinate loses every comparison and is ignored, the accumulators never hold one.
+	struct pose_box
+	{
+		float min_x = __builtin_inff(), min_y = __builtin_inff(), min_z = __builtin_inff();
+		float max_x = -__builtin_inff(), max_y = -__builtin_inff(), max_z = -__builtin_inff();
+		__device__ __forceinline__ void add(const f32x4& translation)
+		{
+			min_x = translation.x < min_x ? translation.x : min_x;
+			min_y = translation.y < min_y ? translation.y : min_y;
+			min_z = translation.z < min_z ? translation.z : min_z;
+			max_x = translation.x > max_x ? translation.x : max_x;
+			max_y = translation.y > max_y ? translation.y : max_y;
+			max_z = translation.z > max_z ? translation.z : max_z;
+		}
+		// the wave's box, by its last lane: 32 bytes, two vector stores
+		__device__ __forceinline__ void reduce_and_store(uint8_t* destination, uint32_t lane)
+		{
+			const f32x4 minimum{ wave_reduce_into_last_lane<false>(min_x), wave_reduce_into_last_lane<false>(min_y), wave_reduce_into_last_lane<false>(min_z), 0.0f };
+			const f32x4 maximum{ wave_reduce_into_last_lane<true>(max_x), wave_reduce_into_last_lane<true>(max_y), wave_reduce_into_last_lane<true>(max_z), 0.0f };
+			if (lane == k_wave_size - 1)
+			{
+				reinterpret_cast<f32x4*>(destination)[0] = minimum;
+				reinterpret_cast<f32x4*>(destination)[1] = maximum;
+			}
+		}
 	};
 
 	// and what the wave brings along from its decode
@@ -403,15 +473,20 @@
 		uint32_t slot, role, lane, wave_in_block, instance;
 		uint32_t num_tracks;		// 0 for a wave without work: past the batch, refused instance, empty track list
 		uint32_t short_exact;
+		bool empty_pose = false;	// kBounds: the instance is served and its pose has no transform (num_tracks is 0 for it too)
 	};
 
 	// The pose consumer kernels behind their decodes, from "both images of every instance are complete" on: the combine with the base
 	// pose, the object space walk, the store. The three kernels differ in how an image is filled; this is shared. kUnitScale and kFast:
 	// decompress_poses_consumer_kernel only.
-	template<bool kObjectSpace, uint32_t kBase, bool kUnitScale, bool kMirrored, bool kFast>
+	// kBounds (aclhip_decompress_poses_batch_bounds; object space): the walking wave, which reads every finished image to store it, also
+	// takes the minimum and maximum of its translation quads -- one box of 32 bytes per instance into args.bounds; args.poses may be
+	// null: the box alone, no row is stored.
+	template<bool kObjectSpace, uint32_t kBase, bool kUnitScale, bool kMirrored, bool kFast, bool kBounds = false>
 	__device__ __forceinline__ void finish_consumer_poses(const consumer_tail_args args, const consumer_wave wave, consumer_walk_slots& walk)
 	{
 		extern __shared__ __attribute__((aligned(16))) uint8_t dynamic_lds[];
+		static_assert(!kBounds || kObjectSpace, "bounds are taken over object space translations");
 		constexpr bool has_base = kBase != k_consumer_base_none;
 		constexpr bool base_is_clip = kBase == k_consumer_base_second_wave || kBase == k_consumer_base_fused;
 		constexpr bool fused_base = kBase == k_consumer_base_fused;
@@ -454,7 +529,10 @@
 					walk.levels[slot] = 0;
 					walk.schedules[slot] = nullptr;
 				}
-				walk.tracks[slot] = num_tracks;
+				if constexpr (kBounds)
+					walk.tracks[slot] = wave.empty_pose ? k_consumer_empty_pose : num_tracks;
+				else
+					walk.tracks[slot] = num_tracks;
 				walk.short_exact[slot] = num_tracks != 0 ? wave.short_exact : 1u;
 			}
 			__syncthreads();
@@ -508,6 +586,48 @@
 			ACLHIP_PHASE_STAMP(2);
 
 			const uint32_t instances_per_block = 1u << log2_instances_per_block;
+			if constexpr (kBounds)
+			{
+				// The store loop below with the box taken on the way: the quad a lane has just read for the row is a translation every
+				// third time (every second one in rotation | translation images) and goes into the lane's box when its bone counts.
+				// Without rows (args.poses == null, launch wide) only the translation quads are read. A slot without work -- past the
+				// batch, refused -- writes neither row nor box; a served pose of no transforms writes the empty box.
+				const ACLHIP_CONSTANT uint8_t* bone_flags = as_constant(args.bone_flags);
+				for (uint32_t store_slot = 0; store_slot < instances_per_block; ++store_slot)
+				{
+					const uint32_t slot_tracks = walk.tracks[store_slot];
+					if (slot_tracks == 0)
+						continue;
+					const uint32_t slot_quads = (slot_tracks & ~k_consumer_empty_pose) * 3u;
+					const uint64_t instance = (blockIdx.x << log2_instances_per_block) + store_slot;
+					const f32x4* slot_image = reinterpret_cast<const f32x4*>(dynamic_lds + size_t(store_slot) * args.lds_bytes_per_instance);
+					pose_box box;
+					if (args.poses != nullptr)
+					{
+						f32x4* slot_pose = reinterpret_cast<f32x4*>(args.poses + instance * args.pose_stride_bytes);
+						for (uint32_t quad = lane; quad < slot_quads; quad += k_wave_size)
+						{
+							const uint32_t track = quad / 3u;
+							const uint32_t kind = quad - track * 3u;
+							f32x4 value;
+							if (kUnitScale)
+								value = kind == 2 ? f32x4{ 1.0f, 1.0f, 1.0f, 0.0f } : slot_image[track * 2u + min(kind, 1u)];
+							else
+								value = slot_image[quad];
+							store_streaming(&slot_pose[quad], value);
+							if (kind == 1 && (bone_flags == nullptr || bone_flags[track] != 0))
+								box.add(value);
+						}
+					}
+					else
+						for (uint32_t track = lane; track * 3u < slot_quads; track += k_wave_size)
+							if (bone_flags == nullptr || bone_flags[track] != 0)
+								box.add(slot_image[track * (kUnitScale ? 2u : 3u) + 1u]);
+					box.reduce_and_store(args.bounds + instance * 32u, lane);
+				}
+				ACLHIP_PHASE_STAMP(3);
+				return;
+			}
 			for (uint32_t store_slot = 0; store_slot < instances_per_block; ++store_slot)
 			{
 				const uint32_t slot_quads = walk.tracks[store_slot] * 3u;
@@ -544,18 +664,20 @@
 	}
 
 	// The entry point of the unmapped launches (aclhip_decompress_poses_batch): the refusal test over the clips, every instance's image
-	// filled by decode_pose_into_image and its kin, then finish_consumer_poses.
-	template<bool kObjectSpace, uint32_t kBase, bool kUnitScale, bool kMirrored, bool kBlend = false, bool kFast = false>
+	// filled by decode_pose_into_image and its kin, then finish_consumer_poses. bounds_types: nothing, or consumer_bounds_launch -- the
+	// bounds instantiations (aclhip_decompress_poses_batch_bounds) take it as their trailing argument.
+	template<bool kObjectSpace, uint32_t kBase, bool kUnitScale, bool kMirrored, bool kBlend = false, bool kFast = false, class... bounds_types>
 	__global__ __launch_bounds__(k_consumer_max_waves * k_wave_size) void decompress_poses_consumer_kernel(const device_clip* __restrict__ clips, uint32_t num_clips,
 		const uint32_t* __restrict__ clip_ids, const float* __restrict__ sample_times, uint32_t num_instances, decode_params launch_params, consumer_params consumers,
 		uint8_t* __restrict__ poses, uint64_t pose_stride_bytes, uint32_t lds_quads_per_image, uint32_t lds_bytes_per_instance, uint32_t packed_block_shape,
-		unsigned long long* __restrict__ rejected_count)
+		unsigned long long* __restrict__ rejected_count, bounds_types... bounds_launch)
 	{
 		// packed_block_shape: log2 of the instances per workgroup (bits 0..7) | words of LDS reserved for the shared walk schedule (bits 8..31)
 		const uint32_t log2_instances_per_block = packed_block_shape & 0xFFu;
 		extern __shared__ __attribute__((aligned(16))) uint8_t dynamic_lds[];
 		__shared__ consumer_walk_slots walk;		// (what the host subtracts from the LDS it may ask for: host_consumers.inl)
 
+		constexpr bool with_bounds = sizeof...(bounds_types) != 0;
 		static_assert(!kUnitScale || (kObjectSpace && kBase == k_consumer_base_none), "rotation | translation images: object space without a base");
 		static_assert(!kBlend || (!kUnitScale && kBase != k_consumer_base_fused), "a blend accumulates whole qvv images; a base clip is decoded by a second wave");
 		static_assert(!kFast || !kBlend, "ACLHIP_CONSUMERS_FAST: not instantiated for blends");
@@ -586,6 +708,7 @@
 		// the walk's normalize may take the short exact forms when every rotation it meets comes out of clips that are proven safe for
 		// them (norms near 1; a caller's base pose buffer holds anything)
 		uint32_t short_exact = kBase == k_consumer_base_buffer ? 0u : 1u;
+		[[maybe_unused]] bool empty_pose = false;		// (bounds: a served instance whose clip has no track)
 		if (instance < num_instances)
 		{
 			const uint32_t clip_id = as_constant(clip_ids)[instance];
@@ -669,10 +792,14 @@
 					}
 				}
 			}
+			else if constexpr (with_bounds)
+				empty_pose = true;
 		}
 
 		// both images of every instance are complete
-		finish_consumer_poses<kObjectSpace, kBase, kUnitScale, kMirrored, kFast>(
-			consumer_tail_args{ poses, pose_stride_bytes, lds_bytes_per_instance, log2_instances_per_block, rejected_count, consumers.base_poses, consumers.base_pose_stride_bytes, consumers.additive_format },
-			consumer_wave{ image, base_image, shared_schedule, slot, role, lane, wave_in_block, instance, num_tracks, short_exact }, walk);
+		const consumer_bounds_launch bounds = bounds_launch_of(bounds_launch...);
+		finish_consumer_poses<kObjectSpace, kBase, kUnitScale, kMirrored, kFast, with_bounds>(
+			consumer_tail_args{ poses, pose_stride_bytes, lds_bytes_per_instance, log2_instances_per_block, rejected_count, consumers.base_poses, consumers.base_pose_stride_bytes, consumers.additive_format,
+				bounds.bounds, bounds.bone_flags },
+			consumer_wave{ image, base_image, shared_schedule, slot, role, lane, wave_in_block, instance, num_tracks, short_exact, empty_pose }, walk);
 	}

@@ -183,12 +183,14 @@
 	// images are filled in slot order --; behind the decodes it is that kernel's finish_consumer_poses, without rotation | translation
 	// images and without ACLHIP_CONSUMERS_FAST. (Until the three kernels were held to resources and time instead of identical disassembly
 	// the whole text was repeated here: profiles/skeleton_poses.md, profiles/consumer_kernel_sharing.md.)
-	template<bool kObjectSpace, uint32_t kBase, bool kMirrored, bool kBlend>
+	template<bool kObjectSpace, uint32_t kBase, bool kMirrored, bool kBlend, class... bounds_types>
 	__global__ __launch_bounds__(k_consumer_max_waves * k_wave_size) void decompress_poses_skeleton_kernel(const device_clip* __restrict__ clips, uint32_t num_clips,
 		const uint32_t* __restrict__ clip_ids, const float* __restrict__ sample_times, uint32_t num_instances, decode_params launch_params, consumer_params consumers,
 		uint8_t* __restrict__ poses, uint64_t pose_stride_bytes, uint32_t lds_quads_per_image, uint32_t lds_bytes_per_instance, uint32_t packed_block_shape,
-		unsigned long long* __restrict__ rejected_count, skeleton_launch skeleton_mapping)
+		unsigned long long* __restrict__ rejected_count, skeleton_launch skeleton_mapping, bounds_types... bounds_launch)
 	{
+		// (bounds_types: nothing, or consumer_bounds_launch -- aclhip_decompress_poses_batch_bounds, kernels_consumers.inl)
+		constexpr bool with_bounds = sizeof...(bounds_types) != 0;
 		const skeleton_launch* const mapping = &skeleton_mapping;
 		// packed_block_shape: log2 of the instances per workgroup (bits 0..7) | words of LDS reserved for the shared walk schedule (bits 8..31)
 		const uint32_t log2_instances_per_block = packed_block_shape & 0xFFu;
@@ -222,6 +224,7 @@
 		// the walk's normalize may take the short exact forms when every rotation it meets comes out of clips that are proven safe for
 		// them (norms near 1; a caller's base pose buffer holds anything)
 		uint32_t short_exact = kBase == k_consumer_base_buffer ? 0u : 1u;
+		[[maybe_unused]] bool empty_pose = false;		// (bounds: a served instance whose pose has no transform)
 		if (instance < num_instances)
 		{
 			const uint32_t clip_id = as_constant(clip_ids)[instance];
@@ -322,12 +325,16 @@
 					}
 				}
 			}
+			else if constexpr (with_bounds)
+				empty_pose = true;
 		}
 
 		// both images of every instance are complete
-		finish_consumer_poses<kObjectSpace, kBase, false, kMirrored, false>(
-			consumer_tail_args{ poses, pose_stride_bytes, lds_bytes_per_instance, log2_instances_per_block, rejected_count, consumers.base_poses, consumers.base_pose_stride_bytes, consumers.additive_format },
-			consumer_wave{ image, base_image, shared_schedule, slot, role, lane, wave_in_block, instance, num_tracks, short_exact }, walk);
+		const consumer_bounds_launch bounds = bounds_launch_of(bounds_launch...);
+		finish_consumer_poses<kObjectSpace, kBase, false, kMirrored, false, with_bounds>(
+			consumer_tail_args{ poses, pose_stride_bytes, lds_bytes_per_instance, log2_instances_per_block, rejected_count, consumers.base_poses, consumers.base_pose_stride_bytes, consumers.additive_format,
+				bounds.bounds, bounds.bone_flags },
+			consumer_wave{ image, base_image, shared_schedule, slot, role, lane, wave_in_block, instance, num_tracks, short_exact, empty_pose }, walk);
 	}
 
 	// ---- blend masks (aclhip_register_blend_mask, aclhip_decompress_poses_batch_masked) ------------------------------------------------
@@ -446,6 +453,13 @@
 	static_assert(offsetof(masked_kernel_args, params) == 40 && offsetof(masked_kernel_args, consumers) == 160 && offsetof(masked_kernel_args, poses) == 232
 		&& offsetof(masked_kernel_args, lds_quads_per_image) == 248 && offsetof(masked_kernel_args, rejected_count) == 264 && offsetof(masked_kernel_args, mapping) == 272
 		&& offsetof(masked_kernel_args, masking) == 336 && sizeof(masked_kernel_args) == 360, "masked_kernel_args mirrors the kernel's argument list");
+	// the bounds instantiations' trailing argument behind them (aclhip_decompress_poses_batch_bounds)
+	struct masked_bounds_kernel_args
+	{
+		masked_kernel_args launch;
+		consumer_bounds_launch bounds;
+	};
+	static_assert(offsetof(masked_bounds_kernel_args, bounds) == 360 && sizeof(masked_bounds_kernel_args) == 376, "masked_bounds_kernel_args mirrors the kernel's argument list");
 
 	__device__ __forceinline__ decode_params load_decode_params(const ACLHIP_CONSTANT decode_params* source)
 	{
@@ -471,12 +485,14 @@
 	// that take a weight -- the first clip's scale, the constant / fill pass, the animated writer -- are handed a slot_weight; and what the
 	// blend's passes and finish_consumer_poses need of the launch is read late, from the kernarg segment (masked_kernel_args). One quad
 	// is still touched by one lane per pass: the LDS hazards and the barriers are that kernel's.
-	template<bool kObjectSpace, uint32_t kBase, bool kMirrored>
+	template<bool kObjectSpace, uint32_t kBase, bool kMirrored, class... bounds_types>
 	__global__ __launch_bounds__(k_consumer_max_waves * k_wave_size) void decompress_poses_masked_kernel(const device_clip* __restrict__ clips, uint32_t num_clips,
 		const uint32_t* __restrict__ clip_ids, const float* __restrict__ sample_times, uint32_t num_instances, decode_params launch_params, consumer_params consumers,
 		uint8_t* __restrict__ poses, uint64_t pose_stride_bytes, uint32_t lds_quads_per_image, uint32_t lds_bytes_per_instance, uint32_t packed_block_shape,
-		unsigned long long* __restrict__ rejected_count, skeleton_launch skeleton_mapping, blend_mask_launch blend_masking)
+		unsigned long long* __restrict__ rejected_count, skeleton_launch skeleton_mapping, blend_mask_launch blend_masking, bounds_types...)
 	{
+		// (bounds_types: nothing, or consumer_bounds_launch, read where the box is stored: masked_bounds_kernel_args)
+		constexpr bool with_bounds = sizeof...(bounds_types) != 0;
 		const skeleton_launch* const mapping = &skeleton_mapping;
 		const blend_mask_launch* const masking = &blend_masking;
 		(void)poses;		// (read where the pose is stored: masked_kernel_args)
@@ -513,6 +529,7 @@
 		// the walk's normalize may take the short exact forms when every rotation it meets comes out of clips that are proven safe for
 		// them (norms near 1; a caller's base pose buffer holds anything)
 		uint32_t short_exact = kBase == k_consumer_base_buffer ? 0u : 1u;
+		[[maybe_unused]] bool empty_pose = false;		// (bounds: a served instance whose pose has no transform)
 		if (instance < num_instances)
 		{
 			const uint32_t clip_id = as_constant(clip_ids)[instance];
@@ -624,13 +641,21 @@
 					}
 				}
 			}
+			else if constexpr (with_bounds)
+				empty_pose = true;
 		}
 
 		// both images of every instance are complete
 		// (what the tail needs of the launch is read from the kernarg segment here, behind the decodes: masked_kernel_args)
 		const ACLHIP_CONSTANT masked_kernel_args* const tail_args = late_masked_kernel_args();
-		finish_consumer_poses<kObjectSpace, kBase, false, kMirrored, false>(
+		consumer_bounds_launch bounds = bounds_launch_of();
+		if constexpr (with_bounds)
+		{
+			const ACLHIP_CONSTANT consumer_bounds_launch* late_bounds = &reinterpret_cast<const ACLHIP_CONSTANT masked_bounds_kernel_args*>(tail_args)->bounds;
+			bounds = bounds_launch_of(consumer_bounds_launch{ late_bounds->bounds, late_bounds->bone_flags });
+		}
+		finish_consumer_poses<kObjectSpace, kBase, false, kMirrored, false, with_bounds>(
 			consumer_tail_args{ tail_args->poses, tail_args->pose_stride_bytes, tail_args->lds_bytes_per_instance, log2_instances_per_block, tail_args->rejected_count,
-				tail_args->consumers.base_poses, tail_args->consumers.base_pose_stride_bytes, tail_args->consumers.additive_format },
-			consumer_wave{ image, base_image, shared_schedule, slot, role, lane, wave_in_block, instance, num_tracks, short_exact }, walk);
+				tail_args->consumers.base_poses, tail_args->consumers.base_pose_stride_bytes, tail_args->consumers.additive_format, bounds.bounds, bounds.bone_flags },
+			consumer_wave{ image, base_image, shared_schedule, slot, role, lane, wave_in_block, instance, num_tracks, short_exact, empty_pose }, walk);
 	}

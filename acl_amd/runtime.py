@@ -46,6 +46,7 @@ EXPORTED_SYMBOLS = [
     "aclhip_check_skeleton", "aclhip_register_skeleton", "aclhip_unregister_skeleton", "aclhip_get_skeleton_info", "aclhip_decompress_poses_batch_mapped",
     "aclhip_check_blend_mask", "aclhip_register_blend_mask", "aclhip_unregister_blend_mask", "aclhip_get_blend_mask_info", "aclhip_decompress_poses_batch_masked",
     "aclhip_decompress_track_object_batch", "aclhip_decompress_bone_object_batch_mapped", "aclhip_plan_bone_chain",
+    "aclhip_decompress_poses_batch_bounds",
 ]
 
 
@@ -118,6 +119,11 @@ class BlendMaskInfo(ctypes.Structure):
 class BlendMasking(ctypes.Structure):
     """aclhip_blend_masking"""
     _fields_ = [("mode", ctypes.c_uint32), ("reserved0", ctypes.c_uint32), ("instance_masks", ctypes.c_void_p), ("reserved", ctypes.c_uint64 * 2)]
+
+
+class PoseBounds(ctypes.Structure):
+    """aclhip_pose_bounds"""
+    _fields_ = [("bounds", ctypes.c_void_p), ("bone_flags", ctypes.c_void_p), ("reserved", ctypes.c_uint64 * 2)]
 
 
 BLEND_WEIGHTED, BLEND_LAYERED = 0, 1   # ACLHIP_BLEND_WEIGHTED / ACLHIP_BLEND_LAYERED
@@ -306,6 +312,8 @@ def load_library():
     lib.aclhip_decompress_track_object_batch.argtypes = [vp, vp, vp, vp, u32, pparams, vp, vp]
     lib.aclhip_decompress_bone_object_batch_mapped.argtypes = [vp, vp, vp, vp, u32, pparams, ctypes.POINTER(PoseMapping), vp, vp]
     lib.aclhip_plan_bone_chain.argtypes = [vp, u32, u32, vp, u32, ctypes.POINTER(u32)]
+    lib.aclhip_decompress_poses_batch_bounds.argtypes = [vp, vp, vp, u32, pparams, ctypes.POINTER(PoseConsumers), ctypes.POINTER(PoseMapping), ctypes.POINTER(BlendMasking),
+                                                         ctypes.POINTER(PoseBounds), vp, u64, vp]
     _lib = lib
     return lib
 
@@ -729,6 +737,16 @@ class Context:
         self._check(self._lib.aclhip_decompress_poses_batch_masked(self._handle, clips_ptr, times_ptr, num_instances, ctypes.byref(params), ctypes.byref(consumers),
                                                                   ctypes.byref(mapping) if mapping is not None else None, ctypes.byref(masking) if masking is not None else None,
                                                                   poses_ptr, pose_stride_bytes, stream))
+
+    def decompress_poses_batch_bounds(self, clips_ptr, times_ptr, num_instances, bounds, poses_ptr, pose_stride_bytes, consumers, mapping=None, masking=None,
+                                      params=None, stream=None):
+        """aclhip_decompress_poses_batch_bounds: the unmapped launch (mapping None), the mapped one, or the masked one (masking set too), in
+        object space, with one box per instance into `bounds` (PoseBounds, device addresses: num_instances x 8 floats, min.xyz 0 | max.xyz 0).
+        poses_ptr None: the boxes alone, no row is written."""
+        params = params if params is not None else default_params()
+        self._check(self._lib.aclhip_decompress_poses_batch_bounds(self._handle, clips_ptr, times_ptr, num_instances, ctypes.byref(params), ctypes.byref(consumers),
+                                                                  ctypes.byref(mapping) if mapping is not None else None, ctypes.byref(masking) if masking is not None else None,
+                                                                  ctypes.byref(bounds) if bounds is not None else None, poses_ptr, pose_stride_bytes, stream))
 
     def decompress_poses_mapped(self, clips, sample_times, skeletons, maps, num_bones, additive_format=ADDITIVE_NONE, object_space=False, base_clips=None,
                                 base_sample_times=None, base_maps=None, base_poses=None, params=None, out=None, instance_rounding=None, instance_looping=None,

@@ -989,6 +989,46 @@ aclhip_status aclhip_decompress_poses_batch_masked(aclhip_context* context, cons
 	const aclhip_decompress_params* params, const aclhip_pose_consumers* consumers, const aclhip_pose_mapping* mapping, const aclhip_blend_masking* masking,
 	void* poses, uint64_t pose_stride_bytes, void* stream);
 
+/* ---- character bounds: one box per instance from the object space pose consumers -------------------
+ * What a crowd does with an object space pose before it renders: one axis aligned box per character, for frustum, occlusion and LOD
+ * culling. Without this launch a caller allocates the full row buffer (315 MB for 65 536 x 100 bones), runs the object space launch and
+ * reads all of it back in a reduction pass of its own for 32 bytes per character. The object space launch has every pose complete in LDS
+ * and one wave walks it from there to HBM: the box is a minimum / maximum over the translation quads that wave reads anyway.
+ * (ABI version 6 still: an added struct and an added function, no existing struct changed.) */
+typedef struct aclhip_pose_bounds
+{
+	void* bounds;					/* DEVICE, num_instances x 32 bytes, 16 byte aligned: min.x min.y min.z 0 | max.x max.y max.z 0 */
+	const uint8_t* bone_flags;		/* DEVICE or NULL: one byte per transform of a row (pose_stride_bytes / 48 entries), launch wide like
+									   aclhip_output_desc::skip_tracks; non-zero = the bone counts. NULL: every bone counts */
+	uint64_t reserved[2];			/* 0 */
+} aclhip_pose_bounds;
+
+/* Which launch it is: aclhip_decompress_poses_batch when `mapping` is NULL, aclhip_decompress_poses_batch_mapped when `mapping` is set,
+ * aclhip_decompress_poses_batch_masked when `masking` is set too. It takes the same `params` and `consumers`, refuses the same cases and
+ * uses the same arithmetic; consumers->object_space must be set.
+ *   The bounds of instance i: bounds[i].min / .max are the component-wise minimum / maximum, over the counted bones b, of
+ * row_i[b].translation, where row_i is the row that launch writes for instance i. Comparison is as float values: a NaN coordinate is
+ * ignored, the sign of a zero result is unspecified, the two pad lanes are 0. An instance with no counted bone -- an all-zero bone_flags,
+ * a clip of zero tracks -- gets the EMPTY box: min = +inf, max = -inf. (min and max are exact and order independent: the box is that of
+ * the row, bit for bit, whatever order the kernel takes the bones in.)
+ *   poses != NULL: the rows are written as well, bit for bit what the launch without bounds writes. poses == NULL: no row is written --
+ * the culling pass, 2 MB out for 65 536 characters. pose_stride_bytes keeps its meaning as the launch's shape in both cases:
+ * pose_stride_bytes / 48 is the largest pose accepted, sizes the LDS image and gives the length of bone_flags; an instance whose pose
+ * does not fit that shape is refused, as by the launch without bounds.
+ *   A refused instance is counted in aclhip_get_rejected_instance_count exactly when the launch without bounds refuses it; its 32 bytes and
+ * its row stay untouched. ACLHIP_CONSUMERS_FAST keeps its meaning where the underlying launch honours it (the unmapped one): the bounds are
+ * then the minimum / maximum of the FAST rows. aclhip_get_negative_scale_count moves as it does for the launch without bounds.
+ *   ACLHIP_ERROR_INVALID_ARGUMENT: bounds == NULL, bounds->bounds NULL or not 16 byte aligned, reserved fields that are not 0,
+ * consumers->object_space == 0 (a local space translation is not a position), masking without mapping, and everything the underlying
+ * launch refuses (poses may be NULL; when set it is 16 byte aligned like the stride). Decided before any device call, each with a message.
+ *   Out of scope (nothing here precludes them): per-bone radii or padding of the box; the host convenience form; the C++ mirror in
+ * aclhip.hpp; instance lists; bounds for the single-bone launches (aclhip_decompress_track_object_batch and its mapped form).
+ *   What it costs: NOT MEASURED YET (tools/pose_bounds.py, profiles/pose_bounds.md). */
+aclhip_status aclhip_decompress_poses_batch_bounds(aclhip_context* context, const aclhip_clip* clips, const float* sample_times, uint32_t num_instances,
+	const aclhip_decompress_params* params, const aclhip_pose_consumers* consumers, const aclhip_pose_mapping* mapping /* NULL: unmapped */,
+	const aclhip_blend_masking* masking /* NULL, or with mapping + blend */, const aclhip_pose_bounds* bounds, void* poses /* may be NULL */,
+	uint64_t pose_stride_bytes, void* stream);
+
 /* ---- multi-GPU ---------------------------------------------------------------------------------- */
 
 /* Decoding never needs a collective: every GPU decodes its own contiguous shard of the instance list. Only a
