@@ -266,3 +266,62 @@ extern "C" aclhip_status aclhip_decompress_poses_batch_bounds(aclhip_context* co
 	return launch_consumers(context, clips, sample_times, num_instances, device_params, *consumers, poses, pose_stride_bytes, static_cast<hipStream_t>(stream),
 		mapping != nullptr ? &launch : nullptr, masking != nullptr ? &mask_launch : nullptr, &bounds_launch);
 }
+
+namespace
+{
+	// What the additive launch checks of its layering
+	aclhip_status check_additive_layering(aclhip_context* context, const aclhip_pose_consumers* consumers, const aclhip_additive_layering* layering)
+	{
+		if (layering->instance_weights == nullptr && layering->instance_masks == nullptr)
+			return fail(context, ACLHIP_ERROR_INVALID_ARGUMENT, "an additive layering names instance_weights or instance_masks (without both it is aclhip_decompress_poses_batch_mapped)");
+		if (layering->reserved[0] != 0 || layering->reserved[1] != 0)
+			return fail(context, ACLHIP_ERROR_INVALID_ARGUMENT, "the reserved fields of an additive layering are 0");
+		if (consumers->additive_format == ACLHIP_ADDITIVE_NONE)
+			return fail(context, ACLHIP_ERROR_INVALID_ARGUMENT, "an additive layering goes with an additive format: additive_format is NONE");
+		return ACLHIP_OK;
+	}
+}
+
+// aclhip_decompress_poses_batch_mapped with a strength per (instance, slot) on the additive pose (include/aclhip.h:
+// aclhip_additive_layering). The argument checks that need no device come first and leave a message, with or without a context.
+extern "C" aclhip_status aclhip_decompress_poses_batch_additive_weighted(aclhip_context* context, const aclhip_clip* clips, const float* sample_times, uint32_t num_instances,
+	const aclhip_decompress_params* params, const aclhip_pose_consumers* consumers, const aclhip_pose_mapping* mapping, const aclhip_additive_layering* layering,
+	void* poses, uint64_t pose_stride_bytes, void* stream)
+{
+	if (layering == nullptr)
+		return fail(context, ACLHIP_ERROR_INVALID_ARGUMENT, "null additive layering");
+	if (consumers == nullptr)
+		return fail(context, ACLHIP_ERROR_INVALID_ARGUMENT, "null consumers");
+	if (mapping == nullptr)
+		return fail(context, ACLHIP_ERROR_INVALID_ARGUMENT, "null pose mapping");
+	aclhip_status status = check_additive_layering(context, consumers, layering);
+	if (status == ACLHIP_OK)
+		status = check_pose_mapping(context, consumers, mapping);
+	if (status != ACLHIP_OK)
+		return status;
+	// (check_batch_arguments' refusals, said here as well: it has no message without a context)
+	if (num_instances != 0 && (clips == nullptr || sample_times == nullptr || poses == nullptr))
+		return fail(context, ACLHIP_ERROR_INVALID_ARGUMENT, "null instance list or output buffer");
+	if ((pose_stride_bytes & 15u) != 0 || (reinterpret_cast<uintptr_t>(poses) & 15u) != 0)
+		return fail(context, ACLHIP_ERROR_INVALID_ARGUMENT, "pose buffer and stride must be 16 byte aligned");
+	if (context == nullptr)
+		return fail(context, ACLHIP_ERROR_INVALID_ARGUMENT, "null context");
+	status = check_batch_arguments(context, clips, sample_times, num_instances, poses, pose_stride_bytes);
+	if (status != ACLHIP_OK)
+		return status;
+	if (num_instances == 0)
+		return ACLHIP_OK;
+
+	decode_params device_params;
+	status = resolve_params(context, params, device_params);
+	if (status != ACLHIP_OK)
+		return status;
+
+	const skeleton_launch launch = skeleton_launch_of(consumers, mapping);
+	additive_strength_launch strength_launch = {};
+	strength_launch.instance_weights = layering->instance_weights;
+	strength_launch.instance_masks = layering->instance_masks;
+
+	device_guard guard(context->device);
+	return launch_consumers(context, clips, sample_times, num_instances, device_params, *consumers, poses, pose_stride_bytes, static_cast<hipStream_t>(stream), &launch, nullptr, nullptr, &strength_launch);
+}

@@ -303,7 +303,7 @@ extern "C" aclhip_status aclhip_set_clip_hierarchy(aclhip_context* context, aclh
 namespace
 {
 	// The three entry points of the pose consumers (kernels_consumers.inl, kernels_skeleton.inl) share their leading arguments; the
-	// skeleton space kernels take the mapping behind them, the masked ones the masking behind that
+	// skeleton space kernels take the mapping behind them, the masked ones the masking behind that, the additive ones the layering
 	template<class... trailing_types>
 	using pose_consumer_kernel = void (*)(const device_clip*, uint32_t, const uint32_t*, const float*, uint32_t, decode_params, consumer_params, uint8_t*, uint64_t, uint32_t, uint32_t, uint32_t, unsigned long long*, trailing_types...);
 
@@ -356,6 +356,7 @@ namespace
 		using unmapped_type = pose_consumer_kernel<bounds_types...>;
 		using skeleton_type = pose_consumer_kernel<skeleton_launch, bounds_types...>;
 		using masked_type = pose_consumer_kernel<skeleton_launch, blend_mask_launch, bounds_types...>;
+		using additive_type = pose_consumer_kernel<skeleton_launch, additive_strength_launch>;
 
 		template<bool kObjectSpace, uint32_t kBase, bool kUnitScale, bool kMirrored, bool kBlend = false, bool kFast = false>
 		static unmapped_type unmapped()
@@ -381,15 +382,26 @@ namespace
 			else
 				return decompress_poses_masked_kernel<kObjectSpace, kBase, kMirrored, bounds_types...>;
 		}
+		// (aclhip_decompress_poses_batch_additive_weighted: additive formats only -- no instantiation without a base, none with bounds)
+		template<bool kObjectSpace, uint32_t kBase, bool kMirrored, bool kBlend>
+		static additive_type additive()
+		{
+			if constexpr (with_bounds || kBase == k_consumer_base_none)
+				return nullptr;
+			else
+				return decompress_poses_additive_kernel<kObjectSpace, kBase, kMirrored, kBlend>;
+		}
 	};
 
 	// `mapping` (aclhip_decompress_poses_batch_mapped): skeleton space -- the launch is shaped by its rows alone (pose_stride_bytes / 48
 	// slots), the skeleton kernels take the mapping as their trailing argument. `masking` (aclhip_decompress_poses_batch_masked, with a
 	// mapping and a blend): the same launch through the masked kernels. `bounds` (aclhip_decompress_poses_batch_bounds, object space): the
 	// same launch through the bounds instantiations, a box per instance on top of the rows -- or in their place, `poses` may then be null.
+	// `layering` (aclhip_decompress_poses_batch_additive_weighted, with a mapping and an additive format, without masking and bounds): the
+	// mapped launch through the additive kernels, a strength per (instance, slot) on the additive pose.
 	aclhip_status launch_consumers(aclhip_context* context, const aclhip_clip* clips, const float* sample_times, uint32_t num_instances,
 		const decode_params& params, const aclhip_pose_consumers& consumers, void* poses, uint64_t pose_stride_bytes, hipStream_t stream, const skeleton_launch* mapping = nullptr,
-		const blend_mask_launch* masking = nullptr, const consumer_bounds_launch* bounds = nullptr)
+		const blend_mask_launch* masking = nullptr, const consumer_bounds_launch* bounds = nullptr, const additive_strength_launch* layering = nullptr)
 	{
 		if (consumers.additive_format > ACLHIP_ADDITIVE_ADDITIVE1)
 			return fail(context, ACLHIP_ERROR_INVALID_ARGUMENT, "unknown additive format %u", consumers.additive_format);
@@ -433,6 +445,16 @@ namespace
 			device_masking = *masking;
 			device_masking.masks = context->d_blend_masks;
 			device_masking.num_masks = context->d_blend_masks != nullptr ? ACLHIP_MAX_BLEND_MASKS : 0u;
+		}
+		additive_strength_launch device_layering = {};
+		if (layering != nullptr)
+		{
+			if (mapping == nullptr || !has_base || masking != nullptr || bounds != nullptr)
+				return fail(context, ACLHIP_ERROR_INVALID_ARGUMENT, "an additive layering goes with an additive format in skeleton space, without blend masks and bounds");
+			// (no mask registered yet: a table of no records -- every handle but the null handle is refused in the kernel)
+			device_layering = *layering;
+			device_layering.masks = context->d_blend_masks;
+			device_layering.num_masks = context->d_blend_masks != nullptr ? ACLHIP_MAX_BLEND_MASKS : 0u;
 		}
 		note_launch_stream(context, stream);
 
@@ -516,6 +538,13 @@ namespace
 		const auto launch_with = [&](const auto&... trailing) -> aclhip_status
 		{
 			using kernels = pose_consumer_kernels<std::decay_t<decltype(trailing)>...>;
+			if constexpr (!kernels::with_bounds)		// (a layering comes without bounds: refused above)
+				if (layering != nullptr)
+					return launch(blend
+						? pose_consumer_kernel_of<typename kernels::additive_type, true>(object_space, base_kind, mirrored, [](auto space, auto base, auto route)
+							{ return kernels::template additive<space(), base(), route(), true>(); })
+						: pose_consumer_kernel_of<typename kernels::additive_type, false>(object_space, base_kind, mirrored, [](auto space, auto base, auto route)
+							{ return kernels::template additive<space(), base(), route(), false>(); }), device_mapping, device_layering);
 			if (masking != nullptr)
 				return launch(pose_consumer_kernel_of<typename kernels::masked_type, true>(object_space, base_kind, mirrored, [](auto space, auto base, auto route)
 					{ return kernels::template masked<space(), base(), route()>(); }), device_mapping, device_masking, trailing...);

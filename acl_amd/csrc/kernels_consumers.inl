@@ -77,16 +77,27 @@
 		return f32x4{ (1.0f + additive.x) * base.x, (1.0f + additive.y) * base.y, (1.0f + additive.z) * base.z, 0.0f };
 	}
 
+	// An additive layer's strength, asked per sub-track in front of apply_additive_sub_track: (transform, kind, the additive value) -> the
+	// value that is applied. Full strength here, the value as it is; a strength per (instance, slot) under aclhip_additive_layering
+	// (additive_strength, kernels_skeleton.inl)
+	struct full_strength
+	{
+		__device__ __forceinline__ float4 operator()(uint32_t, uint32_t, float4 value) const { return value; }
+	};
+
 	// A decoded sub-track of an additive clip goes ONTO the base pose the image already holds
-	template<bool kFastMath = false>
+	// (entry.track_index is the transform the quad belongs to: the track, or the slot behind a slot_image_writer)
+	template<bool kFastMath = false, class strength_type = full_strength>
 	struct additive_image_writer
 	{
 		f32x4* image;
 		uint32_t additive_format;
+		strength_type strength = {};
 		__device__ __forceinline__ void operator()(const clip_range_entry& entry, float4 value) const
 		{
 			const uint32_t quad = entry.quad_index;
-			image[quad] = apply_additive_sub_track<kFastMath>(additive_format, quad - entry.track_index * 3u, value, image[quad]);
+			const uint32_t kind = quad - entry.track_index * 3u;
+			image[quad] = apply_additive_sub_track<kFastMath>(additive_format, kind, strength(entry.track_index, kind, value), image[quad]);
 		}
 	};
 
@@ -192,6 +203,45 @@
 			const f32x4 value = image[track * 3u];
 			const float4 rotation = quat_normalize(make_float4(value.x, value.y, value.z, value.w));
 			image[track * 3u] = f32x4{ rotation.x, rotation.y, rotation.z, rotation.w };
+		}
+	}
+
+	// An additive sub-track at strength e (aclhip_additive_layering; include/aclhip.h states the definition): the two clip blend above of
+	// the additive identity I -- rotation (0, 0, 0, 1), translation 0, scale 1, 0 for additive1 -- and the value, with weights (1 - e, e),
+	// the blend's final normalize included. I * u is multiplied out as written: 0 * u is -0 for a weight below zero. e == 1 keeps the
+	// value's bits (the normalize would move a rotation that is normalized already): a select per lane, no branch.
+	// kShortExact: sqrt_rn_short / rcp_rn_short in the normalize -- for e in [0, 1] and a rotation of a squared length in [1/4, 4] the
+	// sum's squared length u^2 + e^2 |q|^2 + 2 u e |q.w| lies in [1/5, 4].
+	template<bool kShortExact>
+	__device__ __forceinline__ float4 weigh_additive_sub_track(uint32_t additive_format, uint32_t kind, float4 value, float strength)
+	{
+		const float rest = 1.0f - strength;
+		f32x4 weighted;
+		if (kind == 0)
+		{
+			weighted = blend_accumulate(0, f32x4{ 0.0f * rest, 0.0f * rest, 0.0f * rest, 1.0f * rest }, value, strength);
+			const float4 rotation = quat_normalize<kShortExact>(make_float4(weighted.x, weighted.y, weighted.z, weighted.w));
+			weighted = f32x4{ rotation.x, rotation.y, rotation.z, rotation.w };
+		}
+		else
+		{
+			const float identity = (kind == 2 && additive_format != 3) ? 1.0f : 0.0f;
+			weighted = blend_accumulate(kind, f32x4{ identity * rest, identity * rest, identity * rest, 0.0f }, value, strength);
+		}
+		const bool full = strength == 1.0f;
+		return make_float4(full ? value.x : weighted.x, full ? value.y : weighted.y, full ? value.z : weighted.z, full ? value.w : weighted.w);
+	}
+
+	// The additive pose, complete in `image` (decoded, or blended and normalized), at its strength: one pass, lanes <-> quads
+	template<class strength_type>
+	__device__ __forceinline__ void weigh_additive_image(f32x4* image, uint32_t num_quads, const strength_type& strength, uint32_t lane)
+	{
+		for (uint32_t quad = lane; quad < num_quads; quad += k_wave_size)
+		{
+			const uint32_t transform_index = quad / 3u;
+			const f32x4 value = image[quad];
+			const float4 weighted = strength(transform_index, quad - transform_index * 3u, make_float4(value.x, value.y, value.z, value.w));
+			image[quad] = f32x4{ weighted.x, weighted.y, weighted.z, weighted.w };
 		}
 	}
 

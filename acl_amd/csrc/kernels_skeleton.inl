@@ -152,11 +152,13 @@
 		}
 	}
 
+	// strength: full_strength, or under aclhip_additive_layering an additive_strength
+	template<class strength_type = full_strength>
 	__device__ __forceinline__ void apply_additive_clip_onto_slot_image(const device_clip& clip, const device_track_map& map, const slot_fill& fill, float sample_time,
-		uint32_t rounding_policy, const decode_params& params, uint32_t additive_format, uint32_t lane, f32x4* image)
+		uint32_t rounding_policy, const decode_params& params, uint32_t additive_format, uint32_t lane, f32x4* image, const strength_type& strength = {})
 	{
-		combine_constant_slots(clip, map, fill, lane, image, [&](uint32_t, uint32_t kind, float4 value, f32x4 base) { return apply_additive_sub_track(additive_format, kind, value, base); });
-		decode_animated_into_image(clip, sample_time, rounding_policy, params, lane, into_slots(map, additive_image_writer<>{ image, additive_format }));
+		combine_constant_slots(clip, map, fill, lane, image, [&](uint32_t slot, uint32_t kind, float4 value, f32x4 base) { return apply_additive_sub_track(additive_format, kind, strength(slot, kind, value), base); });
+		decode_animated_into_image(clip, sample_time, rounding_policy, params, lane, into_slots(map, additive_image_writer<false, strength_type>{ image, additive_format, strength }));
 	}
 
 	// weight: uniform_weight, or under blend masks a slot_weight
@@ -658,4 +660,225 @@
 			consumer_tail_args{ tail_args->poses, tail_args->pose_stride_bytes, tail_args->lds_bytes_per_instance, log2_instances_per_block, tail_args->rejected_count,
 				tail_args->consumers.base_poses, tail_args->consumers.base_pose_stride_bytes, tail_args->consumers.additive_format, bounds.bounds, bounds.bone_flags },
 			consumer_wave{ image, base_image, shared_schedule, slot, role, lane, wave_in_block, instance, num_tracks, short_exact, empty_pose }, walk);
+	}
+
+	// ---- additive strength (aclhip_additive_layering, aclhip_decompress_poses_batch_additive_weighted) ---------------------------------
+	// A strength per (instance, SLOT) on the additive pose in front of apply_additive_to_base: include/aclhip.h states the definition. The
+	// masks are the blend masks (device_blend_mask, the context's table).
+	// the additive kernels' own trailing argument, behind skeleton_launch
+	struct additive_strength_launch
+	{
+		const device_blend_mask* masks;			// the context's mask table
+		uint32_t num_masks;						// its capacity
+		uint32_t reserved;
+		const float* instance_weights;			// [num_instances] or null: every instance 1
+		const uint32_t* instance_masks;			// [num_instances] or null; 0: no mask
+	};
+
+	// The strength of an instance's additive layer: layer_weight gives e = w, or w * mask[slot] through the vector cache (one load per quad);
+	// the pointer, the weight and the two settings are wave uniform.
+	struct additive_strength
+	{
+		layer_weight weight;
+		uint32_t additive_format;
+		uint32_t short_exact;		// the instance's walk_may_use_short_exact_math verdict, and w in [0, 1] (masks are: aclhip_register_blend_mask)
+		__device__ __forceinline__ float4 operator()(uint32_t slot, uint32_t kind, float4 value) const
+		{
+			const float strength = weight(slot);
+			return short_exact != 0 ? weigh_additive_sub_track<true>(additive_format, kind, value, strength) : weigh_additive_sub_track<false>(additive_format, kind, value, strength);
+		}
+	};
+
+	// The additive kernels' arguments as they lie in the kernarg segment, like masked_kernel_args: the layering is read THERE, where the
+	// strength is made -- behind the base clip's decode in the fused instantiations, behind every decode in the others.
+	struct additive_kernel_args
+	{
+		const device_clip* clips;
+		uint32_t num_clips;
+		const uint32_t* clip_ids;
+		const float* sample_times;
+		uint32_t num_instances;
+		decode_params params;
+		consumer_params consumers;
+		uint8_t* poses;
+		uint64_t pose_stride_bytes;
+		uint32_t lds_quads_per_image;
+		uint32_t lds_bytes_per_instance;
+		uint32_t packed_block_shape;
+		unsigned long long* rejected_count;
+		skeleton_launch mapping;
+		additive_strength_launch layering;
+	};
+	static_assert(offsetof(additive_kernel_args, mapping) == offsetof(masked_kernel_args, mapping) && offsetof(additive_kernel_args, layering) == 336 && sizeof(additive_kernel_args) == 368,
+		"additive_kernel_args mirrors the kernel's argument list");
+
+	// (opaque per use, like late_masked_kernel_args)
+	__device__ __forceinline__ const ACLHIP_CONSTANT additive_strength_launch* late_additive_layering()
+	{
+	#if defined(__HIP_DEVICE_COMPILE__)
+		const ACLHIP_CONSTANT additive_kernel_args* args = (const ACLHIP_CONSTANT additive_kernel_args*)__builtin_amdgcn_kernarg_segment_ptr();
+		asm volatile("" : "+s"(args));
+		return &args->layering;
+	#else
+		return nullptr;		// (the host pass only has to compile)
+	#endif
+	}
+
+	// (the mask behind a handle the kernel has checked: known, of the skeleton's slot count -- or the null handle)
+	__device__ __forceinline__ additive_strength additive_strength_of(uint32_t instance, uint32_t additive_format, uint32_t short_exact)
+	{
+		const ACLHIP_CONSTANT additive_strength_launch* layering = late_additive_layering();
+		const float weight = layering->instance_weights != nullptr ? as_constant(layering->instance_weights)[instance] : 1.0f;
+		const uint32_t handle = layering->instance_masks != nullptr ? as_constant(layering->instance_masks)[instance] : 0u;
+		const ACLHIP_CONSTANT float* mask = handle != 0 ? as_constant(as_constant(layering->masks)[handle].image) : nullptr;
+		return additive_strength{ layer_weight{ mask, weight }, additive_format, (weight >= 0.0f && weight <= 1.0f) ? short_exact : 0u };
+	}
+
+	// decompress_poses_skeleton_kernel's additive instantiations with a strength per (instance, slot) on the additive pose
+	// (aclhip_decompress_poses_batch_additive_weighted), the layering as their own trailing argument. What differs from that kernel: the
+	// instance's mask record is checked next to its maps, and the strength goes in at one of two places. Fused (additive0 / additive1 onto
+	// a base clip, one image): on every additive sub-track in front of apply_additive_sub_track -- one quad is still touched by one lane per
+	// pass, the LDS hazards and the barriers are that kernel's. Otherwise (a second wave's image, a base pose buffer, a blend) the additive
+	// pose sits complete in its own image: one pass over it, behind the blend's normalize and in front of finish_consumer_poses' barrier.
+	// Everything else -- refusals, decode, fill, blend, tail -- is that kernel's text.
+	template<bool kObjectSpace, uint32_t kBase, bool kMirrored, bool kBlend>
+	__global__ __launch_bounds__(k_consumer_max_waves * k_wave_size) void decompress_poses_additive_kernel(const device_clip* __restrict__ clips, uint32_t num_clips,
+		const uint32_t* __restrict__ clip_ids, const float* __restrict__ sample_times, uint32_t num_instances, decode_params launch_params, consumer_params consumers,
+		uint8_t* __restrict__ poses, uint64_t pose_stride_bytes, uint32_t lds_quads_per_image, uint32_t lds_bytes_per_instance, uint32_t packed_block_shape,
+		unsigned long long* __restrict__ rejected_count, skeleton_launch skeleton_mapping, additive_strength_launch)
+	{
+		// (the layering is read from the kernarg segment: additive_kernel_args)
+		const skeleton_launch* const mapping = &skeleton_mapping;
+		// packed_block_shape: log2 of the instances per workgroup (bits 0..7) | words of LDS reserved for the shared walk schedule (bits 8..31)
+		const uint32_t log2_instances_per_block = packed_block_shape & 0xFFu;
+		extern __shared__ __attribute__((aligned(16))) uint8_t dynamic_lds[];
+		__shared__ consumer_walk_slots walk;		// (what the host subtracts from the LDS it may ask for: host_consumers.inl)
+
+		static_assert(kBase != k_consumer_base_none, "an additive layer goes onto a base");
+		static_assert(!kBlend || kBase != k_consumer_base_fused, "a blend accumulates whole qvv images; a base clip is decoded by a second wave");
+		constexpr bool base_is_clip = kBase == k_consumer_base_second_wave || kBase == k_consumer_base_fused;
+		constexpr bool fused_base = kBase == k_consumer_base_fused;
+		constexpr bool two_waves = kBase == k_consumer_base_second_wave;
+		constexpr bool object_space = kObjectSpace;
+		ACLHIP_PHASE_STAMP(0);
+
+		// wave -> (instance slot of the workgroup, role): role 1 waves (base clips only) decode the slot's base
+		const uint32_t lane = threadIdx.x & (k_wave_size - 1);
+		const uint32_t wave_in_block = __builtin_amdgcn_readfirstlane(threadIdx.x / k_wave_size);
+		const uint32_t slot = wave_in_block & ((1u << log2_instances_per_block) - 1u);
+		const uint32_t role = wave_in_block >> log2_instances_per_block;
+		const uint32_t instance = (blockIdx.x << log2_instances_per_block) + slot;
+
+		uint8_t* instance_lds = dynamic_lds + size_t(slot) * lds_bytes_per_instance;
+		f32x4* image = reinterpret_cast<f32x4*>(instance_lds);
+		f32x4* base_image = image + lds_quads_per_image;
+		uint32_t* shared_schedule = reinterpret_cast<uint32_t*>(dynamic_lds + (size_t(lds_bytes_per_instance) << log2_instances_per_block));
+
+		uint32_t num_tracks = 0;		// stays 0 for a wave without work: past the batch, refused instance, empty track list
+		uint32_t short_exact = kBase == k_consumer_base_buffer ? 0u : 1u;
+		if (instance < num_instances)
+		{
+			const uint32_t clip_id = as_constant(clip_ids)[instance];
+			const device_clip clip = load_clip_fields(clips, clip_id < num_clips ? clip_id : 0);
+
+			const uint32_t skeleton_id = mapping->instance_skeletons != nullptr ? as_constant(mapping->instance_skeletons)[instance] : mapping->skeleton;
+			const uint32_t map_id = mapping->instance_maps != nullptr ? as_constant(mapping->instance_maps)[instance] : mapping->map;
+			const device_skeleton skeleton = load_skeleton_fields(mapping->skeletons, skeleton_id < mapping->num_skeletons ? skeleton_id : 0);
+			const device_track_map clip_map = load_map_fields(mapping->maps, map_id < mapping->num_maps ? map_id : 0);
+			const uint32_t pose_tracks = skeleton.num_bones;
+			const uint32_t* const hierarchy = skeleton.hierarchy;
+
+			// refused: an unknown or retired mask and a mask of another slot count (below), and everything decompress_poses_skeleton_kernel refuses
+			constexpr bool multiplies_transforms = object_space || kBase == k_consumer_base_buffer || kBase == k_consumer_base_second_wave;
+			bool refused = clip_id >= num_clips || !is_transform_clip(clip.flags) || (object_space && hierarchy == nullptr)
+				|| skeleton_id >= mapping->num_skeletons || skeleton.reference_pose == nullptr || !map_fits(clip_map, map_id, mapping->num_maps, clip.num_tracks, skeleton.num_bones)
+				|| uint64_t(pose_tracks) * 48u > pose_stride_bytes || pose_tracks * 3u > lds_quads_per_image
+				|| (kBase == k_consumer_base_buffer && uint64_t(pose_tracks) * 48u > consumers.base_pose_stride_bytes)
+				|| (!kMirrored && multiplies_transforms && (skeleton.flags & k_skeleton_negative_scale) != 0)
+				|| (!kMirrored && multiplies_transforms && !base_is_clip && (clip.flags & k_clip_negative_scale) != 0);
+			{
+				// the mask the instance names: the null handle, or a known mask of this skeleton's slot count
+				const ACLHIP_CONSTANT additive_strength_launch* layering = late_additive_layering();
+				const uint32_t mask_id = layering->instance_masks != nullptr ? as_constant(layering->instance_masks)[instance] : 0u;
+				const ACLHIP_CONSTANT device_blend_mask* mask_record = as_constant(layering->masks) + (mask_id < layering->num_masks ? mask_id : 0);
+				refused = refused || (mask_id != 0 && (mask_id >= layering->num_masks || mask_record->image == nullptr || mask_record->num_slots != skeleton.num_bones));
+			}
+
+			const uint32_t rounding_policy = __builtin_amdgcn_readfirstlane(instance_rounding_policy_of(launch_params, instance));
+			decode_params params = launch_params;
+			params.looping_policy = uint8_t(__builtin_amdgcn_readfirstlane(instance_looping_policy_of(launch_params, instance)));
+
+			short_exact &= walk_may_use_short_exact_math(clip.flags, params.normalization);
+			short_exact &= (skeleton.flags & k_skeleton_short_exact_math) != 0 ? 1u : 0u;
+			// (an additive clip and its blend partners fill with the additive identity)
+			const slot_fill clip_fill = slot_fill_of(skeleton, consumers.additive_format);
+			device_clip base_clip = clip;
+			device_track_map base_map = {};
+			if (base_is_clip)
+			{
+				const uint32_t base_clip_id = as_constant(consumers.base_clip_ids)[instance];
+				base_clip = load_clip_fields(clips, base_clip_id < num_clips ? base_clip_id : 0);
+				const uint32_t base_map_id = as_constant(mapping->base_maps)[instance];
+				base_map = load_map_fields(mapping->maps, base_map_id < mapping->num_maps ? base_map_id : 0);
+				refused = refused || base_clip_id >= num_clips || !is_transform_clip(base_clip.flags) || !map_fits(base_map, base_map_id, mapping->num_maps, base_clip.num_tracks, skeleton.num_bones)
+					|| (!kMirrored && multiplies_transforms && ((clip.flags | base_clip.flags) & k_clip_negative_scale) != 0);
+				short_exact &= walk_may_use_short_exact_math(base_clip.flags, params.normalization);
+				if (!refused && two_waves && role == 1 && pose_tracks != 0)
+					decode_pose_into_slot_image(base_clip, base_map, slot_fill{ skeleton.reference_pose, 0 }, as_constant(consumers.base_sample_times)[instance], rounding_policy, params, lane, base_image);
+			}
+
+			if (kBlend && !refused)
+				refused = blend_partners_refused<!kMirrored && multiplies_transforms>(clips, num_clips, consumers, instance, params.normalization, short_exact,
+					[&](size_t entry, const ACLHIP_CONSTANT device_clip* record) { return blend_map_fits(mapping, entry, record, skeleton.num_bones); });
+
+			if (refused)
+			{
+				if (lane == 0 && role == 0)
+					atomicAdd(rejected_count, 1ull);
+			}
+			else if (pose_tracks != 0)
+			{
+				num_tracks = pose_tracks;
+				if (role == 0)
+				{
+					if (object_space)
+						request_walk_schedule(hierarchy, log2_instances_per_block, packed_block_shape >> 8, shared_schedule, slot, lane, walk);
+					if (fused_base)
+					{
+						decode_pose_into_slot_image(base_clip, base_map, slot_fill{ skeleton.reference_pose, 0 }, as_constant(consumers.base_sample_times)[instance], rounding_policy, params, lane, image);
+						wave_lds_barrier();		// the base pose is complete (its DMA has landed)
+						apply_additive_clip_onto_slot_image(clip, clip_map, clip_fill, as_constant(sample_times)[instance], rounding_policy, params, consumers.additive_format, lane, image,
+							additive_strength_of(instance, consumers.additive_format, short_exact));
+					}
+					else
+					{
+						decode_pose_into_slot_image(clip, clip_map, clip_fill, as_constant(sample_times)[instance], rounding_policy, params, lane, image);
+						if constexpr (kBlend)
+						{
+							const uint32_t num_blend_clips = consumers.num_blend_clips;
+							const ACLHIP_CONSTANT float* weights = as_constant(consumers.blend_weights) + size_t(instance) * num_blend_clips;
+							wave_lds_barrier();		// the first pose is complete (its DMA has landed)
+							blend_scale_image(image, pose_tracks * 3u, uniform_weight{ weights[0] }, lane);
+							for (uint32_t k = 1; k < num_blend_clips; ++k)
+							{
+								const size_t entry = size_t(instance) * (num_blend_clips - 1u) + (k - 1u);
+								const device_clip blend_clip = load_clip_fields(clips, as_constant(consumers.blend_clip_ids)[entry]);
+								wave_lds_barrier();		// every quad has its sum so far
+								const device_track_map blend_map = load_map_fields(mapping->maps, as_constant(mapping->blend_maps)[entry]);
+								blend_clip_onto_slot_image(blend_clip, blend_map, clip_fill, as_constant(consumers.blend_sample_times)[entry], rounding_policy, params, uniform_weight{ weights[k] }, lane, image);
+							}
+							wave_lds_barrier();
+							blend_normalize_rotations(image, pose_tracks, lane);
+						}
+						wave_lds_barrier();		// the additive pose is complete (its DMA has landed; a blend's rotations are normalized)
+						weigh_additive_image(image, pose_tracks * 3u, additive_strength_of(instance, consumers.additive_format, short_exact), lane);
+					}
+				}
+			}
+		}
+
+		// both images of every instance are complete
+		finish_consumer_poses<kObjectSpace, kBase, false, kMirrored, false, false>(
+			consumer_tail_args{ poses, pose_stride_bytes, lds_bytes_per_instance, log2_instances_per_block, rejected_count, consumers.base_poses, consumers.base_pose_stride_bytes, consumers.additive_format },
+			consumer_wave{ image, base_image, shared_schedule, slot, role, lane, wave_in_block, instance, num_tracks, short_exact }, walk);
 	}

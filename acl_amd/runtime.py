@@ -47,6 +47,7 @@ EXPORTED_SYMBOLS = [
     "aclhip_check_blend_mask", "aclhip_register_blend_mask", "aclhip_unregister_blend_mask", "aclhip_get_blend_mask_info", "aclhip_decompress_poses_batch_masked",
     "aclhip_decompress_track_object_batch", "aclhip_decompress_bone_object_batch_mapped", "aclhip_plan_bone_chain",
     "aclhip_decompress_poses_batch_bounds",
+    "aclhip_decompress_poses_batch_additive_weighted",
 ]
 
 
@@ -119,6 +120,11 @@ class BlendMaskInfo(ctypes.Structure):
 class BlendMasking(ctypes.Structure):
     """aclhip_blend_masking"""
     _fields_ = [("mode", ctypes.c_uint32), ("reserved0", ctypes.c_uint32), ("instance_masks", ctypes.c_void_p), ("reserved", ctypes.c_uint64 * 2)]
+
+
+class AdditiveLayering(ctypes.Structure):
+    """aclhip_additive_layering"""
+    _fields_ = [("instance_weights", ctypes.c_void_p), ("instance_masks", ctypes.c_void_p), ("reserved", ctypes.c_uint64 * 2)]
 
 
 class PoseBounds(ctypes.Structure):
@@ -314,6 +320,8 @@ def load_library():
     lib.aclhip_plan_bone_chain.argtypes = [vp, u32, u32, vp, u32, ctypes.POINTER(u32)]
     lib.aclhip_decompress_poses_batch_bounds.argtypes = [vp, vp, vp, u32, pparams, ctypes.POINTER(PoseConsumers), ctypes.POINTER(PoseMapping), ctypes.POINTER(BlendMasking),
                                                          ctypes.POINTER(PoseBounds), vp, u64, vp]
+    lib.aclhip_decompress_poses_batch_additive_weighted.argtypes = [vp, vp, vp, u32, pparams, ctypes.POINTER(PoseConsumers), ctypes.POINTER(PoseMapping),
+                                                                    ctypes.POINTER(AdditiveLayering), vp, u64, vp]
     _lib = lib
     return lib
 
@@ -737,6 +745,14 @@ class Context:
         self._check(self._lib.aclhip_decompress_poses_batch_masked(self._handle, clips_ptr, times_ptr, num_instances, ctypes.byref(params), ctypes.byref(consumers),
                                                                   ctypes.byref(mapping) if mapping is not None else None, ctypes.byref(masking) if masking is not None else None,
                                                                   poses_ptr, pose_stride_bytes, stream))
+
+    def decompress_poses_batch_additive_weighted(self, clips_ptr, times_ptr, num_instances, poses_ptr, pose_stride_bytes, consumers, mapping, layering, params=None, stream=None):
+        """aclhip_decompress_poses_batch_additive_weighted: the mapped launch with a strength per (instance, slot) on the additive pose;
+        `consumers` (PoseConsumers), `mapping` (PoseMapping) and `layering` (AdditiveLayering) hold device addresses."""
+        params = params if params is not None else default_params()
+        self._check(self._lib.aclhip_decompress_poses_batch_additive_weighted(self._handle, clips_ptr, times_ptr, num_instances, ctypes.byref(params), ctypes.byref(consumers),
+                                                                             ctypes.byref(mapping) if mapping is not None else None, ctypes.byref(layering) if layering is not None else None,
+                                                                             poses_ptr, pose_stride_bytes, stream))
 
     def decompress_poses_batch_bounds(self, clips_ptr, times_ptr, num_instances, bounds, poses_ptr, pose_stride_bytes, consumers, mapping=None, masking=None,
                                       params=None, stream=None):

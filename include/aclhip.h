@@ -982,12 +982,53 @@ typedef struct aclhip_blend_masking
  * mask.num_slots != B, on any of the K entries of the instance.
  *   ACLHIP_ERROR_INVALID_ARGUMENT: masking == NULL, an unknown mode, reserved fields that are not 0, instance_masks == NULL,
  * num_blend_clips < 2, and everything aclhip_decompress_poses_batch_mapped refuses.
- *   Out of scope (nothing here precludes them): masks on the unmapped aclhip_decompress_poses_batch; masks for the additive apply (an
- * additive layer's strength per bone); the host convenience form, the C++ mirror in aclhip.hpp and instance lists.
+ *   Out of scope (nothing here precludes them): masks on the unmapped aclhip_decompress_poses_batch; the host convenience form, the
+ * C++ mirror in aclhip.hpp and instance lists. (An additive layer's strength per bone: aclhip_additive_layering, below.)
  *   What it costs: DESIGN.md 4.7 ("Blend masks") and profiles/blend_masks.md (tools/blend_masks.py). */
 aclhip_status aclhip_decompress_poses_batch_masked(aclhip_context* context, const aclhip_clip* clips, const float* sample_times, uint32_t num_instances,
 	const aclhip_decompress_params* params, const aclhip_pose_consumers* consumers, const aclhip_pose_mapping* mapping, const aclhip_blend_masking* masking,
 	void* poses, uint64_t pose_stride_bytes, void* stream);
+
+/* ---- additive strength: an additive layer per instance and per bone --------------------------------
+ * apply_additive_to_base takes the additive clip at full strength on every bone, as the reference function does. At run time a lean, a
+ * breathing cycle, a recoil or an aim offset is faded in and out per character (a scalar in [0, 1]) and confined to part of the body (a
+ * registered blend mask, above). aclhip_decompress_poses_batch_additive_weighted is aclhip_decompress_poses_batch_mapped with a strength
+ * per (instance, slot) on the additive pose: decode, fill, the blend of K additive clips, the apply, the walk and the refusals are that
+ * launch's, unchanged. (ABI version 6 still: an added struct and an added function, no existing struct changed.) */
+typedef struct aclhip_additive_layering
+{
+	const float* instance_weights;				/* DEVICE [num_instances] or NULL: every instance 1 */
+	const aclhip_blend_mask* instance_masks;	/* DEVICE [num_instances] or NULL; entries may be 0 (no mask: every slot 1) */
+	uint64_t reserved[2];						/* 0 */
+} aclhip_additive_layering;
+
+/* The definition, for instance i and slot s, all in fp32, one IEEE operation at a time, never fused:
+ *   1. w = instance_weights[i] (1 without the array).
+ *   2. e[s] = w when the instance's mask handle h = instance_masks[i] is 0 (or there is no array), else e[s] = w * mask(h)[s].
+ *   3. A[s] is the additive local transform of the slot as aclhip_decompress_poses_batch_mapped has it in front of
+ *      apply_additive_to_base: the decoded or filled additive clip, or the normalized blend of the K additive clips.
+ *   4. e[s] == 1.0f: A'[s] = A[s], bit for bit (the blend formula below renormalizes, which would change the bits of a rotation that is
+ *      normalized already). So weights that are all 1 with null masks, or with masks that are 1 everywhere, give the bits of
+ *      aclhip_decompress_poses_batch_mapped.
+ *   5. Otherwise A'[s] is the two clip blend of aclhip_pose_consumers over (I, A[s]) with weights (u, e[s]), u = 1 - e[s], where I is the
+ *      additive identity the mapped launch fills with: rotation (0, 0, 0, 1), translation 0, scale 1 (0 for ACLHIP_ADDITIVE_ADDITIVE1).
+ *          rotation: acc = I.r * u; dot = ((acc.x q.x + acc.y q.y) + acc.z q.z) + acc.w q.w; acc = (q * (dot < 0 ? -e : e)) + acc; quat_normalize(acc)
+ *          translation and scale: acc = I.t * u; acc = (t * e) + acc
+ *      Weights are used as given, nothing is clamped. For e in [0, 1) the accumulated w lane is u + e |q.w| > 0: the normalize never
+ *      sees a zero quaternion. Outside [0, 1] the arithmetic gives what it gives.
+ *   6. The row is apply_additive_to_base(additive_format, base[s], A'[s]), then object space as configured.
+ * e[s] == 0 applies the identity: the slot holds the base (through the apply's own arithmetic).
+ *   Refused and counted, the row untouched, on top of every refusal of the mapped launch: a mask handle that is unknown or retired, or
+ * mask.num_slots != B.
+ *   ACLHIP_ERROR_INVALID_ARGUMENT, decided before any device call, each with a message: layering == NULL, both arrays NULL (that is the
+ * mapped launch), reserved fields that are not 0, additive_format == ACLHIP_ADDITIVE_NONE, and everything
+ * aclhip_decompress_poses_batch_mapped refuses.
+ *   Out of scope (nothing here precludes them): the unmapped aclhip_decompress_poses_batch; combining with aclhip_blend_masking; the
+ * bounds entry point; several additive layers; the host convenience form; the C++ mirror in aclhip.hpp; instance lists.
+ *   What it costs: NOT MEASURED YET (tools/additive_strength.py, profiles/additive_strength.md; DESIGN.md 4.7 "Additive strength"). */
+aclhip_status aclhip_decompress_poses_batch_additive_weighted(aclhip_context* context, const aclhip_clip* clips, const float* sample_times,
+	uint32_t num_instances, const aclhip_decompress_params* params, const aclhip_pose_consumers* consumers, const aclhip_pose_mapping* mapping,
+	const aclhip_additive_layering* layering, void* poses, uint64_t pose_stride_bytes, void* stream);
 
 /* ---- character bounds: one box per instance from the object space pose consumers -------------------
  * What a crowd does with an object space pose before it renders: one axis aligned box per character, for frustum, occlusion and LOD
