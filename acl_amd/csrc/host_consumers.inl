@@ -347,6 +347,16 @@ namespace
 		}); });
 	}
 
+	// the same for the entry points that have blend as a template parameter of their own: instantiation_of takes it as a fourth constant
+	template<class kernel_type, class instantiation_type>
+	kernel_type pose_consumer_kernel_of(bool object_space, uint32_t base_kind, bool mirrored, bool blend, instantiation_type instantiation_of)
+	{
+		return with_constant(blend, [&](auto blended)
+		{
+			return pose_consumer_kernel_of<kernel_type, decltype(blended)::value>(object_space, base_kind, mirrored, [&](auto space, auto base, auto route) { return instantiation_of(space, base, route, blended); });
+		});
+	}
+
 	// The instantiations of the three entry points for a launch without (no bounds_types) or with bounds (consumer_bounds_launch, the
 	// kernels' last argument: aclhip_decompress_poses_batch_bounds). Bounds exist in object space only: no local space instantiation.
 	template<class... bounds_types>
@@ -436,25 +446,27 @@ namespace
 			device_mapping.maps = context->d_track_maps;
 			device_mapping.num_maps = ACLHIP_MAX_TRACK_MAPS;
 		}
+		// a masking or a layering with the context's mask table (no mask registered yet: a table of no records -- every handle but the null
+		// handle is refused in the kernel)
+		const auto with_mask_table = [&](auto launch_argument)
+		{
+			launch_argument.masks = context->d_blend_masks;
+			launch_argument.num_masks = context->d_blend_masks != nullptr ? ACLHIP_MAX_BLEND_MASKS : 0u;
+			return launch_argument;
+		};
 		blend_mask_launch device_masking = {};
 		if (masking != nullptr)
 		{
 			if (mapping == nullptr || !blend)
 				return fail(context, ACLHIP_ERROR_INVALID_ARGUMENT, "blend masks go with a blend in skeleton space");
-			// (no mask registered yet: a table of no records -- every handle but the null handle is refused in the kernel)
-			device_masking = *masking;
-			device_masking.masks = context->d_blend_masks;
-			device_masking.num_masks = context->d_blend_masks != nullptr ? ACLHIP_MAX_BLEND_MASKS : 0u;
+			device_masking = with_mask_table(*masking);
 		}
 		additive_strength_launch device_layering = {};
 		if (layering != nullptr)
 		{
 			if (mapping == nullptr || !has_base || masking != nullptr || bounds != nullptr)
 				return fail(context, ACLHIP_ERROR_INVALID_ARGUMENT, "an additive layering goes with an additive format in skeleton space, without blend masks and bounds");
-			// (no mask registered yet: a table of no records -- every handle but the null handle is refused in the kernel)
-			device_layering = *layering;
-			device_layering.masks = context->d_blend_masks;
-			device_layering.num_masks = context->d_blend_masks != nullptr ? ACLHIP_MAX_BLEND_MASKS : 0u;
+			device_layering = with_mask_table(*layering);
 		}
 		note_launch_stream(context, stream);
 
@@ -540,20 +552,14 @@ namespace
 			using kernels = pose_consumer_kernels<std::decay_t<decltype(trailing)>...>;
 			if constexpr (!kernels::with_bounds)		// (a layering comes without bounds: refused above)
 				if (layering != nullptr)
-					return launch(blend
-						? pose_consumer_kernel_of<typename kernels::additive_type, true>(object_space, base_kind, mirrored, [](auto space, auto base, auto route)
-							{ return kernels::template additive<space(), base(), route(), true>(); })
-						: pose_consumer_kernel_of<typename kernels::additive_type, false>(object_space, base_kind, mirrored, [](auto space, auto base, auto route)
-							{ return kernels::template additive<space(), base(), route(), false>(); }), device_mapping, device_layering);
+					return launch(pose_consumer_kernel_of<typename kernels::additive_type>(object_space, base_kind, mirrored, blend, [](auto space, auto base, auto route, auto blended)
+						{ return kernels::template additive<space(), base(), route(), blended()>(); }), device_mapping, device_layering);
 			if (masking != nullptr)
 				return launch(pose_consumer_kernel_of<typename kernels::masked_type, true>(object_space, base_kind, mirrored, [](auto space, auto base, auto route)
 					{ return kernels::template masked<space(), base(), route()>(); }), device_mapping, device_masking, trailing...);
 			if (mapping != nullptr)
-				return launch(blend
-					? pose_consumer_kernel_of<typename kernels::skeleton_type, true>(object_space, base_kind, mirrored, [](auto space, auto base, auto route)
-						{ return kernels::template skeleton<space(), base(), route(), true>(); })
-					: pose_consumer_kernel_of<typename kernels::skeleton_type, false>(object_space, base_kind, mirrored, [](auto space, auto base, auto route)
-						{ return kernels::template skeleton<space(), base(), route(), false>(); }), device_mapping, trailing...);
+				return launch(pose_consumer_kernel_of<typename kernels::skeleton_type>(object_space, base_kind, mirrored, blend, [](auto space, auto base, auto route, auto blended)
+					{ return kernels::template skeleton<space(), base(), route(), blended()>(); }), device_mapping, trailing...);
 			// one instantiation per (object space, kind of base, matrix route); rotation | translation images: object space without a base only
 			if (unit_scale)
 				return launch(fast ? kernels::template unmapped<true, k_consumer_base_none, true, false, false, true>() : kernels::template unmapped<true, k_consumer_base_none, true, false>(), trailing...);

@@ -526,6 +526,26 @@
 		bool empty_pose = false;	// kBounds: the instance is served and its pose has no transform (num_tracks is 0 for it too)
 	};
 
+	// The pose consumer kernels' wave -> (instance slot of the workgroup, role) and the wave's places in the workgroup's dynamic LDS. role 1
+	// waves (base clips only) decode the slot's base.
+	__device__ __forceinline__ consumer_wave consumer_wave_of(uint32_t log2_instances_per_block, uint32_t lds_bytes_per_instance, uint32_t lds_quads_per_image)
+	{
+		extern __shared__ __attribute__((aligned(16))) uint8_t dynamic_lds[];
+		const uint32_t lane = threadIdx.x & (k_wave_size - 1);
+		const uint32_t wave_in_block = __builtin_amdgcn_readfirstlane(threadIdx.x / k_wave_size);
+		const uint32_t slot = wave_in_block & ((1u << log2_instances_per_block) - 1u);
+		const uint32_t role = wave_in_block >> log2_instances_per_block;
+		const uint32_t instance = (blockIdx.x << log2_instances_per_block) + slot;
+
+		uint8_t* instance_lds = dynamic_lds + size_t(slot) * lds_bytes_per_instance;
+		f32x4* image = reinterpret_cast<f32x4*>(instance_lds);
+		f32x4* base_image = image + lds_quads_per_image;
+		// one LDS copy of the walk schedule per workgroup, behind the instances' images: the instances of a workgroup usually share
+		// a skeleton (identical hierarchies are one image, see aclhip_set_clip_hierarchy), and every word kept per instance costs residency
+		uint32_t* shared_schedule = reinterpret_cast<uint32_t*>(dynamic_lds + (size_t(lds_bytes_per_instance) << log2_instances_per_block));
+		return consumer_wave{ image, base_image, shared_schedule, slot, role, lane, wave_in_block, instance, 0, 0 };
+	}
+
 	// The pose consumer kernels behind their decodes, from "both images of every instance are complete" on: the combine with the base
 	// pose, the object space walk, the store. The three kernels differ in how an image is filled; this is shared. kUnitScale and kFast:
 	// decompress_poses_consumer_kernel only.
@@ -724,7 +744,6 @@
 	{
 		// packed_block_shape: log2 of the instances per workgroup (bits 0..7) | words of LDS reserved for the shared walk schedule (bits 8..31)
 		const uint32_t log2_instances_per_block = packed_block_shape & 0xFFu;
-		extern __shared__ __attribute__((aligned(16))) uint8_t dynamic_lds[];
 		__shared__ consumer_walk_slots walk;		// (what the host subtracts from the LDS it may ask for: host_consumers.inl)
 
 		constexpr bool with_bounds = sizeof...(bounds_types) != 0;
@@ -740,19 +759,11 @@
 		constexpr bool unit_scale = kUnitScale;
 		ACLHIP_PHASE_STAMP(0);
 
-		// wave -> (instance slot of the workgroup, role): role 1 waves (base clips only) decode the slot's base
-		const uint32_t lane = threadIdx.x & (k_wave_size - 1);
-		const uint32_t wave_in_block = __builtin_amdgcn_readfirstlane(threadIdx.x / k_wave_size);
-		const uint32_t slot = wave_in_block & ((1u << log2_instances_per_block) - 1u);
-		const uint32_t role = wave_in_block >> log2_instances_per_block;
-		const uint32_t instance = (blockIdx.x << log2_instances_per_block) + slot;
-
-		uint8_t* instance_lds = dynamic_lds + size_t(slot) * lds_bytes_per_instance;
-		f32x4* image = reinterpret_cast<f32x4*>(instance_lds);
-		f32x4* base_image = image + lds_quads_per_image;
-		// one LDS copy of the walk schedule per workgroup, behind the instances' images: the instances of a workgroup usually share
-		// a skeleton (identical hierarchies are one image, see aclhip_set_clip_hierarchy), and every word kept per instance costs residency
-		uint32_t* shared_schedule = reinterpret_cast<uint32_t*>(dynamic_lds + (size_t(lds_bytes_per_instance) << log2_instances_per_block));
+		consumer_wave wave = consumer_wave_of(log2_instances_per_block, lds_bytes_per_instance, lds_quads_per_image);
+		const uint32_t lane = wave.lane, slot = wave.slot, role = wave.role, instance = wave.instance;
+		f32x4* const image = wave.image;
+		f32x4* const base_image = wave.base_image;
+		uint32_t* const shared_schedule = wave.shared_schedule;
 
 		uint32_t num_tracks = 0;		// stays 0 for a wave without work: past the batch, refused instance, empty track list
 		// the walk's normalize may take the short exact forms when every rotation it meets comes out of clips that are proven safe for
@@ -847,9 +858,12 @@
 		}
 
 		// both images of every instance are complete
+		wave.num_tracks = num_tracks;
+		wave.short_exact = short_exact;
+		wave.empty_pose = empty_pose;
 		const consumer_bounds_launch bounds = bounds_launch_of(bounds_launch...);
 		finish_consumer_poses<kObjectSpace, kBase, kUnitScale, kMirrored, kFast, with_bounds>(
 			consumer_tail_args{ poses, pose_stride_bytes, lds_bytes_per_instance, log2_instances_per_block, rejected_count, consumers.base_poses, consumers.base_pose_stride_bytes, consumers.additive_format,
 				bounds.bounds, bounds.bone_flags },
-			consumer_wave{ image, base_image, shared_schedule, slot, role, lane, wave_in_block, instance, num_tracks, short_exact, empty_pose }, walk);
+			wave, walk);
 	}

@@ -179,166 +179,6 @@
 		return blend_map_id < mapping->num_maps && map_record->image != nullptr && map_record->num_tracks == record->num_tracks && map_record->num_slots == num_bones;
 	}
 
-	// decompress_poses_consumer_kernel (kernels_consumers.inl: the workgroup's shape, the LDS layout, the walk and the store are described
-	// there) in skeleton space, with the mapping as its own trailing argument: decode_params, consumer_params and every kernarg offset
-	// are where that kernel has them. An entry point of its own for what differs -- the refusal test takes the skeleton and the maps in, the
-	// images are filled in slot order --; behind the decodes it is that kernel's finish_consumer_poses, without rotation | translation
-	// images and without ACLHIP_CONSUMERS_FAST. (Until the three kernels were held to resources and time instead of identical disassembly
-	// the whole text was repeated here: profiles/skeleton_poses.md, profiles/consumer_kernel_sharing.md.)
-	template<bool kObjectSpace, uint32_t kBase, bool kMirrored, bool kBlend, class... bounds_types>
-	__global__ __launch_bounds__(k_consumer_max_waves * k_wave_size) void decompress_poses_skeleton_kernel(const device_clip* __restrict__ clips, uint32_t num_clips,
-		const uint32_t* __restrict__ clip_ids, const float* __restrict__ sample_times, uint32_t num_instances, decode_params launch_params, consumer_params consumers,
-		uint8_t* __restrict__ poses, uint64_t pose_stride_bytes, uint32_t lds_quads_per_image, uint32_t lds_bytes_per_instance, uint32_t packed_block_shape,
-		unsigned long long* __restrict__ rejected_count, skeleton_launch skeleton_mapping, bounds_types... bounds_launch)
-	{
-		// (bounds_types: nothing, or consumer_bounds_launch -- aclhip_decompress_poses_batch_bounds, kernels_consumers.inl)
-		constexpr bool with_bounds = sizeof...(bounds_types) != 0;
-		const skeleton_launch* const mapping = &skeleton_mapping;
-		// packed_block_shape: log2 of the instances per workgroup (bits 0..7) | words of LDS reserved for the shared walk schedule (bits 8..31)
-		const uint32_t log2_instances_per_block = packed_block_shape & 0xFFu;
-		extern __shared__ __attribute__((aligned(16))) uint8_t dynamic_lds[];
-		__shared__ consumer_walk_slots walk;		// (what the host subtracts from the LDS it may ask for: host_consumers.inl)
-
-		static_assert(!kBlend || kBase != k_consumer_base_fused, "a blend accumulates whole qvv images; a base clip is decoded by a second wave");
-		constexpr bool base_is_clip = kBase == k_consumer_base_second_wave || kBase == k_consumer_base_fused;
-		// a base clip under additive0 / additive1: ONE wave decodes the base into the instance's image and the additive clip onto it
-		// (half the LDS per instance, half the waves: twice the poses a CU holds); otherwise a second wave decodes the base into its own image
-		constexpr bool fused_base = kBase == k_consumer_base_fused;
-		constexpr bool two_waves = kBase == k_consumer_base_second_wave;
-		constexpr bool object_space = kObjectSpace;
-		ACLHIP_PHASE_STAMP(0);
-
-		// wave -> (instance slot of the workgroup, role): role 1 waves (base clips only) decode the slot's base
-		const uint32_t lane = threadIdx.x & (k_wave_size - 1);
-		const uint32_t wave_in_block = __builtin_amdgcn_readfirstlane(threadIdx.x / k_wave_size);
-		const uint32_t slot = wave_in_block & ((1u << log2_instances_per_block) - 1u);
-		const uint32_t role = wave_in_block >> log2_instances_per_block;
-		const uint32_t instance = (blockIdx.x << log2_instances_per_block) + slot;
-
-		uint8_t* instance_lds = dynamic_lds + size_t(slot) * lds_bytes_per_instance;
-		f32x4* image = reinterpret_cast<f32x4*>(instance_lds);
-		f32x4* base_image = image + lds_quads_per_image;
-		// one LDS copy of the walk schedule per workgroup, behind the instances' images: the instances of a workgroup usually share
-		// a skeleton (identical hierarchies are one image, see aclhip_set_clip_hierarchy), and every word kept per instance costs residency
-		uint32_t* shared_schedule = reinterpret_cast<uint32_t*>(dynamic_lds + (size_t(lds_bytes_per_instance) << log2_instances_per_block));
-
-		uint32_t num_tracks = 0;		// stays 0 for a wave without work: past the batch, refused instance, empty track list
-		// the walk's normalize may take the short exact forms when every rotation it meets comes out of clips that are proven safe for
-		// them (norms near 1; a caller's base pose buffer holds anything)
-		uint32_t short_exact = kBase == k_consumer_base_buffer ? 0u : 1u;
-		[[maybe_unused]] bool empty_pose = false;		// (bounds: a served instance whose pose has no transform)
-		if (instance < num_instances)
-		{
-			const uint32_t clip_id = as_constant(clip_ids)[instance];
-			// (every field in registers of its own: load_clip_fields, kernels_pose.inl)
-			const device_clip clip = load_clip_fields(clips, clip_id < num_clips ? clip_id : 0);
-
-			// skeleton space: the instance's skeleton and its clip's map, read on the scalar unit next to the clip record. A cleared record
-			// (an unknown or retired handle) holds no image; record 0 of both tables is never handed out.
-			const uint32_t skeleton_id = mapping->instance_skeletons != nullptr ? as_constant(mapping->instance_skeletons)[instance] : mapping->skeleton;
-			const uint32_t map_id = mapping->instance_maps != nullptr ? as_constant(mapping->instance_maps)[instance] : mapping->map;
-			const device_skeleton skeleton = load_entry(mapping->skeletons, skeleton_id < mapping->num_skeletons ? skeleton_id : 0);
-			const device_track_map clip_map = load_entry(mapping->maps, map_id < mapping->num_maps ? map_id : 0);
-			// the transforms of the instance's pose and the hierarchy they are walked with are the skeleton's (clip.hierarchy is not read)
-			const uint32_t pose_tracks = skeleton.num_bones;
-			const uint32_t* const hierarchy = skeleton.hierarchy;
-
-			// refused: unknown / scalar clips, unknown or retired skeletons and maps, a map made for another clip or another skeleton, object
-			// space without a hierarchy, more bones than the row or the launch's LDS image holds. Both waves of an instance come to the same
-			// verdict; the first one reports it. A launch is shaped for its batch when it is enqueued (launch_consumers: LDS image sizes from
-			// the pose stride, kernel instantiation from what the registry holds) and meets its clips and skeletons when it runs: a clip or a
-			// reference pose that may hand a negative scale to a launch compiled without rtm::qvv_mul's matrix route -- registered behind a
-			// captured launch's back -- is refused here, not computed wrongly. Only launches that MULTIPLY transforms care: local space
-			// without a base, and additive0 / additive1 onto a fused base clip, combine scale with scale and serve mirrored skeletons as they are.
-			constexpr bool multiplies_transforms = object_space || kBase == k_consumer_base_buffer || kBase == k_consumer_base_second_wave;
-			bool refused = clip_id >= num_clips || !is_transform_clip(clip.flags) || (object_space && hierarchy == nullptr)
-				|| skeleton_id >= mapping->num_skeletons || skeleton.reference_pose == nullptr || !map_fits(clip_map, map_id, mapping->num_maps, clip.num_tracks, skeleton.num_bones)
-				|| uint64_t(pose_tracks) * 48u > pose_stride_bytes || pose_tracks * 3u > lds_quads_per_image
-				|| (kBase == k_consumer_base_buffer && uint64_t(pose_tracks) * 48u > consumers.base_pose_stride_bytes)
-				|| (!kMirrored && multiplies_transforms && (skeleton.flags & k_skeleton_negative_scale) != 0)
-				|| (!kMirrored && multiplies_transforms && !base_is_clip && (clip.flags & k_clip_negative_scale) != 0);
-
-			const uint32_t rounding_policy = __builtin_amdgcn_readfirstlane(instance_rounding_policy_of(launch_params, instance));
-			// the instance's own looping policy (decompress.h:149) goes for every clip decoded on its behalf -- its base, its blend partners
-			decode_params params = launch_params;
-			params.looping_policy = uint8_t(__builtin_amdgcn_readfirstlane(instance_looping_policy_of(launch_params, instance)));
-
-			short_exact &= walk_may_use_short_exact_math(clip.flags, params.normalization);
-			short_exact &= (skeleton.flags & k_skeleton_short_exact_math) != 0 ? 1u : 0u;		// (the reference pose fills slots: its rotations are walked too)
-			// what a slot no track maps to holds: the reference pose -- or, for an additive clip and its blend partners, the additive identity
-			const slot_fill clip_fill = slot_fill_of(skeleton, consumers.additive_format);
-			device_clip base_clip = clip;
-			device_track_map base_map = {};
-			if (base_is_clip)
-			{
-				const uint32_t base_clip_id = as_constant(consumers.base_clip_ids)[instance];
-				base_clip = load_clip_fields(clips, base_clip_id < num_clips ? base_clip_id : 0);
-				// (each clip only has to match its own map, each map the skeleton)
-				const uint32_t base_map_id = as_constant(mapping->base_maps)[instance];
-				base_map = load_entry(mapping->maps, base_map_id < mapping->num_maps ? base_map_id : 0);
-				refused = refused || base_clip_id >= num_clips || !is_transform_clip(base_clip.flags) || !map_fits(base_map, base_map_id, mapping->num_maps, base_clip.num_tracks, skeleton.num_bones)
-					|| (!kMirrored && multiplies_transforms && ((clip.flags | base_clip.flags) & k_clip_negative_scale) != 0);
-				short_exact &= walk_may_use_short_exact_math(base_clip.flags, params.normalization);
-				if (!refused && two_waves && role == 1 && pose_tracks != 0)
-					decode_pose_into_slot_image(base_clip, base_map, slot_fill{ skeleton.reference_pose, 0 }, as_constant(consumers.base_sample_times)[instance], rounding_policy, params, lane, base_image);
-			}
-
-			// every clip of the blend: known, a transform clip, with a known map of its own into this skeleton
-			if (kBlend && !refused)
-				refused = blend_partners_refused<!kMirrored && multiplies_transforms>(clips, num_clips, consumers, instance, params.normalization, short_exact,
-					[&](size_t entry, const ACLHIP_CONSTANT device_clip* record) { return blend_map_fits(mapping, entry, record, skeleton.num_bones); });
-
-			if (refused)
-			{
-				if (lane == 0 && role == 0)
-					atomicAdd(rejected_count, 1ull);
-			}
-			else if (pose_tracks != 0)
-			{
-				num_tracks = pose_tracks;
-				if (role == 0)
-				{
-					if (object_space)
-						request_walk_schedule(hierarchy, log2_instances_per_block, packed_block_shape >> 8, shared_schedule, slot, lane, walk);
-					if (fused_base)
-					{
-						decode_pose_into_slot_image(base_clip, base_map, slot_fill{ skeleton.reference_pose, 0 }, as_constant(consumers.base_sample_times)[instance], rounding_policy, params, lane, image);
-						wave_lds_barrier();		// the base pose is complete (its DMA has landed)
-						apply_additive_clip_onto_slot_image(clip, clip_map, clip_fill, as_constant(sample_times)[instance], rounding_policy, params, consumers.additive_format, lane, image);
-					}
-					else
-						decode_pose_into_slot_image(clip, clip_map, clip_fill, as_constant(sample_times)[instance], rounding_policy, params, lane, image);
-					if constexpr (kBlend)
-					{
-						const uint32_t num_blend_clips = consumers.num_blend_clips;
-						const ACLHIP_CONSTANT float* weights = as_constant(consumers.blend_weights) + size_t(instance) * num_blend_clips;
-						wave_lds_barrier();		// the first pose is complete (its DMA has landed)
-						blend_scale_image(image, pose_tracks * 3u, uniform_weight{ weights[0] }, lane);
-						for (uint32_t k = 1; k < num_blend_clips; ++k)
-						{
-							const size_t entry = size_t(instance) * (num_blend_clips - 1u) + (k - 1u);
-							const device_clip blend_clip = load_clip_fields(clips, as_constant(consumers.blend_clip_ids)[entry]);
-							wave_lds_barrier();		// every quad has its sum so far
-							const device_track_map blend_map = load_entry(mapping->maps, as_constant(mapping->blend_maps)[entry]);
-							blend_clip_onto_slot_image(blend_clip, blend_map, clip_fill, as_constant(consumers.blend_sample_times)[entry], rounding_policy, params, uniform_weight{ weights[k] }, lane, image);
-						}
-						wave_lds_barrier();
-						blend_normalize_rotations(image, pose_tracks, lane);
-					}
-				}
-			}
-			else if constexpr (with_bounds)
-				empty_pose = true;
-		}
-
-		// both images of every instance are complete
-		const consumer_bounds_launch bounds = bounds_launch_of(bounds_launch...);
-		finish_consumer_poses<kObjectSpace, kBase, false, kMirrored, false, with_bounds>(
-			consumer_tail_args{ poses, pose_stride_bytes, lds_bytes_per_instance, log2_instances_per_block, rejected_count, consumers.base_poses, consumers.base_pose_stride_bytes, consumers.additive_format,
-				bounds.bounds, bounds.bone_flags },
-			consumer_wave{ image, base_image, shared_schedule, slot, role, lane, wave_in_block, instance, num_tracks, short_exact, empty_pose }, walk);
-	}
-
 	// ---- blend masks (aclhip_register_blend_mask, aclhip_decompress_poses_batch_masked) ------------------------------------------------
 	// A weight per (instance, clip, SLOT) in the place of the blend's weight per (instance, clip): include/aclhip.h states the definition.
 	// A mask's record in the context's mask table (which never moves, like the map table) and its device image: num_slots floats in slot
@@ -482,11 +322,364 @@
 	#endif
 	}
 
-	// decompress_poses_skeleton_kernel's blend instantiations with a weight per slot (aclhip_decompress_poses_batch_masked), the masking as
-	// their own trailing argument. What differs from that kernel: the K mask records are checked next to the K maps; the three places
+	// ---- additive strength (aclhip_additive_layering, aclhip_decompress_poses_batch_additive_weighted) ---------------------------------
+	// A strength per (instance, SLOT) on the additive pose in front of apply_additive_to_base: include/aclhip.h states the definition. The
+	// masks are the blend masks (device_blend_mask, the context's table).
+	// the additive kernels' own trailing argument, behind skeleton_launch
+	struct additive_strength_launch
+	{
+		const device_blend_mask* masks;			// the context's mask table
+		uint32_t num_masks;						// its capacity
+		uint32_t reserved;
+		const float* instance_weights;			// [num_instances] or null: every instance 1
+		const uint32_t* instance_masks;			// [num_instances] or null; 0: no mask
+	};
+
+	// The strength of an instance's additive layer: layer_weight gives e = w, or w * mask[slot] through the vector cache (one load per quad);
+	// the pointer, the weight and the two settings are wave uniform.
+	struct additive_strength
+	{
+		layer_weight weight;
+		uint32_t additive_format;
+		uint32_t short_exact;		// the instance's walk_may_use_short_exact_math verdict, and w in [0, 1] (masks are: aclhip_register_blend_mask)
+		__device__ __forceinline__ float4 operator()(uint32_t slot, uint32_t kind, float4 value) const
+		{
+			const float strength = weight(slot);
+			return short_exact != 0 ? weigh_additive_sub_track<true>(additive_format, kind, value, strength) : weigh_additive_sub_track<false>(additive_format, kind, value, strength);
+		}
+	};
+
+	// The additive kernels' arguments as they lie in the kernarg segment, like masked_kernel_args: the layering is read THERE, where the
+	// strength is made -- behind the base clip's decode in the fused instantiations, behind every decode in the others.
+	struct additive_kernel_args
+	{
+		const device_clip* clips;
+		uint32_t num_clips;
+		const uint32_t* clip_ids;
+		const float* sample_times;
+		uint32_t num_instances;
+		decode_params params;
+		consumer_params consumers;
+		uint8_t* poses;
+		uint64_t pose_stride_bytes;
+		uint32_t lds_quads_per_image;
+		uint32_t lds_bytes_per_instance;
+		uint32_t packed_block_shape;
+		unsigned long long* rejected_count;
+		skeleton_launch mapping;
+		additive_strength_launch layering;
+	};
+	static_assert(offsetof(additive_kernel_args, mapping) == offsetof(masked_kernel_args, mapping) && offsetof(additive_kernel_args, layering) == 336 && sizeof(additive_kernel_args) == 368,
+		"additive_kernel_args mirrors the kernel's argument list");
+
+	// (opaque per use, like late_masked_kernel_args)
+	__device__ __forceinline__ const ACLHIP_CONSTANT additive_strength_launch* late_additive_layering()
+	{
+	#if defined(__HIP_DEVICE_COMPILE__)
+		const ACLHIP_CONSTANT additive_kernel_args* args = (const ACLHIP_CONSTANT additive_kernel_args*)__builtin_amdgcn_kernarg_segment_ptr();
+		asm volatile("" : "+s"(args));
+		return &args->layering;
+	#else
+		return nullptr;		// (the host pass only has to compile)
+	#endif
+	}
+
+	// (the mask behind a handle the kernel has checked: known, of the skeleton's slot count -- or the null handle)
+	__device__ __forceinline__ additive_strength additive_strength_of(uint32_t instance, uint32_t additive_format, uint32_t short_exact)
+	{
+		const ACLHIP_CONSTANT additive_strength_launch* layering = late_additive_layering();
+		const float weight = layering->instance_weights != nullptr ? as_constant(layering->instance_weights)[instance] : 1.0f;
+		const uint32_t handle = layering->instance_masks != nullptr ? as_constant(layering->instance_masks)[instance] : 0u;
+		const ACLHIP_CONSTANT float* mask = handle != 0 ? as_constant(as_constant(layering->masks)[handle].image) : nullptr;
+		return additive_strength{ layer_weight{ mask, weight }, additive_format, (weight >= 0.0f && weight <= 1.0f) ? short_exact : 0u };
+	}
+
+	// ---- one body for the mapped and the additive entry points ---------------------------------------------------------------------------
+	// decompress_poses_skeleton_kernel and decompress_poses_additive_kernel are decompress_poses_consumer_kernel (kernels_consumers.inl: the
+	// workgroup's shape, the LDS layout, the walk and the store are described there) in skeleton space, with the mapping as a trailing
+	// argument: decode_params, consumer_params and every kernarg offset are where that kernel has them. They run ONE text,
+	// skeleton_space_poses -- the refusal test takes the skeleton and the maps in, the images are filled in slot order, and behind the decodes
+	// it is that kernel's finish_consumer_poses, without rotation | translation images and without ACLHIP_CONSUMERS_FAST -- and hand it a
+	// policy for the little that differs between them:
+	//   refuses()      the entry point's own refusal next to the inherited ones: nothing, or the mask handle of an additive layering
+	//   strength()     what an additive clip is weighed with: full_strength (nothing), or the instance's additive_strength -- and whether
+	//                  an additive image that is not fused with its base is weighed behind the blend (k_weighs_additive_image)
+	//   bounds         the bounds instantiations' trailing argument (the mapped kernel's policy only: the additive kernel has no bounds form)
+	// decompress_poses_masked_kernel (below) calls consumer_wave_of, mapped_instance_of, mapped_instance_refused, resolve_base_clip and the
+	// functions the body calls, not the body: on the body, or with the second wave's decode or the refuse / serve ladder inside shared
+	// functions, instantiations of it lost a wave per SIMD or got scratch (profiles/skeleton_kernel_sharing.md has the figures).
+
+	// An instance of a mapped launch: its clip (every field in registers of its own: load_clip_fields, kernels_pose.inl), its skeleton and its
+	// clip's map, read on the scalar unit next to the clip record. A cleared record (an unknown or retired handle) holds no image; record 0
+	// of both tables is never handed out.
+	struct mapped_instance
+	{
+		uint32_t clip_id, skeleton_id, map_id;
+		device_clip clip;
+		device_skeleton skeleton;
+		device_track_map clip_map;
+	};
+	__device__ __forceinline__ mapped_instance mapped_instance_of(const device_clip* clips, uint32_t num_clips, const uint32_t* clip_ids, const skeleton_launch* mapping, uint32_t instance)
+	{
+		mapped_instance the;
+		the.clip_id = as_constant(clip_ids)[instance];
+		the.clip = load_clip_fields(clips, the.clip_id < num_clips ? the.clip_id : 0);
+		the.skeleton_id = mapping->instance_skeletons != nullptr ? as_constant(mapping->instance_skeletons)[instance] : mapping->skeleton;
+		the.map_id = mapping->instance_maps != nullptr ? as_constant(mapping->instance_maps)[instance] : mapping->map;
+		the.skeleton = load_skeleton_fields(mapping->skeletons, the.skeleton_id < mapping->num_skeletons ? the.skeleton_id : 0);
+		the.clip_map = load_map_fields(mapping->maps, the.map_id < mapping->num_maps ? the.map_id : 0);
+		return the;
+	}
+
+	// refused: unknown / scalar clips, unknown or retired skeletons and maps, a map made for another clip or another skeleton, object
+	// space without a hierarchy, more bones than the row or the launch's LDS image holds, and what the entry point's policy refuses
+	// (unknown or retired masks, masks of another slot count). Both waves of an instance come to the same verdict; the first one
+	// reports it. A launch is shaped for its batch when it is enqueued (launch_consumers: LDS image sizes from the pose stride, kernel
+	// instantiation from what the registry holds) and meets its clips and skeletons when it runs: a clip or a reference pose that may
+	// hand a negative scale to a launch compiled without rtm::qvv_mul's matrix route -- registered behind a captured launch's back --
+	// is refused here, not computed wrongly. Only launches that MULTIPLY transforms care: local space without a base, and additive0 /
+	// additive1 onto a fused base clip, combine scale with scale and serve mirrored skeletons as they are.
+	template<bool kObjectSpace, uint32_t kBase, bool kMirrored>
+	__device__ __forceinline__ bool mapped_instance_refused(uint32_t clip_id, uint32_t num_clips, const device_clip& clip, uint32_t skeleton_id, const device_skeleton& skeleton, uint32_t map_id,
+		const device_track_map& clip_map, const skeleton_launch* mapping, uint64_t pose_stride_bytes, uint32_t lds_quads_per_image, uint64_t base_pose_stride_bytes)
+	{
+		constexpr bool base_is_clip = kBase == k_consumer_base_second_wave || kBase == k_consumer_base_fused;
+		constexpr bool multiplies_transforms = kObjectSpace || kBase == k_consumer_base_buffer || kBase == k_consumer_base_second_wave;
+		const uint32_t pose_tracks = skeleton.num_bones;
+		return clip_id >= num_clips || !is_transform_clip(clip.flags) || (kObjectSpace && skeleton.hierarchy == nullptr)
+			|| skeleton_id >= mapping->num_skeletons || skeleton.reference_pose == nullptr || !map_fits(clip_map, map_id, mapping->num_maps, clip.num_tracks, skeleton.num_bones)
+			|| uint64_t(pose_tracks) * 48u > pose_stride_bytes || pose_tracks * 3u > lds_quads_per_image
+			|| (kBase == k_consumer_base_buffer && uint64_t(pose_tracks) * 48u > base_pose_stride_bytes)
+			|| (!kMirrored && multiplies_transforms && (skeleton.flags & k_skeleton_negative_scale) != 0)
+			|| (!kMirrored && multiplies_transforms && !base_is_clip && (clip.flags & k_clip_negative_scale) != 0);
+	}
+
+	// The base clip of an instance (consumer_params::base_clip_ids) and its own map (skeleton_launch::base_maps): each clip only has to match
+	// its own map, each map the skeleton. (The second wave's decode of the base stays with the callers: inside this function it cost
+	// instantiations a wave per SIMD or gave them scratch, profiles/skeleton_kernel_sharing.md.)
+	struct base_records
+	{
+		device_clip clip;
+		device_track_map map;
+	};
+	template<bool kObjectSpace, uint32_t kBase, bool kMirrored>
+	__device__ __forceinline__ base_records resolve_base_clip(const device_clip* clips, uint32_t num_clips, const consumer_params& consumers, const skeleton_launch* mapping, uint32_t instance,
+		const device_clip& clip, const device_skeleton& skeleton, const decode_params& params, bool& refused, uint32_t& short_exact)
+	{
+		constexpr bool multiplies_transforms = kObjectSpace || kBase == k_consumer_base_buffer || kBase == k_consumer_base_second_wave;
+		const uint32_t base_clip_id = as_constant(consumers.base_clip_ids)[instance];
+		const device_clip base_clip = load_clip_fields(clips, base_clip_id < num_clips ? base_clip_id : 0);
+		const uint32_t base_map_id = as_constant(mapping->base_maps)[instance];
+		const device_track_map base_map = load_map_fields(mapping->maps, base_map_id < mapping->num_maps ? base_map_id : 0);
+		refused = refused || base_clip_id >= num_clips || !is_transform_clip(base_clip.flags) || !map_fits(base_map, base_map_id, mapping->num_maps, base_clip.num_tracks, skeleton.num_bones)
+			|| (!kMirrored && multiplies_transforms && ((clip.flags | base_clip.flags) & k_clip_negative_scale) != 0);
+		short_exact &= walk_may_use_short_exact_math(base_clip.flags, params.normalization);
+		return base_records{ base_clip, base_map };
+	}
+
+	// the leading arguments the mapped kernels share and the mapping, as the kernel holds them
+	struct mapped_kernel_launch
+	{
+		const device_clip* clips;
+		uint32_t num_clips;
+		const uint32_t* clip_ids;
+		const float* sample_times;
+		uint32_t num_instances;
+		const decode_params& params;
+		const consumer_params& consumers;
+		uint8_t* poses;
+		uint64_t pose_stride_bytes;
+		uint32_t lds_quads_per_image, lds_bytes_per_instance, packed_block_shape;
+		unsigned long long* rejected_count;
+		const skeleton_launch& mapping;
+	};
+
+	// decompress_poses_skeleton_kernel's policy: nothing of its own. bounds: the bounds instantiations' trailing argument, or null
+	struct mapped_poses_policy
+	{
+		static constexpr bool k_weighs_additive_image = false;
+		const consumer_bounds_launch* bounds = nullptr;
+		__device__ __forceinline__ bool refuses(uint32_t, uint32_t) const { return false; }
+		__device__ __forceinline__ full_strength strength(uint32_t, uint32_t, uint32_t) const { return {}; }
+	};
+
+	// decompress_poses_additive_kernel's: the instance's mask record is checked next to its maps, and the strength goes in at one of two
+	// places. Fused (additive0 / additive1 onto a base clip, one image): on every additive sub-track in front of apply_additive_sub_track --
+	// one quad is still touched by one lane per pass. Otherwise (a second wave's image, a base pose buffer, a blend) the additive pose sits
+	// complete in its own image: one pass over it, behind the blend's normalize and in front of finish_consumer_poses' barrier. The layering
+	// is read from the kernarg segment (additive_kernel_args).
+	struct additive_poses_policy
+	{
+		static constexpr bool k_weighs_additive_image = true;
+		__device__ __forceinline__ bool refuses(uint32_t instance, uint32_t num_bones) const
+		{
+			const ACLHIP_CONSTANT additive_strength_launch* layering = late_additive_layering();
+			const uint32_t mask_id = layering->instance_masks != nullptr ? as_constant(layering->instance_masks)[instance] : 0u;
+			const ACLHIP_CONSTANT device_blend_mask* mask_record = as_constant(layering->masks) + (mask_id < layering->num_masks ? mask_id : 0);
+			return mask_id != 0 && (mask_id >= layering->num_masks || mask_record->image == nullptr || mask_record->num_slots != num_bones);
+		}
+		__device__ __forceinline__ additive_strength strength(uint32_t instance, uint32_t additive_format, uint32_t short_exact) const
+		{
+			return additive_strength_of(instance, additive_format, short_exact);
+		}
+	};
+
+	template<bool kObjectSpace, uint32_t kBase, bool kMirrored, bool kBlend, bool kBounds, class policy_type>
+	__device__ __forceinline__ void skeleton_space_poses(const mapped_kernel_launch& launch, const policy_type& policy, consumer_walk_slots& walk)
+	{
+		static_assert(!kBlend || kBase != k_consumer_base_fused, "a blend accumulates whole qvv images; a base clip is decoded by a second wave");
+		constexpr bool base_is_clip = kBase == k_consumer_base_second_wave || kBase == k_consumer_base_fused;
+		// a base clip under additive0 / additive1: ONE wave decodes the base into the instance's image and the additive clip onto it
+		// (half the LDS per instance, half the waves: twice the poses a CU holds); otherwise a second wave decodes the base into its own image
+		constexpr bool fused_base = kBase == k_consumer_base_fused;
+		constexpr bool two_waves = kBase == k_consumer_base_second_wave;
+		constexpr bool object_space = kObjectSpace;
+		const skeleton_launch* const mapping = &launch.mapping;
+		const consumer_params& consumers = launch.consumers;
+		const device_clip* const clips = launch.clips;
+		const uint32_t num_clips = launch.num_clips;
+		const uint64_t pose_stride_bytes = launch.pose_stride_bytes;
+		const uint32_t lds_quads_per_image = launch.lds_quads_per_image;
+		// packed_block_shape: log2 of the instances per workgroup (bits 0..7) | words of LDS reserved for the shared walk schedule (bits 8..31)
+		const uint32_t log2_instances_per_block = launch.packed_block_shape & 0xFFu;
+		ACLHIP_PHASE_STAMP(0);
+
+		consumer_wave wave = consumer_wave_of(log2_instances_per_block, launch.lds_bytes_per_instance, lds_quads_per_image);
+		const uint32_t lane = wave.lane, role = wave.role, instance = wave.instance;
+		f32x4* const image = wave.image;
+
+		// (wave.num_tracks stays 0 for a wave without work: past the batch, refused instance, empty track list)
+		// the walk's normalize may take the short exact forms when every rotation it meets comes out of clips that are proven safe for
+		// them (norms near 1; a caller's base pose buffer holds anything)
+		uint32_t short_exact = kBase == k_consumer_base_buffer ? 0u : 1u;
+		if (instance < launch.num_instances)
+		{
+			const mapped_instance the = mapped_instance_of(clips, num_clips, launch.clip_ids, mapping, instance);
+			const uint32_t clip_id = the.clip_id, skeleton_id = the.skeleton_id, map_id = the.map_id;
+			const device_clip& clip = the.clip;
+			const device_skeleton& skeleton = the.skeleton;
+			const device_track_map& clip_map = the.clip_map;
+			// the transforms of the instance's pose and the hierarchy they are walked with are the skeleton's (clip.hierarchy is not read)
+			const uint32_t pose_tracks = skeleton.num_bones;
+			const uint32_t* const hierarchy = skeleton.hierarchy;
+
+			constexpr bool multiplies_transforms = object_space || kBase == k_consumer_base_buffer || kBase == k_consumer_base_second_wave;
+			bool refused = mapped_instance_refused<kObjectSpace, kBase, kMirrored>(clip_id, num_clips, clip, skeleton_id, skeleton, map_id, clip_map, mapping, pose_stride_bytes, lds_quads_per_image,
+				consumers.base_pose_stride_bytes);
+
+			const uint32_t rounding_policy = __builtin_amdgcn_readfirstlane(instance_rounding_policy_of(launch.params, instance));
+			// the instance's own looping policy (decompress.h:149) goes for every clip decoded on its behalf -- its base, its blend partners
+			decode_params params = launch.params;
+			params.looping_policy = uint8_t(__builtin_amdgcn_readfirstlane(instance_looping_policy_of(launch.params, instance)));
+
+			short_exact &= walk_may_use_short_exact_math(clip.flags, params.normalization);
+			short_exact &= (skeleton.flags & k_skeleton_short_exact_math) != 0 ? 1u : 0u;		// (the reference pose fills slots: its rotations are walked too)
+			// what a slot no track maps to holds: the reference pose -- or, for an additive clip and its blend partners, the additive identity
+			const slot_fill clip_fill = slot_fill_of(skeleton, consumers.additive_format);
+			device_clip base_clip = clip;
+			device_track_map base_map = {};
+			if constexpr (base_is_clip)
+			{
+				const base_records base = resolve_base_clip<kObjectSpace, kBase, kMirrored>(clips, num_clips, consumers, mapping, instance, clip, skeleton, params, refused, short_exact);
+				base_clip = base.clip;
+				base_map = base.map;
+				if (!refused && two_waves && role == 1 && pose_tracks != 0)
+					decode_pose_into_slot_image(base_clip, base_map, slot_fill{ skeleton.reference_pose, 0 }, as_constant(consumers.base_sample_times)[instance], rounding_policy, params, lane, wave.base_image);
+			}
+
+			// every clip of the blend: known, a transform clip, with a known map of its own into this skeleton
+			if (!refused)
+			{
+				if constexpr (kBlend)
+					refused = blend_partners_refused<!kMirrored && multiplies_transforms>(clips, num_clips, consumers, instance, params.normalization, short_exact,
+						[&](size_t entry, const ACLHIP_CONSTANT device_clip* record) { return blend_map_fits(mapping, entry, record, skeleton.num_bones); });
+				refused = refused || policy.refuses(instance, skeleton.num_bones);
+			}
+
+			if (refused)
+			{
+				if (lane == 0 && role == 0)
+					atomicAdd(launch.rejected_count, 1ull);
+			}
+			else if (pose_tracks != 0)
+			{
+				wave.num_tracks = pose_tracks;
+				if (role == 0)
+				{
+					if (object_space)
+						request_walk_schedule(hierarchy, log2_instances_per_block, launch.packed_block_shape >> 8, wave.shared_schedule, wave.slot, lane, walk);
+					if constexpr (fused_base)
+					{
+						decode_pose_into_slot_image(base_clip, base_map, slot_fill{ skeleton.reference_pose, 0 }, as_constant(consumers.base_sample_times)[instance], rounding_policy, params, lane, image);
+						wave_lds_barrier();		// the base pose is complete (its DMA has landed)
+						apply_additive_clip_onto_slot_image(clip, clip_map, clip_fill, as_constant(launch.sample_times)[instance], rounding_policy, params, consumers.additive_format, lane, image,
+							policy.strength(instance, consumers.additive_format, short_exact));
+					}
+					else
+					{
+						decode_pose_into_slot_image(clip, clip_map, clip_fill, as_constant(launch.sample_times)[instance], rounding_policy, params, lane, image);
+						if constexpr (kBlend)
+						{
+							const uint32_t num_blend_clips = consumers.num_blend_clips;
+							const ACLHIP_CONSTANT float* weights = as_constant(consumers.blend_weights) + size_t(instance) * num_blend_clips;
+							wave_lds_barrier();		// the first pose is complete (its DMA has landed)
+							blend_scale_image(image, pose_tracks * 3u, uniform_weight{ weights[0] }, lane);
+							for (uint32_t k = 1; k < num_blend_clips; ++k)
+							{
+								const size_t entry = size_t(instance) * (num_blend_clips - 1u) + (k - 1u);
+								const device_clip blend_clip = load_clip_fields(clips, as_constant(consumers.blend_clip_ids)[entry]);
+								wave_lds_barrier();		// every quad has its sum so far
+								const device_track_map blend_map = load_map_fields(mapping->maps, as_constant(mapping->blend_maps)[entry]);
+								blend_clip_onto_slot_image(blend_clip, blend_map, clip_fill, as_constant(consumers.blend_sample_times)[entry], rounding_policy, params, uniform_weight{ weights[k] }, lane, image);
+							}
+							wave_lds_barrier();
+							blend_normalize_rotations(image, pose_tracks, lane);
+						}
+						if constexpr (policy_type::k_weighs_additive_image)
+						{
+							wave_lds_barrier();		// the additive pose is complete (its DMA has landed; a blend's rotations are normalized)
+							weigh_additive_image(image, pose_tracks * 3u, policy.strength(instance, consumers.additive_format, short_exact), lane);
+						}
+					}
+				}
+			}
+			else if constexpr (kBounds)
+				wave.empty_pose = true;		// (a served instance whose pose has no transform)
+		}
+
+		// both images of every instance are complete
+		wave.short_exact = short_exact;
+		consumer_bounds_launch bounds = bounds_launch_of();
+		if constexpr (kBounds)
+			bounds = bounds_launch_of(*policy.bounds);
+		finish_consumer_poses<kObjectSpace, kBase, false, kMirrored, false, kBounds>(
+			consumer_tail_args{ launch.poses, launch.pose_stride_bytes, launch.lds_bytes_per_instance, log2_instances_per_block, launch.rejected_count, consumers.base_poses, consumers.base_pose_stride_bytes,
+				consumers.additive_format, bounds.bounds, bounds.bone_flags },
+			wave, walk);
+	}
+
+	// (the bounds instantiations' trailing argument: nothing, or consumer_bounds_launch -- aclhip_decompress_poses_batch_bounds, kernels_consumers.inl)
+	__device__ __forceinline__ const consumer_bounds_launch* bounds_argument_of() { return nullptr; }
+	__device__ __forceinline__ const consumer_bounds_launch* bounds_argument_of(const consumer_bounds_launch& launch) { return &launch; }
+
+	// aclhip_decompress_poses_batch_mapped
+	template<bool kObjectSpace, uint32_t kBase, bool kMirrored, bool kBlend, class... bounds_types>
+	__global__ __launch_bounds__(k_consumer_max_waves * k_wave_size) void decompress_poses_skeleton_kernel(const device_clip* __restrict__ clips, uint32_t num_clips,
+		const uint32_t* __restrict__ clip_ids, const float* __restrict__ sample_times, uint32_t num_instances, decode_params launch_params, consumer_params consumers,
+		uint8_t* __restrict__ poses, uint64_t pose_stride_bytes, uint32_t lds_quads_per_image, uint32_t lds_bytes_per_instance, uint32_t packed_block_shape,
+		unsigned long long* __restrict__ rejected_count, skeleton_launch skeleton_mapping, bounds_types... bounds_launch)
+	{
+		__shared__ consumer_walk_slots walk;		// (what the host subtracts from the LDS it may ask for: host_consumers.inl)
+		skeleton_space_poses<kObjectSpace, kBase, kMirrored, kBlend, sizeof...(bounds_types) != 0>(
+			mapped_kernel_launch{ clips, num_clips, clip_ids, sample_times, num_instances, launch_params, consumers, poses, pose_stride_bytes, lds_quads_per_image, lds_bytes_per_instance, packed_block_shape, rejected_count, skeleton_mapping },
+			mapped_poses_policy{ bounds_argument_of(bounds_launch...) }, walk);
+	}
+
+	// skeleton_space_poses' blend instantiations with a weight per slot (aclhip_decompress_poses_batch_masked), the masking as their own
+	// trailing argument, in a text of their own (see above). What differs from that body: the K mask records are checked next to the K maps; the three places
 	// that take a weight -- the first clip's scale, the constant / fill pass, the animated writer -- are handed a slot_weight; and what the
 	// blend's passes and finish_consumer_poses need of the launch is read late, from the kernarg segment (masked_kernel_args). One quad
-	// is still touched by one lane per pass: the LDS hazards and the barriers are that kernel's.
+	// is still touched by one lane per pass: the LDS hazards and the barriers are that body's.
 	template<bool kObjectSpace, uint32_t kBase, bool kMirrored, class... bounds_types>
 	__global__ __launch_bounds__(k_consumer_max_waves * k_wave_size) void decompress_poses_masked_kernel(const device_clip* __restrict__ clips, uint32_t num_clips,
 		const uint32_t* __restrict__ clip_ids, const float* __restrict__ sample_times, uint32_t num_instances, decode_params launch_params, consumer_params consumers,
@@ -503,7 +696,6 @@
 		asm volatile("" : "+s"(lds_quads_per_image), "+s"(lds_bytes_per_instance), "+s"(packed_block_shape));
 		// packed_block_shape: log2 of the instances per workgroup (bits 0..7) | words of LDS reserved for the shared walk schedule (bits 8..31)
 		const uint32_t log2_instances_per_block = packed_block_shape & 0xFFu;
-		extern __shared__ __attribute__((aligned(16))) uint8_t dynamic_lds[];
 		__shared__ consumer_walk_slots walk;		// (what the host subtracts from the LDS it may ask for: host_consumers.inl)
 
 		static_assert(kBase != k_consumer_base_fused, "a blend accumulates whole qvv images; a base clip is decoded by a second wave");
@@ -513,19 +705,11 @@
 		constexpr bool object_space = kObjectSpace;
 		ACLHIP_PHASE_STAMP(0);
 
-		// wave -> (instance slot of the workgroup, role): role 1 waves (base clips only) decode the slot's base
-		const uint32_t lane = threadIdx.x & (k_wave_size - 1);
-		const uint32_t wave_in_block = __builtin_amdgcn_readfirstlane(threadIdx.x / k_wave_size);
-		const uint32_t slot = wave_in_block & ((1u << log2_instances_per_block) - 1u);
-		const uint32_t role = wave_in_block >> log2_instances_per_block;
-		const uint32_t instance = (blockIdx.x << log2_instances_per_block) + slot;
-
-		uint8_t* instance_lds = dynamic_lds + size_t(slot) * lds_bytes_per_instance;
-		f32x4* image = reinterpret_cast<f32x4*>(instance_lds);
-		f32x4* base_image = image + lds_quads_per_image;
-		// one LDS copy of the walk schedule per workgroup, behind the instances' images: the instances of a workgroup usually share
-		// a skeleton (identical hierarchies are one image, see aclhip_set_clip_hierarchy), and every word kept per instance costs residency
-		uint32_t* shared_schedule = reinterpret_cast<uint32_t*>(dynamic_lds + (size_t(lds_bytes_per_instance) << log2_instances_per_block));
+		const consumer_wave layout = consumer_wave_of(log2_instances_per_block, lds_bytes_per_instance, lds_quads_per_image);
+		const uint32_t lane = layout.lane, wave_in_block = layout.wave_in_block, slot = layout.slot, role = layout.role, instance = layout.instance;
+		f32x4* const image = layout.image;
+		f32x4* const base_image = layout.base_image;
+		uint32_t* const shared_schedule = layout.shared_schedule;
 
 		uint32_t num_tracks = 0;		// stays 0 for a wave without work: past the batch, refused instance, empty track list
 		// the walk's normalize may take the short exact forms when every rotation it meets comes out of clips that are proven safe for
@@ -534,35 +718,20 @@
 		[[maybe_unused]] bool empty_pose = false;		// (bounds: a served instance whose pose has no transform)
 		if (instance < num_instances)
 		{
-			const uint32_t clip_id = as_constant(clip_ids)[instance];
-			// (every field in registers of its own: load_clip_fields, kernels_pose.inl)
-			const device_clip clip = load_clip_fields(clips, clip_id < num_clips ? clip_id : 0);
-
-			// skeleton space: the instance's skeleton and its clip's map, read on the scalar unit next to the clip record. A cleared record
-			// (an unknown or retired handle) holds no image; record 0 of both tables is never handed out.
-			const uint32_t skeleton_id = mapping->instance_skeletons != nullptr ? as_constant(mapping->instance_skeletons)[instance] : mapping->skeleton;
-			const uint32_t map_id = mapping->instance_maps != nullptr ? as_constant(mapping->instance_maps)[instance] : mapping->map;
-			const device_skeleton skeleton = load_skeleton_fields(mapping->skeletons, skeleton_id < mapping->num_skeletons ? skeleton_id : 0);
-			const device_track_map clip_map = load_map_fields(mapping->maps, map_id < mapping->num_maps ? map_id : 0);
+			const mapped_instance the = mapped_instance_of(clips, num_clips, clip_ids, mapping, instance);
+			const uint32_t clip_id = the.clip_id, skeleton_id = the.skeleton_id, map_id = the.map_id;
+			const device_clip& clip = the.clip;
+			const device_skeleton& skeleton = the.skeleton;
+			const device_track_map& clip_map = the.clip_map;
 			// the transforms of the instance's pose and the hierarchy they are walked with are the skeleton's (clip.hierarchy is not read)
 			const uint32_t pose_tracks = skeleton.num_bones;
 			const uint32_t* const hierarchy = skeleton.hierarchy;
 
-			// refused: unknown or retired masks and masks of another slot count (below, next to the blend's maps), and everything the unmasked
-			// kernel refuses: unknown / scalar clips, unknown or retired skeletons and maps, a map made for another clip or another skeleton, object
-			// space without a hierarchy, more bones than the row or the launch's LDS image holds. Both waves of an instance come to the same
-			// verdict; the first one reports it. A launch is shaped for its batch when it is enqueued (launch_consumers: LDS image sizes from
-			// the pose stride, kernel instantiation from what the registry holds) and meets its clips and skeletons when it runs: a clip or a
-			// reference pose that may hand a negative scale to a launch compiled without rtm::qvv_mul's matrix route -- registered behind a
-			// captured launch's back -- is refused here, not computed wrongly. Only launches that MULTIPLY transforms care: local space
-			// without a base, and additive0 / additive1 onto a fused base clip, combine scale with scale and serve mirrored skeletons as they are.
+			// refused: unknown or retired masks and masks of another slot count (below, next to the blend's maps), and everything
+			// mapped_instance_refused refuses
 			constexpr bool multiplies_transforms = object_space || kBase == k_consumer_base_buffer || kBase == k_consumer_base_second_wave;
-			bool refused = clip_id >= num_clips || !is_transform_clip(clip.flags) || (object_space && hierarchy == nullptr)
-				|| skeleton_id >= mapping->num_skeletons || skeleton.reference_pose == nullptr || !map_fits(clip_map, map_id, mapping->num_maps, clip.num_tracks, skeleton.num_bones)
-				|| uint64_t(pose_tracks) * 48u > pose_stride_bytes || pose_tracks * 3u > lds_quads_per_image
-				|| (kBase == k_consumer_base_buffer && uint64_t(pose_tracks) * 48u > consumers.base_pose_stride_bytes)
-				|| (!kMirrored && multiplies_transforms && (skeleton.flags & k_skeleton_negative_scale) != 0)
-				|| (!kMirrored && multiplies_transforms && !base_is_clip && (clip.flags & k_clip_negative_scale) != 0);
+			bool refused = mapped_instance_refused<kObjectSpace, kBase, kMirrored>(clip_id, num_clips, clip, skeleton_id, skeleton, map_id, clip_map, mapping, pose_stride_bytes, lds_quads_per_image,
+				consumers.base_pose_stride_bytes);
 
 			const uint32_t rounding_policy = __builtin_amdgcn_readfirstlane(instance_rounding_policy_of(launch_params, instance));
 			// the instance's own looping policy (decompress.h:149) goes for every clip decoded on its behalf -- its base, its blend partners
@@ -576,16 +745,9 @@
 			const slot_fill clip_fill = slot_fill_of(skeleton, consumers.additive_format);
 			if constexpr (base_is_clip)
 			{
-				const uint32_t base_clip_id = as_constant(consumers.base_clip_ids)[instance];
-				const device_clip base_clip = load_clip_fields(clips, base_clip_id < num_clips ? base_clip_id : 0);
-				// (each clip only has to match its own map, each map the skeleton)
-				const uint32_t base_map_id = as_constant(mapping->base_maps)[instance];
-				const device_track_map base_map = load_map_fields(mapping->maps, base_map_id < mapping->num_maps ? base_map_id : 0);
-				refused = refused || base_clip_id >= num_clips || !is_transform_clip(base_clip.flags) || !map_fits(base_map, base_map_id, mapping->num_maps, base_clip.num_tracks, skeleton.num_bones)
-					|| (!kMirrored && multiplies_transforms && ((clip.flags | base_clip.flags) & k_clip_negative_scale) != 0);
-				short_exact &= walk_may_use_short_exact_math(base_clip.flags, params.normalization);
+				const base_records base = resolve_base_clip<kObjectSpace, kBase, kMirrored>(clips, num_clips, consumers, mapping, instance, clip, skeleton, params, refused, short_exact);
 				if (!refused && two_waves && role == 1 && pose_tracks != 0)
-					decode_pose_into_slot_image(base_clip, base_map, slot_fill{ skeleton.reference_pose, 0 }, as_constant(consumers.base_sample_times)[instance], rounding_policy, params, lane, base_image);
+					decode_pose_into_slot_image(base.clip, base.map, slot_fill{ skeleton.reference_pose, 0 }, as_constant(consumers.base_sample_times)[instance], rounding_policy, params, lane, base_image);
 			}
 
 			if (!refused)
@@ -662,223 +824,17 @@
 			consumer_wave{ image, base_image, shared_schedule, slot, role, lane, wave_in_block, instance, num_tracks, short_exact, empty_pose }, walk);
 	}
 
-	// ---- additive strength (aclhip_additive_layering, aclhip_decompress_poses_batch_additive_weighted) ---------------------------------
-	// A strength per (instance, SLOT) on the additive pose in front of apply_additive_to_base: include/aclhip.h states the definition. The
-	// masks are the blend masks (device_blend_mask, the context's table).
-	// the additive kernels' own trailing argument, behind skeleton_launch
-	struct additive_strength_launch
-	{
-		const device_blend_mask* masks;			// the context's mask table
-		uint32_t num_masks;						// its capacity
-		uint32_t reserved;
-		const float* instance_weights;			// [num_instances] or null: every instance 1
-		const uint32_t* instance_masks;			// [num_instances] or null; 0: no mask
-	};
-
-	// The strength of an instance's additive layer: layer_weight gives e = w, or w * mask[slot] through the vector cache (one load per quad);
-	// the pointer, the weight and the two settings are wave uniform.
-	struct additive_strength
-	{
-		layer_weight weight;
-		uint32_t additive_format;
-		uint32_t short_exact;		// the instance's walk_may_use_short_exact_math verdict, and w in [0, 1] (masks are: aclhip_register_blend_mask)
-		__device__ __forceinline__ float4 operator()(uint32_t slot, uint32_t kind, float4 value) const
-		{
-			const float strength = weight(slot);
-			return short_exact != 0 ? weigh_additive_sub_track<true>(additive_format, kind, value, strength) : weigh_additive_sub_track<false>(additive_format, kind, value, strength);
-		}
-	};
-
-	// The additive kernels' arguments as they lie in the kernarg segment, like masked_kernel_args: the layering is read THERE, where the
-	// strength is made -- behind the base clip's decode in the fused instantiations, behind every decode in the others.
-	struct additive_kernel_args
-	{
-		const device_clip* clips;
-		uint32_t num_clips;
-		const uint32_t* clip_ids;
-		const float* sample_times;
-		uint32_t num_instances;
-		decode_params params;
-		consumer_params consumers;
-		uint8_t* poses;
-		uint64_t pose_stride_bytes;
-		uint32_t lds_quads_per_image;
-		uint32_t lds_bytes_per_instance;
-		uint32_t packed_block_shape;
-		unsigned long long* rejected_count;
-		skeleton_launch mapping;
-		additive_strength_launch layering;
-	};
-	static_assert(offsetof(additive_kernel_args, mapping) == offsetof(masked_kernel_args, mapping) && offsetof(additive_kernel_args, layering) == 336 && sizeof(additive_kernel_args) == 368,
-		"additive_kernel_args mirrors the kernel's argument list");
-
-	// (opaque per use, like late_masked_kernel_args)
-	__device__ __forceinline__ const ACLHIP_CONSTANT additive_strength_launch* late_additive_layering()
-	{
-	#if defined(__HIP_DEVICE_COMPILE__)
-		const ACLHIP_CONSTANT additive_kernel_args* args = (const ACLHIP_CONSTANT additive_kernel_args*)__builtin_amdgcn_kernarg_segment_ptr();
-		asm volatile("" : "+s"(args));
-		return &args->layering;
-	#else
-		return nullptr;		// (the host pass only has to compile)
-	#endif
-	}
-
-	// (the mask behind a handle the kernel has checked: known, of the skeleton's slot count -- or the null handle)
-	__device__ __forceinline__ additive_strength additive_strength_of(uint32_t instance, uint32_t additive_format, uint32_t short_exact)
-	{
-		const ACLHIP_CONSTANT additive_strength_launch* layering = late_additive_layering();
-		const float weight = layering->instance_weights != nullptr ? as_constant(layering->instance_weights)[instance] : 1.0f;
-		const uint32_t handle = layering->instance_masks != nullptr ? as_constant(layering->instance_masks)[instance] : 0u;
-		const ACLHIP_CONSTANT float* mask = handle != 0 ? as_constant(as_constant(layering->masks)[handle].image) : nullptr;
-		return additive_strength{ layer_weight{ mask, weight }, additive_format, (weight >= 0.0f && weight <= 1.0f) ? short_exact : 0u };
-	}
-
-	// decompress_poses_skeleton_kernel's additive instantiations with a strength per (instance, slot) on the additive pose
-	// (aclhip_decompress_poses_batch_additive_weighted), the layering as their own trailing argument. What differs from that kernel: the
-	// instance's mask record is checked next to its maps, and the strength goes in at one of two places. Fused (additive0 / additive1 onto
-	// a base clip, one image): on every additive sub-track in front of apply_additive_sub_track -- one quad is still touched by one lane per
-	// pass, the LDS hazards and the barriers are that kernel's. Otherwise (a second wave's image, a base pose buffer, a blend) the additive
-	// pose sits complete in its own image: one pass over it, behind the blend's normalize and in front of finish_consumer_poses' barrier.
-	// Everything else -- refusals, decode, fill, blend, tail -- is that kernel's text.
+	// aclhip_decompress_poses_batch_additive_weighted: the additive instantiations with a strength per (instance, slot) on the additive pose,
+	// the layering as their own trailing argument (read from the kernarg segment: additive_kernel_args)
 	template<bool kObjectSpace, uint32_t kBase, bool kMirrored, bool kBlend>
 	__global__ __launch_bounds__(k_consumer_max_waves * k_wave_size) void decompress_poses_additive_kernel(const device_clip* __restrict__ clips, uint32_t num_clips,
 		const uint32_t* __restrict__ clip_ids, const float* __restrict__ sample_times, uint32_t num_instances, decode_params launch_params, consumer_params consumers,
 		uint8_t* __restrict__ poses, uint64_t pose_stride_bytes, uint32_t lds_quads_per_image, uint32_t lds_bytes_per_instance, uint32_t packed_block_shape,
 		unsigned long long* __restrict__ rejected_count, skeleton_launch skeleton_mapping, additive_strength_launch)
 	{
-		// (the layering is read from the kernarg segment: additive_kernel_args)
-		const skeleton_launch* const mapping = &skeleton_mapping;
-		// packed_block_shape: log2 of the instances per workgroup (bits 0..7) | words of LDS reserved for the shared walk schedule (bits 8..31)
-		const uint32_t log2_instances_per_block = packed_block_shape & 0xFFu;
-		extern __shared__ __attribute__((aligned(16))) uint8_t dynamic_lds[];
-		__shared__ consumer_walk_slots walk;		// (what the host subtracts from the LDS it may ask for: host_consumers.inl)
-
 		static_assert(kBase != k_consumer_base_none, "an additive layer goes onto a base");
-		static_assert(!kBlend || kBase != k_consumer_base_fused, "a blend accumulates whole qvv images; a base clip is decoded by a second wave");
-		constexpr bool base_is_clip = kBase == k_consumer_base_second_wave || kBase == k_consumer_base_fused;
-		constexpr bool fused_base = kBase == k_consumer_base_fused;
-		constexpr bool two_waves = kBase == k_consumer_base_second_wave;
-		constexpr bool object_space = kObjectSpace;
-		ACLHIP_PHASE_STAMP(0);
-
-		// wave -> (instance slot of the workgroup, role): role 1 waves (base clips only) decode the slot's base
-		const uint32_t lane = threadIdx.x & (k_wave_size - 1);
-		const uint32_t wave_in_block = __builtin_amdgcn_readfirstlane(threadIdx.x / k_wave_size);
-		const uint32_t slot = wave_in_block & ((1u << log2_instances_per_block) - 1u);
-		const uint32_t role = wave_in_block >> log2_instances_per_block;
-		const uint32_t instance = (blockIdx.x << log2_instances_per_block) + slot;
-
-		uint8_t* instance_lds = dynamic_lds + size_t(slot) * lds_bytes_per_instance;
-		f32x4* image = reinterpret_cast<f32x4*>(instance_lds);
-		f32x4* base_image = image + lds_quads_per_image;
-		uint32_t* shared_schedule = reinterpret_cast<uint32_t*>(dynamic_lds + (size_t(lds_bytes_per_instance) << log2_instances_per_block));
-
-		uint32_t num_tracks = 0;		// stays 0 for a wave without work: past the batch, refused instance, empty track list
-		uint32_t short_exact = kBase == k_consumer_base_buffer ? 0u : 1u;
-		if (instance < num_instances)
-		{
-			const uint32_t clip_id = as_constant(clip_ids)[instance];
-			const device_clip clip = load_clip_fields(clips, clip_id < num_clips ? clip_id : 0);
-
-			const uint32_t skeleton_id = mapping->instance_skeletons != nullptr ? as_constant(mapping->instance_skeletons)[instance] : mapping->skeleton;
-			const uint32_t map_id = mapping->instance_maps != nullptr ? as_constant(mapping->instance_maps)[instance] : mapping->map;
-			const device_skeleton skeleton = load_skeleton_fields(mapping->skeletons, skeleton_id < mapping->num_skeletons ? skeleton_id : 0);
-			const device_track_map clip_map = load_map_fields(mapping->maps, map_id < mapping->num_maps ? map_id : 0);
-			const uint32_t pose_tracks = skeleton.num_bones;
-			const uint32_t* const hierarchy = skeleton.hierarchy;
-
-			// refused: an unknown or retired mask and a mask of another slot count (below), and everything decompress_poses_skeleton_kernel refuses
-			constexpr bool multiplies_transforms = object_space || kBase == k_consumer_base_buffer || kBase == k_consumer_base_second_wave;
-			bool refused = clip_id >= num_clips || !is_transform_clip(clip.flags) || (object_space && hierarchy == nullptr)
-				|| skeleton_id >= mapping->num_skeletons || skeleton.reference_pose == nullptr || !map_fits(clip_map, map_id, mapping->num_maps, clip.num_tracks, skeleton.num_bones)
-				|| uint64_t(pose_tracks) * 48u > pose_stride_bytes || pose_tracks * 3u > lds_quads_per_image
-				|| (kBase == k_consumer_base_buffer && uint64_t(pose_tracks) * 48u > consumers.base_pose_stride_bytes)
-				|| (!kMirrored && multiplies_transforms && (skeleton.flags & k_skeleton_negative_scale) != 0)
-				|| (!kMirrored && multiplies_transforms && !base_is_clip && (clip.flags & k_clip_negative_scale) != 0);
-			{
-				// the mask the instance names: the null handle, or a known mask of this skeleton's slot count
-				const ACLHIP_CONSTANT additive_strength_launch* layering = late_additive_layering();
-				const uint32_t mask_id = layering->instance_masks != nullptr ? as_constant(layering->instance_masks)[instance] : 0u;
-				const ACLHIP_CONSTANT device_blend_mask* mask_record = as_constant(layering->masks) + (mask_id < layering->num_masks ? mask_id : 0);
-				refused = refused || (mask_id != 0 && (mask_id >= layering->num_masks || mask_record->image == nullptr || mask_record->num_slots != skeleton.num_bones));
-			}
-
-			const uint32_t rounding_policy = __builtin_amdgcn_readfirstlane(instance_rounding_policy_of(launch_params, instance));
-			decode_params params = launch_params;
-			params.looping_policy = uint8_t(__builtin_amdgcn_readfirstlane(instance_looping_policy_of(launch_params, instance)));
-
-			short_exact &= walk_may_use_short_exact_math(clip.flags, params.normalization);
-			short_exact &= (skeleton.flags & k_skeleton_short_exact_math) != 0 ? 1u : 0u;
-			// (an additive clip and its blend partners fill with the additive identity)
-			const slot_fill clip_fill = slot_fill_of(skeleton, consumers.additive_format);
-			device_clip base_clip = clip;
-			device_track_map base_map = {};
-			if (base_is_clip)
-			{
-				const uint32_t base_clip_id = as_constant(consumers.base_clip_ids)[instance];
-				base_clip = load_clip_fields(clips, base_clip_id < num_clips ? base_clip_id : 0);
-				const uint32_t base_map_id = as_constant(mapping->base_maps)[instance];
-				base_map = load_map_fields(mapping->maps, base_map_id < mapping->num_maps ? base_map_id : 0);
-				refused = refused || base_clip_id >= num_clips || !is_transform_clip(base_clip.flags) || !map_fits(base_map, base_map_id, mapping->num_maps, base_clip.num_tracks, skeleton.num_bones)
-					|| (!kMirrored && multiplies_transforms && ((clip.flags | base_clip.flags) & k_clip_negative_scale) != 0);
-				short_exact &= walk_may_use_short_exact_math(base_clip.flags, params.normalization);
-				if (!refused && two_waves && role == 1 && pose_tracks != 0)
-					decode_pose_into_slot_image(base_clip, base_map, slot_fill{ skeleton.reference_pose, 0 }, as_constant(consumers.base_sample_times)[instance], rounding_policy, params, lane, base_image);
-			}
-
-			if (kBlend && !refused)
-				refused = blend_partners_refused<!kMirrored && multiplies_transforms>(clips, num_clips, consumers, instance, params.normalization, short_exact,
-					[&](size_t entry, const ACLHIP_CONSTANT device_clip* record) { return blend_map_fits(mapping, entry, record, skeleton.num_bones); });
-
-			if (refused)
-			{
-				if (lane == 0 && role == 0)
-					atomicAdd(rejected_count, 1ull);
-			}
-			else if (pose_tracks != 0)
-			{
-				num_tracks = pose_tracks;
-				if (role == 0)
-				{
-					if (object_space)
-						request_walk_schedule(hierarchy, log2_instances_per_block, packed_block_shape >> 8, shared_schedule, slot, lane, walk);
-					if (fused_base)
-					{
-						decode_pose_into_slot_image(base_clip, base_map, slot_fill{ skeleton.reference_pose, 0 }, as_constant(consumers.base_sample_times)[instance], rounding_policy, params, lane, image);
-						wave_lds_barrier();		// the base pose is complete (its DMA has landed)
-						apply_additive_clip_onto_slot_image(clip, clip_map, clip_fill, as_constant(sample_times)[instance], rounding_policy, params, consumers.additive_format, lane, image,
-							additive_strength_of(instance, consumers.additive_format, short_exact));
-					}
-					else
-					{
-						decode_pose_into_slot_image(clip, clip_map, clip_fill, as_constant(sample_times)[instance], rounding_policy, params, lane, image);
-						if constexpr (kBlend)
-						{
-							const uint32_t num_blend_clips = consumers.num_blend_clips;
-							const ACLHIP_CONSTANT float* weights = as_constant(consumers.blend_weights) + size_t(instance) * num_blend_clips;
-							wave_lds_barrier();		// the first pose is complete (its DMA has landed)
-							blend_scale_image(image, pose_tracks * 3u, uniform_weight{ weights[0] }, lane);
-							for (uint32_t k = 1; k < num_blend_clips; ++k)
-							{
-								const size_t entry = size_t(instance) * (num_blend_clips - 1u) + (k - 1u);
-								const device_clip blend_clip = load_clip_fields(clips, as_constant(consumers.blend_clip_ids)[entry]);
-								wave_lds_barrier();		// every quad has its sum so far
-								const device_track_map blend_map = load_map_fields(mapping->maps, as_constant(mapping->blend_maps)[entry]);
-								blend_clip_onto_slot_image(blend_clip, blend_map, clip_fill, as_constant(consumers.blend_sample_times)[entry], rounding_policy, params, uniform_weight{ weights[k] }, lane, image);
-							}
-							wave_lds_barrier();
-							blend_normalize_rotations(image, pose_tracks, lane);
-						}
-						wave_lds_barrier();		// the additive pose is complete (its DMA has landed; a blend's rotations are normalized)
-						weigh_additive_image(image, pose_tracks * 3u, additive_strength_of(instance, consumers.additive_format, short_exact), lane);
-					}
-				}
-			}
-		}
-
-		// both images of every instance are complete
-		finish_consumer_poses<kObjectSpace, kBase, false, kMirrored, false, false>(
-			consumer_tail_args{ poses, pose_stride_bytes, lds_bytes_per_instance, log2_instances_per_block, rejected_count, consumers.base_poses, consumers.base_pose_stride_bytes, consumers.additive_format },
-			consumer_wave{ image, base_image, shared_schedule, slot, role, lane, wave_in_block, instance, num_tracks, short_exact }, walk);
+		__shared__ consumer_walk_slots walk;
+		skeleton_space_poses<kObjectSpace, kBase, kMirrored, kBlend, false>(
+			mapped_kernel_launch{ clips, num_clips, clip_ids, sample_times, num_instances, launch_params, consumers, poses, pose_stride_bytes, lds_quads_per_image, lds_bytes_per_instance, packed_block_shape, rejected_count, skeleton_mapping },
+			additive_poses_policy{}, walk);
 	}
