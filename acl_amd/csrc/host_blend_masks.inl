@@ -220,6 +220,19 @@ extern "C" aclhip_status aclhip_decompress_poses_batch_masked(aclhip_context* co
 	return launch_consumers(context, clips, sample_times, num_instances, device_params, *consumers, poses, pose_stride_bytes, static_cast<hipStream_t>(stream), &launch, &mask_launch);
 }
 
+namespace
+{
+	// What every launch with bounds (_bounds, aclhip_transform_poses_batch) checks of the struct itself
+	aclhip_status check_pose_bounds(aclhip_context* context, const aclhip_pose_bounds* bounds)
+	{
+		if (bounds->bounds == nullptr || (reinterpret_cast<uintptr_t>(bounds->bounds) & 15u) != 0)
+			return fail(context, ACLHIP_ERROR_INVALID_ARGUMENT, "the bounds buffer must be set and 16 byte aligned");
+		if (bounds->reserved[0] != 0 || bounds->reserved[1] != 0)
+			return fail(context, ACLHIP_ERROR_INVALID_ARGUMENT, "the reserved fields of pose bounds are 0");
+		return ACLHIP_OK;
+	}
+}
+
 // The launch above, the mapped launch or the unmapped one -- by which of `mapping` and `masking` are set -- with a box per instance
 // (include/aclhip.h: aclhip_pose_bounds). The argument checks that need no device come first and leave a message, with or without a context.
 extern "C" aclhip_status aclhip_decompress_poses_batch_bounds(aclhip_context* context, const aclhip_clip* clips, const float* sample_times, uint32_t num_instances,
@@ -228,10 +241,8 @@ extern "C" aclhip_status aclhip_decompress_poses_batch_bounds(aclhip_context* co
 {
 	if (bounds == nullptr)
 		return fail(context, ACLHIP_ERROR_INVALID_ARGUMENT, "null pose bounds");
-	if (bounds->bounds == nullptr || (reinterpret_cast<uintptr_t>(bounds->bounds) & 15u) != 0)
-		return fail(context, ACLHIP_ERROR_INVALID_ARGUMENT, "the bounds buffer must be set and 16 byte aligned");
-	if (bounds->reserved[0] != 0 || bounds->reserved[1] != 0)
-		return fail(context, ACLHIP_ERROR_INVALID_ARGUMENT, "the reserved fields of pose bounds are 0");
+	if (const aclhip_status bounds_status = check_pose_bounds(context, bounds); bounds_status != ACLHIP_OK)
+		return bounds_status;
 	if (consumers == nullptr)
 		return fail(context, ACLHIP_ERROR_INVALID_ARGUMENT, "null consumers");
 	if (consumers->object_space == 0)

@@ -403,6 +403,49 @@ namespace
 		}
 	};
 
+	// The shape of a pose consumer launch (launch_consumers, launch_pose_buffers): one wave per instance, the whole pose (its base, its
+	// hierarchy) in LDS; as many instances per workgroup (a power of two, at most 8, 4 unless told otherwise: measured best) as leave room
+	// for three workgroups per CU: the object space walk packs its lanes with instances of one workgroup.
+	// what a workgroup may ask for on top of the kernel's static words (consumer_walk_slots, kernels_consumers.inl)
+	constexpr size_t k_consumer_lds_bytes = 160 * 1024 - ((sizeof(consumer_walk_slots) + 127) / 128) * 128;
+	struct consumer_launch_shape
+	{
+		uint32_t lds_quads_per_image;
+		size_t lds_bytes_per_instance;
+		uint32_t lds_schedule_words;
+		uint32_t log2_instances_per_block;
+		size_t lds_bytes;			// of a workgroup
+		bool fits;					// lds_needed_bytes <= k_consumer_lds_bytes
+		size_t lds_needed_bytes;	// of ONE instance and the schedule: what has to fit
+	};
+
+	// image_quads: the quads of an instance's image (exactly the transforms a pose row holds, or the largest registered clip has, not a quad
+	// more: the kernel's "does the pose fit its image" test is also its "does the pose fit its row" test -- every quad is addressed on its
+	// own: no granularity needed); max_hierarchy_words: the longest walk schedule registered (object space only, else 0 words are kept)
+	consumer_launch_shape consumer_launch_shape_of(uint32_t image_quads, uint32_t batch_transforms, bool two_waves, bool object_space, uint32_t max_hierarchy_words)
+	{
+		consumer_launch_shape shape;
+		shape.lds_quads_per_image = std::max<uint32_t>(image_quads, 1);
+		// (measurement knob: ACLHIP_CONSUMER_LDS_PAD bytes between the instances' images -- the walk's lanes touch the same quad of all of a
+		// workgroup's images at once, and images a multiple of 128 bytes apart put those on the same LDS banks)
+		// 16 bytes: the four images of a workgroup then start on different banks (round 4: 88.8 -> 86.9 us, 90.6 -> 83.7 us with ACLHIP_CONSUMERS_FAST;
+		// 32 the same, 64 less, 0 what rounds 2 and 3 measured)
+		static const size_t lds_pad = []() { const char* value = lab_knob("ACLHIP_CONSUMER_LDS_PAD"); return value != nullptr ? size_t(std::atol(value)) & ~size_t(15) : size_t(16); }();
+		shape.lds_bytes_per_instance = size_t(shape.lds_quads_per_image) * 16 * (two_waves ? 2 : 1) + lds_pad;
+		// a walk schedule of T transforms: 2 words + a step end per step + a pair per transform with a parent, at most 2 + 2 T words
+		shape.lds_schedule_words = object_space ? align_to_u32(std::max<uint32_t>(std::min<uint32_t>(max_hierarchy_words, 2 + 2 * batch_transforms + 3), 4), 4) : 0;
+		const size_t lds_schedule_bytes = size_t(shape.lds_schedule_words) * sizeof(uint32_t);
+		shape.lds_needed_bytes = shape.lds_bytes_per_instance + lds_schedule_bytes;
+		shape.fits = shape.lds_needed_bytes <= k_consumer_lds_bytes;
+		shape.log2_instances_per_block = 2;
+		if (const char* forced = lab_knob("ACLHIP_CONSUMER_LOG2_INSTANCES"))
+			shape.log2_instances_per_block = std::min<uint32_t>(uint32_t(forced[0] - '0'), 3);
+		while (shape.log2_instances_per_block != 0 && (shape.lds_bytes_per_instance << shape.log2_instances_per_block) + lds_schedule_bytes > k_consumer_lds_bytes / 3)
+			shape.log2_instances_per_block--;
+		shape.lds_bytes = (shape.lds_bytes_per_instance << shape.log2_instances_per_block) + lds_schedule_bytes;
+		return shape;
+	}
+
 	// `mapping` (aclhip_decompress_poses_batch_mapped): skeleton space -- the launch is shaped by its rows alone (pose_stride_bytes / 48
 	// slots), the skeleton kernels take the mapping as their trailing argument. `masking` (aclhip_decompress_poses_batch_masked, with a
 	// mapping and a blend): the same launch through the masked kernels. `bounds` (aclhip_decompress_poses_batch_bounds, object space): the
@@ -481,36 +524,21 @@ namespace
 		// (skeleton space: the slots of a row, whatever clips are registered -- a clip may have more tracks than the skeleton has bones)
 		const uint32_t batch_quads = mapping != nullptr ? uint32_t(std::min<uint64_t>(pose_stride_bytes / 48, 0xFFFFu)) * 3u : batch_pose_quads(context, ACLHIP_LAYOUT_QVV48, pose_stride_bytes);
 		const uint32_t image_quads = unit_scale ? batch_quads / 3 * 2 : batch_quads;
-		// exactly the transforms a pose row holds (or the largest registered clip has), not a quad more: the kernel's "does the pose fit
-		// its image" test is also its "does the pose fit its row" test (every quad is addressed on its own: no granularity needed)
-		const uint32_t lds_quads_per_image = std::max<uint32_t>(image_quads, 1);
 		// additive0 / additive1 combine sub-track with sub-track: the base clip is decoded into the instance's image and the additive clip
 		// onto it by one wave; the relative format (a qvv_mul) needs both poses whole: a second wave, a second image
 		// (a blend accumulates its clips in the instance's image before anything else happens to it: its base clip gets a wave and an image of its own)
 		const bool fused_base = base_is_clip && !blend && consumers.additive_format != ACLHIP_ADDITIVE_RELATIVE && lab_knob("ACLHIP_CONSUMER_TWO_IMAGES") == nullptr;
 		const bool two_waves = base_is_clip && !fused_base;
-		// (measurement knob: ACLHIP_CONSUMER_LDS_PAD bytes between the instances' images -- the walk's lanes touch the same quad of all of a
-		// workgroup's images at once, and images a multiple of 128 bytes apart put those on the same LDS banks)
-		// 16 bytes: the four images of a workgroup then start on different banks (round 4: 88.8 -> 86.9 us, 90.6 -> 83.7 us with ACLHIP_CONSUMERS_FAST;
-		// 32 the same, 64 less, 0 what rounds 2 and 3 measured)
-		static const size_t lds_pad = []() { const char* value = lab_knob("ACLHIP_CONSUMER_LDS_PAD"); return value != nullptr ? size_t(std::atol(value)) & ~size_t(15) : size_t(16); }();
-		const size_t lds_bytes_per_instance = size_t(lds_quads_per_image) * 16 * (two_waves ? 2 : 1) + lds_pad;
-		// a walk schedule of T transforms: 2 words + a step end per step + a pair per transform with a parent, at most 2 + 2 T words
-		const uint32_t lds_schedule_words = consumers.object_space != 0 ? align_to_u32(std::max<uint32_t>(std::min<uint32_t>(mapping != nullptr ? context->max_skeleton_hierarchy_words : context->max_hierarchy_words, 2 + 2 * (batch_quads / 3) + 3), 4), 4) : 0;
-		const size_t lds_schedule_bytes = size_t(lds_schedule_words) * sizeof(uint32_t);
-		// what a workgroup may ask for on top of the kernel's static words (consumer_walk_slots, kernels_consumers.inl)
-		constexpr size_t k_lds_bytes = 160 * 1024 - ((sizeof(consumer_walk_slots) + 127) / 128) * 128;
-		if (lds_bytes_per_instance + lds_schedule_bytes > k_lds_bytes)
-			return fail(context, ACLHIP_ERROR_INVALID_ARGUMENT, "poses of %u transforms (the pose stride, the largest registered clip): too large for the pose consumers (%zu bytes of LDS per instance)", batch_quads / 3, lds_bytes_per_instance + lds_schedule_bytes);
-		uint32_t log2_instances_per_block = 2;
-		if (const char* forced = lab_knob("ACLHIP_CONSUMER_LOG2_INSTANCES"))
-			log2_instances_per_block = std::min<uint32_t>(uint32_t(forced[0] - '0'), 3);
-		while (log2_instances_per_block != 0 && (lds_bytes_per_instance << log2_instances_per_block) + lds_schedule_bytes > k_lds_bytes / 3)
-			log2_instances_per_block--;
+		const consumer_launch_shape shape = consumer_launch_shape_of(image_quads, batch_quads / 3, two_waves, consumers.object_space != 0,
+			mapping != nullptr ? context->max_skeleton_hierarchy_words : context->max_hierarchy_words);
+		if (!shape.fits)
+			return fail(context, ACLHIP_ERROR_INVALID_ARGUMENT, "poses of %u transforms (the pose stride, the largest registered clip): too large for the pose consumers (%zu bytes of LDS per instance)", batch_quads / 3, shape.lds_needed_bytes);
+		constexpr size_t k_lds_bytes = k_consumer_lds_bytes;
+		const uint32_t lds_quads_per_image = shape.lds_quads_per_image, lds_schedule_words = shape.lds_schedule_words, log2_instances_per_block = shape.log2_instances_per_block;
+		const size_t lds_bytes_per_instance = shape.lds_bytes_per_instance, lds_bytes = shape.lds_bytes;
 		const uint32_t instances_per_block = 1u << log2_instances_per_block;
 		const uint32_t waves_per_block = instances_per_block * (two_waves ? 2 : 1);
 		const uint32_t num_blocks = (num_instances + instances_per_block - 1) / instances_per_block;
-		const size_t lds_bytes = lds_bytes_per_instance * instances_per_block + lds_schedule_bytes;
 
 		consumer_params device_consumers;
 		device_consumers.base_clip_ids = base_is_clip ? consumers.base_clips : nullptr;

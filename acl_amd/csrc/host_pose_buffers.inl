@@ -1,0 +1,145 @@
+// host_pose_buffers.inl -- part of aclhip.hip (one translation unit; included there, in this order, not compiled on its own).
+// Host side: the pose consumers over a caller's pose buffers (aclhip_transform_poses_batch; kernels_pose_buffers.inl).
+
+namespace
+{
+	// do [a, a + a_stride * n) and [b, b + b_stride * n) share a byte? (a product past 2^64 ends at the top of the address space)
+	bool pose_ranges_overlap(const void* a, uint64_t a_stride, const void* b, uint64_t b_stride, uint32_t num_instances)
+	{
+		const auto end_of = [&](const void* pointer, uint64_t stride)
+		{
+			const unsigned __int128 end = (unsigned __int128)reinterpret_cast<uintptr_t>(pointer) + (unsigned __int128)stride * num_instances;
+			return end > (unsigned __int128)UINT64_MAX ? UINT64_MAX : uint64_t(end);
+		};
+		const uint64_t a_begin = reinterpret_cast<uintptr_t>(a), b_begin = reinterpret_cast<uintptr_t>(b);
+		return a_begin < end_of(b, b_stride) && b_begin < end_of(a, a_stride);
+	}
+
+	// What aclhip_transform_poses_batch checks of its arguments before any device call; every refusal leaves a message, with or without a context
+	aclhip_status check_pose_buffer_consumers(aclhip_context* context, const void* local_poses, uint64_t local_pose_stride_bytes, uint32_t num_instances,
+		const aclhip_pose_buffer_consumers* consumers, const void* poses, uint64_t pose_stride_bytes)
+	{
+		if (consumers == nullptr)
+			return fail(context, ACLHIP_ERROR_INVALID_ARGUMENT, "null pose buffer consumers");
+		if (local_poses == nullptr)
+			return fail(context, ACLHIP_ERROR_INVALID_ARGUMENT, "null local pose buffer");
+		if (consumers->skeleton == 0 && consumers->instance_skeletons == nullptr)
+			return fail(context, ACLHIP_ERROR_INVALID_ARGUMENT, "pose buffer consumers name a skeleton or a list of skeletons");
+		if (consumers->additive_format > ACLHIP_ADDITIVE_ADDITIVE1)
+			return fail(context, ACLHIP_ERROR_INVALID_ARGUMENT, "unknown additive format %u", consumers->additive_format);
+		const bool has_additive = consumers->additive_format != ACLHIP_ADDITIVE_NONE;
+		if (consumers->object_space == 0 && !has_additive)
+			return fail(context, ACLHIP_ERROR_INVALID_ARGUMENT, "neither object_space nor an additive format: nothing to do");
+		if (has_additive != (consumers->additive_poses != nullptr))
+			return fail(context, ACLHIP_ERROR_INVALID_ARGUMENT, "an additive format and an additive pose buffer come together");
+		if (consumers->bounds != nullptr && consumers->object_space == 0)
+			return fail(context, ACLHIP_ERROR_INVALID_ARGUMENT, "pose bounds are taken in object space: a local space translation is not a position");
+		if (poses == nullptr && consumers->bounds == nullptr)
+			return fail(context, ACLHIP_ERROR_INVALID_ARGUMENT, "null output buffer without bounds");
+		if ((local_pose_stride_bytes & 15u) != 0 || (reinterpret_cast<uintptr_t>(local_poses) & 15u) != 0)
+			return fail(context, ACLHIP_ERROR_INVALID_ARGUMENT, "local pose buffer and stride must be 16 byte aligned");
+		if ((pose_stride_bytes & 15u) != 0 || (reinterpret_cast<uintptr_t>(poses) & 15u) != 0)
+			return fail(context, ACLHIP_ERROR_INVALID_ARGUMENT, "pose buffer and stride must be 16 byte aligned");
+		if (has_additive && ((consumers->additive_pose_stride_bytes & 15u) != 0 || (reinterpret_cast<uintptr_t>(consumers->additive_poses) & 15u) != 0))
+			return fail(context, ACLHIP_ERROR_INVALID_ARGUMENT, "additive pose buffer and stride must be 16 byte aligned");
+		if (consumers->reserved[0] != 0 || consumers->reserved[1] != 0)
+			return fail(context, ACLHIP_ERROR_INVALID_ARGUMENT, "the reserved fields of pose buffer consumers are 0");
+		if (consumers->bounds != nullptr)
+			if (const aclhip_status bounds_status = check_pose_bounds(context, consumers->bounds); bounds_status != ACLHIP_OK)
+				return bounds_status;
+		// the rows alone set the shape (an image's quads; the walk schedule's words come on top once the context is known: launch_pose_buffers)
+		const uint64_t shape_stride_bytes = poses != nullptr ? pose_stride_bytes : local_pose_stride_bytes;
+		const uint32_t row_transforms = uint32_t(std::min<uint64_t>(shape_stride_bytes / 48, 0xFFFFu));
+		const consumer_launch_shape shape = consumer_launch_shape_of(row_transforms * 3u, row_transforms, false, false, 0);
+		if (!shape.fits)
+			return fail(context, ACLHIP_ERROR_INVALID_ARGUMENT, "rows of %u transforms: too large for the pose consumers (%zu bytes of LDS per instance)", row_transforms, shape.lds_needed_bytes);
+		// in place is the one overlap allowed: a wave reads its own instance's rows and has them complete in LDS before it stores
+		if (poses != nullptr)
+		{
+			const bool in_place = poses == local_poses && pose_stride_bytes == local_pose_stride_bytes;
+			if (!in_place && pose_ranges_overlap(poses, pose_stride_bytes, local_poses, local_pose_stride_bytes, num_instances))
+				return fail(context, ACLHIP_ERROR_INVALID_ARGUMENT, "the output rows overlap the local pose rows: only poses == local_poses with equal strides (in place) is allowed");
+			if (has_additive && pose_ranges_overlap(poses, pose_stride_bytes, consumers->additive_poses, consumers->additive_pose_stride_bytes, num_instances))
+				return fail(context, ACLHIP_ERROR_INVALID_ARGUMENT, "the output rows overlap the additive pose rows");
+		}
+		return ACLHIP_OK;
+	}
+
+	template<bool kObjectSpace, uint32_t kBase, class... bounds_types>
+	aclhip_status launch_transform_poses_kernel(aclhip_context* context, const consumer_launch_shape& shape, uint32_t num_blocks, hipStream_t stream, const pose_buffer_launch& launch, const bounds_types&... bounds)
+	{
+		const auto kernel = transform_poses_kernel<kObjectSpace, kBase, bounds_types...>;
+		// above the default limit of dynamic LDS the kernel has to be told
+		if (shape.lds_bytes > 64 * 1024 - 128)
+			ACLHIP_CHECK_HIP(context, hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, int(k_consumer_lds_bytes)));
+		hipLaunchKernelGGL(kernel, dim3(num_blocks), dim3((1u << shape.log2_instances_per_block) * k_wave_size), shape.lds_bytes, stream, launch, bounds...);
+		ACLHIP_CHECK_HIP(context, hipGetLastError());
+		return ACLHIP_OK;
+	}
+
+	// The launch: shaped by its rows alone, like the mapped launch (registered clips play no part); the skeleton table is filled in under
+	// the registry lock, as launch_consumers does it; nothing is uploaded
+	aclhip_status launch_pose_buffers(aclhip_context* context, const void* local_poses, uint64_t local_pose_stride_bytes, uint32_t num_instances,
+		const aclhip_pose_buffer_consumers& consumers, void* poses, uint64_t pose_stride_bytes, hipStream_t stream)
+	{
+		std::shared_lock<std::shared_mutex> lock(context->mutex);		// see launch_tracks
+		if (context->d_skeletons == nullptr)
+			return fail(context, ACLHIP_ERROR_INVALID_ARGUMENT, "no skeleton was ever registered with this context");
+		const bool object_space = consumers.object_space != 0;
+		const bool has_additive = consumers.additive_format != ACLHIP_ADDITIVE_NONE;
+		const uint64_t shape_stride_bytes = poses != nullptr ? pose_stride_bytes : local_pose_stride_bytes;
+		const uint32_t row_transforms = uint32_t(std::min<uint64_t>(shape_stride_bytes / 48, 0xFFFFu));
+		const consumer_launch_shape shape = consumer_launch_shape_of(row_transforms * 3u, row_transforms, false, object_space, context->max_skeleton_hierarchy_words);
+		if (!shape.fits)
+			return fail(context, ACLHIP_ERROR_INVALID_ARGUMENT, "rows of %u transforms: too large for the pose consumers (%zu bytes of LDS per instance)", row_transforms, shape.lds_needed_bytes);
+		note_launch_stream(context, stream);
+
+		pose_buffer_launch launch = {};
+		launch.skeletons = context->d_skeletons;
+		launch.num_skeletons = ACLHIP_MAX_SKELETONS;
+		launch.skeleton = consumers.skeleton;
+		launch.instance_skeletons = consumers.instance_skeletons;
+		launch.local_poses = static_cast<const uint8_t*>(local_poses);
+		launch.local_pose_stride_bytes = local_pose_stride_bytes;
+		launch.additive_poses = has_additive ? static_cast<const uint8_t*>(consumers.additive_poses) : nullptr;
+		launch.additive_pose_stride_bytes = has_additive ? consumers.additive_pose_stride_bytes : 0;
+		launch.poses = static_cast<uint8_t*>(poses);
+		launch.pose_stride_bytes = pose_stride_bytes;
+		launch.num_instances = num_instances;
+		launch.additive_format = consumers.additive_format;
+		launch.lds_quads_per_image = shape.lds_quads_per_image;
+		launch.lds_bytes_per_instance = uint32_t(shape.lds_bytes_per_instance);
+		launch.packed_block_shape = shape.log2_instances_per_block | (shape.lds_schedule_words << 8);
+		launch.rejected_count = context->d_rejected;
+
+		const uint32_t instances_per_block = 1u << shape.log2_instances_per_block;
+		const uint32_t num_blocks = (num_instances + instances_per_block - 1) / instances_per_block;
+		// five instantiations: object / none, object / buffer, local / buffer, and the two object forms with bounds
+		if (consumers.bounds != nullptr)
+		{
+			const consumer_bounds_launch bounds = { static_cast<uint8_t*>(consumers.bounds->bounds), consumers.bounds->bone_flags };
+			return has_additive ? launch_transform_poses_kernel<true, k_consumer_base_buffer>(context, shape, num_blocks, stream, launch, bounds)
+				: launch_transform_poses_kernel<true, k_consumer_base_none>(context, shape, num_blocks, stream, launch, bounds);
+		}
+		if (!object_space)
+			return launch_transform_poses_kernel<false, k_consumer_base_buffer>(context, shape, num_blocks, stream, launch);
+		return has_additive ? launch_transform_poses_kernel<true, k_consumer_base_buffer>(context, shape, num_blocks, stream, launch)
+			: launch_transform_poses_kernel<true, k_consumer_base_none>(context, shape, num_blocks, stream, launch);
+	}
+}
+
+// include/aclhip.h states the definition. The argument checks need no device, come first and leave a message, with or without a context.
+extern "C" aclhip_status aclhip_transform_poses_batch(aclhip_context* context, const void* local_poses, uint64_t local_pose_stride_bytes, uint32_t num_instances,
+	const aclhip_pose_buffer_consumers* consumers, void* poses, uint64_t pose_stride_bytes, void* stream)
+{
+	const aclhip_status status = check_pose_buffer_consumers(context, local_poses, local_pose_stride_bytes, num_instances, consumers, poses, pose_stride_bytes);
+	if (status != ACLHIP_OK)
+		return status;
+	if (context == nullptr)
+		return fail(context, ACLHIP_ERROR_INVALID_ARGUMENT, "null context");
+	if (num_instances == 0)
+		return ACLHIP_OK;
+
+	device_guard guard(context->device);
+	return launch_pose_buffers(context, local_poses, local_pose_stride_bytes, num_instances, *consumers, poses, pose_stride_bytes, static_cast<hipStream_t>(stream));
+}

@@ -48,6 +48,7 @@ EXPORTED_SYMBOLS = [
     "aclhip_decompress_track_object_batch", "aclhip_decompress_bone_object_batch_mapped", "aclhip_plan_bone_chain",
     "aclhip_decompress_poses_batch_bounds",
     "aclhip_decompress_poses_batch_additive_weighted",
+    "aclhip_transform_poses_batch",
 ]
 
 
@@ -130,6 +131,14 @@ class AdditiveLayering(ctypes.Structure):
 class PoseBounds(ctypes.Structure):
     """aclhip_pose_bounds"""
     _fields_ = [("bounds", ctypes.c_void_p), ("bone_flags", ctypes.c_void_p), ("reserved", ctypes.c_uint64 * 2)]
+
+
+class PoseBufferConsumers(ctypes.Structure):
+    """aclhip_pose_buffer_consumers; `bounds` is the address of a PoseBounds the caller keeps alive (ctypes.addressof), or None"""
+    _fields_ = [
+        ("skeleton", ctypes.c_uint32), ("instance_skeletons", ctypes.c_void_p), ("object_space", ctypes.c_uint32), ("additive_format", ctypes.c_uint32),
+        ("additive_poses", ctypes.c_void_p), ("additive_pose_stride_bytes", ctypes.c_uint64), ("bounds", ctypes.c_void_p), ("reserved", ctypes.c_uint64 * 2),
+    ]
 
 
 BLEND_WEIGHTED, BLEND_LAYERED = 0, 1   # ACLHIP_BLEND_WEIGHTED / ACLHIP_BLEND_LAYERED
@@ -322,6 +331,7 @@ def load_library():
                                                          ctypes.POINTER(PoseBounds), vp, u64, vp]
     lib.aclhip_decompress_poses_batch_additive_weighted.argtypes = [vp, vp, vp, u32, pparams, ctypes.POINTER(PoseConsumers), ctypes.POINTER(PoseMapping),
                                                                     ctypes.POINTER(AdditiveLayering), vp, u64, vp]
+    lib.aclhip_transform_poses_batch.argtypes = [vp, vp, u64, u32, ctypes.POINTER(PoseBufferConsumers), vp, u64, vp]
     _lib = lib
     return lib
 
@@ -763,6 +773,15 @@ class Context:
         self._check(self._lib.aclhip_decompress_poses_batch_bounds(self._handle, clips_ptr, times_ptr, num_instances, ctypes.byref(params), ctypes.byref(consumers),
                                                                   ctypes.byref(mapping) if mapping is not None else None, ctypes.byref(masking) if masking is not None else None,
                                                                   ctypes.byref(bounds) if bounds is not None else None, poses_ptr, pose_stride_bytes, stream))
+
+    def transform_poses_batch(self, local_poses_ptr, local_pose_stride_bytes, num_instances, consumers, poses_ptr, pose_stride_bytes, bounds=None, stream=None):
+        """aclhip_transform_poses_batch: apply_additive_to_base and / or local_to_object_space over the caller's QVV48 rows (device addresses);
+        poses_ptr == local_poses_ptr with equal strides: in place. `consumers` is a PoseBufferConsumers; `bounds` (a PoseBounds) is put into
+        it for the call. poses_ptr None (with bounds): the boxes alone."""
+        if bounds is not None:
+            consumers.bounds = ctypes.addressof(bounds)
+        self._check(self._lib.aclhip_transform_poses_batch(self._handle, local_poses_ptr, local_pose_stride_bytes, num_instances,
+                                                           ctypes.byref(consumers) if consumers is not None else None, poses_ptr, pose_stride_bytes, stream))
 
     def decompress_poses_mapped(self, clips, sample_times, skeletons, maps, num_bones, additive_format=ADDITIVE_NONE, object_space=False, base_clips=None,
                                 base_sample_times=None, base_maps=None, base_poses=None, params=None, out=None, instance_rounding=None, instance_looping=None,

@@ -1070,6 +1070,65 @@ aclhip_status aclhip_decompress_poses_batch_bounds(aclhip_context* context, cons
 	const aclhip_blend_masking* masking /* NULL, or with mapping + blend */, const aclhip_pose_bounds* bounds, void* poses /* may be NULL */,
 	uint64_t pose_stride_bytes, void* stream);
 
+/* ---- pose buffers: object space and additive apply over a caller's poses ---------------------------
+ * Every consumer above is fused into a decode. A caller who changes the local pose between the decode and the walk -- IK, look-at, ragdoll
+ * or physics blending, procedural secondary motion, retargeting, or a pose it produced itself -- decodes with
+ * aclhip_decompress_tracks_batch(_mapped) and hands the rows to aclhip_transform_poses_batch: the reference's free functions over pose
+ * arrays, acl::local_to_object_space (compression/transform_pose_utils.h:42-56: "it is safe for both pose buffers to alias") and
+ * acl::apply_additive_to_base (core/additive_utils.h:150-160), with the walk schedule, rtm::qvv_mul's matrix route and the normalize of
+ * the fused launches. (ABI version 6 still: an added struct and an added function, no existing struct changed.) */
+typedef struct aclhip_pose_buffer_consumers
+{
+	aclhip_skeleton skeleton;					/* for every instance when instance_skeletons is NULL */
+	const aclhip_skeleton* instance_skeletons;	/* DEVICE [num_instances] or NULL */
+	uint32_t object_space;						/* 1: local_to_object_space with the skeleton's parents */
+	uint32_t additive_format;					/* aclhip_additive_format; NONE: no additive buffer */
+	const void* additive_poses;					/* DEVICE or NULL: additive pose i at additive_poses + i * additive_pose_stride_bytes, QVV48, skeleton order */
+	uint64_t additive_pose_stride_bytes;
+	const aclhip_pose_bounds* bounds;			/* NULL, or one box per instance as aclhip_decompress_poses_batch_bounds defines it (object_space only) */
+	uint64_t reserved[2];						/* 0 */
+} aclhip_pose_buffer_consumers;
+
+/* The definition. Instance i has skeleton S (consumers->skeleton, or instance_skeletons[i]) with B bones and parents P.
+ *   1. L is the B QVV48 records at local_poses + i * local_pose_stride_bytes.
+ *   2. With an additive format, A is the B records of the additive row and L'[b] = apply_additive_to_base(format, base = L[b],
+ *      additive = A[b]) per bone: the operation the base_poses path of aclhip_decompress_poses_batch performs, with the roles of the two
+ *      buffers as named here (the caller's local pose is the base, the additive buffer is what a decode would have produced). Without
+ *      one, L' = L.
+ *   3. With object_space, row i is local_to_object_space(P, L'): roots are copied as they are; every other bone is
+ *      qvv_mul(child, object[parent]) -- rtm::qvv_mul's matrix route where a scale of either side is negative
+ *      (aclhip_get_negative_scale_count's rule, and that counter moves as it does for a launch with a base pose buffer) -- then
+ *      quat_normalize, the decoder's 1 / sqrt. Otherwise row i is L'.
+ *   The arithmetic is the correctly rounded one of the fused launches, bit for bit the oracle's; nothing is assumed about a caller's
+ * rotations or scales. The pads (the fourth float of a translation and of a scale): every transform that went through
+ * apply_additive_to_base or through the walk's qvv_mul is written with both pads 0, whatever the inputs held. What went through neither --
+ * a ROOT of an object_space launch without an additive buffer -- is copied whole, pads included: it keeps the bytes of L.
+ *   All B records are written; bytes of a row behind B * 48 are untouched.
+ *   In place: poses == local_poses with equal strides is allowed, and is the expected use -- a row is complete in LDS before any of it is
+ * stored, and no wave reads another instance's row. Any other overlap of the output range with the input range, and any overlap with the
+ * additive range, is ACLHIP_ERROR_INVALID_ARGUMENT; the host decides this from the three (pointer, stride, num_instances) ranges,
+ * [pointer, pointer + stride * num_instances).
+ *   Bounds (consumers->bounds): the same boxes, the same bone_flags, the same empty box and the same NaN rule as
+ * aclhip_decompress_poses_batch_bounds, over the rows this launch writes; poses == NULL gives the boxes alone.
+ *   Refused and counted (aclhip_get_rejected_instance_count), the row and the box untouched: an unknown or retired skeleton handle (0
+ * included); object_space on a skeleton without hierarchy; B * 48 larger than any of the strides in use (local_pose_stride_bytes,
+ * pose_stride_bytes when poses is set, additive_pose_stride_bytes with an additive format); B beyond the launch's LDS image. No instance
+ * reads or writes outside its rows, whatever instance_skeletons holds. A skeleton unregistered after the launch was enqueued is still served.
+ *   ACLHIP_ERROR_INVALID_ARGUMENT, decided before any device call, each with a message (with or without a context): consumers == NULL or
+ * local_poses == NULL; no skeleton at all (skeleton == 0 and instance_skeletons == NULL); object_space == 0 with
+ * ACLHIP_ADDITIVE_NONE (nothing to do); a format other than NONE without additive_poses, or the reverse; bounds without object_space;
+ * poses == NULL without bounds; pointers or strides that are not 16 byte aligned; reserved fields that are not 0; a bounds struct
+ * aclhip_decompress_poses_batch_bounds would refuse; a shape that does not fit 160 KiB of LDS; the overlaps above.
+ *   The launch's shape comes from the rows alone, as for the mapped launch: pose_stride_bytes / 48 slots per LDS image (and entries of
+ * bone_flags), or local_pose_stride_bytes / 48 when poses is NULL. Registered clips play no part. The launch goes on `stream`, can be
+ * captured into a graph, and uploads nothing.
+ *   Out of scope (nothing here precludes them): object_to_local_space; additive strength and blend masks on buffers; a blend of several
+ * buffers; QVV40 / QV32 rows; ACLHIP_CONSUMERS_FAST; the host convenience form; the C++ mirror in aclhip.hpp; instance lists.
+ *   What it costs: NOT MEASURED YET (tools/pose_buffers.py, profiles/pose_buffers.md; DESIGN.md 4.7 "Pose buffers"). */
+aclhip_status aclhip_transform_poses_batch(aclhip_context* context, const void* local_poses, uint64_t local_pose_stride_bytes,
+	uint32_t num_instances, const aclhip_pose_buffer_consumers* consumers, void* poses /* may be NULL with bounds */,
+	uint64_t pose_stride_bytes, void* stream);
+
 /* ---- multi-GPU ---------------------------------------------------------------------------------- */
 
 /* Decoding never needs a collective: every GPU decodes its own contiguous shard of the instance list. Only a
