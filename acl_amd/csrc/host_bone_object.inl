@@ -68,13 +68,13 @@ namespace
 		skeleton_launch device_mapping = {};
 		if (mapped)
 		{
-			if (context->d_skeletons == nullptr)
+			if (context->skeletons.d_records == nullptr)
 				return fail(context, ACLHIP_ERROR_INVALID_ARGUMENT, "no skeleton was ever registered with this context");
-			if (context->d_track_maps == nullptr)
+			if (context->track_maps.d_records == nullptr)
 				return fail(context, ACLHIP_ERROR_INVALID_ARGUMENT, "no track map was ever registered with this context");
-			device_mapping.skeletons = context->d_skeletons;
+			device_mapping.skeletons = context->skeletons.d_records;
 			device_mapping.num_skeletons = ACLHIP_MAX_SKELETONS;
-			device_mapping.maps = context->d_track_maps;
+			device_mapping.maps = context->track_maps.d_records;
 			device_mapping.num_maps = ACLHIP_MAX_TRACK_MAPS;
 			device_mapping.skeleton = mapping->skeleton;
 			device_mapping.map = mapping->map;

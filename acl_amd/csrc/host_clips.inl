@@ -1202,6 +1202,7 @@ extern "C" aclhip_status aclhip_unregister_clip(aclhip_context* context, aclhip_
 		aclhip_context::retired_item item;
 		item.clip_memory = context->clips[clip].device_memory;
 		item.hierarchy = context->clips[clip].d_hierarchy;
+		item.free_list = &context->free_slots;
 		item.slot = clip;
 		retire(context, std::move(item), context->d_clips + clip);
 	}

@@ -446,15 +446,98 @@ namespace
 		return shape;
 	}
 
-	// `mapping` (aclhip_decompress_poses_batch_mapped): skeleton space -- the launch is shaped by its rows alone (pose_stride_bytes / 48
-	// slots), the skeleton kernels take the mapping as their trailing argument. `masking` (aclhip_decompress_poses_batch_masked, with a
-	// mapping and a blend): the same launch through the masked kernels. `bounds` (aclhip_decompress_poses_batch_bounds, object space): the
+	// What the skeleton space launches (_mapped, _masked, _bounds with a mapping) check of their mapping, and the launch argument made of it
+	aclhip_status check_pose_mapping(aclhip_context* context, const aclhip_pose_consumers* consumers, const aclhip_pose_mapping* mapping)
+	{
+		if (mapping->skeleton == 0 && mapping->instance_skeletons == nullptr)
+			return fail(context, ACLHIP_ERROR_INVALID_ARGUMENT, "a pose mapping names a skeleton or a list of skeletons");
+		if (mapping->map == 0 && mapping->instance_maps == nullptr)
+			return fail(context, ACLHIP_ERROR_INVALID_ARGUMENT, "a pose mapping names a map or a list of maps");
+		if (consumers->num_blend_clips > 1 && mapping->blend_maps == nullptr)
+			return fail(context, ACLHIP_ERROR_INVALID_ARGUMENT, "a blend in skeleton space needs blend_maps");
+		const bool base_is_clip = consumers->additive_format != ACLHIP_ADDITIVE_NONE && consumers->base_clips != nullptr;
+		if (base_is_clip && mapping->base_maps == nullptr)
+			return fail(context, ACLHIP_ERROR_INVALID_ARGUMENT, "base clips in skeleton space need base_maps");
+		return ACLHIP_OK;
+	}
+
+	// (the tables and their capacities are filled in by launch_consumers, under the registry lock: the same goes for the mask table below)
+	skeleton_launch skeleton_launch_of(const aclhip_pose_consumers* consumers, const aclhip_pose_mapping* mapping)
+	{
+		const bool base_is_clip = consumers->additive_format != ACLHIP_ADDITIVE_NONE && consumers->base_clips != nullptr;
+		skeleton_launch launch = {};
+		launch.skeleton = mapping->skeleton;
+		launch.map = mapping->map;
+		launch.instance_skeletons = mapping->instance_skeletons;
+		launch.instance_maps = mapping->instance_maps;
+		launch.blend_maps = consumers->num_blend_clips > 1 ? mapping->blend_maps : nullptr;
+		launch.base_maps = base_is_clip ? mapping->base_maps : nullptr;
+		return launch;
+	}
+
+	// What the masked launches (_masked, _bounds with a masking) check of their masking, and the launch argument made of it
+	aclhip_status check_blend_masking(aclhip_context* context, const aclhip_pose_consumers* consumers, const aclhip_blend_masking* masking)
+	{
+		if (masking->mode > ACLHIP_BLEND_LAYERED)
+			return fail(context, ACLHIP_ERROR_INVALID_ARGUMENT, "unknown blend mode %u", masking->mode);
+		if (masking->reserved0 != 0 || masking->reserved[0] != 0 || masking->reserved[1] != 0)
+			return fail(context, ACLHIP_ERROR_INVALID_ARGUMENT, "the reserved fields of a blend masking are 0");
+		if (masking->instance_masks == nullptr)
+			return fail(context, ACLHIP_ERROR_INVALID_ARGUMENT, "a blend masking names a list of masks (entries may be 0)");
+		if (consumers->num_blend_clips < 2)
+			return fail(context, ACLHIP_ERROR_INVALID_ARGUMENT, "blend masks go with a blend: num_blend_clips is %u", consumers->num_blend_clips);
+		return ACLHIP_OK;
+	}
+
+	blend_mask_launch blend_mask_launch_of(const aclhip_blend_masking* masking)
+	{
+		blend_mask_launch launch = {};
+		launch.layered = masking->mode == ACLHIP_BLEND_LAYERED ? 1u : 0u;
+		launch.instance_masks = masking->instance_masks;
+		return launch;
+	}
+
+	// What every launch with bounds (_bounds, aclhip_transform_poses_batch) checks of the struct itself
+	aclhip_status check_pose_bounds(aclhip_context* context, const aclhip_pose_bounds* bounds)
+	{
+		if (bounds->bounds == nullptr || (reinterpret_cast<uintptr_t>(bounds->bounds) & 15u) != 0)
+			return fail(context, ACLHIP_ERROR_INVALID_ARGUMENT, "the bounds buffer must be set and 16 byte aligned");
+		if (bounds->reserved[0] != 0 || bounds->reserved[1] != 0)
+			return fail(context, ACLHIP_ERROR_INVALID_ARGUMENT, "the reserved fields of pose bounds are 0");
+		return ACLHIP_OK;
+	}
+
+	// What the additive launch checks of its layering
+	aclhip_status check_additive_layering(aclhip_context* context, const aclhip_pose_consumers* consumers, const aclhip_additive_layering* layering)
+	{
+		if (layering->instance_weights == nullptr && layering->instance_masks == nullptr)
+			return fail(context, ACLHIP_ERROR_INVALID_ARGUMENT, "an additive layering names instance_weights or instance_masks (without both it is aclhip_decompress_poses_batch_mapped)");
+		if (layering->reserved[0] != 0 || layering->reserved[1] != 0)
+			return fail(context, ACLHIP_ERROR_INVALID_ARGUMENT, "the reserved fields of an additive layering are 0");
+		if (consumers->additive_format == ACLHIP_ADDITIVE_NONE)
+			return fail(context, ACLHIP_ERROR_INVALID_ARGUMENT, "an additive layering goes with an additive format: additive_format is NONE");
+		return ACLHIP_OK;
+	}
+
+	// What a pose consumer launch takes on top of the plain one, each on its own switch: the device side of the caller's aclhip_pose_mapping,
+	// aclhip_blend_masking, aclhip_pose_bounds and aclhip_additive_layering (launch_pose_consumers makes them)
+	struct consumer_launch_extras
+	{
+		bool mapped = false, masked = false, bounded = false, layered = false;
+		skeleton_launch mapping = {};
+		blend_mask_launch masking = {};
+		consumer_bounds_launch bounds = {};
+		additive_strength_launch layering = {};
+	};
+
+	// `extras.mapped` (aclhip_decompress_poses_batch_mapped): skeleton space -- the launch is shaped by its rows alone (pose_stride_bytes / 48
+	// slots), the skeleton kernels take the mapping as their trailing argument. `masked` (aclhip_decompress_poses_batch_masked, with a
+	// mapping and a blend): the same launch through the masked kernels. `bounded` (aclhip_decompress_poses_batch_bounds, object space): the
 	// same launch through the bounds instantiations, a box per instance on top of the rows -- or in their place, `poses` may then be null.
-	// `layering` (aclhip_decompress_poses_batch_additive_weighted, with a mapping and an additive format, without masking and bounds): the
+	// `layered` (aclhip_decompress_poses_batch_additive_weighted, with a mapping and an additive format, without masking and bounds): the
 	// mapped launch through the additive kernels, a strength per (instance, slot) on the additive pose.
 	aclhip_status launch_consumers(aclhip_context* context, const aclhip_clip* clips, const float* sample_times, uint32_t num_instances,
-		const decode_params& params, const aclhip_pose_consumers& consumers, void* poses, uint64_t pose_stride_bytes, hipStream_t stream, const skeleton_launch* mapping = nullptr,
-		const blend_mask_launch* masking = nullptr, const consumer_bounds_launch* bounds = nullptr, const additive_strength_launch* layering = nullptr)
+		const decode_params& params, const aclhip_pose_consumers& consumers, void* poses, uint64_t pose_stride_bytes, hipStream_t stream, consumer_launch_extras extras)
 	{
 		if (consumers.additive_format > ACLHIP_ADDITIVE_ADDITIVE1)
 			return fail(context, ACLHIP_ERROR_INVALID_ARGUMENT, "unknown additive format %u", consumers.additive_format);
@@ -476,53 +559,46 @@ namespace
 			return fail(context, ACLHIP_ERROR_INVALID_ARGUMENT, "pose consumers take the track_writer's default sub-track modes, no per track rounding, normalization != always");
 
 		std::shared_lock<std::shared_mutex> lock(context->mutex);		// see launch_tracks
-		skeleton_launch device_mapping = {};
-		if (mapping != nullptr)
+		if (extras.mapped)
 		{
-			if (context->d_skeletons == nullptr)
+			if (context->skeletons.d_records == nullptr)
 				return fail(context, ACLHIP_ERROR_INVALID_ARGUMENT, "no skeleton was ever registered with this context");
-			if (context->d_track_maps == nullptr)
+			if (context->track_maps.d_records == nullptr)
 				return fail(context, ACLHIP_ERROR_INVALID_ARGUMENT, "no track map was ever registered with this context");
-			device_mapping = *mapping;
-			device_mapping.skeletons = context->d_skeletons;
-			device_mapping.num_skeletons = ACLHIP_MAX_SKELETONS;
-			device_mapping.maps = context->d_track_maps;
-			device_mapping.num_maps = ACLHIP_MAX_TRACK_MAPS;
+			extras.mapping.skeletons = context->skeletons.d_records;
+			extras.mapping.num_skeletons = ACLHIP_MAX_SKELETONS;
+			extras.mapping.maps = context->track_maps.d_records;
+			extras.mapping.num_maps = ACLHIP_MAX_TRACK_MAPS;
 		}
 		// a masking or a layering with the context's mask table (no mask registered yet: a table of no records -- every handle but the null
 		// handle is refused in the kernel)
-		const auto with_mask_table = [&](auto launch_argument)
+		const auto with_mask_table = [&](auto& launch_argument)
 		{
-			launch_argument.masks = context->d_blend_masks;
-			launch_argument.num_masks = context->d_blend_masks != nullptr ? ACLHIP_MAX_BLEND_MASKS : 0u;
-			return launch_argument;
+			launch_argument.masks = context->blend_masks.d_records;
+			launch_argument.num_masks = context->blend_masks.d_records != nullptr ? ACLHIP_MAX_BLEND_MASKS : 0u;
 		};
-		blend_mask_launch device_masking = {};
-		if (masking != nullptr)
+		if (extras.masked)
 		{
-			if (mapping == nullptr || !blend)
+			if (!extras.mapped || !blend)
 				return fail(context, ACLHIP_ERROR_INVALID_ARGUMENT, "blend masks go with a blend in skeleton space");
-			device_masking = with_mask_table(*masking);
+			with_mask_table(extras.masking);
 		}
-		additive_strength_launch device_layering = {};
-		if (layering != nullptr)
+		if (extras.layered)
 		{
-			if (mapping == nullptr || !has_base || masking != nullptr || bounds != nullptr)
+			if (!extras.mapped || !has_base || extras.masked || extras.bounded)
 				return fail(context, ACLHIP_ERROR_INVALID_ARGUMENT, "an additive layering goes with an additive format in skeleton space, without blend masks and bounds");
-			device_layering = with_mask_table(*layering);
+			with_mask_table(extras.layering);
 		}
 		note_launch_stream(context, stream);
 
-		// one wave per instance, the whole pose (its base, its hierarchy) in LDS; as many instances per workgroup (a power of two, at
-		// most 8, 4 unless told otherwise: measured best) as leave room for three workgroups per CU: the object space walk packs its lanes with instances of one workgroup
 		// No clip with a scale other than 1 registered, no base to combine with: every scale of every pose is 1, in local and in object
 		// space -- the LDS images hold rotation | translation (32 of a transform's 48 bytes: half as many poses again per CU) and the
 		// scales are written on the way out
-		const bool unit_scale = mapping == nullptr && !has_base && !blend && consumers.object_space != 0 && context->num_scaled_clips == 0 && path_knob("ACLHIP_CONSUMER_KEEP_SCALE") == nullptr;
+		const bool unit_scale = !extras.mapped && !has_base && !blend && consumers.object_space != 0 && context->num_scaled_clips == 0 && path_knob("ACLHIP_CONSUMER_KEEP_SCALE") == nullptr;
 		// (sized for the BATCH like every pose launch: no pose of it is larger than its row, pose_launch_shape_of in host_launch.inl --
 		// one 3 500-bone asset in the registry does not take object space away from the 100-bone characters)
 		// (skeleton space: the slots of a row, whatever clips are registered -- a clip may have more tracks than the skeleton has bones)
-		const uint32_t batch_quads = mapping != nullptr ? uint32_t(std::min<uint64_t>(pose_stride_bytes / 48, 0xFFFFu)) * 3u : batch_pose_quads(context, ACLHIP_LAYOUT_QVV48, pose_stride_bytes);
+		const uint32_t batch_quads = extras.mapped ? uint32_t(std::min<uint64_t>(pose_stride_bytes / 48, 0xFFFFu)) * 3u : batch_pose_quads(context, ACLHIP_LAYOUT_QVV48, pose_stride_bytes);
 		const uint32_t image_quads = unit_scale ? batch_quads / 3 * 2 : batch_quads;
 		// additive0 / additive1 combine sub-track with sub-track: the base clip is decoded into the instance's image and the additive clip
 		// onto it by one wave; the relative format (a qvv_mul) needs both poses whole: a second wave, a second image
@@ -530,13 +606,10 @@ namespace
 		const bool fused_base = base_is_clip && !blend && consumers.additive_format != ACLHIP_ADDITIVE_RELATIVE && lab_knob("ACLHIP_CONSUMER_TWO_IMAGES") == nullptr;
 		const bool two_waves = base_is_clip && !fused_base;
 		const consumer_launch_shape shape = consumer_launch_shape_of(image_quads, batch_quads / 3, two_waves, consumers.object_space != 0,
-			mapping != nullptr ? context->max_skeleton_hierarchy_words : context->max_hierarchy_words);
+			extras.mapped ? context->max_skeleton_hierarchy_words : context->max_hierarchy_words);
 		if (!shape.fits)
 			return fail(context, ACLHIP_ERROR_INVALID_ARGUMENT, "poses of %u transforms (the pose stride, the largest registered clip): too large for the pose consumers (%zu bytes of LDS per instance)", batch_quads / 3, shape.lds_needed_bytes);
-		constexpr size_t k_lds_bytes = k_consumer_lds_bytes;
-		const uint32_t lds_quads_per_image = shape.lds_quads_per_image, lds_schedule_words = shape.lds_schedule_words, log2_instances_per_block = shape.log2_instances_per_block;
-		const size_t lds_bytes_per_instance = shape.lds_bytes_per_instance, lds_bytes = shape.lds_bytes;
-		const uint32_t instances_per_block = 1u << log2_instances_per_block;
+		const uint32_t instances_per_block = 1u << shape.log2_instances_per_block;
 		const uint32_t waves_per_block = instances_per_block * (two_waves ? 2 : 1);
 		const uint32_t num_blocks = (num_instances + instances_per_block - 1) / instances_per_block;
 
@@ -557,18 +630,18 @@ namespace
 		// rtm::qvv_mul's matrix route (negative scales) is compiled into the launches that can meet one: a registered clip whose scale
 		// sub-tracks may decode below zero, or a base the library knows nothing about (a caller's pose buffer)
 		// (skeleton space: the reference pose fills slots -- like a clip whose scales registration has looked at)
-		const bool mirrored = context->num_negative_scale_clips != 0 || (has_base && !base_is_clip) || (mapping != nullptr && context->num_negative_scale_skeletons != 0);
+		const bool mirrored = context->num_negative_scale_clips != 0 || (has_base && !base_is_clip) || (extras.mapped && context->num_negative_scale_skeletons != 0);
 		const bool object_space = consumers.object_space != 0;
 		// above the default limit of dynamic LDS the kernel has to be told; trailing: the mapping, the masking
 		const auto launch = [&](auto kernel, const auto&... trailing) -> aclhip_status
 		{
 			if (kernel == nullptr)
 				return fail(context, ACLHIP_ERROR_INVALID_ARGUMENT, "no pose consumer kernel for base kind %u", base_kind);
-			if (lds_bytes > 64 * 1024 - 128)
-				ACLHIP_CHECK_HIP(context, hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, int(k_lds_bytes)));
-			hipLaunchKernelGGL(kernel, dim3(num_blocks), dim3(waves_per_block * k_wave_size), lds_bytes, stream,
+			if (shape.lds_bytes > 64 * 1024 - 128)
+				ACLHIP_CHECK_HIP(context, hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, int(k_consumer_lds_bytes)));
+			hipLaunchKernelGGL(kernel, dim3(num_blocks), dim3(waves_per_block * k_wave_size), shape.lds_bytes, stream,
 				context->d_clips, context->d_clips_capacity, clips, sample_times, num_instances, params, device_consumers,
-				static_cast<uint8_t*>(poses), pose_stride_bytes, lds_quads_per_image, uint32_t(lds_bytes_per_instance), log2_instances_per_block | (lds_schedule_words << 8), context->d_rejected, trailing...);
+				static_cast<uint8_t*>(poses), pose_stride_bytes, shape.lds_quads_per_image, uint32_t(shape.lds_bytes_per_instance), shape.log2_instances_per_block | (shape.lds_schedule_words << 8), context->d_rejected, trailing...);
 			ACLHIP_CHECK_HIP(context, hipGetLastError());
 			return ACLHIP_OK;
 		};
@@ -579,15 +652,15 @@ namespace
 		{
 			using kernels = pose_consumer_kernels<std::decay_t<decltype(trailing)>...>;
 			if constexpr (!kernels::with_bounds)		// (a layering comes without bounds: refused above)
-				if (layering != nullptr)
+				if (extras.layered)
 					return launch(pose_consumer_kernel_of<typename kernels::additive_type>(object_space, base_kind, mirrored, blend, [](auto space, auto base, auto route, auto blended)
-						{ return kernels::template additive<space(), base(), route(), blended()>(); }), device_mapping, device_layering);
-			if (masking != nullptr)
+						{ return kernels::template additive<space(), base(), route(), blended()>(); }), extras.mapping, extras.layering);
+			if (extras.masked)
 				return launch(pose_consumer_kernel_of<typename kernels::masked_type, true>(object_space, base_kind, mirrored, [](auto space, auto base, auto route)
-					{ return kernels::template masked<space(), base(), route()>(); }), device_mapping, device_masking, trailing...);
-			if (mapping != nullptr)
+					{ return kernels::template masked<space(), base(), route()>(); }), extras.mapping, extras.masking, trailing...);
+			if (extras.mapped)
 				return launch(pose_consumer_kernel_of<typename kernels::skeleton_type>(object_space, base_kind, mirrored, blend, [](auto space, auto base, auto route, auto blended)
-					{ return kernels::template skeleton<space(), base(), route(), blended()>(); }), device_mapping, trailing...);
+					{ return kernels::template skeleton<space(), base(), route(), blended()>(); }), extras.mapping, trailing...);
 			// one instantiation per (object space, kind of base, matrix route); rotation | translation images: object space without a base only
 			if (unit_scale)
 				return launch(fast ? kernels::template unmapped<true, k_consumer_base_none, true, false, false, true>() : kernels::template unmapped<true, k_consumer_base_none, true, false>(), trailing...);
@@ -600,28 +673,71 @@ namespace
 			return launch(pose_consumer_kernel_of<typename kernels::unmapped_type, false>(object_space, base_kind, mirrored, [](auto space, auto base, auto route)
 				{ return kernels::template unmapped<space(), base(), false, route()>(); }), trailing...);
 		};
-		return bounds != nullptr ? launch_with(*bounds) : launch_with();
+		return extras.bounded ? launch_with(extras.bounds) : launch_with();
+	}
+
+	// The caller's side of consumer_launch_extras: the optional structs of the pose launch entry points, null where an entry point has none
+	struct pose_launch_structs
+	{
+		const aclhip_pose_mapping* mapping;
+		const aclhip_blend_masking* masking;
+		const aclhip_pose_bounds* bounds;
+		const aclhip_additive_layering* layering;
+	};
+
+	// The one front of the five pose launch entry points (aclhip_decompress_poses_batch, _mapped, _masked, _bounds, _additive_weighted): each
+	// says which of the four structs it requires and calls this. The argument checks that need no device come first and leave a message,
+	// with or without a context -- the structs, the lists and the pose buffer (null with bounds: the boxes alone), the null context last.
+	aclhip_status launch_pose_consumers(aclhip_context* context, const aclhip_clip* clips, const float* sample_times, uint32_t num_instances,
+		const aclhip_decompress_params* params, const aclhip_pose_consumers* consumers, const pose_launch_structs& structs, void* poses, uint64_t pose_stride_bytes, void* stream)
+	{
+		if (consumers == nullptr)
+			return fail(context, ACLHIP_ERROR_INVALID_ARGUMENT, "null consumers");
+		aclhip_status status = structs.bounds != nullptr ? check_pose_bounds(context, structs.bounds) : ACLHIP_OK;
+		if (status == ACLHIP_OK && structs.bounds != nullptr && consumers->object_space == 0)
+			return fail(context, ACLHIP_ERROR_INVALID_ARGUMENT, "pose bounds are taken in object space: a local space translation is not a position");
+		if (status == ACLHIP_OK && structs.masking != nullptr)
+			status = structs.mapping != nullptr ? check_blend_masking(context, consumers, structs.masking) : fail(context, ACLHIP_ERROR_INVALID_ARGUMENT, "blend masks go with a pose mapping");
+		if (status == ACLHIP_OK && structs.layering != nullptr)
+			status = check_additive_layering(context, consumers, structs.layering);
+		if (status == ACLHIP_OK && structs.mapping != nullptr)
+			status = check_pose_mapping(context, consumers, structs.mapping);
+		if (status == ACLHIP_OK)
+			status = check_batch_arguments(context, clips, sample_times, num_instances, poses, pose_stride_bytes, structs.bounds != nullptr);
+		if (status != ACLHIP_OK || num_instances == 0)
+			return status;
+
+		decode_params device_params;
+		status = resolve_params(context, params, device_params);
+		if (status != ACLHIP_OK)
+			return status;
+
+		consumer_launch_extras extras;
+		extras.mapped = structs.mapping != nullptr;
+		if (extras.mapped)
+			extras.mapping = skeleton_launch_of(consumers, structs.mapping);
+		extras.masked = structs.masking != nullptr;
+		if (extras.masked)
+			extras.masking = blend_mask_launch_of(structs.masking);
+		extras.bounded = structs.bounds != nullptr;
+		if (extras.bounded)
+			extras.bounds = { static_cast<uint8_t*>(structs.bounds->bounds), structs.bounds->bone_flags };
+		extras.layered = structs.layering != nullptr;
+		if (extras.layered)
+		{
+			extras.layering.instance_weights = structs.layering->instance_weights;
+			extras.layering.instance_masks = structs.layering->instance_masks;
+		}
+
+		device_guard guard(context->device);
+		return launch_consumers(context, clips, sample_times, num_instances, device_params, *consumers, poses, pose_stride_bytes, static_cast<hipStream_t>(stream), extras);
 	}
 }
 
 extern "C" aclhip_status aclhip_decompress_poses_batch(aclhip_context* context, const aclhip_clip* clips, const float* sample_times, uint32_t num_instances,
 	const aclhip_decompress_params* params, const aclhip_pose_consumers* consumers, void* poses, uint64_t pose_stride_bytes, void* stream)
 {
-	aclhip_status status = check_batch_arguments(context, clips, sample_times, num_instances, poses, pose_stride_bytes);
-	if (status != ACLHIP_OK)
-		return status;
-	if (consumers == nullptr)
-		return fail(context, ACLHIP_ERROR_INVALID_ARGUMENT, "null consumers");
-	if (num_instances == 0)
-		return ACLHIP_OK;
-
-	decode_params device_params;
-	status = resolve_params(context, params, device_params);
-	if (status != ACLHIP_OK)
-		return status;
-
-	device_guard guard(context->device);
-	return launch_consumers(context, clips, sample_times, num_instances, device_params, *consumers, poses, pose_stride_bytes, static_cast<hipStream_t>(stream));
+	return launch_pose_consumers(context, clips, sample_times, num_instances, params, consumers, {}, poses, pose_stride_bytes, stream);
 }
 
 namespace

@@ -59,6 +59,36 @@ namespace
 	};
 }
 
+namespace
+{
+	// The handles of one kind of object that launches name by number: track maps, skeletons and blend masks (host_track_maps.inl,
+	// host_skeletons.inl, host_blend_masks.inl; used three times in aclhip_context). The device table is ONE allocation of kCapacity records
+	// made at the first registration: it never moves and never grows (launches in flight and captured hipGraphs hold its address), a
+	// cleared record is an unknown handle, and record 0 is never handed out (0 is the null handle). What works on a table -- take_handle,
+	// publish_handle, unregister_handle, get_handle_info -- is below, behind the upload and retire functions it calls.
+	// `extras_type`: what the host keeps per entry beyond the info and the payload (the skeleton's share of a walk schedule).
+	struct no_entry_extras {};
+	template<class record_type, class info_type, uint32_t kCapacity, class extras_type = no_entry_extras>
+	struct handle_table
+	{
+		using record = record_type;
+		static constexpr uint32_t capacity = kCapacity;
+		struct entry : extras_type { bool in_use = false; info_type info = {}; uint8_t* device_memory = nullptr; };		// device_memory: the payload, a piece of a clip slab
+		const char* const noun;		// "track map": the unknown track map handle 7, the track map table holds ...
+		const char* const plural;	// ... 16383 "maps"
+		std::vector<entry> entries;
+		std::vector<uint32_t> free_slots;
+		record* d_records = nullptr;
+
+		handle_table(const char* noun_, const char* plural_) : noun(noun_), plural(plural_) {}
+		// the live entry of a handle; null for the null handle, a handle out of range and a retired one
+		const entry* find(uint32_t handle) const { return handle != 0 && handle < entries.size() && entries[handle].in_use ? &entries[handle] : nullptr; }
+		void give_back(uint32_t slot) { free_slots.push_back(slot); }		// a registration that failed behind take_handle
+		void free_device_table() { if (d_records != nullptr) (void)hipFree(d_records); }		// aclhip_destroy
+	};
+	struct skeleton_entry_extras { uint32_t* d_hierarchy = nullptr; bool negative_scale = false; };
+}
+
 struct aclhip_context
 {
 	int device = 0;
@@ -71,26 +101,13 @@ struct aclhip_context
 	std::vector<host_clip> clips;
 	std::vector<uint32_t> free_slots;
 	std::vector<host_database> databases;
-	// Track maps (aclhip_register_track_map, host_track_maps.inl). The device table is ONE allocation of k_track_map_table_entries
-	// records made at the first registration: it never moves and never grows. Record 0 is never handed out (0 is the null map handle).
-	struct track_map_entry { bool in_use = false; aclhip_track_map_info info = {}; uint8_t* device_memory = nullptr; };
-	std::vector<track_map_entry> track_maps;
-	std::vector<uint32_t> free_map_slots;
-	device_track_map* d_track_maps = nullptr;
-	// Skeletons (aclhip_register_skeleton, host_skeletons.inl): what the slot space of a set of track maps means. The same lifetime:
-	// one table of ACLHIP_MAX_SKELETONS records made at the first registration, record 0 never handed out.
-	struct skeleton_entry { bool in_use = false; aclhip_skeleton_info info = {}; uint8_t* device_memory = nullptr; uint32_t* d_hierarchy = nullptr; bool negative_scale = false; };
-	std::vector<skeleton_entry> skeletons;
-	std::vector<uint32_t> free_skeleton_slots;
-	device_skeleton* d_skeletons = nullptr;
+	// The three handle tables (handle_table, above): track maps (aclhip_register_track_map), skeletons (aclhip_register_skeleton: what the
+	// slot space of a set of track maps means) and blend masks (aclhip_register_blend_mask: a weight per slot for the skeleton space blends)
+	handle_table<device_track_map, aclhip_track_map_info, ACLHIP_MAX_TRACK_MAPS> track_maps{ "track map", "maps" };
+	handle_table<device_skeleton, aclhip_skeleton_info, ACLHIP_MAX_SKELETONS, skeleton_entry_extras> skeletons{ "skeleton", "skeletons" };
+	handle_table<device_blend_mask, aclhip_blend_mask_info, ACLHIP_MAX_BLEND_MASKS> blend_masks{ "blend mask", "masks" };
 	uint32_t num_negative_scale_skeletons = 0;		// live skeletons whose reference pose holds a negative scale (see num_negative_scale_clips)
 	uint32_t max_skeleton_hierarchy_words = 0;		// largest walk schedule a skeleton was ever registered with (a longer one is walked from global memory)
-	// Blend masks (aclhip_register_blend_mask, host_blend_masks.inl): a weight per slot for the skeleton space blends. The same lifetime:
-	// one table of ACLHIP_MAX_BLEND_MASKS records made at the first registration, record 0 never handed out.
-	struct blend_mask_entry { bool in_use = false; aclhip_blend_mask_info info = {}; uint8_t* device_memory = nullptr; };
-	std::vector<blend_mask_entry> blend_masks;
-	std::vector<uint32_t> free_blend_mask_slots;
-	device_blend_mask* d_blend_masks = nullptr;
 	device_clip* d_clips = nullptr;
 	uint32_t d_clips_capacity = 0;
 	unsigned long long* d_rejected = nullptr;	// [0] instances the kernels refused, [1] transforms of the pose consumers that met a negative scale
@@ -131,10 +148,8 @@ struct aclhip_context
 		std::vector<hipEvent_t> events;				// one per launch stream, recorded when the item was retired
 		void* clip_memory = nullptr;				// a piece of a slab
 		uint32_t* hierarchy = nullptr;				// a walk schedule image (shared images are reference counted)
-		uint32_t slot = ACLHIP_INVALID_HANDLE;		// clip handle that becomes reusable
-		uint32_t map_slot = ACLHIP_INVALID_HANDLE;	// track map handle that becomes reusable
-		uint32_t skeleton_slot = ACLHIP_INVALID_HANDLE;	// skeleton handle that becomes reusable
-		uint32_t blend_mask_slot = ACLHIP_INVALID_HANDLE;	// blend mask handle that becomes reusable
+		std::vector<uint32_t>* free_list = nullptr;	// the handle that becomes reusable: where it goes back to (the clips' free_slots, a handle table's) ...
+		uint32_t slot = ACLHIP_INVALID_HANDLE;		// ... and the handle
 		uint8_t* database_memory[6] = { nullptr, nullptr, nullptr, nullptr, nullptr, nullptr };		// hipMalloc'ed pieces of a database
 		uint8_t* database_pinned[4] = { nullptr, nullptr, nullptr, nullptr };		// bulk data x 2, patch mirrors x 2
 		void* device_memory = nullptr;				// any other hipMalloc'ed piece
@@ -357,7 +372,7 @@ namespace
 	// `record_to_clear` (a clip's record in the device table, or null): cleared on the context's retire stream BEHIND those same points --
 	// launches already enqueued still find the clip (kernels read the record when they execute, not when they are enqueued), launches
 	// that execute later are refused -- and the item is not recycled before the clear has happened. Nobody waits on the host.
-	// (`record_bytes`: a record of the clip table, or of the track map table)
+	// (`record_bytes`: a record of the clip table, or of a handle table)
 	void retire(aclhip_context* context, aclhip_context::retired_item&& item, void* record_to_clear = nullptr, size_t record_bytes = sizeof(device_clip))
 	{
 		for (size_t i = 0; i < context->launch_streams.size();)
@@ -431,14 +446,8 @@ namespace
 				free_clip_memory(context, item.clip_memory);
 			if (item.hierarchy != nullptr)
 				release_hierarchy(context, item.hierarchy);
-			if (item.slot != ACLHIP_INVALID_HANDLE)
-				context->free_slots.push_back(item.slot);
-			if (item.map_slot != ACLHIP_INVALID_HANDLE)
-				context->free_map_slots.push_back(item.map_slot);
-			if (item.skeleton_slot != ACLHIP_INVALID_HANDLE)
-				context->free_skeleton_slots.push_back(item.skeleton_slot);
-			if (item.blend_mask_slot != ACLHIP_INVALID_HANDLE)
-				context->free_blend_mask_slots.push_back(item.blend_mask_slot);
+			if (item.free_list != nullptr)
+				item.free_list->push_back(item.slot);
 			for (uint8_t* memory : item.database_memory)
 				if (memory != nullptr)
 					(void)hipFree(memory);
@@ -554,6 +563,89 @@ namespace
 		}
 		~device_guard() { if (switched) (void)hipSetDevice(previous); }
 	};
+
+	// ---- handle tables (handle_table, above) -------------------------------------------------------------------------------------------
+	// take_handle and publish_handle are called by a registration that holds the registry lock and has made the context's device current;
+	// unregister_handle and get_handle_info are whole calls and take the lock themselves.
+
+	// A handle for a registration that is about to upload. Makes the device table at the first call; a recycled slot before a new one.
+	template<class table_type>
+	aclhip_status take_handle(aclhip_context* context, table_type& table, uint32_t& out_slot)
+	{
+		if (table.d_records == nullptr)
+		{
+			const size_t table_bytes = sizeof(typename table_type::record) * table_type::capacity;
+			typename table_type::record* records = nullptr;
+			ACLHIP_CHECK_HIP(context, hipMalloc(reinterpret_cast<void**>(&records), table_bytes));
+			hipError_t zeroed = hipMemsetAsync(records, 0, table_bytes, context->copy_stream);
+			if (zeroed == hipSuccess)
+				zeroed = hipStreamSynchronize(context->copy_stream);
+			if (zeroed != hipSuccess)
+			{
+				(void)hipFree(records);
+				ACLHIP_CHECK_HIP(context, zeroed);
+			}
+			table.d_records = records;
+			table.entries.resize(1);		// handle 0: none
+		}
+		if (!table.free_slots.empty())
+		{
+			out_slot = table.free_slots.back();
+			table.free_slots.pop_back();
+			return ACLHIP_OK;
+		}
+		if (table.entries.size() >= table_type::capacity)
+			return fail(context, ACLHIP_ERROR_OUT_OF_MEMORY, "the %s table holds %u %s", table.noun, table_type::capacity - 1, table.plural);
+		out_slot = uint32_t(table.entries.size());
+		table.entries.emplace_back();
+		return ACLHIP_OK;
+	}
+
+	// Publishes the object of `slot`: the caller has staged the uploads of its payload, the record goes behind them (one stream: in order),
+	// the calling thread waits for its copies and the entry becomes live. false: an upload failed -- slot and payload are the caller's to give back.
+	template<class table_type, class info_type>
+	bool publish_handle(aclhip_context* context, table_type& table, uint32_t slot, const typename table_type::record& record, size_t& staging_used, const info_type& info, uint8_t* device_memory)
+	{
+		if (!stage_upload(context, table.d_records + slot, &record, sizeof(record), staging_used) || !finish_uploads(context))
+			return false;
+		table.entries[slot].in_use = true;
+		table.entries[slot].info = info;
+		table.entries[slot].device_memory = device_memory;
+		return true;
+	}
+
+	// Stream ordered, nobody waits (aclhip_unregister_clip): the record is cleared behind the launches already enqueued; the payload, what
+	// `and_retire(entry, item)` adds to the item, and the handle are recycled once both have happened.
+	struct retire_nothing_else { template<class entry_type> void operator()(const entry_type&, aclhip_context::retired_item&) const {} };
+	template<class table_type, class function_type = retire_nothing_else>
+	aclhip_status unregister_handle(aclhip_context* context, table_type& table, uint32_t handle, function_type and_retire = function_type())
+	{
+		std::lock_guard<std::shared_mutex> lock(context->mutex);
+		if (table.find(handle) == nullptr)
+			return fail(context, ACLHIP_ERROR_INVALID_ARGUMENT, "unknown %s handle %u", table.noun, handle);
+
+		device_guard guard(context->device);
+		collect_retired(context, false);
+		aclhip_context::retired_item item;
+		item.clip_memory = table.entries[handle].device_memory;
+		item.free_list = &table.free_slots;
+		item.slot = handle;
+		and_retire(table.entries[handle], item);
+		retire(context, std::move(item), table.d_records + handle, sizeof(typename table_type::record));
+		table.entries[handle] = {};
+		return ACLHIP_OK;
+	}
+
+	template<class table_type, class info_type>
+	aclhip_status get_handle_info(const aclhip_context* context, const table_type& table, uint32_t handle, info_type* out_info)
+	{
+		std::shared_lock<std::shared_mutex> lock(const_cast<aclhip_context*>(context)->mutex);
+		const auto* entry = table.find(handle);
+		if (entry == nullptr)
+			return fail(context, ACLHIP_ERROR_INVALID_ARGUMENT, "unknown %s handle %u", table.noun, handle);
+		*out_info = entry->info;
+		return ACLHIP_OK;
+	}
 
 	// compressed_tracks::is_valid (core/impl/compressed_tracks.impl.h:278-301) + bounds checks so that a decode can never read outside the blob
 	// Scalar track lists: every offset of the scalar_tracks_header and the whole animated stream must lie inside the buffer
@@ -1032,12 +1124,9 @@ extern "C" void aclhip_destroy(aclhip_context* context)
 			(void)hipFree(context->d_clips);
 		if (context->d_rejected != nullptr)
 			(void)hipFree(context->d_rejected);
-		if (context->d_track_maps != nullptr)
-			(void)hipFree(context->d_track_maps);
-		if (context->d_skeletons != nullptr)
-			(void)hipFree(context->d_skeletons);
-		if (context->d_blend_masks != nullptr)
-			(void)hipFree(context->d_blend_masks);
+		context->track_maps.free_device_table();
+		context->skeletons.free_device_table();
+		context->blend_masks.free_device_table();
 		for (const aclhip_context::order_scratch& scratch : context->order_scratches)
 		{
 			(void)hipFree(scratch.bins);

@@ -146,14 +146,17 @@ namespace
 		return ACLHIP_OK;
 	}
 
-	aclhip_status check_batch_arguments(aclhip_context* context, const void* clips, const void* sample_times, uint32_t num_instances, const void* out, uint64_t pose_stride_bytes)
+	// What every batch launch checks of its lists and its output buffer. Needs no device and leaves a message, with or without a context: the
+	// null context is the last thing refused. `out_may_be_null`: a launch that writes something else as well (the bounds of the pose consumers)
+	aclhip_status check_batch_arguments(aclhip_context* context, const void* clips, const void* sample_times, uint32_t num_instances, const void* out, uint64_t pose_stride_bytes,
+		bool out_may_be_null = false)
 	{
-		if (context == nullptr)
-			return ACLHIP_ERROR_INVALID_ARGUMENT;
-		if (num_instances != 0 && (clips == nullptr || sample_times == nullptr || out == nullptr))
-			return fail(context, ACLHIP_ERROR_INVALID_ARGUMENT, "null instance list or output buffer");
+		if (num_instances != 0 && (clips == nullptr || sample_times == nullptr || (out == nullptr && !out_may_be_null)))
+			return fail(context, ACLHIP_ERROR_INVALID_ARGUMENT, out_may_be_null ? "null instance list" : "null instance list or output buffer");
 		if ((pose_stride_bytes & 15u) != 0 || (reinterpret_cast<uintptr_t>(out) & 15u) != 0)
 			return fail(context, ACLHIP_ERROR_INVALID_ARGUMENT, "pose buffer and stride must be 16 byte aligned");
+		if (context == nullptr)
+			return fail(context, ACLHIP_ERROR_INVALID_ARGUMENT, "null context");
 		return ACLHIP_OK;
 	}
 }

@@ -15,6 +15,19 @@ namespace
 		return a_begin < end_of(b, b_stride) && b_begin < end_of(a, a_stride);
 	}
 
+	// The rows alone set the shape of the launch (the output rows when there are any): an image's quads, and the words of the walk schedule on
+	// top of them once the context is known (launch_pose_buffers; the argument check asks without them). Refuses rows that do not fit.
+	aclhip_status pose_buffer_launch_shape_of(aclhip_context* context, const void* poses, uint64_t pose_stride_bytes, uint64_t local_pose_stride_bytes, bool object_space,
+		uint32_t max_hierarchy_words, consumer_launch_shape& out_shape)
+	{
+		const uint64_t shape_stride_bytes = poses != nullptr ? pose_stride_bytes : local_pose_stride_bytes;
+		const uint32_t row_transforms = uint32_t(std::min<uint64_t>(shape_stride_bytes / 48, 0xFFFFu));
+		out_shape = consumer_launch_shape_of(row_transforms * 3u, row_transforms, false, object_space, max_hierarchy_words);
+		if (!out_shape.fits)
+			return fail(context, ACLHIP_ERROR_INVALID_ARGUMENT, "rows of %u transforms: too large for the pose consumers (%zu bytes of LDS per instance)", row_transforms, out_shape.lds_needed_bytes);
+		return ACLHIP_OK;
+	}
+
 	// What aclhip_transform_poses_batch checks of its arguments before any device call; every refusal leaves a message, with or without a context
 	aclhip_status check_pose_buffer_consumers(aclhip_context* context, const void* local_poses, uint64_t local_pose_stride_bytes, uint32_t num_instances,
 		const aclhip_pose_buffer_consumers* consumers, const void* poses, uint64_t pose_stride_bytes)
@@ -47,12 +60,9 @@ namespace
 		if (consumers->bounds != nullptr)
 			if (const aclhip_status bounds_status = check_pose_bounds(context, consumers->bounds); bounds_status != ACLHIP_OK)
 				return bounds_status;
-		// the rows alone set the shape (an image's quads; the walk schedule's words come on top once the context is known: launch_pose_buffers)
-		const uint64_t shape_stride_bytes = poses != nullptr ? pose_stride_bytes : local_pose_stride_bytes;
-		const uint32_t row_transforms = uint32_t(std::min<uint64_t>(shape_stride_bytes / 48, 0xFFFFu));
-		const consumer_launch_shape shape = consumer_launch_shape_of(row_transforms * 3u, row_transforms, false, false, 0);
-		if (!shape.fits)
-			return fail(context, ACLHIP_ERROR_INVALID_ARGUMENT, "rows of %u transforms: too large for the pose consumers (%zu bytes of LDS per instance)", row_transforms, shape.lds_needed_bytes);
+		consumer_launch_shape shape;
+		if (const aclhip_status shape_status = pose_buffer_launch_shape_of(context, poses, pose_stride_bytes, local_pose_stride_bytes, false, 0, shape); shape_status != ACLHIP_OK)
+			return shape_status;
 		// in place is the one overlap allowed: a wave reads its own instance's rows and has them complete in LDS before it stores
 		if (poses != nullptr)
 		{
@@ -83,19 +93,17 @@ namespace
 		const aclhip_pose_buffer_consumers& consumers, void* poses, uint64_t pose_stride_bytes, hipStream_t stream)
 	{
 		std::shared_lock<std::shared_mutex> lock(context->mutex);		// see launch_tracks
-		if (context->d_skeletons == nullptr)
+		if (context->skeletons.d_records == nullptr)
 			return fail(context, ACLHIP_ERROR_INVALID_ARGUMENT, "no skeleton was ever registered with this context");
 		const bool object_space = consumers.object_space != 0;
 		const bool has_additive = consumers.additive_format != ACLHIP_ADDITIVE_NONE;
-		const uint64_t shape_stride_bytes = poses != nullptr ? pose_stride_bytes : local_pose_stride_bytes;
-		const uint32_t row_transforms = uint32_t(std::min<uint64_t>(shape_stride_bytes / 48, 0xFFFFu));
-		const consumer_launch_shape shape = consumer_launch_shape_of(row_transforms * 3u, row_transforms, false, object_space, context->max_skeleton_hierarchy_words);
-		if (!shape.fits)
-			return fail(context, ACLHIP_ERROR_INVALID_ARGUMENT, "rows of %u transforms: too large for the pose consumers (%zu bytes of LDS per instance)", row_transforms, shape.lds_needed_bytes);
+		consumer_launch_shape shape;
+		if (const aclhip_status shape_status = pose_buffer_launch_shape_of(context, poses, pose_stride_bytes, local_pose_stride_bytes, object_space, context->max_skeleton_hierarchy_words, shape); shape_status != ACLHIP_OK)
+			return shape_status;
 		note_launch_stream(context, stream);
 
 		pose_buffer_launch launch = {};
-		launch.skeletons = context->d_skeletons;
+		launch.skeletons = context->skeletons.d_records;
 		launch.num_skeletons = ACLHIP_MAX_SKELETONS;
 		launch.skeleton = consumers.skeleton;
 		launch.instance_skeletons = consumers.instance_skeletons;

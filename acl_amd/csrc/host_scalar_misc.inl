@@ -569,7 +569,7 @@ extern "C" aclhip_status aclhip_time_decompress_poses_batch(aclhip_context* cont
 	ACLHIP_CHECK_HIP(context, hipEventCreate(&stop));
 	ACLHIP_CHECK_HIP(context, hipEventRecord(start, hip_stream));
 	for (uint32_t i = 0; i < repeats && status == ACLHIP_OK; ++i)
-		status = launch_consumers(context, clips, sample_times, num_instances, device_params, *consumers, poses, pose_stride_bytes, hip_stream);
+		status = launch_consumers(context, clips, sample_times, num_instances, device_params, *consumers, poses, pose_stride_bytes, hip_stream, consumer_launch_extras());
 	ACLHIP_CHECK_HIP(context, hipEventRecord(stop, hip_stream));
 	ACLHIP_CHECK_HIP(context, hipEventSynchronize(stop));
 	float elapsed_ms = 0.0f;

@@ -1,6 +1,6 @@
 // host_track_maps.inl -- part of aclhip.hip (one translation unit; included there, in this order, not compiled on its own).
-// Host side: track maps (track_writer::write_*(track_index, value), core/track_writer.h: the writer chooses the destination) and the
-// mapped pose launch.
+// Host side: track maps (track_writer::write_*(track_index, value), core/track_writer.h: the writer chooses the destination) -- what
+// registration checks, the record and its image; the handles are a handle_table's (host_context.inl) -- and the mapped pose launch.
 
 namespace
 {
@@ -103,43 +103,15 @@ extern "C" aclhip_status aclhip_register_track_map(aclhip_context* context, cons
 		device_guard guard(context->device);
 		collect_retired(context, false);
 
-		if (context->d_track_maps == nullptr)
-		{
-			// once: the table never moves and never grows (a cleared record is an unknown map)
-			device_track_map* table = nullptr;
-			ACLHIP_CHECK_HIP(context, hipMalloc(reinterpret_cast<void**>(&table), sizeof(device_track_map) * ACLHIP_MAX_TRACK_MAPS));
-			hipError_t zeroed = hipMemsetAsync(table, 0, sizeof(device_track_map) * ACLHIP_MAX_TRACK_MAPS, context->copy_stream);
-			if (zeroed == hipSuccess)
-				zeroed = hipStreamSynchronize(context->copy_stream);
-			if (zeroed != hipSuccess)
-			{
-				(void)hipFree(table);
-				ACLHIP_CHECK_HIP(context, zeroed);
-			}
-			context->d_track_maps = table;
-			context->track_maps.resize(1);		// handle 0: none
-		}
-
 		uint32_t slot;
-		if (!context->free_map_slots.empty())
-		{
-			slot = context->free_map_slots.back();
-			context->free_map_slots.pop_back();
-		}
-		else
-		{
-			if (context->track_maps.size() >= ACLHIP_MAX_TRACK_MAPS)
-				return fail(context, ACLHIP_ERROR_OUT_OF_MEMORY, "the track map table holds %u maps", ACLHIP_MAX_TRACK_MAPS - 1);
-			slot = uint32_t(context->track_maps.size());
-			context->track_maps.emplace_back();
-		}
-		const auto give_back = [&]() { context->free_map_slots.push_back(slot); };
+		if (const aclhip_status status = take_handle(context, context->track_maps, slot); status != ACLHIP_OK)
+			return status;
 
 		// (a piece of a clip slab, uploaded on the context's copy stream: no allocation call and no copy that would stall the device)
 		uint8_t* d_image = allocate_clip_memory(context, image.size() * sizeof(uint32_t));
 		if (d_image == nullptr)
 		{
-			give_back();
+			context->track_maps.give_back(slot);
 			return fail(context, ACLHIP_ERROR_OUT_OF_MEMORY, "allocating %zu bytes for the track map failed", image.size() * sizeof(uint32_t));
 		}
 		device_track_map record;
@@ -150,19 +122,14 @@ extern "C" aclhip_status aclhip_register_track_map(aclhip_context* context, cons
 		record.num_unmapped = info.num_unmapped_slots;
 		record.flags = (info.is_identity != 0 ? 1u : 0u) | (info.is_order_preserving != 0 ? 2u : 0u);
 		size_t staging_used = 0;
-		// the image first, the record that publishes it behind it (one stream: in order)
+		// the image first, the record that publishes it behind it
 		if (!stage_upload(context, d_image, image.data(), image.size() * sizeof(uint32_t), staging_used)
-			|| !stage_upload(context, context->d_track_maps + slot, &record, sizeof(record), staging_used)
-			|| !finish_uploads(context))
+			|| !publish_handle(context, context->track_maps, slot, record, staging_used, info, d_image))
 		{
 			free_clip_memory(context, d_image);
-			give_back();
+			context->track_maps.give_back(slot);
 			return fail(context, ACLHIP_ERROR_DEVICE, "uploading the track map failed");
 		}
-		aclhip_context::track_map_entry& entry = context->track_maps[slot];
-		entry.in_use = true;
-		entry.info = info;
-		entry.device_memory = d_image;
 		*out_map = slot;
 		return ACLHIP_OK;
 	});
@@ -172,33 +139,14 @@ extern "C" aclhip_status aclhip_unregister_track_map(aclhip_context* context, ac
 {
 	if (context == nullptr)
 		return ACLHIP_ERROR_INVALID_ARGUMENT;
-
-	std::lock_guard<std::shared_mutex> lock(context->mutex);
-	if (map == 0 || map >= context->track_maps.size() || !context->track_maps[map].in_use)
-		return fail(context, ACLHIP_ERROR_INVALID_ARGUMENT, "unknown track map handle %u", map);
-
-	device_guard guard(context->device);
-	collect_retired(context, false);
-	// stream ordered, nobody waits (aclhip_unregister_clip): the record is cleared behind the launches already enqueued, the image and the
-	// handle are recycled once both have happened
-	aclhip_context::retired_item item;
-	item.clip_memory = context->track_maps[map].device_memory;
-	item.map_slot = map;
-	retire(context, std::move(item), context->d_track_maps + map, sizeof(device_track_map));
-	context->track_maps[map] = aclhip_context::track_map_entry();
-	return ACLHIP_OK;
+	return unregister_handle(context, context->track_maps, map);
 }
 
 extern "C" aclhip_status aclhip_get_track_map_info(const aclhip_context* context, aclhip_track_map map, aclhip_track_map_info* out_info)
 {
 	if (context == nullptr || out_info == nullptr)
 		return ACLHIP_ERROR_INVALID_ARGUMENT;
-	aclhip_context* mutable_context = const_cast<aclhip_context*>(context);
-	std::shared_lock<std::shared_mutex> lock(mutable_context->mutex);
-	if (map == 0 || map >= context->track_maps.size() || !context->track_maps[map].in_use)
-		return fail(context, ACLHIP_ERROR_INVALID_ARGUMENT, "unknown track map handle %u", map);
-	*out_info = context->track_maps[map].info;
-	return ACLHIP_OK;
+	return get_handle_info(context, context->track_maps, map, out_info);
 }
 
 extern "C" aclhip_status aclhip_decompress_tracks_batch_mapped(aclhip_context* context, const aclhip_clip* clips, const float* sample_times, uint32_t num_instances,
@@ -230,7 +178,7 @@ extern "C" aclhip_status aclhip_decompress_tracks_batch_mapped(aclhip_context* c
 	device_guard guard(context->device);
 	hipStream_t stream = static_cast<hipStream_t>(stream_handle);
 	std::shared_lock<std::shared_mutex> lock(context->mutex);		// see launch_tracks
-	if (context->d_track_maps == nullptr)
+	if (context->track_maps.d_records == nullptr)
 		return fail(context, ACLHIP_ERROR_INVALID_ARGUMENT, "no track map was ever registered with this context");
 	note_launch_stream(context, stream);
 
@@ -243,7 +191,7 @@ extern "C" aclhip_status aclhip_decompress_tracks_batch_mapped(aclhip_context* c
 	const size_t lds_bytes = size_t(shape.lds_quads_per_wave) * 16 * k_waves_per_block;
 
 	mapped_launch launch;
-	launch.maps = context->d_track_maps;
+	launch.maps = context->track_maps.d_records;
 	launch.num_maps = ACLHIP_MAX_TRACK_MAPS;
 	launch.map = mapping->map;
 	launch.instance_maps = mapping->instance_maps;
