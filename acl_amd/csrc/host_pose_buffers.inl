@@ -1,5 +1,5 @@
 // host_pose_buffers.inl -- part of aclhip.hip (one translation unit; included there, in this order, not compiled on its own).
-// Host side: the pose consumers over a caller's pose buffers (aclhip_transform_poses_batch; kernels_pose_buffers.inl).
+// Host side: the pose consumers over a caller's pose buffers (aclhip_transform_poses_batch, aclhip_blend_poses_batch; kernels_pose_buffers.inl).
 
 namespace
 {
@@ -134,6 +134,135 @@ namespace
 		return has_additive ? launch_transform_poses_kernel<true, k_consumer_base_buffer>(context, shape, num_blocks, stream, launch)
 			: launch_transform_poses_kernel<true, k_consumer_base_none>(context, shape, num_blocks, stream, launch);
 	}
+
+	// ---- a blend of K caller pose buffers (aclhip_blend_poses_batch; blend_poses_kernel in kernels_pose_buffers.inl) ----------------------
+
+	// What aclhip_blend_poses_batch checks of its arguments before any device call; every refusal leaves a message, with or without a context
+	aclhip_status check_pose_buffer_blend(aclhip_context* context, const aclhip_pose_buffer_blend* blend, uint32_t num_instances, const void* poses, uint64_t pose_stride_bytes)
+	{
+		if (blend == nullptr)
+			return fail(context, ACLHIP_ERROR_INVALID_ARGUMENT, "null pose buffer blend");
+		const uint32_t num_buffers = blend->num_buffers;
+		if (num_buffers < 2 || num_buffers > ACLHIP_MAX_BLEND_CLIPS)
+			return fail(context, ACLHIP_ERROR_INVALID_ARGUMENT, "a blend of %u pose buffers: 2 to %u", num_buffers, ACLHIP_MAX_BLEND_CLIPS);
+		if (blend->mode > ACLHIP_BLEND_LAYERED)
+			return fail(context, ACLHIP_ERROR_INVALID_ARGUMENT, "unknown blend mode %u", blend->mode);
+		for (uint32_t k = 0; k < ACLHIP_MAX_BLEND_CLIPS; ++k)
+		{
+			if (k < num_buffers && blend->buffers[k] == nullptr)
+				return fail(context, ACLHIP_ERROR_INVALID_ARGUMENT, "pose buffer %u of the blend's %u is null", k, num_buffers);
+			if (k >= num_buffers && blend->buffers[k] != nullptr)
+				return fail(context, ACLHIP_ERROR_INVALID_ARGUMENT, "pose buffer %u is set in a blend of %u: entries behind the blend are null", k, num_buffers);
+		}
+		if (blend->weights == nullptr)
+			return fail(context, ACLHIP_ERROR_INVALID_ARGUMENT, "a pose buffer blend needs weights");
+		if (blend->skeleton == 0 && blend->instance_skeletons == nullptr)
+			return fail(context, ACLHIP_ERROR_INVALID_ARGUMENT, "a pose buffer blend names a skeleton or a list of skeletons");
+		if (blend->bounds != nullptr && blend->object_space == 0)
+			return fail(context, ACLHIP_ERROR_INVALID_ARGUMENT, "pose bounds are taken in object space: a local space translation is not a position");
+		if (poses == nullptr && blend->bounds == nullptr)
+			return fail(context, ACLHIP_ERROR_INVALID_ARGUMENT, "null output buffer without bounds");
+		for (uint32_t k = 0; k < num_buffers; ++k)
+			if ((blend->buffer_stride_bytes[k] & 15u) != 0 || (reinterpret_cast<uintptr_t>(blend->buffers[k]) & 15u) != 0)
+				return fail(context, ACLHIP_ERROR_INVALID_ARGUMENT, "pose buffer %u and its stride must be 16 byte aligned", k);
+		if ((pose_stride_bytes & 15u) != 0 || (reinterpret_cast<uintptr_t>(poses) & 15u) != 0)
+			return fail(context, ACLHIP_ERROR_INVALID_ARGUMENT, "pose buffer and stride must be 16 byte aligned");
+		if (blend->reserved0 != 0 || blend->reserved[0] != 0 || blend->reserved[1] != 0)
+			return fail(context, ACLHIP_ERROR_INVALID_ARGUMENT, "the reserved fields of a pose buffer blend are 0");
+		if (blend->bounds != nullptr)
+			if (const aclhip_status bounds_status = check_pose_bounds(context, blend->bounds); bounds_status != ACLHIP_OK)
+				return bounds_status;
+		consumer_launch_shape shape;
+		if (const aclhip_status shape_status = pose_buffer_launch_shape_of(context, poses, pose_stride_bytes, blend->buffer_stride_bytes[0], false, 0, shape); shape_status != ACLHIP_OK)
+			return shape_status;
+		// in place on ONE input is the one overlap allowed: a wave reads its own instance's rows and has the blend complete in LDS before it
+		// stores. The inputs are only read: they may overlap each other.
+		for (uint32_t k = 0; k < num_buffers && poses != nullptr; ++k)
+		{
+			const bool in_place = poses == blend->buffers[k] && pose_stride_bytes == blend->buffer_stride_bytes[k];
+			if (!in_place && pose_ranges_overlap(poses, pose_stride_bytes, blend->buffers[k], blend->buffer_stride_bytes[k], num_instances))
+				return fail(context, ACLHIP_ERROR_INVALID_ARGUMENT, "the output rows overlap the rows of pose buffer %u: only poses == buffers[k] with equal strides (in place) is allowed", k);
+		}
+		if (blend->bounds != nullptr)
+		{
+			const void* boxes = blend->bounds->bounds;
+			if (poses != nullptr && pose_ranges_overlap(boxes, 32, poses, pose_stride_bytes, num_instances))
+				return fail(context, ACLHIP_ERROR_INVALID_ARGUMENT, "the bounds overlap the output rows");
+			for (uint32_t k = 0; k < num_buffers; ++k)
+				if (pose_ranges_overlap(boxes, 32, blend->buffers[k], blend->buffer_stride_bytes[k], num_instances))
+					return fail(context, ACLHIP_ERROR_INVALID_ARGUMENT, "the bounds overlap the rows of pose buffer %u", k);
+		}
+		return ACLHIP_OK;
+	}
+
+	template<uint32_t kNumBuffers, bool kObjectSpace, class... bounds_types>
+	aclhip_status launch_blend_poses_kernel(aclhip_context* context, const consumer_launch_shape& shape, uint32_t num_blocks, hipStream_t stream, const pose_blend_launch& launch, const bounds_types&... bounds)
+	{
+		const auto kernel = blend_poses_kernel<kNumBuffers, kObjectSpace, bounds_types...>;
+		// above the default limit of dynamic LDS the kernel has to be told
+		if (shape.lds_bytes > 64 * 1024 - 128)
+			ACLHIP_CHECK_HIP(context, hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, int(k_consumer_lds_bytes)));
+		hipLaunchKernelGGL(kernel, dim3(num_blocks), dim3((1u << shape.log2_instances_per_block) * k_wave_size), shape.lds_bytes, stream, launch, bounds...);
+		ACLHIP_CHECK_HIP(context, hipGetLastError());
+		return ACLHIP_OK;
+	}
+
+	// (nine instantiations: K = 2, 3, 4 x local / object / object with bounds)
+	template<uint32_t kNumBuffers>
+	aclhip_status launch_blend_poses_of(aclhip_context* context, const consumer_launch_shape& shape, uint32_t num_blocks, hipStream_t stream, const pose_blend_launch& launch,
+		bool object_space, const aclhip_pose_bounds* pose_bounds)
+	{
+		if (pose_bounds != nullptr)
+			return launch_blend_poses_kernel<kNumBuffers, true>(context, shape, num_blocks, stream, launch, consumer_bounds_launch{ static_cast<uint8_t*>(pose_bounds->bounds), pose_bounds->bone_flags });
+		return object_space ? launch_blend_poses_kernel<kNumBuffers, true>(context, shape, num_blocks, stream, launch)
+			: launch_blend_poses_kernel<kNumBuffers, false>(context, shape, num_blocks, stream, launch);
+	}
+
+	// The launch: shaped by its rows alone, like launch_pose_buffers; the skeleton table and the mask table are filled in under the registry
+	// lock (no mask registered yet: a table of no records -- every handle but the null handle is refused in the kernel); nothing is uploaded
+	aclhip_status launch_pose_buffer_blend(aclhip_context* context, const aclhip_pose_buffer_blend& blend, uint32_t num_instances, void* poses, uint64_t pose_stride_bytes, hipStream_t stream)
+	{
+		std::shared_lock<std::shared_mutex> lock(context->mutex);		// see launch_tracks
+		if (context->skeletons.d_records == nullptr)
+			return fail(context, ACLHIP_ERROR_INVALID_ARGUMENT, "no skeleton was ever registered with this context");
+		const bool object_space = blend.object_space != 0;
+		consumer_launch_shape shape;
+		if (const aclhip_status shape_status = pose_buffer_launch_shape_of(context, poses, pose_stride_bytes, blend.buffer_stride_bytes[0], object_space, context->max_skeleton_hierarchy_words, shape); shape_status != ACLHIP_OK)
+			return shape_status;
+		note_launch_stream(context, stream);
+
+		pose_blend_launch launch = {};
+		launch.skeletons = context->skeletons.d_records;
+		launch.num_skeletons = ACLHIP_MAX_SKELETONS;
+		launch.skeleton = blend.skeleton;
+		launch.instance_skeletons = blend.instance_skeletons;
+		launch.masks = context->blend_masks.d_records;
+		launch.num_masks = context->blend_masks.d_records != nullptr ? ACLHIP_MAX_BLEND_MASKS : 0u;
+		launch.layered = blend.mode == ACLHIP_BLEND_LAYERED ? 1u : 0u;
+		launch.instance_masks = blend.instance_masks;
+		launch.weights = blend.weights;
+		for (uint32_t k = 0; k < blend.num_buffers; ++k)
+		{
+			launch.buffers[k] = static_cast<const uint8_t*>(blend.buffers[k]);
+			launch.buffer_stride_bytes[k] = blend.buffer_stride_bytes[k];
+		}
+		launch.poses = static_cast<uint8_t*>(poses);
+		launch.pose_stride_bytes = pose_stride_bytes;
+		launch.num_instances = num_instances;
+		launch.lds_quads_per_image = shape.lds_quads_per_image;
+		launch.lds_bytes_per_instance = uint32_t(shape.lds_bytes_per_instance);
+		launch.packed_block_shape = shape.log2_instances_per_block | (shape.lds_schedule_words << 8);
+		launch.rejected_count = context->d_rejected;
+
+		const uint32_t instances_per_block = 1u << shape.log2_instances_per_block;
+		const uint32_t num_blocks = (num_instances + instances_per_block - 1) / instances_per_block;
+		switch (blend.num_buffers)
+		{
+		case 2: return launch_blend_poses_of<2>(context, shape, num_blocks, stream, launch, object_space, blend.bounds);
+		case 3: return launch_blend_poses_of<3>(context, shape, num_blocks, stream, launch, object_space, blend.bounds);
+		default: return launch_blend_poses_of<4>(context, shape, num_blocks, stream, launch, object_space, blend.bounds);
+		}
+	}
 }
 
 // include/aclhip.h states the definition. The argument checks need no device, come first and leave a message, with or without a context.
@@ -150,4 +279,19 @@ extern "C" aclhip_status aclhip_transform_poses_batch(aclhip_context* context, c
 
 	device_guard guard(context->device);
 	return launch_pose_buffers(context, local_poses, local_pose_stride_bytes, num_instances, *consumers, poses, pose_stride_bytes, static_cast<hipStream_t>(stream));
+}
+
+// include/aclhip.h states the definition. The argument checks need no device, come first and leave a message, with or without a context.
+extern "C" aclhip_status aclhip_blend_poses_batch(aclhip_context* context, const aclhip_pose_buffer_blend* blend, uint32_t num_instances, void* poses, uint64_t pose_stride_bytes, void* stream)
+{
+	const aclhip_status status = check_pose_buffer_blend(context, blend, num_instances, poses, pose_stride_bytes);
+	if (status != ACLHIP_OK)
+		return status;
+	if (context == nullptr)
+		return fail(context, ACLHIP_ERROR_INVALID_ARGUMENT, "null context");
+	if (num_instances == 0)
+		return ACLHIP_OK;
+
+	device_guard guard(context->device);
+	return launch_pose_buffer_blend(context, *blend, num_instances, poses, pose_stride_bytes, static_cast<hipStream_t>(stream));
 }

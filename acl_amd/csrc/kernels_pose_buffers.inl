@@ -98,3 +98,177 @@
 				launch.additive_format, bounds.bounds, bounds.bone_flags },
 			wave, walk);
 	}
+
+	// ---- a blend of K caller pose buffers (aclhip_blend_poses_batch; include/aclhip.h states the definition) -----------------------------
+	// the kernel's argument: the K input buffers, the weights and masks of the blend, the output, the tables and the launch's shape
+	struct pose_blend_launch
+	{
+		const device_skeleton* skeletons;		// the context's skeleton table
+		uint32_t num_skeletons;					// its capacity
+		uint32_t skeleton;						// the launch's skeleton, when instance_skeletons is null
+		const uint32_t* instance_skeletons;		// [num_instances] or null
+		const device_blend_mask* masks;			// the context's mask table (null: no mask was ever registered)
+		uint32_t num_masks;						// its capacity
+		uint32_t layered;						// ACLHIP_BLEND_LAYERED
+		const uint32_t* instance_masks;			// [num_instances * K] or null: every handle 0
+		const float* weights;					// [num_instances * K]
+		const uint8_t* buffers[ACLHIP_MAX_BLEND_CLIPS];		// row i of buffer k at buffers[k] + i * buffer_stride_bytes[k]
+		uint64_t buffer_stride_bytes[ACLHIP_MAX_BLEND_CLIPS];
+		uint8_t* poses;							// null: the boxes alone (bounds instantiations)
+		uint64_t pose_stride_bytes;
+		uint32_t num_instances;
+		uint32_t lds_quads_per_image, lds_bytes_per_instance, packed_block_shape;		// as transform_poses_kernel takes them
+		unsigned long long* rejected_count;
+	};
+
+	// transform_poses_kernel's shape -- one wave64 per instance, images as consumer_wave_of lays them out, the skeleton's record on the scalar
+	// unit, the refusal in front of any load of a row -- with the image filled by the masked blend of K rows in the place of one row's DMA:
+	//   kNumBuffers    K, a template constant: the K loads of a quad are K independent global_load_dwordx4 in one basic block, requested
+	//                  together and waited for once (the launch is bound by its HBM reads), and the accumulation is a straight line over
+	//                  registers. The mode and "no masks" are wave uniform data instead: layer_weight's null mask pointer and a weight of
+	//                  1 - 0 for a layer that is not above give the definition's bits (slot_weight, kernels_skeleton.inl), at the price of
+	//                  a few scalar selects per pass -- 9 instantiations, not 36.
+	// Per quad of the row (lanes <-> consecutive quads): e_k = layer_weight's w or w * mask[slot] for every buffer, the weight of buffer k is
+	// e_k * r with r the product of (1 - e_j) over the layers above, top layer first, in layered mode and 1 in weighted mode -- what
+	// slot_weight computes, with every mask value read once instead of once per layer below it --; buffer 0 is scaled as
+	// blend_scale_image scales, buffers 1 .. K - 1 go through blend_accumulate in order, and the sum is written into the LDS image once.
+	// blend_normalize_rotations and finish_consumer_poses follow unchanged; short_exact is 0 and the matrix route is compiled in, as for
+	// every pose of a caller's.
+	// In place (poses == buffers[k], equal strides): a wave reads its own instance's rows and no other, and every row of the workgroup is
+	// complete in LDS -- behind the tail's barriers -- before the first quad of any of them is stored.
+	template<uint32_t kNumBuffers, bool kObjectSpace, class... bounds_types>
+	__global__ __launch_bounds__(k_consumer_max_instances * k_wave_size) void blend_poses_kernel(pose_blend_launch launch, bounds_types... bounds_launch)
+	{
+		static_assert(kNumBuffers >= 2 && kNumBuffers <= ACLHIP_MAX_BLEND_CLIPS, "a blend of 2 .. ACLHIP_MAX_BLEND_CLIPS buffers");
+		constexpr bool with_bounds = sizeof...(bounds_types) != 0;
+		// packed_block_shape: log2 of the instances per workgroup (bits 0..7) | words of LDS reserved for the shared walk schedule (bits 8..31)
+		const uint32_t log2_instances_per_block = launch.packed_block_shape & 0xFFu;
+		__shared__ consumer_walk_slots walk;		// (what the host subtracts from the LDS it may ask for: host_consumers.inl)
+		ACLHIP_PHASE_STAMP(0);
+
+		consumer_wave wave = consumer_wave_of(log2_instances_per_block, launch.lds_bytes_per_instance, launch.lds_quads_per_image);
+		const uint32_t lane = wave.lane, instance = wave.instance;
+
+		// (wave.num_tracks stays 0 for a wave without work: past the batch, refused instance)
+		if (instance < launch.num_instances)
+		{
+			// the skeleton's record on the scalar unit; record 0 is never handed out and a cleared record is an unknown or retired skeleton
+			const uint32_t skeleton_id = launch.instance_skeletons != nullptr ? as_constant(launch.instance_skeletons)[instance] : launch.skeleton;
+			const device_skeleton skeleton = load_skeleton_fields(launch.skeletons, skeleton_id < launch.num_skeletons ? skeleton_id : 0);
+			const uint32_t num_bones = skeleton.num_bones;
+			const uint64_t row_bytes = uint64_t(num_bones) * 48u;
+
+			// refused, wave uniform and in front of any load of a row: what transform_poses_kernel refuses, over every stride in use ...
+			bool refused = skeleton_id >= launch.num_skeletons || skeleton.reference_pose == nullptr || (kObjectSpace && skeleton.hierarchy == nullptr)
+				|| (launch.poses != nullptr && row_bytes > launch.pose_stride_bytes) || num_bones * 3u > launch.lds_quads_per_image;
+			// ... and every mask the instance names: the null handle, or a known mask of this skeleton's slot count. The instance's K
+			// weights and K mask images on the scalar unit, next to the check.
+			layer_weight layers[kNumBuffers];
+			const ACLHIP_CONSTANT float* const weights = as_constant(launch.weights) + size_t(instance) * kNumBuffers;
+			#pragma unroll
+			for (uint32_t k = 0; k < kNumBuffers; ++k)
+			{
+				refused = refused || row_bytes > launch.buffer_stride_bytes[k];
+				const uint32_t mask_id = launch.instance_masks != nullptr ? as_constant(launch.instance_masks)[size_t(instance) * kNumBuffers + k] : 0u;
+				const float* mask_image = nullptr;
+				if (mask_id != 0)
+				{
+					const ACLHIP_CONSTANT device_blend_mask* mask_record = as_constant(launch.masks) + (mask_id < launch.num_masks ? mask_id : 0);
+					if (mask_id >= launch.num_masks || mask_record->image == nullptr || mask_record->num_slots != num_bones)
+						refused = true;
+					else
+						mask_image = mask_record->image;
+				}
+				layers[k] = layer_weight{ as_constant(mask_image), weights[k] };
+			}
+
+			if (refused)
+			{
+				if (lane == 0)
+					atomicAdd(launch.rejected_count, 1ull);
+			}
+			else if (num_bones != 0)
+			{
+				wave.num_tracks = num_bones;
+				// the walk schedule first: its words travel global -> LDS while the rows do
+				if (kObjectSpace)
+					request_walk_schedule(skeleton.hierarchy, log2_instances_per_block, launch.packed_block_shape >> 8, wave.shared_schedule, wave.slot, lane, walk);
+				const f32x4* sources[kNumBuffers];
+				#pragma unroll
+				for (uint32_t k = 0; k < kNumBuffers; ++k)
+					sources[k] = reinterpret_cast<const f32x4*>(launch.buffers[k] + uint64_t(instance) * launch.buffer_stride_bytes[k]);
+				const bool layered = launch.layered != 0;
+				// (a mask of the instance's, when it has one: served instances only name known masks of num_bones slots)
+				const ACLHIP_CONSTANT float* some_mask = nullptr;
+				#pragma unroll
+				for (uint32_t k = 0; k < kNumBuffers; ++k)
+					some_mask = layers[k].mask != nullptr ? layers[k].mask : some_mask;
+				const uint32_t num_quads = num_bones * 3u;
+				for (uint32_t base = 0; base < num_quads; base += k_wave_size)
+				{
+					const uint32_t quad = base + lane;
+					if (quad < num_quads)
+					{
+						// all K quads requested together, then the mask values (the vector cache: a mask is a few hundred bytes every wave reads)
+						// and ONE wait for all of them
+						f32x4 values[kNumBuffers];
+						#pragma unroll
+						for (uint32_t k = 0; k < kNumBuffers; ++k)
+							values[k] = sources[k][quad];
+						const uint32_t slot = quad / 3u;
+						const uint32_t kind = quad - slot * 3u;
+						// e_k = layer_weight's w, or w * mask[slot]: with a mask among the K, K loads without a branch between them (a
+						// layer without one reads another layer's value and keeps its w: a branch per layer made each load wait for
+						// the one before it, and for the rows)
+						float opacities[kNumBuffers];
+						#pragma unroll
+						for (uint32_t k = 0; k < kNumBuffers; ++k)
+							opacities[k] = layers[k].weight;
+						if (some_mask != nullptr)
+						{
+							float mask_values[kNumBuffers];
+							#pragma unroll
+							for (uint32_t k = 0; k < kNumBuffers; ++k)
+								mask_values[k] = (layers[k].mask != nullptr ? layers[k].mask : some_mask)[slot];
+							// (a select between two values that both exist, not a branch around the product: a value that is used under
+							// a branch only has its load moved there, behind a wait for everything in front of it)
+							#pragma unroll
+							for (uint32_t k = 0; k < kNumBuffers; ++k)
+							{
+								const bool has_mask = layers[k].mask != nullptr;
+								const float weight = layers[k].weight, masked = weight * mask_values[k];
+								opacities[k] = has_mask ? masked : weight;
+							}
+						}
+						float slot_weights[kNumBuffers];
+						float rest = 1.0f;
+						#pragma unroll
+						for (uint32_t k = kNumBuffers; k-- != 0;)
+						{
+							slot_weights[k] = opacities[k] * rest;
+							rest = layered ? rest * (1.0f - opacities[k]) : 1.0f;
+						}
+						// buffer 0 times its weight (blend_scale_image), then the others onto it in order (blend_accumulate)
+						const float first_weight = slot_weights[0];
+						f32x4 accumulated{ values[0].x * first_weight, values[0].y * first_weight, values[0].z * first_weight, kind == 0 ? values[0].w * first_weight : 0.0f };
+						#pragma unroll
+						for (uint32_t k = 1; k < kNumBuffers; ++k)
+							accumulated = blend_accumulate(kind, accumulated, make_float4(values[k].x, values[k].y, values[k].z, values[k].w), slot_weights[k]);
+						wave.image[quad] = accumulated;
+					}
+				}
+				wave_lds_barrier();		// every quad has its sum
+				blend_normalize_rotations(wave.image, num_bones, lane);
+			}
+			else if constexpr (with_bounds)
+				wave.empty_pose = true;		// (a served instance whose pose has no transform)
+		}
+
+		// the image of every instance is complete
+		wave.short_exact = 0;
+		const consumer_bounds_launch bounds = bounds_launch_of(bounds_launch...);
+		finish_consumer_poses<kObjectSpace, k_consumer_base_none, false, true, false, with_bounds>(
+			consumer_tail_args{ launch.poses, launch.pose_stride_bytes, launch.lds_bytes_per_instance, log2_instances_per_block, launch.rejected_count, nullptr, 0,
+				ACLHIP_ADDITIVE_NONE, bounds.bounds, bounds.bone_flags },
+			wave, walk);
+	}

@@ -206,6 +206,8 @@
 	// order the definition multiplies (1 - e_j) in. A layer that is not there (fewer than three above, or weighted mode) has no mask and
 	// weight 0: r * (1 - 0) is r, so the product is the definition's bit for bit, and e * 1 is e. (Named fields, not arrays: an array of
 	// pointers here went to scratch in the instantiations with a second wave.)
+	// blend_poses_kernel (kernels_pose_buffers.inl) restates slot_weight's product as ONE running product over its K layers, top layer first,
+	// so that every mask value is read once: a change to the arithmetic here has to be made there as well.
 	struct layer_weight
 	{
 		const ACLHIP_CONSTANT float* mask;		// null: no mask, every slot 1

@@ -49,6 +49,7 @@ EXPORTED_SYMBOLS = [
     "aclhip_decompress_poses_batch_bounds",
     "aclhip_decompress_poses_batch_additive_weighted",
     "aclhip_transform_poses_batch",
+    "aclhip_blend_poses_batch",
 ]
 
 
@@ -138,6 +139,16 @@ class PoseBufferConsumers(ctypes.Structure):
     _fields_ = [
         ("skeleton", ctypes.c_uint32), ("instance_skeletons", ctypes.c_void_p), ("object_space", ctypes.c_uint32), ("additive_format", ctypes.c_uint32),
         ("additive_poses", ctypes.c_void_p), ("additive_pose_stride_bytes", ctypes.c_uint64), ("bounds", ctypes.c_void_p), ("reserved", ctypes.c_uint64 * 2),
+    ]
+
+
+class PoseBufferBlend(ctypes.Structure):
+    """aclhip_pose_buffer_blend; `buffers` are device addresses (entries behind num_buffers stay None), `bounds` is the address of a
+    PoseBounds the caller keeps alive (ctypes.addressof), or None"""
+    _fields_ = [
+        ("skeleton", ctypes.c_uint32), ("instance_skeletons", ctypes.c_void_p), ("num_buffers", ctypes.c_uint32), ("mode", ctypes.c_uint32),
+        ("buffers", ctypes.c_void_p * 4), ("buffer_stride_bytes", ctypes.c_uint64 * 4), ("weights", ctypes.c_void_p), ("instance_masks", ctypes.c_void_p),
+        ("object_space", ctypes.c_uint32), ("reserved0", ctypes.c_uint32), ("bounds", ctypes.c_void_p), ("reserved", ctypes.c_uint64 * 2),
     ]
 
 
@@ -332,6 +343,7 @@ def load_library():
     lib.aclhip_decompress_poses_batch_additive_weighted.argtypes = [vp, vp, vp, u32, pparams, ctypes.POINTER(PoseConsumers), ctypes.POINTER(PoseMapping),
                                                                     ctypes.POINTER(AdditiveLayering), vp, u64, vp]
     lib.aclhip_transform_poses_batch.argtypes = [vp, vp, u64, u32, ctypes.POINTER(PoseBufferConsumers), vp, u64, vp]
+    lib.aclhip_blend_poses_batch.argtypes = [vp, ctypes.POINTER(PoseBufferBlend), u32, vp, u64, vp]
     _lib = lib
     return lib
 
@@ -782,6 +794,14 @@ class Context:
             consumers.bounds = ctypes.addressof(bounds)
         self._check(self._lib.aclhip_transform_poses_batch(self._handle, local_poses_ptr, local_pose_stride_bytes, num_instances,
                                                            ctypes.byref(consumers) if consumers is not None else None, poses_ptr, pose_stride_bytes, stream))
+
+    def blend_poses_batch(self, blend, num_instances, poses_ptr, pose_stride_bytes, bounds=None, stream=None):
+        """aclhip_blend_poses_batch: the masked blend of the K QVV48 row buffers `blend` (a PoseBufferBlend, device addresses) names, in local
+        or object space; poses_ptr equal to one of the buffers with its stride: in place. `bounds` (a PoseBounds) is put into the struct for
+        the call. poses_ptr None (with bounds): the boxes alone."""
+        if bounds is not None:
+            blend.bounds = ctypes.addressof(bounds)
+        self._check(self._lib.aclhip_blend_poses_batch(self._handle, ctypes.byref(blend) if blend is not None else None, num_instances, poses_ptr, pose_stride_bytes, stream))
 
     def decompress_poses_mapped(self, clips, sample_times, skeletons, maps, num_bones, additive_format=ADDITIVE_NONE, object_space=False, base_clips=None,
                                 base_sample_times=None, base_maps=None, base_poses=None, params=None, out=None, instance_rounding=None, instance_looping=None,

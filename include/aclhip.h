@@ -1122,12 +1122,83 @@ typedef struct aclhip_pose_buffer_consumers
  *   The launch's shape comes from the rows alone, as for the mapped launch: pose_stride_bytes / 48 slots per LDS image (and entries of
  * bone_flags), or local_pose_stride_bytes / 48 when poses is NULL. Registered clips play no part. The launch goes on `stream`, can be
  * captured into a graph, and uploads nothing.
- *   Out of scope (nothing here precludes them): object_to_local_space; additive strength and blend masks on buffers; a blend of several
- * buffers; QVV40 / QV32 rows; ACLHIP_CONSUMERS_FAST; the host convenience form; the C++ mirror in aclhip.hpp; instance lists.
+ *   Out of scope (nothing here precludes them): object_to_local_space; additive strength on buffers; QVV40 / QV32 rows;
+ * ACLHIP_CONSUMERS_FAST; the host convenience form; the C++ mirror in aclhip.hpp; instance lists. (A blend of several buffers, with
+ * blend masks: aclhip_blend_poses_batch, below.)
  *   What it costs: NOT MEASURED YET (tools/pose_buffers.py, profiles/pose_buffers.md; DESIGN.md 4.7 "Pose buffers"). */
 aclhip_status aclhip_transform_poses_batch(aclhip_context* context, const void* local_poses, uint64_t local_pose_stride_bytes,
 	uint32_t num_instances, const aclhip_pose_buffer_consumers* consumers, void* poses /* may be NULL with bounds */,
 	uint64_t pose_stride_bytes, void* stream);
+
+/* ---- blended pose buffers: the masked blend over a caller's poses ----------------------------------
+ * The fused blend (aclhip_pose_consumers::num_blend_clips) and the fused masks (aclhip_decompress_poses_batch_masked) blend CLIPS. A
+ * ragdoll or physics pose blended with the animated one per bone (hips 0, arms 1), an IK corrected pose cross-faded back to the decoded
+ * one, a pose cached from a state machine's previous state blended with the pose just decoded: each has an operand that is no clip.
+ * aclhip_blend_poses_batch is that blend -- the same weights, the same masks, the same two modes, the same arithmetic -- over K rows the
+ * caller owns, with the object space walk and the boxes of aclhip_transform_poses_batch behind it in the same launch.
+ * (ABI version 6 still: an added struct and an added function, no existing struct changed.) */
+typedef struct aclhip_pose_buffer_blend
+{
+	aclhip_skeleton skeleton;					/* for every instance when instance_skeletons is NULL */
+	const aclhip_skeleton* instance_skeletons;	/* DEVICE [num_instances] or NULL */
+	uint32_t num_buffers;						/* K: 2 .. ACLHIP_MAX_BLEND_CLIPS */
+	uint32_t mode;								/* ACLHIP_BLEND_WEIGHTED / ACLHIP_BLEND_LAYERED */
+	const void* buffers[ACLHIP_MAX_BLEND_CLIPS];	/* DEVICE: pose i of buffer k at buffers[k] + i * buffer_stride_bytes[k], QVV48, skeleton order; entries >= K are NULL */
+	uint64_t buffer_stride_bytes[ACLHIP_MAX_BLEND_CLIPS];
+	const float* weights;						/* DEVICE [num_instances * K], laid out like blend_weights */
+	const aclhip_blend_mask* instance_masks;	/* DEVICE [num_instances * K] or NULL (no masks); entries may be 0 */
+	uint32_t object_space;						/* 1: local_to_object_space with the skeleton's parents behind the blend */
+	uint32_t reserved0;							/* 0 */
+	const aclhip_pose_bounds* bounds;			/* NULL, or boxes as aclhip_decompress_poses_batch_bounds defines them (object_space only) */
+	uint64_t reserved[2];						/* 0 */
+} aclhip_pose_buffer_blend;
+
+/* The definition. Instance i has skeleton S (blend->skeleton, or instance_skeletons[i]) with B bones and parents P; X_k is the B QVV48
+ * records at buffers[k] + i * buffer_stride_bytes[k].
+ *   1. The effective weight of buffer k at slot s is that of steps 1 and 2 of aclhip_blend_masking's definition, with
+ *      w_k = weights[i * K + k] and h_k = instance_masks[i * K + k] (0 when the array is NULL): e_k[s] in ACLHIP_BLEND_WEIGHTED,
+ *      e'_k[s] in ACLHIP_BLEND_LAYERED -- buffer 0 at the bottom, the product of (1 - e_j) taken from the top layer down. Layered mode
+ *      without masks is allowed: the opacity is then uniform per instance.
+ *   2. Rotation, translation and scale of slot s follow the blend's operation order (aclhip_pose_consumers) with that weight:
+ *      acc = X_0 * w, then for k = 1 .. K - 1 the sign biased accumulate against the running sum, quat_normalize at the end; fp32, one
+ *      IEEE operation at a time, never fused. Nothing is renormalized and nothing is skipped when a weight is 0; a slot whose weights are
+ *      ALL 0 gets what the arithmetic gives (0 / 0): the caller must avoid it, as under aclhip_blend_masking.
+ *   3. With object_space, row i is local_to_object_space(P, blended), exactly as step 3 of aclhip_transform_poses_batch defines it: roots
+ *      are copied, every other bone is qvv_mul(child, object[parent]) -- rtm::qvv_mul's matrix route where a scale of either side is
+ *      negative, and aclhip_get_negative_scale_count moves as it does for that launch -- then quat_normalize, the decoder's 1 / sqrt.
+ *      Otherwise row i is the blended local pose.
+ *   4. Every record written has both pads 0 (the blend writes them so, roots included), whatever the inputs held. All B records are
+ *      written; bytes of a row behind B * 48 are untouched.
+ *   In place: poses may be exactly ONE of the inputs (the pointer and the stride of some buffers[k]) -- the expected use, blending into
+ *   the animated buffer -- or disjoint from every input range. Any other overlap of the output range with an input range is
+ * ACLHIP_ERROR_INVALID_ARGUMENT; the host decides this from the (pointer, stride, num_instances) ranges,
+ * [pointer, pointer + stride * num_instances). The inputs are only read and may overlap each other freely. bounds->bounds
+ * (num_instances x 32 bytes) must not overlap an input or the output.
+ *   Bounds (blend->bounds): the same boxes, the same bone_flags, the same empty box and the same NaN rule as
+ * aclhip_decompress_poses_batch_bounds, over the rows this launch writes; poses == NULL gives the boxes alone.
+ *   Refused and counted (aclhip_get_rejected_instance_count), the row and the box untouched: an unknown or retired skeleton handle (0
+ * included); object_space on a skeleton without hierarchy; B * 48 larger than any of the strides in use (each of the K
+ * buffer_stride_bytes, pose_stride_bytes when poses is set); B beyond the launch's LDS image; on any of the K entries of the instance a
+ * mask handle that is unknown or retired, or mask.num_slots != B. The refusal comes in front of any load of a row: no instance reads or
+ * writes outside its own rows, whatever the device arrays hold. A skeleton or a mask unregistered after the launch was enqueued is still
+ * served.
+ *   ACLHIP_ERROR_INVALID_ARGUMENT, decided before any device call, each with a message (with or without a context): blend == NULL; K
+ * outside 2 .. ACLHIP_MAX_BLEND_CLIPS; an unknown mode; a NULL entry among the first K buffers or a non-NULL entry behind them;
+ * weights == NULL; no skeleton at all (skeleton == 0 and instance_skeletons == NULL); bounds without object_space; poses == NULL
+ * without bounds; a pointer or a stride that is not 16 byte aligned; reserved fields that are not 0; a bounds struct
+ * aclhip_decompress_poses_batch_bounds would refuse; a shape that does not fit 160 KiB of LDS; the overlaps above.
+ *   The launch's shape comes from the rows alone: pose_stride_bytes / 48 slots per LDS image (and entries of bone_flags), or
+ * buffer_stride_bytes[0] / 48 when poses is NULL. Registered clips play no part. The launch goes on `stream`, can be captured into a
+ * graph, and uploads nothing.
+ *   Out of scope (nothing here precludes them): an additive buffer or an additive strength in the same launch (chain
+ * aclhip_transform_poses_batch on the blended rows); QVV40 / QV32 rows; ACLHIP_CONSUMERS_FAST; the host convenience form; the C++ mirror
+ * in aclhip.hpp; instance lists.
+ *   What it costs (one MI355X, 65 536 x 100 bones, medians of three runs): K = 2 162 us local / 177 us object space, K = 4 279 / 283 us,
+ * with or without masks, against 110 us for aclhip_transform_poses_batch with object space on one of the same buffers, measured in the
+ * same rounds: 1.5 x and 2.5 x its time for 1.5 x and 2.5 x its bytes, 0.67 - 0.73 of the HBM peak (tools/pose_buffer_blend.py,
+ * profiles/pose_buffer_blend.md; DESIGN.md 4.7 "Blended pose buffers"). */
+aclhip_status aclhip_blend_poses_batch(aclhip_context* context, const aclhip_pose_buffer_blend* blend, uint32_t num_instances,
+	void* poses /* may be NULL with bounds */, uint64_t pose_stride_bytes, void* stream);
 
 /* ---- multi-GPU ---------------------------------------------------------------------------------- */
 
