@@ -1210,6 +1210,20 @@ namespace aclhip
 		return result;
 	}
 
+	// rtm::qvv_inverse, operation by operation: the rotation conjugated (sign flips), scale^-1 = 1 / scale (the correctly rounded division),
+	// translation^-1 = -quat_mul_vector3(scale^-1 * translation, rotation^-1). Exact for a uniform scale only: QVV transforms are not
+	// closed under inversion otherwise -- RTM's statement, kept as it is. A scale of 0 gives infinities.
+	__device__ __forceinline__ qvv qvv_inverse(const qvv& input)
+	{
+		qvv result;
+		result.rotation = make_float4(-input.rotation.x, -input.rotation.y, -input.rotation.z, input.rotation.w);
+		result.scale = make_float4(1.0f / input.scale.x, 1.0f / input.scale.y, 1.0f / input.scale.z, 0.0f);
+		const float4 scaled = make_float4(result.scale.x * input.translation.x, result.scale.y * input.translation.y, result.scale.z * input.translation.z, 0.0f);
+		const float4 rotated = quat_mul_vector3(scaled, result.rotation);
+		result.translation = make_float4(-rotated.x, -rotated.y, -rotated.z, 0.0f);
+		return result;
+	}
+
 	// the quaternion path of qvv_mul in ACLHIP_CONSUMERS_FAST arithmetic
 	__device__ __forceinline__ qvv qvv_mul_fast(const qvv& lhs, const qvv& rhs)
 	{

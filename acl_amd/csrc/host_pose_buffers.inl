@@ -1,5 +1,6 @@
 // host_pose_buffers.inl -- part of aclhip.hip (one translation unit; included there, in this order, not compiled on its own).
-// Host side: the pose consumers over a caller's pose buffers (aclhip_transform_poses_batch, aclhip_blend_poses_batch; kernels_pose_buffers.inl).
+// Host side: the pose consumers over a caller's pose buffers (aclhip_transform_poses_batch, aclhip_blend_poses_batch,
+// aclhip_inverse_transform_poses_batch; kernels_pose_buffers.inl).
 
 namespace
 {
@@ -263,6 +264,101 @@ namespace
 		default: return launch_blend_poses_of<4>(context, shape, num_blocks, stream, launch, object_space, blend.bounds);
 		}
 	}
+
+	// ---- object -> local space and make-additive (aclhip_inverse_transform_poses_batch; inverse_transform_poses_kernel) --------------------
+
+	// What aclhip_inverse_transform_poses_batch checks of its arguments before any device call; every refusal leaves a message, with or without a context
+	aclhip_status check_pose_buffer_inverse(aclhip_context* context, const void* source_poses, uint64_t source_pose_stride_bytes, uint32_t num_instances,
+		const aclhip_pose_buffer_inverse* inverse, const void* poses, uint64_t pose_stride_bytes)
+	{
+		if (inverse == nullptr)
+			return fail(context, ACLHIP_ERROR_INVALID_ARGUMENT, "null pose buffer inverse");
+		if (source_poses == nullptr)
+			return fail(context, ACLHIP_ERROR_INVALID_ARGUMENT, "null source pose buffer");
+		if (poses == nullptr)
+			return fail(context, ACLHIP_ERROR_INVALID_ARGUMENT, "null output buffer");
+		if (inverse->skeleton == 0 && inverse->instance_skeletons == nullptr)
+			return fail(context, ACLHIP_ERROR_INVALID_ARGUMENT, "a pose buffer inverse names a skeleton or a list of skeletons");
+		if (inverse->additive_format > ACLHIP_ADDITIVE_ADDITIVE1)
+			return fail(context, ACLHIP_ERROR_INVALID_ARGUMENT, "unknown additive format %u", inverse->additive_format);
+		const bool has_base = inverse->additive_format != ACLHIP_ADDITIVE_NONE;
+		if (inverse->local_space == 0 && !has_base)
+			return fail(context, ACLHIP_ERROR_INVALID_ARGUMENT, "neither local_space nor an additive format: nothing to do");
+		if (has_base != (inverse->base_poses != nullptr))
+			return fail(context, ACLHIP_ERROR_INVALID_ARGUMENT, "an additive format and a base pose buffer come together");
+		if ((source_pose_stride_bytes & 15u) != 0 || (reinterpret_cast<uintptr_t>(source_poses) & 15u) != 0)
+			return fail(context, ACLHIP_ERROR_INVALID_ARGUMENT, "source pose buffer and stride must be 16 byte aligned");
+		if ((pose_stride_bytes & 15u) != 0 || (reinterpret_cast<uintptr_t>(poses) & 15u) != 0)
+			return fail(context, ACLHIP_ERROR_INVALID_ARGUMENT, "pose buffer and stride must be 16 byte aligned");
+		if (has_base && ((inverse->base_pose_stride_bytes & 15u) != 0 || (reinterpret_cast<uintptr_t>(inverse->base_poses) & 15u) != 0))
+			return fail(context, ACLHIP_ERROR_INVALID_ARGUMENT, "base pose buffer and stride must be 16 byte aligned");
+		if (inverse->reserved[0] != 0 || inverse->reserved[1] != 0 || inverse->reserved[2] != 0)
+			return fail(context, ACLHIP_ERROR_INVALID_ARGUMENT, "the reserved fields of a pose buffer inverse are 0");
+		consumer_launch_shape shape;
+		if (const aclhip_status shape_status = pose_buffer_launch_shape_of(context, poses, pose_stride_bytes, source_pose_stride_bytes, false, 0, shape); shape_status != ACLHIP_OK)
+			return shape_status;
+		// in place is the one overlap allowed: a wave reads its own instance's row and has it complete in LDS before it stores
+		const bool in_place = poses == source_poses && pose_stride_bytes == source_pose_stride_bytes;
+		if (!in_place && pose_ranges_overlap(poses, pose_stride_bytes, source_poses, source_pose_stride_bytes, num_instances))
+			return fail(context, ACLHIP_ERROR_INVALID_ARGUMENT, "the output rows overlap the source pose rows: only poses == source_poses with equal strides (in place) is allowed");
+		if (has_base && pose_ranges_overlap(poses, pose_stride_bytes, inverse->base_poses, inverse->base_pose_stride_bytes, num_instances))
+			return fail(context, ACLHIP_ERROR_INVALID_ARGUMENT, "the output rows overlap the base pose rows");
+		return ACLHIP_OK;
+	}
+
+	template<bool kLocalSpace, bool kBase>
+	aclhip_status launch_inverse_transform_poses_kernel(aclhip_context* context, const consumer_launch_shape& shape, uint32_t num_blocks, hipStream_t stream, const pose_inverse_launch& launch)
+	{
+		const auto kernel = inverse_transform_poses_kernel<kLocalSpace, kBase>;
+		// above the default limit of dynamic LDS the kernel has to be told
+		if (shape.lds_bytes > 64 * 1024 - 128)
+			ACLHIP_CHECK_HIP(context, hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, int(k_consumer_lds_bytes)));
+		hipLaunchKernelGGL(kernel, dim3(num_blocks), dim3((1u << shape.log2_instances_per_block) * k_wave_size), shape.lds_bytes, stream, launch);
+		ACLHIP_CHECK_HIP(context, hipGetLastError());
+		return ACLHIP_OK;
+	}
+
+	// The launch: shaped by its output rows alone, like launch_pose_buffers but without a walk schedule (the kernel has no walk); the skeleton
+	// table is filled in under the registry lock; nothing is uploaded
+	aclhip_status launch_pose_buffer_inverse(aclhip_context* context, const void* source_poses, uint64_t source_pose_stride_bytes, uint32_t num_instances,
+		const aclhip_pose_buffer_inverse& inverse, void* poses, uint64_t pose_stride_bytes, hipStream_t stream)
+	{
+		std::shared_lock<std::shared_mutex> lock(context->mutex);		// see launch_tracks
+		if (context->skeletons.d_records == nullptr)
+			return fail(context, ACLHIP_ERROR_INVALID_ARGUMENT, "no skeleton was ever registered with this context");
+		const bool local_space = inverse.local_space != 0;
+		const bool has_base = inverse.additive_format != ACLHIP_ADDITIVE_NONE;
+		consumer_launch_shape shape;
+		if (const aclhip_status shape_status = pose_buffer_launch_shape_of(context, poses, pose_stride_bytes, source_pose_stride_bytes, false, 0, shape); shape_status != ACLHIP_OK)
+			return shape_status;
+		note_launch_stream(context, stream);
+
+		pose_inverse_launch launch = {};
+		launch.skeletons = context->skeletons.d_records;
+		launch.num_skeletons = ACLHIP_MAX_SKELETONS;
+		launch.skeleton = inverse.skeleton;
+		launch.instance_skeletons = inverse.instance_skeletons;
+		launch.source_poses = static_cast<const uint8_t*>(source_poses);
+		launch.source_pose_stride_bytes = source_pose_stride_bytes;
+		launch.base_poses = has_base ? static_cast<const uint8_t*>(inverse.base_poses) : nullptr;
+		launch.base_pose_stride_bytes = has_base ? inverse.base_pose_stride_bytes : 0;
+		launch.poses = static_cast<uint8_t*>(poses);
+		launch.pose_stride_bytes = pose_stride_bytes;
+		launch.num_instances = num_instances;
+		launch.additive_format = inverse.additive_format;
+		launch.lds_quads_per_image = shape.lds_quads_per_image;
+		launch.lds_bytes_per_instance = uint32_t(shape.lds_bytes_per_instance);
+		launch.log2_instances_per_block = shape.log2_instances_per_block;
+		launch.rejected_count = context->d_rejected;
+
+		const uint32_t instances_per_block = 1u << shape.log2_instances_per_block;
+		const uint32_t num_blocks = (num_instances + instances_per_block - 1) / instances_per_block;
+		// three instantiations: local / none, local / base, no-local / base
+		if (!local_space)
+			return launch_inverse_transform_poses_kernel<false, true>(context, shape, num_blocks, stream, launch);
+		return has_base ? launch_inverse_transform_poses_kernel<true, true>(context, shape, num_blocks, stream, launch)
+			: launch_inverse_transform_poses_kernel<true, false>(context, shape, num_blocks, stream, launch);
+	}
 }
 
 // include/aclhip.h states the definition. The argument checks need no device, come first and leave a message, with or without a context.
@@ -294,4 +390,20 @@ extern "C" aclhip_status aclhip_blend_poses_batch(aclhip_context* context, const
 
 	device_guard guard(context->device);
 	return launch_pose_buffer_blend(context, *blend, num_instances, poses, pose_stride_bytes, static_cast<hipStream_t>(stream));
+}
+
+// include/aclhip.h states the definition. The argument checks need no device, come first and leave a message, with or without a context.
+extern "C" aclhip_status aclhip_inverse_transform_poses_batch(aclhip_context* context, const void* source_poses, uint64_t source_pose_stride_bytes, uint32_t num_instances,
+	const aclhip_pose_buffer_inverse* inverse, void* poses, uint64_t pose_stride_bytes, void* stream)
+{
+	const aclhip_status status = check_pose_buffer_inverse(context, source_poses, source_pose_stride_bytes, num_instances, inverse, poses, pose_stride_bytes);
+	if (status != ACLHIP_OK)
+		return status;
+	if (context == nullptr)
+		return fail(context, ACLHIP_ERROR_INVALID_ARGUMENT, "null context");
+	if (num_instances == 0)
+		return ACLHIP_OK;
+
+	device_guard guard(context->device);
+	return launch_pose_buffer_inverse(context, source_poses, source_pose_stride_bytes, num_instances, *inverse, poses, pose_stride_bytes, static_cast<hipStream_t>(stream));
 }

@@ -2,6 +2,8 @@
 // The pose consumers over a CALLER'S pose buffers (aclhip_transform_poses_batch): transform_poses_kernel fills its LDS image from a row
 // in HBM instead of from a clip, and everything behind the fill is decompress_poses_consumer_kernel's finish_consumer_poses with the
 // skeleton's bone count and walk schedule -- the combine with a base buffer, the walk, the store and the bounds.
+// inverse_transform_poses_kernel (aclhip_inverse_transform_poses_batch) is the way back over the same rows: object -> local space and
+// make-additive, a bone per lane, no walk.
 
 	// the kernel's argument: the launch's three buffers, its skeletons and its shape
 	struct pose_buffer_launch
@@ -271,4 +273,162 @@
 			consumer_tail_args{ launch.poses, launch.pose_stride_bytes, launch.lds_bytes_per_instance, log2_instances_per_block, launch.rejected_count, nullptr, 0,
 				ACLHIP_ADDITIVE_NONE, bounds.bounds, bounds.bone_flags },
 			wave, walk);
+	}
+
+	// ---- the way back: object -> local space and make-additive over caller pose buffers (aclhip_inverse_transform_poses_batch) ------------
+	// the kernel's argument: the launch's three buffers, its skeletons and its shape
+	struct pose_inverse_launch
+	{
+		const device_skeleton* skeletons;		// the context's skeleton table
+		uint32_t num_skeletons;					// its capacity
+		uint32_t skeleton;						// the launch's skeleton, when instance_skeletons is null
+		const uint32_t* instance_skeletons;		// [num_instances] or null
+		const uint8_t* source_poses;			// row i at source_poses + i * source_pose_stride_bytes
+		uint64_t source_pose_stride_bytes;
+		const uint8_t* base_poses;				// kBase: row i at base_poses + i * base_pose_stride_bytes
+		uint64_t base_pose_stride_bytes;
+		uint8_t* poses;
+		uint64_t pose_stride_bytes;
+		uint32_t num_instances;
+		uint32_t additive_format;
+		uint32_t lds_quads_per_image, lds_bytes_per_instance, log2_instances_per_block;		// consumer_launch_shape's, without a walk schedule
+		unsigned long long* rejected_count;
+	};
+
+	// lhs first, then rhs, with rtm::qvv_mul's matrix route where a scale of either side is negative; the products that take it are counted
+	// (aclhip_get_negative_scale_count), one atomic per wave. Called where every lane that is active has a product.
+	__device__ __forceinline__ qvv qvv_mul_counted(const qvv& lhs, const qvv& rhs, unsigned long long* negative_scale_count, uint32_t lane)
+	{
+		const bool through_matrices = qvv_mul_takes_matrix_path(lhs, rhs);
+		const uint64_t mirrored = __ballot(through_matrices);
+		if (mirrored != 0 && lane == uint32_t(__builtin_ctzll(mirrored)))
+			atomicAdd(negative_scale_count, (unsigned long long)__builtin_popcountll(mirrored));
+		qvv result = qvv_mul(lhs, rhs);
+		if (mirrored != 0 && through_matrices)
+			result = qvv_mul_through_matrices(lhs, rhs);
+		return result;
+	}
+
+	// convert_to_relative / convert_to_additive0 / convert_to_additive1 (core/additive_utils.h:176-195) in the reference's operation order;
+	// nothing is normalized there and nothing is here
+	__device__ __forceinline__ qvv convert_to_additive(uint32_t additive_format, const qvv& base, const qvv& transform, unsigned long long* negative_scale_count, uint32_t lane)
+	{
+		if (additive_format == 1)
+			return qvv_mul_counted(transform, qvv_inverse(base), negative_scale_count, lane);
+		qvv result;
+		result.rotation = quat_mul(transform.rotation, make_float4(-base.rotation.x, -base.rotation.y, -base.rotation.z, base.rotation.w));
+		result.translation = make_float4(transform.translation.x - base.translation.x, transform.translation.y - base.translation.y, transform.translation.z - base.translation.z, 0.0f);
+		if (additive_format == 2)
+			result.scale = make_float4(transform.scale.x / base.scale.x, transform.scale.y / base.scale.y, transform.scale.z / base.scale.z, 0.0f);
+		else
+			result.scale = make_float4((transform.scale.x * (1.0f / base.scale.x)) - 1.0f, (transform.scale.y * (1.0f / base.scale.y)) - 1.0f, (transform.scale.z * (1.0f / base.scale.z)) - 1.0f, 0.0f);
+		return result;
+	}
+
+	// transform_poses_kernel's shape -- one wave64 per instance, images as consumer_wave_of lays them out, the skeleton's record on the scalar
+	// unit, the refusal in front of any load of a row, the row into the image by DMA -- and then no walk: a bone's local transform is
+	// qvv_mul(object[bone], qvv_inverse(object[parent])), both operands INPUTS, so every lane has a bone of its own and no wave waits for
+	// another (no workgroup barrier anywhere, no walk schedule, a wave without work leaves at once).
+	//   kLocalSpace    object -> local space with the parent table of the skeleton's hierarchy image (kernels_bone_object.inl reads the same)
+	//   kBase          the make-additive step against the base row in HBM, read per transform as finish_consumer_poses reads its base buffer
+	// The image is rewritten in place, lanes <-> bones in passes of 64 from the LAST bone down: parents come before their children
+	// (registration enforces it), so a pass over bones [k, k + 64) overwrites only what the passes behind it -- bones < k, parents < k --
+	// never read; inside a pass every read is waited for before the first write. Nothing is known about a caller's poses: the matrix route
+	// is compiled in and the normalize is the correctly rounded one, as in transform_poses_kernel.
+	// In place (poses == source_poses, equal strides): a wave reads its own instance's row and no other, and has it complete in LDS before
+	// it stores.
+	template<bool kLocalSpace, bool kBase>
+	__global__ __launch_bounds__(k_consumer_max_instances * k_wave_size) void inverse_transform_poses_kernel(pose_inverse_launch launch)
+	{
+		static_assert(kLocalSpace || kBase, "object space without a base buffer: nothing to do");
+		const consumer_wave wave = consumer_wave_of(launch.log2_instances_per_block, launch.lds_bytes_per_instance, launch.lds_quads_per_image);
+		const uint32_t lane = wave.lane, instance = wave.instance;
+		if (instance >= launch.num_instances)
+			return;
+
+		// the skeleton's record on the scalar unit; record 0 is never handed out and a cleared record is an unknown or retired skeleton
+		const uint32_t skeleton_id = launch.instance_skeletons != nullptr ? as_constant(launch.instance_skeletons)[instance] : launch.skeleton;
+		const device_skeleton skeleton = load_skeleton_fields(launch.skeletons, skeleton_id < launch.num_skeletons ? skeleton_id : 0);
+		const uint32_t num_bones = skeleton.num_bones;
+		const uint64_t row_bytes = uint64_t(num_bones) * 48u;
+
+		// refused, wave uniform and in front of any load of a row: what transform_poses_kernel refuses, over the strides of this launch
+		const bool refused = skeleton_id >= launch.num_skeletons || skeleton.reference_pose == nullptr || (kLocalSpace && skeleton.hierarchy == nullptr)
+			|| row_bytes > launch.source_pose_stride_bytes || row_bytes > launch.pose_stride_bytes
+			|| (kBase && row_bytes > launch.base_pose_stride_bytes) || num_bones * 3u > launch.lds_quads_per_image;
+		if (refused)
+		{
+			if (lane == 0)
+				atomicAdd(launch.rejected_count, 1ull);
+			return;
+		}
+		if (num_bones == 0)
+			return;
+
+		// the parent words of the first pass (the last bones) travel while the row does: parent | ancestors << 16, 0xFFFF for a root
+		const uint32_t num_passes = (num_bones + k_wave_size - 1) / k_wave_size;
+		[[maybe_unused]] const ACLHIP_CONSTANT uint32_t* parents = nullptr;
+		[[maybe_unused]] uint32_t parent_word = 0xFFFFu;
+		if constexpr (kLocalSpace)
+		{
+			parents = as_constant(skeleton.hierarchy) + as_constant(skeleton.hierarchy)[3];
+			const uint32_t bone = (num_passes - 1u) * k_wave_size + lane;
+			if (bone < num_bones)
+				parent_word = parents[bone];
+		}
+
+		// the row straight into the image by DMA, lanes <-> consecutive quads (the LDS side of a piece is wave uniform + lane * 16)
+		f32x4* const image = wave.image;
+		const uint32_t num_quads = num_bones * 3u;
+		{
+			const f32x4* source = reinterpret_cast<const f32x4*>(launch.source_poses + uint64_t(instance) * launch.source_pose_stride_bytes);
+			for (uint32_t base = 0; base < num_quads; base += k_wave_size)
+			{
+				if (base + lane < num_quads)
+					__builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(source + base + lane),
+						(__attribute__((address_space(3))) void*)(image + base), 16, 0, 0);
+			}
+		}
+		wave_lds_barrier();		// the row is complete (vmcnt)
+
+		unsigned long long* const negative_scale_count = launch.rejected_count + 1;
+		[[maybe_unused]] const f32x4* base_row = kBase ? reinterpret_cast<const f32x4*>(launch.base_poses + uint64_t(instance) * launch.base_pose_stride_bytes) : nullptr;
+		for (uint32_t pass = num_passes; pass-- != 0;)
+		{
+			const uint32_t bone = pass * k_wave_size + lane;
+			const uint32_t parent = parent_word & 0xFFFFu;
+			// the next pass's parent words are asked for in front of this pass's arithmetic
+			if constexpr (kLocalSpace)
+			{
+				parent_word = 0xFFFFu;
+				if (pass != 0)
+					parent_word = parents[bone - k_wave_size];
+			}
+			const bool has_parent = kLocalSpace && bone < num_bones && parent != 0xFFFFu;
+			// a root of a launch without a base keeps the bytes of the input, pads included: it is not written
+			const bool written = kBase ? bone < num_bones : has_parent;
+			qvv result;
+			if (written)
+			{
+				result = load_qvv(image, bone);
+				if constexpr (kLocalSpace)
+				{
+					if (has_parent)
+					{
+						result = qvv_mul_counted(result, qvv_inverse(load_qvv(image, parent)), negative_scale_count, lane);
+						result.rotation = quat_normalize(result.rotation);
+					}
+				}
+				if constexpr (kBase)
+					result = convert_to_additive(launch.additive_format, load_qvv(base_row, bone), result, negative_scale_count, lane);
+			}
+			wave_lds_barrier();		// every read of the pass is behind the wave
+			if (written)
+				store_qvv(image, bone, result);
+			wave_lds_barrier();		// and every write in front of the next pass's reads, and of the store below
+		}
+
+		f32x4* pose = reinterpret_cast<f32x4*>(launch.poses + uint64_t(instance) * launch.pose_stride_bytes);
+		for (uint32_t quad = lane; quad < num_quads; quad += k_wave_size)
+			store_streaming(&pose[quad], image[quad]);
 	}

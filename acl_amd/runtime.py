@@ -50,6 +50,7 @@ EXPORTED_SYMBOLS = [
     "aclhip_decompress_poses_batch_additive_weighted",
     "aclhip_transform_poses_batch",
     "aclhip_blend_poses_batch",
+    "aclhip_inverse_transform_poses_batch",
 ]
 
 
@@ -139,6 +140,14 @@ class PoseBufferConsumers(ctypes.Structure):
     _fields_ = [
         ("skeleton", ctypes.c_uint32), ("instance_skeletons", ctypes.c_void_p), ("object_space", ctypes.c_uint32), ("additive_format", ctypes.c_uint32),
         ("additive_poses", ctypes.c_void_p), ("additive_pose_stride_bytes", ctypes.c_uint64), ("bounds", ctypes.c_void_p), ("reserved", ctypes.c_uint64 * 2),
+    ]
+
+
+class PoseBufferInverse(ctypes.Structure):
+    """aclhip_pose_buffer_inverse; `base_poses` and `instance_skeletons` are device addresses or None"""
+    _fields_ = [
+        ("skeleton", ctypes.c_uint32), ("instance_skeletons", ctypes.c_void_p), ("local_space", ctypes.c_uint32), ("additive_format", ctypes.c_uint32),
+        ("base_poses", ctypes.c_void_p), ("base_pose_stride_bytes", ctypes.c_uint64), ("reserved", ctypes.c_uint64 * 3),
     ]
 
 
@@ -344,6 +353,7 @@ def load_library():
                                                                     ctypes.POINTER(AdditiveLayering), vp, u64, vp]
     lib.aclhip_transform_poses_batch.argtypes = [vp, vp, u64, u32, ctypes.POINTER(PoseBufferConsumers), vp, u64, vp]
     lib.aclhip_blend_poses_batch.argtypes = [vp, ctypes.POINTER(PoseBufferBlend), u32, vp, u64, vp]
+    lib.aclhip_inverse_transform_poses_batch.argtypes = [vp, vp, u64, u32, ctypes.POINTER(PoseBufferInverse), vp, u64, vp]
     _lib = lib
     return lib
 
@@ -802,6 +812,13 @@ class Context:
         if bounds is not None:
             blend.bounds = ctypes.addressof(bounds)
         self._check(self._lib.aclhip_blend_poses_batch(self._handle, ctypes.byref(blend) if blend is not None else None, num_instances, poses_ptr, pose_stride_bytes, stream))
+
+    def inverse_transform_poses_batch(self, source_poses_ptr, source_pose_stride_bytes, num_instances, inverse, poses_ptr, pose_stride_bytes, stream=None):
+        """aclhip_inverse_transform_poses_batch: object -> local space and / or convert_to_relative / additive0 / additive1 against a base
+        buffer over the caller's QVV48 rows (device addresses); poses_ptr == source_poses_ptr with equal strides: in place. `inverse` is a
+        PoseBufferInverse."""
+        self._check(self._lib.aclhip_inverse_transform_poses_batch(self._handle, source_poses_ptr, source_pose_stride_bytes, num_instances,
+                                                                   ctypes.byref(inverse) if inverse is not None else None, poses_ptr, pose_stride_bytes, stream))
 
     def decompress_poses_mapped(self, clips, sample_times, skeletons, maps, num_bones, additive_format=ADDITIVE_NONE, object_space=False, base_clips=None,
                                 base_sample_times=None, base_maps=None, base_poses=None, params=None, out=None, instance_rounding=None, instance_looping=None,

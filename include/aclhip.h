@@ -1122,9 +1122,9 @@ typedef struct aclhip_pose_buffer_consumers
  *   The launch's shape comes from the rows alone, as for the mapped launch: pose_stride_bytes / 48 slots per LDS image (and entries of
  * bone_flags), or local_pose_stride_bytes / 48 when poses is NULL. Registered clips play no part. The launch goes on `stream`, can be
  * captured into a graph, and uploads nothing.
- *   Out of scope (nothing here precludes them): object_to_local_space; additive strength on buffers; QVV40 / QV32 rows;
- * ACLHIP_CONSUMERS_FAST; the host convenience form; the C++ mirror in aclhip.hpp; instance lists. (A blend of several buffers, with
- * blend masks: aclhip_blend_poses_batch, below.)
+ *   Out of scope (nothing here precludes them): additive strength on buffers; QVV40 / QV32 rows; ACLHIP_CONSUMERS_FAST; the host
+ * convenience form; the C++ mirror in aclhip.hpp; instance lists. (A blend of several buffers, with blend masks:
+ * aclhip_blend_poses_batch, below. The way back, object_to_local_space and make-additive: aclhip_inverse_transform_poses_batch, below.)
  *   What it costs: NOT MEASURED YET (tools/pose_buffers.py, profiles/pose_buffers.md; DESIGN.md 4.7 "Pose buffers"). */
 aclhip_status aclhip_transform_poses_batch(aclhip_context* context, const void* local_poses, uint64_t local_pose_stride_bytes,
 	uint32_t num_instances, const aclhip_pose_buffer_consumers* consumers, void* poses /* may be NULL with bounds */,
@@ -1199,6 +1199,79 @@ typedef struct aclhip_pose_buffer_blend
  * profiles/pose_buffer_blend.md; DESIGN.md 4.7 "Blended pose buffers"). */
 aclhip_status aclhip_blend_poses_batch(aclhip_context* context, const aclhip_pose_buffer_blend* blend, uint32_t num_instances,
 	void* poses /* may be NULL with bounds */, uint64_t pose_stride_bytes, void* stream);
+
+/* ---- inverse pose buffers: object -> local space and make-additive over a caller's poses ----------
+ * aclhip_transform_poses_batch takes a pose into object space in one launch. Whatever is solved there -- foot IK, look-at, a ragdoll or
+ * physics pose, an attachment constraint -- has to come back to local space before it can be blended, layered or cached, and an engine's
+ * "make dynamic additive" node needs the difference of two poses. aclhip_inverse_transform_poses_batch is the inverse of the two steps of
+ * aclhip_transform_poses_batch, in the opposite order: object -> local space with the skeleton's parents, then
+ * acl::convert_to_relative / convert_to_additive0 / convert_to_additive1 (core/additive_utils.h:176-195) against a base pose buffer.
+ * (ABI version 6 still: an added struct and an added function, no existing struct changed.) */
+typedef struct aclhip_pose_buffer_inverse
+{
+	aclhip_skeleton skeleton;					/* for every instance when instance_skeletons is NULL */
+	const aclhip_skeleton* instance_skeletons;	/* DEVICE [num_instances] or NULL */
+	uint32_t local_space;						/* 1: object -> local with the skeleton's parents */
+	uint32_t additive_format;					/* aclhip_additive_format; NONE: no base buffer */
+	const void* base_poses;						/* DEVICE or NULL: base pose i at base_poses + i * base_pose_stride_bytes, QVV48, skeleton order, LOCAL space */
+	uint64_t base_pose_stride_bytes;
+	uint64_t reserved[3];						/* 0 */
+} aclhip_pose_buffer_inverse;					/* 64 bytes, offsets 0 8 16 20 24 32 40 */
+
+/* The definition. Instance i has skeleton S (inverse->skeleton, or instance_skeletons[i]) with B bones and parents P; X is the B QVV48
+ * records at source_poses + i * source_pose_stride_bytes.
+ *   1. With local_space: a root (a bone whose parent is ACLHIP_NO_PARENT; bone 0 is one) gives L[b] = X[b]; every other bone gives
+ *      L[b] = qvv_mul(X[b], qvv_inverse(X[P[b]])) with its rotation through quat_normalize. qvv_inverse is rtm::qvv_inverse, in this
+ *      order: the rotation conjugated (sign flips); scale^-1 = 1 / scale, the correctly rounded division; translation^-1 =
+ *      -quat_mul_vector3(scale^-1 * translation, rotation^-1). qvv_mul is the walk's (lhs first), with rtm::qvv_mul's matrix route where
+ *      a scale of either side is negative; the normalize is the walk's correctly rounded sqrt and division. Both operands are read from
+ *      the INPUT row: no bone reads another bone's result. Without local_space, L = X.
+ *      This is NOT the operand order of the reference's text: acl::object_to_local_space (compression/transform_pose_utils.h:59-74)
+ *      writes qvv_normalize(qvv_mul(qvv_inverse(object[parent]), object[bone])). rtm::qvv_mul(lhs, rhs) applies lhs first and
+ *      local_to_object_space computes qvv_mul(local, object[parent]), so its inverse is qvv_mul(object[bone], qvv_inverse(object[parent]))
+ *      -- the order convert_to_relative has in the same tree (qvv_mul(transform, qvv_inverse(base))). Nothing in the reference calls
+ *      object_to_local_space. Pushed back through local_to_object_space the order here returns the object pose to rounding (a few 1e-6
+ *      relative); the reference's order is off by tens of units (tests/test_pose_buffer_inverse_oracle.py pins both). A launch that does
+ *      not undo aclhip_transform_poses_batch is of no use, so the true inverse is what is built.
+ *   2. With an additive format and base row Bs (the B records at base_poses + i * base_pose_stride_bytes), row i is per bone
+ *      convert_to_relative (qvv_mul(L[b], qvv_inverse(Bs[b])), matrix route included), convert_to_additive0 (rotation quat_mul(L.rotation,
+ *      conjugate(Bs.rotation)), translation L - Bs, scale L / Bs, the correctly rounded division) or convert_to_additive1 (rotation and
+ *      translation alike, scale (L * (1 / Bs)) - 1) of (base = Bs[b], transform = L[b]), in exactly the reference's operation order.
+ *      Nothing is normalized there and nothing is here. Otherwise row i is L.
+ *   3. fp32, one IEEE operation at a time, never fused.
+ *   4. The pads (the fourth float of a translation and of a scale): every record that went through step 1's product or through step 2
+ *      is written with both pads 0. A root of a launch without an additive format keeps the bytes of X, pads included -- the rule of
+ *      aclhip_transform_poses_batch.
+ *   5. All B records are written; bytes of a row behind B * 48 are untouched.
+ *   6. aclhip_get_negative_scale_count moves by one per qvv_mul that takes the matrix route: step 1's product and convert_to_relative's,
+ *      as the forward launch counts its own.
+ *   What undoes what: the launch undoes aclhip_transform_poses_batch -- local_space its object_space, format F its format F with the
+ * same base -- up to rounding for unit rotations and ONE scale per bone (s, s, s), mirrored bones (-s, -s, -s) included. QVV transforms
+ * are not closed under inversion when a scale is non-uniform: that is rtm::qvv_inverse, not a choice made here. A scale of 0 gives
+ * infinities.
+ *   In place: poses == source_poses with equal strides is allowed, and is the expected use -- a wave has its row complete in LDS before
+ * it stores, and no wave reads another instance's row. Any other overlap of the output range with the source range, and any overlap of
+ * the output range with the base range, is ACLHIP_ERROR_INVALID_ARGUMENT; the host decides this from the three (pointer, stride,
+ * num_instances) ranges, [pointer, pointer + stride * num_instances).
+ *   Refused and counted (aclhip_get_rejected_instance_count), the row untouched: an unknown or retired skeleton handle (0 included);
+ * local_space on a skeleton without hierarchy; B * 48 larger than any of the strides in use (source_pose_stride_bytes,
+ * pose_stride_bytes, base_pose_stride_bytes with an additive format); B beyond the launch's LDS image. The refusal comes in front of any
+ * load of a row: no instance reads or writes outside its rows, whatever instance_skeletons holds. A skeleton unregistered after the
+ * launch was enqueued is still served.
+ *   ACLHIP_ERROR_INVALID_ARGUMENT, decided before any device call, each with a message (with or without a context): inverse == NULL,
+ * source_poses == NULL or poses == NULL; no skeleton at all (skeleton == 0 and instance_skeletons == NULL); local_space == 0 with
+ * ACLHIP_ADDITIVE_NONE (nothing to do); an unknown format; a format other than NONE without base_poses, or the reverse; pointers or
+ * strides that are not 16 byte aligned; reserved fields that are not 0; a shape that does not fit 160 KiB of LDS; the overlaps above.
+ *   The launch's shape comes from pose_stride_bytes / 48 alone (slots per LDS image). Registered clips play no part. The launch goes on
+ * `stream`, can be captured into a graph, and uploads nothing.
+ *   Out of scope (nothing here precludes them): bounds; blend masks or strengths; QVV40 / QV32 rows; ACLHIP_CONSUMERS_FAST; the host
+ * convenience form; the C++ mirror in aclhip.hpp; instance lists.
+ *   What it costs (one MI355X, 65 536 x 100 bones, medians of three interleaved rounds of 20 launches): local_space 107 us out of place
+ * and 108 us in place, local_space plus relative 165 us for 1.5 x the bytes, against 121 us (112 - 141 over its three rounds) for
+ * aclhip_transform_poses_batch with object space on the same buffers in the same rounds: no slower than the forward launch, 0.72 - 0.74
+ * of the HBM peak (tools/pose_buffer_inverse.py, profiles/pose_buffer_inverse.md; DESIGN.md 4.7 "Inverse pose buffers"). */
+aclhip_status aclhip_inverse_transform_poses_batch(aclhip_context* context, const void* source_poses, uint64_t source_pose_stride_bytes,
+	uint32_t num_instances, const aclhip_pose_buffer_inverse* inverse, void* poses, uint64_t pose_stride_bytes, void* stream);
 
 /* ---- multi-GPU ---------------------------------------------------------------------------------- */
 
