@@ -1,6 +1,6 @@
 // host_pose_buffers.inl -- part of aclhip.hip (one translation unit; included there, in this order, not compiled on its own).
 // Host side: the pose consumers over a caller's pose buffers (aclhip_transform_poses_batch, aclhip_blend_poses_batch,
-// aclhip_inverse_transform_poses_batch; kernels_pose_buffers.inl).
+// aclhip_inverse_transform_poses_batch, aclhip_measure_pose_error_batch; kernels_pose_buffers.inl).
 
 namespace
 {
@@ -359,6 +359,168 @@ namespace
 		return has_base ? launch_inverse_transform_poses_kernel<true, true>(context, shape, num_blocks, stream, launch)
 			: launch_inverse_transform_poses_kernel<true, false>(context, shape, num_blocks, stream, launch);
 	}
+
+	// ---- the shell error of two pose buffers (aclhip_measure_pose_error_batch; measure_pose_error_kernel) ---------------------------------
+
+	// do [a, a + a_bytes) and [b, b + b_bytes) share a byte? (an empty range shares none; an end past 2^64 is the top of the address space)
+	bool byte_ranges_overlap(const void* a, unsigned __int128 a_bytes, const void* b, unsigned __int128 b_bytes)
+	{
+		if (a_bytes == 0 || b_bytes == 0)
+			return false;
+		const unsigned __int128 a_begin = reinterpret_cast<uintptr_t>(a), b_begin = reinterpret_cast<uintptr_t>(b);
+		return a_begin < b_begin + b_bytes && b_begin < a_begin + a_bytes;
+	}
+
+	// The two input rows set the shape of the launch: an image's quads from the smaller stride, two images per instance, and the words of the
+	// walk schedule on top of them once the context is known. Refuses rows that do not fit.
+	aclhip_status pose_error_launch_shape_of(aclhip_context* context, uint64_t raw_pose_stride_bytes, uint64_t lossy_pose_stride_bytes, bool object_space,
+		uint32_t max_hierarchy_words, consumer_launch_shape& out_shape)
+	{
+		const uint32_t row_transforms = uint32_t(std::min<uint64_t>(std::min(raw_pose_stride_bytes, lossy_pose_stride_bytes) / 48, 0xFFFFu));
+		out_shape = consumer_launch_shape_of(row_transforms * 3u, row_transforms, true, object_space, max_hierarchy_words);
+		if (!out_shape.fits)
+			return fail(context, ACLHIP_ERROR_INVALID_ARGUMENT, "rows of %u transforms: two of them are too large for the pose error measure (%zu bytes of LDS per instance)", row_transforms, out_shape.lds_needed_bytes);
+		return ACLHIP_OK;
+	}
+
+	// What aclhip_measure_pose_error_batch checks of its arguments before any device call; every refusal leaves a message, with or without a context
+	aclhip_status check_pose_error(aclhip_context* context, const void* raw_poses, uint64_t raw_pose_stride_bytes, const void* lossy_poses, uint64_t lossy_pose_stride_bytes,
+		uint32_t num_instances, const aclhip_pose_error_desc* desc, const aclhip_pose_error* errors)
+	{
+		if (desc == nullptr)
+			return fail(context, ACLHIP_ERROR_INVALID_ARGUMENT, "null pose error desc");
+		if (raw_poses == nullptr)
+			return fail(context, ACLHIP_ERROR_INVALID_ARGUMENT, "null raw pose buffer");
+		if (lossy_poses == nullptr)
+			return fail(context, ACLHIP_ERROR_INVALID_ARGUMENT, "null lossy pose buffer");
+		if (errors == nullptr)
+			return fail(context, ACLHIP_ERROR_INVALID_ARGUMENT, "null pose error records");
+		if (desc->skeleton == 0 && desc->instance_skeletons == nullptr)
+			return fail(context, ACLHIP_ERROR_INVALID_ARGUMENT, "a pose error desc names a skeleton or a list of skeletons");
+		if (desc->additive_format > ACLHIP_ADDITIVE_ADDITIVE1)
+			return fail(context, ACLHIP_ERROR_INVALID_ARGUMENT, "unknown additive format %u", desc->additive_format);
+		const bool has_base = desc->additive_format != ACLHIP_ADDITIVE_NONE;
+		if (has_base != (desc->base_poses != nullptr))
+			return fail(context, ACLHIP_ERROR_INVALID_ARGUMENT, "an additive format and a base pose buffer come together");
+		if (desc->shell_distances != nullptr && desc->num_shell_distances == 0)
+			return fail(context, ACLHIP_ERROR_INVALID_ARGUMENT, "a shell distance table of no entries");
+		if (desc->bone_errors != nullptr && (desc->bone_error_stride_bytes == 0 || (desc->bone_error_stride_bytes & 3u) != 0 || (reinterpret_cast<uintptr_t>(desc->bone_errors) & 3u) != 0))
+			return fail(context, ACLHIP_ERROR_INVALID_ARGUMENT, "bone errors are 4 byte aligned and their stride is a multiple of 4 that is not 0");
+		if ((raw_pose_stride_bytes & 15u) != 0 || (reinterpret_cast<uintptr_t>(raw_poses) & 15u) != 0)
+			return fail(context, ACLHIP_ERROR_INVALID_ARGUMENT, "raw pose buffer and stride must be 16 byte aligned");
+		if ((lossy_pose_stride_bytes & 15u) != 0 || (reinterpret_cast<uintptr_t>(lossy_poses) & 15u) != 0)
+			return fail(context, ACLHIP_ERROR_INVALID_ARGUMENT, "lossy pose buffer and stride must be 16 byte aligned");
+		if (has_base && ((desc->base_pose_stride_bytes & 15u) != 0 || (reinterpret_cast<uintptr_t>(desc->base_poses) & 15u) != 0))
+			return fail(context, ACLHIP_ERROR_INVALID_ARGUMENT, "base pose buffer and stride must be 16 byte aligned");
+		if ((reinterpret_cast<uintptr_t>(errors) & 7u) != 0)
+			return fail(context, ACLHIP_ERROR_INVALID_ARGUMENT, "pose error records must be 8 byte aligned");
+		if ((reinterpret_cast<uintptr_t>(desc->worst) & 15u) != 0)
+			return fail(context, ACLHIP_ERROR_INVALID_ARGUMENT, "the worst pose error record must be 16 byte aligned");
+		if (desc->reserved[0] != 0 || desc->reserved[1] != 0)
+			return fail(context, ACLHIP_ERROR_INVALID_ARGUMENT, "the reserved fields of a pose error desc are 0");
+		consumer_launch_shape shape;
+		if (const aclhip_status shape_status = pose_error_launch_shape_of(context, raw_pose_stride_bytes, lossy_pose_stride_bytes, false, 0, shape); shape_status != ACLHIP_OK)
+			return shape_status;
+
+		// raw, lossy and base are only read and may overlap each other freely; what is written overlaps nothing that is read and no other output
+		struct byte_range { const char* name; const void* pointer; unsigned __int128 bytes; };
+		const unsigned __int128 n = num_instances;
+		const byte_range inputs[] = {
+			{ "the raw pose rows", raw_poses, n * raw_pose_stride_bytes }, { "the lossy pose rows", lossy_poses, n * lossy_pose_stride_bytes },
+			{ "the base pose rows", desc->base_poses, has_base ? n * desc->base_pose_stride_bytes : 0 },
+			{ "the skeleton list", desc->instance_skeletons, desc->instance_skeletons != nullptr ? n * sizeof(aclhip_skeleton) : 0 },
+			{ "the shell distances", desc->shell_distances, desc->shell_distances != nullptr ? (unsigned __int128)desc->num_shell_distances * sizeof(float) : 0 },
+		};
+		const byte_range outputs[] = {
+			{ "the pose error records", errors, n * sizeof(aclhip_pose_error) },
+			{ "the bone errors", desc->bone_errors, desc->bone_errors != nullptr ? n * desc->bone_error_stride_bytes : 0 },
+			{ "the worst record", desc->worst, desc->worst != nullptr ? sizeof(aclhip_pose_error_worst) : 0 },
+		};
+		for (size_t o = 0; o < std::size(outputs); ++o)
+		{
+			for (const byte_range& input : inputs)
+				if (byte_ranges_overlap(outputs[o].pointer, outputs[o].bytes, input.pointer, input.bytes))
+					return fail(context, ACLHIP_ERROR_INVALID_ARGUMENT, "%s overlap %s", outputs[o].name, input.name);
+			for (size_t other = o + 1; other < std::size(outputs); ++other)
+				if (byte_ranges_overlap(outputs[o].pointer, outputs[o].bytes, outputs[other].pointer, outputs[other].bytes))
+					return fail(context, ACLHIP_ERROR_INVALID_ARGUMENT, "%s overlap %s", outputs[o].name, outputs[other].name);
+		}
+		return ACLHIP_OK;
+	}
+
+	template<bool kObjectSpace, bool kBase>
+	aclhip_status launch_measure_pose_error_kernel(aclhip_context* context, const consumer_launch_shape& shape, uint32_t num_blocks, hipStream_t stream, const pose_error_launch& launch)
+	{
+		const auto kernel = measure_pose_error_kernel<kObjectSpace, kBase>;
+		// above the default limit of dynamic LDS the kernel has to be told
+		if (shape.lds_bytes > 64 * 1024 - 128)
+			ACLHIP_CHECK_HIP(context, hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, int(k_consumer_lds_bytes)));
+		// two waves per instance: one per image
+		hipLaunchKernelGGL(kernel, dim3(num_blocks), dim3((2u << shape.log2_instances_per_block) * k_wave_size), shape.lds_bytes, stream, launch);
+		ACLHIP_CHECK_HIP(context, hipGetLastError());
+		return ACLHIP_OK;
+	}
+
+	// The launch: shaped by its two input rows alone; the skeleton table is filled in under the registry lock; nothing is uploaded. The
+	// worst record is a second, one workgroup launch over the instances' records on the same stream -- the only launch of a batch of none.
+	aclhip_status launch_pose_error(aclhip_context* context, const void* raw_poses, uint64_t raw_pose_stride_bytes, const void* lossy_poses, uint64_t lossy_pose_stride_bytes,
+		uint32_t num_instances, const aclhip_pose_error_desc& desc, aclhip_pose_error* errors, hipStream_t stream)
+	{
+		std::shared_lock<std::shared_mutex> lock(context->mutex);		// see launch_tracks
+		if (num_instances != 0)
+		{
+			if (context->skeletons.d_records == nullptr)
+				return fail(context, ACLHIP_ERROR_INVALID_ARGUMENT, "no skeleton was ever registered with this context");
+			const bool object_space = desc.object_space != 0;
+			const bool has_base = desc.additive_format != ACLHIP_ADDITIVE_NONE;
+			consumer_launch_shape shape;
+			if (const aclhip_status shape_status = pose_error_launch_shape_of(context, raw_pose_stride_bytes, lossy_pose_stride_bytes, object_space, context->max_skeleton_hierarchy_words, shape); shape_status != ACLHIP_OK)
+				return shape_status;
+			note_launch_stream(context, stream);
+
+			pose_error_launch launch = {};
+			launch.skeletons = context->skeletons.d_records;
+			launch.num_skeletons = ACLHIP_MAX_SKELETONS;
+			launch.skeleton = desc.skeleton;
+			launch.instance_skeletons = desc.instance_skeletons;
+			launch.raw_poses = static_cast<const uint8_t*>(raw_poses);
+			launch.raw_pose_stride_bytes = raw_pose_stride_bytes;
+			launch.lossy_poses = static_cast<const uint8_t*>(lossy_poses);
+			launch.lossy_pose_stride_bytes = lossy_pose_stride_bytes;
+			launch.base_poses = has_base ? static_cast<const uint8_t*>(desc.base_poses) : nullptr;
+			launch.base_pose_stride_bytes = has_base ? desc.base_pose_stride_bytes : 0;
+			launch.shell_distances = desc.shell_distances;
+			launch.num_shell_distances = desc.num_shell_distances;
+			launch.shell_distance = desc.shell_distance;
+			launch.bone_errors = reinterpret_cast<uint8_t*>(desc.bone_errors);
+			launch.bone_error_stride_bytes = desc.bone_error_stride_bytes;
+			launch.errors = reinterpret_cast<pose_error_record*>(errors);
+			launch.num_instances = num_instances;
+			launch.additive_format = desc.additive_format;
+			launch.lds_quads_per_image = shape.lds_quads_per_image;
+			launch.lds_bytes_per_instance = uint32_t(shape.lds_bytes_per_instance);
+			launch.packed_block_shape = shape.log2_instances_per_block | (shape.lds_schedule_words << 8);
+			launch.rejected_count = context->d_rejected;
+
+			const uint32_t instances_per_block = 1u << shape.log2_instances_per_block;
+			const uint32_t num_blocks = (num_instances + instances_per_block - 1) / instances_per_block;
+			// four instantiations: object / local x base / none
+			const aclhip_status status = object_space
+				? (has_base ? launch_measure_pose_error_kernel<true, true>(context, shape, num_blocks, stream, launch) : launch_measure_pose_error_kernel<true, false>(context, shape, num_blocks, stream, launch))
+				: (has_base ? launch_measure_pose_error_kernel<false, true>(context, shape, num_blocks, stream, launch) : launch_measure_pose_error_kernel<false, false>(context, shape, num_blocks, stream, launch));
+			if (status != ACLHIP_OK)
+				return status;
+		}
+		else
+			note_launch_stream(context, stream);
+		if (desc.worst != nullptr)
+		{
+			hipLaunchKernelGGL(pose_error_worst_kernel, dim3(1), dim3(k_pose_error_worst_threads), 0, stream, reinterpret_cast<const pose_error_record*>(errors), num_instances,
+				reinterpret_cast<u32x4*>(desc.worst));
+			ACLHIP_CHECK_HIP(context, hipGetLastError());
+		}
+		return ACLHIP_OK;
+	}
 }
 
 // include/aclhip.h states the definition. The argument checks need no device, come first and leave a message, with or without a context.
@@ -406,4 +568,21 @@ extern "C" aclhip_status aclhip_inverse_transform_poses_batch(aclhip_context* co
 
 	device_guard guard(context->device);
 	return launch_pose_buffer_inverse(context, source_poses, source_pose_stride_bytes, num_instances, *inverse, poses, pose_stride_bytes, static_cast<hipStream_t>(stream));
+}
+
+// include/aclhip.h states the definition. The argument checks need no device, come first and leave a message, with or without a context.
+extern "C" aclhip_status aclhip_measure_pose_error_batch(aclhip_context* context, const void* raw_poses, uint64_t raw_pose_stride_bytes, const void* lossy_poses,
+	uint64_t lossy_pose_stride_bytes, uint32_t num_instances, const aclhip_pose_error_desc* desc, aclhip_pose_error* errors, void* stream)
+{
+	const aclhip_status status = check_pose_error(context, raw_poses, raw_pose_stride_bytes, lossy_poses, lossy_pose_stride_bytes, num_instances, desc, errors);
+	if (status != ACLHIP_OK)
+		return status;
+	if (context == nullptr)
+		return fail(context, ACLHIP_ERROR_INVALID_ARGUMENT, "null context");
+	// (a batch of no instances still writes the launch's worst record)
+	if (num_instances == 0 && desc->worst == nullptr)
+		return ACLHIP_OK;
+
+	device_guard guard(context->device);
+	return launch_pose_error(context, raw_poses, raw_pose_stride_bytes, lossy_poses, lossy_pose_stride_bytes, num_instances, *desc, errors, static_cast<hipStream_t>(stream));
 }

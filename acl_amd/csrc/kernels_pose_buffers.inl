@@ -4,6 +4,8 @@
 // skeleton's bone count and walk schedule -- the combine with a base buffer, the walk, the store and the bounds.
 // inverse_transform_poses_kernel (aclhip_inverse_transform_poses_batch) is the way back over the same rows: object -> local space and
 // make-additive, a bone per lane, no walk.
+// measure_pose_error_kernel (aclhip_measure_pose_error_batch) holds TWO rows per instance, takes both through the same additive step and the
+// same walk without storing them, and measures per bone how far three points on the bone's shell moved.
 
 	// the kernel's argument: the launch's three buffers, its skeletons and its shape
 	struct pose_buffer_launch
@@ -431,4 +433,280 @@
 		f32x4* pose = reinterpret_cast<f32x4*>(launch.poses + uint64_t(instance) * launch.pose_stride_bytes);
 		for (uint32_t quad = lane; quad < num_quads; quad += k_wave_size)
 			store_streaming(&pose[quad], image[quad]);
+	}
+
+	// ---- how far two pose buffers are apart (aclhip_measure_pose_error_batch; include/aclhip.h states the definition) --------------------
+	struct pose_error_record { float error; uint32_t bone; };		// aclhip_pose_error
+	constexpr uint32_t k_no_bone = 0xFFFFFFFFu;						// ACLHIP_NO_BONE
+
+	// the kernel's argument: the launch's buffers, its skeletons, its shells, its outputs and its shape
+	struct pose_error_launch
+	{
+		const device_skeleton* skeletons;		// the context's skeleton table
+		uint32_t num_skeletons;					// its capacity
+		uint32_t skeleton;						// the launch's skeleton, when instance_skeletons is null
+		const uint32_t* instance_skeletons;		// [num_instances] or null
+		const uint8_t* raw_poses;				// row i at raw_poses + i * raw_pose_stride_bytes
+		uint64_t raw_pose_stride_bytes;
+		const uint8_t* lossy_poses;				// row i at lossy_poses + i * lossy_pose_stride_bytes
+		uint64_t lossy_pose_stride_bytes;
+		const uint8_t* base_poses;				// kBase: row i at base_poses + i * base_pose_stride_bytes
+		uint64_t base_pose_stride_bytes;
+		const float* shell_distances;			// [num_shell_distances] or null: shell_distance for every bone
+		uint32_t num_shell_distances;
+		float shell_distance;
+		uint8_t* bone_errors;					// null, or the error of bone b of instance i at bone_errors + i * bone_error_stride_bytes + 4 * b
+		uint64_t bone_error_stride_bytes;
+		pose_error_record* errors;				// [num_instances]
+		uint32_t num_instances;
+		uint32_t additive_format;
+		uint32_t lds_quads_per_image, lds_bytes_per_instance, packed_block_shape;		// as transform_poses_kernel takes them, two images per instance
+		unsigned long long* rejected_count;
+	};
+
+	// rtm::qvv_mul_point3: quat_mul_vector3(scale * point, rotation) + translation, all three components of the product multiplied
+	__device__ __forceinline__ float4 qvv_mul_point3(float x, float y, float z, const qvv& transform)
+	{
+		const float4 scaled = make_float4(transform.scale.x * x, transform.scale.y * y, transform.scale.z * z, 0.0f);
+		const float4 rotated = quat_mul_vector3(scaled, transform.rotation);
+		return make_float4(rotated.x + transform.translation.x, rotated.y + transform.translation.y, rotated.z + transform.translation.z, 0.0f);
+	}
+
+	// how far the point (x, y, z) of a bone moved between the raw and the lossy transform
+	__device__ __forceinline__ float shell_point_error(float x, float y, float z, const qvv& raw, const qvv& lossy)
+	{
+		const float4 raw_point = qvv_mul_point3(x, y, z, raw), lossy_point = qvv_mul_point3(x, y, z, lossy);
+		const float dx = lossy_point.x - raw_point.x, dy = lossy_point.y - raw_point.y, dz = lossy_point.z - raw_point.z;
+		return sqrtf(((dx * dx) + (dy * dy)) + (dz * dz));
+	}
+
+	// qvvf_transform_error_metric::calculate_error (compression/transform_error_metrics.h:335-358): the three points at the shell distance
+	__device__ __forceinline__ float shell_error(float distance, const qvv& raw, const qvv& lossy)
+	{
+		const float error_x = shell_point_error(distance, 0.0f, 0.0f, raw, lossy);
+		const float error_y = shell_point_error(0.0f, distance, 0.0f, raw, lossy);
+		const float error_z = shell_point_error(0.0f, 0.0f, distance, raw, lossy);
+		const float error_xy = error_x > error_y ? error_x : error_y;
+		return error_xy > error_z ? error_xy : error_z;
+	}
+
+	// The wave's greatest error and, among equal ones, the lowest key (a bone, an instance), left in every lane: a butterfly over a total
+	// order -- no error here is a NaN (a lane's record starts at -1 and only takes what compares greater) --, so the result is the same
+	// whatever the order of the steps. `payload` travels with the winner.
+	__device__ __forceinline__ void wave_reduce_worst(float& error, uint32_t& key, uint32_t& payload)
+	{
+		#pragma unroll
+		for (int offset = int(k_wave_size) / 2; offset != 0; offset >>= 1)
+		{
+			const float other_error = __shfl_xor(error, offset);
+			const uint32_t other_key = uint32_t(__shfl_xor(int(key), offset)), other_payload = uint32_t(__shfl_xor(int(payload), offset));
+			const bool take = other_error > error || (other_error == error && other_key < key);
+			error = take ? other_error : error;
+			key = take ? other_key : key;
+			payload = take ? other_payload : payload;
+		}
+	}
+
+	// transform_poses_kernel's front twice over: TWO waves per instance as consumer_wave_of lays them out -- role 0 holds the raw row in the
+	// slot's image, role 1 the lossy row in its base image --, the skeleton's record on the scalar unit, the refusal in front of any load of
+	// a row, each row into its image by DMA. Then what finish_consumer_poses does to one image is done to both, without a store:
+	//   kBase          apply_additive_to_base against the base row in HBM, each wave over its own image (the counter moves as for two launches)
+	//   kObjectSpace   walk_hierarchy as it is, by the two waves of ONE slot (it rotates with the workgroup index): role 0 walks every raw
+	//                  image of the workgroup, role 1 every lossy one, lanes <-> (slot, transform of the step) over the schedule made for
+	//                  this many slots. short_exact is 0 and the matrix route is compiled in, as for every pose of a caller's: the images
+	//                  hold the bits aclhip_transform_poses_batch would have written.
+	// Behind the workgroup's barrier both images of a slot are final and its two waves measure: a bone per lane, the passes of 64 bones dealt
+	// out in turn (role 0 the even ones), per lane the scan of track_error.impl.h:358-375 over its bones in ascending order, then the wave's
+	// record by wave_reduce_worst; role 1 hands its record over in LDS and role 0 writes the instance's.
+	// Every wave of the workgroup reaches every __syncthreads: a wave without work (past the batch, refused, no bones) has num_bones 0.
+	template<bool kObjectSpace, bool kBase>
+	__global__ __launch_bounds__(k_consumer_max_waves * k_wave_size) void measure_pose_error_kernel(pose_error_launch launch)
+	{
+		extern __shared__ __attribute__((aligned(16))) uint8_t dynamic_lds[];
+		// packed_block_shape: log2 of the instances per workgroup (bits 0..7) | words of LDS reserved for the shared walk schedule (bits 8..31)
+		const uint32_t log2_instances_per_block = launch.packed_block_shape & 0xFFu;
+		__shared__ consumer_walk_slots walk;		// (what the host subtracts from the LDS it may ask for: host_consumers.inl)
+		__shared__ pose_error_record second_wave_record[k_consumer_max_instances];
+
+		const consumer_wave wave = consumer_wave_of(log2_instances_per_block, launch.lds_bytes_per_instance, launch.lds_quads_per_image);
+		const uint32_t lane = wave.lane, instance = wave.instance, role = wave.role, slot = wave.slot;
+		f32x4* const own_image = role == 0 ? wave.image : wave.base_image;
+		uint32_t num_bones = 0;
+
+		if (instance < launch.num_instances)
+		{
+			// the skeleton's record on the scalar unit; record 0 is never handed out and a cleared record is an unknown or retired skeleton
+			const uint32_t skeleton_id = launch.instance_skeletons != nullptr ? as_constant(launch.instance_skeletons)[instance] : launch.skeleton;
+			const device_skeleton skeleton = load_skeleton_fields(launch.skeletons, skeleton_id < launch.num_skeletons ? skeleton_id : 0);
+			const uint32_t skeleton_bones = skeleton.num_bones;
+			const uint64_t row_bytes = uint64_t(skeleton_bones) * 48u;
+
+			// refused, wave uniform and in front of any load of a row: what transform_poses_kernel refuses, over the strides of this launch,
+			// and a bone without a place in the error row or in the shell table. Both waves of the instance decide alike.
+			const bool refused = skeleton_id >= launch.num_skeletons || skeleton.reference_pose == nullptr || (kObjectSpace && skeleton.hierarchy == nullptr)
+				|| row_bytes > launch.raw_pose_stride_bytes || row_bytes > launch.lossy_pose_stride_bytes || (kBase && row_bytes > launch.base_pose_stride_bytes)
+				|| (launch.bone_errors != nullptr && uint64_t(skeleton_bones) * 4u > launch.bone_error_stride_bytes)
+				|| (launch.shell_distances != nullptr && skeleton_bones > launch.num_shell_distances) || skeleton_bones * 3u > launch.lds_quads_per_image;
+			if (refused || skeleton_bones == 0)
+			{
+				// "not measured" (refused) and the reference's invalid_track_error (no bones) are the same record
+				if (role == 0 && lane == 0)
+				{
+					if (refused)
+						atomicAdd(launch.rejected_count, 1ull);
+					launch.errors[instance] = pose_error_record{ -1.0f, k_no_bone };
+				}
+			}
+			else
+			{
+				num_bones = skeleton_bones;
+				// the walk schedule first: its words travel global -> LDS while the rows do
+				if (kObjectSpace && role == 0)
+					request_walk_schedule(skeleton.hierarchy, log2_instances_per_block, launch.packed_block_shape >> 8, wave.shared_schedule, slot, lane, walk);
+				// the wave's row straight into its image by DMA, lanes <-> consecutive quads (the LDS side of a piece is wave uniform + lane * 16)
+				const uint8_t* row = role == 0 ? launch.raw_poses + uint64_t(instance) * launch.raw_pose_stride_bytes
+					: launch.lossy_poses + uint64_t(instance) * launch.lossy_pose_stride_bytes;
+				const f32x4* source = reinterpret_cast<const f32x4*>(row);
+				const uint32_t num_quads = num_bones * 3u;
+				for (uint32_t base = 0; base < num_quads; base += k_wave_size)
+				{
+					if (base + lane < num_quads)
+						__builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(source + base + lane),
+							(__attribute__((address_space(3))) void*)(own_image + base), 16, 0, 0);
+				}
+			}
+		}
+		wave_lds_barrier();		// the wave's row is complete (vmcnt)
+
+		unsigned long long* const negative_scale_count = launch.rejected_count + 1;
+		if constexpr (kBase)
+		{
+			// finish_consumer_poses' combine, the wave over its own image: the image is the additive pose, the base row is read per transform
+			const f32x4* base_row = reinterpret_cast<const f32x4*>(launch.base_poses + uint64_t(instance) * launch.base_pose_stride_bytes);
+			for (uint32_t bone = lane; bone < num_bones; bone += k_wave_size)
+			{
+				const qvv additive = load_qvv(own_image, bone);
+				const qvv base = load_qvv(base_row, bone);
+				store_qvv(own_image, bone, apply_additive_to_base<true>(launch.additive_format, base, additive));
+				// additive_clip_format8::relative is a qvv_mul (core/additive_utils.h:128-160)
+				const uint64_t mirrored = __ballot(launch.additive_format == 1 && qvv_mul_takes_matrix_path(additive, base));
+				if (mirrored != 0 && lane == uint32_t(__builtin_ctzll(mirrored)))
+					atomicAdd(negative_scale_count, (unsigned long long)__builtin_popcountll(mirrored));
+			}
+		}
+
+		if constexpr (kObjectSpace)
+		{
+			if (lane == 0 && role == 0)
+			{
+				// (a slot with work has its steps and its schedule already: request_walk_schedule)
+				if (num_bones == 0)
+				{
+					walk.levels[slot] = 0;
+					walk.schedules[slot] = nullptr;
+				}
+			}
+			__syncthreads();
+			// the two waves of one slot walk, the others wait at the barrier below
+			if (slot == (blockIdx.x & ((1u << log2_instances_per_block) - 1u)))
+			{
+				const uint32_t walk_slot = lane & ((1u << log2_instances_per_block) - 1u);
+				const uint32_t first = lane >> log2_instances_per_block;
+				f32x4* slot_image = reinterpret_cast<f32x4*>(dynamic_lds + size_t(walk_slot) * launch.lds_bytes_per_instance) + size_t(role) * launch.lds_quads_per_image;
+				const uint32_t slot_steps = walk.levels[walk_slot] & 0x7FFFFFFFu;
+				const bool slot_schedule_is_shared = (walk.levels[walk_slot] & 0x80000000u) == 0;
+				const uint32_t* slot_schedule = walk.schedules[walk_slot];
+				__builtin_amdgcn_s_setprio(3);
+				const uint64_t walkers = __ballot(slot_steps != 0);
+				if (walkers != 0)
+				{
+					// all instances that walk follow the same schedule? then the shared LDS copy is theirs; otherwise each reads its own
+					// from global memory (finish_consumer_poses)
+					const uint32_t leader = uint32_t(__builtin_ctzll(walkers));
+					const uint64_t mine = reinterpret_cast<uint64_t>(slot_schedule);
+					const uint64_t first_schedule = (uint64_t(__shfl(uint32_t(mine >> 32), int(leader))) << 32) | __shfl(uint32_t(mine), int(leader));
+					const bool shared_copy = __all(int(slot_steps == 0 || (mine == first_schedule && slot_schedule_is_shared))) != 0;
+					if (shared_copy)
+						walk_hierarchy<false, true, false, false>(static_cast<const uint32_t*>(wave.shared_schedule), slot_steps, first, slot_image, lane, negative_scale_count);
+					else
+						walk_hierarchy<false, true, false, false>(as_constant(slot_schedule), slot_steps, first, slot_image, lane, negative_scale_count);
+				}
+				__builtin_amdgcn_s_setprio(0);
+			}
+		}
+		__syncthreads();		// both images of every slot are final
+
+		// the measure: lanes <-> bones, the passes of 64 dealt out to the instance's two waves in turn
+		float worst_error = -1.0f;
+		uint32_t worst_bone = k_no_bone;
+		{
+			const f32x4* raw_image = wave.image;
+			const f32x4* lossy_image = wave.base_image;
+			const ACLHIP_CONSTANT float* shell_distances = as_constant(launch.shell_distances);
+			float* bone_errors = launch.bone_errors != nullptr ? reinterpret_cast<float*>(launch.bone_errors + uint64_t(instance) * launch.bone_error_stride_bytes) : nullptr;
+			for (uint32_t bone = role * k_wave_size + lane; bone < num_bones; bone += 2u * k_wave_size)
+			{
+				const float distance = shell_distances != nullptr ? shell_distances[bone] : launch.shell_distance;
+				const float error = shell_error(distance, load_qvv(raw_image, bone), load_qvv(lossy_image, bone));
+				if (bone_errors != nullptr)
+					bone_errors[bone] = error;
+				// (a NaN compares false: it never wins)
+				if (error > worst_error)
+				{
+					worst_error = error;
+					worst_bone = bone;
+				}
+			}
+		}
+		uint32_t unused_payload = 0;
+		wave_reduce_worst(worst_error, worst_bone, unused_payload);
+		if (role == 1 && lane == 0)
+			second_wave_record[slot] = pose_error_record{ worst_error, worst_bone };
+		__syncthreads();
+		if (role == 0 && lane == 0 && num_bones != 0)
+		{
+			const pose_error_record other = second_wave_record[slot];
+			const bool take = other.error > worst_error || (other.error == worst_error && other.bone < worst_bone);
+			launch.errors[instance] = take ? other : pose_error_record{ worst_error, worst_bone };
+		}
+	}
+
+	// The launch's worst record (aclhip_pose_error_worst): the scan of the instances' records in ascending order -- the greatest error,
+	// its bone, the lowest instance that has it; {-1, ACLHIP_NO_BONE, 0xFFFFFFFF, 0} when no record has an error >= 0. ONE workgroup behind
+	// the measure on the same stream: a thread scans every 1024th record, the waves reduce, the first wave reduces the waves.
+	constexpr uint32_t k_pose_error_worst_threads = 1024;
+	__global__ __launch_bounds__(k_pose_error_worst_threads) void pose_error_worst_kernel(const pose_error_record* errors, uint32_t num_instances, u32x4* worst)
+	{
+		__shared__ float wave_errors[k_pose_error_worst_threads / k_wave_size];
+		__shared__ uint32_t wave_instances[k_pose_error_worst_threads / k_wave_size], wave_bones[k_pose_error_worst_threads / k_wave_size];
+		const uint32_t lane = threadIdx.x & (k_wave_size - 1), wave_in_block = threadIdx.x / k_wave_size;
+		float worst_error = -1.0f;
+		uint32_t worst_instance = 0xFFFFFFFFu, worst_bone = k_no_bone;
+		for (uint32_t instance = threadIdx.x; instance < num_instances; instance += k_pose_error_worst_threads)
+		{
+			const pose_error_record record = errors[instance];
+			if (record.error > worst_error)
+			{
+				worst_error = record.error;
+				worst_instance = instance;
+				worst_bone = record.bone;
+			}
+		}
+		wave_reduce_worst(worst_error, worst_instance, worst_bone);
+		if (lane == 0)
+		{
+			wave_errors[wave_in_block] = worst_error;
+			wave_instances[wave_in_block] = worst_instance;
+			wave_bones[wave_in_block] = worst_bone;
+		}
+		__syncthreads();
+		if (wave_in_block != 0)
+			return;
+		const bool has_record = lane < k_pose_error_worst_threads / k_wave_size;
+		worst_error = has_record ? wave_errors[lane] : -1.0f;
+		worst_instance = has_record ? wave_instances[lane] : 0xFFFFFFFFu;
+		worst_bone = has_record ? wave_bones[lane] : k_no_bone;
+		wave_reduce_worst(worst_error, worst_instance, worst_bone);
+		if (lane == 0)
+			*worst = u32x4{ __float_as_uint(worst_error), worst_bone, worst_instance, 0u };
 	}

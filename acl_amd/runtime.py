@@ -51,6 +51,7 @@ EXPORTED_SYMBOLS = [
     "aclhip_transform_poses_batch",
     "aclhip_blend_poses_batch",
     "aclhip_inverse_transform_poses_batch",
+    "aclhip_measure_pose_error_batch",
 ]
 
 
@@ -148,6 +149,31 @@ class PoseBufferInverse(ctypes.Structure):
     _fields_ = [
         ("skeleton", ctypes.c_uint32), ("instance_skeletons", ctypes.c_void_p), ("local_space", ctypes.c_uint32), ("additive_format", ctypes.c_uint32),
         ("base_poses", ctypes.c_void_p), ("base_pose_stride_bytes", ctypes.c_uint64), ("reserved", ctypes.c_uint64 * 3),
+    ]
+
+
+class PoseError(ctypes.Structure):
+    """aclhip_pose_error: the worst bone of one instance; {-1, NO_BONE}: not measured, or nothing to measure"""
+    _fields_ = [("error", ctypes.c_float), ("bone", ctypes.c_uint32)]
+
+
+class PoseErrorWorst(ctypes.Structure):
+    """aclhip_pose_error_worst: the worst record of a launch"""
+    _fields_ = [("error", ctypes.c_float), ("bone", ctypes.c_uint32), ("instance", ctypes.c_uint32), ("reserved", ctypes.c_uint32)]
+
+
+POSE_ERROR_DTYPE = np.dtype([("error", np.float32), ("bone", np.uint32)])                  # aclhip_pose_error as a numpy record
+POSE_ERROR_WORST_DTYPE = np.dtype([("error", np.float32), ("bone", np.uint32), ("instance", np.uint32), ("reserved", np.uint32)])
+NO_BONE = 0xFFFFFFFF        # ACLHIP_NO_BONE
+
+
+class PoseErrorDesc(ctypes.Structure):
+    """aclhip_pose_error_desc; every pointer is a device address or None"""
+    _fields_ = [
+        ("skeleton", ctypes.c_uint32), ("instance_skeletons", ctypes.c_void_p), ("object_space", ctypes.c_uint32), ("additive_format", ctypes.c_uint32),
+        ("base_poses", ctypes.c_void_p), ("base_pose_stride_bytes", ctypes.c_uint64), ("shell_distances", ctypes.c_void_p), ("num_shell_distances", ctypes.c_uint32),
+        ("shell_distance", ctypes.c_float), ("bone_errors", ctypes.c_void_p), ("bone_error_stride_bytes", ctypes.c_uint64), ("worst", ctypes.c_void_p),
+        ("reserved", ctypes.c_uint64 * 2),
     ]
 
 
@@ -354,6 +380,7 @@ def load_library():
     lib.aclhip_transform_poses_batch.argtypes = [vp, vp, u64, u32, ctypes.POINTER(PoseBufferConsumers), vp, u64, vp]
     lib.aclhip_blend_poses_batch.argtypes = [vp, ctypes.POINTER(PoseBufferBlend), u32, vp, u64, vp]
     lib.aclhip_inverse_transform_poses_batch.argtypes = [vp, vp, u64, u32, ctypes.POINTER(PoseBufferInverse), vp, u64, vp]
+    lib.aclhip_measure_pose_error_batch.argtypes = [vp, vp, u64, vp, u64, u32, ctypes.POINTER(PoseErrorDesc), vp, vp]
     _lib = lib
     return lib
 
@@ -820,6 +847,12 @@ class Context:
         self._check(self._lib.aclhip_inverse_transform_poses_batch(self._handle, source_poses_ptr, source_pose_stride_bytes, num_instances,
                                                                    ctypes.byref(inverse) if inverse is not None else None, poses_ptr, pose_stride_bytes, stream))
 
+    def measure_pose_error(self, raw_poses_ptr, raw_pose_stride_bytes, lossy_poses_ptr, lossy_pose_stride_bytes, num_instances, desc, errors_ptr, stream=None):
+        """aclhip_measure_pose_error_batch: per instance the worst bone's shell error between two QVV48 pose buffers (device addresses) into
+        the 8 byte records at errors_ptr; `desc` is a PoseErrorDesc (per bone errors and the launch's worst record on request)."""
+        self._check(self._lib.aclhip_measure_pose_error_batch(self._handle, raw_poses_ptr, raw_pose_stride_bytes, lossy_poses_ptr, lossy_pose_stride_bytes, num_instances,
+                                                              ctypes.byref(desc) if desc is not None else None, errors_ptr, stream))
+
     def decompress_poses_mapped(self, clips, sample_times, skeletons, maps, num_bones, additive_format=ADDITIVE_NONE, object_space=False, base_clips=None,
                                 base_sample_times=None, base_maps=None, base_poses=None, params=None, out=None, instance_rounding=None, instance_looping=None,
                                 blend_clips=None, blend_sample_times=None, blend_maps=None, blend_weights=None, flags=0):
@@ -1158,3 +1191,42 @@ class Context:
         written, read = ctypes.c_uint64(0), ctypes.c_uint64(0)
         self._check(self._lib.aclhip_batch_algorithmic_bytes(self._handle, clips.ctypes.data, clips.size, ctypes.byref(written), ctypes.byref(read)))
         return written.value, read.value
+
+
+def clip_error(ctx, clip_a, clip_b, skeleton, shells, object_space=True, params_a=None, params_b=None):
+    """acl::calculate_compression_error's loop (impl/track_error.impl.h:219-387) as three launches: both registered clips decoded at
+    min(i / sample_rate, duration) for every sample i of clip_a -- instances are samples --, then aclhip_measure_pose_error_batch over the
+    two buffers with the launch's worst record. clip_a plays the raw clip and clip_b the lossy one; both have the skeleton's bones as
+    their tracks, in its order. `shells` is one shell distance for every bone or an array of one per bone. Returns (bone, error,
+    sample_time) of the worst bone of the worst sample -- the lowest sample and bone among equals; (NO_BONE, -1.0, nan) when nothing could
+    be measured. Synchronous; the buffers are torch tensors on the context's device."""
+    import torch
+    device = torch.device("cuda", ctx.device_index)
+    info = ctx.clip_info(clip_a)
+    num_bones, num_samples = int(info.num_tracks), int(info.num_samples)
+    sample_times = np.minimum(np.arange(num_samples, dtype=np.float32) / np.float32(info.sample_rate), np.float32(info.duration)).astype(np.float32)
+    if num_samples == 0:
+        return NO_BONE, -1.0, float("nan")
+    stride = max(num_bones, 1) * 48
+    d_times = torch.from_numpy(sample_times).to(device)
+    d_poses = [torch.zeros((num_samples, stride // 4), dtype=torch.float32, device=device) for _ in range(2)]
+    d_errors = torch.zeros((num_samples, 2), dtype=torch.int32, device=device)
+    d_worst = torch.zeros(4, dtype=torch.int32, device=device)
+    stream = torch.cuda.current_stream(device)
+    for clip, d_pose, params in ((clip_a, d_poses[0], params_a), (clip_b, d_poses[1], params_b)):
+        d_clips = torch.full((num_samples,), int(clip), dtype=torch.int32, device=device)
+        ctx.decompress_tracks_batch(d_clips.data_ptr(), d_times.data_ptr(), num_samples, d_pose.data_ptr(), stride, params=params, stream=stream.cuda_stream)
+    desc = PoseErrorDesc()
+    desc.skeleton, desc.object_space = int(skeleton), 1 if object_space else 0
+    if np.ndim(shells) == 0:
+        desc.shell_distance = float(shells)
+    else:
+        d_shells = torch.from_numpy(np.ascontiguousarray(shells, dtype=np.float32)).to(device)
+        desc.shell_distances, desc.num_shell_distances = d_shells.data_ptr(), d_shells.numel()
+    desc.worst = d_worst.data_ptr()
+    ctx.measure_pose_error(d_poses[0].data_ptr(), stride, d_poses[1].data_ptr(), stride, num_samples, desc, d_errors.data_ptr(), stream=stream.cuda_stream)
+    stream.synchronize()
+    worst = d_worst.cpu().numpy().view(POSE_ERROR_WORST_DTYPE)[0]
+    if int(worst["instance"]) == 0xFFFFFFFF:
+        return NO_BONE, -1.0, float("nan")
+    return int(worst["bone"]), float(worst["error"]), float(sample_times[int(worst["instance"])])

@@ -202,7 +202,8 @@ const char* aclhip_last_error_message(const aclhip_context* context);
  * 6: ACLHIP_DEFAULT_BIND_POSE, aclhip_clip_metadata_info; ACLHIP_ERROR_UNSUPPORTED_FORMAT no longer covers the full-precision formats;
  * track maps -- aclhip_track_map_info, aclhip_track_mapping and their entry points -- were ADDED without a bump: no existing struct or
  * entry point changed shape, so a caller built against the earlier header 6 hands over nothing of another shape; the same goes for
- * skeletons -- aclhip_skeleton_info, aclhip_pose_mapping and their entry points).
+ * skeletons -- aclhip_skeleton_info, aclhip_pose_mapping and their entry points -- and for the pose error measure -- aclhip_pose_error,
+ * aclhip_pose_error_worst, aclhip_pose_error_desc and aclhip_measure_pose_error_batch).
  * A caller compiled against another header would hand over structs of another shape; aclhip_abi_version() says what the LIBRARY was
  * built with, and the C++ mirror (aclhip.hpp) refuses to create a context when the two differ. */
 #define ACLHIP_ABI_VERSION 6u
@@ -1272,6 +1273,89 @@ typedef struct aclhip_pose_buffer_inverse
  * of the HBM peak (tools/pose_buffer_inverse.py, profiles/pose_buffer_inverse.md; DESIGN.md 4.7 "Inverse pose buffers"). */
 aclhip_status aclhip_inverse_transform_poses_batch(aclhip_context* context, const void* source_poses, uint64_t source_pose_stride_bytes,
 	uint32_t num_instances, const aclhip_pose_buffer_inverse* inverse, void* poses, uint64_t pose_stride_bytes, void* stream);
+
+/* ---- pose error: how far two pose buffers are apart, measured on a shell around every bone ----------
+ * The other consumer of a decoded pose in the reference is its error measure: acl::calculate_compression_error
+ * (compression/track_error.h, impl/track_error.impl.h:219-387) decodes every sample of a clip twice, raw and lossy, takes both poses to
+ * object space and asks qvvf_transform_error_metric::calculate_error (compression/transform_error_metrics.h:335-358) per bone how far
+ * three virtual vertices at the bone's shell_distance moved; the worst bone of the worst sample is the track_error acl_compressor prints.
+ * aclhip_measure_pose_error_batch is that measure over two pose buffers the caller filled -- two decodes of a clip, a pose before and
+ * after an IK pass, a full and a stripped database tier -- with an 8 byte record per instance and, on request, every bone's error and the
+ * worst record of the launch. (ABI version 6 still: added structs and an added function, no existing struct changed.) */
+typedef struct aclhip_pose_error { float error; uint32_t bone; } aclhip_pose_error;		/* 8 bytes */
+typedef struct aclhip_pose_error_worst { float error; uint32_t bone; uint32_t instance; uint32_t reserved; } aclhip_pose_error_worst;	/* 16 bytes */
+#define ACLHIP_NO_BONE 0xFFFFFFFFu
+
+typedef struct aclhip_pose_error_desc
+{
+	aclhip_skeleton skeleton;					/*  0  for every instance when instance_skeletons is NULL */
+	const aclhip_skeleton* instance_skeletons;	/*  8  DEVICE [num_instances] or NULL */
+	uint32_t object_space;						/* 16  1: both poses through local_to_object_space first (the reference's measure); 0: local space error */
+	uint32_t additive_format;					/* 20  aclhip_additive_format; NONE: no base buffer */
+	const void* base_poses;						/* 24  DEVICE or NULL: QVV48, skeleton order, local space */
+	uint64_t base_pose_stride_bytes;			/* 32 */
+	const float* shell_distances;				/* 40  DEVICE [num_shell_distances] or NULL: one per bone, shared by the launch */
+	uint32_t num_shell_distances;				/* 48 */
+	float shell_distance;						/* 52  for every bone when shell_distances is NULL */
+	float* bone_errors;							/* 56  DEVICE or NULL: error of bone b of instance i at (char*)bone_errors + i * bone_error_stride_bytes + 4 * b */
+	uint64_t bone_error_stride_bytes;			/* 64 */
+	aclhip_pose_error_worst* worst;				/* 72  DEVICE or NULL: one record for the launch */
+	uint64_t reserved[2];						/* 80  0 */
+} aclhip_pose_error_desc;						/* 96 bytes */
+
+/* The definition. Instance i has skeleton S (desc->skeleton, or instance_skeletons[i]) with B bones and parents P; R and Y are the B QVV48
+ * records at raw_poses + i * raw_pose_stride_bytes and lossy_poses + i * lossy_pose_stride_bytes.
+ *   1. With an additive format and base row Bs (the B records at base_poses + i * base_pose_stride_bytes):
+ *      R'[b] = apply_additive_to_base(format, base = Bs[b], additive = R[b]), and Y' from Y alike -- the roles of
+ *      track_error.impl.h:351-352, the arithmetic of aclhip_transform_poses_batch's step 2. Otherwise R' = R and Y' = Y.
+ *   2. With object_space: Ro = local_to_object_space(P, R') and Yo = local_to_object_space(P, Y'), bit for bit what
+ *      aclhip_transform_poses_batch would write for that buffer: the same walk, rtm::qvv_mul's matrix route where a scale of either side
+ *      is negative, the correctly rounded normalize (short_exact 0); aclhip_get_negative_scale_count moves as it would for those two
+ *      launches (steps 1 and 2). Otherwise Ro = R' and Yo = Y'.
+ *   3. The error of bone b, with d = shell_distances[b], or shell_distance when the table is NULL, and the three points p_0 = (d, 0, 0),
+ *      p_1 = (0, d, 0), p_2 = (0, 0, d) (transform_error_metrics.h:335-358):
+ *        point(p, t) = quat_mul_vector3(t.scale * p, t.rotation) + t.translation            rtm::qvv_mul_point3; quat_mul_vector3(v, q) =
+ *                      quat_mul(quat_mul(conjugate(q), (v, 0)), q), the function the inverse launch uses for a translation
+ *        e_k         = sqrt((dx * dx + dy * dy) + dz * dz) with (dx, dy, dz) = point(p_k, Yo[b]) - point(p_k, Ro[b])
+ *        error[b]    = max(max(e_0, e_1), e_2) with max(a, b) = a > b ? a : b
+ *      fp32, one IEEE operation at a time, never fused, the correctly rounded sqrt; all three components of t.scale * p are multiplied,
+ *      the zero ones too.
+ *   4. errors[i] is the scan of track_error.impl.h:358-375: it starts from { -1, ACLHIP_NO_BONE }, walks the bones in ascending order and
+ *      takes bone b when error[b] > the record's error. A NaN never wins; ties go to the lowest bone; with B = 0, or with every error a
+ *      NaN, the record stays { -1, ACLHIP_NO_BONE } -- the reference's invalid_track_error.
+ *   5. With bone_errors: error[b] is stored for every b < B, a NaN as a NaN (its payload is not specified); bytes of the row behind 4 * B
+ *      are untouched.
+ *   6. With worst: the one record of the launch is the same scan over errors[0 .. num_instances) in ascending instance order -- the
+ *      greatest error, its bone, the lowest instance that has it; { -1, ACLHIP_NO_BONE, 0xFFFFFFFF, 0 } when no instance has an error
+ *      >= 0, num_instances == 0 included. It is deterministic and written by the call itself, stream ordered (a second launch of one
+ *      workgroup over the records): the caller initialises nothing.
+ *   Against the reference itself: identical, but for its x86 normalize in the walk, which starts from the reciprocal square root estimate
+ *   and so differs from the correctly rounded one by a few ulp per level of the hierarchy (the CPU oracle the tests compare with
+ *   says the same of its local_to_object_space). That difference is stated here and not tested.
+ *   Refused and counted (aclhip_get_rejected_instance_count): an unknown or retired skeleton handle (0 included); object_space on a
+ * skeleton without hierarchy; B * 48 larger than any stride in use (raw, lossy, base with an additive format); 4 * B larger than
+ * bone_error_stride_bytes; B larger than num_shell_distances when the table is given; B beyond the launch's LDS images. A refused
+ * instance's errors[i] IS written, as { -1, ACLHIP_NO_BONE }: unlike a pose row this record says "not measured", and the worst scan skips
+ * it by its sign. Its bone_errors row is untouched. The refusal comes in front of any load of a row.
+ *   ACLHIP_ERROR_INVALID_ARGUMENT, decided before any device call, each with a message (with or without a context): desc, raw_poses,
+ * lossy_poses or errors == NULL; no skeleton at all; an unknown format; a format other than NONE without base_poses, or the reverse;
+ * shell_distances with num_shell_distances == 0; bone_errors with a stride that is 0 or no multiple of 4; pointers or strides of pose
+ * rows that are not 16 byte aligned; errors not 8 byte aligned; worst not 16 byte aligned; reserved fields that are not 0; a shape that
+ * does not fit 160 KiB of LDS; any output range (errors, bone_errors, worst) that overlaps an input range or another output. raw, lossy
+ * and base are only read and may overlap each other freely: the same buffer twice gives error 0 and bone 0.
+ *   The launch's shape comes from min(raw_pose_stride_bytes, lossy_pose_stride_bytes) / 48 (slots per LDS image, two images per
+ * instance). Registered clips play no part. The launch goes on `stream`, can be captured into a graph, and uploads nothing.
+ *   Out of scope (nothing here precludes them): qvvf_matrix3x4f_transform_error_metric and the _no_scale variants; a decode fused into the
+ * measure; QVV40 / QV32 rows; the C++ mirror in aclhip.hpp; instance lists.
+ *   What it costs (one MI355X, 65 536 x 100 bones, object space, medians of three interleaved rounds of 20 launches): 293 us for the
+ * records alone, 309 us with the worst record, 311 us with every bone's error as well, against 222 us for the two
+ * aclhip_transform_poses_batch object space launches on the same two buffers in the same rounds -- 1.32 to 1.40 x what a caller pays
+ * today before it has compared anything, and nothing is copied to the host. The launch moves two row reads and 8 bytes per instance
+ * out, 630 MB: 2.1 TB/s, 0.27 of the HBM peak, so its reads do not bound it; no counter run has been taken yet
+ * (tools/pose_error.py, profiles/pose_error.md; DESIGN.md 4.7 "Pose error"). */
+aclhip_status aclhip_measure_pose_error_batch(aclhip_context* context, const void* raw_poses, uint64_t raw_pose_stride_bytes,
+	const void* lossy_poses, uint64_t lossy_pose_stride_bytes, uint32_t num_instances, const aclhip_pose_error_desc* desc,
+	aclhip_pose_error* errors /* DEVICE [num_instances], required */, void* stream);
 
 /* ---- multi-GPU ---------------------------------------------------------------------------------- */
 
