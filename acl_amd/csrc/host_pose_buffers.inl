@@ -1,6 +1,7 @@
 // host_pose_buffers.inl -- part of aclhip.hip (one translation unit; included there, in this order, not compiled on its own).
 // Host side: the pose consumers over a caller's pose buffers (aclhip_transform_poses_batch, aclhip_blend_poses_batch,
-// aclhip_inverse_transform_poses_batch, aclhip_measure_pose_error_batch; kernels_pose_buffers.inl).
+// aclhip_inverse_transform_poses_batch, aclhip_measure_pose_error_batch and its _metric form, aclhip_pose_matrices_batch;
+// kernels_pose_buffers.inl).
 
 namespace
 {
@@ -448,10 +449,9 @@ namespace
 		return ACLHIP_OK;
 	}
 
-	template<bool kObjectSpace, bool kBase>
-	aclhip_status launch_measure_pose_error_kernel(aclhip_context* context, const consumer_launch_shape& shape, uint32_t num_blocks, hipStream_t stream, const pose_error_launch& launch)
+	template<class kernel_type>
+	aclhip_status launch_measure_pose_error_kernel(aclhip_context* context, kernel_type kernel, const consumer_launch_shape& shape, uint32_t num_blocks, hipStream_t stream, const pose_error_launch& launch)
 	{
-		const auto kernel = measure_pose_error_kernel<kObjectSpace, kBase>;
 		// above the default limit of dynamic LDS the kernel has to be told
 		if (shape.lds_bytes > 64 * 1024 - 128)
 			ACLHIP_CHECK_HIP(context, hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, int(k_consumer_lds_bytes)));
@@ -464,7 +464,7 @@ namespace
 	// The launch: shaped by its two input rows alone; the skeleton table is filled in under the registry lock; nothing is uploaded. The
 	// worst record is a second, one workgroup launch over the instances' records on the same stream -- the only launch of a batch of none.
 	aclhip_status launch_pose_error(aclhip_context* context, const void* raw_poses, uint64_t raw_pose_stride_bytes, const void* lossy_poses, uint64_t lossy_pose_stride_bytes,
-		uint32_t num_instances, const aclhip_pose_error_desc& desc, aclhip_pose_error* errors, hipStream_t stream)
+		uint32_t num_instances, const aclhip_pose_error_desc& desc, uint32_t metric, aclhip_pose_error* errors, hipStream_t stream)
 	{
 		std::shared_lock<std::shared_mutex> lock(context->mutex);		// see launch_tracks
 		if (num_instances != 0)
@@ -504,10 +504,12 @@ namespace
 
 			const uint32_t instances_per_block = 1u << shape.log2_instances_per_block;
 			const uint32_t num_blocks = (num_instances + instances_per_block - 1) / instances_per_block;
-			// four instantiations: object / local x base / none
-			const aclhip_status status = object_space
-				? (has_base ? launch_measure_pose_error_kernel<true, true>(context, shape, num_blocks, stream, launch) : launch_measure_pose_error_kernel<true, false>(context, shape, num_blocks, stream, launch))
-				: (has_base ? launch_measure_pose_error_kernel<false, true>(context, shape, num_blocks, stream, launch) : launch_measure_pose_error_kernel<false, false>(context, shape, num_blocks, stream, launch));
+			// four instantiations: object / local x base / none, and the matrix metric's two: object / local (it takes no base)
+			const auto kernel = metric == ACLHIP_METRIC_QVVF_MATRIX3X4F
+				? (object_space ? measure_pose_error_kernel<true, false, true> : measure_pose_error_kernel<false, false, true>)
+				: object_space ? (has_base ? measure_pose_error_kernel<true, true, false> : measure_pose_error_kernel<true, false, false>)
+				: (has_base ? measure_pose_error_kernel<false, true, false> : measure_pose_error_kernel<false, false, false>);
+			const aclhip_status status = launch_measure_pose_error_kernel(context, kernel, shape, num_blocks, stream, launch);
 			if (status != ACLHIP_OK)
 				return status;
 		}
@@ -520,6 +522,96 @@ namespace
 			ACLHIP_CHECK_HIP(context, hipGetLastError());
 		}
 		return ACLHIP_OK;
+	}
+
+	// ---- 3x4 matrices of a pose buffer (aclhip_pose_matrices_batch; pose_matrices_kernel) -------------------------------------------------
+
+	// Both rows set the shape of the launch: an image holds min(local_pose_stride_bytes / 48, matrix_stride_bytes / 64) transforms (a
+	// matrix takes the three quads of its QVV record), and the words of the walk schedule on top once the context is known
+	aclhip_status pose_matrices_launch_shape_of(aclhip_context* context, uint64_t local_pose_stride_bytes, uint64_t matrix_stride_bytes, bool object_space,
+		uint32_t max_hierarchy_words, consumer_launch_shape& out_shape)
+	{
+		const uint32_t row_transforms = uint32_t(std::min<uint64_t>(std::min(local_pose_stride_bytes / 48, matrix_stride_bytes / 64), 0xFFFFu));
+		out_shape = consumer_launch_shape_of(row_transforms * 3u, row_transforms, false, object_space, max_hierarchy_words);
+		if (!out_shape.fits)
+			return fail(context, ACLHIP_ERROR_INVALID_ARGUMENT, "rows of %u transforms: too large for the pose matrices (%zu bytes of LDS per instance)", row_transforms, out_shape.lds_needed_bytes);
+		return ACLHIP_OK;
+	}
+
+	// What aclhip_pose_matrices_batch checks of its arguments before any device call; every refusal leaves a message, with or without a context
+	aclhip_status check_pose_matrices(aclhip_context* context, const void* local_poses, uint64_t local_pose_stride_bytes, uint32_t num_instances,
+		const aclhip_pose_matrices_desc* desc, const void* matrices, uint64_t matrix_stride_bytes)
+	{
+		if (desc == nullptr)
+			return fail(context, ACLHIP_ERROR_INVALID_ARGUMENT, "null pose matrices desc");
+		if (local_poses == nullptr)
+			return fail(context, ACLHIP_ERROR_INVALID_ARGUMENT, "null local pose buffer");
+		if (matrices == nullptr)
+			return fail(context, ACLHIP_ERROR_INVALID_ARGUMENT, "null matrix buffer");
+		if (desc->skeleton == 0 && desc->instance_skeletons == nullptr)
+			return fail(context, ACLHIP_ERROR_INVALID_ARGUMENT, "a pose matrices desc names a skeleton or a list of skeletons");
+		if (desc->layout != ACLHIP_MATRIX_3X4F_64)
+			return fail(context, ACLHIP_ERROR_INVALID_ARGUMENT, "unknown matrix layout %u", desc->layout);
+		if ((local_pose_stride_bytes & 15u) != 0 || (reinterpret_cast<uintptr_t>(local_poses) & 15u) != 0)
+			return fail(context, ACLHIP_ERROR_INVALID_ARGUMENT, "local pose buffer and stride must be 16 byte aligned");
+		if ((matrix_stride_bytes & 15u) != 0 || (reinterpret_cast<uintptr_t>(matrices) & 15u) != 0)
+			return fail(context, ACLHIP_ERROR_INVALID_ARGUMENT, "matrix buffer and stride must be 16 byte aligned");
+		if (desc->reserved[0] != 0 || desc->reserved[1] != 0)
+			return fail(context, ACLHIP_ERROR_INVALID_ARGUMENT, "the reserved fields of a pose matrices desc are 0");
+		consumer_launch_shape shape;
+		if (const aclhip_status shape_status = pose_matrices_launch_shape_of(context, local_pose_stride_bytes, matrix_stride_bytes, false, 0, shape); shape_status != ACLHIP_OK)
+			return shape_status;
+		// records differ in size: there is no in place form, and no other overlap either (the skeleton list is only read as well)
+		if (pose_ranges_overlap(matrices, matrix_stride_bytes, local_poses, local_pose_stride_bytes, num_instances))
+			return fail(context, ACLHIP_ERROR_INVALID_ARGUMENT, "the matrix rows overlap the local pose rows: a matrix is larger than its transform, there is no in place form");
+		if (desc->instance_skeletons != nullptr && pose_ranges_overlap(matrices, matrix_stride_bytes, desc->instance_skeletons, sizeof(aclhip_skeleton), num_instances))
+			return fail(context, ACLHIP_ERROR_INVALID_ARGUMENT, "the matrix rows overlap the skeleton list");
+		return ACLHIP_OK;
+	}
+
+	template<bool kObjectSpace>
+	aclhip_status launch_pose_matrices_kernel(aclhip_context* context, const consumer_launch_shape& shape, uint32_t num_blocks, hipStream_t stream, const pose_matrices_launch& launch)
+	{
+		const auto kernel = pose_matrices_kernel<kObjectSpace>;
+		// above the default limit of dynamic LDS the kernel has to be told
+		if (shape.lds_bytes > 64 * 1024 - 128)
+			ACLHIP_CHECK_HIP(context, hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, int(k_consumer_lds_bytes)));
+		hipLaunchKernelGGL(kernel, dim3(num_blocks), dim3((1u << shape.log2_instances_per_block) * k_wave_size), shape.lds_bytes, stream, launch);
+		ACLHIP_CHECK_HIP(context, hipGetLastError());
+		return ACLHIP_OK;
+	}
+
+	// The launch: shaped by its rows alone, like launch_pose_buffers; the skeleton table is filled in under the registry lock; nothing is uploaded
+	aclhip_status launch_pose_matrices(aclhip_context* context, const void* local_poses, uint64_t local_pose_stride_bytes, uint32_t num_instances,
+		const aclhip_pose_matrices_desc& desc, void* matrices, uint64_t matrix_stride_bytes, hipStream_t stream)
+	{
+		std::shared_lock<std::shared_mutex> lock(context->mutex);		// see launch_tracks
+		if (context->skeletons.d_records == nullptr)
+			return fail(context, ACLHIP_ERROR_INVALID_ARGUMENT, "no skeleton was ever registered with this context");
+		const bool object_space = desc.object_space != 0;
+		consumer_launch_shape shape;
+		if (const aclhip_status shape_status = pose_matrices_launch_shape_of(context, local_pose_stride_bytes, matrix_stride_bytes, object_space, context->max_skeleton_hierarchy_words, shape); shape_status != ACLHIP_OK)
+			return shape_status;
+		note_launch_stream(context, stream);
+
+		pose_matrices_launch launch = {};
+		launch.skeletons = context->skeletons.d_records;
+		launch.num_skeletons = ACLHIP_MAX_SKELETONS;
+		launch.skeleton = desc.skeleton;
+		launch.instance_skeletons = desc.instance_skeletons;
+		launch.local_poses = static_cast<const uint8_t*>(local_poses);
+		launch.local_pose_stride_bytes = local_pose_stride_bytes;
+		launch.matrices = static_cast<uint8_t*>(matrices);
+		launch.matrix_stride_bytes = matrix_stride_bytes;
+		launch.num_instances = num_instances;
+		launch.lds_quads_per_image = shape.lds_quads_per_image;
+		launch.lds_bytes_per_instance = uint32_t(shape.lds_bytes_per_instance);
+		launch.packed_block_shape = shape.log2_instances_per_block | (shape.lds_schedule_words << 8);
+		launch.rejected_count = context->d_rejected;
+
+		const uint32_t instances_per_block = 1u << shape.log2_instances_per_block;
+		const uint32_t num_blocks = (num_instances + instances_per_block - 1) / instances_per_block;
+		return object_space ? launch_pose_matrices_kernel<true>(context, shape, num_blocks, stream, launch) : launch_pose_matrices_kernel<false>(context, shape, num_blocks, stream, launch);
 	}
 }
 
@@ -571,12 +663,16 @@ extern "C" aclhip_status aclhip_inverse_transform_poses_batch(aclhip_context* co
 }
 
 // include/aclhip.h states the definition. The argument checks need no device, come first and leave a message, with or without a context.
-extern "C" aclhip_status aclhip_measure_pose_error_batch(aclhip_context* context, const void* raw_poses, uint64_t raw_pose_stride_bytes, const void* lossy_poses,
-	uint64_t lossy_pose_stride_bytes, uint32_t num_instances, const aclhip_pose_error_desc* desc, aclhip_pose_error* errors, void* stream)
+extern "C" aclhip_status aclhip_measure_pose_error_metric_batch(aclhip_context* context, const void* raw_poses, uint64_t raw_pose_stride_bytes, const void* lossy_poses,
+	uint64_t lossy_pose_stride_bytes, uint32_t num_instances, const aclhip_pose_error_desc* desc, uint32_t metric, aclhip_pose_error* errors, void* stream)
 {
 	const aclhip_status status = check_pose_error(context, raw_poses, raw_pose_stride_bytes, lossy_poses, lossy_pose_stride_bytes, num_instances, desc, errors);
 	if (status != ACLHIP_OK)
 		return status;
+	if (metric > ACLHIP_METRIC_QVVF_MATRIX3X4F)
+		return fail(context, ACLHIP_ERROR_INVALID_ARGUMENT, "unknown error metric %u", metric);
+	if (metric == ACLHIP_METRIC_QVVF_MATRIX3X4F && desc->additive_format != ACLHIP_ADDITIVE_NONE)
+		return fail(context, ACLHIP_ERROR_INVALID_ARGUMENT, "the matrix error metric takes no additive format: apply_additive_to_base is defined over QVV poses only");
 	if (context == nullptr)
 		return fail(context, ACLHIP_ERROR_INVALID_ARGUMENT, "null context");
 	// (a batch of no instances still writes the launch's worst record)
@@ -584,5 +680,28 @@ extern "C" aclhip_status aclhip_measure_pose_error_batch(aclhip_context* context
 		return ACLHIP_OK;
 
 	device_guard guard(context->device);
-	return launch_pose_error(context, raw_poses, raw_pose_stride_bytes, lossy_poses, lossy_pose_stride_bytes, num_instances, *desc, errors, static_cast<hipStream_t>(stream));
+	return launch_pose_error(context, raw_poses, raw_pose_stride_bytes, lossy_poses, lossy_pose_stride_bytes, num_instances, *desc, metric, errors, static_cast<hipStream_t>(stream));
+}
+
+// ACLHIP_METRIC_QVVF of the call above: one host path
+extern "C" aclhip_status aclhip_measure_pose_error_batch(aclhip_context* context, const void* raw_poses, uint64_t raw_pose_stride_bytes, const void* lossy_poses,
+	uint64_t lossy_pose_stride_bytes, uint32_t num_instances, const aclhip_pose_error_desc* desc, aclhip_pose_error* errors, void* stream)
+{
+	return aclhip_measure_pose_error_metric_batch(context, raw_poses, raw_pose_stride_bytes, lossy_poses, lossy_pose_stride_bytes, num_instances, desc, ACLHIP_METRIC_QVVF, errors, stream);
+}
+
+// include/aclhip.h states the definition. The argument checks need no device, come first and leave a message, with or without a context.
+extern "C" aclhip_status aclhip_pose_matrices_batch(aclhip_context* context, const void* local_poses, uint64_t local_pose_stride_bytes, uint32_t num_instances,
+	const aclhip_pose_matrices_desc* desc, void* matrices, uint64_t matrix_stride_bytes, void* stream)
+{
+	const aclhip_status status = check_pose_matrices(context, local_poses, local_pose_stride_bytes, num_instances, desc, matrices, matrix_stride_bytes);
+	if (status != ACLHIP_OK)
+		return status;
+	if (context == nullptr)
+		return fail(context, ACLHIP_ERROR_INVALID_ARGUMENT, "null context");
+	if (num_instances == 0)
+		return ACLHIP_OK;
+
+	device_guard guard(context->device);
+	return launch_pose_matrices(context, local_poses, local_pose_stride_bytes, num_instances, *desc, matrices, matrix_stride_bytes, static_cast<hipStream_t>(stream));
 }

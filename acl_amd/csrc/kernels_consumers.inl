@@ -626,7 +626,8 @@
 				const uint32_t* slot_schedule = walk.schedules[walk_slot];
 
 				// all instances that walk follow the same schedule? then the shared LDS copy is theirs; otherwise each reads its own
-				// from global memory (rare: mixed skeletons inside one workgroup)
+				// from global memory (rare: mixed skeletons inside one workgroup). The same selection stands in measure_pose_error_kernel's
+				// QVVF branch and in walk_workgroup_matrices (kernels_pose_buffers.inl): a change to the rule visits all three
 				// the rest of the workgroup waits for this wave: it goes first on its SIMD
 				__builtin_amdgcn_s_setprio(3);
 				const uint64_t walkers = __ballot(slot_steps != 0);

@@ -6,6 +6,8 @@
 // make-additive, a bone per lane, no walk.
 // measure_pose_error_kernel (aclhip_measure_pose_error_batch) holds TWO rows per instance, takes both through the same additive step and the
 // same walk without storing them, and measures per bone how far three points on the bone's shell moved.
+// pose_matrices_kernel (aclhip_pose_matrices_batch) writes 3x4 matrices, local or object space, with the matrix walk of the reference's
+// qvvf_matrix3x4f_transform_error_metric; measure_pose_error_kernel's kMatrices instantiations are the measure in that arithmetic.
 
 	// the kernel's argument: the launch's three buffers, its skeletons and its shape
 	struct pose_buffer_launch
@@ -435,6 +437,249 @@
 			store_streaming(&pose[quad], image[quad]);
 	}
 
+	// ---- 3x4 matrices of caller pose buffers (aclhip_pose_matrices_batch; include/aclhip.h states the definition) -------------------------
+	// rtm::matrix3x4f as the reference's matrix error metric uses it (compression/transform_error_metrics.h:389-462): row vectors, point *
+	// matrix. Twelve floats: lane 3 of an axis is not part of the value and is not kept. In an LDS image a bone's matrix takes the three
+	// quads its QVV record took: x_axis.xyz y_axis.x | y_axis.yz z_axis.xy | z_axis.z w_axis.xyz.
+	struct matrix3x4 { float4 x_axis, y_axis, z_axis, w_axis; };
+
+	__device__ __forceinline__ matrix3x4 load_matrix(const f32x4* image, uint32_t transform_index)
+	{
+		const f32x4 a = image[transform_index * 3u + 0], b = image[transform_index * 3u + 1], c = image[transform_index * 3u + 2];
+		return matrix3x4{ make_float4(a.x, a.y, a.z, 0.0f), make_float4(a.w, b.x, b.y, 0.0f), make_float4(b.z, b.w, c.x, 0.0f), make_float4(c.y, c.z, c.w, 0.0f) };
+	}
+
+	__device__ __forceinline__ void store_matrix(f32x4* image, uint32_t transform_index, const matrix3x4& value)
+	{
+		image[transform_index * 3u + 0] = f32x4{ value.x_axis.x, value.x_axis.y, value.x_axis.z, value.y_axis.x };
+		image[transform_index * 3u + 1] = f32x4{ value.y_axis.y, value.y_axis.z, value.z_axis.x, value.z_axis.y };
+		image[transform_index * 3u + 2] = f32x4{ value.z_axis.z, value.w_axis.x, value.w_axis.y, value.w_axis.z };
+	}
+
+	// rtm::matrix_from_qvv: nothing is assumed about the rotation's length or the scale's sign
+	__device__ __forceinline__ matrix3x4 matrix_from_qvv(const qvv& transform)
+	{
+		const float x = transform.rotation.x, y = transform.rotation.y, z = transform.rotation.z, w = transform.rotation.w;
+		const float x2 = x + x, y2 = y + y, z2 = z + z;
+		const float xx = x * x2, xy = x * y2, xz = x * z2, yy = y * y2, yz = y * z2, zz = z * z2, wx = w * x2, wy = w * y2, wz = w * z2;
+		const float sx = transform.scale.x, sy = transform.scale.y, sz = transform.scale.z;
+		matrix3x4 result;
+		result.x_axis = make_float4((1.0f - (yy + zz)) * sx, (xy + wz) * sx, (xz - wy) * sx, 0.0f);
+		result.y_axis = make_float4((xy - wz) * sy, (1.0f - (xx + zz)) * sy, (yz + wx) * sy, 0.0f);
+		result.z_axis = make_float4((xz + wy) * sz, (yz - wx) * sz, (1.0f - (xx + yy)) * sz, 0.0f);
+		result.w_axis = make_float4(transform.translation.x, transform.translation.y, transform.translation.z, 0.0f);
+		return result;
+	}
+
+	// rtm::matrix_mul_vector3: ((x_axis * v.x) + y_axis * v.y) + z_axis * v.z, all three products made
+	__device__ __forceinline__ float4 matrix_mul_vector3(float x, float y, float z, const matrix3x4& matrix)
+	{
+		return make_float4(((matrix.x_axis.x * x) + (matrix.y_axis.x * y)) + (matrix.z_axis.x * z), ((matrix.x_axis.y * x) + (matrix.y_axis.y * y)) + (matrix.z_axis.y * z),
+			((matrix.x_axis.z * x) + (matrix.y_axis.z * y)) + (matrix.z_axis.z * z), 0.0f);
+	}
+
+	// rtm::matrix_mul_point3: the same, and the translation added last
+	__device__ __forceinline__ float4 matrix_mul_point3(float x, float y, float z, const matrix3x4& matrix)
+	{
+		const float4 rotated = matrix_mul_vector3(x, y, z, matrix);
+		return make_float4(rotated.x + matrix.w_axis.x, rotated.y + matrix.w_axis.y, rotated.z + matrix.w_axis.z, 0.0f);
+	}
+
+	// rtm::matrix_mul: lhs first, then rhs
+	__device__ __forceinline__ matrix3x4 matrix_mul(const matrix3x4& lhs, const matrix3x4& rhs)
+	{
+		matrix3x4 result;
+		result.x_axis = matrix_mul_vector3(lhs.x_axis.x, lhs.x_axis.y, lhs.x_axis.z, rhs);
+		result.y_axis = matrix_mul_vector3(lhs.y_axis.x, lhs.y_axis.y, lhs.y_axis.z, rhs);
+		result.z_axis = matrix_mul_vector3(lhs.z_axis.x, lhs.z_axis.y, lhs.z_axis.z, rhs);
+		result.w_axis = matrix_mul_point3(lhs.w_axis.x, lhs.w_axis.y, lhs.w_axis.z, rhs);
+		return result;
+	}
+
+	// a wave's image rewritten in place, a bone per lane: every QVV record becomes its matrix in the same three quads (a lane reads and
+	// writes its own bone's quads and no other)
+	__device__ __forceinline__ void convert_image_to_matrices(f32x4* image, uint32_t num_bones, uint32_t lane)
+	{
+		for (uint32_t bone = lane; bone < num_bones; bone += k_wave_size)
+			store_matrix(image, bone, matrix_from_qvv(load_qvv(image, bone)));
+	}
+
+	// walk_hierarchy (kernels_consumers.inl) over images of matrices: the SAME schedules -- lanes <-> (instance slot, transform of the current
+	// step), `first` picks the lane's transform inside a step, a transform's parent was scheduled in an earlier step and is final by the
+	// time it is read -- with matrix_mul(local child, object parent) as its body: 63 operations, no normalize, no route to decide, nothing
+	// to count.
+	template<class schedule_word_type>
+	__device__ __forceinline__ void walk_hierarchy_matrices(const schedule_word_type* schedule_words, uint32_t slot_steps, uint32_t first, f32x4* slot_image)
+	{
+		const uint32_t first_pair = 2u + slot_steps;		// (behind the step ends)
+		uint32_t step_start = 0;
+		for (uint32_t step = 0; __any(int(step < slot_steps)) != 0; ++step)
+		{
+			if (step < slot_steps)
+			{
+				const uint32_t step_end = schedule_words[2 + step];
+				const uint32_t pair_index = step_start + first;
+				if (pair_index < step_end)
+				{
+					const uint32_t pair = schedule_words[first_pair + pair_index];		// transform | parent << 16
+					store_matrix(slot_image, pair & 0xFFFFu, matrix_mul(load_matrix(slot_image, pair & 0xFFFFu), load_matrix(slot_image, pair >> 16)));
+				}
+				step_start = step_end;
+			}
+			wave_lds_barrier();
+		}
+	}
+
+	// The walk of a workgroup's images by the wave that calls it, as finish_consumer_poses arranges it: the lane's slot, its steps and its
+	// schedule from the walk's slots, the shared LDS copy of the schedule when every slot that walks follows the same one, otherwise each
+	// slot's own in global memory. role_quads: where the image of the caller's role starts inside a slot (the measure's second image).
+	// The selection is the third copy of the one in finish_consumer_poses and in measure_pose_error_kernel's QVVF branch, which stay as
+	// they are to keep their registers: a change to the schedule-sharing rule visits all three.
+	__device__ __forceinline__ void walk_workgroup_matrices(const consumer_walk_slots& walk, const uint32_t* shared_schedule, uint32_t log2_instances_per_block,
+		uint32_t lds_bytes_per_instance, uint32_t role_quads, uint32_t lane)
+	{
+		extern __shared__ __attribute__((aligned(16))) uint8_t dynamic_lds[];
+		const uint32_t walk_slot = lane & ((1u << log2_instances_per_block) - 1u);
+		const uint32_t first = lane >> log2_instances_per_block;
+		f32x4* slot_image = reinterpret_cast<f32x4*>(dynamic_lds + size_t(walk_slot) * lds_bytes_per_instance) + role_quads;
+		const uint32_t slot_steps = walk.levels[walk_slot] & 0x7FFFFFFFu;
+		const bool slot_schedule_is_shared = (walk.levels[walk_slot] & 0x80000000u) == 0;
+		const uint32_t* slot_schedule = walk.schedules[walk_slot];
+		// the rest of the workgroup waits for this wave: it goes first on its SIMD
+		__builtin_amdgcn_s_setprio(3);
+		const uint64_t walkers = __ballot(slot_steps != 0);
+		if (walkers != 0)
+		{
+			const uint32_t leader = uint32_t(__builtin_ctzll(walkers));
+			const uint64_t mine = reinterpret_cast<uint64_t>(slot_schedule);
+			const uint64_t first_schedule = (uint64_t(__shfl(uint32_t(mine >> 32), int(leader))) << 32) | __shfl(uint32_t(mine), int(leader));
+			const bool shared_copy = __all(int(slot_steps == 0 || (mine == first_schedule && slot_schedule_is_shared))) != 0;
+			if (shared_copy)
+				walk_hierarchy_matrices(shared_schedule, slot_steps, first, slot_image);
+			else
+				walk_hierarchy_matrices(as_constant(slot_schedule), slot_steps, first, slot_image);
+		}
+		__builtin_amdgcn_s_setprio(0);
+	}
+
+	// the kernel's argument: the launch's two buffers, its skeletons and its shape
+	struct pose_matrices_launch
+	{
+		const device_skeleton* skeletons;		// the context's skeleton table
+		uint32_t num_skeletons;					// its capacity
+		uint32_t skeleton;						// the launch's skeleton, when instance_skeletons is null
+		const uint32_t* instance_skeletons;		// [num_instances] or null
+		const uint8_t* local_poses;				// row i at local_poses + i * local_pose_stride_bytes: QVV48
+		uint64_t local_pose_stride_bytes;
+		uint8_t* matrices;						// row i at matrices + i * matrix_stride_bytes: 64 bytes per bone
+		uint64_t matrix_stride_bytes;
+		uint32_t num_instances;
+		uint32_t lds_quads_per_image, lds_bytes_per_instance, packed_block_shape;		// as transform_poses_kernel takes them
+		unsigned long long* rejected_count;
+	};
+
+	// a finished image of matrices into its output row, lanes <-> consecutive OUTPUT quads (a wave writes contiguous pieces of 1 KiB): the
+	// three floats of an axis from the image's twelve per bone, and the lane that is no part of the matrix -- +0 for the three axes, 1 for
+	// w_axis
+	__device__ __forceinline__ void store_matrix_row(const f32x4* image, uint32_t num_bones, uint8_t* row, uint32_t lane)
+	{
+		const float* floats = reinterpret_cast<const float*>(image);
+		f32x4* out = reinterpret_cast<f32x4*>(row);
+		const uint32_t num_quads = num_bones * 4u;
+		for (uint32_t quad = lane; quad < num_quads; quad += k_wave_size)
+		{
+			const uint32_t axis = quad & 3u;
+			const float* source = floats + (quad >> 2) * 12u + axis * 3u;
+			store_streaming(&out[quad], f32x4{ source[0], source[1], source[2], axis == 3u ? 1.0f : 0.0f });
+		}
+	}
+
+	// transform_poses_kernel's front -- one wave64 per instance, up to 8 instances per workgroup, images as consumer_wave_of lays them out,
+	// the skeleton's record on the scalar unit, the refusal in front of any load of a row, the row into the image by DMA, the walk schedule
+	// requested in front of it -- and then the matrix arithmetic: every wave rewrites its image as matrices (a bone per lane), with
+	//   kObjectSpace   ONE wave of the workgroup (it rotates with the workgroup index) walks all its images with walk_hierarchy_matrices
+	//                  and then stores all of them, as finish_consumer_poses does for QVV rows; without it every wave stores its own.
+	// Nothing is normalized, routed or counted. The output never overlaps the input (the host refuses it: records differ in size).
+	// Every wave of the workgroup reaches the __syncthreads: a wave without work (past the batch, refused, no bones) has num_bones 0.
+	template<bool kObjectSpace>
+	__global__ __launch_bounds__(k_consumer_max_instances * k_wave_size) void pose_matrices_kernel(pose_matrices_launch launch)
+	{
+		extern __shared__ __attribute__((aligned(16))) uint8_t dynamic_lds[];
+		// packed_block_shape: log2 of the instances per workgroup (bits 0..7) | words of LDS reserved for the shared walk schedule (bits 8..31)
+		const uint32_t log2_instances_per_block = launch.packed_block_shape & 0xFFu;
+		__shared__ consumer_walk_slots walk;		// (what the host subtracts from the LDS it may ask for: host_consumers.inl)
+
+		const consumer_wave wave = consumer_wave_of(log2_instances_per_block, launch.lds_bytes_per_instance, launch.lds_quads_per_image);
+		const uint32_t lane = wave.lane, instance = wave.instance, slot = wave.slot;
+		uint32_t num_bones = 0;
+
+		if (instance < launch.num_instances)
+		{
+			// the skeleton's record on the scalar unit; record 0 is never handed out and a cleared record is an unknown or retired skeleton
+			const uint32_t skeleton_id = launch.instance_skeletons != nullptr ? as_constant(launch.instance_skeletons)[instance] : launch.skeleton;
+			const device_skeleton skeleton = load_skeleton_fields(launch.skeletons, skeleton_id < launch.num_skeletons ? skeleton_id : 0);
+			const uint32_t skeleton_bones = skeleton.num_bones;
+
+			// refused, wave uniform and in front of any load of a row: what transform_poses_kernel refuses, with 64 bytes per bone on the
+			// output side. What is served reads and writes inside its own rows.
+			const bool refused = skeleton_id >= launch.num_skeletons || skeleton.reference_pose == nullptr || (kObjectSpace && skeleton.hierarchy == nullptr)
+				|| uint64_t(skeleton_bones) * 48u > launch.local_pose_stride_bytes || uint64_t(skeleton_bones) * 64u > launch.matrix_stride_bytes
+				|| skeleton_bones * 3u > launch.lds_quads_per_image;
+			if (refused)
+			{
+				if (lane == 0)
+					atomicAdd(launch.rejected_count, 1ull);
+			}
+			else if (skeleton_bones != 0)
+			{
+				num_bones = skeleton_bones;
+				// the walk schedule first: its words travel global -> LDS while the row does
+				if (kObjectSpace)
+					request_walk_schedule(skeleton.hierarchy, log2_instances_per_block, launch.packed_block_shape >> 8, wave.shared_schedule, slot, lane, walk);
+				// the row straight into the image by DMA, lanes <-> consecutive quads (the LDS side of a piece is wave uniform + lane * 16)
+				const f32x4* source = reinterpret_cast<const f32x4*>(launch.local_poses + uint64_t(instance) * launch.local_pose_stride_bytes);
+				const uint32_t num_quads = num_bones * 3u;
+				for (uint32_t base = 0; base < num_quads; base += k_wave_size)
+				{
+					if (base + lane < num_quads)
+						__builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(source + base + lane),
+							(__attribute__((address_space(3))) void*)(wave.image + base), 16, 0, 0);
+				}
+			}
+		}
+		wave_lds_barrier();		// the wave's row is complete (vmcnt)
+		convert_image_to_matrices(wave.image, num_bones, lane);
+
+		if constexpr (kObjectSpace)
+		{
+			if (lane == 0)
+			{
+				// (a slot with work has its steps and its schedule already: request_walk_schedule)
+				if (num_bones == 0)
+				{
+					walk.levels[slot] = 0;
+					walk.schedules[slot] = nullptr;
+				}
+				walk.tracks[slot] = num_bones;
+			}
+			__syncthreads();
+			// ONE wave walks and then stores the workgroup's matrices; the others are done (finish_consumer_poses says why, and why it rotates)
+			if (wave.wave_in_block != (blockIdx.x & ((blockDim.x / k_wave_size) - 1u)))
+				return;
+			walk_workgroup_matrices(walk, wave.shared_schedule, log2_instances_per_block, launch.lds_bytes_per_instance, 0, lane);
+			wave_lds_barrier();
+			const uint32_t instances_per_block = 1u << log2_instances_per_block;
+			for (uint32_t store_slot = 0; store_slot < instances_per_block; ++store_slot)
+				store_matrix_row(reinterpret_cast<const f32x4*>(dynamic_lds + size_t(store_slot) * launch.lds_bytes_per_instance), walk.tracks[store_slot],
+					launch.matrices + uint64_t((blockIdx.x << log2_instances_per_block) + store_slot) * launch.matrix_stride_bytes, lane);
+		}
+		else
+		{
+			wave_lds_barrier();		// every bone has its matrix
+			store_matrix_row(wave.image, num_bones, launch.matrices + uint64_t(instance) * launch.matrix_stride_bytes, lane);
+		}
+	}
+
 	// ---- how far two pose buffers are apart (aclhip_measure_pose_error_batch; include/aclhip.h states the definition) --------------------
 	struct pose_error_record { float error; uint32_t bone; };		// aclhip_pose_error
 	constexpr uint32_t k_no_bone = 0xFFFFFFFFu;						// ACLHIP_NO_BONE
@@ -490,6 +735,24 @@
 		return error_xy > error_z ? error_xy : error_z;
 	}
 
+	// qvvf_matrix3x4f_transform_error_metric::calculate_error (compression/transform_error_metrics.h:438-461): the same three points through
+	// rtm::matrix_mul_point3, all three products of every point made, the zero ones too
+	__device__ __forceinline__ float matrix_shell_point_error(float x, float y, float z, const matrix3x4& raw, const matrix3x4& lossy)
+	{
+		const float4 raw_point = matrix_mul_point3(x, y, z, raw), lossy_point = matrix_mul_point3(x, y, z, lossy);
+		const float dx = lossy_point.x - raw_point.x, dy = lossy_point.y - raw_point.y, dz = lossy_point.z - raw_point.z;
+		return sqrtf(((dx * dx) + (dy * dy)) + (dz * dz));
+	}
+
+	__device__ __forceinline__ float matrix_shell_error(float distance, const matrix3x4& raw, const matrix3x4& lossy)
+	{
+		const float error_x = matrix_shell_point_error(distance, 0.0f, 0.0f, raw, lossy);
+		const float error_y = matrix_shell_point_error(0.0f, distance, 0.0f, raw, lossy);
+		const float error_z = matrix_shell_point_error(0.0f, 0.0f, distance, raw, lossy);
+		const float error_xy = error_x > error_y ? error_x : error_y;
+		return error_xy > error_z ? error_xy : error_z;
+	}
+
 	// The wave's greatest error and, among equal ones, the lowest key (a bone, an instance), left in every lane: a butterfly over a total
 	// order -- no error here is a NaN (a lane's record starts at -1 and only takes what compares greater) --, so the result is the same
 	// whatever the order of the steps. `payload` travels with the winner.
@@ -519,9 +782,13 @@
 	// out in turn (role 0 the even ones), per lane the scan of track_error.impl.h:358-375 over its bones in ascending order, then the wave's
 	// record by wave_reduce_worst; role 1 hands its record over in LDS and role 0 writes the instance's.
 	// Every wave of the workgroup reaches every __syncthreads: a wave without work (past the batch, refused, no bones) has num_bones 0.
-	template<bool kObjectSpace, bool kBase>
+	//   kMatrices      qvvf_matrix3x4f_transform_error_metric (aclhip_measure_pose_error_metric_batch, ACLHIP_METRIC_QVVF_MATRIX3X4F; never
+	//                  with kBase): each wave rewrites its image as matrices behind its DMA, the walk is walk_hierarchy_matrices over the
+	//                  same schedules and the measure is matrix_shell_error; nothing is counted. Without it the text is what it was.
+	template<bool kObjectSpace, bool kBase, bool kMatrices = false>
 	__global__ __launch_bounds__(k_consumer_max_waves * k_wave_size) void measure_pose_error_kernel(pose_error_launch launch)
 	{
+		static_assert(!(kMatrices && kBase), "the matrix metric takes no additive base");
 		extern __shared__ __attribute__((aligned(16))) uint8_t dynamic_lds[];
 		// packed_block_shape: log2 of the instances per workgroup (bits 0..7) | words of LDS reserved for the shared walk schedule (bits 8..31)
 		const uint32_t log2_instances_per_block = launch.packed_block_shape & 0xFFu;
@@ -578,7 +845,9 @@
 		}
 		wave_lds_barrier();		// the wave's row is complete (vmcnt)
 
-		unsigned long long* const negative_scale_count = launch.rejected_count + 1;
+		[[maybe_unused]] unsigned long long* const negative_scale_count = launch.rejected_count + 1;
+		if constexpr (kMatrices)
+			convert_image_to_matrices(own_image, num_bones, lane);
 		if constexpr (kBase)
 		{
 			// finish_consumer_poses' combine, the wave over its own image: the image is the additive pose, the base row is read per transform
@@ -610,28 +879,34 @@
 			// the two waves of one slot walk, the others wait at the barrier below
 			if (slot == (blockIdx.x & ((1u << log2_instances_per_block) - 1u)))
 			{
-				const uint32_t walk_slot = lane & ((1u << log2_instances_per_block) - 1u);
-				const uint32_t first = lane >> log2_instances_per_block;
-				f32x4* slot_image = reinterpret_cast<f32x4*>(dynamic_lds + size_t(walk_slot) * launch.lds_bytes_per_instance) + size_t(role) * launch.lds_quads_per_image;
-				const uint32_t slot_steps = walk.levels[walk_slot] & 0x7FFFFFFFu;
-				const bool slot_schedule_is_shared = (walk.levels[walk_slot] & 0x80000000u) == 0;
-				const uint32_t* slot_schedule = walk.schedules[walk_slot];
-				__builtin_amdgcn_s_setprio(3);
-				const uint64_t walkers = __ballot(slot_steps != 0);
-				if (walkers != 0)
+				if constexpr (kMatrices)
+					walk_workgroup_matrices(walk, wave.shared_schedule, log2_instances_per_block, launch.lds_bytes_per_instance, role * launch.lds_quads_per_image, lane);
+				else
 				{
-					// all instances that walk follow the same schedule? then the shared LDS copy is theirs; otherwise each reads its own
-					// from global memory (finish_consumer_poses)
-					const uint32_t leader = uint32_t(__builtin_ctzll(walkers));
-					const uint64_t mine = reinterpret_cast<uint64_t>(slot_schedule);
-					const uint64_t first_schedule = (uint64_t(__shfl(uint32_t(mine >> 32), int(leader))) << 32) | __shfl(uint32_t(mine), int(leader));
-					const bool shared_copy = __all(int(slot_steps == 0 || (mine == first_schedule && slot_schedule_is_shared))) != 0;
-					if (shared_copy)
-						walk_hierarchy<false, true, false, false>(static_cast<const uint32_t*>(wave.shared_schedule), slot_steps, first, slot_image, lane, negative_scale_count);
-					else
-						walk_hierarchy<false, true, false, false>(as_constant(slot_schedule), slot_steps, first, slot_image, lane, negative_scale_count);
+					const uint32_t walk_slot = lane & ((1u << log2_instances_per_block) - 1u);
+					const uint32_t first = lane >> log2_instances_per_block;
+					f32x4* slot_image = reinterpret_cast<f32x4*>(dynamic_lds + size_t(walk_slot) * launch.lds_bytes_per_instance) + size_t(role) * launch.lds_quads_per_image;
+					const uint32_t slot_steps = walk.levels[walk_slot] & 0x7FFFFFFFu;
+					const bool slot_schedule_is_shared = (walk.levels[walk_slot] & 0x80000000u) == 0;
+					const uint32_t* slot_schedule = walk.schedules[walk_slot];
+					__builtin_amdgcn_s_setprio(3);
+					const uint64_t walkers = __ballot(slot_steps != 0);
+					if (walkers != 0)
+					{
+						// all instances that walk follow the same schedule? then the shared LDS copy is theirs; otherwise each reads its own
+						// from global memory (finish_consumer_poses). walk_workgroup_matrices above holds the same selection for the matrix
+						// walk, kept apart so that this branch compiles to what it was: a change to the rule visits all three
+						const uint32_t leader = uint32_t(__builtin_ctzll(walkers));
+						const uint64_t mine = reinterpret_cast<uint64_t>(slot_schedule);
+						const uint64_t first_schedule = (uint64_t(__shfl(uint32_t(mine >> 32), int(leader))) << 32) | __shfl(uint32_t(mine), int(leader));
+						const bool shared_copy = __all(int(slot_steps == 0 || (mine == first_schedule && slot_schedule_is_shared))) != 0;
+						if (shared_copy)
+							walk_hierarchy<false, true, false, false>(static_cast<const uint32_t*>(wave.shared_schedule), slot_steps, first, slot_image, lane, negative_scale_count);
+						else
+							walk_hierarchy<false, true, false, false>(as_constant(slot_schedule), slot_steps, first, slot_image, lane, negative_scale_count);
+					}
+					__builtin_amdgcn_s_setprio(0);
 				}
-				__builtin_amdgcn_s_setprio(0);
 			}
 		}
 		__syncthreads();		// both images of every slot are final
@@ -647,7 +922,11 @@
 			for (uint32_t bone = role * k_wave_size + lane; bone < num_bones; bone += 2u * k_wave_size)
 			{
 				const float distance = shell_distances != nullptr ? shell_distances[bone] : launch.shell_distance;
-				const float error = shell_error(distance, load_qvv(raw_image, bone), load_qvv(lossy_image, bone));
+				float error;
+				if constexpr (kMatrices)
+					error = matrix_shell_error(distance, load_matrix(raw_image, bone), load_matrix(lossy_image, bone));
+				else
+					error = shell_error(distance, load_qvv(raw_image, bone), load_qvv(lossy_image, bone));
 				if (bone_errors != nullptr)
 					bone_errors[bone] = error;
 				// (a NaN compares false: it never wins)

@@ -52,6 +52,7 @@ EXPORTED_SYMBOLS = [
     "aclhip_blend_poses_batch",
     "aclhip_inverse_transform_poses_batch",
     "aclhip_measure_pose_error_batch",
+    "aclhip_pose_matrices_batch", "aclhip_measure_pose_error_metric_batch",
 ]
 
 
@@ -175,6 +176,18 @@ class PoseErrorDesc(ctypes.Structure):
         ("shell_distance", ctypes.c_float), ("bone_errors", ctypes.c_void_p), ("bone_error_stride_bytes", ctypes.c_uint64), ("worst", ctypes.c_void_p),
         ("reserved", ctypes.c_uint64 * 2),
     ]
+
+
+class PoseMatricesDesc(ctypes.Structure):
+    """aclhip_pose_matrices_desc; `instance_skeletons` is a device address or None"""
+    _fields_ = [
+        ("skeleton", ctypes.c_uint32), ("instance_skeletons", ctypes.c_void_p), ("object_space", ctypes.c_uint32), ("layout", ctypes.c_uint32),
+        ("reserved", ctypes.c_uint64 * 2),
+    ]
+
+
+MATRIX_3X4F_64 = 0                                          # aclhip_matrix_layout: 64 bytes per bone, x_axis | y_axis | z_axis | w_axis
+ERROR_METRIC_QVVF, ERROR_METRIC_QVVF_MATRIX3X4F = 0, 1      # aclhip_error_metric
 
 
 class PoseBufferBlend(ctypes.Structure):
@@ -381,6 +394,8 @@ def load_library():
     lib.aclhip_blend_poses_batch.argtypes = [vp, ctypes.POINTER(PoseBufferBlend), u32, vp, u64, vp]
     lib.aclhip_inverse_transform_poses_batch.argtypes = [vp, vp, u64, u32, ctypes.POINTER(PoseBufferInverse), vp, u64, vp]
     lib.aclhip_measure_pose_error_batch.argtypes = [vp, vp, u64, vp, u64, u32, ctypes.POINTER(PoseErrorDesc), vp, vp]
+    lib.aclhip_measure_pose_error_metric_batch.argtypes = [vp, vp, u64, vp, u64, u32, ctypes.POINTER(PoseErrorDesc), u32, vp, vp]
+    lib.aclhip_pose_matrices_batch.argtypes = [vp, vp, u64, u32, ctypes.POINTER(PoseMatricesDesc), vp, u64, vp]
     _lib = lib
     return lib
 
@@ -853,6 +868,18 @@ class Context:
         self._check(self._lib.aclhip_measure_pose_error_batch(self._handle, raw_poses_ptr, raw_pose_stride_bytes, lossy_poses_ptr, lossy_pose_stride_bytes, num_instances,
                                                               ctypes.byref(desc) if desc is not None else None, errors_ptr, stream))
 
+    def measure_pose_error_metric(self, raw_poses_ptr, raw_pose_stride_bytes, lossy_poses_ptr, lossy_pose_stride_bytes, num_instances, desc, metric, errors_ptr, stream=None):
+        """aclhip_measure_pose_error_metric_batch: measure_pose_error with the error metric as an argument -- ERROR_METRIC_QVVF is
+        measure_pose_error itself, ERROR_METRIC_QVVF_MATRIX3X4F the reference's matrix metric (no additive format)."""
+        self._check(self._lib.aclhip_measure_pose_error_metric_batch(self._handle, raw_poses_ptr, raw_pose_stride_bytes, lossy_poses_ptr, lossy_pose_stride_bytes,
+                                                                     num_instances, ctypes.byref(desc) if desc is not None else None, metric, errors_ptr, stream))
+
+    def pose_matrices_batch(self, local_poses_ptr, local_pose_stride_bytes, num_instances, desc, matrices_ptr, matrix_stride_bytes, stream=None):
+        """aclhip_pose_matrices_batch: 3x4 matrices (64 bytes per bone) of the QVV48 rows at local_poses_ptr into the rows at matrices_ptr
+        (device addresses), in local space or, with desc.object_space, through the matrix walk; `desc` is a PoseMatricesDesc."""
+        self._check(self._lib.aclhip_pose_matrices_batch(self._handle, local_poses_ptr, local_pose_stride_bytes, num_instances,
+                                                         ctypes.byref(desc) if desc is not None else None, matrices_ptr, matrix_stride_bytes, stream))
+
     def decompress_poses_mapped(self, clips, sample_times, skeletons, maps, num_bones, additive_format=ADDITIVE_NONE, object_space=False, base_clips=None,
                                 base_sample_times=None, base_maps=None, base_poses=None, params=None, out=None, instance_rounding=None, instance_looping=None,
                                 blend_clips=None, blend_sample_times=None, blend_maps=None, blend_weights=None, flags=0):
@@ -1193,13 +1220,15 @@ class Context:
         return written.value, read.value
 
 
-def clip_error(ctx, clip_a, clip_b, skeleton, shells, object_space=True, params_a=None, params_b=None):
+def clip_error(ctx, clip_a, clip_b, skeleton, shells, object_space=True, params_a=None, params_b=None, metric=ERROR_METRIC_QVVF):
     """acl::calculate_compression_error's loop (impl/track_error.impl.h:219-387) as three launches: both registered clips decoded at
     min(i / sample_rate, duration) for every sample i of clip_a -- instances are samples --, then aclhip_measure_pose_error_batch over the
     two buffers with the launch's worst record. clip_a plays the raw clip and clip_b the lossy one; both have the skeleton's bones as
     their tracks, in its order. `shells` is one shell distance for every bone or an array of one per bone. Returns (bone, error,
     sample_time) of the worst bone of the worst sample -- the lowest sample and bone among equals; (NO_BONE, -1.0, nan) when nothing could
-    be measured. Synchronous; the buffers are torch tensors on the context's device."""
+    be measured. `metric` is an aclhip_error_metric: ERROR_METRIC_QVVF_MATRIX3X4F measures with the reference's matrix metric
+    (aclhip_measure_pose_error_metric_batch); the default is aclhip_measure_pose_error_batch as before. Synchronous; the buffers are torch
+    tensors on the context's device."""
     import torch
     device = torch.device("cuda", ctx.device_index)
     info = ctx.clip_info(clip_a)
@@ -1224,7 +1253,10 @@ def clip_error(ctx, clip_a, clip_b, skeleton, shells, object_space=True, params_
         d_shells = torch.from_numpy(np.ascontiguousarray(shells, dtype=np.float32)).to(device)
         desc.shell_distances, desc.num_shell_distances = d_shells.data_ptr(), d_shells.numel()
     desc.worst = d_worst.data_ptr()
-    ctx.measure_pose_error(d_poses[0].data_ptr(), stride, d_poses[1].data_ptr(), stride, num_samples, desc, d_errors.data_ptr(), stream=stream.cuda_stream)
+    if metric == ERROR_METRIC_QVVF:
+        ctx.measure_pose_error(d_poses[0].data_ptr(), stride, d_poses[1].data_ptr(), stride, num_samples, desc, d_errors.data_ptr(), stream=stream.cuda_stream)
+    else:
+        ctx.measure_pose_error_metric(d_poses[0].data_ptr(), stride, d_poses[1].data_ptr(), stride, num_samples, desc, metric, d_errors.data_ptr(), stream=stream.cuda_stream)
     stream.synchronize()
     worst = d_worst.cpu().numpy().view(POSE_ERROR_WORST_DTYPE)[0]
     if int(worst["instance"]) == 0xFFFFFFFF:

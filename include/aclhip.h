@@ -203,7 +203,9 @@ const char* aclhip_last_error_message(const aclhip_context* context);
  * track maps -- aclhip_track_map_info, aclhip_track_mapping and their entry points -- were ADDED without a bump: no existing struct or
  * entry point changed shape, so a caller built against the earlier header 6 hands over nothing of another shape; the same goes for
  * skeletons -- aclhip_skeleton_info, aclhip_pose_mapping and their entry points -- and for the pose error measure -- aclhip_pose_error,
- * aclhip_pose_error_worst, aclhip_pose_error_desc and aclhip_measure_pose_error_batch).
+ * aclhip_pose_error_worst, aclhip_pose_error_desc and aclhip_measure_pose_error_batch -- and for the matrix object space --
+ * aclhip_matrix_layout, aclhip_pose_matrices_desc, aclhip_error_metric, aclhip_pose_matrices_batch and
+ * aclhip_measure_pose_error_metric_batch).
  * A caller compiled against another header would hand over structs of another shape; aclhip_abi_version() says what the LIBRARY was
  * built with, and the C++ mirror (aclhip.hpp) refuses to create a context when the two differ. */
 #define ACLHIP_ABI_VERSION 6u
@@ -1345,8 +1347,8 @@ typedef struct aclhip_pose_error_desc
  * and base are only read and may overlap each other freely: the same buffer twice gives error 0 and bone 0.
  *   The launch's shape comes from min(raw_pose_stride_bytes, lossy_pose_stride_bytes) / 48 (slots per LDS image, two images per
  * instance). Registered clips play no part. The launch goes on `stream`, can be captured into a graph, and uploads nothing.
- *   Out of scope (nothing here precludes them): qvvf_matrix3x4f_transform_error_metric and the _no_scale variants; a decode fused into the
- * measure; QVV40 / QV32 rows; the C++ mirror in aclhip.hpp; instance lists.
+ *   Out of scope (nothing here precludes them): the _no_scale variants; a decode fused into the measure; QVV40 / QV32 rows; the C++
+ * mirror in aclhip.hpp; instance lists. (qvvf_matrix3x4f_transform_error_metric is aclhip_measure_pose_error_metric_batch, below.)
  *   What it costs (one MI355X, 65 536 x 100 bones, object space, medians of three interleaved rounds of 20 launches): 293 us for the
  * records alone, 309 us with the worst record, 311 us with every bone's error as well, against 222 us for the two
  * aclhip_transform_poses_batch object space launches on the same two buffers in the same rounds -- 1.32 to 1.40 x what a caller pays
@@ -1355,6 +1357,88 @@ typedef struct aclhip_pose_error_desc
  * (tools/pose_error.py, profiles/pose_error.md; DESIGN.md 4.7 "Pose error"). */
 aclhip_status aclhip_measure_pose_error_batch(aclhip_context* context, const void* raw_poses, uint64_t raw_pose_stride_bytes,
 	const void* lossy_poses, uint64_t lossy_pose_stride_bytes, uint32_t num_instances, const aclhip_pose_error_desc* desc,
+	aclhip_pose_error* errors /* DEVICE [num_instances], required */, void* stream);
+
+/* ---- matrix object space: 3x4 pose matrices and the matrix3x4f error metric -------------------------
+ * Everything above works in rtm::qvvf. The reference has a second arithmetic: qvvf_matrix3x4f_transform_error_metric
+ * (compression/transform_error_metrics.h:389-462) converts every local transform with rtm::matrix_from_qvv, walks the hierarchy with
+ * rtm::matrix_mul and measures with rtm::matrix_mul_point3. It is the metric the reference names for clips with scale: a QVV product
+ * cannot hold the shear a non-uniform parent scale puts on a rotated child, so for such rigs the QVV object space pose is not the pose the
+ * renderer draws. aclhip_pose_matrices_batch writes those matrices -- what leaves an animation system for the renderer -- from a pose
+ * buffer the caller filled, and aclhip_measure_pose_error_metric_batch measures two pose buffers in that arithmetic. (ABI version 6
+ * still: an added struct, two added enums and two added functions, no existing struct changed.) */
+typedef enum aclhip_matrix_layout
+{
+	ACLHIP_MATRIX_3X4F_64 = 0		/* rtm::matrix3x4f: x_axis | y_axis | z_axis | w_axis, four floats each, 64 bytes per bone */
+} aclhip_matrix_layout;
+
+typedef struct aclhip_pose_matrices_desc
+{
+	aclhip_skeleton skeleton;					/*  0  for every instance when instance_skeletons is NULL */
+	const aclhip_skeleton* instance_skeletons;	/*  8  DEVICE [num_instances] or NULL */
+	uint32_t object_space;						/* 16  1: the matrix walk; 0: convert_transforms alone */
+	uint32_t layout;							/* 20  aclhip_matrix_layout */
+	uint64_t reserved[2];						/* 24  0 */
+} aclhip_pose_matrices_desc;					/* 40 bytes */
+
+/* The definition. Instance i has skeleton S (desc->skeleton, or instance_skeletons[i]) with B bones and parents P; L is the B QVV48
+ * records at local_poses + i * local_pose_stride_bytes.
+ *   1. M[b] = matrix_from_qvv(L[b]) (rtm::matrix_from_qvv, in the operation order the tests' CPU restatement spells out), with
+ *      (x, y, z, w) the rotation: x2 = x + x, y2 = y + y, z2 = z + z; xx = x * x2, xy = x * y2, xz = x * z2, yy = y * y2, yz = y * z2, zz = z * z2,
+ *      wx = w * x2, wy = w * y2, wz = w * z2;
+ *        x_axis = (1 - (yy + zz), xy + wz, xz - wy) * scale.x
+ *        y_axis = (xy - wz, 1 - (xx + zz), yz + wx) * scale.y
+ *        z_axis = (xz + wy, yz - wx, 1 - (xx + yy)) * scale.z
+ *        w_axis = translation
+ *   2. With object_space: a root keeps M; every other bone is O[b] = matrix_mul(M[b], O[P[b]]), lhs first -- the metric's
+ *      local_to_object_space (transform_error_metrics.h:415-436). With R = O[P[b]] and v one of the three axis rows of M[b], the row of
+ *      O[b] is ((R.x_axis * v.x) + R.y_axis * v.y) + R.z_axis * v.z per component; the w row is the same with v = M[b].w_axis, plus
+ *      R.w_axis, added last. Without object_space O = M (the metric's convert_transforms alone).
+ *   3. Row i of `matrices` (at matrices + i * matrix_stride_bytes) gets B records of 64 bytes, x_axis | y_axis | z_axis | w_axis: the
+ *      three components of each axis in lanes 0-2; lane 3 is written as +0 for the three axes and 1.0f for w_axis, whatever the inputs
+ *      held -- the fourth lane is no part of a 3x4 matrix's value. Bytes of a row behind 64 * B are untouched.
+ *   fp32, one IEEE operation at a time, never fused. Nothing is assumed about a caller's rotations or scales: nothing is normalized, and a
+ *   NaN or an infinity propagates to the bone and its descendants and nowhere else. There is no rtm::qvv_mul here:
+ *   aclhip_get_negative_scale_count does not move.
+ *   Refused and counted (aclhip_get_rejected_instance_count), the row untouched, decided in front of any load of a row: an unknown or
+ * retired skeleton handle (0 included); object_space on a skeleton without hierarchy; B * 48 > local_pose_stride_bytes; B * 64 >
+ * matrix_stride_bytes; B beyond the launch's LDS image.
+ *   ACLHIP_ERROR_INVALID_ARGUMENT, decided before any device call, each with a message (with or without a context): desc, local_poses or
+ * matrices == NULL; no skeleton at all; an unknown layout; pointers or strides that are not 16 byte aligned; reserved fields that are not
+ * 0; a shape that does not fit the LDS; ANY overlap of the output range with the input range -- records differ in size, so there is no in
+ * place form.
+ *   The launch's shape comes from min(local_pose_stride_bytes / 48, matrix_stride_bytes / 64) slots per LDS image. Registered clips play
+ * no part. The launch goes on `stream`, can be captured into a graph, and uploads nothing.
+ *   Out of scope (nothing here precludes them): an additive buffer in the matrix launch (chain aclhip_transform_poses_batch in local
+ * space first); a 48 byte transposed layout and inverse bind matrices; bounds; the _no_scale variants; a decode fused into either launch;
+ * QVV40 / QV32 rows; instance lists; the C++ mirror in aclhip.hpp.
+ *   What it costs (one MI355X, 65 536 x 100 bones, object space; tools/pose_matrices.py, profiles/pose_matrices.md, DESIGN.md 4.7 "Pose
+ * matrices"): 129.8 us next to 109.6 us of aclhip_transform_poses_batch with object space from the same buffer -- 1.18 x the time for
+ * 1.17 x the bytes, both at 0.71 of the HBM peak. */
+aclhip_status aclhip_pose_matrices_batch(aclhip_context* context, const void* local_poses, uint64_t local_pose_stride_bytes,
+	uint32_t num_instances, const aclhip_pose_matrices_desc* desc, void* matrices, uint64_t matrix_stride_bytes, void* stream);
+
+typedef enum aclhip_error_metric
+{
+	ACLHIP_METRIC_QVVF = 0,				/* qvvf_transform_error_metric: aclhip_measure_pose_error_batch itself */
+	ACLHIP_METRIC_QVVF_MATRIX3X4F = 1	/* qvvf_matrix3x4f_transform_error_metric */
+} aclhip_error_metric;
+
+/* aclhip_measure_pose_error_batch with the error metric as an argument: the same desc, the same records, the same bone_errors and worst,
+ * the same refusals and argument checks.
+ *   ACLHIP_METRIC_QVVF is aclhip_measure_pose_error_batch: one host path, the same kernel, the same bits.
+ *   ACLHIP_METRIC_QVVF_MATRIX3X4F: steps 1 and 2 of that definition are replaced by steps 1 and 2 of aclhip_pose_matrices_batch, applied to
+ * both rows (with object_space == 0 the conversion alone), and step 3 by the metric's calculate_error (transform_error_metrics.h:438-461):
+ *        point(p, T) = (((T.x_axis * p.x) + T.y_axis * p.y) + T.z_axis * p.z) + T.w_axis       rtm::matrix_mul_point3; all three products
+ *                      are made, the zero ones too
+ *   with e_k, the max of three, the scan (step 4), bone_errors (step 5) and the worst record (step 6) unchanged. The negative scale counter
+ *   does not move. additive_format != NONE is ACLHIP_ERROR_INVALID_ARGUMENT with a message: the reference's matrix metric inherits the
+ *   QVV apply_additive_to_base and runs it over matrix buffers, so there is nothing defined to reproduce.
+ *   An unknown metric is ACLHIP_ERROR_INVALID_ARGUMENT.
+ *   What it costs (same batch; tools/pose_matrices.py, profiles/pose_matrices.md): the matrix metric 203.4 us next to 286.1 us of
+ *   aclhip_measure_pose_error_batch over the same two buffers, 0.39 of the HBM peak. */
+aclhip_status aclhip_measure_pose_error_metric_batch(aclhip_context* context, const void* raw_poses, uint64_t raw_pose_stride_bytes,
+	const void* lossy_poses, uint64_t lossy_pose_stride_bytes, uint32_t num_instances, const aclhip_pose_error_desc* desc, uint32_t metric,
 	aclhip_pose_error* errors /* DEVICE [num_instances], required */, void* stream);
 
 /* ---- multi-GPU ---------------------------------------------------------------------------------- */
