@@ -79,5 +79,6 @@ using namespace aclhip;
 #include "host_skeletons.inl"
 #include "host_blend_masks.inl"
 #include "host_pose_buffers.inl"
+#include "host_skins.inl"
 #include "host_bone_object.inl"
 #include "host_scalar_misc.inl"

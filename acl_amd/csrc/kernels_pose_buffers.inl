@@ -680,6 +680,207 @@
 		}
 	}
 
+	// ---- skinning matrix palettes of caller pose buffers (aclhip_skinning_matrices_batch; include/aclhip.h states the definition) ---------
+	// A skin's record in the context's skin table (which never moves, like the skeleton table) and its device image: the joint list,
+	// num_joints bone indices, and the inverse bind matrices, twelve floats per joint in the three quads load_matrix reads (lane 3 of the
+	// caller's axes is dropped at registration). A cleared record (inverse_bind == null) is an unknown or retired skin; record 0 is never
+	// handed out. Both arrays are always there: an identity list and identity matrices are stored like any others.
+	struct device_skin
+	{
+		const uint32_t* joint_bones;		// [num_joints] the skeleton bone a joint follows, each < num_bones
+		const f32x4* inverse_bind;			// [3 * num_joints] x_axis.xyz y_axis.x | y_axis.yz z_axis.xy | z_axis.z w_axis.xyz per joint
+		uint32_t num_joints;
+		uint32_t num_bones;					// of the skeleton the skin was made for
+		uint32_t flags;						// k_skin_*: what registration found, for whoever reads the table; NO kernel branches on them (see below)
+		uint32_t reserved;
+	};
+	static_assert(sizeof(device_skin) == 32, "load_entry: two dwordx4 loads");
+	constexpr uint32_t k_skin_identity_joint_list = 1u << 0;	// joint_bones[j] == j and num_joints == num_bones
+	constexpr uint32_t k_skin_has_inverse_bind = 1u << 1;		// registered with matrices (not NULL: identity)
+	// The flags are informational. The store always reads the joint list and always makes the product, with an identity list and identity
+	// matrices too: 0 * NaN is what carries a NaN or an infinity of bone k[j] into every float of joint j, as the header defines. A
+	// shortcut that copies O[k[j]] when a flag is set would write different bits for such rows.
+
+	// a skin's record with every field in scalar registers of its own (load_skeleton_fields, kernels_skeleton.inl, says why)
+	__device__ __forceinline__ device_skin load_skin_fields(const device_skin* table, uint32_t index)
+	{
+		device_skin skin = load_entry(table, index);
+		asm volatile("" : "+s"(skin.joint_bones), "+s"(skin.inverse_bind), "+s"(skin.num_joints), "+s"(skin.num_bones));
+		return skin;
+	}
+
+	constexpr uint32_t k_palette_3x4f_64 = 0, k_palette_3x4f_transposed_48 = 1;		// aclhip_palette_layout
+
+	// the kernel's argument: pose_matrices_launch with the context's skin table and the launch's skins
+	struct skinning_matrices_launch
+	{
+		const device_skeleton* skeletons;		// the context's skeleton table
+		uint32_t num_skeletons;					// its capacity
+		uint32_t skeleton;						// the launch's skeleton, when instance_skeletons is null
+		const uint32_t* instance_skeletons;		// [num_instances] or null
+		const device_skin* skins;				// the context's skin table
+		uint32_t num_skins;						// its capacity
+		uint32_t skin;							// the launch's skin, when instance_skins is null
+		const uint32_t* instance_skins;			// [num_instances] or null
+		const uint8_t* poses;					// row i at poses + i * pose_stride_bytes: QVV48
+		uint64_t pose_stride_bytes;
+		uint8_t* palettes;						// row i at palettes + i * palette_stride_bytes: 64 or 48 bytes per joint
+		uint64_t palette_stride_bytes;
+		uint32_t num_instances;
+		uint32_t lds_quads_per_image, lds_bytes_per_instance, packed_block_shape;		// as transform_poses_kernel takes them
+		unsigned long long* rejected_count;
+	};
+
+	// A finished image of object matrices into its palette row: S[j] = matrix_mul(IB[j], O[k[j]]), lanes <-> consecutive OUTPUT quads as in
+	// store_matrix_row (a wave writes contiguous pieces of 1 KiB). A lane computes exactly the four floats it stores:
+	//   transposed   quad q is row r = q % 3 of joint q / 3 -- component r of the four rows of the product: the lane reads IB[j] whole (three
+	//                quads that its two neighbours read as well) and the four floats of column r of O[k[j]] from the image
+	//   64 bytes     quad q is axis a = q & 3 of joint q >> 2 -- matrix_mul_vector3 (a < 3) or matrix_mul_point3 (a == 3) of row a of IB[j]
+	//                with O[k[j]], read whole from the image; lane 3 is the constant store_matrix_row writes
+	// in matrix_mul's operation order. The gather by k[j] is the LDS read; the joint list and IB come through the vector cache (every
+	// instance of a skin reads the same few KiB).
+	template<uint32_t kLayout>
+	__device__ __forceinline__ void store_palette_row(const f32x4* image, const uint32_t* joint_bones, const f32x4* inverse_bind, uint32_t num_joints, uint8_t* row, uint32_t lane)
+	{
+		const float* floats = reinterpret_cast<const float*>(image);
+		f32x4* out = reinterpret_cast<f32x4*>(row);
+		if constexpr (kLayout == k_palette_3x4f_transposed_48)
+		{
+			const uint32_t num_quads = num_joints * 3u;
+			for (uint32_t quad = lane; quad < num_quads; quad += k_wave_size)
+			{
+				const uint32_t joint = quad / 3u;
+				const uint32_t component = quad - joint * 3u;
+				const matrix3x4 bind = load_matrix(inverse_bind, joint);
+				const float* object = floats + joint_bones[joint] * 12u + component;
+				const float x = object[0], y = object[3], z = object[6], w = object[9];		// x_axis, y_axis, z_axis, w_axis of O at the component
+				store_streaming(&out[quad], f32x4{ ((x * bind.x_axis.x) + (y * bind.x_axis.y)) + (z * bind.x_axis.z), ((x * bind.y_axis.x) + (y * bind.y_axis.y)) + (z * bind.y_axis.z),
+					((x * bind.z_axis.x) + (y * bind.z_axis.y)) + (z * bind.z_axis.z), (((x * bind.w_axis.x) + (y * bind.w_axis.y)) + (z * bind.w_axis.z)) + w });
+			}
+		}
+		else
+		{
+			const uint32_t num_quads = num_joints * 4u;
+			for (uint32_t quad = lane; quad < num_quads; quad += k_wave_size)
+			{
+				const uint32_t joint = quad >> 2, axis = quad & 3u;
+				const float* bind_row = reinterpret_cast<const float*>(inverse_bind) + joint * 12u + axis * 3u;
+				const matrix3x4 object = load_matrix(image, joint_bones[joint]);
+				const float4 rotated = matrix_mul_vector3(bind_row[0], bind_row[1], bind_row[2], object);
+				// (the w row alone takes the translation: adding a zero to the others would turn a -0 into +0)
+				const bool is_point = axis == 3u;
+				store_streaming(&out[quad], f32x4{ is_point ? rotated.x + object.w_axis.x : rotated.x, is_point ? rotated.y + object.w_axis.y : rotated.y,
+					is_point ? rotated.z + object.w_axis.z : rotated.z, is_point ? 1.0f : 0.0f });
+			}
+		}
+	}
+
+	// pose_matrices_kernel with a palette for its store: the same front -- one wave64 per instance, images as consumer_wave_of lays them
+	// out, the skeleton's record and now the skin's on the scalar unit, the refusal in front of any load of a row, the row into the image by
+	// DMA behind the request for the walk schedule --, convert_image_to_matrices, with kObjectSpace the walk of the workgroup's images by
+	// the one rotating wave, and then store_palette_row in the place of store_matrix_row. The object matrices never leave LDS.
+	// With kObjectSpace the walking wave stores every image of the workgroup: it reads the skin of each slot that has work again on the
+	// scalar unit (a slot's work is walk.tracks; a retirement clears a record behind the launches enqueued before it, never inside one).
+	// Every wave of the workgroup reaches the __syncthreads: a wave without work (past the batch, refused, no bones) has num_bones 0.
+	template<bool kObjectSpace, uint32_t kLayout>
+	__global__ __launch_bounds__(k_consumer_max_instances * k_wave_size) void skinning_matrices_kernel(skinning_matrices_launch launch)
+	{
+		extern __shared__ __attribute__((aligned(16))) uint8_t dynamic_lds[];
+		// packed_block_shape: log2 of the instances per workgroup (bits 0..7) | words of LDS reserved for the shared walk schedule (bits 8..31)
+		const uint32_t log2_instances_per_block = launch.packed_block_shape & 0xFFu;
+		__shared__ consumer_walk_slots walk;		// (what the host subtracts from the LDS it may ask for: host_consumers.inl)
+		constexpr uint32_t record_bytes = kLayout == k_palette_3x4f_transposed_48 ? 48u : 64u;
+
+		const consumer_wave wave = consumer_wave_of(log2_instances_per_block, launch.lds_bytes_per_instance, launch.lds_quads_per_image);
+		const uint32_t lane = wave.lane, instance = wave.instance, slot = wave.slot;
+		uint32_t num_bones = 0;
+		[[maybe_unused]] uint32_t num_joints = 0;
+		[[maybe_unused]] const uint32_t* joint_bones = nullptr;
+		[[maybe_unused]] const f32x4* inverse_bind = nullptr;
+
+		if (instance < launch.num_instances)
+		{
+			// the skeleton's and the skin's record on the scalar unit; record 0 is never handed out and a cleared record is an unknown or retired handle
+			const uint32_t skeleton_id = launch.instance_skeletons != nullptr ? as_constant(launch.instance_skeletons)[instance] : launch.skeleton;
+			const uint32_t skin_id = launch.instance_skins != nullptr ? as_constant(launch.instance_skins)[instance] : launch.skin;
+			const device_skeleton skeleton = load_skeleton_fields(launch.skeletons, skeleton_id < launch.num_skeletons ? skeleton_id : 0);
+			const device_skin skin = load_skin_fields(launch.skins, skin_id < launch.num_skins ? skin_id : 0);
+			const uint32_t skeleton_bones = skeleton.num_bones;
+
+			// refused, wave uniform and in front of any load of a row: what pose_matrices_kernel refuses, with the skin's records on the output
+			// side, and a skin that is unknown or was made for another bone count. What is served reads and writes inside its own rows, and
+			// every joint's bone (< skin.num_bones at registration) lies inside the image.
+			const bool refused = skeleton_id >= launch.num_skeletons || skeleton.reference_pose == nullptr || (kObjectSpace && skeleton.hierarchy == nullptr)
+				|| skin_id >= launch.num_skins || skin.inverse_bind == nullptr || skin.num_bones != skeleton_bones
+				|| uint64_t(skeleton_bones) * 48u > launch.pose_stride_bytes || uint64_t(skin.num_joints) * record_bytes > launch.palette_stride_bytes
+				|| skeleton_bones * 3u > launch.lds_quads_per_image;
+			if (refused)
+			{
+				if (lane == 0)
+					atomicAdd(launch.rejected_count, 1ull);
+			}
+			else if (skeleton_bones != 0)
+			{
+				num_bones = skeleton_bones;
+				num_joints = skin.num_joints;
+				joint_bones = skin.joint_bones;
+				inverse_bind = skin.inverse_bind;
+				// the walk schedule first: its words travel global -> LDS while the row does
+				if (kObjectSpace)
+					request_walk_schedule(skeleton.hierarchy, log2_instances_per_block, launch.packed_block_shape >> 8, wave.shared_schedule, slot, lane, walk);
+				// the row straight into the image by DMA, lanes <-> consecutive quads (the LDS side of a piece is wave uniform + lane * 16)
+				const f32x4* source = reinterpret_cast<const f32x4*>(launch.poses + uint64_t(instance) * launch.pose_stride_bytes);
+				const uint32_t num_quads = num_bones * 3u;
+				for (uint32_t base = 0; base < num_quads; base += k_wave_size)
+				{
+					if (base + lane < num_quads)
+						__builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(source + base + lane),
+							(__attribute__((address_space(3))) void*)(wave.image + base), 16, 0, 0);
+				}
+			}
+		}
+		wave_lds_barrier();		// the wave's row is complete (vmcnt)
+		convert_image_to_matrices(wave.image, num_bones, lane);
+
+		if constexpr (kObjectSpace)
+		{
+			if (lane == 0)
+			{
+				// (a slot with work has its steps and its schedule already: request_walk_schedule)
+				if (num_bones == 0)
+				{
+					walk.levels[slot] = 0;
+					walk.schedules[slot] = nullptr;
+				}
+				walk.tracks[slot] = num_bones;
+			}
+			__syncthreads();
+			// ONE wave walks and then stores the workgroup's palettes; the others are done (finish_consumer_poses says why, and why it rotates)
+			if (wave.wave_in_block != (blockIdx.x & ((blockDim.x / k_wave_size) - 1u)))
+				return;
+			walk_workgroup_matrices(walk, wave.shared_schedule, log2_instances_per_block, launch.lds_bytes_per_instance, 0, lane);
+			wave_lds_barrier();
+			const uint32_t instances_per_block = 1u << log2_instances_per_block;
+			for (uint32_t store_slot = 0; store_slot < instances_per_block; ++store_slot)
+			{
+				// (wave uniform: every lane reads the same word)
+				if (__builtin_amdgcn_readfirstlane(walk.tracks[store_slot]) == 0)
+					continue;
+				// the slot was served: its handle is a live skin's, checked by the slot's own wave
+				const uint32_t store_instance = (blockIdx.x << log2_instances_per_block) + store_slot;
+				const uint32_t skin_id = launch.instance_skins != nullptr ? as_constant(launch.instance_skins)[store_instance] : launch.skin;
+				const device_skin skin = load_skin_fields(launch.skins, skin_id);
+				store_palette_row<kLayout>(reinterpret_cast<const f32x4*>(dynamic_lds + size_t(store_slot) * launch.lds_bytes_per_instance), skin.joint_bones, skin.inverse_bind,
+					skin.num_joints, launch.palettes + uint64_t(store_instance) * launch.palette_stride_bytes, lane);
+			}
+		}
+		else
+		{
+			wave_lds_barrier();		// every bone has its matrix
+			store_palette_row<kLayout>(wave.image, joint_bones, inverse_bind, num_joints, launch.palettes + uint64_t(instance) * launch.palette_stride_bytes, lane);
+		}
+	}
+
 	// ---- how far two pose buffers are apart (aclhip_measure_pose_error_batch; include/aclhip.h states the definition) --------------------
 	struct pose_error_record { float error; uint32_t bone; };		// aclhip_pose_error
 	constexpr uint32_t k_no_bone = 0xFFFFFFFFu;						// ACLHIP_NO_BONE

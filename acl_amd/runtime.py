@@ -53,6 +53,7 @@ EXPORTED_SYMBOLS = [
     "aclhip_inverse_transform_poses_batch",
     "aclhip_measure_pose_error_batch",
     "aclhip_pose_matrices_batch", "aclhip_measure_pose_error_metric_batch",
+    "aclhip_check_skin", "aclhip_register_skin", "aclhip_unregister_skin", "aclhip_get_skin_info", "aclhip_skinning_matrices_batch",
 ]
 
 
@@ -188,6 +189,27 @@ class PoseMatricesDesc(ctypes.Structure):
 
 MATRIX_3X4F_64 = 0                                          # aclhip_matrix_layout: 64 bytes per bone, x_axis | y_axis | z_axis | w_axis
 ERROR_METRIC_QVVF, ERROR_METRIC_QVVF_MATRIX3X4F = 0, 1      # aclhip_error_metric
+
+
+class SkinInfo(ctypes.Structure):
+    """aclhip_skin_info"""
+    _fields_ = [
+        ("num_joints", ctypes.c_uint32), ("num_bones", ctypes.c_uint32), ("is_identity_joint_list", ctypes.c_uint32), ("has_inverse_bind", ctypes.c_uint32),
+        ("reserved", ctypes.c_uint32 * 4),
+    ]
+
+
+class SkinningDesc(ctypes.Structure):
+    """aclhip_skinning_desc; `instance_skeletons` and `instance_skins` are device addresses or None"""
+    _fields_ = [
+        ("skeleton", ctypes.c_uint32), ("instance_skeletons", ctypes.c_void_p), ("skin", ctypes.c_uint32), ("instance_skins", ctypes.c_void_p),
+        ("object_space", ctypes.c_uint32), ("layout", ctypes.c_uint32), ("reserved", ctypes.c_uint64 * 2),
+    ]
+
+
+PALETTE_3X4F_64, PALETTE_3X4F_TRANSPOSED_48 = 0, 1         # aclhip_palette_layout: 64 bytes per joint as MATRIX_3X4F_64 | three float4 rows, 48 bytes
+PALETTE_RECORD_BYTES = {PALETTE_3X4F_64: 64, PALETTE_3X4F_TRANSPOSED_48: 48}
+MAX_SKINS = 4096            # ACLHIP_MAX_SKINS
 
 
 class PoseBufferBlend(ctypes.Structure):
@@ -396,6 +418,11 @@ def load_library():
     lib.aclhip_measure_pose_error_batch.argtypes = [vp, vp, u64, vp, u64, u32, ctypes.POINTER(PoseErrorDesc), vp, vp]
     lib.aclhip_measure_pose_error_metric_batch.argtypes = [vp, vp, u64, vp, u64, u32, ctypes.POINTER(PoseErrorDesc), u32, vp, vp]
     lib.aclhip_pose_matrices_batch.argtypes = [vp, vp, u64, u32, ctypes.POINTER(PoseMatricesDesc), vp, u64, vp]
+    lib.aclhip_check_skin.argtypes = [vp, vp, u32, u32, ctypes.POINTER(SkinInfo), ctypes.c_char_p, u32]
+    lib.aclhip_register_skin.argtypes = [vp, vp, vp, u32, u32, ctypes.POINTER(u32)]
+    lib.aclhip_unregister_skin.argtypes = [vp, u32]
+    lib.aclhip_get_skin_info.argtypes = [vp, u32, ctypes.POINTER(SkinInfo)]
+    lib.aclhip_skinning_matrices_batch.argtypes = [vp, vp, u64, u32, ctypes.POINTER(SkinningDesc), vp, u64, vp]
     _lib = lib
     return lib
 
@@ -426,6 +453,31 @@ def check_blend_mask(weights, num_slots=None):
         num_slots = table.size if table is not None else 0
     message, info = ctypes.create_string_buffer(256), BlendMaskInfo()
     status = load_library().aclhip_check_blend_mask(table.ctypes.data if table is not None else None, int(num_slots), ctypes.byref(info), message, 256)
+    return status, message.value.decode(), info
+
+
+def _skin_arrays(joint_bones, inverse_bind, num_joints, num_bones):
+    joints = np.ascontiguousarray(joint_bones, dtype=np.uint32) if joint_bones is not None else None
+    matrices = np.ascontiguousarray(inverse_bind, dtype=np.float32) if inverse_bind is not None else None
+    if num_joints is None:
+        num_joints = joints.size if joints is not None else (matrices.size // 16 if matrices is not None else num_bones)
+    num_joints = int(num_joints)
+    # (the library reads num_joints entries of each array it is handed: never more than the caller's arrays hold)
+    if joints is not None and joints.size < num_joints:
+        raise ValueError(f"joint_bones holds {joints.size} entries, num_joints is {num_joints}")
+    if matrices is not None and matrices.size < 16 * num_joints:
+        raise ValueError(f"inverse_bind holds {matrices.size} floats, {num_joints} joints need {16 * num_joints}")
+    return joints, matrices, num_joints
+
+
+def check_skin(joint_bones, inverse_bind, num_bones, num_joints=None):
+    """Host only validation of a skin (no GPU needed): what aclhip_register_skin checks. joint_bones: uint32 [num_joints] or None (the
+    identity list); inverse_bind: float32 [num_joints, 4, 4] in the MATRIX_3X4F_64 layout or None (identity matrices). Returns (status,
+    message, SkinInfo)."""
+    joints, matrices, num_joints = _skin_arrays(joint_bones, inverse_bind, num_joints, num_bones)
+    message, info = ctypes.create_string_buffer(256), SkinInfo()
+    status = load_library().aclhip_check_skin(joints.ctypes.data if joints is not None else None, matrices.ctypes.data if matrices is not None else None,
+                                              num_joints, int(num_bones), ctypes.byref(info), message, 256)
     return status, message.value.decode(), info
 
 
@@ -879,6 +931,31 @@ class Context:
         (device addresses), in local space or, with desc.object_space, through the matrix walk; `desc` is a PoseMatricesDesc."""
         self._check(self._lib.aclhip_pose_matrices_batch(self._handle, local_poses_ptr, local_pose_stride_bytes, num_instances,
                                                          ctypes.byref(desc) if desc is not None else None, matrices_ptr, matrix_stride_bytes, stream))
+
+    # ---- skins: a mesh's joint list and inverse bind matrices, and the skinning palettes made with them ----
+    def register_skin(self, joint_bones, inverse_bind, num_bones, num_joints=None):
+        """joint_bones: host uint32 [num_joints], each < num_bones, or None (the identity list); inverse_bind: host float32 [num_joints, 4, 4]
+        in the MATRIX_3X4F_64 layout, or None (identity matrices). Returns the skin handle (>= 1)."""
+        joints, matrices, num_joints = _skin_arrays(joint_bones, inverse_bind, num_joints, num_bones)
+        handle = ctypes.c_uint32(0)
+        self._check(self._lib.aclhip_register_skin(self._handle, joints.ctypes.data if joints is not None else None, matrices.ctypes.data if matrices is not None else None,
+                                                   num_joints, int(num_bones), ctypes.byref(handle)))
+        return handle.value
+
+    def unregister_skin(self, skin):
+        self._check(self._lib.aclhip_unregister_skin(self._handle, skin))
+
+    def skin_info(self, skin):
+        info = SkinInfo()
+        self._check(self._lib.aclhip_get_skin_info(self._handle, skin, ctypes.byref(info)))
+        return info
+
+    def skinning_matrices_batch(self, poses_ptr, pose_stride_bytes, num_instances, desc, palettes_ptr, palette_stride_bytes, stream=None):
+        """aclhip_skinning_matrices_batch: per joint of desc's skin inverse_bind * object matrix of its bone, from the QVV48 rows at poses_ptr
+        into the rows at palettes_ptr (device addresses), 64 or 48 bytes per joint by desc.layout; with desc.object_space the rows are local
+        and go through the matrix walk. `desc` is a SkinningDesc."""
+        self._check(self._lib.aclhip_skinning_matrices_batch(self._handle, poses_ptr, pose_stride_bytes, num_instances,
+                                                             ctypes.byref(desc) if desc is not None else None, palettes_ptr, palette_stride_bytes, stream))
 
     def decompress_poses_mapped(self, clips, sample_times, skeletons, maps, num_bones, additive_format=ADDITIVE_NONE, object_space=False, base_clips=None,
                                 base_sample_times=None, base_maps=None, base_poses=None, params=None, out=None, instance_rounding=None, instance_looping=None,

@@ -205,7 +205,8 @@ const char* aclhip_last_error_message(const aclhip_context* context);
  * skeletons -- aclhip_skeleton_info, aclhip_pose_mapping and their entry points -- and for the pose error measure -- aclhip_pose_error,
  * aclhip_pose_error_worst, aclhip_pose_error_desc and aclhip_measure_pose_error_batch -- and for the matrix object space --
  * aclhip_matrix_layout, aclhip_pose_matrices_desc, aclhip_error_metric, aclhip_pose_matrices_batch and
- * aclhip_measure_pose_error_metric_batch).
+ * aclhip_measure_pose_error_metric_batch -- and for the skinning palettes -- aclhip_skin_info, aclhip_palette_layout,
+ * aclhip_skinning_desc, the four skin entry points and aclhip_skinning_matrices_batch).
  * A caller compiled against another header would hand over structs of another shape; aclhip_abi_version() says what the LIBRARY was
  * built with, and the C++ mirror (aclhip.hpp) refuses to create a context when the two differ. */
 #define ACLHIP_ABI_VERSION 6u
@@ -1410,8 +1411,8 @@ typedef struct aclhip_pose_matrices_desc
  *   The launch's shape comes from min(local_pose_stride_bytes / 48, matrix_stride_bytes / 64) slots per LDS image. Registered clips play
  * no part. The launch goes on `stream`, can be captured into a graph, and uploads nothing.
  *   Out of scope (nothing here precludes them): an additive buffer in the matrix launch (chain aclhip_transform_poses_batch in local
- * space first); a 48 byte transposed layout and inverse bind matrices; bounds; the _no_scale variants; a decode fused into either launch;
- * QVV40 / QV32 rows; instance lists; the C++ mirror in aclhip.hpp.
+ * space first); bounds; the _no_scale variants; a decode fused into either launch; QVV40 / QV32 rows; instance lists; the C++ mirror in
+ * aclhip.hpp. (A 48 byte transposed layout and inverse bind matrices: aclhip_skinning_matrices_batch, below.)
  *   What it costs (one MI355X, 65 536 x 100 bones, object space; tools/pose_matrices.py, profiles/pose_matrices.md, DESIGN.md 4.7 "Pose
  * matrices"): 129.8 us next to 109.6 us of aclhip_transform_poses_batch with object space from the same buffer -- 1.18 x the time for
  * 1.17 x the bytes, both at 0.71 of the HBM peak. */
@@ -1440,6 +1441,97 @@ typedef enum aclhip_error_metric
 aclhip_status aclhip_measure_pose_error_metric_batch(aclhip_context* context, const void* raw_poses, uint64_t raw_pose_stride_bytes,
 	const void* lossy_poses, uint64_t lossy_pose_stride_bytes, uint32_t num_instances, const aclhip_pose_error_desc* desc, uint32_t metric,
 	aclhip_pose_error* errors /* DEVICE [num_instances], required */, void* stream);
+
+/* ---- skinning palettes: inverse bind matrices times object matrices, per mesh joint ------------------
+ * A renderer does not skin with the object space matrices of the bones: it skins with a PALETTE -- per mesh joint j the matrix
+ * inverse_bind[j] * object[bone_of_joint[j]], usually packed as three float4 rows (48 bytes). aclhip_skinning_matrices_batch is
+ * aclhip_pose_matrices_batch with that product and that packing in the place of its store: the object matrices never reach HBM, and a
+ * caller needs no kernel of its own between the pose buffer and the draw. (ABI version 6 still: two added structs, an added enum and five
+ * added functions, no existing struct changed.)
+ *
+ * A SKIN is what a mesh brings to a skeleton (glTF skin.joints + inverseBindMatrices, an FBX cluster list): num_joints palette entries,
+ * for each the skeleton bone it follows and its inverse bind matrix.
+ * aclhip_register_skin: `joint_bones` (HOST, num_joints entries, each < num_bones; NULL: the identity list, and then num_joints ==
+ * num_bones is required; duplicates are allowed -- two joints may follow one bone, so num_joints may exceed num_bones); `inverse_bind`
+ * (HOST, num_joints records in the ACLHIP_MATRIX_3X4F_64 layout -- 16 floats, x_axis | y_axis | z_axis | w_axis, what
+ * aclhip_pose_matrices_batch writes: a caller can make the bind pose's object matrices with that call and invert them on the host; lane 3
+ * of every axis is ignored; NULL: identity matrices). Refused with ACLHIP_ERROR_INVALID_ARGUMENT before any device call (the message
+ * names the first offending joint): num_joints == 0 or > 0xFFFF; num_bones == 0 or > 0xFFFF; a joint bone >= num_bones; a matrix
+ * component (lanes 0-2) that is not finite; NULL joint_bones with num_joints != num_bones. Lifetime is a blend mask's: the device table
+ * (ACLHIP_MAX_SKINS records) is allocated at the first registration and never moves, so a captured hipGraph that names a skin stays valid
+ * while others come and go; handle 0 is null; uploads go on the context's own stream; unregistration is stream ordered (launches already
+ * enqueued still see the skin, later ones refuse it) and nobody waits. */
+typedef uint32_t aclhip_skin;				/* handle returned by aclhip_register_skin; 0 = none */
+#define ACLHIP_MAX_SKINS 4096u				/* live skins of one context, the null handle included */
+
+typedef struct aclhip_skin_info
+{
+	uint32_t num_joints;
+	uint32_t num_bones;						/* the skeleton size the skin was made for */
+	uint32_t is_identity_joint_list;		/* num_joints == num_bones and joint_bones[j] == j */
+	uint32_t has_inverse_bind;				/* 0: registered with NULL (identity matrices) */
+	uint32_t reserved[4];
+} aclhip_skin_info;
+
+/* Host only (no context, no device): what registration checks and what aclhip_get_skin_info reports. `message` (may be NULL,
+ * `message_capacity` bytes) receives the reason when the skin is refused; `out_info` may be NULL. */
+aclhip_status aclhip_check_skin(const uint32_t* joint_bones, const float* inverse_bind, uint32_t num_joints, uint32_t num_bones,
+	aclhip_skin_info* out_info, char* message, uint32_t message_capacity);
+
+aclhip_status aclhip_register_skin(aclhip_context* context, const uint32_t* joint_bones, const float* inverse_bind, uint32_t num_joints,
+	uint32_t num_bones, aclhip_skin* out_skin);
+aclhip_status aclhip_unregister_skin(aclhip_context* context, aclhip_skin skin);
+aclhip_status aclhip_get_skin_info(const aclhip_context* context, aclhip_skin skin, aclhip_skin_info* out_info);
+
+typedef enum aclhip_palette_layout
+{
+	ACLHIP_PALETTE_3X4F_64 = 0,				/* rtm::matrix3x4f, as aclhip_pose_matrices_batch writes it: lane 3 = 0, 0, 0, 1 */
+	ACLHIP_PALETTE_3X4F_TRANSPOSED_48 = 1	/* three float4 rows r_k = (x_axis[k], y_axis[k], z_axis[k], w_axis[k]), k = 0, 1, 2:
+											 * p' = (dot(r_0, (p, 1)), dot(r_1, (p, 1)), dot(r_2, (p, 1))) -- an HLSL float3x4, three texel fetches */
+} aclhip_palette_layout;
+
+typedef struct aclhip_skinning_desc
+{
+	aclhip_skeleton skeleton;					/*  0  for every instance when instance_skeletons is NULL */
+	const aclhip_skeleton* instance_skeletons;	/*  8  DEVICE [num_instances] or NULL */
+	aclhip_skin skin;							/* 16  for every instance when instance_skins is NULL */
+	const aclhip_skin* instance_skins;			/* 24  DEVICE [num_instances] or NULL */
+	uint32_t object_space;						/* 32  1: the matrix walk over local rows; 0: the rows are taken as they are (already object space) */
+	uint32_t layout;							/* 36  aclhip_palette_layout */
+	uint64_t reserved[2];						/* 40  0 */
+} aclhip_skinning_desc;							/* 56 bytes */
+
+/* The definition. Instance i has skeleton S (desc->skeleton, or instance_skeletons[i]) with B bones and skin K (desc->skin, or
+ * instance_skins[i]) with J joints, bones k[j] and inverse bind matrices IB[j]; L is the B QVV48 records at poses + i * pose_stride_bytes.
+ *   1. O = steps 1 and 2 of aclhip_pose_matrices_batch over L: M[b] = matrix_from_qvv(L[b]) and, with object_space, O[b] =
+ *      matrix_mul(M[b], O[P[b]]) for every bone that has a parent; without it O = M. Bit for bit what that launch would store.
+ *   2. S[j] = matrix_mul(IB[j], O[k[j]]), lhs first, in the operation order of step 2 there: with R = O[k[j]] and v one of the three axis
+ *      rows of IB[j], the row of S[j] is ((R.x_axis * v.x) + R.y_axis * v.y) + R.z_axis * v.z per component; the w row is the same with v =
+ *      IB[j].w_axis, plus R.w_axis, added last. fp32, one IEEE operation at a time, never fused. The product is made with identity
+ *      matrices too (a skin registered with NULL): a NaN or an infinity of bone k[j] reaches joint j, and no other joint.
+ *   3. Row i of `palettes` (at palettes + i * palette_stride_bytes) gets J records. ACLHIP_PALETTE_3X4F_64: 64 bytes, x_axis | y_axis |
+ *      z_axis | w_axis of S[j] with lane 3 written as +0, +0, +0, 1.0f. ACLHIP_PALETTE_3X4F_TRANSPOSED_48: 48 bytes, the three rows
+ *      r_k = (S[j].x_axis[k], S[j].y_axis[k], S[j].z_axis[k], S[j].w_axis[k]); there is no spare lane. Bytes of a row behind the J
+ *      records are untouched.
+ *   Nothing is normalized and there is no rtm::qvv_mul here: aclhip_get_negative_scale_count does not move.
+ *   Refused and counted (aclhip_get_rejected_instance_count), the row untouched, decided in front of any load of a row: an unknown or
+ * retired skeleton or skin handle (0 included); a skin whose num_bones differs from the skeleton's; object_space on a skeleton without
+ * hierarchy; B * 48 > pose_stride_bytes; J * (64 or 48) > palette_stride_bytes; B beyond the launch's LDS image.
+ *   ACLHIP_ERROR_INVALID_ARGUMENT, decided before any device call, each with a message (with or without a context): desc, poses or
+ * palettes == NULL; no skeleton at all; no skin at all; an unknown layout; pointers or strides that are not 16 byte aligned; reserved
+ * fields that are not 0; a shape that does not fit the LDS; ANY overlap of the output range with the input range (the pose rows, the
+ * skeleton list, the skin list) -- there is no in place form.
+ *   The launch's shape comes from pose_stride_bytes / 48 slots per LDS image. Registered clips play no part. The launch goes on `stream`,
+ * can be captured into a graph, and uploads nothing.
+ *   Out of scope (nothing here precludes them): computing inverse bind matrices on the device; bounds; a decode fused into the launch;
+ * QVV40 / QV32 rows; dual quaternions; the C++ mirror in aclhip.hpp.
+ *   What it costs (one MI355X, 65 536 x 100 bones, a skin of 100 joints, object space, medians of three interleaved rounds of 20 launches;
+ * tools/skinning_matrices.py, profiles/skinning_matrices.md, DESIGN.md 4.7 "Skinning matrices"): 166.3 us for the transposed layout and
+ * 186.9 us for the 64 byte layout next to 130.9 us of aclhip_pose_matrices_batch with object space from the same buffer in the same
+ * rounds -- 1.27 x and 1.43 x its time for 0.86 x and 1.00 x its bytes, 0.47 and 0.49 of the HBM peak against its 0.70: the launch is not
+ * priced by its bytes yet; the one storing wave's dependent loads per joint are the suspect, and no counter run has been taken. */
+aclhip_status aclhip_skinning_matrices_batch(aclhip_context* context, const void* poses, uint64_t pose_stride_bytes, uint32_t num_instances,
+	const aclhip_skinning_desc* desc, void* palettes, uint64_t palette_stride_bytes, void* stream);
 
 /* ---- multi-GPU ---------------------------------------------------------------------------------- */
 
