@@ -13,6 +13,7 @@
 //   decompress_poses_consumer_kernel   the same decode, whole pose per wave, followed by what callers do next with a local pose -- blend K
 //                                      clip instances, apply an additive clip onto its base, local -> object space -- before the pose leaves LDS.
 //   transform_poses_kernel             the same consumers over a caller's pose buffers: the LDS image is filled from a row in HBM, not from a clip.
+//   sample_raw_tracks_kernel           uncompressed clips (raw track arrays): one lane per quad of the pose row, two 16 byte loads, one store.
 //   decompress_track_kernel            one thread per (instance, bone) request; the registration time plan replaces the
 //                                      reference's O(track index) skip over preceding widths.
 //   decompress_scalar_tracks_kernel    scalar track lists: one wave64 per (instance, 256 tracks), lanes <-> tracks.
@@ -55,6 +56,7 @@ namespace aclhip
 #include "kernels_consumers.inl"
 #include "kernels_skeleton.inl"
 #include "kernels_pose_buffers.inl"
+#include "kernels_raw_tracks.inl"
 #include "kernels_misc.inl"
 #include "kernels_scalar.inl"
 #include "kernels_track.inl"
@@ -80,5 +82,6 @@ using namespace aclhip;
 #include "host_blend_masks.inl"
 #include "host_pose_buffers.inl"
 #include "host_skins.inl"
+#include "host_raw_tracks.inl"
 #include "host_bone_object.inl"
 #include "host_scalar_misc.inl"

@@ -54,6 +54,8 @@ EXPORTED_SYMBOLS = [
     "aclhip_measure_pose_error_batch",
     "aclhip_pose_matrices_batch", "aclhip_measure_pose_error_metric_batch",
     "aclhip_check_skin", "aclhip_register_skin", "aclhip_unregister_skin", "aclhip_get_skin_info", "aclhip_skinning_matrices_batch",
+    "aclhip_check_raw_tracks", "aclhip_register_raw_tracks", "aclhip_unregister_raw_tracks", "aclhip_get_raw_tracks_info",
+    "aclhip_sample_raw_tracks_batch",
 ]
 
 
@@ -210,6 +212,26 @@ class SkinningDesc(ctypes.Structure):
 PALETTE_3X4F_64, PALETTE_3X4F_TRANSPOSED_48 = 0, 1         # aclhip_palette_layout: 64 bytes per joint as MATRIX_3X4F_64 | three float4 rows, 48 bytes
 PALETTE_RECORD_BYTES = {PALETTE_3X4F_64: 64, PALETTE_3X4F_TRANSPOSED_48: 48}
 MAX_SKINS = 4096            # ACLHIP_MAX_SKINS
+
+
+class RawTracksInfo(ctypes.Structure):
+    """aclhip_raw_tracks_info"""
+    _fields_ = [
+        ("num_tracks", ctypes.c_uint32), ("num_samples", ctypes.c_uint32), ("sample_rate", ctypes.c_float), ("duration", ctypes.c_float),
+        ("looping_policy", ctypes.c_uint32), ("reserved", ctypes.c_uint32 * 3),
+    ]
+
+
+class RawSampleDesc(ctypes.Structure):
+    """aclhip_raw_sample_desc; every pointer is a device address or None"""
+    _fields_ = [
+        ("rounding_policy", ctypes.c_uint8), ("reserved0", ctypes.c_uint8 * 7), ("instance_rounding_policies", ctypes.c_void_p),
+        ("track_rounding_policies", ctypes.c_void_p), ("num_track_rounding_policies", ctypes.c_uint32), ("reserved1", ctypes.c_uint32),
+        ("rows", ctypes.c_void_p), ("reserved", ctypes.c_uint64 * 2),
+    ]
+
+
+MAX_RAW_TRACKS = 4096       # ACLHIP_MAX_RAW_TRACKS
 
 
 class PoseBufferBlend(ctypes.Structure):
@@ -423,6 +445,11 @@ def load_library():
     lib.aclhip_unregister_skin.argtypes = [vp, u32]
     lib.aclhip_get_skin_info.argtypes = [vp, u32, ctypes.POINTER(SkinInfo)]
     lib.aclhip_skinning_matrices_batch.argtypes = [vp, vp, u64, u32, ctypes.POINTER(SkinningDesc), vp, u64, vp]
+    lib.aclhip_check_raw_tracks.argtypes = [vp, u32, u32, ctypes.c_float, u32, ctypes.POINTER(RawTracksInfo), ctypes.c_char_p, u32]
+    lib.aclhip_register_raw_tracks.argtypes = [vp, vp, u32, u32, ctypes.c_float, u32, ctypes.POINTER(u32)]
+    lib.aclhip_unregister_raw_tracks.argtypes = [vp, u32]
+    lib.aclhip_get_raw_tracks_info.argtypes = [vp, u32, ctypes.POINTER(RawTracksInfo)]
+    lib.aclhip_sample_raw_tracks_batch.argtypes = [vp, vp, vp, u32, ctypes.POINTER(RawSampleDesc), vp, u64, vp]
     _lib = lib
     return lib
 
@@ -478,6 +505,23 @@ def check_skin(joint_bones, inverse_bind, num_bones, num_joints=None):
     message, info = ctypes.create_string_buffer(256), SkinInfo()
     status = load_library().aclhip_check_skin(joints.ctypes.data if joints is not None else None, matrices.ctypes.data if matrices is not None else None,
                                               num_joints, int(num_bones), ctypes.byref(info), message, 256)
+    return status, message.value.decode(), info
+
+
+def _raw_samples(samples):
+    """[num_samples, num_tracks, 12] float32, contiguous: the sample major QVV48 layout the library takes"""
+    array = np.ascontiguousarray(samples, dtype=np.float32)
+    if array.ndim != 3 or array.shape[2] != 12:
+        raise ValueError(f"raw samples are [num_samples, num_tracks, 12] floats, not {array.shape}")
+    return array
+
+
+def check_raw_tracks(samples, sample_rate, looping_policy=LOOP_CLAMP):
+    """Host only validation of a raw track array (no GPU needed): what aclhip_register_raw_tracks checks. samples: float32
+    [num_samples, num_tracks, 12]. Returns (status, message, RawTracksInfo)."""
+    array = _raw_samples(samples)
+    message, info = ctypes.create_string_buffer(256), RawTracksInfo()
+    status = load_library().aclhip_check_raw_tracks(array.ctypes.data, array.shape[1], array.shape[0], float(sample_rate), int(looping_policy), ctypes.byref(info), message, 256)
     return status, message.value.decode(), info
 
 
@@ -957,6 +1001,31 @@ class Context:
         self._check(self._lib.aclhip_skinning_matrices_batch(self._handle, poses_ptr, pose_stride_bytes, num_instances,
                                                              ctypes.byref(desc) if desc is not None else None, palettes_ptr, palette_stride_bytes, stream))
 
+    # ---- raw track arrays: uncompressed clips (acl::track_array_qvvf) and their sample_tracks ----
+    def register_raw_tracks(self, samples, sample_rate, looping_policy=LOOP_CLAMP):
+        """samples: host float32 [num_samples, num_tracks, 12], QVV48 records, sample major (what the tests hand to ref_compress); the array
+        is copied. looping_policy: LOOP_CLAMP or LOOP_WRAP. Returns the raw tracks handle (>= 1)."""
+        array = _raw_samples(samples)
+        handle = ctypes.c_uint32(0)
+        self._check(self._lib.aclhip_register_raw_tracks(self._handle, array.ctypes.data, array.shape[1], array.shape[0], float(sample_rate), int(looping_policy),
+                                                         ctypes.byref(handle)))
+        return handle.value
+
+    def unregister_raw_tracks(self, raw):
+        self._check(self._lib.aclhip_unregister_raw_tracks(self._handle, raw))
+
+    def raw_tracks_info(self, raw):
+        info = RawTracksInfo()
+        self._check(self._lib.aclhip_get_raw_tracks_info(self._handle, raw, ctypes.byref(info)))
+        return info
+
+    def sample_raw_tracks_batch(self, raws_ptr, times_ptr, num_instances, poses_ptr, pose_stride_bytes, desc=None, stream=None):
+        """aclhip_sample_raw_tracks_batch: track_array_qvvf::sample_tracks of the raw track arrays named at raws_ptr (device uint32
+        [num_instances]) at the times at times_ptr into QVV48 rows at poses_ptr (device addresses). `desc` is a RawSampleDesc or None
+        (ROUND_NONE, row i)."""
+        self._check(self._lib.aclhip_sample_raw_tracks_batch(self._handle, raws_ptr, times_ptr, num_instances, ctypes.byref(desc) if desc is not None else None,
+                                                             poses_ptr, pose_stride_bytes, stream))
+
     def decompress_poses_mapped(self, clips, sample_times, skeletons, maps, num_bones, additive_format=ADDITIVE_NONE, object_space=False, base_clips=None,
                                 base_sample_times=None, base_maps=None, base_poses=None, params=None, out=None, instance_rounding=None, instance_looping=None,
                                 blend_clips=None, blend_sample_times=None, blend_maps=None, blend_weights=None, flags=0):
@@ -1334,6 +1403,75 @@ def clip_error(ctx, clip_a, clip_b, skeleton, shells, object_space=True, params_
         ctx.measure_pose_error(d_poses[0].data_ptr(), stride, d_poses[1].data_ptr(), stride, num_samples, desc, d_errors.data_ptr(), stream=stream.cuda_stream)
     else:
         ctx.measure_pose_error_metric(d_poses[0].data_ptr(), stride, d_poses[1].data_ptr(), stride, num_samples, desc, metric, d_errors.data_ptr(), stream=stream.cuda_stream)
+    stream.synchronize()
+    worst = d_worst.cpu().numpy().view(POSE_ERROR_WORST_DTYPE)[0]
+    if int(worst["instance"]) == 0xFFFFFFFF:
+        return NO_BONE, -1.0, float("nan")
+    return int(worst["bone"]), float(worst["error"]), float(sample_times[int(worst["instance"])])
+
+
+def raw_clip_error(ctx, raw, clip, skeleton, shells, object_space=True, params=None, metric=ERROR_METRIC_QVVF, additive_base=None, additive_format=ADDITIVE_NONE,
+                   rounding=None):
+    """acl::calculate_compression_error(allocator, raw_tracks, context, error_metric, additive_base_tracks) (impl/track_error.impl.h:581-689,
+    loop :319-376) as launches: what a compression setting costs a clip. `raw` is a raw track array (register_raw_tracks) and `clip` its
+    registered compressed form; the clip's tracks are the raw array's, in order, and the skeleton's bones. Instances are the raw array's
+    samples: the array is sampled (aclhip_sample_raw_tracks_batch) and the clip decoded at min(i / rate, duration) with the array's rate
+    and duration, both with `rounding` -- by default the reference's choice: ROUND_NONE when the clip has a database or stripped key
+    frames, ROUND_NEAREST otherwise --, then the two buffers are measured with the launch's worst record. `additive_base` is another raw
+    track array: it fills a base buffer at (t / duration) * its own duration (at 0 when it has one sample) and the measure applies both
+    poses onto it with `additive_format`; the matrix metric takes no additive base (the measure refuses it). `params` are the decode's
+    (its rounding policy is replaced). Returns (bone, error, sample_time) like clip_error. Synchronous."""
+    import torch
+    device = torch.device("cuda", ctx.device_index)
+    info = ctx.raw_tracks_info(raw)
+    num_bones, num_samples = int(info.num_tracks), int(info.num_samples)
+    duration = np.float32(info.duration)
+    sample_times = np.minimum(np.arange(num_samples, dtype=np.float32) / np.float32(info.sample_rate), duration).astype(np.float32)
+    if rounding is None:
+        clip_info = ctx.clip_info(clip)
+        rounding = ROUND_NONE if clip_info.has_database or clip_info.has_stripped_keyframes else ROUND_NEAREST
+    stride = num_bones * 48
+    stream = torch.cuda.current_stream(device)
+    d_times = torch.from_numpy(sample_times).to(device)
+    d_raw, d_lossy = (torch.zeros((num_samples, stride // 4), dtype=torch.float32, device=device) for _ in range(2))
+    d_errors = torch.zeros((num_samples, 2), dtype=torch.int32, device=device)
+    d_worst = torch.zeros(4, dtype=torch.int32, device=device)
+
+    sample_desc = RawSampleDesc()
+    sample_desc.rounding_policy = int(rounding)
+    d_raws = torch.full((num_samples,), int(raw), dtype=torch.int32, device=device)
+    ctx.sample_raw_tracks_batch(d_raws.data_ptr(), d_times.data_ptr(), num_samples, d_raw.data_ptr(), stride, desc=sample_desc, stream=stream.cuda_stream)
+    decode_params = DecompressParams.from_buffer_copy(params) if params is not None else default_params()
+    decode_params.rounding_policy = int(rounding)
+    d_clips = torch.full((num_samples,), int(clip), dtype=torch.int32, device=device)
+    ctx.decompress_tracks_batch(d_clips.data_ptr(), d_times.data_ptr(), num_samples, d_lossy.data_ptr(), stride, params=decode_params, stream=stream.cuda_stream)
+
+    desc = PoseErrorDesc()
+    desc.skeleton, desc.object_space = int(skeleton), 1 if object_space else 0
+    if additive_base is not None:
+        base_info = ctx.raw_tracks_info(additive_base)
+        if int(base_info.num_samples) > 1:
+            with np.errstate(invalid="ignore", divide="ignore"):
+                base_times = ((sample_times / duration) * np.float32(base_info.duration)).astype(np.float32)
+            base_times[np.isnan(base_times)] = 0.0          # (a raw array of one sample: its duration is 0)
+        else:
+            base_times = np.zeros(num_samples, dtype=np.float32)
+        base_stride = int(base_info.num_tracks) * 48
+        d_base_times = torch.from_numpy(base_times).to(device)
+        d_base = torch.zeros((num_samples, base_stride // 4), dtype=torch.float32, device=device)
+        d_bases = torch.full((num_samples,), int(additive_base), dtype=torch.int32, device=device)
+        ctx.sample_raw_tracks_batch(d_bases.data_ptr(), d_base_times.data_ptr(), num_samples, d_base.data_ptr(), base_stride, desc=sample_desc, stream=stream.cuda_stream)
+        desc.additive_format, desc.base_poses, desc.base_pose_stride_bytes = int(additive_format), d_base.data_ptr(), base_stride
+    if np.ndim(shells) == 0:
+        desc.shell_distance = float(shells)
+    else:
+        d_shells = torch.from_numpy(np.ascontiguousarray(shells, dtype=np.float32)).to(device)
+        desc.shell_distances, desc.num_shell_distances = d_shells.data_ptr(), d_shells.numel()
+    desc.worst = d_worst.data_ptr()
+    if metric == ERROR_METRIC_QVVF:
+        ctx.measure_pose_error(d_raw.data_ptr(), stride, d_lossy.data_ptr(), stride, num_samples, desc, d_errors.data_ptr(), stream=stream.cuda_stream)
+    else:
+        ctx.measure_pose_error_metric(d_raw.data_ptr(), stride, d_lossy.data_ptr(), stride, num_samples, desc, metric, d_errors.data_ptr(), stream=stream.cuda_stream)
     stream.synchronize()
     worst = d_worst.cpu().numpy().view(POSE_ERROR_WORST_DTYPE)[0]
     if int(worst["instance"]) == 0xFFFFFFFF:

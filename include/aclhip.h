@@ -206,7 +206,8 @@ const char* aclhip_last_error_message(const aclhip_context* context);
  * aclhip_pose_error_worst, aclhip_pose_error_desc and aclhip_measure_pose_error_batch -- and for the matrix object space --
  * aclhip_matrix_layout, aclhip_pose_matrices_desc, aclhip_error_metric, aclhip_pose_matrices_batch and
  * aclhip_measure_pose_error_metric_batch -- and for the skinning palettes -- aclhip_skin_info, aclhip_palette_layout,
- * aclhip_skinning_desc, the four skin entry points and aclhip_skinning_matrices_batch).
+ * aclhip_skinning_desc, the four skin entry points and aclhip_skinning_matrices_batch -- and for raw track arrays --
+ * aclhip_raw_tracks_info, aclhip_raw_sample_desc, the four raw track entry points and aclhip_sample_raw_tracks_batch).
  * A caller compiled against another header would hand over structs of another shape; aclhip_abi_version() says what the LIBRARY was
  * built with, and the C++ mirror (aclhip.hpp) refuses to create a context when the two differ. */
 #define ACLHIP_ABI_VERSION 6u
@@ -1532,6 +1533,103 @@ typedef struct aclhip_skinning_desc
  * priced by its bytes yet; the one storing wave's dependent loads per joint are the suspect, and no counter run has been taken. */
 aclhip_status aclhip_skinning_matrices_batch(aclhip_context* context, const void* poses, uint64_t pose_stride_bytes, uint32_t num_instances,
 	const aclhip_skinning_desc* desc, void* palettes, uint64_t palette_stride_bytes, void* stream);
+
+/* ---- raw track arrays: batched sample_tracks of uncompressed clips -----------------------------------
+ * Every other pose here starts from a compressed_tracks blob. A RAW TRACK ARRAY is the reference's second source of poses, an
+ * UNCOMPRESSED clip -- acl::track_array_qvvf (compression/track_array.h) -- and aclhip_sample_raw_tracks_batch is its sample_tracks
+ * (compression/impl/track_array.impl.h:209-343) over a batch: the raw side of calculate_compression_error, and the way mocap takes under
+ * review, replays being recorded, procedural clips and clips queued for compression join a batch whose other rows are decoded. (ABI
+ * version 6 still: two added structs and five added functions, no existing struct changed.)
+ *
+ * aclhip_register_raw_tracks: `samples` is a HOST array of [num_samples][num_tracks] QVV48 records (rotation xyzw | translation xyz, any
+ * | scale xyz, any), SAMPLE MAJOR: one key frame of the whole pose is one contiguous run. The caller may free it when the call returns.
+ * The device image keeps that layout; the fourth lanes of translations and scales are kept as given and no kernel reads them.
+ * `looping_policy` is ACLHIP_LOOP_CLAMP or ACLHIP_LOOP_WRAP (track_array::set_looping_policy takes nothing else either, :126-133);
+ * the array's duration is calculate_finite_duration(num_samples + (wrap ? 1 : 0), sample_rate) (track_array::get_finite_duration,
+ * :113-124), computed on the host. Refused with ACLHIP_ERROR_INVALID_ARGUMENT and a message, before any device call: samples or out_raw
+ * == NULL; num_tracks == 0 or > 0xFFFF; num_samples == 0; num_samples * num_tracks * 48 >= 2^31; a sample_rate that is not finite or
+ * not > 0; ACLHIP_LOOP_AS_COMPRESSED or an unknown policy. VALUES ARE NOT CHECKED: a NaN in a key frame reaches the tracks that read it,
+ * and no others. Lifetime is a skin's: the device table (ACLHIP_MAX_RAW_TRACKS records) is allocated at the first registration and never
+ * moves, so a captured hipGraph that names an array stays valid while others come and go; handle 0 is null; uploads go on the context's
+ * own stream; unregistration is stream ordered (launches already enqueued still see the array, later ones refuse it) and nobody waits. */
+typedef uint32_t aclhip_raw_tracks;			/* handle returned by aclhip_register_raw_tracks; 0 = none */
+#define ACLHIP_MAX_RAW_TRACKS 4096u			/* live arrays of one context, the null handle included */
+
+typedef struct aclhip_raw_tracks_info
+{
+	uint32_t num_tracks;
+	uint32_t num_samples;
+	float sample_rate;
+	float duration;							/* track_array::get_finite_duration() */
+	uint32_t looping_policy;				/* ACLHIP_LOOP_CLAMP or ACLHIP_LOOP_WRAP */
+	uint32_t reserved[3];
+} aclhip_raw_tracks_info;
+
+/* Host only (no context, no device): what registration checks and what aclhip_get_raw_tracks_info reports; `samples` is only tested
+ * against NULL. `message` (may be NULL, `message_capacity` bytes) receives the reason when the array is refused; `out_info` may be NULL. */
+aclhip_status aclhip_check_raw_tracks(const void* samples, uint32_t num_tracks, uint32_t num_samples, float sample_rate,
+	uint32_t looping_policy, aclhip_raw_tracks_info* out_info, char* message, uint32_t message_capacity);
+
+aclhip_status aclhip_register_raw_tracks(aclhip_context* context, const void* samples, uint32_t num_tracks, uint32_t num_samples,
+	float sample_rate, uint32_t looping_policy, aclhip_raw_tracks* out_raw);
+aclhip_status aclhip_unregister_raw_tracks(aclhip_context* context, aclhip_raw_tracks raw);
+aclhip_status aclhip_get_raw_tracks_info(const aclhip_context* context, aclhip_raw_tracks raw, aclhip_raw_tracks_info* out_info);
+
+typedef struct aclhip_raw_sample_desc
+{
+	uint8_t rounding_policy;					/*  0  aclhip_rounding_policy for every instance; ROUND_PER_TRACK needs track_rounding_policies */
+	uint8_t reserved0[7];
+	const uint8_t* instance_rounding_policies;	/*  8  DEVICE [num_instances] or NULL: overrides rounding_policy */
+	const uint8_t* track_rounding_policies;		/* 16  DEVICE [num_track_rounding_policies] or NULL: track_writer::get_rounding_policy per track,
+												       read for an instance whose policy is PER_TRACK; an entry is NONE/FLOOR/CEIL/NEAREST */
+	uint32_t num_track_rounding_policies;		/* 24 */
+	uint32_t reserved1;
+	const uint32_t* rows;						/* 32  DEVICE [num_instances] distinct rows, or NULL: row i */
+	uint64_t reserved[2];						/* 40  0 */
+} aclhip_raw_sample_desc;						/* 56 bytes */
+
+/* The definition. All arithmetic is fp32, one IEEE operation at a time, never fused. Instance i has array A = raws[i] with T tracks, S
+ * samples, rate r, looping policy L and duration D, and rounding policy p = instance_rounding_policies[i], or desc->rounding_policy (a
+ * device value above PER_TRACK is taken as NONE).
+ *   1. t = min(max(sample_times[i], 0), D); (k0, k1, alpha) = find_linear_interpolation_samples_with_sample_rate(S, r, t, per_track, L)
+ *      (core/impl/interpolation_utils.impl.h:143-201): the two key frames and the UNROUNDED alpha = t * r - k0 (k0 = k1 = 0 and alpha = 0
+ *      when a wrapped t * r lands behind the last sample). A NaN sample time is not specified (nothing is read outside the array).
+ *   2. Per track b < T: q = p, or track_rounding_policies[b] when p is PER_TRACK; a_b = apply_rounding_policy(alpha, q) (:261-278): alpha,
+ *      0, 1, or floor(alpha + 0.5).
+ *   3. With V0, V1 the records of track b at key frames k0, k1:
+ *        rotation    = quat_normalize(quat_lerp_no_normalization(V0.rotation, V1.rotation, a_b)): dot = ((x0 * x1 + y0 * y1) + z0 * z1) +
+ *                      w0 * w1 accumulated in that order, V1's components get the dot's sign bit flipped in, each component is
+ *                      (end * a_b) + (start - (start * a_b)); then n = ((x * x + y * y) + z * z) + w * w, the components times the
+ *                      correctly rounded 1.0f / sqrtf(n) -- the general form for every input, denormal n included: nothing is proven about
+ *                      a caller's rotations. The normalize runs for every policy (rtm::quat_lerp normalizes at alpha 0 and 1 too).
+ *        translation, scale = (V1.x * a_b) + (V0.x - (V0.x * a_b)) per component (rtm::vector_lerp).
+ *   4. Track b is stored at poses + row * pose_stride_bytes + 48 * b (row = rows[i], or i): rotation xyzw | translation xyz, +0 | scale
+ *      xyz, +0. The fourth lanes are written as +0 whatever the key frames held, as the decode writes them. Bytes of a row behind 48 * T
+ *      are untouched.
+ *   Against the reference itself the results are identical but for rtm::quat_normalize's x86 reciprocal square root estimate, the
+ * difference DESIGN.md 8 states for decompress_track: here the normalize is the correctly rounded one.
+ *   Refused and counted (aclhip_get_rejected_instance_count), the row untouched, decided in front of any load of a key frame: an unknown
+ * or retired handle (0 included); 48 * T > pose_stride_bytes; PER_TRACK with T > num_track_rounding_policies.
+ *   ACLHIP_ERROR_INVALID_ARGUMENT, decided before any device call, each with a message (with or without a context): raws, sample_times or
+ * poses == NULL; poses or pose_stride_bytes not 16 byte aligned; a rounding_policy above PER_TRACK; PER_TRACK without
+ * track_rounding_policies; track_rounding_policies with a count of 0; reserved fields that are not 0; the output range (num_instances
+ * rows from `poses`) overlapping raws, sample_times or any array of the desc.
+ *   desc == NULL: ROUND_NONE, row i. The launch goes on `stream`, can be captured into a graph and uploads nothing; registered clips play
+ * no part. The instance arrays are plain device arrays: a retired handle in them is refused by the kernel, not by the host.
+ *   Out of scope (nothing here precludes them): remapped output bones (track_array's remap_output); the scalar track types of
+ * track_array; sample_track, the single-track form; QVV40 / QV32 rows; the C++ mirror in aclhip.hpp.
+ *   What it costs: (one MI355X, 65 536 instances of one array of 100 tracks x 301 samples at uniformly drawn times, rows of 4 800 bytes,
+ * medians of three interleaved rounds of 20 launches; tools/raw_tracks.py, profiles/raw_tracks.md, DESIGN.md 4.7 "Raw track arrays"):
+ * 81.1 us next to 60.1 us of aclhip_decompress_tracks_batch of a compressed clip of the same shape at the same times in the same rounds
+ * -- 1.35 x its time for the same rows, 0.49 of the HBM peak (315 MB of rows plus the array's 1.4 MB) against its 0.65; the rig shape,
+ * 300 tracks: 215.4 us against 172.7 us, 0.55 against 0.68. The spread between rounds is 31 % here (the fastest round took 64.7 us)
+ * against the decode's 14 %. What the counters show per launch: the waves are parked at a wait for 65 % of their cycles (the decode's:
+ * 52 %), they issue 1.56 x the decode's vector instructions (every wave runs the rotation's square root and division for a third of its
+ * lanes), and the vector cache waits for the L2 four times as long (two loads per store): a wave waits for its two loads, computes and
+ * stores, five times in turn, with nothing of the next turn in flight. NOT BUILT: the next turn's loads issued ahead of the arithmetic. */
+aclhip_status aclhip_sample_raw_tracks_batch(aclhip_context* context, const aclhip_raw_tracks* raws /* DEVICE [num_instances] */,
+	const float* sample_times /* DEVICE [num_instances] */, uint32_t num_instances, const aclhip_raw_sample_desc* desc, void* poses,
+	uint64_t pose_stride_bytes, void* stream);
 
 /* ---- multi-GPU ---------------------------------------------------------------------------------- */
 
