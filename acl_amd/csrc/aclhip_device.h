@@ -126,10 +126,12 @@ namespace aclhip
 
 	__device__ __forceinline__ bool is_rotation_entry(const clip_range_entry& entry) { return entry.quad_index == entry.track_index * 3u; }
 
-	// Markers in the W lane of a base pose quad: the bit patterns from 0xFFC00000 up (negative quiet NaNs). A real W is never one of
-	// them: sqrt(|..|) for the drop-W rotation formats, 0 for vectors, and for quatf_full -- whose W is stored and may be NEGATIVE, which is
-	// why the sign bit alone (rounds 1-5) no longer marks anything -- any float but a NaN (registration makes a garbage constant's NaN
-	// positive; the device's own arithmetic produces 0x7FC00000).
+	// Markers in the W lane of a base pose quad: the bit patterns from 0xFFC00000 up (negative quiet NaNs). A W that was computed from
+	// numbers is never one of them: sqrt(|..|) for the drop-W rotation formats, 0 for vectors, and for quatf_full -- whose W is stored and
+	// may be NEGATIVE, which is why the sign bit alone no longer marks anything -- any float. A NaN is another matter: registration makes
+	// a garbage constant's NaN positive, but a stored animated sample that is a NaN (or holds one in x, y or z) decodes to a NaN of any
+	// sign and payload. The kernels that read markers out of an image AFTER decoding into it make such a W canonical first
+	// (canonical_w, kernels_pose.inl); every other kernel decides from the base pose table, never from a decoded quad.
 	constexpr uint32_t k_quad_special = 0xFFC00000u;			// bits >= this: not a constant sub-track (is_special_quad)
 	constexpr uint32_t k_quad_animated = 0x00200000u;			// special + this bit: low 21 bits = animated ordinal
 	constexpr uint32_t k_quad_default_w_one = 0x00000001u;		// special, not animated: default sub-track, this bit = its identity W is 1
@@ -842,6 +844,20 @@ namespace aclhip
 			__builtin_fmaf(q1.z, signed_alpha, q0.z * beta), __builtin_fmaf(q1.w, signed_alpha, q0.w * beta));
 	}
 
+	// ACLHIP_CONSUMERS_FAST: the interpolations in the reference's stable form, end * alpha + (start - start * alpha), each half fused.
+	// Numbers move by an ulp against start * (1 - alpha); what matters is a stored sample that is an INFINITY: this form reaches
+	// inf - inf and 0 * inf exactly where the bit exact kernels' does, so both make NaNs of the same words
+	// (tests/test_gpu_nonfinite_samples.py::test_consumers_fast).
+	__device__ __forceinline__ float lerp_stable_fast(float start, float end, float alpha) { return __builtin_fmaf(end, alpha, __builtin_fmaf(-start, alpha, start)); }
+
+	__device__ __forceinline__ float4 quat_lerp_no_normalization_stable_fast(float4 q0, float4 q1, float alpha)
+	{
+		const float dot = __builtin_fmaf(q0.w, q1.w, __builtin_fmaf(q0.z, q1.z, __builtin_fmaf(q0.y, q1.y, q0.x * q1.x)));
+		const float signed_alpha = __uint_as_float(__float_as_uint(alpha) ^ (__float_as_uint(dot) & 0x80000000u));
+		return make_float4(__builtin_fmaf(q1.x, signed_alpha, __builtin_fmaf(-q0.x, alpha, q0.x)), __builtin_fmaf(q1.y, signed_alpha, __builtin_fmaf(-q0.y, alpha, q0.y)),
+			__builtin_fmaf(q1.z, signed_alpha, __builtin_fmaf(-q0.z, alpha, q0.z)), __builtin_fmaf(q1.w, signed_alpha, __builtin_fmaf(-q0.w, alpha, q0.w)));
+	}
+
 	// rtm::quat_mul's formula (lhs first, then rhs), one multiply and three fused multiply-adds per lane
 	__device__ __forceinline__ float4 quat_mul_fast(float4 l, float4 r)
 	{
@@ -965,7 +981,7 @@ namespace aclhip
 			{
 				const float4 q0 = make_float4(v0[0], v0[1], v0[2], quat_from_positive_w_fast(v0[0], v0[1], v0[2]));
 				const float4 q1 = make_float4(v1[0], v1[1], v1[2], quat_from_positive_w_fast(v1[0], v1[1], v1[2]));
-				float4 result = quat_lerp_no_normalization_fast(q0, q1, lerp_alpha);
+				float4 result = kFastMath == 1 ? quat_lerp_no_normalization_stable_fast(q0, q1, lerp_alpha) : quat_lerp_no_normalization_fast(q0, q1, lerp_alpha);
 				if (normalization >= 1)
 					result = quat_normalize_fast(result);
 				return result;
@@ -973,8 +989,7 @@ namespace aclhip
 			// ACLHIP_DECODE_FAST keeps translations and scales exact: their error would scale with the rig's size, a rotation's does not
 			if constexpr (kFastMath == 1)
 			{
-				const float beta = 1.0f - lerp_alpha;
-				return make_float4(__builtin_fmaf(v1[0], lerp_alpha, v0[0] * beta), __builtin_fmaf(v1[1], lerp_alpha, v0[1] * beta), __builtin_fmaf(v1[2], lerp_alpha, v0[2] * beta), 0.0f);
+				return make_float4(lerp_stable_fast(v0[0], v1[0], lerp_alpha), lerp_stable_fast(v0[1], v1[1], lerp_alpha), lerp_stable_fast(v0[2], v1[2], lerp_alpha), 0.0f);
 			}
 			return make_float4(lerp_stable(v0[0], v1[0], lerp_alpha), lerp_stable(v0[1], v1[1], lerp_alpha), lerp_stable(v0[2], v1[2], lerp_alpha), 0.0f);
 		}

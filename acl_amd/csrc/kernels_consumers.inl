@@ -546,6 +546,20 @@
 		return consumer_wave{ image, base_image, shared_schedule, slot, role, lane, wave_in_block, instance, 0, 0 };
 	}
 
+	__device__ __forceinline__ bool quad_is_finite(f32x4 value)
+	{
+		constexpr uint32_t k_exponents = 0x7F800000u;
+		return (__float_as_uint(value.x) & k_exponents) != k_exponents && (__float_as_uint(value.y) & k_exponents) != k_exponents
+			&& (__float_as_uint(value.z) & k_exponents) != k_exponents && (__float_as_uint(value.w) & k_exponents) != k_exponents;
+	}
+
+	__device__ __forceinline__ bool qvv_is_finite(const qvv& value)
+	{
+		return quad_is_finite(f32x4{ value.rotation.x, value.rotation.y, value.rotation.z, value.rotation.w })
+			&& quad_is_finite(f32x4{ value.translation.x, value.translation.y, value.translation.z, 0.0f })
+			&& quad_is_finite(f32x4{ value.scale.x, value.scale.y, value.scale.z, 0.0f });
+	}
+
 	// The pose consumer kernels behind their decodes, from "both images of every instance are complete" on: the combine with the base
 	// pose, the object space walk, the store. The three kernels differ in how an image is filled; this is shared. kUnitScale and kFast:
 	// decompress_poses_consumer_kernel only.
@@ -571,6 +585,7 @@
 		else
 			wave_lds_barrier();
 
+		[[maybe_unused]] bool not_finite = false;		// kFast: a value of this wave's part of the local pose is an infinity or a NaN
 		if (has_base && !fused_base)
 		{
 			const f32x4* base_source = base_is_clip ? wave.base_image : reinterpret_cast<const f32x4*>(args.base_poses + uint64_t(wave.instance) * args.base_pose_stride_bytes);
@@ -578,7 +593,10 @@
 			{
 				const qvv additive = load_qvv(image, transform_index);
 				const qvv base = load_qvv(base_source, transform_index);
-				store_qvv(image, transform_index, apply_additive_to_base<kMirrored>(args.additive_format, base, additive));
+				const qvv combined = apply_additive_to_base<kMirrored>(args.additive_format, base, additive);
+				store_qvv(image, transform_index, combined);
+				if constexpr (kFast && kObjectSpace)
+					not_finite = not_finite || !qvv_is_finite(combined);
 				// additive_clip_format8::relative is a qvv_mul (core/additive_utils.h:128-160)
 				if constexpr (kMirrored)
 				{
@@ -603,7 +621,26 @@
 					walk.tracks[slot] = wave.empty_pose ? k_consumer_empty_pose : num_tracks;
 				else
 					walk.tracks[slot] = num_tracks;
-				walk.short_exact[slot] = num_tracks != 0 ? wave.short_exact : 1u;
+				if constexpr (!kFast)
+					walk.short_exact[slot] = num_tracks != 0 ? wave.short_exact : 1u;
+			}
+			if constexpr (kFast)
+			{
+				// ACLHIP_CONSUMERS_FAST: the walk keeps the fast forms for local poses of numbers only (see the walk below). Every decoding
+				// wave looks through what it finished -- the image, or the transforms it has just combined with their base -- and leaves
+				// its finding where the exact kernels keep short_exact, which the fast walk does not read: 0 = finite. Two waves of one
+				// instance write a half of the word each.
+				if (!has_base || fused_base)
+					for (uint32_t quad = lane; quad < num_tracks * (kUnitScale ? 2u : 3u); quad += k_wave_size)
+						not_finite = not_finite || !quad_is_finite(image[quad]);
+				const bool wave_not_finite = __any(int(not_finite)) != 0;
+				if (lane == 0)
+				{
+					if (two_waves)
+						reinterpret_cast<uint16_t*>(&walk.short_exact[slot])[role] = wave_not_finite ? 1u : 0u;
+					else
+						walk.short_exact[slot] = wave_not_finite ? 1u : 0u;
+				}
 			}
 			__syncthreads();
 			ACLHIP_PHASE_STAMP(1);
@@ -638,18 +675,30 @@
 					const uint64_t first_schedule = (uint64_t(__shfl(uint32_t(mine >> 32), int(leader))) << 32) | __shfl(uint32_t(mine), int(leader));
 					const bool shared_copy = __all(int(slot_steps == 0 || (mine == first_schedule && slot_schedule_is_shared))) != 0;
 					const bool short_exact_walk = !kFast && __all(int(walk.short_exact[walk_slot] != 0)) != 0;
-					const auto walk_with = [&](auto short_exact_tag)
+					const auto walk_with = [&](auto short_exact_tag, auto fast_tag)
 					{
 						constexpr bool k_short_exact = decltype(short_exact_tag)::value;
+						constexpr bool k_fast = decltype(fast_tag)::value;
 						if (shared_copy)
-							walk_hierarchy<kUnitScale, kMirrored, kFast, k_short_exact>(static_cast<const uint32_t*>(wave.shared_schedule), slot_steps, first, slot_image, lane, negative_scale_count);
+							walk_hierarchy<kUnitScale, kMirrored, k_fast, k_short_exact>(static_cast<const uint32_t*>(wave.shared_schedule), slot_steps, first, slot_image, lane, negative_scale_count);
 						else
-							walk_hierarchy<kUnitScale, kMirrored, kFast, k_short_exact>(as_constant(slot_schedule), slot_steps, first, slot_image, lane, negative_scale_count);
+							walk_hierarchy<kUnitScale, kMirrored, k_fast, k_short_exact>(as_constant(slot_schedule), slot_steps, first, slot_image, lane, negative_scale_count);
 					};
-					if (short_exact_walk)
-						walk_with(std::true_type());
+					if constexpr (kFast)
+					{
+						// ACLHIP_CONSUMERS_FAST: quat_mul_vector3 as two cross products and the fused products reach inf - inf and 0 * inf in other
+						// places than the quaternion products do. A workgroup whose local poses hold an infinity or a NaN (a clip that stores
+						// one) walks with the bit exact forms: the same words come out as NaNs as without the flag.
+						const bool finite = slot_steps == 0 || walk.short_exact[walk_slot] == 0;		// (what the decoding waves found, above)
+						if (__all(int(finite)) != 0)
+							walk_with(std::false_type(), std::true_type());
+						else
+							walk_with(std::false_type(), std::false_type());
+					}
+					else if (short_exact_walk)
+						walk_with(std::true_type(), std::false_type());
 					else
-						walk_with(std::false_type());
+						walk_with(std::false_type(), std::false_type());
 				}
 				__builtin_amdgcn_s_setprio(0);
 			}

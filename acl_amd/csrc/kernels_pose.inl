@@ -126,8 +126,8 @@
 		return params.instance_track_counts != nullptr ? min(clip_tracks, as_constant(params.instance_track_counts)[caller_instance]) : clip_tracks;
 	}
 
-	// What the any-settings pose kernel stores for a quad of the LDS image: default sub-tracks -- still tagged in their W lane, every
-	// other quad holds a real W >= +0 by now -- follow the default sub-track modes, the rest passes through.
+	// What the any-settings pose kernel stores for a quad of the LDS image: default sub-tracks -- still tagged in their W lane; no other
+	// quad holds a marker by now (canonical_w below) -- follow the default sub-track modes, the rest passes through.
 	__device__ __forceinline__ float4 resolve_quad(const decode_params& params, float4 value, uint32_t quad, bool& out_store, const float* clip_bind_pose)
 	{
 		out_store = true;
@@ -139,6 +139,15 @@
 		const uint32_t kind = quad - track_index * 3u;
 		value.w = (marker & k_quad_default_w_one) != 0 ? 1.0f : 0.0f;
 		return default_quad(params, kind, track_index, value, out_store, clip_bind_pose);
+	}
+
+	// A W lane that goes into an image whose readers look for markers (is_special_quad: the bit patterns from 0xFFC00000 up) must not
+	// be one by accident. A decoded W is a square root, +0 or a stored float -- but a NaN where a stored sample was one (quatf_full
+	// stores W itself; a NaN in x, y or z travels through the lerp and the normalize into every lane), and the sign and payload of that
+	// NaN are whatever the arithmetic made of the input's. Such a NaN becomes the canonical positive one: still a NaN, never a marker.
+	__device__ __forceinline__ float canonical_w(float w)
+	{
+		return is_special_quad(__float_as_uint(w)) ? __uint_as_float(0x7FC00000u) : w;
 	}
 
 	// Where the tables of a pose window's animated sub-tracks are
@@ -227,7 +236,9 @@
 		out.sample_time = sample_time;
 	}
 
-	template<bool kPolicies, bool kWideKeyLoads = false, uint32_t kFastMath = 0, class image_writer_type>
+	// kMarkersAreRead: the image's readers take markers out of its W lanes AFTER the decode (the any-settings pose kernel): a decoded W
+	// goes through canonical_w. The other kernels never look at a decoded W and keep their code.
+	template<bool kPolicies, bool kWideKeyLoads = false, uint32_t kFastMath = 0, bool kMarkersAreRead = false, class image_writer_type>
 	__device__ __forceinline__ void decode_window_sub_tracks_into(const window_tables& tables, const seek_state& state, const decode_params& params,
 		uint32_t rounding_policy, uint32_t normalization, uint32_t first_ordinal, uint32_t end_ordinal, uint32_t lane, image_writer_type write_to_image,
 		const uint8_t* track_rounding_policies = nullptr, bool clip_range_first = false)
@@ -281,7 +292,10 @@
 			else
 				value = decode_animated_sub_track<true, kPolicies, kWideKeyLoads, (kFastMath == 2 ? 0u : kFastMath)>(state, plan0, plan1, current_range, is_rotation, policy, state.interpolation_alpha, normalization, normalize_samples, tables.short_exact_math);		// (ACLHIP_DECODE_FAST: a wave that meets a raw sample keeps the exact forms)
 
-			// a decoded W is never negative (a square root, or +0): the marker the base pose carried in this quad is gone
+			// the marker the base pose carried in this quad is gone: a decoded W is a square root, +0 or a stored float, and where a stored
+			// sample made a NaN of it, canonical_w keeps it from being read as a marker
+			if (kMarkersAreRead)
+				value.w = canonical_w(value.w);
 			if (valid)
 				write_to_image(current_range, value);
 
@@ -303,9 +317,9 @@
 	{
 		const qvv48_image_writer writer = { image, first_quad, window_quads };
 		if (kAnySettings && params.per_track_rounding != 0)
-			decode_window_sub_tracks_into<true, kWideKeyLoads>(tables, state, params, rounding_policy, normalization, first_ordinal, end_ordinal, lane, writer, track_rounding_policies, clip_range_first);
+			decode_window_sub_tracks_into<true, kWideKeyLoads, 0, kAnySettings>(tables, state, params, rounding_policy, normalization, first_ordinal, end_ordinal, lane, writer, track_rounding_policies, clip_range_first);
 		else
-			decode_window_sub_tracks_into<false, kWideKeyLoads, kFastMath>(tables, state, params, rounding_policy, normalization, first_ordinal, end_ordinal, lane, writer, nullptr, clip_range_first);
+			decode_window_sub_tracks_into<false, kWideKeyLoads, kFastMath, kAnySettings>(tables, state, params, rounding_policy, normalization, first_ordinal, end_ordinal, lane, writer, nullptr, clip_range_first);
 	}
 
 	// The pose kernels. One wave64 per (instance, pose window): a window is k_image_chunk_quads consecutive quads of the pose (a
@@ -565,8 +579,9 @@
 				const f32x4 value = image[quad];
 				if ((first_quad + quad) % 3u == 0 && !is_special_quad(__float_as_uint(value.w)))
 				{
+					// (a constant with a NaN in it normalizes to NaNs: a constant still, not a default -- canonical_w)
 					const float4 normalized = quat_normalize(make_float4(value.x, value.y, value.z, value.w));
-					image[quad] = f32x4{ normalized.x, normalized.y, normalized.z, normalized.w };
+					image[quad] = f32x4{ normalized.x, normalized.y, normalized.z, canonical_w(normalized.w) };
 				}
 			}
 		}
@@ -742,8 +757,8 @@
 			f32x4 value = staged[r];
 			if (kAnySettings && resolve_defaults)
 			{
-				// default sub-tracks still carry their tag in the W lane (every other quad holds a real W >= +0 by now) and follow the
-				// default sub-track modes (unpack_default_*_sub_tracks, decompression.transform.h:575-675,883-985,1203-1310,1653-1680)
+				// default sub-tracks still carry their tag in the W lane (no other quad holds a marker by now: constants were scrubbed at
+				// registration, decoded and normalized ones went through canonical_w) and follow the default sub-track modes (unpack_default_*_sub_tracks, decompression.transform.h:575-675,883-985,1203-1310,1653-1680)
 				const uint32_t marker = __float_as_uint(value.w);
 				const bool is_default = is_special_quad(marker);
 				const uint32_t mode = kind == 0 ? params.default_modes[0] : (kind == 1 ? params.default_modes[1] : params.default_modes[2]);

@@ -870,6 +870,15 @@ class Context:
         self._check(self._lib.aclhip_decompress_tracks_batch_mapped(self._handle, clips.data_ptr(), sample_times.data_ptr(), int(clips.numel()), ctypes.byref(params),
                                                                    ctypes.byref(output) if output is not None else None, ctypes.byref(mapping), poses.data_ptr(), int(pose_stride_bytes), stream))
 
+    def decompress_tracks_batch_mapped_at(self, clips_ptr, times_ptr, num_instances, poses_ptr, pose_stride_bytes, track_map=0, instance_maps_ptr=None,
+                                          fill_pose_ptr=None, output=None, params=None, stream=None):
+        """aclhip_decompress_tracks_batch_mapped on device ADDRESSES (ints), like decompress_tracks_batch"""
+        params = params if params is not None else default_params()
+        mapping = TrackMapping()
+        mapping.map, mapping.instance_maps, mapping.fill_pose, mapping.fill_unmapped = int(track_map), instance_maps_ptr, fill_pose_ptr, 1 if fill_pose_ptr else 0
+        self._check(self._lib.aclhip_decompress_tracks_batch_mapped(self._handle, clips_ptr, times_ptr, int(num_instances), ctypes.byref(params),
+                                                                   ctypes.byref(output) if output is not None else None, ctypes.byref(mapping), poses_ptr, int(pose_stride_bytes), stream))
+
     # ---- skeletons: the pose consumers in skeleton space ----
     def register_skeleton(self, parent_indices, reference_pose, num_bones=None):
         """parent_indices: host array in slot order or None (local space only); reference_pose: float32 [num_bones, 12]. Returns the handle (>= 1)."""

@@ -760,7 +760,9 @@ typedef struct aclhip_pose_consumers
  * hardware's 1 ulp square root / reciprocal square root, fused multiply-adds and quat_mul_vector3 as two cross products -- in the
  * decode of the instance and of its base, the fused additive apply and the walk. Rotations stay within 2e-6 of the default's per
  * component, translations within 2e-6 of the pose's extent (tests/test_gpu_consumers.py; DESIGN.md 4.7 has the measured figures).
- * Ignored (the default arithmetic runs) for local space output and for blends; mirrored transforms keep rtm's matrix route. */
+ * Ignored (the default arithmetic runs) for local space output and for blends; mirrored transforms keep rtm's matrix route. A
+ * workgroup whose local poses hold an infinity or a NaN (a clip that stores one) walks with the default arithmetic: the flag moves
+ * numbers, never which words are NaNs (tests/test_gpu_nonfinite_samples.py). */
 #define ACLHIP_CONSUMERS_FAST 1u
 
 /* aclhip_decompress_tracks_batch followed by the consumers, in one kernel. `params` as for aclhip_decompress_tracks_batch but
