@@ -14,6 +14,9 @@
 //                                      clip instances, apply an additive clip onto its base, local -> object space -- before the pose leaves LDS.
 //   transform_poses_kernel             the same consumers over a caller's pose buffers: the LDS image is filled from a row in HBM, not from a clip.
 //   sample_raw_tracks_kernel           uncompressed clips (raw track arrays): one lane per quad of the pose row, two 16 byte loads, one store.
+//   sample_raw_scalar_tracks_kernel    uncompressed scalar curve sets (raw scalar track arrays): one lane per float of the value row (four floats where row and key frames are 16 byte aligned), two loads, one store.
+//   sample_raw_scalar_track_kernel     the same arrays, one thread per (instance, track) request.
+//   measure_scalar_error_kernel        the scalar track error of two value buffers: one wave64 per instance, lanes <-> tracks.
 //   decompress_track_kernel            one thread per (instance, bone) request; the registration time plan replaces the
 //                                      reference's O(track index) skip over preceding widths.
 //   decompress_scalar_tracks_kernel    scalar track lists: one wave64 per (instance, 256 tracks), lanes <-> tracks.
@@ -57,6 +60,7 @@ namespace aclhip
 #include "kernels_skeleton.inl"
 #include "kernels_pose_buffers.inl"
 #include "kernels_raw_tracks.inl"
+#include "kernels_raw_scalar_tracks.inl"
 #include "kernels_misc.inl"
 #include "kernels_scalar.inl"
 #include "kernels_track.inl"
@@ -83,5 +87,6 @@ using namespace aclhip;
 #include "host_pose_buffers.inl"
 #include "host_skins.inl"
 #include "host_raw_tracks.inl"
+#include "host_raw_scalar_tracks.inl"
 #include "host_bone_object.inl"
 #include "host_scalar_misc.inl"

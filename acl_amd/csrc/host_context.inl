@@ -61,8 +61,8 @@ namespace
 
 namespace
 {
-	// The handles of one kind of object that launches name by number: track maps, skeletons, blend masks, skins and raw track arrays
-	// (host_track_maps.inl, host_skeletons.inl, host_blend_masks.inl, host_skins.inl, host_raw_tracks.inl; used five times in aclhip_context). The device table is ONE allocation of kCapacity records
+	// The handles of one kind of object that launches name by number: track maps, skeletons, blend masks, skins, raw track arrays and raw scalar track arrays
+	// (host_track_maps.inl, host_skeletons.inl, host_blend_masks.inl, host_skins.inl, host_raw_tracks.inl, host_raw_scalar_tracks.inl; used six times in aclhip_context). The device table is ONE allocation of kCapacity records
 	// made at the first registration: it never moves and never grows (launches in flight and captured hipGraphs hold its address), a
 	// cleared record is an unknown handle, and record 0 is never handed out (0 is the null handle). What works on a table -- take_handle,
 	// publish_handle, unregister_handle, get_handle_info -- is below, behind the upload and retire functions it calls.
@@ -101,15 +101,18 @@ struct aclhip_context
 	std::vector<host_clip> clips;
 	std::vector<uint32_t> free_slots;
 	std::vector<host_database> databases;
-	// The five handle tables (handle_table, above): track maps (aclhip_register_track_map), skeletons (aclhip_register_skeleton: what the
+	// The six handle tables (handle_table, above): track maps (aclhip_register_track_map), skeletons (aclhip_register_skeleton: what the
 	// slot space of a set of track maps means), blend masks (aclhip_register_blend_mask: a weight per slot for the skeleton space blends),
-	// skins (aclhip_register_skin: a mesh's joint list and inverse bind matrices for the skinning palettes) and raw track arrays
-	// (aclhip_register_raw_tracks: an uncompressed clip's key frames for aclhip_sample_raw_tracks_batch)
+	// skins (aclhip_register_skin: a mesh's joint list and inverse bind matrices for the skinning palettes), raw track arrays
+	// (aclhip_register_raw_tracks: an uncompressed clip's key frames for aclhip_sample_raw_tracks_batch) and raw scalar track arrays
+	// (aclhip_register_raw_scalar_tracks: an uncompressed curve set's key frames; a table of its own, so that neither kind of handle names
+	// an array of the other kind)
 	handle_table<device_track_map, aclhip_track_map_info, ACLHIP_MAX_TRACK_MAPS> track_maps{ "track map", "maps" };
 	handle_table<device_skeleton, aclhip_skeleton_info, ACLHIP_MAX_SKELETONS, skeleton_entry_extras> skeletons{ "skeleton", "skeletons" };
 	handle_table<device_blend_mask, aclhip_blend_mask_info, ACLHIP_MAX_BLEND_MASKS> blend_masks{ "blend mask", "masks" };
 	handle_table<device_skin, aclhip_skin_info, ACLHIP_MAX_SKINS> skins{ "skin", "skins" };
 	handle_table<device_raw_tracks, aclhip_raw_tracks_info, ACLHIP_MAX_RAW_TRACKS> raw_tracks{ "raw track array", "arrays" };
+	handle_table<device_raw_scalar_tracks, aclhip_raw_scalar_tracks_info, ACLHIP_MAX_RAW_SCALAR_TRACKS> raw_scalar_tracks{ "raw scalar track array", "arrays" };
 	uint32_t num_negative_scale_skeletons = 0;		// live skeletons whose reference pose holds a negative scale (see num_negative_scale_clips)
 	uint32_t max_skeleton_hierarchy_words = 0;		// largest walk schedule a skeleton was ever registered with (a longer one is walked from global memory)
 	device_clip* d_clips = nullptr;
@@ -1133,6 +1136,7 @@ extern "C" void aclhip_destroy(aclhip_context* context)
 		context->blend_masks.free_device_table();
 		context->skins.free_device_table();
 		context->raw_tracks.free_device_table();
+		context->raw_scalar_tracks.free_device_table();
 		for (const aclhip_context::order_scratch& scratch : context->order_scratches)
 		{
 			(void)hipFree(scratch.bins);

@@ -56,6 +56,8 @@ EXPORTED_SYMBOLS = [
     "aclhip_check_skin", "aclhip_register_skin", "aclhip_unregister_skin", "aclhip_get_skin_info", "aclhip_skinning_matrices_batch",
     "aclhip_check_raw_tracks", "aclhip_register_raw_tracks", "aclhip_unregister_raw_tracks", "aclhip_get_raw_tracks_info",
     "aclhip_sample_raw_tracks_batch",
+    "aclhip_check_raw_scalar_tracks", "aclhip_register_raw_scalar_tracks", "aclhip_unregister_raw_scalar_tracks", "aclhip_get_raw_scalar_tracks_info",
+    "aclhip_sample_raw_scalar_tracks_batch", "aclhip_sample_raw_scalar_track_batch", "aclhip_measure_scalar_error_batch",
 ]
 
 
@@ -232,6 +234,30 @@ class RawSampleDesc(ctypes.Structure):
 
 
 MAX_RAW_TRACKS = 4096       # ACLHIP_MAX_RAW_TRACKS
+
+
+class RawScalarTracksInfo(ctypes.Structure):
+    """aclhip_raw_scalar_tracks_info"""
+    _fields_ = [
+        ("num_tracks", ctypes.c_uint32), ("num_samples", ctypes.c_uint32), ("sample_rate", ctypes.c_float), ("duration", ctypes.c_float),
+        ("looping_policy", ctypes.c_uint32), ("track_type", ctypes.c_uint32), ("num_components", ctypes.c_uint32), ("reserved", ctypes.c_uint32),
+    ]
+
+
+class ScalarErrorDesc(ctypes.Structure):
+    """aclhip_scalar_error_desc; every pointer is a device address or None"""
+    _fields_ = [
+        ("num_tracks", ctypes.c_uint32), ("num_components", ctypes.c_uint32), ("track_errors", ctypes.c_void_p), ("track_error_stride_bytes", ctypes.c_uint64),
+        ("worst", ctypes.c_void_p), ("reserved", ctypes.c_uint64 * 2),
+    ]
+
+
+MAX_RAW_SCALAR_TRACKS = 4096        # ACLHIP_MAX_RAW_SCALAR_TRACKS
+NO_TRACK = 0xFFFFFFFF               # ACLHIP_NO_TRACK
+TRACK_FLOAT1F, TRACK_FLOAT2F, TRACK_FLOAT3F, TRACK_FLOAT4F, TRACK_VECTOR4F, TRACK_QVVF = 0, 1, 2, 3, 4, 12     # acl::track_type8
+SCALAR_TRACK_COMPONENTS = {TRACK_FLOAT1F: 1, TRACK_FLOAT2F: 2, TRACK_FLOAT3F: 3, TRACK_FLOAT4F: 4, TRACK_VECTOR4F: 4}
+TRACK_ERROR_DTYPE = np.dtype([("error", np.float32), ("track", np.uint32)])                 # aclhip_track_error as a numpy record
+TRACK_ERROR_WORST_DTYPE = np.dtype([("error", np.float32), ("track", np.uint32), ("instance", np.uint32), ("reserved", np.uint32)])
 
 
 class PoseBufferBlend(ctypes.Structure):
@@ -450,6 +476,13 @@ def load_library():
     lib.aclhip_unregister_raw_tracks.argtypes = [vp, u32]
     lib.aclhip_get_raw_tracks_info.argtypes = [vp, u32, ctypes.POINTER(RawTracksInfo)]
     lib.aclhip_sample_raw_tracks_batch.argtypes = [vp, vp, vp, u32, ctypes.POINTER(RawSampleDesc), vp, u64, vp]
+    lib.aclhip_check_raw_scalar_tracks.argtypes = [vp, u32, u32, u32, ctypes.c_float, u32, ctypes.POINTER(RawScalarTracksInfo), ctypes.c_char_p, u32]
+    lib.aclhip_register_raw_scalar_tracks.argtypes = [vp, vp, u32, u32, u32, ctypes.c_float, u32, ctypes.POINTER(u32)]
+    lib.aclhip_unregister_raw_scalar_tracks.argtypes = [vp, u32]
+    lib.aclhip_get_raw_scalar_tracks_info.argtypes = [vp, u32, ctypes.POINTER(RawScalarTracksInfo)]
+    lib.aclhip_sample_raw_scalar_tracks_batch.argtypes = [vp, vp, vp, u32, ctypes.POINTER(RawSampleDesc), vp, u64, vp]
+    lib.aclhip_sample_raw_scalar_track_batch.argtypes = [vp, vp, vp, vp, u32, ctypes.POINTER(RawSampleDesc), vp, u64, vp]
+    lib.aclhip_measure_scalar_error_batch.argtypes = [vp, vp, u64, vp, u64, u32, ctypes.POINTER(ScalarErrorDesc), vp, vp]
     _lib = lib
     return lib
 
@@ -522,6 +555,27 @@ def check_raw_tracks(samples, sample_rate, looping_policy=LOOP_CLAMP):
     array = _raw_samples(samples)
     message, info = ctypes.create_string_buffer(256), RawTracksInfo()
     status = load_library().aclhip_check_raw_tracks(array.ctypes.data, array.shape[1], array.shape[0], float(sample_rate), int(looping_policy), ctypes.byref(info), message, 256)
+    return status, message.value.decode(), info
+
+
+def _raw_scalar_samples(samples, track_type):
+    """[num_samples, num_tracks, C] float32, contiguous ([num_samples, num_tracks] is taken as C = 1): the sample major layout the library takes"""
+    array = np.ascontiguousarray(samples, dtype=np.float32)
+    if array.ndim == 2:
+        array = array[:, :, None]
+    components = SCALAR_TRACK_COMPONENTS.get(int(track_type))
+    if array.ndim != 3 or (components is not None and array.shape[2] != components):
+        raise ValueError(f"raw scalar samples of track type {track_type} are [num_samples, num_tracks, {components}] floats, not {array.shape}")
+    return array
+
+
+def check_raw_scalar_tracks(samples, track_type, sample_rate, looping_policy=LOOP_CLAMP):
+    """Host only validation of a raw scalar track array (no GPU needed): what aclhip_register_raw_scalar_tracks checks. samples: float32
+    [num_samples, num_tracks, C] or [num_samples, num_tracks]. Returns (status, message, RawScalarTracksInfo)."""
+    array = _raw_scalar_samples(samples, track_type)
+    message, info = ctypes.create_string_buffer(256), RawScalarTracksInfo()
+    status = load_library().aclhip_check_raw_scalar_tracks(array.ctypes.data, int(track_type), array.shape[1], array.shape[0], float(sample_rate), int(looping_policy),
+                                                           ctypes.byref(info), message, 256)
     return status, message.value.decode(), info
 
 
@@ -1035,6 +1089,43 @@ class Context:
         self._check(self._lib.aclhip_sample_raw_tracks_batch(self._handle, raws_ptr, times_ptr, num_instances, ctypes.byref(desc) if desc is not None else None,
                                                              poses_ptr, pose_stride_bytes, stream))
 
+    # ---- raw scalar track arrays: uncompressed curve sets (acl::track_array of float1f .. vector4f), sample_tracks / sample_track ----
+    def register_raw_scalar_tracks(self, samples, track_type, sample_rate, looping_policy=LOOP_CLAMP):
+        """samples: host float32 [num_samples, num_tracks, C] (or [num_samples, num_tracks] for float1f), sample major (what the tests hand to
+        ref_scalar_compress); the array is copied. track_type: TRACK_FLOAT1F .. TRACK_VECTOR4F. Returns the raw scalar tracks handle (>= 1)."""
+        array = _raw_scalar_samples(samples, track_type)
+        handle = ctypes.c_uint32(0)
+        self._check(self._lib.aclhip_register_raw_scalar_tracks(self._handle, array.ctypes.data, int(track_type), array.shape[1], array.shape[0], float(sample_rate),
+                                                                int(looping_policy), ctypes.byref(handle)))
+        return handle.value
+
+    def unregister_raw_scalar_tracks(self, raw):
+        self._check(self._lib.aclhip_unregister_raw_scalar_tracks(self._handle, raw))
+
+    def raw_scalar_tracks_info(self, raw):
+        info = RawScalarTracksInfo()
+        self._check(self._lib.aclhip_get_raw_scalar_tracks_info(self._handle, raw, ctypes.byref(info)))
+        return info
+
+    def sample_raw_scalar_tracks_batch(self, raws_ptr, times_ptr, num_instances, values_ptr, stride_bytes, desc=None, stream=None):
+        """aclhip_sample_raw_scalar_tracks_batch: track_array::sample_tracks of the raw scalar track arrays named at raws_ptr (device uint32
+        [num_instances]) at the times at times_ptr into rows of T * C floats at values_ptr (device addresses). `desc` is a RawSampleDesc or
+        None (ROUND_NONE, row i)."""
+        self._check(self._lib.aclhip_sample_raw_scalar_tracks_batch(self._handle, raws_ptr, times_ptr, num_instances, ctypes.byref(desc) if desc is not None else None,
+                                                                    values_ptr, stride_bytes, stream))
+
+    def sample_raw_scalar_track_batch(self, raws_ptr, times_ptr, tracks_ptr, num_instances, values_ptr, stride_bytes, desc=None, stream=None):
+        """aclhip_sample_raw_scalar_track_batch: track_array::sample_track, C floats per request of the track at tracks_ptr (device uint32
+        [num_instances])."""
+        self._check(self._lib.aclhip_sample_raw_scalar_track_batch(self._handle, raws_ptr, times_ptr, tracks_ptr, num_instances,
+                                                                   ctypes.byref(desc) if desc is not None else None, values_ptr, stride_bytes, stream))
+
+    def measure_scalar_error(self, raw_values_ptr, raw_stride_bytes, lossy_values_ptr, lossy_stride_bytes, num_instances, desc, errors_ptr, stream=None):
+        """aclhip_measure_scalar_error_batch: calculate_scalar_track_error between the rows of T * C floats at the two device addresses, into
+        the 8 byte records at errors_ptr; `desc` is a ScalarErrorDesc (per track errors and the launch's worst record on request)."""
+        self._check(self._lib.aclhip_measure_scalar_error_batch(self._handle, raw_values_ptr, raw_stride_bytes, lossy_values_ptr, lossy_stride_bytes, num_instances,
+                                                                ctypes.byref(desc) if desc is not None else None, errors_ptr, stream))
+
     def decompress_poses_mapped(self, clips, sample_times, skeletons, maps, num_bones, additive_format=ADDITIVE_NONE, object_space=False, base_clips=None,
                                 base_sample_times=None, base_maps=None, base_poses=None, params=None, out=None, instance_rounding=None, instance_looping=None,
                                 blend_clips=None, blend_sample_times=None, blend_maps=None, blend_weights=None, flags=0):
@@ -1486,3 +1577,76 @@ def raw_clip_error(ctx, raw, clip, skeleton, shells, object_space=True, params=N
     if int(worst["instance"]) == 0xFFFFFFFF:
         return NO_BONE, -1.0, float("nan")
     return int(worst["bone"]), float(worst["error"]), float(sample_times[int(worst["instance"])])
+
+
+def _worst_scalar_error(ctx, device, stream, d_raw, d_lossy, stride, num_samples, num_tracks, num_components, sample_times):
+    """aclhip_measure_scalar_error_batch with the worst record over two filled value buffers: (track, error, sample_time)"""
+    import torch
+    d_errors = torch.zeros((num_samples, 2), dtype=torch.int32, device=device)
+    d_worst = torch.zeros(4, dtype=torch.int32, device=device)
+    desc = ScalarErrorDesc()
+    desc.num_tracks, desc.num_components, desc.worst = num_tracks, num_components, d_worst.data_ptr()
+    ctx.measure_scalar_error(d_raw.data_ptr(), stride, d_lossy.data_ptr(), stride, num_samples, desc, d_errors.data_ptr(), stream=stream.cuda_stream)
+    stream.synchronize()
+    worst = d_worst.cpu().numpy().view(TRACK_ERROR_WORST_DTYPE)[0]
+    if int(worst["instance"]) == 0xFFFFFFFF:
+        return NO_TRACK, -1.0, float("nan")
+    return int(worst["track"]), float(worst["error"]), float(sample_times[int(worst["instance"])])
+
+
+def raw_scalar_clip_error(ctx, raw, clip, rounding=None):
+    """acl::calculate_compression_error(allocator, raw_tracks, context) (impl/track_error.impl.h:399-462) for scalar tracks as launches:
+    what a precision setting costs a scalar clip. `raw` is a raw scalar track array (register_raw_scalar_tracks) and `clip` its registered
+    compressed form. Instances are the raw array's samples at min(i / rate, duration) with the array's rate and duration: the array is
+    sampled (aclhip_sample_raw_scalar_tracks_batch) and the clip decoded (aclhip_decompress_scalar_tracks_batch) with `rounding` -- by
+    default the reference's choice: ROUND_NONE when the clip has a database or stripped key frames, ROUND_NEAREST otherwise --, then the
+    two buffers are measured (aclhip_measure_scalar_error_batch) with the launch's worst record. Returns (track, error, sample_time): the
+    lowest sample and track among equals; (NO_TRACK, -1.0, nan) when nothing could be measured. A clip whose track type or track count
+    differs from the array's raises ValueError. Synchronous; the buffers are torch tensors on the context's device."""
+    import torch
+    device = torch.device("cuda", ctx.device_index)
+    info, clip_info = ctx.raw_scalar_tracks_info(raw), ctx.clip_info(clip)
+    if int(clip_info.track_type) != int(info.track_type) or int(clip_info.num_tracks) != int(info.num_tracks):
+        raise ValueError(f"the clip holds {clip_info.num_tracks} tracks of type {clip_info.track_type}, the raw array {info.num_tracks} of type {info.track_type}")
+    num_tracks, num_components, num_samples = int(info.num_tracks), int(info.num_components), int(info.num_samples)
+    sample_times = np.minimum(np.arange(num_samples, dtype=np.float32) / np.float32(info.sample_rate), np.float32(info.duration)).astype(np.float32)
+    if rounding is None:
+        rounding = ROUND_NONE if clip_info.has_database or clip_info.has_stripped_keyframes else ROUND_NEAREST
+    stride = num_tracks * num_components * 4
+    stream = torch.cuda.current_stream(device)
+    d_times = torch.from_numpy(sample_times).to(device)
+    d_raw, d_lossy = (torch.zeros((num_samples, stride // 4), dtype=torch.float32, device=device) for _ in range(2))
+    sample_desc = RawSampleDesc()
+    sample_desc.rounding_policy = int(rounding)
+    d_raws = torch.full((num_samples,), int(raw), dtype=torch.int32, device=device)
+    ctx.sample_raw_scalar_tracks_batch(d_raws.data_ptr(), d_times.data_ptr(), num_samples, d_raw.data_ptr(), stride, desc=sample_desc, stream=stream.cuda_stream)
+    decode_params = default_params()
+    decode_params.rounding_policy = int(rounding)
+    d_clips = torch.full((num_samples,), int(clip), dtype=torch.int32, device=device)
+    ctx.decompress_scalar_tracks_batch(d_clips.data_ptr(), d_times.data_ptr(), num_samples, d_lossy.data_ptr(), stride, params=decode_params, stream=stream.cuda_stream)
+    return _worst_scalar_error(ctx, device, stream, d_raw, d_lossy, stride, num_samples, num_tracks, num_components, sample_times)
+
+
+def scalar_clip_error(ctx, clip_a, clip_b):
+    """The two-context overload (impl/track_error.impl.h:692-750) for scalar tracks, as clip_error is for transforms: both registered scalar
+    clips decoded at min(i / sample_rate, duration) for every sample i of clip_a with ROUND_NEAREST, then measured. clip_a plays the raw
+    clip. Returns (track, error, sample_time) like raw_scalar_clip_error; clips of different track types or counts raise ValueError."""
+    import torch
+    device = torch.device("cuda", ctx.device_index)
+    info, info_b = ctx.clip_info(clip_a), ctx.clip_info(clip_b)
+    if int(info.track_type) == TRACK_QVVF or int(info.track_type) != int(info_b.track_type) or int(info.num_tracks) != int(info_b.num_tracks):
+        raise ValueError(f"two scalar clips of one track type and count are needed, not {info.num_tracks} of type {info.track_type} and {info_b.num_tracks} of type {info_b.track_type}")
+    num_tracks, num_components, num_samples = int(info.num_tracks), int(info.num_components), int(info.num_samples)
+    if num_samples == 0 or num_tracks == 0:
+        return NO_TRACK, -1.0, float("nan")
+    sample_times = np.minimum(np.arange(num_samples, dtype=np.float32) / np.float32(info.sample_rate), np.float32(info.duration)).astype(np.float32)
+    stride = num_tracks * num_components * 4
+    stream = torch.cuda.current_stream(device)
+    d_times = torch.from_numpy(sample_times).to(device)
+    d_values = [torch.zeros((num_samples, stride // 4), dtype=torch.float32, device=device) for _ in range(2)]
+    decode_params = default_params()
+    decode_params.rounding_policy = ROUND_NEAREST
+    for clip, d_value in zip((clip_a, clip_b), d_values):
+        d_clips = torch.full((num_samples,), int(clip), dtype=torch.int32, device=device)
+        ctx.decompress_scalar_tracks_batch(d_clips.data_ptr(), d_times.data_ptr(), num_samples, d_value.data_ptr(), stride, params=decode_params, stream=stream.cuda_stream)
+    return _worst_scalar_error(ctx, device, stream, d_values[0], d_values[1], stride, num_samples, num_tracks, num_components, sample_times)

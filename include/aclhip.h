@@ -207,7 +207,9 @@ const char* aclhip_last_error_message(const aclhip_context* context);
  * aclhip_matrix_layout, aclhip_pose_matrices_desc, aclhip_error_metric, aclhip_pose_matrices_batch and
  * aclhip_measure_pose_error_metric_batch -- and for the skinning palettes -- aclhip_skin_info, aclhip_palette_layout,
  * aclhip_skinning_desc, the four skin entry points and aclhip_skinning_matrices_batch -- and for raw track arrays --
- * aclhip_raw_tracks_info, aclhip_raw_sample_desc, the four raw track entry points and aclhip_sample_raw_tracks_batch).
+ * aclhip_raw_tracks_info, aclhip_raw_sample_desc, the four raw track entry points and aclhip_sample_raw_tracks_batch -- and for raw
+ * scalar track arrays and the scalar track error -- aclhip_raw_scalar_tracks_info, aclhip_scalar_error_desc, the four raw scalar track
+ * entry points, aclhip_sample_raw_scalar_tracks_batch, aclhip_sample_raw_scalar_track_batch and aclhip_measure_scalar_error_batch).
  * A caller compiled against another header would hand over structs of another shape; aclhip_abi_version() says what the LIBRARY was
  * built with, and the C++ mirror (aclhip.hpp) refuses to create a context when the two differ. */
 #define ACLHIP_ABI_VERSION 6u
@@ -1618,8 +1620,8 @@ typedef struct aclhip_raw_sample_desc
  * rows from `poses`) overlapping raws, sample_times or any array of the desc.
  *   desc == NULL: ROUND_NONE, row i. The launch goes on `stream`, can be captured into a graph and uploads nothing; registered clips play
  * no part. The instance arrays are plain device arrays: a retired handle in them is refused by the kernel, not by the host.
- *   Out of scope (nothing here precludes them): remapped output bones (track_array's remap_output); the scalar track types of
- * track_array; sample_track, the single-track form; QVV40 / QV32 rows; the C++ mirror in aclhip.hpp.
+ *   Out of scope (nothing here precludes them): remapped output bones (track_array's remap_output); sample_track, the single-track
+ * form; QVV40 / QV32 rows; the C++ mirror in aclhip.hpp. (The scalar track types of track_array are the raw scalar track arrays, below.)
  *   What it costs: (one MI355X, 65 536 instances of one array of 100 tracks x 301 samples at uniformly drawn times, rows of 4 800 bytes,
  * medians of three interleaved rounds of 20 launches; tools/raw_tracks.py, profiles/raw_tracks.md, DESIGN.md 4.7 "Raw track arrays"):
  * 81.1 us next to 60.1 us of aclhip_decompress_tracks_batch of a compressed clip of the same shape at the same times in the same rounds
@@ -1632,6 +1634,137 @@ typedef struct aclhip_raw_sample_desc
 aclhip_status aclhip_sample_raw_tracks_batch(aclhip_context* context, const aclhip_raw_tracks* raws /* DEVICE [num_instances] */,
 	const float* sample_times /* DEVICE [num_instances] */, uint32_t num_instances, const aclhip_raw_sample_desc* desc, void* poses,
 	uint64_t pose_stride_bytes, void* stream);
+
+/* ---- raw scalar track arrays: batched sample_tracks / sample_track of uncompressed curve sets, and the scalar track error ------------
+ * acl::track_array holds five more track types than qvvf: float1f, float2f, float3f, float4f and vector4f (compression/track_array.h).
+ * A RAW SCALAR TRACK ARRAY is such an uncompressed curve set -- blend shape weights, material and camera curves, recorded or procedural
+ * curves, curves queued for compression --, aclhip_sample_raw_scalar_tracks_batch is its sample_tracks
+ * (compression/impl/track_array.impl.h:209-343) over a batch, aclhip_sample_raw_scalar_track_batch its sample_track (:345-438), and
+ * aclhip_measure_scalar_error_batch is calculate_scalar_track_error (compression/impl/track_error.impl.h:53-103, :166-217) over two value
+ * buffers: what the reference's scalar overloads of calculate_compression_error run for everything but qvvf. (ABI version 6 still: added
+ * structs and added functions, no existing struct changed.)
+ *
+ * aclhip_register_raw_scalar_tracks: `samples` is a HOST array of [num_samples][num_tracks][C] floats, SAMPLE MAJOR and tight: one key
+ * frame of the whole list is one contiguous run, laid out like the row aclhip_decompress_scalar_tracks_batch writes. `track_type` is
+ * acl::track_type8 as aclhip_clip_info::track_type reports it: 0 to 3 for float1f to float4f, 4 for vector4f; C is 1, 2, 3, 4, 4 in that
+ * order. The caller may free the array when the call returns; the device image keeps the layout. Looping policy and duration are a raw
+ * track array's: ACLHIP_LOOP_CLAMP or ACLHIP_LOOP_WRAP, calculate_finite_duration(num_samples + (wrap ? 1 : 0), sample_rate). Refused with
+ * ACLHIP_ERROR_INVALID_ARGUMENT and a message, before any device call: everything aclhip_register_raw_tracks refuses (samples or out_raw
+ * == NULL; num_tracks == 0 or > 0xFFFF; num_samples == 0; a sample_rate that is not finite or not > 0; ACLHIP_LOOP_AS_COMPRESSED or an
+ * unknown policy), its size limit as num_samples * num_tracks * C * 4 >= 2^31, track type 12 (qvvf: that is a raw track array) and any
+ * unknown track type. VALUES ARE NOT CHECKED. The handles are a table of their own (ACLHIP_MAX_RAW_SCALAR_TRACKS records): a raw track
+ * handle names no scalar array and the reverse, whatever its value. Lifetime, stream ordered unregistration and graph safety are a raw
+ * track array's. */
+typedef uint32_t aclhip_raw_scalar_tracks;		/* handle returned by aclhip_register_raw_scalar_tracks; 0 = none */
+#define ACLHIP_MAX_RAW_SCALAR_TRACKS 4096u		/* live arrays of one context, the null handle included */
+
+typedef struct aclhip_raw_scalar_tracks_info
+{
+	uint32_t num_tracks;
+	uint32_t num_samples;
+	float sample_rate;
+	float duration;							/* track_array::get_finite_duration() */
+	uint32_t looping_policy;				/* ACLHIP_LOOP_CLAMP or ACLHIP_LOOP_WRAP */
+	uint32_t track_type;					/* acl::track_type8: 0 .. 4 */
+	uint32_t num_components;				/* C: floats per track, 1 .. 4 */
+	uint32_t reserved;
+} aclhip_raw_scalar_tracks_info;			/* 32 bytes */
+
+/* Host only (no context, no device): what registration checks and what aclhip_get_raw_scalar_tracks_info reports; `samples` is only
+ * tested against NULL. `message` (may be NULL, `message_capacity` bytes) receives the reason when the array is refused; `out_info` may be NULL. */
+aclhip_status aclhip_check_raw_scalar_tracks(const void* samples, uint32_t track_type, uint32_t num_tracks, uint32_t num_samples,
+	float sample_rate, uint32_t looping_policy, aclhip_raw_scalar_tracks_info* out_info, char* message, uint32_t message_capacity);
+
+aclhip_status aclhip_register_raw_scalar_tracks(aclhip_context* context, const void* samples, uint32_t track_type, uint32_t num_tracks,
+	uint32_t num_samples, float sample_rate, uint32_t looping_policy, aclhip_raw_scalar_tracks* out_raw);
+aclhip_status aclhip_unregister_raw_scalar_tracks(aclhip_context* context, aclhip_raw_scalar_tracks raw);
+aclhip_status aclhip_get_raw_scalar_tracks_info(const aclhip_context* context, aclhip_raw_scalar_tracks raw, aclhip_raw_scalar_tracks_info* out_info);
+
+/* The definition of aclhip_sample_raw_scalar_tracks_batch; the desc is aclhip_raw_sample_desc, unchanged. All arithmetic is fp32, one
+ * IEEE operation at a time, never fused. Instance i has array A = raws[i] with T tracks of C floats, S samples, rate r, looping policy L
+ * and duration D, and rounding policy p = instance_rounding_policies[i], or desc->rounding_policy (a device value above PER_TRACK is
+ * taken as NONE).
+ *   1. t = min(max(sample_times[i], 0), D); (k0, k1, alpha) as in step 1 of aclhip_sample_raw_tracks_batch: the two key frames and the
+ *      UNROUNDED alpha, k0 guarded by min(k0, S - 1). A NaN sample time is not specified (nothing is read outside the array).
+ *   2. Per track b < T: q = p, or track_rounding_policies[b] when p is PER_TRACK; a_b = apply_rounding_policy(alpha, q).
+ *   3. Per component c < C, with V0, V1 the values of track b at key frames k0, k1: value = (V1[c] * a_b) + (V0[c] - (V0[c] * a_b))
+ *      (rtm::scalar_lerp and rtm::vector_lerp are this expression).
+ *   4. Track b is stored as C floats at values + row * stride_bytes + 4 * C * b (row = rows[i], or i): the row layout of
+ *      aclhip_decompress_scalar_tracks_batch, so a sampled row and a decoded row of the same list compare element for element. Nothing
+ *      is padded or zero filled; bytes of the row behind 4 * C * T are untouched. Arrays of different types may share a launch: each row
+ *      has its own array's shape.
+ *   Against the reference itself the values are identical in every bit (the tests hold it through a precision 0 compression).
+ *   Refused and counted (aclhip_get_rejected_instance_count), the row untouched, decided in front of any load of a key frame: an unknown
+ * or retired handle (0 included); 4 * C * T > stride_bytes; PER_TRACK with T > num_track_rounding_policies.
+ *   ACLHIP_ERROR_INVALID_ARGUMENT, decided before any device call, each with a message (with or without a context): raws, sample_times or
+ * values == NULL; values or stride_bytes not 4 byte aligned, or a stride of 0; a rounding_policy above PER_TRACK; PER_TRACK without
+ * track_rounding_policies; track_rounding_policies with a count of 0; reserved fields that are not 0; the output range (num_instances
+ * rows from `values`) overlapping raws, sample_times or any array of the desc.
+ *   desc == NULL: ROUND_NONE, row i. The launch goes on `stream`, can be captured into a graph and uploads nothing.
+ *   The kernel has two paths. Row base, stride and T * C are only 4 byte aligned in general: the DWORD path gives every lane one float
+ * of the row and serves every case. A wave whose row and whose two key frames all start on 16 byte boundaries -- decided per instance
+ * from the addresses themselves -- takes the row's whole quads with 16 byte loads and stores, each float of a quad with its own
+ * track's alpha, and the last T * C % 4 floats the dword way. The bits are the same on both paths.
+ *   Out of scope (nothing here precludes them): track_array's remap_output and stripped tracks (output_index); per-instance shapes in the
+ * measure; the C++ mirror in aclhip.hpp; the qvvf single-track form.
+ *   What it costs: (one MI355X, 65 536 instances of one float1f array of 256 tracks x 120 samples -- the bench's scalar list shape -- at
+ * uniformly drawn times, medians of three interleaved rounds of 20 launches; tools/raw_scalar_tracks.py, profiles/raw_scalar_tracks.md,
+ * DESIGN.md 4.7 "Raw scalar track arrays"): rows of 1 024 bytes, base and stride 16 byte aligned (the 16 byte path): 18.9 us next to
+ * 25.6 us of aclhip_decompress_scalar_tracks_batch of the reference-compressed clip of the same array at the same times in the same
+ * rounds, 0.74 x its time, 0.45 of the HBM peak (67 MB of rows plus the array's 123 KB) against its 0.33, spread 11 %. The same rows on
+ * the dword path (the lab library's ACLHIP_RAW_SCALAR_DWORD=1): 26.5 us, 1.07 x the decode: the 16 byte path buys 0.71 x. Rows of 1 028
+ * bytes, only 4 byte aligned (three rows of four on the dword path): 36.5 us next to 28.9 us, 1.26 x -- both launches pay for rows that
+ * share cache lines with their neighbours, this one more. The single-track launch: 3.5 us next to 3.7 us of
+ * aclhip_decompress_scalar_track_batch for the same 65 536 requests. No counter run has been taken. */
+aclhip_status aclhip_sample_raw_scalar_tracks_batch(aclhip_context* context, const aclhip_raw_scalar_tracks* raws /* DEVICE [num_instances] */,
+	const float* sample_times /* DEVICE [num_instances] */, uint32_t num_instances, const aclhip_raw_sample_desc* desc, void* values,
+	uint64_t stride_bytes, void* stream);
+
+/* track_array::sample_track, the single-track form: request i writes the C floats of track track_indices[i] of array raws[i] at values +
+ * row * stride_bytes. The policy is the launch's or the instance's, or track_rounding_policies[track] under PER_TRACK. The reference
+ * hands the policy to the key frame search, which rounds the alpha with the same apply_rounding_policy: THE BITS ARE THOSE OF THE
+ * WHOLE-LIST LAUNCH FOR THAT TRACK (steps 1 to 3 above), and the tests hold it.
+ *   Refused and counted, the request's bytes untouched: an unknown or retired handle; track >= T; 4 * C > stride_bytes; PER_TRACK with
+ * track >= num_track_rounding_policies.
+ *   ACLHIP_ERROR_INVALID_ARGUMENT: as above, plus track_indices == NULL and the output range overlapping track_indices. */
+aclhip_status aclhip_sample_raw_scalar_track_batch(aclhip_context* context, const aclhip_raw_scalar_tracks* raws /* DEVICE [num_instances] */,
+	const float* sample_times /* DEVICE [num_instances] */, const uint32_t* track_indices /* DEVICE [num_instances] */, uint32_t num_instances,
+	const aclhip_raw_sample_desc* desc, void* values, uint64_t stride_bytes, void* stream);
+
+/* The scalar track error. The records are the pose error's, so that one worst scan serves both. */
+typedef aclhip_pose_error aclhip_track_error;				/* { float error; uint32_t track; } -- the same 8 bytes (the field is named bone) */
+typedef aclhip_pose_error_worst aclhip_track_error_worst;	/* { error, track, instance, reserved } -- the same 16 bytes */
+#define ACLHIP_NO_TRACK 0xFFFFFFFFu
+
+typedef struct aclhip_scalar_error_desc
+{
+	uint32_t num_tracks;						/*  0  T >= 1, for every instance */
+	uint32_t num_components;					/*  4  C in 1 .. 4 */
+	float* track_errors;						/*  8  DEVICE or NULL: error of track b of instance i at (char*)track_errors + i * track_error_stride_bytes + 4 * b */
+	uint64_t track_error_stride_bytes;			/* 16 */
+	aclhip_track_error_worst* worst;			/* 24  DEVICE or NULL: one record for the launch */
+	uint64_t reserved[2];						/* 32  0 */
+} aclhip_scalar_error_desc;						/* 48 bytes */
+
+/* The definition (track_error.impl.h:53-103 and :198-213). R and Y are the T tracks of C floats at raw_values + i * raw_stride_bytes and
+ * lossy_values + i * lossy_stride_bytes, tight.
+ *   1. e_c = fabs(R[b][c] - Y[b][c]) for c < C (the reference's zeroed missing lanes cannot win against an error >= 0).
+ *   2. error[b] is the greatest e_c with max(a, b) = a > b ? a : b, taken in ascending component order; it is a NaN if any e_c is a NaN
+ *      (the reference leaves NaN handling to the host's SIMD max; this rule is this library's: stored as a NaN, never wins).
+ *   3. errors[i] starts from { -1, ACLHIP_NO_TRACK } and takes track b, in ascending order, when error[b] > the record's error. A NaN
+ *      never wins; ties go to the lowest track.
+ *   4. With track_errors: every error[b] is stored, a NaN as a NaN (its payload is not specified); bytes behind 4 * T are untouched.
+ *   5. With worst: step 6 of aclhip_measure_pose_error_batch word for word -- the scan of errors[0 .. num_instances) in ascending instance
+ *      order; { -1, ACLHIP_NO_TRACK, 0xFFFFFFFF, 0 } when nothing was measured; written by the call itself, also for num_instances == 0.
+ *   There is no handle and no hierarchy: nothing is refused per instance. ACLHIP_ERROR_INVALID_ARGUMENT, decided before any device call,
+ * each with a message (with or without a context): desc, raw_values, lossy_values or errors == NULL; T == 0; C outside 1 .. 4; 4 * C * T
+ * larger than either stride; track_errors with a stride that is 0, no multiple of 4, or < 4 * T; values or strides that are not 4 byte
+ * aligned; errors not 8 byte aligned; worst not 16 byte aligned; reserved fields that are not 0; any output range (errors, track_errors,
+ * worst) overlapping an input or another output. raw and lossy may be the same buffer: every error is 0 and the record names track 0.
+ *   One wave per instance, a lane per track in turn, 8 bytes out per instance: not a kernel tuned for bandwidth, and not measured. */
+aclhip_status aclhip_measure_scalar_error_batch(aclhip_context* context, const void* raw_values, uint64_t raw_stride_bytes,
+	const void* lossy_values, uint64_t lossy_stride_bytes, uint32_t num_instances, const aclhip_scalar_error_desc* desc,
+	aclhip_track_error* errors /* DEVICE [num_instances], required */, void* stream);
 
 /* ---- multi-GPU ---------------------------------------------------------------------------------- */
 
