@@ -17,6 +17,7 @@
 //   sample_raw_scalar_tracks_kernel    uncompressed scalar curve sets (raw scalar track arrays): one lane per float of the value row (four floats where row and key frames are 16 byte aligned), two loads, one store.
 //   sample_raw_scalar_track_kernel     the same arrays, one thread per (instance, track) request.
 //   measure_scalar_error_kernel        the scalar track error of two value buffers: one wave64 per instance, lanes <-> tracks.
+//   scalar_compress_*_kernel           compress_track_list of raw scalar track arrays in five launches: vote, per-track analysis (one wave64 per track), layout, bit stream (one lane per output dword), hash.
 //   decompress_track_kernel            one thread per (instance, bone) request; the registration time plan replaces the
 //                                      reference's O(track index) skip over preceding widths.
 //   decompress_scalar_tracks_kernel    scalar track lists: one wave64 per (instance, 256 tracks), lanes <-> tracks.
@@ -61,6 +62,7 @@ namespace aclhip
 #include "kernels_pose_buffers.inl"
 #include "kernels_raw_tracks.inl"
 #include "kernels_raw_scalar_tracks.inl"
+#include "kernels_scalar_compress.inl"
 #include "kernels_misc.inl"
 #include "kernels_scalar.inl"
 #include "kernels_track.inl"
@@ -88,5 +90,6 @@ using namespace aclhip;
 #include "host_skins.inl"
 #include "host_raw_tracks.inl"
 #include "host_raw_scalar_tracks.inl"
+#include "host_scalar_compress.inl"
 #include "host_bone_object.inl"
 #include "host_scalar_misc.inl"

@@ -108,7 +108,7 @@ extern "C" aclhip_status aclhip_register_raw_scalar_tracks(aclhip_context* conte
 		record.num_samples = num_samples;
 		record.sample_rate = sample_rate;
 		record.duration = info.duration;
-		record.looping_policy = looping_policy;
+		record.looping_policy = looping_policy | (track_type << 8);
 		record.num_components = info.num_components;
 		size_t staging_used = 0;
 		// the image first, as the caller laid it out, and the record that publishes it behind it

@@ -16,7 +16,7 @@
 		uint32_t num_samples;
 		float sample_rate;
 		float duration;						// calculate_finite_duration(num_samples + (wrap ? 1 : 0), sample_rate), made on the host
-		uint32_t looping_policy;			// k_loop_clamp or k_loop_wrap
+		uint32_t looping_policy;			// k_loop_clamp or k_loop_wrap | acl::track_type8 << 8 (float4f and vector4f both hold 4 floats: the compressor's header names the type)
 		uint32_t num_components;			// C: 1 to 4
 	};
 	static_assert(sizeof(device_raw_scalar_tracks) == 32, "load_entry: two dwordx4 loads");
@@ -28,6 +28,9 @@
 		asm volatile("" : "+s"(raw.samples), "+s"(raw.num_tracks), "+s"(raw.num_samples), "+s"(raw.sample_rate), "+s"(raw.duration), "+s"(raw.looping_policy), "+s"(raw.num_components));
 		return raw;
 	}
+
+	__device__ __forceinline__ uint32_t raw_scalar_looping_policy_of(const device_raw_scalar_tracks& raw) { return raw.looping_policy & 0xFFu; }
+	__device__ __forceinline__ uint32_t raw_scalar_track_type_of(const device_raw_scalar_tracks& raw) { return raw.looping_policy >> 8; }
 
 	// the argument of both sampling kernels
 	struct raw_scalar_sample_launch
@@ -101,7 +104,7 @@
 		// what is served reads inside its two key frames (both < num_samples) and writes inside the first 4 * C * num_tracks bytes of its row
 		uint32_t key_frame0, key_frame1;
 		float alpha;
-		find_key_frames(0, raw.num_samples, raw.sample_rate, raw.duration, raw.duration, sample_time, k_round_none, raw.looping_policy == k_loop_wrap ? k_loop_wrap : k_loop_clamp,
+		find_key_frames(0, raw.num_samples, raw.sample_rate, raw.duration, raw.duration, sample_time, k_round_none, raw_scalar_looping_policy_of(raw) == k_loop_wrap ? k_loop_wrap : k_loop_clamp,
 			key_frame0, key_frame1, alpha);
 		key_frame0 = min(key_frame0, raw.num_samples - 1u);		// (sample_raw_tracks_kernel says when)
 
@@ -172,7 +175,7 @@
 		uint32_t key_frame0, key_frame1;
 		float alpha;
 		find_key_frames(0, raw.num_samples, raw.sample_rate, raw.duration, raw.duration, launch.sample_times[instance], k_round_none,
-			raw.looping_policy == k_loop_wrap ? k_loop_wrap : k_loop_clamp, key_frame0, key_frame1, alpha);
+			raw_scalar_looping_policy_of(raw) == k_loop_wrap ? k_loop_wrap : k_loop_clamp, key_frame0, key_frame1, alpha);
 		key_frame0 = min(key_frame0, raw.num_samples - 1u);
 		alpha = apply_rounding_policy(alpha, policy == k_round_per_track ? uint32_t(launch.track_rounding_policies[track]) : policy);
 

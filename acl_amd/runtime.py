@@ -58,6 +58,7 @@ EXPORTED_SYMBOLS = [
     "aclhip_sample_raw_tracks_batch",
     "aclhip_check_raw_scalar_tracks", "aclhip_register_raw_scalar_tracks", "aclhip_unregister_raw_scalar_tracks", "aclhip_get_raw_scalar_tracks_info",
     "aclhip_sample_raw_scalar_tracks_batch", "aclhip_sample_raw_scalar_track_batch", "aclhip_measure_scalar_error_batch",
+    "aclhip_scalar_compress_bound", "aclhip_scalar_compress_workspace_bytes", "aclhip_compress_raw_scalar_tracks_batch",
 ]
 
 
@@ -252,6 +253,17 @@ class ScalarErrorDesc(ctypes.Structure):
     ]
 
 
+class ScalarCompressDesc(ctypes.Structure):
+    """aclhip_scalar_compress_desc; track_precisions and workspace are device addresses"""
+    _fields_ = [
+        ("precision", ctypes.c_float), ("flags", ctypes.c_uint32), ("track_precisions", ctypes.c_void_p), ("num_track_precisions", ctypes.c_uint32),
+        ("max_tracks", ctypes.c_uint32), ("workspace", ctypes.c_void_p), ("reserved", ctypes.c_uint64 * 2),
+    ]
+
+
+COMPRESS_OPTIMIZE_LOOPS = 1                                                                 # ACLHIP_COMPRESS_OPTIMIZE_LOOPS
+COMPRESS_OK, COMPRESS_NOT_FINITE, COMPRESS_REFUSED = 0, 1, 2                                # aclhip_compress_result::status
+COMPRESS_RESULT_DTYPE = np.dtype([("status", np.uint32), ("size", np.uint32)])              # aclhip_compress_result as a numpy record
 MAX_RAW_SCALAR_TRACKS = 4096        # ACLHIP_MAX_RAW_SCALAR_TRACKS
 NO_TRACK = 0xFFFFFFFF               # ACLHIP_NO_TRACK
 TRACK_FLOAT1F, TRACK_FLOAT2F, TRACK_FLOAT3F, TRACK_FLOAT4F, TRACK_VECTOR4F, TRACK_QVVF = 0, 1, 2, 3, 4, 12     # acl::track_type8
@@ -483,6 +495,11 @@ def load_library():
     lib.aclhip_sample_raw_scalar_tracks_batch.argtypes = [vp, vp, vp, u32, ctypes.POINTER(RawSampleDesc), vp, u64, vp]
     lib.aclhip_sample_raw_scalar_track_batch.argtypes = [vp, vp, vp, vp, u32, ctypes.POINTER(RawSampleDesc), vp, u64, vp]
     lib.aclhip_measure_scalar_error_batch.argtypes = [vp, vp, u64, vp, u64, u32, ctypes.POINTER(ScalarErrorDesc), vp, vp]
+    lib.aclhip_scalar_compress_bound.argtypes = [u32, u32, u32]
+    lib.aclhip_scalar_compress_bound.restype = u64
+    lib.aclhip_scalar_compress_workspace_bytes.argtypes = [u32, u32]
+    lib.aclhip_scalar_compress_workspace_bytes.restype = u64
+    lib.aclhip_compress_raw_scalar_tracks_batch.argtypes = [vp, vp, u32, ctypes.POINTER(ScalarCompressDesc), vp, u64, vp, vp]
     _lib = lib
     return lib
 
@@ -1126,6 +1143,13 @@ class Context:
         self._check(self._lib.aclhip_measure_scalar_error_batch(self._handle, raw_values_ptr, raw_stride_bytes, lossy_values_ptr, lossy_stride_bytes, num_instances,
                                                                 ctypes.byref(desc) if desc is not None else None, errors_ptr, stream))
 
+    def compress_raw_scalar_tracks_batch(self, raws_ptr, num_instances, desc, blobs_ptr, blob_stride_bytes, results_ptr, stream=None):
+        """aclhip_compress_raw_scalar_tracks_batch: compress_track_list of the raw scalar track arrays named at raws_ptr (device uint32
+        [num_instances]) into the rows at blobs_ptr, one aclhip_compress_result per instance at results_ptr (device addresses); `desc` is
+        a ScalarCompressDesc with its workspace."""
+        self._check(self._lib.aclhip_compress_raw_scalar_tracks_batch(self._handle, raws_ptr, num_instances, ctypes.byref(desc) if desc is not None else None,
+                                                                      blobs_ptr, blob_stride_bytes, results_ptr, stream))
+
     def decompress_poses_mapped(self, clips, sample_times, skeletons, maps, num_bones, additive_format=ADDITIVE_NONE, object_space=False, base_clips=None,
                                 base_sample_times=None, base_maps=None, base_poses=None, params=None, out=None, instance_rounding=None, instance_looping=None,
                                 blend_clips=None, blend_sample_times=None, blend_maps=None, blend_weights=None, flags=0):
@@ -1625,6 +1649,66 @@ def raw_scalar_clip_error(ctx, raw, clip, rounding=None):
     d_clips = torch.full((num_samples,), int(clip), dtype=torch.int32, device=device)
     ctx.decompress_scalar_tracks_batch(d_clips.data_ptr(), d_times.data_ptr(), num_samples, d_lossy.data_ptr(), stride, params=decode_params, stream=stream.cuda_stream)
     return _worst_scalar_error(ctx, device, stream, d_raw, d_lossy, stride, num_samples, num_tracks, num_components, sample_times)
+
+
+def scalar_compress_bound(track_type, num_tracks, num_samples):
+    """aclhip_scalar_compress_bound (host only): the bytes a blob of such an array can take, rounded up to 16; 0 for a track type that is no
+    scalar type"""
+    return int(load_library().aclhip_scalar_compress_bound(int(track_type), int(num_tracks), int(num_samples)))
+
+
+def scalar_compress_workspace_bytes(num_instances, max_tracks):
+    """aclhip_scalar_compress_workspace_bytes (host only)"""
+    return int(load_library().aclhip_scalar_compress_workspace_bytes(int(num_instances), int(max_tracks)))
+
+
+def compress_scalar_tracks(ctx, raws, precision=1.0e-5, track_precisions=None, optimize_loops=False):
+    """acl::compress_track_list for raw scalar track arrays as one launch: `raws` is a handle or a list of handles
+    (register_raw_scalar_tracks; they may repeat and differ in type and shape), `precision` the tracks' precision (the reference's default)
+    or `track_precisions` one per track, shared by the arrays. Rows are sized from aclhip_scalar_compress_bound, the workspace is allocated,
+    the results and the blobs are copied back: returns a list of 16 byte aligned numpy uint8 blobs, byte for byte the reference's.
+    aclhip_register_clip takes a host pointer, so a blob comes back before it is registered. Raises RuntimeError with the reference's
+    message when a sample is not finite, ValueError when an instance is refused. Synchronous; the buffers are torch tensors on the
+    context's device."""
+    import torch
+    from .synth import aligned_bytes
+    device = torch.device("cuda", ctx.device_index)
+    handles = np.atleast_1d(np.asarray(raws, dtype=np.uint32))
+    infos = [ctx.raw_scalar_tracks_info(int(handle)) for handle in handles]
+    num_instances = len(handles)
+    if num_instances == 0:
+        return []
+    stride = max(scalar_compress_bound(info.track_type, info.num_tracks, info.num_samples) for info in infos)
+    max_tracks = max(int(info.num_tracks) for info in infos)
+    stream = torch.cuda.current_stream(device)
+    d_raws = torch.from_numpy(handles.view(np.int32)).to(device)
+    d_blobs = torch.zeros((num_instances, stride), dtype=torch.uint8, device=device)
+    d_results = torch.zeros((num_instances, 2), dtype=torch.int32, device=device)
+    d_workspace = torch.zeros(scalar_compress_workspace_bytes(num_instances, max_tracks) + 16, dtype=torch.uint8, device=device)
+    desc = ScalarCompressDesc()
+    desc.precision = float(precision)
+    desc.flags = COMPRESS_OPTIMIZE_LOOPS if optimize_loops else 0
+    desc.max_tracks = max_tracks
+    desc.workspace = d_workspace.data_ptr()
+    d_precisions = None
+    if track_precisions is not None:
+        d_precisions = torch.from_numpy(np.ascontiguousarray(track_precisions, dtype=np.float32)).to(device)
+        desc.track_precisions, desc.num_track_precisions = d_precisions.data_ptr(), d_precisions.numel()
+    ctx.compress_raw_scalar_tracks_batch(d_raws.data_ptr(), num_instances, desc, d_blobs.data_ptr(), stride, d_results.data_ptr(), stream=stream.cuda_stream)
+    stream.synchronize()
+    results = d_results.cpu().numpy().view(np.uint32).reshape(num_instances, 2)
+    rows = d_blobs.cpu().numpy()
+    blobs = []
+    for i in range(num_instances):
+        status, size = int(results[i, 0]), int(results[i, 1])
+        if status == COMPRESS_NOT_FINITE:
+            raise RuntimeError("Some samples are not finite")
+        if status != COMPRESS_OK:
+            raise ValueError(f"instance {i} (raw scalar track array {int(handles[i])}) was refused (ACLHIP_COMPRESS_REFUSED)")
+        blob = aligned_bytes(size)
+        blob[:] = rows[i, :size]
+        blobs.append(blob)
+    return blobs
 
 
 def scalar_clip_error(ctx, clip_a, clip_b):

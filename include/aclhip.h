@@ -209,7 +209,9 @@ const char* aclhip_last_error_message(const aclhip_context* context);
  * aclhip_skinning_desc, the four skin entry points and aclhip_skinning_matrices_batch -- and for raw track arrays --
  * aclhip_raw_tracks_info, aclhip_raw_sample_desc, the four raw track entry points and aclhip_sample_raw_tracks_batch -- and for raw
  * scalar track arrays and the scalar track error -- aclhip_raw_scalar_tracks_info, aclhip_scalar_error_desc, the four raw scalar track
- * entry points, aclhip_sample_raw_scalar_tracks_batch, aclhip_sample_raw_scalar_track_batch and aclhip_measure_scalar_error_batch).
+ * entry points, aclhip_sample_raw_scalar_tracks_batch, aclhip_sample_raw_scalar_track_batch and aclhip_measure_scalar_error_batch -- and
+ * for the scalar compressor -- aclhip_scalar_compress_desc, aclhip_compress_result, aclhip_scalar_compress_bound,
+ * aclhip_scalar_compress_workspace_bytes and aclhip_compress_raw_scalar_tracks_batch).
  * A caller compiled against another header would hand over structs of another shape; aclhip_abi_version() says what the LIBRARY was
  * built with, and the C++ mirror (aclhip.hpp) refuses to create a context when the two differ. */
 #define ACLHIP_ABI_VERSION 6u
@@ -1765,6 +1767,94 @@ typedef struct aclhip_scalar_error_desc
 aclhip_status aclhip_measure_scalar_error_batch(aclhip_context* context, const void* raw_values, uint64_t raw_stride_bytes,
 	const void* lossy_values, uint64_t lossy_stride_bytes, uint32_t num_instances, const aclhip_scalar_error_desc* desc,
 	aclhip_track_error* errors /* DEVICE [num_instances], required */, void* stream);
+
+/* ---- compress_track_list for raw scalar track arrays ------------------------------------------------------------------------------------
+ * acl::compress_track_list for float1f .. vector4f (compression/impl/compress.scalar.impl.h:65-269 and the files it calls), batched: a
+ * registered raw scalar track array -- it already lives in HBM -- becomes a `compressed_tracks` blob there. THE BLOB IS BYTE FOR BYTE THE
+ * REFERENCE'S for the same samples and settings, hash included; nothing rests on a tolerance, and the tests hold every byte.
+ *   Instance i compresses array raws[i] into (char*)blobs + i * blob_stride_bytes; blobs and the stride are 16 byte aligned. The launch
+ * writes every byte of [0, size) itself -- the zero padding between the sections and the 15 trailing zero bytes included -- and touches
+ * nothing behind `size`. Handles may repeat; arrays of different types and shapes share a launch. results[i] says how it went. */
+#define ACLHIP_COMPRESS_OPTIMIZE_LOOPS 1u      /* compression_settings::optimize_loops (default off) */
+
+typedef struct aclhip_scalar_compress_desc
+{
+	float precision;                  /*  0  track_desc_scalarf::precision of every track when track_precisions is NULL (reference default 0.00001F) */
+	uint32_t flags;                   /*  4  ACLHIP_COMPRESS_* */
+	const float* track_precisions;    /*  8  DEVICE or NULL: precision of track b, shared by the launch (like track_rounding_policies) */
+	uint32_t num_track_precisions;    /* 16 */
+	uint32_t max_tracks;              /* 20  tracks the workspace was sized for; an instance with more is refused */
+	void* workspace;                  /* 24  DEVICE, 16 byte aligned, aclhip_scalar_compress_workspace_bytes(num_instances, max_tracks) bytes */
+	uint64_t reserved[2];             /* 32  0 */
+} aclhip_scalar_compress_desc;        /* 48 bytes */
+
+typedef struct aclhip_compress_result { uint32_t status; uint32_t size; } aclhip_compress_result;   /* 8 bytes */
+#define ACLHIP_COMPRESS_OK 0u
+#define ACLHIP_COMPRESS_NOT_FINITE 1u          /* the reference's "Some samples are not finite": size 0, row untouched */
+#define ACLHIP_COMPRESS_REFUSED 2u             /* size 0, row untouched, counted by aclhip_get_rejected_instance_count */
+
+/* Host only. The bound of a blob: 52 + align4(T) + 8 * C * T + 4 * C * T * S + 15 rounded up to 16 -- headers, per-track metadata, the
+ * larger of constants and ranges, every track raw, padding; 0 for a track type that is no scalar type. The workspace holds what the
+ * launches of one call hand to each other (64 bytes per instance and 56 per instance and track, rounded up to 16); its contents before
+ * and after a call mean nothing. */
+uint64_t aclhip_scalar_compress_bound(uint32_t track_type, uint32_t num_tracks, uint32_t num_samples);
+uint64_t aclhip_scalar_compress_workspace_bytes(uint32_t num_instances, uint32_t max_tracks);
+
+/* The definition. All arithmetic is fp32, one IEEE operation at a time, never fused, denormals kept. The array has T tracks of C floats
+ * and S samples; track b has precision p_b = track_precisions[b], or desc->precision. v[s][b][c] is a sample value; num_bits(r) is r for
+ * rates 1 .. 23 and 32 for rate 24.
+ *   1. Finite check. If any of the S * T * C floats is not finite, the status is ACLHIP_COMPRESS_NOT_FINITE.
+ *   2. Looping (optimize_looping.scalar.h). With ACLHIP_COMPRESS_OPTIMIZE_LOOPS, an array registered with ACLHIP_LOOP_CLAMP and S > 1: if
+ *      fabs(v[0][b][c] - v[S-1][b][c]) <= p_b for EVERY track and component, S becomes S - 1 and the blob is wrap optimized -- the whole
+ *      list or nothing. An array registered with ACLHIP_LOOP_WRAP keeps S and is wrap optimized without a vote, with or without the
+ *      flag. Everything below uses the new S.
+ *   3. Ranges (track_range_impl.h:44-63), per track and component: min starts at 1e10F, max at -1e10F; in ascending sample order
+ *      min = (min < x) ? min : x and max = (max > x) ? max : x (SSE minps / maxps: the second operand wins a tie); extent = max - min.
+ *      The start values take part: a track whose samples all lie above 1e10 has min = 1e10. When the extreme is a zero, its sign is that
+ *      of the LAST sample equal to it (+0 and -0 compare equal) -- min and extent are written into the blob, so this shows in the bytes.
+ *      The kernel's parallel reduction gives those bits.
+ *   4. Constant tracks: track b is constant iff fabs(extent[c]) < p_b for every component, strictly: with p_b == 0 nothing is constant,
+ *      and a flat track ends at bit rate 1.
+ *   5. Normalization (normalize.scalar.h:44-76) of the other tracks: n = (x - min) / extent, the division correctly rounded;
+ *      n = (n < 1) ? n : 1; n = 0 where extent < 0.000000001F.
+ *   6. Bit rate (quantize.scalar.h:84-160): best starts at 24 (raw); the rates r = 23, 22, ..., 1 are tried in that order.
+ *      max_value = float((1u << r) - 1), inv = 1.0F / max_value, q = floorf(n * max_value + 0.5F) (round_symmetric of a value >= 0),
+ *      d = (q * inv) * extent + min as a multiply, a multiply and an add; rate r passes iff fabs(x - d) <= p_b for every sample and
+ *      component. The first rate that fails ends the search, even if a lower one would pass again; best is the last rate that passed.
+ *   7. The blob (compress.scalar.impl.h:93-251, write_track_data_impl.h): raw_buffer_header { size, hash }; tracks_header { the
+ *      compressed_tracks tag, version 10 (latest), uniformly_sampled, the track type, T, S, the sample rate, bit 30 of the packed word
+ *      when wrap optimized, no metadata }; scalar_tracks_header { num_bits_per_frame, and the offsets of the four sections from its own
+ *      start }. The sections in order: one byte per track -- 0 for a constant track, best otherwise --, padded to 4 bytes; C floats of
+ *      sample 0 per constant track; C floats of min, then C of extent, per track of rate 1 .. 23; ONE bit stream, most significant bit
+ *      first: per sample ascending, per track ascending with the constant ones skipped, per component ascending, num_bits(best) bits --
+ *      uint32(q) for rates 1 .. 23, the float's own 32 bits for rate 24 --, padded to a whole byte (num_bits_per_frame is the bits of one
+ *      sample); 15 zero bytes. size is the total, hash is FNV-1a 32 (core/hash.h) over [8, size).
+ *   A NaN in track_precisions makes nothing constant and every rate fail: the track stays raw. Values of track_precisions are not checked.
+ *   Refused per instance (ACLHIP_COMPRESS_REFUSED, counted, decided in front of any write to the row): an unknown or retired handle (0
+ * included); T > max_tracks; track_precisions with T > num_track_precisions; a blob larger than blob_stride_bytes -- known after the
+ * analysis and before the write, so a stride that is too small never writes outside its row; a bit stream of 2^32 bits or more (the
+ * reference counts them in 32 bits).
+ *   ACLHIP_ERROR_INVALID_ARGUMENT, decided before any device call, each with a message (with or without a context): raws, desc, blobs,
+ * results or desc->workspace == NULL; blobs, the stride or the workspace not 16 byte aligned; a stride of 0; results not 8 byte aligned;
+ * unknown flags or reserved fields that are not 0; a precision that is negative or not finite; track_precisions with a count of 0;
+ * max_tracks == 0; the blob rows, the results or the workspace overlapping one another, raws or track_precisions.
+ *   The call is stream ordered, uploads nothing and can be captured into a graph. Five launches (DESIGN.md 4.7 "Scalar compression"):
+ * the vote per instance; the analysis, one wave per (instance, track); the layout, one wave per instance, which also stores headers,
+ * metadata, constants and ranges; the bit stream, one lane per output dword gathering the values that fall into it (no atomics: the
+ * same bytes on every run); the hash, serial in the bytes of a blob, one wave per blob with the chain on the scalar unit.
+ *   Left out (nothing here precludes them): the transform (qvvf) compressor; the optional metadata sections (names, descriptions);
+ * output_index remapping and stripped tracks; registering a clip straight from a device blob (aclhip_register_clip takes a host
+ * pointer: runtime.compress_scalar_tracks copies back); the C++ mirror in aclhip.hpp; instance lists.
+ *   What it costs (no time is promised; one MI355X, 4 096 instances over 256 distinct float1f arrays of 256 tracks x 120 samples -- the
+ * bench's scalar list shape -- at precision 1e-4, where the rates spread from constant to 17; medians of three interleaved rounds of 20
+ * launches; tools/scalar_compress.py, profiles/scalar_compress.md, DESIGN.md 4.7 "Scalar compression"): 3.57 ms a batch, 0.87 us an
+ * array, next to the reference's compress_track_list over the same instances on the same box: 27.97 s on one thread, 1.83 s on 16.
+ * By phase: vote 3.8 us, analysis 1 508 us (42 %), layout 54 us, bit stream 946 us (26 %), hash 1 061 us (30 %). The hash is a serial
+ * chain per blob: for ONE large array it is the call's critical path, and nothing was built against that. */
+aclhip_status aclhip_compress_raw_scalar_tracks_batch(aclhip_context* context,
+	const aclhip_raw_scalar_tracks* raws /* DEVICE [num_instances] */, uint32_t num_instances,
+	const aclhip_scalar_compress_desc* desc, void* blobs /* DEVICE */, uint64_t blob_stride_bytes,
+	aclhip_compress_result* results /* DEVICE [num_instances] */, void* stream);
 
 /* ---- multi-GPU ---------------------------------------------------------------------------------- */
 
