@@ -63,6 +63,7 @@ namespace aclhip
 #include "kernels_raw_tracks.inl"
 #include "kernels_raw_scalar_tracks.inl"
 #include "kernels_scalar_compress.inl"
+#include "kernels_transform_compress.inl"
 #include "kernels_misc.inl"
 #include "kernels_scalar.inl"
 #include "kernels_track.inl"
@@ -91,5 +92,6 @@ using namespace aclhip;
 #include "host_raw_tracks.inl"
 #include "host_raw_scalar_tracks.inl"
 #include "host_scalar_compress.inl"
+#include "host_transform_compress.inl"
 #include "host_bone_object.inl"
 #include "host_scalar_misc.inl"

@@ -59,6 +59,7 @@ EXPORTED_SYMBOLS = [
     "aclhip_check_raw_scalar_tracks", "aclhip_register_raw_scalar_tracks", "aclhip_unregister_raw_scalar_tracks", "aclhip_get_raw_scalar_tracks_info",
     "aclhip_sample_raw_scalar_tracks_batch", "aclhip_sample_raw_scalar_track_batch", "aclhip_measure_scalar_error_batch",
     "aclhip_scalar_compress_bound", "aclhip_scalar_compress_workspace_bytes", "aclhip_compress_raw_scalar_tracks_batch",
+    "aclhip_transform_compress_bound", "aclhip_transform_compress_workspace_bytes", "aclhip_compress_raw_tracks_batch",
 ]
 
 
@@ -261,8 +262,19 @@ class ScalarCompressDesc(ctypes.Structure):
     ]
 
 
+class TransformCompressDesc(ctypes.Structure):
+    """aclhip_transform_compress_desc; the four tables and the workspace are device addresses"""
+    _fields_ = [
+        ("flags", ctypes.c_uint32), ("max_tracks", ctypes.c_uint32), ("default_pose", ctypes.c_void_p), ("parent_indices", ctypes.c_void_p),
+        ("track_precisions", ctypes.c_void_p), ("track_shell_distances", ctypes.c_void_p), ("num_table_tracks", ctypes.c_uint32), ("precision", ctypes.c_float),
+        ("shell_distance", ctypes.c_float), ("workspace", ctypes.c_void_p), ("reserved", ctypes.c_uint64 * 2),
+    ]
+
+
 COMPRESS_OPTIMIZE_LOOPS = 1                                                                 # ACLHIP_COMPRESS_OPTIMIZE_LOOPS
+COMPRESS_INCLUDE_PARENT_TRACK_INDICES, COMPRESS_INCLUDE_TRACK_DESCRIPTIONS = 2, 4           # ACLHIP_COMPRESS_INCLUDE_* (the transform compressor's)
 COMPRESS_OK, COMPRESS_NOT_FINITE, COMPRESS_REFUSED = 0, 1, 2                                # aclhip_compress_result::status
+COMPRESS_NOT_NORMALIZED = 3                                                                 # (the transform compressor's)
 COMPRESS_RESULT_DTYPE = np.dtype([("status", np.uint32), ("size", np.uint32)])              # aclhip_compress_result as a numpy record
 MAX_RAW_SCALAR_TRACKS = 4096        # ACLHIP_MAX_RAW_SCALAR_TRACKS
 NO_TRACK = 0xFFFFFFFF               # ACLHIP_NO_TRACK
@@ -500,6 +512,11 @@ def load_library():
     lib.aclhip_scalar_compress_workspace_bytes.argtypes = [u32, u32]
     lib.aclhip_scalar_compress_workspace_bytes.restype = u64
     lib.aclhip_compress_raw_scalar_tracks_batch.argtypes = [vp, vp, u32, ctypes.POINTER(ScalarCompressDesc), vp, u64, vp, vp]
+    lib.aclhip_transform_compress_bound.argtypes = [u32, u32, u32]
+    lib.aclhip_transform_compress_bound.restype = u64
+    lib.aclhip_transform_compress_workspace_bytes.argtypes = [u32, u32]
+    lib.aclhip_transform_compress_workspace_bytes.restype = u64
+    lib.aclhip_compress_raw_tracks_batch.argtypes = [vp, vp, u32, ctypes.POINTER(TransformCompressDesc), vp, u64, vp, vp]
     _lib = lib
     return lib
 
@@ -1150,6 +1167,13 @@ class Context:
         self._check(self._lib.aclhip_compress_raw_scalar_tracks_batch(self._handle, raws_ptr, num_instances, ctypes.byref(desc) if desc is not None else None,
                                                                       blobs_ptr, blob_stride_bytes, results_ptr, stream))
 
+    def compress_raw_tracks_batch(self, raws_ptr, num_instances, desc, blobs_ptr, blob_stride_bytes, results_ptr, stream=None):
+        """aclhip_compress_raw_tracks_batch: compress_track_list with the reference's raw compression settings of the raw track arrays named
+        at raws_ptr (device uint32 [num_instances]) into the rows at blobs_ptr, one aclhip_compress_result per instance at results_ptr
+        (device addresses); `desc` is a TransformCompressDesc with its workspace."""
+        self._check(self._lib.aclhip_compress_raw_tracks_batch(self._handle, raws_ptr, num_instances, ctypes.byref(desc) if desc is not None else None,
+                                                               blobs_ptr, blob_stride_bytes, results_ptr, stream))
+
     def decompress_poses_mapped(self, clips, sample_times, skeletons, maps, num_bones, additive_format=ADDITIVE_NONE, object_space=False, base_clips=None,
                                 base_sample_times=None, base_maps=None, base_poses=None, params=None, out=None, instance_rounding=None, instance_looping=None,
                                 blend_clips=None, blend_sample_times=None, blend_maps=None, blend_weights=None, flags=0):
@@ -1705,6 +1729,77 @@ def compress_scalar_tracks(ctx, raws, precision=1.0e-5, track_precisions=None, o
             raise RuntimeError("Some samples are not finite")
         if status != COMPRESS_OK:
             raise ValueError(f"instance {i} (raw scalar track array {int(handles[i])}) was refused (ACLHIP_COMPRESS_REFUSED)")
+        blob = aligned_bytes(size)
+        blob[:] = rows[i, :size]
+        blobs.append(blob)
+    return blobs
+
+
+def transform_compress_bound(num_tracks, num_samples, flags=0):
+    """aclhip_transform_compress_bound (host only): the bytes a blob of such an array can take with these ACLHIP_COMPRESS_* flags, rounded up to 16"""
+    return int(load_library().aclhip_transform_compress_bound(int(num_tracks), int(num_samples), int(flags)))
+
+
+def transform_compress_workspace_bytes(num_instances, max_tracks):
+    """aclhip_transform_compress_workspace_bytes (host only)"""
+    return int(load_library().aclhip_transform_compress_workspace_bytes(int(num_instances), int(max_tracks)))
+
+
+def compress_raw_tracks(ctx, raws, default_pose=None, parents=None, precision=1.0e-4, shell_distance=1.0, track_precisions=None, track_shell_distances=None,
+                        include_parent_track_indices=False, include_track_descriptions=False):
+    """acl::compress_track_list with the reference's raw compression settings (quatf_full, vector3f_full, vector3f_full) for raw track
+    arrays as one launch: `raws` is a handle or a list of handles (register_raw_tracks; they may repeat and differ in shape). default_pose
+    float32 [tracks, 12] (QVV48; None: the identity), parents uint32 [tracks] (NO_PARENT for a root; None: every track a root),
+    track_precisions and track_shell_distances float32 [tracks] are shared by the arrays and hold at least as many tracks as the largest;
+    parents, precisions and shell distances only reach the optional metadata. Rows are sized from aclhip_transform_compress_bound, the
+    workspace is allocated, the results and the blobs are copied back: returns a list of 16 byte aligned numpy uint8 blobs, byte for
+    byte the reference's and lossless. Raises RuntimeError with the reference's message when a sample is not finite, ValueError when a
+    rotation is not normalized (ACLHIP_COMPRESS_NOT_NORMALIZED) or an instance is refused. Synchronous; the buffers are torch tensors on
+    the context's device."""
+    import torch
+    from .synth import aligned_bytes
+    device = torch.device("cuda", ctx.device_index)
+    handles = np.atleast_1d(np.asarray(raws, dtype=np.uint32))
+    infos = [ctx.raw_tracks_info(int(handle)) for handle in handles]
+    num_instances = len(handles)
+    if num_instances == 0:
+        return []
+    flags = (COMPRESS_INCLUDE_PARENT_TRACK_INDICES if include_parent_track_indices else 0) | (COMPRESS_INCLUDE_TRACK_DESCRIPTIONS if include_track_descriptions else 0)
+    stride = max(transform_compress_bound(info.num_tracks, info.num_samples, flags) for info in infos)
+    max_tracks = max(int(info.num_tracks) for info in infos)
+    stream = torch.cuda.current_stream(device)
+    d_raws = torch.from_numpy(handles.view(np.int32)).to(device)
+    d_blobs = torch.zeros((num_instances, stride), dtype=torch.uint8, device=device)
+    d_results = torch.zeros((num_instances, 2), dtype=torch.int32, device=device)
+    d_workspace = torch.zeros(transform_compress_workspace_bytes(num_instances, max_tracks) + 16, dtype=torch.uint8, device=device)
+    desc = TransformCompressDesc()
+    desc.flags, desc.max_tracks, desc.precision, desc.shell_distance = flags, max_tracks, float(precision), float(shell_distance)
+    desc.workspace = d_workspace.data_ptr()
+    tables = []         # (kept alive until the launch has run)
+    for field, table, dtype, width in (("default_pose", default_pose, np.float32, 12), ("parent_indices", parents, np.uint32, 1),
+                                       ("track_precisions", track_precisions, np.float32, 1), ("track_shell_distances", track_shell_distances, np.float32, 1)):
+        if table is None:
+            continue
+        host = np.ascontiguousarray(table, dtype=dtype).reshape(-1, width)
+        if tables and host.shape[0] != tables[0][1]:
+            raise ValueError("default_pose, parents, track_precisions and track_shell_distances hold the same number of tracks")
+        d_table = torch.from_numpy(host.view(np.int32) if dtype is np.uint32 else host).to(device)
+        tables.append((d_table, host.shape[0]))
+        setattr(desc, field, d_table.data_ptr())
+        desc.num_table_tracks = host.shape[0]
+    ctx.compress_raw_tracks_batch(d_raws.data_ptr(), num_instances, desc, d_blobs.data_ptr(), stride, d_results.data_ptr(), stream=stream.cuda_stream)
+    stream.synchronize()
+    results = d_results.cpu().numpy().view(np.uint32).reshape(num_instances, 2)
+    rows = d_blobs.cpu().numpy()
+    blobs = []
+    for i in range(num_instances):
+        status, size = int(results[i, 0]), int(results[i, 1])
+        if status == COMPRESS_NOT_FINITE:
+            raise RuntimeError("Some samples are not finite")
+        if status == COMPRESS_NOT_NORMALIZED:
+            raise ValueError(f"instance {i} (raw track array {int(handles[i])}) holds a rotation that is not normalized (ACLHIP_COMPRESS_NOT_NORMALIZED)")
+        if status != COMPRESS_OK:
+            raise ValueError(f"instance {i} (raw track array {int(handles[i])}) was refused (ACLHIP_COMPRESS_REFUSED)")
         blob = aligned_bytes(size)
         blob[:] = rows[i, :size]
         blobs.append(blob)

@@ -211,7 +211,9 @@ const char* aclhip_last_error_message(const aclhip_context* context);
  * scalar track arrays and the scalar track error -- aclhip_raw_scalar_tracks_info, aclhip_scalar_error_desc, the four raw scalar track
  * entry points, aclhip_sample_raw_scalar_tracks_batch, aclhip_sample_raw_scalar_track_batch and aclhip_measure_scalar_error_batch -- and
  * for the scalar compressor -- aclhip_scalar_compress_desc, aclhip_compress_result, aclhip_scalar_compress_bound,
- * aclhip_scalar_compress_workspace_bytes and aclhip_compress_raw_scalar_tracks_batch).
+ * aclhip_scalar_compress_workspace_bytes and aclhip_compress_raw_scalar_tracks_batch -- and for the raw-format transform compressor --
+ * aclhip_transform_compress_desc, aclhip_transform_compress_bound, aclhip_transform_compress_workspace_bytes and
+ * aclhip_compress_raw_tracks_batch).
  * A caller compiled against another header would hand over structs of another shape; aclhip_abi_version() says what the LIBRARY was
  * built with, and the C++ mirror (aclhip.hpp) refuses to create a context when the two differ. */
 #define ACLHIP_ABI_VERSION 6u
@@ -1842,7 +1844,8 @@ uint64_t aclhip_scalar_compress_workspace_bytes(uint32_t num_instances, uint32_t
  * the vote per instance; the analysis, one wave per (instance, track); the layout, one wave per instance, which also stores headers,
  * metadata, constants and ranges; the bit stream, one lane per output dword gathering the values that fall into it (no atomics: the
  * same bytes on every run); the hash, serial in the bytes of a blob, one wave per blob with the chain on the scalar unit.
- *   Left out (nothing here precludes them): the transform (qvvf) compressor; the optional metadata sections (names, descriptions);
+ *   Left out (nothing here precludes them): the variable bit rates of the transform (qvvf) compressor (its raw formats exist:
+ * aclhip_compress_raw_tracks_batch, below); the optional metadata sections (names, descriptions) for scalar lists;
  * output_index remapping and stripped tracks; registering a clip straight from a device blob (aclhip_register_clip takes a host
  * pointer: runtime.compress_scalar_tracks copies back); the C++ mirror in aclhip.hpp; instance lists.
  *   What it costs (no time is promised; one MI355X, 4 096 instances over 256 distinct float1f arrays of 256 tracks x 120 samples -- the
@@ -1854,6 +1857,102 @@ uint64_t aclhip_scalar_compress_workspace_bytes(uint32_t num_instances, uint32_t
 aclhip_status aclhip_compress_raw_scalar_tracks_batch(aclhip_context* context,
 	const aclhip_raw_scalar_tracks* raws /* DEVICE [num_instances] */, uint32_t num_instances,
 	const aclhip_scalar_compress_desc* desc, void* blobs /* DEVICE */, uint64_t blob_stride_bytes,
+	aclhip_compress_result* results /* DEVICE [num_instances] */, void* stream);
+
+/* ---- compress_track_list for raw track arrays, raw formats ---------------------------------------------------------------------------------
+ * acl::compress_track_list for a track_array_qvvf with the reference's RAW compression settings -- rotation_format = quatf_full,
+ * translation_format = scale_format = vector3f_full: get_raw_compression_settings() (compression/impl/compress.transform.impl.h:138-530
+ * and the files it calls) --, batched: a registered raw track array becomes a LOSSLESS `compressed_tracks` blob where it lives, one that
+ * every consumer of this library takes. With these settings the reference segments nothing, reduces no range, takes no looping vote,
+ * tests constant and default sub-tracks binary and stores every animated sample as its own 32 bit words; what remains is the transform
+ * blob writer. THE BLOB IS BYTE FOR BYTE THE REFERENCE'S for the same samples and settings, hash included; the tests hold every byte.
+ *   Instance i compresses array raws[i] into (char*)blobs + i * blob_stride_bytes; blobs and the stride are 16 byte aligned. The launch
+ * writes every byte of [0, size) itself -- padding and the 15 trailing zero bytes included -- and touches nothing behind `size`. Handles
+ * may repeat; arrays of different shapes share a launch. results[i] = { status, size } says how it went (aclhip_compress_result). */
+#define ACLHIP_COMPRESS_INCLUDE_PARENT_TRACK_INDICES 2u   /* compression_settings::metadata.include_parent_track_indices */
+#define ACLHIP_COMPRESS_INCLUDE_TRACK_DESCRIPTIONS 4u     /* ...include_track_descriptions; implies the parent indices, as in the reference */
+#define ACLHIP_COMPRESS_NOT_NORMALIZED 3u                 /* aclhip_compress_result::status: a rotation fails rtm::quat_is_normalized: size 0, row untouched */
+
+typedef struct aclhip_transform_compress_desc
+{
+	uint32_t flags;                        /*  0  ACLHIP_COMPRESS_INCLUDE_PARENT_TRACK_INDICES, ACLHIP_COMPRESS_INCLUDE_TRACK_DESCRIPTIONS;
+	                                              ACLHIP_COMPRESS_OPTIMIZE_LOOPS is accepted and changes nothing (the reference's rule for raw settings) */
+	uint32_t max_tracks;                   /*  4  tracks the workspace was sized for; an instance with more is refused */
+	const void* default_pose;              /*  8  DEVICE or NULL: QVV48 record b = track_desc_transformf::default_value of track b, shared by the
+	                                              launch, 16 byte aligned; NULL = identity / zero / one */
+	const uint32_t* parent_indices;        /* 16  DEVICE or NULL (every track a root): desc.parent_index, ACLHIP_NO_PARENT for a root; metadata only */
+	const float* track_precisions;         /* 24  DEVICE or NULL (-> precision): metadata only */
+	const float* track_shell_distances;    /* 32  DEVICE or NULL (-> shell_distance): metadata only */
+	uint32_t num_table_tracks;             /* 40  entries of every non-NULL table above */
+	float precision;                       /* 44  reference default 0.0001F */
+	float shell_distance;                  /* 48  reference default 1.0F; 4 bytes of padding follow */
+	void* workspace;                       /* 56  DEVICE, 16 byte aligned, aclhip_transform_compress_workspace_bytes(num_instances, max_tracks) bytes */
+	uint64_t reserved[2];                  /* 64  0 */
+} aclhip_transform_compress_desc;          /* 80 bytes */
+
+/* Host only. The bound of a blob: 100 + 12 * ceil(T / 16) + 40 * T * S + (with metadata: 4 * T, + 48 * T with descriptions, + 20; without:
+ * 15), rounded up to 16 -- headers, sub-track types, every sub-track animated, metadata or the tail; computed 128 bits wide and capped at
+ * the largest multiple of 16, so absurd counts do not wrap. The workspace holds what the launches of one call hand to each other (64
+ * bytes per instance, 1 + 6 per instance and track, each part rounded up to 16); its contents before and after a call mean nothing. */
+uint64_t aclhip_transform_compress_bound(uint32_t num_tracks, uint32_t num_samples, uint32_t flags);
+uint64_t aclhip_transform_compress_workspace_bytes(uint32_t num_instances, uint32_t max_tracks);
+
+/* The definition. The array has T tracks and S samples of QVV48 records; the USED LANES of a record are the four of the rotation and xyz
+ * of translation and scale. The fourth lanes of translations and scales are never read, neither of the samples nor of default_pose. (The
+ * reference compares all four lanes of its vector4f; a caller's array says nothing about the fourth. This call is the reference for track
+ * arrays and default values whose fourth lanes agree, which is what rtm::vector_load3 and rtm::vector_set(x, y, z) make.)
+ *   1. Checks over the registered samples. Every used lane must be finite, or the status is ACLHIP_COMPRESS_NOT_FINITE (the reference's
+ *      "Some samples are not finite"). Every rotation must pass rtm::quat_is_normalized: fabs(((x * x + z * z) + (y * y + w * w)) - 1.0F)
+ *      < 0.00001F, fp32, one IEEE operation at a time in this order (rtm::vector_dot), or the status is ACLHIP_COMPRESS_NOT_NORMALIZED:
+ *      the reference renormalizes such a rotation (clip_context.impl.h:147-153) through rtm::quat_normalize, which starts from the x86
+ *      reciprocal square root estimate -- not bit-reproducible between CPU vendors --, and this call promises bytes; it does
+ *      not normalize some other way. NOT_FINITE wins when both hold: the reference tests finiteness on the value it would store.
+ *   2. Looping. Nothing is removed (optimize_looping returns at once for raw settings). An array registered with ACLHIP_LOOP_WRAP keeps S
+ *      and sets the header's wrap-optimized bit (clip_context.impl.h:87,103, compress.transform.impl.h:427).
+ *   3. Per sub-track (compact.transform.h:213-346, track_stream.h:373-381): CONSTANT iff every sample compares equal (==, so -0 == +0) to
+ *      sample 0 in every used lane; DEFAULT iff it is constant and sample 0 compares equal to the default value in every used lane. A
+ *      default sub-track stores nothing; a constant one the bytes of sample 0, 16 for a rotation and 12 otherwise; the others are ANIMATED.
+ *   4. has_scale is false iff every scale sub-track is default; then the scale third of the sub-track types and the scale data are absent.
+ *   5. The blob (compress.transform.impl.h:287-530, write_segment_data.h, write_sub_track_types.h, write_stream_data.h): raw_buffer_header
+ *      { size, hash }; tracks_header { the compressed_tracks tag, version 10 (latest), uniformly_sampled, qvvf, T, S, the sample rate, the
+ *      packed word: has_scale, default scale 1, the three full formats, no database, no trivial default values (the reference asks
+ *      quat_near_identity with a threshold of 0, which holds for no rotation), no stripped key frames, wrap optimized, has metadata };
+ *      transform_tracks_header { one segment, no variable sub-tracks, the three animated and the three constant counts, no database, the
+ *      offsets from its own start }; one segment_header { the bits of one animated pose, of its rotations, of its translations, the
+ *      offset of the segment's data }; the sub-track types, 2 bits each (0 default, 1 constant, 2 animated), 16 per 32 bit word with the
+ *      first track in the top bits, rotations, then translations, then scales, each type starting a new word; the constant data:
+ *      rotations, translations, scales, each in track order; no range data and no per-track format data; the animated stream: per sample
+ *      ascending the animated rotations xyzw, the translations xyz, the scales xyz, each in track order (output_index is the identity),
+ *      every float as a 32 bit word, most significant byte first.
+ *   6. Metadata (write_track_metadata.h:106-194), with either flag: T parent indices (parent_indices[b] when it is < T, else
+ *      ACLHIP_NO_PARENT); with ACLHIP_COMPRESS_INCLUDE_TRACK_DESCRIPTIONS 12 floats per track: precision, shell distance, the default
+ *      rotation xyzw, translation xyz, scale xyz; the optional_metadata_header { no list name, no track names, the two offsets from the
+ *      blob's start, no contributing error } ends the blob. Without metadata the blob ends in 15 zero bytes.
+ *   7. size is the total, hash is FNV-1a 32 (core/hash.h) over [8, size).
+ *   compression_settings::level, precision and shell_distance change no byte outside the descriptions.
+ *   Refused per instance (ACLHIP_COMPRESS_REFUSED, counted by aclhip_get_rejected_instance_count, decided in front of any write to the
+ * row): an unknown or retired handle (0 included); T > max_tracks; any table given and T > num_table_tracks; a blob larger than
+ * blob_stride_bytes; an animated stream of 2^32 bits or more (the reference counts them in 32 bits).
+ *   ACLHIP_ERROR_INVALID_ARGUMENT, decided before any device call, each with a message (with or without a context): raws, desc, blobs,
+ * results or desc->workspace == NULL; blobs, the stride, the workspace or default_pose not 16 byte aligned; a stride of 0; results not 8
+ * byte aligned; a table not 4 byte aligned; unknown flags or reserved fields that are not 0; a precision or a shell distance that is
+ * negative or not finite; a table given with num_table_tracks == 0; max_tracks == 0; the blob rows, the results or the workspace
+ * overlapping one another, raws or a table.
+ *   The call is stream ordered, uploads nothing and can be captured into a graph. Four launches (DESIGN.md 4.7 "Transform compression
+ * (raw formats)"): the analysis, one wave per (instance, track), which leaves one flag byte per track and uses no atomics; the layout,
+ * one wave per instance, which decides the statuses and the refusal and stores headers, sub-track types, constants, metadata and the
+ * tail; the stream, one lane per output dword (one 4 byte load, a byte swap, one coalesced store); the scalar compressor's hash.
+ *   Left out (nothing here precludes them): the variable formats and everything they need (segmenting, range reduction, the bit rate
+ * search, the error metric over the hierarchy); quatf_drop_w_full; additive bases; track and list names; output_index remapping and
+ * stripped tracks; a flag that normalizes rotations within a tolerance; the C++ mirror in aclhip.hpp.
+ *   What it costs (no time is promised; one MI355X, 4 096 instances over 256 distinct arrays of 100 tracks x 301 samples -- the bench's
+ * pose shape, 91 % of the rotations, a third of the translations and a tenth of the scales animated: 5.92 GB of samples, 2.43 GB of
+ * blobs --; medians of three interleaved rounds of 20 launches; tools/transform_compress.py, profiles/transform_compress.md, DESIGN.md 4.7
+ * "Transform compression (raw formats)"): 22.8 ms a batch, 5.6 us an array, next to the reference's compress_track_list over the same
+ * instances on the same box: 35.5 s on one thread, 2.36 s on 16. By phase: analysis 1 098 us (5 %), layout 8 us, stream 1 966 us (9 %),
+ * hash 19 692 us (87 %): 594 KB of serial chain per blob. The hash is the call, and nothing was built against that. */
+aclhip_status aclhip_compress_raw_tracks_batch(aclhip_context* context, const aclhip_raw_tracks* raws /* DEVICE [num_instances] */,
+	uint32_t num_instances, const aclhip_transform_compress_desc* desc, void* blobs /* DEVICE */, uint64_t blob_stride_bytes,
 	aclhip_compress_result* results /* DEVICE [num_instances] */, void* stream);
 
 /* ---- multi-GPU ---------------------------------------------------------------------------------- */
