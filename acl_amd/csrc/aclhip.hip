@@ -17,7 +17,7 @@
 //   sample_raw_scalar_tracks_kernel    uncompressed scalar curve sets (raw scalar track arrays): one lane per float of the value row (four floats where row and key frames are 16 byte aligned), two loads, one store.
 //   sample_raw_scalar_track_kernel     the same arrays, one thread per (instance, track) request.
 //   measure_scalar_error_kernel        the scalar track error of two value buffers: one wave64 per instance, lanes <-> tracks.
-//   scalar_compress_*_kernel           compress_track_list of raw scalar track arrays in five launches: vote, per-track analysis (one wave64 per track), layout, bit stream (one lane per output dword), hash.
+//   scalar_compress_*_kernel           compress_track_list of raw scalar track arrays in five launches: vote, per-track analysis (one wave64 per track), layout, bit stream (one lane per output dword), hash (compress_hash_kernel, the transform compressor's too).
 //   decompress_track_kernel            one thread per (instance, bone) request; the registration time plan replaces the
 //                                      reference's O(track index) skip over preceding widths.
 //   decompress_scalar_tracks_kernel    scalar track lists: one wave64 per (instance, 256 tracks), lanes <-> tracks.
@@ -34,6 +34,7 @@
 #include <dlfcn.h>
 
 #include <algorithm>
+#include <climits>
 #include <cmath>
 #include <cstdarg>
 #include <cstdio>
@@ -87,6 +88,7 @@ using namespace aclhip;
 #include "host_consumers.inl"
 #include "host_skeletons.inl"
 #include "host_blend_masks.inl"
+#include "host_ranges.inl"
 #include "host_pose_buffers.inl"
 #include "host_skins.inl"
 #include "host_raw_tracks.inl"

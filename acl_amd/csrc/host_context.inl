@@ -62,7 +62,8 @@ namespace
 namespace
 {
 	// The handles of one kind of object that launches name by number: track maps, skeletons, blend masks, skins, raw track arrays and raw scalar track arrays
-	// (host_track_maps.inl, host_skeletons.inl, host_blend_masks.inl, host_skins.inl, host_raw_tracks.inl, host_raw_scalar_tracks.inl; used six times in aclhip_context). The device table is ONE allocation of kCapacity records
+	// (host_track_maps.inl, host_skeletons.inl, host_blend_masks.inl, host_skins.inl, and host_raw_tracks.inl for both kinds of raw array:
+	// register_raw_array; used six times in aclhip_context). The device table is ONE allocation of kCapacity records
 	// made at the first registration: it never moves and never grows (launches in flight and captured hipGraphs hold its address), a
 	// cleared record is an unknown handle, and record 0 is never handed out (0 is the null handle). What works on a table -- take_handle,
 	// publish_handle, unregister_handle, get_handle_info -- is below, behind the upload and retire functions it calls.

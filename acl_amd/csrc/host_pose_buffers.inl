@@ -5,18 +5,6 @@
 
 namespace
 {
-	// do [a, a + a_stride * n) and [b, b + b_stride * n) share a byte? (a product past 2^64 ends at the top of the address space)
-	bool pose_ranges_overlap(const void* a, uint64_t a_stride, const void* b, uint64_t b_stride, uint32_t num_instances)
-	{
-		const auto end_of = [&](const void* pointer, uint64_t stride)
-		{
-			const unsigned __int128 end = (unsigned __int128)reinterpret_cast<uintptr_t>(pointer) + (unsigned __int128)stride * num_instances;
-			return end > (unsigned __int128)UINT64_MAX ? UINT64_MAX : uint64_t(end);
-		};
-		const uint64_t a_begin = reinterpret_cast<uintptr_t>(a), b_begin = reinterpret_cast<uintptr_t>(b);
-		return a_begin < end_of(b, b_stride) && b_begin < end_of(a, a_stride);
-	}
-
 	// The rows alone set the shape of the launch (the output rows when there are any): an image's quads, and the words of the walk schedule on
 	// top of them once the context is known (launch_pose_buffers; the argument check asks without them). Refuses rows that do not fit.
 	aclhip_status pose_buffer_launch_shape_of(aclhip_context* context, const void* poses, uint64_t pose_stride_bytes, uint64_t local_pose_stride_bytes, bool object_space,
@@ -363,15 +351,6 @@ namespace
 
 	// ---- the shell error of two pose buffers (aclhip_measure_pose_error_batch; measure_pose_error_kernel) ---------------------------------
 
-	// do [a, a + a_bytes) and [b, b + b_bytes) share a byte? (an empty range shares none; an end past 2^64 is the top of the address space)
-	bool byte_ranges_overlap(const void* a, unsigned __int128 a_bytes, const void* b, unsigned __int128 b_bytes)
-	{
-		if (a_bytes == 0 || b_bytes == 0)
-			return false;
-		const unsigned __int128 a_begin = reinterpret_cast<uintptr_t>(a), b_begin = reinterpret_cast<uintptr_t>(b);
-		return a_begin < b_begin + b_bytes && b_begin < a_begin + a_bytes;
-	}
-
 	// The two input rows set the shape of the launch: an image's quads from the smaller stride, two images per instance, and the words of the
 	// walk schedule on top of them once the context is known. Refuses rows that do not fit.
 	aclhip_status pose_error_launch_shape_of(aclhip_context* context, uint64_t raw_pose_stride_bytes, uint64_t lossy_pose_stride_bytes, bool object_space,
@@ -424,29 +403,19 @@ namespace
 			return shape_status;
 
 		// raw, lossy and base are only read and may overlap each other freely; what is written overlaps nothing that is read and no other output
-		struct byte_range { const char* name; const void* pointer; unsigned __int128 bytes; };
 		const unsigned __int128 n = num_instances;
-		const byte_range inputs[] = {
-			{ "the raw pose rows", raw_poses, n * raw_pose_stride_bytes }, { "the lossy pose rows", lossy_poses, n * lossy_pose_stride_bytes },
-			{ "the base pose rows", desc->base_poses, has_base ? n * desc->base_pose_stride_bytes : 0 },
-			{ "the skeleton list", desc->instance_skeletons, desc->instance_skeletons != nullptr ? n * sizeof(aclhip_skeleton) : 0 },
-			{ "the shell distances", desc->shell_distances, desc->shell_distances != nullptr ? (unsigned __int128)desc->num_shell_distances * sizeof(float) : 0 },
-		};
-		const byte_range outputs[] = {
-			{ "the pose error records", errors, n * sizeof(aclhip_pose_error) },
-			{ "the bone errors", desc->bone_errors, desc->bone_errors != nullptr ? n * desc->bone_error_stride_bytes : 0 },
-			{ "the worst record", desc->worst, desc->worst != nullptr ? sizeof(aclhip_pose_error_worst) : 0 },
-		};
-		for (size_t o = 0; o < std::size(outputs); ++o)
-		{
-			for (const byte_range& input : inputs)
-				if (byte_ranges_overlap(outputs[o].pointer, outputs[o].bytes, input.pointer, input.bytes))
-					return fail(context, ACLHIP_ERROR_INVALID_ARGUMENT, "%s overlap %s", outputs[o].name, input.name);
-			for (size_t other = o + 1; other < std::size(outputs); ++other)
-				if (byte_ranges_overlap(outputs[o].pointer, outputs[o].bytes, outputs[other].pointer, outputs[other].bytes))
-					return fail(context, ACLHIP_ERROR_INVALID_ARGUMENT, "%s overlap %s", outputs[o].name, outputs[other].name);
-		}
-		return ACLHIP_OK;
+		return check_no_overlap(context,
+			{
+				{ "the pose error records", errors, n * sizeof(aclhip_pose_error) },
+				{ "the bone errors", desc->bone_errors, desc->bone_errors != nullptr ? n * desc->bone_error_stride_bytes : 0 },
+				{ "the worst record", desc->worst, desc->worst != nullptr ? sizeof(aclhip_pose_error_worst) : 0 },
+			},
+			{
+				{ "the raw pose rows", raw_poses, n * raw_pose_stride_bytes }, { "the lossy pose rows", lossy_poses, n * lossy_pose_stride_bytes },
+				{ "the base pose rows", desc->base_poses, has_base ? n * desc->base_pose_stride_bytes : 0 },
+				{ "the skeleton list", desc->instance_skeletons, desc->instance_skeletons != nullptr ? n * sizeof(aclhip_skeleton) : 0 },
+				{ "the shell distances", desc->shell_distances, desc->shell_distances != nullptr ? (unsigned __int128)desc->num_shell_distances * sizeof(float) : 0 },
+			});
 	}
 
 	template<class kernel_type>

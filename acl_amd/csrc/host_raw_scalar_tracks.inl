@@ -83,45 +83,15 @@ extern "C" aclhip_status aclhip_register_raw_scalar_tracks(aclhip_context* conte
 		return fail(context, ACLHIP_ERROR_INVALID_ARGUMENT, "%s", message);
 	if (context == nullptr)
 		return fail(context, ACLHIP_ERROR_INVALID_ARGUMENT, "null context");
-	return guarded(context, [&]() -> aclhip_status
-	{
-		const size_t image_bytes = size_t(num_samples) * num_tracks * info.num_components * 4;
-
-		std::lock_guard<std::shared_mutex> lock(context->mutex);
-		device_guard guard(context->device);
-		collect_retired(context, false);
-
-		uint32_t slot;
-		if (const aclhip_status status = take_handle(context, context->raw_scalar_tracks, slot); status != ACLHIP_OK)
-			return status;
-
-		uint8_t* d_image = allocate_clip_memory(context, image_bytes);
-		if (d_image == nullptr)
-		{
-			context->raw_scalar_tracks.give_back(slot);
-			return fail(context, ACLHIP_ERROR_OUT_OF_MEMORY, "allocating %zu bytes for the raw scalar track array failed", image_bytes);
-		}
-		device_raw_scalar_tracks record;
-		std::memset(&record, 0, sizeof(record));
-		record.samples = reinterpret_cast<const float*>(d_image);
-		record.num_tracks = num_tracks;
-		record.num_samples = num_samples;
-		record.sample_rate = sample_rate;
-		record.duration = info.duration;
-		record.looping_policy = looping_policy | (track_type << 8);
-		record.num_components = info.num_components;
-		size_t staging_used = 0;
-		// the image first, as the caller laid it out, and the record that publishes it behind it
-		if (!stage_upload(context, d_image, samples, image_bytes, staging_used)
-			|| !publish_handle(context, context->raw_scalar_tracks, slot, record, staging_used, info, d_image))
-		{
-			free_clip_memory(context, d_image);
-			context->raw_scalar_tracks.give_back(slot);
-			return fail(context, ACLHIP_ERROR_DEVICE, "uploading the raw scalar track array failed");
-		}
-		*out_raw = slot;
-		return ACLHIP_OK;
-	});
+	device_raw_scalar_tracks record;
+	std::memset(&record, 0, sizeof(record));
+	record.num_tracks = num_tracks;
+	record.num_samples = num_samples;
+	record.sample_rate = sample_rate;
+	record.duration = info.duration;
+	record.looping_policy = looping_policy | (track_type << 8);
+	record.num_components = info.num_components;
+	return register_raw_array(context, context->raw_scalar_tracks, samples, size_t(num_samples) * num_tracks * info.num_components * 4, record, info, out_raw);
 }
 
 extern "C" aclhip_status aclhip_unregister_raw_scalar_tracks(aclhip_context* context, aclhip_raw_scalar_tracks raw)
@@ -140,134 +110,67 @@ extern "C" aclhip_status aclhip_get_raw_scalar_tracks_info(const aclhip_context*
 
 namespace
 {
-	// ---- sampling a batch of raw scalar track arrays (both launches) -----------------------------------------------------------------------
+	// ---- sampling a batch of raw scalar track arrays (both launches; their checks and their front are sample_raw's, host_raw_tracks.inl) ---
 
-	// What both launches check of their arguments before any device call; every refusal leaves a message, with or without a context.
-	// `track_indices` belongs to the single-track form (single_track).
-	aclhip_status check_raw_scalar_sample(aclhip_context* context, const aclhip_raw_scalar_tracks* raws, const float* sample_times, const uint32_t* track_indices, bool single_track,
-		uint32_t num_instances, const aclhip_raw_sample_desc& desc, const void* values, uint64_t stride_bytes)
-	{
-		if (raws == nullptr)
-			return fail(context, ACLHIP_ERROR_INVALID_ARGUMENT, "null raw scalar track handles");
-		if (sample_times == nullptr)
-			return fail(context, ACLHIP_ERROR_INVALID_ARGUMENT, "null sample times");
-		if (single_track && track_indices == nullptr)
-			return fail(context, ACLHIP_ERROR_INVALID_ARGUMENT, "null track indices");
-		if (values == nullptr)
-			return fail(context, ACLHIP_ERROR_INVALID_ARGUMENT, "null value buffer");
-		if ((reinterpret_cast<uintptr_t>(values) & 3u) != 0 || (stride_bytes & 3u) != 0 || stride_bytes == 0)
-			return fail(context, ACLHIP_ERROR_INVALID_ARGUMENT, "the value buffer and its stride must be 4 byte aligned, and the stride is not 0");
-		if (desc.rounding_policy > ACLHIP_ROUND_PER_TRACK)
-			return fail(context, ACLHIP_ERROR_INVALID_ARGUMENT, "unknown rounding policy %u", uint32_t(desc.rounding_policy));
-		if (desc.rounding_policy == ACLHIP_ROUND_PER_TRACK && desc.track_rounding_policies == nullptr)
-			return fail(context, ACLHIP_ERROR_INVALID_ARGUMENT, "ACLHIP_ROUND_PER_TRACK needs track_rounding_policies");
-		if (desc.track_rounding_policies != nullptr && desc.num_track_rounding_policies == 0)
-			return fail(context, ACLHIP_ERROR_INVALID_ARGUMENT, "track_rounding_policies with a count of 0");
-		bool reserved_clear = desc.reserved1 == 0 && desc.reserved[0] == 0 && desc.reserved[1] == 0;
-		for (const uint8_t byte : desc.reserved0)
-			reserved_clear = reserved_clear && byte == 0;
-		if (!reserved_clear)
-			return fail(context, ACLHIP_ERROR_INVALID_ARGUMENT, "the reserved fields of a raw sample desc are 0");
-		// the rows are written while every array of the launch is read (with `rows` the output range is still taken as num_instances rows)
-		if (pose_ranges_overlap(values, stride_bytes, raws, sizeof(aclhip_raw_scalar_tracks), num_instances))
-			return fail(context, ACLHIP_ERROR_INVALID_ARGUMENT, "the value rows overlap the raw scalar track handles");
-		if (pose_ranges_overlap(values, stride_bytes, sample_times, sizeof(float), num_instances))
-			return fail(context, ACLHIP_ERROR_INVALID_ARGUMENT, "the value rows overlap the sample times");
-		if (single_track && pose_ranges_overlap(values, stride_bytes, track_indices, sizeof(uint32_t), num_instances))
-			return fail(context, ACLHIP_ERROR_INVALID_ARGUMENT, "the value rows overlap the track indices");
-		if (desc.instance_rounding_policies != nullptr && pose_ranges_overlap(values, stride_bytes, desc.instance_rounding_policies, 1, num_instances))
-			return fail(context, ACLHIP_ERROR_INVALID_ARGUMENT, "the value rows overlap the instance rounding policies");
-		if (desc.rows != nullptr && pose_ranges_overlap(values, stride_bytes, desc.rows, sizeof(uint32_t), num_instances))
-			return fail(context, ACLHIP_ERROR_INVALID_ARGUMENT, "the value rows overlap the row list");
-		if (desc.track_rounding_policies != nullptr
-			&& byte_ranges_overlap(values, (unsigned __int128)stride_bytes * num_instances, desc.track_rounding_policies, desc.num_track_rounding_policies))
-			return fail(context, ACLHIP_ERROR_INVALID_ARGUMENT, "the value rows overlap the track rounding policies");
-		return ACLHIP_OK;
-	}
+	constexpr const char* k_raw_scalar_alignment_message = "the value buffer and its stride must be 4 byte aligned, and the stride is not 0";
+	constexpr raw_sample_kind k_raw_scalar_tracks_sample = { "raw scalar track", "value", 4, true, k_raw_scalar_alignment_message, sizeof(aclhip_raw_scalar_tracks), false };
+	constexpr raw_sample_kind k_raw_scalar_track_sample = { "raw scalar track", "value", 4, true, k_raw_scalar_alignment_message, sizeof(aclhip_raw_scalar_tracks), true };
 
 	// The launches. The whole-list one is shaped by its rows alone: a row of stride_bytes holds at most stride_bytes / 4 floats, and a wave
 	// takes up to k_raw_scalar_elements_per_lane of them per lane (in turns of one float per lane, or of four where the 16 byte path is taken) (launch_raw_sample, host_raw_tracks.inl, says why a wave loops);
-	// which arrays the instances name is the kernel's business. The single-track one is a thread per request. The table is filled in under
-	// the registry lock; nothing is uploaded.
-	aclhip_status launch_raw_scalar_sample(aclhip_context* context, const aclhip_raw_scalar_tracks* raws, const float* sample_times, const uint32_t* track_indices, bool single_track,
+	// which arrays the instances name is the kernel's business. The single-track one (`track_indices`) is a thread per request. The table
+	// is filled in under the registry lock; nothing is uploaded.
+	aclhip_status launch_raw_scalar_sample(aclhip_context* context, const aclhip_raw_scalar_tracks* raws, const float* sample_times, const uint32_t* track_indices,
 		uint32_t num_instances, const aclhip_raw_sample_desc& desc, void* values, uint64_t stride_bytes, hipStream_t stream)
 	{
 		std::shared_lock<std::shared_mutex> lock(context->mutex);		// see launch_tracks
-		if (context->raw_scalar_tracks.d_records == nullptr)
-			return fail(context, ACLHIP_ERROR_INVALID_ARGUMENT, "no raw scalar track array was ever registered with this context");
-		note_launch_stream(context, stream);
+		if (const aclhip_status status = begin_raw_launch(context, context->raw_scalar_tracks, stream); status != ACLHIP_OK)
+			return status;
 
-		raw_scalar_sample_launch launch = {};
-		launch.arrays = context->raw_scalar_tracks.d_records;
-		launch.num_arrays = ACLHIP_MAX_RAW_SCALAR_TRACKS;
-		launch.num_instances = num_instances;
-		launch.raws = raws;
-		launch.sample_times = sample_times;
+		raw_scalar_sample_launch launch = raw_sample_launch_of<raw_scalar_sample_launch>(context, context->raw_scalar_tracks, raws, sample_times, num_instances, desc);
 		launch.track_indices = track_indices;
-		launch.rows = desc.rows;
-		launch.instance_rounding_policies = desc.instance_rounding_policies;
-		launch.track_rounding_policies = desc.track_rounding_policies;
-		launch.num_track_rounding_policies = desc.track_rounding_policies != nullptr ? desc.num_track_rounding_policies : 0u;
-		launch.rounding_policy = desc.rounding_policy;
 		launch.values = static_cast<uint8_t*>(values);
 		launch.stride_bytes = stride_bytes;
-		launch.waves_per_instance = 1;
 		// measurement knob: the dword path for every row (what the 16 byte path buys: tools/raw_scalar_tracks.py, profiles/raw_scalar_tracks.md)
 		static const bool dword_only = []() { const char* value = lab_knob("ACLHIP_RAW_SCALAR_DWORD"); return value != nullptr && value[0] == '1'; }();
 		launch.dword_only = dword_only ? 1u : 0u;
-		launch.rejected_count = context->d_rejected;
 
-		if (single_track)
+		if (track_indices != nullptr)
 		{
 			constexpr uint32_t block_size = k_raw_scalar_waves_per_block * k_wave_size;
 			hipLaunchKernelGGL(sample_raw_scalar_track_kernel, dim3((num_instances + block_size - 1) / block_size), dim3(block_size), 0, stream, launch);
 		}
 		else
 		{
-			// (an array holds at most 0xFFFF tracks of 4 floats; the wave index of the kernel is 32 bits wide: a batch too large for its share of waves loops)
+			// (an array holds at most 0xFFFF tracks of 4 floats)
 			const uint64_t row_elements = std::min<uint64_t>(stride_bytes / 4, uint64_t(0xFFFFu) * 4);
-			constexpr uint64_t elements_per_wave = uint64_t(k_wave_size) * k_raw_scalar_elements_per_lane;
-			uint64_t waves_per_instance = std::max<uint64_t>((row_elements + elements_per_wave - 1) / elements_per_wave, 1);
-			waves_per_instance = std::min<uint64_t>(waves_per_instance, std::max<uint64_t>(0xFFFFFFF0ull / num_instances, 1));
-			launch.waves_per_instance = uint32_t(waves_per_instance);
-			const uint64_t num_waves = uint64_t(num_instances) * waves_per_instance;
+			launch.waves_per_instance = waves_per_instance_of(row_elements, uint64_t(k_wave_size) * k_raw_scalar_elements_per_lane, num_instances);
+			const uint64_t num_waves = uint64_t(num_instances) * launch.waves_per_instance;
 			const uint32_t num_blocks = uint32_t((num_waves + k_raw_scalar_waves_per_block - 1) / k_raw_scalar_waves_per_block);
 			hipLaunchKernelGGL(sample_raw_scalar_tracks_kernel, dim3(num_blocks), dim3(k_raw_scalar_waves_per_block * k_wave_size), 0, stream, launch);
 		}
 		ACLHIP_CHECK_HIP(context, hipGetLastError());
 		return ACLHIP_OK;
 	}
-
-	aclhip_status sample_raw_scalar(aclhip_context* context, const aclhip_raw_scalar_tracks* raws, const float* sample_times, const uint32_t* track_indices, bool single_track,
-		uint32_t num_instances, const aclhip_raw_sample_desc* desc, void* values, uint64_t stride_bytes, void* stream)
-	{
-		aclhip_raw_sample_desc local = {};		// NULL: ROUND_NONE, row i
-		if (desc != nullptr)
-			local = *desc;
-		const aclhip_status status = check_raw_scalar_sample(context, raws, sample_times, track_indices, single_track, num_instances, local, values, stride_bytes);
-		if (status != ACLHIP_OK)
-			return status;
-		if (context == nullptr)
-			return fail(context, ACLHIP_ERROR_INVALID_ARGUMENT, "null context");
-		if (num_instances == 0)
-			return ACLHIP_OK;
-
-		device_guard guard(context->device);
-		return launch_raw_scalar_sample(context, raws, sample_times, track_indices, single_track, num_instances, local, values, stride_bytes, static_cast<hipStream_t>(stream));
-	}
 }
 
-// include/aclhip.h states the definitions. The argument checks need no device, come first and leave a message, with or without a context.
+// include/aclhip.h states the definitions
 extern "C" aclhip_status aclhip_sample_raw_scalar_tracks_batch(aclhip_context* context, const aclhip_raw_scalar_tracks* raws, const float* sample_times, uint32_t num_instances,
 	const aclhip_raw_sample_desc* desc, void* values, uint64_t stride_bytes, void* stream)
 {
-	return sample_raw_scalar(context, raws, sample_times, nullptr, false, num_instances, desc, values, stride_bytes, stream);
+	return sample_raw(context, k_raw_scalar_tracks_sample, raws, sample_times, nullptr, num_instances, desc, values, stride_bytes, [&](const aclhip_raw_sample_desc& local)
+	{
+		return launch_raw_scalar_sample(context, raws, sample_times, nullptr, num_instances, local, values, stride_bytes, static_cast<hipStream_t>(stream));
+	});
 }
 
 extern "C" aclhip_status aclhip_sample_raw_scalar_track_batch(aclhip_context* context, const aclhip_raw_scalar_tracks* raws, const float* sample_times, const uint32_t* track_indices,
 	uint32_t num_instances, const aclhip_raw_sample_desc* desc, void* values, uint64_t stride_bytes, void* stream)
 {
-	return sample_raw_scalar(context, raws, sample_times, track_indices, true, num_instances, desc, values, stride_bytes, stream);
+	return sample_raw(context, k_raw_scalar_track_sample, raws, sample_times, track_indices, num_instances, desc, values, stride_bytes, [&](const aclhip_raw_sample_desc& local)
+	{
+		return launch_raw_scalar_sample(context, raws, sample_times, track_indices, num_instances, local, values, stride_bytes, static_cast<hipStream_t>(stream));
+	});
 }
 
 namespace
@@ -308,24 +211,14 @@ namespace
 			return fail(context, ACLHIP_ERROR_INVALID_ARGUMENT, "the reserved fields of a scalar error desc are 0");
 
 		// raw and lossy are only read and may be the same buffer; what is written overlaps nothing that is read and no other output
-		struct byte_range { const char* name; const void* pointer; unsigned __int128 bytes; };
 		const unsigned __int128 n = num_instances;
-		const byte_range inputs[] = { { "the raw value rows", raw_values, n * raw_stride_bytes }, { "the lossy value rows", lossy_values, n * lossy_stride_bytes } };
-		const byte_range outputs[] = {
-			{ "the track error records", errors, n * sizeof(aclhip_track_error) },
-			{ "the track errors", desc->track_errors, desc->track_errors != nullptr ? n * desc->track_error_stride_bytes : 0 },
-			{ "the worst record", desc->worst, desc->worst != nullptr ? sizeof(aclhip_track_error_worst) : 0 },
-		};
-		for (size_t o = 0; o < std::size(outputs); ++o)
-		{
-			for (const byte_range& input : inputs)
-				if (byte_ranges_overlap(outputs[o].pointer, outputs[o].bytes, input.pointer, input.bytes))
-					return fail(context, ACLHIP_ERROR_INVALID_ARGUMENT, "%s overlap %s", outputs[o].name, input.name);
-			for (size_t other = o + 1; other < std::size(outputs); ++other)
-				if (byte_ranges_overlap(outputs[o].pointer, outputs[o].bytes, outputs[other].pointer, outputs[other].bytes))
-					return fail(context, ACLHIP_ERROR_INVALID_ARGUMENT, "%s overlap %s", outputs[o].name, outputs[other].name);
-		}
-		return ACLHIP_OK;
+		return check_no_overlap(context,
+			{
+				{ "the track error records", errors, n * sizeof(aclhip_track_error) },
+				{ "the track errors", desc->track_errors, desc->track_errors != nullptr ? n * desc->track_error_stride_bytes : 0 },
+				{ "the worst record", desc->worst, desc->worst != nullptr ? sizeof(aclhip_track_error_worst) : 0 },
+			},
+			{ { "the raw value rows", raw_values, n * raw_stride_bytes }, { "the lossy value rows", lossy_values, n * lossy_stride_bytes } });
 	}
 }
 

@@ -62,6 +62,45 @@ extern "C" aclhip_status aclhip_check_raw_tracks(const void* samples, uint32_t n
 	return valid ? ACLHIP_OK : ACLHIP_ERROR_INVALID_ARGUMENT;
 }
 
+namespace
+{
+	// The registration of a raw array of either kind, behind its checks: a handle, the image -- a piece of a clip slab, uploaded on the
+	// context's copy stream as the caller laid it out: no copy that would stall the device -- and the record that publishes it behind it.
+	// `record` comes filled in but for `samples`.
+	template<class table_type, class info_type>
+	aclhip_status register_raw_array(aclhip_context* context, table_type& table, const void* samples, size_t image_bytes, typename table_type::record record,
+		const info_type& info, uint32_t* out_raw)
+	{
+		return guarded(context, [&]() -> aclhip_status
+		{
+			std::lock_guard<std::shared_mutex> lock(context->mutex);
+			device_guard guard(context->device);
+			collect_retired(context, false);
+
+			uint32_t slot;
+			if (const aclhip_status status = take_handle(context, table, slot); status != ACLHIP_OK)
+				return status;
+
+			uint8_t* d_image = allocate_clip_memory(context, image_bytes);
+			if (d_image == nullptr)
+			{
+				table.give_back(slot);
+				return fail(context, ACLHIP_ERROR_OUT_OF_MEMORY, "allocating %zu bytes for the %s failed", image_bytes, table.noun);
+			}
+			record.samples = reinterpret_cast<decltype(record.samples)>(d_image);
+			size_t staging_used = 0;
+			if (!stage_upload(context, d_image, samples, image_bytes, staging_used) || !publish_handle(context, table, slot, record, staging_used, info, d_image))
+			{
+				free_clip_memory(context, d_image);
+				table.give_back(slot);
+				return fail(context, ACLHIP_ERROR_DEVICE, "uploading the %s failed", table.noun);
+			}
+			*out_raw = slot;
+			return ACLHIP_OK;
+		});
+	}
+}
+
 extern "C" aclhip_status aclhip_register_raw_tracks(aclhip_context* context, const void* samples, uint32_t num_tracks, uint32_t num_samples, float sample_rate,
 	uint32_t looping_policy, aclhip_raw_tracks* out_raw)
 {
@@ -75,45 +114,14 @@ extern "C" aclhip_status aclhip_register_raw_tracks(aclhip_context* context, con
 		return fail(context, ACLHIP_ERROR_INVALID_ARGUMENT, "%s", message);
 	if (context == nullptr)
 		return fail(context, ACLHIP_ERROR_INVALID_ARGUMENT, "null context");
-	return guarded(context, [&]() -> aclhip_status
-	{
-		const size_t image_bytes = size_t(num_samples) * num_tracks * 48;
-
-		std::lock_guard<std::shared_mutex> lock(context->mutex);
-		device_guard guard(context->device);
-		collect_retired(context, false);
-
-		uint32_t slot;
-		if (const aclhip_status status = take_handle(context, context->raw_tracks, slot); status != ACLHIP_OK)
-			return status;
-
-		// (a piece of a clip slab, uploaded on the context's copy stream: no copy that would stall the device)
-		uint8_t* d_image = allocate_clip_memory(context, image_bytes);
-		if (d_image == nullptr)
-		{
-			context->raw_tracks.give_back(slot);
-			return fail(context, ACLHIP_ERROR_OUT_OF_MEMORY, "allocating %zu bytes for the raw track array failed", image_bytes);
-		}
-		device_raw_tracks record;
-		std::memset(&record, 0, sizeof(record));
-		record.samples = reinterpret_cast<const f32x4*>(d_image);
-		record.num_tracks = num_tracks;
-		record.num_samples = num_samples;
-		record.sample_rate = sample_rate;
-		record.duration = info.duration;
-		record.looping_policy = looping_policy;
-		size_t staging_used = 0;
-		// the image first, as the caller laid it out, and the record that publishes it behind it
-		if (!stage_upload(context, d_image, samples, image_bytes, staging_used)
-			|| !publish_handle(context, context->raw_tracks, slot, record, staging_used, info, d_image))
-		{
-			free_clip_memory(context, d_image);
-			context->raw_tracks.give_back(slot);
-			return fail(context, ACLHIP_ERROR_DEVICE, "uploading the raw track array failed");
-		}
-		*out_raw = slot;
-		return ACLHIP_OK;
-	});
+	device_raw_tracks record;
+	std::memset(&record, 0, sizeof(record));
+	record.num_tracks = num_tracks;
+	record.num_samples = num_samples;
+	record.sample_rate = sample_rate;
+	record.duration = info.duration;
+	record.looping_policy = looping_policy;
+	return register_raw_array(context, context->raw_tracks, samples, size_t(num_samples) * num_tracks * 48, record, info, out_raw);
 }
 
 extern "C" aclhip_status aclhip_unregister_raw_tracks(aclhip_context* context, aclhip_raw_tracks raw)
@@ -132,20 +140,35 @@ extern "C" aclhip_status aclhip_get_raw_tracks_info(const aclhip_context* contex
 
 namespace
 {
-	// ---- sampling a batch of raw track arrays (aclhip_sample_raw_tracks_batch; sample_raw_tracks_kernel) ---------------------------------
+	// ---- sampling a batch of raw arrays of either kind (the three sampling launches) -----------------------------------------------------
 
-	// What aclhip_sample_raw_tracks_batch checks of its arguments before any device call; every refusal leaves a message, with or without a context
-	aclhip_status check_raw_sample(aclhip_context* context, const aclhip_raw_tracks* raws, const float* sample_times, uint32_t num_instances, const aclhip_raw_sample_desc& desc,
-		const void* poses, uint64_t pose_stride_bytes)
+	// What tells the three launches apart in their argument checks
+	struct raw_sample_kind
+	{
+		const char* handles;			// "raw track": null raw track handles, the pose rows overlap the raw track handles
+		const char* row;				// "pose": null pose buffer, the pose rows overlap the sample times
+		uint32_t alignment;				// of the buffer and of its stride, in bytes
+		bool refuses_zero_stride;
+		const char* alignment_message;
+		uint32_t handle_bytes;
+		bool has_track_indices;			// the single-track form
+	};
+	constexpr raw_sample_kind k_raw_tracks_sample = { "raw track", "pose", 16, false, "pose buffer and stride must be 16 byte aligned", sizeof(aclhip_raw_tracks), false };
+
+	// What a sampling launch checks of its arguments before any device call; every refusal leaves a message, with or without a context
+	aclhip_status check_raw_sample(aclhip_context* context, const raw_sample_kind& kind, const void* raws, const float* sample_times, const uint32_t* track_indices,
+		uint32_t num_instances, const aclhip_raw_sample_desc& desc, const void* rows, uint64_t stride_bytes)
 	{
 		if (raws == nullptr)
-			return fail(context, ACLHIP_ERROR_INVALID_ARGUMENT, "null raw track handles");
+			return fail(context, ACLHIP_ERROR_INVALID_ARGUMENT, "null %s handles", kind.handles);
 		if (sample_times == nullptr)
 			return fail(context, ACLHIP_ERROR_INVALID_ARGUMENT, "null sample times");
-		if (poses == nullptr)
-			return fail(context, ACLHIP_ERROR_INVALID_ARGUMENT, "null pose buffer");
-		if ((pose_stride_bytes & 15u) != 0 || (reinterpret_cast<uintptr_t>(poses) & 15u) != 0)
-			return fail(context, ACLHIP_ERROR_INVALID_ARGUMENT, "pose buffer and stride must be 16 byte aligned");
+		if (kind.has_track_indices && track_indices == nullptr)
+			return fail(context, ACLHIP_ERROR_INVALID_ARGUMENT, "null track indices");
+		if (rows == nullptr)
+			return fail(context, ACLHIP_ERROR_INVALID_ARGUMENT, "null %s buffer", kind.row);
+		if (((reinterpret_cast<uintptr_t>(rows) | stride_bytes) & (kind.alignment - 1u)) != 0 || (kind.refuses_zero_stride && stride_bytes == 0))
+			return fail(context, ACLHIP_ERROR_INVALID_ARGUMENT, "%s", kind.alignment_message);
 		if (desc.rounding_policy > ACLHIP_ROUND_PER_TRACK)
 			return fail(context, ACLHIP_ERROR_INVALID_ARGUMENT, "unknown rounding policy %u", uint32_t(desc.rounding_policy));
 		if (desc.rounding_policy == ACLHIP_ROUND_PER_TRACK && desc.track_rounding_policies == nullptr)
@@ -158,23 +181,74 @@ namespace
 		if (!reserved_clear)
 			return fail(context, ACLHIP_ERROR_INVALID_ARGUMENT, "the reserved fields of a raw sample desc are 0");
 		// the rows are written while every array of the launch is read (with `rows` the output range is still taken as num_instances rows)
-		if (pose_ranges_overlap(poses, pose_stride_bytes, raws, sizeof(aclhip_raw_tracks), num_instances))
-			return fail(context, ACLHIP_ERROR_INVALID_ARGUMENT, "the pose rows overlap the raw track handles");
-		if (pose_ranges_overlap(poses, pose_stride_bytes, sample_times, sizeof(float), num_instances))
-			return fail(context, ACLHIP_ERROR_INVALID_ARGUMENT, "the pose rows overlap the sample times");
-		if (desc.instance_rounding_policies != nullptr && pose_ranges_overlap(poses, pose_stride_bytes, desc.instance_rounding_policies, 1, num_instances))
-			return fail(context, ACLHIP_ERROR_INVALID_ARGUMENT, "the pose rows overlap the instance rounding policies");
-		if (desc.rows != nullptr && pose_ranges_overlap(poses, pose_stride_bytes, desc.rows, sizeof(uint32_t), num_instances))
-			return fail(context, ACLHIP_ERROR_INVALID_ARGUMENT, "the pose rows overlap the row list");
-		if (desc.track_rounding_policies != nullptr && num_instances != 0)
-		{
-			const uint64_t begin = reinterpret_cast<uintptr_t>(desc.track_rounding_policies), end = begin + desc.num_track_rounding_policies;
-			const uint64_t out_begin = reinterpret_cast<uintptr_t>(poses);
-			const unsigned __int128 out_end = (unsigned __int128)out_begin + (unsigned __int128)pose_stride_bytes * num_instances;
-			if (begin < out_end && out_begin < end)
-				return fail(context, ACLHIP_ERROR_INVALID_ARGUMENT, "the pose rows overlap the track rounding policies");
-		}
+		const auto overlap = [&](const void* array, uint64_t element_bytes) { return array != nullptr && pose_ranges_overlap(rows, stride_bytes, array, element_bytes, num_instances); };
+		if (overlap(raws, kind.handle_bytes))
+			return fail(context, ACLHIP_ERROR_INVALID_ARGUMENT, "the %s rows overlap the %s handles", kind.row, kind.handles);
+		if (overlap(sample_times, sizeof(float)))
+			return fail(context, ACLHIP_ERROR_INVALID_ARGUMENT, "the %s rows overlap the sample times", kind.row);
+		if (kind.has_track_indices && overlap(track_indices, sizeof(uint32_t)))
+			return fail(context, ACLHIP_ERROR_INVALID_ARGUMENT, "the %s rows overlap the track indices", kind.row);
+		if (overlap(desc.instance_rounding_policies, 1))
+			return fail(context, ACLHIP_ERROR_INVALID_ARGUMENT, "the %s rows overlap the instance rounding policies", kind.row);
+		if (overlap(desc.rows, sizeof(uint32_t)))
+			return fail(context, ACLHIP_ERROR_INVALID_ARGUMENT, "the %s rows overlap the row list", kind.row);
+		// (the table's size does not follow the batch. Rows of a stride of 0 are a point, as they are to the checks above: inside the table, it overlaps)
+		if (desc.track_rounding_policies != nullptr && num_instances != 0
+			&& byte_ranges_meet(rows, (unsigned __int128)stride_bytes * num_instances, desc.track_rounding_policies, desc.num_track_rounding_policies))
+			return fail(context, ACLHIP_ERROR_INVALID_ARGUMENT, "the %s rows overlap the track rounding policies", kind.row);
 		return ACLHIP_OK;
+	}
+
+	// The front of the three launches: a NULL desc, the checks -- they need no device and come first --, the batch of none, the device.
+	// `launch(desc)` is the kind's own.
+	template<class launch_function>
+	aclhip_status sample_raw(aclhip_context* context, const raw_sample_kind& kind, const void* raws, const float* sample_times, const uint32_t* track_indices,
+		uint32_t num_instances, const aclhip_raw_sample_desc* desc, const void* rows, uint64_t stride_bytes, launch_function launch)
+	{
+		aclhip_raw_sample_desc local = {};		// NULL: ROUND_NONE, row i
+		if (desc != nullptr)
+			local = *desc;
+		const aclhip_status status = check_raw_sample(context, kind, raws, sample_times, track_indices, num_instances, local, rows, stride_bytes);
+		if (status != ACLHIP_OK)
+			return status;
+		if (context == nullptr)
+			return fail(context, ACLHIP_ERROR_INVALID_ARGUMENT, "null context");
+		if (num_instances == 0)
+			return ACLHIP_OK;
+
+		device_guard guard(context->device);
+		return launch(local);
+	}
+
+	// How a launch that reads one of the two tables begins, under the registry lock (its caller holds it shared: see launch_tracks)
+	template<class table_type>
+	aclhip_status begin_raw_launch(aclhip_context* context, const table_type& table, hipStream_t stream)
+	{
+		if (table.d_records == nullptr)
+			return fail(context, ACLHIP_ERROR_INVALID_ARGUMENT, "no %s was ever registered with this context", table.noun);
+		note_launch_stream(context, stream);
+		return ACLHIP_OK;
+	}
+
+	// What the sampling kernels' arguments (raw_sample_launch, raw_scalar_sample_launch) have in common; the rows and the shape are the caller's
+	template<class launch_type, class table_type>
+	launch_type raw_sample_launch_of(aclhip_context* context, const table_type& table, const uint32_t* raws, const float* sample_times, uint32_t num_instances,
+		const aclhip_raw_sample_desc& desc)
+	{
+		launch_type launch = {};
+		launch.arrays = table.d_records;
+		launch.num_arrays = table_type::capacity;
+		launch.num_instances = num_instances;
+		launch.raws = raws;
+		launch.sample_times = sample_times;
+		launch.rows = desc.rows;
+		launch.instance_rounding_policies = desc.instance_rounding_policies;
+		launch.track_rounding_policies = desc.track_rounding_policies;
+		launch.num_track_rounding_policies = desc.track_rounding_policies != nullptr ? desc.num_track_rounding_policies : 0u;
+		launch.rounding_policy = desc.rounding_policy;
+		launch.waves_per_instance = 1;
+		launch.rejected_count = context->d_rejected;
+		return launch;
 	}
 
 	// The launch: shaped by its pose rows alone -- a row of pose_stride_bytes holds at most pose_stride_bytes / 16 quads, and a wave takes
@@ -187,37 +261,21 @@ namespace
 		void* poses, uint64_t pose_stride_bytes, hipStream_t stream)
 	{
 		std::shared_lock<std::shared_mutex> lock(context->mutex);		// see launch_tracks
-		if (context->raw_tracks.d_records == nullptr)
-			return fail(context, ACLHIP_ERROR_INVALID_ARGUMENT, "no raw track array was ever registered with this context");
-		note_launch_stream(context, stream);
+		if (const aclhip_status status = begin_raw_launch(context, context->raw_tracks, stream); status != ACLHIP_OK)
+			return status;
 
-		// (an array holds at most 0xFFFF tracks; the wave index of the kernel is 32 bits wide: a batch too large for a lane per quad loops)
+		raw_sample_launch launch = raw_sample_launch_of<raw_sample_launch>(context, context->raw_tracks, raws, sample_times, num_instances, desc);
+		launch.poses = static_cast<uint8_t*>(poses);
+		launch.pose_stride_bytes = pose_stride_bytes;
+		// (an array holds at most 0xFFFF tracks)
 		const uint64_t row_quads = std::min<uint64_t>(pose_stride_bytes / 16, uint64_t(0xFFFFu) * 3);
-		constexpr uint64_t quads_per_wave = uint64_t(k_wave_size) * k_raw_sample_quads_per_lane;
-		uint64_t waves_per_instance = std::max<uint64_t>((row_quads + quads_per_wave - 1) / quads_per_wave, 1);
+		launch.waves_per_instance = waves_per_instance_of(row_quads, uint64_t(k_wave_size) * k_raw_sample_quads_per_lane, num_instances);
 		// measurement knob: the waves that share an instance, 1 to one per 64 quads (how the shape above was chosen)
 		static const uint32_t forced_waves = []() { const char* value = lab_knob("ACLHIP_RAW_SAMPLE_WAVES"); return value != nullptr ? uint32_t(std::max(0L, std::atol(value))) : 0u; }();
 		if (forced_waves != 0)
-			waves_per_instance = std::min<uint64_t>(std::max<uint64_t>((row_quads + k_wave_size - 1) / k_wave_size, 1), forced_waves);
-		waves_per_instance = std::min<uint64_t>(waves_per_instance, std::max<uint64_t>(0xFFFFFFF0ull / num_instances, 1));
+			launch.waves_per_instance = std::min(waves_per_instance_of(row_quads, k_wave_size, num_instances), forced_waves);
 
-		raw_sample_launch launch = {};
-		launch.arrays = context->raw_tracks.d_records;
-		launch.num_arrays = ACLHIP_MAX_RAW_TRACKS;
-		launch.num_instances = num_instances;
-		launch.raws = raws;
-		launch.sample_times = sample_times;
-		launch.rows = desc.rows;
-		launch.instance_rounding_policies = desc.instance_rounding_policies;
-		launch.track_rounding_policies = desc.track_rounding_policies;
-		launch.num_track_rounding_policies = desc.track_rounding_policies != nullptr ? desc.num_track_rounding_policies : 0u;
-		launch.rounding_policy = desc.rounding_policy;
-		launch.poses = static_cast<uint8_t*>(poses);
-		launch.pose_stride_bytes = pose_stride_bytes;
-		launch.waves_per_instance = uint32_t(waves_per_instance);
-		launch.rejected_count = context->d_rejected;
-
-		const uint64_t num_waves = uint64_t(num_instances) * waves_per_instance;
+		const uint64_t num_waves = uint64_t(num_instances) * launch.waves_per_instance;
 		const uint32_t num_blocks = uint32_t((num_waves + k_raw_sample_waves_per_block - 1) / k_raw_sample_waves_per_block);
 		hipLaunchKernelGGL(sample_raw_tracks_kernel, dim3(num_blocks), dim3(k_raw_sample_waves_per_block * k_wave_size), 0, stream, launch);
 		ACLHIP_CHECK_HIP(context, hipGetLastError());
@@ -225,21 +283,12 @@ namespace
 	}
 }
 
-// include/aclhip.h states the definition. The argument checks need no device, come first and leave a message, with or without a context.
+// include/aclhip.h states the definition
 extern "C" aclhip_status aclhip_sample_raw_tracks_batch(aclhip_context* context, const aclhip_raw_tracks* raws, const float* sample_times, uint32_t num_instances,
 	const aclhip_raw_sample_desc* desc, void* poses, uint64_t pose_stride_bytes, void* stream)
 {
-	aclhip_raw_sample_desc local = {};		// NULL: ROUND_NONE, row i
-	if (desc != nullptr)
-		local = *desc;
-	const aclhip_status status = check_raw_sample(context, raws, sample_times, num_instances, local, poses, pose_stride_bytes);
-	if (status != ACLHIP_OK)
-		return status;
-	if (context == nullptr)
-		return fail(context, ACLHIP_ERROR_INVALID_ARGUMENT, "null context");
-	if (num_instances == 0)
-		return ACLHIP_OK;
-
-	device_guard guard(context->device);
-	return launch_raw_sample(context, raws, sample_times, num_instances, local, poses, pose_stride_bytes, static_cast<hipStream_t>(stream));
+	return sample_raw(context, k_raw_tracks_sample, raws, sample_times, nullptr, num_instances, desc, poses, pose_stride_bytes, [&](const aclhip_raw_sample_desc& local)
+	{
+		return launch_raw_sample(context, raws, sample_times, num_instances, local, poses, pose_stride_bytes, static_cast<hipStream_t>(stream));
+	});
 }

@@ -7,14 +7,15 @@
 //                                    per-track metadata, constant and range values
 //   scalar_compress_write_kernel     per output dword of the animated bit stream (and of the tail behind it): a lane gathers the values that
 //                                    fall into its dword -- no atomics, the same bytes on every run
-//   scalar_compress_hash_kernel      per instance: FNV-1a 32 over [8, size), serial in the bytes; the wave stages the loads, the chain runs
+//   compress_hash_kernel             per instance: FNV-1a 32 over [8, size), serial in the bytes; the wave stages the loads, the chain runs
 //                                    on the scalar unit
 // include/aclhip.h states the definition (fp32, one IEEE operation at a time: this file is compiled with -ffp-contract=off; the division is
 // the compiler's correctly rounded one -- nothing is proven about a caller's values, so none of the clip decode's short forms is used).
 
 	// What the launches hand to each other, in the caller's workspace: one record per instance, one per (instance, track) and one per
-	// (instance, animated track). Every byte that is read was written by an earlier launch of the same call.
-	struct scalar_compress_instance
+	// (instance, animated track). Every byte that is read was written by an earlier launch of the same call. The record per instance is
+	// the transform compressor's too (kernels_transform_compress.inl), and what compress_hash_kernel reads of either: status and size.
+	struct compress_instance
 	{
 		const float* samples;
 		uint32_t num_tracks;
@@ -27,11 +28,15 @@
 		uint32_t status;				// bit 0: a sample is not finite (analyze, atomic OR); bit 1: refused (prepare or layout)
 		uint32_t size;					// layout: the blob's
 		uint32_t num_bits_per_frame;
-		uint32_t num_animated;			// tracks with bits in the stream
-		uint32_t animated_offset;		// of the stream, from the blob's start (4 byte aligned)
-		uint32_t reserved[2];
+		// layout: what each compressor's stream kernel needs. (One flat record with a name for every word, not a union of a view per
+		// compressor: with a union of any shape in this record the compiler orders the loads of the scalar analyze, layout and write
+		// kernels differently.)
+		uint32_t num_animated;					// scalar: tracks with bits in the stream; transform: animated rotations
+		uint32_t animated_offset;				// of the stream, from the blob's start (4 byte aligned)
+		uint32_t num_animated_translations;		// the transform compressor's; the scalar one leaves both 0
+		uint32_t num_animated_scales;
 	};
-	static_assert(sizeof(scalar_compress_instance) == 64, "four dwordx4 loads");
+	static_assert(sizeof(compress_instance) == 64, "four dwordx4 loads");
 
 	struct scalar_compress_track
 	{
@@ -64,7 +69,7 @@
 		float precision;
 		uint32_t optimize_loops;
 		uint32_t max_tracks;
-		scalar_compress_instance* instances;		// [num_instances]
+		compress_instance* instances;				// [num_instances]
 		scalar_compress_track* tracks;				// [num_instances][max_tracks]
 		scalar_compress_animated* animated;			// [num_instances][max_tracks]
 		uint8_t* blobs;
@@ -74,15 +79,24 @@
 		unsigned long long* rejected_count;
 	};
 
+	// compress_hash_kernel's, filled in by both compressors
+	struct compress_hash_launch
+	{
+		const compress_instance* instances;			// [num_instances]
+		uint32_t num_instances;
+		uint8_t* blobs;
+		uint64_t blob_stride_bytes;
+	};
+
 	constexpr uint32_t k_compress_waves_per_block = 4;
 	constexpr uint32_t k_compress_dwords_per_lane = 16;		// the output dwords one lane of the write kernel takes in turn, at most
 	constexpr uint32_t k_compress_cached_values = 4;		// (sample, component) values per lane the rate search keeps normalized in registers
 
-	__device__ __forceinline__ scalar_compress_instance load_compress_instance(const scalar_compress_instance* table, uint32_t index)
+	__device__ __forceinline__ compress_instance load_compress_instance(const compress_instance* table, uint32_t index)
 	{
 		const ACLHIP_CONSTANT u32x4* source = (const ACLHIP_CONSTANT u32x4*)(table + index);
 		struct { u32x4 a, b, c, d; } raw = { source[0], source[1], source[2], source[3] };
-		scalar_compress_instance instance;
+		compress_instance instance;
 		__builtin_memcpy(&instance, &raw, sizeof(instance));
 		return instance;
 	}
@@ -135,7 +149,7 @@
 		const uint32_t num_components = raw.num_components;
 		const uint32_t num_samples = raw.num_samples;
 
-		scalar_compress_instance record = {};
+		compress_instance record = {};
 		const bool refused = handle >= launch.num_arrays || raw.samples == nullptr || num_tracks > launch.max_tracks
 			|| (launch.track_precisions != nullptr && num_tracks > launch.num_track_precisions);
 		if (refused)
@@ -229,7 +243,7 @@
 		const uint32_t track = blockIdx.x * k_compress_waves_per_block + __builtin_amdgcn_readfirstlane(threadIdx.x / k_wave_size);
 		for (uint32_t instance = blockIdx.y; instance < launch.num_instances; instance += gridDim.y)
 		{
-			const scalar_compress_instance record = load_compress_instance(launch.instances, instance);
+			const compress_instance record = load_compress_instance(launch.instances, instance);
 			if ((record.status & k_compress_status_refused) != 0 || track >= record.num_tracks)
 				continue;
 
@@ -364,7 +378,7 @@
 		if (instance >= launch.num_instances)
 			return;
 
-		const scalar_compress_instance record = load_compress_instance(launch.instances, instance);
+		const compress_instance record = load_compress_instance(launch.instances, instance);
 		if ((record.status & k_compress_status_refused) != 0)
 			return;		// (prepare said so)
 		if ((record.status & k_compress_status_not_finite) != 0)
@@ -424,7 +438,7 @@
 		uint8_t* blob = launch.blobs + uint64_t(instance) * launch.blob_stride_bytes;
 		if (lane == 0)
 		{
-			scalar_compress_instance* out = launch.instances + instance;
+			compress_instance* out = launch.instances + instance;
 			out->size = uint32_t(size);
 			out->num_bits_per_frame = frame_bits;
 			out->num_animated = num_animated;
@@ -432,7 +446,7 @@
 			launch.results[instance] = make_uint2(ACLHIP_COMPRESS_OK, uint32_t(size));
 
 			uint32_t* words = reinterpret_cast<uint32_t*>(blob);
-			words[0] = uint32_t(size);					// raw_buffer_header; the hash is scalar_compress_hash_kernel's
+			words[0] = uint32_t(size);					// raw_buffer_header; the hash is compress_hash_kernel's
 			words[1] = 0;
 			words[2] = k_tag_compressed_tracks;			// tracks_header
 			words[3] = uint32_t(k_version_latest) | (uint32_t(k_algorithm_uniformly_sampled) << 16) | (record.track_type << 24);
@@ -487,7 +501,7 @@
 		if (instance >= launch.num_instances)
 			return;
 
-		const scalar_compress_instance record = load_compress_instance(launch.instances, instance);
+		const compress_instance record = load_compress_instance(launch.instances, instance);
 		if (record.status != 0)
 			return;
 
@@ -573,11 +587,11 @@
 	// walks the current one out of the lanes' registers (v_readlane) on the scalar unit.
 	__device__ __forceinline__ uint32_t compress_hash_step(uint32_t hash, uint32_t byte) { return (hash ^ byte) * 16777619u; }
 
-	__global__ __launch_bounds__(k_wave_size) void scalar_compress_hash_kernel(scalar_compress_launch launch)
+	__global__ __launch_bounds__(k_wave_size) void compress_hash_kernel(compress_hash_launch launch)
 	{
 		const uint32_t lane = threadIdx.x;
 		const uint32_t instance = blockIdx.x;
-		const scalar_compress_instance record = load_compress_instance(launch.instances, instance);
+		const compress_instance record = load_compress_instance(launch.instances, instance);
 		if (record.status != 0)
 			return;
 

@@ -8,14 +8,14 @@
 //                                       packed sub-track types, the constant samples, the metadata, the tail; the compact per-type lists of
 //                                       animated tracks for the stream
 //   transform_compress_stream_kernel    per output dword of the animated stream: one 4 byte load, a byte swap, one coalesced store
-//   scalar_compress_hash_kernel         (kernels_scalar_compress.inl, as it is) FNV-1a 32 over [8, size)
+//   compress_hash_kernel                (kernels_scalar_compress.inl: both compressors') FNV-1a 32 over [8, size)
 // include/aclhip.h states the definition. No float arithmetic touches a stored value: the only arithmetic is the normalized test, one IEEE
 // operation at a time in the order of the reference's dot product.
 
-	// What the launches hand to each other, in the caller's workspace: the scalar compressor's 64 byte record per instance (the hash kernel
-	// reads status and size out of it; num_animated / reserved[0] / reserved[1] hold the animated rotation / translation / scale counts,
-	// num_bits_per_frame the bits of one animated pose), one flag byte per (instance, track) and three lists of 16 bit track indices per
-	// instance. Every byte that is read was written by an earlier launch of the same call.
+	// What the launches hand to each other, in the caller's workspace: the 64 byte compress_instance per instance (the hash kernel reads
+	// status and size out of it; num_animated / num_animated_translations / num_animated_scales hold the animated rotation / translation /
+	// scale counts, num_bits_per_frame the bits of one animated pose), one flag byte per (instance, track) and three lists of 16 bit track
+	// indices per instance. Every byte that is read was written by an earlier launch of the same call.
 	constexpr uint32_t k_transform_flag_not_finite = 0x40;			// bits 0-1 / 2-3 / 4-5: the rotation / translation / scale sub-track type
 	constexpr uint32_t k_transform_flag_not_normalized = 0x80;
 	constexpr uint32_t k_compress_status_not_normalized = 4;		// (behind k_compress_status_not_finite and k_compress_status_refused)
@@ -39,7 +39,7 @@
 		float shell_distance;
 		uint32_t max_tracks;
 		uint32_t waves_per_instance;				// the stream kernel's
-		scalar_compress_instance* instances;		// [num_instances]
+		compress_instance* instances;				// [num_instances]
 		uint8_t* track_flags;						// [num_instances][max_tracks]
 		uint16_t* animated;							// [num_instances][3][max_tracks]: the animated tracks of a type, ascending
 		uint8_t* blobs;
@@ -151,7 +151,7 @@
 		const uint32_t num_samples = raw.num_samples;
 		const uint8_t* track_flags = launch.track_flags + size_t(instance) * launch.max_tracks;
 
-		scalar_compress_instance record = {};
+		compress_instance record = {};
 		uint32_t status = transform_compress_refused(launch, handle, raw) ? k_compress_status_refused : 0u;
 		uint32_t num_constant[3] = { 0, 0, 0 }, num_animated[3] = { 0, 0, 0 };
 		if (status == 0)
@@ -216,13 +216,13 @@
 			record.num_bits_per_frame = pose_dwords * 32u;
 			record.num_animated = num_animated[0];
 			record.animated_offset = stream_at;
-			record.reserved[0] = num_animated[1];
-			record.reserved[1] = num_animated[2];
+			record.num_animated_translations = num_animated[1];
+			record.num_animated_scales = num_animated[2];
 			launch.instances[instance] = record;
 			launch.results[instance] = make_uint2(ACLHIP_COMPRESS_OK, uint32_t(size));
 
 			uint32_t* words = reinterpret_cast<uint32_t*>(blob);
-			words[0] = uint32_t(size);					// raw_buffer_header; the hash is scalar_compress_hash_kernel's
+			words[0] = uint32_t(size);					// raw_buffer_header; the hash is compress_hash_kernel's
 			words[1] = 0;
 			words[2] = k_tag_compressed_tracks;			// tracks_header
 			words[3] = uint32_t(k_version_latest) | (uint32_t(k_algorithm_uniformly_sampled) << 16) | (uint32_t(k_track_type_qvvf) << 24);
@@ -345,12 +345,12 @@
 		if (instance >= launch.num_instances)
 			return;
 
-		const scalar_compress_instance record = load_compress_instance(launch.instances, instance);
+		const compress_instance record = load_compress_instance(launch.instances, instance);
 		if (record.status != 0)
 			return;
 
 		const uint32_t rotation_dwords = record.num_animated * 4u;
-		const uint32_t translation_dwords = record.reserved[0] * 3u;
+		const uint32_t translation_dwords = record.num_animated_translations * 3u;
 		const uint32_t pose_dwords = record.num_bits_per_frame / 32u;
 		const uint32_t num_dwords = pose_dwords * record.num_samples;		// < 2^27 (layout refuses the rest)
 		const uint32_t* samples = reinterpret_cast<const uint32_t*>(record.samples);

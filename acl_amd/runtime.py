@@ -1686,6 +1686,39 @@ def scalar_compress_workspace_bytes(num_instances, max_tracks):
     return int(load_library().aclhip_scalar_compress_workspace_bytes(int(num_instances), int(max_tracks)))
 
 
+def _compress_batch(ctx, launch, handles, noun, stride, workspace_bytes, desc):
+    """What compress_scalar_tracks and compress_raw_tracks share: rows of `stride` bytes, the results and the workspace are allocated on the
+    context's device, `launch` (the context's method) runs on the current stream and is waited for, and each result becomes a 16 byte
+    aligned blob or the documented exception. `desc` comes filled in but for the workspace."""
+    import torch
+    from .synth import aligned_bytes
+    device = torch.device("cuda", ctx.device_index)
+    num_instances = len(handles)
+    stream = torch.cuda.current_stream(device)
+    d_raws = torch.from_numpy(handles.view(np.int32)).to(device)
+    d_blobs = torch.zeros((num_instances, stride), dtype=torch.uint8, device=device)
+    d_results = torch.zeros((num_instances, 2), dtype=torch.int32, device=device)
+    d_workspace = torch.zeros(workspace_bytes + 16, dtype=torch.uint8, device=device)
+    desc.workspace = d_workspace.data_ptr()
+    launch(d_raws.data_ptr(), num_instances, desc, d_blobs.data_ptr(), stride, d_results.data_ptr(), stream=stream.cuda_stream)
+    stream.synchronize()
+    results = d_results.cpu().numpy().view(np.uint32).reshape(num_instances, 2)
+    rows = d_blobs.cpu().numpy()
+    blobs = []
+    for i in range(num_instances):
+        status, size = int(results[i, 0]), int(results[i, 1])
+        if status == COMPRESS_NOT_FINITE:
+            raise RuntimeError("Some samples are not finite")
+        if status == COMPRESS_NOT_NORMALIZED:
+            raise ValueError(f"instance {i} ({noun} {int(handles[i])}) holds a rotation that is not normalized (ACLHIP_COMPRESS_NOT_NORMALIZED)")
+        if status != COMPRESS_OK:
+            raise ValueError(f"instance {i} ({noun} {int(handles[i])}) was refused (ACLHIP_COMPRESS_REFUSED)")
+        blob = aligned_bytes(size)
+        blob[:] = rows[i, :size]
+        blobs.append(blob)
+    return blobs
+
+
 def compress_scalar_tracks(ctx, raws, precision=1.0e-5, track_precisions=None, optimize_loops=False):
     """acl::compress_track_list for raw scalar track arrays as one launch: `raws` is a handle or a list of handles
     (register_raw_scalar_tracks; they may repeat and differ in type and shape), `precision` the tracks' precision (the reference's default)
@@ -1695,44 +1728,20 @@ def compress_scalar_tracks(ctx, raws, precision=1.0e-5, track_precisions=None, o
     message when a sample is not finite, ValueError when an instance is refused. Synchronous; the buffers are torch tensors on the
     context's device."""
     import torch
-    from .synth import aligned_bytes
-    device = torch.device("cuda", ctx.device_index)
     handles = np.atleast_1d(np.asarray(raws, dtype=np.uint32))
     infos = [ctx.raw_scalar_tracks_info(int(handle)) for handle in handles]
-    num_instances = len(handles)
-    if num_instances == 0:
+    if len(handles) == 0:
         return []
     stride = max(scalar_compress_bound(info.track_type, info.num_tracks, info.num_samples) for info in infos)
-    max_tracks = max(int(info.num_tracks) for info in infos)
-    stream = torch.cuda.current_stream(device)
-    d_raws = torch.from_numpy(handles.view(np.int32)).to(device)
-    d_blobs = torch.zeros((num_instances, stride), dtype=torch.uint8, device=device)
-    d_results = torch.zeros((num_instances, 2), dtype=torch.int32, device=device)
-    d_workspace = torch.zeros(scalar_compress_workspace_bytes(num_instances, max_tracks) + 16, dtype=torch.uint8, device=device)
     desc = ScalarCompressDesc()
     desc.precision = float(precision)
     desc.flags = COMPRESS_OPTIMIZE_LOOPS if optimize_loops else 0
-    desc.max_tracks = max_tracks
-    desc.workspace = d_workspace.data_ptr()
-    d_precisions = None
-    if track_precisions is not None:
-        d_precisions = torch.from_numpy(np.ascontiguousarray(track_precisions, dtype=np.float32)).to(device)
+    desc.max_tracks = max(int(info.num_tracks) for info in infos)
+    if track_precisions is not None:        # (d_precisions: alive until the launch has run)
+        d_precisions = torch.from_numpy(np.ascontiguousarray(track_precisions, dtype=np.float32)).to(torch.device("cuda", ctx.device_index))
         desc.track_precisions, desc.num_track_precisions = d_precisions.data_ptr(), d_precisions.numel()
-    ctx.compress_raw_scalar_tracks_batch(d_raws.data_ptr(), num_instances, desc, d_blobs.data_ptr(), stride, d_results.data_ptr(), stream=stream.cuda_stream)
-    stream.synchronize()
-    results = d_results.cpu().numpy().view(np.uint32).reshape(num_instances, 2)
-    rows = d_blobs.cpu().numpy()
-    blobs = []
-    for i in range(num_instances):
-        status, size = int(results[i, 0]), int(results[i, 1])
-        if status == COMPRESS_NOT_FINITE:
-            raise RuntimeError("Some samples are not finite")
-        if status != COMPRESS_OK:
-            raise ValueError(f"instance {i} (raw scalar track array {int(handles[i])}) was refused (ACLHIP_COMPRESS_REFUSED)")
-        blob = aligned_bytes(size)
-        blob[:] = rows[i, :size]
-        blobs.append(blob)
-    return blobs
+    return _compress_batch(ctx, ctx.compress_raw_scalar_tracks_batch, handles, "raw scalar track array", stride,
+                           scalar_compress_workspace_bytes(len(handles), desc.max_tracks), desc)
 
 
 def transform_compress_bound(num_tracks, num_samples, flags=0):
@@ -1757,24 +1766,14 @@ def compress_raw_tracks(ctx, raws, default_pose=None, parents=None, precision=1.
     rotation is not normalized (ACLHIP_COMPRESS_NOT_NORMALIZED) or an instance is refused. Synchronous; the buffers are torch tensors on
     the context's device."""
     import torch
-    from .synth import aligned_bytes
-    device = torch.device("cuda", ctx.device_index)
     handles = np.atleast_1d(np.asarray(raws, dtype=np.uint32))
     infos = [ctx.raw_tracks_info(int(handle)) for handle in handles]
-    num_instances = len(handles)
-    if num_instances == 0:
+    if len(handles) == 0:
         return []
     flags = (COMPRESS_INCLUDE_PARENT_TRACK_INDICES if include_parent_track_indices else 0) | (COMPRESS_INCLUDE_TRACK_DESCRIPTIONS if include_track_descriptions else 0)
     stride = max(transform_compress_bound(info.num_tracks, info.num_samples, flags) for info in infos)
-    max_tracks = max(int(info.num_tracks) for info in infos)
-    stream = torch.cuda.current_stream(device)
-    d_raws = torch.from_numpy(handles.view(np.int32)).to(device)
-    d_blobs = torch.zeros((num_instances, stride), dtype=torch.uint8, device=device)
-    d_results = torch.zeros((num_instances, 2), dtype=torch.int32, device=device)
-    d_workspace = torch.zeros(transform_compress_workspace_bytes(num_instances, max_tracks) + 16, dtype=torch.uint8, device=device)
     desc = TransformCompressDesc()
-    desc.flags, desc.max_tracks, desc.precision, desc.shell_distance = flags, max_tracks, float(precision), float(shell_distance)
-    desc.workspace = d_workspace.data_ptr()
+    desc.flags, desc.max_tracks, desc.precision, desc.shell_distance = flags, max(int(info.num_tracks) for info in infos), float(precision), float(shell_distance)
     tables = []         # (kept alive until the launch has run)
     for field, table, dtype, width in (("default_pose", default_pose, np.float32, 12), ("parent_indices", parents, np.uint32, 1),
                                        ("track_precisions", track_precisions, np.float32, 1), ("track_shell_distances", track_shell_distances, np.float32, 1)):
@@ -1783,27 +1782,12 @@ def compress_raw_tracks(ctx, raws, default_pose=None, parents=None, precision=1.
         host = np.ascontiguousarray(table, dtype=dtype).reshape(-1, width)
         if tables and host.shape[0] != tables[0][1]:
             raise ValueError("default_pose, parents, track_precisions and track_shell_distances hold the same number of tracks")
-        d_table = torch.from_numpy(host.view(np.int32) if dtype is np.uint32 else host).to(device)
+        d_table = torch.from_numpy(host.view(np.int32) if dtype is np.uint32 else host).to(torch.device("cuda", ctx.device_index))
         tables.append((d_table, host.shape[0]))
         setattr(desc, field, d_table.data_ptr())
         desc.num_table_tracks = host.shape[0]
-    ctx.compress_raw_tracks_batch(d_raws.data_ptr(), num_instances, desc, d_blobs.data_ptr(), stride, d_results.data_ptr(), stream=stream.cuda_stream)
-    stream.synchronize()
-    results = d_results.cpu().numpy().view(np.uint32).reshape(num_instances, 2)
-    rows = d_blobs.cpu().numpy()
-    blobs = []
-    for i in range(num_instances):
-        status, size = int(results[i, 0]), int(results[i, 1])
-        if status == COMPRESS_NOT_FINITE:
-            raise RuntimeError("Some samples are not finite")
-        if status == COMPRESS_NOT_NORMALIZED:
-            raise ValueError(f"instance {i} (raw track array {int(handles[i])}) holds a rotation that is not normalized (ACLHIP_COMPRESS_NOT_NORMALIZED)")
-        if status != COMPRESS_OK:
-            raise ValueError(f"instance {i} (raw track array {int(handles[i])}) was refused (ACLHIP_COMPRESS_REFUSED)")
-        blob = aligned_bytes(size)
-        blob[:] = rows[i, :size]
-        blobs.append(blob)
-    return blobs
+    return _compress_batch(ctx, ctx.compress_raw_tracks_batch, handles, "raw track array", stride,
+                           transform_compress_workspace_bytes(len(handles), desc.max_tracks), desc)
 
 
 def scalar_clip_error(ctx, clip_a, clip_b):

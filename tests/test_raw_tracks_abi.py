@@ -184,3 +184,6 @@ def test_every_invalid_argument_of_the_launch_has_its_message():
     assert sample(desc_with(rows=end, instance_rounding_policies=POSES - COUNT, track_rounding_policies=POSES - 100, num_track_rounding_policies=100)) == (INVALID, "null context")
     # no instances: nothing can overlap, and the launch would be a no-op
     assert sample(raws=POSES, count=0) == (INVALID, "null context")
+    # a stride of 0 leaves the rows a point: inside the policy table it overlaps, at the table's end it does not
+    assert sample(desc_with(track_rounding_policies=POSES - 50, num_track_rounding_policies=100), stride=0) == (INVALID, "the pose rows overlap the track rounding policies")
+    assert sample(desc_with(track_rounding_policies=POSES - 100, num_track_rounding_policies=100), stride=0) == (INVALID, "null context")
