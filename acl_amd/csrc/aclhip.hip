@@ -18,6 +18,7 @@
 //   sample_raw_scalar_track_kernel     the same arrays, one thread per (instance, track) request.
 //   measure_scalar_error_kernel        the scalar track error of two value buffers: one wave64 per instance, lanes <-> tracks.
 //   scalar_compress_*_kernel           compress_track_list of raw scalar track arrays in five launches: vote, per-track analysis (one wave64 per track), layout, bit stream (one lane per output dword), hash (compress_hash_kernel, the transform compressor's too).
+//   tracks_compress_*_kernel           compress_track_list with drop-w rotations: the rigid shell and the looping vote (one wave64 per instance), the shell error analysis (one wave64 per track), then the raw-format compressor's layout and stream with three words per rotation.
 //   decompress_track_kernel            one thread per (instance, bone) request; the registration time plan replaces the
 //                                      reference's O(track index) skip over preceding widths.
 //   decompress_scalar_tracks_kernel    scalar track lists: one wave64 per (instance, 256 tracks), lanes <-> tracks.
@@ -65,6 +66,7 @@ namespace aclhip
 #include "kernels_raw_scalar_tracks.inl"
 #include "kernels_scalar_compress.inl"
 #include "kernels_transform_compress.inl"
+#include "kernels_tracks_compress.inl"
 #include "kernels_misc.inl"
 #include "kernels_scalar.inl"
 #include "kernels_track.inl"
@@ -95,5 +97,6 @@ using namespace aclhip;
 #include "host_raw_scalar_tracks.inl"
 #include "host_scalar_compress.inl"
 #include "host_transform_compress.inl"
+#include "host_tracks_compress.inl"
 #include "host_bone_object.inl"
 #include "host_scalar_misc.inl"

@@ -112,12 +112,12 @@ extern "C" aclhip_status aclhip_compress_raw_tracks_batch(aclhip_context* contex
 		ACLHIP_CHECK_HIP(context, hipGetLastError());
 		if (shape.phases >= 2)
 		{
-			hipLaunchKernelGGL(transform_compress_layout_kernel, dim3(shape.instance_blocks), dim3(shape.block_size), 0, stream, launch);
+			hipLaunchKernelGGL(transform_compress_layout_kernel<false>, dim3(shape.instance_blocks), dim3(shape.block_size), 0, stream, launch);
 			ACLHIP_CHECK_HIP(context, hipGetLastError());
 		}
 		if (shape.phases >= 3)
 		{
-			hipLaunchKernelGGL(transform_compress_stream_kernel, dim3(shape.stream_blocks), dim3(shape.block_size), 0, stream, launch);
+			hipLaunchKernelGGL(transform_compress_stream_kernel<false>, dim3(shape.stream_blocks), dim3(shape.block_size), 0, stream, launch);
 			ACLHIP_CHECK_HIP(context, hipGetLastError());
 		}
 		if (shape.phases >= 4)

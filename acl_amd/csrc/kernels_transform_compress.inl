@@ -11,6 +11,8 @@
 //   compress_hash_kernel                (kernels_scalar_compress.inl: both compressors') FNV-1a 32 over [8, size)
 // include/aclhip.h states the definition. No float arithmetic touches a stored value: the only arithmetic is the normalized test, one IEEE
 // operation at a time in the order of the reference's dot product.
+// The layout and the stream kernel are templates: their <true> instantiations are aclhip_compress_tracks_batch's (kernels_tracks_compress.inl)
+// for quatf_drop_w_full -- three words per rotation, normalized and of positive w --, their <false> ones this call's, unchanged.
 
 	// What the launches hand to each other, in the caller's workspace: the 64 byte compress_instance per instance (the hash kernel reads
 	// status and size out of it; num_animated / num_animated_translations / num_animated_scales hold the animated rotation / translation /
@@ -46,6 +48,9 @@
 		uint64_t blob_stride_bytes;
 		uint2* results;								// [num_instances] aclhip_compress_result
 		unsigned long long* rejected_count;
+		// aclhip_compress_tracks_batch alone (kernels_tracks_compress.inl), behind everything the raw call reads
+		float2* shells;								// [num_instances][max_tracks] { local shell distance, precision } of the rigid shell
+		float2* shell_metadata;						// the caller's copy of them, or null
 	};
 
 	// wave uniform, decided from the handle, the record and the launch alone: the analysis and the layout come to the same answer
@@ -58,6 +63,22 @@
 
 	// 0 default, 1 constant, 2 animated
 	__device__ __forceinline__ uint32_t transform_compress_type(bool constant, bool is_default) { return constant ? (is_default ? k_sub_track_default : k_sub_track_constant) : k_sub_track_animated; }
+
+	// quatf_drop_w_full (aclhip_compress_tracks_batch; include/aclhip.h states the definition): every rotation normalized with the
+	// correctly rounded 1 / sqrt over vector_dot's lane order, and, where it is stored or compared, of positive w (convert_rotation.transform.h:93-96:
+	// the sign bit of w xored into all four lanes, a w of -0 included)
+	__device__ __forceinline__ float4 tracks_compress_normalize(f32x4 q)
+	{
+		const float inv_length = 1.0f / sqrtf((q.x * q.x + q.z * q.z) + (q.y * q.y + q.w * q.w));
+		return make_float4(q.x * inv_length, q.y * inv_length, q.z * inv_length, q.w * inv_length);
+	}
+
+	__device__ __forceinline__ float4 tracks_compress_positive_w(float4 q)
+	{
+		const uint32_t sign = __float_as_uint(q.w) & 0x80000000u;
+		return make_float4(__uint_as_float(__float_as_uint(q.x) ^ sign), __uint_as_float(__float_as_uint(q.y) ^ sign), __uint_as_float(__float_as_uint(q.z) ^ sign),
+			__uint_as_float(__float_as_uint(q.w) ^ sign));
+	}
 
 	// ---- per (instance, track): the checks and the three sub-track types ----------------------------------------------------------------------
 	// One wave64 per track, samples across the lanes: a lane takes the three quads of its sample's record (a track's records lie 48 T bytes
@@ -138,8 +159,12 @@
 	// row. A second pass gives every track its place: a constant sub-track's in the constant data (rotations, then translations, then scales:
 	// write_stream_data.h:199-310), an animated one's in its type's list, its type's in the packed words (write_sub_track_types.h). Then the
 	// headers (compress.transform.impl.h:404-452, write_segment_data.h:67-122), the metadata (write_track_metadata.h:106-194) or the tail.
+	// kDropW (aclhip_compress_tracks_batch with quatf_drop_w_full): the statuses, the sample count behind the looping vote and the wrap bit
+	// are tracks_compress_shell_kernel's, in the instance's record; a rotation is three words, normalized and of positive w.
+	template<bool kDropW>
 	__global__ __launch_bounds__(k_compress_waves_per_block * k_wave_size) void transform_compress_layout_kernel(transform_compress_launch launch)
 	{
+		constexpr uint32_t rotation_width = kDropW ? 3u : 4u;
 		const uint32_t lane = threadIdx.x & (k_wave_size - 1);
 		const uint32_t instance = blockIdx.x * k_compress_waves_per_block + __builtin_amdgcn_readfirstlane(threadIdx.x / k_wave_size);
 		if (instance >= launch.num_instances)
@@ -148,11 +173,19 @@
 		const uint32_t handle = as_constant(launch.raws)[instance];
 		const device_raw_tracks raw = load_raw_tracks_fields(launch.arrays, handle < launch.num_arrays ? handle : 0);
 		const uint32_t num_tracks = raw.num_tracks;
-		const uint32_t num_samples = raw.num_samples;
+		uint32_t num_samples = raw.num_samples;
 		const uint8_t* track_flags = launch.track_flags + size_t(instance) * launch.max_tracks;
 
 		compress_instance record = {};
 		uint32_t status = transform_compress_refused(launch, handle, raw) ? k_compress_status_refused : 0u;
+		uint32_t wrap = raw.looping_policy == k_loop_wrap ? 1u : 0u;
+		if constexpr (kDropW)
+		{
+			const compress_instance voted = load_compress_instance(launch.instances, instance);
+			status = voted.status;
+			num_samples = voted.num_out_samples;
+			wrap = voted.wrap;
+		}
 		uint32_t num_constant[3] = { 0, 0, 0 }, num_animated[3] = { 0, 0, 0 };
 		if (status == 0)
 		{
@@ -176,8 +209,8 @@
 		const bool with_parents = with_descriptions || (launch.flags & k_compress_include_parents) != 0;
 		const uint32_t type_words = (num_tracks + 15u) / 16u;
 		const uint32_t types_bytes = 4u * type_words * (has_scale ? 3u : 2u);
-		const uint32_t constant_bytes = 16u * num_constant[0] + 12u * num_constant[1] + 12u * num_constant[2];
-		const uint32_t pose_dwords = 4u * num_animated[0] + 3u * num_animated[1] + 3u * num_animated[2];
+		const uint32_t constant_bytes = 4u * rotation_width * num_constant[0] + 12u * num_constant[1] + 12u * num_constant[2];
+		const uint32_t pose_dwords = rotation_width * num_animated[0] + 3u * num_animated[1] + 3u * num_animated[2];
 		const uint64_t stream_bytes = 4ull * pose_dwords * num_samples;
 		const uint32_t constants_at = k_transform_blob_headers + types_bytes;
 		const uint32_t stream_at = constants_at + constant_bytes;
@@ -210,7 +243,7 @@
 			record.num_tracks = num_tracks;
 			record.num_samples = record.num_out_samples = num_samples;
 			record.track_type = k_track_type_qvvf;
-			record.wrap = raw.looping_policy == k_loop_wrap ? 1u : 0u;
+			record.wrap = wrap;
 			record.sample_rate = raw.sample_rate;
 			record.size = uint32_t(size);
 			record.num_bits_per_frame = pose_dwords * 32u;
@@ -231,7 +264,7 @@
 			words[6] = __float_as_uint(raw.sample_rate);
 			// has_scale | default scale 1 | the three full formats (0) | no database, no trivial defaults (quat_near_identity with a
 			// threshold of 0 holds for no rotation), no stripped key frames | wrap optimized | metadata
-			words[7] = (has_scale ? 1u : 0u) | 2u | (record.wrap != 0 ? 1u << 30 : 0u) | (with_parents ? 1u << 31 : 0u);
+			words[7] = (has_scale ? 1u : 0u) | 2u | (kDropW ? uint32_t(k_rotation_quatf_drop_w_full) << 4 : 0u) | (record.wrap != 0 ? 1u << 30 : 0u) | (with_parents ? 1u << 31 : 0u);
 			words[8] = 1;								// transform_tracks_header: one segment; offsets from its own start
 			words[9] = 0;								// no variable sub-tracks
 			words[10] = num_animated[0];
@@ -246,7 +279,7 @@
 			words[19] = constants_at - k_transform_header_offset;
 			words[20] = stream_at - k_transform_header_offset;		// no clip range data
 			words[21] = pose_dwords * 32u;				// segment_header
-			words[22] = num_animated[0] * 128u;
+			words[22] = num_animated[0] * (32u * rotation_width);
 			words[23] = num_animated[1] * 96u;
 			words[24] = stream_at - k_transform_header_offset;		// no format per track data, no segment range data
 		}
@@ -255,7 +288,7 @@
 		const uint32_t* first_frame = reinterpret_cast<const uint32_t*>(raw.samples);
 		uint16_t* animated = launch.animated + size_t(instance) * 3u * launch.max_tracks;
 		uint32_t constants_before[3] = { 0, 0, 0 }, animated_before[3] = { 0, 0, 0 };
-		const uint32_t section_at[3] = { constants_at, constants_at + 16u * num_constant[0], constants_at + 16u * num_constant[0] + 12u * num_constant[1] };
+		const uint32_t section_at[3] = { constants_at, constants_at + 4u * rotation_width * num_constant[0], constants_at + 4u * rotation_width * num_constant[0] + 12u * num_constant[1] };
 		for (uint32_t first = 0; first < num_tracks; first += k_wave_size)
 		{
 			const uint32_t track = first + lane;
@@ -264,14 +297,26 @@
 			for (uint32_t kind = 0; kind < 3; ++kind)
 			{
 				const uint32_t type = (flags >> (2u * kind)) & 3u;
-				const uint32_t width = kind == 0 ? 4u : 3u;
+				const uint32_t width = kind == 0 ? rotation_width : 3u;
 				const uint64_t constant_mask = __ballot(type == k_sub_track_constant), animated_mask = __ballot(type == k_sub_track_animated);
 				if (type == k_sub_track_constant)
 				{
 					uint32_t* out = reinterpret_cast<uint32_t*>(blob + section_at[kind]) + (constants_before[kind] + transform_compress_rank(constant_mask)) * width;
 					const uint32_t* in = first_frame + size_t(track) * 12u + kind * 4u;
-					for (uint32_t component = 0; component < width; ++component)
-						out[component] = in[component];
+					if (kDropW && kind == 0)
+					{
+						// write_stream_data.h:213-267: groups of four constant rotations as xxxx yyyy zzzz, a last group of n as n, n and n
+						const float4 rotation = tracks_compress_positive_w(tracks_compress_normalize(*reinterpret_cast<const f32x4*>(in)));
+						const uint32_t rank = constants_before[0] + transform_compress_rank(constant_mask);
+						const uint32_t group = rank / 4u, entry = rank % 4u, group_size = num_constant[0] - group * 4u < 4u ? num_constant[0] - group * 4u : 4u;
+						out = reinterpret_cast<uint32_t*>(blob + section_at[0]) + group * 12u;
+						out[entry] = __float_as_uint(rotation.x);
+						out[group_size + entry] = __float_as_uint(rotation.y);
+						out[2u * group_size + entry] = __float_as_uint(rotation.z);
+					}
+					else
+						for (uint32_t component = 0; component < width; ++component)
+							out[component] = in[component];
 				}
 				if (type == k_sub_track_animated)
 					animated[kind * launch.max_tracks + animated_before[kind] + transform_compress_rank(animated_mask)] = uint16_t(track);
@@ -336,8 +381,11 @@
 	// translations xyz, then the scales xyz, each in track order; every float as a 32 bit word, most significant byte first). The pose is a
 	// whole number of dwords: a division gives the sample and the slot, compares give the type, the list gives the track. One 4 byte load,
 	// a byte swap, one coalesced store; no atomics and no zero fill.
+	// kDropW: a rotation is x, y, z of the registered sample normalized and made of positive w -- a rotation's lane loads the whole quaternion.
+	template<bool kDropW>
 	__global__ __launch_bounds__(k_compress_waves_per_block * k_wave_size) void transform_compress_stream_kernel(transform_compress_launch launch)
 	{
+		constexpr uint32_t rotation_width = kDropW ? 3u : 4u;
 		const uint32_t lane = threadIdx.x & (k_wave_size - 1);
 		const uint32_t wave = blockIdx.x * k_compress_waves_per_block + __builtin_amdgcn_readfirstlane(threadIdx.x / k_wave_size);
 		const uint32_t instance = wave / launch.waves_per_instance;
@@ -349,7 +397,7 @@
 		if (record.status != 0)
 			return;
 
-		const uint32_t rotation_dwords = record.num_animated * 4u;
+		const uint32_t rotation_dwords = record.num_animated * rotation_width;
 		const uint32_t translation_dwords = record.num_animated_translations * 3u;
 		const uint32_t pose_dwords = record.num_bits_per_frame / 32u;
 		const uint32_t num_dwords = pose_dwords * record.num_samples;		// < 2^27 (layout refuses the rest)
@@ -361,7 +409,7 @@
 		{
 			const uint32_t sample = dword / pose_dwords;
 			uint32_t slot = dword - sample * pose_dwords;
-			uint32_t kind = 0, width = 4;
+			uint32_t kind = 0, width = rotation_width;
 			if (slot >= rotation_dwords)
 			{
 				slot -= rotation_dwords;
@@ -375,6 +423,20 @@
 			}
 			const uint32_t entry = slot / width, component = slot - entry * width;
 			const uint32_t track = animated[kind * launch.max_tracks + entry];
-			out[dword] = __builtin_bswap32(samples[(size_t(sample) * record.num_tracks + track) * 12u + kind * 4u + component]);
+			if constexpr (kDropW)
+			{
+				const uint32_t* in = samples + (size_t(sample) * record.num_tracks + track) * 12u + kind * 4u;
+				uint32_t value;
+				if (kind == 0)
+				{
+					const float4 rotation = tracks_compress_positive_w(tracks_compress_normalize(*reinterpret_cast<const f32x4*>(in)));
+					value = __float_as_uint(component == 0 ? rotation.x : component == 1 ? rotation.y : rotation.z);
+				}
+				else
+					value = in[component];
+				out[dword] = __builtin_bswap32(value);
+			}
+			else
+				out[dword] = __builtin_bswap32(samples[(size_t(sample) * record.num_tracks + track) * 12u + kind * 4u + component]);
 		}
 	}

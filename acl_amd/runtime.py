@@ -60,6 +60,7 @@ EXPORTED_SYMBOLS = [
     "aclhip_sample_raw_scalar_tracks_batch", "aclhip_sample_raw_scalar_track_batch", "aclhip_measure_scalar_error_batch",
     "aclhip_scalar_compress_bound", "aclhip_scalar_compress_workspace_bytes", "aclhip_compress_raw_scalar_tracks_batch",
     "aclhip_transform_compress_bound", "aclhip_transform_compress_workspace_bytes", "aclhip_compress_raw_tracks_batch",
+    "aclhip_compress_tracks_workspace_bytes", "aclhip_compress_tracks_batch",
 ]
 
 
@@ -271,6 +272,18 @@ class TransformCompressDesc(ctypes.Structure):
     ]
 
 
+class CompressTracksDesc(ctypes.Structure):
+    """aclhip_compress_tracks_desc; the four tables, the workspace and shell_metadata are device addresses"""
+    _fields_ = [
+        ("rotation_format", ctypes.c_uint32), ("translation_format", ctypes.c_uint32), ("scale_format", ctypes.c_uint32), ("flags", ctypes.c_uint32),
+        ("max_tracks", ctypes.c_uint32), ("num_table_tracks", ctypes.c_uint32), ("default_pose", ctypes.c_void_p), ("parent_indices", ctypes.c_void_p),
+        ("track_precisions", ctypes.c_void_p), ("track_shell_distances", ctypes.c_void_p), ("precision", ctypes.c_float), ("shell_distance", ctypes.c_float),
+        ("workspace", ctypes.c_void_p), ("shell_metadata", ctypes.c_void_p), ("reserved", ctypes.c_uint64 * 2),
+    ]
+
+
+ROTATION_QUATF_FULL, ROTATION_QUATF_DROP_W_FULL = 0, 2                                      # acl::rotation_format8 (aclhip_compress_tracks_desc::rotation_format)
+VECTOR_VECTOR3F_FULL = 0                                                                    # acl::vector_format8
 COMPRESS_OPTIMIZE_LOOPS = 1                                                                 # ACLHIP_COMPRESS_OPTIMIZE_LOOPS
 COMPRESS_INCLUDE_PARENT_TRACK_INDICES, COMPRESS_INCLUDE_TRACK_DESCRIPTIONS = 2, 4           # ACLHIP_COMPRESS_INCLUDE_* (the transform compressor's)
 COMPRESS_OK, COMPRESS_NOT_FINITE, COMPRESS_REFUSED = 0, 1, 2                                # aclhip_compress_result::status
@@ -517,6 +530,9 @@ def load_library():
     lib.aclhip_transform_compress_workspace_bytes.argtypes = [u32, u32]
     lib.aclhip_transform_compress_workspace_bytes.restype = u64
     lib.aclhip_compress_raw_tracks_batch.argtypes = [vp, vp, u32, ctypes.POINTER(TransformCompressDesc), vp, u64, vp, vp]
+    lib.aclhip_compress_tracks_workspace_bytes.argtypes = [u32, u32]
+    lib.aclhip_compress_tracks_workspace_bytes.restype = u64
+    lib.aclhip_compress_tracks_batch.argtypes = [vp, vp, u32, ctypes.POINTER(CompressTracksDesc), vp, u64, vp, vp]
     _lib = lib
     return lib
 
@@ -1174,6 +1190,14 @@ class Context:
         self._check(self._lib.aclhip_compress_raw_tracks_batch(self._handle, raws_ptr, num_instances, ctypes.byref(desc) if desc is not None else None,
                                                                blobs_ptr, blob_stride_bytes, results_ptr, stream))
 
+    def compress_tracks_batch(self, raws_ptr, num_instances, desc, blobs_ptr, blob_stride_bytes, results_ptr, stream=None):
+        """aclhip_compress_tracks_batch: compress_track_list with quatf_full or quatf_drop_w_full rotations (the rigid shell, the looping vote,
+        constant and default rotations by the error metric) of the raw track arrays named at raws_ptr (device uint32 [num_instances]) into
+        the rows at blobs_ptr, one aclhip_compress_result per instance at results_ptr (device addresses); `desc` is a CompressTracksDesc
+        with its workspace."""
+        self._check(self._lib.aclhip_compress_tracks_batch(self._handle, raws_ptr, num_instances, ctypes.byref(desc) if desc is not None else None,
+                                                           blobs_ptr, blob_stride_bytes, results_ptr, stream))
+
     def decompress_poses_mapped(self, clips, sample_times, skeletons, maps, num_bones, additive_format=ADDITIVE_NONE, object_space=False, base_clips=None,
                                 base_sample_times=None, base_maps=None, base_poses=None, params=None, out=None, instance_rounding=None, instance_looping=None,
                                 blend_clips=None, blend_sample_times=None, blend_maps=None, blend_weights=None, flags=0):
@@ -1687,7 +1711,7 @@ def scalar_compress_workspace_bytes(num_instances, max_tracks):
 
 
 def _compress_batch(ctx, launch, handles, noun, stride, workspace_bytes, desc):
-    """What compress_scalar_tracks and compress_raw_tracks share: rows of `stride` bytes, the results and the workspace are allocated on the
+    """What compress_scalar_tracks, compress_raw_tracks and compress_tracks share: rows of `stride` bytes, the results and the workspace are allocated on the
     context's device, `launch` (the context's method) runs on the current stream and is waited for, and each result becomes a 16 byte
     aligned blob or the documented exception. `desc` comes filled in but for the workspace."""
     import torch
@@ -1788,6 +1812,46 @@ def compress_raw_tracks(ctx, raws, default_pose=None, parents=None, precision=1.
         desc.num_table_tracks = host.shape[0]
     return _compress_batch(ctx, ctx.compress_raw_tracks_batch, handles, "raw track array", stride,
                            transform_compress_workspace_bytes(len(handles), desc.max_tracks), desc)
+
+
+def compress_tracks_workspace_bytes(num_instances, max_tracks):
+    """aclhip_compress_tracks_workspace_bytes (host only)"""
+    return int(load_library().aclhip_compress_tracks_workspace_bytes(int(num_instances), int(max_tracks)))
+
+
+def compress_tracks(ctx, raws, rotation_format=ROTATION_QUATF_DROP_W_FULL, default_pose=None, parents=None, precision=1.0e-4, shell_distance=1.0, track_precisions=None,
+                    track_shell_distances=None, optimize_loops=False, include_parent_track_indices=False, include_track_descriptions=False):
+    """acl::compress_track_list with quatf_drop_w_full (or quatf_full) rotations and vector3f_full translations and scales for raw track
+    arrays as one launch, like compress_raw_tracks: `raws` is a handle or a list of handles. With quatf_drop_w_full the parents, precisions
+    and shell distances make the rigid shell at which constant and default rotations and the looping vote (optimize_loops) are decided;
+    every parent index is smaller than its child's. Rows are sized from aclhip_transform_compress_bound. Returns a list of 16 byte
+    aligned numpy uint8 blobs. Raises RuntimeError with the reference's message when a sample is not finite (a zero quaternion
+    included), ValueError when an instance is refused. Synchronous; the buffers are torch tensors on the context's device."""
+    import torch
+    handles = np.atleast_1d(np.asarray(raws, dtype=np.uint32))
+    infos = [ctx.raw_tracks_info(int(handle)) for handle in handles]
+    if len(handles) == 0:
+        return []
+    flags = ((COMPRESS_OPTIMIZE_LOOPS if optimize_loops else 0) | (COMPRESS_INCLUDE_PARENT_TRACK_INDICES if include_parent_track_indices else 0)
+             | (COMPRESS_INCLUDE_TRACK_DESCRIPTIONS if include_track_descriptions else 0))
+    stride = max(transform_compress_bound(info.num_tracks, info.num_samples, flags) for info in infos)
+    desc = CompressTracksDesc()
+    desc.rotation_format, desc.translation_format, desc.scale_format = int(rotation_format), VECTOR_VECTOR3F_FULL, VECTOR_VECTOR3F_FULL
+    desc.flags, desc.max_tracks, desc.precision, desc.shell_distance = flags, max(int(info.num_tracks) for info in infos), float(precision), float(shell_distance)
+    tables = []         # (kept alive until the launch has run)
+    for field, table, dtype, width in (("default_pose", default_pose, np.float32, 12), ("parent_indices", parents, np.uint32, 1),
+                                       ("track_precisions", track_precisions, np.float32, 1), ("track_shell_distances", track_shell_distances, np.float32, 1)):
+        if table is None:
+            continue
+        host = np.ascontiguousarray(table, dtype=dtype).reshape(-1, width)
+        if tables and host.shape[0] != tables[0][1]:
+            raise ValueError("default_pose, parents, track_precisions and track_shell_distances hold the same number of tracks")
+        d_table = torch.from_numpy(host.view(np.int32) if dtype is np.uint32 else host).to(torch.device("cuda", ctx.device_index))
+        tables.append((d_table, host.shape[0]))
+        setattr(desc, field, d_table.data_ptr())
+        desc.num_table_tracks = host.shape[0]
+    return _compress_batch(ctx, ctx.compress_tracks_batch, handles, "raw track array", stride,
+                           compress_tracks_workspace_bytes(len(handles), desc.max_tracks), desc)
 
 
 def scalar_clip_error(ctx, clip_a, clip_b):

@@ -213,7 +213,8 @@ const char* aclhip_last_error_message(const aclhip_context* context);
  * for the scalar compressor -- aclhip_scalar_compress_desc, aclhip_compress_result, aclhip_scalar_compress_bound,
  * aclhip_scalar_compress_workspace_bytes and aclhip_compress_raw_scalar_tracks_batch -- and for the raw-format transform compressor --
  * aclhip_transform_compress_desc, aclhip_transform_compress_bound, aclhip_transform_compress_workspace_bytes and
- * aclhip_compress_raw_tracks_batch).
+ * aclhip_compress_raw_tracks_batch -- and for the drop-w transform compressor -- aclhip_compress_tracks_desc,
+ * aclhip_compress_tracks_workspace_bytes and aclhip_compress_tracks_batch).
  * A caller compiled against another header would hand over structs of another shape; aclhip_abi_version() says what the LIBRARY was
  * built with, and the C++ mirror (aclhip.hpp) refuses to create a context when the two differ. */
 #define ACLHIP_ABI_VERSION 6u
@@ -1943,7 +1944,7 @@ uint64_t aclhip_transform_compress_workspace_bytes(uint32_t num_instances, uint3
  * one wave per instance, which decides the statuses and the refusal and stores headers, sub-track types, constants, metadata and the
  * tail; the stream, one lane per output dword (one 4 byte load, a byte swap, one coalesced store); the scalar compressor's hash.
  *   Left out (nothing here precludes them): the variable formats and everything they need (segmenting, range reduction, the bit rate
- * search, the error metric over the hierarchy); quatf_drop_w_full; additive bases; track and list names; output_index remapping and
+ * search; the error metric over the hierarchy and quatf_drop_w_full exist: aclhip_compress_tracks_batch, below); additive bases; track and list names; output_index remapping and
  * stripped tracks; a flag that normalizes rotations within a tolerance; the C++ mirror in aclhip.hpp.
  *   What it costs (no time is promised; one MI355X, 4 096 instances over 256 distinct arrays of 100 tracks x 301 samples -- the bench's
  * pose shape, 91 % of the rotations, a third of the translations and a tenth of the scales animated: 5.92 GB of samples, 2.43 GB of
@@ -1953,6 +1954,97 @@ uint64_t aclhip_transform_compress_workspace_bytes(uint32_t num_instances, uint3
  * hash 19 692 us (87 %): 594 KB of serial chain per blob. The hash is the call, and nothing was built against that. */
 aclhip_status aclhip_compress_raw_tracks_batch(aclhip_context* context, const aclhip_raw_tracks* raws /* DEVICE [num_instances] */,
 	uint32_t num_instances, const aclhip_transform_compress_desc* desc, void* blobs /* DEVICE */, uint64_t blob_stride_bytes,
+	aclhip_compress_result* results /* DEVICE [num_instances] */, void* stream);
+
+/* ---- compress_track_list for raw track arrays: drop-w rotations, the rigid shell -----------------------------------------------------------
+ * acl::compress_track_list for a track_array_qvvf with rotation_format = quatf_drop_w_full, translation_format = scale_format =
+ * vector3f_full (compression/impl/compress.transform.impl.h:138-530), batched. Once the rotation format is not quatf_full the reference
+ * normalizes every rotation, computes the RIGID SHELL of every transform from the hierarchy, takes the looping vote with the error metric,
+ * converts rotations to positive w, decides constant and default ROTATION sub-tracks by the error metric at the shell and writes 96 bit
+ * rotations; with these three formats it does nothing else: no segmenting, no range reduction, no search. A locked joint whose rotation
+ * jitters below the precision loses its sub-track entirely.
+ *   rotation_format == 0 (quatf_full) runs aclhip_compress_raw_tracks_batch's four launches: the bytes, statuses and refusals are that
+ * call's for the same arguments, ACLHIP_COMPRESS_NOT_NORMALIZED included. Everything below is rotation_format == 2.
+ *   THE BLOB IS THE REFERENCE'S for the same samples and settings IN EVERY BYTE BUT THE ROTATION VALUE WORDS (and the hash over them):
+ * the reference normalizes through rtm::quat_normalize, which starts from the x86 reciprocal square root ESTIMATE -- not reproducible
+ * between CPU vendors --; this call normalizes with the correctly rounded 1 / sqrt, the project's standing definition. The
+ * words differ by at most a few ulp (measured: 1.2e-7 absolute; the tests hold 1e-5). Every decision -- constant, default, the vote --
+ * is the reference's wherever its error is not within rounding of its precision.
+ *   Rows, results, statuses, refusal counting, alignment rules, overlap checks, stream ordering, "uploads nothing" and graph capture are
+ * as for aclhip_compress_raw_tracks_batch. aclhip_transform_compress_bound(T, S, flags) STAYS THE BOUND: a drop-w blob has the raw blob's
+ * sections with 12 bytes where that has 16 per rotation, and never more samples: it is never larger than the raw one. */
+typedef struct aclhip_compress_tracks_desc
+{
+	uint32_t rotation_format;              /*  0  acl::rotation_format8: 0 quatf_full, 2 quatf_drop_w_full */
+	uint32_t translation_format;           /*  4  acl::vector_format8: 0 vector3f_full */
+	uint32_t scale_format;                 /*  8  0 vector3f_full */
+	uint32_t flags;                        /* 12  ACLHIP_COMPRESS_OPTIMIZE_LOOPS | ACLHIP_COMPRESS_INCLUDE_PARENT_TRACK_INDICES | ACLHIP_COMPRESS_INCLUDE_TRACK_DESCRIPTIONS */
+	uint32_t max_tracks;                   /* 16  tracks the workspace was sized for; an instance with more is refused */
+	uint32_t num_table_tracks;             /* 20  entries of every non-NULL table below */
+	const void* default_pose;              /* 24  DEVICE or NULL, as in the raw call */
+	const uint32_t* parent_indices;        /* 32  DEVICE or NULL (every track a root): the hierarchy the shell is made from, and metadata */
+	const float* track_precisions;         /* 40  DEVICE or NULL (-> precision) */
+	const float* track_shell_distances;    /* 48  DEVICE or NULL (-> shell_distance) */
+	float precision;                       /* 56  reference default 0.0001F */
+	float shell_distance;                  /* 60  reference default 1.0F */
+	void* workspace;                       /* 64  DEVICE, 16 byte aligned, aclhip_compress_tracks_workspace_bytes(num_instances, max_tracks) bytes */
+	void* shell_metadata;                  /* 72  DEVICE or NULL, 8 byte aligned: [num_instances][max_tracks] { float local_shell_distance, precision }: what step 2
+	                                              computed, for b < T of every instance whose shell was computed: all but those that are not finite or
+	                                              refused for their handle, their track count or by step 0 (rotation_format 2 only) */
+	uint64_t reserved[2];                  /* 80  0 */
+} aclhip_compress_tracks_desc;             /* 96 bytes */
+
+/* Host only. The raw call's workspace and 8 bytes per instance and track (the shell), each part rounded up to 16, 128 bits wide and capped. */
+uint64_t aclhip_compress_tracks_workspace_bytes(uint32_t num_instances, uint32_t max_tracks);
+
+/* The definition for quatf_drop_w_full. All arithmetic is fp32, one IEEE operation at a time, never fused, denormals kept. The array has
+ * T tracks and S samples. Used lanes and fourth lanes are as in the raw call.
+ *   Per-track values. prec_b = track_precisions[b] or precision. dist_b = track_shell_distances[b] or shell_distance. parent_b =
+ * parent_indices[b] if the table is given and the value is < T, else none.
+ *   Helpers. shell_error(d, A, B) is qvvf_transform_error_metric::calculate_error with scale (transform_error_metrics.h:335-358), as
+ * aclhip_measure_pose_error_batch states it: the three points (d,0,0), (0,d,0), (0,0,d) through rtm::qvv_mul_point3 of A and of B,
+ * sqrtf(((dx * dx) + (dy * dy)) + (dz * dz)) of each difference, the greatest of the three with a > b ? a : b.
+ *   0. Parent refusal. An instance with a parent_b in [b, T) is ACLHIP_COMPRESS_REFUSED and counted, before any write to the row. The
+ *      reference orders transforms by (parent + 1, index) (clip_context.impl.h:62-79): children before parents in reverse only when every
+ *      parent index is smaller than its child's. For any other numbering its shell is an artefact of that sort; this call does not imitate it.
+ *   1. Normalize, then the finite check. n = q * (1.0F / sqrtf(((x * x + z * z) + (y * y + w * w)))) for EVERY rotation
+ *      (clip_context.impl.h:150). Any used lane not finite after that gives ACLHIP_COMPRESS_NOT_FINITE; a zero quaternion ends there, as
+ *      in the reference. ACLHIP_COMPRESS_NOT_NORMALIZED does not occur: (0, 0, 0, 2) is normalized and compresses. This is the one step
+ *      where the bytes are this library's and not the reference's.
+ *   2. Rigid shell (rigid_shell_utils.h:51-170), from ALL S samples of the normalized, not yet sign-converted array. Start with local_b =
+ *      dist_b, sprec_b = prec_b. Visit the tracks in DESCENDING index order (with parent < child: the reference's reverse parent-first
+ *      order, siblings included). For track b: d = local_b; stretch = the maximum over the samples and over the three points (d,0,0),
+ *      (0,d,0), (0,0,d) of sqrtf((x * x + y * y) + z * z) of qvv_mul_point3(point, sample), started from 0.0F, with a > b ? a : b;
+ *      psd_b = stretch, plus prec_b when d != dist_b; when parent_b exists and psd_b > local_parent: local_parent = psd_b, sprec_parent =
+ *      sprec_b. The comparison is strict: of siblings with equal psd the highest index wins, and the parent's own distance wins a tie.
+ *      An array whose shell arithmetic produces a NaN intermediate (finite samples whose products overflow) is outside the definition: it
+ *      ends with a status and without a fault, and its bytes mean nothing.
+ *      shell_metadata, when given, receives { local_b, sprec_b } for b < T.
+ *   3. Looping (optimize_looping.transform.h:178-243). With ACLHIP_COMPRESS_OPTIMIZE_LOOPS, an array registered ACLHIP_LOOP_CLAMP and
+ *      S > 1: when NOT shell_error(local_b, sample 0 of b, sample S-1 of b) > sprec_b for every track, S becomes S - 1 and the blob is
+ *      wrap optimized. An array registered ACLHIP_LOOP_WRAP keeps S and is wrap optimized without a vote. Steps 4 to 6 use the new S.
+ *   4. Positive w (convert_rotation.transform.h:93-96). All four lanes of a rotation are xored with the sign bit of its w; a w of -0
+ *      flips too.
+ *   5. Sub-tracks (compact.transform.h:72-254, :401-420). A rotation is CONSTANT iff no sample s has shell_error(local_b, {r_s, t_s, s_s},
+ *      {r_0, t_s, s_s}) > sprec_b. It is DEFAULT iff it is constant and the same holds with the default rotation in place of r_0; the
+ *      default rotation is used as given in default_pose, not normalized and not converted. A constant rotation stores x, y, z of r_0, 12
+ *      bytes, SWIZZLED (write_stream_data.h:213-267): the constant rotations in track order in groups of four, a group as its four x,
+ *      its four y, its four z; a last group of n < 4 as n x, n y, n z. Translations and scales are as in the raw call: binary == against sample 0 and the default, over the S of step 3.
+ *      has_scale is as in the raw call.
+ *   6. The blob. It is the raw call's blob with four differences: quatf_drop_w_full in the packed header word; 12 byte constant
+ *      rotations, swizzled as step 5 says; three words per animated rotation in the stream (x, y, z); the segment header's bit counts follow from that. Metadata
+ *      is unchanged: the descriptions carry prec_b and dist_b, not the shell's values. Tail, size and hash are as there.
+ *   Refused per instance, besides step 0: as in the raw call. ACLHIP_ERROR_INVALID_ARGUMENT, each with a message: everything the raw call
+ * refuses; shell_metadata not 8 byte aligned or overlapping anything else the call reads or writes; a format value that is no format of
+ * the reference (rotation 1 or >= 4, vector >= 2); the reference's variable formats (rotation 3, vector 1), which are not built.
+ *   Five launches (DESIGN.md 4.7 "Transform compression (drop-w rotations, rigid shell)"): the shell, one wave per instance, tracks in
+ * descending order with samples across the lanes, which also takes the step 0 refusal, the finite test and the vote; the analysis, one wave
+ * per (instance, track): two shell error ballots for the rotation, the raw call's for translation and scale; the raw call's layout and
+ * stream with three words per rotation; the hash. No atomics besides the refusal counter: the same bytes on every run.
+ *   Left out: the variable formats, segmenting, range reduction and the bit rate search; the matrix error metric and additive bases;
+ * track and list names; output_index remapping; the C++ mirror in aclhip.hpp. What it costs: profiles/compress_tracks.md. */
+aclhip_status aclhip_compress_tracks_batch(aclhip_context* context, const aclhip_raw_tracks* raws /* DEVICE [num_instances] */,
+	uint32_t num_instances, const aclhip_compress_tracks_desc* desc, void* blobs /* DEVICE */, uint64_t blob_stride_bytes,
 	aclhip_compress_result* results /* DEVICE [num_instances] */, void* stream);
 
 /* ---- multi-GPU ---------------------------------------------------------------------------------- */
