@@ -403,7 +403,7 @@ namespace
 		}
 	};
 
-	// The shape of a pose consumer launch (launch_consumers, launch_pose_buffers): one wave per instance, the whole pose (its base, its
+	// The shape of a pose consumer launch (launch_consumers, launch_pose_rows): one wave per instance, the whole pose (its base, its
 	// hierarchy) in LDS; as many instances per workgroup (a power of two, at most 8, 4 unless told otherwise: measured best) as leave room
 	// for three workgroups per CU: the object space walk packs its lanes with instances of one workgroup.
 	// what a workgroup may ask for on top of the kernel's static words (consumer_walk_slots, kernels_consumers.inl)
@@ -444,6 +444,19 @@ namespace
 			shape.log2_instances_per_block--;
 		shape.lds_bytes = (shape.lds_bytes_per_instance << shape.log2_instances_per_block) + lds_schedule_bytes;
 		return shape;
+	}
+
+	// The launch of a kernel of that shape, one wave per instance or two (launch_consumers and every launch of host_pose_buffers.inl):
+	// above the default limit of dynamic LDS the kernel has to be told
+	template<class kernel_type, class... argument_types>
+	aclhip_status launch_consumer_kernel(aclhip_context* context, kernel_type kernel, const consumer_launch_shape& shape, uint32_t num_blocks, uint32_t waves_per_instance,
+		hipStream_t stream, const argument_types&... arguments)
+	{
+		if (shape.lds_bytes > 64 * 1024 - 128)
+			ACLHIP_CHECK_HIP(context, hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, int(k_consumer_lds_bytes)));
+		hipLaunchKernelGGL(kernel, dim3(num_blocks), dim3((waves_per_instance << shape.log2_instances_per_block) * k_wave_size), shape.lds_bytes, stream, arguments...);
+		ACLHIP_CHECK_HIP(context, hipGetLastError());
+		return ACLHIP_OK;
 	}
 
 	// What the skeleton space launches (_mapped, _masked, _bounds with a mapping) check of their mapping, and the launch argument made of it
@@ -610,7 +623,6 @@ namespace
 		if (!shape.fits)
 			return fail(context, ACLHIP_ERROR_INVALID_ARGUMENT, "poses of %u transforms (the pose stride, the largest registered clip): too large for the pose consumers (%zu bytes of LDS per instance)", batch_quads / 3, shape.lds_needed_bytes);
 		const uint32_t instances_per_block = 1u << shape.log2_instances_per_block;
-		const uint32_t waves_per_block = instances_per_block * (two_waves ? 2 : 1);
 		const uint32_t num_blocks = (num_instances + instances_per_block - 1) / instances_per_block;
 
 		consumer_params device_consumers;
@@ -632,18 +644,14 @@ namespace
 		// (skeleton space: the reference pose fills slots -- like a clip whose scales registration has looked at)
 		const bool mirrored = context->num_negative_scale_clips != 0 || (has_base && !base_is_clip) || (extras.mapped && context->num_negative_scale_skeletons != 0);
 		const bool object_space = consumers.object_space != 0;
-		// above the default limit of dynamic LDS the kernel has to be told; trailing: the mapping, the masking
+		// trailing: the mapping, the masking
 		const auto launch = [&](auto kernel, const auto&... trailing) -> aclhip_status
 		{
 			if (kernel == nullptr)
 				return fail(context, ACLHIP_ERROR_INVALID_ARGUMENT, "no pose consumer kernel for base kind %u", base_kind);
-			if (shape.lds_bytes > 64 * 1024 - 128)
-				ACLHIP_CHECK_HIP(context, hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, int(k_consumer_lds_bytes)));
-			hipLaunchKernelGGL(kernel, dim3(num_blocks), dim3(waves_per_block * k_wave_size), shape.lds_bytes, stream,
+			return launch_consumer_kernel(context, kernel, shape, num_blocks, two_waves ? 2 : 1, stream,
 				context->d_clips, context->d_clips_capacity, clips, sample_times, num_instances, params, device_consumers,
 				static_cast<uint8_t*>(poses), pose_stride_bytes, shape.lds_quads_per_image, uint32_t(shape.lds_bytes_per_instance), shape.log2_instances_per_block | (shape.lds_schedule_words << 8), context->d_rejected, trailing...);
-			ACLHIP_CHECK_HIP(context, hipGetLastError());
-			return ACLHIP_OK;
 		};
 		// ACLHIP_CONSUMERS_FAST: object space launches without a blend, in the hardware's 1 ulp arithmetic (include/aclhip.h)
 		const bool fast = (consumers.flags & ACLHIP_CONSUMERS_FAST) != 0 && object_space && !blend;

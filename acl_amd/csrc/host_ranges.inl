@@ -1,6 +1,7 @@
 // host_ranges.inl -- part of aclhip.hip (one translation unit; included there in front of host_pose_buffers.inl, not compiled on its own).
 // Host side: what the argument checks and the launches of the caller-buffer entry points share -- do two ranges of bytes overlap, does any
-// output of a launch overlap what it reads or another output, and how many waves share an instance.
+// output of a launch overlap what it reads or another output, and how many waves share an instance. (What only the launches over a
+// caller's pose rows share -- the other clauses of their checks, their shape and their front -- stands at the top of host_pose_buffers.inl.)
 
 namespace
 {

@@ -1,6 +1,7 @@
 // host_skins.inl -- part of aclhip.hip (one translation unit; included there behind host_pose_buffers.inl, not compiled on its own).
 // Host side: skins (a mesh's joint list and inverse bind matrices) -- what registration checks, the record and its image; the handles are
-// a handle_table's (host_context.inl) -- and aclhip_skinning_matrices_batch (skinning_matrices_kernel, kernels_pose_buffers.inl).
+// a handle_table's (host_context.inl) -- and aclhip_skinning_matrices_batch (skinning_matrices_kernel, kernels_pose_buffers.inl): its
+// own argument check and kernel argument behind what host_pose_buffers.inl states for every launch over a caller's pose rows.
 
 namespace
 {
@@ -143,20 +144,11 @@ namespace
 {
 	// ---- skinning matrix palettes of a pose buffer (aclhip_skinning_matrices_batch; skinning_matrices_kernel) ------------------------------
 
-	// The pose row alone sets the shape of the launch: an image holds pose_stride_bytes / 48 transforms (a palette row has as many records as
-	// the skin has joints, which says nothing about the image), and the words of the walk schedule on top once the context is known
-	aclhip_status skinning_matrices_launch_shape_of(aclhip_context* context, uint64_t pose_stride_bytes, bool object_space, uint32_t max_hierarchy_words, consumer_launch_shape& out_shape)
-	{
-		const uint32_t row_transforms = uint32_t(std::min<uint64_t>(pose_stride_bytes / 48, 0xFFFFu));
-		out_shape = consumer_launch_shape_of(row_transforms * 3u, row_transforms, false, object_space, max_hierarchy_words);
-		if (!out_shape.fits)
-			return fail(context, ACLHIP_ERROR_INVALID_ARGUMENT, "rows of %u transforms: too large for the skinning matrices (%zu bytes of LDS per instance)", row_transforms, out_shape.lds_needed_bytes);
-		return ACLHIP_OK;
-	}
-
-	// What aclhip_skinning_matrices_batch checks of its arguments before any device call; every refusal leaves a message, with or without a context
+	// What aclhip_skinning_matrices_batch checks of its arguments before any device call; every refusal leaves a message, with or without a
+	// context. The rows that shape the launch: the pose row alone -- an image holds pose_stride_bytes / 48 transforms (a palette row has as
+	// many records as the skin has joints, which says nothing about the image).
 	aclhip_status check_skinning_matrices(aclhip_context* context, const void* poses, uint64_t pose_stride_bytes, uint32_t num_instances, const aclhip_skinning_desc* desc,
-		const void* palettes, uint64_t palette_stride_bytes)
+		const void* palettes, uint64_t palette_stride_bytes, pose_rows& out_rows)
 	{
 		if (desc == nullptr)
 			return fail(context, ACLHIP_ERROR_INVALID_ARGUMENT, "null skinning desc");
@@ -164,20 +156,19 @@ namespace
 			return fail(context, ACLHIP_ERROR_INVALID_ARGUMENT, "null pose buffer");
 		if (palettes == nullptr)
 			return fail(context, ACLHIP_ERROR_INVALID_ARGUMENT, "null palette buffer");
-		if (desc->skeleton == 0 && desc->instance_skeletons == nullptr)
-			return fail(context, ACLHIP_ERROR_INVALID_ARGUMENT, "a skinning desc names a skeleton or a list of skeletons");
+		if (const aclhip_status status = check_names_skeleton(context, "a skinning desc names", desc->skeleton, desc->instance_skeletons); status != ACLHIP_OK)
+			return status;
 		if (desc->skin == 0 && desc->instance_skins == nullptr)
 			return fail(context, ACLHIP_ERROR_INVALID_ARGUMENT, "a skinning desc names a skin or a list of skins");
 		if (desc->layout != ACLHIP_PALETTE_3X4F_64 && desc->layout != ACLHIP_PALETTE_3X4F_TRANSPOSED_48)
 			return fail(context, ACLHIP_ERROR_INVALID_ARGUMENT, "unknown palette layout %u", desc->layout);
-		if ((pose_stride_bytes & 15u) != 0 || (reinterpret_cast<uintptr_t>(poses) & 15u) != 0)
-			return fail(context, ACLHIP_ERROR_INVALID_ARGUMENT, "pose buffer and stride must be 16 byte aligned");
-		if ((palette_stride_bytes & 15u) != 0 || (reinterpret_cast<uintptr_t>(palettes) & 15u) != 0)
-			return fail(context, ACLHIP_ERROR_INVALID_ARGUMENT, "palette buffer and stride must be 16 byte aligned");
+		if (const aclhip_status status = check_rows_aligned(context, { { "pose", poses, pose_stride_bytes }, { "palette", palettes, palette_stride_bytes } }); status != ACLHIP_OK)
+			return status;
 		if (desc->reserved[0] != 0 || desc->reserved[1] != 0)
 			return fail(context, ACLHIP_ERROR_INVALID_ARGUMENT, "the reserved fields of a skinning desc are 0");
+		out_rows = { pose_stride_bytes / 48, false, "too large for the skinning matrices" };
 		consumer_launch_shape shape;
-		if (const aclhip_status shape_status = skinning_matrices_launch_shape_of(context, pose_stride_bytes, false, 0, shape); shape_status != ACLHIP_OK)
+		if (const aclhip_status shape_status = pose_rows_launch_shape_of(context, out_rows, false, 0, shape); shape_status != ACLHIP_OK)
 			return shape_status;
 		// records differ from transforms in size and in number: there is no in place form, and no other overlap either (the lists are only read as well)
 		if (pose_ranges_overlap(palettes, palette_stride_bytes, poses, pose_stride_bytes, num_instances))
@@ -188,76 +179,35 @@ namespace
 			return fail(context, ACLHIP_ERROR_INVALID_ARGUMENT, "the palette rows overlap the skin list");
 		return ACLHIP_OK;
 	}
+}
 
-	template<bool kObjectSpace, uint32_t kLayout>
-	aclhip_status launch_skinning_matrices_kernel(aclhip_context* context, const consumer_launch_shape& shape, uint32_t num_blocks, hipStream_t stream, const skinning_matrices_launch& launch)
+// include/aclhip.h states the definition. The argument checks need no device, come first and leave a message, with or without a context.
+// The front is launch_pose_rows (host_pose_buffers.inl), which asks for the skin table as well.
+extern "C" aclhip_status aclhip_skinning_matrices_batch(aclhip_context* context, const void* poses, uint64_t pose_stride_bytes, uint32_t num_instances,
+	const aclhip_skinning_desc* desc, void* palettes, uint64_t palette_stride_bytes, void* stream_handle)
+{
+	pose_rows rows;
+	const aclhip_status status = check_skinning_matrices(context, poses, pose_stride_bytes, num_instances, desc, palettes, palette_stride_bytes, rows);
+	if (status != ACLHIP_OK)
+		return status;
+	const bool object_space = desc->object_space != 0;
+	return launch_pose_rows(context, num_instances, stream_handle, rows, object_space, true, false, [&](hipStream_t stream, const consumer_launch_shape& shape, uint32_t num_blocks) -> aclhip_status
 	{
-		const auto kernel = skinning_matrices_kernel<kObjectSpace, kLayout>;
-		// above the default limit of dynamic LDS the kernel has to be told
-		if (shape.lds_bytes > 64 * 1024 - 128)
-			ACLHIP_CHECK_HIP(context, hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, int(k_consumer_lds_bytes)));
-		hipLaunchKernelGGL(kernel, dim3(num_blocks), dim3((1u << shape.log2_instances_per_block) * k_wave_size), shape.lds_bytes, stream, launch);
-		ACLHIP_CHECK_HIP(context, hipGetLastError());
-		return ACLHIP_OK;
-	}
-
-	// The launch: shaped by its pose rows alone, like launch_pose_matrices; the two tables are filled in under the registry lock; nothing is uploaded
-	aclhip_status launch_skinning_matrices(aclhip_context* context, const void* poses, uint64_t pose_stride_bytes, uint32_t num_instances, const aclhip_skinning_desc& desc,
-		void* palettes, uint64_t palette_stride_bytes, hipStream_t stream)
-	{
-		std::shared_lock<std::shared_mutex> lock(context->mutex);		// see launch_tracks
-		if (context->skeletons.d_records == nullptr)
-			return fail(context, ACLHIP_ERROR_INVALID_ARGUMENT, "no skeleton was ever registered with this context");
-		if (context->skins.d_records == nullptr)
-			return fail(context, ACLHIP_ERROR_INVALID_ARGUMENT, "no skin was ever registered with this context");
-		const bool object_space = desc.object_space != 0;
-		consumer_launch_shape shape;
-		if (const aclhip_status shape_status = skinning_matrices_launch_shape_of(context, pose_stride_bytes, object_space, context->max_skeleton_hierarchy_words, shape); shape_status != ACLHIP_OK)
-			return shape_status;
-		note_launch_stream(context, stream);
-
-		skinning_matrices_launch launch = {};
-		launch.skeletons = context->skeletons.d_records;
-		launch.num_skeletons = ACLHIP_MAX_SKELETONS;
-		launch.skeleton = desc.skeleton;
-		launch.instance_skeletons = desc.instance_skeletons;
+		skinning_matrices_launch launch = pose_rows_launch_of<skinning_matrices_launch>(context, *desc, num_instances, shape);
 		launch.skins = context->skins.d_records;
 		launch.num_skins = ACLHIP_MAX_SKINS;
-		launch.skin = desc.skin;
-		launch.instance_skins = desc.instance_skins;
+		launch.skin = desc->skin;
+		launch.instance_skins = desc->instance_skins;
 		launch.poses = static_cast<const uint8_t*>(poses);
 		launch.pose_stride_bytes = pose_stride_bytes;
 		launch.palettes = static_cast<uint8_t*>(palettes);
 		launch.palette_stride_bytes = palette_stride_bytes;
-		launch.num_instances = num_instances;
-		launch.lds_quads_per_image = shape.lds_quads_per_image;
-		launch.lds_bytes_per_instance = uint32_t(shape.lds_bytes_per_instance);
 		launch.packed_block_shape = shape.log2_instances_per_block | (shape.lds_schedule_words << 8);
-		launch.rejected_count = context->d_rejected;
 
-		const uint32_t instances_per_block = 1u << shape.log2_instances_per_block;
-		const uint32_t num_blocks = (num_instances + instances_per_block - 1) / instances_per_block;
-		const bool transposed = desc.layout == ACLHIP_PALETTE_3X4F_TRANSPOSED_48;
-		if (object_space)
-			return transposed ? launch_skinning_matrices_kernel<true, k_palette_3x4f_transposed_48>(context, shape, num_blocks, stream, launch)
-				: launch_skinning_matrices_kernel<true, k_palette_3x4f_64>(context, shape, num_blocks, stream, launch);
-		return transposed ? launch_skinning_matrices_kernel<false, k_palette_3x4f_transposed_48>(context, shape, num_blocks, stream, launch)
-			: launch_skinning_matrices_kernel<false, k_palette_3x4f_64>(context, shape, num_blocks, stream, launch);
-	}
-}
-
-// include/aclhip.h states the definition. The argument checks need no device, come first and leave a message, with or without a context.
-extern "C" aclhip_status aclhip_skinning_matrices_batch(aclhip_context* context, const void* poses, uint64_t pose_stride_bytes, uint32_t num_instances,
-	const aclhip_skinning_desc* desc, void* palettes, uint64_t palette_stride_bytes, void* stream)
-{
-	const aclhip_status status = check_skinning_matrices(context, poses, pose_stride_bytes, num_instances, desc, palettes, palette_stride_bytes);
-	if (status != ACLHIP_OK)
-		return status;
-	if (context == nullptr)
-		return fail(context, ACLHIP_ERROR_INVALID_ARGUMENT, "null context");
-	if (num_instances == 0)
-		return ACLHIP_OK;
-
-	device_guard guard(context->device);
-	return launch_skinning_matrices(context, poses, pose_stride_bytes, num_instances, *desc, palettes, palette_stride_bytes, static_cast<hipStream_t>(stream));
+		const bool transposed = desc->layout == ACLHIP_PALETTE_3X4F_TRANSPOSED_48;
+		const auto kernel = object_space
+			? (transposed ? skinning_matrices_kernel<true, k_palette_3x4f_transposed_48> : skinning_matrices_kernel<true, k_palette_3x4f_64>)
+			: (transposed ? skinning_matrices_kernel<false, k_palette_3x4f_transposed_48> : skinning_matrices_kernel<false, k_palette_3x4f_64>);
+		return launch_consumer_kernel(context, kernel, shape, num_blocks, 1, stream, launch);
+	});
 }

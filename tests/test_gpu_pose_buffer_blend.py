@@ -276,6 +276,24 @@ def test_parity_with_the_oracle(num_buffers, mode):
         assert ctx.negative_scale_count() == 0
 
 
+@pytest.mark.parametrize("object_space", [False, True])
+def test_rows_beyond_the_default_limit_of_dynamic_lds(object_space):
+    """rows of 1400 transforms: an image of 67 216 bytes, more dynamic LDS than a kernel gets without asking (65 408 bytes; BONES ends at
+    100) -- one instance per workgroup, 22 passes of 64 quads and a partial one; two buffers, three instances"""
+    rng = np.random.default_rng(7150 + int(object_space))
+    num_bones, n, num_buffers = 1400, 3, 2
+    parents = forest(rng, num_bones)
+    inputs, weights = random_inputs(rng, num_buffers, n, num_bones), blend_weights(rng, WEIGHTED, n, num_buffers)
+    rows = [expected_local([inputs[k][i] for k in range(num_buffers)], weights[i], [None] * num_buffers, WEIGHTED) for i in range(n)]
+    if object_space:
+        rows = [walked(parents, row) for row in rows]
+    with runtime.Context(0) as ctx:
+        skeleton = ctx.register_skeleton(parents, identity_pose(num_bones))
+        check(ctx, inputs, weights, WEIGHTED, rows, skeleton=skeleton, object_space=object_space)
+        assert ctx.rejected_instance_count() == 0
+        assert ctx.negative_scale_count() == 0
+
+
 # ---- 2. per instance skeletons ------------------------------------------------------------------------------------------------------
 
 @pytest.mark.parametrize("mode", [WEIGHTED, LAYERED])
