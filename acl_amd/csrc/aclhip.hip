@@ -97,6 +97,5 @@ using namespace aclhip;
 #include "host_raw_scalar_tracks.inl"
 #include "host_scalar_compress.inl"
 #include "host_transform_compress.inl"
-#include "host_tracks_compress.inl"
 #include "host_bone_object.inl"
 #include "host_scalar_misc.inl"

@@ -33,18 +33,22 @@ namespace
 	// What is written overlaps nothing that is read and no other output; the inputs are only read and may share bytes. The first pair that
 	// does: for each output in turn, every input, then every later output.
 	struct byte_range { const char* name; const void* pointer; unsigned __int128 bytes; };
-	aclhip_status check_no_overlap(const aclhip_context* context, std::initializer_list<byte_range> outputs, std::initializer_list<byte_range> inputs)
+	aclhip_status check_no_overlap(const aclhip_context* context, const byte_range* outputs, size_t num_outputs, const byte_range* inputs, size_t num_inputs)
 	{
-		for (const byte_range* output = outputs.begin(); output != outputs.end(); ++output)
+		for (const byte_range* output = outputs; output != outputs + num_outputs; ++output)
 		{
-			for (const byte_range& input : inputs)
-				if (byte_ranges_overlap(output->pointer, output->bytes, input.pointer, input.bytes))
-					return fail(context, ACLHIP_ERROR_INVALID_ARGUMENT, "%s overlap %s", output->name, input.name);
-			for (const byte_range* other = output + 1; other != outputs.end(); ++other)
+			for (const byte_range* input = inputs; input != inputs + num_inputs; ++input)
+				if (byte_ranges_overlap(output->pointer, output->bytes, input->pointer, input->bytes))
+					return fail(context, ACLHIP_ERROR_INVALID_ARGUMENT, "%s overlap %s", output->name, input->name);
+			for (const byte_range* other = output + 1; other != outputs + num_outputs; ++other)
 				if (byte_ranges_overlap(output->pointer, output->bytes, other->pointer, other->bytes))
 					return fail(context, ACLHIP_ERROR_INVALID_ARGUMENT, "%s overlap %s", output->name, other->name);
 		}
 		return ACLHIP_OK;
+	}
+	aclhip_status check_no_overlap(const aclhip_context* context, std::initializer_list<byte_range> outputs, std::initializer_list<byte_range> inputs)
+	{
+		return check_no_overlap(context, outputs.begin(), outputs.size(), inputs.begin(), inputs.size());
 	}
 
 	// The waves that share an instance's `units` (quads, floats or dwords of a row), units_per_wave to each and one at least. The wave

@@ -1,10 +1,21 @@
 // host_scalar_compress.inl -- part of aclhip.hip (one translation unit; included there behind host_raw_scalar_tracks.inl, not compiled on its own).
 // Host side of aclhip_compress_raw_scalar_tracks_batch (kernels_scalar_compress.inl): the two sizes a caller needs, the argument checks
-// and the five launches -- and what aclhip_compress_raw_tracks_batch (host_transform_compress.inl) does the same way, stated once for both
-// compressors: the common checks, the launches' shapes and their front. include/aclhip.h states the definitions.
+// and the five launches -- and what the two transform compressors (host_transform_compress.inl) do the same way, stated once for all
+// three: the cap of a size, the common checks, the launches' shapes, their front and their list of phases. include/aclhip.h states the
+// definitions.
 
 static_assert(sizeof(aclhip_scalar_compress_desc) == 48, "header layout");
 static_assert(sizeof(aclhip_compress_result) == 8, "header layout");
+
+namespace
+{
+	// A size computed 128 bits wide, rounded up to 16; what no address space holds is reported as the largest multiple of 16
+	uint64_t compress_size_of(unsigned __int128 bytes)
+	{
+		constexpr uint64_t largest = UINT64_MAX & ~uint64_t(15);
+		return bytes > largest ? largest : (uint64_t(bytes) + 15u) & ~uint64_t(15);
+	}
+}
 
 extern "C" uint64_t aclhip_scalar_compress_bound(uint32_t track_type, uint32_t num_tracks, uint32_t num_samples)
 {
@@ -18,15 +29,14 @@ extern "C" uint64_t aclhip_scalar_compress_bound(uint32_t track_type, uint32_t n
 
 extern "C" uint64_t aclhip_scalar_compress_workspace_bytes(uint32_t num_instances, uint32_t max_tracks)
 {
-	// (128 bits wide: 2^32 instances of 2^32 tracks do not wrap into a small number; what no address space holds is reported as the largest multiple of 16)
+	// (128 bits wide: 2^32 instances of 2^32 tracks do not wrap into a small number)
 	const unsigned __int128 per_track = sizeof(scalar_compress_track) + sizeof(scalar_compress_animated);
-	const unsigned __int128 bytes = (unsigned __int128)num_instances * sizeof(compress_instance) + (unsigned __int128)num_instances * max_tracks * per_track;
-	return bytes > (UINT64_MAX & ~uint64_t(15)) ? UINT64_MAX & ~uint64_t(15) : (uint64_t(bytes) + 15u) & ~uint64_t(15);
+	return compress_size_of((unsigned __int128)num_instances * sizeof(compress_instance) + (unsigned __int128)num_instances * max_tracks * per_track);
 }
 
 namespace
 {
-	// ---- what the two compressors do alike (host_transform_compress.inl is the other) -----------------------------------------------------
+	// ---- what the compressors do alike (host_transform_compress.inl holds the other two) ---------------------------------------------------
 
 	// What a compress launch checks of its arguments before any device call; every refusal leaves a message, with or without a context.
 	// In three parts, and a kind's own checks stand where they stood between them: the pointers and their alignment,
@@ -68,17 +78,19 @@ namespace
 		return ACLHIP_OK;
 	}
 
-	// and max_tracks with the ranges: what is written (`workspace_bytes`: the kind's own count) overlaps nothing that is read and no other output
-	template<class desc_type>
+	// and max_tracks with the ranges: what is written (`workspace_bytes`: the kind's own count) overlaps nothing that is read and no other
+	// output. `ranges` comes with three free places in front of what the kind reads: the three outputs every kind has are stated here.
+	template<class desc_type, size_t count>
 	aclhip_status check_compress_ranges(aclhip_context* context, const char* kind, const desc_type& desc, uint64_t workspace_bytes, uint32_t num_instances, const void* blobs,
-		uint64_t blob_stride_bytes, const aclhip_compress_result* results, std::initializer_list<byte_range> inputs)
+		uint64_t blob_stride_bytes, const aclhip_compress_result* results, byte_range (&ranges)[count])
 	{
 		if (desc.max_tracks == 0)
 			return fail(context, ACLHIP_ERROR_INVALID_ARGUMENT, "a %s compress desc of 0 max_tracks", kind);
 		const unsigned __int128 n = num_instances;
-		return check_no_overlap(context,
-			{ { "the blob rows", blobs, n * blob_stride_bytes }, { "the compress results", results, n * sizeof(aclhip_compress_result) }, { "the workspace", desc.workspace, workspace_bytes } },
-			inputs);
+		ranges[0] = { "the blob rows", blobs, n * blob_stride_bytes };
+		ranges[1] = { "the compress results", results, n * sizeof(aclhip_compress_result) };
+		ranges[2] = { "the workspace", desc.workspace, workspace_bytes };
+		return check_no_overlap(context, ranges, 3, ranges + 3, count - 3);
 	}
 
 	// The shapes of a compressor's launches. They come from the arguments alone -- the handles live on the device --: the analysis takes
@@ -90,7 +102,7 @@ namespace
 		uint32_t waves_per_instance;		// the stream's
 		uint32_t instance_blocks, stream_blocks;
 		dim3 track_blocks;					// (tracks, instances)
-		int phases;							// measurement knob: only the first k launches -- what each phase costs (tools/scalar_compress.py, tools/transform_compress.py)
+		int phases;							// measurement knob: only the first k launches -- what each phase costs (tools/scalar_compress.py, tools/transform_compress.py, tools/compress_tracks.py)
 	};
 	compress_launch_shape compress_launch_shape_of(uint32_t num_instances, uint32_t max_tracks, uint64_t blob_stride_bytes, const char* phases_knob_name)
 	{
@@ -104,7 +116,7 @@ namespace
 		return shape;
 	}
 
-	// The front of both entry points behind their checks: the batch of none, the device, the registry lock (shared: see launch_tracks)
+	// The front of the entry points behind their checks: the batch of none, the device, the registry lock (shared: see launch_tracks)
 	// and the table. `launch(stream)` is the kind's own list of kernels, in stream order: each reads what the one before it left in the
 	// workspace. Nothing is uploaded.
 	template<class table_type, class launch_function>
@@ -123,6 +135,34 @@ namespace
 		return launch(stream);
 	}
 
+	// One launch of that list: a kernel that takes its launch record by value, with its grid and block
+	struct compress_phase
+	{
+		const void* kernel;
+		dim3 grid, block;
+		const void* record;
+		template<class record_type>
+		compress_phase(void (*kernel)(record_type), dim3 grid, dim3 block, const record_type& record)
+			: kernel(reinterpret_cast<const void*>(kernel)), grid(grid), block(block), record(&record) {}
+		void operator()(hipStream_t stream) const
+		{
+			void* arguments[] = { const_cast<void*>(record) };
+			(void)hipLaunchKernel(kernel, grid, block, arguments, 0, stream);		// (what it returns is what hipGetLastError() gives next)
+		}
+	};
+
+	// The first `phases` (compress_launch_shape::phases) of a call's launches, in stream order, each asked for its error. The first one
+	// always runs: a knob below 1 counts as 1.
+	aclhip_status launch_compress_phases(aclhip_context* context, hipStream_t stream, int phases, const compress_phase* launches, int count)
+	{
+		for (int k = 0; k < count && k < std::max(phases, 1); ++k)
+		{
+			launches[k](stream);
+			ACLHIP_CHECK_HIP(context, hipGetLastError());
+		}
+		return ACLHIP_OK;
+	}
+
 	// ---- the scalar compressor ---------------------------------------------------------------------------------------------------------
 
 	aclhip_status check_scalar_compress(aclhip_context* context, const aclhip_raw_scalar_tracks* raws, uint32_t num_instances, const aclhip_scalar_compress_desc* desc,
@@ -134,12 +174,13 @@ namespace
 			return status;
 		if (desc->track_precisions != nullptr && desc->num_track_precisions == 0)
 			return fail(context, ACLHIP_ERROR_INVALID_ARGUMENT, "track_precisions with a count of 0");
-		const unsigned __int128 n = num_instances;
-		return check_compress_ranges(context, "scalar", *desc, aclhip_scalar_compress_workspace_bytes(num_instances, desc->max_tracks), num_instances, blobs, blob_stride_bytes, results,
-			{
-				{ "the raw scalar track handles", raws, n * sizeof(aclhip_raw_scalar_tracks) },
-				{ "the track precisions", desc->track_precisions, desc->track_precisions != nullptr ? (unsigned __int128)desc->num_track_precisions * sizeof(float) : 0 },
-			});
+		byte_range ranges[] =
+		{
+			{}, {}, {},
+			{ "the raw scalar track handles", raws, (unsigned __int128)num_instances * sizeof(aclhip_raw_scalar_tracks) },
+			{ "the track precisions", desc->track_precisions, desc->track_precisions != nullptr ? (unsigned __int128)desc->num_track_precisions * sizeof(float) : 0 },
+		};
+		return check_compress_ranges(context, "scalar", *desc, aclhip_scalar_compress_workspace_bytes(num_instances, desc->max_tracks), num_instances, blobs, blob_stride_bytes, results, ranges);
 	}
 }
 
@@ -174,28 +215,15 @@ extern "C" aclhip_status aclhip_compress_raw_scalar_tracks_batch(aclhip_context*
 		launch.rejected_count = context->d_rejected;
 		const compress_hash_launch hash_launch = { launch.instances, num_instances, launch.blobs, blob_stride_bytes };
 
-		hipLaunchKernelGGL(scalar_compress_prepare_kernel, dim3(shape.instance_blocks), dim3(shape.block_size), 0, stream, launch);
-		ACLHIP_CHECK_HIP(context, hipGetLastError());
-		if (shape.phases >= 2)
+		const dim3 block(shape.block_size);
+		const compress_phase phases[] =
 		{
-			hipLaunchKernelGGL(scalar_compress_analyze_kernel, shape.track_blocks, dim3(shape.block_size), 0, stream, launch);
-			ACLHIP_CHECK_HIP(context, hipGetLastError());
-		}
-		if (shape.phases >= 3)
-		{
-			hipLaunchKernelGGL(scalar_compress_layout_kernel, dim3(shape.instance_blocks), dim3(shape.block_size), 0, stream, launch);
-			ACLHIP_CHECK_HIP(context, hipGetLastError());
-		}
-		if (shape.phases >= 4)
-		{
-			hipLaunchKernelGGL(scalar_compress_write_kernel, dim3(shape.stream_blocks), dim3(shape.block_size), 0, stream, launch);
-			ACLHIP_CHECK_HIP(context, hipGetLastError());
-		}
-		if (shape.phases >= 5)
-		{
-			hipLaunchKernelGGL(compress_hash_kernel, dim3(num_instances), dim3(k_wave_size), 0, stream, hash_launch);
-			ACLHIP_CHECK_HIP(context, hipGetLastError());
-		}
-		return ACLHIP_OK;
+			{ scalar_compress_prepare_kernel, dim3(shape.instance_blocks), block, launch },
+			{ scalar_compress_analyze_kernel, shape.track_blocks, block, launch },
+			{ scalar_compress_layout_kernel, dim3(shape.instance_blocks), block, launch },
+			{ scalar_compress_write_kernel, dim3(shape.stream_blocks), block, launch },
+			{ compress_hash_kernel, dim3(num_instances), dim3(k_wave_size), hash_launch },
+		};
+		return launch_compress_phases(context, stream, shape.phases, phases, 5);
 	});
 }

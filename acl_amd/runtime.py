@@ -1778,25 +1778,16 @@ def transform_compress_workspace_bytes(num_instances, max_tracks):
     return int(load_library().aclhip_transform_compress_workspace_bytes(int(num_instances), int(max_tracks)))
 
 
-def compress_raw_tracks(ctx, raws, default_pose=None, parents=None, precision=1.0e-4, shell_distance=1.0, track_precisions=None, track_shell_distances=None,
-                        include_parent_track_indices=False, include_track_descriptions=False):
-    """acl::compress_track_list with the reference's raw compression settings (quatf_full, vector3f_full, vector3f_full) for raw track
-    arrays as one launch: `raws` is a handle or a list of handles (register_raw_tracks; they may repeat and differ in shape). default_pose
-    float32 [tracks, 12] (QVV48; None: the identity), parents uint32 [tracks] (NO_PARENT for a root; None: every track a root),
-    track_precisions and track_shell_distances float32 [tracks] are shared by the arrays and hold at least as many tracks as the largest;
-    parents, precisions and shell distances only reach the optional metadata. Rows are sized from aclhip_transform_compress_bound, the
-    workspace is allocated, the results and the blobs are copied back: returns a list of 16 byte aligned numpy uint8 blobs, byte for
-    byte the reference's and lossless. Raises RuntimeError with the reference's message when a sample is not finite, ValueError when a
-    rotation is not normalized (ACLHIP_COMPRESS_NOT_NORMALIZED) or an instance is refused. Synchronous; the buffers are torch tensors on
-    the context's device."""
+def _compress_transform_tracks(ctx, launch, workspace_bytes, desc, raws, flags, default_pose, parents, precision, shell_distance, track_precisions, track_shell_distances):
+    """What compress_raw_tracks and compress_tracks share: `desc` (either struct: the fields have one name in both) comes with its formats
+    and gets the flag word, max_tracks, the two settings and the four per-track tables, uploaded; `launch` is the context's method,
+    `workspace_bytes` the size function of its workspace."""
     import torch
     handles = np.atleast_1d(np.asarray(raws, dtype=np.uint32))
     infos = [ctx.raw_tracks_info(int(handle)) for handle in handles]
     if len(handles) == 0:
         return []
-    flags = (COMPRESS_INCLUDE_PARENT_TRACK_INDICES if include_parent_track_indices else 0) | (COMPRESS_INCLUDE_TRACK_DESCRIPTIONS if include_track_descriptions else 0)
     stride = max(transform_compress_bound(info.num_tracks, info.num_samples, flags) for info in infos)
-    desc = TransformCompressDesc()
     desc.flags, desc.max_tracks, desc.precision, desc.shell_distance = flags, max(int(info.num_tracks) for info in infos), float(precision), float(shell_distance)
     tables = []         # (kept alive until the launch has run)
     for field, table, dtype, width in (("default_pose", default_pose, np.float32, 12), ("parent_indices", parents, np.uint32, 1),
@@ -1810,8 +1801,23 @@ def compress_raw_tracks(ctx, raws, default_pose=None, parents=None, precision=1.
         tables.append((d_table, host.shape[0]))
         setattr(desc, field, d_table.data_ptr())
         desc.num_table_tracks = host.shape[0]
-    return _compress_batch(ctx, ctx.compress_raw_tracks_batch, handles, "raw track array", stride,
-                           transform_compress_workspace_bytes(len(handles), desc.max_tracks), desc)
+    return _compress_batch(ctx, launch, handles, "raw track array", stride, workspace_bytes(len(handles), desc.max_tracks), desc)
+
+
+def compress_raw_tracks(ctx, raws, default_pose=None, parents=None, precision=1.0e-4, shell_distance=1.0, track_precisions=None, track_shell_distances=None,
+                        include_parent_track_indices=False, include_track_descriptions=False):
+    """acl::compress_track_list with the reference's raw compression settings (quatf_full, vector3f_full, vector3f_full) for raw track
+    arrays as one launch: `raws` is a handle or a list of handles (register_raw_tracks; they may repeat and differ in shape). default_pose
+    float32 [tracks, 12] (QVV48; None: the identity), parents uint32 [tracks] (NO_PARENT for a root; None: every track a root),
+    track_precisions and track_shell_distances float32 [tracks] are shared by the arrays and hold at least as many tracks as the largest;
+    parents, precisions and shell distances only reach the optional metadata. Rows are sized from aclhip_transform_compress_bound, the
+    workspace is allocated, the results and the blobs are copied back: returns a list of 16 byte aligned numpy uint8 blobs, byte for
+    byte the reference's and lossless. Raises RuntimeError with the reference's message when a sample is not finite, ValueError when a
+    rotation is not normalized (ACLHIP_COMPRESS_NOT_NORMALIZED) or an instance is refused. Synchronous; the buffers are torch tensors on
+    the context's device."""
+    flags = (COMPRESS_INCLUDE_PARENT_TRACK_INDICES if include_parent_track_indices else 0) | (COMPRESS_INCLUDE_TRACK_DESCRIPTIONS if include_track_descriptions else 0)
+    return _compress_transform_tracks(ctx, ctx.compress_raw_tracks_batch, transform_compress_workspace_bytes, TransformCompressDesc(), raws, flags, default_pose, parents,
+                                      precision, shell_distance, track_precisions, track_shell_distances)
 
 
 def compress_tracks_workspace_bytes(num_instances, max_tracks):
@@ -1827,31 +1833,12 @@ def compress_tracks(ctx, raws, rotation_format=ROTATION_QUATF_DROP_W_FULL, defau
     every parent index is smaller than its child's. Rows are sized from aclhip_transform_compress_bound. Returns a list of 16 byte
     aligned numpy uint8 blobs. Raises RuntimeError with the reference's message when a sample is not finite (a zero quaternion
     included), ValueError when an instance is refused. Synchronous; the buffers are torch tensors on the context's device."""
-    import torch
-    handles = np.atleast_1d(np.asarray(raws, dtype=np.uint32))
-    infos = [ctx.raw_tracks_info(int(handle)) for handle in handles]
-    if len(handles) == 0:
-        return []
     flags = ((COMPRESS_OPTIMIZE_LOOPS if optimize_loops else 0) | (COMPRESS_INCLUDE_PARENT_TRACK_INDICES if include_parent_track_indices else 0)
              | (COMPRESS_INCLUDE_TRACK_DESCRIPTIONS if include_track_descriptions else 0))
-    stride = max(transform_compress_bound(info.num_tracks, info.num_samples, flags) for info in infos)
     desc = CompressTracksDesc()
     desc.rotation_format, desc.translation_format, desc.scale_format = int(rotation_format), VECTOR_VECTOR3F_FULL, VECTOR_VECTOR3F_FULL
-    desc.flags, desc.max_tracks, desc.precision, desc.shell_distance = flags, max(int(info.num_tracks) for info in infos), float(precision), float(shell_distance)
-    tables = []         # (kept alive until the launch has run)
-    for field, table, dtype, width in (("default_pose", default_pose, np.float32, 12), ("parent_indices", parents, np.uint32, 1),
-                                       ("track_precisions", track_precisions, np.float32, 1), ("track_shell_distances", track_shell_distances, np.float32, 1)):
-        if table is None:
-            continue
-        host = np.ascontiguousarray(table, dtype=dtype).reshape(-1, width)
-        if tables and host.shape[0] != tables[0][1]:
-            raise ValueError("default_pose, parents, track_precisions and track_shell_distances hold the same number of tracks")
-        d_table = torch.from_numpy(host.view(np.int32) if dtype is np.uint32 else host).to(torch.device("cuda", ctx.device_index))
-        tables.append((d_table, host.shape[0]))
-        setattr(desc, field, d_table.data_ptr())
-        desc.num_table_tracks = host.shape[0]
-    return _compress_batch(ctx, ctx.compress_tracks_batch, handles, "raw track array", stride,
-                           compress_tracks_workspace_bytes(len(handles), desc.max_tracks), desc)
+    return _compress_transform_tracks(ctx, ctx.compress_tracks_batch, compress_tracks_workspace_bytes, desc, raws, flags, default_pose, parents, precision, shell_distance,
+                                      track_precisions, track_shell_distances)
 
 
 def scalar_clip_error(ctx, clip_a, clip_b):

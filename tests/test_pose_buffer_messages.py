@@ -13,62 +13,19 @@ Per entry point the file holds `base`, the C arguments in order of a call that p
 that are not 0, `bounds` in it an object of aclhip_pose_bounds' fields), and every call as its differences from them -- "<index>": a C
 argument, "<name>": a field of the struct -- under the message it was refused with (`recorded`) or under the two checks that fail in it
 (`two_at_once`: [differences, message]). Every status is `status`."""
-import copy
-import ctypes
 import json
 import os
 
 import pytest
 
 from acl_amd import runtime
+from message_replay import arguments_of, replay
 
 with open(os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "pose_buffer_messages.json")) as file:
     FIXTURE = json.load(file)
 STATUS = FIXTURE.pop("status")
 FUNCTIONS = ("aclhip_transform_poses_batch", "aclhip_blend_poses_batch", "aclhip_inverse_transform_poses_batch", "aclhip_measure_pose_error_batch",
              "aclhip_measure_pose_error_metric_batch", "aclhip_pose_matrices_batch", "aclhip_skinning_matrices_batch")
-
-
-def struct_of(struct_type, fields, alive):
-    """the ctypes struct of a recorded object; a nested object is a struct of its own, kept in `alive`, that the field points to"""
-    struct = struct_type()
-    for name, value in fields.items():
-        if isinstance(value, dict):
-            nested = struct_of(runtime.PoseBounds, value, alive)
-            alive.append(nested)
-            setattr(struct, name, ctypes.addressof(nested))
-        elif isinstance(value, list):
-            array = getattr(struct, name)
-            for index, element in enumerate(value):
-                array[index] = element
-        else:
-            setattr(struct, name, value)
-    return struct
-
-
-def arguments_of(base, changes):
-    """the C arguments of a recorded call"""
-    arguments = copy.deepcopy(base)
-    struct = next(index for index, argument in enumerate(base) if isinstance(argument, dict))
-    for key, value in changes.items():
-        if key.isdigit():
-            arguments[int(key)] = value
-        else:
-            arguments[struct][key] = value
-    return arguments
-
-
-def replay(lib, entry):
-    """(status, message) of a call: entry["function"] with entry["arguments"]"""
-    function = getattr(lib, entry["function"])
-    alive, arguments = [], []
-    for argument, argument_type in zip(entry["arguments"], function.argtypes):
-        if isinstance(argument, dict):
-            alive.append(struct_of(argument_type._type_, argument, alive))
-            argument = ctypes.byref(alive[-1])
-        arguments.append(argument)
-    status = function(*arguments)
-    return status, lib.aclhip_last_error_message(None).decode()
 
 
 def test_the_recording_covers_every_entry_point_and_pairs_of_failing_checks():
