@@ -67,6 +67,7 @@ namespace aclhip
 #include "kernels_scalar_compress.inl"
 #include "kernels_transform_compress.inl"
 #include "kernels_tracks_compress.inl"
+#include "kernels_variable_compress.inl"
 #include "kernels_misc.inl"
 #include "kernels_scalar.inl"
 #include "kernels_track.inl"

@@ -1,7 +1,9 @@
 // host_transform_compress.inl -- part of aclhip.hip (one translation unit; included there behind host_scalar_compress.inl, not compiled on its own).
-// Host side of the two transform compressors, aclhip_compress_raw_tracks_batch (kernels_transform_compress.inl) and
-// aclhip_compress_tracks_batch (kernels_tracks_compress.inl): the sizes a caller needs, and one argument check, one workspace layout,
-// one launch record and one list of launches for both -- the raw call is the other with the full formats, no shell and its own words.
+// Host side of the three transform compressors, aclhip_compress_raw_tracks_batch (kernels_transform_compress.inl),
+// aclhip_compress_tracks_batch (kernels_tracks_compress.inl) and aclhip_compress_tracks_variable_batch (kernels_variable_compress.inl):
+// the sizes a caller needs, and one argument check, one workspace layout and one launch record for all -- the raw call is the drop-w
+// call with the full formats, no shell and its own words; the variable call is it with its own kernels behind the shell, its rate
+// table and three more parts of the workspace.
 // What they share with the scalar compressor -- the cap of a size, the common checks, the launches' shapes, their front and their list
 // of phases -- is in host_scalar_compress.inl. include/aclhip.h states the definitions.
 
@@ -22,18 +24,23 @@ namespace
 
 	// The workspace: where each part begins and where the last one ends, each part rounded up to 16 bytes (128 bits wide: see
 	// aclhip_scalar_compress_workspace_bytes). The raw call has the first three parts, aclhip_compress_tracks_batch the shells
-	// ({ local shell distance, precision } per instance and track) behind them. The size functions and the launch record both read it.
+	// ({ local shell distance, precision } per instance and track) behind them, aclhip_compress_tracks_variable_batch behind those the
+	// clip ranges (18 floats per instance and track) and, per instance and segment of max_samples (max_segments; 0: none of the three),
+	// a variable_segment and the prefix sums (a dword per sub-track). The size functions and the launch record both read it.
 	struct transform_workspace_layout
 	{
-		unsigned __int128 instances = 0, track_flags, animated, shells, total;
-		transform_workspace_layout(uint32_t num_instances, uint32_t max_tracks, bool with_shells)
+		unsigned __int128 instances = 0, track_flags, animated, shells, clip_ranges, segments, prefix, total;
+		transform_workspace_layout(uint32_t num_instances, uint32_t max_tracks, bool with_shells, uint32_t max_segments = 0)
 		{
 			const auto part = [](unsigned __int128 bytes) { return (bytes + 15u) & ~(unsigned __int128)15; };
 			const unsigned __int128 n = num_instances;
 			track_flags = instances + part(n * sizeof(compress_instance));
 			animated = track_flags + part(n * max_tracks);
 			shells = animated + part(n * max_tracks * 3u * sizeof(uint16_t));
-			total = shells + (with_shells ? part(n * max_tracks * sizeof(float2)) : 0);
+			clip_ranges = shells + (with_shells ? part(n * max_tracks * sizeof(float2)) : 0);
+			segments = clip_ranges + (max_segments != 0 ? part(n * max_tracks * k_variable_range_floats * sizeof(float)) : 0);
+			prefix = segments + part(n * max_segments * sizeof(variable_segment));
+			total = prefix + part(n * max_segments * max_tracks * 3u * sizeof(uint32_t));
 		}
 	};
 }
@@ -61,11 +68,38 @@ extern "C" uint64_t aclhip_compress_tracks_workspace_bytes(uint32_t num_instance
 	return compress_size_of(transform_workspace_layout(num_instances, max_tracks, true).total);
 }
 
+extern "C" uint32_t aclhip_variable_compress_num_segments(uint32_t num_samples)
+{
+	return variable_split_of(num_samples).num_segments;
+}
+
+extern "C" uint64_t aclhip_variable_compress_bound(uint32_t num_tracks, uint32_t num_samples, uint32_t flags)
+{
+	// every sub-track animated at rate 24: headers, start indices, segment headers, types, 24 bytes of clip range per sub-track; per
+	// segment a format byte per sub-track (rotations padded to 4), the byte to an even offset, 6 range bytes per padded sub-track, up
+	// to 3 bytes to the stream; 36 bytes per track and sample; up to 3 bytes to the metadata, or the tail
+	const unsigned __int128 tracks = num_tracks, segments = variable_split_of(num_samples).num_segments;
+	const unsigned __int128 num_variable = ((tracks + 3u) & ~(unsigned __int128)3) + 2u * tracks;
+	unsigned __int128 bytes = k_transform_header_offset + k_segment_start_indices_offset + (segments > 1 ? 4u * (segments + 1u) : 0u) + 16u * segments
+		+ 12u * ((tracks + 15u) / 16u) + 72u * tracks + segments * (num_variable + 1u + (segments > 1 ? 6u * num_variable : 0u) + 3u) + 36u * tracks * num_samples;
+	if ((flags & (ACLHIP_COMPRESS_INCLUDE_PARENT_TRACK_INDICES | ACLHIP_COMPRESS_INCLUDE_TRACK_DESCRIPTIONS)) != 0)
+		bytes += 3u + 4u * tracks + ((flags & ACLHIP_COMPRESS_INCLUDE_TRACK_DESCRIPTIONS) != 0 ? 48u * tracks : 0u) + sizeof(optional_metadata_header);
+	else
+		bytes += 15u;
+	return compress_size_of(bytes);
+}
+
+extern "C" uint64_t aclhip_compress_variable_workspace_bytes(uint32_t num_instances, uint32_t max_tracks, uint32_t max_samples)
+{
+	return compress_size_of(transform_workspace_layout(num_instances, max_tracks, true, variable_split_of(std::max(max_samples, 1u)).num_segments).total);
+}
+
 namespace
 {
-	// What an entry point says of itself: the word of its messages, the knob of its phases and whether its workspace holds shells. The
-	// rest of what tells the two apart is in the desc: the formats and the shell metadata, 0 for the raw call.
-	struct transform_compress_kind { const char* name; const char* phases_knob; bool with_shells; };
+	// What an entry point says of itself: the word of its messages, the knob of its phases, whether its workspace holds shells and the
+	// segments it holds the variable call's parts for (0: none). The rest of what tells the raw and the drop-w call apart is in the
+	// desc: the formats and the shell metadata, 0 for the raw call.
+	struct transform_compress_kind { const char* name; const char* phases_knob; bool with_shells; uint32_t max_segments = 0; };
 
 	// The kernels between the shell and the hash, per rotation format: quatf_full (the raw call's), quatf_drop_w_full
 	struct transform_compress_kernels { void (*analyze)(transform_compress_launch), (*layout)(transform_compress_launch), (*stream)(transform_compress_launch); };
@@ -120,7 +154,7 @@ namespace
 			{ "the track precisions", desc->track_precisions, desc->track_precisions != nullptr ? table * sizeof(float) : 0 },
 			{ "the track shell distances", desc->track_shell_distances, desc->track_shell_distances != nullptr ? table * sizeof(float) : 0 },
 		};
-		const uint64_t workspace_bytes = compress_size_of(transform_workspace_layout(num_instances, desc->max_tracks, kind.with_shells).total);
+		const uint64_t workspace_bytes = compress_size_of(transform_workspace_layout(num_instances, desc->max_tracks, kind.with_shells, kind.max_segments).total);
 		if (const aclhip_status status = check_compress_ranges(context, kind.name, *desc, workspace_bytes, num_instances, blobs, blob_stride_bytes, results, ranges); status != ACLHIP_OK)
 			return status;
 		// the fourth output, in a pass of its own behind that one: it overlaps no other and nothing that is read
@@ -128,8 +162,40 @@ namespace
 		return check_no_overlap(context, &shell_metadata, 1, ranges, 8);
 	}
 
-	// Both entry points behind their own words: the check, the launch record and the launches -- four for quatf_full (the raw call's), the
-	// shell in front of them and its own analysis for quatf_drop_w_full.
+	// The launch record of a checked call: the tables, the settings and where the workspace's parts lie
+	transform_compress_launch transform_compress_launch_of(aclhip_context* context, const aclhip_raw_tracks* raws, uint32_t num_instances, const aclhip_compress_tracks_desc* desc,
+		void* blobs, uint64_t blob_stride_bytes, aclhip_compress_result* results, const compress_launch_shape& shape, const transform_workspace_layout& layout, bool with_shells)
+	{
+		uint8_t* workspace = static_cast<uint8_t*>(desc->workspace);
+		transform_compress_launch launch = {};
+		launch.arrays = context->raw_tracks.d_records;
+		launch.num_arrays = ACLHIP_MAX_RAW_TRACKS;
+		launch.num_instances = num_instances;
+		launch.raws = raws;
+		launch.default_pose = static_cast<const f32x4*>(desc->default_pose);
+		launch.parent_indices = desc->parent_indices;
+		launch.track_precisions = desc->track_precisions;
+		launch.track_shell_distances = desc->track_shell_distances;
+		launch.table_tracks = transform_compress_has_table(*desc) ? desc->num_table_tracks : 0xFFFFFFFFu;
+		launch.flags = desc->flags;
+		launch.precision = desc->precision;
+		launch.shell_distance = desc->shell_distance;
+		launch.max_tracks = desc->max_tracks;
+		launch.instances = reinterpret_cast<compress_instance*>(workspace + uint64_t(layout.instances));
+		launch.track_flags = workspace + uint64_t(layout.track_flags);
+		launch.animated = reinterpret_cast<uint16_t*>(workspace + uint64_t(layout.animated));
+		launch.shells = with_shells ? reinterpret_cast<float2*>(workspace + uint64_t(layout.shells)) : nullptr;
+		launch.shell_metadata = static_cast<float2*>(desc->shell_metadata);
+		launch.blobs = static_cast<uint8_t*>(blobs);
+		launch.blob_stride_bytes = blob_stride_bytes;
+		launch.results = reinterpret_cast<uint2*>(results);
+		launch.waves_per_instance = shape.waves_per_instance;
+		launch.rejected_count = context->d_rejected;
+		return launch;
+	}
+
+	// The raw and the drop-w entry point behind their own words: the check, the launch record and the launches -- four for quatf_full
+	// (the raw call's), the shell in front of them and its own analysis for quatf_drop_w_full.
 	aclhip_status compress_transform_tracks(aclhip_context* context, const transform_compress_kind& kind, const aclhip_raw_tracks* raws, uint32_t num_instances,
 		const aclhip_compress_tracks_desc* desc, void* blobs, uint64_t blob_stride_bytes, aclhip_compress_result* results, void* stream_handle)
 	{
@@ -140,31 +206,7 @@ namespace
 		{
 			const compress_launch_shape shape = compress_launch_shape_of(num_instances, desc->max_tracks, blob_stride_bytes, kind.phases_knob);
 			const transform_workspace_layout layout(num_instances, desc->max_tracks, kind.with_shells);
-			uint8_t* workspace = static_cast<uint8_t*>(desc->workspace);
-			transform_compress_launch launch = {};
-			launch.arrays = context->raw_tracks.d_records;
-			launch.num_arrays = ACLHIP_MAX_RAW_TRACKS;
-			launch.num_instances = num_instances;
-			launch.raws = raws;
-			launch.default_pose = static_cast<const f32x4*>(desc->default_pose);
-			launch.parent_indices = desc->parent_indices;
-			launch.track_precisions = desc->track_precisions;
-			launch.track_shell_distances = desc->track_shell_distances;
-			launch.table_tracks = transform_compress_has_table(*desc) ? desc->num_table_tracks : 0xFFFFFFFFu;
-			launch.flags = desc->flags;
-			launch.precision = desc->precision;
-			launch.shell_distance = desc->shell_distance;
-			launch.max_tracks = desc->max_tracks;
-			launch.instances = reinterpret_cast<compress_instance*>(workspace + uint64_t(layout.instances));
-			launch.track_flags = workspace + uint64_t(layout.track_flags);
-			launch.animated = reinterpret_cast<uint16_t*>(workspace + uint64_t(layout.animated));
-			launch.shells = kind.with_shells ? reinterpret_cast<float2*>(workspace + uint64_t(layout.shells)) : nullptr;
-			launch.shell_metadata = static_cast<float2*>(desc->shell_metadata);
-			launch.blobs = static_cast<uint8_t*>(blobs);
-			launch.blob_stride_bytes = blob_stride_bytes;
-			launch.results = reinterpret_cast<uint2*>(results);
-			launch.waves_per_instance = shape.waves_per_instance;
-			launch.rejected_count = context->d_rejected;
+			const transform_compress_launch launch = transform_compress_launch_of(context, raws, num_instances, desc, blobs, blob_stride_bytes, results, shape, layout, kind.with_shells);
 			const compress_hash_launch hash_launch = { launch.instances, num_instances, launch.blobs, blob_stride_bytes };
 
 			// (the phases knob counts the call's own launches: four for quatf_full, five for quatf_drop_w_full)
@@ -180,6 +222,91 @@ namespace
 				{ compress_hash_kernel, dim3(num_instances), dim3(k_wave_size), hash_launch },
 			};
 			return launch_compress_phases(context, stream, shape.phases, phases + (drop_w ? 0 : 1), drop_w ? 5 : 4);
+		});
+	}
+
+	// The variable call: its desc as the drop-w one for the shared check (quatf_drop_w_full passes the format clauses: the call has no
+	// formats to choose), its own checks behind it, and its six launches.
+	aclhip_status compress_variable_tracks(aclhip_context* context, const aclhip_raw_tracks* raws, uint32_t num_instances, const aclhip_compress_variable_desc* desc,
+		void* blobs, uint64_t blob_stride_bytes, aclhip_compress_result* results, void* stream_handle)
+	{
+		aclhip_compress_tracks_desc as_tracks = {};
+		if (desc != nullptr)
+		{
+			as_tracks.rotation_format = k_rotation_quatf_drop_w_full;
+			as_tracks.flags = desc->flags;
+			as_tracks.max_tracks = desc->max_tracks;
+			as_tracks.num_table_tracks = desc->num_table_tracks;
+			as_tracks.default_pose = desc->default_pose;
+			as_tracks.parent_indices = desc->parent_indices;
+			as_tracks.track_precisions = desc->track_precisions;
+			as_tracks.track_shell_distances = desc->track_shell_distances;
+			as_tracks.precision = desc->precision;
+			as_tracks.shell_distance = desc->shell_distance;
+			as_tracks.workspace = desc->workspace;
+			as_tracks.shell_metadata = desc->shell_metadata;
+			as_tracks.reserved[0] = desc->reserved[0] | desc->reserved_rate | desc->reserved_word;
+			as_tracks.reserved[1] = desc->reserved[1];
+		}
+		const uint32_t max_segments = desc != nullptr ? variable_split_of(std::max(desc->max_samples, 1u)).num_segments : 1u;
+		const transform_compress_kind kind = { "variable", "ACLHIP_VARIABLE_COMPRESS_PHASES", true, max_segments };
+		if (const aclhip_status status = check_transform_compress(context, kind, raws, num_instances, desc != nullptr ? &as_tracks : nullptr, blobs, blob_stride_bytes, results); status != ACLHIP_OK)
+			return status;
+		if (desc->max_samples == 0)
+			return fail(context, ACLHIP_ERROR_INVALID_ARGUMENT, "a variable compress desc of 0 max_samples");
+		if ((reinterpret_cast<uintptr_t>(desc->bit_rates) & 3u) != 0)
+			return fail(context, ACLHIP_ERROR_INVALID_ARGUMENT, "the bit rate table must be 4 byte aligned");
+		if (desc->bit_rates != nullptr && ((desc->bit_rate_instance_stride | desc->bit_rate_segment_stride) & 3u) != 0)
+			return fail(context, ACLHIP_ERROR_INVALID_ARGUMENT, "the strides of the bit rate table are multiples of 4");
+		if (desc->bit_rates == nullptr && (desc->rotation_bit_rate > k_variable_raw_rate || desc->translation_bit_rate > k_variable_raw_rate || desc->scale_bit_rate > k_variable_raw_rate))
+			return fail(context, ACLHIP_ERROR_INVALID_ARGUMENT, "uniform bit rates of %u, %u and %u: 0 to 24", desc->rotation_bit_rate, desc->translation_bit_rate, desc->scale_bit_rate);
+		const transform_workspace_layout layout(num_instances, desc->max_tracks, true, max_segments);
+		if (desc->bit_rates != nullptr)
+		{
+			const unsigned __int128 n = num_instances;
+			const unsigned __int128 table_bytes = (n - (n != 0 ? 1u : 0u)) * desc->bit_rate_instance_stride + (unsigned __int128)(max_segments - 1u) * desc->bit_rate_segment_stride + 4u * (unsigned __int128)desc->max_tracks;
+			const byte_range table = { "the bit rate table", desc->bit_rates, table_bytes };
+			const byte_range written[] =
+			{
+				{ "the blob rows", blobs, n * blob_stride_bytes },
+				{ "the compress results", results, n * sizeof(aclhip_compress_result) },
+				{ "the workspace", desc->workspace, compress_size_of(layout.total) },
+				{ "the shell metadata", desc->shell_metadata, desc->shell_metadata != nullptr ? n * desc->max_tracks * sizeof(float2) : 0 },
+			};
+			if (const aclhip_status status = check_no_overlap(context, written, 4, &table, 1); status != ACLHIP_OK)
+				return status;
+		}
+		return launch_compress(context, &aclhip_context::raw_tracks, num_instances, stream_handle, [&](hipStream_t stream) -> aclhip_status
+		{
+			const compress_launch_shape shape = compress_launch_shape_of(num_instances, desc->max_tracks, blob_stride_bytes, kind.phases_knob);
+			uint8_t* workspace = static_cast<uint8_t*>(desc->workspace);
+			variable_compress_launch launch = {};
+			launch.base = transform_compress_launch_of(context, raws, num_instances, &as_tracks, blobs, blob_stride_bytes, results, shape, layout, true);
+			launch.bit_rates = desc->bit_rates;
+			launch.bit_rate_instance_stride = desc->bit_rate_instance_stride;
+			launch.bit_rate_segment_stride = desc->bit_rate_segment_stride;
+			launch.uniform_rates = uint32_t(desc->rotation_bit_rate) | (uint32_t(desc->translation_bit_rate) << 8) | (uint32_t(desc->scale_bit_rate) << 16);
+			launch.max_samples = desc->max_samples;
+			launch.max_segments = max_segments;
+			launch.clip_ranges = reinterpret_cast<float*>(workspace + uint64_t(layout.clip_ranges));
+			launch.segments = reinterpret_cast<variable_segment*>(workspace + uint64_t(layout.segments));
+			launch.prefix = reinterpret_cast<uint32_t*>(workspace + uint64_t(layout.prefix));
+			const compress_hash_launch hash_launch = { launch.base.instances, num_instances, launch.base.blobs, blob_stride_bytes };
+
+			// the segment ranges: a wave per (instance, segment), the waves in turn where the grid would not hold them
+			const uint64_t range_waves = uint64_t(num_instances) * max_segments;
+			const uint32_t range_blocks = uint32_t(std::min<uint64_t>((range_waves - 1) / k_compress_waves_per_block + 1, 1u << 20));
+			const dim3 block(shape.block_size);
+			const compress_phase phases[] =
+			{
+				{ tracks_compress_shell_kernel, dim3(shape.instance_blocks), block, launch.base },
+				{ variable_compress_analyze_kernel, shape.track_blocks, block, launch },
+				{ variable_compress_layout_kernel, dim3(shape.instance_blocks), block, launch },
+				{ variable_compress_ranges_kernel, dim3(range_blocks), block, launch },
+				{ variable_compress_stream_kernel, dim3(shape.stream_blocks), block, launch },
+				{ compress_hash_kernel, dim3(num_instances), dim3(k_wave_size), hash_launch },
+			};
+			return launch_compress_phases(context, stream, shape.phases, phases, 6);
 		});
 	}
 }
@@ -212,4 +339,10 @@ extern "C" aclhip_status aclhip_compress_tracks_batch(aclhip_context* context, c
 	const aclhip_compress_tracks_desc* desc, void* blobs, uint64_t blob_stride_bytes, aclhip_compress_result* results, void* stream_handle)
 {
 	return compress_transform_tracks(context, { "tracks", "ACLHIP_TRACKS_COMPRESS_PHASES", true }, raws, num_instances, desc, blobs, blob_stride_bytes, results, stream_handle);
+}
+
+extern "C" aclhip_status aclhip_compress_tracks_variable_batch(aclhip_context* context, const aclhip_raw_tracks* raws, uint32_t num_instances,
+	const aclhip_compress_variable_desc* desc, void* blobs, uint64_t blob_stride_bytes, aclhip_compress_result* results, void* stream_handle)
+{
+	return compress_variable_tracks(context, raws, num_instances, desc, blobs, blob_stride_bytes, results, stream_handle);
 }

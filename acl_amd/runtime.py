@@ -61,6 +61,7 @@ EXPORTED_SYMBOLS = [
     "aclhip_scalar_compress_bound", "aclhip_scalar_compress_workspace_bytes", "aclhip_compress_raw_scalar_tracks_batch",
     "aclhip_transform_compress_bound", "aclhip_transform_compress_workspace_bytes", "aclhip_compress_raw_tracks_batch",
     "aclhip_compress_tracks_workspace_bytes", "aclhip_compress_tracks_batch",
+    "aclhip_variable_compress_num_segments", "aclhip_variable_compress_bound", "aclhip_compress_variable_workspace_bytes", "aclhip_compress_tracks_variable_batch",
 ]
 
 
@@ -279,6 +280,18 @@ class CompressTracksDesc(ctypes.Structure):
         ("max_tracks", ctypes.c_uint32), ("num_table_tracks", ctypes.c_uint32), ("default_pose", ctypes.c_void_p), ("parent_indices", ctypes.c_void_p),
         ("track_precisions", ctypes.c_void_p), ("track_shell_distances", ctypes.c_void_p), ("precision", ctypes.c_float), ("shell_distance", ctypes.c_float),
         ("workspace", ctypes.c_void_p), ("shell_metadata", ctypes.c_void_p), ("reserved", ctypes.c_uint64 * 2),
+    ]
+
+
+class CompressVariableDesc(ctypes.Structure):
+    """aclhip_compress_variable_desc; the four tables, the workspace, shell_metadata and bit_rates are device addresses"""
+    _fields_ = [
+        ("flags", ctypes.c_uint32), ("max_tracks", ctypes.c_uint32), ("max_samples", ctypes.c_uint32), ("num_table_tracks", ctypes.c_uint32),
+        ("default_pose", ctypes.c_void_p), ("parent_indices", ctypes.c_void_p), ("track_precisions", ctypes.c_void_p), ("track_shell_distances", ctypes.c_void_p),
+        ("precision", ctypes.c_float), ("shell_distance", ctypes.c_float), ("workspace", ctypes.c_void_p), ("shell_metadata", ctypes.c_void_p),
+        ("bit_rates", ctypes.c_void_p), ("bit_rate_instance_stride", ctypes.c_uint64), ("bit_rate_segment_stride", ctypes.c_uint64),
+        ("rotation_bit_rate", ctypes.c_uint8), ("translation_bit_rate", ctypes.c_uint8), ("scale_bit_rate", ctypes.c_uint8), ("reserved_rate", ctypes.c_uint8),
+        ("reserved_word", ctypes.c_uint32), ("reserved", ctypes.c_uint64 * 2),
     ]
 
 
@@ -533,6 +546,13 @@ def load_library():
     lib.aclhip_compress_tracks_workspace_bytes.argtypes = [u32, u32]
     lib.aclhip_compress_tracks_workspace_bytes.restype = u64
     lib.aclhip_compress_tracks_batch.argtypes = [vp, vp, u32, ctypes.POINTER(CompressTracksDesc), vp, u64, vp, vp]
+    lib.aclhip_variable_compress_num_segments.argtypes = [u32]
+    lib.aclhip_variable_compress_num_segments.restype = u32
+    lib.aclhip_variable_compress_bound.argtypes = [u32, u32, u32]
+    lib.aclhip_variable_compress_bound.restype = u64
+    lib.aclhip_compress_variable_workspace_bytes.argtypes = [u32, u32, u32]
+    lib.aclhip_compress_variable_workspace_bytes.restype = u64
+    lib.aclhip_compress_tracks_variable_batch.argtypes = [vp, vp, u32, ctypes.POINTER(CompressVariableDesc), vp, u64, vp, vp]
     _lib = lib
     return lib
 
@@ -1198,6 +1218,13 @@ class Context:
         self._check(self._lib.aclhip_compress_tracks_batch(self._handle, raws_ptr, num_instances, ctypes.byref(desc) if desc is not None else None,
                                                            blobs_ptr, blob_stride_bytes, results_ptr, stream))
 
+    def compress_tracks_variable_batch(self, raws_ptr, num_instances, desc, blobs_ptr, blob_stride_bytes, results_ptr, stream=None):
+        """aclhip_compress_tracks_variable_batch: compress_track_list with quatf_drop_w_variable / vector3f_variable / vector3f_variable at the
+        bit rates `desc` (a CompressVariableDesc with its workspace) names, of the raw track arrays named at raws_ptr (device uint32
+        [num_instances]) into the rows at blobs_ptr, one aclhip_compress_result per instance at results_ptr (device addresses)."""
+        self._check(self._lib.aclhip_compress_tracks_variable_batch(self._handle, raws_ptr, num_instances, ctypes.byref(desc) if desc is not None else None,
+                                                                    blobs_ptr, blob_stride_bytes, results_ptr, stream))
+
     def decompress_poses_mapped(self, clips, sample_times, skeletons, maps, num_bones, additive_format=ADDITIVE_NONE, object_space=False, base_clips=None,
                                 base_sample_times=None, base_maps=None, base_poses=None, params=None, out=None, instance_rounding=None, instance_looping=None,
                                 blend_clips=None, blend_sample_times=None, blend_maps=None, blend_weights=None, flags=0):
@@ -1778,16 +1805,18 @@ def transform_compress_workspace_bytes(num_instances, max_tracks):
     return int(load_library().aclhip_transform_compress_workspace_bytes(int(num_instances), int(max_tracks)))
 
 
-def _compress_transform_tracks(ctx, launch, workspace_bytes, desc, raws, flags, default_pose, parents, precision, shell_distance, track_precisions, track_shell_distances):
-    """What compress_raw_tracks and compress_tracks share: `desc` (either struct: the fields have one name in both) comes with its formats
-    and gets the flag word, max_tracks, the two settings and the four per-track tables, uploaded; `launch` is the context's method,
-    `workspace_bytes` the size function of its workspace."""
+def _compress_transform_tracks(ctx, launch, workspace_bytes, desc, raws, flags, default_pose, parents, precision, shell_distance, track_precisions, track_shell_distances,
+                               bound=None):
+    """What compress_raw_tracks, compress_tracks and compress_tracks_variable share: `desc` (any of the three structs: the fields have one
+    name in all) comes with its formats or rates and gets the flag word, max_tracks, the two settings and the four per-track tables,
+    uploaded; `launch` is the context's method, `workspace_bytes` the size function of its workspace, `bound` that of a row
+    (transform_compress_bound when None)."""
     import torch
     handles = np.atleast_1d(np.asarray(raws, dtype=np.uint32))
     infos = [ctx.raw_tracks_info(int(handle)) for handle in handles]
     if len(handles) == 0:
         return []
-    stride = max(transform_compress_bound(info.num_tracks, info.num_samples, flags) for info in infos)
+    stride = max((bound or transform_compress_bound)(info.num_tracks, info.num_samples, flags) for info in infos)
     desc.flags, desc.max_tracks, desc.precision, desc.shell_distance = flags, max(int(info.num_tracks) for info in infos), float(precision), float(shell_distance)
     tables = []         # (kept alive until the launch has run)
     for field, table, dtype, width in (("default_pose", default_pose, np.float32, 12), ("parent_indices", parents, np.uint32, 1),
@@ -1839,6 +1868,80 @@ def compress_tracks(ctx, raws, rotation_format=ROTATION_QUATF_DROP_W_FULL, defau
     desc.rotation_format, desc.translation_format, desc.scale_format = int(rotation_format), VECTOR_VECTOR3F_FULL, VECTOR_VECTOR3F_FULL
     return _compress_transform_tracks(ctx, ctx.compress_tracks_batch, compress_tracks_workspace_bytes, desc, raws, flags, default_pose, parents, precision, shell_distance,
                                       track_precisions, track_shell_distances)
+
+
+def variable_compress_num_segments(num_samples):
+    """aclhip_variable_compress_num_segments (host only): the segments of an array of that many samples"""
+    return int(load_library().aclhip_variable_compress_num_segments(int(num_samples)))
+
+
+def variable_compress_bound(num_tracks, num_samples, flags=0):
+    """aclhip_variable_compress_bound (host only): the bytes a variable blob of such an array can take with any rate table, rounded up to 16"""
+    return int(load_library().aclhip_variable_compress_bound(int(num_tracks), int(num_samples), int(flags)))
+
+
+def compress_variable_workspace_bytes(num_instances, max_tracks, max_samples):
+    """aclhip_compress_variable_workspace_bytes (host only)"""
+    return int(load_library().aclhip_compress_variable_workspace_bytes(int(num_instances), int(max_tracks), int(max_samples)))
+
+
+def compress_tracks_variable(ctx, raws, bit_rates=(16, 16, 16), default_pose=None, parents=None, precision=1.0e-4, shell_distance=1.0, track_precisions=None,
+                             track_shell_distances=None, optimize_loops=False, include_parent_track_indices=False, include_track_descriptions=False):
+    """acl::compress_track_list with quatf_drop_w_variable rotations and vector3f_variable translations and scales AT GIVEN BIT RATES for
+    raw track arrays as one launch, like compress_tracks: `raws` is a handle or a list of handles. bit_rates is three uniform rates
+    (rotation, translation, scale: 0 .. 24), or a uint8 table of { rotation, translation, scale, 0 } entries: [tracks, 4] shared by every
+    instance and segment, [segments, tracks, 4] shared by the instances, or [instances, segments, tracks, 4]; it covers
+    variable_compress_num_segments(samples) rows and the tracks of the largest array. Rows are sized from aclhip_variable_compress_bound.
+    Returns a list of 16 byte aligned numpy uint8 blobs in the format the fast decode paths read. Raises RuntimeError with the
+    reference's message when a sample is not finite, ValueError when an instance is refused (a rate above 24, a rate of 0 in a blob of
+    one segment included). Synchronous; the buffers are torch tensors on the context's device."""
+    import torch
+    flags = ((COMPRESS_OPTIMIZE_LOOPS if optimize_loops else 0) | (COMPRESS_INCLUDE_PARENT_TRACK_INDICES if include_parent_track_indices else 0)
+             | (COMPRESS_INCLUDE_TRACK_DESCRIPTIONS if include_track_descriptions else 0))
+    handles = np.atleast_1d(np.asarray(raws, dtype=np.uint32))
+    infos = [ctx.raw_tracks_info(int(handle)) for handle in handles]
+    if len(handles) == 0:
+        return []
+    desc = CompressVariableDesc()
+    desc.max_samples = max(int(info.num_samples) for info in infos)
+    rates = np.asarray(bit_rates, dtype=np.uint8)
+    if rates.ndim == 1:
+        if rates.shape[0] != 3:
+            raise ValueError("uniform bit rates are three: rotation, translation, scale")
+        desc.rotation_bit_rate, desc.translation_bit_rate, desc.scale_bit_rate = (int(rate) for rate in rates)
+    else:
+        if rates.shape[-1] != 4:
+            raise ValueError("a bit rate table holds { rotation, translation, scale, 0 } per track")
+        rates = np.ascontiguousarray(rates)
+        d_rates = torch.from_numpy(rates).to(torch.device("cuda", ctx.device_index))        # (alive until the launch has run)
+        desc.bit_rates = d_rates.data_ptr()
+        desc.bit_rate_segment_stride = rates.shape[-2] * 4 if rates.ndim >= 3 else 0
+        desc.bit_rate_instance_stride = rates.shape[-3] * rates.shape[-2] * 4 if rates.ndim == 4 else 0
+
+    def workspace_bytes(num_instances, max_tracks):
+        return compress_variable_workspace_bytes(num_instances, max_tracks, desc.max_samples)
+    return _compress_transform_tracks(ctx, ctx.compress_tracks_variable_batch, workspace_bytes, desc, raws, flags, default_pose, parents, precision, shell_distance,
+                                      track_precisions, track_shell_distances, bound=variable_compress_bound)
+
+
+def compress_tracks_at_precision(ctx, raw, skeleton, shells, precision, parents=None, default_pose=None, shell_distance=1.0, optimize_loops=False, **error_settings):
+    """For ONE raw track array: the smallest uniform bit rate whose blob is within `precision` of the array by raw_clip_error(ctx, raw, clip,
+    skeleton, shells, **error_settings). Scans the rate from 1 upward -- compress_tracks_variable, register, raw_clip_error, unregister --
+    and returns (blob, rate) of the first rate whose error is at most `precision`; when rate 24 fails too, the drop-w full blob of
+    compress_tracks with rate None. A host loop over existing launches, up to 24 of each: NOT the reference's search
+    (find_optimal_bit_rates chooses a rate per sub-track and segment and walks the hierarchy); it is here so that a blob of the fast
+    format at a stated error can be had today."""
+    settings = {"default_pose": default_pose, "parents": parents, "precision": precision, "shell_distance": shell_distance, "optimize_loops": optimize_loops}
+    for rate in range(1, 25):
+        blob = compress_tracks_variable(ctx, raw, bit_rates=(rate, rate, rate), **settings)[0]
+        clip = ctx.register_clip(blob)
+        try:
+            _, error, _ = raw_clip_error(ctx, raw, clip, skeleton, shells, **error_settings)
+        finally:
+            ctx.unregister_clip(clip)
+        if error <= precision:
+            return blob, rate
+    return compress_tracks(ctx, raw, **settings)[0], None
 
 
 def scalar_clip_error(ctx, clip_a, clip_b):

@@ -214,7 +214,9 @@ const char* aclhip_last_error_message(const aclhip_context* context);
  * aclhip_scalar_compress_workspace_bytes and aclhip_compress_raw_scalar_tracks_batch -- and for the raw-format transform compressor --
  * aclhip_transform_compress_desc, aclhip_transform_compress_bound, aclhip_transform_compress_workspace_bytes and
  * aclhip_compress_raw_tracks_batch -- and for the drop-w transform compressor -- aclhip_compress_tracks_desc,
- * aclhip_compress_tracks_workspace_bytes and aclhip_compress_tracks_batch).
+ * aclhip_compress_tracks_workspace_bytes and aclhip_compress_tracks_batch -- and for the variable formats at given bit rates --
+ * aclhip_compress_variable_desc, aclhip_variable_compress_num_segments, aclhip_variable_compress_bound,
+ * aclhip_compress_variable_workspace_bytes and aclhip_compress_tracks_variable_batch).
  * A caller compiled against another header would hand over structs of another shape; aclhip_abi_version() says what the LIBRARY was
  * built with, and the C++ mirror (aclhip.hpp) refuses to create a context when the two differ. */
 #define ACLHIP_ABI_VERSION 6u
@@ -1944,7 +1946,8 @@ uint64_t aclhip_transform_compress_workspace_bytes(uint32_t num_instances, uint3
  * one wave per instance, which decides the statuses and the refusal and stores headers, sub-track types, constants, metadata and the
  * tail; the stream, one lane per output dword (one 4 byte load, a byte swap, one coalesced store); the scalar compressor's hash.
  *   Left out (nothing here precludes them): the variable formats and everything they need (segmenting, range reduction, the bit rate
- * search; the error metric over the hierarchy and quatf_drop_w_full exist: aclhip_compress_tracks_batch, below); additive bases; track and list names; output_index remapping and
+ * search; the error metric over the hierarchy and quatf_drop_w_full exist: aclhip_compress_tracks_batch, below; so do the variable formats at given
+ * bit rates, with segmenting and range reduction: aclhip_compress_tracks_variable_batch, below; the search does not); additive bases; track and list names; output_index remapping and
  * stripped tracks; a flag that normalizes rotations within a tolerance; the C++ mirror in aclhip.hpp.
  *   What it costs (no time is promised; one MI355X, 4 096 instances over 256 distinct arrays of 100 tracks x 301 samples -- the bench's
  * pose shape, 91 % of the rotations, a third of the translations and a tenth of the scales animated: 5.92 GB of samples, 2.43 GB of
@@ -2041,10 +2044,129 @@ uint64_t aclhip_compress_tracks_workspace_bytes(uint32_t num_instances, uint32_t
  * descending order with samples across the lanes, which also takes the step 0 refusal, the finite test and the vote; the analysis, one wave
  * per (instance, track): two shell error ballots for the rotation, the raw call's for translation and scale; the raw call's layout and
  * stream with three words per rotation; the hash. No atomics besides the refusal counter: the same bytes on every run.
- *   Left out: the variable formats, segmenting, range reduction and the bit rate search; the matrix error metric and additive bases;
- * track and list names; output_index remapping; the C++ mirror in aclhip.hpp. What it costs: profiles/compress_tracks.md. */
+ *   Left out: the variable formats, segmenting, range reduction and the bit rate search (all but the search exist since:
+ * aclhip_compress_tracks_variable_batch, below); the matrix error metric and additive bases; track and list names; output_index
+ * remapping; the C++ mirror in aclhip.hpp. What it costs: profiles/compress_tracks.md. */
 aclhip_status aclhip_compress_tracks_batch(aclhip_context* context, const aclhip_raw_tracks* raws /* DEVICE [num_instances] */,
 	uint32_t num_instances, const aclhip_compress_tracks_desc* desc, void* blobs /* DEVICE */, uint64_t blob_stride_bytes,
+	aclhip_compress_result* results /* DEVICE [num_instances] */, void* stream);
+
+/* ---- compress_track_list for raw track arrays: the variable formats at given bit rates --------------------------------------------------
+ * acl::compress_track_list for a track_array_qvvf with rotation_format = quatf_drop_w_variable, translation_format = scale_format =
+ * vector3f_variable (compression/impl/compress.transform.impl.h:138-530), batched, with ONE THING TAKEN OUT: find_optimal_bit_rates
+ * (quantize.transform.h:1174-1550). The bit rate of every (segment, animated sub-track) is an INPUT: a device table, or one rate per
+ * kind. Everything else of the variable compressor is here: sub-track compaction of all three kinds under the error metric, clip range
+ * reduction, segmenting, segment range reduction with the 8 bit fix-up, quantization and the segmented, bit packed blob -- the format
+ * the fast decode paths read. Handed the rates the reference chose (its blob's format bytes), the call writes the reference's blob in
+ * every byte that does not depend on a rotation's normalization (see aclhip_compress_tracks_batch: the words that do are within a few
+ * ulp, the quantized rotation fields within one code). Alone it is a fixed-rate lossy compressor whose output a caller grades with
+ * the raw clip error. The call is these three formats and nothing else; mixed full / variable settings are aclhip_compress_tracks_batch's
+ * to refuse.
+ *   Rows, results, the statuses ACLHIP_COMPRESS_OK, ACLHIP_COMPRESS_NOT_FINITE and ACLHIP_COMPRESS_REFUSED, refusal counting, alignment
+ * and overlap rules, stream ordering, "uploads nothing" and graph capture are as for the two calls above. This is an addition to ABI
+ * version 6: new names only, no existing struct or function changes. */
+typedef struct aclhip_compress_variable_desc
+{
+	uint32_t flags;                        /*   0  ACLHIP_COMPRESS_OPTIMIZE_LOOPS | ACLHIP_COMPRESS_INCLUDE_PARENT_TRACK_INDICES | ACLHIP_COMPRESS_INCLUDE_TRACK_DESCRIPTIONS */
+	uint32_t max_tracks;                   /*   4  tracks the workspace was sized for; an instance with more is refused */
+	uint32_t max_samples;                  /*   8  samples the workspace was sized for; an instance with more (behind the looping vote) is refused */
+	uint32_t num_table_tracks;             /*  12  entries of every non-NULL per-track table below */
+	const void* default_pose;              /*  16  DEVICE or NULL, as in the raw call */
+	const uint32_t* parent_indices;        /*  24  DEVICE or NULL (every track a root) */
+	const float* track_precisions;         /*  32  DEVICE or NULL (-> precision) */
+	const float* track_shell_distances;    /*  40  DEVICE or NULL (-> shell_distance) */
+	float precision;                       /*  48  reference default 0.0001F */
+	float shell_distance;                  /*  52  reference default 1.0F */
+	void* workspace;                       /*  56  DEVICE, 16 byte aligned, aclhip_compress_variable_workspace_bytes(num_instances, max_tracks, max_samples) bytes */
+	void* shell_metadata;                  /*  64  DEVICE or NULL, 8 byte aligned: as in aclhip_compress_tracks_desc */
+	const uint8_t* bit_rates;              /*  72  DEVICE or NULL, 4 byte aligned: the entry of (instance i, segment g, track b) is the 4 bytes { rotation, translation,
+	                                               scale, 0 } at bit_rates + i * bit_rate_instance_stride + g * bit_rate_segment_stride + 4 * b. A table covers
+	                                               aclhip_variable_compress_num_segments(S) rows of T entries for the S the array was REGISTERED with (the vote can
+	                                               only lower the count). Entries of constant and default sub-tracks are not read; neither is the fourth byte. */
+	uint64_t bit_rate_instance_stride;     /*  80  bytes, a multiple of 4; 0: every instance reads the same rows */
+	uint64_t bit_rate_segment_stride;      /*  88  bytes, a multiple of 4; 0: every segment reads the same row */
+	uint8_t rotation_bit_rate;             /*  96  with bit_rates == NULL: the rate of every animated rotation, */
+	uint8_t translation_bit_rate;          /*  97  translation */
+	uint8_t scale_bit_rate;                /*  98  and scale sub-track, in every segment */
+	uint8_t reserved_rate;                 /*  99  0 */
+	uint32_t reserved_word;                /* 100  0 */
+	uint64_t reserved[2];                  /* 104  0 */
+} aclhip_compress_variable_desc;           /* 120 bytes */
+
+/* Host only. The segments of an array of num_samples samples: split_samples_per_segment (segment.transform.h:65-128) with the reference's
+ * 16 ideal and 31 at most: one segment up to 31 samples; else ceil(S / 16) segments, the last one dealt out over the others when they
+ * have room for it. Never larger for S - 1 than for S. */
+uint32_t aclhip_variable_compress_num_segments(uint32_t num_samples);
+/* Host only. An upper bound of a blob's size for ANY rate table, rounded up to 16: every sub-track animated at rate 24, with segment start
+ * indices, segment headers, format bytes, padded segment range data and clip range data. 128 bits wide, capped like the other bounds. */
+uint64_t aclhip_variable_compress_bound(uint32_t num_tracks, uint32_t num_samples, uint32_t flags);
+/* Host only. aclhip_compress_tracks_workspace_bytes and, per instance, 72 bytes per track (the clip ranges), and per segment of
+ * max_samples 32 bytes and 12 bytes per track (the prefix sums); each part rounded up to 16, 128 bits wide and capped. */
+uint64_t aclhip_compress_variable_workspace_bytes(uint32_t num_instances, uint32_t max_tracks, uint32_t max_samples);
+
+/* The definition. All arithmetic is fp32, one IEEE operation at a time, never fused, denormals kept; divisions are true divisions. The
+ * array has T tracks and S samples. Steps 0 to 4 are those of aclhip_compress_tracks_batch, word for word: 0 parent refusal, 1 normalize
+ * and the finite check, 2 the rigid shell { local_b, sprec_b } (shell_metadata receives it), 3 the looping vote (S may become S - 1),
+ * 4 positive w. min(a, b) below is a < b ? a : b and max(a, b) is a > b ? a : b (rtm::vector_min, vector_max: of two that compare
+ * equal, the second).
+ *   5. Sub-tracks (compact.transform.h:72-346, 384-485). Per track, in the order rotation, translation, scale, each with shell_error at
+ *      local_b against sprec_b over the S samples. Rotation: as in aclhip_compress_tracks_batch. Translation: CONSTANT iff no sample s has
+ *      shell_error(local_b, {R_s, t_s, s_s}, {R_s, t_0, s_s}) > sprec_b, where R_s is the rotation AFTER ITS COMPACTION (the reference
+ *      reads the stream it has already replaced): r_s of an animated rotation, r_0 of a constant one, the default rotation as given of a
+ *      default one. DEFAULT iff constant and the same holds with the default translation in place of t_0. Scale: likewise with s_0 and the
+ *      default scale, under the compacted rotation and the compacted translation (t_0 of a constant one, the default of a default one).
+ *      has_scale is true throughout these tests (clip_context.impl.h:173) and afterwards "not every scale is default". Constant values are
+ *      stored as in the drop-w call: rotations 12 bytes swizzled in fours, translations and scales x, y, z of sample 0.
+ *   6. Clip ranges (normalize.transform.h:51-95, 200-262), per animated sub-track and component over the S samples of x, y, z (of the
+ *      rotation as step 4 left it): lo = min(... min(min(1e10F, v_0), v_1) ..., v_S-1), hi likewise with max from -1e10F (a zero that is
+ *      the minimum or maximum has the sign of the LAST sample that is a zero); extent = hi - lo. n_s = min((v_s - lo) / extent, 1.0F), or
+ *      0.0F where extent < 0.000000001F.
+ *   7. Segments: the sample counts of aclhip_variable_compress_num_segments' split, in order. One segment has no segment ranges.
+ *   8. Segment ranges (only with more than one segment; normalize.transform.h:117-198). Per segment, animated sub-track and component:
+ *      lo, hi of the n_s of the segment as in 6; fixup_range AS WRITTEN: q0 = clamp(floorf(lo * 255.0F), 0, 255), q1 = max(q0 - 1.0F, 0),
+ *      pmin = q0 * (1.0F / 255.0F) where that is <= lo, else q1 * (1.0F / 255.0F); e0 = clamp(ceilf((hi - pmin) * 255.0F), 0, 255), e1 =
+ *      min(e0 + 1.0F, 255), pext = e0 * (1.0F / 255.0F) where that is >= hi (the maximum, not the extent: the reference's comparison),
+ *      else e1 * (1.0F / 255.0F). m_s = min((n_s - pmin) / pext, 1.0F), or 0.0F where pext < 0.000000001F. The stored bytes are
+ *      pack(pmin, 8) and pack(pext, 8) per component, with pack(x, bits) = (uint32_t)floorf(x * (float)(2^bits - 1) + 0.5F)
+ *      (math/scalar_packing.h:42-48: scalar_round_symmetric of a value that is not negative).
+ *   9. Quantization (quantize.transform.h:370-660; pack_vector3_uXX_unsafe, _u48_, _u24_ of math/vector4_packing.h) at the entry's rate r
+ *      (core/impl/variable_bit_rates.h:45): r in 1 .. 23 stores pack(m_s, r) per component (pack(n_s, r) with one segment), r bits each; 24
+ *      stores the 32 bit words of the UNNORMALIZED x, y, z -- the rotation as step 4 left it, the translation or scale as registered --,
+ *      96 bits; 0 ("constant in this segment") stores pack(n, 16) of the segment's FIRST sample, clip-normalized and not
+ *      segment-normalized, in the sub-track's segment range bytes and nothing in the stream.
+ *  10. The blob (compress.transform.impl.h:287-530, write_segment_data.h, write_range_data.h, write_stream_data.h:104-197, 312-531), every
+ *      offset from the transform_tracks_header: the headers with quatf_drop_w_variable and vector3f_variable twice in the packed word,
+ *      num_segments and num_animated_variable_sub_tracks (the animated rotations rounded up to 4, plus translations and scales); with more
+ *      than one segment the segments' first samples and 0xFFFFFFFF; a 16 byte segment_header per segment (the bits of a pose, of its
+ *      rotations, of its translations, the offset of the segment's data); sub-track types; constant data; CLIP RANGE DATA: rotations in
+ *      groups of four as min xxxx yyyy zzzz then extent xxxx yyyy zzzz, a last group of n < 4 as rows of n; then translations, then
+ *      scales, min.xyz extent.xyz each. Per segment, back to back: one FORMAT BYTE per animated sub-track, rotations (padded with zeros
+ *      to a multiple of 4), translations, scales: the number of bits, 31 for rate 24; a zero byte up to an even offset; with more than one
+ *      segment the SEGMENT RANGE DATA: rotations in groups of four, always padded to four with zeros, 24 bytes a group: min x of the
+ *      four, min y, min z, extent x, y, z -- a rate 0 rotation's six rows hold x high byte, x low byte, y high, y low, z high, z low
+ *      instead --; translations, then scales, six bytes each: min xyz extent xyz, or three little endian 16 bit words at rate 0; zero
+ *      bytes up to a multiple of 4; the ANIMATED BIT STREAM: samples ascending, per sample the rotations, translations, scales in track
+ *      order, three fields each, rate 0 sub-tracks absent, most significant bit first, continuous across samples, zero bits up to a whole
+ *      byte once per segment. Then zero bytes up to a multiple of 4 and the metadata, or the 15 byte tail; size and hash as in the raw call.
+ *   Refused per instance (ACLHIP_COMPRESS_REFUSED, counted, decided in front of any write to the row): everything the drop-w call
+ * refuses; more samples behind step 3 than max_samples; an animated sub-track whose rate in a segment is above 24, or is 0 while the blob
+ * has one segment (the reference allows 0 only where segment ranges exist, quantize.transform.h:1111-1140); a blob larger than the
+ * stride or than 32 bits count, a segment of more than 2^32 bits. ACLHIP_ERROR_INVALID_ARGUMENT before any device call, each with a
+ * message: everything aclhip_compress_tracks_batch refuses of the arguments both have; max_samples == 0; a rate table not 4 byte
+ * aligned, a stride that is no multiple of 4, a table that overlaps the rows, the results, the workspace or the shell metadata (its
+ * extent taken as (num_instances - 1) instance strides, (aclhip_variable_compress_num_segments(max_samples) - 1) segment strides and
+ * 4 * max_tracks bytes); without a table a uniform rate above 24; reserved fields that are not 0.
+ *   Six launches (DESIGN.md 4.7 "Transform compression (variable formats at given bit rates)"): the drop-w call's shell kernel; the
+ * analysis, one wave per (instance, track): six shell error ballots in three passes and the clip ranges by butterfly; the layout, one wave
+ * per instance: per segment the prefix sums of the bit widths in stream order into the workspace, the refusals, then everything but
+ * segment ranges and streams; the segment ranges, one wave per (instance, segment) with lanes over the animated sub-tracks; the stream,
+ * one lane per output dword, which finds its sub-track in the prefix sums and recomputes every component; the hash. No atomics besides
+ * the refusal counter and no zero fill: the same bytes on every run.
+ *   Left out: the bit rate search and compression levels; mixed full / variable formats; keyframe stripping, database support and the
+ * contributing error; the matrix error metric and additive bases; track and list names; output_index remapping; the C++ mirror in
+ * aclhip.hpp; anything against the serial hash. What it costs: profiles/compress_variable.md. */
+aclhip_status aclhip_compress_tracks_variable_batch(aclhip_context* context, const aclhip_raw_tracks* raws /* DEVICE [num_instances] */,
+	uint32_t num_instances, const aclhip_compress_variable_desc* desc, void* blobs /* DEVICE */, uint64_t blob_stride_bytes,
 	aclhip_compress_result* results /* DEVICE [num_instances] */, void* stream);
 
 /* ---- multi-GPU ---------------------------------------------------------------------------------- */
