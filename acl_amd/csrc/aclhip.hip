@@ -68,6 +68,7 @@ namespace aclhip
 #include "kernels_transform_compress.inl"
 #include "kernels_tracks_compress.inl"
 #include "kernels_variable_compress.inl"
+#include "kernels_bit_rate_search.inl"
 #include "kernels_misc.inl"
 #include "kernels_scalar.inl"
 #include "kernels_track.inl"

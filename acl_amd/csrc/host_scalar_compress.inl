@@ -39,24 +39,25 @@ namespace
 	// ---- what the compressors do alike (host_transform_compress.inl holds the other two) ---------------------------------------------------
 
 	// What a compress launch checks of its arguments before any device call; every refusal leaves a message, with or without a context.
-	// In three parts, and a kind's own checks stand where they stood between them: the pointers and their alignment,
+	// In three parts, and a kind's own checks stand where they stood between them: the pointers and their alignment (`kind` is the
+	// word a desc goes by in the messages: "scalar compress"; a call that writes no blob rows has none to be null or misaligned),
 	template<class desc_type>
 	aclhip_status check_compress_buffers(aclhip_context* context, const char* kind, const char* handles, const void* raws, const desc_type* desc, const void* blobs,
-		uint64_t blob_stride_bytes, const aclhip_compress_result* results)
+		uint64_t blob_stride_bytes, const aclhip_compress_result* results, bool with_rows = true)
 	{
 		if (raws == nullptr)
 			return fail(context, ACLHIP_ERROR_INVALID_ARGUMENT, "null %s handles", handles);
 		if (desc == nullptr)
-			return fail(context, ACLHIP_ERROR_INVALID_ARGUMENT, "null %s compress desc", kind);
-		if (blobs == nullptr)
+			return fail(context, ACLHIP_ERROR_INVALID_ARGUMENT, "null %s desc", kind);
+		if (with_rows && blobs == nullptr)
 			return fail(context, ACLHIP_ERROR_INVALID_ARGUMENT, "null blob buffer");
 		if (results == nullptr)
 			return fail(context, ACLHIP_ERROR_INVALID_ARGUMENT, "null compress results");
 		if (desc->workspace == nullptr)
 			return fail(context, ACLHIP_ERROR_INVALID_ARGUMENT, "null workspace");
-		if (blob_stride_bytes == 0)
+		if (with_rows && blob_stride_bytes == 0)
 			return fail(context, ACLHIP_ERROR_INVALID_ARGUMENT, "a blob stride of 0");
-		if ((reinterpret_cast<uintptr_t>(blobs) & 15u) != 0 || (blob_stride_bytes & 15u) != 0)
+		if (with_rows && ((reinterpret_cast<uintptr_t>(blobs) & 15u) != 0 || (blob_stride_bytes & 15u) != 0))
 			return fail(context, ACLHIP_ERROR_INVALID_ARGUMENT, "the blob buffer and its stride must be 16 byte aligned");
 		if ((reinterpret_cast<uintptr_t>(desc->workspace) & 15u) != 0)
 			return fail(context, ACLHIP_ERROR_INVALID_ARGUMENT, "the workspace must be 16 byte aligned");
@@ -72,7 +73,7 @@ namespace
 		if ((desc.flags & ~known_flags) != 0)
 			return fail(context, ACLHIP_ERROR_INVALID_ARGUMENT, "unknown compress flags 0x%x", desc.flags);
 		if (desc.reserved[0] != 0 || desc.reserved[1] != 0)
-			return fail(context, ACLHIP_ERROR_INVALID_ARGUMENT, "the reserved fields of a %s compress desc are 0", kind);
+			return fail(context, ACLHIP_ERROR_INVALID_ARGUMENT, "the reserved fields of a %s desc are 0", kind);
 		if (!std::isfinite(desc.precision) || desc.precision < 0.0f)
 			return fail(context, ACLHIP_ERROR_INVALID_ARGUMENT, "a precision of %g: it must be finite and not negative", double(desc.precision));
 		return ACLHIP_OK;
@@ -85,7 +86,7 @@ namespace
 		uint64_t blob_stride_bytes, const aclhip_compress_result* results, byte_range (&ranges)[count])
 	{
 		if (desc.max_tracks == 0)
-			return fail(context, ACLHIP_ERROR_INVALID_ARGUMENT, "a %s compress desc of 0 max_tracks", kind);
+			return fail(context, ACLHIP_ERROR_INVALID_ARGUMENT, "a %s desc of 0 max_tracks", kind);
 		const unsigned __int128 n = num_instances;
 		ranges[0] = { "the blob rows", blobs, n * blob_stride_bytes };
 		ranges[1] = { "the compress results", results, n * sizeof(aclhip_compress_result) };
@@ -168,9 +169,9 @@ namespace
 	aclhip_status check_scalar_compress(aclhip_context* context, const aclhip_raw_scalar_tracks* raws, uint32_t num_instances, const aclhip_scalar_compress_desc* desc,
 		const void* blobs, uint64_t blob_stride_bytes, const aclhip_compress_result* results)
 	{
-		if (const aclhip_status status = check_compress_buffers(context, "scalar", "raw scalar track", raws, desc, blobs, blob_stride_bytes, results); status != ACLHIP_OK)
+		if (const aclhip_status status = check_compress_buffers(context, "scalar compress", "raw scalar track", raws, desc, blobs, blob_stride_bytes, results); status != ACLHIP_OK)
 			return status;
-		if (const aclhip_status status = check_compress_settings(context, "scalar", *desc, ACLHIP_COMPRESS_OPTIMIZE_LOOPS); status != ACLHIP_OK)
+		if (const aclhip_status status = check_compress_settings(context, "scalar compress", *desc, ACLHIP_COMPRESS_OPTIMIZE_LOOPS); status != ACLHIP_OK)
 			return status;
 		if (desc->track_precisions != nullptr && desc->num_track_precisions == 0)
 			return fail(context, ACLHIP_ERROR_INVALID_ARGUMENT, "track_precisions with a count of 0");
@@ -180,7 +181,7 @@ namespace
 			{ "the raw scalar track handles", raws, (unsigned __int128)num_instances * sizeof(aclhip_raw_scalar_tracks) },
 			{ "the track precisions", desc->track_precisions, desc->track_precisions != nullptr ? (unsigned __int128)desc->num_track_precisions * sizeof(float) : 0 },
 		};
-		return check_compress_ranges(context, "scalar", *desc, aclhip_scalar_compress_workspace_bytes(num_instances, desc->max_tracks), num_instances, blobs, blob_stride_bytes, results, ranges);
+		return check_compress_ranges(context, "scalar compress", *desc, aclhip_scalar_compress_workspace_bytes(num_instances, desc->max_tracks), num_instances, blobs, blob_stride_bytes, results, ranges);
 	}
 }
 

@@ -1,9 +1,10 @@
 // host_transform_compress.inl -- part of aclhip.hip (one translation unit; included there behind host_scalar_compress.inl, not compiled on its own).
 // Host side of the three transform compressors, aclhip_compress_raw_tracks_batch (kernels_transform_compress.inl),
-// aclhip_compress_tracks_batch (kernels_tracks_compress.inl) and aclhip_compress_tracks_variable_batch (kernels_variable_compress.inl):
+// aclhip_compress_tracks_batch (kernels_tracks_compress.inl) and aclhip_compress_tracks_variable_batch (kernels_variable_compress.inl),
+// and of the bit rate search, aclhip_find_bit_rates_batch (kernels_bit_rate_search.inl):
 // the sizes a caller needs, and one argument check, one workspace layout and one launch record for all -- the raw call is the drop-w
 // call with the full formats, no shell and its own words; the variable call is it with its own kernels behind the shell, its rate
-// table and three more parts of the workspace.
+// table and three more parts of the workspace; the search is the variable call without rows, its table written, and four more parts.
 // What they share with the scalar compressor -- the cap of a size, the common checks, the launches' shapes, their front and their list
 // of phases -- is in host_scalar_compress.inl. include/aclhip.h states the definitions.
 
@@ -11,6 +12,10 @@ static_assert(sizeof(aclhip_transform_compress_desc) == 80, "header layout");
 static_assert(offsetof(aclhip_transform_compress_desc, default_pose) == 8 && offsetof(aclhip_transform_compress_desc, num_table_tracks) == 40
 	&& offsetof(aclhip_transform_compress_desc, shell_distance) == 48 && offsetof(aclhip_transform_compress_desc, workspace) == 56
 	&& offsetof(aclhip_transform_compress_desc, reserved) == 64, "header layout");
+static_assert(sizeof(aclhip_find_bit_rates_desc) == 96, "header layout");
+static_assert(offsetof(aclhip_find_bit_rates_desc, default_pose) == 16 && offsetof(aclhip_find_bit_rates_desc, precision) == 48
+	&& offsetof(aclhip_find_bit_rates_desc, workspace) == 56 && offsetof(aclhip_find_bit_rates_desc, shell_metadata) == 64
+	&& offsetof(aclhip_find_bit_rates_desc, level) == 72 && offsetof(aclhip_find_bit_rates_desc, reserved) == 80, "header layout");
 static_assert(sizeof(aclhip_compress_tracks_desc) == 96, "header layout");
 static_assert(offsetof(aclhip_compress_tracks_desc, flags) == 12 && offsetof(aclhip_compress_tracks_desc, num_table_tracks) == 20
 	&& offsetof(aclhip_compress_tracks_desc, default_pose) == 24 && offsetof(aclhip_compress_tracks_desc, track_shell_distances) == 48
@@ -26,11 +31,13 @@ namespace
 	// aclhip_scalar_compress_workspace_bytes). The raw call has the first three parts, aclhip_compress_tracks_batch the shells
 	// ({ local shell distance, precision } per instance and track) behind them, aclhip_compress_tracks_variable_batch behind those the
 	// clip ranges (18 floats per instance and track) and, per instance and segment of max_samples (max_segments; 0: none of the three),
-	// a variable_segment and the prefix sums (a dword per sub-track). The size functions and the launch record both read it.
+	// a variable_segment and the prefix sums (a dword per sub-track); aclhip_find_bit_rates_batch behind those, per instance and segment,
+	// a search_segment and, per track, the segment range (18 floats), the segment's shell and an entry of the chain under work. The
+	// size functions and the launch record both read it.
 	struct transform_workspace_layout
 	{
-		unsigned __int128 instances = 0, track_flags, animated, shells, clip_ranges, segments, prefix, total;
-		transform_workspace_layout(uint32_t num_instances, uint32_t max_tracks, bool with_shells, uint32_t max_segments = 0)
+		unsigned __int128 instances = 0, track_flags, animated, shells, clip_ranges, segments, prefix, search_segments, segment_ranges, segment_shells, chains, total;
+		transform_workspace_layout(uint32_t num_instances, uint32_t max_tracks, bool with_shells, uint32_t max_segments = 0, bool with_search = false)
 		{
 			const auto part = [](unsigned __int128 bytes) { return (bytes + 15u) & ~(unsigned __int128)15; };
 			const unsigned __int128 n = num_instances;
@@ -40,7 +47,11 @@ namespace
 			clip_ranges = shells + (with_shells ? part(n * max_tracks * sizeof(float2)) : 0);
 			segments = clip_ranges + (max_segments != 0 ? part(n * max_tracks * k_variable_range_floats * sizeof(float)) : 0);
 			prefix = segments + part(n * max_segments * sizeof(variable_segment));
-			total = prefix + part(n * max_segments * max_tracks * 3u * sizeof(uint32_t));
+			search_segments = prefix + part(n * max_segments * max_tracks * 3u * sizeof(uint32_t));
+			segment_ranges = search_segments + (with_search ? part(n * max_segments * sizeof(search_segment)) : 0);
+			segment_shells = segment_ranges + (with_search ? part(n * max_segments * max_tracks * k_search_segment_floats * sizeof(float)) : 0);
+			chains = segment_shells + (with_search ? part(n * max_segments * max_tracks * sizeof(float2)) : 0);
+			total = chains + (with_search ? part(n * max_segments * max_tracks * sizeof(uint16_t)) : 0);
 		}
 	};
 }
@@ -94,12 +105,18 @@ extern "C" uint64_t aclhip_compress_variable_workspace_bytes(uint32_t num_instan
 	return compress_size_of(transform_workspace_layout(num_instances, max_tracks, true, variable_split_of(std::max(max_samples, 1u)).num_segments).total);
 }
 
+extern "C" uint64_t aclhip_find_bit_rates_workspace_bytes(uint32_t num_instances, uint32_t max_tracks, uint32_t max_samples)
+{
+	return compress_size_of(transform_workspace_layout(num_instances, max_tracks, true, variable_split_of(std::max(max_samples, 1u)).num_segments, true).total);
+}
+
 namespace
 {
-	// What an entry point says of itself: the word of its messages, the knob of its phases, whether its workspace holds shells and the
-	// segments it holds the variable call's parts for (0: none). The rest of what tells the raw and the drop-w call apart is in the
-	// desc: the formats and the shell metadata, 0 for the raw call.
-	struct transform_compress_kind { const char* name; const char* phases_knob; bool with_shells; uint32_t max_segments = 0; };
+	// What an entry point says of itself: the word its desc goes by in the messages, the knob of its phases, whether its workspace holds shells and the
+	// segments it holds the variable call's parts for (0: none), whether it writes blob rows and whether its workspace holds the
+	// search's parts. The rest of what tells the raw and the drop-w call apart is in the desc: the formats and the shell metadata, 0
+	// for the raw call.
+	struct transform_compress_kind { const char* name; const char* phases_knob; bool with_shells; uint32_t max_segments = 0; bool with_rows = true; bool with_search = false; };
 
 	// The kernels between the shell and the hash, per rotation format: quatf_full (the raw call's), quatf_drop_w_full
 	struct transform_compress_kernels { void (*analyze)(transform_compress_launch), (*layout)(transform_compress_launch), (*stream)(transform_compress_launch); };
@@ -120,7 +137,13 @@ namespace
 	aclhip_status check_transform_compress(aclhip_context* context, const transform_compress_kind& kind, const aclhip_raw_tracks* raws, uint32_t num_instances,
 		const aclhip_compress_tracks_desc* desc, const void* blobs, uint64_t blob_stride_bytes, const aclhip_compress_result* results)
 	{
-		if (const aclhip_status status = check_compress_buffers(context, kind.name, "raw track", raws, desc, blobs, blob_stride_bytes, results); status != ACLHIP_OK)
+		// (a call without rows has none to be null or misaligned, and none that could overlap)
+		if (!kind.with_rows)
+		{
+			blobs = nullptr;
+			blob_stride_bytes = 0;
+		}
+		if (const aclhip_status status = check_compress_buffers(context, kind.name, "raw track", raws, desc, blobs, blob_stride_bytes, results, kind.with_rows); status != ACLHIP_OK)
 			return status;
 		if ((reinterpret_cast<uintptr_t>(desc->default_pose) & 15u) != 0)
 			return fail(context, ACLHIP_ERROR_INVALID_ARGUMENT, "the default pose must be 16 byte aligned");
@@ -154,7 +177,7 @@ namespace
 			{ "the track precisions", desc->track_precisions, desc->track_precisions != nullptr ? table * sizeof(float) : 0 },
 			{ "the track shell distances", desc->track_shell_distances, desc->track_shell_distances != nullptr ? table * sizeof(float) : 0 },
 		};
-		const uint64_t workspace_bytes = compress_size_of(transform_workspace_layout(num_instances, desc->max_tracks, kind.with_shells, kind.max_segments).total);
+		const uint64_t workspace_bytes = compress_size_of(transform_workspace_layout(num_instances, desc->max_tracks, kind.with_shells, kind.max_segments, kind.with_search).total);
 		if (const aclhip_status status = check_compress_ranges(context, kind.name, *desc, workspace_bytes, num_instances, blobs, blob_stride_bytes, results, ranges); status != ACLHIP_OK)
 			return status;
 		// the fourth output, in a pass of its own behind that one: it overlaps no other and nothing that is read
@@ -249,7 +272,7 @@ namespace
 			as_tracks.reserved[1] = desc->reserved[1];
 		}
 		const uint32_t max_segments = desc != nullptr ? variable_split_of(std::max(desc->max_samples, 1u)).num_segments : 1u;
-		const transform_compress_kind kind = { "variable", "ACLHIP_VARIABLE_COMPRESS_PHASES", true, max_segments };
+		const transform_compress_kind kind = { "variable compress", "ACLHIP_VARIABLE_COMPRESS_PHASES", true, max_segments };
 		if (const aclhip_status status = check_transform_compress(context, kind, raws, num_instances, desc != nullptr ? &as_tracks : nullptr, blobs, blob_stride_bytes, results); status != ACLHIP_OK)
 			return status;
 		if (desc->max_samples == 0)
@@ -311,6 +334,112 @@ namespace
 	}
 }
 
+namespace
+{
+	// The search: its desc as the drop-w one for the shared check, like the variable call; no rows; the table on the written side.
+	aclhip_status find_bit_rates(aclhip_context* context, const aclhip_raw_tracks* raws, uint32_t num_instances, const aclhip_find_bit_rates_desc* desc,
+		uint8_t* bit_rates, uint64_t instance_stride, uint64_t segment_stride, aclhip_compress_result* results, void* stream_handle)
+	{
+		aclhip_compress_tracks_desc as_tracks = {};
+		if (desc != nullptr)
+		{
+			as_tracks.rotation_format = k_rotation_quatf_drop_w_full;
+			as_tracks.flags = desc->flags;
+			as_tracks.max_tracks = desc->max_tracks;
+			as_tracks.num_table_tracks = desc->num_table_tracks;
+			as_tracks.default_pose = desc->default_pose;
+			as_tracks.parent_indices = desc->parent_indices;
+			as_tracks.track_precisions = desc->track_precisions;
+			as_tracks.track_shell_distances = desc->track_shell_distances;
+			as_tracks.precision = desc->precision;
+			as_tracks.shell_distance = desc->shell_distance;
+			as_tracks.workspace = desc->workspace;
+			as_tracks.shell_metadata = desc->shell_metadata;
+			as_tracks.reserved[0] = desc->reserved[0] | desc->reserved_word;
+			as_tracks.reserved[1] = desc->reserved[1];
+		}
+		const uint32_t max_segments = desc != nullptr ? variable_split_of(std::max(desc->max_samples, 1u)).num_segments : 1u;
+		const transform_compress_kind kind = { "bit rate search", "ACLHIP_FIND_BIT_RATES_PHASES", true, max_segments, false, true };
+		if (const aclhip_status status = check_transform_compress(context, kind, raws, num_instances, desc != nullptr ? &as_tracks : nullptr, nullptr, 0, results); status != ACLHIP_OK)
+			return status;
+		if (desc->max_samples == 0)
+			return fail(context, ACLHIP_ERROR_INVALID_ARGUMENT, "a bit rate search desc of 0 max_samples");
+		if (desc->level == 3 || desc->level == 4)
+			return fail(context, ACLHIP_ERROR_INVALID_ARGUMENT, "level %u (%s) is not built: 0 (lowest), 1 (low) and 2 (medium) are", desc->level, desc->level == 3 ? "high" : "highest");
+		if (desc->level > 4)
+			return fail(context, ACLHIP_ERROR_INVALID_ARGUMENT, "a level of %u: 0 (lowest), 1 (low) or 2 (medium)", desc->level);
+		if (bit_rates == nullptr)
+			return fail(context, ACLHIP_ERROR_INVALID_ARGUMENT, "null bit rate table");
+		if ((reinterpret_cast<uintptr_t>(bit_rates) & 3u) != 0)
+			return fail(context, ACLHIP_ERROR_INVALID_ARGUMENT, "the bit rate table must be 4 byte aligned");
+		if (((instance_stride | segment_stride) & 3u) != 0)
+			return fail(context, ACLHIP_ERROR_INVALID_ARGUMENT, "the strides of the bit rate table are multiples of 4");
+		if (segment_stride < 4ull * desc->max_tracks)
+			return fail(context, ACLHIP_ERROR_INVALID_ARGUMENT, "a segment stride of %llu: a written row takes 4 * max_tracks = %llu bytes", (unsigned long long)segment_stride, 4ull * desc->max_tracks);
+		if ((unsigned __int128)instance_stride < (unsigned __int128)max_segments * segment_stride)
+			return fail(context, ACLHIP_ERROR_INVALID_ARGUMENT, "an instance stride of %llu: the %u rows of an instance take %u segment strides", (unsigned long long)instance_stride, max_segments, max_segments);
+		const transform_workspace_layout layout(num_instances, desc->max_tracks, true, max_segments, true);
+		{
+			const unsigned __int128 n = num_instances, table_tracks = desc->num_table_tracks;
+			const unsigned __int128 table_bytes = (n - (n != 0 ? 1u : 0u)) * instance_stride + (unsigned __int128)(max_segments - 1u) * segment_stride + 4u * (unsigned __int128)desc->max_tracks;
+			const byte_range written[] =
+			{
+				{ "the bit rate table", bit_rates, table_bytes },
+				{ "the compress results", results, n * sizeof(aclhip_compress_result) },
+				{ "the workspace", desc->workspace, compress_size_of(layout.total) },
+				{ "the shell metadata", desc->shell_metadata, desc->shell_metadata != nullptr ? n * desc->max_tracks * sizeof(float2) : 0 },
+			};
+			const byte_range read[] =
+			{
+				{ "the raw track handles", raws, n * sizeof(aclhip_raw_tracks) },
+				{ "the default pose", desc->default_pose, desc->default_pose != nullptr ? table_tracks * 48u : 0 },
+				{ "the parent indices", desc->parent_indices, desc->parent_indices != nullptr ? table_tracks * sizeof(uint32_t) : 0 },
+				{ "the track precisions", desc->track_precisions, desc->track_precisions != nullptr ? table_tracks * sizeof(float) : 0 },
+				{ "the track shell distances", desc->track_shell_distances, desc->track_shell_distances != nullptr ? table_tracks * sizeof(float) : 0 },
+			};
+			// (the table alone is new among them: the shared check has held the other three against each other and against what is read)
+			if (const aclhip_status status = check_no_overlap(context, written, 1, read, 5); status != ACLHIP_OK)
+				return status;
+			if (const aclhip_status status = check_no_overlap(context, written, 4, nullptr, 0); status != ACLHIP_OK)
+				return status;
+		}
+		return launch_compress(context, &aclhip_context::raw_tracks, num_instances, stream_handle, [&](hipStream_t stream) -> aclhip_status
+		{
+			const compress_launch_shape shape = compress_launch_shape_of(num_instances, desc->max_tracks, 16, kind.phases_knob);
+			uint8_t* workspace = static_cast<uint8_t*>(desc->workspace);
+			bit_rate_search_launch launch = {};
+			launch.variable.base = transform_compress_launch_of(context, raws, num_instances, &as_tracks, nullptr, 0, results, shape, layout, true);
+			launch.variable.max_samples = desc->max_samples;
+			launch.variable.max_segments = max_segments;
+			launch.variable.clip_ranges = reinterpret_cast<float*>(workspace + uint64_t(layout.clip_ranges));
+			launch.variable.segments = reinterpret_cast<variable_segment*>(workspace + uint64_t(layout.segments));
+			launch.variable.prefix = reinterpret_cast<uint32_t*>(workspace + uint64_t(layout.prefix));
+			launch.table = bit_rates;
+			launch.instance_stride = instance_stride;
+			launch.segment_stride = segment_stride;
+			launch.segments = reinterpret_cast<search_segment*>(workspace + uint64_t(layout.search_segments));
+			launch.segment_ranges = reinterpret_cast<float*>(workspace + uint64_t(layout.segment_ranges));
+			launch.segment_shells = reinterpret_cast<float2*>(workspace + uint64_t(layout.segment_shells));
+			launch.chains = reinterpret_cast<uint16_t*>(workspace + uint64_t(layout.chains));
+
+			// a wave per (instance, segment), and for the local phase per (instance, segment, track), in turn where the grid would not hold them
+			const uint64_t segment_waves = uint64_t(num_instances) * max_segments;
+			const uint32_t segment_blocks = uint32_t(std::min<uint64_t>((segment_waves - 1) / k_compress_waves_per_block + 1, 1u << 20));
+			const uint32_t track_blocks = uint32_t(std::min<unsigned __int128>((unsigned __int128)segment_waves * desc->max_tracks, 1u << 22));
+			const dim3 block(shape.block_size);
+			const compress_phase phases[] =
+			{
+				{ tracks_compress_shell_kernel, dim3(shape.instance_blocks), block, launch.variable.base },
+				{ variable_compress_analyze_kernel, shape.track_blocks, block, launch.variable },
+				{ bit_rate_search_segment_kernel, dim3(segment_blocks), block, launch },
+				{ bit_rate_search_local_kernel, dim3(track_blocks), dim3(k_wave_size), launch },
+				{ bit_rate_search_object_kernel, dim3(segment_blocks), block, launch },
+			};
+			return launch_compress_phases(context, stream, shape.phases, phases, 5);
+		});
+	}
+}
+
 extern "C" aclhip_status aclhip_compress_raw_tracks_batch(aclhip_context* context, const aclhip_raw_tracks* raws, uint32_t num_instances,
 	const aclhip_transform_compress_desc* desc, void* blobs, uint64_t blob_stride_bytes, aclhip_compress_result* results, void* stream_handle)
 {
@@ -331,18 +460,24 @@ extern "C" aclhip_status aclhip_compress_raw_tracks_batch(aclhip_context* contex
 		as_tracks.reserved[0] = desc->reserved[0];
 		as_tracks.reserved[1] = desc->reserved[1];
 	}
-	return compress_transform_tracks(context, { "transform", "ACLHIP_TRANSFORM_COMPRESS_PHASES", false }, raws, num_instances, desc != nullptr ? &as_tracks : nullptr, blobs,
+	return compress_transform_tracks(context, { "transform compress", "ACLHIP_TRANSFORM_COMPRESS_PHASES", false }, raws, num_instances, desc != nullptr ? &as_tracks : nullptr, blobs,
 		blob_stride_bytes, results, stream_handle);
 }
 
 extern "C" aclhip_status aclhip_compress_tracks_batch(aclhip_context* context, const aclhip_raw_tracks* raws, uint32_t num_instances,
 	const aclhip_compress_tracks_desc* desc, void* blobs, uint64_t blob_stride_bytes, aclhip_compress_result* results, void* stream_handle)
 {
-	return compress_transform_tracks(context, { "tracks", "ACLHIP_TRACKS_COMPRESS_PHASES", true }, raws, num_instances, desc, blobs, blob_stride_bytes, results, stream_handle);
+	return compress_transform_tracks(context, { "tracks compress", "ACLHIP_TRACKS_COMPRESS_PHASES", true }, raws, num_instances, desc, blobs, blob_stride_bytes, results, stream_handle);
 }
 
 extern "C" aclhip_status aclhip_compress_tracks_variable_batch(aclhip_context* context, const aclhip_raw_tracks* raws, uint32_t num_instances,
 	const aclhip_compress_variable_desc* desc, void* blobs, uint64_t blob_stride_bytes, aclhip_compress_result* results, void* stream_handle)
 {
 	return compress_variable_tracks(context, raws, num_instances, desc, blobs, blob_stride_bytes, results, stream_handle);
+}
+
+extern "C" aclhip_status aclhip_find_bit_rates_batch(aclhip_context* context, const aclhip_raw_tracks* raws, uint32_t num_instances,
+	const aclhip_find_bit_rates_desc* desc, uint8_t* bit_rates, uint64_t instance_stride, uint64_t segment_stride, aclhip_compress_result* results, void* stream_handle)
+{
+	return find_bit_rates(context, raws, num_instances, desc, bit_rates, instance_stride, segment_stride, results, stream_handle);
 }

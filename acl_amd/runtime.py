@@ -62,6 +62,7 @@ EXPORTED_SYMBOLS = [
     "aclhip_transform_compress_bound", "aclhip_transform_compress_workspace_bytes", "aclhip_compress_raw_tracks_batch",
     "aclhip_compress_tracks_workspace_bytes", "aclhip_compress_tracks_batch",
     "aclhip_variable_compress_num_segments", "aclhip_variable_compress_bound", "aclhip_compress_variable_workspace_bytes", "aclhip_compress_tracks_variable_batch",
+    "aclhip_find_bit_rates_workspace_bytes", "aclhip_find_bit_rates_batch",
 ]
 
 
@@ -295,6 +296,17 @@ class CompressVariableDesc(ctypes.Structure):
     ]
 
 
+class FindBitRatesDesc(ctypes.Structure):
+    """aclhip_find_bit_rates_desc; the four tables, the workspace and shell_metadata are device addresses"""
+    _fields_ = [
+        ("flags", ctypes.c_uint32), ("max_tracks", ctypes.c_uint32), ("max_samples", ctypes.c_uint32), ("num_table_tracks", ctypes.c_uint32),
+        ("default_pose", ctypes.c_void_p), ("parent_indices", ctypes.c_void_p), ("track_precisions", ctypes.c_void_p), ("track_shell_distances", ctypes.c_void_p),
+        ("precision", ctypes.c_float), ("shell_distance", ctypes.c_float), ("workspace", ctypes.c_void_p), ("shell_metadata", ctypes.c_void_p),
+        ("level", ctypes.c_uint32), ("reserved_word", ctypes.c_uint32), ("reserved", ctypes.c_uint64 * 2),
+    ]
+
+
+COMPRESSION_LEVELS = {"lowest": 0, "low": 1, "medium": 2, "high": 3, "highest": 4}          # acl::compression_level8 (aclhip_find_bit_rates_desc::level)
 ROTATION_QUATF_FULL, ROTATION_QUATF_DROP_W_FULL = 0, 2                                      # acl::rotation_format8 (aclhip_compress_tracks_desc::rotation_format)
 VECTOR_VECTOR3F_FULL = 0                                                                    # acl::vector_format8
 COMPRESS_OPTIMIZE_LOOPS = 1                                                                 # ACLHIP_COMPRESS_OPTIMIZE_LOOPS
@@ -553,6 +565,9 @@ def load_library():
     lib.aclhip_compress_variable_workspace_bytes.argtypes = [u32, u32, u32]
     lib.aclhip_compress_variable_workspace_bytes.restype = u64
     lib.aclhip_compress_tracks_variable_batch.argtypes = [vp, vp, u32, ctypes.POINTER(CompressVariableDesc), vp, u64, vp, vp]
+    lib.aclhip_find_bit_rates_workspace_bytes.argtypes = [u32, u32, u32]
+    lib.aclhip_find_bit_rates_workspace_bytes.restype = u64
+    lib.aclhip_find_bit_rates_batch.argtypes = [vp, vp, u32, ctypes.POINTER(FindBitRatesDesc), vp, u64, u64, vp, vp]
     _lib = lib
     return lib
 
@@ -1225,6 +1240,14 @@ class Context:
         self._check(self._lib.aclhip_compress_tracks_variable_batch(self._handle, raws_ptr, num_instances, ctypes.byref(desc) if desc is not None else None,
                                                                     blobs_ptr, blob_stride_bytes, results_ptr, stream))
 
+    def find_bit_rates_batch(self, raws_ptr, num_instances, desc, bit_rates_ptr, instance_stride, segment_stride, results_ptr, stream=None):
+        """aclhip_find_bit_rates_batch: find_optimal_bit_rates (levels lowest to medium) of the raw track arrays named at raws_ptr (device
+        uint32 [num_instances]): the { rotation, translation, scale, 0 } entry of every (instance, segment, track) into the table at
+        bit_rates_ptr with the two strides, in the layout aclhip_compress_tracks_variable_batch reads; one aclhip_compress_result (size 0)
+        per instance at results_ptr (device addresses); `desc` is a FindBitRatesDesc with its workspace."""
+        self._check(self._lib.aclhip_find_bit_rates_batch(self._handle, raws_ptr, num_instances, ctypes.byref(desc) if desc is not None else None,
+                                                          bit_rates_ptr, instance_stride, segment_stride, results_ptr, stream))
+
     def decompress_poses_mapped(self, clips, sample_times, skeletons, maps, num_bones, additive_format=ADDITIVE_NONE, object_space=False, base_clips=None,
                                 base_sample_times=None, base_maps=None, base_poses=None, params=None, out=None, instance_rounding=None, instance_looping=None,
                                 blend_clips=None, blend_sample_times=None, blend_maps=None, blend_weights=None, flags=0):
@@ -1805,31 +1828,45 @@ def transform_compress_workspace_bytes(num_instances, max_tracks):
     return int(load_library().aclhip_transform_compress_workspace_bytes(int(num_instances), int(max_tracks)))
 
 
+def _upload_track_tables(ctx, default_pose, parents, track_precisions, track_shell_distances):
+    """The four per-track tables a transform compress desc or a search desc names, on the context's device: a list of
+    (field, tensor, tracks) for _set_track_tables; the tensors stay alive as long as the list does."""
+    import torch
+    tables = []
+    for field, table, dtype, width in (("default_pose", default_pose, np.float32, 12), ("parent_indices", parents, np.uint32, 1),
+                                       ("track_precisions", track_precisions, np.float32, 1), ("track_shell_distances", track_shell_distances, np.float32, 1)):
+        if table is None:
+            continue
+        host = np.ascontiguousarray(table, dtype=dtype).reshape(-1, width)
+        if tables and host.shape[0] != tables[0][2]:
+            raise ValueError("default_pose, parents, track_precisions and track_shell_distances hold the same number of tracks")
+        d_table = torch.from_numpy(host.view(np.int32) if dtype is np.uint32 else host).to(torch.device("cuda", ctx.device_index))
+        tables.append((field, d_table, host.shape[0]))
+    return tables
+
+
+def _set_track_tables(desc, tables):
+    for field, d_table, num_tracks in tables:
+        setattr(desc, field, d_table.data_ptr())
+        desc.num_table_tracks = num_tracks
+
+
 def _compress_transform_tracks(ctx, launch, workspace_bytes, desc, raws, flags, default_pose, parents, precision, shell_distance, track_precisions, track_shell_distances,
-                               bound=None):
+                               bound=None, tables=None):
     """What compress_raw_tracks, compress_tracks and compress_tracks_variable share: `desc` (any of the three structs: the fields have one
     name in all) comes with its formats or rates and gets the flag word, max_tracks, the two settings and the four per-track tables,
     uploaded; `launch` is the context's method, `workspace_bytes` the size function of its workspace, `bound` that of a row
-    (transform_compress_bound when None)."""
-    import torch
+    (transform_compress_bound when None); `tables`: those four as _upload_track_tables left them, when a call before this one has
+    uploaded them already."""
     handles = np.atleast_1d(np.asarray(raws, dtype=np.uint32))
     infos = [ctx.raw_tracks_info(int(handle)) for handle in handles]
     if len(handles) == 0:
         return []
     stride = max((bound or transform_compress_bound)(info.num_tracks, info.num_samples, flags) for info in infos)
     desc.flags, desc.max_tracks, desc.precision, desc.shell_distance = flags, max(int(info.num_tracks) for info in infos), float(precision), float(shell_distance)
-    tables = []         # (kept alive until the launch has run)
-    for field, table, dtype, width in (("default_pose", default_pose, np.float32, 12), ("parent_indices", parents, np.uint32, 1),
-                                       ("track_precisions", track_precisions, np.float32, 1), ("track_shell_distances", track_shell_distances, np.float32, 1)):
-        if table is None:
-            continue
-        host = np.ascontiguousarray(table, dtype=dtype).reshape(-1, width)
-        if tables and host.shape[0] != tables[0][1]:
-            raise ValueError("default_pose, parents, track_precisions and track_shell_distances hold the same number of tracks")
-        d_table = torch.from_numpy(host.view(np.int32) if dtype is np.uint32 else host).to(torch.device("cuda", ctx.device_index))
-        tables.append((d_table, host.shape[0]))
-        setattr(desc, field, d_table.data_ptr())
-        desc.num_table_tracks = host.shape[0]
+    if tables is None:
+        tables = _upload_track_tables(ctx, default_pose, parents, track_precisions, track_shell_distances)       # (kept alive until the launch has run)
+    _set_track_tables(desc, tables)
     return _compress_batch(ctx, launch, handles, "raw track array", stride, workspace_bytes(len(handles), desc.max_tracks), desc)
 
 
@@ -1885,13 +1922,75 @@ def compress_variable_workspace_bytes(num_instances, max_tracks, max_samples):
     return int(load_library().aclhip_compress_variable_workspace_bytes(int(num_instances), int(max_tracks), int(max_samples)))
 
 
+def find_bit_rates_workspace_bytes(num_instances, max_tracks, max_samples):
+    """aclhip_find_bit_rates_workspace_bytes (host only)"""
+    return int(load_library().aclhip_find_bit_rates_workspace_bytes(int(num_instances), int(max_tracks), int(max_samples)))
+
+
+def _find_bit_rates(ctx, handles, infos, level, flags, default_pose, parents, precision, shell_distance, track_precisions, track_shell_distances, tables=None):
+    """The search over `handles` into a zero-filled device table uint8 [instances, segments, tracks, 4] of the largest array's segments
+    and tracks: (the table, still on the device, and the results as a host array [instances, 2]). Synchronous."""
+    import torch
+    device = torch.device("cuda", ctx.device_index)
+    desc = FindBitRatesDesc()
+    if level not in COMPRESSION_LEVELS and level not in COMPRESSION_LEVELS.values():
+        raise ValueError(f"a compression level of {level!r}: one of {sorted(COMPRESSION_LEVELS, key=COMPRESSION_LEVELS.get)} or 0 to 4")
+    desc.level = COMPRESSION_LEVELS.get(level, level)
+    desc.flags, desc.precision, desc.shell_distance = flags, float(precision), float(shell_distance)
+    desc.max_tracks = max(int(info.num_tracks) for info in infos)
+    desc.max_samples = max(int(info.num_samples) for info in infos)
+    if tables is None:
+        tables = _upload_track_tables(ctx, default_pose, parents, track_precisions, track_shell_distances)       # (kept alive until the launch has run)
+    _set_track_tables(desc, tables)
+    num_instances, num_segments = len(handles), variable_compress_num_segments(desc.max_samples)
+    stream = torch.cuda.current_stream(device)
+    d_raws = torch.from_numpy(handles.view(np.int32)).to(device)
+    d_rates = torch.zeros((num_instances, num_segments, desc.max_tracks, 4), dtype=torch.uint8, device=device)
+    d_results = torch.zeros((num_instances, 2), dtype=torch.int32, device=device)
+    d_workspace = torch.zeros(find_bit_rates_workspace_bytes(num_instances, desc.max_tracks, desc.max_samples) + 16, dtype=torch.uint8, device=device)
+    desc.workspace = d_workspace.data_ptr()
+    ctx.find_bit_rates_batch(d_raws.data_ptr(), num_instances, desc, d_rates.data_ptr(), num_segments * desc.max_tracks * 4, desc.max_tracks * 4, d_results.data_ptr(),
+                             stream=stream.cuda_stream)
+    stream.synchronize()
+    return d_rates, d_results.cpu().numpy().view(np.uint32).reshape(num_instances, 2)
+
+
+def find_bit_rates(ctx, raws, level="medium", default_pose=None, parents=None, precision=1.0e-4, shell_distance=1.0, track_precisions=None, track_shell_distances=None,
+                   optimize_loops=False):
+    """acl::find_optimal_bit_rates -- the bit rate search of compress_track_list with quatf_drop_w_variable / vector3f_variable /
+    vector3f_variable at the levels "lowest", "low" and "medium" (one search) -- for raw track arrays as one launch: `raws` is a handle
+    or a list of handles; the settings are compress_tracks_variable's. Returns a uint8 array [instances, segments, tracks, 4] of
+    { rotation, translation, scale, 0 } entries over the segments and tracks of the largest array, zero-filled before the launch: 255
+    marks a constant or default sub-track, rows and entries an instance does not have stay 0. It is the table compress_tracks_variable
+    takes. Raises RuntimeError with the reference's message when a sample is not finite, ValueError when an instance is refused.
+    Synchronous; the buffers are torch tensors on the context's device."""
+    handles = np.atleast_1d(np.asarray(raws, dtype=np.uint32))
+    infos = [ctx.raw_tracks_info(int(handle)) for handle in handles]
+    if len(handles) == 0:
+        return np.zeros((0, 0, 0, 4), dtype=np.uint8)
+    d_rates, results = _find_bit_rates(ctx, handles, infos, level, COMPRESS_OPTIMIZE_LOOPS if optimize_loops else 0, default_pose, parents, precision, shell_distance,
+                                       track_precisions, track_shell_distances)
+    _raise_for_search_results(handles, results)
+    return d_rates.cpu().numpy()
+
+
+def _raise_for_search_results(handles, results):
+    for i in range(len(handles)):
+        if int(results[i, 0]) == COMPRESS_NOT_FINITE:
+            raise RuntimeError("Some samples are not finite")
+        if int(results[i, 0]) != COMPRESS_OK:
+            raise ValueError(f"instance {i} (raw track array {int(handles[i])}) was refused (ACLHIP_COMPRESS_REFUSED)")
+
+
 def compress_tracks_variable(ctx, raws, bit_rates=(16, 16, 16), default_pose=None, parents=None, precision=1.0e-4, shell_distance=1.0, track_precisions=None,
-                             track_shell_distances=None, optimize_loops=False, include_parent_track_indices=False, include_track_descriptions=False):
+                             track_shell_distances=None, optimize_loops=False, include_parent_track_indices=False, include_track_descriptions=False, level="medium"):
     """acl::compress_track_list with quatf_drop_w_variable rotations and vector3f_variable translations and scales AT GIVEN BIT RATES for
     raw track arrays as one launch, like compress_tracks: `raws` is a handle or a list of handles. bit_rates is three uniform rates
     (rotation, translation, scale: 0 .. 24), or a uint8 table of { rotation, translation, scale, 0 } entries: [tracks, 4] shared by every
     instance and segment, [segments, tracks, 4] shared by the instances, or [instances, segments, tracks, 4]; it covers
-    variable_compress_num_segments(samples) rows and the tracks of the largest array. Rows are sized from aclhip_variable_compress_bound.
+    variable_compress_num_segments(samples) rows and the tracks of the largest array. bit_rates="search" runs find_bit_rates at `level`
+    with the same settings first and compresses at its table, which stays on the device: the reference's compress_track_list at the
+    levels lowest to medium. Rows are sized from aclhip_variable_compress_bound.
     Returns a list of 16 byte aligned numpy uint8 blobs in the format the fast decode paths read. Raises RuntimeError with the
     reference's message when a sample is not finite, ValueError when an instance is refused (a rate above 24, a rate of 0 in a blob of
     one segment included). Synchronous; the buffers are torch tensors on the context's device."""
@@ -1904,24 +2003,35 @@ def compress_tracks_variable(ctx, raws, bit_rates=(16, 16, 16), default_pose=Non
         return []
     desc = CompressVariableDesc()
     desc.max_samples = max(int(info.num_samples) for info in infos)
-    rates = np.asarray(bit_rates, dtype=np.uint8)
-    if rates.ndim == 1:
-        if rates.shape[0] != 3:
-            raise ValueError("uniform bit rates are three: rotation, translation, scale")
-        desc.rotation_bit_rate, desc.translation_bit_rate, desc.scale_bit_rate = (int(rate) for rate in rates)
+    tables = None
+    if isinstance(bit_rates, str):
+        if bit_rates != "search":
+            raise ValueError('bit_rates is three rates, a table or "search"')
+        tables = _upload_track_tables(ctx, default_pose, parents, track_precisions, track_shell_distances)         # (once, for both calls)
+        d_rates, results = _find_bit_rates(ctx, handles, infos, level, flags, default_pose, parents, precision, shell_distance, track_precisions, track_shell_distances, tables)
+        _raise_for_search_results(handles, results)
+        desc.bit_rates = d_rates.data_ptr()                                                 # (alive until the launch has run)
+        desc.bit_rate_segment_stride = d_rates.shape[2] * 4
+        desc.bit_rate_instance_stride = d_rates.shape[1] * d_rates.shape[2] * 4
     else:
-        if rates.shape[-1] != 4:
-            raise ValueError("a bit rate table holds { rotation, translation, scale, 0 } per track")
-        rates = np.ascontiguousarray(rates)
-        d_rates = torch.from_numpy(rates).to(torch.device("cuda", ctx.device_index))        # (alive until the launch has run)
-        desc.bit_rates = d_rates.data_ptr()
-        desc.bit_rate_segment_stride = rates.shape[-2] * 4 if rates.ndim >= 3 else 0
-        desc.bit_rate_instance_stride = rates.shape[-3] * rates.shape[-2] * 4 if rates.ndim == 4 else 0
+        rates = np.asarray(bit_rates, dtype=np.uint8)
+        if rates.ndim == 1:
+            if rates.shape[0] != 3:
+                raise ValueError("uniform bit rates are three: rotation, translation, scale")
+            desc.rotation_bit_rate, desc.translation_bit_rate, desc.scale_bit_rate = (int(rate) for rate in rates)
+        else:
+            if rates.shape[-1] != 4:
+                raise ValueError("a bit rate table holds { rotation, translation, scale, 0 } per track")
+            rates = np.ascontiguousarray(rates)
+            d_rates = torch.from_numpy(rates).to(torch.device("cuda", ctx.device_index))        # (alive until the launch has run)
+            desc.bit_rates = d_rates.data_ptr()
+            desc.bit_rate_segment_stride = rates.shape[-2] * 4 if rates.ndim >= 3 else 0
+            desc.bit_rate_instance_stride = rates.shape[-3] * rates.shape[-2] * 4 if rates.ndim == 4 else 0
 
     def workspace_bytes(num_instances, max_tracks):
         return compress_variable_workspace_bytes(num_instances, max_tracks, desc.max_samples)
     return _compress_transform_tracks(ctx, ctx.compress_tracks_variable_batch, workspace_bytes, desc, raws, flags, default_pose, parents, precision, shell_distance,
-                                      track_precisions, track_shell_distances, bound=variable_compress_bound)
+                                      track_precisions, track_shell_distances, bound=variable_compress_bound, tables=tables)
 
 
 def compress_tracks_at_precision(ctx, raw, skeleton, shells, precision, parents=None, default_pose=None, shell_distance=1.0, optimize_loops=False, **error_settings):

@@ -216,7 +216,8 @@ const char* aclhip_last_error_message(const aclhip_context* context);
  * aclhip_compress_raw_tracks_batch -- and for the drop-w transform compressor -- aclhip_compress_tracks_desc,
  * aclhip_compress_tracks_workspace_bytes and aclhip_compress_tracks_batch -- and for the variable formats at given bit rates --
  * aclhip_compress_variable_desc, aclhip_variable_compress_num_segments, aclhip_variable_compress_bound,
- * aclhip_compress_variable_workspace_bytes and aclhip_compress_tracks_variable_batch).
+ * aclhip_compress_variable_workspace_bytes and aclhip_compress_tracks_variable_batch -- and for their bit rate search --
+ * aclhip_find_bit_rates_desc, aclhip_find_bit_rates_workspace_bytes and aclhip_find_bit_rates_batch).
  * A caller compiled against another header would hand over structs of another shape; aclhip_abi_version() says what the LIBRARY was
  * built with, and the C++ mirror (aclhip.hpp) refuses to create a context when the two differ. */
 #define ACLHIP_ABI_VERSION 6u
@@ -1947,7 +1948,8 @@ uint64_t aclhip_transform_compress_workspace_bytes(uint32_t num_instances, uint3
  * tail; the stream, one lane per output dword (one 4 byte load, a byte swap, one coalesced store); the scalar compressor's hash.
  *   Left out (nothing here precludes them): the variable formats and everything they need (segmenting, range reduction, the bit rate
  * search; the error metric over the hierarchy and quatf_drop_w_full exist: aclhip_compress_tracks_batch, below; so do the variable formats at given
- * bit rates, with segmenting and range reduction: aclhip_compress_tracks_variable_batch, below; the search does not); additive bases; track and list names; output_index remapping and
+ * bit rates, with segmenting and range reduction: aclhip_compress_tracks_variable_batch, below; so does the search that finds those rates:
+ * aclhip_find_bit_rates_batch, below); additive bases; track and list names; output_index remapping and
  * stripped tracks; a flag that normalizes rotations within a tolerance; the C++ mirror in aclhip.hpp.
  *   What it costs (no time is promised; one MI355X, 4 096 instances over 256 distinct arrays of 100 tracks x 301 samples -- the bench's
  * pose shape, 91 % of the rotations, a third of the translations and a tenth of the scales animated: 5.92 GB of samples, 2.43 GB of
@@ -2044,8 +2046,8 @@ uint64_t aclhip_compress_tracks_workspace_bytes(uint32_t num_instances, uint32_t
  * descending order with samples across the lanes, which also takes the step 0 refusal, the finite test and the vote; the analysis, one wave
  * per (instance, track): two shell error ballots for the rotation, the raw call's for translation and scale; the raw call's layout and
  * stream with three words per rotation; the hash. No atomics besides the refusal counter: the same bytes on every run.
- *   Left out: the variable formats, segmenting, range reduction and the bit rate search (all but the search exist since:
- * aclhip_compress_tracks_variable_batch, below); the matrix error metric and additive bases; track and list names; output_index
+ *   Left out: the variable formats, segmenting, range reduction and the bit rate search (all exist since:
+ * aclhip_compress_tracks_variable_batch and aclhip_find_bit_rates_batch, below); the matrix error metric and additive bases; track and list names; output_index
  * remapping; the C++ mirror in aclhip.hpp. What it costs: profiles/compress_tracks.md. */
 aclhip_status aclhip_compress_tracks_batch(aclhip_context* context, const aclhip_raw_tracks* raws /* DEVICE [num_instances] */,
 	uint32_t num_instances, const aclhip_compress_tracks_desc* desc, void* blobs /* DEVICE */, uint64_t blob_stride_bytes,
@@ -2162,12 +2164,114 @@ uint64_t aclhip_compress_variable_workspace_bytes(uint32_t num_instances, uint32
  * segment ranges and streams; the segment ranges, one wave per (instance, segment) with lanes over the animated sub-tracks; the stream,
  * one lane per output dword, which finds its sub-track in the prefix sums and recomputes every component; the hash. No atomics besides
  * the refusal counter and no zero fill: the same bytes on every run.
- *   Left out: the bit rate search and compression levels; mixed full / variable formats; keyframe stripping, database support and the
+ *   Left out: the bit rate search (a call of its own: aclhip_find_bit_rates_batch, below, writes the table this call reads); mixed full /
+ * variable formats; keyframe stripping, database support and the
  * contributing error; the matrix error metric and additive bases; track and list names; output_index remapping; the C++ mirror in
  * aclhip.hpp; anything against the serial hash. What it costs: profiles/compress_variable.md. */
 aclhip_status aclhip_compress_tracks_variable_batch(aclhip_context* context, const aclhip_raw_tracks* raws /* DEVICE [num_instances] */,
 	uint32_t num_instances, const aclhip_compress_variable_desc* desc, void* blobs /* DEVICE */, uint64_t blob_stride_bytes,
 	aclhip_compress_result* results /* DEVICE [num_instances] */, void* stream);
+
+/* ---- the variable formats' bit rate search ---------------------------------------------------------------------------------------------
+ * acl::find_optimal_bit_rates (compression/impl/quantize.transform.h:1174-1523) for quatf_drop_w_variable / vector3f_variable /
+ * vector3f_variable and the qvvf error metric at the compression levels lowest, low and medium, batched: THE RATE TABLE
+ * aclhip_compress_tracks_variable_batch reads, in exactly that call's layout. "Search, then compress" with the same settings is the
+ * reference's compress_track_list at those levels -- up to the one step where this library's bytes are its own, the normalization of
+ * rotations (aclhip_compress_tracks_batch, step 1): a last bit there can flip a comparison that sits on a threshold, and the search
+ * then takes another road. Measured against the reference on 28 clips (tests/test_bit_rate_search_oracle.py): 0.56 % of the animated
+ * sub-track rates differ, 2.5 % in the worst clip, the stream bits by 0.11 % -- what the reference shows against itself when its input
+ * rotations move by one ulp (0.51 %, 2.5 %, 0.10 %).
+ *   Results (size 0), the statuses ACLHIP_COMPRESS_OK, ACLHIP_COMPRESS_NOT_FINITE and ACLHIP_COMPRESS_REFUSED, refusal counting,
+ * alignment rules, stream ordering, "uploads nothing" and graph capture are as for aclhip_compress_tracks_variable_batch. This is an
+ * addition to ABI version 6: new names only, no existing struct or function changes. */
+typedef struct aclhip_find_bit_rates_desc
+{
+	uint32_t flags;                        /*   0  as aclhip_compress_variable_desc: ACLHIP_COMPRESS_OPTIMIZE_LOOPS decides the samples; the two INCLUDE flags are accepted */
+	uint32_t max_tracks;                   /*   4  tracks the workspace was sized for; an instance with more is refused */
+	uint32_t max_samples;                  /*   8  samples the workspace was sized for; an instance with more (behind the looping vote) is refused */
+	uint32_t num_table_tracks;             /*  12  entries of every non-NULL per-track table below */
+	const void* default_pose;              /*  16  DEVICE or NULL, as in the raw call */
+	const uint32_t* parent_indices;        /*  24  DEVICE or NULL (every track a root) */
+	const float* track_precisions;         /*  32  DEVICE or NULL (-> precision) */
+	const float* track_shell_distances;    /*  40  DEVICE or NULL (-> shell_distance) */
+	float precision;                       /*  48  reference default 0.0001F */
+	float shell_distance;                  /*  52  reference default 1.0F */
+	void* workspace;                       /*  56  DEVICE, 16 byte aligned, aclhip_find_bit_rates_workspace_bytes(num_instances, max_tracks, max_samples) bytes */
+	void* shell_metadata;                  /*  64  DEVICE or NULL, 8 byte aligned: as in aclhip_compress_tracks_desc (the CLIP's shell of step 2, not S0's) */
+	uint32_t level;                        /*  72  acl::compression_level8: 0 lowest, 1 low, 2 medium -- one search: the reference only branches at >= high */
+	uint32_t reserved_word;                /*  76  0 */
+	uint64_t reserved[2];                  /*  80  0 */
+} aclhip_find_bit_rates_desc;              /* 96 bytes */
+
+/* Host only. aclhip_compress_variable_workspace_bytes and, per instance and segment of max_samples, 16 bytes and 82 bytes per track (the
+ * segment ranges as 18 floats, the segment's shell, an entry of the chain under work); each part rounded up to 16, 128 bits wide, capped. */
+uint64_t aclhip_find_bit_rates_workspace_bytes(uint32_t num_instances, uint32_t max_tracks, uint32_t max_samples);
+
+/* The definition. All arithmetic is fp32, one IEEE operation at a time, never fused, denormals kept; divisions are true divisions. Steps
+ * 0 to 8 are those of aclhip_compress_tracks_variable_batch, word for word: the statuses, the samples S behind the vote, the sub-track
+ * types, has_scale, the clip ranges {lo, extent}, the segments, and per segment and animated sub-track {pmin, pext} and m_s (n_s with
+ * one segment). The search runs per segment; nothing of one segment enters another. normalize(q) is step 1's. A rotation made from
+ * x, y, z is Q(x, y, z) = normalize((x, y, z, sqrtf(fabsf(((1.0F - x * x) - y * y) - z * z)))) (rotation_to_quat_32, rtm::quat_normalize).
+ *   S0. THE SEGMENT'S SHELL (quantize.transform.h:232, rigid_shell_utils.h:175-283). The search does not use step 2's shell. For every
+ *      segment the reference recomputes {local_b, sprec_b} by step 2's walk -- the same order, the same strict comparison, the same
+ *      "+ prec_b when d != dist_b" -- over the segment's samples of WHAT THE SEGMENT'S STREAMS HOLD at that point of the compressor, not
+ *      of the registered transforms: per kind the x, y, z of m_s of an animated sub-track (the range-normalized sample), of sample 0 of a
+ *      constant one (the rotation as step 4 left it), of the default of a default one; the rotation is Q of its three. Both errors below
+ *      use this {local_b, sprec_b}. (With the clip's shell in their place 10.7 % of the reference's rates are missed instead of 0.56 %.)
+ *   S1. The sample a rate stands for (sample_streams.h:163-212, 306-355, 446-495), a pure function of (sub-track, sample, rate): the
+ *      reference's track_bit_rate_database is a cache of it and is not rebuilt. decay(x, bits) = floorf(x * (float)(2^bits - 1) + 0.5F) *
+ *      (1.0F / (float)(2^bits - 1)) per component (decay_vector3_uXX, _u48). For an animated sub-track at rate r and sample s: r in
+ *      1 .. 23: v = decay(m_s, r), then v * pext + pmin (only with more than one segment), then v * extent + lo, a multiply then an add
+ *      each; r = 0: decay(n of the segment's FIRST sample, 16), then * extent + lo only; r = 24: the unnormalized x, y, z of step 9.
+ *      A rotation is Q(v). A constant sub-track contributes its sample 0 (a rotation as normalize of what step 4 left), a default one
+ *      the default as given. The S1 transform of a track at rates (r, t, s) is {rotation, translation, scale} so made.
+ *   S2. The two errors (:674-867), both of track b at local_b against sprec_b of S0. E(A, B) is shell_error(local_b, A, B) when has_scale;
+ *      otherwise calculate_error_no_scale: only the points (d,0,0) and (0,d,0), through qvv_mul_point3 WITHOUT the scale
+ *      (transform_error_metrics.h:360-378). The raw transform of a sample is {normalize(r_s as step 4 left it), t_s, s_s}. LOCAL error:
+ *      E(raw, S1 transform). OBJECT error: both sides multiplied down the chain root = c_0, c_1 .. c_n = b: O_0 = L_0, O_k =
+ *      {normalize(quat_mul(L_k.q, O_k-1.q)), quat_mul_vector3(L_k.t * O_k-1.s, O_k-1.q) + O_k-1.t, L_k.s * O_k-1.s} with has_scale,
+ *      without it the same with every scale 1 (qvv_normalize of qvv_mul / qvv_mul_no_scale, :289-333; always the quaternion route: a
+ *      negative scale does not leave it); then E(O_n raw, O_n lossy). A scan UNTIL THE ERROR IS TOO HIGH returns the maximum, from 0.0F,
+ *      over the samples up to and including the first whose error is >= sprec_b; a scan TO THE END the maximum over all.
+ *   S3. Local phase (:869-989, 1111-1140), per track with an animated sub-track. The list: every tuple of one rate 0 .. 24 per animated
+ *      kind (rotation, translation, scale in that order), sorted by the summed bits of a component (rate r: r bits, 24: 32), then by the
+ *      rates themselves, the first kind first -- the rule of the reference's generator script; the library makes the three lists from it
+ *      at compile time. With one segment a tuple with a rate of 0 is skipped. best_error = 1e10F; walk the list: the tuple's local error
+ *      scanned until too high; error < best_error (strict) replaces best and best_error, across sizes. At the first tuple whose size
+ *      differs from the one before it while best_error < sprec_b, stop. The track's rates are best; the byte of a sub-track that is not
+ *      animated is 255 and never changes.
+ *   S4. Object phase (:997-1098, 1227-1475). Tracks in the order (parent_b + 1 in 32 bits, b): roots first. Per track b with chain c_0 .. c_n
+ *      and all scans until too high unless said: error = object error of b; if error < sprec_b the track is done. Else loop while
+ *      error >= sprec_b: for k = n down to 0 (own track first, then toward the root): INCREASE c_k -- of the candidates "c_k's scale + 1"
+ *      (only with has_scale), "translation + 1", "rotation + 1", in that order, each only where that rate is below 24 (the reference's
+ *      three nested loops with their breaks, written out in the kernel), the one whose object error MEASURED AT c_k, not at b, is lowest
+ *      and strictly below b's error before the loop's round; none: c_k is skipped -- then the object error of b with c_k so increased;
+ *      strictly below the best of this round so far: it becomes the round's best, and if also < sprec_b no further k is tried. A round
+ *      that found none ends the loop; otherwise the best is applied and, unless it is < sprec_b, the loop goes on from its error. Then the
+ *      object error of b TO THE END is taken (as is every error from here on), and while it is >= sprec_b: for k = n down to 0, while
+ *      the error is >= sprec_b: the smallest of c_k's three bytes (the first of equals; 255 counts as 255) -- if it is >= 24, c_k is
+ *      maxed out, next k --, or the translation when rotation == translation < 24 and the scale byte is >= 24, is raised by one; the
+ *      error is measured again; c_k keeps the rates of its lowest error so far (its own at the start included) and the error goes on from
+ *      that; < sprec_b ends everything. When every c_k was maxed out the track is done. The reference's last pass (rates to the maximum)
+ *      is for quatf_full rotations only: never here. Every loop ends: a round of the first loop that goes on raises a rate, and rates stop
+ *      at 24; in the last pass every c_k ends below the threshold or maxed out, so its outer loop runs once (it may LOWER rates again:
+ *      c_k keeps its best).
+ *   Output. Four bytes { rotation, translation, scale, 0 } per (instance i, segment g, track b) at bit_rates + i * instance_stride + g *
+ *      segment_stride + 4 * b, for b < T and the segments the instance has behind the vote; 255 for a constant or default sub-track.
+ *      Other rows and entries are not touched. An instance that ends with another status than ACLHIP_COMPRESS_OK writes nothing to its rows.
+ *   Refused per instance: everything aclhip_compress_tracks_variable_batch refuses that does not concern rates or rows.
+ * ACLHIP_ERROR_INVALID_ARGUMENT before any device call, each with a message: what that call refuses of the arguments both have;
+ * max_samples == 0; a level of 3 or 4 (high, highest: not built) or above; a NULL table, one not 4 byte aligned, strides that are no
+ * multiples of 4, a segment_stride below 4 * max_tracks or an instance_stride below aclhip_variable_compress_num_segments(max_samples)
+ * segment strides (the writers of two rows must not meet); a table -- it is WRITTEN -- that overlaps anything else the call reads or writes.
+ *   Five launches (DESIGN.md 4.7 "Bit rate search"): the shell and the analysis of the variable call, unchanged; per (instance, segment)
+ * the segment ranges and S0; per (instance, segment, track) S3 from a table of S1 in LDS, lanes over the tuples of a size; per (instance,
+ * segment) S4 with lanes over the samples. No atomics besides the refusal counter and no zero fill: the same bytes on every run.
+ *   Left out: the levels high and highest (chains with two and three increments); the matrix error metric; additive bases; the
+ * contributing error and keyframe stripping. What it costs: profiles/bit_rate_search.md. */
+aclhip_status aclhip_find_bit_rates_batch(aclhip_context* context, const aclhip_raw_tracks* raws /* DEVICE [num_instances] */,
+	uint32_t num_instances, const aclhip_find_bit_rates_desc* desc, uint8_t* bit_rates /* DEVICE */, uint64_t instance_stride,
+	uint64_t segment_stride, aclhip_compress_result* results /* DEVICE [num_instances] */, void* stream);
 
 /* ---- multi-GPU ---------------------------------------------------------------------------------- */
 

@@ -1,0 +1,301 @@
+"""aclhip_find_bit_rates_batch through the C ABI: find_optimal_bit_rates (levels lowest to medium) of registered raw track arrays. The
+expected tables are the restatement's (tests/bit_rate_search_restatement.py, which tests/test_bit_rate_search_oracle.py holds to the
+reference's compressor), and every comparison is on BYTES: both sides follow one definition, nothing has a tolerance.
+
+The table is a flat buffer of a sentinel byte: a guard, n instances of `instance_stride` bytes, a guard. One comparison holds the four
+bytes of every (instance, segment behind the vote, track) to the restatement and EVERYTHING ELSE to the sentinel: the rows of segments
+the vote removed, the entries of tracks an array does not have, the room between rows of a larger stride, the rows of an instance that
+is refused or not finite. The shapes are the smallest at which each mechanism can still go wrong: T in 1, 3, 5, 17, 65 (65: one more
+than a wave of sub-track lanes) and S in 2 (the shortest scan), 31 (one segment: rates start at 1), 33 (17 + 16) and 65 (four
+segments). The sample rate is a power of two. Then "search, then compress" end to end. Needs a GPU. Fails on a library without the call."""
+import numpy as np
+import pytest
+
+from acl_amd import runtime
+import bit_rate_search_restatement as search_restatement
+import variable_compress_restatement as restatement
+from variable_compress_restatement import ANIMATED, IDENTITY, OPTIMIZE_LOOPS
+from test_gpu_lossy_rotation_compress import GUARD, SENTINEL, Launched, Registered
+
+pytestmark = pytest.mark.gpu
+
+RATE = 32.0
+PRECISION, SHELL = 0.01, 3.0
+TRACK_COUNTS, SAMPLE_COUNTS = (1, 3, 5, 17, 65), (2, 31, 33, 65)
+SHAPES = [(t, s) for t in TRACK_COUNTS for s in SAMPLE_COUNTS]
+MAX_TRACKS, MAX_SAMPLES, MAX_SEGMENTS = 65, 65, 4
+REFUSED, NOT_FINITE = runtime.COMPRESS_REFUSED, runtime.COMPRESS_NOT_FINITE
+
+
+@pytest.fixture(scope="module")
+def ctx():
+    context = runtime.Context(0)
+    yield context
+    context.close()
+
+
+def find(samples, **settings):
+    settings.setdefault("precision", PRECISION)
+    settings.setdefault("shell_distance", SHELL)
+    return search_restatement.find_bit_rates(samples, RATE, **settings)
+
+
+def launch(ctx, handles, max_tracks=MAX_TRACKS, max_samples=MAX_SAMPLES, flags=0, parents=None, default_pose=None, track_precisions=None, track_shell_distances=None,
+           level=2, segment_stride=None, instance_stride=None, precision=PRECISION):
+    """One launch over `handles` into a table of sentinel bytes"""
+    import torch
+    device = torch.device("cuda:0")
+    n = len(handles)
+    max_segments = runtime.variable_compress_num_segments(max_samples)
+    segment_stride = 4 * max_tracks if segment_stride is None else segment_stride
+    instance_stride = max_segments * segment_stride if instance_stride is None else instance_stride
+    flat = torch.full((GUARD + n * instance_stride + GUARD,), SENTINEL, dtype=torch.uint8, device=device)
+    d_handles = torch.from_numpy(np.asarray(handles, dtype=np.uint32).view(np.int32)).to(device)
+    d_results = torch.full((n, 2), 0x5A5A5A5A, dtype=torch.int32, device=device)
+    workspace_bytes = runtime.find_bit_rates_workspace_bytes(n, max_tracks, max_samples)
+    d_workspace = torch.full((workspace_bytes + GUARD,), SENTINEL, dtype=torch.uint8, device=device)
+    d_metadata = torch.full((GUARD + n * max_tracks * 8 + GUARD,), SENTINEL, dtype=torch.uint8, device=device)
+    desc = runtime.FindBitRatesDesc()
+    desc.shell_metadata = d_metadata.data_ptr() + GUARD
+    desc.flags, desc.max_tracks, desc.max_samples, desc.precision, desc.shell_distance, desc.level = flags, max_tracks, max_samples, precision, SHELL, level
+    desc.workspace = d_workspace.data_ptr()
+    tables = []
+    for field, table, dtype in (("default_pose", default_pose, np.float32), ("parent_indices", parents, np.uint32), ("track_precisions", track_precisions, np.float32),
+                                ("track_shell_distances", track_shell_distances, np.float32)):
+        if table is not None:
+            host = np.ascontiguousarray(table, dtype=dtype)
+            d_table = torch.from_numpy(host.view(np.int32)).to(device)
+            tables.append((host, d_table))
+            setattr(desc, field, d_table.data_ptr())
+            desc.num_table_tracks = host.shape[0]
+    rejected_before = ctx.rejected_instance_count()
+    stream = torch.cuda.current_stream(device)
+    ctx.find_bit_rates_batch(d_handles.data_ptr(), n, desc, flat.data_ptr() + GUARD, instance_stride, segment_stride, d_results.data_ptr(), stream=stream.cuda_stream)
+    stream.synchronize()
+    out = Launched()
+    out.flat, out.n, out.max_tracks, out.instance_stride, out.segment_stride = flat.cpu().numpy(), n, max_tracks, instance_stride, segment_stride
+    out.results = d_results.cpu().numpy().view(np.uint32).reshape(n, 2)
+    out.metadata = d_metadata.cpu().numpy()
+    out.rejected = ctx.rejected_instance_count() - rejected_before
+    assert np.all(d_workspace.cpu().numpy()[workspace_bytes:] == SENTINEL)                      # the workspace is as large as it says
+    for host, d_table in tables:
+        assert np.array_equal(d_table.cpu().numpy().view(np.uint8).reshape(-1), host.view(np.uint8).reshape(-1))      # the inputs are only read
+    return out
+
+
+def check(launched, expected):
+    """expected: per instance a Search of the restatement, or the status of an instance that writes nothing"""
+    want = np.full(launched.flat.shape, SENTINEL, dtype=np.uint8)
+    metadata = np.full(launched.metadata.shape, SENTINEL, dtype=np.uint8)
+    statuses = []
+    for i, found in enumerate(expected):
+        if isinstance(found, int):
+            statuses.append(found)
+            continue
+        statuses.append(runtime.COMPRESS_OK)
+        for g in range(found.table.shape[0]):
+            at = GUARD + i * launched.instance_stride + g * launched.segment_stride
+            want[at: at + 4 * found.table.shape[1]] = found.table[g].reshape(-1)
+        at = GUARD + i * launched.max_tracks * 8
+        metadata[at: at + 8 * found.base.shells.shape[0]] = found.base.shells.view(np.uint8).reshape(-1)
+    different = np.flatnonzero(launched.flat != want)
+    assert different.size == 0, (different.size, [(int(d - GUARD) // launched.instance_stride, int(d - GUARD) % launched.instance_stride // launched.segment_stride,
+                                                   int(d - GUARD) % launched.segment_stride // 4, int(d - GUARD) % 4, int(launched.flat[d]), int(want[d])) for d in different[:12]])
+    assert launched.results[:, 0].tolist() == statuses and (launched.results[:, 1] == 0).all()
+    assert launched.rejected == statuses.count(REFUSED)
+    if all(not isinstance(found, int) for found in expected):
+        assert np.array_equal(launched.metadata, metadata)
+
+
+@pytest.fixture(scope="module")
+def sweep(ctx):
+    """every shape registered once, from variable_compress_restatement.mixed_clip: track b of array k has the (b + 9 k)-th of the 27
+    (rotation, translation, scale) type triples, every seventh array no scale (the _no_scale forms), about every second array of more than two
+    samples ends on its first sample (the vote removes it: 65 samples then make three segments and leave the fourth row alone); the restatement's tables with tree(0, 65), loops on -- computed once, shared
+    and left unchanged"""
+    with Registered(ctx) as arrays:
+        clips = [restatement.mixed_clip(k, num_samples, num_tracks, offset=9 * k, scales="default" if k % 7 == 3 else "mixed", close_loop=(k // 4 + k) % 2 == 1 and num_samples > 2)
+                 for k, (num_tracks, num_samples) in enumerate(SHAPES)]
+        handles = [arrays.add(samples) for samples in clips]
+        parents = restatement.tree(0, MAX_TRACKS)
+        found = [find(samples, parents=parents, flags=OPTIMIZE_LOOPS) for samples in clips]
+        yield ctx, handles, clips, parents, found
+
+
+def test_the_table_is_the_restatements(sweep):
+    """mixed shapes and a repeated handle in one launch: every byte of every row, the sentinel everywhere else, the results, the clip's
+    shell as metadata"""
+    ctx, handles, clips, parents, found = sweep
+    order = [(7 * i + 2) % len(handles) for i in range(len(handles) + 3)]
+    check(launch(ctx, [handles[k] for k in order], flags=OPTIMIZE_LOOPS, parents=parents), [found[k] for k in order])
+    by_shape = dict(zip(SHAPES, found))
+    assert [len(by_shape[17, s].base.segments) for s in SAMPLE_COUNTS] == [1, 1, 2, 4]
+    assert any(f.base.wrap and f.base.num_samples == clip.shape[0] - 1 for f, clip in zip(found, clips))            # a vote that removed a sample
+    assert by_shape[5, 65].base.wrap and len(by_shape[5, 65].base.segments) == 3 and by_shape[5, 65].base.num_samples == 64 and by_shape[65, 33].base.segments == [(0, 17), (17, 16)]
+    assert len(set().union(*(restatement.triples_of(f.base) for f in found))) == 27 and len(restatement.triples_of(by_shape[65, 65].base)) == 27
+    assert any(not (f.base.types[2] != restatement.DEFAULT).any() and (f.base.types[0:2] == ANIMATED).any() for f in found)          # a clip without scale
+    # the object phase had work to do, and one segment never has a rate of 0
+    assert any(not np.array_equal(f.table, f.local_table) for f in found)
+    for f in found:
+        animated = np.stack([f.base.types[kind] == ANIMATED for kind in range(3)], axis=1)
+        assert (f.table[:, :, 0:3][:, ~animated] == 255).all() and (f.table[:, :, 0:3][:, animated] <= 24).all()
+        if len(f.base.segments) == 1:
+            assert (f.table[:, :, 0:3][:, animated] >= 1).all()
+
+
+def test_the_three_levels_are_one_search(sweep):
+    ctx, handles, clips, parents, found = sweep
+    picked = [k for k, shape in enumerate(SHAPES) if shape in ((17, 33), (5, 65))]
+    for level in (0, 1):
+        check(launch(ctx, [handles[k] for k in picked], flags=OPTIMIZE_LOOPS, parents=parents, level=level), [found[k] for k in picked])
+
+
+def test_all_roots_and_a_single_chain(ctx):
+    """no parent table: every object error is a local one; a chain of 17: the longest walk, every scale the default"""
+    roots = restatement.mixed_clip(5, 33, 17, offset=9)
+    chain = restatement.mixed_clip(6, 33, 17, offset=18, scales="default")
+    chain_parents = restatement.tree(0, 17, "chain")
+    with Registered(ctx) as arrays:
+        h_roots, h_chain = arrays.add(roots), arrays.add(chain)
+        found = find(roots)
+        assert np.array_equal(found.table, found.local_table)
+        check(launch(ctx, [h_roots], max_tracks=17, max_samples=33), [found])
+        deep = find(chain, parents=chain_parents)
+        assert not np.array_equal(deep.table, deep.local_table)
+        check(launch(ctx, [h_chain, h_chain], max_tracks=17, max_samples=33, parents=chain_parents), [deep, deep])
+
+
+def half_frozen(seed, num_samples, num_tracks):
+    """every sub-track moves in the first 16 samples and stands still behind them (tests/test_variable_compress_oracle.py)"""
+    samples = restatement.clip(seed, num_samples, num_tracks)
+    rng = np.random.default_rng(seed)
+    samples[:, :, 0:4] = restatement.lossy.raw_restatement.unit_quaternions(rng, (num_samples, num_tracks))
+    samples[:, :, 4:7] = rng.uniform(-0.5, 0.5, size=(num_samples, num_tracks, 3))
+    samples[16:] = samples[16]
+    return samples
+
+
+def test_rate_0_where_a_segment_stands_still(ctx):
+    clips = [half_frozen(seed, num_samples, num_tracks) for seed, (num_tracks, num_samples) in enumerate(((5, 49), (17, 33), (4, 65)))]
+    with Registered(ctx) as arrays:
+        handles = [arrays.add(samples) for samples in clips]
+        parents = restatement.tree(1, 17)
+        found = [find(samples, parents=parents) for samples in clips]
+        for f in found:
+            for kind in range(3):
+                tracks = np.flatnonzero(f.base.types[kind] == ANIMATED)
+                assert (f.table[0, tracks, kind] != 0).all() and (f.table[-1, tracks, kind] == 0).all()
+        check(launch(ctx, handles, max_tracks=17, parents=parents), found)
+
+
+def test_precisions_and_shell_distances_per_track_and_a_default_pose(ctx):
+    rng = np.random.default_rng(31)
+    precisions = rng.choice(np.array([0.002, 0.01, 0.05], dtype=np.float32), size=17)
+    distances = rng.choice(np.array([1.0, 3.0, 10.0], dtype=np.float32), size=17)
+    pose = restatement.lossy.raw_restatement.bind_pose(21, 17)
+    clips = [restatement.mixed_clip(7, 33, 17, offset=3, default_pose=pose), restatement.mixed_clip(8, 65, 5, offset=12, default_pose=pose)]
+    parents = restatement.tree(3, 17)
+    settings = {"parents": parents, "track_precisions": precisions, "track_shell_distances": distances, "default_pose": pose}
+    with Registered(ctx) as arrays:
+        handles = [arrays.add(samples) for samples in clips]
+        found = [find(samples, **settings) for samples in clips]
+        assert len({float(p) for p in found[0].shells[:, :, 1].reshape(-1)}) > 1
+        check(launch(ctx, handles, max_tracks=17, **settings), found)
+
+
+def test_an_instance_that_ends_with_a_status_leaves_its_rows(ctx):
+    """handle 0 and a parent behind its child (refused), a sample that is not finite, more samples than max_samples -- each between served
+    neighbours whose rows are right"""
+    small, long = restatement.mixed_clip(2, 12, 5, offset=20), restatement.mixed_clip(3, 40, 5, offset=20)
+    parents = restatement.tree(4, 5)
+    with Registered(ctx) as arrays:
+        h_small, h_long = arrays.add(small), arrays.add(long)
+        bad = long.copy()
+        bad[7, 2, 5] = np.nan
+        h_bad = arrays.add(bad)
+        f_small, f_long = find(small, parents=parents), find(long, parents=parents)
+        settings = {"max_tracks": 5, "max_samples": 40, "parents": parents}
+        check(launch(ctx, [h_small, 0, h_long, h_bad, h_small], **settings), [f_small, REFUSED, f_long, NOT_FINITE, f_small])
+        check(launch(ctx, [h_small, h_long, h_small], max_tracks=5, max_samples=39, parents=parents), [f_small, REFUSED, f_small])
+        check(launch(ctx, [h_small, h_long], max_tracks=5, max_samples=40, parents=np.array([0xFFFFFFFF, 0, 3, 0, 0], dtype=np.uint32)), [REFUSED, REFUSED])
+        with pytest.raises(ValueError, match="ACLHIP_COMPRESS_REFUSED"):
+            runtime.find_bit_rates(ctx, [h_small, h_long], parents=np.array([0xFFFFFFFF, 0, 3, 0, 0], dtype=np.uint32), precision=PRECISION, shell_distance=SHELL)
+        with pytest.raises(RuntimeError, match="not finite"):
+            runtime.find_bit_rates(ctx, h_bad, parents=parents, precision=PRECISION, shell_distance=SHELL)
+
+
+def test_strides_larger_than_the_minimum(sweep):
+    ctx, handles, clips, parents, found = sweep
+    picked = [k for k, shape in enumerate(SHAPES) if shape in ((3, 33), (65, 33), (17, 65), (1, 2))]
+    segment_stride = 4 * MAX_TRACKS + 12
+    check(launch(ctx, [handles[k] for k in picked], flags=OPTIMIZE_LOOPS, parents=parents, segment_stride=segment_stride, instance_stride=MAX_SEGMENTS * segment_stride + 8),
+          [found[k] for k in picked])
+
+
+def test_two_runs_give_the_same_bytes_and_a_capture_replays_to_them(sweep):
+    import torch
+    ctx, handles, clips, parents, found = sweep
+    picked = [k for k, shape in enumerate(SHAPES) if shape[0] in (5, 17)]
+    runs = [launch(ctx, [handles[k] for k in picked], flags=OPTIMIZE_LOOPS, parents=parents) for _ in range(2)]
+    assert np.array_equal(runs[0].flat, runs[1].flat) and np.array_equal(runs[0].results, runs[1].results) and np.array_equal(runs[0].metadata, runs[1].metadata)
+    device = torch.device("cuda:0")
+    n, instance_stride = len(picked), runs[0].instance_stride
+    d_parents = torch.from_numpy(parents.view(np.int32)).to(device)
+    d_handles = torch.from_numpy(np.asarray([handles[k] for k in picked], dtype=np.uint32).view(np.int32)).to(device)
+    flat = torch.full((n * instance_stride,), SENTINEL, dtype=torch.uint8, device=device)
+    d_results = torch.zeros((n, 2), dtype=torch.int32, device=device)
+    d_workspace = torch.zeros((runtime.find_bit_rates_workspace_bytes(n, MAX_TRACKS, MAX_SAMPLES),), dtype=torch.uint8, device=device)
+    desc = runtime.FindBitRatesDesc()
+    desc.flags, desc.max_tracks, desc.max_samples, desc.precision, desc.shell_distance, desc.level = OPTIMIZE_LOOPS, MAX_TRACKS, MAX_SAMPLES, PRECISION, SHELL, 2
+    desc.parent_indices, desc.num_table_tracks, desc.workspace = d_parents.data_ptr(), MAX_TRACKS, d_workspace.data_ptr()
+    stream = torch.cuda.Stream(device)
+    with torch.cuda.stream(stream):
+        captured = torch.cuda.CUDAGraph()
+        with torch.cuda.graph(captured, stream=stream):
+            ctx.find_bit_rates_batch(d_handles.data_ptr(), n, desc, flat.data_ptr(), instance_stride, runs[0].segment_stride, d_results.data_ptr(), stream=stream.cuda_stream)
+        flat.fill_(SENTINEL)         # what the capture itself may have left does not count
+        captured.replay()
+    stream.synchronize()
+    assert np.array_equal(flat.cpu().numpy(), runs[0].flat[GUARD: GUARD + n * instance_stride])
+    assert np.array_equal(d_results.cpu().numpy().view(np.uint32), runs[0].results[:n])
+
+
+def test_search_then_compress_end_to_end(sweep):
+    """runtime.find_bit_rates returns the restatement's table over zeros; compress_tracks_variable(bit_rates="search") is the restatement's
+    blob at that table in every byte; the blob registers. Every track whose threshold the search met in every segment -- the
+    restatement's record -- is to be within its precision by raw_clip_error. raw_clip_error names only the WORST bone of a clip, so
+    this holds in full only where EVERY track met its threshold: then the clip's worst error is within the precision, and at least
+    three of the five clips must be such (all five are). Where some track did not, the test can only say that the worst bone is one
+    of those: a track that met its threshold and ends above its precision behind a worse one would go unnoticed there."""
+    ctx, handles, clips, parents, found = sweep
+    picked = [k for k, shape in enumerate(SHAPES) if shape in ((65, 33), (17, 33), (17, 65), (65, 65), (3, 31))]
+    settings = {"parents": parents, "precision": PRECISION, "shell_distance": SHELL, "optimize_loops": True}
+    tables = runtime.find_bit_rates(ctx, [handles[k] for k in picked], **settings)
+    assert tables.shape == (len(picked), MAX_SEGMENTS, MAX_TRACKS, 4) and tables.dtype == np.uint8
+    blobs = runtime.compress_tracks_variable(ctx, [handles[k] for k in picked], bit_rates="search", **settings)
+    identity = np.tile(IDENTITY, (MAX_TRACKS, 1))
+    all_met = 0
+    for k, table, blob in zip(picked, tables, blobs):
+        want = np.zeros((MAX_SEGMENTS, MAX_TRACKS, 4), dtype=np.uint8)
+        want[:found[k].table.shape[0], :found[k].table.shape[1]] = found[k].table
+        assert np.array_equal(table, want)
+        num_tracks = clips[k].shape[1]
+        expected = restatement.compress(clips[k], RATE, found[k].table, parents=parents, flags=OPTIMIZE_LOOPS, precision=PRECISION, shell_distance=SHELL)
+        assert np.array_equal(blob, expected.blob)
+        status, message = runtime.check_clip(blob, check_hash=True)
+        assert status == 0, message
+        clip = ctx.register_clip(blob)
+        skeleton = ctx.register_skeleton(parents[:num_tracks], identity[:num_tracks])
+        try:
+            bone, error, _ = runtime.raw_clip_error(ctx, handles[k], clip, skeleton, SHELL)
+        finally:
+            ctx.unregister_skeleton(skeleton)
+            ctx.unregister_clip(clip)
+        met = found[k].met.all(axis=0)
+        print("shape %s: %d of %d tracks met their threshold in every segment; worst error %.6f at bone %d" % (SHAPES[k], int(met.sum()), num_tracks, error, bone))
+        if met.all():
+            all_met += 1
+            assert error <= PRECISION
+        else:
+            assert error <= PRECISION or not met[bone]
+    assert all_met >= 3

@@ -1,0 +1,159 @@
+#!/usr/bin/env python3
+"""Measurement aid: aclhip_find_bit_rates_batch, HIP events on one stream, on the workload of tools/compress_tracks.py -- its arrays,
+its parent table, its settings: COMPRESS_TRACKS_INSTANCES instances over COMPRESS_TRACKS_ARRAYS distinct raw track arrays of 100
+tracks x 301 samples.
+Before anything is timed the table is CHECKED: the rows of the first FIND_BIT_RATES_RESTATED distinct arrays byte for byte against the
+restatement of tests/bit_rate_search_restatement.py. A mismatch, a refused instance or a status that is not ok exits non-zero.
+Time is reported, never judged: the median of FIND_BIT_RATES_ROUNDS interleaved rounds of FIND_BIT_RATES_REPEATS launches each and the
+spread (max - min) / median; in the same rounds aclhip_compress_tracks_variable_batch at the table the search found, so that the two
+are measured side by side; the bytes of those blobs next to the bytes at a uniform rate of 16. With ACLHIP_LIBRARY pointing at
+libaclhip_lab.so the line also carries the per-phase split: ACLHIP_FIND_BIT_RATES_PHASES=k stops the call behind its k-th launch (shell,
+analysis, segments, local, object), and a phase's time is the difference of two medians measured in the same rounds. With
+FIND_BIT_RATES_AT_PRECISION=1 the first array also goes through runtime.compress_tracks_at_precision, for its blob's size and rate.
+Prints one JSON line."""
+import json
+import os
+import sys
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+sys.path.insert(0, os.path.join(ROOT, "tests"))
+sys.path.insert(0, os.path.join(ROOT, "tools"))
+import torch  # noqa: E402
+from acl_amd import runtime  # noqa: E402
+import compress_tracks as workload  # noqa: E402  (the arrays, the skeleton, the timer)
+import bit_rate_search_restatement as restatement  # noqa: E402  (the checker's restatement)
+
+N, ARRAYS, TRACKS, SAMPLES = workload.N, workload.ARRAYS, workload.TRACKS, workload.SAMPLES
+ROUNDS = int(os.environ.get("FIND_BIT_RATES_ROUNDS", "3"))
+REPEATS = int(os.environ.get("FIND_BIT_RATES_REPEATS", "3"))
+RESTATED = int(os.environ.get("FIND_BIT_RATES_RESTATED", "1"))
+AT_PRECISION = os.environ.get("FIND_BIT_RATES_AT_PRECISION", "0") == "1"
+RATE, PRECISION, SHELL = workload.RATE, workload.PRECISION, workload.SHELL
+PHASES = ("shell", "analysis", "segments", "local", "object")
+KNOB = "ACLHIP_FIND_BIT_RATES_PHASES"
+
+
+def main():
+    if not torch.cuda.is_available():
+        raise SystemExit("tools/find_bit_rates.py needs a GPU: nothing is measured without one")
+    rng = np.random.default_rng(9100 + TRACKS)
+    arrays = [workload.make_array(rng) for _ in range(ARRAYS)]
+    order = rng.integers(0, ARRAYS, size=N)
+    order[:ARRAYS] = np.arange(ARRAYS)[: min(ARRAYS, N)]        # every distinct array is in the batch
+    parents = workload.skeleton(TRACKS)
+    segments = runtime.variable_compress_num_segments(SAMPLES)
+
+    stream = torch.cuda.Stream()
+    s = stream.cuda_stream
+    ctx = runtime.Context(0)
+    handles = np.array([ctx.register_raw_tracks(a, RATE) for a in arrays], dtype=np.uint32)
+    stride = runtime.variable_compress_bound(TRACKS, SAMPLES, 0)
+    with torch.cuda.stream(stream):
+        d_raws = torch.from_numpy(handles[order].view(np.int32)).cuda()
+        d_parents = torch.from_numpy(parents.view(np.int32)).cuda()
+        d_rates = torch.zeros((N, segments, TRACKS, 4), dtype=torch.uint8, device="cuda")
+        d_blobs = torch.zeros((N, stride), dtype=torch.uint8, device="cuda")
+        d_results = torch.zeros((N, 2), dtype=torch.int32, device="cuda")
+        d_workspace = torch.zeros(runtime.find_bit_rates_workspace_bytes(N, TRACKS, SAMPLES), dtype=torch.uint8, device="cuda")
+    search = runtime.FindBitRatesDesc()
+    search.precision, search.shell_distance, search.max_tracks, search.max_samples, search.workspace, search.level = PRECISION, SHELL, TRACKS, SAMPLES, d_workspace.data_ptr(), 2
+    search.parent_indices, search.num_table_tracks = d_parents.data_ptr(), TRACKS
+    desc = runtime.CompressVariableDesc()
+    desc.precision, desc.shell_distance, desc.max_tracks, desc.max_samples, desc.workspace = PRECISION, SHELL, TRACKS, SAMPLES, d_workspace.data_ptr()
+    desc.parent_indices, desc.num_table_tracks = d_parents.data_ptr(), TRACKS
+    desc.bit_rates, desc.bit_rate_segment_stride, desc.bit_rate_instance_stride = d_rates.data_ptr(), 4 * TRACKS, 4 * TRACKS * segments
+
+    def launch_search():
+        ctx.find_bit_rates_batch(d_raws.data_ptr(), N, search, d_rates.data_ptr(), 4 * TRACKS * segments, 4 * TRACKS, d_results.data_ptr(), stream=s)
+
+    def launch_compress():
+        ctx.compress_tracks_variable_batch(d_raws.data_ptr(), N, desc, d_blobs.data_ptr(), stride, d_results.data_ptr(), stream=s)
+
+    # ---- checked before it is timed
+    os.environ.pop(KNOB, None)
+    with torch.cuda.stream(stream):
+        launch_search()
+        results = d_results.cpu().numpy().view(np.uint32).copy()
+        tables = d_rates[:ARRAYS].cpu().numpy()
+    if ctx.rejected_instance_count() != 0 or np.any(results[:, 0] != runtime.COMPRESS_OK):
+        print(f"refused or failed instances: {ctx.rejected_instance_count()}, statuses {np.unique(results[:, 0])}", flush=True)
+        sys.exit(1)
+    for i in range(min(ARRAYS, N, RESTATED)):
+        expected = restatement.find_bit_rates(arrays[i], RATE, parents=parents, precision=PRECISION, shell_distance=SHELL).table
+        if not np.array_equal(tables[i], expected):
+            print(f"MISMATCH with the restatement in the table of array {i}: {int((tables[i] != expected).sum())} bytes", flush=True)
+            sys.exit(1)
+    with torch.cuda.stream(stream):
+        launch_compress()
+        results = d_results.cpu().numpy().view(np.uint32).copy()
+    if np.any(results[:, 0] != runtime.COMPRESS_OK):
+        print(f"the compress call at the table the search found: statuses {np.unique(results[:, 0])}", flush=True)
+        sys.exit(1)
+    blob_bytes = int(results[:, 1].astype(np.int64).sum())
+    animated = tables[:, :, :, 0:3][tables[:, :, :, 0:3] != 255]
+    uniform = runtime.CompressVariableDesc.from_buffer_copy(desc)
+    uniform.bit_rates, uniform.rotation_bit_rate, uniform.translation_bit_rate, uniform.scale_bit_rate = None, 16, 16, 16
+    with torch.cuda.stream(stream):
+        ctx.compress_tracks_variable_batch(d_raws.data_ptr(), N, uniform, d_blobs.data_ptr(), stride, d_results.data_ptr(), stream=s)
+        uniform_bytes = int(d_results.cpu().numpy().view(np.uint32)[:, 1].astype(np.int64).sum())
+
+    at_precision = None
+    if AT_PRECISION:
+        skeleton = ctx.register_skeleton(parents, np.tile(restatement.IDENTITY, (TRACKS, 1)))
+        blob, rate = runtime.compress_tracks_at_precision(ctx, int(handles[0]), skeleton, SHELL, PRECISION, parents=parents, shell_distance=SHELL)
+        searched = runtime.compress_tracks_variable(ctx, int(handles[0]), bit_rates="search", parents=parents, precision=PRECISION, shell_distance=SHELL)[0]
+        clip = ctx.register_clip(searched)
+        error = runtime.raw_clip_error(ctx, int(handles[0]), clip, skeleton, SHELL)[1]
+        ctx.unregister_clip(clip)
+        ctx.unregister_skeleton(skeleton)
+        at_precision = {"uniform_rate": rate, "uniform_rate_blob_bytes": int(blob.size), "searched_blob_bytes": int(searched.size), "searched_raw_clip_error": round(float(error), 6)}
+
+    lab = "lab" in os.path.basename(runtime.library_path())
+    cases = {"search": (launch_search, None), "compress_at_the_table": (launch_compress, None)}
+    if lab:
+        for k in range(1, 5):
+            cases["phases_%d" % k] = (launch_search, str(k))
+
+    def run(case, repeats):
+        call, knob = case
+        if knob is None:
+            os.environ.pop(KNOB, None)
+        else:
+            os.environ[KNOB] = knob
+        return workload.timed(stream, call, repeats)
+
+    for case in cases.values():
+        run(case, 1)
+    samples = {key: [] for key in cases}
+    for _ in range(ROUNDS):
+        for key, case in cases.items():
+            samples[key].append(run(case, REPEATS))
+    os.environ.pop(KNOB, None)
+
+    def summary(values):
+        values = np.array(values)
+        return {"median": round(float(np.median(values)), 2), "min": round(float(values.min()), 2), "max": round(float(values.max()), 2),
+                "spread": round(float((values.max() - values.min()) / np.median(values)), 4)}
+
+    result = {"instances": N, "distinct_arrays": ARRAYS, "tracks": TRACKS, "samples": SAMPLES, "segments": segments, "rounds": ROUNDS, "repeats": REPEATS,
+              "checked_against": "restatement (%d arrays)" % min(ARRAYS, N, RESTATED), "library": os.path.basename(runtime.library_path()),
+              "raw_bytes": int(N * TRACKS * SAMPLES * 48), "searched_blob_bytes": blob_bytes, "uniform_16_blob_bytes": uniform_bytes,
+              "rates": {"min": int(animated.min()), "max": int(animated.max()), "mean": round(float(animated.mean()), 2)} if animated.size else None,
+              "us": {key: summary(values) for key, values in samples.items()}}
+    if at_precision is not None:
+        result["first_array"] = at_precision
+    if lab:
+        total = result["us"]["search"]["median"]
+        upto = [result["us"]["phases_%d" % k]["median"] for k in range(1, 5)] + [total]
+        split = [upto[0]] + [upto[k] - upto[k - 1] for k in range(1, 5)]
+        result["phase_us"] = {name: round(value, 2) for name, value in zip(PHASES, split)}
+        result["phase_share"] = {name: round(value / total, 3) for name, value in zip(PHASES, split)}
+    ctx.close()
+    print(json.dumps(result), flush=True)
+
+
+if __name__ == "__main__":
+    main()
