@@ -211,17 +211,6 @@
 		return result;
 	}
 
-	__device__ __forceinline__ float search_wave_max(float value)
-	{
-		#pragma unroll
-		for (int offset = int(k_wave_size) / 2; offset != 0; offset >>= 1)
-		{
-			const float other = __shfl_xor(value, offset);
-			value = other > value ? other : value;
-		}
-		return __uint_as_float(__builtin_amdgcn_readfirstlane(__float_as_uint(value)));
-	}
-
 	// ---- per (instance, segment): the segment ranges, the segment's shell, the record ------------------------------------------------------------
 	__global__ __launch_bounds__(k_compress_waves_per_block * k_wave_size) void bit_rate_search_segment_kernel(bit_rate_search_launch launch)
 	{
@@ -279,24 +268,13 @@
 				if (type != k_sub_track_animated || !source.multiple)
 					continue;
 				const float* clip_range = source.clip_ranges + size_t(track) * k_variable_range_floats + kind * 6u;
-				float low[3] = { 1.0e10f, 1.0e10f, 1.0e10f }, high[3] = { -1.0e10f, -1.0e10f, -1.0e10f };
-				for (uint32_t sample = out.start; sample < out.start + out.count; ++sample)
-				{
-					const float3 v = variable_compress_normalize3(variable_compress_value(source.samples, source.pose_quads, sample, track, kind), clip_range);
-					const float normalized[3] = { v.x, v.y, v.z };
-					#pragma unroll
-					for (uint32_t c = 0; c < 3; ++c)
-					{
-						low[c] = low[c] < normalized[c] ? low[c] : normalized[c];
-						high[c] = high[c] > normalized[c] ? high[c] : normalized[c];
-					}
-				}
+				float2 padded[3];
+				variable_segment_range(source.samples, source.pose_quads, track, kind, clip_range, out.start, out.count, padded);
 				#pragma unroll
 				for (uint32_t c = 0; c < 3; ++c)
 				{
-					const float2 padded = variable_compress_fixup(low[c], high[c]);
-					ranges[size_t(track) * k_search_segment_floats + kind * 6u + c] = padded.x;
-					ranges[size_t(track) * k_search_segment_floats + kind * 6u + 3u + c] = padded.y;
+					ranges[size_t(track) * k_search_segment_floats + kind * 6u + c] = padded[c].x;
+					ranges[size_t(track) * k_search_segment_floats + kind * 6u + 3u + c] = padded[c].y;
 				}
 			}
 			out.has_scale = __ballot(scaled) != 0 ? 1u : 0u;
@@ -305,7 +283,8 @@
 				launch.segments[wave] = out;
 			__threadfence();		// (the ranges are read back below by other lanes of this wave)
 
-			// S0: the segment's shell, tracks_compress_shell_kernel's walk over what the segment's streams hold
+			// S0: the segment's shell, tracks_compress_shell_kernel's walk over what the segment's streams hold (spelled out here, the
+			// settings included: with any of it shared this kernel takes 65 VGPRs where it takes 61, a wave a SIMD less)
 			float2* shells = launch.segment_shells + wave * base.max_tracks;
 			for (uint32_t track = lane; track < num_tracks; track += k_wave_size)
 				shells[track] = make_float2(base.track_shell_distances != nullptr ? base.track_shell_distances[track] : base.shell_distance,
@@ -343,7 +322,7 @@
 					stretch = length_y > stretch ? length_y : stretch;
 					stretch = length_z > stretch ? length_z : stretch;
 				}
-				stretch = search_wave_max(stretch);
+				stretch = compress_wave_max(stretch);
 				const float own_distance = base.track_shell_distances != nullptr ? base.track_shell_distances[track] : base.shell_distance;
 				const float own_precision = base.track_precisions != nullptr ? base.track_precisions[track] : base.precision;
 				const float parent_shell_distance = distance != own_distance ? stretch + own_precision : stretch;
@@ -568,11 +547,7 @@
 			source.count = at.count;
 			source.multiple = variable_split_of(voted.num_out_samples).num_segments > 1;
 
-			const auto parent_of = [&](uint32_t track) -> uint32_t
-			{
-				const uint32_t parent = base.parent_indices != nullptr ? base.parent_indices[track] : ACLHIP_NO_PARENT;
-				return parent < num_tracks ? parent : ACLHIP_NO_PARENT;
-			};
+			const auto parent_of = [&](uint32_t track) -> uint32_t { return compress_track_parent(base, track, num_tracks); };
 
 			// S2: the object error of chain[links - 1] with the rates of `replaced` taken from `replacement`
 			const auto object_error = [&](uint32_t links, uint32_t replaced, uint32_t replacement, bool until_end) -> float
@@ -595,7 +570,7 @@
 					if (high != 0)
 						error = lane <= uint32_t(__ffsll((long long)high)) - 1u ? error : 0.0f;
 				}
-				return search_wave_max(error);
+				return compress_wave_max(error);
 			};
 
 			const auto increment = [](uint32_t rate, uint32_t by) -> uint32_t

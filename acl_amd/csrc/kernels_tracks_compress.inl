@@ -27,13 +27,26 @@
 
 	__device__ __forceinline__ float tracks_compress_length3(float4 v) { return sqrtf((v.x * v.x + v.y * v.y) + v.z * v.z); }
 
+	// the largest value of the wave, the same in every lane (a butterfly; no value is a NaN inside the definition, so the order of the
+	// steps does not show)
+	__device__ __forceinline__ float compress_wave_max(float value)
+	{
+		#pragma unroll
+		for (int offset = int(k_wave_size) / 2; offset != 0; offset >>= 1)
+		{
+			const float other = __shfl_xor(value, offset);
+			value = other > value ? other : value;
+		}
+		return __uint_as_float(__builtin_amdgcn_readfirstlane(__float_as_uint(value)));
+	}
+
 	// ---- per instance: the refusals, the finite test, the rigid shell, the looping vote -----------------------------------------------------
 	// One wave64 per instance. The shell (rigid_shell_utils.h:51-170) walks the tracks in DESCENDING order -- every parent index is smaller
-	// than its child's, or the instance is refused --, samples across the lanes: a track's stretch is a max over its samples (a butterfly;
-	// no value is a NaN inside the definition, so the order of the steps does not show), and what it hands to its parent waits in the
-	// workspace, { local shell distance, precision } per track: the wave's own stores, read back by the wave itself. Every lane ends a
-	// visit with the same numbers (readfirstlane), whatever the samples hold. The looping vote (optimize_looping.transform.h:178-243) takes
-	// lanes <-> tracks. Leaves status, the sample count behind the vote and the wrap bit in the instance's record: the layout reads them.
+	// than its child's, or the instance is refused --, samples across the lanes: a track's stretch is a max over its samples
+	// (compress_wave_max), and what it hands to its parent waits in the workspace, { local shell distance, precision } per track: the
+	// wave's own stores, read back by the wave itself. Every lane ends a visit with the same numbers, whatever the samples hold. The
+	// looping vote (optimize_looping.transform.h:178-243) takes lanes <-> tracks. Leaves status, the sample count behind the vote and
+	// the wrap bit in the instance's record: the layout reads them.
 	__global__ __launch_bounds__(k_compress_waves_per_block * k_wave_size) void tracks_compress_shell_kernel(transform_compress_launch launch)
 	{
 		const uint32_t lane = threadIdx.x & (k_wave_size - 1);
@@ -71,8 +84,7 @@
 		}
 
 		for (uint32_t track = lane; track < num_tracks; track += k_wave_size)
-			shells[track] = make_float2(launch.track_shell_distances != nullptr ? launch.track_shell_distances[track] : launch.shell_distance,
-				launch.track_precisions != nullptr ? launch.track_precisions[track] : launch.precision);
+			shells[track] = make_float2(compress_track_shell_distance(launch, track), compress_track_precision(launch, track));
 
 		const size_t pose_quads = size_t(num_tracks) * 3u;
 		bool finite = true;
@@ -95,19 +107,12 @@
 				stretch = length_y > stretch ? length_y : stretch;
 				stretch = length_z > stretch ? length_z : stretch;
 			}
-			#pragma unroll
-			for (int offset = int(k_wave_size) / 2; offset != 0; offset >>= 1)
-			{
-				const float other = __shfl_xor(stretch, offset);
-				stretch = other > stretch ? other : stretch;
-			}
-			stretch = __uint_as_float(__builtin_amdgcn_readfirstlane(__float_as_uint(stretch)));
+			stretch = compress_wave_max(stretch);
 
-			const float own_distance = launch.track_shell_distances != nullptr ? launch.track_shell_distances[track] : launch.shell_distance;
-			const float own_precision = launch.track_precisions != nullptr ? launch.track_precisions[track] : launch.precision;
+			const float own_distance = compress_track_shell_distance(launch, track), own_precision = compress_track_precision(launch, track);
 			// a transform whose distance a child has raised is not dominant: the error it may add itself comes on top
 			const float parent_shell_distance = distance != own_distance ? stretch + own_precision : stretch;
-			const uint32_t parent = launch.parent_indices != nullptr ? launch.parent_indices[track] : ACLHIP_NO_PARENT;
+			const uint32_t parent = compress_track_parent(launch, track);
 			if (parent < track && parent_shell_distance > shells[parent].x)
 				shells[parent] = make_float2(parent_shell_distance, shell.y);
 		}

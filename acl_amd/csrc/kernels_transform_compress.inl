@@ -59,6 +59,17 @@
 		return handle >= launch.num_arrays || raw.samples == nullptr || raw.num_tracks > launch.max_tracks || raw.num_tracks > launch.table_tracks;
 	}
 
+	// a track's settings: its table's entry, or the desc's value; its parent as given, and as an output index (the identity map here: a
+	// parent that is no track of the array is no parent)
+	__device__ __forceinline__ float compress_track_precision(const transform_compress_launch& launch, uint32_t track) { return launch.track_precisions != nullptr ? launch.track_precisions[track] : launch.precision; }
+	__device__ __forceinline__ float compress_track_shell_distance(const transform_compress_launch& launch, uint32_t track) { return launch.track_shell_distances != nullptr ? launch.track_shell_distances[track] : launch.shell_distance; }
+	__device__ __forceinline__ uint32_t compress_track_parent(const transform_compress_launch& launch, uint32_t track) { return launch.parent_indices != nullptr ? launch.parent_indices[track] : ACLHIP_NO_PARENT; }
+	__device__ __forceinline__ uint32_t compress_track_parent(const transform_compress_launch& launch, uint32_t track, uint32_t num_tracks)
+	{
+		const uint32_t parent = compress_track_parent(launch, track);
+		return parent < num_tracks ? parent : ACLHIP_NO_PARENT;
+	}
+
 	__device__ __forceinline__ bool transform_compress_finite(float x) { return (__float_as_uint(x) & 0x7F800000u) != 0x7F800000u; }
 
 	// 0 default, 1 constant, 2 animated
@@ -153,6 +164,87 @@
 		return word;
 	}
 
+	// What an instance that ends with a status leaves for the caller: the result word, no size, and the refusal counted. One lane's.
+	__device__ __forceinline__ void compress_write_refusal(const transform_compress_launch& launch, uint32_t instance, uint32_t status)
+	{
+		// NOT_FINITE wins over NOT_NORMALIZED: the reference tests what it would store
+		const uint32_t result = (status & k_compress_status_refused) != 0 ? ACLHIP_COMPRESS_REFUSED
+			: (status & k_compress_status_not_finite) != 0 ? ACLHIP_COMPRESS_NOT_FINITE : ACLHIP_COMPRESS_NOT_NORMALIZED;
+		launch.results[instance] = make_uint2(result, 0);
+		if (result == ACLHIP_COMPRESS_REFUSED)
+			atomicAdd(launch.rejected_count, 1ull);
+	}
+
+	// The header words every transform blob has alike: raw_buffer_header (the hash is compress_hash_kernel's), tracks_header up to the
+	// sample rate, and of transform_tracks_header the six counts and "no database". One lane's.
+	__device__ __forceinline__ void transform_compress_write_common_header(uint32_t* words, uint32_t size, uint32_t num_tracks, uint32_t num_samples, float sample_rate,
+		const uint32_t (&num_animated)[3], const uint32_t (&num_constant)[3])
+	{
+		words[0] = size;
+		words[1] = 0;
+		words[2] = k_tag_compressed_tracks;
+		words[3] = uint32_t(k_version_latest) | (uint32_t(k_algorithm_uniformly_sampled) << 16) | (uint32_t(k_track_type_qvvf) << 24);
+		words[4] = num_tracks;
+		words[5] = num_samples;
+		words[6] = __float_as_uint(sample_rate);
+		words[10] = num_animated[0];
+		words[11] = num_animated[1];
+		words[12] = num_animated[2];
+		words[13] = num_constant[0];
+		words[14] = num_constant[1];
+		words[15] = num_constant[2];
+		words[16] = k_invalid_offset;
+	}
+
+	// A constant drop-w rotation, the `rank`-th of `num_constant`, into the constant rotations at `section` (write_stream_data.h:213-267):
+	// groups of four as xxxx yyyy zzzz, a last group of n as n, n and n; normalized and of positive w
+	__device__ __forceinline__ void transform_compress_write_constant_rotation(uint32_t* section, const uint32_t* in, uint32_t rank, uint32_t num_constant)
+	{
+		const float4 rotation = tracks_compress_positive_w(tracks_compress_normalize(*reinterpret_cast<const f32x4*>(in)));
+		const uint32_t group = rank / 4u, entry = rank % 4u, group_size = num_constant - group * 4u < 4u ? num_constant - group * 4u : 4u;
+		uint32_t* out = section + group * 12u;
+		out[entry] = __float_as_uint(rotation.x);
+		out[group_size + entry] = __float_as_uint(rotation.y);
+		out[2u * group_size + entry] = __float_as_uint(rotation.z);
+	}
+
+	// The metadata of a blob with parents (write_track_metadata.h:106-194) at `metadata_at`: the parent indices as output indices, the
+	// descriptions, the optional_metadata_header. The whole wave's.
+	__device__ __forceinline__ void transform_compress_write_tail(const transform_compress_launch& launch, uint8_t* blob, uint64_t metadata_at, uint32_t num_tracks, uint32_t lane, bool with_descriptions)
+	{
+		uint32_t* tail = reinterpret_cast<uint32_t*>(blob + metadata_at);
+		for (uint32_t track = lane; track < num_tracks; track += k_wave_size)
+			tail[track] = compress_track_parent(launch, track, num_tracks);
+		uint32_t* descriptions = tail + num_tracks;
+		if (with_descriptions)
+		{
+			// precision, shell distance, the default rotation xyzw, translation xyz, scale xyz
+			const uint32_t* default_pose = reinterpret_cast<const uint32_t*>(launch.default_pose);
+			for (uint32_t word = lane; word < num_tracks * 12u; word += k_wave_size)
+			{
+				const uint32_t track = word / 12u, field = word - track * 12u;
+				uint32_t value;
+				if (field == 0)
+					value = __float_as_uint(compress_track_precision(launch, track));
+				else if (field == 1)
+					value = __float_as_uint(compress_track_shell_distance(launch, track));
+				else
+				{
+					const uint32_t at = field - 2u;			// 0 .. 9 -> QVV48 dwords 0 1 2 3 | 4 5 6 | 8 9 10; the identity: w and the scale are 1
+					value = default_pose != nullptr ? default_pose[size_t(track) * 12u + at + (at >= 7u ? 1u : 0u)] : (at == 3u || at >= 7u) ? 0x3F800000u : 0u;
+				}
+				descriptions[word] = value;
+			}
+			descriptions += size_t(num_tracks) * 12u;
+		}
+		if (lane < 5)
+		{
+			// optional_metadata_header: no list name, no track names, parent indices, track descriptions, no contributing error
+			const uint32_t offset = lane == 2 ? uint32_t(metadata_at) : lane == 3 && with_descriptions ? uint32_t(metadata_at) + 4u * num_tracks : k_invalid_offset;
+			descriptions[lane] = offset;
+		}
+	}
+
 	// ---- per instance: the statuses, where everything goes, and everything but the stream -------------------------------------------------------
 	// One wave64 per instance, lanes <-> tracks, 64 at a time. A first pass over the flag bytes gives the statuses, the three constant and
 	// the three animated counts and has_scale, and with them the size -- and the refusal against the stride, in front of any write to the
@@ -222,16 +314,11 @@
 
 		if (status != 0)
 		{
-			// NOT_FINITE wins over NOT_NORMALIZED: the reference tests what it would store
 			if (lane == 0)
 			{
 				record.status = status;
 				launch.instances[instance] = record;
-				const uint32_t result = (status & k_compress_status_refused) != 0 ? ACLHIP_COMPRESS_REFUSED
-					: (status & k_compress_status_not_finite) != 0 ? ACLHIP_COMPRESS_NOT_FINITE : ACLHIP_COMPRESS_NOT_NORMALIZED;
-				launch.results[instance] = make_uint2(result, 0);
-				if (result == ACLHIP_COMPRESS_REFUSED)
-					atomicAdd(launch.rejected_count, 1ull);
+				compress_write_refusal(launch, instance, status);
 			}
 			return;
 		}
@@ -255,25 +342,12 @@
 			launch.results[instance] = make_uint2(ACLHIP_COMPRESS_OK, uint32_t(size));
 
 			uint32_t* words = reinterpret_cast<uint32_t*>(blob);
-			words[0] = uint32_t(size);					// raw_buffer_header; the hash is compress_hash_kernel's
-			words[1] = 0;
-			words[2] = k_tag_compressed_tracks;			// tracks_header
-			words[3] = uint32_t(k_version_latest) | (uint32_t(k_algorithm_uniformly_sampled) << 16) | (uint32_t(k_track_type_qvvf) << 24);
-			words[4] = num_tracks;
-			words[5] = num_samples;
-			words[6] = __float_as_uint(raw.sample_rate);
+			transform_compress_write_common_header(words, uint32_t(size), num_tracks, num_samples, raw.sample_rate, num_animated, num_constant);
 			// has_scale | default scale 1 | the three full formats (0) | no database, no trivial defaults (quat_near_identity with a
 			// threshold of 0 holds for no rotation), no stripped key frames | wrap optimized | metadata
 			words[7] = (has_scale ? 1u : 0u) | 2u | (kDropW ? uint32_t(k_rotation_quatf_drop_w_full) << 4 : 0u) | (record.wrap != 0 ? 1u << 30 : 0u) | (with_parents ? 1u << 31 : 0u);
 			words[8] = 1;								// transform_tracks_header: one segment; offsets from its own start
 			words[9] = 0;								// no variable sub-tracks
-			words[10] = num_animated[0];
-			words[11] = num_animated[1];
-			words[12] = num_animated[2];
-			words[13] = num_constant[0];
-			words[14] = num_constant[1];
-			words[15] = num_constant[2];
-			words[16] = k_invalid_offset;				// no database
 			words[17] = uint32_t(sizeof(transform_tracks_header));
 			words[18] = k_transform_blob_headers - k_transform_header_offset;
 			words[19] = constants_at - k_transform_header_offset;
@@ -304,16 +378,7 @@
 					uint32_t* out = reinterpret_cast<uint32_t*>(blob + section_at[kind]) + (constants_before[kind] + transform_compress_rank(constant_mask)) * width;
 					const uint32_t* in = first_frame + size_t(track) * 12u + kind * 4u;
 					if (kDropW && kind == 0)
-					{
-						// write_stream_data.h:213-267: groups of four constant rotations as xxxx yyyy zzzz, a last group of n as n, n and n
-						const float4 rotation = tracks_compress_positive_w(tracks_compress_normalize(*reinterpret_cast<const f32x4*>(in)));
-						const uint32_t rank = constants_before[0] + transform_compress_rank(constant_mask);
-						const uint32_t group = rank / 4u, entry = rank % 4u, group_size = num_constant[0] - group * 4u < 4u ? num_constant[0] - group * 4u : 4u;
-						out = reinterpret_cast<uint32_t*>(blob + section_at[0]) + group * 12u;
-						out[entry] = __float_as_uint(rotation.x);
-						out[group_size + entry] = __float_as_uint(rotation.y);
-						out[2u * group_size + entry] = __float_as_uint(rotation.z);
-					}
+						transform_compress_write_constant_rotation(reinterpret_cast<uint32_t*>(blob + section_at[0]), in, constants_before[0] + transform_compress_rank(constant_mask), num_constant[0]);
 					else
 						for (uint32_t component = 0; component < width; ++component)
 							out[component] = in[component];
@@ -339,41 +404,7 @@
 				blob[metadata_at + 9u + lane] = 0;
 			return;
 		}
-
-		// parent indices as output indices (the identity map here: a parent that is no track of the array is no parent)
-		for (uint32_t track = lane; track < num_tracks; track += k_wave_size)
-		{
-			const uint32_t parent = launch.parent_indices != nullptr ? launch.parent_indices[track] : ACLHIP_NO_PARENT;
-			tail[track] = parent < num_tracks ? parent : ACLHIP_NO_PARENT;
-		}
-		uint32_t* descriptions = tail + num_tracks;
-		if (with_descriptions)
-		{
-			// precision, shell distance, the default rotation xyzw, translation xyz, scale xyz
-			const uint32_t* default_pose = reinterpret_cast<const uint32_t*>(launch.default_pose);
-			for (uint32_t word = lane; word < num_tracks * 12u; word += k_wave_size)
-			{
-				const uint32_t track = word / 12u, field = word - track * 12u;
-				uint32_t value;
-				if (field == 0)
-					value = __float_as_uint(launch.track_precisions != nullptr ? launch.track_precisions[track] : launch.precision);
-				else if (field == 1)
-					value = __float_as_uint(launch.track_shell_distances != nullptr ? launch.track_shell_distances[track] : launch.shell_distance);
-				else
-				{
-					const uint32_t at = field - 2u;			// 0 .. 9 -> QVV48 dwords 0 1 2 3 | 4 5 6 | 8 9 10; the identity: w and the scale are 1
-					value = default_pose != nullptr ? default_pose[size_t(track) * 12u + at + (at >= 7u ? 1u : 0u)] : (at == 3u || at >= 7u) ? 0x3F800000u : 0u;
-				}
-				descriptions[word] = value;
-			}
-			descriptions += size_t(num_tracks) * 12u;
-		}
-		if (lane < 5)
-		{
-			// optional_metadata_header: no list name, no track names, parent indices, track descriptions, no contributing error
-			const uint32_t offset = lane == 2 ? uint32_t(metadata_at) : lane == 3 && with_descriptions ? uint32_t(metadata_at) + 4u * num_tracks : k_invalid_offset;
-			descriptions[lane] = offset;
-		}
+		transform_compress_write_tail(launch, blob, metadata_at, num_tracks, lane, with_descriptions);
 	}
 
 	// ---- the animated stream ----------------------------------------------------------------------------------------------------------------

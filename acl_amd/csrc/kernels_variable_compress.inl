@@ -126,6 +126,27 @@
 		return make_float2(padded_min, padded_extent0 >= range_max ? padded_extent0 : padded_extent1);
 	}
 
+	// A segment's range of an animated sub-track: minimum and maximum of its clip-normalized samples [start, start + count), padded by
+	// variable_compress_fixup: { padded minimum, padded extent } of x, y and z
+	__device__ __forceinline__ void variable_segment_range(const f32x4* samples, size_t pose_quads, uint32_t track, uint32_t kind, const float* clip_range, uint32_t start, uint32_t count, float2 (&padded)[3])
+	{
+		float low[3] = { 1.0e10f, 1.0e10f, 1.0e10f }, high[3] = { -1.0e10f, -1.0e10f, -1.0e10f };
+		for (uint32_t sample = start; sample < start + count; ++sample)
+		{
+			const float3 v = variable_compress_normalize3(variable_compress_value(samples, pose_quads, sample, track, kind), clip_range);
+			const float normalized[3] = { v.x, v.y, v.z };
+			#pragma unroll
+			for (uint32_t c = 0; c < 3; ++c)
+			{
+				low[c] = low[c] < normalized[c] ? low[c] : normalized[c];
+				high[c] = high[c] > normalized[c] ? high[c] : normalized[c];
+			}
+		}
+		#pragma unroll
+		for (uint32_t c = 0; c < 3; ++c)
+			padded[c] = variable_compress_fixup(low[c], high[c]);
+	}
+
 	// the entry `entry` of an instance's animated sub-tracks in stream order: rotations, translations, scales, each in track order
 	struct variable_entry { uint32_t kind, rank, track; };
 	__device__ __forceinline__ variable_entry variable_compress_entry(const uint16_t* animated, uint32_t max_tracks, uint32_t num_rotations, uint32_t num_translations, uint32_t entry)
@@ -299,8 +320,8 @@
 	}
 
 	// ---- per instance: the segments, the prefix sums, the refusals, and everything but segment ranges and streams ------------------------------
-	// One wave64 per instance, as transform_compress_layout_kernel. In front of any write to the row: the counts and the lists of animated
-	// tracks (lanes <-> tracks), then per segment the bit widths of the animated sub-tracks in stream order (lanes <-> entries of the
+	// One wave64 per instance, as transform_compress_layout_kernel, whose refusal, common header words, constant rotations and metadata
+	// these are. In front of any write to the row: the counts and the lists of animated tracks (lanes <-> tracks), then per segment the bit widths of the animated sub-tracks in stream order (lanes <-> entries of the
 	// lists), their prefix sums and where the segment's three parts lie -- all into the workspace --, and with the last segment the size:
 	// the refusals. Then the row: headers, start indices, segment headers (compress.transform.impl.h:404-470, write_segment_data.h:67-122),
 	// types, constants (write_stream_data.h:199-310), clip range data (write_range_data.h:60-207), per segment the format bytes
@@ -421,10 +442,7 @@
 			{
 				record.status = status;
 				base.instances[instance] = record;
-				const uint32_t result = (status & k_compress_status_refused) != 0 ? ACLHIP_COMPRESS_REFUSED : ACLHIP_COMPRESS_NOT_FINITE;
-				base.results[instance] = make_uint2(result, 0);
-				if (result == ACLHIP_COMPRESS_REFUSED)
-					atomicAdd(base.rejected_count, 1ull);
+				compress_write_refusal(base, instance, status);
 			}
 			return;
 		}
@@ -448,26 +466,13 @@
 			base.instances[instance] = record;
 			base.results[instance] = make_uint2(ACLHIP_COMPRESS_OK, uint32_t(size));
 
-			words[0] = uint32_t(size);					// raw_buffer_header; the hash is compress_hash_kernel's
-			words[1] = 0;
-			words[2] = k_tag_compressed_tracks;			// tracks_header
-			words[3] = uint32_t(k_version_latest) | (uint32_t(k_algorithm_uniformly_sampled) << 16) | (uint32_t(k_track_type_qvvf) << 24);
-			words[4] = num_tracks;
-			words[5] = num_samples;
-			words[6] = __float_as_uint(raw.sample_rate);
+			transform_compress_write_common_header(words, uint32_t(size), num_tracks, num_samples, raw.sample_rate, num_animated, num_constant);
 			// has_scale | default scale 1 | vector3f_variable twice | quatf_drop_w_variable | no database, no trivial defaults, no stripped
 			// key frames | wrap optimized | metadata
 			words[7] = (has_scale ? 1u : 0u) | 2u | (uint32_t(k_vector_vector3f_variable) << 2) | (uint32_t(k_vector_vector3f_variable) << 3)
 				| (uint32_t(k_rotation_quatf_drop_w_variable) << 4) | (voted.wrap != 0 ? 1u << 30 : 0u) | (with_parents ? 1u << 31 : 0u);
 			words[8] = num_segments;					// transform_tracks_header; offsets from its own start
 			words[9] = num_variable;
-			words[10] = num_animated[0];
-			words[11] = num_animated[1];
-			words[12] = num_animated[2];
-			words[13] = num_constant[0];
-			words[14] = num_constant[1];
-			words[15] = num_constant[2];
-			words[16] = k_invalid_offset;				// no database
 			words[17] = uint32_t(segment_headers_at) - k_transform_header_offset;
 			words[18] = uint32_t(types_at) - k_transform_header_offset;
 			words[19] = uint32_t(constants_at) - k_transform_header_offset;
@@ -534,15 +539,7 @@
 					const uint32_t rank = constants_before[kind] + transform_compress_rank(constant_mask);
 					const uint32_t* in = first_frame + size_t(track) * 12u + kind * 4u;
 					if (kind == 0)
-					{
-						// write_stream_data.h:213-267: groups of four constant rotations as xxxx yyyy zzzz, a last group of n as n, n and n
-						const float4 rotation = tracks_compress_positive_w(tracks_compress_normalize(*reinterpret_cast<const f32x4*>(in)));
-						const uint32_t group = rank / 4u, entry = rank % 4u, group_size = num_constant[0] - group * 4u < 4u ? num_constant[0] - group * 4u : 4u;
-						uint32_t* out = reinterpret_cast<uint32_t*>(blob + section_at[0]) + group * 12u;
-						out[entry] = __float_as_uint(rotation.x);
-						out[group_size + entry] = __float_as_uint(rotation.y);
-						out[2u * group_size + entry] = __float_as_uint(rotation.z);
-					}
+						transform_compress_write_constant_rotation(reinterpret_cast<uint32_t*>(blob + section_at[0]), in, rank, num_constant[0]);
 					else
 					{
 						uint32_t* out = reinterpret_cast<uint32_t*>(blob + section_at[kind]) + rank * 3u;
@@ -588,39 +585,7 @@
 		if (lane < metadata_at - cursor)
 			blob[cursor + lane] = 0;
 
-		// parent indices as output indices, the descriptions, the optional_metadata_header: as transform_compress_layout_kernel
-		uint32_t* tail = reinterpret_cast<uint32_t*>(blob + metadata_at);
-		for (uint32_t track = lane; track < num_tracks; track += k_wave_size)
-		{
-			const uint32_t parent = base.parent_indices != nullptr ? base.parent_indices[track] : ACLHIP_NO_PARENT;
-			tail[track] = parent < num_tracks ? parent : ACLHIP_NO_PARENT;
-		}
-		uint32_t* descriptions = tail + num_tracks;
-		if (with_descriptions)
-		{
-			const uint32_t* default_pose = reinterpret_cast<const uint32_t*>(base.default_pose);
-			for (uint32_t word = lane; word < num_tracks * 12u; word += k_wave_size)
-			{
-				const uint32_t track = word / 12u, field = word - track * 12u;
-				uint32_t value;
-				if (field == 0)
-					value = __float_as_uint(base.track_precisions != nullptr ? base.track_precisions[track] : base.precision);
-				else if (field == 1)
-					value = __float_as_uint(base.track_shell_distances != nullptr ? base.track_shell_distances[track] : base.shell_distance);
-				else
-				{
-					const uint32_t at = field - 2u;			// 0 .. 9 -> QVV48 dwords 0 1 2 3 | 4 5 6 | 8 9 10; the identity: w and the scale are 1
-					value = default_pose != nullptr ? default_pose[size_t(track) * 12u + at + (at >= 7u ? 1u : 0u)] : (at == 3u || at >= 7u) ? 0x3F800000u : 0u;
-				}
-				descriptions[word] = value;
-			}
-			descriptions += size_t(num_tracks) * 12u;
-		}
-		if (lane < 5)
-		{
-			const uint32_t offset = lane == 2 ? uint32_t(metadata_at) : lane == 3 && with_descriptions ? uint32_t(metadata_at) + 4u * num_tracks : k_invalid_offset;
-			descriptions[lane] = offset;
-		}
+		transform_compress_write_tail(base, blob, metadata_at, num_tracks, lane, with_descriptions);
 	}
 
 	// ---- per (instance, segment): the segment ranges ---------------------------------------------------------------------------------------------
@@ -668,24 +633,13 @@
 					out[5u * step] = uint8_t(z >> (8u - high_first));
 					continue;
 				}
-				float low[3] = { 1.0e10f, 1.0e10f, 1.0e10f }, high[3] = { -1.0e10f, -1.0e10f, -1.0e10f };
-				for (uint32_t sample = at.start; sample < at.start + at.count; ++sample)
-				{
-					const float3 v = variable_compress_normalize3(variable_compress_value(samples, pose_quads, sample, entry.track, entry.kind), clip_range);
-					const float normalized[3] = { v.x, v.y, v.z };
-					#pragma unroll
-					for (uint32_t c = 0; c < 3; ++c)
-					{
-						low[c] = low[c] < normalized[c] ? low[c] : normalized[c];
-						high[c] = high[c] > normalized[c] ? high[c] : normalized[c];
-					}
-				}
+				float2 padded[3];
+				variable_segment_range(samples, pose_quads, entry.track, entry.kind, clip_range, at.start, at.count, padded);
 				#pragma unroll
 				for (uint32_t c = 0; c < 3; ++c)
 				{
-					const float2 padded = variable_compress_fixup(low[c], high[c]);
-					out[c * step] = uint8_t(variable_compress_pack(padded.x, 8));
-					out[(3u + c) * step] = uint8_t(variable_compress_pack(padded.y, 8));
+					out[c * step] = uint8_t(variable_compress_pack(padded[c].x, 8));
+					out[(3u + c) * step] = uint8_t(variable_compress_pack(padded[c].y, 8));
 				}
 			}
 		}
