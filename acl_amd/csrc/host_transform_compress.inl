@@ -1,7 +1,8 @@
 // host_transform_compress.inl -- part of aclhip.hip (one translation unit; included there behind host_scalar_compress.inl, not compiled on its own).
 // Host side of the three transform compressors, aclhip_compress_raw_tracks_batch (kernels_transform_compress.inl),
 // aclhip_compress_tracks_batch (kernels_tracks_compress.inl) and aclhip_compress_tracks_variable_batch (kernels_variable_compress.inl),
-// and of the bit rate search, aclhip_find_bit_rates_batch (kernels_bit_rate_search.inl):
+// and of the bit rate search, aclhip_find_bit_rates_batch (kernels_bit_rate_search.inl), and of the last three with the error metric as
+// an argument (the _metric entry points: the metric is one more thing a call says of itself, and picks the instantiations of its phases):
 // the sizes a caller needs, and one argument check, one workspace layout and one launch record for all -- the raw call is the drop-w
 // call with the full formats, no shell and its own words; the variable call is it with its own kernels behind the shell, its rate
 // table and three more parts of the workspace; the search is the variable call without rows, its table written, and four more parts.
@@ -31,9 +32,14 @@ namespace
 
 	// What an entry point says of itself: the word its desc goes by in the messages, the knob of its phases, whether its workspace holds shells and the
 	// segments it holds the variable call's parts for (0: none), whether it writes blob rows and whether its workspace holds the
-	// search's parts. The rest of what tells the raw and the drop-w call apart is in the desc: the formats and the shell metadata, 0
+	// search's parts; and the error metric its decisions are taken by (an aclhip_error_metric: the entry points without one say
+	// ACLHIP_METRIC_QVVF). The rest of what tells the raw and the drop-w call apart is in the desc: the formats and the shell metadata, 0
 	// for the raw call.
-	struct transform_compress_kind { const char* name; const char* phases_knob; bool with_shells; uint32_t max_segments = 0; bool with_rows = true; bool with_search = false; };
+	struct transform_compress_kind
+	{
+		const char* name; const char* phases_knob; bool with_shells; uint32_t max_segments = 0; bool with_rows = true; bool with_search = false; uint32_t metric = ACLHIP_METRIC_QVVF;
+		transform_compress_kind with_metric(uint32_t error_metric) const { transform_compress_kind kind = *this; kind.metric = error_metric; return kind; }
+	};
 
 	// the segments of the longest array a caller announces (a desc of 0 max_samples is refused: it counts as 1 here)
 	uint32_t variable_max_segments_of(uint32_t max_samples) { return variable_split_of(std::max(max_samples, 1u)).num_segments; }
@@ -132,12 +138,27 @@ extern "C" uint64_t aclhip_find_bit_rates_workspace_bytes(uint32_t num_instances
 
 namespace
 {
-	// The kernels between the shell and the hash, per rotation format: quatf_full (the raw call's), quatf_drop_w_full
+	// The kernels between the shell and the hash, per rotation format: quatf_full (the raw call's: no metric enters it), quatf_drop_w_full
+	// per error metric
 	struct transform_compress_kernels { void (*analyze)(transform_compress_launch), (*layout)(transform_compress_launch), (*stream)(transform_compress_launch); };
-	const transform_compress_kernels k_transform_compress_kernels[2] =
+	const transform_compress_kernels k_transform_compress_kernels[3] =
 	{
 		{ transform_compress_analyze_kernel, transform_compress_layout_kernel<false>, transform_compress_stream_kernel<false> },
-		{ tracks_compress_analyze_kernel, transform_compress_layout_kernel<true>, transform_compress_stream_kernel<true> },
+		{ tracks_compress_analyze_kernel<k_metric_qvvf>, transform_compress_layout_kernel<true>, transform_compress_stream_kernel<true> },
+		{ tracks_compress_analyze_kernel<k_metric_matrix>, transform_compress_layout_kernel<true>, transform_compress_stream_kernel<true> },
+	};
+
+	// The kernels that decide by the error metric, per metric: the shell (its vote) and the variable call's analysis, which the drop-w
+	// call, the variable call and the search share, and the search's two phases
+	struct metric_kernels
+	{
+		void (*shell)(transform_compress_launch); void (*variable_analyze)(variable_compress_launch);
+		void (*search_local)(bit_rate_search_launch); void (*search_object)(bit_rate_search_launch);
+	};
+	const metric_kernels k_metric_kernels[2] =
+	{
+		{ tracks_compress_shell_kernel<k_metric_qvvf>, variable_compress_analyze_kernel<k_metric_qvvf>, bit_rate_search_local_kernel<k_metric_qvvf>, bit_rate_search_object_kernel<k_metric_qvvf> },
+		{ tracks_compress_shell_kernel<k_metric_matrix>, variable_compress_analyze_kernel<k_metric_matrix>, bit_rate_search_local_kernel<k_metric_matrix>, bit_rate_search_object_kernel<k_metric_matrix> },
 	};
 
 	// A smaller desc as the drop-w call's, which the shared check and the launch record read: the rotation format the call stands for
@@ -226,6 +247,8 @@ namespace
 			blobs = nullptr;
 			blob_stride_bytes = 0;
 		}
+		if (kind.metric > ACLHIP_METRIC_QVVF_MATRIX3X4F)
+			return fail(context, ACLHIP_ERROR_INVALID_ARGUMENT, "unknown error metric %u", kind.metric);
 		if (const aclhip_status status = check_compress_buffers(context, kind.name, "raw track", raws, desc, blobs, blob_stride_bytes, results, kind.with_rows); status != ACLHIP_OK)
 			return status;
 		if ((reinterpret_cast<uintptr_t>(desc->default_pose) & 15u) != 0)
@@ -331,11 +354,11 @@ namespace
 
 			// (the phases knob counts the call's own launches: four for quatf_full, five for quatf_drop_w_full)
 			const bool drop_w = desc->rotation_format == k_rotation_quatf_drop_w_full;
-			const transform_compress_kernels& kernels = k_transform_compress_kernels[drop_w ? 1 : 0];
+			const transform_compress_kernels& kernels = k_transform_compress_kernels[drop_w ? 1u + kind.metric : 0u];
 			const dim3 block(shape.block_size);
 			const compress_phase phases[] =
 			{
-				{ tracks_compress_shell_kernel, dim3(shape.instance_blocks), block, launch },
+				{ k_metric_kernels[kind.metric].shell, dim3(shape.instance_blocks), block, launch },
 				{ kernels.analyze, shape.track_blocks, block, launch },
 				{ kernels.layout, dim3(shape.instance_blocks), block, launch },
 				{ kernels.stream, dim3(shape.stream_blocks), block, launch },
@@ -354,19 +377,27 @@ extern "C" aclhip_status aclhip_compress_raw_tracks_batch(aclhip_context* contex
 	return compress_transform_tracks(context, k_transform_compress_kind, raws, num_instances, desc != nullptr ? &as_tracks : nullptr, blobs, blob_stride_bytes, results, stream_handle);
 }
 
+// The three calls that decide by an error metric, with the metric as an argument; the entry points without one are these with
+// ACLHIP_METRIC_QVVF.
+extern "C" aclhip_status aclhip_compress_tracks_metric_batch(aclhip_context* context, const aclhip_raw_tracks* raws, uint32_t num_instances,
+	const aclhip_compress_tracks_desc* desc, void* blobs, uint64_t blob_stride_bytes, aclhip_compress_result* results, uint32_t metric, void* stream_handle)
+{
+	return compress_transform_tracks(context, k_tracks_compress_kind.with_metric(metric), raws, num_instances, desc, blobs, blob_stride_bytes, results, stream_handle);
+}
+
 extern "C" aclhip_status aclhip_compress_tracks_batch(aclhip_context* context, const aclhip_raw_tracks* raws, uint32_t num_instances,
 	const aclhip_compress_tracks_desc* desc, void* blobs, uint64_t blob_stride_bytes, aclhip_compress_result* results, void* stream_handle)
 {
-	return compress_transform_tracks(context, k_tracks_compress_kind, raws, num_instances, desc, blobs, blob_stride_bytes, results, stream_handle);
+	return aclhip_compress_tracks_metric_batch(context, raws, num_instances, desc, blobs, blob_stride_bytes, results, ACLHIP_METRIC_QVVF, stream_handle);
 }
 
 // The variable call: the shared check over its desc as the drop-w one, its own checks behind it, and its six launches.
-extern "C" aclhip_status aclhip_compress_tracks_variable_batch(aclhip_context* context, const aclhip_raw_tracks* raws, uint32_t num_instances,
-	const aclhip_compress_variable_desc* desc_or_null, void* blobs, uint64_t blob_stride_bytes, aclhip_compress_result* results, void* stream_handle)
+extern "C" aclhip_status aclhip_compress_tracks_variable_metric_batch(aclhip_context* context, const aclhip_raw_tracks* raws, uint32_t num_instances,
+	const aclhip_compress_variable_desc* desc_or_null, void* blobs, uint64_t blob_stride_bytes, aclhip_compress_result* results, uint32_t metric, void* stream_handle)
 {
 	const aclhip_compress_variable_desc& desc = desc_or_null != nullptr ? *desc_or_null : aclhip_compress_variable_desc{};
 	const aclhip_compress_tracks_desc as_tracks = compress_tracks_desc_of(desc, k_rotation_quatf_drop_w_full, desc.reserved_rate | desc.reserved_word);
-	const transform_compress_kind kind = variable_compress_kind_of(desc.max_samples);
+	const transform_compress_kind kind = variable_compress_kind_of(desc.max_samples).with_metric(metric);
 	if (const aclhip_status status = check_transform_compress(context, kind, raws, num_instances, desc_or_null != nullptr ? &as_tracks : nullptr, blobs, blob_stride_bytes, results); status != ACLHIP_OK)
 		return status;
 	if (desc.max_samples == 0)
@@ -396,8 +427,8 @@ extern "C" aclhip_status aclhip_compress_tracks_variable_batch(aclhip_context* c
 		const dim3 block(shape.block_size);
 		const compress_phase phases[] =
 		{
-			{ tracks_compress_shell_kernel, dim3(shape.instance_blocks), block, launch.base },
-			{ variable_compress_analyze_kernel, shape.track_blocks, block, launch },
+			{ k_metric_kernels[kind.metric].shell, dim3(shape.instance_blocks), block, launch.base },
+			{ k_metric_kernels[kind.metric].variable_analyze, shape.track_blocks, block, launch },
 			{ variable_compress_layout_kernel, dim3(shape.instance_blocks), block, launch },
 			{ variable_compress_ranges_kernel, dim3(compress_segment_blocks_of(num_instances, kind.max_segments)), block, launch },
 			{ variable_compress_stream_kernel, dim3(shape.stream_blocks), block, launch },
@@ -407,13 +438,20 @@ extern "C" aclhip_status aclhip_compress_tracks_variable_batch(aclhip_context* c
 	});
 }
 
+extern "C" aclhip_status aclhip_compress_tracks_variable_batch(aclhip_context* context, const aclhip_raw_tracks* raws, uint32_t num_instances,
+	const aclhip_compress_variable_desc* desc, void* blobs, uint64_t blob_stride_bytes, aclhip_compress_result* results, void* stream_handle)
+{
+	return aclhip_compress_tracks_variable_metric_batch(context, raws, num_instances, desc, blobs, blob_stride_bytes, results, ACLHIP_METRIC_QVVF, stream_handle);
+}
+
 // The search: the shared check over its desc as the drop-w one, like the variable call; no rows; the table on the written side.
-extern "C" aclhip_status aclhip_find_bit_rates_batch(aclhip_context* context, const aclhip_raw_tracks* raws, uint32_t num_instances,
-	const aclhip_find_bit_rates_desc* desc_or_null, uint8_t* bit_rates, uint64_t instance_stride, uint64_t segment_stride, aclhip_compress_result* results, void* stream_handle)
+extern "C" aclhip_status aclhip_find_bit_rates_metric_batch(aclhip_context* context, const aclhip_raw_tracks* raws, uint32_t num_instances,
+	const aclhip_find_bit_rates_desc* desc_or_null, uint8_t* bit_rates, uint64_t instance_stride, uint64_t segment_stride, aclhip_compress_result* results, uint32_t metric,
+	void* stream_handle)
 {
 	const aclhip_find_bit_rates_desc& desc = desc_or_null != nullptr ? *desc_or_null : aclhip_find_bit_rates_desc{};
 	const aclhip_compress_tracks_desc as_tracks = compress_tracks_desc_of(desc, k_rotation_quatf_drop_w_full, desc.reserved_word);
-	const transform_compress_kind kind = bit_rate_search_kind_of(desc.max_samples);
+	const transform_compress_kind kind = bit_rate_search_kind_of(desc.max_samples).with_metric(metric);
 	const uint32_t max_segments = kind.max_segments;
 	if (const aclhip_status status = check_transform_compress(context, kind, raws, num_instances, desc_or_null != nullptr ? &as_tracks : nullptr, nullptr, 0, results); status != ACLHIP_OK)
 		return status;
@@ -463,12 +501,18 @@ extern "C" aclhip_status aclhip_find_bit_rates_batch(aclhip_context* context, co
 		const dim3 block(shape.block_size);
 		const compress_phase phases[] =
 		{
-			{ tracks_compress_shell_kernel, dim3(shape.instance_blocks), block, launch.variable.base },
-			{ variable_compress_analyze_kernel, shape.track_blocks, block, launch.variable },
+			{ k_metric_kernels[kind.metric].shell, dim3(shape.instance_blocks), block, launch.variable.base },
+			{ k_metric_kernels[kind.metric].variable_analyze, shape.track_blocks, block, launch.variable },
 			{ bit_rate_search_segment_kernel, dim3(segment_blocks), block, launch },
-			{ bit_rate_search_local_kernel, dim3(track_blocks), dim3(k_wave_size), launch },
-			{ bit_rate_search_object_kernel, dim3(segment_blocks), block, launch },
+			{ k_metric_kernels[kind.metric].search_local, dim3(track_blocks), dim3(k_wave_size), launch },
+			{ k_metric_kernels[kind.metric].search_object, dim3(segment_blocks), block, launch },
 		};
 		return launch_compress_phases(context, stream, shape.phases, phases, 5);
 	});
+}
+
+extern "C" aclhip_status aclhip_find_bit_rates_batch(aclhip_context* context, const aclhip_raw_tracks* raws, uint32_t num_instances,
+	const aclhip_find_bit_rates_desc* desc, uint8_t* bit_rates, uint64_t instance_stride, uint64_t segment_stride, aclhip_compress_result* results, void* stream_handle)
+{
+	return aclhip_find_bit_rates_metric_batch(context, raws, num_instances, desc, bit_rates, instance_stride, segment_stride, results, ACLHIP_METRIC_QVVF, stream_handle);
 }

@@ -1,7 +1,9 @@
 // kernels_bit_rate_search.inl -- part of aclhip.hip (one translation unit; included there behind kernels_variable_compress.inl, not compiled on its own).
 // aclhip_find_bit_rates_batch: the reference's find_optimal_bit_rates (compression/impl/quantize.transform.h:1174-1523) at the levels
-// lowest, low and medium for quatf_drop_w_variable / vector3f_variable / vector3f_variable and the qvvf error metric: the rate table
-// aclhip_compress_tracks_variable_batch reads. Five stream ordered launches:
+// lowest, low and medium for quatf_drop_w_variable / vector3f_variable / vector3f_variable: the rate table
+// aclhip_compress_tracks_variable_batch reads. The error metric (aclhip_find_bit_rates_metric_batch) is a template argument of the local
+// and of the object kernel, as of the two launches in front of them: the qvvf instantiations are the kernels without it, the matrix
+// ones take S2 with scale through matrix_from_qvv, matrix_mul and matrix_shell_error (kernels_pose_buffers.inl). Five stream ordered launches:
 //   tracks_compress_shell_kernel         (kernels_tracks_compress.inl, unchanged) the refusals, the finite test, the clip's rigid shell, the vote
 //   variable_compress_analyze_kernel     (kernels_variable_compress.inl, unchanged) the sub-track types and the clip ranges
 //   bit_rate_search_segment_kernel       per (instance, segment): the segment ranges as six floats per animated sub-track (lanes <->
@@ -186,11 +188,13 @@
 		return lossy;
 	}
 
-	// S2: calculate_error, or calculate_error_no_scale: the x and the y point only, no scale (transform_error_metrics.h:335-378)
+	// S2: calculate_error of the metric, or calculate_error_no_scale: the x and the y point only, no scale (transform_error_metrics.h:335-378;
+	// the matrix metric inherits it: without scale both metrics are one)
+	template<uint32_t kMetric>
 	__device__ __forceinline__ float search_error(bool has_scale, float distance, const qvv& raw, const qvv& lossy)
 	{
 		if (has_scale)
-			return shell_error(distance, raw, lossy);
+			return compress_shell_error<kMetric>(distance, raw, lossy);
 		qvv raw_rigid = raw, lossy_rigid = lossy;
 		raw_rigid.scale = lossy_rigid.scale = make_float4(1.0f, 1.0f, 1.0f, 0.0f);
 		const float error_x = shell_point_error(distance, 0.0f, 0.0f, raw_rigid, lossy_rigid);
@@ -339,6 +343,7 @@
 	// size class at a time -- a round takes the lanes that share the size of the first entry not yet tried --: a lane scans the samples
 	// until its error is >= the threshold and keeps the maximum so far; the wave keeps the smallest error and, of equals, the first
 	// entry: what the reference's sequence of strict `<` updates keeps. A class that ends good enough ends the list.
+	template<uint32_t kMetric>
 	__global__ __launch_bounds__(k_wave_size) void bit_rate_search_local_kernel(bit_rate_search_launch launch)
 	{
 		__shared__ float4 rotation_table[k_search_num_rates * k_variable_max_samples];
@@ -469,7 +474,7 @@
 						lossy.rotation = (flags & 3u) == k_sub_track_animated ? rotation_table[r] : fixed_rotation;
 						lossy.translation = ((flags >> 2) & 3u) == k_sub_track_animated ? make_float4(vector_table[0][t * 3u], vector_table[0][t * 3u + 1u], vector_table[0][t * 3u + 2u], 0.0f) : fixed_translation;
 						lossy.scale = ((flags >> 4) & 3u) == k_sub_track_animated ? make_float4(vector_table[1][s * 3u], vector_table[1][s * 3u + 1u], vector_table[1][s * 3u + 2u], 0.0f) : fixed_scale;
-						const float sample_error = search_error(has_scale, shell.x, raw_local, lossy);
+						const float sample_error = search_error<kMetric>(has_scale, shell.x, raw_local, lossy);
 						error = sample_error > error ? sample_error : error;
 						if (sample_error >= shell.y)
 							break;
@@ -512,7 +517,9 @@
 	// (31 at most). An object
 	// error walks the chain of its target from the root per lane, the raw transforms beside the lossy ones, and ends in a ballot (the
 	// first sample whose error is too high) and a butterfly: every decision is wave uniform. A candidate is the table with ONE track's
-	// rates replaced: nothing is copied. The first version recomputes the whole chain for every candidate.
+	// rates replaced: nothing is copied. The first version recomputes the whole chain for every candidate. Under the matrix metric
+	// (kMetric) a segment with scale takes both chains down as 3x4 matrices, 24 floats a lane; without scale it is the qvvf walk.
+	template<uint32_t kMetric>
 	__global__ __launch_bounds__(k_compress_waves_per_block * k_wave_size) void bit_rate_search_object_kernel(bit_rate_search_launch launch)
 	{
 		const transform_compress_launch& base = launch.variable.base;
@@ -550,20 +557,47 @@
 			const auto parent_of = [&](uint32_t track) -> uint32_t { return compress_track_parent(base, track, num_tracks); };
 
 			// S2: the object error of chain[links - 1] with the rates of `replaced` taken from `replacement`
-			const auto object_error = [&](uint32_t links, uint32_t replaced, uint32_t replacement, bool until_end) -> float
+			const auto object_error = [&](uint32_t links, uint32_t replaced, uint32_t replacement, bool until_end) __attribute__((always_inline)) -> float
 			{
-				qvv raw_object, lossy_object;
-				for (uint32_t link = 0; link < links; ++link)
+				float2 shell;
+				float error = 0.0f;
+				bool measured = false;
+				if constexpr (kMetric == k_metric_matrix)
 				{
-					const uint32_t track = chain[link];
-					const uint32_t rates = track == replaced ? replacement : row[track];
-					const qvv lossy_local = search_lossy_local(source, track, track_flags[track], rates, sample);
-					const qvv raw_local = search_raw_local(source, track, at.start + sample);
-					raw_object = link == 0 ? raw_local : search_to_object(has_scale, raw_local, raw_object);
-					lossy_object = link == 0 ? lossy_local : search_to_object(has_scale, lossy_local, lossy_object);
+					// the matrix metric with scale: O_0 = M(L_0), O_k = matrix_mul(M(L_k), O_k-1), nothing normalized (transform_error_metrics.h:415-436);
+					// two matrices, 24 floats, go down the chain where the qvvf metric takes two QVVs
+					if (has_scale)
+					{
+						matrix3x4 raw_object, lossy_object;
+						for (uint32_t link = 0; link < links; ++link)
+						{
+							const uint32_t track = chain[link];
+							const uint32_t rates = track == replaced ? replacement : row[track];
+							const matrix3x4 lossy_local = matrix_from_qvv(search_lossy_local(source, track, track_flags[track], rates, sample));
+							const matrix3x4 raw_local = matrix_from_qvv(search_raw_local(source, track, at.start + sample));
+							raw_object = link == 0 ? raw_local : matrix_mul(raw_local, raw_object);
+							lossy_object = link == 0 ? lossy_local : matrix_mul(lossy_local, lossy_object);
+						}
+						shell = shells[chain[links - 1u]];
+						error = lane < at.count ? matrix_shell_error(shell.x, raw_object, lossy_object) : 0.0f;
+						measured = true;
+					}
 				}
-				const float2 shell = shells[chain[links - 1u]];
-				float error = lane < at.count ? search_error(has_scale, shell.x, raw_object, lossy_object) : 0.0f;
+				if (!measured)
+				{
+					qvv raw_object, lossy_object;
+					for (uint32_t link = 0; link < links; ++link)
+					{
+						const uint32_t track = chain[link];
+						const uint32_t rates = track == replaced ? replacement : row[track];
+						const qvv lossy_local = search_lossy_local(source, track, track_flags[track], rates, sample);
+						const qvv raw_local = search_raw_local(source, track, at.start + sample);
+						raw_object = link == 0 ? raw_local : search_to_object(has_scale, raw_local, raw_object);
+						lossy_object = link == 0 ? lossy_local : search_to_object(has_scale, lossy_local, lossy_object);
+					}
+					shell = shells[chain[links - 1u]];
+					error = lane < at.count ? search_error<kMetric>(has_scale, shell.x, raw_object, lossy_object) : 0.0f;
+				}
 				if (!until_end)
 				{
 					const uint64_t high = __ballot(lane < at.count && error >= shell.y);

@@ -9,7 +9,8 @@
 //   transform_compress_layout_kernel<true>, transform_compress_stream_kernel<true>   (kernels_transform_compress.inl) with three words per rotation
 //   compress_hash_kernel               (kernels_scalar_compress.inl)
 // include/aclhip.h states the definition: fp32, one IEEE operation at a time; shell_error and qvv_mul_point3 are the pose error kernel's
-// (kernels_pose_buffers.inl).
+// (kernels_pose_buffers.inl). The shell kernel and the analysis take the error metric of their decisions as a template argument
+// (aclhip_compress_tracks_metric_batch): compress_shell_error, below.
 
 	constexpr uint32_t k_compress_optimize_loops = 1;				// ACLHIP_COMPRESS_OPTIMIZE_LOOPS
 
@@ -40,6 +41,19 @@
 		return __uint_as_float(__builtin_amdgcn_readfirstlane(__float_as_uint(value)));
 	}
 
+	// The error a compressor's decisions are taken by, per aclhip_error_metric (a template argument of the kernels that decide: the qvvf
+	// instantiations are the kernels without it): qvvf_transform_error_metric's shell_error, or qvvf_matrix3x4f_transform_error_metric's
+	// -- both transforms through matrix_from_qvv, then matrix_shell_error (kernels_pose_buffers.inl; transform_error_metrics.h:389-461).
+	constexpr uint32_t k_metric_qvvf = 0, k_metric_matrix = 1;		// ACLHIP_METRIC_QVVF, ACLHIP_METRIC_QVVF_MATRIX3X4F
+	template<uint32_t kMetric>
+	__device__ __forceinline__ float compress_shell_error(float distance, const qvv& raw, const qvv& lossy)
+	{
+		if constexpr (kMetric == k_metric_matrix)
+			return matrix_shell_error(distance, matrix_from_qvv(raw), matrix_from_qvv(lossy));
+		else
+			return shell_error(distance, raw, lossy);
+	}
+
 	// ---- per instance: the refusals, the finite test, the rigid shell, the looping vote -----------------------------------------------------
 	// One wave64 per instance. The shell (rigid_shell_utils.h:51-170) walks the tracks in DESCENDING order -- every parent index is smaller
 	// than its child's, or the instance is refused --, samples across the lanes: a track's stretch is a max over its samples
@@ -47,6 +61,7 @@
 	// wave's own stores, read back by the wave itself. Every lane ends a visit with the same numbers, whatever the samples hold. The
 	// looping vote (optimize_looping.transform.h:178-243) takes lanes <-> tracks. Leaves status, the sample count behind the vote and
 	// the wrap bit in the instance's record: the layout reads them.
+	template<uint32_t kMetric>
 	__global__ __launch_bounds__(k_compress_waves_per_block * k_wave_size) void tracks_compress_shell_kernel(transform_compress_launch launch)
 	{
 		const uint32_t lane = threadIdx.x & (k_wave_size - 1);
@@ -127,7 +142,7 @@
 			{
 				const float2 shell = shells[track];
 				const qvv first = tracks_compress_sample(raw.samples, pose_quads, 0, track), last = tracks_compress_sample(raw.samples, pose_quads, num_samples - 1u, track);
-				apart = apart || shell_error(shell.x, first, last) > shell.y;
+				apart = apart || compress_shell_error<kMetric>(shell.x, first, last) > shell.y;
 			}
 			if (__ballot(apart) == 0)
 			{
@@ -157,6 +172,7 @@
 	// transform_compress_analyze_kernel's shape: one wave64 per track, samples across the lanes, over the samples the vote left. The three
 	// rotation ballots are two shell error ballots (compact.transform.h:72-254): a sample against sample 0's rotation and against the
 	// default rotation, each under the sample's own translation and scale, at the track's shell. Translations and scales as there.
+	template<uint32_t kMetric>
 	__global__ __launch_bounds__(k_compress_waves_per_block * k_wave_size) void tracks_compress_analyze_kernel(transform_compress_launch launch)
 	{
 		const uint32_t lane = threadIdx.x & (k_wave_size - 1);
@@ -187,9 +203,9 @@
 				kept.rotation = tracks_compress_positive_w(kept.rotation);
 				qvv other = kept;
 				other.rotation = rotation0;
-				rotation_moves = rotation_moves || shell_error(shell.x, kept, other) > shell.y;
+				rotation_moves = rotation_moves || compress_shell_error<kMetric>(shell.x, kept, other) > shell.y;
 				other.rotation = make_float4(default_rotation.x, default_rotation.y, default_rotation.z, default_rotation.w);
-				rotation_leaves_default = rotation_leaves_default || shell_error(shell.x, kept, other) > shell.y;
+				rotation_leaves_default = rotation_leaves_default || compress_shell_error<kMetric>(shell.x, kept, other) > shell.y;
 				same_translation = same_translation && kept.translation.x == translation0.x && kept.translation.y == translation0.y && kept.translation.z == translation0.z;
 				same_scale = same_scale && kept.scale.x == scale0.x && kept.scale.y == scale0.y && kept.scale.z == scale0.z;
 			}

@@ -170,7 +170,9 @@
 	// tracks_compress_analyze_kernel's shape: one wave64 per track, samples across the lanes, over the samples the vote left. Three passes
 	// over the samples, each with two shell error ballots (compact.transform.h:72-346): a kind is tested against its sample 0 and against its
 	// default under the rotation and translation the passes before it left -- the verdicts are wave uniform behind their ballots. The
-	// first pass also takes the minimum and maximum of the nine stored components (normalize.transform.h:51-76).
+	// first pass also takes the minimum and maximum of the nine stored components (normalize.transform.h:51-76). kMetric: the error metric
+	// of the six ballots (compress_shell_error, kernels_tracks_compress.inl).
+	template<uint32_t kMetric>
 	__global__ __launch_bounds__(k_compress_waves_per_block * k_wave_size) void variable_compress_analyze_kernel(variable_compress_launch launch)
 	{
 		const transform_compress_launch& base = launch.base;
@@ -211,9 +213,9 @@
 				kept.rotation = tracks_compress_positive_w(kept.rotation);
 				qvv other = kept;
 				other.rotation = rotation0;
-				moves = moves || shell_error(shell.x, kept, other) > shell.y;
+				moves = moves || compress_shell_error<kMetric>(shell.x, kept, other) > shell.y;
 				other.rotation = make_float4(default_rotation.x, default_rotation.y, default_rotation.z, default_rotation.w);
-				leaves_default = leaves_default || shell_error(shell.x, kept, other) > shell.y;
+				leaves_default = leaves_default || compress_shell_error<kMetric>(shell.x, kept, other) > shell.y;
 				const float stored[9] = { kept.rotation.x, kept.rotation.y, kept.rotation.z, kept.translation.x, kept.translation.y, kept.translation.z, kept.scale.x, kept.scale.y, kept.scale.z };
 				#pragma unroll
 				for (uint32_t c = 0; c < 9; ++c)
@@ -233,9 +235,9 @@
 				kept.rotation = rotation_type == k_sub_track_animated ? tracks_compress_positive_w(kept.rotation) : constant_rotation;
 				qvv other = kept;
 				other.translation = first.translation;
-				moves = moves || shell_error(shell.x, kept, other) > shell.y;
+				moves = moves || compress_shell_error<kMetric>(shell.x, kept, other) > shell.y;
 				other.translation = make_float4(default_translation.x, default_translation.y, default_translation.z, 0.0f);
-				leaves_default = leaves_default || shell_error(shell.x, kept, other) > shell.y;
+				leaves_default = leaves_default || compress_shell_error<kMetric>(shell.x, kept, other) > shell.y;
 			}
 			const uint32_t translation_type = transform_compress_type(__ballot(moves) == 0, __ballot(leaves_default) == 0);
 
@@ -250,9 +252,9 @@
 					kept.translation = constant_translation;
 				qvv other = kept;
 				other.scale = first.scale;
-				moves = moves || shell_error(shell.x, kept, other) > shell.y;
+				moves = moves || compress_shell_error<kMetric>(shell.x, kept, other) > shell.y;
 				other.scale = make_float4(default_scale.x, default_scale.y, default_scale.z, 0.0f);
-				leaves_default = leaves_default || shell_error(shell.x, kept, other) > shell.y;
+				leaves_default = leaves_default || compress_shell_error<kMetric>(shell.x, kept, other) > shell.y;
 			}
 			const uint32_t scale_type = transform_compress_type(__ballot(moves) == 0, __ballot(leaves_default) == 0);
 

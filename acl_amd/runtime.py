@@ -63,6 +63,7 @@ EXPORTED_SYMBOLS = [
     "aclhip_compress_tracks_workspace_bytes", "aclhip_compress_tracks_batch",
     "aclhip_variable_compress_num_segments", "aclhip_variable_compress_bound", "aclhip_compress_variable_workspace_bytes", "aclhip_compress_tracks_variable_batch",
     "aclhip_find_bit_rates_workspace_bytes", "aclhip_find_bit_rates_batch",
+    "aclhip_compress_tracks_metric_batch", "aclhip_compress_tracks_variable_metric_batch", "aclhip_find_bit_rates_metric_batch",
 ]
 
 
@@ -568,6 +569,9 @@ def load_library():
     lib.aclhip_find_bit_rates_workspace_bytes.argtypes = [u32, u32, u32]
     lib.aclhip_find_bit_rates_workspace_bytes.restype = u64
     lib.aclhip_find_bit_rates_batch.argtypes = [vp, vp, u32, ctypes.POINTER(FindBitRatesDesc), vp, u64, u64, vp, vp]
+    lib.aclhip_compress_tracks_metric_batch.argtypes = [vp, vp, u32, ctypes.POINTER(CompressTracksDesc), vp, u64, vp, u32, vp]
+    lib.aclhip_compress_tracks_variable_metric_batch.argtypes = [vp, vp, u32, ctypes.POINTER(CompressVariableDesc), vp, u64, vp, u32, vp]
+    lib.aclhip_find_bit_rates_metric_batch.argtypes = [vp, vp, u32, ctypes.POINTER(FindBitRatesDesc), vp, u64, u64, vp, u32, vp]
     _lib = lib
     return lib
 
@@ -1225,6 +1229,24 @@ class Context:
         self._check(self._lib.aclhip_compress_raw_tracks_batch(self._handle, raws_ptr, num_instances, ctypes.byref(desc) if desc is not None else None,
                                                                blobs_ptr, blob_stride_bytes, results_ptr, stream))
 
+    def compress_tracks_metric_batch(self, raws_ptr, num_instances, desc, blobs_ptr, blob_stride_bytes, results_ptr, metric, stream=None):
+        """aclhip_compress_tracks_metric_batch: compress_tracks_batch with the error metric of the vote and of the constant and default
+        rotations as an argument -- ERROR_METRIC_QVVF is compress_tracks_batch itself, ERROR_METRIC_QVVF_MATRIX3X4F the reference's matrix
+        metric."""
+        self._check(self._lib.aclhip_compress_tracks_metric_batch(self._handle, raws_ptr, num_instances, ctypes.byref(desc) if desc is not None else None,
+                                                                  blobs_ptr, blob_stride_bytes, results_ptr, int(metric) & 0xFFFFFFFF, stream))
+
+    def compress_tracks_variable_metric_batch(self, raws_ptr, num_instances, desc, blobs_ptr, blob_stride_bytes, results_ptr, metric, stream=None):
+        """aclhip_compress_tracks_variable_metric_batch: compress_tracks_variable_batch with the error metric of the vote and of the
+        compaction of all three kinds as an argument."""
+        self._check(self._lib.aclhip_compress_tracks_variable_metric_batch(self._handle, raws_ptr, num_instances, ctypes.byref(desc) if desc is not None else None,
+                                                                           blobs_ptr, blob_stride_bytes, results_ptr, int(metric) & 0xFFFFFFFF, stream))
+
+    def find_bit_rates_metric_batch(self, raws_ptr, num_instances, desc, bit_rates_ptr, instance_stride, segment_stride, results_ptr, metric, stream=None):
+        """aclhip_find_bit_rates_metric_batch: find_bit_rates_batch with the error metric the search optimises as an argument."""
+        self._check(self._lib.aclhip_find_bit_rates_metric_batch(self._handle, raws_ptr, num_instances, ctypes.byref(desc) if desc is not None else None,
+                                                                 bit_rates_ptr, instance_stride, segment_stride, results_ptr, int(metric) & 0xFFFFFFFF, stream))
+
     def compress_tracks_batch(self, raws_ptr, num_instances, desc, blobs_ptr, blob_stride_bytes, results_ptr, stream=None):
         """aclhip_compress_tracks_batch: compress_track_list with quatf_full or quatf_drop_w_full rotations (the rigid shell, the looping vote,
         constant and default rotations by the error metric) of the raw track arrays named at raws_ptr (device uint32 [num_instances]) into
@@ -1851,6 +1873,14 @@ def _set_track_tables(desc, tables):
         desc.num_table_tracks = num_tracks
 
 
+def _with_metric(launch, metric_launch, metric):
+    """The context's method a call with an error metric goes through: the entry point without one for ERROR_METRIC_QVVF (it is that
+    call), else the _metric entry point at `metric` (an unknown one is the library's to refuse)."""
+    if metric == ERROR_METRIC_QVVF:
+        return launch
+    return lambda *arguments, **keywords: metric_launch(*arguments, metric=metric, **keywords)
+
+
 def _compress_transform_tracks(ctx, launch, workspace_bytes, desc, raws, flags, default_pose, parents, precision, shell_distance, track_precisions, track_shell_distances,
                                bound=None, tables=None):
     """What compress_raw_tracks, compress_tracks and compress_tracks_variable share: `desc` (any of the three structs: the fields have one
@@ -1892,18 +1922,19 @@ def compress_tracks_workspace_bytes(num_instances, max_tracks):
 
 
 def compress_tracks(ctx, raws, rotation_format=ROTATION_QUATF_DROP_W_FULL, default_pose=None, parents=None, precision=1.0e-4, shell_distance=1.0, track_precisions=None,
-                    track_shell_distances=None, optimize_loops=False, include_parent_track_indices=False, include_track_descriptions=False):
+                    track_shell_distances=None, optimize_loops=False, include_parent_track_indices=False, include_track_descriptions=False, metric=ERROR_METRIC_QVVF):
     """acl::compress_track_list with quatf_drop_w_full (or quatf_full) rotations and vector3f_full translations and scales for raw track
     arrays as one launch, like compress_raw_tracks: `raws` is a handle or a list of handles. With quatf_drop_w_full the parents, precisions
     and shell distances make the rigid shell at which constant and default rotations and the looping vote (optimize_loops) are decided;
     every parent index is smaller than its child's. Rows are sized from aclhip_transform_compress_bound. Returns a list of 16 byte
-    aligned numpy uint8 blobs. Raises RuntimeError with the reference's message when a sample is not finite (a zero quaternion
-    included), ValueError when an instance is refused. Synchronous; the buffers are torch tensors on the context's device."""
+    aligned numpy uint8 blobs. `metric` is an aclhip_error_metric: ERROR_METRIC_QVVF_MATRIX3X4F decides the vote and the rotations with
+    the reference's matrix metric (quatf_full uses none). Raises RuntimeError with the reference's message when a sample is not finite
+    (a zero quaternion included), ValueError when an instance is refused. Synchronous; the buffers are torch tensors on the context's device."""
     flags = ((COMPRESS_OPTIMIZE_LOOPS if optimize_loops else 0) | (COMPRESS_INCLUDE_PARENT_TRACK_INDICES if include_parent_track_indices else 0)
              | (COMPRESS_INCLUDE_TRACK_DESCRIPTIONS if include_track_descriptions else 0))
     desc = CompressTracksDesc()
     desc.rotation_format, desc.translation_format, desc.scale_format = int(rotation_format), VECTOR_VECTOR3F_FULL, VECTOR_VECTOR3F_FULL
-    return _compress_transform_tracks(ctx, ctx.compress_tracks_batch, compress_tracks_workspace_bytes, desc, raws, flags, default_pose, parents, precision, shell_distance,
+    return _compress_transform_tracks(ctx, _with_metric(ctx.compress_tracks_batch, ctx.compress_tracks_metric_batch, metric), compress_tracks_workspace_bytes, desc, raws, flags, default_pose, parents, precision, shell_distance,
                                       track_precisions, track_shell_distances)
 
 
@@ -1927,7 +1958,8 @@ def find_bit_rates_workspace_bytes(num_instances, max_tracks, max_samples):
     return int(load_library().aclhip_find_bit_rates_workspace_bytes(int(num_instances), int(max_tracks), int(max_samples)))
 
 
-def _find_bit_rates(ctx, handles, infos, level, flags, default_pose, parents, precision, shell_distance, track_precisions, track_shell_distances, tables=None):
+def _find_bit_rates(ctx, handles, infos, level, flags, default_pose, parents, precision, shell_distance, track_precisions, track_shell_distances, tables=None,
+                    metric=ERROR_METRIC_QVVF):
     """The search over `handles` into a zero-filled device table uint8 [instances, segments, tracks, 4] of the largest array's segments
     and tracks: (the table, still on the device, and the results as a host array [instances, 2]). Synchronous."""
     import torch
@@ -1949,27 +1981,28 @@ def _find_bit_rates(ctx, handles, infos, level, flags, default_pose, parents, pr
     d_results = torch.zeros((num_instances, 2), dtype=torch.int32, device=device)
     d_workspace = torch.zeros(find_bit_rates_workspace_bytes(num_instances, desc.max_tracks, desc.max_samples) + 16, dtype=torch.uint8, device=device)
     desc.workspace = d_workspace.data_ptr()
-    ctx.find_bit_rates_batch(d_raws.data_ptr(), num_instances, desc, d_rates.data_ptr(), num_segments * desc.max_tracks * 4, desc.max_tracks * 4, d_results.data_ptr(),
-                             stream=stream.cuda_stream)
+    launch = _with_metric(ctx.find_bit_rates_batch, ctx.find_bit_rates_metric_batch, metric)
+    launch(d_raws.data_ptr(), num_instances, desc, d_rates.data_ptr(), num_segments * desc.max_tracks * 4, desc.max_tracks * 4, d_results.data_ptr(), stream=stream.cuda_stream)
     stream.synchronize()
     return d_rates, d_results.cpu().numpy().view(np.uint32).reshape(num_instances, 2)
 
 
 def find_bit_rates(ctx, raws, level="medium", default_pose=None, parents=None, precision=1.0e-4, shell_distance=1.0, track_precisions=None, track_shell_distances=None,
-                   optimize_loops=False):
+                   optimize_loops=False, metric=ERROR_METRIC_QVVF):
     """acl::find_optimal_bit_rates -- the bit rate search of compress_track_list with quatf_drop_w_variable / vector3f_variable /
     vector3f_variable at the levels "lowest", "low" and "medium" (one search) -- for raw track arrays as one launch: `raws` is a handle
     or a list of handles; the settings are compress_tracks_variable's. Returns a uint8 array [instances, segments, tracks, 4] of
     { rotation, translation, scale, 0 } entries over the segments and tracks of the largest array, zero-filled before the launch: 255
     marks a constant or default sub-track, rows and entries an instance does not have stay 0. It is the table compress_tracks_variable
-    takes. Raises RuntimeError with the reference's message when a sample is not finite, ValueError when an instance is refused.
-    Synchronous; the buffers are torch tensors on the context's device."""
+    takes. `metric` is the aclhip_error_metric the search optimises: ERROR_METRIC_QVVF_MATRIX3X4F is the reference's matrix metric, what
+    clip_error and raw_clip_error measure with metric=1. Raises RuntimeError with the reference's message when a sample is not finite,
+    ValueError when an instance is refused. Synchronous; the buffers are torch tensors on the context's device."""
     handles = np.atleast_1d(np.asarray(raws, dtype=np.uint32))
     infos = [ctx.raw_tracks_info(int(handle)) for handle in handles]
     if len(handles) == 0:
         return np.zeros((0, 0, 0, 4), dtype=np.uint8)
     d_rates, results = _find_bit_rates(ctx, handles, infos, level, COMPRESS_OPTIMIZE_LOOPS if optimize_loops else 0, default_pose, parents, precision, shell_distance,
-                                       track_precisions, track_shell_distances)
+                                       track_precisions, track_shell_distances, metric=metric)
     _raise_for_search_results(handles, results)
     return d_rates.cpu().numpy()
 
@@ -1983,14 +2016,16 @@ def _raise_for_search_results(handles, results):
 
 
 def compress_tracks_variable(ctx, raws, bit_rates=(16, 16, 16), default_pose=None, parents=None, precision=1.0e-4, shell_distance=1.0, track_precisions=None,
-                             track_shell_distances=None, optimize_loops=False, include_parent_track_indices=False, include_track_descriptions=False, level="medium"):
+                             track_shell_distances=None, optimize_loops=False, include_parent_track_indices=False, include_track_descriptions=False, level="medium",
+                             metric=ERROR_METRIC_QVVF):
     """acl::compress_track_list with quatf_drop_w_variable rotations and vector3f_variable translations and scales AT GIVEN BIT RATES for
     raw track arrays as one launch, like compress_tracks: `raws` is a handle or a list of handles. bit_rates is three uniform rates
     (rotation, translation, scale: 0 .. 24), or a uint8 table of { rotation, translation, scale, 0 } entries: [tracks, 4] shared by every
     instance and segment, [segments, tracks, 4] shared by the instances, or [instances, segments, tracks, 4]; it covers
     variable_compress_num_segments(samples) rows and the tracks of the largest array. bit_rates="search" runs find_bit_rates at `level`
     with the same settings first and compresses at its table, which stays on the device: the reference's compress_track_list at the
-    levels lowest to medium. Rows are sized from aclhip_variable_compress_bound.
+    levels lowest to medium. `metric` is the aclhip_error_metric of the vote, the compaction and the search (find_bit_rates). Rows are
+    sized from aclhip_variable_compress_bound.
     Returns a list of 16 byte aligned numpy uint8 blobs in the format the fast decode paths read. Raises RuntimeError with the
     reference's message when a sample is not finite, ValueError when an instance is refused (a rate above 24, a rate of 0 in a blob of
     one segment included). Synchronous; the buffers are torch tensors on the context's device."""
@@ -2008,7 +2043,8 @@ def compress_tracks_variable(ctx, raws, bit_rates=(16, 16, 16), default_pose=Non
         if bit_rates != "search":
             raise ValueError('bit_rates is three rates, a table or "search"')
         tables = _upload_track_tables(ctx, default_pose, parents, track_precisions, track_shell_distances)         # (once, for both calls)
-        d_rates, results = _find_bit_rates(ctx, handles, infos, level, flags, default_pose, parents, precision, shell_distance, track_precisions, track_shell_distances, tables)
+        d_rates, results = _find_bit_rates(ctx, handles, infos, level, flags, default_pose, parents, precision, shell_distance, track_precisions, track_shell_distances, tables,
+                                           metric=metric)
         _raise_for_search_results(handles, results)
         desc.bit_rates = d_rates.data_ptr()                                                 # (alive until the launch has run)
         desc.bit_rate_segment_stride = d_rates.shape[2] * 4
@@ -2030,23 +2066,25 @@ def compress_tracks_variable(ctx, raws, bit_rates=(16, 16, 16), default_pose=Non
 
     def workspace_bytes(num_instances, max_tracks):
         return compress_variable_workspace_bytes(num_instances, max_tracks, desc.max_samples)
-    return _compress_transform_tracks(ctx, ctx.compress_tracks_variable_batch, workspace_bytes, desc, raws, flags, default_pose, parents, precision, shell_distance,
+    return _compress_transform_tracks(ctx, _with_metric(ctx.compress_tracks_variable_batch, ctx.compress_tracks_variable_metric_batch, metric), workspace_bytes, desc, raws, flags, default_pose, parents, precision, shell_distance,
                                       track_precisions, track_shell_distances, bound=variable_compress_bound, tables=tables)
 
 
-def compress_tracks_at_precision(ctx, raw, skeleton, shells, precision, parents=None, default_pose=None, shell_distance=1.0, optimize_loops=False, **error_settings):
+def compress_tracks_at_precision(ctx, raw, skeleton, shells, precision, parents=None, default_pose=None, shell_distance=1.0, optimize_loops=False,
+                                 metric=ERROR_METRIC_QVVF, **error_settings):
     """For ONE raw track array: the smallest uniform bit rate whose blob is within `precision` of the array by raw_clip_error(ctx, raw, clip,
     skeleton, shells, **error_settings). Scans the rate from 1 upward -- compress_tracks_variable, register, raw_clip_error, unregister --
     and returns (blob, rate) of the first rate whose error is at most `precision`; when rate 24 fails too, the drop-w full blob of
     compress_tracks with rate None. A host loop over existing launches, up to 24 of each: NOT the reference's search
     (find_optimal_bit_rates chooses a rate per sub-track and segment and walks the hierarchy); it is here so that a blob of the fast
-    format at a stated error can be had today."""
-    settings = {"default_pose": default_pose, "parents": parents, "precision": precision, "shell_distance": shell_distance, "optimize_loops": optimize_loops}
+    format at a stated error can be had today. `metric` is the aclhip_error_metric of both the compressors' decisions and the measure."""
+    settings = {"default_pose": default_pose, "parents": parents, "precision": precision, "shell_distance": shell_distance, "optimize_loops": optimize_loops,
+                "metric": metric}
     for rate in range(1, 25):
         blob = compress_tracks_variable(ctx, raw, bit_rates=(rate, rate, rate), **settings)[0]
         clip = ctx.register_clip(blob)
         try:
-            _, error, _ = raw_clip_error(ctx, raw, clip, skeleton, shells, **error_settings)
+            _, error, _ = raw_clip_error(ctx, raw, clip, skeleton, shells, metric=metric, **error_settings)
         finally:
             ctx.unregister_clip(clip)
         if error <= precision:

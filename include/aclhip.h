@@ -217,7 +217,9 @@ const char* aclhip_last_error_message(const aclhip_context* context);
  * aclhip_compress_tracks_workspace_bytes and aclhip_compress_tracks_batch -- and for the variable formats at given bit rates --
  * aclhip_compress_variable_desc, aclhip_variable_compress_num_segments, aclhip_variable_compress_bound,
  * aclhip_compress_variable_workspace_bytes and aclhip_compress_tracks_variable_batch -- and for their bit rate search --
- * aclhip_find_bit_rates_desc, aclhip_find_bit_rates_workspace_bytes and aclhip_find_bit_rates_batch).
+ * aclhip_find_bit_rates_desc, aclhip_find_bit_rates_workspace_bytes and aclhip_find_bit_rates_batch -- and for the transform
+ * compressors with the error metric as an argument -- aclhip_compress_tracks_metric_batch,
+ * aclhip_compress_tracks_variable_metric_batch and aclhip_find_bit_rates_metric_batch).
  * A caller compiled against another header would hand over structs of another shape; aclhip_abi_version() says what the LIBRARY was
  * built with, and the C++ mirror (aclhip.hpp) refuses to create a context when the two differ. */
 #define ACLHIP_ABI_VERSION 6u
@@ -2047,7 +2049,8 @@ uint64_t aclhip_compress_tracks_workspace_bytes(uint32_t num_instances, uint32_t
  * per (instance, track): two shell error ballots for the rotation, the raw call's for translation and scale; the raw call's layout and
  * stream with three words per rotation; the hash. No atomics besides the refusal counter: the same bytes on every run.
  *   Left out: the variable formats, segmenting, range reduction and the bit rate search (all exist since:
- * aclhip_compress_tracks_variable_batch and aclhip_find_bit_rates_batch, below); the matrix error metric and additive bases; track and list names; output_index
+ * aclhip_compress_tracks_variable_batch and aclhip_find_bit_rates_batch, below; so does the matrix error metric:
+ * aclhip_compress_tracks_metric_batch, below); additive bases; track and list names; output_index
  * remapping; the C++ mirror in aclhip.hpp. What it costs: profiles/compress_tracks.md. */
 aclhip_status aclhip_compress_tracks_batch(aclhip_context* context, const aclhip_raw_tracks* raws /* DEVICE [num_instances] */,
 	uint32_t num_instances, const aclhip_compress_tracks_desc* desc, void* blobs /* DEVICE */, uint64_t blob_stride_bytes,
@@ -2166,7 +2169,7 @@ uint64_t aclhip_compress_variable_workspace_bytes(uint32_t num_instances, uint32
  * the refusal counter and no zero fill: the same bytes on every run.
  *   Left out: the bit rate search (a call of its own: aclhip_find_bit_rates_batch, below, writes the table this call reads); mixed full /
  * variable formats; keyframe stripping, database support and the
- * contributing error; the matrix error metric and additive bases; track and list names; output_index remapping; the C++ mirror in
+ * contributing error; additive bases (the matrix error metric: aclhip_compress_tracks_variable_metric_batch, below); track and list names; output_index remapping; the C++ mirror in
  * aclhip.hpp; anything against the serial hash. What it costs: profiles/compress_variable.md. */
 aclhip_status aclhip_compress_tracks_variable_batch(aclhip_context* context, const aclhip_raw_tracks* raws /* DEVICE [num_instances] */,
 	uint32_t num_instances, const aclhip_compress_variable_desc* desc, void* blobs /* DEVICE */, uint64_t blob_stride_bytes,
@@ -2267,11 +2270,66 @@ uint64_t aclhip_find_bit_rates_workspace_bytes(uint32_t num_instances, uint32_t 
  *   Five launches (DESIGN.md 4.7 "Bit rate search"): the shell and the analysis of the variable call, unchanged; per (instance, segment)
  * the segment ranges and S0; per (instance, segment, track) S3 from a table of S1 in LDS, lanes over the tuples of a size; per (instance,
  * segment) S4 with lanes over the samples. No atomics besides the refusal counter and no zero fill: the same bytes on every run.
- *   Left out: the levels high and highest (chains with two and three increments); the matrix error metric; additive bases; the
+ *   Left out: the levels high and highest (chains with two and three increments); additive bases (the matrix error metric:
+ * aclhip_find_bit_rates_metric_batch, below); the
  * contributing error and keyframe stripping. What it costs: profiles/bit_rate_search.md. */
 aclhip_status aclhip_find_bit_rates_batch(aclhip_context* context, const aclhip_raw_tracks* raws /* DEVICE [num_instances] */,
 	uint32_t num_instances, const aclhip_find_bit_rates_desc* desc, uint8_t* bit_rates /* DEVICE */, uint64_t instance_stride,
 	uint64_t segment_stride, aclhip_compress_result* results /* DEVICE [num_instances] */, void* stream);
+
+/* ---- the transform compressors with the error metric as an argument ----------------------------------------------------------------------
+ * aclhip_compress_tracks_batch, aclhip_compress_tracks_variable_batch and aclhip_find_bit_rates_batch with the error metric their
+ * decisions are taken by as an argument, as aclhip_measure_pose_error_metric_batch is to aclhip_measure_pose_error_batch: `metric` is
+ * an aclhip_error_metric. What a clip is compressed towards is then what aclhip_measure_pose_error_metric_batch measures of it: the
+ * reference names its matrix metric for rigs with non-uniform scale, where a QVV product cannot hold the shear a scaled parent puts on
+ * a rotated child. This is an addition to ABI version 6: new names only, no existing struct, function or message changes.
+ *   ACLHIP_METRIC_QVVF is the call without the argument: one host path, the same kernels, the same bytes. The three entry points above
+ * are these with ACLHIP_METRIC_QVVF.
+ *   An unknown metric is ACLHIP_ERROR_INVALID_ARGUMENT with a message, before any device call and before any other argument is looked at.
+ *   rotation_format == 0 (quatf_full, the raw call through aclhip_compress_tracks_metric_batch) uses no metric: any known one is
+ * accepted and gives the raw call's bytes.
+ *   Everything else is the base call's, word for word: the descs, every refusal, message, status, result and refusal count, the
+ * alignment and overlap rules, the workspace (the *_workspace_bytes functions above serve both metrics: nothing new lies in it), the
+ * shell metadata, stream ordering, "uploads nothing" and graph capture.
+ *   The definition for ACLHIP_METRIC_QVVF_MATRIX3X4F follows the reference's CODE (qvvf_matrix3x4f_transform_error_metric,
+ * transform_error_metrics.h:389-462; the comment above that class says the local error stays in qvvf, the code converts wherever
+ * needs_conversion(has_scale) holds). M(t) is step 1 of aclhip_pose_matrices_batch (rtm::matrix_from_qvv) of the transform t;
+ * E_m(d, A, B) is step 3 of aclhip_measure_pose_error_metric_batch under this metric for two matrices: the points (d,0,0), (0,d,0), (0,0,d)
+ * through point(p, T) of both, the largest of the three distances. In the definitions above, and in nothing else of them:
+ *   Step 3, the looping vote (optimize_looping.transform.h:115-173): a track votes against the wrap iff
+ *      E_m(local_b, M(first sample), M(last sample)) > sprec_b. Always the matrix route: has_scale is true at that point
+ *      (clip_context.impl.h:173).
+ *   Step 5, the compaction of constant and default sub-tracks (compact.transform.h:72-211): every shell_error(d, raw, lossy) is
+ *      E_m(d, M(raw), M(lossy)), for the same reason always. In the drop-w call that is the rotation; in the variable call and the
+ *      search all three kinds, each kind seeing the kinds before it as compacted, as there.
+ *   S2 WITH has_scale (quantize.transform.h:223-314, 674-867). LOCAL error: E_m(local_b, M(raw), M(S1 transform)). OBJECT error: both
+ *      sides go down the chain as matrices, O_0 = M(L_0), O_k = matrix_mul(M(L_k), O_k-1) -- step 2 of aclhip_pose_matrices_batch: the
+ *      product is lhs first; nothing is normalized anywhere and a negative scale is no special case, a matrix needs none -- then
+ *      E_m(local_b, O_n raw, O_n lossy). The two scans and their thresholds are unchanged.
+ *   S2 WITHOUT has_scale: exactly ACLHIP_METRIC_QVVF's. The matrix metric inherits calculate_error_no_scale, qvv_mul_no_scale and
+ *      qvv_normalize: a clip whose scales are all default gets the table of the qvvf search, byte for byte, wherever vote and
+ *      compaction fell the same way.
+ *   Unchanged: step 1's normalization; the clip's rigid shell of step 2 and S0's shell per segment (rigid_shell_utils.h never asks the
+ *      metric: both stay qvv_mul_point3); ranges, the fix-up, quantization and S1; the permutation lists; every loop, order and strict
+ *      comparison of S3 and S4; the blob's layout and the hash.
+ *   Measured against the reference under its matrix metric on the 28 clips of tests/test_bit_rate_search_oracle.py
+ * (tests/test_matrix_metric_compress_oracle.py): 0.25 % of the animated sub-track rates differ, 2.5 % in the worst clip, the stream bits
+ * by 0.10 % -- the reference against itself with its input rotations one ulp away: 0.71 %, 3.6 %, 0.16 %. The two metrics differ from
+ * each other in 12 % of those rates.
+ *   The launches are the base calls' (DESIGN.md 4.7 "Transform compression (the matrix error metric)"): the metric is a template
+ * argument of the five kernels that decide by it -- the shell kernel's vote, both analyses, the local and the object phase of the
+ * search --, and the qvvf instantiations are the kernels as they were. The object phase carries two 3x4 matrices down the chain per lane
+ * in the place of two QVVs; the local phase keeps its LDS image in QVV and applies M() behind the read.
+ *   Left out: what the base calls leave out, but for the metric. What it costs: profiles/compress_metric.md. */
+aclhip_status aclhip_compress_tracks_metric_batch(aclhip_context* context, const aclhip_raw_tracks* raws /* DEVICE [num_instances] */,
+	uint32_t num_instances, const aclhip_compress_tracks_desc* desc, void* blobs /* DEVICE */, uint64_t blob_stride_bytes,
+	aclhip_compress_result* results /* DEVICE [num_instances] */, uint32_t metric, void* stream);
+aclhip_status aclhip_compress_tracks_variable_metric_batch(aclhip_context* context, const aclhip_raw_tracks* raws /* DEVICE [num_instances] */,
+	uint32_t num_instances, const aclhip_compress_variable_desc* desc, void* blobs /* DEVICE */, uint64_t blob_stride_bytes,
+	aclhip_compress_result* results /* DEVICE [num_instances] */, uint32_t metric, void* stream);
+aclhip_status aclhip_find_bit_rates_metric_batch(aclhip_context* context, const aclhip_raw_tracks* raws /* DEVICE [num_instances] */,
+	uint32_t num_instances, const aclhip_find_bit_rates_desc* desc, uint8_t* bit_rates /* DEVICE */, uint64_t instance_stride,
+	uint64_t segment_stride, aclhip_compress_result* results /* DEVICE [num_instances] */, uint32_t metric, void* stream);
 
 /* ---- multi-GPU ---------------------------------------------------------------------------------- */
 

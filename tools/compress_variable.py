@@ -9,7 +9,10 @@ Time is reported, never judged: the median of COMPRESS_TRACKS_ROUNDS interleaved
 spread (max - min) / median; in the same rounds aclhip_compress_tracks_batch (quatf_drop_w_full) on the same arrays, so that the two are
 measured side by side. With ACLHIP_LIBRARY pointing at libaclhip_lab.so the line also carries the per-phase split:
 ACLHIP_VARIABLE_COMPRESS_PHASES=k stops the call behind its k-th launch (shell, analysis, layout, segment ranges, stream, hash), and a
-phase's time is the difference of two medians measured in the same rounds. Prints one JSON line."""
+phase's time is the difference of two medians measured in the same rounds. --metric {0,1}: the aclhip_error_metric of both calls (1:
+the _metric entry points with the reference's matrix metric, checked against tests/matrix_metric_compress_restatement.py). Prints one
+JSON line."""
+import argparse
 import json
 import os
 import sys
@@ -24,6 +27,7 @@ import torch  # noqa: E402
 from acl_amd import runtime  # noqa: E402
 import compress_tracks as workload  # noqa: E402  (the arrays, the skeleton, the timer)
 import variable_compress_restatement as restatement  # noqa: E402  (the checker's restatement)
+import matrix_metric_compress_restatement as metric_restatement  # noqa: E402  (and with the metric as an argument)
 
 N, ARRAYS, TRACKS, SAMPLES = workload.N, workload.ARRAYS, workload.TRACKS, workload.SAMPLES
 ROUNDS, REPEATS, RESTATED = workload.ROUNDS, workload.REPEATS, workload.RESTATED
@@ -34,6 +38,9 @@ KNOB = "ACLHIP_VARIABLE_COMPRESS_PHASES"
 
 
 def main():
+    parser = argparse.ArgumentParser(description=__doc__.split("\n")[0])
+    parser.add_argument("--metric", type=int, choices=(0, 1), default=0, help="aclhip_error_metric: 0 qvvf (the entry points without a metric), 1 qvvf_matrix3x4f")
+    metric = parser.parse_args().metric
     if not torch.cuda.is_available():
         raise SystemExit("tools/compress_variable.py needs a GPU: nothing is measured without one")
     rng = np.random.default_rng(9100 + TRACKS)
@@ -62,10 +69,16 @@ def main():
     drop_w.parent_indices, drop_w.num_table_tracks = d_parents.data_ptr(), TRACKS
 
     def launch():
-        ctx.compress_tracks_variable_batch(d_raws.data_ptr(), N, desc, d_blobs.data_ptr(), stride, d_results.data_ptr(), stream=s)
+        if metric == runtime.ERROR_METRIC_QVVF:
+            ctx.compress_tracks_variable_batch(d_raws.data_ptr(), N, desc, d_blobs.data_ptr(), stride, d_results.data_ptr(), stream=s)
+        else:
+            ctx.compress_tracks_variable_metric_batch(d_raws.data_ptr(), N, desc, d_blobs.data_ptr(), stride, d_results.data_ptr(), metric, stream=s)
 
     def launch_drop_w():
-        ctx.compress_tracks_batch(d_raws.data_ptr(), N, drop_w, d_blobs.data_ptr(), stride, d_results.data_ptr(), stream=s)
+        if metric == runtime.ERROR_METRIC_QVVF:
+            ctx.compress_tracks_batch(d_raws.data_ptr(), N, drop_w, d_blobs.data_ptr(), stride, d_results.data_ptr(), stream=s)
+        else:
+            ctx.compress_tracks_metric_batch(d_raws.data_ptr(), N, drop_w, d_blobs.data_ptr(), stride, d_results.data_ptr(), metric, stream=s)
 
     # ---- checked before it is timed
     os.environ.pop(KNOB, None)
@@ -79,7 +92,7 @@ def main():
         print(f"refused or failed instances: {ctx.rejected_instance_count()}, statuses {np.unique(results[:, 0])}", flush=True)
         sys.exit(1)
     for i in range(min(ARRAYS, N, RESTATED)):
-        expected = restatement.compress(arrays[i], RATE, (BIT_RATE,) * 3, parents=parents, precision=PRECISION, shell_distance=SHELL).blob
+        expected = metric_restatement.compress_variable(arrays[i], RATE, (BIT_RATE,) * 3, metric, parents=parents, precision=PRECISION, shell_distance=SHELL).blob
         if results[i, 1] != expected.size or not np.array_equal(first[i, : expected.size], expected):
             print(f"MISMATCH with the restatement in the blob of array {i}", flush=True)
             sys.exit(1)
@@ -120,7 +133,7 @@ def main():
         return {"median": round(float(np.median(values)), 2), "min": round(float(values.min()), 2), "max": round(float(values.max()), 2),
                 "spread": round(float((values.max() - values.min()) / np.median(values)), 4)}
 
-    result = {"instances": N, "distinct_arrays": ARRAYS, "tracks": TRACKS, "samples": SAMPLES, "rounds": ROUNDS, "repeats": REPEATS, "bit_rate": BIT_RATE,
+    result = {"metric": metric, "instances": N, "distinct_arrays": ARRAYS, "tracks": TRACKS, "samples": SAMPLES, "rounds": ROUNDS, "repeats": REPEATS, "bit_rate": BIT_RATE,
               "checked_against": "restatement (%d arrays), aclhip_check_clip with the hash (%d)" % (min(ARRAYS, N, RESTATED), min(ARRAYS, N)),
               "library": os.path.basename(runtime.library_path()), "raw_bytes": int(N * TRACKS * SAMPLES * 48), "blob_bytes": blob_bytes,
               "drop_w_blob_bytes": drop_w_blob_bytes, "row_stride": stride, "segments": runtime.variable_compress_num_segments(SAMPLES),

@@ -10,7 +10,12 @@ are measured side by side; the bytes of those blobs next to the bytes at a unifo
 libaclhip_lab.so the line also carries the per-phase split: ACLHIP_FIND_BIT_RATES_PHASES=k stops the call behind its k-th launch (shell,
 analysis, segments, local, object), and a phase's time is the difference of two medians measured in the same rounds. With
 FIND_BIT_RATES_AT_PRECISION=1 the first array also goes through runtime.compress_tracks_at_precision, for its blob's size and rate.
-Prints one JSON line."""
+--metric {0,1}: the aclhip_error_metric of the search and of the compress call. With 1 (the reference's matrix metric, through the
+_metric entry points, checked against tests/matrix_metric_compress_restatement.py) the qvvf calls are timed IN THE SAME ROUNDS, their
+blob bytes reported beside, and every key of metric 0 carries the suffix _qvvf. --scales nonuniform: every scale of the workload's
+arrays drawn anew per sample and component within 0.9 .. 1.1, so that has_scale holds in every array and shear builds up down the
+chains -- the workload the matrix metric is for. Prints one JSON line."""
+import argparse
 import json
 import os
 import sys
@@ -25,6 +30,7 @@ import torch  # noqa: E402
 from acl_amd import runtime  # noqa: E402
 import compress_tracks as workload  # noqa: E402  (the arrays, the skeleton, the timer)
 import bit_rate_search_restatement as restatement  # noqa: E402  (the checker's restatement)
+import matrix_metric_compress_restatement as metric_restatement  # noqa: E402  (and with the metric as an argument)
 
 N, ARRAYS, TRACKS, SAMPLES = workload.N, workload.ARRAYS, workload.TRACKS, workload.SAMPLES
 ROUNDS = int(os.environ.get("FIND_BIT_RATES_ROUNDS", "3"))
@@ -37,10 +43,19 @@ KNOB = "ACLHIP_FIND_BIT_RATES_PHASES"
 
 
 def main():
+    parser = argparse.ArgumentParser(description=__doc__.split("\n")[0])
+    parser.add_argument("--metric", type=int, choices=(0, 1), default=0, help="aclhip_error_metric: 0 qvvf (the entry points without a metric), 1 qvvf_matrix3x4f")
+    parser.add_argument("--scales", choices=("workload", "nonuniform"), default="workload", help="nonuniform: every scale within 0.9 .. 1.1, per sample and component")
+    arguments = parser.parse_args()
+    metric = arguments.metric
     if not torch.cuda.is_available():
         raise SystemExit("tools/find_bit_rates.py needs a GPU: nothing is measured without one")
     rng = np.random.default_rng(9100 + TRACKS)
     arrays = [workload.make_array(rng) for _ in range(ARRAYS)]
+    if arguments.scales == "nonuniform":
+        scale_rng = np.random.default_rng(9200 + TRACKS)
+        for samples in arrays:
+            samples[:, :, 8:11] = scale_rng.uniform(0.9, 1.1, size=(SAMPLES, TRACKS, 3))
     order = rng.integers(0, ARRAYS, size=N)
     order[:ARRAYS] = np.arange(ARRAYS)[: min(ARRAYS, N)]        # every distinct array is in the batch
     parents = workload.skeleton(TRACKS)
@@ -66,14 +81,30 @@ def main():
     desc.parent_indices, desc.num_table_tracks = d_parents.data_ptr(), TRACKS
     desc.bit_rates, desc.bit_rate_segment_stride, desc.bit_rate_instance_stride = d_rates.data_ptr(), 4 * TRACKS, 4 * TRACKS * segments
 
-    def launch_search():
+    def launch_search_qvvf():
         ctx.find_bit_rates_batch(d_raws.data_ptr(), N, search, d_rates.data_ptr(), 4 * TRACKS * segments, 4 * TRACKS, d_results.data_ptr(), stream=s)
 
-    def launch_compress():
+    def launch_compress_qvvf():
         ctx.compress_tracks_variable_batch(d_raws.data_ptr(), N, desc, d_blobs.data_ptr(), stride, d_results.data_ptr(), stream=s)
+
+    def launch_search():
+        if metric == runtime.ERROR_METRIC_QVVF:
+            return launch_search_qvvf()
+        ctx.find_bit_rates_metric_batch(d_raws.data_ptr(), N, search, d_rates.data_ptr(), 4 * TRACKS * segments, 4 * TRACKS, d_results.data_ptr(), metric, stream=s)
+
+    def launch_compress():
+        if metric == runtime.ERROR_METRIC_QVVF:
+            return launch_compress_qvvf()
+        ctx.compress_tracks_variable_metric_batch(d_raws.data_ptr(), N, desc, d_blobs.data_ptr(), stride, d_results.data_ptr(), metric, stream=s)
 
     # ---- checked before it is timed
     os.environ.pop(KNOB, None)
+    qvvf_blob_bytes = None
+    if metric != runtime.ERROR_METRIC_QVVF:         # (the qvvf search's blobs, for their bytes; the table is searched again below)
+        with torch.cuda.stream(stream):
+            launch_search_qvvf()
+            launch_compress_qvvf()
+            qvvf_blob_bytes = int(d_results.cpu().numpy().view(np.uint32)[:, 1].astype(np.int64).sum())
     with torch.cuda.stream(stream):
         launch_search()
         results = d_results.cpu().numpy().view(np.uint32).copy()
@@ -82,7 +113,7 @@ def main():
         print(f"refused or failed instances: {ctx.rejected_instance_count()}, statuses {np.unique(results[:, 0])}", flush=True)
         sys.exit(1)
     for i in range(min(ARRAYS, N, RESTATED)):
-        expected = restatement.find_bit_rates(arrays[i], RATE, parents=parents, precision=PRECISION, shell_distance=SHELL).table
+        expected = metric_restatement.find_bit_rates(arrays[i], RATE, metric, parents=parents, precision=PRECISION, shell_distance=SHELL).table
         if not np.array_equal(tables[i], expected):
             print(f"MISMATCH with the restatement in the table of array {i}: {int((tables[i] != expected).sum())} bytes", flush=True)
             sys.exit(1)
@@ -116,6 +147,12 @@ def main():
     if lab:
         for k in range(1, 5):
             cases["phases_%d" % k] = (launch_search, str(k))
+    if metric != runtime.ERROR_METRIC_QVVF:         # (the compress call behind the qvvf search reads the matrix table: its time does not depend on the rates' metric)
+        cases["search_qvvf"] = (launch_search_qvvf, None)
+        cases["compress_at_the_table_qvvf"] = (launch_compress_qvvf, None)
+        if lab:
+            for k in range(1, 5):
+                cases["phases_%d_qvvf" % k] = (launch_search_qvvf, str(k))
 
     def run(case, repeats):
         call, knob = case
@@ -138,19 +175,23 @@ def main():
         return {"median": round(float(np.median(values)), 2), "min": round(float(values.min()), 2), "max": round(float(values.max()), 2),
                 "spread": round(float((values.max() - values.min()) / np.median(values)), 4)}
 
-    result = {"instances": N, "distinct_arrays": ARRAYS, "tracks": TRACKS, "samples": SAMPLES, "segments": segments, "rounds": ROUNDS, "repeats": REPEATS,
+    result = {"metric": metric, "scales": arguments.scales, "instances": N, "distinct_arrays": ARRAYS, "tracks": TRACKS, "samples": SAMPLES, "segments": segments, "rounds": ROUNDS, "repeats": REPEATS,
               "checked_against": "restatement (%d arrays)" % min(ARRAYS, N, RESTATED), "library": os.path.basename(runtime.library_path()),
               "raw_bytes": int(N * TRACKS * SAMPLES * 48), "searched_blob_bytes": blob_bytes, "uniform_16_blob_bytes": uniform_bytes,
               "rates": {"min": int(animated.min()), "max": int(animated.max()), "mean": round(float(animated.mean()), 2)} if animated.size else None,
               "us": {key: summary(values) for key, values in samples.items()}}
     if at_precision is not None:
         result["first_array"] = at_precision
-    if lab:
-        total = result["us"]["search"]["median"]
-        upto = [result["us"]["phases_%d" % k]["median"] for k in range(1, 5)] + [total]
+    if qvvf_blob_bytes is not None:
+        result["searched_blob_bytes_qvvf"] = qvvf_blob_bytes
+    for suffix in ("", "_qvvf") if lab else ():
+        if "search" + suffix not in result["us"]:
+            continue
+        total = result["us"]["search" + suffix]["median"]
+        upto = [result["us"]["phases_%d%s" % (k, suffix)]["median"] for k in range(1, 5)] + [total]
         split = [upto[0]] + [upto[k] - upto[k - 1] for k in range(1, 5)]
-        result["phase_us"] = {name: round(value, 2) for name, value in zip(PHASES, split)}
-        result["phase_share"] = {name: round(value / total, 3) for name, value in zip(PHASES, split)}
+        result["phase_us" + suffix] = {name: round(value, 2) for name, value in zip(PHASES, split)}
+        result["phase_share" + suffix] = {name: round(value / total, 3) for name, value in zip(PHASES, split)}
     ctx.close()
     print(json.dumps(result), flush=True)
 
