@@ -436,9 +436,12 @@ _ref_compress_ex = None
 
 
 def ref_compress_ex(raw, sample_rate, parents=None, bind_pose=None, level="medium", rotation_format="quatf_drop_w_variable", translation_format="vector3f_variable",
-                    scale_format="vector3f_variable", precision=0.0001, shell_distance=1.0, strip_proportion=0.0, strip_threshold=0.0, **flags):
+                    scale_format="vector3f_variable", precision=0.0001, shell_distance=1.0, strip_proportion=0.0, strip_threshold=0.0, track_precisions=None,
+                    track_shell_distances=None, **flags):
     """compress_track_list with any compression_settings (the reference's regression configs: test_data/configs/*.sjson).
-    raw [num_samples, num_tracks, 12]; bind_pose [num_tracks, 12] = track_desc_transformf::default_value; flags: COMPRESS_FLAGS names = True."""
+    raw [num_samples, num_tracks, 12]; bind_pose [num_tracks, 12] = track_desc_transformf::default_value; track_precisions and
+    track_shell_distances [num_tracks] = track_desc_transformf::precision and shell_distance per track (None: `precision` and
+    `shell_distance` for every track; given, they need a library that has aclref_compress_per_track); flags: COMPRESS_FLAGS names = True."""
     global _ref_compress_ex
     if _ref_compress_ex is None:
         if not os.path.exists(REF_COMPRESS_PATH):
@@ -460,12 +463,21 @@ def ref_compress_ex(raw, sample_rate, parents=None, bind_pose=None, level="mediu
                                    sum(COMPRESS_FLAGS[name] for name, on in flags.items() if on), strip_proportion, strip_threshold, precision, shell_distance)
     error = ctypes.create_string_buffer(256)
     args = [raw.ctypes.data, num_tracks, num_samples, ctypes.c_float(sample_rate), parents.ctypes.data, _ptr(bind_pose), ctypes.byref(settings)]
-    size = _ref_compress_ex.aclref_compress_ex(*args, None, 0, error, 256)
+    call = _ref_compress_ex.aclref_compress_ex
+    if track_precisions is not None or track_shell_distances is not None:
+        per_track = [None if table is None else np.ascontiguousarray(table, dtype=np.float32) for table in (track_precisions, track_shell_distances)]
+        assert all(table is None or table.shape == (num_tracks,) for table in per_track)
+        call = _ref_compress_ex.aclref_compress_per_track         # (an AttributeError on a library from before the per-track tables)
+        call.argtypes = [ctypes.c_void_p, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_float, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
+                         ctypes.POINTER(RefCompressSettings), ctypes.c_void_p, ctypes.c_uint32, ctypes.c_char_p, ctypes.c_uint32]
+        call.restype = ctypes.c_uint32
+        args[6:6] = [_ptr(per_track[0]), _ptr(per_track[1])]
+    size = call(*args, None, 0, error, 256)
     if size == 0:
         raise RuntimeError(f"aclref_compress_ex failed: {error.value.decode()}")
     from acl_amd.synth import aligned_bytes
     blob = aligned_bytes(size)
-    written = _ref_compress_ex.aclref_compress_ex(*args, blob.ctypes.data, size, error, 256)
+    written = call(*args, blob.ctypes.data, size, error, 256)
     assert written == size
     return blob
 

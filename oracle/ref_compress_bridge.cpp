@@ -35,9 +35,12 @@ extern "C"
 		float shell_distance;
 	};
 
-	// raw / parents as for aclref_compress; bind_pose: [num_tracks][12] floats = track_desc_transformf::default_value per track, or null (identity)
-	uint32_t aclref_compress_ex(const float* raw, uint32_t num_tracks, uint32_t num_samples, float sample_rate, const int32_t* parents, const float* bind_pose,
-		const aclref_compress_settings* options, void* out, uint32_t capacity, char* error, uint32_t error_capacity)
+	// raw / parents as for aclref_compress; bind_pose: [num_tracks][12] floats = track_desc_transformf::default_value per track, or null (identity);
+	// track_precisions / track_shell_distances: [num_tracks] floats = track_desc_transformf::precision / shell_distance per track, or null
+	// (the one value of `options` for every track)
+	uint32_t aclref_compress_per_track(const float* raw, uint32_t num_tracks, uint32_t num_samples, float sample_rate, const int32_t* parents, const float* bind_pose,
+		const float* track_precisions, const float* track_shell_distances, const aclref_compress_settings* options, void* out, uint32_t capacity, char* error,
+		uint32_t error_capacity)
 	{
 		acl::ansi_allocator allocator;
 		uint32_t size = 0;
@@ -50,8 +53,8 @@ extern "C"
 				acl::track_desc_transformf desc;
 				desc.output_index = track_index;
 				desc.parent_index = parents != nullptr && parents[track_index] >= 0 ? uint32_t(parents[track_index]) : acl::k_invalid_track_index;
-				desc.precision = options->precision;
-				desc.shell_distance = options->shell_distance;
+				desc.precision = track_precisions != nullptr ? track_precisions[track_index] : options->precision;
+				desc.shell_distance = track_shell_distances != nullptr ? track_shell_distances[track_index] : options->shell_distance;
 				if (bind_pose != nullptr)
 				{
 					const float* qvv = bind_pose + size_t(track_index) * 12;
@@ -111,6 +114,13 @@ extern "C"
 			allocator.deallocate(compressed, size);
 		}
 		return size;
+	}
+
+	// one precision and one shell distance, those of `options`, for every track
+	uint32_t aclref_compress_ex(const float* raw, uint32_t num_tracks, uint32_t num_samples, float sample_rate, const int32_t* parents, const float* bind_pose,
+		const aclref_compress_settings* options, void* out, uint32_t capacity, char* error, uint32_t error_capacity)
+	{
+		return aclref_compress_per_track(raw, num_tracks, num_samples, sample_rate, parents, bind_pose, nullptr, nullptr, options, out, capacity, error, error_capacity);
 	}
 
 	// raw: [num_samples][num_tracks][12] floats (rot xyzw | trans xyz_ | scale xyz_). parents: num_tracks entries, -1 = root.

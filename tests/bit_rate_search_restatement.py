@@ -14,6 +14,7 @@ per (segment, track), the object error over the whole segment at the final rates
 The permutations and samples of a size class are evaluated at once; object transforms are kept per (track, rates of its chain).
 A helper, not a test file: tests/test_bit_rate_search_oracle.py holds it to the reference's compressor,
 tests/test_gpu_bit_rate_search.py holds the kernels to it on every byte."""
+import collections
 import itertools
 
 import numpy as np
@@ -89,9 +90,21 @@ def scan(errors, threshold, stop):
     return np.maximum(errors.max(axis=-1), F32(0.0)).astype(np.float32)
 
 
+# what Search.visits counts
+VISITS = ("local_not_met",                  # S3 went through a track's whole permutation list and no entry was below the threshold
+          "local_picked_raw",               # S3's winner holds a 24: the row of raw samples
+          "increment_reached_raw",          # increment() took a real rate (one below 24) to 24; never the 255 of a sub-track that is not animated
+          "link_maxed_out",                 # the last pass left a link that has an animated sub-track at three rates of 24 (or 255)
+          "chain_maxed_out",                # ... and every link of the chain: the pass ends above the threshold
+          "scale_raw_translation_bump",     # "rotation == translation, scale already raw" with a real scale rate of 24
+          "ancestor_improved",              # the increment the first loop kept was on a link above the target
+          "no_progress")                    # the first loop ended because no single increment lowered the error
+
+
 class Search:
     """table uint8 [G, T, 4]; local_table: the same behind the local phase; errors float32 [G, T]; met bool [G, T]; base: the Compressed
-    of variable_compress_restatement at the table; evaluations: how many object errors were measured"""
+    of variable_compress_restatement at the table; evaluations: how many object errors were measured; visits: a collections.Counter of
+    the edges the search went over, by name (VISITS) -- a record beside the search: nothing is decided from it"""
 
 
 def find_bit_rates(samples, sample_rate, default_pose=None, parents=None, flags=0, precision=1.0e-4, shell_distance=1.0, track_precisions=None,
@@ -131,6 +144,7 @@ def find_bit_rates(samples, sample_rate, default_pose=None, parents=None, flags=
     out.errors = np.zeros((len(base.segments), num_tracks), dtype=np.float32)
     out.met = np.zeros((len(base.segments), num_tracks), dtype=bool)
     out.evaluations = 0
+    visits = out.visits = collections.Counter()
     out.shells = np.zeros((len(base.segments), num_tracks, 2), dtype=np.float32)
 
     for g, (start, count) in enumerate(base.segments):
@@ -215,6 +229,8 @@ def find_bit_rates(samples, sample_rate, default_pose=None, parents=None, flags=
                 if best_error < threshold:
                     break                               # good enough: the sizes behind this one are not tried
             rates[b] = best
+            visits["local_not_met"] += int(not best_error < threshold)
+            visits["local_picked_raw"] += int((best[kinds] == RAW_RATE).any())
         out.local_table[g, :, 0:3] = rates
 
         # S2: the object error, S4: the object phase
@@ -238,6 +254,7 @@ def find_bit_rates(samples, sample_rate, default_pose=None, parents=None, flags=
             return error_cache[key, stop]
 
         def increment(rate, by):
+            visits["increment_reached_raw"] += int(rate < RAW_RATE <= rate + by)
             return rate if rate >= RAW_RATE else min(rate + by, RAW_RATE)
 
         def increase_bone_bit_rate(b, num_increments, old_error):
@@ -294,11 +311,14 @@ def find_bit_rates(samples, sample_rate, default_pose=None, parents=None, flags=
                     if error < best_error:
                         best_error, best_rates = error, found
                         if error < threshold:
+                            visits["ancestor_improved"] += int(found[0] != b)
                             break
                     if best_error >= original_error:
+                        visits["no_progress"] += 1
                         break                           # no progress
                     error = best_error
                     rates[best_rates[0]] = best_rates[1]
+                    visits["ancestor_improved"] += int(best_rates[0] != b)
                 if error < initial_error:
                     rates[best_rates[0]] = best_rates[1]
 
@@ -312,8 +332,10 @@ def find_bit_rates(samples, sample_rate, default_pose=None, parents=None, flags=
                             smallest = int(np.argmin(rates[link]))          # std::min_element: the first of the smallest
                             if rates[link, smallest] >= RAW_RATE:
                                 num_maxed_out += 1
+                                visits["link_maxed_out"] += int((types[:, link] == ANIMATED).any())
                                 break
                             if rates[link, 0] == rates[link, 1] and rates[link, 1] < RAW_RATE and rates[link, 2] >= RAW_RATE:
+                                visits["scale_raw_translation_bump"] += int(rates[link, 2] == RAW_RATE)
                                 rates[link, 1] += 1
                             else:
                                 rates[link, smallest] += 1
@@ -325,6 +347,7 @@ def find_bit_rates(samples, sample_rate, default_pose=None, parents=None, flags=
                         if error < threshold:
                             break
                     if num_maxed_out == len(chain):
+                        visits["chain_maxed_out"] += 1
                         break
                 # (the max-out pass behind this is for quatf_full only: never here)
         out.table[g, :, 0:3] = rates

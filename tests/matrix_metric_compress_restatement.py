@@ -99,7 +99,7 @@ def compress_variable(samples, sample_rate, bit_rates, metric=METRIC_QVVF, **set
 
 
 def find_bit_rates(samples, sample_rate, metric=METRIC_QVVF, **settings):
-    """bit_rate_search_restatement.find_bit_rates under `metric`"""
+    """bit_rate_search_restatement.find_bit_rates under `metric`: its Search as it is, the record of visits included"""
     with arithmetic_of(metric):
         return search.find_bit_rates(samples, sample_rate, **settings)
 

@@ -462,6 +462,75 @@ def mixed_clip(seed, num_samples, num_tracks, offset=0, default_pose=None, scale
     return samples
 
 
+def gentle_clip(seed, num_samples, num_tracks, offset=0, scales="mixed"):
+    """mixed_clip() with every ANIMATED sub-track replaced by a smooth small motion about the track's first sample: the low end of the
+    rate table (rates 1 to 4 at precision 0.01 and shell distance 3), where white noise never lands. With u(i) = sin(phi + 2 pi f i / S),
+    phi uniform in [0, 2 pi) and f in [0.5, 2]: a rotation is the first sample's, pre-multiplied by a turn of a u(i) about one fixed
+    random axis, a in [0.01, 0.05] rad; a translation component is the first sample's plus A u(i), A in [0.03, 0.15]; a scale component is
+    1 + B u(i), B in [0.01, 0.03]; one amplitude for a sub-track, phi and f drawn per component of a translation or a scale. 2 to 15 precisions at the
+    shell: every sub-track stays clearly ANIMATED. Computed in float64, rounded to float32 once."""
+    samples = mixed_clip(seed, num_samples, num_tracks, offset, scales=scales)
+    rng = np.random.default_rng(500 + seed)
+    steps = np.arange(num_samples, dtype=np.float64)
+
+    def wave():
+        phase, frequency = rng.uniform(0.0, 2.0 * np.pi), rng.uniform(0.5, 2.0)
+        return np.sin(phase + 2.0 * np.pi * frequency * steps / num_samples)
+    for track in range(num_tracks):
+        rotation, translation, scale = triple_of(track, offset)
+        if rotation == ANIMATED:
+            axis = rng.standard_normal(3)
+            axis /= np.linalg.norm(axis)
+            half = 0.5 * rng.uniform(0.01, 0.05) * wave()
+            x, y, z = (axis[:, None] * np.sin(half)).astype(np.float64)
+            w = np.cos(half)
+            first = samples[0, track, 0:4].astype(np.float64)
+            first /= np.linalg.norm(first)
+            fx, fy, fz, fw = first
+            turned = np.stack([w * fx + x * fw + y * fz - z * fy, w * fy - x * fz + y * fw + z * fx, w * fz + x * fy - y * fx + z * fw, w * fw - x * fx - y * fy - z * fz], axis=1)
+            samples[:, track, 0:4] = (turned / np.linalg.norm(turned, axis=1, keepdims=True)).astype(np.float32)
+        if translation == ANIMATED:
+            waves = np.stack([wave() for _ in range(3)], axis=1)
+            samples[:, track, 4:7] = (samples[0, track, 4:7].astype(np.float64) + rng.uniform(0.03, 0.15) * waves).astype(np.float32)
+        if scale == ANIMATED and scales == "mixed":
+            waves = np.stack([wave() for _ in range(3)], axis=1)
+            samples[:, track, 8:11] = (1.0 + rng.uniform(0.01, 0.03) * waves).astype(np.float32)
+    return samples
+
+
+def far_roots_clip(seed, num_samples, num_tracks, factor, offset=0, scales="mixed", parents=None):
+    """mixed_clip() with the translation of every track that has no parent in `parents` (tree(seed, T) when None) multiplied by
+    float32(factor): at 60 000 and more a root's translation cannot be held to 0.01 by anything but the last rates of the table, the
+    raw samples among them. A track that HAS a parent keeps its translation: a long lever below a rotating parent turns the parent's
+    last bit into an error above the precision, and the reference's own search is no longer stable under one ulp."""
+    samples = mixed_clip(seed, num_samples, num_tracks, offset, scales=scales)
+    parents = tree(seed, num_tracks) if parents is None else np.asarray(parents).astype(np.uint32)[:num_tracks]
+    roots = np.flatnonzero(parents >= num_tracks)
+    samples[:, roots, 4:7] = (samples[:, roots, 4:7].astype(np.float64) * float(np.float32(factor))).astype(np.float32)
+    return samples
+
+
+def raw_scale_clip(seed, num_samples):
+    """(samples [S, 2, 12], parents, track_precisions): a root and a leaf, built by hand for ONE event of the bit rate search that no drawn
+    input reaches -- its last pass meeting a link whose rotation and translation rates are equal and below 24 while its scale rate is a
+    real 24 (the pass raises the smallest rate first, so a scale it raised itself reaches 24 last). Both precisions are 1e-9.
+    The root: every rotation is (0, 0, 0, 1) or (1, 0, 0, 0) and every translation component 0 or one value, which every rate gives
+    back exactly; its scales are uniform in [0, 1), whose small values no rate below the raw one gives back to 1e-9: the local phase
+    ends on (1, 1, 24) with an error of 0. The leaf: a free rotation, which dropping w alone moves by more than 1e-9, nothing else
+    animated: it cannot be met, and the last pass walks up to the root. Needs more than two samples (two samples are exact at rate 1).
+    What it holds is that the branch is WALKED and the table is still the restatement's: the root's rotation and translation are exact
+    at every rate, so raising either first ends on the same rates, and a kernel that compared the scale with `> 24` gives these bytes too."""
+    rng = np.random.default_rng(700 + seed)
+    samples = np.tile(IDENTITY, (num_samples, 2, 1))
+    pick = rng.integers(0, 2, size=num_samples)
+    pick[0:2] = (0, 1)
+    samples[:, 0, 0:4] = np.array([[0, 0, 0, 1], [1, 0, 0, 0]], dtype=np.float32)[pick]
+    samples[:, 0, 4:7] = pick[:, None] * rng.uniform(0.1, 0.5, size=3).astype(np.float32)
+    samples[:, 0, 8:11] = rng.uniform(0.0, 1.0, size=(num_samples, 3))
+    samples[:, 1, 0:4] = lossy.raw_restatement.unit_quaternions(rng, (num_samples,))
+    return samples, np.array([NO_PARENT, 0], dtype=np.uint32), np.full(2, 1.0e-9, dtype=np.float32)
+
+
 def triples_of(compressed):
     """the set of (rotation, translation, scale) type triples of a Compressed"""
     return {tuple(int(kind) for kind in compressed.types[:, b]) for b in range(compressed.types.shape[1])}
