@@ -1,11 +1,13 @@
 // host_transform_compress.inl -- part of aclhip.hip (one translation unit; included there behind host_scalar_compress.inl, not compiled on its own).
 // Host side of the three transform compressors, aclhip_compress_raw_tracks_batch (kernels_transform_compress.inl),
 // aclhip_compress_tracks_batch (kernels_tracks_compress.inl) and aclhip_compress_tracks_variable_batch (kernels_variable_compress.inl),
-// and of the bit rate search, aclhip_find_bit_rates_batch (kernels_bit_rate_search.inl), and of the last three with the error metric as
+// and of the bit rate search, aclhip_find_bit_rates_batch (kernels_bit_rate_search.inl) and, with every level,
+// aclhip_find_bit_rates_level_batch, and of the last three with the error metric as
 // an argument (the _metric entry points: the metric is one more thing a call says of itself, and picks the instantiations of its phases):
 // the sizes a caller needs, and one argument check, one workspace layout and one launch record for all -- the raw call is the drop-w
 // call with the full formats, no shell and its own words; the variable call is it with its own kernels behind the shell, its rate
-// table and three more parts of the workspace; the search is the variable call without rows, its table written, and four more parts.
+// table and three more parts of the workspace; the search is the variable call without rows, its table written, and four more parts;
+// the search with the levels is the search with its own words, one more part and one more launch.
 // What a call says of itself is its transform_compress_kind; what the smaller descs, the rate table, the written and the read ranges,
 // the variable launch record and the grid of a wave per segment are is stated once each, in front of the check and of the calls.
 // What they share with the scalar compressor -- the cap of a size, the common checks, the launches' shapes, their front and their list
@@ -31,13 +33,13 @@ namespace
 	constexpr uint32_t k_transform_compress_flags = ACLHIP_COMPRESS_OPTIMIZE_LOOPS | ACLHIP_COMPRESS_INCLUDE_PARENT_TRACK_INDICES | ACLHIP_COMPRESS_INCLUDE_TRACK_DESCRIPTIONS;
 
 	// What an entry point says of itself: the word its desc goes by in the messages, the knob of its phases, whether its workspace holds shells and the
-	// segments it holds the variable call's parts for (0: none), whether it writes blob rows and whether its workspace holds the
-	// search's parts; and the error metric its decisions are taken by (an aclhip_error_metric: the entry points without one say
+	// segments it holds the variable call's parts for (0: none), whether it writes blob rows, whether its workspace holds the
+	// search's parts and whether the search takes every level; and the error metric its decisions are taken by (an aclhip_error_metric: the entry points without one say
 	// ACLHIP_METRIC_QVVF). The rest of what tells the raw and the drop-w call apart is in the desc: the formats and the shell metadata, 0
 	// for the raw call.
 	struct transform_compress_kind
 	{
-		const char* name; const char* phases_knob; bool with_shells; uint32_t max_segments = 0; bool with_rows = true; bool with_search = false; uint32_t metric = ACLHIP_METRIC_QVVF;
+		const char* name; const char* phases_knob; bool with_shells; uint32_t max_segments = 0; bool with_rows = true; bool with_search = false; bool with_levels = false; uint32_t metric = ACLHIP_METRIC_QVVF;
 		transform_compress_kind with_metric(uint32_t error_metric) const { transform_compress_kind kind = *this; kind.metric = error_metric; return kind; }
 	};
 
@@ -48,17 +50,19 @@ namespace
 	const transform_compress_kind k_tracks_compress_kind = { "tracks compress", "ACLHIP_TRACKS_COMPRESS_PHASES", true };
 	transform_compress_kind variable_compress_kind_of(uint32_t max_samples) { return { "variable compress", "ACLHIP_VARIABLE_COMPRESS_PHASES", true, variable_max_segments_of(max_samples) }; }
 	transform_compress_kind bit_rate_search_kind_of(uint32_t max_samples) { return { "bit rate search", "ACLHIP_FIND_BIT_RATES_PHASES", true, variable_max_segments_of(max_samples), false, true }; }
+	transform_compress_kind bit_rate_level_search_kind_of(uint32_t max_samples) { return { "bit rate level search", "ACLHIP_FIND_BIT_RATES_LEVEL_PHASES", true, variable_max_segments_of(max_samples), false, true, true }; }
 
 	// The workspace: where each part begins and where the last one ends, each part rounded up to 16 bytes (128 bits wide: see
 	// aclhip_scalar_compress_workspace_bytes). The raw call has the first three parts, aclhip_compress_tracks_batch the shells
 	// ({ local shell distance, precision } per instance and track) behind them, aclhip_compress_tracks_variable_batch behind those the
 	// clip ranges (18 floats per instance and track) and, per instance and segment of max_samples (max_segments; 0: none of the three),
 	// a variable_segment and the prefix sums (a dword per sub-track); aclhip_find_bit_rates_batch behind those, per instance and segment,
-	// a search_segment and, per track, the segment range (18 floats), the segment's shell and an entry of the chain under work. The
-	// size functions and the launch record both read it.
+	// a search_segment and, per track, the segment range (18 floats), the segment's shell and an entry of the chain under work;
+	// aclhip_find_bit_rates_level_batch behind those, per instance, segment and track, the memo of its object phase (three dwords: what
+	// increasing that link of the chain by 1, 2 and 3 gives in this round). The size functions and the launch record both read it.
 	struct transform_workspace_layout
 	{
-		unsigned __int128 instances = 0, track_flags, animated, shells, clip_ranges, segments, prefix, search_segments, segment_ranges, segment_shells, chains, total;
+		unsigned __int128 instances = 0, track_flags, animated, shells, clip_ranges, segments, prefix, search_segments, segment_ranges, segment_shells, chains, memo, total;
 		transform_workspace_layout(uint32_t num_instances, uint32_t max_tracks, const transform_compress_kind& kind)
 		{
 			const auto part = [](unsigned __int128 bytes) { return (bytes + 15u) & ~(unsigned __int128)15; };
@@ -73,7 +77,8 @@ namespace
 			segment_ranges = search_segments + (kind.with_search ? part(n * max_segments * sizeof(search_segment)) : 0);
 			segment_shells = segment_ranges + (kind.with_search ? part(n * max_segments * max_tracks * k_search_segment_floats * sizeof(float)) : 0);
 			chains = segment_shells + (kind.with_search ? part(n * max_segments * max_tracks * sizeof(float2)) : 0);
-			total = chains + (kind.with_search ? part(n * max_segments * max_tracks * sizeof(uint16_t)) : 0);
+			memo = chains + (kind.with_search ? part(n * max_segments * max_tracks * sizeof(uint16_t)) : 0);
+			total = memo + (kind.with_levels ? part(n * max_segments * max_tracks * 3u * sizeof(uint32_t)) : 0);
 		}
 	};
 	uint64_t transform_workspace_bytes(uint32_t num_instances, uint32_t max_tracks, const transform_compress_kind& kind)
@@ -136,6 +141,11 @@ extern "C" uint64_t aclhip_find_bit_rates_workspace_bytes(uint32_t num_instances
 	return transform_workspace_bytes(num_instances, max_tracks, bit_rate_search_kind_of(max_samples));
 }
 
+extern "C" uint64_t aclhip_find_bit_rates_level_workspace_bytes(uint32_t num_instances, uint32_t max_tracks, uint32_t max_samples)
+{
+	return transform_workspace_bytes(num_instances, max_tracks, bit_rate_level_search_kind_of(max_samples));
+}
+
 namespace
 {
 	// The kernels between the shell and the hash, per rotation format: quatf_full (the raw call's: no metric enters it), quatf_drop_w_full
@@ -149,16 +159,18 @@ namespace
 	};
 
 	// The kernels that decide by the error metric, per metric: the shell (its vote) and the variable call's analysis, which the drop-w
-	// call, the variable call and the search share, and the search's two phases
+	// call, the variable call and the search share, and the search's two phases, the object phase without and with the levels
 	struct metric_kernels
 	{
 		void (*shell)(transform_compress_launch); void (*variable_analyze)(variable_compress_launch);
-		void (*search_local)(bit_rate_search_launch); void (*search_object)(bit_rate_search_launch);
+		void (*search_local)(bit_rate_search_launch); void (*search_object)(bit_rate_search_launch); void (*search_object_levels)(bit_rate_search_levels_launch);
 	};
 	const metric_kernels k_metric_kernels[2] =
 	{
-		{ tracks_compress_shell_kernel<k_metric_qvvf>, variable_compress_analyze_kernel<k_metric_qvvf>, bit_rate_search_local_kernel<k_metric_qvvf>, bit_rate_search_object_kernel<k_metric_qvvf> },
-		{ tracks_compress_shell_kernel<k_metric_matrix>, variable_compress_analyze_kernel<k_metric_matrix>, bit_rate_search_local_kernel<k_metric_matrix>, bit_rate_search_object_kernel<k_metric_matrix> },
+		{ tracks_compress_shell_kernel<k_metric_qvvf>, variable_compress_analyze_kernel<k_metric_qvvf>, bit_rate_search_local_kernel<k_metric_qvvf>,
+			bit_rate_search_object_kernel<k_metric_qvvf>, bit_rate_search_object_kernel<k_metric_qvvf, true> },
+		{ tracks_compress_shell_kernel<k_metric_matrix>, variable_compress_analyze_kernel<k_metric_matrix>, bit_rate_search_local_kernel<k_metric_matrix>,
+			bit_rate_search_object_kernel<k_metric_matrix>, bit_rate_search_object_kernel<k_metric_matrix, true> },
 	};
 
 	// A smaller desc as the drop-w call's, which the shared check and the launch record read: the rotation format the call stands for
@@ -444,22 +456,29 @@ extern "C" aclhip_status aclhip_compress_tracks_variable_batch(aclhip_context* c
 	return aclhip_compress_tracks_variable_metric_batch(context, raws, num_instances, desc, blobs, blob_stride_bytes, results, ACLHIP_METRIC_QVVF, stream_handle);
 }
 
-// The search: the shared check over its desc as the drop-w one, like the variable call; no rows; the table on the written side.
-extern "C" aclhip_status aclhip_find_bit_rates_metric_batch(aclhip_context* context, const aclhip_raw_tracks* raws, uint32_t num_instances,
-	const aclhip_find_bit_rates_desc* desc_or_null, uint8_t* bit_rates, uint64_t instance_stride, uint64_t segment_stride, aclhip_compress_result* results, uint32_t metric,
-	void* stream_handle)
+// The search, of either kind: the shared check over its desc as the drop-w one, like the variable call; no rows; the table on the
+// written side. The kind with the levels takes every level, has its memo in the workspace, and launches the level per instance in
+// front of its own object phase.
+namespace
+{
+aclhip_status find_bit_rates(aclhip_context* context, const transform_compress_kind& kind, const aclhip_raw_tracks* raws, uint32_t num_instances,
+	const aclhip_find_bit_rates_desc* desc_or_null, uint8_t* bit_rates, uint64_t instance_stride, uint64_t segment_stride, aclhip_compress_result* results, void* stream_handle)
 {
 	const aclhip_find_bit_rates_desc& desc = desc_or_null != nullptr ? *desc_or_null : aclhip_find_bit_rates_desc{};
 	const aclhip_compress_tracks_desc as_tracks = compress_tracks_desc_of(desc, k_rotation_quatf_drop_w_full, desc.reserved_word);
-	const transform_compress_kind kind = bit_rate_search_kind_of(desc.max_samples).with_metric(metric);
 	const uint32_t max_segments = kind.max_segments;
 	if (const aclhip_status status = check_transform_compress(context, kind, raws, num_instances, desc_or_null != nullptr ? &as_tracks : nullptr, nullptr, 0, results); status != ACLHIP_OK)
 		return status;
 	if (desc.max_samples == 0)
-		return fail(context, ACLHIP_ERROR_INVALID_ARGUMENT, "a bit rate search desc of 0 max_samples");
-	if (desc.level == 3 || desc.level == 4)
+		return fail(context, ACLHIP_ERROR_INVALID_ARGUMENT, "a %s desc of 0 max_samples", kind.name);
+	if (kind.with_levels)
+	{
+		if (desc.level > 4 && desc.level != ACLHIP_LEVEL_AUTOMATIC)
+			return fail(context, ACLHIP_ERROR_INVALID_ARGUMENT, "a level of %u: 0 (lowest), 1 (low), 2 (medium), 3 (high), 4 (highest) or %u (automatic)", desc.level, ACLHIP_LEVEL_AUTOMATIC);
+	}
+	else if (desc.level == 3 || desc.level == 4)
 		return fail(context, ACLHIP_ERROR_INVALID_ARGUMENT, "level %u (%s) is not built: 0 (lowest), 1 (low) and 2 (medium) are", desc.level, desc.level == 3 ? "high" : "highest");
-	if (desc.level > 4)
+	else if (desc.level > 4)
 		return fail(context, ACLHIP_ERROR_INVALID_ARGUMENT, "a level of %u: 0 (lowest), 1 (low) or 2 (medium)", desc.level);
 	if (bit_rates == nullptr)
 		return fail(context, ACLHIP_ERROR_INVALID_ARGUMENT, "null bit rate table");
@@ -494,6 +513,7 @@ extern "C" aclhip_status aclhip_find_bit_rates_metric_batch(aclhip_context* cont
 		launch.segment_ranges = reinterpret_cast<float*>(workspace + uint64_t(layout.segment_ranges));
 		launch.segment_shells = reinterpret_cast<float2*>(workspace + uint64_t(layout.segment_shells));
 		launch.chains = reinterpret_cast<uint16_t*>(workspace + uint64_t(layout.chains));
+		const bit_rate_search_levels_launch levels_launch = { launch, reinterpret_cast<uint32_t*>(workspace + uint64_t(layout.memo)), desc.level };
 
 		// a wave per (instance, segment), and for the local phase per (instance, segment, track), in turn where the grid would not hold them
 		const uint32_t segment_blocks = compress_segment_blocks_of(num_instances, max_segments);
@@ -507,8 +527,33 @@ extern "C" aclhip_status aclhip_find_bit_rates_metric_batch(aclhip_context* cont
 			{ k_metric_kernels[kind.metric].search_local, dim3(track_blocks), dim3(k_wave_size), launch },
 			{ k_metric_kernels[kind.metric].search_object, dim3(segment_blocks), block, launch },
 		};
-		return launch_compress_phases(context, stream, shape.phases, phases, 5);
+		if (!kind.with_levels)
+			return launch_compress_phases(context, stream, shape.phases, phases, 5);
+		const compress_phase level_phases[] =
+		{
+			phases[0], phases[1], phases[2], phases[3],
+			{ bit_rate_search_level_kernel, dim3(shape.instance_blocks), block, levels_launch },
+			{ k_metric_kernels[kind.metric].search_object_levels, dim3(segment_blocks), block, levels_launch },
+		};
+		return launch_compress_phases(context, stream, shape.phases, level_phases, 6);
 	});
+}
+}
+
+extern "C" aclhip_status aclhip_find_bit_rates_metric_batch(aclhip_context* context, const aclhip_raw_tracks* raws, uint32_t num_instances,
+	const aclhip_find_bit_rates_desc* desc, uint8_t* bit_rates, uint64_t instance_stride, uint64_t segment_stride, aclhip_compress_result* results, uint32_t metric,
+	void* stream_handle)
+{
+	return find_bit_rates(context, bit_rate_search_kind_of(desc != nullptr ? desc->max_samples : 0).with_metric(metric), raws, num_instances, desc, bit_rates, instance_stride, segment_stride,
+		results, stream_handle);
+}
+
+extern "C" aclhip_status aclhip_find_bit_rates_level_batch(aclhip_context* context, const aclhip_raw_tracks* raws, uint32_t num_instances,
+	const aclhip_find_bit_rates_desc* desc, uint8_t* bit_rates, uint64_t instance_stride, uint64_t segment_stride, aclhip_compress_result* results, uint32_t metric,
+	void* stream_handle)
+{
+	return find_bit_rates(context, bit_rate_level_search_kind_of(desc != nullptr ? desc->max_samples : 0).with_metric(metric), raws, num_instances, desc, bit_rates, instance_stride, segment_stride,
+		results, stream_handle);
 }
 
 extern "C" aclhip_status aclhip_find_bit_rates_batch(aclhip_context* context, const aclhip_raw_tracks* raws, uint32_t num_instances,

@@ -17,9 +17,13 @@
 // include/aclhip.h states the definition (S0 to S4): fp32, one IEEE operation at a time. No atomics besides the refusal counter and no
 // zero fill: the same bytes on every run. The rates live in the caller's table between the last two launches and while the object
 // phase works: every lane stores the same four bytes and reads back what it stored itself.
+// aclhip_find_bit_rates_level_batch (the levels high and highest, and automatic) is these with one small launch in front of the
+// object phase, bit_rate_search_level_kernel (the level per instance), and the object kernel's second instantiation, kLevels: its
+// first loop tries the wider shapes of increments over the chain. The kernels of the other two calls are the instantiations without.
 
 	constexpr uint32_t k_search_num_rates = 25;					// 0 .. 24
 	constexpr uint32_t k_search_invalid_rates = 0x00FFFFFFu;		// { 255, 255, 255, 0 }: no sub-track of the track is animated
+	constexpr uint32_t k_search_memo_unset = 0xFFFFFFFFu;		// (no packed rates: their fourth byte is 0)
 	constexpr uint32_t k_search_segment_floats = 18;			// per track: pmin xyz, pext xyz of the rotation, the translation, the scale
 
 	// ---- the permutation lists ---------------------------------------------------------------------------------------------------------------
@@ -72,6 +76,17 @@
 		float2* segment_shells;					// [num_instances][max_segments][max_tracks] { local shell distance, precision } of S0
 		uint16_t* chains;						// [num_instances][max_segments][max_tracks]: the chain of the track under work, from the root
 	};
+
+	// and what aclhip_find_bit_rates_level_batch has besides: a record of its own, for its two kernels alone (the kernel arguments of
+	// the others stay as they are)
+	struct bit_rate_search_levels_launch
+	{
+		bit_rate_search_launch search;
+		uint32_t* memo;							// [num_instances][max_segments][max_tracks][3]: per link of the chain under work, increase_bone_bit_rate by 1, 2 and 3 of this round
+		uint32_t level;							// an acl::compression_level8: 0 .. 4, or ACLHIP_LEVEL_AUTOMATIC
+	};
+	__device__ __forceinline__ const bit_rate_search_launch& search_launch_of(const bit_rate_search_launch& launch) { return launch; }
+	__device__ __forceinline__ const bit_rate_search_launch& search_launch_of(const bit_rate_search_levels_launch& launch) { return launch.search; }
 
 	// What S0 and S1 read of an (instance, segment)
 	struct search_source
@@ -509,6 +524,48 @@
 		}
 	}
 
+	// ---- per instance: the level that is searched (aclhip_find_bit_rates_level_batch) ---------------------------------------------------------------
+	// Behind the segment launch, which has written the instance's status: an instance that is served gets its level, 0 .. 4, in the second
+	// word of its result, where the object phase reads it; any other keeps the 0. ACLHIP_LEVEL_AUTOMATIC is find_best_compression_level
+	// (compress.transform.impl.h:114-136) per instance: medium above 500 samples -- the count as registered: the reference resolves the
+	// level before its looping vote --, else by the longest chain in bones from a root to a leaf over the instance's tracks (lanes <->
+	// tracks; a parent lies in front of its child, or the instance was refused: every walk ends): below 18 highest, below 25 high.
+	__global__ __launch_bounds__(k_compress_waves_per_block * k_wave_size) void bit_rate_search_level_kernel(bit_rate_search_levels_launch launch)
+	{
+		const transform_compress_launch& base = launch.search.variable.base;
+		const uint32_t lane = threadIdx.x & (k_wave_size - 1);
+		const uint32_t instance = blockIdx.x * k_compress_waves_per_block + __builtin_amdgcn_readfirstlane(threadIdx.x / k_wave_size);
+		if (instance >= base.num_instances || base.results[instance].x != ACLHIP_COMPRESS_OK)
+			return;
+		uint32_t level = launch.level;
+		if (level == ACLHIP_LEVEL_AUTOMATIC)
+		{
+			const uint32_t handle = as_constant(base.raws)[instance];
+			const device_raw_tracks raw = load_raw_tracks_fields(base.arrays, handle < base.num_arrays ? handle : 0);
+			level = 2;
+			if (raw.num_samples <= 500)
+			{
+				uint32_t longest = 0;
+				for (uint32_t track = lane; track < raw.num_tracks; track += k_wave_size)
+				{
+					uint32_t links = 1;
+					for (uint32_t up = compress_track_parent(base, track, raw.num_tracks); up != ACLHIP_NO_PARENT; up = compress_track_parent(base, up, raw.num_tracks))
+						++links;
+					longest = links > longest ? links : longest;
+				}
+				#pragma unroll
+				for (int offset = int(k_wave_size) / 2; offset != 0; offset >>= 1)
+				{
+					const uint32_t other = uint32_t(__shfl_xor(int(longest), offset));
+					longest = other > longest ? other : longest;
+				}
+				level = longest < 18 ? 4u : longest < 25 ? 3u : 2u;
+			}
+		}
+		if (lane == 0)
+			base.results[instance].y = level;
+	}
+
 	// ---- per (instance, segment): the object phase -------------------------------------------------------------------------------------------------
 	// S4, loop for loop (quantize.transform.h:997-1098, 1227-1475). Every loop ends. The first one raises one rate of the chain by one in
 	// every round that goes on, and a rate stops at 24. The last pass may LOWER rates again (a link keeps the rates of its lowest error,
@@ -519,9 +576,10 @@
 	// first sample whose error is too high) and a butterfly: every decision is wave uniform. A candidate is the table with ONE track's
 	// rates replaced: nothing is copied. The first version recomputes the whole chain for every candidate. Under the matrix metric
 	// (kMetric) a segment with scale takes both chains down as 3x4 matrices, 24 floats a lane; without scale it is the qvvf walk.
-	template<uint32_t kMetric>
-	__global__ __launch_bounds__(k_compress_waves_per_block * k_wave_size) void bit_rate_search_object_kernel(bit_rate_search_launch launch)
+	template<uint32_t kMetric, bool kLevels = false>
+	__global__ __launch_bounds__(k_compress_waves_per_block * k_wave_size) void bit_rate_search_object_kernel(std::conditional_t<kLevels, bit_rate_search_levels_launch, bit_rate_search_launch> record)
 	{
+		const bit_rate_search_launch& launch = search_launch_of(record);
 		const transform_compress_launch& base = launch.variable.base;
 		const uint32_t max_segments = launch.variable.max_segments;
 		const uint32_t lane = threadIdx.x & (k_wave_size - 1);
@@ -543,6 +601,10 @@
 			uint32_t* row = reinterpret_cast<uint32_t*>(launch.table + instance * launch.instance_stride + segment * launch.segment_stride);
 			const bool has_scale = at.has_scale != 0;
 			const uint32_t sample = lane < at.count ? lane : 0u;
+			// the level that is searched: bit_rate_search_level_kernel left it in the instance's result
+			[[maybe_unused]] uint32_t level = 0;
+			if constexpr (kLevels)
+				level = __builtin_amdgcn_readfirstlane(base.results[instance].y);
 
 			search_source source;
 			source.samples = raw.samples;
@@ -555,9 +617,12 @@
 			source.multiple = variable_split_of(voted.num_out_samples).num_segments > 1;
 
 			const auto parent_of = [&](uint32_t track) -> uint32_t { return compress_track_parent(base, track, num_tracks); };
+			const uint32_t none = ACLHIP_NO_PARENT;
 
-			// S2: the object error of chain[links - 1] with the rates of `replaced` taken from `replacement`
-			const auto object_error = [&](uint32_t links, uint32_t replaced, uint32_t replacement, bool until_end) __attribute__((always_inline)) -> float
+			// S2: the object error of chain[links - 1] with the rates of `replaced` taken from `replacement` (with the levels: of up to three
+			// tracks; a place that is not used names no track)
+			const auto candidate_error = [&](uint32_t links, uint32_t replaced, uint32_t replacement, uint32_t replaced_1, uint32_t replacement_1, uint32_t replaced_2,
+				uint32_t replacement_2, bool until_end) __attribute__((always_inline)) -> float
 			{
 				float2 shell;
 				float error = 0.0f;
@@ -572,7 +637,9 @@
 						for (uint32_t link = 0; link < links; ++link)
 						{
 							const uint32_t track = chain[link];
-							const uint32_t rates = track == replaced ? replacement : row[track];
+							uint32_t rates = track == replaced ? replacement : row[track];
+							if constexpr (kLevels)
+								rates = track == replaced_1 ? replacement_1 : track == replaced_2 ? replacement_2 : rates;
 							const matrix3x4 lossy_local = matrix_from_qvv(search_lossy_local(source, track, track_flags[track], rates, sample));
 							const matrix3x4 raw_local = matrix_from_qvv(search_raw_local(source, track, at.start + sample));
 							raw_object = link == 0 ? raw_local : matrix_mul(raw_local, raw_object);
@@ -589,7 +656,9 @@
 					for (uint32_t link = 0; link < links; ++link)
 					{
 						const uint32_t track = chain[link];
-						const uint32_t rates = track == replaced ? replacement : row[track];
+						uint32_t rates = track == replaced ? replacement : row[track];
+						if constexpr (kLevels)
+							rates = track == replaced_1 ? replacement_1 : track == replaced_2 ? replacement_2 : rates;
 						const qvv lossy_local = search_lossy_local(source, track, track_flags[track], rates, sample);
 						const qvv raw_local = search_raw_local(source, track, at.start + sample);
 						raw_object = link == 0 ? raw_local : search_to_object(has_scale, raw_local, raw_object);
@@ -606,6 +675,10 @@
 				}
 				return compress_wave_max(error);
 			};
+			const auto object_error = [&](uint32_t links, uint32_t replaced, uint32_t replacement, bool until_end) __attribute__((always_inline)) -> float
+			{
+				return candidate_error(links, replaced, replacement, none, 0, none, 0, until_end);
+			};
 
 			const auto increment = [](uint32_t rate, uint32_t by) -> uint32_t
 			{
@@ -613,24 +686,25 @@
 				return rate >= k_variable_raw_rate ? rate : sum < k_variable_raw_rate ? sum : k_variable_raw_rate;
 			};
 
-			// increase_bone_bit_rate with one increment: the error is measured AT chain[link], the chain bone whose rate is being tried
-			const auto increase_bone_bit_rate = [&](uint32_t link, float old_error) -> uint32_t
+			// increase_bone_bit_rate with `by` increments (one without the levels): the error is measured AT chain[link], the chain bone
+			// whose rate is being tried
+			const auto increase_bone_bit_rate = [&](uint32_t link, uint32_t by, float old_error) -> uint32_t
 			{
 				const uint32_t track = chain[link];
 				const uint32_t rates = row[track];
 				const uint32_t rotation_rate = rates & 0xFFu, translation_rate = (rates >> 8) & 0xFFu, scale_rate = (rates >> 16) & 0xFFu;
 				uint32_t best = rates;
 				float best_error = old_error;
-				for (uint32_t rotation_increment = 0; rotation_increment <= 1; ++rotation_increment)
+				for (uint32_t rotation_increment = 0; rotation_increment <= by; ++rotation_increment)
 				{
 					const uint32_t rotation = increment(rotation_rate, rotation_increment);
-					for (uint32_t translation_increment = 0; translation_increment <= 1; ++translation_increment)
+					for (uint32_t translation_increment = 0; translation_increment <= by; ++translation_increment)
 					{
 						const uint32_t translation = increment(translation_rate, translation_increment);
-						for (uint32_t scale_increment = 0; scale_increment <= (has_scale ? 1u : 0u); ++scale_increment)
+						for (uint32_t scale_increment = 0; scale_increment <= (has_scale ? by : 0u); ++scale_increment)
 						{
 							const uint32_t scale = increment(scale_rate, scale_increment);
-							if (rotation_increment + translation_increment + scale_increment != 1)
+							if (rotation_increment + translation_increment + scale_increment != by)
 							{
 								if (scale >= k_variable_raw_rate)
 									break;
@@ -667,52 +741,221 @@
 						chain[--at_link] = uint16_t(up);
 				}
 				const float threshold = shells[track].y;
-				const uint32_t none = ACLHIP_NO_PARENT;
 
 				float error = object_error(links, none, 0, false);
 				if (error < threshold)
 					return;
 				const float initial_error = error;
-				uint32_t best_track = none, best_rates = 0;
-				while (error >= threshold)
+				if constexpr (!kLevels)
 				{
-					const float original_error = error;
-					float best_error = error;
-					// calculate_bone_permutation_error for "one increment somewhere in the chain": own track first, then toward the root
-					uint32_t found_track = none, found_rates = 0;
-					float found_error = original_error;
-					for (uint32_t link = links; link-- != 0;)
+					uint32_t best_track = none, best_rates = 0;
+					while (error >= threshold)
 					{
-						const uint32_t chain_track = chain[link];
-						const uint32_t tried = increase_bone_bit_rate(link, original_error);
-						if (tried == row[chain_track])
-							continue;
-						const float permutation_error = object_error(links, chain_track, tried, false);
-						if (permutation_error < found_error)
+						const float original_error = error;
+						float best_error = error;
+						// calculate_bone_permutation_error for "one increment somewhere in the chain": own track first, then toward the root
+						uint32_t found_track = none, found_rates = 0;
+						float found_error = original_error;
+						for (uint32_t link = links; link-- != 0;)
 						{
-							found_error = permutation_error;
-							found_track = chain_track;
-							found_rates = tried;
-							if (permutation_error < threshold)
+							const uint32_t chain_track = chain[link];
+							const uint32_t tried = increase_bone_bit_rate(link, 1, original_error);
+							if (tried == row[chain_track])
+								continue;
+							const float permutation_error = object_error(links, chain_track, tried, false);
+							if (permutation_error < found_error)
+							{
+								found_error = permutation_error;
+								found_track = chain_track;
+								found_rates = tried;
+								if (permutation_error < threshold)
+									break;
+							}
+						}
+						error = found_error;
+						if (error < best_error)
+						{
+							best_error = error;
+							best_track = found_track;
+							best_rates = found_rates;
+							if (error < threshold)
 								break;
 						}
+						if (best_error >= original_error)
+							break;				// no progress
+						error = best_error;
+						row[best_track] = best_rates;
 					}
-					error = found_error;
-					if (error < best_error)
-					{
-						best_error = error;
-						best_track = found_track;
-						best_rates = found_rates;
-						if (error < threshold)
-							break;
-					}
-					if (best_error >= original_error)
-						break;				// no progress
-					error = best_error;
-					row[best_track] = best_rates;
+					if (error < initial_error)
+						row[best_track] = best_rates;
 				}
-				if (error < initial_error)
-					row[best_track] = best_rates;
+				else
+				{
+					// The first loop with the levels (quantize.transform.h:1250-1377). A round's bar is original_error throughout and best_error is
+					// carried across its calls of calculate_bone_permutation_error, one per SHAPE of increments over the chain:
+					//   every level  {1} on one link (the loop above)
+					//   >= high      {2} on one link; with more than one link {1,1} on two
+					//   >= highest   {3} on one link; with more than one link {2,1}; with more than two {1,1,1}
+					// After a call: error < best_error keeps that permutation's rates, and error < threshold leaves the round. A shape's
+					// arrangements come in std::next_permutation order over the chain array, root first -- the own track changes fastest --,
+					// which the positions a > b > c below count down: no array is permuted. What to keep in mind:
+					//   1. {2,1} STARTS at [..., 2, 1], parent + 2 and own + 1, which is not its smallest arrangement: next_permutation runs
+					//      from there to the end, so [..., 1, 2] is never tried and a chain of two links tries exactly one arrangement. Every
+					//      other shape starts at its smallest arrangement and visits all of them.
+					//   2. increase_bone_bit_rate(link, n) enumerates the (rotation, translation, scale) increments that sum to n with the
+					//      reference's break and continue rules at rate 24; without scale the scale's is 0. It measures at the chain bone
+					//      whose rate is tried, not at the track under work, and its bar is old_error, the round's original_error.
+					//   3. A permutation counts only if one of its links changed its rates (is_permutation_valid): an invalid one is skipped
+					//      without measuring.
+					//   4. Inside one call a permutation below the threshold ends that call at once.
+					//   5. A candidate is the table with up to three tracks' rates replaced: nothing is copied.
+					// THE MEMO. Within a round neither the rates nor original_error change, so increase_bone_bit_rate(link, n) depends on (link, n)
+					// alone. The reference recomputes it for every arrangement; here it is computed when an arrangement first asks for it and
+					// kept, three dwords per link (k_search_memo_unset: not asked yet), in the workspace: every lane stores the same dword and
+					// reads its own. No decision sees the difference. Every loop ends: a shape has finitely many arrangements, each visited
+					// once; a round that goes on has lowered the error by raising at least one rate, and rates stop at 24.
+					uint32_t* memo = record.memo + wave * base.max_tracks * 3u;
+					uint32_t best_tracks[3] = { none, none, none }, best_rates[3] = { 0, 0, 0 };
+					const auto apply_best = [&]()
+					{
+						#pragma unroll
+						for (uint32_t k = 0; k < 3; ++k)
+							if (best_tracks[k] != none)
+								row[best_tracks[k]] = best_rates[k];
+					};
+					while (error >= threshold)
+					{
+						const float original_error = error;
+						float best_error = error;
+						for (uint32_t index = 0; index < links * 3u; ++index)
+							memo[index] = k_search_memo_unset;
+						bool met = false;
+						// the shapes in the reference's order: {1}, {2}, {1,1}, {3}, {2,1}, {1,1,1}
+						for (uint32_t shape = 0; shape < 6 && !met; ++shape)
+						{
+							const uint32_t shape_links = shape == 2 || shape == 4 ? 2u : shape == 5 ? 3u : 1u;
+							if (level < (shape == 0 ? 0u : shape < 3 ? 3u : 4u) || links < shape_links)
+								continue;
+							// calculate_bone_permutation_error. The links that carry an increment are a > b > c (the root is link 0); of {2,1}
+							// b, the link nearer the root, carries the 2 and a the 1 while `parent_two`, else b the 1 and a the 2.
+							uint32_t a = links - 1u, b = links - 2u, c = links - 3u;
+							bool parent_two = shape == 4;		// (trap 1: the start)
+							uint32_t found_tracks[3] = { none, none, none }, found_rates[3] = { 0, 0, 0 };
+							float found_error = original_error;
+							for (;;)
+							{
+								const uint32_t increment_a = shape == 1 ? 2u : shape == 3 ? 3u : shape == 4 && !parent_two ? 2u : 1u;
+								const uint32_t increment_b = shape_links < 2 ? 0u : shape == 4 && parent_two ? 2u : 1u;
+								const uint32_t increment_c = shape_links < 3 ? 0u : 1u;
+								// what the memo lacks of this arrangement, root first
+								#pragma nounroll
+								for (uint32_t k = 3; k-- != 0;)
+								{
+									const uint32_t link = k == 0 ? a : k == 1 ? b : c, by = k == 0 ? increment_a : k == 1 ? increment_b : increment_c;
+									if (by == 0)
+										continue;
+									if (__builtin_amdgcn_readfirstlane(memo[link * 3u + by - 1u]) == k_search_memo_unset)
+										memo[link * 3u + by - 1u] = increase_bone_bit_rate(link, by, original_error);
+								}
+								uint32_t tried_tracks[3] = { chain[a], none, none }, tried_rates[3] = { memo[a * 3u + increment_a - 1u], 0, 0 };
+								if (increment_b != 0)
+								{
+									tried_tracks[1] = chain[b];
+									tried_rates[1] = memo[b * 3u + increment_b - 1u];
+								}
+								if (increment_c != 0)
+								{
+									tried_tracks[2] = chain[c];
+									tried_rates[2] = memo[c * 3u + increment_c - 1u];
+								}
+								bool valid = false;
+								#pragma unroll
+								for (uint32_t k = 0; k < 3; ++k)
+									valid = valid || (tried_tracks[k] != none && tried_rates[k] != row[tried_tracks[k] != none ? tried_tracks[k] : 0u]);
+								if (__builtin_amdgcn_readfirstlane(uint32_t(valid)) != 0)
+								{
+									const float permutation_error = candidate_error(links, tried_tracks[0], tried_rates[0], tried_tracks[1], tried_rates[1], tried_tracks[2], tried_rates[2], false);
+									if (permutation_error < found_error)
+									{
+										found_error = permutation_error;
+										#pragma unroll
+										for (uint32_t k = 0; k < 3; ++k)
+										{
+											found_tracks[k] = tried_tracks[k];
+											found_rates[k] = tried_rates[k];
+										}
+										if (permutation_error < threshold)
+											break;
+									}
+								}
+								// the next arrangement: the lowest link steps toward the one above it, then that one steps and the lower ones start
+								// again at the own track's end; {2,1} goes through "b carries the 1" before "b carries the 2" at every b but the first
+								if (shape_links == 1)
+								{
+									if (a == 0)
+										break;
+									--a;
+								}
+								else if (shape_links == 2)
+								{
+									if (a > b + 1u)
+										--a;
+									else if (shape == 4 && !parent_two)
+									{
+										parent_two = true;
+										a = links - 1u;
+									}
+									else if (b == 0)
+										break;
+									else
+									{
+										--b;
+										a = links - 1u;
+										parent_two = false;
+									}
+								}
+								else
+								{
+									if (a > b + 1u)
+										--a;
+									else if (b > c + 1u)
+									{
+										--b;
+										a = links - 1u;
+									}
+									else if (c == 0)
+										break;
+									else
+									{
+										--c;
+										b = links - 2u;
+										a = links - 1u;
+									}
+								}
+							}
+							error = found_error;
+							if (error < best_error)
+							{
+								best_error = error;
+								#pragma unroll
+								for (uint32_t k = 0; k < 3; ++k)
+								{
+									best_tracks[k] = found_tracks[k];
+									best_rates[k] = found_rates[k];
+								}
+								met = error < threshold;
+							}
+						}
+						if (met)
+							break;
+						if (best_error >= original_error)
+							break;				// no progress
+						error = best_error;
+						apply_best();
+					}
+					if (error < initial_error)
+						apply_best();
+				}
 
 				// the error remains too high: from child to parent, increase indiscriminately and keep the best
 				error = object_error(links, none, 0, true);

@@ -64,6 +64,7 @@ EXPORTED_SYMBOLS = [
     "aclhip_variable_compress_num_segments", "aclhip_variable_compress_bound", "aclhip_compress_variable_workspace_bytes", "aclhip_compress_tracks_variable_batch",
     "aclhip_find_bit_rates_workspace_bytes", "aclhip_find_bit_rates_batch",
     "aclhip_compress_tracks_metric_batch", "aclhip_compress_tracks_variable_metric_batch", "aclhip_find_bit_rates_metric_batch",
+    "aclhip_find_bit_rates_level_workspace_bytes", "aclhip_find_bit_rates_level_batch",
 ]
 
 
@@ -307,7 +308,8 @@ class FindBitRatesDesc(ctypes.Structure):
     ]
 
 
-COMPRESSION_LEVELS = {"lowest": 0, "low": 1, "medium": 2, "high": 3, "highest": 4}          # acl::compression_level8 (aclhip_find_bit_rates_desc::level)
+COMPRESSION_LEVELS = {"lowest": 0, "low": 1, "medium": 2, "high": 3, "highest": 4, "automatic": 100}     # acl::compression_level8 (aclhip_find_bit_rates_desc::level)
+LEVEL_AUTOMATIC = 100                   # ACLHIP_LEVEL_AUTOMATIC: aclhip_find_bit_rates_level_batch alone takes it, and the levels 3 and 4
 ROTATION_QUATF_FULL, ROTATION_QUATF_DROP_W_FULL = 0, 2                                      # acl::rotation_format8 (aclhip_compress_tracks_desc::rotation_format)
 VECTOR_VECTOR3F_FULL = 0                                                                    # acl::vector_format8
 COMPRESS_OPTIMIZE_LOOPS = 1                                                                 # ACLHIP_COMPRESS_OPTIMIZE_LOOPS
@@ -572,6 +574,9 @@ def load_library():
     lib.aclhip_compress_tracks_metric_batch.argtypes = [vp, vp, u32, ctypes.POINTER(CompressTracksDesc), vp, u64, vp, u32, vp]
     lib.aclhip_compress_tracks_variable_metric_batch.argtypes = [vp, vp, u32, ctypes.POINTER(CompressVariableDesc), vp, u64, vp, u32, vp]
     lib.aclhip_find_bit_rates_metric_batch.argtypes = [vp, vp, u32, ctypes.POINTER(FindBitRatesDesc), vp, u64, u64, vp, u32, vp]
+    lib.aclhip_find_bit_rates_level_workspace_bytes.argtypes = [u32, u32, u32]
+    lib.aclhip_find_bit_rates_level_workspace_bytes.restype = u64
+    lib.aclhip_find_bit_rates_level_batch.argtypes = [vp, vp, u32, ctypes.POINTER(FindBitRatesDesc), vp, u64, u64, vp, u32, vp]
     _lib = lib
     return lib
 
@@ -1246,6 +1251,12 @@ class Context:
         """aclhip_find_bit_rates_metric_batch: find_bit_rates_batch with the error metric the search optimises as an argument."""
         self._check(self._lib.aclhip_find_bit_rates_metric_batch(self._handle, raws_ptr, num_instances, ctypes.byref(desc) if desc is not None else None,
                                                                  bit_rates_ptr, instance_stride, segment_stride, results_ptr, int(metric) & 0xFFFFFFFF, stream))
+
+    def find_bit_rates_level_batch(self, raws_ptr, num_instances, desc, bit_rates_ptr, instance_stride, segment_stride, results_ptr, metric=ERROR_METRIC_QVVF, stream=None):
+        """aclhip_find_bit_rates_level_batch: find_bit_rates_metric_batch at every level -- desc.level 0 to 4 or LEVEL_AUTOMATIC --; its
+        workspace is find_bit_rates_level_workspace_bytes, and the second word of an instance's result is the level that was searched."""
+        self._check(self._lib.aclhip_find_bit_rates_level_batch(self._handle, raws_ptr, num_instances, ctypes.byref(desc) if desc is not None else None,
+                                                                bit_rates_ptr, instance_stride, segment_stride, results_ptr, int(metric) & 0xFFFFFFFF, stream))
 
     def compress_tracks_batch(self, raws_ptr, num_instances, desc, blobs_ptr, blob_stride_bytes, results_ptr, stream=None):
         """aclhip_compress_tracks_batch: compress_track_list with quatf_full or quatf_drop_w_full rotations (the rigid shell, the looping vote,
@@ -1958,16 +1969,24 @@ def find_bit_rates_workspace_bytes(num_instances, max_tracks, max_samples):
     return int(load_library().aclhip_find_bit_rates_workspace_bytes(int(num_instances), int(max_tracks), int(max_samples)))
 
 
+def find_bit_rates_level_workspace_bytes(num_instances, max_tracks, max_samples):
+    """aclhip_find_bit_rates_level_workspace_bytes (host only)"""
+    return int(load_library().aclhip_find_bit_rates_level_workspace_bytes(int(num_instances), int(max_tracks), int(max_samples)))
+
+
 def _find_bit_rates(ctx, handles, infos, level, flags, default_pose, parents, precision, shell_distance, track_precisions, track_shell_distances, tables=None,
                     metric=ERROR_METRIC_QVVF):
     """The search over `handles` into a zero-filled device table uint8 [instances, segments, tracks, 4] of the largest array's segments
-    and tracks: (the table, still on the device, and the results as a host array [instances, 2]). Synchronous."""
+    and tracks: (the table, still on the device, and the results as a host array [instances, 2]). The levels lowest to medium go
+    through aclhip_find_bit_rates_batch or its _metric form, as before; high, highest and automatic through
+    aclhip_find_bit_rates_level_batch, whose results carry the level that was searched. Synchronous."""
     import torch
     device = torch.device("cuda", ctx.device_index)
     desc = FindBitRatesDesc()
     if level not in COMPRESSION_LEVELS and level not in COMPRESSION_LEVELS.values():
-        raise ValueError(f"a compression level of {level!r}: one of {sorted(COMPRESSION_LEVELS, key=COMPRESSION_LEVELS.get)} or 0 to 4")
+        raise ValueError(f"a compression level of {level!r}: one of {sorted(COMPRESSION_LEVELS, key=COMPRESSION_LEVELS.get)}, 0 to 4 or {LEVEL_AUTOMATIC}")
     desc.level = COMPRESSION_LEVELS.get(level, level)
+    with_levels = desc.level > COMPRESSION_LEVELS["medium"]
     desc.flags, desc.precision, desc.shell_distance = flags, float(precision), float(shell_distance)
     desc.max_tracks = max(int(info.num_tracks) for info in infos)
     desc.max_samples = max(int(info.num_samples) for info in infos)
@@ -1979,18 +1998,25 @@ def _find_bit_rates(ctx, handles, infos, level, flags, default_pose, parents, pr
     d_raws = torch.from_numpy(handles.view(np.int32)).to(device)
     d_rates = torch.zeros((num_instances, num_segments, desc.max_tracks, 4), dtype=torch.uint8, device=device)
     d_results = torch.zeros((num_instances, 2), dtype=torch.int32, device=device)
-    d_workspace = torch.zeros(find_bit_rates_workspace_bytes(num_instances, desc.max_tracks, desc.max_samples) + 16, dtype=torch.uint8, device=device)
+    workspace_bytes = find_bit_rates_level_workspace_bytes if with_levels else find_bit_rates_workspace_bytes
+    d_workspace = torch.zeros(workspace_bytes(num_instances, desc.max_tracks, desc.max_samples) + 16, dtype=torch.uint8, device=device)
     desc.workspace = d_workspace.data_ptr()
-    launch = _with_metric(ctx.find_bit_rates_batch, ctx.find_bit_rates_metric_batch, metric)
+    if with_levels:
+        def launch(*arguments, **keywords):
+            return ctx.find_bit_rates_level_batch(*arguments, metric=metric, **keywords)
+    else:
+        launch = _with_metric(ctx.find_bit_rates_batch, ctx.find_bit_rates_metric_batch, metric)
     launch(d_raws.data_ptr(), num_instances, desc, d_rates.data_ptr(), num_segments * desc.max_tracks * 4, desc.max_tracks * 4, d_results.data_ptr(), stream=stream.cuda_stream)
     stream.synchronize()
     return d_rates, d_results.cpu().numpy().view(np.uint32).reshape(num_instances, 2)
 
 
 def find_bit_rates(ctx, raws, level="medium", default_pose=None, parents=None, precision=1.0e-4, shell_distance=1.0, track_precisions=None, track_shell_distances=None,
-                   optimize_loops=False, metric=ERROR_METRIC_QVVF):
+                   optimize_loops=False, metric=ERROR_METRIC_QVVF, return_levels=False):
     """acl::find_optimal_bit_rates -- the bit rate search of compress_track_list with quatf_drop_w_variable / vector3f_variable /
-    vector3f_variable at the levels "lowest", "low" and "medium" (one search) -- for raw track arrays as one launch: `raws` is a handle
+    vector3f_variable at `level`: "lowest", "low" and "medium" (one search), "high", "highest", or "automatic", the reference's default,
+    which picks one of the last three per array (medium above 500 samples, else by the longest bone chain) -- for raw track arrays as
+    one launch. With return_levels the result is (the table, the level that was searched per instance as a uint32 array). `raws` is a handle
     or a list of handles; the settings are compress_tracks_variable's. Returns a uint8 array [instances, segments, tracks, 4] of
     { rotation, translation, scale, 0 } entries over the segments and tracks of the largest array, zero-filled before the launch: 255
     marks a constant or default sub-track, rows and entries an instance does not have stay 0. It is the table compress_tracks_variable
@@ -2004,6 +2030,10 @@ def find_bit_rates(ctx, raws, level="medium", default_pose=None, parents=None, p
     d_rates, results = _find_bit_rates(ctx, handles, infos, level, COMPRESS_OPTIMIZE_LOOPS if optimize_loops else 0, default_pose, parents, precision, shell_distance,
                                        track_precisions, track_shell_distances, metric=metric)
     _raise_for_search_results(handles, results)
+    if return_levels:
+        # (the calls without the levels leave 0 in that word: their one search is the level they were asked for)
+        asked = COMPRESSION_LEVELS.get(level, level)
+        return d_rates.cpu().numpy(), results[:, 1].copy() if asked > COMPRESSION_LEVELS["medium"] else np.full(len(handles), asked, dtype=np.uint32)
     return d_rates.cpu().numpy()
 
 
@@ -2017,14 +2047,14 @@ def _raise_for_search_results(handles, results):
 
 def compress_tracks_variable(ctx, raws, bit_rates=(16, 16, 16), default_pose=None, parents=None, precision=1.0e-4, shell_distance=1.0, track_precisions=None,
                              track_shell_distances=None, optimize_loops=False, include_parent_track_indices=False, include_track_descriptions=False, level="medium",
-                             metric=ERROR_METRIC_QVVF):
+                             metric=ERROR_METRIC_QVVF, return_levels=False):
     """acl::compress_track_list with quatf_drop_w_variable rotations and vector3f_variable translations and scales AT GIVEN BIT RATES for
     raw track arrays as one launch, like compress_tracks: `raws` is a handle or a list of handles. bit_rates is three uniform rates
     (rotation, translation, scale: 0 .. 24), or a uint8 table of { rotation, translation, scale, 0 } entries: [tracks, 4] shared by every
     instance and segment, [segments, tracks, 4] shared by the instances, or [instances, segments, tracks, 4]; it covers
     variable_compress_num_segments(samples) rows and the tracks of the largest array. bit_rates="search" runs find_bit_rates at `level`
-    with the same settings first and compresses at its table, which stays on the device: the reference's compress_track_list at the
-    levels lowest to medium. `metric` is the aclhip_error_metric of the vote, the compaction and the search (find_bit_rates). Rows are
+    with the same settings first and compresses at its table, which stays on the device: the reference's compress_track_list at
+    that level ("automatic" is its default); with return_levels the result is (the blobs, the level that was searched per instance). `metric` is the aclhip_error_metric of the vote, the compaction and the search (find_bit_rates). Rows are
     sized from aclhip_variable_compress_bound.
     Returns a list of 16 byte aligned numpy uint8 blobs in the format the fast decode paths read. Raises RuntimeError with the
     reference's message when a sample is not finite, ValueError when an instance is refused (a rate above 24, a rate of 0 in a blob of
@@ -2032,10 +2062,12 @@ def compress_tracks_variable(ctx, raws, bit_rates=(16, 16, 16), default_pose=Non
     import torch
     flags = ((COMPRESS_OPTIMIZE_LOOPS if optimize_loops else 0) | (COMPRESS_INCLUDE_PARENT_TRACK_INDICES if include_parent_track_indices else 0)
              | (COMPRESS_INCLUDE_TRACK_DESCRIPTIONS if include_track_descriptions else 0))
+    if return_levels and not isinstance(bit_rates, str):
+        raise ValueError('return_levels goes with bit_rates="search"')
     handles = np.atleast_1d(np.asarray(raws, dtype=np.uint32))
     infos = [ctx.raw_tracks_info(int(handle)) for handle in handles]
     if len(handles) == 0:
-        return []
+        return ([], np.zeros(0, dtype=np.uint32)) if return_levels else []
     desc = CompressVariableDesc()
     desc.max_samples = max(int(info.num_samples) for info in infos)
     tables = None
@@ -2046,6 +2078,8 @@ def compress_tracks_variable(ctx, raws, bit_rates=(16, 16, 16), default_pose=Non
         d_rates, results = _find_bit_rates(ctx, handles, infos, level, flags, default_pose, parents, precision, shell_distance, track_precisions, track_shell_distances, tables,
                                            metric=metric)
         _raise_for_search_results(handles, results)
+        asked = COMPRESSION_LEVELS.get(level, level)
+        levels = results[:, 1].copy() if asked > COMPRESSION_LEVELS["medium"] else np.full(len(handles), asked, dtype=np.uint32)
         desc.bit_rates = d_rates.data_ptr()                                                 # (alive until the launch has run)
         desc.bit_rate_segment_stride = d_rates.shape[2] * 4
         desc.bit_rate_instance_stride = d_rates.shape[1] * d_rates.shape[2] * 4
@@ -2066,8 +2100,9 @@ def compress_tracks_variable(ctx, raws, bit_rates=(16, 16, 16), default_pose=Non
 
     def workspace_bytes(num_instances, max_tracks):
         return compress_variable_workspace_bytes(num_instances, max_tracks, desc.max_samples)
-    return _compress_transform_tracks(ctx, _with_metric(ctx.compress_tracks_variable_batch, ctx.compress_tracks_variable_metric_batch, metric), workspace_bytes, desc, raws, flags, default_pose, parents, precision, shell_distance,
-                                      track_precisions, track_shell_distances, bound=variable_compress_bound, tables=tables)
+    blobs = _compress_transform_tracks(ctx, _with_metric(ctx.compress_tracks_variable_batch, ctx.compress_tracks_variable_metric_batch, metric), workspace_bytes, desc, raws, flags, default_pose, parents, precision, shell_distance,
+                                       track_precisions, track_shell_distances, bound=variable_compress_bound, tables=tables)
+    return (blobs, levels) if return_levels else blobs
 
 
 def compress_tracks_at_precision(ctx, raw, skeleton, shells, precision, parents=None, default_pose=None, shell_distance=1.0, optimize_loops=False,

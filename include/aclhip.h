@@ -2270,7 +2270,7 @@ uint64_t aclhip_find_bit_rates_workspace_bytes(uint32_t num_instances, uint32_t 
  *   Five launches (DESIGN.md 4.7 "Bit rate search"): the shell and the analysis of the variable call, unchanged; per (instance, segment)
  * the segment ranges and S0; per (instance, segment, track) S3 from a table of S1 in LDS, lanes over the tuples of a size; per (instance,
  * segment) S4 with lanes over the samples. No atomics besides the refusal counter and no zero fill: the same bytes on every run.
- *   Left out: the levels high and highest (chains with two and three increments); additive bases (the matrix error metric:
+ *   Left out: the levels high and highest (chains with two and three increments: aclhip_find_bit_rates_level_batch, below); additive bases (the matrix error metric:
  * aclhip_find_bit_rates_metric_batch, below); the
  * contributing error and keyframe stripping. What it costs: profiles/bit_rate_search.md. */
 aclhip_status aclhip_find_bit_rates_batch(aclhip_context* context, const aclhip_raw_tracks* raws /* DEVICE [num_instances] */,
@@ -2328,6 +2328,53 @@ aclhip_status aclhip_compress_tracks_variable_metric_batch(aclhip_context* conte
 	uint32_t num_instances, const aclhip_compress_variable_desc* desc, void* blobs /* DEVICE */, uint64_t blob_stride_bytes,
 	aclhip_compress_result* results /* DEVICE [num_instances] */, uint32_t metric, void* stream);
 aclhip_status aclhip_find_bit_rates_metric_batch(aclhip_context* context, const aclhip_raw_tracks* raws /* DEVICE [num_instances] */,
+	uint32_t num_instances, const aclhip_find_bit_rates_desc* desc, uint8_t* bit_rates /* DEVICE */, uint64_t instance_stride,
+	uint64_t segment_stride, aclhip_compress_result* results /* DEVICE [num_instances] */, uint32_t metric, void* stream);
+
+/* ---- the bit rate search at every compression level ----------------------------------------------------------------------------------------
+ * aclhip_find_bit_rates_metric_batch with the levels it leaves out: `desc->level` is 0 to 4 (lowest, low, medium, high, highest) or
+ * ACLHIP_LEVEL_AUTOMATIC, the level of acl::get_default_compression_settings(). With it "search, then compress" is the reference's
+ * default compress_track_list. This is an addition to ABI version 6: new names only, no existing struct, function or message changes.
+ *   Everything is that call's, word for word -- the desc, the table's layout, every check, refusal and status, the alignment and overlap
+ * rules, the metric, stream ordering, "uploads nothing" and graph capture -- but for: the messages name this call ("bit rate level
+ * search"); any other level is ACLHIP_ERROR_INVALID_ARGUMENT with a message that names the accepted ones; the workspace is
+ * aclhip_find_bit_rates_level_workspace_bytes; and the second word of an instance's result (`size`, 0 from the other two calls) is THE
+ * LEVEL THAT WAS SEARCHED, 0 to 4, for an instance that ends ACLHIP_COMPRESS_OK and 0 for any other.
+ *   The levels 0, 1 and 2 give aclhip_find_bit_rates_metric_batch's table, byte for byte.
+ *   AUTOMATIC (find_best_compression_level, compress.transform.impl.h:114-136) is decided per instance on the device, so a launch may
+ * mix rigs: medium when the array has more than 500 samples AS REGISTERED (the reference resolves the level before its looping vote
+ * removes a sample); otherwise by the longest chain of the instance, counted in bones from a root to a leaf over its tracks and
+ * `parent_indices`: below 18 highest, below 25 high, else medium.
+ *   HIGH AND HIGHEST change S4's first loop alone (quantize.transform.h:1250-1377); S0 to S3 and the last pass are as stated above. In
+ * a round -- error >= sprec_b, original = best = error -- the reference calls calculate_bone_permutation_error once per SHAPE of
+ * increments over the chain c_0 .. c_n, in this order: {1} (every level: the loop stated above); from high on {2} and, when n >= 1,
+ * {1,1}; at highest also {3}, when n >= 1 {2,1}, and when n >= 2 {1,1,1}. A shape's ARRANGEMENTS put its increments on distinct links,
+ * 0 elsewhere, and come in std::next_permutation order over the array of increments indexed by link, root first (the own track's
+ * place changes fastest), from the arrangement with the increments on the last links in the order written: every shape starts at
+ * its smallest arrangement and visits all, except {2,1}, which starts at "c_n-1 + 2, c_n + 1" and runs from there to the end, so
+ * "c_n-1 + 1, c_n + 2" is never tried and a chain of two links tries one arrangement. For an arrangement, every link c_k with an
+ * increment m is INCREASED by m: of the (rotation, translation, scale) increments that sum to m -- three nested loops 0 .. m, the
+ * scale's 0 .. 0 without has_scale, each clamped at 24, a rate of 255 left alone, with the reference's rules at 24 (:1005-1046: behind
+ * a rotation, translation or scale that reached 24 the loop of that kind ends; a sum other than m is passed over) -- the one whose
+ * object error measured AT c_k is lowest and strictly below `original`, else c_k's rates as they are. An arrangement none of whose
+ * links changed is skipped unmeasured. Otherwise the object error of b with those links so increased is taken: strictly below the
+ * call's best so far (from `original`) it becomes the call's best, and if also < sprec_b the call ends at once. After a call: its
+ * best strictly below the round's best replaces it, with its rates, and if < sprec_b the round and the loop end. A round none of
+ * whose calls improved ends the loop; otherwise the best is applied and the loop goes on from its error. Every loop ends: a shape's
+ * arrangements are finitely many, and a round that goes on has raised a rate, and rates stop at 24.
+ *   Measured against the reference (tests/test_bit_rate_search_levels_oracle.py, which states the figures and the caps): the
+ * differences are what the reference shows against itself with its input rotations one ulp away.
+ *   Six launches (DESIGN.md 4.7 "Bit rate search", the levels): the five of aclhip_find_bit_rates_batch with one small launch in front of the
+ * object phase that leaves the level per instance, and the object phase's second instantiation, which tries the wider shapes. What
+ * INCREASING c_k by m gives does not change within a round: that kernel computes it once per round and link, where the reference
+ * recomputes it for every arrangement, and keeps it in the workspace; no decision differs. What it costs: profiles/bit_rate_search_levels.md. */
+#define ACLHIP_LEVEL_AUTOMATIC 100u        /* acl::compression_level8::automatic */
+
+/* Host only. aclhip_find_bit_rates_workspace_bytes and, per instance, segment of max_samples and track, 12 bytes more (what
+ * increasing a link of the chain under work by 1, 2 and 3 gives in this round); rounded up to 16, 128 bits wide, capped. */
+uint64_t aclhip_find_bit_rates_level_workspace_bytes(uint32_t num_instances, uint32_t max_tracks, uint32_t max_samples);
+
+aclhip_status aclhip_find_bit_rates_level_batch(aclhip_context* context, const aclhip_raw_tracks* raws /* DEVICE [num_instances] */,
 	uint32_t num_instances, const aclhip_find_bit_rates_desc* desc, uint8_t* bit_rates /* DEVICE */, uint64_t instance_stride,
 	uint64_t segment_stride, aclhip_compress_result* results /* DEVICE [num_instances] */, uint32_t metric, void* stream);
 

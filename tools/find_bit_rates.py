@@ -14,7 +14,12 @@ FIND_BIT_RATES_AT_PRECISION=1 the first array also goes through runtime.compress
 _metric entry points, checked against tests/matrix_metric_compress_restatement.py) the qvvf calls are timed IN THE SAME ROUNDS, their
 blob bytes reported beside, and every key of metric 0 carries the suffix _qvvf. --scales nonuniform: every scale of the workload's
 arrays drawn anew per sample and component within 0.9 .. 1.1, so that has_scale holds in every array and shear builds up down the
-chains -- the workload the matrix metric is for. Prints one JSON line."""
+chains -- the workload the matrix metric is for. --level: the compression level of the search; lowest, low and medium go through
+aclhip_find_bit_rates_batch (or its _metric form), high, highest and automatic through aclhip_find_bit_rates_level_batch with its
+workspace, checked against tests/bit_rate_search_levels_restatement.py; the lab library's knob is then
+ACLHIP_FIND_BIT_RATES_LEVEL_PHASES and the split has a sixth phase, the level per instance, in front of the object phase. The
+workload's spine makes chains of 26 bones, where the wider levels are at their most expensive (automatic picks medium for it): size
+the batch with COMPRESS_TRACKS_INSTANCES. Prints one JSON line."""
 import argparse
 import json
 import os
@@ -30,6 +35,7 @@ import torch  # noqa: E402
 from acl_amd import runtime  # noqa: E402
 import compress_tracks as workload  # noqa: E402  (the arrays, the skeleton, the timer)
 import bit_rate_search_restatement as restatement  # noqa: E402  (the checker's restatement)
+import bit_rate_search_levels_restatement as levels_restatement  # noqa: E402  (and at every level)
 import matrix_metric_compress_restatement as metric_restatement  # noqa: E402  (and with the metric as an argument)
 
 N, ARRAYS, TRACKS, SAMPLES = workload.N, workload.ARRAYS, workload.TRACKS, workload.SAMPLES
@@ -40,14 +46,21 @@ AT_PRECISION = os.environ.get("FIND_BIT_RATES_AT_PRECISION", "0") == "1"
 RATE, PRECISION, SHELL = workload.RATE, workload.PRECISION, workload.SHELL
 PHASES = ("shell", "analysis", "segments", "local", "object")
 KNOB = "ACLHIP_FIND_BIT_RATES_PHASES"
+LEVEL_PHASES = ("shell", "analysis", "segments", "local", "level", "object")         # aclhip_find_bit_rates_level_batch
+LEVEL_KNOB = "ACLHIP_FIND_BIT_RATES_LEVEL_PHASES"
 
 
 def main():
     parser = argparse.ArgumentParser(description=__doc__.split("\n")[0])
     parser.add_argument("--metric", type=int, choices=(0, 1), default=0, help="aclhip_error_metric: 0 qvvf (the entry points without a metric), 1 qvvf_matrix3x4f")
     parser.add_argument("--scales", choices=("workload", "nonuniform"), default="workload", help="nonuniform: every scale within 0.9 .. 1.1, per sample and component")
+    parser.add_argument("--level", choices=sorted(runtime.COMPRESSION_LEVELS, key=runtime.COMPRESSION_LEVELS.get), default="medium",
+                        help="the compression level; high, highest and automatic go through aclhip_find_bit_rates_level_batch")
     arguments = parser.parse_args()
     metric = arguments.metric
+    level = runtime.COMPRESSION_LEVELS[arguments.level]
+    with_levels = level > runtime.COMPRESSION_LEVELS["medium"]
+    phases, knob_name = (LEVEL_PHASES, LEVEL_KNOB) if with_levels else (PHASES, KNOB)
     if not torch.cuda.is_available():
         raise SystemExit("tools/find_bit_rates.py needs a GPU: nothing is measured without one")
     rng = np.random.default_rng(9100 + TRACKS)
@@ -72,9 +85,10 @@ def main():
         d_rates = torch.zeros((N, segments, TRACKS, 4), dtype=torch.uint8, device="cuda")
         d_blobs = torch.zeros((N, stride), dtype=torch.uint8, device="cuda")
         d_results = torch.zeros((N, 2), dtype=torch.int32, device="cuda")
-        d_workspace = torch.zeros(runtime.find_bit_rates_workspace_bytes(N, TRACKS, SAMPLES), dtype=torch.uint8, device="cuda")
+        workspace_bytes = runtime.find_bit_rates_level_workspace_bytes if with_levels else runtime.find_bit_rates_workspace_bytes
+        d_workspace = torch.zeros(workspace_bytes(N, TRACKS, SAMPLES), dtype=torch.uint8, device="cuda")
     search = runtime.FindBitRatesDesc()
-    search.precision, search.shell_distance, search.max_tracks, search.max_samples, search.workspace, search.level = PRECISION, SHELL, TRACKS, SAMPLES, d_workspace.data_ptr(), 2
+    search.precision, search.shell_distance, search.max_tracks, search.max_samples, search.workspace, search.level = PRECISION, SHELL, TRACKS, SAMPLES, d_workspace.data_ptr(), level
     search.parent_indices, search.num_table_tracks = d_parents.data_ptr(), TRACKS
     desc = runtime.CompressVariableDesc()
     desc.precision, desc.shell_distance, desc.max_tracks, desc.max_samples, desc.workspace = PRECISION, SHELL, TRACKS, SAMPLES, d_workspace.data_ptr()
@@ -82,6 +96,8 @@ def main():
     desc.bit_rates, desc.bit_rate_segment_stride, desc.bit_rate_instance_stride = d_rates.data_ptr(), 4 * TRACKS, 4 * TRACKS * segments
 
     def launch_search_qvvf():
+        if with_levels:
+            return ctx.find_bit_rates_level_batch(d_raws.data_ptr(), N, search, d_rates.data_ptr(), 4 * TRACKS * segments, 4 * TRACKS, d_results.data_ptr(), stream=s)
         ctx.find_bit_rates_batch(d_raws.data_ptr(), N, search, d_rates.data_ptr(), 4 * TRACKS * segments, 4 * TRACKS, d_results.data_ptr(), stream=s)
 
     def launch_compress_qvvf():
@@ -90,6 +106,8 @@ def main():
     def launch_search():
         if metric == runtime.ERROR_METRIC_QVVF:
             return launch_search_qvvf()
+        if with_levels:
+            return ctx.find_bit_rates_level_batch(d_raws.data_ptr(), N, search, d_rates.data_ptr(), 4 * TRACKS * segments, 4 * TRACKS, d_results.data_ptr(), metric=metric, stream=s)
         ctx.find_bit_rates_metric_batch(d_raws.data_ptr(), N, search, d_rates.data_ptr(), 4 * TRACKS * segments, 4 * TRACKS, d_results.data_ptr(), metric, stream=s)
 
     def launch_compress():
@@ -98,7 +116,7 @@ def main():
         ctx.compress_tracks_variable_metric_batch(d_raws.data_ptr(), N, desc, d_blobs.data_ptr(), stride, d_results.data_ptr(), metric, stream=s)
 
     # ---- checked before it is timed
-    os.environ.pop(KNOB, None)
+    os.environ.pop(knob_name, None)
     qvvf_blob_bytes = None
     if metric != runtime.ERROR_METRIC_QVVF:         # (the qvvf search's blobs, for their bytes; the table is searched again below)
         with torch.cuda.stream(stream):
@@ -112,9 +130,14 @@ def main():
     if ctx.rejected_instance_count() != 0 or np.any(results[:, 0] != runtime.COMPRESS_OK):
         print(f"refused or failed instances: {ctx.rejected_instance_count()}, statuses {np.unique(results[:, 0])}", flush=True)
         sys.exit(1)
+    searched_levels = sorted(int(word) for word in np.unique(results[:, 1])) if with_levels else [level]
+    evaluations = None
     for i in range(min(ARRAYS, N, RESTATED)):
-        expected = metric_restatement.find_bit_rates(arrays[i], RATE, metric, parents=parents, precision=PRECISION, shell_distance=SHELL).table
-        if not np.array_equal(tables[i], expected):
+        restated = levels_restatement.find_bit_rates_metric(arrays[i], RATE, metric, level=level, parents=parents, precision=PRECISION, shell_distance=SHELL)
+        expected = restated.table
+        if with_levels:
+            evaluations = {"array": i, "with_the_memo": int(restated.evaluations), "without_the_memo": int(restated.evaluations_unmemoized)}
+        if (with_levels and int(results[i, 1]) != restated.level) or not np.array_equal(tables[i], expected):
             print(f"MISMATCH with the restatement in the table of array {i}: {int((tables[i] != expected).sum())} bytes", flush=True)
             sys.exit(1)
     with torch.cuda.stream(stream):
@@ -145,21 +168,21 @@ def main():
     lab = "lab" in os.path.basename(runtime.library_path())
     cases = {"search": (launch_search, None), "compress_at_the_table": (launch_compress, None)}
     if lab:
-        for k in range(1, 5):
+        for k in range(1, len(phases)):
             cases["phases_%d" % k] = (launch_search, str(k))
     if metric != runtime.ERROR_METRIC_QVVF:         # (the compress call behind the qvvf search reads the matrix table: its time does not depend on the rates' metric)
         cases["search_qvvf"] = (launch_search_qvvf, None)
         cases["compress_at_the_table_qvvf"] = (launch_compress_qvvf, None)
         if lab:
-            for k in range(1, 5):
+            for k in range(1, len(phases)):
                 cases["phases_%d_qvvf" % k] = (launch_search_qvvf, str(k))
 
     def run(case, repeats):
         call, knob = case
         if knob is None:
-            os.environ.pop(KNOB, None)
+            os.environ.pop(knob_name, None)
         else:
-            os.environ[KNOB] = knob
+            os.environ[knob_name] = knob
         return workload.timed(stream, call, repeats)
 
     for case in cases.values():
@@ -168,14 +191,14 @@ def main():
     for _ in range(ROUNDS):
         for key, case in cases.items():
             samples[key].append(run(case, REPEATS))
-    os.environ.pop(KNOB, None)
+    os.environ.pop(knob_name, None)
 
     def summary(values):
         values = np.array(values)
         return {"median": round(float(np.median(values)), 2), "min": round(float(values.min()), 2), "max": round(float(values.max()), 2),
                 "spread": round(float((values.max() - values.min()) / np.median(values)), 4)}
 
-    result = {"metric": metric, "scales": arguments.scales, "instances": N, "distinct_arrays": ARRAYS, "tracks": TRACKS, "samples": SAMPLES, "segments": segments, "rounds": ROUNDS, "repeats": REPEATS,
+    result = {"metric": metric, "level": arguments.level, "searched_levels": searched_levels, "scales": arguments.scales, "instances": N, "distinct_arrays": ARRAYS, "tracks": TRACKS, "samples": SAMPLES, "segments": segments, "rounds": ROUNDS, "repeats": REPEATS,
               "checked_against": "restatement (%d arrays)" % min(ARRAYS, N, RESTATED), "library": os.path.basename(runtime.library_path()),
               "raw_bytes": int(N * TRACKS * SAMPLES * 48), "searched_blob_bytes": blob_bytes, "uniform_16_blob_bytes": uniform_bytes,
               "rates": {"min": int(animated.min()), "max": int(animated.max()), "mean": round(float(animated.mean()), 2)} if animated.size else None,
@@ -184,14 +207,16 @@ def main():
         result["first_array"] = at_precision
     if qvvf_blob_bytes is not None:
         result["searched_blob_bytes_qvvf"] = qvvf_blob_bytes
+    if evaluations is not None:
+        result["object_errors_in_the_restatement"] = evaluations
     for suffix in ("", "_qvvf") if lab else ():
         if "search" + suffix not in result["us"]:
             continue
         total = result["us"]["search" + suffix]["median"]
-        upto = [result["us"]["phases_%d%s" % (k, suffix)]["median"] for k in range(1, 5)] + [total]
-        split = [upto[0]] + [upto[k] - upto[k - 1] for k in range(1, 5)]
-        result["phase_us" + suffix] = {name: round(value, 2) for name, value in zip(PHASES, split)}
-        result["phase_share" + suffix] = {name: round(value / total, 3) for name, value in zip(PHASES, split)}
+        upto = [result["us"]["phases_%d%s" % (k, suffix)]["median"] for k in range(1, len(phases))] + [total]
+        split = [upto[0]] + [upto[k] - upto[k - 1] for k in range(1, len(phases))]
+        result["phase_us" + suffix] = {name: round(value, 2) for name, value in zip(phases, split)}
+        result["phase_share" + suffix] = {name: round(value / total, 3) for name, value in zip(phases, split)}
     ctx.close()
     print(json.dumps(result), flush=True)
 
