@@ -7,7 +7,9 @@
 // the sizes a caller needs, and one argument check, one workspace layout and one launch record for all -- the raw call is the drop-w
 // call with the full formats, no shell and its own words; the variable call is it with its own kernels behind the shell, its rate
 // table and three more parts of the workspace; the search is the variable call without rows, its table written, and four more parts;
-// the search with the levels is the search with its own words, one more part and one more launch.
+// the search with the levels is the search with its own words, one more part and one more launch. The _additive entry points are
+// the drop-w call, the variable call and the search with the levels with the additive base as one more thing a call says of itself:
+// it picks the instantiations of the kernels the base enters, and its format goes into the launch record.
 // What a call says of itself is its transform_compress_kind; what the smaller descs, the rate table, the written and the read ranges,
 // the variable launch record and the grid of a wave per segment are is stated once each, in front of the check and of the calls.
 // What they share with the scalar compressor -- the cap of a size, the common checks, the launches' shapes, their front and their list
@@ -21,6 +23,7 @@ static_assert(sizeof(aclhip_find_bit_rates_desc) == 96, "header layout");
 static_assert(offsetof(aclhip_find_bit_rates_desc, default_pose) == 16 && offsetof(aclhip_find_bit_rates_desc, precision) == 48
 	&& offsetof(aclhip_find_bit_rates_desc, workspace) == 56 && offsetof(aclhip_find_bit_rates_desc, shell_metadata) == 64
 	&& offsetof(aclhip_find_bit_rates_desc, level) == 72 && offsetof(aclhip_find_bit_rates_desc, reserved) == 80, "header layout");
+static_assert(sizeof(aclhip_additive_base) == 32 && offsetof(aclhip_additive_base, additive_format) == 8 && offsetof(aclhip_additive_base, reserved) == 16, "header layout");
 static_assert(sizeof(aclhip_compress_tracks_desc) == 96, "header layout");
 static_assert(offsetof(aclhip_compress_tracks_desc, flags) == 12 && offsetof(aclhip_compress_tracks_desc, num_table_tracks) == 20
 	&& offsetof(aclhip_compress_tracks_desc, default_pose) == 24 && offsetof(aclhip_compress_tracks_desc, track_shell_distances) == 48
@@ -35,12 +38,17 @@ namespace
 	// What an entry point says of itself: the word its desc goes by in the messages, the knob of its phases, whether its workspace holds shells and the
 	// segments it holds the variable call's parts for (0: none), whether it writes blob rows, whether its workspace holds the
 	// search's parts and whether the search takes every level; and the error metric its decisions are taken by (an aclhip_error_metric: the entry points without one say
-	// ACLHIP_METRIC_QVVF). The rest of what tells the raw and the drop-w call apart is in the desc: the formats and the shell metadata, 0
+	// ACLHIP_METRIC_QVVF); and whether it takes an additive base, and the caller's (the _additive entry points: it may be null, which
+	// the check refuses). The rest of what tells the raw and the drop-w call apart is in the desc: the formats and the shell metadata, 0
 	// for the raw call.
 	struct transform_compress_kind
 	{
 		const char* name; const char* phases_knob; bool with_shells; uint32_t max_segments = 0; bool with_rows = true; bool with_search = false; bool with_levels = false; uint32_t metric = ACLHIP_METRIC_QVVF;
+		bool with_base = false; const aclhip_additive_base* base = nullptr;
 		transform_compress_kind with_metric(uint32_t error_metric) const { transform_compress_kind kind = *this; kind.metric = error_metric; return kind; }
+		transform_compress_kind with_additive_base(const aclhip_additive_base* additive_base) const { transform_compress_kind kind = *this; kind.with_base = true; kind.base = additive_base; return kind; }
+		// the format its kernels apply: ACLHIP_ADDITIVE_NONE for every call without a base (only behind the check)
+		uint32_t additive_format() const { return with_base && base != nullptr ? base->additive_format : uint32_t(ACLHIP_ADDITIVE_NONE); }
 	};
 
 	// the segments of the longest array a caller announces (a desc of 0 max_samples is refused: it counts as 1 here)
@@ -160,18 +168,32 @@ namespace
 
 	// The kernels that decide by the error metric, per metric: the shell (its vote) and the variable call's analysis, which the drop-w
 	// call, the variable call and the search share, and the search's two phases, the object phase without and with the levels
+	// -- and, for a call with an additive base of a format other than NONE, the seven kernels the base enters: those five, the drop-w
+	// call's analysis and the search's segment kernel (S0), which no metric enters. The qvvf metric alone has them: the reference has
+	// no additive matrix metric.
 	struct metric_kernels
 	{
 		void (*shell)(transform_compress_launch); void (*variable_analyze)(variable_compress_launch);
 		void (*search_local)(bit_rate_search_launch); void (*search_object)(bit_rate_search_launch); void (*search_object_levels)(bit_rate_search_levels_launch);
+		void (*tracks_analyze)(transform_compress_launch); void (*search_segment)(bit_rate_search_launch);
 	};
 	const metric_kernels k_metric_kernels[2] =
 	{
 		{ tracks_compress_shell_kernel<k_metric_qvvf>, variable_compress_analyze_kernel<k_metric_qvvf>, bit_rate_search_local_kernel<k_metric_qvvf>,
-			bit_rate_search_object_kernel<k_metric_qvvf>, bit_rate_search_object_kernel<k_metric_qvvf, true> },
+			bit_rate_search_object_kernel<k_metric_qvvf>, bit_rate_search_object_kernel<k_metric_qvvf, true>, tracks_compress_analyze_kernel<k_metric_qvvf>, bit_rate_search_segment_kernel<false> },
 		{ tracks_compress_shell_kernel<k_metric_matrix>, variable_compress_analyze_kernel<k_metric_matrix>, bit_rate_search_local_kernel<k_metric_matrix>,
-			bit_rate_search_object_kernel<k_metric_matrix>, bit_rate_search_object_kernel<k_metric_matrix, true> },
+			bit_rate_search_object_kernel<k_metric_matrix>, bit_rate_search_object_kernel<k_metric_matrix, true>, tracks_compress_analyze_kernel<k_metric_matrix>, bit_rate_search_segment_kernel<false> },
 	};
+	const metric_kernels k_additive_kernels =
+	{
+		tracks_compress_shell_kernel<k_metric_qvvf, true>, variable_compress_analyze_kernel<k_metric_qvvf, true>, bit_rate_search_local_kernel<k_metric_qvvf, true>,
+		bit_rate_search_object_kernel<k_metric_qvvf, false, true>, bit_rate_search_object_kernel<k_metric_qvvf, true, true>, tracks_compress_analyze_kernel<k_metric_qvvf, true>,
+		bit_rate_search_segment_kernel<true>,
+	};
+	const metric_kernels& deciding_kernels_of(const transform_compress_kind& kind)
+	{
+		return kind.additive_format() != ACLHIP_ADDITIVE_NONE ? k_additive_kernels : k_metric_kernels[kind.metric];
+	}
 
 	// A smaller desc as the drop-w call's, which the shared check and the launch record read: the rotation format the call stands for
 	// (the raw call the full one; the variable call and the search quatf_drop_w_full, which passes the format clauses: they have no
@@ -248,6 +270,13 @@ namespace
 		read[4] = { "the track shell distances", desc.track_shell_distances, desc.track_shell_distances != nullptr ? table * sizeof(float) : 0 };
 	}
 
+	// the handles of the bases a call reads: none without a base or with ACLHIP_ADDITIVE_NONE
+	byte_range additive_base_range(const transform_compress_kind& kind, uint32_t num_instances)
+	{
+		const bool read = kind.additive_format() != ACLHIP_ADDITIVE_NONE;
+		return { "the additive base handles", read ? kind.base->base_raws : nullptr, read ? (unsigned __int128)num_instances * sizeof(aclhip_raw_tracks) : 0 };
+	}
+
 	// What the launch checks of its arguments before any device call, its own between the parts every compressor checks
 	// (host_scalar_compress.inl). The raw call's desc has no shell metadata and the full formats: those clauses pass.
 	aclhip_status check_transform_compress(aclhip_context* context, const transform_compress_kind& kind, const aclhip_raw_tracks* raws, uint32_t num_instances,
@@ -261,6 +290,19 @@ namespace
 		}
 		if (kind.metric > ACLHIP_METRIC_QVVF_MATRIX3X4F)
 			return fail(context, ACLHIP_ERROR_INVALID_ARGUMENT, "unknown error metric %u", kind.metric);
+		if (kind.with_base)
+		{
+			if (kind.base == nullptr)
+				return fail(context, ACLHIP_ERROR_INVALID_ARGUMENT, "null additive base");
+			if (kind.base->additive_format > ACLHIP_ADDITIVE_ADDITIVE1)
+				return fail(context, ACLHIP_ERROR_INVALID_ARGUMENT, "unknown additive format %u", kind.base->additive_format);
+			if (kind.base->reserved_word != 0 || kind.base->reserved[0] != 0 || kind.base->reserved[1] != 0)
+				return fail(context, ACLHIP_ERROR_INVALID_ARGUMENT, "reserved fields of the additive base are not 0");
+			if (kind.base->additive_format != ACLHIP_ADDITIVE_NONE && kind.base->base_raws == nullptr)
+				return fail(context, ACLHIP_ERROR_INVALID_ARGUMENT, "additive format %u without base_raws", kind.base->additive_format);
+			if (kind.base->additive_format != ACLHIP_ADDITIVE_NONE && (reinterpret_cast<uintptr_t>(kind.base->base_raws) & 3u) != 0)
+				return fail(context, ACLHIP_ERROR_INVALID_ARGUMENT, "base_raws must be 4 byte aligned");
+		}
 		if (const aclhip_status status = check_compress_buffers(context, kind.name, "raw track", raws, desc, blobs, blob_stride_bytes, results, kind.with_rows); status != ACLHIP_OK)
 			return status;
 		if ((reinterpret_cast<uintptr_t>(desc->default_pose) & 15u) != 0)
@@ -277,6 +319,8 @@ namespace
 			return fail(context, ACLHIP_ERROR_INVALID_ARGUMENT, "rotation format quatf_drop_w_variable is not built");
 		if (desc->rotation_format != k_rotation_quatf_full && desc->rotation_format != k_rotation_quatf_drop_w_full)
 			return fail(context, ACLHIP_ERROR_INVALID_ARGUMENT, "a rotation format of %u: 0 (quatf_full) or 2 (quatf_drop_w_full)", desc->rotation_format);
+		if (desc->rotation_format == k_rotation_quatf_full && kind.additive_format() != ACLHIP_ADDITIVE_NONE)
+			return fail(context, ACLHIP_ERROR_INVALID_ARGUMENT, "rotation format quatf_full takes no additive base: the raw settings decide nothing by a metric");
 		if (desc->translation_format == 1 || desc->scale_format == 1)
 			return fail(context, ACLHIP_ERROR_INVALID_ARGUMENT, "vector format vector3f_variable is not built");
 		if (desc->translation_format != 0)
@@ -291,7 +335,11 @@ namespace
 		if (const aclhip_status status = check_compress_ranges(context, kind.name, *desc, uint64_t(written[2].bytes), num_instances, blobs, blob_stride_bytes, results, ranges); status != ACLHIP_OK)
 			return status;
 		// the fourth output, in a pass of its own behind that one: it overlaps no other and nothing that is read
-		return check_no_overlap(context, &written[3], 1, ranges, 8);
+		if (const aclhip_status status = check_no_overlap(context, &written[3], 1, ranges, 8); status != ACLHIP_OK)
+			return status;
+		// the bases' handles, where a call reads them: they overlap nothing that is written
+		const byte_range base_range = additive_base_range(kind, num_instances);
+		return check_no_overlap(context, written, 4, &base_range, 1);
 	}
 
 	// The launch record of a checked call: the tables, the settings and where the workspace's parts lie
@@ -323,6 +371,8 @@ namespace
 		launch.results = reinterpret_cast<uint2*>(results);
 		launch.waves_per_instance = shape.waves_per_instance;
 		launch.rejected_count = context->d_rejected;
+		launch.additive_format = kind.additive_format();
+		launch.base_raws = launch.additive_format != ACLHIP_ADDITIVE_NONE ? kind.base->base_raws : nullptr;
 		return launch;
 	}
 
@@ -367,11 +417,12 @@ namespace
 			// (the phases knob counts the call's own launches: four for quatf_full, five for quatf_drop_w_full)
 			const bool drop_w = desc->rotation_format == k_rotation_quatf_drop_w_full;
 			const transform_compress_kernels& kernels = k_transform_compress_kernels[drop_w ? 1u + kind.metric : 0u];
+			const metric_kernels& deciding = deciding_kernels_of(kind);
 			const dim3 block(shape.block_size);
 			const compress_phase phases[] =
 			{
-				{ k_metric_kernels[kind.metric].shell, dim3(shape.instance_blocks), block, launch },
-				{ kernels.analyze, shape.track_blocks, block, launch },
+				{ deciding.shell, dim3(shape.instance_blocks), block, launch },
+				{ drop_w ? deciding.tracks_analyze : kernels.analyze, shape.track_blocks, block, launch },
 				{ kernels.layout, dim3(shape.instance_blocks), block, launch },
 				{ kernels.stream, dim3(shape.stream_blocks), block, launch },
 				{ compress_hash_kernel, dim3(num_instances), dim3(k_wave_size), hash_launch },
@@ -403,13 +454,20 @@ extern "C" aclhip_status aclhip_compress_tracks_batch(aclhip_context* context, c
 	return aclhip_compress_tracks_metric_batch(context, raws, num_instances, desc, blobs, blob_stride_bytes, results, ACLHIP_METRIC_QVVF, stream_handle);
 }
 
+extern "C" aclhip_status aclhip_compress_tracks_additive_batch(aclhip_context* context, const aclhip_raw_tracks* raws, uint32_t num_instances,
+	const aclhip_compress_tracks_desc* desc, void* blobs, uint64_t blob_stride_bytes, aclhip_compress_result* results, const aclhip_additive_base* additive_base, void* stream_handle)
+{
+	return compress_transform_tracks(context, k_tracks_compress_kind.with_additive_base(additive_base), raws, num_instances, desc, blobs, blob_stride_bytes, results, stream_handle);
+}
+
 // The variable call: the shared check over its desc as the drop-w one, its own checks behind it, and its six launches.
-extern "C" aclhip_status aclhip_compress_tracks_variable_metric_batch(aclhip_context* context, const aclhip_raw_tracks* raws, uint32_t num_instances,
-	const aclhip_compress_variable_desc* desc_or_null, void* blobs, uint64_t blob_stride_bytes, aclhip_compress_result* results, uint32_t metric, void* stream_handle)
+namespace
+{
+aclhip_status compress_variable_tracks(aclhip_context* context, const transform_compress_kind& kind, const aclhip_raw_tracks* raws, uint32_t num_instances,
+	const aclhip_compress_variable_desc* desc_or_null, void* blobs, uint64_t blob_stride_bytes, aclhip_compress_result* results, void* stream_handle)
 {
 	const aclhip_compress_variable_desc& desc = desc_or_null != nullptr ? *desc_or_null : aclhip_compress_variable_desc{};
 	const aclhip_compress_tracks_desc as_tracks = compress_tracks_desc_of(desc, k_rotation_quatf_drop_w_full, desc.reserved_rate | desc.reserved_word);
-	const transform_compress_kind kind = variable_compress_kind_of(desc.max_samples).with_metric(metric);
 	if (const aclhip_status status = check_transform_compress(context, kind, raws, num_instances, desc_or_null != nullptr ? &as_tracks : nullptr, blobs, blob_stride_bytes, results); status != ACLHIP_OK)
 		return status;
 	if (desc.max_samples == 0)
@@ -436,11 +494,12 @@ extern "C" aclhip_status aclhip_compress_tracks_variable_metric_batch(aclhip_con
 		launch.uniform_rates = uint32_t(desc.rotation_bit_rate) | (uint32_t(desc.translation_bit_rate) << 8) | (uint32_t(desc.scale_bit_rate) << 16);
 		const compress_hash_launch hash_launch = { launch.base.instances, num_instances, launch.base.blobs, blob_stride_bytes };
 
+		const metric_kernels& deciding = deciding_kernels_of(kind);
 		const dim3 block(shape.block_size);
 		const compress_phase phases[] =
 		{
-			{ k_metric_kernels[kind.metric].shell, dim3(shape.instance_blocks), block, launch.base },
-			{ k_metric_kernels[kind.metric].variable_analyze, shape.track_blocks, block, launch },
+			{ deciding.shell, dim3(shape.instance_blocks), block, launch.base },
+			{ deciding.variable_analyze, shape.track_blocks, block, launch },
 			{ variable_compress_layout_kernel, dim3(shape.instance_blocks), block, launch },
 			{ variable_compress_ranges_kernel, dim3(compress_segment_blocks_of(num_instances, kind.max_segments)), block, launch },
 			{ variable_compress_stream_kernel, dim3(shape.stream_blocks), block, launch },
@@ -448,6 +507,21 @@ extern "C" aclhip_status aclhip_compress_tracks_variable_metric_batch(aclhip_con
 		};
 		return launch_compress_phases(context, stream, shape.phases, phases, 6);
 	});
+}
+}
+
+extern "C" aclhip_status aclhip_compress_tracks_variable_metric_batch(aclhip_context* context, const aclhip_raw_tracks* raws, uint32_t num_instances,
+	const aclhip_compress_variable_desc* desc, void* blobs, uint64_t blob_stride_bytes, aclhip_compress_result* results, uint32_t metric, void* stream_handle)
+{
+	return compress_variable_tracks(context, variable_compress_kind_of(desc != nullptr ? desc->max_samples : 0).with_metric(metric), raws, num_instances, desc, blobs, blob_stride_bytes,
+		results, stream_handle);
+}
+
+extern "C" aclhip_status aclhip_compress_tracks_variable_additive_batch(aclhip_context* context, const aclhip_raw_tracks* raws, uint32_t num_instances,
+	const aclhip_compress_variable_desc* desc, void* blobs, uint64_t blob_stride_bytes, aclhip_compress_result* results, const aclhip_additive_base* additive_base, void* stream_handle)
+{
+	return compress_variable_tracks(context, variable_compress_kind_of(desc != nullptr ? desc->max_samples : 0).with_additive_base(additive_base), raws, num_instances, desc, blobs,
+		blob_stride_bytes, results, stream_handle);
 }
 
 extern "C" aclhip_status aclhip_compress_tracks_variable_batch(aclhip_context* context, const aclhip_raw_tracks* raws, uint32_t num_instances,
@@ -499,6 +573,9 @@ aclhip_status find_bit_rates(aclhip_context* context, const transform_compress_k
 		return status;
 	if (const aclhip_status status = check_no_overlap(context, written, 4, nullptr, 0); status != ACLHIP_OK)
 		return status;
+	const byte_range base_range = additive_base_range(kind, num_instances);
+	if (const aclhip_status status = check_no_overlap(context, written, 1, &base_range, 1); status != ACLHIP_OK)
+		return status;
 	return launch_compress(context, &aclhip_context::raw_tracks, num_instances, stream_handle, [&](hipStream_t stream) -> aclhip_status
 	{
 		const compress_launch_shape shape = compress_launch_shape_of(num_instances, desc.max_tracks, 16, kind.phases_knob);
@@ -519,13 +596,14 @@ aclhip_status find_bit_rates(aclhip_context* context, const transform_compress_k
 		const uint32_t segment_blocks = compress_segment_blocks_of(num_instances, max_segments);
 		const uint32_t track_blocks = uint32_t(std::min<unsigned __int128>((unsigned __int128)num_instances * max_segments * desc.max_tracks, 1u << 22));
 		const dim3 block(shape.block_size);
+		const metric_kernels& deciding = deciding_kernels_of(kind);
 		const compress_phase phases[] =
 		{
-			{ k_metric_kernels[kind.metric].shell, dim3(shape.instance_blocks), block, launch.variable.base },
-			{ k_metric_kernels[kind.metric].variable_analyze, shape.track_blocks, block, launch.variable },
-			{ bit_rate_search_segment_kernel, dim3(segment_blocks), block, launch },
-			{ k_metric_kernels[kind.metric].search_local, dim3(track_blocks), dim3(k_wave_size), launch },
-			{ k_metric_kernels[kind.metric].search_object, dim3(segment_blocks), block, launch },
+			{ deciding.shell, dim3(shape.instance_blocks), block, launch.variable.base },
+			{ deciding.variable_analyze, shape.track_blocks, block, launch.variable },
+			{ deciding.search_segment, dim3(segment_blocks), block, launch },
+			{ deciding.search_local, dim3(track_blocks), dim3(k_wave_size), launch },
+			{ deciding.search_object, dim3(segment_blocks), block, launch },
 		};
 		if (!kind.with_levels)
 			return launch_compress_phases(context, stream, shape.phases, phases, 5);
@@ -533,7 +611,7 @@ aclhip_status find_bit_rates(aclhip_context* context, const transform_compress_k
 		{
 			phases[0], phases[1], phases[2], phases[3],
 			{ bit_rate_search_level_kernel, dim3(shape.instance_blocks), block, levels_launch },
-			{ k_metric_kernels[kind.metric].search_object_levels, dim3(segment_blocks), block, levels_launch },
+			{ deciding.search_object_levels, dim3(segment_blocks), block, levels_launch },
 		};
 		return launch_compress_phases(context, stream, shape.phases, level_phases, 6);
 	});
@@ -554,6 +632,14 @@ extern "C" aclhip_status aclhip_find_bit_rates_level_batch(aclhip_context* conte
 {
 	return find_bit_rates(context, bit_rate_level_search_kind_of(desc != nullptr ? desc->max_samples : 0).with_metric(metric), raws, num_instances, desc, bit_rates, instance_stride, segment_stride,
 		results, stream_handle);
+}
+
+extern "C" aclhip_status aclhip_find_bit_rates_additive_batch(aclhip_context* context, const aclhip_raw_tracks* raws, uint32_t num_instances,
+	const aclhip_find_bit_rates_desc* desc, uint8_t* bit_rates, uint64_t instance_stride, uint64_t segment_stride, aclhip_compress_result* results,
+	const aclhip_additive_base* additive_base, void* stream_handle)
+{
+	return find_bit_rates(context, bit_rate_level_search_kind_of(desc != nullptr ? desc->max_samples : 0).with_additive_base(additive_base), raws, num_instances, desc, bit_rates,
+		instance_stride, segment_stride, results, stream_handle);
 }
 
 extern "C" aclhip_status aclhip_find_bit_rates_batch(aclhip_context* context, const aclhip_raw_tracks* raws, uint32_t num_instances,

@@ -20,6 +20,9 @@
 // aclhip_find_bit_rates_level_batch (the levels high and highest, and automatic) is these with one small launch in front of the
 // object phase, bit_rate_search_level_kernel (the level per instance), and the object kernel's second instantiation, kLevels: its
 // first loop tries the wider shapes of increments over the chain. The kernels of the other two calls are the instantiations without.
+// aclhip_find_bit_rates_additive_batch is that call with the kAdditive instantiations of the segment kernel (S0), the local and the
+// object kernel, as of the two launches in front of them: every transform S0 and S2 look at goes through A on the instance's base
+// (kernels_tracks_compress.inl: compress_additive_base) first.
 
 	constexpr uint32_t k_search_num_rates = 25;					// 0 .. 24
 	constexpr uint32_t k_search_invalid_rates = 0x00FFFFFFu;		// { 255, 255, 255, 0 }: no sub-track of the track is animated
@@ -230,7 +233,32 @@
 		return result;
 	}
 
+	// S2's base sample (kAdditive): what sample_streams gives of the base (sample_streams.h:649-673) -- base(b, s) at the same nearest
+	// key, its rotation normalized ONCE MORE, a quat_normalize of the already normalized value, as written there
+	__device__ __forceinline__ qvv search_base_local(const compress_additive_base& base, uint32_t track, uint32_t key)
+	{
+		qvv transform = compress_base_sample(base, track, key);
+		transform.rotation = search_normalize(transform.rotation);
+		return transform;
+	}
+
+	// S2's A: apply_additive_to_base, or without has_scale apply_additive_to_base_no_scale (core/additive_utils.h:145-174): relative is
+	// rtm::qvv_mul_no_scale(additive, base), additive0 and additive1 are transform_add_no_scale; the scale is 1
+	__device__ __forceinline__ qvv search_apply_additive(bool has_scale, const compress_additive_base& base, const qvv& base_transform, const qvv& additive)
+	{
+		if (has_scale)
+			return compress_apply_additive(base, base_transform, additive);
+		qvv result;
+		result.rotation = quat_mul(additive.rotation, base_transform.rotation);
+		const float4 moved = base.format == 1 ? quat_mul_vector3(additive.translation, base_transform.rotation) : additive.translation;
+		result.translation = make_float4(moved.x + base_transform.translation.x, moved.y + base_transform.translation.y, moved.z + base_transform.translation.z, 0.0f);
+		result.scale = make_float4(1.0f, 1.0f, 1.0f, 0.0f);
+		return result;
+	}
+
 	// ---- per (instance, segment): the segment ranges, the segment's shell, the record ------------------------------------------------------------
+	// kAdditive: S0's stretch over A(what the segment's streams hold) with base(b, s), s the index in the clip (rigid_shell_utils.h:220-242)
+	template<bool kAdditive = false>
 	__global__ __launch_bounds__(k_compress_waves_per_block * k_wave_size) void bit_rate_search_segment_kernel(bit_rate_search_launch launch)
 	{
 		const transform_compress_launch& base = launch.variable.base;
@@ -310,6 +338,13 @@
 					base.track_precisions != nullptr ? base.track_precisions[track] : base.precision);
 			__threadfence();		// (a lane's entry is read below by every lane)
 			const uint32_t sample = lane < out.count ? lane : 0u;
+			[[maybe_unused]] compress_additive_base additive = {};
+			[[maybe_unused]] uint32_t base_key = 0;
+			if constexpr (kAdditive)
+			{
+				additive = compress_additive_base_of(base, instance, raw);
+				base_key = compress_base_key(additive, out.start + sample);
+			}
 			for (uint32_t track = num_tracks; track-- != 0;)
 			{
 				const float2 shell = shells[track];
@@ -331,6 +366,8 @@
 				transform.rotation = search_rotation_of(stored[0]);
 				transform.translation = make_float4(stored[1].x, stored[1].y, stored[1].z, 0.0f);
 				transform.scale = make_float4(stored[2].x, stored[2].y, stored[2].z, 0.0f);
+				if constexpr (kAdditive)
+					transform = compress_apply_additive(additive, compress_base_sample(additive, track, base_key), transform);
 				float stretch = 0.0f;
 				if (lane < out.count)
 				{
@@ -358,7 +395,10 @@
 	// size class at a time -- a round takes the lanes that share the size of the first entry not yet tried --: a lane scans the samples
 	// until its error is >= the threshold and keeps the maximum so far; the wave keeps the smallest error and, of equals, the first
 	// entry: what the reference's sequence of strict `<` updates keeps. A class that ends good enough ends the list.
-	template<uint32_t kMetric>
+	// kAdditive: the raw table holds A(raw), and every candidate's S1 transform goes through A at its sample. The segment's base samples
+	// (search_base_local) stay in registers, lane l holding sample l's: the scan's sample is the same in every lane that still scans, so
+	// ten v_readlane fetch it. (In LDS beside the raw table they cost 1 240 bytes, and the fifth block of a CU with them.)
+	template<uint32_t kMetric, bool kAdditive = false>
 	__global__ __launch_bounds__(k_wave_size) void bit_rate_search_local_kernel(bit_rate_search_launch launch)
 	{
 		__shared__ float4 rotation_table[k_search_num_rates * k_variable_max_samples];
@@ -430,9 +470,18 @@
 					}
 				}
 			}
+			[[maybe_unused]] compress_additive_base additive = {};
+			[[maybe_unused]] qvv own_base = {};			// (kAdditive: the base sample that goes with sample `lane` of the segment)
+			if constexpr (kAdditive)
+			{
+				additive = compress_additive_base_of(base, instance, raw);
+				own_base = search_base_local(additive, track, compress_base_key(additive, at.start + (lane < at.count ? lane : 0u)));
+			}
 			if (lane < at.count)
 			{
-				const qvv local = search_raw_local(source, track, at.start + lane);
+				qvv local = search_raw_local(source, track, at.start + lane);
+				if constexpr (kAdditive)
+					local = search_apply_additive(has_scale, additive, own_base, local);
 				float* out = raw_table + lane * 10u;
 				out[0] = local.rotation.x; out[1] = local.rotation.y; out[2] = local.rotation.z; out[3] = local.rotation.w;
 				out[4] = local.translation.x; out[5] = local.translation.y; out[6] = local.translation.z;
@@ -489,6 +538,17 @@
 						lossy.rotation = (flags & 3u) == k_sub_track_animated ? rotation_table[r] : fixed_rotation;
 						lossy.translation = ((flags >> 2) & 3u) == k_sub_track_animated ? make_float4(vector_table[0][t * 3u], vector_table[0][t * 3u + 1u], vector_table[0][t * 3u + 2u], 0.0f) : fixed_translation;
 						lossy.scale = ((flags >> 4) & 3u) == k_sub_track_animated ? make_float4(vector_table[1][s * 3u], vector_table[1][s * 3u + 1u], vector_table[1][s * 3u + 2u], 0.0f) : fixed_scale;
+						if constexpr (kAdditive)
+						{
+							// (a lane that has left the scan has left this loop: `sample` is one value over the lanes that are here)
+							const int from = int(__builtin_amdgcn_readfirstlane(sample));
+							const auto of_lane = [&](float value) __attribute__((always_inline)) -> float { return __uint_as_float(__builtin_amdgcn_readlane(__float_as_uint(value), from)); };
+							qvv base_local;
+							base_local.rotation = make_float4(of_lane(own_base.rotation.x), of_lane(own_base.rotation.y), of_lane(own_base.rotation.z), of_lane(own_base.rotation.w));
+							base_local.translation = make_float4(of_lane(own_base.translation.x), of_lane(own_base.translation.y), of_lane(own_base.translation.z), 0.0f);
+							base_local.scale = make_float4(of_lane(own_base.scale.x), of_lane(own_base.scale.y), of_lane(own_base.scale.z), 0.0f);
+							lossy = search_apply_additive(has_scale, additive, base_local, lossy);
+						}
 						const float sample_error = search_error<kMetric>(has_scale, shell.x, raw_local, lossy);
 						error = sample_error > error ? sample_error : error;
 						if (sample_error >= shell.y)
@@ -576,7 +636,9 @@
 	// first sample whose error is too high) and a butterfly: every decision is wave uniform. A candidate is the table with ONE track's
 	// rates replaced: nothing is copied. The first version recomputes the whole chain for every candidate. Under the matrix metric
 	// (kMetric) a segment with scale takes both chains down as 3x4 matrices, 24 floats a lane; without scale it is the qvvf walk.
-	template<uint32_t kMetric, bool kLevels = false>
+	// kAdditive: where a link's two local transforms are made, both go through A with the link's base sample (search_base_local at the
+	// lane's key) before the walk down the chain: A(raw) is made there once per (link, sample), beside the raw transform it comes from.
+	template<uint32_t kMetric, bool kLevels = false, bool kAdditive = false>
 	__global__ __launch_bounds__(k_compress_waves_per_block * k_wave_size) void bit_rate_search_object_kernel(std::conditional_t<kLevels, bit_rate_search_levels_launch, bit_rate_search_launch> record)
 	{
 		const bit_rate_search_launch& launch = search_launch_of(record);
@@ -615,6 +677,13 @@
 			source.start = at.start;
 			source.count = at.count;
 			source.multiple = variable_split_of(voted.num_out_samples).num_segments > 1;
+			[[maybe_unused]] compress_additive_base additive = {};
+			[[maybe_unused]] uint32_t base_key = 0;
+			if constexpr (kAdditive)
+			{
+				additive = compress_additive_base_of(base, instance, raw);
+				base_key = compress_base_key(additive, at.start + sample);
+			}
 
 			const auto parent_of = [&](uint32_t track) -> uint32_t { return compress_track_parent(base, track, num_tracks); };
 			const uint32_t none = ACLHIP_NO_PARENT;
@@ -659,8 +728,14 @@
 						uint32_t rates = track == replaced ? replacement : row[track];
 						if constexpr (kLevels)
 							rates = track == replaced_1 ? replacement_1 : track == replaced_2 ? replacement_2 : rates;
-						const qvv lossy_local = search_lossy_local(source, track, track_flags[track], rates, sample);
-						const qvv raw_local = search_raw_local(source, track, at.start + sample);
+						qvv lossy_local = search_lossy_local(source, track, track_flags[track], rates, sample);
+						qvv raw_local = search_raw_local(source, track, at.start + sample);
+						if constexpr (kAdditive)
+						{
+							const qvv base_local = search_base_local(additive, track, base_key);
+							raw_local = search_apply_additive(has_scale, additive, base_local, raw_local);
+							lossy_local = search_apply_additive(has_scale, additive, base_local, lossy_local);
+						}
 						raw_object = link == 0 ? raw_local : search_to_object(has_scale, raw_local, raw_object);
 						lossy_object = link == 0 ? lossy_local : search_to_object(has_scale, lossy_local, lossy_object);
 					}

@@ -51,7 +51,13 @@
 		// aclhip_compress_tracks_batch alone (kernels_tracks_compress.inl), behind everything the raw call reads
 		float2* shells;								// [num_instances][max_tracks] { local shell distance, precision } of the rigid shell
 		float2* shell_metadata;						// the caller's copy of them, or null
+		// the _additive entry points alone (kernels_tracks_compress.inl: compress_additive_base), behind everything the others read
+		const uint32_t* base_raws;					// [num_instances] handles of the instances' bases, or null: additive_format is 0
+		uint32_t additive_format;					// an aclhip_additive_format; 0 (none) in every other call
 	};
+
+	// the default-scale bit of the header's word 7: default scale 0 under additive1, 1 otherwise (compress.transform.impl.h:422-423)
+	__device__ __forceinline__ uint32_t transform_compress_default_scale_bit(const transform_compress_launch& launch) { return launch.additive_format == 3 ? 0u : 2u; }
 
 	// wave uniform, decided from the handle, the record and the launch alone: the analysis and the layout come to the same answer
 	__device__ __forceinline__ bool transform_compress_refused(const transform_compress_launch& launch, uint32_t handle, const device_raw_tracks& raw)
@@ -343,9 +349,9 @@
 
 			uint32_t* words = reinterpret_cast<uint32_t*>(blob);
 			transform_compress_write_common_header(words, uint32_t(size), num_tracks, num_samples, raw.sample_rate, num_animated, num_constant);
-			// has_scale | default scale 1 | the three full formats (0) | no database, no trivial defaults (quat_near_identity with a
+			// has_scale | default scale 1 (0 for an additive1 clip) | the three full formats (0) | no database, no trivial defaults (quat_near_identity with a
 			// threshold of 0 holds for no rotation), no stripped key frames | wrap optimized | metadata
-			words[7] = (has_scale ? 1u : 0u) | 2u | (kDropW ? uint32_t(k_rotation_quatf_drop_w_full) << 4 : 0u) | (record.wrap != 0 ? 1u << 30 : 0u) | (with_parents ? 1u << 31 : 0u);
+			words[7] = (has_scale ? 1u : 0u) | transform_compress_default_scale_bit(launch) | (kDropW ? uint32_t(k_rotation_quatf_drop_w_full) << 4 : 0u) | (record.wrap != 0 ? 1u << 30 : 0u) | (with_parents ? 1u << 31 : 0u);
 			words[8] = 1;								// transform_tracks_header: one segment; offsets from its own start
 			words[9] = 0;								// no variable sub-tracks
 			words[17] = uint32_t(sizeof(transform_tracks_header));

@@ -13,7 +13,9 @@
 //                                        sums, every component recomputed from the registered sample and the two ranges, one store
 //   compress_hash_kernel                 (kernels_scalar_compress.inl, unchanged)
 // include/aclhip.h states the definition: fp32, one IEEE operation at a time. No atomics besides the refusal counter and no zero fill:
-// every byte of [0, size) has one writer, the same bytes on every run.
+// every byte of [0, size) has one writer, the same bytes on every run. aclhip_compress_tracks_variable_additive_batch is these with the
+// shell kernel's and the analysis' kAdditive instantiations (kernels_tracks_compress.inl: compress_additive_base); the layout takes the
+// header's default-scale bit from the launch record.
 
 	constexpr uint32_t k_variable_raw_rate = 24;				// core/impl/variable_bit_rates.h:45: 32 bits per component; its format byte says 31
 	constexpr uint32_t k_variable_raw_format = 31;
@@ -172,7 +174,8 @@
 	// default under the rotation and translation the passes before it left -- the verdicts are wave uniform behind their ballots. The
 	// first pass also takes the minimum and maximum of the nine stored components (normalize.transform.h:51-76). kMetric: the error metric
 	// of the six ballots (compress_shell_error, kernels_tracks_compress.inl).
-	template<uint32_t kMetric>
+	// kAdditive: both sides of the six shell errors go through A with the sample's base(b, s) (compress_shell_error_on_base).
+	template<uint32_t kMetric, bool kAdditive = false>
 	__global__ __launch_bounds__(k_compress_waves_per_block * k_wave_size) void variable_compress_analyze_kernel(variable_compress_launch launch)
 	{
 		const transform_compress_launch& base = launch.base;
@@ -197,6 +200,17 @@
 			}
 			const qvv first = tracks_compress_sample(raw.samples, pose_quads, 0, track);
 			const float4 rotation0 = tracks_compress_positive_w(first.rotation);
+			[[maybe_unused]] compress_additive_base additive = {};
+			if constexpr (kAdditive)
+				additive = compress_additive_base_of(base, instance, raw);
+			// the base sample that goes with a sample of the clip (read anew in every pass: nothing of the base is kept)
+			const auto base_of = [&](uint32_t sample) __attribute__((always_inline)) -> qvv
+			{
+				if constexpr (kAdditive)
+					return compress_base_sample(additive, track, compress_base_key(additive, sample));
+				else
+					return qvv{};
+			};
 
 			// the rotation, as in tracks_compress_analyze_kernel, and the ranges
 			float low[9], high[9];
@@ -213,9 +227,10 @@
 				kept.rotation = tracks_compress_positive_w(kept.rotation);
 				qvv other = kept;
 				other.rotation = rotation0;
-				moves = moves || compress_shell_error<kMetric>(shell.x, kept, other) > shell.y;
+				[[maybe_unused]] const qvv base_transform = base_of(sample);
+				moves = moves || compress_shell_error_on_base<kMetric, kAdditive>(shell.x, additive, base_transform, kept, other) > shell.y;
 				other.rotation = make_float4(default_rotation.x, default_rotation.y, default_rotation.z, default_rotation.w);
-				leaves_default = leaves_default || compress_shell_error<kMetric>(shell.x, kept, other) > shell.y;
+				leaves_default = leaves_default || compress_shell_error_on_base<kMetric, kAdditive>(shell.x, additive, base_transform, kept, other) > shell.y;
 				const float stored[9] = { kept.rotation.x, kept.rotation.y, kept.rotation.z, kept.translation.x, kept.translation.y, kept.translation.z, kept.scale.x, kept.scale.y, kept.scale.z };
 				#pragma unroll
 				for (uint32_t c = 0; c < 9; ++c)
@@ -235,9 +250,10 @@
 				kept.rotation = rotation_type == k_sub_track_animated ? tracks_compress_positive_w(kept.rotation) : constant_rotation;
 				qvv other = kept;
 				other.translation = first.translation;
-				moves = moves || compress_shell_error<kMetric>(shell.x, kept, other) > shell.y;
+				[[maybe_unused]] const qvv base_transform = base_of(sample);
+				moves = moves || compress_shell_error_on_base<kMetric, kAdditive>(shell.x, additive, base_transform, kept, other) > shell.y;
 				other.translation = make_float4(default_translation.x, default_translation.y, default_translation.z, 0.0f);
-				leaves_default = leaves_default || compress_shell_error<kMetric>(shell.x, kept, other) > shell.y;
+				leaves_default = leaves_default || compress_shell_error_on_base<kMetric, kAdditive>(shell.x, additive, base_transform, kept, other) > shell.y;
 			}
 			const uint32_t translation_type = transform_compress_type(__ballot(moves) == 0, __ballot(leaves_default) == 0);
 
@@ -252,9 +268,10 @@
 					kept.translation = constant_translation;
 				qvv other = kept;
 				other.scale = first.scale;
-				moves = moves || compress_shell_error<kMetric>(shell.x, kept, other) > shell.y;
+				[[maybe_unused]] const qvv base_transform = base_of(sample);
+				moves = moves || compress_shell_error_on_base<kMetric, kAdditive>(shell.x, additive, base_transform, kept, other) > shell.y;
 				other.scale = make_float4(default_scale.x, default_scale.y, default_scale.z, 0.0f);
-				leaves_default = leaves_default || compress_shell_error<kMetric>(shell.x, kept, other) > shell.y;
+				leaves_default = leaves_default || compress_shell_error_on_base<kMetric, kAdditive>(shell.x, additive, base_transform, kept, other) > shell.y;
 			}
 			const uint32_t scale_type = transform_compress_type(__ballot(moves) == 0, __ballot(leaves_default) == 0);
 
@@ -469,9 +486,9 @@
 			base.results[instance] = make_uint2(ACLHIP_COMPRESS_OK, uint32_t(size));
 
 			transform_compress_write_common_header(words, uint32_t(size), num_tracks, num_samples, raw.sample_rate, num_animated, num_constant);
-			// has_scale | default scale 1 | vector3f_variable twice | quatf_drop_w_variable | no database, no trivial defaults, no stripped
+			// has_scale | default scale 1 (0 for an additive1 clip) | vector3f_variable twice | quatf_drop_w_variable | no database, no trivial defaults, no stripped
 			// key frames | wrap optimized | metadata
-			words[7] = (has_scale ? 1u : 0u) | 2u | (uint32_t(k_vector_vector3f_variable) << 2) | (uint32_t(k_vector_vector3f_variable) << 3)
+			words[7] = (has_scale ? 1u : 0u) | transform_compress_default_scale_bit(base) | (uint32_t(k_vector_vector3f_variable) << 2) | (uint32_t(k_vector_vector3f_variable) << 3)
 				| (uint32_t(k_rotation_quatf_drop_w_variable) << 4) | (voted.wrap != 0 ? 1u << 30 : 0u) | (with_parents ? 1u << 31 : 0u);
 			words[8] = num_segments;					// transform_tracks_header; offsets from its own start
 			words[9] = num_variable;

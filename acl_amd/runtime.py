@@ -65,6 +65,7 @@ EXPORTED_SYMBOLS = [
     "aclhip_find_bit_rates_workspace_bytes", "aclhip_find_bit_rates_batch",
     "aclhip_compress_tracks_metric_batch", "aclhip_compress_tracks_variable_metric_batch", "aclhip_find_bit_rates_metric_batch",
     "aclhip_find_bit_rates_level_workspace_bytes", "aclhip_find_bit_rates_level_batch",
+    "aclhip_compress_tracks_additive_batch", "aclhip_compress_tracks_variable_additive_batch", "aclhip_find_bit_rates_additive_batch",
 ]
 
 
@@ -306,6 +307,11 @@ class FindBitRatesDesc(ctypes.Structure):
         ("precision", ctypes.c_float), ("shell_distance", ctypes.c_float), ("workspace", ctypes.c_void_p), ("shell_metadata", ctypes.c_void_p),
         ("level", ctypes.c_uint32), ("reserved_word", ctypes.c_uint32), ("reserved", ctypes.c_uint64 * 2),
     ]
+
+
+class AdditiveBase(ctypes.Structure):
+    """aclhip_additive_base: base_raws is a device address, uint32 [num_instances] handles of registered raw track arrays"""
+    _fields_ = [("base_raws", ctypes.c_void_p), ("additive_format", ctypes.c_uint32), ("reserved_word", ctypes.c_uint32), ("reserved", ctypes.c_uint64 * 2)]
 
 
 COMPRESSION_LEVELS = {"lowest": 0, "low": 1, "medium": 2, "high": 3, "highest": 4, "automatic": 100}     # acl::compression_level8 (aclhip_find_bit_rates_desc::level)
@@ -577,6 +583,9 @@ def load_library():
     lib.aclhip_find_bit_rates_level_workspace_bytes.argtypes = [u32, u32, u32]
     lib.aclhip_find_bit_rates_level_workspace_bytes.restype = u64
     lib.aclhip_find_bit_rates_level_batch.argtypes = [vp, vp, u32, ctypes.POINTER(FindBitRatesDesc), vp, u64, u64, vp, u32, vp]
+    lib.aclhip_compress_tracks_additive_batch.argtypes = [vp, vp, u32, ctypes.POINTER(CompressTracksDesc), vp, u64, vp, ctypes.POINTER(AdditiveBase), vp]
+    lib.aclhip_compress_tracks_variable_additive_batch.argtypes = [vp, vp, u32, ctypes.POINTER(CompressVariableDesc), vp, u64, vp, ctypes.POINTER(AdditiveBase), vp]
+    lib.aclhip_find_bit_rates_additive_batch.argtypes = [vp, vp, u32, ctypes.POINTER(FindBitRatesDesc), vp, u64, u64, vp, ctypes.POINTER(AdditiveBase), vp]
     _lib = lib
     return lib
 
@@ -1258,6 +1267,25 @@ class Context:
         self._check(self._lib.aclhip_find_bit_rates_level_batch(self._handle, raws_ptr, num_instances, ctypes.byref(desc) if desc is not None else None,
                                                                 bit_rates_ptr, instance_stride, segment_stride, results_ptr, int(metric) & 0xFFFFFFFF, stream))
 
+    def compress_tracks_additive_batch(self, raws_ptr, num_instances, desc, blobs_ptr, blob_stride_bytes, results_ptr, additive_base, stream=None):
+        """aclhip_compress_tracks_additive_batch: compress_tracks_batch for additive clips -- every decision taken after the clip has been
+        applied onto its base; `additive_base` is an AdditiveBase (ADDITIVE_NONE: compress_tracks_batch itself)."""
+        self._check(self._lib.aclhip_compress_tracks_additive_batch(self._handle, raws_ptr, num_instances, ctypes.byref(desc) if desc is not None else None,
+                                                                    blobs_ptr, blob_stride_bytes, results_ptr, ctypes.byref(additive_base) if additive_base is not None else None, stream))
+
+    def compress_tracks_variable_additive_batch(self, raws_ptr, num_instances, desc, blobs_ptr, blob_stride_bytes, results_ptr, additive_base, stream=None):
+        """aclhip_compress_tracks_variable_additive_batch: compress_tracks_variable_batch for additive clips (compress_tracks_additive_batch)."""
+        self._check(self._lib.aclhip_compress_tracks_variable_additive_batch(self._handle, raws_ptr, num_instances, ctypes.byref(desc) if desc is not None else None,
+                                                                             blobs_ptr, blob_stride_bytes, results_ptr,
+                                                                             ctypes.byref(additive_base) if additive_base is not None else None, stream))
+
+    def find_bit_rates_additive_batch(self, raws_ptr, num_instances, desc, bit_rates_ptr, instance_stride, segment_stride, results_ptr, additive_base, stream=None):
+        """aclhip_find_bit_rates_additive_batch: find_bit_rates_level_batch under the qvvf metric for additive clips: both errors of the
+        search measured on the base. Its workspace is find_bit_rates_level_workspace_bytes."""
+        self._check(self._lib.aclhip_find_bit_rates_additive_batch(self._handle, raws_ptr, num_instances, ctypes.byref(desc) if desc is not None else None,
+                                                                   bit_rates_ptr, instance_stride, segment_stride, results_ptr,
+                                                                   ctypes.byref(additive_base) if additive_base is not None else None, stream))
+
     def compress_tracks_batch(self, raws_ptr, num_instances, desc, blobs_ptr, blob_stride_bytes, results_ptr, stream=None):
         """aclhip_compress_tracks_batch: compress_track_list with quatf_full or quatf_drop_w_full rotations (the rigid shell, the looping vote,
         constant and default rotations by the error metric) of the raw track arrays named at raws_ptr (device uint32 [num_instances]) into
@@ -1892,6 +1920,29 @@ def _with_metric(launch, metric_launch, metric):
     return lambda *arguments, **keywords: metric_launch(*arguments, metric=metric, **keywords)
 
 
+def _with_additive_base(ctx, launch, additive_launch, handles, additive_base, additive_format, metric):
+    """The context's method a transform compressor goes through when it may have an additive base: `launch` itself without one
+    (additive_base None and ADDITIVE_NONE: today's call, untouched), else `additive_launch` with an AdditiveBase whose handles -- one
+    for every instance, or one per instance -- are uploaded here. Returns (the method, what must stay alive until it has run)."""
+    if additive_base is None and additive_format == ADDITIVE_NONE:
+        return launch, None
+    if metric != ERROR_METRIC_QVVF:
+        raise ValueError("an additive base goes with the qvvf error metric: the reference has no additive matrix metric")
+    import torch
+    record = AdditiveBase()
+    record.additive_format = int(additive_format) & 0xFFFFFFFF
+    d_bases = None
+    if additive_base is not None:
+        bases = np.atleast_1d(np.asarray(additive_base, dtype=np.uint32))
+        if len(bases) == 1:
+            bases = np.repeat(bases, len(handles))
+        if len(bases) != len(handles):
+            raise ValueError(f"{len(bases)} additive bases for {len(handles)} instances: one handle, or one per instance")
+        d_bases = torch.from_numpy(np.ascontiguousarray(bases).view(np.int32)).to(torch.device("cuda", ctx.device_index))
+        record.base_raws = d_bases.data_ptr()
+    return (lambda *arguments, **keywords: additive_launch(*arguments, additive_base=record, **keywords)), (record, d_bases)
+
+
 def _compress_transform_tracks(ctx, launch, workspace_bytes, desc, raws, flags, default_pose, parents, precision, shell_distance, track_precisions, track_shell_distances,
                                bound=None, tables=None):
     """What compress_raw_tracks, compress_tracks and compress_tracks_variable share: `desc` (any of the three structs: the fields have one
@@ -1933,19 +1984,25 @@ def compress_tracks_workspace_bytes(num_instances, max_tracks):
 
 
 def compress_tracks(ctx, raws, rotation_format=ROTATION_QUATF_DROP_W_FULL, default_pose=None, parents=None, precision=1.0e-4, shell_distance=1.0, track_precisions=None,
-                    track_shell_distances=None, optimize_loops=False, include_parent_track_indices=False, include_track_descriptions=False, metric=ERROR_METRIC_QVVF):
+                    track_shell_distances=None, optimize_loops=False, include_parent_track_indices=False, include_track_descriptions=False, metric=ERROR_METRIC_QVVF,
+                    additive_base=None, additive_format=ADDITIVE_NONE):
     """acl::compress_track_list with quatf_drop_w_full (or quatf_full) rotations and vector3f_full translations and scales for raw track
     arrays as one launch, like compress_raw_tracks: `raws` is a handle or a list of handles. With quatf_drop_w_full the parents, precisions
     and shell distances make the rigid shell at which constant and default rotations and the looping vote (optimize_loops) are decided;
     every parent index is smaller than its child's. Rows are sized from aclhip_transform_compress_bound. Returns a list of 16 byte
     aligned numpy uint8 blobs. `metric` is an aclhip_error_metric: ERROR_METRIC_QVVF_MATRIX3X4F decides the vote and the rotations with
-    the reference's matrix metric (quatf_full uses none). Raises RuntimeError with the reference's message when a sample is not finite
+    the reference's matrix metric (quatf_full uses none). `additive_base` (a raw track array's handle, or one per instance) and
+    `additive_format` (ADDITIVE_RELATIVE, _ADDITIVE0, _ADDITIVE1) compress an additive clip against its base
+    (aclhip_compress_tracks_additive_batch): every decision is taken on the clip applied onto the base. Raises RuntimeError with the reference's message when a sample is not finite
     (a zero quaternion included), ValueError when an instance is refused. Synchronous; the buffers are torch tensors on the context's device."""
     flags = ((COMPRESS_OPTIMIZE_LOOPS if optimize_loops else 0) | (COMPRESS_INCLUDE_PARENT_TRACK_INDICES if include_parent_track_indices else 0)
              | (COMPRESS_INCLUDE_TRACK_DESCRIPTIONS if include_track_descriptions else 0))
     desc = CompressTracksDesc()
     desc.rotation_format, desc.translation_format, desc.scale_format = int(rotation_format), VECTOR_VECTOR3F_FULL, VECTOR_VECTOR3F_FULL
-    return _compress_transform_tracks(ctx, _with_metric(ctx.compress_tracks_batch, ctx.compress_tracks_metric_batch, metric), compress_tracks_workspace_bytes, desc, raws, flags, default_pose, parents, precision, shell_distance,
+    handles = np.atleast_1d(np.asarray(raws, dtype=np.uint32))
+    launch, alive = _with_additive_base(ctx, _with_metric(ctx.compress_tracks_batch, ctx.compress_tracks_metric_batch, metric), ctx.compress_tracks_additive_batch, handles,
+                                        additive_base, additive_format, metric)          # (alive until the launch has run)
+    return _compress_transform_tracks(ctx, launch, compress_tracks_workspace_bytes, desc, raws, flags, default_pose, parents, precision, shell_distance,
                                       track_precisions, track_shell_distances)
 
 
@@ -1975,18 +2032,20 @@ def find_bit_rates_level_workspace_bytes(num_instances, max_tracks, max_samples)
 
 
 def _find_bit_rates(ctx, handles, infos, level, flags, default_pose, parents, precision, shell_distance, track_precisions, track_shell_distances, tables=None,
-                    metric=ERROR_METRIC_QVVF):
+                    metric=ERROR_METRIC_QVVF, additive_base=None, additive_format=ADDITIVE_NONE):
     """The search over `handles` into a zero-filled device table uint8 [instances, segments, tracks, 4] of the largest array's segments
     and tracks: (the table, still on the device, and the results as a host array [instances, 2]). The levels lowest to medium go
     through aclhip_find_bit_rates_batch or its _metric form, as before; high, highest and automatic through
-    aclhip_find_bit_rates_level_batch, whose results carry the level that was searched. Synchronous."""
+    aclhip_find_bit_rates_level_batch, whose results carry the level that was searched; with an additive base every level goes through
+    aclhip_find_bit_rates_additive_batch, which is the level search. Synchronous."""
     import torch
     device = torch.device("cuda", ctx.device_index)
     desc = FindBitRatesDesc()
     if level not in COMPRESSION_LEVELS and level not in COMPRESSION_LEVELS.values():
         raise ValueError(f"a compression level of {level!r}: one of {sorted(COMPRESSION_LEVELS, key=COMPRESSION_LEVELS.get)}, 0 to 4 or {LEVEL_AUTOMATIC}")
     desc.level = COMPRESSION_LEVELS.get(level, level)
-    with_levels = desc.level > COMPRESSION_LEVELS["medium"]
+    with_base = additive_base is not None or additive_format != ADDITIVE_NONE
+    with_levels = desc.level > COMPRESSION_LEVELS["medium"] or with_base
     desc.flags, desc.precision, desc.shell_distance = flags, float(precision), float(shell_distance)
     desc.max_tracks = max(int(info.num_tracks) for info in infos)
     desc.max_samples = max(int(info.num_samples) for info in infos)
@@ -2001,18 +2060,22 @@ def _find_bit_rates(ctx, handles, infos, level, flags, default_pose, parents, pr
     workspace_bytes = find_bit_rates_level_workspace_bytes if with_levels else find_bit_rates_workspace_bytes
     d_workspace = torch.zeros(workspace_bytes(num_instances, desc.max_tracks, desc.max_samples) + 16, dtype=torch.uint8, device=device)
     desc.workspace = d_workspace.data_ptr()
-    if with_levels:
+    alive = None
+    if with_base:
+        launch, alive = _with_additive_base(ctx, None, ctx.find_bit_rates_additive_batch, handles, additive_base, additive_format, metric)
+    elif with_levels:
         def launch(*arguments, **keywords):
             return ctx.find_bit_rates_level_batch(*arguments, metric=metric, **keywords)
     else:
         launch = _with_metric(ctx.find_bit_rates_batch, ctx.find_bit_rates_metric_batch, metric)
     launch(d_raws.data_ptr(), num_instances, desc, d_rates.data_ptr(), num_segments * desc.max_tracks * 4, desc.max_tracks * 4, d_results.data_ptr(), stream=stream.cuda_stream)
     stream.synchronize()
+    del alive
     return d_rates, d_results.cpu().numpy().view(np.uint32).reshape(num_instances, 2)
 
 
 def find_bit_rates(ctx, raws, level="medium", default_pose=None, parents=None, precision=1.0e-4, shell_distance=1.0, track_precisions=None, track_shell_distances=None,
-                   optimize_loops=False, metric=ERROR_METRIC_QVVF, return_levels=False):
+                   optimize_loops=False, metric=ERROR_METRIC_QVVF, return_levels=False, additive_base=None, additive_format=ADDITIVE_NONE):
     """acl::find_optimal_bit_rates -- the bit rate search of compress_track_list with quatf_drop_w_variable / vector3f_variable /
     vector3f_variable at `level`: "lowest", "low" and "medium" (one search), "high", "highest", or "automatic", the reference's default,
     which picks one of the last three per array (medium above 500 samples, else by the longest bone chain) -- for raw track arrays as
@@ -2021,19 +2084,22 @@ def find_bit_rates(ctx, raws, level="medium", default_pose=None, parents=None, p
     { rotation, translation, scale, 0 } entries over the segments and tracks of the largest array, zero-filled before the launch: 255
     marks a constant or default sub-track, rows and entries an instance does not have stay 0. It is the table compress_tracks_variable
     takes. `metric` is the aclhip_error_metric the search optimises: ERROR_METRIC_QVVF_MATRIX3X4F is the reference's matrix metric, what
-    clip_error and raw_clip_error measure with metric=1. Raises RuntimeError with the reference's message when a sample is not finite,
-    ValueError when an instance is refused. Synchronous; the buffers are torch tensors on the context's device."""
+    clip_error and raw_clip_error measure with metric=1. `additive_base` (a handle, or one per instance) and `additive_format` search
+    for an additive clip against its base (aclhip_find_bit_rates_additive_batch): both errors are measured on the clip applied onto the
+    base, what raw_clip_error(additive_base=, additive_format=) measures. Raises RuntimeError with the reference's message when a sample
+    is not finite, ValueError when an instance is refused. Synchronous; the buffers are torch tensors on the context's device."""
     handles = np.atleast_1d(np.asarray(raws, dtype=np.uint32))
     infos = [ctx.raw_tracks_info(int(handle)) for handle in handles]
     if len(handles) == 0:
         return np.zeros((0, 0, 0, 4), dtype=np.uint8)
     d_rates, results = _find_bit_rates(ctx, handles, infos, level, COMPRESS_OPTIMIZE_LOOPS if optimize_loops else 0, default_pose, parents, precision, shell_distance,
-                                       track_precisions, track_shell_distances, metric=metric)
+                                       track_precisions, track_shell_distances, metric=metric, additive_base=additive_base, additive_format=additive_format)
     _raise_for_search_results(handles, results)
     if return_levels:
         # (the calls without the levels leave 0 in that word: their one search is the level they were asked for)
         asked = COMPRESSION_LEVELS.get(level, level)
-        return d_rates.cpu().numpy(), results[:, 1].copy() if asked > COMPRESSION_LEVELS["medium"] else np.full(len(handles), asked, dtype=np.uint32)
+        with_levels = asked > COMPRESSION_LEVELS["medium"] or additive_base is not None or additive_format != ADDITIVE_NONE
+        return d_rates.cpu().numpy(), results[:, 1].copy() if with_levels else np.full(len(handles), asked, dtype=np.uint32)
     return d_rates.cpu().numpy()
 
 
@@ -2047,7 +2113,7 @@ def _raise_for_search_results(handles, results):
 
 def compress_tracks_variable(ctx, raws, bit_rates=(16, 16, 16), default_pose=None, parents=None, precision=1.0e-4, shell_distance=1.0, track_precisions=None,
                              track_shell_distances=None, optimize_loops=False, include_parent_track_indices=False, include_track_descriptions=False, level="medium",
-                             metric=ERROR_METRIC_QVVF, return_levels=False):
+                             metric=ERROR_METRIC_QVVF, return_levels=False, additive_base=None, additive_format=ADDITIVE_NONE):
     """acl::compress_track_list with quatf_drop_w_variable rotations and vector3f_variable translations and scales AT GIVEN BIT RATES for
     raw track arrays as one launch, like compress_tracks: `raws` is a handle or a list of handles. bit_rates is three uniform rates
     (rotation, translation, scale: 0 .. 24), or a uint8 table of { rotation, translation, scale, 0 } entries: [tracks, 4] shared by every
@@ -2055,7 +2121,8 @@ def compress_tracks_variable(ctx, raws, bit_rates=(16, 16, 16), default_pose=Non
     variable_compress_num_segments(samples) rows and the tracks of the largest array. bit_rates="search" runs find_bit_rates at `level`
     with the same settings first and compresses at its table, which stays on the device: the reference's compress_track_list at
     that level ("automatic" is its default); with return_levels the result is (the blobs, the level that was searched per instance). `metric` is the aclhip_error_metric of the vote, the compaction and the search (find_bit_rates). Rows are
-    sized from aclhip_variable_compress_bound.
+    sized from aclhip_variable_compress_bound. `additive_base` (a handle, or one per instance) and `additive_format` compress an additive
+    clip against its base (aclhip_compress_tracks_variable_additive_batch); with bit_rates="search" both steps get the base.
     Returns a list of 16 byte aligned numpy uint8 blobs in the format the fast decode paths read. Raises RuntimeError with the
     reference's message when a sample is not finite, ValueError when an instance is refused (a rate above 24, a rate of 0 in a blob of
     one segment included). Synchronous; the buffers are torch tensors on the context's device."""
@@ -2076,10 +2143,11 @@ def compress_tracks_variable(ctx, raws, bit_rates=(16, 16, 16), default_pose=Non
             raise ValueError('bit_rates is three rates, a table or "search"')
         tables = _upload_track_tables(ctx, default_pose, parents, track_precisions, track_shell_distances)         # (once, for both calls)
         d_rates, results = _find_bit_rates(ctx, handles, infos, level, flags, default_pose, parents, precision, shell_distance, track_precisions, track_shell_distances, tables,
-                                           metric=metric)
+                                           metric=metric, additive_base=additive_base, additive_format=additive_format)
         _raise_for_search_results(handles, results)
         asked = COMPRESSION_LEVELS.get(level, level)
-        levels = results[:, 1].copy() if asked > COMPRESSION_LEVELS["medium"] else np.full(len(handles), asked, dtype=np.uint32)
+        with_levels = asked > COMPRESSION_LEVELS["medium"] or additive_base is not None or additive_format != ADDITIVE_NONE
+        levels = results[:, 1].copy() if with_levels else np.full(len(handles), asked, dtype=np.uint32)
         desc.bit_rates = d_rates.data_ptr()                                                 # (alive until the launch has run)
         desc.bit_rate_segment_stride = d_rates.shape[2] * 4
         desc.bit_rate_instance_stride = d_rates.shape[1] * d_rates.shape[2] * 4
@@ -2100,7 +2168,9 @@ def compress_tracks_variable(ctx, raws, bit_rates=(16, 16, 16), default_pose=Non
 
     def workspace_bytes(num_instances, max_tracks):
         return compress_variable_workspace_bytes(num_instances, max_tracks, desc.max_samples)
-    blobs = _compress_transform_tracks(ctx, _with_metric(ctx.compress_tracks_variable_batch, ctx.compress_tracks_variable_metric_batch, metric), workspace_bytes, desc, raws, flags, default_pose, parents, precision, shell_distance,
+    launch, alive = _with_additive_base(ctx, _with_metric(ctx.compress_tracks_variable_batch, ctx.compress_tracks_variable_metric_batch, metric),
+                                        ctx.compress_tracks_variable_additive_batch, handles, additive_base, additive_format, metric)      # (alive until the launch has run)
+    blobs = _compress_transform_tracks(ctx, launch, workspace_bytes, desc, raws, flags, default_pose, parents, precision, shell_distance,
                                        track_precisions, track_shell_distances, bound=variable_compress_bound, tables=tables)
     return (blobs, levels) if return_levels else blobs
 

@@ -1951,7 +1951,9 @@ uint64_t aclhip_transform_compress_workspace_bytes(uint32_t num_instances, uint3
  *   Left out (nothing here precludes them): the variable formats and everything they need (segmenting, range reduction, the bit rate
  * search; the error metric over the hierarchy and quatf_drop_w_full exist: aclhip_compress_tracks_batch, below; so do the variable formats at given
  * bit rates, with segmenting and range reduction: aclhip_compress_tracks_variable_batch, below; so does the search that finds those rates:
- * aclhip_find_bit_rates_batch, below); additive bases; track and list names; output_index remapping and
+ * aclhip_find_bit_rates_batch, below); additive bases (they exist for the formats that decide by a metric:
+ * aclhip_compress_tracks_additive_batch, below; a raw blob of an additive1 clip would need only the header's default-scale bit); track
+ * and list names; output_index remapping and
  * stripped tracks; a flag that normalizes rotations within a tolerance; the C++ mirror in aclhip.hpp.
  *   What it costs (no time is promised; one MI355X, 4 096 instances over 256 distinct arrays of 100 tracks x 301 samples -- the bench's
  * pose shape, 91 % of the rotations, a third of the translations and a tenth of the scales animated: 5.92 GB of samples, 2.43 GB of
@@ -2050,7 +2052,7 @@ uint64_t aclhip_compress_tracks_workspace_bytes(uint32_t num_instances, uint32_t
  * stream with three words per rotation; the hash. No atomics besides the refusal counter: the same bytes on every run.
  *   Left out: the variable formats, segmenting, range reduction and the bit rate search (all exist since:
  * aclhip_compress_tracks_variable_batch and aclhip_find_bit_rates_batch, below; so does the matrix error metric:
- * aclhip_compress_tracks_metric_batch, below); additive bases; track and list names; output_index
+ * aclhip_compress_tracks_metric_batch, below; so do additive bases: aclhip_compress_tracks_additive_batch, below); track and list names; output_index
  * remapping; the C++ mirror in aclhip.hpp. What it costs: profiles/compress_tracks.md. */
 aclhip_status aclhip_compress_tracks_batch(aclhip_context* context, const aclhip_raw_tracks* raws /* DEVICE [num_instances] */,
 	uint32_t num_instances, const aclhip_compress_tracks_desc* desc, void* blobs /* DEVICE */, uint64_t blob_stride_bytes,
@@ -2169,7 +2171,8 @@ uint64_t aclhip_compress_variable_workspace_bytes(uint32_t num_instances, uint32
  * the refusal counter and no zero fill: the same bytes on every run.
  *   Left out: the bit rate search (a call of its own: aclhip_find_bit_rates_batch, below, writes the table this call reads); mixed full /
  * variable formats; keyframe stripping, database support and the
- * contributing error; additive bases (the matrix error metric: aclhip_compress_tracks_variable_metric_batch, below); track and list names; output_index remapping; the C++ mirror in
+ * contributing error (the matrix error metric: aclhip_compress_tracks_variable_metric_batch, below; additive bases:
+ * aclhip_compress_tracks_variable_additive_batch, below); track and list names; output_index remapping; the C++ mirror in
  * aclhip.hpp; anything against the serial hash. What it costs: profiles/compress_variable.md. */
 aclhip_status aclhip_compress_tracks_variable_batch(aclhip_context* context, const aclhip_raw_tracks* raws /* DEVICE [num_instances] */,
 	uint32_t num_instances, const aclhip_compress_variable_desc* desc, void* blobs /* DEVICE */, uint64_t blob_stride_bytes,
@@ -2270,8 +2273,8 @@ uint64_t aclhip_find_bit_rates_workspace_bytes(uint32_t num_instances, uint32_t 
  *   Five launches (DESIGN.md 4.7 "Bit rate search"): the shell and the analysis of the variable call, unchanged; per (instance, segment)
  * the segment ranges and S0; per (instance, segment, track) S3 from a table of S1 in LDS, lanes over the tuples of a size; per (instance,
  * segment) S4 with lanes over the samples. No atomics besides the refusal counter and no zero fill: the same bytes on every run.
- *   Left out: the levels high and highest (chains with two and three increments: aclhip_find_bit_rates_level_batch, below); additive bases (the matrix error metric:
- * aclhip_find_bit_rates_metric_batch, below); the
+ *   Left out: the levels high and highest (chains with two and three increments: aclhip_find_bit_rates_level_batch, below; the matrix error metric:
+ * aclhip_find_bit_rates_metric_batch, below; additive bases: aclhip_find_bit_rates_additive_batch, below); the
  * contributing error and keyframe stripping. What it costs: profiles/bit_rate_search.md. */
 aclhip_status aclhip_find_bit_rates_batch(aclhip_context* context, const aclhip_raw_tracks* raws /* DEVICE [num_instances] */,
 	uint32_t num_instances, const aclhip_find_bit_rates_desc* desc, uint8_t* bit_rates /* DEVICE */, uint64_t instance_stride,
@@ -2377,6 +2380,92 @@ uint64_t aclhip_find_bit_rates_level_workspace_bytes(uint32_t num_instances, uin
 aclhip_status aclhip_find_bit_rates_level_batch(aclhip_context* context, const aclhip_raw_tracks* raws /* DEVICE [num_instances] */,
 	uint32_t num_instances, const aclhip_find_bit_rates_desc* desc, uint8_t* bit_rates /* DEVICE */, uint64_t instance_stride,
 	uint64_t segment_stride, aclhip_compress_result* results /* DEVICE [num_instances] */, uint32_t metric, void* stream);
+
+/* ---- the transform compressors for additive clips: compressed against their base -------------------------------------------------------------
+ * aclhip_compress_tracks_batch, aclhip_compress_tracks_variable_batch and aclhip_find_bit_rates_level_batch with the one input of the
+ * reference's call they leave out: compress_track_list(allocator, track_list, settings, additive_base_track_list, additive_format, ...)
+ * (compression/impl/compress.impl.h:68-88). Every decision the reference takes for an additive clip is measured AFTER the clip has been
+ * applied onto its base -- the rigid shell, the looping vote, constant and default compaction, the per-segment shell and both errors of
+ * the search --, and for additive1 the header says default scale 0. Without the base a `relative` clip's rotation error is not levered
+ * by the base's translation and an additive1 scale of 0.001 is not "1.001 times the base": the search spends its bits in the wrong
+ * places. What a clip is compressed towards is then what runtime.raw_clip_error(additive_base=, additive_format=) measures of it.
+ * This is an addition to ABI version 6: new names only; no existing struct, function, message or byte of an existing call changes.
+ *   The metric is the reference's additive_qvvf_transform_error_metric<format> (transform_error_metrics.h:469-524): the qvvf metric
+ * with apply_additive_to_base / apply_additive_to_base_no_scale in front. The reference has no additive matrix metric (the base class
+ * asserts "Not implemented"): these calls take no metric argument. The search call is the level search: desc->level is 0 to 4 or
+ * ACLHIP_LEVEL_AUTOMATIC, and the second result word is the level searched.
+ *   With additive_format == ACLHIP_ADDITIVE_NONE the calls give exactly the base calls' results by the same kernels -- the base calls
+ * being the three named above, the search with ACLHIP_METRIC_QVVF --, whatever base_raws is, NULL included. All six are fronts of one
+ * host path.
+ *   Everything not stated here is the base call's, word for word: the descs, refusals, statuses, alignment and overlap rules, stream
+ * ordering, "uploads nothing", graph capture and the workspace: the existing *_workspace_bytes functions serve these calls. Nothing
+ * of the base is stored: a base sample is read and normalized where it is used, and the normalization is a pure function of the sample.
+ *   ACLHIP_ERROR_INVALID_ARGUMENT with a message, before any device call: a NULL aclhip_additive_base; an unknown format; reserved
+ * fields that are not 0; a format other than NONE with base_raws NULL, or not 4 byte aligned; base_raws (num_instances handles)
+ * overlapping anything the call writes; rotation_format == 0 (quatf_full) with a format other than NONE: the raw settings decide
+ * nothing by a metric.
+ *   ACLHIP_COMPRESS_REFUSED per instance, counted, before any write to its row: a base handle that is no live raw track array; a base
+ * with fewer tracks than the instance (the reference would read out of bounds). ACLHIP_COMPRESS_NOT_FINITE: a base with a used lane
+ * (rotation x, y, z, w as normalized; translation and scale x, y, z) not finite in any of ITS tracks and samples -- the reference's
+ * "Some base samples are not finite". A base may have any sample count and any sample rate of its own.
+ *   The definition, as the changes to steps 1 to 5 and 10 of aclhip_compress_tracks_batch / _variable_batch and to S0 to S4 of the search;
+ * nothing else of them changes.
+ *   base(b, s), the base's sample of track b that goes with sample s of the instance. Its rotation is normalize() of step 1
+ *      (clip_context.impl.h:150: the base goes through the same initialize_clip_context; it is NOT made of positive w: no
+ *      convert_rotation_streams runs over the base), translation and scale as registered. With S_b the base's sample count, rate_b its
+ *      rate and D, D_b the two arrays' finite durations as registered: S_b == 1: key 0. Else t = s / rate; t = t < D ? t : D
+ *      (rtm::scalar_min); x = ((t / D) * D_b) * rate_b; key0 = (uint32)x (never above S_b - 1 inside the definition; the kernels take
+ *      S_b - 1 then), key1 = min(key0 + 1, S_b - 1); key = floorf((x - (float)key0) + 0.5F) == 0.0F ? key0 : key1
+ *      (get_uniform_sample_key: find_linear_interpolation_samples_with_sample_rate with sample_rounding_policy::nearest, never looping,
+ *      over the base's own count and rate; sample_streams.h:557-601, interpolation_utils.impl.h:143-201). In segments s is the index in
+ *      the clip. The base is never interpolated. An instance of ONE sample has D = 0 and x is 0 / 0: the reference converts that NaN
+ *      to an integer, which C++ leaves undefined; its x86 build gets key0 = 0 and an alpha that fails `== 0`: key = min(1, S_b - 1),
+ *      which is what this library states and does.
+ *   A(x) = apply_additive_to_base(format, base(b, s), x) (core/additive_utils.h:128-162): RELATIVE qvv_mul(x, base), always its
+ *      quaternion route as everywhere else in the compressors: {quat_mul(x.q, base.q), quat_mul_vector3(x.t * base.s, base.q) + base.t,
+ *      x.s * base.s}; ADDITIVE0 {quat_mul(x.q, base.q), x.t + base.t, x.s * base.s}; ADDITIVE1 the same with (1.0F + x.s) * base.s.
+ *      Where the definition uses the _no_scale arithmetic (S2 without has_scale) it is apply_additive_to_base_no_scale (:145-174):
+ *      RELATIVE {quat_mul(x.q, base.q), quat_mul_vector3(x.t, base.q) + base.t, 1}, the other two {quat_mul(x.q, base.q), x.t + base.t, 1}.
+ *   Step 2, the clip's shell (rigid_shell_utils.h:93-138): the stretch is taken over A(sample) in the place of the sample. The finite
+ *      test of step 1 is of the instance's own samples, as before, and of the base's.
+ *   Step 3, the vote (optimize_looping.transform.h:115-173): shell_error(local_b, A_first(first), A_last(last)), where A_first applies
+ *      onto the base's sample 0 and A_last onto the base's LAST sample, S_b - 1: they are not base(b, s).
+ *   Step 5, compaction (compact.transform.h:124-207): both sides of every shell_error go through A with the same base(b, s), s the
+ *      sample under test.
+ *   Step 10, the header: the default-scale bit of the packed word is 0 under ADDITIVE1 and 1 otherwise (compress.transform.impl.h:422-423);
+ *      has_trivial_default_values stays false. A caller whose additive1 clip rests at scale 0 says so in default_pose.
+ *   S0, the segment's shell (rigid_shell_utils.h:212-246): the stretch over A(what the segment's streams hold), s the index in the clip.
+ *   S2, the search's errors (quantize.transform.h:269-313, 720-762, 834-842): the raw side is A(raw) per track, before the walk down the
+ *      chain; the lossy side is A(S1 transform); in the local and in the object error alike. The base here comes out of sample_streams
+ *      (sample_streams.h:649-673): base(b, s) at the same key, its rotation normalized ONCE MORE -- rtm::quat_normalize of the already
+ *      normalized value --, as written there. (Confirmed against the reference: the base's clip context is never compacted, so its
+ *      three kinds are always read as animated and its has_scale is true: its scale is the registered one, never a default.)
+ *   Unchanged: every loop, order, threshold and strict comparison of S3 and S4, the permutation lists, the levels, the ranges, the
+ *      quantization and the layout.
+ *   The launches are the base calls' (DESIGN.md 4.7 "Transform compression (additive bases)"): the base is a template argument of the
+ *   seven kernels it enters -- the shell kernel, both analyses, the segment kernel, the local phase and the two instantiations of the
+ *   object phase --, the format a word of the launch record; the instantiations without it serve NONE and every other call. The layout
+ *   kernels take the header bit from their launch record.
+ *   Left out: a base under quatf_full (an additive1 raw blob would need only the header bit); an additive matrix metric (the reference
+ *   has none); the levels-free search with a base (levels 0 to 2 of this call are it); what the base calls leave out. Measured against
+ *   the reference and what it costs: profiles/compress_additive.md. */
+typedef struct aclhip_additive_base
+{
+	const aclhip_raw_tracks* base_raws;  /*   0  DEVICE [num_instances]: the base of instance i, a registered raw track array; NULL only with NONE */
+	uint32_t additive_format;            /*   8  aclhip_additive_format: NONE, RELATIVE, ADDITIVE0, ADDITIVE1 */
+	uint32_t reserved_word;              /*  12  0 */
+	uint64_t reserved[2];                /*  16  0 */
+} aclhip_additive_base;                  /* 32 bytes */
+
+aclhip_status aclhip_compress_tracks_additive_batch(aclhip_context* context, const aclhip_raw_tracks* raws /* DEVICE [num_instances] */,
+	uint32_t num_instances, const aclhip_compress_tracks_desc* desc, void* blobs /* DEVICE */, uint64_t blob_stride_bytes,
+	aclhip_compress_result* results /* DEVICE [num_instances] */, const aclhip_additive_base* additive_base, void* stream);
+aclhip_status aclhip_compress_tracks_variable_additive_batch(aclhip_context* context, const aclhip_raw_tracks* raws /* DEVICE [num_instances] */,
+	uint32_t num_instances, const aclhip_compress_variable_desc* desc, void* blobs /* DEVICE */, uint64_t blob_stride_bytes,
+	aclhip_compress_result* results /* DEVICE [num_instances] */, const aclhip_additive_base* additive_base, void* stream);
+aclhip_status aclhip_find_bit_rates_additive_batch(aclhip_context* context, const aclhip_raw_tracks* raws /* DEVICE [num_instances] */,
+	uint32_t num_instances, const aclhip_find_bit_rates_desc* desc, uint8_t* bit_rates /* DEVICE */, uint64_t instance_stride,
+	uint64_t segment_stride, aclhip_compress_result* results /* DEVICE [num_instances] */, const aclhip_additive_base* additive_base, void* stream);
 
 /* ---- multi-GPU ---------------------------------------------------------------------------------- */
 

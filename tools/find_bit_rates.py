@@ -19,7 +19,11 @@ aclhip_find_bit_rates_batch (or its _metric form), high, highest and automatic t
 workspace, checked against tests/bit_rate_search_levels_restatement.py; the lab library's knob is then
 ACLHIP_FIND_BIT_RATES_LEVEL_PHASES and the split has a sixth phase, the level per instance, in front of the object phase. The
 workload's spine makes chains of 26 bones, where the wider levels are at their most expensive (automatic picks medium for it): size
-the batch with COMPRESS_TRACKS_INSTANCES. Prints one JSON line."""
+the batch with COMPRESS_TRACKS_INSTANCES. --additive-format {relative,additive0,additive1}: every array is an additive clip on a drawn
+base clip of its own (another array of the workload's; under additive1 the clips' scales are moved by -1 and the default scale is 0):
+the search and the compress call go through the _additive entry points (the search is then the level search at every level), checked
+against tests/additive_compress_restatement.py, and the calls WITHOUT a base are timed in the same rounds on the same arrays, every
+key of theirs with the suffix _no_base. Prints one JSON line."""
 import argparse
 import json
 import os
@@ -37,6 +41,7 @@ import compress_tracks as workload  # noqa: E402  (the arrays, the skeleton, the
 import bit_rate_search_restatement as restatement  # noqa: E402  (the checker's restatement)
 import bit_rate_search_levels_restatement as levels_restatement  # noqa: E402  (and at every level)
 import matrix_metric_compress_restatement as metric_restatement  # noqa: E402  (and with the metric as an argument)
+import additive_compress_restatement as additive_restatement  # noqa: E402  (and with an additive base)
 
 N, ARRAYS, TRACKS, SAMPLES = workload.N, workload.ARRAYS, workload.TRACKS, workload.SAMPLES
 ROUNDS = int(os.environ.get("FIND_BIT_RATES_ROUNDS", "3"))
@@ -56,10 +61,16 @@ def main():
     parser.add_argument("--scales", choices=("workload", "nonuniform"), default="workload", help="nonuniform: every scale within 0.9 .. 1.1, per sample and component")
     parser.add_argument("--level", choices=sorted(runtime.COMPRESSION_LEVELS, key=runtime.COMPRESSION_LEVELS.get), default="medium",
                         help="the compression level; high, highest and automatic go through aclhip_find_bit_rates_level_batch")
+    parser.add_argument("--additive-format", choices=("none", "relative", "additive0", "additive1"), default="none",
+                        help="compress every array as an additive clip against a drawn base clip, through the _additive entry points")
     arguments = parser.parse_args()
     metric = arguments.metric
     level = runtime.COMPRESSION_LEVELS[arguments.level]
-    with_levels = level > runtime.COMPRESSION_LEVELS["medium"]
+    additive_format = {"none": runtime.ADDITIVE_NONE, "relative": runtime.ADDITIVE_RELATIVE, "additive0": runtime.ADDITIVE_ADDITIVE0, "additive1": runtime.ADDITIVE_ADDITIVE1}[arguments.additive_format]
+    with_base = additive_format != runtime.ADDITIVE_NONE
+    if with_base and metric != runtime.ERROR_METRIC_QVVF:
+        parser.error("an additive base goes with the qvvf error metric: the reference has no additive matrix metric")
+    with_levels = level > runtime.COMPRESSION_LEVELS["medium"] or with_base           # (the _additive search is the level search)
     phases, knob_name = (LEVEL_PHASES, LEVEL_KNOB) if with_levels else (PHASES, KNOB)
     if not torch.cuda.is_available():
         raise SystemExit("tools/find_bit_rates.py needs a GPU: nothing is measured without one")
@@ -69,6 +80,15 @@ def main():
         scale_rng = np.random.default_rng(9200 + TRACKS)
         for samples in arrays:
             samples[:, :, 8:11] = scale_rng.uniform(0.9, 1.1, size=(SAMPLES, TRACKS, 3))
+    base_arrays, default_pose = [], None
+    if with_base:
+        base_rng = np.random.default_rng(9300 + TRACKS)
+        base_arrays = [workload.make_array(base_rng) for _ in range(ARRAYS)]
+        if additive_format == runtime.ADDITIVE_ADDITIVE1:
+            default_pose = np.tile(restatement.IDENTITY, (TRACKS, 1)).astype(np.float32)
+            default_pose[:, 8:11] = 0.0
+            for samples in arrays:
+                samples[:, :, 8:11] = samples[:, :, 8:11] - np.float32(1.0)
     order = rng.integers(0, ARRAYS, size=N)
     order[:ARRAYS] = np.arange(ARRAYS)[: min(ARRAYS, N)]        # every distinct array is in the batch
     parents = workload.skeleton(TRACKS)
@@ -87,6 +107,14 @@ def main():
         d_results = torch.zeros((N, 2), dtype=torch.int32, device="cuda")
         workspace_bytes = runtime.find_bit_rates_level_workspace_bytes if with_levels else runtime.find_bit_rates_workspace_bytes
         d_workspace = torch.zeros(workspace_bytes(N, TRACKS, SAMPLES), dtype=torch.uint8, device="cuda")
+    additive_base = runtime.AdditiveBase()
+    additive_base.additive_format = additive_format
+    if with_base:
+        base_handles = np.array([ctx.register_raw_tracks(a, RATE) for a in base_arrays], dtype=np.uint32)
+        with torch.cuda.stream(stream):
+            d_bases = torch.from_numpy(base_handles[order].view(np.int32)).cuda()
+            d_pose = torch.from_numpy(default_pose).cuda() if default_pose is not None else None
+        additive_base.base_raws = d_bases.data_ptr()
     search = runtime.FindBitRatesDesc()
     search.precision, search.shell_distance, search.max_tracks, search.max_samples, search.workspace, search.level = PRECISION, SHELL, TRACKS, SAMPLES, d_workspace.data_ptr(), level
     search.parent_indices, search.num_table_tracks = d_parents.data_ptr(), TRACKS
@@ -94,6 +122,8 @@ def main():
     desc.precision, desc.shell_distance, desc.max_tracks, desc.max_samples, desc.workspace = PRECISION, SHELL, TRACKS, SAMPLES, d_workspace.data_ptr()
     desc.parent_indices, desc.num_table_tracks = d_parents.data_ptr(), TRACKS
     desc.bit_rates, desc.bit_rate_segment_stride, desc.bit_rate_instance_stride = d_rates.data_ptr(), 4 * TRACKS, 4 * TRACKS * segments
+    if default_pose is not None:
+        search.default_pose = desc.default_pose = d_pose.data_ptr()
 
     def launch_search_qvvf():
         if with_levels:
@@ -104,6 +134,8 @@ def main():
         ctx.compress_tracks_variable_batch(d_raws.data_ptr(), N, desc, d_blobs.data_ptr(), stride, d_results.data_ptr(), stream=s)
 
     def launch_search():
+        if with_base:
+            return ctx.find_bit_rates_additive_batch(d_raws.data_ptr(), N, search, d_rates.data_ptr(), 4 * TRACKS * segments, 4 * TRACKS, d_results.data_ptr(), additive_base, stream=s)
         if metric == runtime.ERROR_METRIC_QVVF:
             return launch_search_qvvf()
         if with_levels:
@@ -111,6 +143,8 @@ def main():
         ctx.find_bit_rates_metric_batch(d_raws.data_ptr(), N, search, d_rates.data_ptr(), 4 * TRACKS * segments, 4 * TRACKS, d_results.data_ptr(), metric, stream=s)
 
     def launch_compress():
+        if with_base:
+            return ctx.compress_tracks_variable_additive_batch(d_raws.data_ptr(), N, desc, d_blobs.data_ptr(), stride, d_results.data_ptr(), additive_base, stream=s)
         if metric == runtime.ERROR_METRIC_QVVF:
             return launch_compress_qvvf()
         ctx.compress_tracks_variable_metric_batch(d_raws.data_ptr(), N, desc, d_blobs.data_ptr(), stride, d_results.data_ptr(), metric, stream=s)
@@ -118,7 +152,8 @@ def main():
     # ---- checked before it is timed
     os.environ.pop(knob_name, None)
     qvvf_blob_bytes = None
-    if metric != runtime.ERROR_METRIC_QVVF:         # (the qvvf search's blobs, for their bytes; the table is searched again below)
+    other = "_qvvf" if metric != runtime.ERROR_METRIC_QVVF else "_no_base" if with_base else None       # the calls timed beside: without the metric, or without the base
+    if other is not None:         # (the other search's blobs, for their bytes; the table is searched again below)
         with torch.cuda.stream(stream):
             launch_search_qvvf()
             launch_compress_qvvf()
@@ -133,7 +168,11 @@ def main():
     searched_levels = sorted(int(word) for word in np.unique(results[:, 1])) if with_levels else [level]
     evaluations = None
     for i in range(min(ARRAYS, N, RESTATED)):
-        restated = levels_restatement.find_bit_rates_metric(arrays[i], RATE, metric, level=level, parents=parents, precision=PRECISION, shell_distance=SHELL)
+        if with_base:
+            restated = additive_restatement.find_bit_rates(arrays[i], RATE, additive_restatement.Base(base_arrays[i], RATE, additive_format), level=level, parents=parents,
+                                                           precision=PRECISION, shell_distance=SHELL, **({"default_pose": default_pose} if default_pose is not None else {}))
+        else:
+            restated = levels_restatement.find_bit_rates_metric(arrays[i], RATE, metric, level=level, parents=parents, precision=PRECISION, shell_distance=SHELL)
         expected = restated.table
         if with_levels:
             evaluations = {"array": i, "with_the_memo": int(restated.evaluations), "without_the_memo": int(restated.evaluations_unmemoized)}
@@ -170,12 +209,12 @@ def main():
     if lab:
         for k in range(1, len(phases)):
             cases["phases_%d" % k] = (launch_search, str(k))
-    if metric != runtime.ERROR_METRIC_QVVF:         # (the compress call behind the qvvf search reads the matrix table: its time does not depend on the rates' metric)
-        cases["search_qvvf"] = (launch_search_qvvf, None)
-        cases["compress_at_the_table_qvvf"] = (launch_compress_qvvf, None)
+    if other is not None:         # (the compress call behind the other search reads this table: its time does not depend on how the rates were found)
+        cases["search" + other] = (launch_search_qvvf, None)
+        cases["compress_at_the_table" + other] = (launch_compress_qvvf, None)
         if lab:
             for k in range(1, len(phases)):
-                cases["phases_%d_qvvf" % k] = (launch_search_qvvf, str(k))
+                cases["phases_%d%s" % (k, other)] = (launch_search_qvvf, str(k))
 
     def run(case, repeats):
         call, knob = case
@@ -198,7 +237,7 @@ def main():
         return {"median": round(float(np.median(values)), 2), "min": round(float(values.min()), 2), "max": round(float(values.max()), 2),
                 "spread": round(float((values.max() - values.min()) / np.median(values)), 4)}
 
-    result = {"metric": metric, "level": arguments.level, "searched_levels": searched_levels, "scales": arguments.scales, "instances": N, "distinct_arrays": ARRAYS, "tracks": TRACKS, "samples": SAMPLES, "segments": segments, "rounds": ROUNDS, "repeats": REPEATS,
+    result = {"metric": metric, "additive_format": arguments.additive_format, "level": arguments.level, "searched_levels": searched_levels, "scales": arguments.scales, "instances": N, "distinct_arrays": ARRAYS, "tracks": TRACKS, "samples": SAMPLES, "segments": segments, "rounds": ROUNDS, "repeats": REPEATS,
               "checked_against": "restatement (%d arrays)" % min(ARRAYS, N, RESTATED), "library": os.path.basename(runtime.library_path()),
               "raw_bytes": int(N * TRACKS * SAMPLES * 48), "searched_blob_bytes": blob_bytes, "uniform_16_blob_bytes": uniform_bytes,
               "rates": {"min": int(animated.min()), "max": int(animated.max()), "mean": round(float(animated.mean()), 2)} if animated.size else None,
@@ -206,10 +245,10 @@ def main():
     if at_precision is not None:
         result["first_array"] = at_precision
     if qvvf_blob_bytes is not None:
-        result["searched_blob_bytes_qvvf"] = qvvf_blob_bytes
+        result["searched_blob_bytes" + other] = qvvf_blob_bytes
     if evaluations is not None:
         result["object_errors_in_the_restatement"] = evaluations
-    for suffix in ("", "_qvvf") if lab else ():
+    for suffix in ("", "_qvvf", "_no_base") if lab else ():
         if "search" + suffix not in result["us"]:
             continue
         total = result["us"]["search" + suffix]["median"]
