@@ -7,6 +7,7 @@ for batches of clip instances. torch is used only for device memory and streams.
 The HIP library is the only implementation: if it cannot be loaded this module raises, it never falls back to a CPU path.
 """
 import ctypes
+import functools
 import os
 
 import numpy as np
@@ -1912,37 +1913,6 @@ def _set_track_tables(desc, tables):
         desc.num_table_tracks = num_tracks
 
 
-def _with_metric(launch, metric_launch, metric):
-    """The context's method a call with an error metric goes through: the entry point without one for ERROR_METRIC_QVVF (it is that
-    call), else the _metric entry point at `metric` (an unknown one is the library's to refuse)."""
-    if metric == ERROR_METRIC_QVVF:
-        return launch
-    return lambda *arguments, **keywords: metric_launch(*arguments, metric=metric, **keywords)
-
-
-def _with_additive_base(ctx, launch, additive_launch, handles, additive_base, additive_format, metric):
-    """The context's method a transform compressor goes through when it may have an additive base: `launch` itself without one
-    (additive_base None and ADDITIVE_NONE: today's call, untouched), else `additive_launch` with an AdditiveBase whose handles -- one
-    for every instance, or one per instance -- are uploaded here. Returns (the method, what must stay alive until it has run)."""
-    if additive_base is None and additive_format == ADDITIVE_NONE:
-        return launch, None
-    if metric != ERROR_METRIC_QVVF:
-        raise ValueError("an additive base goes with the qvvf error metric: the reference has no additive matrix metric")
-    import torch
-    record = AdditiveBase()
-    record.additive_format = int(additive_format) & 0xFFFFFFFF
-    d_bases = None
-    if additive_base is not None:
-        bases = np.atleast_1d(np.asarray(additive_base, dtype=np.uint32))
-        if len(bases) == 1:
-            bases = np.repeat(bases, len(handles))
-        if len(bases) != len(handles):
-            raise ValueError(f"{len(bases)} additive bases for {len(handles)} instances: one handle, or one per instance")
-        d_bases = torch.from_numpy(np.ascontiguousarray(bases).view(np.int32)).to(torch.device("cuda", ctx.device_index))
-        record.base_raws = d_bases.data_ptr()
-    return (lambda *arguments, **keywords: additive_launch(*arguments, additive_base=record, **keywords)), (record, d_bases)
-
-
 def _compress_transform_tracks(ctx, launch, workspace_bytes, desc, raws, flags, default_pose, parents, precision, shell_distance, track_precisions, track_shell_distances,
                                bound=None, tables=None):
     """What compress_raw_tracks, compress_tracks and compress_tracks_variable share: `desc` (any of the three structs: the fields have one
@@ -2000,10 +1970,8 @@ def compress_tracks(ctx, raws, rotation_format=ROTATION_QUATF_DROP_W_FULL, defau
     desc = CompressTracksDesc()
     desc.rotation_format, desc.translation_format, desc.scale_format = int(rotation_format), VECTOR_VECTOR3F_FULL, VECTOR_VECTOR3F_FULL
     handles = np.atleast_1d(np.asarray(raws, dtype=np.uint32))
-    launch, alive = _with_additive_base(ctx, _with_metric(ctx.compress_tracks_batch, ctx.compress_tracks_metric_batch, metric), ctx.compress_tracks_additive_batch, handles,
-                                        additive_base, additive_format, metric)          # (alive until the launch has run)
-    return _compress_transform_tracks(ctx, launch, compress_tracks_workspace_bytes, desc, raws, flags, default_pose, parents, precision, shell_distance,
-                                      track_precisions, track_shell_distances)
+    launch, workspace_bytes, _, alive = transform_compress_route(ctx, "tracks", handles, metric, None, additive_base, additive_format)     # (alive until the launch has run)
+    return _compress_transform_tracks(ctx, launch, workspace_bytes, desc, raws, flags, default_pose, parents, precision, shell_distance, track_precisions, track_shell_distances)
 
 
 def variable_compress_num_segments(num_samples):
@@ -2031,21 +1999,64 @@ def find_bit_rates_level_workspace_bytes(num_instances, max_tracks, max_samples)
     return int(load_library().aclhip_find_bit_rates_level_workspace_bytes(int(num_instances), int(max_tracks), int(max_samples)))
 
 
+# per call of the transform compressor family: the Context method without a front, and the size function of its workspace
+_TRANSFORM_COMPRESS_CALLS = {"tracks": ("compress_tracks", compress_tracks_workspace_bytes), "variable": ("compress_tracks_variable", compress_variable_workspace_bytes),
+                             "search": ("find_bit_rates", find_bit_rates_workspace_bytes)}
+
+
+def transform_compress_route(ctx, call, handles, metric=ERROR_METRIC_QVVF, level=None, additive_base=None, additive_format=ADDITIVE_NONE, device=None):
+    """The entry point one call of the transform compressor family goes through. `call` is "tracks" (compress_tracks_batch),
+    "variable" (compress_tracks_variable_batch) or "search" (find_bit_rates_batch), `handles` the instances' raw track arrays; `level`
+    (a name of COMPRESSION_LEVELS or its number) counts for the search alone. Returns (launch, workspace_bytes, with_levels, alive):
+    the context's method with its extra argument bound, the size function of its workspace, whether the second word of a result is
+    the level that was searched, and what must stay alive until the launch has run.
+      tracks, variable: without a base the method itself for ERROR_METRIC_QVVF (it is that call), else the _metric method at `metric`
+        (an unknown one is the library's to refuse).
+      search: without a base, at a level above medium find_bit_rates_level_batch at `metric`; else find_bit_rates_batch for
+        ERROR_METRIC_QVVF, else find_bit_rates_metric_batch.
+      With additive_base (a handle for every instance, or one per instance) or an additive_format other than ADDITIVE_NONE: the _additive
+        method with an AdditiveBase whose handles are uploaded here, to `device` (None: the context's); for the search that is the
+        level search at every level. ValueError with another metric than ERROR_METRIC_QVVF, or a count of bases that is neither.
+    find_bit_rates_level_batch and find_bit_rates_additive_batch have with_levels and find_bit_rates_level_workspace_bytes."""
+    stem, workspace_bytes = _TRANSFORM_COMPRESS_CALLS[call]
+    front, extra, alive = "", {}, None
+    if additive_base is not None or additive_format != ADDITIVE_NONE:
+        if metric != ERROR_METRIC_QVVF:
+            raise ValueError("an additive base goes with the qvvf error metric: the reference has no additive matrix metric")
+        import torch
+        record = AdditiveBase()
+        record.additive_format = int(additive_format) & 0xFFFFFFFF
+        d_bases = None
+        if additive_base is not None:
+            bases = np.atleast_1d(np.asarray(additive_base, dtype=np.uint32))
+            if len(bases) == 1:
+                bases = np.repeat(bases, len(handles))
+            if len(bases) != len(handles):
+                raise ValueError(f"{len(bases)} additive bases for {len(handles)} instances: one handle, or one per instance")
+            d_bases = torch.from_numpy(np.ascontiguousarray(bases).view(np.int32)).to(torch.device("cuda", ctx.device_index) if device is None else device)
+            record.base_raws = d_bases.data_ptr()
+        front, extra, alive = "_additive", {"additive_base": record}, (record, d_bases)
+    elif call == "search" and COMPRESSION_LEVELS.get(level, level) > COMPRESSION_LEVELS["medium"]:
+        front, extra = "_level", {"metric": metric}
+    elif metric != ERROR_METRIC_QVVF:
+        front, extra = "_metric", {"metric": metric}
+    with_levels = call == "search" and front in ("_level", "_additive")
+    return (functools.partial(getattr(ctx, stem + front + "_batch"), **extra), find_bit_rates_level_workspace_bytes if with_levels else workspace_bytes,
+            with_levels, alive)
+
+
 def _find_bit_rates(ctx, handles, infos, level, flags, default_pose, parents, precision, shell_distance, track_precisions, track_shell_distances, tables=None,
                     metric=ERROR_METRIC_QVVF, additive_base=None, additive_format=ADDITIVE_NONE):
     """The search over `handles` into a zero-filled device table uint8 [instances, segments, tracks, 4] of the largest array's segments
-    and tracks: (the table, still on the device, and the results as a host array [instances, 2]). The levels lowest to medium go
-    through aclhip_find_bit_rates_batch or its _metric form, as before; high, highest and automatic through
-    aclhip_find_bit_rates_level_batch, whose results carry the level that was searched; with an additive base every level goes through
-    aclhip_find_bit_rates_additive_batch, which is the level search. Synchronous."""
+    and tracks: (the table, still on the device, the results as a host array [instances, 2], and the level that was searched per
+    instance as a uint32 array). The entry point is transform_compress_route's; the calls without the levels leave 0 in a result's
+    second word: their one search is the level they were asked for. Synchronous."""
     import torch
     device = torch.device("cuda", ctx.device_index)
     desc = FindBitRatesDesc()
     if level not in COMPRESSION_LEVELS and level not in COMPRESSION_LEVELS.values():
         raise ValueError(f"a compression level of {level!r}: one of {sorted(COMPRESSION_LEVELS, key=COMPRESSION_LEVELS.get)}, 0 to 4 or {LEVEL_AUTOMATIC}")
     desc.level = COMPRESSION_LEVELS.get(level, level)
-    with_base = additive_base is not None or additive_format != ADDITIVE_NONE
-    with_levels = desc.level > COMPRESSION_LEVELS["medium"] or with_base
     desc.flags, desc.precision, desc.shell_distance = flags, float(precision), float(shell_distance)
     desc.max_tracks = max(int(info.num_tracks) for info in infos)
     desc.max_samples = max(int(info.num_samples) for info in infos)
@@ -2057,21 +2068,14 @@ def _find_bit_rates(ctx, handles, infos, level, flags, default_pose, parents, pr
     d_raws = torch.from_numpy(handles.view(np.int32)).to(device)
     d_rates = torch.zeros((num_instances, num_segments, desc.max_tracks, 4), dtype=torch.uint8, device=device)
     d_results = torch.zeros((num_instances, 2), dtype=torch.int32, device=device)
-    workspace_bytes = find_bit_rates_level_workspace_bytes if with_levels else find_bit_rates_workspace_bytes
+    launch, workspace_bytes, with_levels, alive = transform_compress_route(ctx, "search", handles, metric, desc.level, additive_base, additive_format)
     d_workspace = torch.zeros(workspace_bytes(num_instances, desc.max_tracks, desc.max_samples) + 16, dtype=torch.uint8, device=device)
     desc.workspace = d_workspace.data_ptr()
-    alive = None
-    if with_base:
-        launch, alive = _with_additive_base(ctx, None, ctx.find_bit_rates_additive_batch, handles, additive_base, additive_format, metric)
-    elif with_levels:
-        def launch(*arguments, **keywords):
-            return ctx.find_bit_rates_level_batch(*arguments, metric=metric, **keywords)
-    else:
-        launch = _with_metric(ctx.find_bit_rates_batch, ctx.find_bit_rates_metric_batch, metric)
     launch(d_raws.data_ptr(), num_instances, desc, d_rates.data_ptr(), num_segments * desc.max_tracks * 4, desc.max_tracks * 4, d_results.data_ptr(), stream=stream.cuda_stream)
     stream.synchronize()
     del alive
-    return d_rates, d_results.cpu().numpy().view(np.uint32).reshape(num_instances, 2)
+    results = d_results.cpu().numpy().view(np.uint32).reshape(num_instances, 2)
+    return d_rates, results, results[:, 1].copy() if with_levels else np.full(num_instances, desc.level, dtype=np.uint32)
 
 
 def find_bit_rates(ctx, raws, level="medium", default_pose=None, parents=None, precision=1.0e-4, shell_distance=1.0, track_precisions=None, track_shell_distances=None,
@@ -2092,15 +2096,10 @@ def find_bit_rates(ctx, raws, level="medium", default_pose=None, parents=None, p
     infos = [ctx.raw_tracks_info(int(handle)) for handle in handles]
     if len(handles) == 0:
         return np.zeros((0, 0, 0, 4), dtype=np.uint8)
-    d_rates, results = _find_bit_rates(ctx, handles, infos, level, COMPRESS_OPTIMIZE_LOOPS if optimize_loops else 0, default_pose, parents, precision, shell_distance,
-                                       track_precisions, track_shell_distances, metric=metric, additive_base=additive_base, additive_format=additive_format)
+    d_rates, results, levels = _find_bit_rates(ctx, handles, infos, level, COMPRESS_OPTIMIZE_LOOPS if optimize_loops else 0, default_pose, parents, precision, shell_distance,
+                                               track_precisions, track_shell_distances, metric=metric, additive_base=additive_base, additive_format=additive_format)
     _raise_for_search_results(handles, results)
-    if return_levels:
-        # (the calls without the levels leave 0 in that word: their one search is the level they were asked for)
-        asked = COMPRESSION_LEVELS.get(level, level)
-        with_levels = asked > COMPRESSION_LEVELS["medium"] or additive_base is not None or additive_format != ADDITIVE_NONE
-        return d_rates.cpu().numpy(), results[:, 1].copy() if with_levels else np.full(len(handles), asked, dtype=np.uint32)
-    return d_rates.cpu().numpy()
+    return (d_rates.cpu().numpy(), levels) if return_levels else d_rates.cpu().numpy()
 
 
 def _raise_for_search_results(handles, results):
@@ -2142,12 +2141,9 @@ def compress_tracks_variable(ctx, raws, bit_rates=(16, 16, 16), default_pose=Non
         if bit_rates != "search":
             raise ValueError('bit_rates is three rates, a table or "search"')
         tables = _upload_track_tables(ctx, default_pose, parents, track_precisions, track_shell_distances)         # (once, for both calls)
-        d_rates, results = _find_bit_rates(ctx, handles, infos, level, flags, default_pose, parents, precision, shell_distance, track_precisions, track_shell_distances, tables,
-                                           metric=metric, additive_base=additive_base, additive_format=additive_format)
+        d_rates, results, levels = _find_bit_rates(ctx, handles, infos, level, flags, default_pose, parents, precision, shell_distance, track_precisions, track_shell_distances,
+                                                   tables, metric=metric, additive_base=additive_base, additive_format=additive_format)
         _raise_for_search_results(handles, results)
-        asked = COMPRESSION_LEVELS.get(level, level)
-        with_levels = asked > COMPRESSION_LEVELS["medium"] or additive_base is not None or additive_format != ADDITIVE_NONE
-        levels = results[:, 1].copy() if with_levels else np.full(len(handles), asked, dtype=np.uint32)
         desc.bit_rates = d_rates.data_ptr()                                                 # (alive until the launch has run)
         desc.bit_rate_segment_stride = d_rates.shape[2] * 4
         desc.bit_rate_instance_stride = d_rates.shape[1] * d_rates.shape[2] * 4
@@ -2166,10 +2162,10 @@ def compress_tracks_variable(ctx, raws, bit_rates=(16, 16, 16), default_pose=Non
             desc.bit_rate_segment_stride = rates.shape[-2] * 4 if rates.ndim >= 3 else 0
             desc.bit_rate_instance_stride = rates.shape[-3] * rates.shape[-2] * 4 if rates.ndim == 4 else 0
 
+    launch, size_function, _, alive = transform_compress_route(ctx, "variable", handles, metric, None, additive_base, additive_format)      # (alive until the launch has run)
+
     def workspace_bytes(num_instances, max_tracks):
-        return compress_variable_workspace_bytes(num_instances, max_tracks, desc.max_samples)
-    launch, alive = _with_additive_base(ctx, _with_metric(ctx.compress_tracks_variable_batch, ctx.compress_tracks_variable_metric_batch, metric),
-                                        ctx.compress_tracks_variable_additive_batch, handles, additive_base, additive_format, metric)      # (alive until the launch has run)
+        return size_function(num_instances, max_tracks, desc.max_samples)
     blobs = _compress_transform_tracks(ctx, launch, workspace_bytes, desc, raws, flags, default_pose, parents, precision, shell_distance,
                                        track_precisions, track_shell_distances, bound=variable_compress_bound, tables=tables)
     return (blobs, levels) if return_levels else blobs

@@ -3,9 +3,8 @@ the C ABI: the expected tables, blobs, results and shells are the restatement's 
 tests/test_additive_compress_oracle.py holds to the reference's compressor with the base), and every comparison is on BYTES: both
 sides follow one definition, nothing has a tolerance.
 
-The launches and the comparisons are the base calls' own (tests/test_gpu_bit_rate_search.py, tests/test_gpu_variable_compress.py,
-tests/test_gpu_lossy_rotation_compress.py: a flat buffer of a sentinel byte between guards, one comparison for every byte), handed a
-context whose three base launches go through the _additive fronts. The shapes are the smallest at which the kernels can go wrong: T in
+The launches and the comparisons are the family's own (tests/compress_launches.py: a flat buffer of a sentinel byte between guards, one
+comparison for every byte), at the three entries of the _additive front. The shapes are the smallest at which the kernels can go wrong: T in
 1 (a root alone), 4 (one group of four rotations), 9 and 17 (the chains of the level tests; a group and a tail); S in 1 (no vote
 possible), 2 (a vote), 17 (one segment), 33 and 48 (two) and 49 (three); bases of 1, 2, 7 and S samples and one of 2 S - 1 samples at another
 rate, so that the nearest key lands on both sides of a half; clips with scale and without (the _no_scale route); ADDITIVE1 with a
@@ -16,19 +15,15 @@ import pytest
 
 from acl_amd import runtime
 import additive_compress_restatement as additive
+import compress_launches as launches
 import variable_compress_restatement as restatement
-import test_gpu_bit_rate_search as search_launches
-import test_gpu_bit_rate_search_levels as level_launches
-import test_gpu_lossy_rotation_compress as drop_w_launches
-import test_gpu_variable_compress as variable_launches
 from additive_compress_restatement import ADDITIVE0, ADDITIVE1, NONE, RELATIVE
-from test_gpu_lossy_rotation_compress import GUARD, SENTINEL
+from compress_launches import PRECISION, RATE, SHELL, Entry, check_rows, check_table, ctx  # noqa: F401  (ctx: this module's fixture)
 from variable_compress_restatement import ANIMATED, DEFAULT, IDENTITY, OPTIMIZE_LOOPS
 
 pytestmark = pytest.mark.gpu
 
-RATE, BASE_RATE = 32.0, 19.0            # the clips' rate (the base launches' own) and the rate of a base that has another
-PRECISION, SHELL = 0.01, 3.0
+BASE_RATE = 19.0                        # the rate of a base that has another than the clips' (RATE, the launches' own)
 # (48 samples are two segments of 24: split_samples_per_segment deals the last 16 out over the other two; 49 are 17 + 16 + 16)
 TRACK_COUNTS, SAMPLE_COUNTS = (1, 4, 9, 17), (1, 2, 17, 33, 48, 49)
 SHAPES = [(t, s) for t in TRACK_COUNTS for s in SAMPLE_COUNTS]
@@ -39,43 +34,15 @@ REFUSED, NOT_FINITE = runtime.COMPRESS_REFUSED, runtime.COMPRESS_NOT_FINITE
 ADDITIVE1_POSE = np.tile(np.array([0, 0, 0, 1, 0, 0, 0, 0, 0, 0, 0, 0], dtype=np.float32), (MAX_TRACKS, 1))     # a default scale of 0
 
 
-class ThroughTheAdditiveFronts:
-    """a context whose three base launches are the _additive fronts with `bases` (a handle for every instance, or one per instance;
-    None: no handles at all) and `additive_format`; everything else is the context's"""
-    def __init__(self, context, bases, additive_format):
-        self.context, self.bases, self.additive_format = context, bases, additive_format
-
-    def __getattr__(self, name):
-        return getattr(self.context, name)
-
-    def record_for(self, num_instances):
-        import torch
-        record = runtime.AdditiveBase()
-        record.additive_format = self.additive_format
-        self.d_bases = None
-        if self.bases is not None:
-            bases = np.atleast_1d(np.asarray(self.bases, dtype=np.uint32))
-            bases = np.repeat(bases, num_instances) if len(bases) == 1 else bases
-            assert len(bases) == num_instances
-            self.d_bases = torch.from_numpy(bases.view(np.int32)).to(torch.device("cuda:0"))
-            record.base_raws = self.d_bases.data_ptr()
-        return record
-
-    def compress_tracks_batch(self, raws_ptr, num_instances, *arguments, **keywords):
-        return self.context.compress_tracks_additive_batch(raws_ptr, num_instances, *arguments, additive_base=self.record_for(num_instances), **keywords)
-
-    def compress_tracks_variable_batch(self, raws_ptr, num_instances, *arguments, **keywords):
-        return self.context.compress_tracks_variable_additive_batch(raws_ptr, num_instances, *arguments, additive_base=self.record_for(num_instances), **keywords)
-
-    def find_bit_rates_batch(self, raws_ptr, num_instances, *arguments, **keywords):
-        return self.context.find_bit_rates_additive_batch(raws_ptr, num_instances, *arguments, additive_base=self.record_for(num_instances), **keywords)
+def through(kind, bases, additive_format):
+    """the _additive front of `kind` with `bases` (a handle for every instance, or one per instance; None: no handles at all)"""
+    return Entry(kind, "additive", bases=bases, additive_format=additive_format)
 
 
-@pytest.fixture(scope="module")
-def ctx():
-    context = runtime.Context(0)
-    yield context
-    context.close()
+def launch(ctx, entry, handles, **settings):
+    settings.setdefault("max_tracks", MAX_TRACKS)
+    settings.setdefault("max_samples", MAX_SAMPLES)
+    return launches.launch(ctx, entry, handles, **settings)
 
 
 class Case:
@@ -138,11 +105,11 @@ def unregister(ctx, cases):
 
 
 def search(ctx, cases, additive_format, level=MEDIUM, **settings):
-    settings.setdefault("max_tracks", MAX_TRACKS)
-    settings.setdefault("max_samples", MAX_SAMPLES)
-    front = ThroughTheAdditiveFronts(ctx, [case.base_handle for case in cases], additive_format)
-    with level_launches.level_workspace():
-        return search_launches.launch(front, [case.handle for case in cases], level=level, **settings)
+    return launch(ctx, through("search", [case.base_handle for case in cases], additive_format), [case.handle for case in cases], level=level, **settings)
+
+
+def check_levels(launched, expected):
+    check_table(launched, expected, levels=True)
 
 
 @pytest.fixture(scope="module")
@@ -172,7 +139,7 @@ def test_the_table_is_the_restatements(sweep, additive_format):
     ctx, parents, by_format = sweep
     cases = by_format[additive_format]
     settings = launch_settings(settings_of(additive_format, parents, flags=OPTIMIZE_LOOPS))
-    level_launches.check(search(ctx, cases, additive_format, **settings), [case.found for case in cases])
+    check_levels(search(ctx, cases, additive_format, **settings), [case.found for case in cases])
     # the sweep is worth its name: the base decides, votes pass and fail, clips without scale, every segment count, the object phase at work
     assert sum(not np.array_equal(case.found.table, case.found_without.table) for case in cases if case.samples.shape[1] >= 9) >= 3
     assert {len(case.found.base.segments) for case in cases} == {1, 2, 3}
@@ -188,13 +155,13 @@ def test_the_two_writers_are_the_restatements(sweep, additive_format):
     ctx, parents, by_format = sweep
     cases = by_format[additive_format]
     settings = launch_settings(settings_of(additive_format, parents, flags=OPTIMIZE_LOOPS))
-    front = ThroughTheAdditiveFronts(ctx, [case.base_handle for case in cases], additive_format)
+    bases = [case.base_handle for case in cases]
     tables = np.zeros((len(cases), MAX_SEGMENTS, MAX_TRACKS, 4), dtype=np.uint8)
     for row, case in enumerate(cases):
         tables[row, :case.found.table.shape[0], :case.found.table.shape[1]] = case.found.table
     handles = [case.handle for case in cases]
-    drop_w_launches.check(variable_launches.launch(front, handles, tables, max_tracks=MAX_TRACKS, max_samples=MAX_SAMPLES, **settings), [case.variable for case in cases])
-    drop_w_launches.check(drop_w_launches.launch(front, handles, max_tracks=MAX_TRACKS, max_samples=MAX_SAMPLES, **settings), [case.drop_w for case in cases])
+    check_rows(launch(ctx, through("variable", bases, additive_format), handles, rates=tables, **settings), [case.variable for case in cases])
+    check_rows(launch(ctx, through("tracks", bases, additive_format), handles, **settings), [case.drop_w for case in cases])
     for case in cases:
         for blob in (case.variable.blob, case.drop_w.blob):
             assert (int(blob[28]) >> 1) & 1 == (0 if additive_format == ADDITIVE1 else 1)
@@ -214,7 +181,7 @@ def test_the_levels_on_the_chain_of_nine(ctx):
             found = {level: additive.find_bit_rates(case.samples, RATE, case.base, level=level, **settings) for level in (MEDIUM, HIGHEST)}
             for level, expected in ((MEDIUM, found[MEDIUM]), (HIGHEST, found[HIGHEST]), (AUTOMATIC, found[HIGHEST])):
                 launched = search(ctx, [case, case], additive_format, level=level, max_tracks=9, max_samples=33, **launch_settings(settings))
-                level_launches.check(launched, [expected] * 2)
+                check_levels(launched, [expected] * 2)
         finally:
             unregister(ctx, [case])
 
@@ -240,10 +207,9 @@ def test_a_loop_that_closes_only_on_the_base(ctx):
     register(ctx, [case])
     try:
         keywords = dict(max_tracks=num_tracks, max_samples=num_samples, **launch_settings(settings))
-        level_launches.check(search(ctx, [case], ADDITIVE0, **keywords), [with_base[0]])
-        front = ThroughTheAdditiveFronts(ctx, [case.base_handle], ADDITIVE0)
-        drop_w_launches.check(variable_launches.launch(front, [case.handle], with_base[0].table, **keywords), [with_base[1]])
-        drop_w_launches.check(drop_w_launches.launch(front, [case.handle], **keywords), [additive.compress_drop_w(case.samples, RATE, case.base, **settings)])
+        check_levels(search(ctx, [case], ADDITIVE0, **keywords), [with_base[0]])
+        check_rows(launch(ctx, through("variable", [case.base_handle], ADDITIVE0), [case.handle], rates=with_base[0].table, **keywords), [with_base[1]])
+        check_rows(launch(ctx, through("tracks", [case.base_handle], ADDITIVE0), [case.handle], **keywords), [additive.compress_drop_w(case.samples, RATE, case.base, **settings)])
     finally:
         unregister(ctx, [case])
 
@@ -254,17 +220,12 @@ def test_none_through_the_fronts_is_the_base_calls_bytes(sweep):
     ctx, parents, by_format = sweep
     cases = [case for case in by_format[RELATIVE] if case.samples.shape[1] in (9, 17)]
     handles = [case.handle for case in cases]
-    settings = dict(flags=OPTIMIZE_LOOPS, parents=parents, max_tracks=MAX_TRACKS, max_samples=MAX_SAMPLES)
+    settings = dict(flags=OPTIMIZE_LOOPS, parents=parents)
     for bases in ([case.base_handle for case in cases], [0xFFFFFF], None):
-        front = ThroughTheAdditiveFronts(ctx, bases, NONE)
-        with level_launches.level_workspace():
-            base, through = (search_launches.launch(context, handles, level=HIGHEST, **settings) for context in (level_launches.ThroughTheLevelFront(ctx, 0), front))
-        assert np.array_equal(base.flat, through.flat) and np.array_equal(base.results, through.results) and np.array_equal(base.metadata, through.metadata)
-        assert (base.results[:, 0] == runtime.COMPRESS_OK).all() and base.rejected == through.rejected == 0
-        for launch, arguments in ((variable_launches.launch, ((9, 14, 7),)), (drop_w_launches.launch, ())):
-            base, through = (launch(context, handles, *arguments, **settings) for context in (ctx, front))
-            assert np.array_equal(base.flat, through.flat) and np.array_equal(base.results, through.results) and np.array_equal(base.metadata, through.metadata)
-            assert (base.results[:, 0] == runtime.COMPRESS_OK).all() and base.rejected == through.rejected == 0
+        for without, kind, arguments in ((Entry("search", "level", 0), "search", {"level": HIGHEST}), (Entry("variable"), "variable", {"rates": (9, 14, 7)}), (Entry("tracks"), "tracks", {})):
+            base, front = (launch(ctx, entry, handles, **arguments, **settings) for entry in (without, through(kind, bases, NONE)))
+            assert np.array_equal(base.flat, front.flat) and np.array_equal(base.results, front.results) and np.array_equal(base.metadata, front.metadata)
+            assert (base.results[:, 0] == runtime.COMPRESS_OK).all() and base.rejected == front.rejected == 0
 
 
 def test_refusals_and_a_base_that_is_not_finite_leave_their_rows(sweep):
@@ -283,17 +244,15 @@ def test_refusals_and_a_base_that_is_not_finite_leave_their_rows(sweep):
         bases = [nine.base_handle, four.base_handle, four.base_handle, dead, h_bad, nine.base_handle]
         assert four.base_samples.shape[1] < 9
         settings = launch_settings(settings_of(ADDITIVE0, parents, flags=OPTIMIZE_LOOPS))
-        front = ThroughTheAdditiveFronts(ctx, bases, ADDITIVE0)
-        with level_launches.level_workspace():
-            launched = search_launches.launch(front, handles, max_tracks=MAX_TRACKS, max_samples=MAX_SAMPLES, **settings)
-        level_launches.check(launched, [nine.found, REFUSED, four.found, REFUSED, NOT_FINITE, nine.found])
+        launched = launch(ctx, through("search", bases, ADDITIVE0), handles, **settings)
+        check_levels(launched, [nine.found, REFUSED, four.found, REFUSED, NOT_FINITE, nine.found])
         tables = np.zeros((len(handles), MAX_SEGMENTS, MAX_TRACKS, 4), dtype=np.uint8)
         for row, case in ((0, nine), (2, four), (5, nine)):
             tables[row, :case.found.table.shape[0], :case.found.table.shape[1]] = case.found.table
-        out = variable_launches.launch(front, handles, tables, max_tracks=MAX_TRACKS, max_samples=MAX_SAMPLES, with_metadata=False, **settings)
-        drop_w_launches.check(out, [nine.variable.blob, REFUSED, four.variable.blob, REFUSED, NOT_FINITE, nine.variable.blob])
-        out = drop_w_launches.launch(front, handles, max_tracks=MAX_TRACKS, max_samples=MAX_SAMPLES, with_metadata=False, **settings)
-        drop_w_launches.check(out, [nine.drop_w.blob, REFUSED, four.drop_w.blob, REFUSED, NOT_FINITE, nine.drop_w.blob])
+        out = launch(ctx, through("variable", bases, ADDITIVE0), handles, rates=tables, with_metadata=False, **settings)
+        check_rows(out, [nine.variable.blob, REFUSED, four.variable.blob, REFUSED, NOT_FINITE, nine.variable.blob])
+        out = launch(ctx, through("tracks", bases, ADDITIVE0), handles, with_metadata=False, **settings)
+        check_rows(out, [nine.drop_w.blob, REFUSED, four.drop_w.blob, REFUSED, NOT_FINITE, nine.drop_w.blob])
         with pytest.raises(ValueError, match="ACLHIP_COMPRESS_REFUSED"):
             runtime.find_bit_rates(ctx, [nine.handle], parents=parents, precision=PRECISION, shell_distance=SHELL, additive_base=four.base_handle, additive_format=ADDITIVE0)
         with pytest.raises(RuntimeError, match="not finite"):

@@ -13,25 +13,17 @@ import pytest
 
 from acl_amd import runtime
 import bit_rate_search_restatement as search_restatement
+import compress_launches as launches
 import variable_compress_restatement as restatement
+from compress_launches import PRECISION, RATE, SHELL, Entry, Registered, check_table, ctx, same  # noqa: F401  (ctx: this module's fixture)
 from variable_compress_restatement import ANIMATED, IDENTITY, OPTIMIZE_LOOPS
-from test_gpu_lossy_rotation_compress import GUARD, SENTINEL, Launched, Registered
 
 pytestmark = pytest.mark.gpu
 
-RATE = 32.0
-PRECISION, SHELL = 0.01, 3.0
 TRACK_COUNTS, SAMPLE_COUNTS = (1, 3, 5, 17, 65), (2, 31, 33, 65)
 SHAPES = [(t, s) for t in TRACK_COUNTS for s in SAMPLE_COUNTS]
 MAX_TRACKS, MAX_SAMPLES, MAX_SEGMENTS = 65, 65, 4
 REFUSED, NOT_FINITE = runtime.COMPRESS_REFUSED, runtime.COMPRESS_NOT_FINITE
-
-
-@pytest.fixture(scope="module")
-def ctx():
-    context = runtime.Context(0)
-    yield context
-    context.close()
 
 
 def find(samples, **settings):
@@ -40,71 +32,9 @@ def find(samples, **settings):
     return search_restatement.find_bit_rates(samples, RATE, **settings)
 
 
-def launch(ctx, handles, max_tracks=MAX_TRACKS, max_samples=MAX_SAMPLES, flags=0, parents=None, default_pose=None, track_precisions=None, track_shell_distances=None,
-           level=2, segment_stride=None, instance_stride=None, precision=PRECISION):
-    """One launch over `handles` into a table of sentinel bytes"""
-    import torch
-    device = torch.device("cuda:0")
-    n = len(handles)
-    max_segments = runtime.variable_compress_num_segments(max_samples)
-    segment_stride = 4 * max_tracks if segment_stride is None else segment_stride
-    instance_stride = max_segments * segment_stride if instance_stride is None else instance_stride
-    flat = torch.full((GUARD + n * instance_stride + GUARD,), SENTINEL, dtype=torch.uint8, device=device)
-    d_handles = torch.from_numpy(np.asarray(handles, dtype=np.uint32).view(np.int32)).to(device)
-    d_results = torch.full((n, 2), 0x5A5A5A5A, dtype=torch.int32, device=device)
-    workspace_bytes = runtime.find_bit_rates_workspace_bytes(n, max_tracks, max_samples)
-    d_workspace = torch.full((workspace_bytes + GUARD,), SENTINEL, dtype=torch.uint8, device=device)
-    d_metadata = torch.full((GUARD + n * max_tracks * 8 + GUARD,), SENTINEL, dtype=torch.uint8, device=device)
-    desc = runtime.FindBitRatesDesc()
-    desc.shell_metadata = d_metadata.data_ptr() + GUARD
-    desc.flags, desc.max_tracks, desc.max_samples, desc.precision, desc.shell_distance, desc.level = flags, max_tracks, max_samples, precision, SHELL, level
-    desc.workspace = d_workspace.data_ptr()
-    tables = []
-    for field, table, dtype in (("default_pose", default_pose, np.float32), ("parent_indices", parents, np.uint32), ("track_precisions", track_precisions, np.float32),
-                                ("track_shell_distances", track_shell_distances, np.float32)):
-        if table is not None:
-            host = np.ascontiguousarray(table, dtype=dtype)
-            d_table = torch.from_numpy(host.view(np.int32)).to(device)
-            tables.append((host, d_table))
-            setattr(desc, field, d_table.data_ptr())
-            desc.num_table_tracks = host.shape[0]
-    rejected_before = ctx.rejected_instance_count()
-    stream = torch.cuda.current_stream(device)
-    ctx.find_bit_rates_batch(d_handles.data_ptr(), n, desc, flat.data_ptr() + GUARD, instance_stride, segment_stride, d_results.data_ptr(), stream=stream.cuda_stream)
-    stream.synchronize()
-    out = Launched()
-    out.flat, out.n, out.max_tracks, out.instance_stride, out.segment_stride = flat.cpu().numpy(), n, max_tracks, instance_stride, segment_stride
-    out.results = d_results.cpu().numpy().view(np.uint32).reshape(n, 2)
-    out.metadata = d_metadata.cpu().numpy()
-    out.rejected = ctx.rejected_instance_count() - rejected_before
-    assert np.all(d_workspace.cpu().numpy()[workspace_bytes:] == SENTINEL)                      # the workspace is as large as it says
-    for host, d_table in tables:
-        assert np.array_equal(d_table.cpu().numpy().view(np.uint8).reshape(-1), host.view(np.uint8).reshape(-1))      # the inputs are only read
-    return out
-
-
-def check(launched, expected):
-    """expected: per instance a Search of the restatement, or the status of an instance that writes nothing"""
-    want = np.full(launched.flat.shape, SENTINEL, dtype=np.uint8)
-    metadata = np.full(launched.metadata.shape, SENTINEL, dtype=np.uint8)
-    statuses = []
-    for i, found in enumerate(expected):
-        if isinstance(found, int):
-            statuses.append(found)
-            continue
-        statuses.append(runtime.COMPRESS_OK)
-        for g in range(found.table.shape[0]):
-            at = GUARD + i * launched.instance_stride + g * launched.segment_stride
-            want[at: at + 4 * found.table.shape[1]] = found.table[g].reshape(-1)
-        at = GUARD + i * launched.max_tracks * 8
-        metadata[at: at + 8 * found.base.shells.shape[0]] = found.base.shells.view(np.uint8).reshape(-1)
-    different = np.flatnonzero(launched.flat != want)
-    assert different.size == 0, (different.size, [(int(d - GUARD) // launched.instance_stride, int(d - GUARD) % launched.instance_stride // launched.segment_stride,
-                                                   int(d - GUARD) % launched.segment_stride // 4, int(d - GUARD) % 4, int(launched.flat[d]), int(want[d])) for d in different[:12]])
-    assert launched.results[:, 0].tolist() == statuses and (launched.results[:, 1] == 0).all()
-    assert launched.rejected == statuses.count(REFUSED)
-    if all(not isinstance(found, int) for found in expected):
-        assert np.array_equal(launched.metadata, metadata)
+def launch(ctx, handles, entry=Entry("search"), max_tracks=MAX_TRACKS, max_samples=MAX_SAMPLES, **settings):
+    """One launch over `handles` into a table of sentinel bytes (tests/compress_launches.py)"""
+    return launches.launch(ctx, entry, handles, max_tracks, max_samples, **settings)
 
 
 @pytest.fixture(scope="module")
@@ -127,7 +57,7 @@ def test_the_table_is_the_restatements(sweep):
     shell as metadata"""
     ctx, handles, clips, parents, found = sweep
     order = [(7 * i + 2) % len(handles) for i in range(len(handles) + 3)]
-    check(launch(ctx, [handles[k] for k in order], flags=OPTIMIZE_LOOPS, parents=parents), [found[k] for k in order])
+    check_table(launch(ctx, [handles[k] for k in order], flags=OPTIMIZE_LOOPS, parents=parents), [found[k] for k in order])
     by_shape = dict(zip(SHAPES, found))
     assert [len(by_shape[17, s].base.segments) for s in SAMPLE_COUNTS] == [1, 1, 2, 4]
     assert any(f.base.wrap and f.base.num_samples == clip.shape[0] - 1 for f, clip in zip(found, clips))            # a vote that removed a sample
@@ -147,7 +77,7 @@ def test_the_three_levels_are_one_search(sweep):
     ctx, handles, clips, parents, found = sweep
     picked = [k for k, shape in enumerate(SHAPES) if shape in ((17, 33), (5, 65))]
     for level in (0, 1):
-        check(launch(ctx, [handles[k] for k in picked], flags=OPTIMIZE_LOOPS, parents=parents, level=level), [found[k] for k in picked])
+        check_table(launch(ctx, [handles[k] for k in picked], flags=OPTIMIZE_LOOPS, parents=parents, level=level), [found[k] for k in picked])
 
 
 def test_all_roots_and_a_single_chain(ctx):
@@ -159,10 +89,10 @@ def test_all_roots_and_a_single_chain(ctx):
         h_roots, h_chain = arrays.add(roots), arrays.add(chain)
         found = find(roots)
         assert np.array_equal(found.table, found.local_table)
-        check(launch(ctx, [h_roots], max_tracks=17, max_samples=33), [found])
+        check_table(launch(ctx, [h_roots], max_tracks=17, max_samples=33), [found])
         deep = find(chain, parents=chain_parents)
         assert not np.array_equal(deep.table, deep.local_table)
-        check(launch(ctx, [h_chain, h_chain], max_tracks=17, max_samples=33, parents=chain_parents), [deep, deep])
+        check_table(launch(ctx, [h_chain, h_chain], max_tracks=17, max_samples=33, parents=chain_parents), [deep, deep])
 
 
 def half_frozen(seed, num_samples, num_tracks):
@@ -185,7 +115,7 @@ def test_rate_0_where_a_segment_stands_still(ctx):
             for kind in range(3):
                 tracks = np.flatnonzero(f.base.types[kind] == ANIMATED)
                 assert (f.table[0, tracks, kind] != 0).all() and (f.table[-1, tracks, kind] == 0).all()
-        check(launch(ctx, handles, max_tracks=17, parents=parents), found)
+        check_table(launch(ctx, handles, max_tracks=17, parents=parents), found)
 
 
 def test_precisions_and_shell_distances_per_track_and_a_default_pose(ctx):
@@ -200,7 +130,7 @@ def test_precisions_and_shell_distances_per_track_and_a_default_pose(ctx):
         handles = [arrays.add(samples) for samples in clips]
         found = [find(samples, **settings) for samples in clips]
         assert len({float(p) for p in found[0].shells[:, :, 1].reshape(-1)}) > 1
-        check(launch(ctx, handles, max_tracks=17, **settings), found)
+        check_table(launch(ctx, handles, max_tracks=17, **settings), found)
 
 
 def test_an_instance_that_ends_with_a_status_leaves_its_rows(ctx):
@@ -215,9 +145,9 @@ def test_an_instance_that_ends_with_a_status_leaves_its_rows(ctx):
         h_bad = arrays.add(bad)
         f_small, f_long = find(small, parents=parents), find(long, parents=parents)
         settings = {"max_tracks": 5, "max_samples": 40, "parents": parents}
-        check(launch(ctx, [h_small, 0, h_long, h_bad, h_small], **settings), [f_small, REFUSED, f_long, NOT_FINITE, f_small])
-        check(launch(ctx, [h_small, h_long, h_small], max_tracks=5, max_samples=39, parents=parents), [f_small, REFUSED, f_small])
-        check(launch(ctx, [h_small, h_long], max_tracks=5, max_samples=40, parents=np.array([0xFFFFFFFF, 0, 3, 0, 0], dtype=np.uint32)), [REFUSED, REFUSED])
+        check_table(launch(ctx, [h_small, 0, h_long, h_bad, h_small], **settings), [f_small, REFUSED, f_long, NOT_FINITE, f_small])
+        check_table(launch(ctx, [h_small, h_long, h_small], max_tracks=5, max_samples=39, parents=parents), [f_small, REFUSED, f_small])
+        check_table(launch(ctx, [h_small, h_long], max_tracks=5, max_samples=40, parents=np.array([0xFFFFFFFF, 0, 3, 0, 0], dtype=np.uint32)), [REFUSED, REFUSED])
         with pytest.raises(ValueError, match="ACLHIP_COMPRESS_REFUSED"):
             runtime.find_bit_rates(ctx, [h_small, h_long], parents=np.array([0xFFFFFFFF, 0, 3, 0, 0], dtype=np.uint32), precision=PRECISION, shell_distance=SHELL)
         with pytest.raises(RuntimeError, match="not finite"):
@@ -228,36 +158,16 @@ def test_strides_larger_than_the_minimum(sweep):
     ctx, handles, clips, parents, found = sweep
     picked = [k for k, shape in enumerate(SHAPES) if shape in ((3, 33), (65, 33), (17, 65), (1, 2))]
     segment_stride = 4 * MAX_TRACKS + 12
-    check(launch(ctx, [handles[k] for k in picked], flags=OPTIMIZE_LOOPS, parents=parents, segment_stride=segment_stride, instance_stride=MAX_SEGMENTS * segment_stride + 8),
+    check_table(launch(ctx, [handles[k] for k in picked], flags=OPTIMIZE_LOOPS, parents=parents, segment_stride=segment_stride, instance_stride=MAX_SEGMENTS * segment_stride + 8),
           [found[k] for k in picked])
 
 
 def test_two_runs_give_the_same_bytes_and_a_capture_replays_to_them(sweep):
-    import torch
     ctx, handles, clips, parents, found = sweep
     picked = [k for k, shape in enumerate(SHAPES) if shape[0] in (5, 17)]
-    runs = [launch(ctx, [handles[k] for k in picked], flags=OPTIMIZE_LOOPS, parents=parents) for _ in range(2)]
-    assert np.array_equal(runs[0].flat, runs[1].flat) and np.array_equal(runs[0].results, runs[1].results) and np.array_equal(runs[0].metadata, runs[1].metadata)
-    device = torch.device("cuda:0")
-    n, instance_stride = len(picked), runs[0].instance_stride
-    d_parents = torch.from_numpy(parents.view(np.int32)).to(device)
-    d_handles = torch.from_numpy(np.asarray([handles[k] for k in picked], dtype=np.uint32).view(np.int32)).to(device)
-    flat = torch.full((n * instance_stride,), SENTINEL, dtype=torch.uint8, device=device)
-    d_results = torch.zeros((n, 2), dtype=torch.int32, device=device)
-    d_workspace = torch.zeros((runtime.find_bit_rates_workspace_bytes(n, MAX_TRACKS, MAX_SAMPLES),), dtype=torch.uint8, device=device)
-    desc = runtime.FindBitRatesDesc()
-    desc.flags, desc.max_tracks, desc.max_samples, desc.precision, desc.shell_distance, desc.level = OPTIMIZE_LOOPS, MAX_TRACKS, MAX_SAMPLES, PRECISION, SHELL, 2
-    desc.parent_indices, desc.num_table_tracks, desc.workspace = d_parents.data_ptr(), MAX_TRACKS, d_workspace.data_ptr()
-    stream = torch.cuda.Stream(device)
-    with torch.cuda.stream(stream):
-        captured = torch.cuda.CUDAGraph()
-        with torch.cuda.graph(captured, stream=stream):
-            ctx.find_bit_rates_batch(d_handles.data_ptr(), n, desc, flat.data_ptr(), instance_stride, runs[0].segment_stride, d_results.data_ptr(), stream=stream.cuda_stream)
-        flat.fill_(SENTINEL)         # what the capture itself may have left does not count
-        captured.replay()
-    stream.synchronize()
-    assert np.array_equal(flat.cpu().numpy(), runs[0].flat[GUARD: GUARD + n * instance_stride])
-    assert np.array_equal(d_results.cpu().numpy().view(np.uint32), runs[0].results[:n])
+    runs = [launch(ctx, [handles[k] for k in picked], flags=OPTIMIZE_LOOPS, parents=parents, graph=graph) for graph in (False, False, True)]
+    assert same(runs[0], runs[1])
+    assert same(runs[0], runs[2])           # the same launch captured into a graph and replayed
 
 
 def test_search_then_compress_end_to_end(sweep):

@@ -1,27 +1,26 @@
 """aclhip_find_bit_rates_level_batch through the C ABI: find_optimal_bit_rates at the levels high and highest, and at automatic, of
 registered raw track arrays. The expected tables are the restatement's (tests/bit_rate_search_levels_restatement.py, which
 tests/test_bit_rate_search_levels_oracle.py holds to the reference's compressor), and every comparison is on BYTES, as in
-tests/test_gpu_bit_rate_search.py, whose launch and check this file goes through: a table of sentinel bytes behind guards, every
-byte of every row held to the restatement and everything else to the sentinel, the statuses, the refusal count, the clip's shell as
-metadata, the workspace no larger than its size function says -- and here the second word of every result, the level that was searched.
+tests/test_gpu_bit_rate_search.py, through the launch and check_table of tests/compress_launches.py: a table of sentinel bytes behind
+guards, every byte of every row held to the restatement and everything else to the sentinel, the statuses, the refusal count, the
+clip's shell as metadata, the workspace no larger than its size function says -- and here the second word of every result, the level
+that was searched.
 
 The shapes are the smallest at which each mechanism can still go wrong: T in 1, 2, 3, 5, 17, 65 by S in 2, 31, 33 under tree(0, 65);
 chains of 2 links (the single {2,1} arrangement, no triple), of 3 (the one {1,1,1}), of 9 and of 17 (680 arrangements of {1,1,1}); and
 for every edge the wider first loop has (bit_rate_search_levels_restatement.VISITS) an input whose restatement went over it, asserted
 before the launch. Needs a GPU. Fails on a library without the call."""
 import collections
-import contextlib
 
 import numpy as np
 import pytest
 
 from acl_amd import runtime
 import bit_rate_search_levels_restatement as levels
+import compress_launches as launches
 import variable_compress_restatement as restatement
-import test_gpu_bit_rate_search as search_launches
+from compress_launches import PRECISION, RATE, SENTINEL, SHELL, Entry, Registered, check_table, ctx, same  # noqa: F401  (ctx: this module's fixture)
 from matrix_metric_compress_restatement import METRIC_MATRIX, METRIC_QVVF
-from test_gpu_bit_rate_search import PRECISION, RATE, SHELL
-from test_gpu_lossy_rotation_compress import GUARD, SENTINEL, Registered
 from variable_compress_restatement import IDENTITY, OPTIMIZE_LOOPS
 
 pytestmark = pytest.mark.gpu
@@ -35,54 +34,20 @@ NEW_EDGES = tuple("shape_%s_won" % name for name in levels.SHAPES) + ("invalid_p
                                                                          "two_one_on_two_links")
 
 
-class ThroughTheLevelFront:
-    """a context whose search launch is aclhip_find_bit_rates_level_batch at `metric`; everything else is the context's"""
-    def __init__(self, context, metric):
-        self.context, self.metric = context, metric
-
-    def __getattr__(self, name):
-        return getattr(self.context, name)
-
-    def find_bit_rates_batch(self, *arguments, **keywords):
-        return self.context.find_bit_rates_level_batch(*arguments, metric=self.metric, **keywords)
-
-
-@contextlib.contextmanager
-def level_workspace():
-    """test_gpu_bit_rate_search.launch sizes (and guards) the workspace by runtime.find_bit_rates_workspace_bytes: this call's while the block runs"""
-    saved = runtime.find_bit_rates_workspace_bytes
-    runtime.find_bit_rates_workspace_bytes = runtime.find_bit_rates_level_workspace_bytes
-    try:
-        yield
-    finally:
-        runtime.find_bit_rates_workspace_bytes = saved
-
-
-@pytest.fixture(scope="module")
-def ctx():
-    context = runtime.Context(0)
-    yield context
-    context.close()
-
-
 def find(samples, level=HIGHEST, metric=METRIC_QVVF, **settings):
     settings.setdefault("precision", PRECISION)
     settings.setdefault("shell_distance", SHELL)
     return levels.find_bit_rates_metric(samples, RATE, metric, level=level, **settings)
 
 
-def launch(ctx, handles, level=HIGHEST, metric=METRIC_QVVF, **settings):
-    settings.setdefault("max_samples", MAX_SAMPLES)
-    with level_workspace():
-        return search_launches.launch(ThroughTheLevelFront(ctx, metric), handles, level=level, **settings)
+def launch(ctx, handles, level=HIGHEST, metric=METRIC_QVVF, entry=None, max_tracks=MAX_TRACKS, max_samples=MAX_SAMPLES, **settings):
+    """One launch of aclhip_find_bit_rates_level_batch at `metric` (or of `entry`) over `handles` (tests/compress_launches.py)"""
+    return launches.launch(ctx, entry or Entry("search", "level", metric), handles, max_tracks, max_samples, level=level, **settings)
 
 
 def check(launched, expected):
-    """test_gpu_bit_rate_search.check, and the level that was searched in the second word of every served instance's result"""
-    assert launched.results[:, 1].tolist() == [0 if isinstance(found, int) else found.level for found in expected]
-    launched.results = launched.results.copy()
-    launched.results[:, 1] = 0
-    search_launches.check(launched, expected)
+    """the table, and the level that was searched in the second word of every served instance's result"""
+    check_table(launched, expected, levels=True)
 
 
 def edges_of(found):
@@ -132,8 +97,8 @@ def test_the_levels_below_high_are_the_other_calls_bytes(sweep):
     for level in (0, 1, 2):
         for metric in (METRIC_QVVF, METRIC_MATRIX) if level == 2 else (METRIC_QVVF,):
             new = launch(ctx, [handles[k] for k in picked], level, metric, flags=OPTIMIZE_LOOPS, parents=parents)
-            front = ctx if metric == METRIC_QVVF else type("Front", (ThroughTheLevelFront,), {"find_bit_rates_batch": lambda self, *a, **k: self.context.find_bit_rates_metric_batch(*a, metric=self.metric, **k)})(ctx, metric)
-            old = search_launches.launch(front, [handles[k] for k in picked], max_samples=MAX_SAMPLES, level=level, flags=OPTIMIZE_LOOPS, parents=parents)
+            other = Entry("search") if metric == METRIC_QVVF else Entry("search", "metric", metric)
+            old = launch(ctx, [handles[k] for k in picked], level, entry=other, flags=OPTIMIZE_LOOPS, parents=parents)
             assert np.array_equal(new.flat, old.flat) and np.array_equal(new.metadata, old.metadata)
             assert np.array_equal(new.results[:, 0], old.results[:, 0]) and (old.results[:, 1] == 0).all() and (new.results[:, 1] == level).all()
             assert (new.flat != SENTINEL).any()
@@ -224,32 +189,11 @@ def test_strides_larger_than_the_minimum(sweep):
 
 
 def test_two_runs_give_the_same_bytes_and_a_capture_replays_to_them(sweep):
-    import torch
     ctx, handles, clips, parents, found = sweep
     picked = [k for k, shape in enumerate(SHAPES) if shape[0] in (5, 17)]
-    runs = [launch(ctx, [handles[k] for k in picked], HIGHEST, flags=OPTIMIZE_LOOPS, parents=parents) for _ in range(2)]
-    assert np.array_equal(runs[0].flat, runs[1].flat) and np.array_equal(runs[0].results, runs[1].results) and np.array_equal(runs[0].metadata, runs[1].metadata)
-    device = torch.device("cuda:0")
-    n, instance_stride = len(picked), runs[0].instance_stride
-    d_parents = torch.from_numpy(parents.view(np.int32)).to(device)
-    d_handles = torch.from_numpy(np.asarray([handles[k] for k in picked], dtype=np.uint32).view(np.int32)).to(device)
-    flat = torch.full((n * instance_stride,), SENTINEL, dtype=torch.uint8, device=device)
-    d_results = torch.zeros((n, 2), dtype=torch.int32, device=device)
-    d_workspace = torch.zeros((runtime.find_bit_rates_level_workspace_bytes(n, MAX_TRACKS, MAX_SAMPLES),), dtype=torch.uint8, device=device)
-    desc = runtime.FindBitRatesDesc()
-    desc.flags, desc.max_tracks, desc.max_samples, desc.precision, desc.shell_distance, desc.level = OPTIMIZE_LOOPS, MAX_TRACKS, MAX_SAMPLES, PRECISION, SHELL, HIGHEST
-    desc.parent_indices, desc.num_table_tracks, desc.workspace = d_parents.data_ptr(), MAX_TRACKS, d_workspace.data_ptr()
-    stream = torch.cuda.Stream(device)
-    with torch.cuda.stream(stream):
-        captured = torch.cuda.CUDAGraph()
-        with torch.cuda.graph(captured, stream=stream):
-            ctx.find_bit_rates_level_batch(d_handles.data_ptr(), n, desc, flat.data_ptr(), instance_stride, runs[0].segment_stride, d_results.data_ptr(), stream=stream.cuda_stream)
-        flat.fill_(SENTINEL)         # what the capture itself may have left does not count
-        d_results.zero_()
-        captured.replay()
-    stream.synchronize()
-    assert np.array_equal(flat.cpu().numpy(), runs[0].flat[GUARD: GUARD + n * instance_stride])
-    assert np.array_equal(d_results.cpu().numpy().view(np.uint32), runs[0].results[:n]) and (runs[0].results[:n, 1] == HIGHEST).all()
+    runs = [launch(ctx, [handles[k] for k in picked], HIGHEST, flags=OPTIMIZE_LOOPS, parents=parents, graph=graph) for graph in (False, False, True)]
+    assert same(runs[0], runs[1])
+    assert same(runs[0], runs[2]) and (runs[2].results[:, 1] == HIGHEST).all()           # the same launch captured into a graph and replayed
 
 
 def test_automatic_decides_the_level_per_instance(ctx):

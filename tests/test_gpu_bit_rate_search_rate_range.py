@@ -14,8 +14,8 @@ and a repeated handle in each (T in 1, 5, 17: one track has no parent, every obj
                  either order of raising ends on the same rates)
   chains of 17   gentle motion, and tight motion, where saturation climbs the longest chain
 
-As in tests/test_gpu_bit_rate_search.py the expected tables are the restatement's and every comparison is on BYTES (its launch and
-check: every byte of every row, the sentinel everywhere else, the results, the shell metadata). Before a launch each test asserts on
+As in tests/test_gpu_bit_rate_search.py the expected tables are the restatement's and every comparison is on BYTES (the launch and
+check_table of tests/compress_launches.py: every byte of every row, the sentinel everywhere else, the results, the shell metadata). Before a launch each test asserts on
 the restatement's tables and Search.visits that its input goes where it is there to go: the comparison cannot pass on an input that
 never went there. tests/test_bit_rate_search_rate_range_oracle.py holds the restatement to the reference's compressor on the gentle
 and the far families; the tight and the unreachable inputs have no reference to be held to (the reference's own search is not stable
@@ -29,18 +29,15 @@ import numpy as np
 import pytest
 
 from acl_amd import runtime
+import compress_launches as launches
 import matrix_metric_compress_restatement as metric_restatement
 import variable_compress_restatement as restatement
-import test_gpu_bit_rate_search as search_launches
+from compress_launches import PRECISION, RATE, SHELL, Entry, Registered, check_table, ctx  # noqa: F401  (ctx: this module's fixture)
 from matrix_metric_compress_restatement import METRIC_MATRIX, METRIC_QVVF
-from test_gpu_lossy_rotation_compress import Registered
-from test_gpu_matrix_metric_compress import ThroughTheMetricFronts
 from variable_compress_restatement import ANIMATED, IDENTITY
 
 pytestmark = pytest.mark.gpu
 
-RATE = 32.0
-PRECISION, SHELL = 0.01, 3.0
 TIGHT = 1.0e-5
 UNREACHABLE = 1.0e-9
 TRACK_COUNTS, SAMPLE_COUNTS = (1, 5, 17), (2, 31, 33, 65)
@@ -51,16 +48,9 @@ PARENTS = restatement.tree(0, MAX_TRACKS)
 CHAIN = restatement.tree(0, MAX_TRACKS, "chain")
 
 
-@pytest.fixture(scope="module")
-def ctx():
-    context = runtime.Context(0)
-    yield context
-    context.close()
-
-
-def through(ctx, metric):
+def through(metric):
     """the entry point without a metric for the qvvf metric, the _metric front for the matrix metric"""
-    return ctx if metric == METRIC_QVVF else ThroughTheMetricFronts(ctx, metric)
+    return Entry("search") if metric == METRIC_QVVF else Entry("search", "metric", metric)
 
 
 def find(samples, metric, **settings):
@@ -96,9 +86,10 @@ def hold(ctx, clips, found, **settings):
         handles = [arrays.add(samples) for samples in clips]
         order = [(7 * i + 2) % len(handles) for i in range(len(handles) + 3)] if len(handles) > 1 else [0, 0]
         settings.setdefault("max_tracks", MAX_TRACKS)
+        settings.setdefault("max_samples", MAX_SAMPLES)
         for metric in METRICS:
-            launched = search_launches.launch(through(ctx, metric), [handles[k] for k in order], **settings)
-            search_launches.check(launched, [found[metric][k] for k in order])
+            launched = launches.launch(ctx, through(metric), [handles[k] for k in order], **settings)
+            check_table(launched, [found[metric][k] for k in order])
 
 
 def unreachable_precisions(*leaves):

@@ -11,16 +11,14 @@ import pytest
 
 from acl_amd import runtime
 from oracle import bindings as ob
+import compress_launches as launches
 import lossy_rotation_compress_restatement as restatement
 import transform_compress_restatement as raw_restatement
+from compress_launches import GUARD, PRECISION, RATE, SENTINEL, SHELL, Entry, Registered, check_rows, ctx, same  # noqa: F401  (ctx: this module's fixture)
 from lossy_rotation_compress_restatement import ANIMATED, CONSTANT, DEFAULT, IDENTITY, LANES, NO_PARENT, OPTIMIZE_LOOPS
 
 pytestmark = pytest.mark.gpu
 
-RATE = 32.0
-SENTINEL = 0xA5
-GUARD = 256
-PRECISION, SHELL = 0.01, 3.0
 PARENTS, DESCRIPTIONS = restatement.INCLUDE_PARENT_TRACK_INDICES, restatement.INCLUDE_TRACK_DESCRIPTIONS
 # T: the wave edges of the layout's passes of 64 tracks and the 16 tracks of a packed word; S: the wave edges of the sample reductions,
 # and S' = 1 behind a vote
@@ -29,112 +27,9 @@ MAX_TRACKS = 130
 TREES = ("chain", "star", "two_roots")
 
 
-class Launched:
-    pass
-
-
-@pytest.fixture(scope="module")
-def ctx():
-    context = runtime.Context(0)
-    yield context
-    context.close()
-
-
-def launch(ctx, handles, max_tracks=MAX_TRACKS, max_samples=129, rotation_format=runtime.ROTATION_QUATF_DROP_W_FULL, flags=0, default_pose=None, parents=None,
-           track_precisions=None, track_shell_distances=None, precision=PRECISION, shell_distance=SHELL, stride=None, with_metadata=True, raw_call=False):
-    """One launch over `handles`; rows of the bound of (max_tracks, max_samples) unless `stride` says otherwise. raw_call:
-    aclhip_compress_raw_tracks_batch with the same arguments instead."""
-    import torch
-    device = torch.device("cuda:0")
-    n = len(handles)
-    if stride is None:
-        stride = runtime.transform_compress_bound(max_tracks, max_samples, flags)
-    flat = torch.full((GUARD + n * stride + GUARD,), SENTINEL, dtype=torch.uint8, device=device)
-    assert flat.data_ptr() % 16 == 0
-    host_handles = np.asarray(handles, dtype=np.uint32)
-    d_handles = torch.from_numpy(host_handles.view(np.int32)).to(device)
-    d_results = torch.full((n, 2), 0x5A5A5A5A, dtype=torch.int32, device=device)
-    workspace_bytes = runtime.transform_compress_workspace_bytes(n, max_tracks) if raw_call else runtime.compress_tracks_workspace_bytes(n, max_tracks)
-    d_workspace = torch.full((workspace_bytes + GUARD,), SENTINEL, dtype=torch.uint8, device=device)
-    d_metadata = torch.full((GUARD + n * max_tracks * 8 + GUARD,), SENTINEL, dtype=torch.uint8, device=device)
-    desc = runtime.TransformCompressDesc() if raw_call else runtime.CompressTracksDesc()
-    if not raw_call:
-        desc.rotation_format = rotation_format
-        if with_metadata:
-            desc.shell_metadata = d_metadata.data_ptr() + GUARD
-    desc.flags, desc.max_tracks, desc.precision, desc.shell_distance = flags, max_tracks, precision, shell_distance
-    desc.workspace = d_workspace.data_ptr()
-    tables = []
-    for field, table, dtype in (("default_pose", default_pose, np.float32), ("parent_indices", parents, np.uint32), ("track_precisions", track_precisions, np.float32),
-                                ("track_shell_distances", track_shell_distances, np.float32)):
-        if table is not None:
-            host = np.ascontiguousarray(table, dtype=dtype)
-            d_table = torch.from_numpy(host.view(np.int32)).to(device)
-            tables.append((host, d_table))
-            setattr(desc, field, d_table.data_ptr())
-            desc.num_table_tracks = host.shape[0]
-    rejected_before = ctx.rejected_instance_count()
-    stream = torch.cuda.current_stream(device)
-    call = ctx.compress_raw_tracks_batch if raw_call else ctx.compress_tracks_batch
-    call(d_handles.data_ptr(), n, desc, flat.data_ptr() + GUARD, stride, d_results.data_ptr(), stream=stream.cuda_stream)
-    stream.synchronize()
-    out = Launched()
-    out.flat, out.stride, out.n, out.max_tracks = flat.cpu().numpy(), stride, n, max_tracks
-    out.results = d_results.cpu().numpy().view(np.uint32).reshape(n, 2)
-    out.metadata = d_metadata.cpu().numpy()
-    out.rejected = ctx.rejected_instance_count() - rejected_before
-    assert np.array_equal(d_handles.cpu().numpy().view(np.uint32), host_handles)                # the inputs are only read
-    assert np.all(d_workspace.cpu().numpy()[workspace_bytes:] == SENTINEL)                      # the workspace is as large as it says
-    for host, d_table in tables:
-        assert np.array_equal(d_table.cpu().numpy().view(np.uint32), host.view(np.uint32))
-    return out
-
-
-def check(out, expected):
-    """expected: per instance a Compressed (blob and shells), a blob alone (uint8: the shell metadata is not looked at), or the status
-    of an instance that writes nothing"""
-    want = np.full(out.flat.shape, SENTINEL, dtype=np.uint8)
-    want_metadata = np.full(out.metadata.shape, SENTINEL, dtype=np.uint8)
-    want_results = np.zeros((out.n, 2), dtype=np.uint32)
-    with_shells = True
-    for i, item in enumerate(expected):
-        if isinstance(item, int):
-            want_results[i] = (item, 0)
-            continue
-        blob = item if isinstance(item, np.ndarray) else item.blob
-        want[GUARD + i * out.stride: GUARD + i * out.stride + blob.size] = blob
-        want_results[i] = (runtime.COMPRESS_OK, blob.size)
-        if isinstance(item, np.ndarray):
-            with_shells = False
-        else:
-            shells = np.ascontiguousarray(item.shells, dtype=np.float32).view(np.uint8).reshape(-1)
-            at = GUARD + i * out.max_tracks * 8
-            want_metadata[at: at + shells.size] = shells
-    assert np.array_equal(out.results, want_results), (out.results[:8], want_results[:8])
-    different = np.flatnonzero(out.flat != want)
-    assert different.size == 0, [(int(at - GUARD) // out.stride, int(at - GUARD) % out.stride, int(out.flat[at]), int(want[at])) for at in different[:8]]
-    if with_shells:
-        different = np.flatnonzero(out.metadata != want_metadata)
-        assert different.size == 0, [(int(at - GUARD) // (out.max_tracks * 8), int(at - GUARD) % (out.max_tracks * 8) // 8, int(out.metadata[at]), int(want_metadata[at])) for at in different[:8]]
-    assert out.rejected == sum(1 for item in expected if isinstance(item, int) and item == runtime.COMPRESS_REFUSED)
-
-
-class Registered:
-    """arrays registered with one context, unregistered together"""
-    def __init__(self, ctx):
-        self.ctx, self.handles = ctx, []
-
-    def add(self, samples, looping=runtime.LOOP_CLAMP):
-        handle = self.ctx.register_raw_tracks(samples, RATE, looping)
-        self.handles.append(handle)
-        return handle
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *args):
-        for handle in self.handles:
-            self.ctx.unregister_raw_tracks(handle)
+def launch(ctx, handles, entry=Entry("tracks"), max_tracks=MAX_TRACKS, max_samples=129, **settings):
+    """One launch over `handles` (tests/compress_launches.py); rows of the bound of (max_tracks, max_samples) unless `stride` says otherwise"""
+    return launches.launch(ctx, entry, handles, max_tracks, max_samples, **settings)
 
 
 def sweep_clips():
@@ -164,7 +59,7 @@ def test_the_blobs_results_and_shells_are_the_restatement(sweep, shape):
     ctx, handles, clips, expected = sweep
     parents, compressed = expected[shape]
     order = [(5 * i + 2) % len(handles) for i in range(len(handles) + 7)]
-    check(launch(ctx, [handles[k] for k in order], flags=OPTIMIZE_LOOPS, parents=parents), [compressed[k] for k in order])
+    check_rows(launch(ctx, [handles[k] for k in order], flags=OPTIMIZE_LOOPS, parents=parents), [compressed[k] for k in order])
     if shape == "chain":
         assert any(c.wrap and c.num_samples == 1 for c in compressed) and any(not c.wrap for c in compressed)        # S' = 1 behind a vote
         kinds = np.concatenate([c.types[0] for c in compressed])
@@ -177,7 +72,7 @@ def test_loops_off_metadata_and_tables(sweep):
     precisions and shell distances; no shell metadata asked for"""
     ctx, handles, clips, _ = sweep
     parents, compressed = sweep_expected(clips, "star")
-    check(launch(ctx, handles, parents=parents), compressed)
+    check_rows(launch(ctx, handles, parents=parents), compressed)
     assert not any(c.wrap for c in compressed)
     pose = raw_restatement.bind_pose(21, MAX_TRACKS)
     precisions = np.linspace(0.002, 0.05, MAX_TRACKS).astype(np.float32)
@@ -186,11 +81,11 @@ def test_loops_off_metadata_and_tables(sweep):
     flags = PARENTS | DESCRIPTIONS | OPTIMIZE_LOOPS
     compressed = [restatement.compress(samples, RATE, default_pose=pose, parents=parents, flags=flags, track_precisions=precisions, track_shell_distances=shells) for samples in clips]
     out = launch(ctx, handles, flags=flags, default_pose=pose, parents=parents, track_precisions=precisions, track_shell_distances=shells)
-    check(out, compressed)
-    check(launch(ctx, handles, flags=flags, default_pose=pose, parents=parents, track_precisions=precisions, track_shell_distances=shells, with_metadata=False),
+    check_rows(out, compressed)
+    check_rows(launch(ctx, handles, flags=flags, default_pose=pose, parents=parents, track_precisions=precisions, track_shell_distances=shells, with_metadata=False),
           [c.blob for c in compressed])
     # no table at all: every track a root of its own shell
-    check(launch(ctx, handles[:4], flags=PARENTS), [restatement.compress(samples, RATE, flags=PARENTS, precision=PRECISION, shell_distance=SHELL) for samples in clips[:4]])
+    check_rows(launch(ctx, handles[:4], flags=PARENTS), [restatement.compress(samples, RATE, flags=PARENTS, precision=PRECISION, shell_distance=SHELL) for samples in clips[:4]])
 
 
 def test_rotation_format_0_is_the_raw_call(sweep):
@@ -205,7 +100,7 @@ def test_rotation_format_0_is_the_raw_call(sweep):
         batch = handles + [arrays.add(long), arrays.add(bad), 0, handles[0]]
         for flags in (0, OPTIMIZE_LOOPS | PARENTS | DESCRIPTIONS):
             new = launch(ctx, batch, rotation_format=runtime.ROTATION_QUATF_FULL, flags=flags, parents=parents)
-            old = launch(ctx, batch, flags=flags, parents=parents, raw_call=True)
+            old = launch(ctx, batch, Entry("raw"), flags=flags, parents=parents)
             assert np.array_equal(new.flat, old.flat) and np.array_equal(new.results, old.results) and new.rejected == old.rejected == 1
             assert np.all(new.metadata == SENTINEL)
             assert new.results[len(handles)].tolist() == [runtime.COMPRESS_NOT_NORMALIZED, 0] and new.results[len(handles) + 1].tolist() == [runtime.COMPRESS_NOT_FINITE, 0]
@@ -213,7 +108,7 @@ def test_rotation_format_0_is_the_raw_call(sweep):
         # and the drop-w call takes the rotation of length 1.5
         expected = restatement.compress(long, RATE, parents=parents, precision=PRECISION, shell_distance=SHELL)
         assert np.array_equal(expected.blob, restatement.compress(clips[2], RATE, parents=parents, precision=PRECISION, shell_distance=SHELL).blob)
-        check(launch(ctx, [batch[len(handles)]], parents=parents), [expected])
+        check_rows(launch(ctx, [batch[len(handles)]], parents=parents), [expected])
 
 
 def shell_error_of_poses(shells, registered, decoded):
@@ -273,7 +168,7 @@ def test_the_vote_is_the_whole_list_or_nothing(ctx):
                     restatement.compress(apart, RATE, parents=parents, flags=OPTIMIZE_LOOPS, precision=PRECISION, shell_distance=SHELL),
                     restatement.compress(samples, RATE, parents=parents, flags=OPTIMIZE_LOOPS, precision=PRECISION, shell_distance=SHELL, looping_wrap=True)]
         assert [(c.wrap, c.num_samples) for c in expected] == [(True, 8), (False, 9), (True, 9)]
-        check(launch(ctx, handles, max_tracks=17, max_samples=9, flags=OPTIMIZE_LOOPS, parents=parents), expected)
+        check_rows(launch(ctx, handles, max_tracks=17, max_samples=9, flags=OPTIMIZE_LOOPS, parents=parents), expected)
 
 
 def test_statuses_and_refusals_leave_their_rows(ctx):
@@ -296,7 +191,7 @@ def test_statuses_and_refusals_leave_their_rows(ctx):
         samples[5, 7, 0:4] = 0.0                                # a zero quaternion: 0 * (1 / 0) is not finite
         bad.append(arrays.add(samples))
         handles = [h_small] + bad + [h_large]
-        check(launch(ctx, handles, max_tracks=9, max_samples=12, parents=parents), [c_small] + [not_finite] * len(bad) + [c_large])
+        check_rows(launch(ctx, handles, max_tracks=9, max_samples=12, parents=parents), [c_small] + [not_finite] * len(bad) + [c_large])
         with pytest.raises(RuntimeError, match="Some samples are not finite"):
             runtime.compress_tracks(ctx, [h_small, bad[-1]], parents=parents)
 
@@ -304,7 +199,7 @@ def test_statuses_and_refusals_leave_their_rows(ctx):
         for forward in ([NO_PARENT, 0, 2, 0, 0, 1, 2, 3, 4], [NO_PARENT, 0, 1, 2, 3, 4, 5, 8, 0], [NO_PARENT, 0, 1, 2, 6, 0, 0, 0, 0]):
             table = np.array(forward, dtype=np.uint32)
             small_ok = not any(b <= p < 4 for b, p in enumerate(forward[:4]))
-            check(launch(ctx, [h_small, h_large, h_small], max_tracks=9, max_samples=12, parents=table),
+            check_rows(launch(ctx, [h_small, h_large, h_small], max_tracks=9, max_samples=12, parents=table),
                   [restatement.compress(small, RATE, parents=table, **settings) if small_ok else refused, refused,
                    restatement.compress(small, RATE, parents=table, **settings) if small_ok else refused])
         with pytest.raises(ValueError, match="ACLHIP_COMPRESS_REFUSED"):
@@ -313,51 +208,30 @@ def test_statuses_and_refusals_leave_their_rows(ctx):
         retired = ctx.register_raw_tracks(small, RATE)         # (behind every other registration: its slot is not handed out again here)
         ctx.unregister_raw_tracks(retired)
         handles = [h_small, 0, 4000, retired, 0xFFFFFFFF, h_large, h_small]
-        check(launch(ctx, handles, max_tracks=9, max_samples=12, parents=parents), [c_small, refused, refused, refused, refused, c_large, c_small])
+        check_rows(launch(ctx, handles, max_tracks=9, max_samples=12, parents=parents), [c_small, refused, refused, refused, refused, c_large, c_small])
         # max_tracks 4: the array of 9 tracks is refused
-        check(launch(ctx, handles, max_tracks=4, max_samples=12, parents=parents[:4]),
+        check_rows(launch(ctx, handles, max_tracks=4, max_samples=12, parents=parents[:4]),
               [restatement.compress(small, RATE, parents=parents[:4], **settings), refused, refused, refused, refused, refused, restatement.compress(small, RATE, parents=parents[:4], **settings)])
         # tables of 4 entries, each kind alone
         roots = restatement.compress(small, RATE, **settings)
         short = {"default_pose": np.tile(IDENTITY, (4, 1)), "parents": np.full(4, NO_PARENT, dtype=np.uint32),
                  "track_precisions": np.full(4, PRECISION, dtype=np.float32), "track_shell_distances": np.full(4, SHELL, dtype=np.float32)}
         for name, table in short.items():
-            check(launch(ctx, handles, max_tracks=9, max_samples=12, **{name: table}), [roots, refused, refused, refused, refused, refused, roots])
+            check_rows(launch(ctx, handles, max_tracks=9, max_samples=12, **{name: table}), [roots, refused, refused, refused, refused, refused, roots])
         # a stride that holds the small blob and not the large one; and the largest stride that does not hold the small one
         assert c_small.blob.size < c_large.blob.size
         stride = (c_small.blob.size + 15) & ~15
         assert stride < c_large.blob.size
         # (the shell of an instance refused for its size was computed: its metadata is written; only the rows are looked at)
-        check(launch(ctx, handles, max_tracks=9, max_samples=12, parents=parents, stride=stride, with_metadata=False),
+        check_rows(launch(ctx, handles, max_tracks=9, max_samples=12, parents=parents, stride=stride, with_metadata=False),
               [c_small.blob, refused, refused, refused, refused, refused, c_small.blob])
         assert c_small.blob.size % 16 != 0
-        check(launch(ctx, [h_small, h_large], max_tracks=9, max_samples=12, parents=parents, stride=c_small.blob.size & ~15, with_metadata=False), [refused, refused])
+        check_rows(launch(ctx, [h_small, h_large], max_tracks=9, max_samples=12, parents=parents, stride=c_small.blob.size & ~15, with_metadata=False), [refused, refused])
 
 
 def test_two_runs_give_the_same_bytes_and_a_capture_replays_to_them(sweep):
-    import torch
     ctx, handles, clips, expected = sweep
     parents, compressed = expected["two_roots"]
-    runs = [launch(ctx, handles + [0], flags=OPTIMIZE_LOOPS, parents=parents) for _ in range(2)]
-    assert np.array_equal(runs[0].flat, runs[1].flat) and np.array_equal(runs[0].results, runs[1].results) and np.array_equal(runs[0].metadata, runs[1].metadata)
-    # the same launch captured into a graph and replayed
-    device = torch.device("cuda:0")
-    n, stride = len(handles), runs[0].stride
-    d_parents = torch.from_numpy(parents.view(np.int32)).to(device)
-    d_handles = torch.from_numpy(np.asarray(handles, dtype=np.uint32).view(np.int32)).to(device)
-    flat = torch.full((n * stride,), SENTINEL, dtype=torch.uint8, device=device)
-    d_results = torch.zeros((n, 2), dtype=torch.int32, device=device)
-    d_workspace = torch.zeros((runtime.compress_tracks_workspace_bytes(n, MAX_TRACKS),), dtype=torch.uint8, device=device)
-    desc = runtime.CompressTracksDesc()
-    desc.rotation_format, desc.flags, desc.max_tracks, desc.precision, desc.shell_distance = runtime.ROTATION_QUATF_DROP_W_FULL, OPTIMIZE_LOOPS, MAX_TRACKS, PRECISION, SHELL
-    desc.parent_indices, desc.num_table_tracks, desc.workspace = d_parents.data_ptr(), MAX_TRACKS, d_workspace.data_ptr()
-    stream = torch.cuda.Stream(device)
-    with torch.cuda.stream(stream):
-        captured = torch.cuda.CUDAGraph()
-        with torch.cuda.graph(captured, stream=stream):
-            ctx.compress_tracks_batch(d_handles.data_ptr(), n, desc, flat.data_ptr(), stride, d_results.data_ptr(), stream=stream.cuda_stream)
-        flat.fill_(SENTINEL)         # what the capture itself may have left does not count
-        captured.replay()
-    stream.synchronize()
-    assert np.array_equal(flat.cpu().numpy(), runs[0].flat[GUARD: GUARD + n * stride])
-    assert np.array_equal(d_results.cpu().numpy().view(np.uint32), runs[0].results[:n])
+    runs = [launch(ctx, handles + [0], flags=OPTIMIZE_LOOPS, parents=parents, graph=graph) for graph in (False, False, True)]
+    assert same(runs[0], runs[1])
+    assert same(runs[0], runs[2])           # the same launch captured into a graph and replayed

@@ -3,9 +3,8 @@ ABI under ACLHIP_METRIC_QVVF_MATRIX3X4F: the expected tables, blobs, results and
 (tests/matrix_metric_compress_restatement.py, which tests/test_matrix_metric_compress_oracle.py holds to the reference's compressor under
 its matrix metric), and every comparison is on BYTES: both sides follow one definition, nothing has a tolerance.
 
-The launches and the comparisons are the base calls' own (tests/test_gpu_bit_rate_search.py, tests/test_gpu_variable_compress.py,
-tests/test_gpu_lossy_rotation_compress.py: a flat buffer of a sentinel byte between guards, one comparison for every byte), handed a
-context whose three base launches go through the _metric fronts. The shapes are T in 1, 3, 5, 17 and S in 2 (the shortest scan), 31
+The launches and the comparisons are the family's own (tests/compress_launches.py: a flat buffer of a sentinel byte between guards, one
+comparison for every byte), at the three entries of the _metric front. The shapes are T in 1, 3, 5, 17 and S in 2 (the shortest scan), 31
 (one segment), 33 (17 + 16) and 65 (four segments, three behind a vote); every (rotation, translation, scale) type triple; a chain of
 17 whose scales are not uniform at any level -- the one place where two 3x4 matrices go down the chain and shear builds up --; the
 clips of one track on which only the arithmetic decides the vote and the compaction. Metric 0 through the fronts is the base calls'
@@ -15,48 +14,19 @@ import pytest
 
 from acl_amd import runtime
 from oracle import bindings as ob
+import compress_launches as launches
 import matrix_metric_compress_restatement as metric_restatement
 import variable_compress_restatement as restatement
-import test_gpu_bit_rate_search as search_launches
-import test_gpu_lossy_rotation_compress as drop_w_launches
-import test_gpu_variable_compress as variable_launches
+from compress_launches import PRECISION, RATE, SENTINEL, SHELL, Entry, Registered, check_rows, check_table, ctx, same  # noqa: F401  (ctx: this module's fixture)
 from matrix_metric_compress_restatement import METRIC_MATRIX, METRIC_QVVF
-from test_gpu_lossy_rotation_compress import GUARD, SENTINEL, Registered
 from variable_compress_restatement import ANIMATED, CONSTANT, DEFAULT, IDENTITY, LANES, OPTIMIZE_LOOPS
 
 pytestmark = pytest.mark.gpu
 
-RATE = 32.0
-PRECISION, SHELL = 0.01, 3.0
 TRACK_COUNTS, SAMPLE_COUNTS = (1, 3, 5, 17), (2, 31, 33, 65)
 SHAPES = [(t, s) for t in TRACK_COUNTS for s in SAMPLE_COUNTS]
 MAX_TRACKS, MAX_SAMPLES, MAX_SEGMENTS = 17, 65, 4
 REFUSED, NOT_FINITE = runtime.COMPRESS_REFUSED, runtime.COMPRESS_NOT_FINITE
-
-
-class ThroughTheMetricFronts:
-    """a context whose three base launches are the _metric fronts at `metric`; everything else is the context's"""
-    def __init__(self, context, metric):
-        self.context, self.metric = context, metric
-
-    def __getattr__(self, name):
-        return getattr(self.context, name)
-
-    def compress_tracks_batch(self, *arguments, **keywords):
-        return self.context.compress_tracks_metric_batch(*arguments, metric=self.metric, **keywords)
-
-    def compress_tracks_variable_batch(self, *arguments, **keywords):
-        return self.context.compress_tracks_variable_metric_batch(*arguments, metric=self.metric, **keywords)
-
-    def find_bit_rates_batch(self, *arguments, **keywords):
-        return self.context.find_bit_rates_metric_batch(*arguments, metric=self.metric, **keywords)
-
-
-@pytest.fixture(scope="module")
-def ctx():
-    context = runtime.Context(0)
-    yield context
-    context.close()
 
 
 def find(samples, metric=METRIC_MATRIX, **settings):
@@ -65,9 +35,19 @@ def find(samples, metric=METRIC_MATRIX, **settings):
     return metric_restatement.find_bit_rates(samples, RATE, metric, **settings)
 
 
-def search(ctx, handles, metric=METRIC_MATRIX, **settings):
+def through(kind, metric=METRIC_MATRIX):
+    """the _metric front of `kind` at `metric`"""
+    return Entry(kind, "metric", metric)
+
+
+def launch(ctx, entry, handles, **settings):
     settings.setdefault("max_tracks", MAX_TRACKS)
-    return search_launches.launch(ThroughTheMetricFronts(ctx, metric), handles, **settings)
+    settings.setdefault("max_samples", MAX_SAMPLES)
+    return launches.launch(ctx, entry, handles, **settings)
+
+
+def search(ctx, handles, metric=METRIC_MATRIX, **settings):
+    return launch(ctx, through("search", metric), handles, **settings)
 
 
 def scaled_chain(seed, num_samples, num_tracks):
@@ -100,12 +80,12 @@ def test_the_table_is_the_matrix_restatements(sweep):
     ctx, handles, clips, parents, found, *_ = sweep
     matrix = found[METRIC_MATRIX]
     order = [(7 * i + 2) % len(handles) for i in range(len(handles) + 3)]
-    search_launches.check(search(ctx, [handles[k] for k in order], flags=OPTIMIZE_LOOPS, parents=parents), [matrix[k] for k in order])
+    check_table(search(ctx, [handles[k] for k in order], flags=OPTIMIZE_LOOPS, parents=parents), [matrix[k] for k in order])
     picked = [k for k, shape in enumerate(SHAPES) if shape in ((3, 33), (17, 33), (17, 65), (1, 2), (5, 65))]
     segment_stride = 4 * MAX_TRACKS + 12
     with_refused = [handles[picked[0]], 0, handles[picked[1]], handles[picked[2]], 0xFFFFFF, handles[picked[3]], handles[picked[4]]]
     expected = [matrix[picked[0]], REFUSED, matrix[picked[1]], matrix[picked[2]], REFUSED, matrix[picked[3]], matrix[picked[4]]]
-    search_launches.check(search(ctx, with_refused, flags=OPTIMIZE_LOOPS, parents=parents, segment_stride=segment_stride, instance_stride=MAX_SEGMENTS * segment_stride + 8), expected)
+    check_table(search(ctx, with_refused, flags=OPTIMIZE_LOOPS, parents=parents, segment_stride=segment_stride, instance_stride=MAX_SEGMENTS * segment_stride + 8), expected)
     by_shape = dict(zip(SHAPES, matrix))
     assert [len(by_shape[17, s].base.segments) for s in SAMPLE_COUNTS] == [1, 1, 2, 4]
     assert any(f.base.wrap and f.base.num_samples == clip.shape[0] - 1 for f, clip in zip(matrix, clips))               # a vote that removed a sample
@@ -123,9 +103,9 @@ def test_a_chain_of_17_with_scales_that_are_not_uniform(sweep):
     assert not np.array_equal(deep[METRIC_MATRIX].table, deep[METRIC_MATRIX].local_table)
     assert not np.array_equal(deep[METRIC_MATRIX].table, deep[METRIC_QVVF].table)
     by_matrix = search(ctx, [h_chain, h_chain], max_samples=33, parents=chain_parents)
-    search_launches.check(by_matrix, [deep[METRIC_MATRIX]] * 2)
+    check_table(by_matrix, [deep[METRIC_MATRIX]] * 2)
     by_qvvf = search(ctx, [h_chain, h_chain], METRIC_QVVF, max_samples=33, parents=chain_parents)
-    search_launches.check(by_qvvf, [deep[METRIC_QVVF]] * 2)
+    check_table(by_qvvf, [deep[METRIC_QVVF]] * 2)
     assert not np.array_equal(by_matrix.flat, by_qvvf.flat)
 
 
@@ -145,41 +125,20 @@ def test_all_roots_a_clip_without_scale_and_per_track_settings(ctx):
         h_roots, h_plain = arrays.add(roots), arrays.add(plain)
         found = find(roots)
         assert np.array_equal(found.table, found.local_table)
-        search_launches.check(search(ctx, [h_roots], max_samples=33), [found])
+        check_table(search(ctx, [h_roots], max_samples=33), [found])
         without_scale = find(plain, parents=chain_parents)
         assert not (without_scale.base.types[2] != DEFAULT).any() and np.array_equal(without_scale.table, find(plain, METRIC_QVVF, parents=chain_parents).table)
-        search_launches.check(search(ctx, [h_plain, h_plain], max_samples=33, parents=chain_parents), [without_scale] * 2)
+        check_table(search(ctx, [h_plain, h_plain], max_samples=33, parents=chain_parents), [without_scale] * 2)
         handles = [arrays.add(samples) for samples in posed]
-        search_launches.check(search(ctx, handles, **settings), [find(samples, **settings) for samples in posed])
+        check_table(search(ctx, handles, **settings), [find(samples, **settings) for samples in posed])
 
 
 def test_two_runs_give_the_same_bytes_and_a_capture_replays_to_them(sweep):
-    import torch
     ctx, handles, clips, parents, found, *_ = sweep
     picked = [k for k, shape in enumerate(SHAPES) if shape[0] in (5, 17)]
-    runs = [search(ctx, [handles[k] for k in picked], flags=OPTIMIZE_LOOPS, parents=parents) for _ in range(2)]
-    assert np.array_equal(runs[0].flat, runs[1].flat) and np.array_equal(runs[0].results, runs[1].results) and np.array_equal(runs[0].metadata, runs[1].metadata)
-    device = torch.device("cuda:0")
-    n, instance_stride = len(picked), runs[0].instance_stride
-    d_parents = torch.from_numpy(parents.view(np.int32)).to(device)
-    d_handles = torch.from_numpy(np.asarray([handles[k] for k in picked], dtype=np.uint32).view(np.int32)).to(device)
-    flat = torch.full((n * instance_stride,), SENTINEL, dtype=torch.uint8, device=device)
-    d_results = torch.zeros((n, 2), dtype=torch.int32, device=device)
-    d_workspace = torch.zeros((runtime.find_bit_rates_workspace_bytes(n, MAX_TRACKS, MAX_SAMPLES),), dtype=torch.uint8, device=device)
-    desc = runtime.FindBitRatesDesc()
-    desc.flags, desc.max_tracks, desc.max_samples, desc.precision, desc.shell_distance, desc.level = OPTIMIZE_LOOPS, MAX_TRACKS, MAX_SAMPLES, PRECISION, SHELL, 2
-    desc.parent_indices, desc.num_table_tracks, desc.workspace = d_parents.data_ptr(), MAX_TRACKS, d_workspace.data_ptr()
-    stream = torch.cuda.Stream(device)
-    with torch.cuda.stream(stream):
-        captured = torch.cuda.CUDAGraph()
-        with torch.cuda.graph(captured, stream=stream):
-            ctx.find_bit_rates_metric_batch(d_handles.data_ptr(), n, desc, flat.data_ptr(), instance_stride, runs[0].segment_stride, d_results.data_ptr(), METRIC_MATRIX,
-                                            stream=stream.cuda_stream)
-        flat.fill_(SENTINEL)         # what the capture itself may have left does not count
-        captured.replay()
-    stream.synchronize()
-    assert np.array_equal(flat.cpu().numpy(), runs[0].flat[GUARD: GUARD + n * instance_stride])
-    assert np.array_equal(d_results.cpu().numpy().view(np.uint32), runs[0].results[:n])
+    runs = [search(ctx, [handles[k] for k in picked], flags=OPTIMIZE_LOOPS, parents=parents, graph=graph) for graph in (False, False, True)]
+    assert same(runs[0], runs[1])
+    assert same(runs[0], runs[2])           # the same launch captured into a graph and replayed
 
 
 def arithmetic_cases():
@@ -193,7 +152,6 @@ def test_the_two_writers_are_the_matrix_restatements(sweep):
     and the clips of one track on which only the arithmetic decides -- there the qvvf restatement gives other bytes, so these alone show
     that the vote and the compaction switched arithmetic"""
     ctx, handles, clips, parents, found, h_chain, chain, chain_parents, deep = sweep
-    matrix_ctx = ThroughTheMetricFronts(ctx, METRIC_MATRIX)
     picked = [k for k, shape in enumerate(SHAPES) if shape in ((3, 33), (17, 33), (17, 65), (5, 2), (17, 31), (5, 65))]
     tables = np.zeros((len(picked), MAX_SEGMENTS, MAX_TRACKS, 4), dtype=np.uint8)
     expected = []
@@ -202,25 +160,24 @@ def test_the_two_writers_are_the_matrix_restatements(sweep):
         tables[row, :table.shape[0], :table.shape[1]] = table
         expected.append(metric_restatement.compress_variable(clips[k], RATE, table, METRIC_MATRIX, parents=parents, flags=OPTIMIZE_LOOPS, precision=PRECISION, shell_distance=SHELL))
     assert any(c.wrap for c in expected)
-    drop_w_launches.check(variable_launches.launch(matrix_ctx, [handles[k] for k in picked], tables, max_tracks=MAX_TRACKS, flags=OPTIMIZE_LOOPS, parents=parents), expected)
+    check_rows(launch(ctx, through("variable"), [handles[k] for k in picked], rates=tables, flags=OPTIMIZE_LOOPS, parents=parents), expected)
     expected = [metric_restatement.compress_drop_w(clips[k], RATE, METRIC_MATRIX, parents=parents, flags=OPTIMIZE_LOOPS, precision=PRECISION, shell_distance=SHELL) for k in picked]
-    drop_w_launches.check(drop_w_launches.launch(matrix_ctx, [handles[k] for k in picked], max_tracks=MAX_TRACKS, max_samples=MAX_SAMPLES, flags=OPTIMIZE_LOOPS, parents=parents), expected)
+    check_rows(launch(ctx, through("tracks"), [handles[k] for k in picked], flags=OPTIMIZE_LOOPS, parents=parents), expected)
     # the chain under its own table
     want = metric_restatement.compress_variable(chain, RATE, deep[METRIC_MATRIX].table, METRIC_MATRIX, parents=chain_parents, precision=PRECISION, shell_distance=SHELL)
-    drop_w_launches.check(variable_launches.launch(matrix_ctx, [h_chain], deep[METRIC_MATRIX].table, max_tracks=17, max_samples=33, parents=chain_parents), [want])
+    check_rows(launch(ctx, through("variable"), [h_chain], rates=deep[METRIC_MATRIX].table, max_tracks=17, max_samples=33, parents=chain_parents), [want])
 
     with Registered(ctx) as arrays:
         for what, (samples, precision, flags) in arithmetic_cases().items():
             handle = arrays.add(samples)
             settings = dict(flags=flags, precision=precision, shell_distance=SHELL)
             for metric in (METRIC_MATRIX, METRIC_QVVF):
-                through = ThroughTheMetricFronts(ctx, metric)
                 by_variable = metric_restatement.compress_variable(samples, RATE, (12, 12, 12), metric, **settings)
                 by_drop_w = metric_restatement.compress_drop_w(samples, RATE, metric, **settings)
-                drop_w_launches.check(variable_launches.launch(through, [handle], (12, 12, 12), max_tracks=1, max_samples=9, flags=flags, precision=float(precision)), [by_variable])
-                drop_w_launches.check(drop_w_launches.launch(through, [handle], max_tracks=1, max_samples=9, flags=flags, precision=float(precision)), [by_drop_w])
+                check_rows(launch(ctx, through("variable", metric), [handle], rates=(12, 12, 12), max_tracks=1, max_samples=9, flags=flags, precision=float(precision)), [by_variable])
+                check_rows(launch(ctx, through("tracks", metric), [handle], max_tracks=1, max_samples=9, flags=flags, precision=float(precision)), [by_drop_w])
                 f = find(samples, metric, flags=flags, precision=precision)
-                search_launches.check(search_launches.launch(through, [handle], max_tracks=1, max_samples=9, flags=flags, precision=float(precision)), [f])
+                check_table(search(ctx, [handle], metric, max_tracks=1, max_samples=9, flags=flags, precision=float(precision)), [f])
                 if what == "constant":
                     assert (by_drop_w.types[0, 0] == ANIMATED) == (metric == METRIC_MATRIX) and (by_variable.types[0, 0] == ANIMATED) == (metric == METRIC_MATRIX)
                 else:
@@ -231,17 +188,15 @@ def test_metric_0_through_the_fronts_is_the_base_calls_bytes(sweep):
     """table and blobs: the entry points without a metric and the fronts at ACLHIP_METRIC_QVVF, byte for byte, sentinels included; and the
     raw format takes either metric and gives the raw format's bytes"""
     ctx, handles, clips, parents, found, h_chain, chain, chain_parents, deep = sweep
-    through = ThroughTheMetricFronts(ctx, METRIC_QVVF)
     picked = [handles[k] for k, shape in enumerate(SHAPES) if shape[0] in (5, 17)] + [h_chain]
     settings = dict(flags=OPTIMIZE_LOOPS, parents=parents)
-    for launch, arguments in ((search_launches.launch, ()), (variable_launches.launch, ((9, 14, 7),)), (drop_w_launches.launch, ())):
-        extra = {"max_samples": MAX_SAMPLES} if launch is drop_w_launches.launch else {}
-        base, front = (launch(context, picked, *arguments, max_tracks=MAX_TRACKS, **extra, **settings) for context in (ctx, through))
+    for kind, arguments in (("search", {}), ("variable", {"rates": (9, 14, 7)}), ("tracks", {})):
+        base, front = (launch(ctx, entry, picked, **arguments, **settings) for entry in (Entry(kind), through(kind, METRIC_QVVF)))
         assert np.array_equal(base.flat, front.flat) and np.array_equal(base.results, front.results) and np.array_equal(base.metadata, front.metadata)
         assert (base.results[:, 0] == runtime.COMPRESS_OK).all() and base.rejected == front.rejected == 0
     raw_format = {"rotation_format": runtime.ROTATION_QUATF_FULL, "max_tracks": MAX_TRACKS, "max_samples": MAX_SAMPLES, "with_metadata": False}
     normalized = [k for k, shape in enumerate(SHAPES) if shape in ((5, 33), (17, 2))]
-    rows = [drop_w_launches.launch(context, [handles[k] for k in normalized], **raw_format) for context in (ctx, through, ThroughTheMetricFronts(ctx, METRIC_MATRIX))]
+    rows = [launch(ctx, entry, [handles[k] for k in normalized], **raw_format) for entry in (Entry("tracks"), through("tracks", METRIC_QVVF), through("tracks"))]
     assert np.array_equal(rows[0].flat, rows[1].flat) and np.array_equal(rows[0].flat, rows[2].flat)
     assert np.array_equal(rows[0].results, rows[1].results) and np.array_equal(rows[0].results, rows[2].results) and (rows[0].results[:, 1] > 0).any()
 
@@ -312,7 +267,7 @@ def test_an_unknown_metric_and_a_refused_instance_write_nothing_they_should_not(
     d_workspace = torch.full((runtime.find_bit_rates_workspace_bytes(n, MAX_TRACKS, MAX_SAMPLES),), SENTINEL, dtype=torch.uint8, device=device)
     stream = torch.cuda.current_stream(device)
     for metric in (2, 255, 0xFFFFFFFF):
-        for desc, launch, extra in ((runtime.FindBitRatesDesc(), ctx.find_bit_rates_metric_batch, (MAX_SEGMENTS * MAX_TRACKS * 4, MAX_TRACKS * 4)),
+        for desc, method, extra in ((runtime.FindBitRatesDesc(), ctx.find_bit_rates_metric_batch, (MAX_SEGMENTS * MAX_TRACKS * 4, MAX_TRACKS * 4)),
                                     (runtime.CompressVariableDesc(), ctx.compress_tracks_variable_metric_batch, (stride,)),
                                     (runtime.CompressTracksDesc(), ctx.compress_tracks_metric_batch, (stride,))):
             desc.max_tracks, desc.precision, desc.shell_distance, desc.workspace = MAX_TRACKS, PRECISION, SHELL, d_workspace.data_ptr()
@@ -325,7 +280,7 @@ def test_an_unknown_metric_and_a_refused_instance_write_nothing_they_should_not(
                 desc.rotation_bit_rate = desc.translation_bit_rate = desc.scale_bit_rate = 12
             rejected_before = ctx.rejected_instance_count()
             with pytest.raises(runtime.AclHipError, match="unknown error metric %d" % metric):
-                launch(d_handles.data_ptr(), n, desc, flat.data_ptr(), *extra, d_results.data_ptr(), metric, stream=stream.cuda_stream)
+                method(d_handles.data_ptr(), n, desc, flat.data_ptr(), *extra, d_results.data_ptr(), metric, stream=stream.cuda_stream)
             stream.synchronize()
             assert ctx.rejected_instance_count() == rejected_before
             assert (flat.cpu().numpy() == SENTINEL).all() and (d_workspace.cpu().numpy() == SENTINEL).all() and (d_results.cpu().numpy() == 0x5A5A5A5A).all()
@@ -337,12 +292,11 @@ def test_an_unknown_metric_and_a_refused_instance_write_nothing_they_should_not(
         bad[7, 2, 5] = np.nan
         h_bad = arrays.add(bad)
         f_small, f_long = find(small, parents=tree), find(long, parents=tree)
-        search_launches.check(search(ctx, [h_small, 0, h_long, h_bad, h_small], max_tracks=5, max_samples=40, parents=tree), [f_small, REFUSED, f_long, NOT_FINITE, f_small])
-        search_launches.check(search(ctx, [h_small, h_long, h_small], max_tracks=5, max_samples=39, parents=tree), [f_small, REFUSED, f_small])
+        check_table(search(ctx, [h_small, 0, h_long, h_bad, h_small], max_tracks=5, max_samples=40, parents=tree), [f_small, REFUSED, f_long, NOT_FINITE, f_small])
+        check_table(search(ctx, [h_small, h_long, h_small], max_tracks=5, max_samples=39, parents=tree), [f_small, REFUSED, f_small])
         c_small, c_long = (metric_restatement.compress_variable(samples, RATE, (12, 12, 12), METRIC_MATRIX, parents=tree, precision=PRECISION, shell_distance=SHELL) for samples in (small, long))
-        through = ThroughTheMetricFronts(ctx, METRIC_MATRIX)
-        out = variable_launches.launch(through, [h_small, 0, h_long, h_bad, h_small], (12, 12, 12), max_tracks=5, max_samples=40, parents=tree, with_metadata=False)
-        drop_w_launches.check(out, [c_small.blob, REFUSED, c_long.blob, NOT_FINITE, c_small.blob])
+        out = launch(ctx, through("variable"), [h_small, 0, h_long, h_bad, h_small], rates=(12, 12, 12), max_tracks=5, max_samples=40, parents=tree, with_metadata=False)
+        check_rows(out, [c_small.blob, REFUSED, c_long.blob, NOT_FINITE, c_small.blob])
         with pytest.raises(ValueError, match="ACLHIP_COMPRESS_REFUSED"):
             runtime.find_bit_rates(ctx, [h_small, h_long], parents=np.array([0xFFFFFFFF, 0, 3, 0, 0], dtype=np.uint32), precision=PRECISION, shell_distance=SHELL,
                                    metric=runtime.ERROR_METRIC_QVVF_MATRIX3X4F)

@@ -10,116 +10,25 @@ import numpy as np
 import pytest
 
 from acl_amd import runtime
+import compress_launches as launches
 import transform_compress_restatement as restatement
+from compress_launches import RATE, Entry, Registered, check_rows, ctx, same  # noqa: F401  (ctx: this module's fixture)
 from transform_compress_restatement import IDENTITY, LANES, SAMPLE_COUNTS, TRACK_COUNTS
 
 pytestmark = pytest.mark.gpu
 
-RATE = 32.0
-SENTINEL = 0xA5
-GUARD = 256
 PARENTS, DESCRIPTIONS = restatement.INCLUDE_PARENT_TRACK_INDICES, restatement.INCLUDE_TRACK_DESCRIPTIONS
 SHAPES = [(t, s) for t in TRACK_COUNTS for s in SAMPLE_COUNTS] + [(2, 64), (2, 129), (130, 3)]      # samples around a wave's 64 lanes; three turns of 64 tracks
 
 
-class Launched:
-    pass
-
-
-@pytest.fixture(scope="module")
-def ctx():
-    context = runtime.Context(0)
-    yield context
-    context.close()
-
-
-def launch(ctx, handles, shapes, flags=0, default_pose=None, parents=None, track_precisions=None, track_shell_distances=None, precision=1.0e-4, shell_distance=1.0,
-           stride=None, max_tracks=None, graph=False):
-    """One launch over `handles`. `shapes`: (T, S) per instance, or one for all, for the default stride (the largest bound) and max_tracks."""
-    import torch
-    device = torch.device("cuda:0")
-    n = len(handles)
+def launch(ctx, handles, shapes, flags=0, precision=1.0e-4, shell_distance=1.0, stride=None, max_tracks=None, **settings):
+    """One launch of the raw call over `handles` (tests/compress_launches.py). `shapes`: (T, S) per instance, or one for all, for the
+    default stride (the largest bound) and max_tracks."""
     if stride is None:
         stride = max(runtime.transform_compress_bound(tracks, samples, flags) for tracks, samples in shapes)
     if max_tracks is None:
         max_tracks = max(tracks for tracks, _ in shapes)
-    flat = torch.full((GUARD + n * stride + GUARD,), SENTINEL, dtype=torch.uint8, device=device)
-    assert flat.data_ptr() % 16 == 0
-    host_handles = np.asarray(handles, dtype=np.uint32)
-    d_handles = torch.from_numpy(host_handles.view(np.int32)).to(device)
-    d_results = torch.full((n, 2), 0x5A5A5A5A, dtype=torch.int32, device=device)
-    workspace_bytes = runtime.transform_compress_workspace_bytes(n, max_tracks)
-    d_workspace = torch.full((workspace_bytes + GUARD,), SENTINEL, dtype=torch.uint8, device=device)
-    desc = runtime.TransformCompressDesc()
-    desc.flags, desc.max_tracks, desc.precision, desc.shell_distance = flags, max_tracks, precision, shell_distance
-    desc.workspace = d_workspace.data_ptr()
-    tables = []
-    for field, table, dtype in (("default_pose", default_pose, np.float32), ("parent_indices", parents, np.uint32), ("track_precisions", track_precisions, np.float32),
-                                ("track_shell_distances", track_shell_distances, np.float32)):
-        if table is not None:
-            host = np.ascontiguousarray(table, dtype=dtype)
-            d_table = torch.from_numpy(host.view(np.int32)).to(device)
-            tables.append((host, d_table))
-            setattr(desc, field, d_table.data_ptr())
-            desc.num_table_tracks = host.shape[0]
-    rejected_before = ctx.rejected_instance_count()
-    if graph:
-        stream = torch.cuda.Stream(device)
-        with torch.cuda.stream(stream):
-            captured = torch.cuda.CUDAGraph()
-            with torch.cuda.graph(captured, stream=stream):
-                ctx.compress_raw_tracks_batch(d_handles.data_ptr(), n, desc, flat.data_ptr() + GUARD, stride, d_results.data_ptr(), stream=stream.cuda_stream)
-            flat.fill_(SENTINEL)         # what the capture itself may have left does not count
-            d_results.fill_(0x5A5A5A5A)
-            captured.replay()
-        stream.synchronize()
-    else:
-        stream = torch.cuda.current_stream(device)
-        ctx.compress_raw_tracks_batch(d_handles.data_ptr(), n, desc, flat.data_ptr() + GUARD, stride, d_results.data_ptr(), stream=stream.cuda_stream)
-        stream.synchronize()
-    out = Launched()
-    out.flat, out.stride, out.n = flat.cpu().numpy(), stride, n
-    out.results = d_results.cpu().numpy().view(np.uint32).reshape(n, 2)
-    out.rejected = ctx.rejected_instance_count() - rejected_before
-    assert np.array_equal(d_handles.cpu().numpy().view(np.uint32), host_handles)                # the inputs are only read
-    assert np.all(d_workspace.cpu().numpy()[workspace_bytes:] == SENTINEL)                      # the workspace is as large as it says
-    for host, d_table in tables:
-        assert np.array_equal(d_table.cpu().numpy().view(np.uint32), host.view(np.uint32))
-    return out
-
-
-def check(out, expected):
-    """expected: per instance a blob (uint8), or the status of an instance that writes nothing"""
-    want = np.full(out.flat.shape, SENTINEL, dtype=np.uint8)
-    want_results = np.zeros((out.n, 2), dtype=np.uint32)
-    for i, blob in enumerate(expected):
-        if isinstance(blob, int):
-            want_results[i] = (blob, 0)
-        else:
-            want[GUARD + i * out.stride: GUARD + i * out.stride + blob.size] = blob
-            want_results[i] = (runtime.COMPRESS_OK, blob.size)
-    assert np.array_equal(out.results, want_results), (out.results[:8], want_results[:8])
-    different = np.flatnonzero(out.flat != want)
-    assert different.size == 0, [(int(at - GUARD) // out.stride, int(at - GUARD) % out.stride, int(out.flat[at]), int(want[at])) for at in different[:8]]
-    assert out.rejected == sum(1 for blob in expected if isinstance(blob, int) and blob == runtime.COMPRESS_REFUSED)
-
-
-class Registered:
-    """arrays registered with one context, unregistered together"""
-    def __init__(self, ctx):
-        self.ctx, self.handles = ctx, []
-
-    def add(self, samples, looping=runtime.LOOP_CLAMP):
-        handle = self.ctx.register_raw_tracks(samples, RATE, looping)
-        self.handles.append(handle)
-        return handle
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *args):
-        for handle in self.handles:
-            self.ctx.unregister_raw_tracks(handle)
+    return launches.launch(ctx, Entry("raw"), handles, max_tracks, stride=stride, flags=flags, precision=precision, shell_distance=shell_distance, **settings)
 
 
 def shapes_of(clips):
@@ -137,9 +46,9 @@ def sweep(ctx):
 def test_the_blobs_are_the_restatement(sweep):
     ctx, handles, clips = sweep
     expected = [restatement.compress(samples, RATE) for samples in clips]
-    check(launch(ctx, handles, shapes_of(clips)), expected)
+    check_rows(launch(ctx, handles, shapes_of(clips)), expected)
     # ACLHIP_COMPRESS_OPTIMIZE_LOOPS is accepted and changes nothing
-    check(launch(ctx, handles, shapes_of(clips), flags=runtime.COMPRESS_OPTIMIZE_LOOPS), expected)
+    check_rows(launch(ctx, handles, shapes_of(clips), flags=runtime.COMPRESS_OPTIMIZE_LOOPS), expected)
     kinds = np.array([restatement.parse(blob)["num_animated"] + restatement.parse(blob)["num_constant"] for blob in expected])
     assert (kinds.max(axis=0) > 0).all() and (kinds.min(axis=0) == 0).all()
 
@@ -154,16 +63,16 @@ def test_a_default_pose_that_is_not_the_identity_and_no_scale_section(ctx):
             clips.append(restatement.clip(k % 3, num_samples, num_tracks, default_pose=pose[:num_tracks], scales="default" if k % 2 else "mixed"))
         handles = [arrays.add(samples) for samples in clips]
         expected = [restatement.compress(samples, RATE, default_pose=pose) for samples in clips]
-        check(launch(ctx, handles, shapes_of(clips), default_pose=pose), expected)
+        check_rows(launch(ctx, handles, shapes_of(clips), default_pose=pose), expected)
         assert any(not restatement.parse(blob)["has_scale"] for blob in expected) and any(restatement.parse(blob)["has_scale"] for blob in expected)
         # the same arrays against the identity: what was default is constant now
         against_identity = [restatement.compress(samples, RATE) for samples in clips]
-        check(launch(ctx, handles, shapes_of(clips)), against_identity)
+        check_rows(launch(ctx, handles, shapes_of(clips)), against_identity)
         assert sum(blob.size for blob in against_identity) > sum(blob.size for blob in expected)
         no_scale = [restatement.clip(k % 3, num_samples, num_tracks, scales="default") for k, (num_tracks, num_samples) in enumerate(SHAPES[::3])]
         expected = [restatement.compress(samples, RATE) for samples in no_scale]
         assert not any(restatement.parse(blob)["has_scale"] for blob in expected)
-        check(launch(ctx, [arrays.add(samples) for samples in no_scale], shapes_of(no_scale)), expected)
+        check_rows(launch(ctx, [arrays.add(samples) for samples in no_scale], shapes_of(no_scale)), expected)
 
 
 def test_zeros_of_both_signs_and_fourth_lanes_that_are_not_finite(ctx):
@@ -183,8 +92,8 @@ def test_zeros_of_both_signs_and_fourth_lanes_that_are_not_finite(ctx):
         blob = restatement.compress(samples, RATE)
         types, _ = restatement.classify(samples, np.tile(IDENTITY, (5, 1)))
         assert types[1, 1] == restatement.DEFAULT and types[1, 3] == restatement.CONSTANT and samples[0, 3, 4:7].tobytes() in blob.tobytes()
-        check(launch(ctx, handles, [(5, 7)]), [blob, blob])
-        check(launch(ctx, handles, [(5, 7)], default_pose=pose), [blob, blob])
+        check_rows(launch(ctx, handles, [(5, 7)]), [blob, blob])
+        check_rows(launch(ctx, handles, [(5, 7)], default_pose=pose), [blob, blob])
 
 
 def test_the_metadata(ctx):
@@ -199,14 +108,14 @@ def test_the_metadata(ctx):
         shells = np.linspace(1.0, 5.0, 130).astype(np.float32)
         for flags in (PARENTS, DESCRIPTIONS, PARENTS | DESCRIPTIONS):
             expected = [restatement.compress(samples, RATE, flags=flags, precision=0.01, shell_distance=3.0) for samples in clips]
-            check(launch(ctx, handles, shapes_of(clips), flags=flags, precision=0.01, shell_distance=3.0), expected)
+            check_rows(launch(ctx, handles, shapes_of(clips), flags=flags, precision=0.01, shell_distance=3.0), expected)
             expected = [restatement.compress(samples, RATE, flags=flags, default_pose=pose, parents=parents, track_precisions=precisions, track_shell_distances=shells) for samples in clips]
-            check(launch(ctx, handles, shapes_of(clips), flags=flags, default_pose=pose, parents=parents, track_precisions=precisions, track_shell_distances=shells), expected)
+            check_rows(launch(ctx, handles, shapes_of(clips), flags=flags, default_pose=pose, parents=parents, track_precisions=precisions, track_shell_distances=shells), expected)
             expected = [restatement.compress(samples, RATE, flags=flags, parents=parents, shell_distance=2.0) for samples in clips]
-            check(launch(ctx, handles, shapes_of(clips), flags=flags, parents=parents, shell_distance=2.0), expected)
+            check_rows(launch(ctx, handles, shapes_of(clips), flags=flags, parents=parents, shell_distance=2.0), expected)
             assert all(restatement.parse(blob)["has_metadata"] for blob in expected)
         # the tables without a flag: no metadata, the blobs of the plain launch
-        check(launch(ctx, handles, shapes_of(clips), parents=parents, track_precisions=precisions), [restatement.compress(samples, RATE) for samples in clips])
+        check_rows(launch(ctx, handles, shapes_of(clips), parents=parents, track_precisions=precisions), [restatement.compress(samples, RATE) for samples in clips])
 
 
 def decode(ctx, blob, times, rounding, looping=runtime.LOOP_AS_COMPRESSED, normalization=runtime.NORMALIZE_NEVER):
@@ -260,8 +169,8 @@ def test_a_wrapping_array_keeps_its_samples_and_is_marked(ctx):
         handles = [arrays.add(samples, runtime.LOOP_WRAP), arrays.add(samples, runtime.LOOP_CLAMP)]
         wrapped, clamped = restatement.compress(samples, RATE, looping_wrap=True), restatement.compress(samples, RATE)
         assert restatement.parse(wrapped)["wrap"] and restatement.parse(wrapped)["num_samples"] == 7 and not restatement.parse(clamped)["wrap"]
-        check(launch(ctx, handles, [(5, 7)]), [wrapped, clamped])
-        check(launch(ctx, handles, [(5, 7)], flags=runtime.COMPRESS_OPTIMIZE_LOOPS), [wrapped, clamped])
+        check_rows(launch(ctx, handles, [(5, 7)]), [wrapped, clamped])
+        check_rows(launch(ctx, handles, [(5, 7)], flags=runtime.COMPRESS_OPTIMIZE_LOOPS), [wrapped, clamped])
         blob = runtime.compress_raw_tracks(ctx, handles[0])[0]
         assert np.array_equal(blob, wrapped)
         types = restatement.classify(samples, np.tile(IDENTITY, (5, 1)))[0]
@@ -316,13 +225,13 @@ def test_mixed_shapes_and_repeated_handles_in_one_launch(sweep):
     ctx, handles, clips = sweep
     order = [(7 * i + 3) % len(handles) for i in range(2 * len(handles) + 5)]
     cache = {k: restatement.compress(clips[k], RATE, flags=PARENTS) for k in set(order)}
-    check(launch(ctx, [handles[k] for k in order], shapes_of(clips), flags=PARENTS), [cache[k] for k in order])
+    check_rows(launch(ctx, [handles[k] for k in order], shapes_of(clips), flags=PARENTS), [cache[k] for k in order])
 
 
 def test_one_instance(ctx):
     samples = restatement.clip(0, 65, 17)
     with Registered(ctx) as arrays:
-        check(launch(ctx, [arrays.add(samples)], [(17, 65)]), [restatement.compress(samples, RATE)])
+        check_rows(launch(ctx, [arrays.add(samples)], [(17, 65)]), [restatement.compress(samples, RATE)])
 
 
 def test_statuses_and_refusals_leave_their_rows(ctx):
@@ -354,7 +263,7 @@ def test_statuses_and_refusals_leave_their_rows(ctx):
         assert restatement.rotations_normalized(samples[3, 2, 0:4])
         h_inside, blob_inside = arrays.add(samples), restatement.compress(samples, RATE)
         handles = [h_small] + [handle for handle, _ in bad] + [h_inside, h_large]
-        check(launch(ctx, handles, [(9, 12)]), [blob_small] + [status for _, status in bad] + [blob_inside, blob_large])
+        check_rows(launch(ctx, handles, [(9, 12)]), [blob_small] + [status for _, status in bad] + [blob_inside, blob_large])
         with pytest.raises(RuntimeError, match="Some samples are not finite"):
             runtime.compress_raw_tracks(ctx, [h_small, bad[0][0]])
         with pytest.raises(ValueError, match="ACLHIP_COMPRESS_NOT_NORMALIZED"):
@@ -363,32 +272,34 @@ def test_statuses_and_refusals_leave_their_rows(ctx):
         retired = ctx.register_raw_tracks(small, RATE)         # (behind every other registration: its slot is not handed out again here)
         ctx.unregister_raw_tracks(retired)
         handles = [h_small, 0, 4000, retired, 0xFFFFFFFF, h_large, h_small]
-        check(launch(ctx, handles, [(9, 12)]), [blob_small, refused, refused, refused, refused, blob_large, blob_small])
+        check_rows(launch(ctx, handles, [(9, 12)]), [blob_small, refused, refused, refused, refused, blob_large, blob_small])
         # max_tracks 4: the array of 9 tracks is refused
-        check(launch(ctx, handles, [(9, 12)], max_tracks=4), [blob_small, refused, refused, refused, refused, refused, blob_small])
+        check_rows(launch(ctx, handles, [(9, 12)], max_tracks=4), [blob_small, refused, refused, refused, refused, refused, blob_small])
         # tables of 4 entries, each kind alone
         short = {"default_pose": np.tile(IDENTITY, (4, 1)), "parents": np.full(4, restatement.NO_PARENT, dtype=np.uint32),
                  "track_precisions": np.full(4, 0.01, dtype=np.float32), "track_shell_distances": np.ones(4, dtype=np.float32)}
         for name, table in short.items():
-            check(launch(ctx, handles, [(9, 12)], **{name: table}), [blob_small, refused, refused, refused, refused, refused, blob_small])
+            check_rows(launch(ctx, handles, [(9, 12)], **{name: table}), [blob_small, refused, refused, refused, refused, refused, blob_small])
         # a stride that holds the small blob and not the large one; and the largest stride that does not hold the small one
         assert blob_small.size < blob_large.size
         stride = (blob_small.size + 15) & ~15
         assert stride < blob_large.size
-        check(launch(ctx, handles, [(9, 12)], stride=stride), [blob_small, refused, refused, refused, refused, refused, blob_small])
+        check_rows(launch(ctx, handles, [(9, 12)], stride=stride), [blob_small, refused, refused, refused, refused, refused, blob_small])
         assert blob_small.size % 16 != 0
-        check(launch(ctx, [h_small, h_large], [(9, 12)], stride=blob_small.size & ~15), [refused, refused])
+        check_rows(launch(ctx, [h_small, h_large], [(9, 12)], stride=blob_small.size & ~15), [refused, refused])
         # with metadata: the stride that just holds the blob, and 16 bytes less
         with_parents = restatement.compress(small, RATE, flags=PARENTS | DESCRIPTIONS)
         stride = (with_parents.size + 15) & ~15
-        check(launch(ctx, [h_small, h_small], [(4, 12)], flags=PARENTS | DESCRIPTIONS, stride=stride), [with_parents, with_parents])
-        check(launch(ctx, [h_small, h_small], [(4, 12)], flags=PARENTS | DESCRIPTIONS, stride=stride - 16), [refused, refused])
+        check_rows(launch(ctx, [h_small, h_small], [(4, 12)], flags=PARENTS | DESCRIPTIONS, stride=stride), [with_parents, with_parents])
+        check_rows(launch(ctx, [h_small, h_small], [(4, 12)], flags=PARENTS | DESCRIPTIONS, stride=stride - 16), [refused, refused])
 
 
 def test_a_captured_launch_replays_to_the_same_bytes(sweep):
     ctx, handles, clips = sweep
     expected = [restatement.compress(samples, RATE, flags=DESCRIPTIONS) for samples in clips]
-    check(launch(ctx, handles, shapes_of(clips), flags=DESCRIPTIONS, graph=True), expected)
+    plain, replayed = (launch(ctx, handles, shapes_of(clips), flags=DESCRIPTIONS, graph=graph) for graph in (False, True))
+    check_rows(replayed, expected)
+    assert same(plain, replayed)
 
 
 def test_two_runs_give_the_same_bytes(sweep):

@@ -3,7 +3,7 @@ vector3f_variable at GIVEN bit rates of registered raw track arrays. The expecte
 (tests/variable_compress_restatement.py, which tests/test_variable_compress_oracle.py holds to the reference's compressor), and every
 comparison is on BYTES and BITS: both sides follow one definition, nothing has a tolerance.
 
-The output region is the one of tests/test_gpu_lossy_rotation_compress.py: a flat buffer of a sentinel byte, a guard, n rows, a guard;
+The output region is the one of tests/compress_launches.py: a flat buffer of a sentinel byte, a guard, n rows, a guard;
 one comparison holds [0, size) of every row to the blob and everything else to the sentinel. The shapes are T in 1, 3, 4, 5, 17, 65 (a
 partial and a full group of four, a types word, a wave) and S in 1, 2, 31, 32, 33, 49, 65 (one segment; two; two dealt out 17 + 16;
 three; and 32 closing on its first sample, voted down to one segment of 31). The sample rate is a power of two, so that the key times
@@ -13,14 +13,13 @@ import pytest
 
 from acl_amd import runtime
 from oracle import bindings as ob
+import compress_launches as launches
 import variable_compress_restatement as restatement
+from compress_launches import PRECISION, RATE, SHELL, Entry, Registered, check_rows, ctx, same  # noqa: F401  (ctx: this module's fixture)
 from variable_compress_restatement import ANIMATED, LANES, OPTIMIZE_LOOPS, XYZ
-from test_gpu_lossy_rotation_compress import GUARD, SENTINEL, Launched, Registered, check
 
 pytestmark = pytest.mark.gpu
 
-RATE = 32.0
-PRECISION, SHELL = 0.01, 3.0
 TRACK_COUNTS, SAMPLE_COUNTS = (1, 3, 4, 5, 17, 65), (1, 2, 31, 32, 33, 49, 65)
 SHAPES = [(t, s) for t in TRACK_COUNTS for s in SAMPLE_COUNTS]
 MAX_TRACKS, MAX_SAMPLES = 65, 65
@@ -28,64 +27,9 @@ MAX_SEGMENTS = 4
 PARENTS, DESCRIPTIONS = restatement.INCLUDE_PARENT_TRACK_INDICES, restatement.INCLUDE_TRACK_DESCRIPTIONS
 
 
-@pytest.fixture(scope="module")
-def ctx():
-    context = runtime.Context(0)
-    yield context
-    context.close()
-
-
-def launch(ctx, handles, rates, max_tracks=MAX_TRACKS, max_samples=MAX_SAMPLES, flags=0, parents=None, default_pose=None, stride=None, with_metadata=True,
-           instance_stride=None, segment_stride=None, precision=PRECISION):
-    """One launch over `handles`. rates: three uniform rates, or a uint8 array whose last axes are [tracks, 4]: the strides default to its
-    own shape ([tracks, 4]: 0 and 0; [segments, tracks, 4]: shared by the instances; [instances, segments, tracks, 4])"""
-    import torch
-    device = torch.device("cuda:0")
-    n = len(handles)
-    if stride is None:
-        stride = runtime.variable_compress_bound(max_tracks, max_samples, flags)
-    flat = torch.full((GUARD + n * stride + GUARD,), SENTINEL, dtype=torch.uint8, device=device)
-    host_handles = np.asarray(handles, dtype=np.uint32)
-    d_handles = torch.from_numpy(host_handles.view(np.int32)).to(device)
-    d_results = torch.full((n, 2), 0x5A5A5A5A, dtype=torch.int32, device=device)
-    workspace_bytes = runtime.compress_variable_workspace_bytes(n, max_tracks, max_samples)
-    d_workspace = torch.full((workspace_bytes + GUARD,), SENTINEL, dtype=torch.uint8, device=device)
-    d_metadata = torch.full((GUARD + n * max_tracks * 8 + GUARD,), SENTINEL, dtype=torch.uint8, device=device)
-    desc = runtime.CompressVariableDesc()
-    if with_metadata:
-        desc.shell_metadata = d_metadata.data_ptr() + GUARD
-    desc.flags, desc.max_tracks, desc.max_samples, desc.precision, desc.shell_distance = flags, max_tracks, max_samples, precision, SHELL
-    desc.workspace = d_workspace.data_ptr()
-    tables = []
-    for field, table, dtype in (("default_pose", default_pose, np.float32), ("parent_indices", parents, np.uint32)):
-        if table is not None:
-            host = np.ascontiguousarray(table, dtype=dtype)
-            d_table = torch.from_numpy(host.view(np.int32)).to(device)
-            tables.append((host, d_table))
-            setattr(desc, field, d_table.data_ptr())
-            desc.num_table_tracks = host.shape[0]
-    rates = np.ascontiguousarray(rates, dtype=np.uint8)
-    if rates.ndim == 1:
-        desc.rotation_bit_rate, desc.translation_bit_rate, desc.scale_bit_rate = (int(rate) for rate in rates)
-    else:
-        d_rates = torch.from_numpy(rates).to(device)
-        tables.append((rates, d_rates))
-        desc.bit_rates = d_rates.data_ptr()
-        desc.bit_rate_segment_stride = (rates.shape[-2] * 4 if rates.ndim >= 3 else 0) if segment_stride is None else segment_stride
-        desc.bit_rate_instance_stride = (rates.shape[-3] * rates.shape[-2] * 4 if rates.ndim == 4 else 0) if instance_stride is None else instance_stride
-    rejected_before = ctx.rejected_instance_count()
-    stream = torch.cuda.current_stream(device)
-    ctx.compress_tracks_variable_batch(d_handles.data_ptr(), n, desc, flat.data_ptr() + GUARD, stride, d_results.data_ptr(), stream=stream.cuda_stream)
-    stream.synchronize()
-    out = Launched()
-    out.flat, out.stride, out.n, out.max_tracks = flat.cpu().numpy(), stride, n, max_tracks
-    out.results = d_results.cpu().numpy().view(np.uint32).reshape(n, 2)
-    out.metadata = d_metadata.cpu().numpy()
-    out.rejected = ctx.rejected_instance_count() - rejected_before
-    assert np.all(d_workspace.cpu().numpy()[workspace_bytes:] == SENTINEL)                      # the workspace is as large as it says
-    for host, d_table in tables:
-        assert np.array_equal(d_table.cpu().numpy().view(np.uint8).reshape(-1), host.view(np.uint8).reshape(-1))      # the inputs are only read
-    return out
+def launch(ctx, handles, rates, entry=Entry("variable"), max_tracks=MAX_TRACKS, max_samples=MAX_SAMPLES, **settings):
+    """One launch over `handles` (tests/compress_launches.py). rates: three uniform rates, or a uint8 array whose last axes are [tracks, 4]"""
+    return launches.launch(ctx, entry, handles, max_tracks, max_samples, rates=rates, **settings)
 
 
 def compress(samples, rates, **settings):
@@ -126,7 +70,7 @@ def test_uniform_rates_are_the_restatement(sweep):
     shell metadata on bits"""
     ctx, handles, clips, parents, _, _, uniform = sweep
     order = [(5 * i + 2) % len(handles) for i in range(len(handles) + 5)]
-    check(launch(ctx, [handles[k] for k in order], (9, 14, 7), flags=OPTIMIZE_LOOPS, parents=parents), [uniform[k] for k in order])
+    check_rows(launch(ctx, [handles[k] for k in order], (9, 14, 7), flags=OPTIMIZE_LOOPS, parents=parents), [uniform[k] for k in order])
     by_shape = dict(zip(SHAPES, uniform))
     assert [len(by_shape[17, s].segments) for s in SAMPLE_COUNTS] == [1, 1, 1, 1, 2, 2, 4] and len(by_shape[65, 49].segments) == 3       # (17, 49) closes: 48 samples are two segments
     assert by_shape[17, 32].wrap and by_shape[17, 32].segments == [(0, 31)] and by_shape[17, 33].segments == [(0, 17), (17, 16)]
@@ -138,7 +82,7 @@ def test_uniform_rates_are_the_restatement(sweep):
 def test_a_table_per_instance_and_segment_is_the_restatement(sweep):
     """every rate 0 .. 24 in one launch, 0 in some segments only; instance and segment strides from the table's shape"""
     ctx, handles, clips, parents, rates, by_table, _ = sweep
-    check(launch(ctx, handles, rates, flags=OPTIMIZE_LOOPS, parents=parents), by_table)
+    check_rows(launch(ctx, handles, rates, flags=OPTIMIZE_LOOPS, parents=parents), by_table)
     used = set()
     for c in by_table:
         for kind in range(3):
@@ -155,16 +99,16 @@ def test_shared_rows_and_metadata(sweep):
     row = rates[3, 0]
     picked = list(range(0, len(handles), 3))
     want = [compress(clips[k], row, parents=parents, flags=flags, default_pose=pose) for k in picked]
-    check(launch(ctx, [handles[k] for k in picked], row, flags=flags, parents=parents, default_pose=pose), want)
-    check(launch(ctx, [handles[k] for k in picked], row, flags=flags, parents=parents, default_pose=pose, with_metadata=False), [c.blob for c in want])
+    check_rows(launch(ctx, [handles[k] for k in picked], row, flags=flags, parents=parents, default_pose=pose), want)
+    check_rows(launch(ctx, [handles[k] for k in picked], row, flags=flags, parents=parents, default_pose=pose, with_metadata=False), [c.blob for c in want])
     table = rates[3]
     want = [compress(clips[k], table, parents=parents, flags=PARENTS) for k in picked]
-    check(launch(ctx, [handles[k] for k in picked], table, flags=PARENTS, parents=parents), want)
+    check_rows(launch(ctx, [handles[k] for k in picked], table, flags=PARENTS, parents=parents), want)
     # the same table through explicit strides with room between the rows
     wide = np.zeros((len(picked), MAX_SEGMENTS + 1, MAX_TRACKS + 3, 4), dtype=np.uint8)
     wide[:, :MAX_SEGMENTS, :MAX_TRACKS] = rates[picked]
     want = [compress(clips[k], rates[k], parents=parents) for k in picked]
-    check(launch(ctx, [handles[k] for k in picked], wide, parents=parents), want)
+    check_rows(launch(ctx, [handles[k] for k in picked], wide, parents=parents), want)
 
 
 def test_the_blobs_check_register_and_decode(sweep):
@@ -205,7 +149,7 @@ def test_a_zero_minimum_or_maximum_has_the_sign_of_the_last_zero_sample(ctx):
         handles = [arrays.add(samples) for samples in clips]
         want = [compress(samples, (11, 12, 13), parents=parents) for samples in clips]
         assert all(c.types[1, 0] == ANIMATED and c.clip_ranges[1, 0][0].view(np.uint32)[0] == 0x80000000 for c in want)
-        check(launch(ctx, handles, (11, 12, 13), max_tracks=5, parents=parents), want)
+        check_rows(launch(ctx, handles, (11, 12, 13), max_tracks=5, parents=parents), want)
 
 
 def test_segment_ranges_on_the_edges_of_the_fix_up(ctx):
@@ -216,7 +160,7 @@ def test_segment_ranges_on_the_edges_of_the_fix_up(ctx):
     with Registered(ctx) as arrays:
         handles = [arrays.add(samples) for samples in clips]
         for rates in ((8, 3, 8), (12, 11, 12), (16, 23, 16)):
-            check(launch(ctx, handles, rates, parents=parents), [compress(samples, rates, parents=parents) for samples in clips])
+            check_rows(launch(ctx, handles, rates, parents=parents), [compress(samples, rates, parents=parents) for samples in clips])
 
 
 def test_translation_and_scale_see_the_rotation_as_it_was_compacted(ctx):
@@ -229,8 +173,8 @@ def test_translation_and_scale_see_the_rotation_as_it_was_compacted(ctx):
         assert want.types[:, 0].tolist() == [restatement.DEFAULT, restatement.DEFAULT, ANIMATED]
         unit = restatement.compress(samples, RATE, (9, 9, 9), precision=84.0, shell_distance=SHELL)
         assert unit.types[:, 0].tolist() == [restatement.DEFAULT, restatement.DEFAULT, restatement.DEFAULT]
-        check(launch(ctx, [handle, handle], (9, 9, 9), max_tracks=1, max_samples=12, default_pose=pose, precision=84.0), [want, want])
-        check(launch(ctx, [handle], (9, 9, 9), max_tracks=1, max_samples=12, precision=84.0), [unit])
+        check_rows(launch(ctx, [handle, handle], (9, 9, 9), max_tracks=1, max_samples=12, default_pose=pose, precision=84.0), [want, want])
+        check_rows(launch(ctx, [handle], (9, 9, 9), max_tracks=1, max_samples=12, precision=84.0), [unit])
 
 
 def test_refusals_leave_their_rows(ctx):
@@ -255,63 +199,41 @@ def test_refusals_leave_their_rows(ctx):
         rates[1, 0, moving[1][0], 1] = 25               # one translation of one segment of instance 1
         rates[2, :, moving[0][0], 0] = 0                # every segment of a rotation of instance 2
         settings = {"max_tracks": 5, "max_samples": 40, "parents": parents}
-        check(launch(ctx, [h_small, h_long, 0, h_bad, h_small], (8, 8, 8), **settings), [c_small, c_long, refused, runtime.COMPRESS_NOT_FINITE, c_small])
+        check_rows(launch(ctx, [h_small, h_long, 0, h_bad, h_small], (8, 8, 8), **settings), [c_small, c_long, refused, runtime.COMPRESS_NOT_FINITE, c_small])
         # (the shell of an instance the layout refuses was computed: its metadata is written; from here on only the rows are looked at)
         settings["with_metadata"] = False
         c_small, c_long = c_small.blob, c_long.blob
-        check(launch(ctx, [h_small, h_long, h_long], rates, **settings), [c_small, refused, compress(long, rates[2], parents=parents).blob])
-        check(launch(ctx, [h_long, h_small, h_small], rates, **settings), [c_long, refused, refused])
-        check(launch(ctx, [h_small, h_small], (0, 8, 8), **settings), [refused, refused])
+        check_rows(launch(ctx, [h_small, h_long, h_long], rates, **settings), [c_small, refused, compress(long, rates[2], parents=parents).blob])
+        check_rows(launch(ctx, [h_long, h_small, h_small], rates, **settings), [c_long, refused, refused])
+        check_rows(launch(ctx, [h_small, h_small], (0, 8, 8), **settings), [refused, refused])
         # a rate that no animated sub-track reads is not looked at
         ignored = rates[0].copy()
         for kind in range(3):
             ignored[:, long_types[kind] != ANIMATED, kind] = 77
-        check(launch(ctx, [h_long], ignored, **settings), [c_long])
+        check_rows(launch(ctx, [h_long], ignored, **settings), [c_long])
         # max_samples 39: the array of 40 is refused, unless the vote takes one away
-        check(launch(ctx, [h_small, h_long, h_small], (8, 8, 8), max_tracks=5, max_samples=39, parents=parents, with_metadata=False), [c_small, refused, c_small])
+        check_rows(launch(ctx, [h_small, h_long, h_small], (8, 8, 8), max_tracks=5, max_samples=39, parents=parents, with_metadata=False), [c_small, refused, c_small])
         closed = long.copy()
         closed[-1] = closed[0]
         h_closed = arrays.add(closed)
         voted = compress(closed, (8, 8, 8), parents=parents, flags=OPTIMIZE_LOOPS)
         assert voted.num_samples == 39
-        check(launch(ctx, [h_closed, h_long], (8, 8, 8), max_tracks=5, max_samples=39, flags=OPTIMIZE_LOOPS, parents=parents, with_metadata=False), [voted.blob, refused])
+        check_rows(launch(ctx, [h_closed, h_long], (8, 8, 8), max_tracks=5, max_samples=39, flags=OPTIMIZE_LOOPS, parents=parents, with_metadata=False), [voted.blob, refused])
         # a stride that holds the small blob and not the long one; and the largest stride that does not hold the small one
         stride = (c_small.size + 15) & ~15
         assert stride < c_long.size and c_small.size % 16 != 0
-        check(launch(ctx, [h_small, h_long, h_small], rates[0], stride=stride, **settings), [c_small, refused, c_small])
-        check(launch(ctx, [h_small, h_long], rates[0], stride=c_small.size & ~15, **settings), [refused, refused])
-        check(launch(ctx, [h_small, h_long], rates[0], max_tracks=5, max_samples=40, parents=np.array([0xFFFFFFFF, 0, 3, 0, 0], dtype=np.uint32)), [refused, refused])
+        check_rows(launch(ctx, [h_small, h_long, h_small], rates[0], stride=stride, **settings), [c_small, refused, c_small])
+        check_rows(launch(ctx, [h_small, h_long], rates[0], stride=c_small.size & ~15, **settings), [refused, refused])
+        check_rows(launch(ctx, [h_small, h_long], rates[0], max_tracks=5, max_samples=40, parents=np.array([0xFFFFFFFF, 0, 3, 0, 0], dtype=np.uint32)), [refused, refused])
         with pytest.raises(ValueError, match="ACLHIP_COMPRESS_REFUSED"):
             runtime.compress_tracks_variable(ctx, h_small, bit_rates=(0, 8, 8), parents=parents, precision=PRECISION, shell_distance=SHELL)
 
 
 def test_two_runs_give_the_same_bytes_and_a_capture_replays_to_them(sweep):
-    import torch
     ctx, handles, clips, parents, rates, by_table, _ = sweep
-    runs = [launch(ctx, handles, rates, flags=OPTIMIZE_LOOPS, parents=parents) for _ in range(2)]
-    assert np.array_equal(runs[0].flat, runs[1].flat) and np.array_equal(runs[0].results, runs[1].results) and np.array_equal(runs[0].metadata, runs[1].metadata)
-    device = torch.device("cuda:0")
-    n, stride = len(handles), runs[0].stride
-    d_parents = torch.from_numpy(parents.view(np.int32)).to(device)
-    d_rates = torch.from_numpy(rates).to(device)
-    d_handles = torch.from_numpy(np.asarray(handles, dtype=np.uint32).view(np.int32)).to(device)
-    flat = torch.full((n * stride,), SENTINEL, dtype=torch.uint8, device=device)
-    d_results = torch.zeros((n, 2), dtype=torch.int32, device=device)
-    d_workspace = torch.zeros((runtime.compress_variable_workspace_bytes(n, MAX_TRACKS, MAX_SAMPLES),), dtype=torch.uint8, device=device)
-    desc = runtime.CompressVariableDesc()
-    desc.flags, desc.max_tracks, desc.max_samples, desc.precision, desc.shell_distance = OPTIMIZE_LOOPS, MAX_TRACKS, MAX_SAMPLES, PRECISION, SHELL
-    desc.parent_indices, desc.num_table_tracks, desc.workspace = d_parents.data_ptr(), MAX_TRACKS, d_workspace.data_ptr()
-    desc.bit_rates, desc.bit_rate_segment_stride, desc.bit_rate_instance_stride = d_rates.data_ptr(), MAX_TRACKS * 4, MAX_SEGMENTS * MAX_TRACKS * 4
-    stream = torch.cuda.Stream(device)
-    with torch.cuda.stream(stream):
-        captured = torch.cuda.CUDAGraph()
-        with torch.cuda.graph(captured, stream=stream):
-            ctx.compress_tracks_variable_batch(d_handles.data_ptr(), n, desc, flat.data_ptr(), stride, d_results.data_ptr(), stream=stream.cuda_stream)
-        flat.fill_(SENTINEL)         # what the capture itself may have left does not count
-        captured.replay()
-    stream.synchronize()
-    assert np.array_equal(flat.cpu().numpy(), runs[0].flat[GUARD: GUARD + n * stride])
-    assert np.array_equal(d_results.cpu().numpy().view(np.uint32), runs[0].results[:n])
+    runs = [launch(ctx, handles, rates, flags=OPTIMIZE_LOOPS, parents=parents, graph=graph) for graph in (False, False, True)]
+    assert same(runs[0], runs[1])
+    assert same(runs[0], runs[2])           # the same launch captured into a graph and replayed
 
 
 def test_compress_tracks_at_precision(ctx):

@@ -70,8 +70,6 @@ def main():
     with_base = additive_format != runtime.ADDITIVE_NONE
     if with_base and metric != runtime.ERROR_METRIC_QVVF:
         parser.error("an additive base goes with the qvvf error metric: the reference has no additive matrix metric")
-    with_levels = level > runtime.COMPRESSION_LEVELS["medium"] or with_base           # (the _additive search is the level search)
-    phases, knob_name = (LEVEL_PHASES, LEVEL_KNOB) if with_levels else (PHASES, KNOB)
     if not torch.cuda.is_available():
         raise SystemExit("tools/find_bit_rates.py needs a GPU: nothing is measured without one")
     rng = np.random.default_rng(9100 + TRACKS)
@@ -98,6 +96,12 @@ def main():
     s = stream.cuda_stream
     ctx = runtime.Context(0)
     handles = np.array([ctx.register_raw_tracks(a, RATE) for a in arrays], dtype=np.uint32)
+    base_handles = np.array([ctx.register_raw_tracks(a, RATE) for a in base_arrays], dtype=np.uint32)
+    # the entry points of the search and of the compress call, their workspace and whether the results carry levels: the runtime's own route
+    route = dict(metric=metric, additive_base=base_handles[order] if with_base else None, additive_format=additive_format)
+    search_call, workspace_bytes, with_levels, search_alive = runtime.transform_compress_route(ctx, "search", handles[order], level=level, **route)
+    compress_call, _, _, compress_alive = runtime.transform_compress_route(ctx, "variable", handles[order], **route)
+    phases, knob_name = (LEVEL_PHASES, LEVEL_KNOB) if with_levels else (PHASES, KNOB)
     stride = runtime.variable_compress_bound(TRACKS, SAMPLES, 0)
     with torch.cuda.stream(stream):
         d_raws = torch.from_numpy(handles[order].view(np.int32)).cuda()
@@ -105,16 +109,8 @@ def main():
         d_rates = torch.zeros((N, segments, TRACKS, 4), dtype=torch.uint8, device="cuda")
         d_blobs = torch.zeros((N, stride), dtype=torch.uint8, device="cuda")
         d_results = torch.zeros((N, 2), dtype=torch.int32, device="cuda")
-        workspace_bytes = runtime.find_bit_rates_level_workspace_bytes if with_levels else runtime.find_bit_rates_workspace_bytes
         d_workspace = torch.zeros(workspace_bytes(N, TRACKS, SAMPLES), dtype=torch.uint8, device="cuda")
-    additive_base = runtime.AdditiveBase()
-    additive_base.additive_format = additive_format
-    if with_base:
-        base_handles = np.array([ctx.register_raw_tracks(a, RATE) for a in base_arrays], dtype=np.uint32)
-        with torch.cuda.stream(stream):
-            d_bases = torch.from_numpy(base_handles[order].view(np.int32)).cuda()
-            d_pose = torch.from_numpy(default_pose).cuda() if default_pose is not None else None
-        additive_base.base_raws = d_bases.data_ptr()
+        d_pose = torch.from_numpy(default_pose).cuda() if default_pose is not None else None
     search = runtime.FindBitRatesDesc()
     search.precision, search.shell_distance, search.max_tracks, search.max_samples, search.workspace, search.level = PRECISION, SHELL, TRACKS, SAMPLES, d_workspace.data_ptr(), level
     search.parent_indices, search.num_table_tracks = d_parents.data_ptr(), TRACKS
@@ -125,29 +121,21 @@ def main():
     if default_pose is not None:
         search.default_pose = desc.default_pose = d_pose.data_ptr()
 
-    def launch_search_qvvf():
-        if with_levels:
-            return ctx.find_bit_rates_level_batch(d_raws.data_ptr(), N, search, d_rates.data_ptr(), 4 * TRACKS * segments, 4 * TRACKS, d_results.data_ptr(), stream=s)
-        ctx.find_bit_rates_batch(d_raws.data_ptr(), N, search, d_rates.data_ptr(), 4 * TRACKS * segments, 4 * TRACKS, d_results.data_ptr(), stream=s)
-
-    def launch_compress_qvvf():
-        ctx.compress_tracks_variable_batch(d_raws.data_ptr(), N, desc, d_blobs.data_ptr(), stride, d_results.data_ptr(), stream=s)
+    search_arguments = (d_raws.data_ptr(), N, search, d_rates.data_ptr(), 4 * TRACKS * segments, 4 * TRACKS, d_results.data_ptr())
+    compress_arguments = (d_raws.data_ptr(), N, desc, d_blobs.data_ptr(), stride, d_results.data_ptr())
 
     def launch_search():
-        if with_base:
-            return ctx.find_bit_rates_additive_batch(d_raws.data_ptr(), N, search, d_rates.data_ptr(), 4 * TRACKS * segments, 4 * TRACKS, d_results.data_ptr(), additive_base, stream=s)
-        if metric == runtime.ERROR_METRIC_QVVF:
-            return launch_search_qvvf()
-        if with_levels:
-            return ctx.find_bit_rates_level_batch(d_raws.data_ptr(), N, search, d_rates.data_ptr(), 4 * TRACKS * segments, 4 * TRACKS, d_results.data_ptr(), metric=metric, stream=s)
-        ctx.find_bit_rates_metric_batch(d_raws.data_ptr(), N, search, d_rates.data_ptr(), 4 * TRACKS * segments, 4 * TRACKS, d_results.data_ptr(), metric, stream=s)
+        search_call(*search_arguments, stream=s)
 
     def launch_compress():
-        if with_base:
-            return ctx.compress_tracks_variable_additive_batch(d_raws.data_ptr(), N, desc, d_blobs.data_ptr(), stride, d_results.data_ptr(), additive_base, stream=s)
-        if metric == runtime.ERROR_METRIC_QVVF:
-            return launch_compress_qvvf()
-        ctx.compress_tracks_variable_metric_batch(d_raws.data_ptr(), N, desc, d_blobs.data_ptr(), stride, d_results.data_ptr(), metric, stream=s)
+        compress_call(*compress_arguments, stream=s)
+
+    # timed beside under --metric 1 or a base, named here on purpose: the qvvf entry points without a base that take the same desc and workspace
+    def launch_search_qvvf():
+        (ctx.find_bit_rates_level_batch if with_levels else ctx.find_bit_rates_batch)(*search_arguments, stream=s)
+
+    def launch_compress_qvvf():
+        ctx.compress_tracks_variable_batch(*compress_arguments, stream=s)
 
     # ---- checked before it is timed
     os.environ.pop(knob_name, None)
