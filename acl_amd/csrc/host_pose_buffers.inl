@@ -92,22 +92,16 @@ namespace
 		return launch(stream, shape, (num_instances + instances_per_block - 1) / instances_per_block);
 	}
 
-	// What the kernels' arguments have in common by name: the skeleton table and the launch's skeletons (`desc`: the entry point's struct
-	// that names them), the instances, the images of the shape. The rows are the caller's; so is the block shape word (pose_inverse_launch
-	// has a field of its own for it).
-	template<class launch_type, class desc_type>
-	launch_type pose_rows_launch_of(aclhip_context* context, const desc_type& desc, uint32_t num_instances, const consumer_launch_shape& shape)
+	// The two ends every kernel's argument has (kernels_pose_buffers.inl): the skeleton table and the skeletons the entry point's struct
+	// names, and the instances with the images of the shape. The rows between them are the caller's.
+	pose_rows_head pose_rows_head_of(const aclhip_context* context, aclhip_skeleton skeleton, const aclhip_skeleton* instance_skeletons)
 	{
-		launch_type launch = {};
-		launch.skeletons = context->skeletons.d_records;
-		launch.num_skeletons = ACLHIP_MAX_SKELETONS;
-		launch.skeleton = desc.skeleton;
-		launch.instance_skeletons = desc.instance_skeletons;
-		launch.num_instances = num_instances;
-		launch.lds_quads_per_image = shape.lds_quads_per_image;
-		launch.lds_bytes_per_instance = uint32_t(shape.lds_bytes_per_instance);
-		launch.rejected_count = context->d_rejected;
-		return launch;
+		return { context->skeletons.d_records, ACLHIP_MAX_SKELETONS, skeleton, instance_skeletons };
+	}
+
+	pose_rows_shape pose_rows_shape_of(const aclhip_context* context, uint32_t num_instances, const consumer_launch_shape& shape)
+	{
+		return { num_instances, shape.lds_quads_per_image, uint32_t(shape.lds_bytes_per_instance), shape.log2_instances_per_block | (shape.lds_schedule_words << 8), context->d_rejected };
 	}
 
 	// ---- object space and additive apply (aclhip_transform_poses_batch; transform_poses_kernel) --------------------------------------------
@@ -375,7 +369,9 @@ extern "C" aclhip_status aclhip_transform_poses_batch(aclhip_context* context, c
 	return launch_pose_rows(context, num_instances, stream_handle, rows, object_space, false, false, [&](hipStream_t stream, const consumer_launch_shape& shape, uint32_t num_blocks) -> aclhip_status
 	{
 		const bool has_additive = consumers->additive_format != ACLHIP_ADDITIVE_NONE;
-		pose_buffer_launch launch = pose_rows_launch_of<pose_buffer_launch>(context, *consumers, num_instances, shape);
+		pose_buffer_launch launch = {};
+		launch.head = pose_rows_head_of(context, consumers->skeleton, consumers->instance_skeletons);
+		launch.shape = pose_rows_shape_of(context, num_instances, shape);
 		launch.local_poses = static_cast<const uint8_t*>(local_poses);
 		launch.local_pose_stride_bytes = local_pose_stride_bytes;
 		launch.additive_poses = has_additive ? static_cast<const uint8_t*>(consumers->additive_poses) : nullptr;
@@ -383,7 +379,6 @@ extern "C" aclhip_status aclhip_transform_poses_batch(aclhip_context* context, c
 		launch.poses = static_cast<uint8_t*>(poses);
 		launch.pose_stride_bytes = pose_stride_bytes;
 		launch.additive_format = consumers->additive_format;
-		launch.packed_block_shape = shape.log2_instances_per_block | (shape.lds_schedule_words << 8);
 
 		// five instantiations: object / none, object / buffer, local / buffer, and the two object forms with bounds
 		if (consumers->bounds != nullptr)
@@ -411,7 +406,9 @@ extern "C" aclhip_status aclhip_blend_poses_batch(aclhip_context* context, const
 	const bool object_space = blend->object_space != 0;
 	return launch_pose_rows(context, num_instances, stream_handle, rows, object_space, false, false, [&](hipStream_t stream, const consumer_launch_shape& shape, uint32_t num_blocks) -> aclhip_status
 	{
-		pose_blend_launch launch = pose_rows_launch_of<pose_blend_launch>(context, *blend, num_instances, shape);
+		pose_blend_launch launch = {};
+		launch.head = pose_rows_head_of(context, blend->skeleton, blend->instance_skeletons);
+		launch.shape = pose_rows_shape_of(context, num_instances, shape);
 		launch.masks = context->blend_masks.d_records;
 		launch.num_masks = context->blend_masks.d_records != nullptr ? ACLHIP_MAX_BLEND_MASKS : 0u;
 		launch.layered = blend->mode == ACLHIP_BLEND_LAYERED ? 1u : 0u;
@@ -424,7 +421,6 @@ extern "C" aclhip_status aclhip_blend_poses_batch(aclhip_context* context, const
 		}
 		launch.poses = static_cast<uint8_t*>(poses);
 		launch.pose_stride_bytes = pose_stride_bytes;
-		launch.packed_block_shape = shape.log2_instances_per_block | (shape.lds_schedule_words << 8);
 
 		switch (blend->num_buffers)
 		{
@@ -447,7 +443,9 @@ extern "C" aclhip_status aclhip_inverse_transform_poses_batch(aclhip_context* co
 	return launch_pose_rows(context, num_instances, stream_handle, rows, false, false, false, [&](hipStream_t stream, const consumer_launch_shape& shape, uint32_t num_blocks) -> aclhip_status
 	{
 		const bool has_base = inverse->additive_format != ACLHIP_ADDITIVE_NONE;
-		pose_inverse_launch launch = pose_rows_launch_of<pose_inverse_launch>(context, *inverse, num_instances, shape);
+		pose_inverse_launch launch = {};
+		launch.head = pose_rows_head_of(context, inverse->skeleton, inverse->instance_skeletons);
+		launch.shape = pose_rows_shape_of(context, num_instances, shape);
 		launch.source_poses = static_cast<const uint8_t*>(source_poses);
 		launch.source_pose_stride_bytes = source_pose_stride_bytes;
 		launch.base_poses = has_base ? static_cast<const uint8_t*>(inverse->base_poses) : nullptr;
@@ -455,7 +453,6 @@ extern "C" aclhip_status aclhip_inverse_transform_poses_batch(aclhip_context* co
 		launch.poses = static_cast<uint8_t*>(poses);
 		launch.pose_stride_bytes = pose_stride_bytes;
 		launch.additive_format = inverse->additive_format;
-		launch.log2_instances_per_block = shape.log2_instances_per_block;
 
 		// three instantiations: local / none, local / base, no-local / base
 		if (inverse->local_space == 0)
@@ -483,7 +480,9 @@ extern "C" aclhip_status aclhip_measure_pose_error_metric_batch(aclhip_context* 
 		if (num_instances != 0)
 		{
 			const bool has_base = desc->additive_format != ACLHIP_ADDITIVE_NONE;
-			pose_error_launch launch = pose_rows_launch_of<pose_error_launch>(context, *desc, num_instances, shape);
+			pose_error_launch launch = {};
+			launch.head = pose_rows_head_of(context, desc->skeleton, desc->instance_skeletons);
+			launch.shape = pose_rows_shape_of(context, num_instances, shape);
 			launch.raw_poses = static_cast<const uint8_t*>(raw_poses);
 			launch.raw_pose_stride_bytes = raw_pose_stride_bytes;
 			launch.lossy_poses = static_cast<const uint8_t*>(lossy_poses);
@@ -497,7 +496,6 @@ extern "C" aclhip_status aclhip_measure_pose_error_metric_batch(aclhip_context* 
 			launch.bone_error_stride_bytes = desc->bone_error_stride_bytes;
 			launch.errors = reinterpret_cast<pose_error_record*>(errors);
 			launch.additive_format = desc->additive_format;
-			launch.packed_block_shape = shape.log2_instances_per_block | (shape.lds_schedule_words << 8);
 
 			// four instantiations: object / local x base / none, and the matrix metric's two: object / local (it takes no base)
 			const auto kernel = metric == ACLHIP_METRIC_QVVF_MATRIX3X4F
@@ -536,12 +534,13 @@ extern "C" aclhip_status aclhip_pose_matrices_batch(aclhip_context* context, con
 	const bool object_space = desc->object_space != 0;
 	return launch_pose_rows(context, num_instances, stream_handle, rows, object_space, false, false, [&](hipStream_t stream, const consumer_launch_shape& shape, uint32_t num_blocks) -> aclhip_status
 	{
-		pose_matrices_launch launch = pose_rows_launch_of<pose_matrices_launch>(context, *desc, num_instances, shape);
+		pose_matrices_launch launch = {};
+		launch.head = pose_rows_head_of(context, desc->skeleton, desc->instance_skeletons);
+		launch.shape = pose_rows_shape_of(context, num_instances, shape);
 		launch.local_poses = static_cast<const uint8_t*>(local_poses);
 		launch.local_pose_stride_bytes = local_pose_stride_bytes;
 		launch.matrices = static_cast<uint8_t*>(matrices);
 		launch.matrix_stride_bytes = matrix_stride_bytes;
-		launch.packed_block_shape = shape.log2_instances_per_block | (shape.lds_schedule_words << 8);
 		return launch_consumer_kernel(context, object_space ? pose_matrices_kernel<true> : pose_matrices_kernel<false>, shape, num_blocks, 1, stream, launch);
 	});
 }

@@ -193,7 +193,9 @@ extern "C" aclhip_status aclhip_skinning_matrices_batch(aclhip_context* context,
 	const bool object_space = desc->object_space != 0;
 	return launch_pose_rows(context, num_instances, stream_handle, rows, object_space, true, false, [&](hipStream_t stream, const consumer_launch_shape& shape, uint32_t num_blocks) -> aclhip_status
 	{
-		skinning_matrices_launch launch = pose_rows_launch_of<skinning_matrices_launch>(context, *desc, num_instances, shape);
+		skinning_matrices_launch launch = {};
+		launch.head = pose_rows_head_of(context, desc->skeleton, desc->instance_skeletons);
+		launch.shape = pose_rows_shape_of(context, num_instances, shape);
 		launch.skins = context->skins.d_records;
 		launch.num_skins = ACLHIP_MAX_SKINS;
 		launch.skin = desc->skin;
@@ -202,7 +204,6 @@ extern "C" aclhip_status aclhip_skinning_matrices_batch(aclhip_context* context,
 		launch.pose_stride_bytes = pose_stride_bytes;
 		launch.palettes = static_cast<uint8_t*>(palettes);
 		launch.palette_stride_bytes = palette_stride_bytes;
-		launch.packed_block_shape = shape.log2_instances_per_block | (shape.lds_schedule_words << 8);
 
 		const bool transposed = desc->layout == ACLHIP_PALETTE_3X4F_TRANSPOSED_48;
 		const auto kernel = object_space

@@ -8,24 +8,94 @@
 // same walk without storing them, and measures per bone how far three points on the bone's shell moved.
 // pose_matrices_kernel (aclhip_pose_matrices_batch) writes 3x4 matrices, local or object space, with the matrix walk of the reference's
 // qvvf_matrix3x4f_transform_error_metric; measure_pose_error_kernel's kMatrices instantiations are the measure in that arithmetic.
+// skinning_matrices_kernel (aclhip_skinning_matrices_batch) is pose_matrices_kernel with a palette for its store: one body, two writers.
+// What the six kernels do alike stands first, once: the two ends of their arguments, the opening of an instance with the refusal every
+// launch shares (open_instance, count_refused), the fill of an image from a row (fill_image_from_row), the closing of a walk slot
+// without work (close_idle_walk_slot).
 
-	// the kernel's argument: the launch's three buffers, its skeletons and its shape
-	struct pose_buffer_launch
+	// ---- what the kernels over a caller's pose rows do alike ------------------------------------------------------------------------------
+	// The two ends of every kernel's argument (the host fills them: pose_rows_head_of, pose_rows_shape_of). Two records, not one: the
+	// skeletons stay the first 24 bytes of the argument and the shape stays behind the launch's own rows, so the rows between them keep
+	// their places among the argument words that arrive preloaded in SGPRs. Kernels and helpers take them BY VALUE: read through a
+	// reference, an argument word is loaded again behind every atomic (the blend's object space kernels paid two VGPRs for it).
+	struct pose_rows_head
 	{
 		const device_skeleton* skeletons;		// the context's skeleton table
 		uint32_t num_skeletons;					// its capacity
 		uint32_t skeleton;						// the launch's skeleton, when instance_skeletons is null
 		const uint32_t* instance_skeletons;		// [num_instances] or null
+	};
+	struct pose_rows_shape
+	{
+		uint32_t num_instances;
+		uint32_t lds_quads_per_image, lds_bytes_per_instance;		// as decompress_poses_consumer_kernel takes them
+		uint32_t packed_block_shape;			// log2 of the instances per workgroup (bits 0..7) | words of LDS reserved for the shared walk schedule (bits 8..31)
+		unsigned long long* rejected_count;
+		__device__ __forceinline__ uint32_t log2_instances_per_block() const { return packed_block_shape & 0xFFu; }
+		__device__ __forceinline__ uint32_t schedule_words() const { return packed_block_shape >> 8; }
+	};
+
+	// An instance of a launch, opened: its skeleton's record with every field on the scalar unit, and what every launch refuses of it.
+	// Record 0 is never handed out and a cleared record (reference_pose == null) is an unknown or retired skeleton; kNeedsHierarchy: the
+	// launch walks or reads parents, and the skeleton has no hierarchy; more bones than the launch's LDS image holds (the image is sized
+	// from a stride on the host, and a skeleton may be registered behind a captured launch's back). Wave uniform, and in front of any load
+	// of a row: a kernel ORs in its own clauses -- its strides, its masks, its skin, its tables -- and serves what is left, which then
+	// reads and writes inside its own rows.
+	struct opened_instance { device_skeleton skeleton; uint32_t num_bones; bool refused; };
+	template<bool kNeedsHierarchy>
+	__device__ __forceinline__ opened_instance open_instance(pose_rows_head head, pose_rows_shape shape, uint32_t instance)
+	{
+		const uint32_t skeleton_id = head.instance_skeletons != nullptr ? as_constant(head.instance_skeletons)[instance] : head.skeleton;
+		const device_skeleton skeleton = load_skeleton_fields(head.skeletons, skeleton_id < head.num_skeletons ? skeleton_id : 0);
+		const bool refused = skeleton_id >= head.num_skeletons || skeleton.reference_pose == nullptr || (kNeedsHierarchy && skeleton.hierarchy == nullptr)
+			|| skeleton.num_bones * 3u > shape.lds_quads_per_image;
+		return opened_instance{ skeleton, skeleton.num_bones, refused };
+	}
+
+	// a refused instance is counted once, by the wave that opened it (aclhip_get_rejected_instance_count)
+	__device__ __forceinline__ void count_refused(unsigned long long* rejected_count, uint32_t lane)
+	{
+		if (lane == 0)
+			atomicAdd(rejected_count, 1ull);
+	}
+
+	// A row straight into an LDS image by DMA, lanes <-> consecutive quads (the LDS side of a piece is wave uniform + lane * 16). Nothing
+	// waits here: the caller's next wave_lds_barrier does (vmcnt), in front of the first LDS read.
+	__device__ __forceinline__ void fill_image_from_row(f32x4* image, const uint8_t* row, uint32_t num_quads, uint32_t lane)
+	{
+		const f32x4* source = reinterpret_cast<const f32x4*>(row);
+		for (uint32_t base = 0; base < num_quads; base += k_wave_size)
+		{
+			if (base + lane < num_quads)
+				__builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(source + base + lane),
+					(__attribute__((address_space(3))) void*)(image + base), 16, 0, 0);
+		}
+	}
+
+	// A slot without work clears its entry of the walk (a slot with work has its steps and its schedule already: request_walk_schedule).
+	// Called by the one lane that speaks for the slot.
+	__device__ __forceinline__ void close_idle_walk_slot(consumer_walk_slots& walk, uint32_t slot, uint32_t num_bones)
+	{
+		if (num_bones == 0)
+		{
+			walk.levels[slot] = 0;
+			walk.schedules[slot] = nullptr;
+		}
+	}
+
+	// ---- object space and additive apply (aclhip_transform_poses_batch) -------------------------------------------------------------------
+	// the kernel's argument: the launch's three buffers between the two shared ends
+	struct pose_buffer_launch
+	{
+		pose_rows_head head;
 		const uint8_t* local_poses;				// row i at local_poses + i * local_pose_stride_bytes
 		uint64_t local_pose_stride_bytes;
 		const uint8_t* additive_poses;			// kBase == k_consumer_base_buffer: row i at additive_poses + i * additive_pose_stride_bytes
 		uint64_t additive_pose_stride_bytes;
 		uint8_t* poses;							// null: the boxes alone (bounds instantiations)
 		uint64_t pose_stride_bytes;
-		uint32_t num_instances;
 		uint32_t additive_format;
-		uint32_t lds_quads_per_image, lds_bytes_per_instance, packed_block_shape;		// as decompress_poses_consumer_kernel takes them
-		unsigned long long* rejected_count;
+		pose_rows_shape shape;
 	};
 
 	// One wave64 per instance, up to 8 instances per workgroup, images as consumer_wave_of lays them out.
@@ -45,52 +115,34 @@
 		static_assert(kBase == k_consumer_base_none || kBase == k_consumer_base_buffer, "the additive pose is a caller's buffer, never a clip");
 		static_assert(kObjectSpace || kBase == k_consumer_base_buffer, "local space without an additive buffer: nothing to do");
 		constexpr bool with_bounds = sizeof...(bounds_types) != 0;
-		// packed_block_shape: log2 of the instances per workgroup (bits 0..7) | words of LDS reserved for the shared walk schedule (bits 8..31)
-		const uint32_t log2_instances_per_block = launch.packed_block_shape & 0xFFu;
+		const pose_rows_shape shape = launch.shape;
+		const uint32_t log2_instances_per_block = shape.log2_instances_per_block();
 		__shared__ consumer_walk_slots walk;		// (what the host subtracts from the LDS it may ask for: host_consumers.inl)
 		ACLHIP_PHASE_STAMP(0);
 
-		consumer_wave wave = consumer_wave_of(log2_instances_per_block, launch.lds_bytes_per_instance, launch.lds_quads_per_image);
+		consumer_wave wave = consumer_wave_of(log2_instances_per_block, shape.lds_bytes_per_instance, shape.lds_quads_per_image);
 		const uint32_t lane = wave.lane, instance = wave.instance;
 
 		// (wave.num_tracks stays 0 for a wave without work: past the batch, refused instance)
-		if (instance < launch.num_instances)
+		if (instance < shape.num_instances)
 		{
-			// the skeleton's record on the scalar unit; record 0 is never handed out and a cleared record is an unknown or retired skeleton
-			const uint32_t skeleton_id = launch.instance_skeletons != nullptr ? as_constant(launch.instance_skeletons)[instance] : launch.skeleton;
-			const device_skeleton skeleton = load_skeleton_fields(launch.skeletons, skeleton_id < launch.num_skeletons ? skeleton_id : 0);
-			const uint32_t num_bones = skeleton.num_bones;
+			// open_instance's refusal, and more bones than a row of any buffer in use holds
+			const opened_instance opened = open_instance<kObjectSpace>(launch.head, shape, instance);
+			const uint32_t num_bones = opened.num_bones;
 			const uint64_t row_bytes = uint64_t(num_bones) * 48u;
-
-			// refused, wave uniform and in front of any load of a row: an unknown or retired skeleton, object space without a hierarchy, more
-			// bones than a row of any buffer in use or the launch's LDS image holds (the image is sized from a stride on the host, and a
-			// skeleton may be registered behind a captured launch's back). What is served reads and writes inside its own rows.
-			const bool refused = skeleton_id >= launch.num_skeletons || skeleton.reference_pose == nullptr || (kObjectSpace && skeleton.hierarchy == nullptr)
-				|| row_bytes > launch.local_pose_stride_bytes || (launch.poses != nullptr && row_bytes > launch.pose_stride_bytes)
-				|| (kBase == k_consumer_base_buffer && row_bytes > launch.additive_pose_stride_bytes) || num_bones * 3u > launch.lds_quads_per_image;
+			const bool refused = opened.refused || row_bytes > launch.local_pose_stride_bytes || (launch.poses != nullptr && row_bytes > launch.pose_stride_bytes)
+				|| (kBase == k_consumer_base_buffer && row_bytes > launch.additive_pose_stride_bytes);
 			if (refused)
-			{
-				if (lane == 0)
-					atomicAdd(launch.rejected_count, 1ull);
-			}
+				count_refused(shape.rejected_count, lane);
 			else if (num_bones != 0)
 			{
 				wave.num_tracks = num_bones;
 				// the walk schedule first: its words travel global -> LDS while the row does
 				if (kObjectSpace)
-					request_walk_schedule(skeleton.hierarchy, log2_instances_per_block, launch.packed_block_shape >> 8, wave.shared_schedule, wave.slot, lane, walk);
-				// the row straight into the image by DMA, lanes <-> consecutive quads (the LDS side of a piece is wave uniform + lane * 16);
-				// the tail's first barrier waits for it (vmcnt) in front of the first LDS read
-				const uint8_t* row = kBase == k_consumer_base_buffer ? launch.additive_poses + uint64_t(instance) * launch.additive_pose_stride_bytes
-					: launch.local_poses + uint64_t(instance) * launch.local_pose_stride_bytes;
-				const f32x4* source = reinterpret_cast<const f32x4*>(row);
-				const uint32_t num_quads = num_bones * 3u;
-				for (uint32_t base = 0; base < num_quads; base += k_wave_size)
-				{
-					if (base + lane < num_quads)
-						__builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(source + base + lane),
-							(__attribute__((address_space(3))) void*)(wave.image + base), 16, 0, 0);
-				}
+					request_walk_schedule(opened.skeleton.hierarchy, log2_instances_per_block, shape.schedule_words(), wave.shared_schedule, wave.slot, lane, walk);
+				// (the tail's first barrier waits for the row)
+				fill_image_from_row(wave.image, kBase == k_consumer_base_buffer ? launch.additive_poses + uint64_t(instance) * launch.additive_pose_stride_bytes
+					: launch.local_poses + uint64_t(instance) * launch.local_pose_stride_bytes, num_bones * 3u, lane);
 			}
 			else if constexpr (with_bounds)
 				wave.empty_pose = true;		// (a served instance whose pose has no transform)
@@ -100,7 +152,7 @@
 		wave.short_exact = 0;
 		const consumer_bounds_launch bounds = bounds_launch_of(bounds_launch...);
 		finish_consumer_poses<kObjectSpace, kBase, false, true, false, with_bounds>(
-			consumer_tail_args{ launch.poses, launch.pose_stride_bytes, launch.lds_bytes_per_instance, log2_instances_per_block, launch.rejected_count, launch.local_poses, launch.local_pose_stride_bytes,
+			consumer_tail_args{ launch.poses, launch.pose_stride_bytes, shape.lds_bytes_per_instance, log2_instances_per_block, shape.rejected_count, launch.local_poses, launch.local_pose_stride_bytes,
 				launch.additive_format, bounds.bounds, bounds.bone_flags },
 			wave, walk);
 	}
@@ -109,10 +161,7 @@
 	// the kernel's argument: the K input buffers, the weights and masks of the blend, the output, the tables and the launch's shape
 	struct pose_blend_launch
 	{
-		const device_skeleton* skeletons;		// the context's skeleton table
-		uint32_t num_skeletons;					// its capacity
-		uint32_t skeleton;						// the launch's skeleton, when instance_skeletons is null
-		const uint32_t* instance_skeletons;		// [num_instances] or null
+		pose_rows_head head;
 		const device_blend_mask* masks;			// the context's mask table (null: no mask was ever registered)
 		uint32_t num_masks;						// its capacity
 		uint32_t layered;						// ACLHIP_BLEND_LAYERED
@@ -122,13 +171,11 @@
 		uint64_t buffer_stride_bytes[ACLHIP_MAX_BLEND_CLIPS];
 		uint8_t* poses;							// null: the boxes alone (bounds instantiations)
 		uint64_t pose_stride_bytes;
-		uint32_t num_instances;
-		uint32_t lds_quads_per_image, lds_bytes_per_instance, packed_block_shape;		// as transform_poses_kernel takes them
-		unsigned long long* rejected_count;
+		pose_rows_shape shape;
 	};
 
-	// transform_poses_kernel's shape -- one wave64 per instance, images as consumer_wave_of lays them out, the skeleton's record on the scalar
-	// unit, the refusal in front of any load of a row -- with the image filled by the masked blend of K rows in the place of one row's DMA:
+	// transform_poses_kernel's shape -- one wave64 per instance, images as consumer_wave_of lays them out, open_instance in front of any load
+	// of a row -- with the image filled by the masked blend of K rows in the place of one row's DMA:
 	//   kNumBuffers    K, a template constant: the K loads of a quad are K independent global_load_dwordx4 in one basic block, requested
 	//                  together and waited for once (the launch is bound by its HBM reads), and the accumulation is a straight line over
 	//                  registers. The mode and "no masks" are wave uniform data instead: layer_weight's null mask pointer and a weight of
@@ -147,26 +194,22 @@
 	{
 		static_assert(kNumBuffers >= 2 && kNumBuffers <= ACLHIP_MAX_BLEND_CLIPS, "a blend of 2 .. ACLHIP_MAX_BLEND_CLIPS buffers");
 		constexpr bool with_bounds = sizeof...(bounds_types) != 0;
-		// packed_block_shape: log2 of the instances per workgroup (bits 0..7) | words of LDS reserved for the shared walk schedule (bits 8..31)
-		const uint32_t log2_instances_per_block = launch.packed_block_shape & 0xFFu;
+		const pose_rows_shape shape = launch.shape;
+		const uint32_t log2_instances_per_block = shape.log2_instances_per_block();
 		__shared__ consumer_walk_slots walk;		// (what the host subtracts from the LDS it may ask for: host_consumers.inl)
 		ACLHIP_PHASE_STAMP(0);
 
-		consumer_wave wave = consumer_wave_of(log2_instances_per_block, launch.lds_bytes_per_instance, launch.lds_quads_per_image);
+		consumer_wave wave = consumer_wave_of(log2_instances_per_block, shape.lds_bytes_per_instance, shape.lds_quads_per_image);
 		const uint32_t lane = wave.lane, instance = wave.instance;
 
 		// (wave.num_tracks stays 0 for a wave without work: past the batch, refused instance)
-		if (instance < launch.num_instances)
+		if (instance < shape.num_instances)
 		{
-			// the skeleton's record on the scalar unit; record 0 is never handed out and a cleared record is an unknown or retired skeleton
-			const uint32_t skeleton_id = launch.instance_skeletons != nullptr ? as_constant(launch.instance_skeletons)[instance] : launch.skeleton;
-			const device_skeleton skeleton = load_skeleton_fields(launch.skeletons, skeleton_id < launch.num_skeletons ? skeleton_id : 0);
-			const uint32_t num_bones = skeleton.num_bones;
+			// open_instance's refusal, over every stride in use ...
+			const opened_instance opened = open_instance<kObjectSpace>(launch.head, shape, instance);
+			const uint32_t num_bones = opened.num_bones;
 			const uint64_t row_bytes = uint64_t(num_bones) * 48u;
-
-			// refused, wave uniform and in front of any load of a row: what transform_poses_kernel refuses, over every stride in use ...
-			bool refused = skeleton_id >= launch.num_skeletons || skeleton.reference_pose == nullptr || (kObjectSpace && skeleton.hierarchy == nullptr)
-				|| (launch.poses != nullptr && row_bytes > launch.pose_stride_bytes) || num_bones * 3u > launch.lds_quads_per_image;
+			bool refused = opened.refused || (launch.poses != nullptr && row_bytes > launch.pose_stride_bytes);
 			// ... and every mask the instance names: the null handle, or a known mask of this skeleton's slot count. The instance's K
 			// weights and K mask images on the scalar unit, next to the check.
 			layer_weight layers[kNumBuffers];
@@ -189,16 +232,13 @@
 			}
 
 			if (refused)
-			{
-				if (lane == 0)
-					atomicAdd(launch.rejected_count, 1ull);
-			}
+				count_refused(shape.rejected_count, lane);
 			else if (num_bones != 0)
 			{
 				wave.num_tracks = num_bones;
 				// the walk schedule first: its words travel global -> LDS while the rows do
 				if (kObjectSpace)
-					request_walk_schedule(skeleton.hierarchy, log2_instances_per_block, launch.packed_block_shape >> 8, wave.shared_schedule, wave.slot, lane, walk);
+					request_walk_schedule(opened.skeleton.hierarchy, log2_instances_per_block, shape.schedule_words(), wave.shared_schedule, wave.slot, lane, walk);
 				const f32x4* sources[kNumBuffers];
 				#pragma unroll
 				for (uint32_t k = 0; k < kNumBuffers; ++k)
@@ -274,29 +314,24 @@
 		wave.short_exact = 0;
 		const consumer_bounds_launch bounds = bounds_launch_of(bounds_launch...);
 		finish_consumer_poses<kObjectSpace, k_consumer_base_none, false, true, false, with_bounds>(
-			consumer_tail_args{ launch.poses, launch.pose_stride_bytes, launch.lds_bytes_per_instance, log2_instances_per_block, launch.rejected_count, nullptr, 0,
+			consumer_tail_args{ launch.poses, launch.pose_stride_bytes, shape.lds_bytes_per_instance, log2_instances_per_block, shape.rejected_count, nullptr, 0,
 				ACLHIP_ADDITIVE_NONE, bounds.bounds, bounds.bone_flags },
 			wave, walk);
 	}
 
 	// ---- the way back: object -> local space and make-additive over caller pose buffers (aclhip_inverse_transform_poses_batch) ------------
-	// the kernel's argument: the launch's three buffers, its skeletons and its shape
+	// the kernel's argument: the launch's three buffers between the two shared ends (a shape of 0 schedule words: there is no walk)
 	struct pose_inverse_launch
 	{
-		const device_skeleton* skeletons;		// the context's skeleton table
-		uint32_t num_skeletons;					// its capacity
-		uint32_t skeleton;						// the launch's skeleton, when instance_skeletons is null
-		const uint32_t* instance_skeletons;		// [num_instances] or null
+		pose_rows_head head;
 		const uint8_t* source_poses;			// row i at source_poses + i * source_pose_stride_bytes
 		uint64_t source_pose_stride_bytes;
 		const uint8_t* base_poses;				// kBase: row i at base_poses + i * base_pose_stride_bytes
 		uint64_t base_pose_stride_bytes;
 		uint8_t* poses;
 		uint64_t pose_stride_bytes;
-		uint32_t num_instances;
 		uint32_t additive_format;
-		uint32_t lds_quads_per_image, lds_bytes_per_instance, log2_instances_per_block;		// consumer_launch_shape's, without a walk schedule
-		unsigned long long* rejected_count;
+		pose_rows_shape shape;
 	};
 
 	// lhs first, then rhs, with rtm::qvv_mul's matrix route where a scale of either side is negative; the products that take it are counted
@@ -329,8 +364,8 @@
 		return result;
 	}
 
-	// transform_poses_kernel's shape -- one wave64 per instance, images as consumer_wave_of lays them out, the skeleton's record on the scalar
-	// unit, the refusal in front of any load of a row, the row into the image by DMA -- and then no walk: a bone's local transform is
+	// transform_poses_kernel's shape -- one wave64 per instance, images as consumer_wave_of lays them out, open_instance in front of any load
+	// of a row, fill_image_from_row -- and then no walk: a bone's local transform is
 	// qvv_mul(object[bone], qvv_inverse(object[parent])), both operands INPUTS, so every lane has a bone of its own and no wave waits for
 	// another (no workgroup barrier anywhere, no walk schedule, a wave without work leaves at once).
 	//   kLocalSpace    object -> local space with the parent table of the skeleton's hierarchy image (kernels_bone_object.inl reads the same)
@@ -345,25 +380,22 @@
 	__global__ __launch_bounds__(k_consumer_max_instances * k_wave_size) void inverse_transform_poses_kernel(pose_inverse_launch launch)
 	{
 		static_assert(kLocalSpace || kBase, "object space without a base buffer: nothing to do");
-		const consumer_wave wave = consumer_wave_of(launch.log2_instances_per_block, launch.lds_bytes_per_instance, launch.lds_quads_per_image);
+		const pose_rows_shape shape = launch.shape;
+		const consumer_wave wave = consumer_wave_of(shape.log2_instances_per_block(), shape.lds_bytes_per_instance, shape.lds_quads_per_image);
 		const uint32_t lane = wave.lane, instance = wave.instance;
-		if (instance >= launch.num_instances)
+		if (instance >= shape.num_instances)
 			return;
 
-		// the skeleton's record on the scalar unit; record 0 is never handed out and a cleared record is an unknown or retired skeleton
-		const uint32_t skeleton_id = launch.instance_skeletons != nullptr ? as_constant(launch.instance_skeletons)[instance] : launch.skeleton;
-		const device_skeleton skeleton = load_skeleton_fields(launch.skeletons, skeleton_id < launch.num_skeletons ? skeleton_id : 0);
-		const uint32_t num_bones = skeleton.num_bones;
+		// open_instance's refusal, over the strides of this launch
+		const opened_instance opened = open_instance<kLocalSpace>(launch.head, shape, instance);
+		const device_skeleton& skeleton = opened.skeleton;
+		const uint32_t num_bones = opened.num_bones;
 		const uint64_t row_bytes = uint64_t(num_bones) * 48u;
-
-		// refused, wave uniform and in front of any load of a row: what transform_poses_kernel refuses, over the strides of this launch
-		const bool refused = skeleton_id >= launch.num_skeletons || skeleton.reference_pose == nullptr || (kLocalSpace && skeleton.hierarchy == nullptr)
-			|| row_bytes > launch.source_pose_stride_bytes || row_bytes > launch.pose_stride_bytes
-			|| (kBase && row_bytes > launch.base_pose_stride_bytes) || num_bones * 3u > launch.lds_quads_per_image;
+		const bool refused = opened.refused || row_bytes > launch.source_pose_stride_bytes || row_bytes > launch.pose_stride_bytes
+			|| (kBase && row_bytes > launch.base_pose_stride_bytes);
 		if (refused)
 		{
-			if (lane == 0)
-				atomicAdd(launch.rejected_count, 1ull);
+			count_refused(shape.rejected_count, lane);
 			return;
 		}
 		if (num_bones == 0)
@@ -381,21 +413,12 @@
 				parent_word = parents[bone];
 		}
 
-		// the row straight into the image by DMA, lanes <-> consecutive quads (the LDS side of a piece is wave uniform + lane * 16)
 		f32x4* const image = wave.image;
 		const uint32_t num_quads = num_bones * 3u;
-		{
-			const f32x4* source = reinterpret_cast<const f32x4*>(launch.source_poses + uint64_t(instance) * launch.source_pose_stride_bytes);
-			for (uint32_t base = 0; base < num_quads; base += k_wave_size)
-			{
-				if (base + lane < num_quads)
-					__builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(source + base + lane),
-						(__attribute__((address_space(3))) void*)(image + base), 16, 0, 0);
-			}
-		}
+		fill_image_from_row(image, launch.source_poses + uint64_t(instance) * launch.source_pose_stride_bytes, num_quads, lane);
 		wave_lds_barrier();		// the row is complete (vmcnt)
 
-		unsigned long long* const negative_scale_count = launch.rejected_count + 1;
+		unsigned long long* const negative_scale_count = shape.rejected_count + 1;
 		[[maybe_unused]] const f32x4* base_row = kBase ? reinterpret_cast<const f32x4*>(launch.base_poses + uint64_t(instance) * launch.base_pose_stride_bytes) : nullptr;
 		for (uint32_t pass = num_passes; pass-- != 0;)
 		{
@@ -562,20 +585,15 @@
 		__builtin_amdgcn_s_setprio(0);
 	}
 
-	// the kernel's argument: the launch's two buffers, its skeletons and its shape
+	// the kernel's argument: the launch's two buffers between the two shared ends
 	struct pose_matrices_launch
 	{
-		const device_skeleton* skeletons;		// the context's skeleton table
-		uint32_t num_skeletons;					// its capacity
-		uint32_t skeleton;						// the launch's skeleton, when instance_skeletons is null
-		const uint32_t* instance_skeletons;		// [num_instances] or null
+		pose_rows_head head;
 		const uint8_t* local_poses;				// row i at local_poses + i * local_pose_stride_bytes: QVV48
 		uint64_t local_pose_stride_bytes;
 		uint8_t* matrices;						// row i at matrices + i * matrix_stride_bytes: 64 bytes per bone
 		uint64_t matrix_stride_bytes;
-		uint32_t num_instances;
-		uint32_t lds_quads_per_image, lds_bytes_per_instance, packed_block_shape;		// as transform_poses_kernel takes them
-		unsigned long long* rejected_count;
+		pose_rows_shape shape;
 	};
 
 	// a finished image of matrices into its output row, lanes <-> consecutive OUTPUT quads (a wave writes contiguous pieces of 1 KiB): the
@@ -594,57 +612,53 @@
 		}
 	}
 
-	// transform_poses_kernel's front -- one wave64 per instance, up to 8 instances per workgroup, images as consumer_wave_of lays them out,
-	// the skeleton's record on the scalar unit, the refusal in front of any load of a row, the row into the image by DMA, the walk schedule
-	// requested in front of it -- and then the matrix arithmetic: every wave rewrites its image as matrices (a bone per lane), with
+	// pose_matrices_kernel's rows: its clause of the refusal -- 64 bytes per bone on the output side -- and store_matrix_row
+	struct matrix_row_writer
+	{
+		uint8_t* matrices;
+		uint64_t matrix_stride_bytes;
+		__device__ __forceinline__ bool refuses(uint32_t, uint32_t num_bones) const { return uint64_t(num_bones) * 64u > matrix_stride_bytes; }
+		__device__ __forceinline__ void store(const f32x4* image, uint32_t num_bones, uint32_t instance, uint32_t lane) const
+		{
+			store_matrix_row(image, num_bones, matrices + uint64_t(instance) * matrix_stride_bytes, lane);
+		}
+	};
+
+	// The body of pose_matrices_kernel and skinning_matrices_kernel, which differ in their `writer` alone. transform_poses_kernel's front
+	// -- one wave64 per instance, up to 8 instances per workgroup, images as consumer_wave_of lays them out, open_instance in front of any
+	// load of a row, fill_image_from_row behind the request for the walk schedule -- over the rows at `rows`, and then the matrix
+	// arithmetic: every wave rewrites its image as matrices (a bone per lane), with
 	//   kObjectSpace   ONE wave of the workgroup (it rotates with the workgroup index) walks all its images with walk_hierarchy_matrices
 	//                  and then stores all of them, as finish_consumer_poses does for QVV rows; without it every wave stores its own.
+	//   writer         refuses(instance, num_bones): its clauses of the refusal, asked once per instance by the instance's own wave;
+	//                  store(image, num_bones, instance, lane): a finished image into its output row, num_bones 0 for an image without work
 	// Nothing is normalized, routed or counted. The output never overlaps the input (the host refuses it: records differ in size).
 	// Every wave of the workgroup reaches the __syncthreads: a wave without work (past the batch, refused, no bones) has num_bones 0.
-	template<bool kObjectSpace>
-	__global__ __launch_bounds__(k_consumer_max_instances * k_wave_size) void pose_matrices_kernel(pose_matrices_launch launch)
+	template<bool kObjectSpace, class row_writer_type>
+	__device__ __forceinline__ void matrices_of_pose_rows(pose_rows_head head, pose_rows_shape shape, const uint8_t* rows, uint64_t row_stride_bytes, row_writer_type writer)
 	{
 		extern __shared__ __attribute__((aligned(16))) uint8_t dynamic_lds[];
-		// packed_block_shape: log2 of the instances per workgroup (bits 0..7) | words of LDS reserved for the shared walk schedule (bits 8..31)
-		const uint32_t log2_instances_per_block = launch.packed_block_shape & 0xFFu;
+		const uint32_t log2_instances_per_block = shape.log2_instances_per_block();
 		__shared__ consumer_walk_slots walk;		// (what the host subtracts from the LDS it may ask for: host_consumers.inl)
 
-		const consumer_wave wave = consumer_wave_of(log2_instances_per_block, launch.lds_bytes_per_instance, launch.lds_quads_per_image);
+		const consumer_wave wave = consumer_wave_of(log2_instances_per_block, shape.lds_bytes_per_instance, shape.lds_quads_per_image);
 		const uint32_t lane = wave.lane, instance = wave.instance, slot = wave.slot;
 		uint32_t num_bones = 0;
 
-		if (instance < launch.num_instances)
+		if (instance < shape.num_instances)
 		{
-			// the skeleton's record on the scalar unit; record 0 is never handed out and a cleared record is an unknown or retired skeleton
-			const uint32_t skeleton_id = launch.instance_skeletons != nullptr ? as_constant(launch.instance_skeletons)[instance] : launch.skeleton;
-			const device_skeleton skeleton = load_skeleton_fields(launch.skeletons, skeleton_id < launch.num_skeletons ? skeleton_id : 0);
-			const uint32_t skeleton_bones = skeleton.num_bones;
-
-			// refused, wave uniform and in front of any load of a row: what transform_poses_kernel refuses, with 64 bytes per bone on the
-			// output side. What is served reads and writes inside its own rows.
-			const bool refused = skeleton_id >= launch.num_skeletons || skeleton.reference_pose == nullptr || (kObjectSpace && skeleton.hierarchy == nullptr)
-				|| uint64_t(skeleton_bones) * 48u > launch.local_pose_stride_bytes || uint64_t(skeleton_bones) * 64u > launch.matrix_stride_bytes
-				|| skeleton_bones * 3u > launch.lds_quads_per_image;
-			if (refused)
+			// open_instance's refusal, more bones than a pose row holds, and what the writer refuses
+			const opened_instance opened = open_instance<kObjectSpace>(head, shape, instance);
+			const bool writer_refuses = writer.refuses(instance, opened.num_bones);
+			if (opened.refused || uint64_t(opened.num_bones) * 48u > row_stride_bytes || writer_refuses)
+				count_refused(shape.rejected_count, lane);
+			else if (opened.num_bones != 0)
 			{
-				if (lane == 0)
-					atomicAdd(launch.rejected_count, 1ull);
-			}
-			else if (skeleton_bones != 0)
-			{
-				num_bones = skeleton_bones;
+				num_bones = opened.num_bones;
 				// the walk schedule first: its words travel global -> LDS while the row does
 				if (kObjectSpace)
-					request_walk_schedule(skeleton.hierarchy, log2_instances_per_block, launch.packed_block_shape >> 8, wave.shared_schedule, slot, lane, walk);
-				// the row straight into the image by DMA, lanes <-> consecutive quads (the LDS side of a piece is wave uniform + lane * 16)
-				const f32x4* source = reinterpret_cast<const f32x4*>(launch.local_poses + uint64_t(instance) * launch.local_pose_stride_bytes);
-				const uint32_t num_quads = num_bones * 3u;
-				for (uint32_t base = 0; base < num_quads; base += k_wave_size)
-				{
-					if (base + lane < num_quads)
-						__builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(source + base + lane),
-							(__attribute__((address_space(3))) void*)(wave.image + base), 16, 0, 0);
-				}
+					request_walk_schedule(opened.skeleton.hierarchy, log2_instances_per_block, shape.schedule_words(), wave.shared_schedule, slot, lane, walk);
+				fill_image_from_row(wave.image, rows + uint64_t(instance) * row_stride_bytes, num_bones * 3u, lane);
 			}
 		}
 		wave_lds_barrier();		// the wave's row is complete (vmcnt)
@@ -654,30 +668,31 @@
 		{
 			if (lane == 0)
 			{
-				// (a slot with work has its steps and its schedule already: request_walk_schedule)
-				if (num_bones == 0)
-				{
-					walk.levels[slot] = 0;
-					walk.schedules[slot] = nullptr;
-				}
+				close_idle_walk_slot(walk, slot, num_bones);
 				walk.tracks[slot] = num_bones;
 			}
 			__syncthreads();
-			// ONE wave walks and then stores the workgroup's matrices; the others are done (finish_consumer_poses says why, and why it rotates)
+			// ONE wave walks and then stores the workgroup's rows; the others are done (finish_consumer_poses says why, and why it rotates)
 			if (wave.wave_in_block != (blockIdx.x & ((blockDim.x / k_wave_size) - 1u)))
 				return;
-			walk_workgroup_matrices(walk, wave.shared_schedule, log2_instances_per_block, launch.lds_bytes_per_instance, 0, lane);
+			walk_workgroup_matrices(walk, wave.shared_schedule, log2_instances_per_block, shape.lds_bytes_per_instance, 0, lane);
 			wave_lds_barrier();
 			const uint32_t instances_per_block = 1u << log2_instances_per_block;
 			for (uint32_t store_slot = 0; store_slot < instances_per_block; ++store_slot)
-				store_matrix_row(reinterpret_cast<const f32x4*>(dynamic_lds + size_t(store_slot) * launch.lds_bytes_per_instance), walk.tracks[store_slot],
-					launch.matrices + uint64_t((blockIdx.x << log2_instances_per_block) + store_slot) * launch.matrix_stride_bytes, lane);
+				writer.store(reinterpret_cast<const f32x4*>(dynamic_lds + size_t(store_slot) * shape.lds_bytes_per_instance), walk.tracks[store_slot],
+					(blockIdx.x << log2_instances_per_block) + store_slot, lane);
 		}
 		else
 		{
 			wave_lds_barrier();		// every bone has its matrix
-			store_matrix_row(wave.image, num_bones, launch.matrices + uint64_t(instance) * launch.matrix_stride_bytes, lane);
+			writer.store(wave.image, num_bones, instance, lane);
 		}
+	}
+
+	template<bool kObjectSpace>
+	__global__ __launch_bounds__(k_consumer_max_instances * k_wave_size) void pose_matrices_kernel(pose_matrices_launch launch)
+	{
+		matrices_of_pose_rows<kObjectSpace>(launch.head, launch.shape, launch.local_poses, launch.local_pose_stride_bytes, matrix_row_writer{ launch.matrices, launch.matrix_stride_bytes });
 	}
 
 	// ---- skinning matrix palettes of caller pose buffers (aclhip_skinning_matrices_batch; include/aclhip.h states the definition) ---------
@@ -714,10 +729,7 @@
 	// the kernel's argument: pose_matrices_launch with the context's skin table and the launch's skins
 	struct skinning_matrices_launch
 	{
-		const device_skeleton* skeletons;		// the context's skeleton table
-		uint32_t num_skeletons;					// its capacity
-		uint32_t skeleton;						// the launch's skeleton, when instance_skeletons is null
-		const uint32_t* instance_skeletons;		// [num_instances] or null
+		pose_rows_head head;
 		const device_skin* skins;				// the context's skin table
 		uint32_t num_skins;						// its capacity
 		uint32_t skin;							// the launch's skin, when instance_skins is null
@@ -726,9 +738,7 @@
 		uint64_t pose_stride_bytes;
 		uint8_t* palettes;						// row i at palettes + i * palette_stride_bytes: 64 or 48 bytes per joint
 		uint64_t palette_stride_bytes;
-		uint32_t num_instances;
-		uint32_t lds_quads_per_image, lds_bytes_per_instance, packed_block_shape;		// as transform_poses_kernel takes them
-		unsigned long long* rejected_count;
+		pose_rows_shape shape;
 	};
 
 	// A finished image of object matrices into its palette row: S[j] = matrix_mul(IB[j], O[k[j]]), lanes <-> consecutive OUTPUT quads as in
@@ -775,123 +785,65 @@
 		}
 	}
 
-	// pose_matrices_kernel with a palette for its store: the same front -- one wave64 per instance, images as consumer_wave_of lays them
-	// out, the skeleton's record and now the skin's on the scalar unit, the refusal in front of any load of a row, the row into the image by
-	// DMA behind the request for the walk schedule --, convert_image_to_matrices, with kObjectSpace the walk of the workgroup's images by
-	// the one rotating wave, and then store_palette_row in the place of store_matrix_row. The object matrices never leave LDS.
-	// With kObjectSpace the walking wave stores every image of the workgroup: it reads the skin of each slot that has work again on the
-	// scalar unit (a slot's work is walk.tracks; a retirement clears a record behind the launches enqueued before it, never inside one).
-	// Every wave of the workgroup reaches the __syncthreads: a wave without work (past the batch, refused, no bones) has num_bones 0.
+	// skinning_matrices_kernel's rows, and everything about the skin: the skin's record next to the skeleton's on the scalar unit, its
+	// clauses of the refusal -- a skin that is unknown, retired (record 0 is never handed out, a cleared record has no inverse_bind) or made
+	// for another bone count, more joints than a palette row holds; every joint's bone of what is served (< skin.num_bones at
+	// registration) lies inside the image -- and store_palette_row.
+	//   kObjectSpace   the walking wave stores every image of the workgroup: it reads the skin of each slot that has work again on the
+	//                  scalar unit (a retirement clears a record behind the launches enqueued before it, never inside one); without it a
+	//                  wave stores its own image with the record `refuses` read
+	template<uint32_t kLayout, bool kObjectSpace>
+	struct palette_row_writer
+	{
+		const device_skin* skins;
+		uint32_t num_skins, skin;
+		const uint32_t* instance_skins;
+		uint8_t* palettes;
+		uint64_t palette_stride_bytes;
+		device_skin own_skin = {};		// of the wave's own instance: from refuses to the local space store
+		static constexpr uint32_t record_bytes = kLayout == k_palette_3x4f_transposed_48 ? 48u : 64u;
+
+		__device__ __forceinline__ uint32_t skin_of(uint32_t instance) const { return instance_skins != nullptr ? as_constant(instance_skins)[instance] : skin; }
+		__device__ __forceinline__ bool refuses(uint32_t instance, uint32_t num_bones)
+		{
+			const uint32_t skin_id = skin_of(instance);
+			own_skin = load_skin_fields(skins, skin_id < num_skins ? skin_id : 0);
+			return skin_id >= num_skins || own_skin.inverse_bind == nullptr || own_skin.num_bones != num_bones || uint64_t(own_skin.num_joints) * record_bytes > palette_stride_bytes;
+		}
+		__device__ __forceinline__ void store(const f32x4* image, uint32_t num_bones, uint32_t instance, uint32_t lane) const
+		{
+			uint8_t* row = palettes + uint64_t(instance) * palette_stride_bytes;
+			if constexpr (kObjectSpace)
+			{
+				// (wave uniform: every lane reads the same word)
+				if (__builtin_amdgcn_readfirstlane(num_bones) == 0)
+					return;
+				// the slot was served: its handle is a live skin's, checked by the slot's own wave
+				const device_skin served = load_skin_fields(skins, skin_of(instance));
+				store_palette_row<kLayout>(image, served.joint_bones, served.inverse_bind, served.num_joints, row, lane);
+			}
+			else
+				store_palette_row<kLayout>(image, own_skin.joint_bones, own_skin.inverse_bind, num_bones != 0 ? own_skin.num_joints : 0u, row, lane);
+		}
+	};
+
+	// pose_matrices_kernel with a palette for its store: matrices_of_pose_rows with store_palette_row in the place of store_matrix_row.
+	// The object matrices never leave LDS.
 	template<bool kObjectSpace, uint32_t kLayout>
 	__global__ __launch_bounds__(k_consumer_max_instances * k_wave_size) void skinning_matrices_kernel(skinning_matrices_launch launch)
 	{
-		extern __shared__ __attribute__((aligned(16))) uint8_t dynamic_lds[];
-		// packed_block_shape: log2 of the instances per workgroup (bits 0..7) | words of LDS reserved for the shared walk schedule (bits 8..31)
-		const uint32_t log2_instances_per_block = launch.packed_block_shape & 0xFFu;
-		__shared__ consumer_walk_slots walk;		// (what the host subtracts from the LDS it may ask for: host_consumers.inl)
-		constexpr uint32_t record_bytes = kLayout == k_palette_3x4f_transposed_48 ? 48u : 64u;
-
-		const consumer_wave wave = consumer_wave_of(log2_instances_per_block, launch.lds_bytes_per_instance, launch.lds_quads_per_image);
-		const uint32_t lane = wave.lane, instance = wave.instance, slot = wave.slot;
-		uint32_t num_bones = 0;
-		[[maybe_unused]] uint32_t num_joints = 0;
-		[[maybe_unused]] const uint32_t* joint_bones = nullptr;
-		[[maybe_unused]] const f32x4* inverse_bind = nullptr;
-
-		if (instance < launch.num_instances)
-		{
-			// the skeleton's and the skin's record on the scalar unit; record 0 is never handed out and a cleared record is an unknown or retired handle
-			const uint32_t skeleton_id = launch.instance_skeletons != nullptr ? as_constant(launch.instance_skeletons)[instance] : launch.skeleton;
-			const uint32_t skin_id = launch.instance_skins != nullptr ? as_constant(launch.instance_skins)[instance] : launch.skin;
-			const device_skeleton skeleton = load_skeleton_fields(launch.skeletons, skeleton_id < launch.num_skeletons ? skeleton_id : 0);
-			const device_skin skin = load_skin_fields(launch.skins, skin_id < launch.num_skins ? skin_id : 0);
-			const uint32_t skeleton_bones = skeleton.num_bones;
-
-			// refused, wave uniform and in front of any load of a row: what pose_matrices_kernel refuses, with the skin's records on the output
-			// side, and a skin that is unknown or was made for another bone count. What is served reads and writes inside its own rows, and
-			// every joint's bone (< skin.num_bones at registration) lies inside the image.
-			const bool refused = skeleton_id >= launch.num_skeletons || skeleton.reference_pose == nullptr || (kObjectSpace && skeleton.hierarchy == nullptr)
-				|| skin_id >= launch.num_skins || skin.inverse_bind == nullptr || skin.num_bones != skeleton_bones
-				|| uint64_t(skeleton_bones) * 48u > launch.pose_stride_bytes || uint64_t(skin.num_joints) * record_bytes > launch.palette_stride_bytes
-				|| skeleton_bones * 3u > launch.lds_quads_per_image;
-			if (refused)
-			{
-				if (lane == 0)
-					atomicAdd(launch.rejected_count, 1ull);
-			}
-			else if (skeleton_bones != 0)
-			{
-				num_bones = skeleton_bones;
-				num_joints = skin.num_joints;
-				joint_bones = skin.joint_bones;
-				inverse_bind = skin.inverse_bind;
-				// the walk schedule first: its words travel global -> LDS while the row does
-				if (kObjectSpace)
-					request_walk_schedule(skeleton.hierarchy, log2_instances_per_block, launch.packed_block_shape >> 8, wave.shared_schedule, slot, lane, walk);
-				// the row straight into the image by DMA, lanes <-> consecutive quads (the LDS side of a piece is wave uniform + lane * 16)
-				const f32x4* source = reinterpret_cast<const f32x4*>(launch.poses + uint64_t(instance) * launch.pose_stride_bytes);
-				const uint32_t num_quads = num_bones * 3u;
-				for (uint32_t base = 0; base < num_quads; base += k_wave_size)
-				{
-					if (base + lane < num_quads)
-						__builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(source + base + lane),
-							(__attribute__((address_space(3))) void*)(wave.image + base), 16, 0, 0);
-				}
-			}
-		}
-		wave_lds_barrier();		// the wave's row is complete (vmcnt)
-		convert_image_to_matrices(wave.image, num_bones, lane);
-
-		if constexpr (kObjectSpace)
-		{
-			if (lane == 0)
-			{
-				// (a slot with work has its steps and its schedule already: request_walk_schedule)
-				if (num_bones == 0)
-				{
-					walk.levels[slot] = 0;
-					walk.schedules[slot] = nullptr;
-				}
-				walk.tracks[slot] = num_bones;
-			}
-			__syncthreads();
-			// ONE wave walks and then stores the workgroup's palettes; the others are done (finish_consumer_poses says why, and why it rotates)
-			if (wave.wave_in_block != (blockIdx.x & ((blockDim.x / k_wave_size) - 1u)))
-				return;
-			walk_workgroup_matrices(walk, wave.shared_schedule, log2_instances_per_block, launch.lds_bytes_per_instance, 0, lane);
-			wave_lds_barrier();
-			const uint32_t instances_per_block = 1u << log2_instances_per_block;
-			for (uint32_t store_slot = 0; store_slot < instances_per_block; ++store_slot)
-			{
-				// (wave uniform: every lane reads the same word)
-				if (__builtin_amdgcn_readfirstlane(walk.tracks[store_slot]) == 0)
-					continue;
-				// the slot was served: its handle is a live skin's, checked by the slot's own wave
-				const uint32_t store_instance = (blockIdx.x << log2_instances_per_block) + store_slot;
-				const uint32_t skin_id = launch.instance_skins != nullptr ? as_constant(launch.instance_skins)[store_instance] : launch.skin;
-				const device_skin skin = load_skin_fields(launch.skins, skin_id);
-				store_palette_row<kLayout>(reinterpret_cast<const f32x4*>(dynamic_lds + size_t(store_slot) * launch.lds_bytes_per_instance), skin.joint_bones, skin.inverse_bind,
-					skin.num_joints, launch.palettes + uint64_t(store_instance) * launch.palette_stride_bytes, lane);
-			}
-		}
-		else
-		{
-			wave_lds_barrier();		// every bone has its matrix
-			store_palette_row<kLayout>(wave.image, joint_bones, inverse_bind, num_joints, launch.palettes + uint64_t(instance) * launch.palette_stride_bytes, lane);
-		}
+		matrices_of_pose_rows<kObjectSpace>(launch.head, launch.shape, launch.poses, launch.pose_stride_bytes,
+			palette_row_writer<kLayout, kObjectSpace>{ launch.skins, launch.num_skins, launch.skin, launch.instance_skins, launch.palettes, launch.palette_stride_bytes });
 	}
 
 	// ---- how far two pose buffers are apart (aclhip_measure_pose_error_batch; include/aclhip.h states the definition) --------------------
 	struct pose_error_record { float error; uint32_t bone; };		// aclhip_pose_error
 	constexpr uint32_t k_no_bone = 0xFFFFFFFFu;						// ACLHIP_NO_BONE
 
-	// the kernel's argument: the launch's buffers, its skeletons, its shells, its outputs and its shape
+	// the kernel's argument: the launch's buffers, its shells and its outputs between the two shared ends (two images per instance)
 	struct pose_error_launch
 	{
-		const device_skeleton* skeletons;		// the context's skeleton table
-		uint32_t num_skeletons;					// its capacity
-		uint32_t skeleton;						// the launch's skeleton, when instance_skeletons is null
-		const uint32_t* instance_skeletons;		// [num_instances] or null
+		pose_rows_head head;
 		const uint8_t* raw_poses;				// row i at raw_poses + i * raw_pose_stride_bytes
 		uint64_t raw_pose_stride_bytes;
 		const uint8_t* lossy_poses;				// row i at lossy_poses + i * lossy_pose_stride_bytes
@@ -904,10 +856,8 @@
 		uint8_t* bone_errors;					// null, or the error of bone b of instance i at bone_errors + i * bone_error_stride_bytes + 4 * b
 		uint64_t bone_error_stride_bytes;
 		pose_error_record* errors;				// [num_instances]
-		uint32_t num_instances;
 		uint32_t additive_format;
-		uint32_t lds_quads_per_image, lds_bytes_per_instance, packed_block_shape;		// as transform_poses_kernel takes them, two images per instance
-		unsigned long long* rejected_count;
+		pose_rows_shape shape;
 	};
 
 	// rtm::qvv_mul_point3: quat_mul_vector3(scale * point, rotation) + translation, all three components of the product multiplied
@@ -972,8 +922,8 @@
 	}
 
 	// transform_poses_kernel's front twice over: TWO waves per instance as consumer_wave_of lays them out -- role 0 holds the raw row in the
-	// slot's image, role 1 the lossy row in its base image --, the skeleton's record on the scalar unit, the refusal in front of any load of
-	// a row, each row into its image by DMA. Then what finish_consumer_poses does to one image is done to both, without a store:
+	// slot's image, role 1 the lossy row in its base image --, open_instance in front of any load of a row, each row into its image by
+	// fill_image_from_row. Then what finish_consumer_poses does to one image is done to both, without a store:
 	//   kBase          apply_additive_to_base against the base row in HBM, each wave over its own image (the counter moves as for two launches)
 	//   kObjectSpace   walk_hierarchy as it is, by the two waves of ONE slot (it rotates with the workgroup index): role 0 walks every raw
 	//                  image of the workgroup, role 1 every lossy one, lanes <-> (slot, transform of the step) over the schedule made for
@@ -991,38 +941,35 @@
 	{
 		static_assert(!(kMatrices && kBase), "the matrix metric takes no additive base");
 		extern __shared__ __attribute__((aligned(16))) uint8_t dynamic_lds[];
-		// packed_block_shape: log2 of the instances per workgroup (bits 0..7) | words of LDS reserved for the shared walk schedule (bits 8..31)
-		const uint32_t log2_instances_per_block = launch.packed_block_shape & 0xFFu;
+		const pose_rows_shape shape = launch.shape;
+		const uint32_t log2_instances_per_block = shape.log2_instances_per_block();
 		__shared__ consumer_walk_slots walk;		// (what the host subtracts from the LDS it may ask for: host_consumers.inl)
 		__shared__ pose_error_record second_wave_record[k_consumer_max_instances];
 
-		const consumer_wave wave = consumer_wave_of(log2_instances_per_block, launch.lds_bytes_per_instance, launch.lds_quads_per_image);
+		const consumer_wave wave = consumer_wave_of(log2_instances_per_block, shape.lds_bytes_per_instance, shape.lds_quads_per_image);
 		const uint32_t lane = wave.lane, instance = wave.instance, role = wave.role, slot = wave.slot;
 		f32x4* const own_image = role == 0 ? wave.image : wave.base_image;
 		uint32_t num_bones = 0;
 
-		if (instance < launch.num_instances)
+		if (instance < shape.num_instances)
 		{
-			// the skeleton's record on the scalar unit; record 0 is never handed out and a cleared record is an unknown or retired skeleton
-			const uint32_t skeleton_id = launch.instance_skeletons != nullptr ? as_constant(launch.instance_skeletons)[instance] : launch.skeleton;
-			const device_skeleton skeleton = load_skeleton_fields(launch.skeletons, skeleton_id < launch.num_skeletons ? skeleton_id : 0);
-			const uint32_t skeleton_bones = skeleton.num_bones;
+			// open_instance's refusal, over the strides of this launch, and a bone without a place in the error row or in the shell table.
+			// Both waves of the instance decide alike.
+			const opened_instance opened = open_instance<kObjectSpace>(launch.head, shape, instance);
+			const uint32_t skeleton_bones = opened.num_bones;
 			const uint64_t row_bytes = uint64_t(skeleton_bones) * 48u;
-
-			// refused, wave uniform and in front of any load of a row: what transform_poses_kernel refuses, over the strides of this launch,
-			// and a bone without a place in the error row or in the shell table. Both waves of the instance decide alike.
-			const bool refused = skeleton_id >= launch.num_skeletons || skeleton.reference_pose == nullptr || (kObjectSpace && skeleton.hierarchy == nullptr)
-				|| row_bytes > launch.raw_pose_stride_bytes || row_bytes > launch.lossy_pose_stride_bytes || (kBase && row_bytes > launch.base_pose_stride_bytes)
-				|| (launch.bone_errors != nullptr && uint64_t(skeleton_bones) * 4u > launch.bone_error_stride_bytes)
-				|| (launch.shell_distances != nullptr && skeleton_bones > launch.num_shell_distances) || skeleton_bones * 3u > launch.lds_quads_per_image;
+			const bool refused = opened.refused || row_bytes > launch.raw_pose_stride_bytes || row_bytes > launch.lossy_pose_stride_bytes
+				|| (kBase && row_bytes > launch.base_pose_stride_bytes) || (launch.bone_errors != nullptr && uint64_t(skeleton_bones) * 4u > launch.bone_error_stride_bytes)
+				|| (launch.shell_distances != nullptr && skeleton_bones > launch.num_shell_distances);
 			if (refused || skeleton_bones == 0)
 			{
 				// "not measured" (refused) and the reference's invalid_track_error (no bones) are the same record
-				if (role == 0 && lane == 0)
+				if (role == 0)
 				{
 					if (refused)
-						atomicAdd(launch.rejected_count, 1ull);
-					launch.errors[instance] = pose_error_record{ -1.0f, k_no_bone };
+						count_refused(shape.rejected_count, lane);
+					if (lane == 0)
+						launch.errors[instance] = pose_error_record{ -1.0f, k_no_bone };
 				}
 			}
 			else
@@ -1030,23 +977,14 @@
 				num_bones = skeleton_bones;
 				// the walk schedule first: its words travel global -> LDS while the rows do
 				if (kObjectSpace && role == 0)
-					request_walk_schedule(skeleton.hierarchy, log2_instances_per_block, launch.packed_block_shape >> 8, wave.shared_schedule, slot, lane, walk);
-				// the wave's row straight into its image by DMA, lanes <-> consecutive quads (the LDS side of a piece is wave uniform + lane * 16)
-				const uint8_t* row = role == 0 ? launch.raw_poses + uint64_t(instance) * launch.raw_pose_stride_bytes
-					: launch.lossy_poses + uint64_t(instance) * launch.lossy_pose_stride_bytes;
-				const f32x4* source = reinterpret_cast<const f32x4*>(row);
-				const uint32_t num_quads = num_bones * 3u;
-				for (uint32_t base = 0; base < num_quads; base += k_wave_size)
-				{
-					if (base + lane < num_quads)
-						__builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(source + base + lane),
-							(__attribute__((address_space(3))) void*)(own_image + base), 16, 0, 0);
-				}
+					request_walk_schedule(opened.skeleton.hierarchy, log2_instances_per_block, shape.schedule_words(), wave.shared_schedule, slot, lane, walk);
+				fill_image_from_row(own_image, role == 0 ? launch.raw_poses + uint64_t(instance) * launch.raw_pose_stride_bytes
+					: launch.lossy_poses + uint64_t(instance) * launch.lossy_pose_stride_bytes, num_bones * 3u, lane);
 			}
 		}
 		wave_lds_barrier();		// the wave's row is complete (vmcnt)
 
-		[[maybe_unused]] unsigned long long* const negative_scale_count = launch.rejected_count + 1;
+		[[maybe_unused]] unsigned long long* const negative_scale_count = shape.rejected_count + 1;
 		if constexpr (kMatrices)
 			convert_image_to_matrices(own_image, num_bones, lane);
 		if constexpr (kBase)
@@ -1068,25 +1006,18 @@
 		if constexpr (kObjectSpace)
 		{
 			if (lane == 0 && role == 0)
-			{
-				// (a slot with work has its steps and its schedule already: request_walk_schedule)
-				if (num_bones == 0)
-				{
-					walk.levels[slot] = 0;
-					walk.schedules[slot] = nullptr;
-				}
-			}
+				close_idle_walk_slot(walk, slot, num_bones);
 			__syncthreads();
 			// the two waves of one slot walk, the others wait at the barrier below
 			if (slot == (blockIdx.x & ((1u << log2_instances_per_block) - 1u)))
 			{
 				if constexpr (kMatrices)
-					walk_workgroup_matrices(walk, wave.shared_schedule, log2_instances_per_block, launch.lds_bytes_per_instance, role * launch.lds_quads_per_image, lane);
+					walk_workgroup_matrices(walk, wave.shared_schedule, log2_instances_per_block, shape.lds_bytes_per_instance, role * shape.lds_quads_per_image, lane);
 				else
 				{
 					const uint32_t walk_slot = lane & ((1u << log2_instances_per_block) - 1u);
 					const uint32_t first = lane >> log2_instances_per_block;
-					f32x4* slot_image = reinterpret_cast<f32x4*>(dynamic_lds + size_t(walk_slot) * launch.lds_bytes_per_instance) + size_t(role) * launch.lds_quads_per_image;
+					f32x4* slot_image = reinterpret_cast<f32x4*>(dynamic_lds + size_t(walk_slot) * shape.lds_bytes_per_instance) + size_t(role) * shape.lds_quads_per_image;
 					const uint32_t slot_steps = walk.levels[walk_slot] & 0x7FFFFFFFu;
 					const bool slot_schedule_is_shared = (walk.levels[walk_slot] & 0x80000000u) == 0;
 					const uint32_t* slot_schedule = walk.schedules[walk_slot];
